@@ -2,13 +2,18 @@
 """Headline benchmark: images/sec of the 4-step LCM `enhance` loop, variant small, 256x256, fp16,
 batch 32 per GPU (BASELINE.json configs[1]), synthetic inputs and random-init weights.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A "step" is one `LowLightDiffusion.enhance(x, 4)` call on this rank's batch (4 UNet forwards + 4
 scheduler steps), inputs already resident in HBM.  For N > 1 the driver launches one process per GPU
 with torch.distributed.run; ranks hold independent batch shards (weak scaling) and the outputs are
 collected with a single RCCL all_gather inside the timed region.  Rank 0 prints one
 JSON line.
+
+--dump-outputs DIR: rank 0 writes what the last timed step returned as DIR/<name>.npy (float32) after the
+timed region -- `enhanced` (the gathered batch for N > 1), or with --train `loss` and `params` (the parameters
+after the step).  At most DUMP_BYTES in all; a larger array is replaced by a fixed, seeded sample of its
+flattened entries.  Weights, inputs and device noise are seeded, so equal arguments give equal inputs.
 """
 from __future__ import annotations
 
@@ -27,10 +32,30 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy rate
+DUMP_BYTES = 64 << 20  # --dump-outputs: total size of the written arrays
 
 
 def log(msg: str) -> None:
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+def dump_outputs(outdir: str, arrays: dict, seed: int = 20240613) -> None:
+    """Writes each tensor of `arrays` as outdir/<name>.npy in float32.  The budget DUMP_BYTES is shared in proportion
+    to the arrays' sizes; an array over its share is written as a sample of its flattened entries at sorted indices
+    drawn from a generator seeded with `seed` (the same indices for the same shape on every run)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    total = sum(4 * t.numel() for t in arrays.values())
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        share = max(1, int(a.size * min(1.0, DUMP_BYTES / total)))
+        note = ""
+        if share < a.size:
+            idx = np.unique(np.random.default_rng(seed).integers(0, a.size, share, dtype=np.int64))
+            a = a.reshape(-1)[idx]
+            note = f" (seeded sample of {t.numel()} entries)"
+        np.save(os.path.join(outdir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+        log(f"dumped {name}: {tuple(a.shape)}{note} -> {outdir}")
 
 
 def host_cores() -> int:
@@ -243,6 +268,8 @@ def train_bench(args, M, dev, rank: int, world: int) -> None:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"loss": loss.reshape(1), "params": torch.cat([p.detach().reshape(-1) for p in params])})
         native = importlib.import_module("cv-diffusion-model_amd._native")
         extra = {}
         if not args.no_roofline:
@@ -289,7 +316,11 @@ def main() -> None:
     ap.add_argument("--train", action="store_true",
                     help="time the training step instead (BASELINE config 5; not the headline line): compute_loss -> "
                          "backward -> gradient all-reduce -> clip -> AdamW -> EMA, as src/training/trainer.py:281-338")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32, <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -365,7 +396,7 @@ def main() -> None:
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
     drain()
     if world > 1:
         dist.barrier()
@@ -379,6 +410,9 @@ def main() -> None:
     images = world * B * args.steps
     value = images / elapsed
     log(f"timed region done: {elapsed:.3f} s for {args.steps} steps")
+    if rank == 0 and args.dump_outputs:
+        # the last step's result as its caller receives it: with N > 1, the gathered batch of every rank
+        dump_outputs(args.dump_outputs, {"enhanced": gather_bufs[(nstep[0] - 1) & 1] if world > 1 else out})
     breakdown, dom_prof = None, None
     if prof:
         # (rank 0 only: these passes call the model directly -- no collective, the other ranks are not here)

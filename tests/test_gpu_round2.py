@@ -490,14 +490,18 @@ def _bench(args, world):
     return json.loads(lines[0])
 
 
-def test_bench_two_ranks_inference():
+def test_bench_two_ranks_inference(tmp_path):
     """bench.py as the driver launches it for N > 1 (torch.distributed.run, one rank per process, barrier + max over ranks,
     async all_gather of the outputs), rehearsed with both ranks on this box's one GPU over gloo."""
-    line = _bench(["--steps", "2", "--warmup", "1", "--batch", "4", "--no-cpu-baseline"], 2)
+    line = _bench(["--steps", "2", "--warmup", "1", "--batch", "4", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], 2)
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 8 and line["scaling"] == "weak"
     assert line["value"] > 0 and line["steps"] == 2 and line["unit"] == "images/sec"
     assert abs(line["value"] - 8 * 2 / (line["ms_per_step"] * 2e-3)) / line["value"] < 1e-2
     assert line["roofline"]["frac"] > 0 and line["roofline"]["whole_path"]["frac"] > 0
+    # --dump-outputs: the gathered batch of the last timed step, both ranks' shards
+    enh = np.load(tmp_path / "enhanced.npy")
+    assert enh.dtype == np.float32 and enh.shape == (8, 3, 256, 256)
+    assert np.isfinite(enh).all() and np.abs(enh).max() <= 1.0 and not np.array_equal(enh[:4], enh[4:])
 
 
 def test_bench_two_ranks_training():

@@ -392,6 +392,28 @@ def test_bench_kernel_class_mapping():
     assert b.pmc_lookup(table, "expand_dw_kernel<_Float16, 4, 0>") is None
 
 
+def test_bench_dump_outputs_budget_and_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy files, whole arrays while they fit, a seeded sample (the same on every run)
+    of an array over its share of the budget, never more than DUMP_BYTES in all."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    small = torch.arange(12, dtype=torch.float64).reshape(3, 4)
+    b.dump_outputs(str(tmp_path / "a"), {"enhanced": small})
+    got = np.load(tmp_path / "a" / "enhanced.npy")
+    assert got.dtype == np.float32 and got.shape == (3, 4) and np.array_equal(got, small.numpy())
+    monkeypatch.setattr(b, "DUMP_BYTES", 4096)
+    big = torch.randn(10000)
+    for d in ("b", "c"):
+        b.dump_outputs(str(tmp_path / d), {"loss": torch.ones(1), "params": big})
+    files = sorted((tmp_path / "b").iterdir())
+    assert [f.name for f in files] == ["loss.npy", "params.npy"] and sum(np.load(f).nbytes for f in files) <= 4096
+    p = np.load(tmp_path / "b" / "params.npy")
+    assert 0 < p.size < big.numel() and np.isin(p, big.numpy()).all()
+    assert np.array_equal(p, np.load(tmp_path / "c" / "params.npy"))
+
+
 def test_custom_op_registry_slots():
     """`register_model` hands out stable small integers (or the caller's `key`), not `id(model)`: an exported graph that
     bakes the integer in can be re-bound in another process."""
