@@ -10,16 +10,18 @@ namespace llie {
 
 // =============================================================================================
 // (1) dz = g * act'(x*as + ab); slab[b][tile][0][c] = sum dz, [1] = sum dz*x over tiles of 64 rows.
-// Block = 64 rows x 64 channels.
-template <typename T>
+// Block = 64 rows x 64 channels.  RAGGED (P % 64 != 0: image sizes that are not a multiple of 64): ceil(P / 64) tiles per
+// image, the last one partly empty -- rows past the image are neither read nor counted.
+template <typename T, bool RAGGED = false>
 __global__ void __launch_bounds__(256) bwd_mask_reduce_kernel(const BwdMaskArgs a) {
   constexpr int VEC = Elem<T>::VEC, CB = 64, VPR = CB / VEC, RL = 256 / VPR;
   __shared__ float red[RL][2][CB];
   const int tid = threadIdx.x, cv = tid % VPR, rl = tid / VPR;
   const int c = blockIdx.y * CB + cv * VEC;
-  const size_t m0 = (size_t)blockIdx.x * 64;
-  const int ntiles = a.P / 64;
+  const int ntiles = RAGGED ? (a.P + 63) / 64 : a.P / 64;
   const int b = (int)(blockIdx.x / (unsigned)ntiles), tile = (int)(blockIdx.x - (unsigned)b * ntiles);
+  const size_t m0 = RAGGED ? (size_t)b * a.P + (size_t)tile * 64 : (size_t)blockIdx.x * 64;
+  const int nrows = RAGGED ? min(64, a.P - tile * 64) : 64;
   float s1[VEC], s2[VEC];
 #pragma unroll
   for (int e = 0; e < VEC; ++e) s1[e] = s2[e] = 0.f;
@@ -38,7 +40,7 @@ __global__ void __launch_bounds__(256) bwd_mask_reduce_kernel(const BwdMaskArgs 
     }
     const T* gp = reinterpret_cast<const T*>(a.g);
     T* dzp = reinterpret_cast<T*>(a.dz);
-    for (int r = rl; r < 64; r += RL) {
+    for (int r = rl; r < nrows; r += RL) {
       const size_t m = m0 + r;
       float g[VEC], x[VEC], dz[VEC];
       ld_f32<T>(gp + m * a.C + c, g);
@@ -80,7 +82,17 @@ __global__ void __launch_bounds__(256) bwd_mask_reduce_kernel(const BwdMaskArgs 
   }
 }
 hipError_t launch_bwd_mask_reduce(int dtype, const BwdMaskArgs& a, hipStream_t s) {
-  if (a.P % 64 || a.M % a.P || a.C % 32 || (a.x0 && a.c0 + a.c1 != a.C)) return hipErrorInvalidValue;
+  if (a.P < 1 || a.M % a.P || a.C % 32 || (a.x0 && a.c0 + a.c1 != a.C)) return hipErrorInvalidValue;
+  if (a.P % 64) {  // slab of ceil(P / 64) tiles per image
+    dim3 grid((a.M / a.P) * ((a.P + 63) / 64), (a.C + 63) / 64);
+    switch (dtype) {
+      case 0: hipLaunchKernelGGL((bwd_mask_reduce_kernel<float, true>), grid, dim3(256), 0, s, a); break;
+      case 1: hipLaunchKernelGGL((bwd_mask_reduce_kernel<half_t, true>), grid, dim3(256), 0, s, a); break;
+      case 2: hipLaunchKernelGGL((bwd_mask_reduce_kernel<bf16_t, true>), grid, dim3(256), 0, s, a); break;
+      default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  }
   dim3 grid(a.M / 64, (a.C + 63) / 64);
   switch (dtype) {
     case 0: hipLaunchKernelGGL(bwd_mask_reduce_kernel<float>, grid, dim3(256), 0, s, a); break;
@@ -333,19 +345,22 @@ __global__ void __launch_bounds__(256) partial_groups_kernel(float* partial, int
 // over the strip's pixels through LDS at the end (fixed order).
 constexpr int kDwgTY = 32;
 static int dwg_tx(int W) { return (W % 32 == 0) ? 32 : ((W % 16 == 0) ? 16 : 8); }
-int dw_wgrad_strips(int H, int W) { return (W / dwg_tx(W)) * ((H + kDwgTY - 1) / kDwgTY); }
+int dw_wgrad_strips(int H, int W) { return ((W + dwg_tx(W) - 1) / dwg_tx(W)) * ((H + kDwgTY - 1) / kDwgTY); }
 
-template <typename T, int TX>
+// RAGGED (W % 8 != 0: maps of image sizes that are not a multiple of 64; TX = 8): the last strip of a row is partly empty --
+// its columns past the image read zero dh2 and zero activations (the conv's padding) and add nothing.
+template <typename T, int TX, bool RAGGED = false>
 __global__ void __launch_bounds__(8 * TX, 3) dw_wgrad_kernel(const DwWgradArgs a) {  // 3 waves per SIMD: 170 VGPRs (the unconstrained allocation lands 4 above)
   constexpr int VEC = Elem<T>::VEC, CC = 8 * VEC, PW = TX + 2;
   typedef typename Elem<T>::vec_t vec_t;
   __shared__ vec_t ring[2][PW * 8];
   __shared__ float red[TX][CC];
   const int tid = threadIdx.x, cl = tid & 7, xl = tid >> 3;
-  const int tiles_x = a.W / TX;
+  const int tiles_x = RAGGED ? (a.W + TX - 1) / TX : a.W / TX;
   const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x;
   const int x0 = tx * TX, y0 = ty * kDwgTY, TY = min(kDwgTY, a.H - y0);
   const int c0 = blockIdx.y * CC + cl * VEC, b = blockIdx.z;
+  const bool col_ok = RAGGED ? x0 + xl < a.W : true;
   const bool is_halo = tid < 16;
   const int hx = tid < 8 ? x0 - 1 : x0 + TX;
   const bool hx_ok = is_halo && hx >= 0 && hx < a.W;
@@ -377,7 +392,7 @@ __global__ void __launch_bounds__(8 * TX, 3) dw_wgrad_kernel(const DwWgradArgs a
 #pragma unroll
     for (int e = 0; e < VEC; ++e) acc[t][e] = 0.f;
   auto load_g = [&](int y, float* out) {  // dh2 of this thread's pixel in row y (zero outside the strip)
-    if (y >= y0 && y < y0 + TY) {
+    if (y >= y0 && y < y0 + TY && col_ok) {
       float g[VEC];
       ld_f32<T>(gp + ((size_t)y * a.W + x0 + xl) * a.C, g);
 #pragma unroll
@@ -396,7 +411,7 @@ __global__ void __launch_bounds__(8 * TX, 3) dw_wgrad_kernel(const DwWgradArgs a
     const int gy = y0 - 1 + r;
     if (r < nrows && gy >= 0 && gy < a.H) {
       const T* row = hp + (size_t)gy * a.W * a.C;
-      hpre = ld_vec<T>(row + (size_t)(x0 + xl) * a.C);
+      if (col_ok) hpre = ld_vec<T>(row + (size_t)(x0 + xl) * a.C);
       if (hx_ok) hpre_h = ld_vec<T>(row + (size_t)hx * a.C);
     }
   };
@@ -405,7 +420,7 @@ __global__ void __launch_bounds__(8 * TX, 3) dw_wgrad_kernel(const DwWgradArgs a
     const int gy = y0 - 1 + r;
     const bool row_ok = gy >= 0 && gy < a.H;
     vec_t* buf = ring[r & 1];
-    buf[(xl + 1) * 8 + cl] = row_ok ? activate(hpre) : zero;
+    buf[(xl + 1) * 8 + cl] = (row_ok && col_ok) ? activate(hpre) : zero;
     if (is_halo) buf[hslot * 8 + cl] = (row_ok && hx_ok) ? activate(hpre_h) : zero;
     issue(r + 1);
     float gload[VEC];
@@ -454,13 +469,14 @@ __global__ void dw_wgrad_reduce_kernel(const float* partial, float* out, int npa
 }
 template <typename T>
 static void launch_dw_wgrad_t(const DwWgradArgs& a, dim3 grid, int TX, hipStream_t s) {
-  if (TX == 32) hipLaunchKernelGGL((dw_wgrad_kernel<T, 32>), grid, dim3(256), 0, s, a);
+  if (a.W % 8) hipLaunchKernelGGL((dw_wgrad_kernel<T, 8, true>), grid, dim3(64), 0, s, a);
+  else if (TX == 32) hipLaunchKernelGGL((dw_wgrad_kernel<T, 32>), grid, dim3(256), 0, s, a);
   else if (TX == 16) hipLaunchKernelGGL((dw_wgrad_kernel<T, 16>), grid, dim3(128), 0, s, a);
   else hipLaunchKernelGGL((dw_wgrad_kernel<T, 8>), grid, dim3(64), 0, s, a);
 }
 hipError_t launch_dw_wgrad(int dtype, const DwWgradArgs& a, hipStream_t s) {
   const int CC = dtype == 0 ? 32 : 64;
-  if (a.C % CC || a.W % 8) return hipErrorInvalidValue;
+  if (a.C % CC || a.W < 1 || a.H < 1) return hipErrorInvalidValue;
   const int TX = dwg_tx(a.W);
   dim3 grid(dw_wgrad_strips(a.H, a.W), a.C / CC, a.B);
   switch (dtype) {
@@ -813,13 +829,16 @@ hipError_t launch_pack_planes(int dtype, const float* x0, const float* x1, int c
 __device__ __forceinline__ float phi_f(float x) { return x > 0.f ? x + 1.f : __expf(x); }
 __device__ __forceinline__ float dphi_f(float x) { return x > 0.f ? 1.f : __expf(x); }
 
-// pass A: one block per (64 positions, head, image): dq and this tile's dkv / dks partial
-template <typename T>
+// pass A: one block per (64 positions, head, image): dq and this tile's dkv / dks partial.
+// RAGGED (N % 64 != 0): ceil(N / 64) tiles, the last one partly empty -- its positions past N hold zeros in LDS (so they add
+// nothing to the partial) and are not stored.
+template <typename T, bool RAGGED = false>
 __global__ void __launch_bounds__(256) linattn_bwd_q_kernel(const AttnBwdArgs a) {
   __shared__ float skv[32 * 33];
   __shared__ float sq[64][33], sraw[64][33], sdn[64][33], sdd[64];
   const int h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
-  const int n0 = blockIdx.x * 64, ntile = a.N / 64;
+  const int n0 = blockIdx.x * 64, ntile = RAGGED ? (a.N + 63) / 64 : a.N / 64;
+  const int nv = RAGGED ? min(64, a.N - n0) : 64;  // positions of this tile that exist
   const int inner = a.heads * 32, ld = 3 * inner;
   const float* kvp = a.kv + (size_t)(b * a.heads + h) * 32 * 33;
   const size_t sps = (size_t)a.B * a.heads * 32 * 33;
@@ -832,6 +851,11 @@ __global__ void __launch_bounds__(256) linattn_bwd_q_kernel(const AttnBwdArgs a)
   const T* dobase = reinterpret_cast<const T*>(a.dout) + ((size_t)b * a.N + n0) * inner + h * 32;
   for (int i = tid; i < 64 * 32; i += 256) {
     const int n = i >> 5, c = i & 31;
+    if (RAGGED && n >= nv) {
+      sraw[n][c] = 0.f;
+      sq[n][c] = 0.f;
+      continue;
+    }
     const float q = (float)qbase[(size_t)n * ld + c];
     sraw[n][c] = q;
     sq[n][c] = phi_f(q);
@@ -852,7 +876,7 @@ __global__ void __launch_bounds__(256) linattn_bwd_q_kernel(const AttnBwdArgs a)
     const float inv = 1.f / (den + 1e-6f);
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-      const float dout = (float)dobase[(size_t)n * inner + e0 + q];
+      const float dout = (RAGGED && n >= nv) ? 0.f : (float)dobase[(size_t)n * inner + e0 + q];
       const float dn = dout * inv;
       sdn[n][e0 + q] = dn;
       dsum += dn * (num[q] * inv);  // dout*out/den
@@ -862,7 +886,7 @@ __global__ void __launch_bounds__(256) linattn_bwd_q_kernel(const AttnBwdArgs a)
     if ((tid & 3) == 0) sdd[n] = -dsum;
   }
   wg_barrier();
-  {  // dq for d in [e0, e0+8)
+  if (!RAGGED || n < nv) {  // dq for d in [e0, e0+8)
     T* dq = reinterpret_cast<T*>(a.dqkv) + ((size_t)b * a.N + n0 + n) * ld + h * 32 + e0;
     const float dd = sdd[n];
 #pragma unroll
@@ -891,18 +915,20 @@ __global__ void __launch_bounds__(256) linattn_bwd_q_kernel(const AttnBwdArgs a)
   }
 }
 // pass B: dk, dv from the reduced dkv [B][heads][32][33] (a.dkv points at the reduced table here)
-template <typename T>
+template <typename T, bool RAGGED = false>
 __global__ void __launch_bounds__(256) linattn_bwd_kv_kernel(const AttnBwdArgs a) {
   __shared__ float sd[32 * 33];
   __shared__ float sk[64][33], sraw[64][33], sv[64][33];
   const int h = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
   const int n0 = blockIdx.x * 64;
+  const int nv = RAGGED ? min(64, a.N - n0) : 64;
   const int inner = a.heads * 32, ld = 3 * inner;
   const float* dp = a.dkv + (size_t)(b * a.heads + h) * 32 * 33;
   for (int i = tid; i < 32 * 33; i += 256) sd[i] = dp[i];
   const T* base = reinterpret_cast<const T*>(a.qkv) + ((size_t)b * a.N + n0) * ld + h * 32;
   for (int i = tid; i < 64 * 32; i += 256) {
     const int n = i >> 5, c = i & 31;
+    if (RAGGED && n >= nv) continue;  // never read below
     const float k = (float)base[(size_t)n * ld + inner + c];
     sraw[n][c] = k;
     sk[n][c] = phi_f(k);
@@ -910,6 +936,7 @@ __global__ void __launch_bounds__(256) linattn_bwd_kv_kernel(const AttnBwdArgs a
   }
   wg_barrier();
   const int n = tid >> 2, e0 = (tid & 3) * 8;
+  if (RAGGED && n >= nv) return;  // no barrier follows
   T* drow = reinterpret_cast<T*>(a.dqkv) + ((size_t)b * a.N + n0 + n) * ld + h * 32 + e0;
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
@@ -925,7 +952,17 @@ __global__ void __launch_bounds__(256) linattn_bwd_kv_kernel(const AttnBwdArgs a
   }
 }
 hipError_t launch_linattn_bwd_q(int dtype, const AttnBwdArgs& a, hipStream_t s) {
-  if (a.N % 64) return hipErrorInvalidValue;
+  if (a.N < 1) return hipErrorInvalidValue;
+  if (a.N % 64) {
+    dim3 grid((a.N + 63) / 64, a.heads, a.B);
+    switch (dtype) {
+      case 0: hipLaunchKernelGGL((linattn_bwd_q_kernel<float, true>), grid, dim3(256), 0, s, a); break;
+      case 1: hipLaunchKernelGGL((linattn_bwd_q_kernel<half_t, true>), grid, dim3(256), 0, s, a); break;
+      case 2: hipLaunchKernelGGL((linattn_bwd_q_kernel<bf16_t, true>), grid, dim3(256), 0, s, a); break;
+      default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  }
   dim3 grid(a.N / 64, a.heads, a.B);
   switch (dtype) {
     case 0: hipLaunchKernelGGL(linattn_bwd_q_kernel<float>, grid, dim3(256), 0, s, a); break;
@@ -936,7 +973,17 @@ hipError_t launch_linattn_bwd_q(int dtype, const AttnBwdArgs& a, hipStream_t s) 
   return hipGetLastError();
 }
 hipError_t launch_linattn_bwd_kv(int dtype, const AttnBwdArgs& a, hipStream_t s) {
-  if (a.N % 64) return hipErrorInvalidValue;
+  if (a.N < 1) return hipErrorInvalidValue;
+  if (a.N % 64) {
+    dim3 grid((a.N + 63) / 64, a.heads, a.B);
+    switch (dtype) {
+      case 0: hipLaunchKernelGGL((linattn_bwd_kv_kernel<float, true>), grid, dim3(256), 0, s, a); break;
+      case 1: hipLaunchKernelGGL((linattn_bwd_kv_kernel<half_t, true>), grid, dim3(256), 0, s, a); break;
+      case 2: hipLaunchKernelGGL((linattn_bwd_kv_kernel<bf16_t, true>), grid, dim3(256), 0, s, a); break;
+      default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+  }
   dim3 grid(a.N / 64, a.heads, a.B);
   switch (dtype) {
     case 0: hipLaunchKernelGGL(linattn_bwd_kv_kernel<float>, grid, dim3(256), 0, s, a); break;

@@ -834,14 +834,10 @@ static hipError_t launch_conv_t(const Conv3Args& a, hipStream_t s) {
   const int Ho = MODE == 0 ? a.Hi / 2 : (MODE == 1 ? a.Hi * 2 : a.Hi), Wo = MODE == 0 ? a.Wi / 2 : (MODE == 1 ? a.Wi * 2 : a.Wi);
   if (Ho < 1 || Wo < 1 || a.Cin % 32 || a.Cout % 32 || (MODE == 0 && (a.Hi % 2 || a.Wi % 2))) return hipErrorInvalidValue;
   const int BN = (a.Cout % 128 == 0) ? 128 : ((a.Cout % 64 == 0) ? 64 : 32);
-  if (Ho % 8 || Wo % 8) {  // partly empty edge tiles: forward convs onto maps that are not a multiple of 8 (image sizes % 64 != 0)
-    if constexpr (MODE == 0 || MODE == 1) {
-      if (BN == 128) return launch_conv_cfg<T, MODE, 8, 128, 2, 2, true>(a, s);
-      if (BN == 64) return launch_conv_cfg<T, MODE, 8, 64, 2, 2, true>(a, s);
-      return launch_conv_cfg<T, MODE, 8, 32, 2, 1, true>(a, s);
-    } else {
-      return hipErrorInvalidValue;
-    }
+  if (Ho % 8 || Wo % 8) {  // partly empty edge tiles: maps that are not a multiple of 8 (image sizes % 64 != 0); MODE 2 = training
+    if (BN == 128) return launch_conv_cfg<T, MODE, 8, 128, 2, 2, true>(a, s);
+    if (BN == 64) return launch_conv_cfg<T, MODE, 8, 64, 2, 2, true>(a, s);
+    return launch_conv_cfg<T, MODE, 8, 32, 2, 1, true>(a, s);
   }
   if (conv_tw(Wo) == 16) {
     if (BN == 128) return launch_conv_cfg<T, MODE, 16, 128, 2, 2>(a, s);

@@ -66,8 +66,8 @@ __device__ __forceinline__ void dw_body_impl(const DwArgs& a, const int TYL, con
   const T* in = reinterpret_cast<const T*>(a.in) + (size_t)b * a.H * a.W * a.C + c0;
   T* out = reinterpret_cast<T*>(a.out) + (size_t)b * a.H * a.W * a.C + c0;
 
-  // ragged images (W % TX != 0 or H % TYL != 0: image sizes that are not a multiple of 64, forward only): columns / rows past the
-  // image are read as zero (the conv's padding) and neither stored nor pooled
+  // ragged images (W % TX != 0 or H % TYL != 0: image sizes that are not a multiple of 64): columns / rows past the image are
+  // read as zero (the conv's padding) and neither stored nor pooled (BWD: nor counted in the norm partials)
   const bool col_ok = RAGGED ? x0 + xl < a.W : true;
   // halo duty: threads 0..7 fetch column x0-1, threads 8..15 column x0+TX (their own channel lane)
   const bool is_halo = tid < 16;
@@ -129,7 +129,7 @@ __device__ __forceinline__ void dw_body_impl(const DwArgs& a, const int TYL, con
   }
   auto issue_b = [&](int r, vec_t& v) {  // output row r - 2 is produced at iteration r
     if constexpr (BWD) {
-      if (r >= 2 && r < nrows) v = ld_vec<T>(bx + ((size_t)(y0 + r - 2) * a.W + x0 + xl) * a.C);
+      if (r >= 2 && r < nrows && (!RAGGED || (col_ok && y0 + r - 2 < a.H))) v = ld_vec<T>(bx + ((size_t)(y0 + r - 2) * a.W + x0 + xl) * a.C);
     }
   };
 #pragma unroll
@@ -206,14 +206,16 @@ __device__ __forceinline__ void dw_body_impl(const DwArgs& a, const int TYL, con
         if constexpr (BWD) {
           float hb[VEC], dz[VEC];
           vec_to_f32<T>(preb[j % 4], hb);
+          const bool px_ok = !RAGGED || (col_ok && y0 + r - 2 < a.H);
 #pragma unroll
           for (int e = 0; e < VEC; ++e) {
             const float z = hb[e] * bsc[e] + bsh[e];
-            dz[e] = round_to<T>((z > 0.f && z < 6.f) ? a2[e] : 0.f);
+            dz[e] = round_to<T>((px_ok && z > 0.f && z < 6.f) ? a2[e] : 0.f);
+            if (RAGGED) hb[e] = px_ok ? hb[e] : 0.f;
             psum[e] += dz[e];
             psum2[e] += dz[e] * hb[e];
           }
-          st_f32<T>(out + ((size_t)(y0 + r - 2) * a.W + x0 + xl) * a.C, dz);
+          if (px_ok) st_f32<T>(out + ((size_t)(y0 + r - 2) * a.W + x0 + xl) * a.C, dz);
           if (((r - 2) & 7) == 7) {  // uniform: an 8-row segment is complete
             pool_segment_flush<VEC>(psum, red + (((r - 2) >> 3) * (NT / 64) + (tid >> 6)) * CC, tid & 63);
             pool_segment_flush<VEC>(psum2, red + ((8 + ((r - 2) >> 3)) * (NT / 64) + (tid >> 6)) * CC, tid & 63);
@@ -237,7 +239,7 @@ __device__ __forceinline__ void dw_body_impl(const DwArgs& a, const int TYL, con
   // ---- SE pool partials, one per 8-row segment (layout independent of the strip height)
   if constexpr (BWD) {  // slab[b][tile][{sum dz, sum dz*bx}][C]
     wg_barrier();
-    const int ntiles = tiles_x * (a.H / kPoolSegRows);
+    const int ntiles = tiles_x * (RAGGED ? (a.H + kPoolSegRows - 1) / kPoolSegRows : a.H / kPoolSegRows);
     float* base = a.bslab + (size_t)b * ntiles * 2 * a.C + chunk_id * CC;
     pool_segments_store<CC, NT>(red, TYL / kPoolSegRows, tid, base, 2 * a.C, ty * (TYL / kPoolSegRows), tiles_x, tx);
     pool_segments_store<CC, NT>(red + 8 * (NT / 64) * CC, TYL / kPoolSegRows, tid, base + a.C, 2 * a.C,
@@ -266,6 +268,10 @@ template <typename T, int TX, int PFV>
 __global__ void __launch_bounds__(8 * TX) dwconv3x3_bwd_kernel(const DwArgs a, const int TYL, const int swap) {
   dw_body<T, TX, PFV, true>(a, TYL, 0, swap);
 }
+template <typename T, int TX, int PFV>
+__global__ void __launch_bounds__(8 * TX) dwconv3x3_bwd_ragged_kernel(const DwArgs a, const int TYL, const int swap) {
+  dw_body_impl<T, TX, PFV, true, false, true>(a, TYL, 0, swap);  // partial strips at the right / bottom edge
+}
 
 static int g_dw_swap = 0;
 void dwconv_swap(int v) { g_dw_swap = v; }
@@ -288,8 +294,8 @@ int dwconv_ntiles(int H, int W) { return ((H + kPoolSegRows - 1) / kPoolSegRows)
 template <typename T>
 static hipError_t launch_dw_t(const DwArgs& a, hipStream_t s) {
   constexpr int CC = 8 * Elem<T>::VEC;
-  const bool ragged = a.H % 8 || a.W % 8;  // forward only: partial strips at the right / bottom edge
-  if (a.C % CC || a.H < 1 || a.W < 1 || (ragged && a.bx)) return hipErrorInvalidValue;
+  const bool ragged = a.H % 8 || a.W % 8;  // partial strips at the right / bottom edge
+  if (a.C % CC || a.H < 1 || a.W < 1) return hipErrorInvalidValue;
   const int tx = dw_tx(a.W), tyl = dw_pick_tyl(a.B, a.H, a.W, a.C / CC);
   const int tiles = ((a.W + tx - 1) / tx) * ((a.H + tyl - 1) / tyl);
   dim3 grid(tiles, a.C / CC, a.B);
@@ -298,7 +304,14 @@ static hipError_t launch_dw_t(const DwArgs& a, hipStream_t s) {
                                        std::string("dwconv3x3_kernel<") + TypeName<T>::value + ", 16, 4>",
                                        std::string("dwconv3x3_kernel<") + TypeName<T>::value + ", 8, 4>"};
   note_kernel(names[tx == 32 ? 0 : (tx == 16 ? 1 : 2)].c_str());
-  if (ragged) {  // forward only (checked above); TX is 16 or 32 here
+  if (ragged && a.bx) {  // backward instantiation; TX is 16 or 32 here
+    if (!a.bas || !a.bab || !a.bslab || a.pool || a.s6) return hipErrorInvalidValue;
+    note_kernel("dwconv3x3_bwd_ragged_kernel");
+    if (tx == 32) hipLaunchKernelGGL((dwconv3x3_bwd_ragged_kernel<T, 32, kDwPF>), grid, dim3(256), 0, s, a, tyl, g_dw_swap);
+    else hipLaunchKernelGGL((dwconv3x3_bwd_ragged_kernel<T, 16, kDwPF>), grid, dim3(128), 0, s, a, tyl, g_dw_swap);
+    return hipGetLastError();
+  }
+  if (ragged) {  // TX is 16 or 32 here
     note_kernel("dwconv3x3_ragged_kernel");
     if constexpr (sizeof(T) == 2) {
       if (a.s6) {

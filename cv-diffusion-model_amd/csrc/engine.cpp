@@ -1183,8 +1183,10 @@ struct Back {
   struct Geo { int Ho, Wo, Hi, Wi, stride, dy, dx; };
   void wgrad(size_t g, int N, const GemmSeg* segs, int nseg, int K, Geo geo, float* out, int64_t ldn, int64_t ldk, int64_t off,
              int ntap = 1, int nstore = 0, int kstore = 0) {
-    const int M = B * geo.Ho * geo.Wo;
-    const int ms = wgrad_msplit(dt, M, N, K, ntap);
+    const int M = wgrad_rows(B, geo.Ho * geo.Wo);  // ragged maps: padded per image to whole 64-row chunks
+    // image sizes off the multiples of 64 split their rows freely (every level); the launch decisions at multiples of 64 stay
+    const bool off64 = c->cfg.kind == LLIE_UNET && c->cfg.image_size % 64;
+    const int ms = off64 ? wgrad_msplit_ragged(dt, M, N, K, ntap) : wgrad_msplit(dt, M, N, K, ntap);
     const size_t part = alloc((size_t)ms * ntap * N * K * 4);
     if (!dry) {
       WgradArgs a{};
@@ -1205,7 +1207,7 @@ struct Back {
   Coef gn_site(size_t g, const Tens& x0, const Tens* x1, const GnRec& rec, int act, size_t gamma, size_t beta,
                float* dgamma, float* dbeta, const float* film, int64_t fstride, float* dfilm, int64_t dfstride,
                size_t pre_slab = 0, int pre_tiles = 0) {
-    const int C = x0.C + (x1 ? x1->C : 0), P = x0.H * x0.W, M = B * P, nt = pre_tiles ? pre_tiles : P / 64;
+    const int C = x0.C + (x1 ? x1->C : 0), P = x0.H * x0.W, M = B * P, nt = pre_tiles ? pre_tiles : (P + 63) / 64;
     const size_t slab = pre_tiles ? pre_slab : alloc((size_t)B * nt * 2 * C * 4);
     const size_t S = alloc((size_t)B * 2 * C * 4);
     Coef k{alloc((size_t)B * C * 4), alloc((size_t)B * C * 4), alloc((size_t)B * C * 4)};
@@ -1258,7 +1260,7 @@ struct Back {
     const Geo g11{H, W, H, W, 1, 0, 0};
     // project (+ skip) input gradients
     const size_t da3 = alloc((size_t)M * hid * es());
-    const int gtiles = P / pw_gemm_tile_rows(P);
+    const int gtiles = pw_gemm_ntiles(P);
     const size_t gslab = alloc((size_t)B * gtiles * 2 * hid * 4);  // d(gate) partials from the GEMM's epilogue: sum_px da3*h2
     gemm(dY, cout, wptr(w.w_proj_t), da3, hid, M, P, gslab, r.h2, true);
     size_t dxs = 0;
@@ -1370,7 +1372,7 @@ struct Back {
     // attention core
     const size_t dqkv = alloc((size_t)M * 3 * inner * es());
     {
-      const int nt = N / 64;
+      const int nt = (N + 63) / 64;
       const size_t part = alloc((size_t)B * w.heads * nt * 32 * 33 * 4), tot = alloc((size_t)B * w.heads * 32 * 33 * 4);
       if (!dry) {
         AttnBwdArgs a{};
@@ -1410,7 +1412,7 @@ struct Back {
     const int C = w.c, Ho = r.y.H, Wo = r.y.W, Mo = B * Ho * Wo, pf = w.p_first;
     const size_t dY = take_grad(r.y);
     {  // bias gradient: column sums of dY
-      const int nt = Ho * Wo / 64;
+      const int nt = (Ho * Wo + 63) / 64;
       const size_t slab = alloc((size_t)B * nt * 2 * C * 4), S = alloc((size_t)B * C * 4);
       if (!dry) {
         BwdMaskArgs m{};
@@ -1914,7 +1916,6 @@ int64_t llie_param_grad_offset(const llie_ctx* c, int i) {
 int64_t llie_train_workspace_bytes(llie_ctx* c, int batch, int height, int width) {
   if (!c || batch <= 0) return LLIE_ERR_ARG;
   if (c->padded) { set_err("the unpinned variants (tiny / base, zero-padded channels) are inference-only"); return LLIE_ERR_CONFIG; }
-  if (c->cfg.kind == LLIE_UNET && c->cfg.image_size % 64) { set_err("training needs an image_size that is a multiple of 64 (inference: 32)"); return LLIE_ERR_SHAPE; }
   Arena ar((size_t)1 << 46);
   Tape tape;
   Run r{c, &ar, nullptr, nullptr, true, batch, c->dt};
@@ -1937,7 +1938,6 @@ int llie_unet_train_forward(llie_ctx* c, const float* lat, const float* cond, co
                             void* ws, int64_t ws_bytes, llie_stream stream) {
   if (!c || !lat || !cond || !t || !eps || !ws || batch <= 0 || c->cfg.kind != LLIE_UNET) return LLIE_ERR_ARG;
   if (c->padded) { set_err("the unpinned variants (tiny / base, zero-padded channels) are inference-only"); return LLIE_ERR_CONFIG; }
-  if (c->cfg.image_size % 64) { set_err("training needs an image_size that is a multiple of 64 (inference: 32)"); return LLIE_ERR_SHAPE; }
   if (!c->blob) { set_err("no HIP device"); return LLIE_ERR_NO_DEVICE; }
   int rc = check_loaded(c);
   if (rc) return rc;

@@ -420,6 +420,8 @@ struct WgradArgs {
   int msplit;
 };
 int wgrad_msplit(int dtype, int M, int N, int K, int ntap);
+int wgrad_msplit_ragged(int dtype, int M, int N, int K, int ntap);  // image sizes off the multiples of 64
+int wgrad_rows(int B, int P);  // rows the weight-gradient GEMM walks: B * P, padded per image to 64-row chunks when P % 64 != 0
 void wgrad_set_target(int workgroups);  // tuning knob: workgroups per launch the row split aims for (default 1024)
 hipError_t launch_wgrad(int dtype, const WgradArgs& a, hipStream_t s);
 

@@ -37,7 +37,10 @@ __device__ __forceinline__ void load_operand_rows(const T* img, int pitch, int r
 
 // WT = 32-wide blocks per wave and dimension: the workgroup tile is (64*WT) x (64*WT) outputs.  WT = 2 halves the
 // re-reads of g (once per k-tile) and A' (once per n-tile) for the wide layers.
-template <typename T, int WT>
+// RAGGED (image sizes that are not a multiple of 64): the rows are padded per image to ceil(P / 64) chunks, so a chunk still
+// lies inside one image; rows past the image stage zeros in both operands (nothing is read).  The splits need not divide the
+// chunks: the last one ends at the last chunk (wgrad_msplit_ragged).
+template <typename T, int WT, bool RAGGED = false>
 __global__ void __launch_bounds__(256) wgrad_kernel(const WgradArgs a, int rows_per_split) {
   constexpr int TILE = 64 * WT;
   constexpr int VEC = Elem<T>::VEC, VPR = TILE / VEC, RPP = 256 / VPR, NP = kWgRows / RPP;  // passes to load 64 rows x TILE channels
@@ -89,10 +92,10 @@ __global__ void __launch_bounds__(256) wgrad_kernel(const WgradArgs a, int rows_
 #pragma unroll
   for (int e = 0; e < VEC; ++e) zero[e] = (T)0.f;
 
-  // Every 64-row chunk lies inside one image (P % 64 == 0, splits start on multiples of 64), so the image index and
+  // Every 64-row chunk lies inside one image (P % 64 == 0 or padded rows, splits start on multiples of 64), so the image index and
   // the prologue's per-(image, channel) affine are chunk-uniform: 32-bit index math once per chunk, the affine is
   // reloaded only when the image changes.  1x1 layers (source pixel == output pixel) skip the pixel decomposition.
-  const int chunks_per_image = P / kWgRows;
+  const int chunks_per_image = RAGGED ? (P + kWgRows - 1) / kWgRows : P / kWgRows;
   const int chunk0 = (int)(m_begin / kWgRows);
   const bool plain = a.ntap == 1 && a.stride == 1 && a.dy == 0 && a.dx == 0 && a.Hi == a.Ho && a.Wi == a.Wo;
   float sc[VEC], sh[VEC];
@@ -110,13 +113,14 @@ __global__ void __launch_bounds__(256) wgrad_kernel(const WgradArgs a, int rows_
         sh[e] = aab ? aab[(size_t)b * ald + aoff + e] : 0.f;
       }
     }
-    const size_t mrow0 = (size_t)chunk * kWgRows;
+    const size_t mrow0 = RAGGED ? (size_t)b * P + pix0 : (size_t)chunk * kWgRows;  // first row of the chunk in memory
 #pragma unroll
     for (int ps = 0; ps < NP; ++ps) {
       const int r = ps * RPP + rl;
-      gv[ps] = g_ok ? ld_vec<T>(gp + (mrow0 + r) * a.N + n0 + cv) : zero;
+      const bool row_ok = !RAGGED || pix0 + r < P;
+      gv[ps] = (g_ok && row_ok) ? ld_vec<T>(gp + (mrow0 + r) * a.N + n0 + cv) : zero;
       av[ps] = zero;
-      if (aptr) {
+      if (aptr && row_ok) {
         bool ok = true;
         size_t src = mrow0 + r;  // plain: same pixel
         if (!plain) {
@@ -139,8 +143,10 @@ __global__ void __launch_bounds__(256) wgrad_kernel(const WgradArgs a, int rows_
       }
     }
   };
-  fetch(0);
-  for (int mc = 0; mc < rows_per_split; mc += kWgRows) {
+  // rows of this split (RAGGED: the last split may be shorter)
+  const int rows = RAGGED ? min(rows_per_split, (a.B * chunks_per_image - chunk0) * kWgRows) : rows_per_split;
+  if (!RAGGED || rows > 0) fetch(0);
+  for (int mc = 0; mc < rows; mc += kWgRows) {
     wg_barrier();  // previous chunk's operand reads are done
 #pragma unroll
     for (int ps = 0; ps < NP; ++ps) {
@@ -149,7 +155,7 @@ __global__ void __launch_bounds__(256) wgrad_kernel(const WgradArgs a, int rows_
       st_vec<T>(sA + r * PITCH + cv, av[ps]);
     }
     wg_barrier();
-    if (mc + kWgRows < rows_per_split) fetch(mc + kWgRows);  // next chunk's global loads fly under the MFMAs
+    if (mc + kWgRows < rows) fetch(mc + kWgRows);  // next chunk's global loads fly under the MFMAs
 #pragma unroll
     for (int ch = 0; ch < kWgRows / 32; ++ch) {
       T fa[WT][16], fb[WT][16];
@@ -205,7 +211,9 @@ __global__ void __launch_bounds__(256) wgrad_reduce_kernel(const float* partial,
   if (n < nstore && k < kstore) out[(size_t)n * ldn + (size_t)k * ldk + off + (ntap == 9 ? tap : 0)] = s;
 }
 
-// number of row splits: enough workgroups to fill the GPU, each split a multiple of 64 rows
+// rows the kernel walks: B * P, or, for ragged maps, B images padded to whole 64-row chunks
+int wgrad_rows(int B, int P) { return B * ((P + kWgRows - 1) / kWgRows) * kWgRows; }
+// number of row splits: enough workgroups to fill the GPU, each split a multiple of 64 rows (M = wgrad_rows)
 static int g_wgrad_target = 1024;  // workgroups per launch the row split aims for
 void wgrad_set_target(int v) { g_wgrad_target = v > 0 ? v : 1024; }
 // 128x128 tiles for the wide layers of the 2-byte engines (fp32 tiles would not fit the 64 KB static LDS)
@@ -218,9 +226,24 @@ int wgrad_msplit(int dtype, int M, int N, int K, int ntap) {
   return ms;
 }
 
+// Image sizes that are not a multiple of 64 (whatever the level's P): the same doubling rule without the divisibility stop --
+// 224 x 224 at B = 8 has 2^7 * 49 chunks at its top level, where the rule above stops at 128 splits for a 1024-workgroup target
+// (1.7x the kernel time of the 256 x 256 step's weight gradients).  Splits of ceil(chunks / ms) chunks, none empty.
+int wgrad_msplit_ragged(int dtype, int M, int N, int K, int ntap) {
+  const int t = wgrad_tile(dtype, N, K);
+  const int tiles = ((N + t - 1) / t) * ((K + t - 1) / t) * ntap;
+  const int chunks = M / kWgRows;
+  int ms = 1;
+  while (tiles * ms < g_wgrad_target && M / (ms * 2) >= 256 && ms * 2 <= chunks) ms *= 2;
+  const int per = (chunks + ms - 1) / ms;
+  return (chunks + per - 1) / per;
+}
+
 hipError_t launch_wgrad(int dtype, const WgradArgs& a, hipStream_t s) {
-  const int M = a.B * a.Ho * a.Wo;
-  if (a.msplit < 1 || M % (a.msplit * kWgRows) || a.N % 32 || a.K % 32 || a.nseg < 1 || a.nseg > 3) return hipErrorInvalidValue;
+  const int P = a.Ho * a.Wo, M = wgrad_rows(a.B, P);  // == B * P unless P % 64 != 0
+  // splits that do not divide the chunks: wgrad_msplit_ragged (ragged kernel, whatever P)
+  const bool ragged = P % kWgRows || M % (a.msplit * kWgRows);
+  if (a.msplit < 1 || a.msplit > M / kWgRows || a.N % 32 || a.K % 32 || a.nseg < 1 || a.nseg > 3) return hipErrorInvalidValue;
   int k = 0;
   for (int i = 0; i < a.nseg; ++i) {
     if (a.seg[i].ch % 32) return hipErrorInvalidValue;
@@ -230,18 +253,33 @@ hipError_t launch_wgrad(int dtype, const WgradArgs& a, hipStream_t s) {
   if (a.ntap != 1 && a.ntap != 9) return hipErrorInvalidValue;
   const int t = wgrad_tile(dtype, a.N, a.K);
   dim3 grid((a.N + t - 1) / t, ((a.K + t - 1) / t) * a.ntap, a.msplit);
-  const int rps = M / a.msplit;
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL((wgrad_kernel<float, 1>), grid, dim3(256), 0, s, a, rps); break;
-    case 1:
-      if (t == 128) hipLaunchKernelGGL((wgrad_kernel<half_t, 2>), grid, dim3(256), 0, s, a, rps);
-      else hipLaunchKernelGGL((wgrad_kernel<half_t, 1>), grid, dim3(256), 0, s, a, rps);
-      break;
-    case 2:
-      if (t == 128) hipLaunchKernelGGL((wgrad_kernel<bf16_t, 2>), grid, dim3(256), 0, s, a, rps);
-      else hipLaunchKernelGGL((wgrad_kernel<bf16_t, 1>), grid, dim3(256), 0, s, a, rps);
-      break;
-    default: return hipErrorInvalidValue;
+  const int rps = (M / kWgRows + a.msplit - 1) / a.msplit * kWgRows;  // == M / msplit unless ragged
+  if (ragged) {  // the splits start on padded chunk boundaries
+    switch (dtype) {
+      case 0: hipLaunchKernelGGL((wgrad_kernel<float, 1, true>), grid, dim3(256), 0, s, a, rps); break;
+      case 1:
+        if (t == 128) hipLaunchKernelGGL((wgrad_kernel<half_t, 2, true>), grid, dim3(256), 0, s, a, rps);
+        else hipLaunchKernelGGL((wgrad_kernel<half_t, 1, true>), grid, dim3(256), 0, s, a, rps);
+        break;
+      case 2:
+        if (t == 128) hipLaunchKernelGGL((wgrad_kernel<bf16_t, 2, true>), grid, dim3(256), 0, s, a, rps);
+        else hipLaunchKernelGGL((wgrad_kernel<bf16_t, 1, true>), grid, dim3(256), 0, s, a, rps);
+        break;
+      default: return hipErrorInvalidValue;
+    }
+  } else {
+    switch (dtype) {
+      case 0: hipLaunchKernelGGL((wgrad_kernel<float, 1>), grid, dim3(256), 0, s, a, rps); break;
+      case 1:
+        if (t == 128) hipLaunchKernelGGL((wgrad_kernel<half_t, 2>), grid, dim3(256), 0, s, a, rps);
+        else hipLaunchKernelGGL((wgrad_kernel<half_t, 1>), grid, dim3(256), 0, s, a, rps);
+        break;
+      case 2:
+        if (t == 128) hipLaunchKernelGGL((wgrad_kernel<bf16_t, 2>), grid, dim3(256), 0, s, a, rps);
+        else hipLaunchKernelGGL((wgrad_kernel<bf16_t, 1>), grid, dim3(256), 0, s, a, rps);
+        break;
+      default: return hipErrorInvalidValue;
+    }
   }
   const int64_t n = (int64_t)a.ntap * a.N * a.K;
   int rows = a.msplit;
