@@ -27,6 +27,7 @@ EXPORTS = [
     "llie_grad_numel", "llie_param_grad_offset", "llie_train_workspace_bytes", "llie_unet_train_forward",
     "llie_unet_backward", "llie_module_backward", "llie_load_all", "llie_profile_dump", "llie_copy_probe", "llie_rw_probe", "llie_pw_expand", "llie_gram_stats", "llie_gram_part_floats", "llie_groupnorm_finalize", "llie_conv3x3", "llie_conv3x3_tiles", "llie_linattn", "llie_linattn_splits", "llie_se_mlp", "llie_film", "llie_refresh_params", "llie_path_bytes", "llie_time_embed", "llie_debug_irbx_stamps", "llie_debug_gemm_stamps", "llie_debug_pwx_stamps", "llie_graph_cache_entries", "llie_debug_conv_stamps", "llie_gram_finalize",
     "llie_optimizer_create", "llie_optimizer_destroy", "llie_optimizer_numel", "llie_optimizer_step",
+    "llie_consistency_target", "llie_consistency_loss", "llie_ema_create", "llie_ema_update", "llie_ema_destroy",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 
@@ -67,6 +68,13 @@ class StepCoef(C.Structure):
         ("sqrt_alpha_t", C.c_float), ("sqrt_beta_t", C.c_float), ("sqrt_alpha_prev", C.c_float),
         ("sqrt_beta_prev", C.c_float), ("is_last", C.c_int), ("v_prediction", C.c_int), ("clamp_x0", C.c_int),
     ]
+
+
+DISTILL_LOSS_PER_WG = 1024  # kDistillLossPerWG (csrc/kernels.h): llie_consistency_loss needs one double per this many elements
+
+
+def distill_scratch_bytes(n: int) -> int:
+    return 8 * ((n + DISTILL_LOSS_PER_WG - 1) // DISTILL_LOSS_PER_WG)
 
 
 _lib = None
@@ -140,6 +148,12 @@ def lib() -> C.CDLL:
     L.llie_optimizer_numel.argtypes = [C.c_void_p]
     L.llie_optimizer_numel.restype = C.c_int64
     L.llie_optimizer_step.argtypes = [C.c_void_p, vp, C.POINTER(OptHyper), vp, vp]
+    L.llie_consistency_target.argtypes = [vp, vp, vp, vp, vp, ci, vp, ci, i64, vp]
+    L.llie_consistency_loss.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, ci, i64, vp, i64, vp]
+    L.llie_ema_create.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), ci, C.POINTER(vp)]
+    L.llie_ema_update.argtypes = [vp, C.c_double, vp]
+    L.llie_ema_destroy.argtypes = [vp]
+    L.llie_ema_destroy.restype = None
     L.llie_graph_cache_entries.argtypes = [C.c_void_p]
     L.llie_graph_cache_entries.restype = C.c_int
     L.llie_debug_gemm_stamps.argtypes = [C.POINTER(C.c_double)]

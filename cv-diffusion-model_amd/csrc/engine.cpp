@@ -2414,6 +2414,85 @@ int llie_optimizer_step(llie_optimizer* o, const float* grad_base, const llie_op
   return LLIE_OK;
 }
 
+// ---- consistency distillation
+int llie_consistency_target(const float* x_t, const float* e_teacher, const int64_t* t, const int64_t* t_next, const float* acp, int table_len,
+                            float* x_next, int batch, int64_t per, llie_stream stream) {
+  DistillArgs a{};
+  a.x_t = x_t; a.e_a = e_teacher; a.t = t; a.t_next = t_next; a.acp = acp; a.table_len = table_len; a.batch = batch; a.per = per; a.out = x_next;
+  hipError_t e = launch_consistency_target(a, reinterpret_cast<hipStream_t>(stream));
+  if (e == hipErrorInvalidValue) { set_err("consistency_target: null pointer or empty shape"); return LLIE_ERR_ARG; }
+  if (e != hipSuccess) { set_err("consistency_target: %s", hipGetErrorString(e)); return (int)e; }
+  return LLIE_OK;
+}
+
+int llie_consistency_loss(const float* x_t, const float* x_next, const float* e_student, const float* e_ema, const int64_t* t,
+                          const int64_t* t_next, const float* acp, int table_len, float* d_student, float* loss_out, int batch, int64_t per,
+                          void* scratch, int64_t scratch_bytes, llie_stream stream) {
+  if (batch <= 0 || per <= 0) return LLIE_ERR_ARG;
+  const int64_t need = distill_loss_partials((int64_t)batch * per) * (int64_t)sizeof(double);
+  if (!scratch || scratch_bytes < need) {
+    set_err("consistency_loss: scratch of %lld bytes needed, %lld given", (long long)need, (long long)scratch_bytes);
+    return LLIE_ERR_WORKSPACE;
+  }
+  DistillArgs a{};
+  a.x_t = x_t; a.x_next = x_next; a.e_a = e_student; a.e_b = e_ema; a.t = t; a.t_next = t_next; a.acp = acp; a.table_len = table_len;
+  a.batch = batch; a.per = per; a.out = d_student;
+  hipError_t e = launch_consistency_loss(a, reinterpret_cast<double*>(scratch), loss_out, reinterpret_cast<hipStream_t>(stream));
+  if (e == hipErrorInvalidValue) { set_err("consistency_loss: null pointer or empty shape"); return LLIE_ERR_ARG; }
+  if (e != hipSuccess) { set_err("consistency_loss: %s", hipGetErrorString(e)); return (int)e; }
+  return LLIE_OK;
+}
+
+// the optimiser's table types: OptTensor.p = source parameter, OptTensor.ema = shadow written in place (m, v unused)
+struct llie_ema {
+  OptTensor* tensors = nullptr;
+  OptChunk* chunks = nullptr;
+  int nchunks = 0;
+};
+
+int llie_ema_create(float* const* ema, const float* const* params, const int64_t* numel, int count, llie_ema** out) {
+  if (!ema || !params || !numel || count <= 0 || !out) return LLIE_ERR_ARG;
+  std::vector<OptTensor> tt((size_t)count);
+  std::vector<OptChunk> cc;
+  for (int i = 0; i < count; ++i) {
+    if (!ema[i] || !params[i] || numel[i] <= 0 || numel[i] > (int64_t)INT32_MAX) {
+      set_err("ema_create: tensor %d: null pointer or empty tensor", i);
+      return LLIE_ERR_ARG;
+    }
+    tt[(size_t)i] = OptTensor{const_cast<float*>(params[i]), nullptr, nullptr, ema[i], 0, (long long)numel[i]};
+    for (int64_t o = 0; o < numel[i]; o += kOptChunk) cc.push_back(OptChunk{i, (int)o});
+  }
+  if (cc.size() > (size_t)INT32_MAX) return LLIE_ERR_ARG;
+  auto* o = new llie_ema();
+  o->nchunks = (int)cc.size();
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->tensors), tt.size() * sizeof(OptTensor));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&o->chunks), cc.size() * sizeof(OptChunk));
+  if (e == hipSuccess) e = hipMemcpy(o->tensors, tt.data(), tt.size() * sizeof(OptTensor), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(o->chunks, cc.data(), cc.size() * sizeof(OptChunk), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    set_err("ema_create: %s", hipGetErrorString(e));
+    llie_ema_destroy(o);
+    return e == hipErrorNoDevice ? LLIE_ERR_NO_DEVICE : (int)e;
+  }
+  *out = o;
+  return LLIE_OK;
+}
+
+int llie_ema_update(llie_ema* o, double decay, llie_stream stream) {
+  if (!o) return LLIE_ERR_ARG;
+  hipError_t e = launch_ema_lerp(o->tensors, o->chunks, o->nchunks, decay, reinterpret_cast<hipStream_t>(stream));
+  if (e == hipErrorInvalidValue) { set_err("ema_update: decay must be in [0, 1]"); return LLIE_ERR_ARG; }
+  if (e != hipSuccess) { set_err("ema_update: %s", hipGetErrorString(e)); return (int)e; }
+  return LLIE_OK;
+}
+
+void llie_ema_destroy(llie_ema* o) {
+  if (!o) return;
+  if (o->tensors) (void)hipFree(o->tensors);
+  if (o->chunks) (void)hipFree(o->chunks);
+  delete o;
+}
+
 int llie_copy_probe(const void* src, void* dst, int64_t bytes, llie_stream stream) {
   if (!src || !dst || bytes <= 0) return LLIE_ERR_ARG;
   hipError_t e = launch_copy_probe(src, dst, bytes, reinterpret_cast<hipStream_t>(stream));

@@ -500,4 +500,20 @@ struct OptStepArgs {
 };
 hipError_t launch_optimizer_step(const OptStepArgs& a, hipStream_t s);
 
+// (10) consistency distillation (distill.hip): per-sample alpha-bar from a device table, fp32 [batch, per] tensors
+constexpr int kDistillLossPerWG = 1024;  // elements per workgroup of the loss pass (one double partial each)
+inline long long distill_loss_partials(long long n) { return (n + kDistillLossPerWG - 1) / kDistillLossPerWG; }
+struct DistillArgs {
+  const float* x_t; const float* x_next;     // x_next: loss only
+  const float* e_a; const float* e_b;        // target: e_a = teacher eps; loss: e_a = student eps, e_b = EMA-target eps
+  const int64_t* t; const int64_t* t_next;   // device int64 [batch]
+  const float* acp; int table_len;           // device alphas_cumprod
+  int batch; long long per;                  // elements per sample
+  float* out;                                // target: x_next; loss: d(loss)/d(e_a)
+};
+hipError_t launch_consistency_target(const DistillArgs& a, hipStream_t s);
+hipError_t launch_consistency_loss(const DistillArgs& a, double* partial, float* loss, hipStream_t s);
+// ema = ema * decay + (1 - decay) * p over the tables' tensors (OptTensor.p = source, OptTensor.ema = destination)
+hipError_t launch_ema_lerp(const OptTensor* tensors, const OptChunk* chunks, int nchunks, double decay, hipStream_t s);
+
 }  // namespace llie

@@ -4,12 +4,17 @@ Constructor, `forward` / `enhance` / `compute_loss` / `get_model_size` signature
 (`.unet`, `.scheduler`, `.image_size`, `.condition_mode`) and the `state_dict` layout (all keys under
 `unet.`) are the reference's, so scripts/inference.py and scripts/benchmark.py of the reference can
 call it unchanged.  The whole denoising loop runs as one launch sequence in libllie_hip.so.
+
+`LowLightLCMDistillation` (low_light_diffusion.py:284-408) is the teacher -> student consistency-distillation
+objective on the same engine: the denoisers run through the engine's forward / backward passes, the arithmetic
+around them and the EMA update through csrc/distill.hip.
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Union
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 import torch.nn as nn
@@ -177,6 +182,204 @@ class LowLightDiffusion(nn.Module):
 
     def get_model_size(self) -> Dict[str, float]:
         return self.unet.get_memory_footprint()
+
+
+# ---------------------------------------------------------------------- consistency distillation (:284-408)
+def _require_hip(t: torch.Tensor, what: str) -> None:
+    if t.device.type != "cuda":
+        raise RuntimeError(f"{what} runs only on a HIP device (got '{t.device}'); there is no CPU fallback")
+
+
+def consistency_target(scheduler: LCMScheduler, x_t: torch.Tensor, e_teacher: torch.Tensor, t: torch.Tensor,
+                       t_next: torch.Tensor) -> torch.Tensor:
+    """The teacher's DDIM step t -> t_next (:365-376): x_next = sqrt(a_n) x0 + sqrt(1-a_n) e_T, x0 = (x_t - sqrt(1-a_t) e_T) / sqrt(a_t),
+    a from `scheduler`'s alpha-bar table; t / t_next device int64 [B] (llie_consistency_target)."""
+    _require_hip(x_t, "consistency_target")
+    dev = x_t.device
+    x_t, e_teacher = x_t.detach().float().contiguous(), e_teacher.detach().float().contiguous()
+    acp = scheduler._acp_on(dev)
+    b = x_t.shape[0]
+    out = torch.empty_like(x_t)
+    with torch.cuda.device(dev):
+        N.check(N.lib().llie_consistency_target(x_t.data_ptr(), e_teacher.data_ptr(), t.data_ptr(), t_next.data_ptr(), acp.data_ptr(),
+                                                acp.numel(), out.data_ptr(), b, x_t.numel() // b,
+                                                torch.cuda.current_stream(dev).cuda_stream), "consistency_target")
+    return out
+
+
+def consistency_loss(scheduler: LCMScheduler, x_t: torch.Tensor, x_next: torch.Tensor, e_student: torch.Tensor, e_ema: torch.Tensor,
+                     t: torch.Tensor, t_next: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """F.huber_loss(s0, g0) of :385-393 and its gradient with respect to the student's prediction (llie_consistency_loss):
+    -> (loss, a 0-d device tensor; d(loss)/d(e_student), shaped like it)."""
+    _require_hip(x_t, "consistency_loss")
+    dev = x_t.device
+    x_t, x_next = x_t.detach().float().contiguous(), x_next.detach().float().contiguous()
+    e_student, e_ema = e_student.detach().float().contiguous(), e_ema.detach().float().contiguous()
+    acp = scheduler._acp_on(dev)
+    b, n = x_t.shape[0], x_t.numel()
+    d = torch.empty_like(x_t)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    nbytes = N.distill_scratch_bytes(n)
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        N.check(N.lib().llie_consistency_loss(x_t.data_ptr(), x_next.data_ptr(), e_student.data_ptr(), e_ema.data_ptr(), t.data_ptr(),
+                                              t_next.data_ptr(), acp.data_ptr(), acp.numel(), d.data_ptr(), loss.data_ptr(), b, n // b,
+                                              scratch.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream),
+                "consistency_loss")
+    return loss, d
+
+
+class _ConsistencyLossFn(torch.autograd.Function):
+    """The Huber consistency loss as an autograd node of the student's prediction: forward = llie_consistency_loss, backward =
+    the gradient it wrote times grad_output (so GradScaler's scaled backward works)."""
+
+    @staticmethod
+    def forward(ctx, e_student, scheduler, x_t, x_next, e_ema, t, t_next):
+        loss, d = consistency_loss(scheduler, x_t, x_next, e_student, e_ema, t, t_next)
+        ctx.save_for_backward(d)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        d, = ctx.saved_tensors
+        return (d * grad_output,) + (None,) * 6
+
+
+class LowLightLCMDistillation(nn.Module):
+    """Consistency distillation teacher -> student (low_light_diffusion.py:284-408).  Constructor, attributes (`teacher`,
+    `student`, `ema_student`, `num_ddim_timesteps`, `guidance_scale_range`) and the `state_dict` keys (`teacher.unet.*`,
+    `student.unet.*`, `ema_student.unet.*`) are the reference's.  The teacher is put in eval mode and frozen; `ema_student` is
+    `copy.deepcopy(student_model)` and gets its own engine context.  `guidance_scale_range` is stored and never used, as in
+    the reference.  Teacher and student may be different variants but must share `image_size`.
+
+    The timestep pair of a sample is t = idx*c + c-1, t_next = (idx+k)*c + c-1 (c = T // num_ddim_timesteps, k =
+    num_ddim_timesteps // num_inference_steps, idx uniform in [0, num_ddim_timesteps - k)): t_next is the noisier one, as
+    written in the reference.  With the zero-SNR table alpha-bar[999] == 0, so idx = num_ddim_timesteps - k - 1 makes the
+    target x0 +-inf and the loss +inf while every gradient stays finite (Huber's gradient saturates) -- reproduced as is."""
+
+    def __init__(self, teacher_model: LowLightDiffusion, student_model: LowLightDiffusion, num_ddim_timesteps: int = 50,
+                 guidance_scale_range: Tuple[float, float] = (3.0, 15.0)):
+        super().__init__()
+        if teacher_model.image_size != student_model.image_size:
+            raise ValueError(f"teacher and student must share image_size (got {teacher_model.image_size} and "
+                             f"{student_model.image_size}): both denoise the same x_t")
+        self.teacher = teacher_model
+        self.teacher.eval()
+        self.teacher.requires_grad_(False)
+        self.student = student_model
+        self.num_ddim_timesteps = num_ddim_timesteps
+        self.guidance_scale_range = guidance_scale_range
+        self.ema_student = copy.deepcopy(student_model)  # own parameters, own engine context (built lazily)
+        self.ema_student.eval()
+        self.ema_student.requires_grad_(False)
+        object.__setattr__(self, "_ema_native", None)   # llie_ema* over (ema_student, student) parameters
+        object.__setattr__(self, "_ema_layout", None)
+
+    def __getstate__(self):
+        st = dict(self.__dict__)
+        st["_ema_native"], st["_ema_layout"] = None, None
+        return st
+
+    def __del__(self):
+        try:
+            self._release_ema()
+        except Exception:  # noqa: BLE001
+            pass
+
+    # ------------------------------------------------------------------ timestep pairs (:344-355)
+    def timestep_pairs(self, idx: torch.Tensor, num_inference_steps: int = 4) -> Tuple[torch.Tensor, torch.Tensor]:
+        """idx -> (t, t_next) on idx's device."""
+        c = self.teacher.scheduler.config.num_train_timesteps // self.num_ddim_timesteps
+        k = self.num_ddim_timesteps // num_inference_steps
+        return idx * c + c - 1, (idx + k) * c + c - 1
+
+    def _draws(self, normal_light: torch.Tensor, num_inference_steps: int, noise: Optional[torch.Tensor],
+               idx: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
+        b, dev = normal_light.shape[0], normal_light.device
+        k = self.num_ddim_timesteps // num_inference_steps
+        if k < 1 or self.num_ddim_timesteps - k < 1:
+            raise ValueError(f"num_inference_steps={num_inference_steps} leaves no timestep pair for "
+                             f"num_ddim_timesteps={self.num_ddim_timesteps}")
+        # the reference's draw order on the device generator: noise first, then idx (:337-349)
+        noise = torch.randn_like(normal_light) if noise is None else noise.to(device=dev, dtype=torch.float32)
+        if idx is None:
+            idx = torch.randint(0, self.num_ddim_timesteps - k, (b,), device=dev)
+        else:
+            idx = torch.as_tensor(idx)
+            if idx.device.type == "cpu" and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self.num_ddim_timesteps - k):
+                raise ValueError(f"idx must lie in [0, {self.num_ddim_timesteps - k})")
+            idx = idx.to(device=dev, dtype=torch.long)
+        if tuple(noise.shape) != tuple(normal_light.shape) or tuple(idx.shape) != (b,):
+            raise ValueError(f"noise must be shaped like normal_light and idx must be [{b}]")
+        return noise.contiguous(), idx.contiguous()
+
+    def _check_inputs(self, low_light: torch.Tensor, normal_light: torch.Tensor) -> None:
+        _require_hip(low_light, "LowLightLCMDistillation")
+        _require_hip(normal_light, "LowLightLCMDistillation")
+        s = self.student.image_size
+        if tuple(low_light.shape[1:]) != (3, s, s) or tuple(normal_light.shape) != tuple(low_light.shape):
+            raise ValueError(f"low_light / normal_light must be [B,3,{s},{s}]")
+
+    # ------------------------------------------------------------------ the loss (:325-393)
+    def consistency_distillation_loss(self, low_light: torch.Tensor, normal_light: torch.Tensor, num_inference_steps: int = 4, *,
+                                      noise: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Huber consistency loss (0-d device tensor with a grad_fn reaching the student's parameters).  `noise` / `idx`
+        (extensions) supply the two draws, e.g. CPU-generated ones for a run comparable with the CPU reference."""
+        self._check_inputs(low_light, normal_light)
+        noise, idx = self._draws(normal_light, num_inference_steps, noise, idx)
+        t, t_next = self.timestep_pairs(idx, num_inference_steps)
+        sched = self.teacher.scheduler
+        low = low_light.detach().float().contiguous()
+        x_t = sched.add_noise(normal_light, noise, t)
+        with torch.no_grad():
+            e_teacher = self.teacher.unet.forward_split(x_t, low, t)
+            x_next = consistency_target(sched, x_t, e_teacher, t, t_next)
+        e_student = self.student.unet.forward_split(x_t, low, t)
+        with torch.no_grad():
+            e_ema = self.ema_student.unet.forward_split(x_next, low, t_next)
+        if torch.is_grad_enabled() and e_student.requires_grad:
+            return _ConsistencyLossFn.apply(e_student, sched, x_t, x_next, e_ema, t, t_next)
+        return consistency_loss(sched, x_t, x_next, e_student, e_ema, t, t_next)[0]
+
+    # ------------------------------------------------------------------ EMA (:316-323)
+    def _ema_pairs(self):
+        ema, src = list(self.ema_student.parameters()), list(self.student.parameters())
+        if len(ema) != len(src) or any(a.shape != b.shape for a, b in zip(ema, src)):
+            raise ValueError("ema_student and student no longer have the same parameters")
+        for p in ema + src:
+            _require_hip(p, "update_ema")
+            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != ema[0].device:
+                raise ValueError("update_ema: fp32 contiguous parameters on one device")
+        return ema, src
+
+    def _release_ema(self) -> None:
+        if self.__dict__.get("_ema_native") is not None:
+            torch.cuda.synchronize()  # an update reading the table may still be in flight
+            N.lib().llie_ema_destroy(self._ema_native)
+            object.__setattr__(self, "_ema_native", None)
+
+    def _ema_handle(self):
+        ema, src = self._ema_pairs()
+        layout = (tuple(p.data_ptr() for p in ema), tuple(p.data_ptr() for p in src))
+        if self._ema_native is not None and layout == self._ema_layout:
+            return self._ema_native, ema[0].device
+        self._release_ema()
+        n = len(ema)
+        out = C.c_void_p()
+        with torch.cuda.device(ema[0].device):
+            N.check(N.lib().llie_ema_create((C.c_void_p * n)(*layout[0]), (C.c_void_p * n)(*layout[1]),
+                                            (C.c_int64 * n)(*[p.numel() for p in ema]), n, C.byref(out)), "update_ema")
+        object.__setattr__(self, "_ema_native", out)
+        object.__setattr__(self, "_ema_layout", layout)
+        return out, ema[0].device
+
+    @torch.no_grad()
+    def update_ema(self, decay: float = 0.95) -> None:
+        """ema = ema * decay + (1 - decay) * student over every parameter, one launch (llie_ema_update).  The EMA student's
+        engine weights follow at its next forward (the engine notices the changed content)."""
+        h, dev = self._ema_handle()
+        with torch.cuda.device(dev):
+            N.check(N.lib().llie_ema_update(h, float(decay), torch.cuda.current_stream(dev).cuda_stream), "update_ema")
 
 
 def normalize_image(x: torch.Tensor) -> torch.Tensor:

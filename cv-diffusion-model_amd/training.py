@@ -11,8 +11,10 @@
 `TrainStep`   -- `compute_loss -> backward -> gradient all-reduce -> clip -> AdamW -> EMA` without the autograd graph: the
                  engine's backward pass writes one flat gradient buffer and the optimiser reads it in place (no per-parameter
                  `.grad` views, no AccumulateGrad nodes).  Same numbers as the autograd path (tests/test_gpu_round4.py).
+`DistillStep` -- one step of consistency distillation (`LowLightLCMDistillation.consistency_distillation_loss -> backward ->
+                 AdamW -> update_ema`) the same way: three denoiser passes, the distillation kernels and one flat gradient buffer.
 
-There is no CPU fallback: both need the HIP library and parameters on a HIP device.
+There is no CPU fallback: all three need the HIP library and parameters on a HIP device.
 """
 import ctypes as C
 from typing import Iterable, List, Optional
@@ -187,6 +189,28 @@ class FusedAdamW(torch.optim.Optimizer):
             self._ema.copy_(ema.to(self._dev))
 
 
+def _engine_order(unet, optimizer: FusedAdamW, who: str) -> List[int]:
+    """Engine (llie_param_info) index of each of the optimiser's parameters; they must be exactly `unet`'s."""
+    index = {id(p): i for i, (_, p) in enumerate(unet._ordered_params())}
+    have = optimizer.param_groups[0]["params"]
+    if len(index) != len(have) or any(id(p) not in index for p in have):
+        raise ValueError(f"{who}: the optimiser must hold exactly model.unet's parameters (FusedAdamW(model.parameters(), ...))")
+    return [index[id(p)] for p in have]
+
+
+def _train_buffers(step, h: N.Handle, batch: int, dev: torch.device) -> int:
+    """Grow `step._ws` (train workspace) and allocate `step._flat` (flat gradients) / `step._offsets` (the optimiser's order)
+    for handle `h`; returns the workspace bytes the engine needs."""
+    nbytes = h.train_workspace_bytes(batch)
+    if step._ws is None or step._ws.numel() < nbytes or step._ws.device != dev:
+        step._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if step._flat is None or step._flat.numel() != h.grad_numel() or step._flat.device != dev:
+        step._flat = torch.empty(h.grad_numel(), dtype=torch.float32, device=dev)
+        offs = h.grad_offsets()
+        step._offsets = [offs[i] for i in step._order]
+    return nbytes
+
+
 class TrainStep:
     """One optimisation step of the reference trainer (trainer.py:281-324) on the engine, without autograd:
     q-sample (low_light_diffusion.py:140-160) -> llie_unet_train_forward -> loss and d(loss)/d(eps) -> llie_unet_backward into a
@@ -197,12 +221,7 @@ class TrainStep:
         if loss_type not in ("mse", "huber", "l1"):
             raise ValueError(f"Unknown loss type: {loss_type}")
         self.model, self.opt, self.loss_type, self.velocity, self.group = model, optimizer, loss_type, use_velocity_target, group
-        unet = model.unet
-        index = {id(p): i for i, (_, p) in enumerate(unet._ordered_params())}  # engine (llie_param_info) order
-        have = optimizer.param_groups[0]["params"]
-        if len(index) != len(have) or any(id(p) not in index for p in have):
-            raise ValueError("TrainStep: the optimiser must hold exactly model.unet's parameters (FusedAdamW(model.parameters(), ...))")
-        self._order = [index[id(p)] for p in have]
+        self._order = _engine_order(model.unet, optimizer, "TrainStep")
         if use_velocity_target and getattr(model.scheduler.config, "prediction_type", "epsilon") != "v_prediction":
             raise ValueError("use_velocity_target needs a scheduler with prediction_type='v_prediction'")
         self._flat = None
@@ -226,13 +245,7 @@ class TrainStep:
         cond = low_light.detach().float().contiguous()
         t = timesteps.to(device=dev, dtype=torch.long).contiguous()
         h = unet._handle(resolve_compute_dtype(unet.compute_dtype))
-        nbytes = h.train_workspace_bytes(b)
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != dev:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        if self._flat is None or self._flat.numel() != h.grad_numel() or self._flat.device != dev:
-            self._flat = torch.empty(h.grad_numel(), dtype=torch.float32, device=dev)
-            offs = h.grad_offsets()
-            self._offsets = [offs[i] for i in self._order]
+        nbytes = _train_buffers(self, h, b, dev)
         eps = torch.empty(b, unet.config.out_channels, s, s, dtype=torch.float32, device=dev)
         L = N.lib()
         with torch.cuda.device(dev):
@@ -258,4 +271,65 @@ class TrainStep:
             dist.all_reduce(self._flat, group=self.group)  # one collective over all gradients; the average rides on grad_scale
             scale = 1.0 / dist.get_world_size(self.group)
         self.opt.step_flat(self._flat, self._offsets, grad_scale=scale)
+        return loss
+
+
+class DistillStep:
+    """One optimisation step of consistency distillation (LowLightLCMDistillation, low_light_diffusion.py:325-393, then
+    AdamW and update_ema) without autograd:
+      draws (noise, idx) -> add_noise -> teacher forward at t -> llie_consistency_target (x_next) -> student
+      llie_unet_train_forward at t -> EMA-target forward at t_next -> llie_consistency_loss (loss, d/d eps) ->
+      llie_unet_backward into a flat buffer -> FusedAdamW.step_flat -> llie_ema_update.
+    Same numbers as `loss = distill.consistency_distillation_loss(...); loss.backward(); optimizer.step();
+    distill.update_ema(ema_decay)`.  The EMA student's engine weights are reloaded at its next forward (content check on the
+    device).  Returns the loss (device scalar).  fp16 students are refused: the step has no loss scaling (the autograd path
+    with GradScaler has); fp32 and bf16 run."""
+
+    def __init__(self, distill, optimizer: FusedAdamW, ema_decay: float = 0.95):
+        if not (0 <= ema_decay <= 1):
+            raise ValueError("ema_decay must be in [0, 1]")
+        if distill.student.compute_dtype in ("fp16", "float16", torch.float16):
+            raise ValueError("DistillStep: fp16 students need loss scaling, which this step does not do; use the autograd "
+                             "path (consistency_distillation_loss + GradScaler) or bf16")
+        self.distill, self.opt, self.ema_decay = distill, optimizer, ema_decay
+        self._order = _engine_order(distill.student.unet, optimizer, "DistillStep")
+        self._flat = None
+        self._ws = None
+
+    @torch.no_grad()
+    def __call__(self, low_light: torch.Tensor, normal_light: torch.Tensor, num_inference_steps: int = 4, *,
+                 noise: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+        from .pipeline import consistency_loss, consistency_target
+        from .unet import resolve_compute_dtype
+        d = self.distill
+        d._check_inputs(low_light, normal_light)
+        unet = d.student.unet
+        dtype = resolve_compute_dtype(unet.compute_dtype)
+        if dtype == N.LLIE_F16:
+            raise ValueError("DistillStep: fp16 students need loss scaling, which this step does not do; use the autograd "
+                             "path (consistency_distillation_loss + GradScaler) or bf16")
+        b, dev = low_light.shape[0], low_light.device
+        noise, idx = d._draws(normal_light, num_inference_steps, noise, idx)
+        t, t_next = d.timestep_pairs(idx, num_inference_steps)
+        sched = d.teacher.scheduler
+        low = low_light.detach().float().contiguous()
+        x_t = sched.add_noise(normal_light, noise, t)
+        e_teacher = d.teacher.unet.forward_split(x_t, low, t)
+        x_next = consistency_target(sched, x_t, e_teacher, t, t_next)
+        h = unet._handle(dtype)
+        nbytes = _train_buffers(self, h, b, dev)
+        s = unet.config.image_size
+        e_student = torch.empty(b, unet.config.out_channels, s, s, dtype=torch.float32, device=dev)
+        L = N.lib()
+        with torch.cuda.device(dev):
+            N.check(L.llie_unet_train_forward(h.h, x_t.data_ptr(), low.data_ptr(), t.data_ptr(), e_student.data_ptr(), b,
+                                              self._ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream),
+                    "EfficientUNet.forward (training)")
+        e_ema = d.ema_student.unet.forward_split(x_next, low, t_next)
+        loss, d_eps = consistency_loss(sched, x_t, x_next, e_student, e_ema, t, t_next)
+        with torch.cuda.device(dev):
+            N.check(L.llie_unet_backward(h.h, d_eps.data_ptr(), self._flat.data_ptr(), b, self._ws.data_ptr(), nbytes,
+                                         torch.cuda.current_stream(dev).cuda_stream), "EfficientUNet.backward")
+        self.opt.step_flat(self._flat, self._offsets)
+        d.update_ema(self.ema_decay)
         return loss

@@ -193,6 +193,33 @@ void llie_optimizer_destroy(llie_optimizer* opt);
 int64_t llie_optimizer_numel(const llie_optimizer* opt);
 int llie_optimizer_step(llie_optimizer* opt, const float* grad_base, const llie_opt_hyper* hyper, float* stats3, llie_stream stream);
 
+/* ---- Consistency distillation (LowLightLCMDistillation.consistency_distillation_loss / update_ema,
+ * low_light_diffusion.py:284-408).  Tensors are device fp32 NCHW [batch, 3, S, S] (per_sample = 3*S*S elements per
+ * sample); `t` / `t_next` are device int64 [batch]; `alphas_cumprod` is the teacher scheduler's device fp32 table of
+ * `table_len` entries.  The reference's operation order is kept (no fused multiply-adds).  A timestep outside
+ * [0, table_len) is never used as an index: that sample's outputs are NaN (the call is asynchronous and cannot raise).
+ *   llie_consistency_target:  x_next = sqrt(a_n) x0 + sqrt(1 - a_n) e_teacher,  x0 = (x_t - sqrt(1 - a_t) e_teacher) / sqrt(a_t)
+ *   llie_consistency_loss:    s0 = (x_t - sqrt(1 - a_t) e_student) / sqrt(a_t),  g0 = (x_next - sqrt(1 - a_n) e_ema) / sqrt(a_n);
+ *                             loss_out (device, 1 float) = F.huber_loss(s0, g0) (delta 1, mean);  d_student (like x_t) =
+ *                             d(loss)/d(e_student) = clamp(s0 - g0, -1, 1) / n * (-sqrt(1 - a_t) / sqrt(a_t)).  The loss is a
+ *                             fixed-order sum in double, bitwise reproducible; an inf / NaN term makes it inf / NaN (with
+ *                             a zero-SNR table, t_next = T-1 has a_n = 0: g0 = +-inf, loss +inf, d_student finite).
+ *                             `scratch` (device) must hold ceil(batch * per_sample / 1024) doubles.
+ * a_t = alphas_cumprod[t[b]], a_n = alphas_cumprod[t_next[b]]. */
+int llie_consistency_target(const float* x_t, const float* e_teacher, const int64_t* t, const int64_t* t_next,
+                            const float* alphas_cumprod, int table_len, float* x_next, int batch, int64_t per_sample,
+                            llie_stream stream);
+int llie_consistency_loss(const float* x_t, const float* x_next, const float* e_student, const float* e_ema,
+                          const int64_t* t, const int64_t* t_next, const float* alphas_cumprod, int table_len,
+                          float* d_student, float* loss_out, int batch, int64_t per_sample, void* scratch,
+                          int64_t scratch_bytes, llie_stream stream);
+/* EMA of a parameter set (update_ema, :316-323): ema[i] = ema[i] * decay + (1 - decay) * param[i] over `count` tensors in
+ * one launch.  The table (device pointers, all fp32 and valid for the object's life) is built once by create. */
+typedef struct llie_ema llie_ema;
+int llie_ema_create(float* const* ema, const float* const* params, const int64_t* numel, int count, llie_ema** out);
+int llie_ema_update(llie_ema* ema, double decay, llie_stream stream);
+void llie_ema_destroy(llie_ema* ema);
+
 /* LCMScheduler.step (lcm_scheduler.py:176-253), elementwise on fp32 [n]:
  *   x0 = (sample - sqrt_beta_t*model_output)/sqrt_alpha_t      (epsilon)
  *   prev = is_last ? x0 : sqrt_alpha_prev*x0 + sqrt_beta_prev*noise
