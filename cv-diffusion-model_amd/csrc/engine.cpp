@@ -2351,6 +2351,7 @@ struct llie_optimizer {
   OptTensor* tensors = nullptr;
   OptChunk* chunks = nullptr;
   double* partial = nullptr;
+  float* amp_coef = nullptr;  // [5]: the AMP step's stats and bias corrections, from its clip kernel to its update kernel
   int count = 0, nchunks = 0;
   int64_t numel = 0;
 };
@@ -2379,6 +2380,7 @@ int llie_optimizer_create(const llie_opt_tensor* tensors, int count, llie_optimi
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&o->tensors), tt.size() * sizeof(OptTensor));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&o->chunks), cc.size() * sizeof(OptChunk));
   if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&o->partial), cc.size() * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&o->amp_coef), 5 * sizeof(float));
   if (e == hipSuccess) e = hipMemcpy(o->tensors, tt.data(), tt.size() * sizeof(OptTensor), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(o->chunks, cc.data(), cc.size() * sizeof(OptChunk), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
@@ -2395,6 +2397,7 @@ void llie_optimizer_destroy(llie_optimizer* o) {
   if (o->tensors) (void)hipFree(o->tensors);
   if (o->chunks) (void)hipFree(o->chunks);
   if (o->partial) (void)hipFree(o->partial);
+  if (o->amp_coef) (void)hipFree(o->amp_coef);
   delete o;
 }
 
@@ -2411,6 +2414,23 @@ int llie_optimizer_step(llie_optimizer* o, const float* grad_base, const llie_op
   hipError_t e = launch_optimizer_step(a, reinterpret_cast<hipStream_t>(stream));
   if (e == hipErrorInvalidValue) { set_err("optimizer_step: hyper-parameters outside their ranges (lr, eps, weight_decay >= 0; 0 <= beta < 1; ema_decay <= 1; step >= 1)"); return LLIE_ERR_ARG; }
   if (e != hipSuccess) { set_err("optimizer_step: %s", hipGetErrorString(e)); return (int)e; }
+  return LLIE_OK;
+}
+
+int llie_optimizer_step_amp(llie_optimizer* o, const float* grad_base, const llie_opt_hyper* h, const llie_amp_state* state,
+                            const llie_amp_config* cfg, float* stats3, llie_stream stream) {
+  if (!o || !grad_base || !h || !state || !cfg || !stats3 || !state->scale || !state->growth_tracker || !state->step) return LLIE_ERR_ARG;
+  OptStepArgs a{};
+  a.tensors = o->tensors; a.chunks = o->chunks; a.nchunks = o->nchunks;
+  a.gbase = grad_base; a.partial = o->partial; a.stats = stats3;
+  a.lr = h->lr; a.beta1 = h->beta1; a.beta2 = h->beta2; a.eps = h->eps; a.weight_decay = h->weight_decay;
+  a.max_grad_norm = h->max_grad_norm; a.ema_decay = h->ema_decay; a.grad_scale = h->grad_scale;
+  OptAmpArgs amp{};
+  amp.scale = state->scale; amp.growth_tracker = state->growth_tracker; amp.step = state->step;
+  amp.growth_factor = cfg->growth_factor; amp.backoff_factor = cfg->backoff_factor; amp.growth_interval = cfg->growth_interval;
+  hipError_t e = launch_optimizer_step_amp(a, amp, o->amp_coef, reinterpret_cast<hipStream_t>(stream));
+  if (e == hipErrorInvalidValue) { set_err("optimizer_step_amp: hyper-parameters outside their ranges (lr, eps, weight_decay >= 0; 0 <= beta < 1; ema_decay <= 1)"); return LLIE_ERR_ARG; }
+  if (e != hipSuccess) { set_err("optimizer_step_amp: %s", hipGetErrorString(e)); return (int)e; }
   return LLIE_OK;
 }
 

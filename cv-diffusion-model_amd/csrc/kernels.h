@@ -499,6 +499,16 @@ struct OptStepArgs {
   int skip_nonfinite;    // leave everything untouched when the norm is inf / NaN (GradScaler.step)
 };
 hipError_t launch_optimizer_step(const OptStepArgs& a, hipStream_t s);
+// AMP form (loss-scaler state in device memory, torch.amp.GradScaler's semantics): a.step and a.skip_nonfinite are unused,
+// the step count is *step (updates taken so far), a step is skipped exactly when some gradient is inf / NaN
+struct OptAmpArgs {
+  float* scale;            // device: loss scale, read for the unscale, then updated (_amp_update_scale_)
+  int* growth_tracker;     // device: steps since the last backoff / growth
+  int* step;               // device: AdamW step count, incremented by a taken step
+  double growth_factor, backoff_factor;
+  int growth_interval;
+};
+hipError_t launch_optimizer_step_amp(const OptStepArgs& a, const OptAmpArgs& amp, float* coef /* device [5] */, hipStream_t s);
 
 // (10) consistency distillation (distill.hip): per-sample alpha-bar from a device table, fp32 [batch, per] tensors
 constexpr int kDistillLossPerWG = 1024;  // elements per workgroup of the loss pass (one double partial each)

@@ -24,27 +24,29 @@ constexpr int kOptThreads = 256;
 
 __device__ __forceinline__ bool opt_aligned16(const void* a) { return (reinterpret_cast<uintptr_t>(a) & 15) == 0; }
 
-// sum of squares of (grad * gscale) per chunk -> partial[chunk]
-__global__ void __launch_bounds__(kOptThreads) opt_sumsq_kernel(const OptTensor* __restrict__ tensors, const OptChunk* __restrict__ chunks,
-                                                               const float* __restrict__ gbase, double* __restrict__ partial) {
+// sum of squares of the gradients per chunk -> partial[chunk].  Per-thread sums in Acc: float for the plain step; double for
+// the AMP step, where a squared fp32 cannot overflow, so the sum is non-finite exactly when some gradient element is inf / NaN
+template <typename Acc>
+__device__ __forceinline__ void opt_sumsq(const OptTensor* __restrict__ tensors, const OptChunk* __restrict__ chunks,
+                                          const float* __restrict__ gbase, double* __restrict__ partial) {
   const OptChunk ch = chunks[blockIdx.x];
   const OptTensor t = tensors[ch.tensor];
   const float* g = gbase + t.goff + ch.first;
   const long long left = t.n - ch.first;
   const int n = left < kOptChunk ? (int)left : kOptChunk;
-  float acc = 0.f;
+  Acc acc = 0;
   if (opt_aligned16(g)) {
     const int nv = n >> 2;
     for (int i = threadIdx.x; i < nv; i += kOptThreads) {
       const f32x4 v = reinterpret_cast<const f32x4*>(g)[i];
-      acc += v[0] * v[0];
-      acc += v[1] * v[1];
-      acc += v[2] * v[2];
-      acc += v[3] * v[3];
+      acc += (Acc)v[0] * (Acc)v[0];
+      acc += (Acc)v[1] * (Acc)v[1];
+      acc += (Acc)v[2] * (Acc)v[2];
+      acc += (Acc)v[3] * (Acc)v[3];
     }
-    for (int i = (nv << 2) + threadIdx.x; i < n; i += kOptThreads) acc += g[i] * g[i];
+    for (int i = (nv << 2) + threadIdx.x; i < n; i += kOptThreads) acc += (Acc)g[i] * (Acc)g[i];
   } else {
-    for (int i = threadIdx.x; i < n; i += kOptThreads) acc += g[i] * g[i];
+    for (int i = threadIdx.x; i < n; i += kOptThreads) acc += (Acc)g[i] * (Acc)g[i];
   }
   __shared__ double red[kOptThreads];
   red[threadIdx.x] = (double)acc;
@@ -54,6 +56,28 @@ __global__ void __launch_bounds__(kOptThreads) opt_sumsq_kernel(const OptTensor*
     wg_barrier();
   }
   if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+__global__ void __launch_bounds__(kOptThreads) opt_sumsq_kernel(const OptTensor* __restrict__ tensors, const OptChunk* __restrict__ chunks,
+                                                               const float* __restrict__ gbase, double* __restrict__ partial) {
+  opt_sumsq<float>(tensors, chunks, gbase, partial);
+}
+
+__global__ void __launch_bounds__(kOptThreads) opt_sumsq_amp_kernel(const OptTensor* __restrict__ tensors, const OptChunk* __restrict__ chunks,
+                                                                   const float* __restrict__ gbase, double* __restrict__ partial) {
+  opt_sumsq<double>(tensors, chunks, gbase, partial);
+}
+
+// fixed-order sum of the chunk partials by one workgroup -> red[0] (opt_clip_kernel keeps its own inline copy: unchanged code)
+__device__ __forceinline__ void opt_sum_partials(const double* __restrict__ partial, int nchunks, double* red) {
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nchunks; i += kOptThreads) acc += partial[i];
+  red[threadIdx.x] = acc;
+  wg_barrier();
+  for (int o = kOptThreads / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    wg_barrier();
+  }
 }
 
 // stats[0] = ||gscale * g||, stats[1] = factor applied to every gradient = gscale * clip coefficient, stats[2] = 1 if the step
@@ -83,6 +107,55 @@ __global__ void __launch_bounds__(kOptThreads) opt_clip_kernel(const double* __r
   }
 }
 
+// The AMP form (torch.amp.GradScaler around the step, with the loss scaler's state in device memory):
+//   inv = 1 / scale as scale.double().reciprocal().float(); found_inf = some gradient element is inf / NaN (the double sum
+//   of squares is non-finite); norm = ||inv * gscale * g|| formed in double before rounding; factor = inv * gscale * clip
+//   coefficient; a taken step advances the AdamW step count and forms its bias corrections in double from it; then
+//   _amp_update_scale_ (aten/src/ATen/native/cuda/AmpKernels.cu).
+// stats / coef[0..2] as opt_clip_kernel's stats; coef[3] = lr / (1 - beta1^t), coef[4] = sqrt(1 - beta2^t) for the update kernel.
+__global__ void __launch_bounds__(kOptThreads) opt_clip_amp_kernel(const double* __restrict__ partial, int nchunks, float gscale, float max_norm,
+                                                                  OptAmpArgs amp, double lr, double beta1, double beta2,
+                                                                  float* __restrict__ stats, float* __restrict__ coef) {
+  __shared__ double red[kOptThreads];
+  opt_sum_partials(partial, nchunks, red);
+  if (threadIdx.x == 0) {
+    const double sum = red[0];
+    const float scale = *amp.scale;
+    const float inv = (float)(1.0 / (double)scale);
+    const bool found_inf = !(sum <= 1.7976931348623157e308);  // inf or NaN
+    const float norm = (float)(sqrt(sum) * (double)inv * fabs((double)gscale));
+    float clip = 1.f;
+    if (max_norm > 0.f) {
+      clip = max_norm / (norm + 1e-6f);
+      clip = clip > 1.f ? 1.f : clip;
+    }
+    const float gf = (inv * gscale) * clip;
+    const float skip = found_inf ? 1.f : 0.f;
+    stats[0] = coef[0] = norm;
+    stats[1] = coef[1] = gf;
+    stats[2] = coef[2] = skip;
+    if (!found_inf) {
+      const int t = *amp.step + 1;
+      *amp.step = t;
+      coef[3] = (float)(lr / (1.0 - pow(beta1, (double)t)));
+      coef[4] = (float)sqrt(1.0 - pow(beta2, (double)t));
+    }
+    if (found_inf) {
+      *amp.scale = (float)((double)scale * amp.backoff_factor);
+      *amp.growth_tracker = 0;
+    } else {
+      const int successful = *amp.growth_tracker + 1;
+      if (successful == amp.growth_interval) {
+        const float grown = (float)((double)scale * amp.growth_factor);
+        if (isfinite(grown)) *amp.scale = grown;
+        *amp.growth_tracker = 0;
+      } else {
+        *amp.growth_tracker = successful;
+      }
+    }
+  }
+}
+
 struct OptHyper {
   float decay_mul;   // 1 - lr * weight_decay (formed in double, as Python does for torch)
   float one_m_b1;    // 1 - beta1
@@ -95,19 +168,51 @@ struct OptHyper {
   float one_m_ema;
 };
 
-__device__ __forceinline__ void opt_update(float g, float& p, float& m, float& v, float& e, const OptHyper& h, float gf, bool has_ema) {
+__device__ __forceinline__ void opt_update(float g, float& p, float& m, float& v, float& e, const OptHyper& h, float step_size, float bc2_sqrt,
+                                           float gf, bool has_ema) {
   g *= gf;
   p *= h.decay_mul;
   m = m + (g - m) * h.one_m_b1;
   v = v * h.beta2 + (h.one_m_b2 * g) * g;
-  const float denom = __fsqrt_rn(v) / h.bc2_sqrt + h.eps;
-  p = p + (m / denom) * (-h.step_size);
+  const float denom = __fsqrt_rn(v) / bc2_sqrt + h.eps;
+  p = p + (m / denom) * (-step_size);
   if (has_ema) e = e * h.ema_decay + p * h.one_m_ema;
 }
 
+// shadow = decay * shadow + (1 - decay) * param over one chunk: the EMA update of an AMP step the loss scaler skipped
+__device__ __forceinline__ void opt_ema_only(const OptTensor* __restrict__ tensors, const OptChunk* __restrict__ chunks, const OptHyper& h) {
+  const OptChunk ch = chunks[blockIdx.x];
+  const OptTensor t = tensors[ch.tensor];
+  if (t.ema == nullptr || h.ema_decay < 0.f) return;
+  const float* p = t.p + ch.first;
+  float* e = t.ema + ch.first;
+  const long long left = t.n - ch.first;
+  const int n = left < kOptChunk ? (int)left : kOptChunk;
+  int done = 0;
+  if (opt_aligned16(p) && opt_aligned16(e)) {
+    const int nv = n >> 2;
+    for (int i = threadIdx.x; i < nv; i += kOptThreads) {
+      const f32x4 pv = reinterpret_cast<const f32x4*>(p)[i];
+      f32x4 ev = reinterpret_cast<f32x4*>(e)[i];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) ev[k] = ev[k] * h.ema_decay + pv[k] * h.one_m_ema;
+      reinterpret_cast<f32x4*>(e)[i] = ev;
+    }
+    done = nv << 2;
+  }
+  for (int i = done + threadIdx.x; i < n; i += kOptThreads) e[i] = e[i] * h.ema_decay + p[i] * h.one_m_ema;
+}
+
+// kAmp: `stats` is the optimiser's coefficient slot written by opt_clip_amp_kernel (the bias corrections come from it too),
+// and a skipped step still moves the EMA shadows (the reference trainer calls ema.update whether or not GradScaler stepped)
+template <bool kAmp>
 __global__ void __launch_bounds__(kOptThreads) opt_adamw_kernel(const OptTensor* __restrict__ tensors, const OptChunk* __restrict__ chunks,
                                                                const float* __restrict__ gbase, const float* __restrict__ stats, const OptHyper h) {
-  if (stats[2] != 0.f) return;  // skipped step: nothing moves
+  if (stats[2] != 0.f) {  // skipped step: nothing moves
+    if constexpr (kAmp) opt_ema_only(tensors, chunks, h);
+    return;
+  }
+  const float step_size = kAmp ? stats[3] : h.step_size, bc2_sqrt = kAmp ? stats[4] : h.bc2_sqrt;
   const float gf = stats[1];
   const OptChunk ch = chunks[blockIdx.x];
   const OptTensor t = tensors[ch.tensor];
@@ -129,7 +234,7 @@ __global__ void __launch_bounds__(kOptThreads) opt_adamw_kernel(const OptTensor*
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         float pk = pv[k], mk = mv[k], vk = vv[k], ek = ev[k];
-        opt_update(gv[k], pk, mk, vk, ek, h, gf, has_ema);
+        opt_update(gv[k], pk, mk, vk, ek, h, step_size, bc2_sqrt, gf, has_ema);
         pv[k] = pk; mv[k] = mk; vv[k] = vk; ev[k] = ek;
       }
       reinterpret_cast<f32x4*>(p)[i] = pv;
@@ -141,25 +246,20 @@ __global__ void __launch_bounds__(kOptThreads) opt_adamw_kernel(const OptTensor*
   }
   for (int i = done + threadIdx.x; i < n; i += kOptThreads) {
     float pk = p[i], mk = m[i], vk = v[i], ek = has_ema ? e[i] : 0.f;
-    opt_update(g[i], pk, mk, vk, ek, h, gf, has_ema);
+    opt_update(g[i], pk, mk, vk, ek, h, step_size, bc2_sqrt, gf, has_ema);
     p[i] = pk; m[i] = mk; v[i] = vk;
     if (has_ema) e[i] = ek;
   }
 }
 
-hipError_t launch_optimizer_step(const OptStepArgs& a, hipStream_t s) {
-  if (!a.tensors || !a.chunks || !a.gbase || !a.partial || !a.stats || a.nchunks <= 0 || a.step < 1) return hipErrorInvalidValue;
-  if (!(a.lr >= 0.0) || !(a.beta1 >= 0.0 && a.beta1 < 1.0) || !(a.beta2 >= 0.0 && a.beta2 < 1.0) || !(a.eps >= 0.0) || !(a.weight_decay >= 0.0) ||
-      !(a.ema_decay <= 1.0))
-    return hipErrorInvalidValue;
-  note_kernel("opt_sumsq_kernel");
-  hipLaunchKernelGGL(opt_sumsq_kernel, dim3(a.nchunks), dim3(kOptThreads), 0, s, a.tensors, a.chunks, a.gbase, a.partial);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-  note_kernel("opt_clip_kernel");
-  hipLaunchKernelGGL(opt_clip_kernel, dim3(1), dim3(kOptThreads), 0, s, a.partial, a.nchunks, (float)a.grad_scale, (float)a.max_grad_norm, a.skip_nonfinite, a.stats);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+static bool opt_hyper_ok(const OptStepArgs& a) {
+  return a.tensors && a.chunks && a.gbase && a.partial && a.stats && a.nchunks > 0 && a.lr >= 0.0 && a.beta1 >= 0.0 && a.beta1 < 1.0 &&
+         a.beta2 >= 0.0 && a.beta2 < 1.0 && a.eps >= 0.0 && a.weight_decay >= 0.0 && a.ema_decay <= 1.0;
+}
+
+static OptHyper opt_hyper(const OptStepArgs& a, double step) {
   OptHyper h;
-  const double bc1 = 1.0 - pow(a.beta1, (double)a.step), bc2 = 1.0 - pow(a.beta2, (double)a.step);
+  const double bc1 = 1.0 - pow(a.beta1, step), bc2 = 1.0 - pow(a.beta2, step);
   h.decay_mul = (float)(1.0 - a.lr * a.weight_decay);
   h.one_m_b1 = (float)(1.0 - a.beta1);
   h.beta2 = (float)a.beta2;
@@ -169,8 +269,35 @@ hipError_t launch_optimizer_step(const OptStepArgs& a, hipStream_t s) {
   h.eps = (float)a.eps;
   h.ema_decay = (float)a.ema_decay;
   h.one_m_ema = (float)(1.0 - a.ema_decay);
+  return h;
+}
+
+hipError_t launch_optimizer_step(const OptStepArgs& a, hipStream_t s) {
+  if (!opt_hyper_ok(a) || a.step < 1) return hipErrorInvalidValue;
+  note_kernel("opt_sumsq_kernel");
+  hipLaunchKernelGGL(opt_sumsq_kernel, dim3(a.nchunks), dim3(kOptThreads), 0, s, a.tensors, a.chunks, a.gbase, a.partial);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  note_kernel("opt_clip_kernel");
+  hipLaunchKernelGGL(opt_clip_kernel, dim3(1), dim3(kOptThreads), 0, s, a.partial, a.nchunks, (float)a.grad_scale, (float)a.max_grad_norm, a.skip_nonfinite, a.stats);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  const OptHyper h = opt_hyper(a, (double)a.step);
   note_kernel("opt_adamw_kernel");
-  hipLaunchKernelGGL(opt_adamw_kernel, dim3(a.nchunks), dim3(kOptThreads), 0, s, a.tensors, a.chunks, a.gbase, a.stats, h);
+  hipLaunchKernelGGL(opt_adamw_kernel<false>, dim3(a.nchunks), dim3(kOptThreads), 0, s, a.tensors, a.chunks, a.gbase, a.stats, h);
+  return hipGetLastError();
+}
+
+hipError_t launch_optimizer_step_amp(const OptStepArgs& a, const OptAmpArgs& amp, float* coef, hipStream_t s) {
+  if (!opt_hyper_ok(a) || !amp.scale || !amp.growth_tracker || !amp.step || !coef) return hipErrorInvalidValue;
+  note_kernel("opt_sumsq_amp_kernel");
+  hipLaunchKernelGGL(opt_sumsq_amp_kernel, dim3(a.nchunks), dim3(kOptThreads), 0, s, a.tensors, a.chunks, a.gbase, a.partial);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  note_kernel("opt_clip_amp_kernel");
+  hipLaunchKernelGGL(opt_clip_amp_kernel, dim3(1), dim3(kOptThreads), 0, s, a.partial, a.nchunks, (float)a.grad_scale, (float)a.max_grad_norm,
+                     amp, a.lr, a.beta1, a.beta2, a.stats, coef);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  const OptHyper h = opt_hyper(a, 1.0);  // step_size / bc2_sqrt are replaced by the device's coef[3], coef[4]
+  note_kernel("opt_adamw_kernel<amp>");
+  hipLaunchKernelGGL(opt_adamw_kernel<true>, dim3(a.nchunks), dim3(kOptThreads), 0, s, a.tensors, a.chunks, a.gbase, coef, h);
   return hipGetLastError();
 }
 

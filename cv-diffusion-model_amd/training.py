@@ -11,6 +11,10 @@
 `TrainStep`   -- `compute_loss -> backward -> gradient all-reduce -> clip -> AdamW -> EMA` without the autograd graph: the
                  engine's backward pass writes one flat gradient buffer and the optimiser reads it in place (no per-parameter
                  `.grad` views, no AccumulateGrad nodes).  Same numbers as the autograd path (tests/test_gpu_round4.py).
+`FusedGradScaler` -- `torch.amp.GradScaler` for the fused step: its state (scale, growth tracker) lives on the device and the
+                 optimiser's launches read and update it (llie_optimizer_step_amp), so `optimizer.step(grad_scaler=scaler)`
+                 replaces `scaler.unscale_ -> clip_grad_norm_ -> scaler.step -> scaler.update -> ema.update` (the reference's
+                 fp16 loop, trainer.py:285-322) with no host synchronisation.
 `DistillStep` -- one step of consistency distillation (`LowLightLCMDistillation.consistency_distillation_loss -> backward ->
                  AdamW -> update_ema`) the same way: three denoiser passes, the distillation kernels and one flat gradient buffer.
 
@@ -23,6 +27,81 @@ import torch
 import torch.distributed as dist
 
 from . import _native as N
+
+
+class FusedGradScaler:
+    """Dynamic loss scaling with torch.amp.GradScaler's semantics and checkpoint layout, for FusedAdamW / TrainStep /
+    DistillStep.  The scale (fp32) and growth tracker (int32) are device scalars, created on first use on that device; the
+    optimiser's step unscales, checks for inf / NaN, skips and updates them on the device (include/llie.h,
+    llie_optimizer_step_amp).  `enabled=False` and several optimisers per scaler are not supported."""
+
+    def __init__(self, init_scale: float = 2.0 ** 16, growth_factor: float = 2.0, backoff_factor: float = 0.5,
+                 growth_interval: int = 2000):
+        if not growth_factor > 1.0:
+            raise ValueError("The growth factor must be > 1.0.")
+        if not backoff_factor < 1.0:
+            raise ValueError("The backoff factor must be < 1.0.")
+        self._init_scale = init_scale
+        self._growth_factor = growth_factor
+        self._backoff_factor = backoff_factor
+        self._growth_interval = growth_interval
+        self._init_growth_tracker = 0
+        self._scale: Optional[torch.Tensor] = None
+        self._growth_tracker: Optional[torch.Tensor] = None
+
+    def _device_scale(self, dev: torch.device) -> torch.Tensor:
+        """The scale tensor on `dev`, created there on first use (as GradScaler._lazy_init_scale_growth_tracker: no sync)."""
+        if self._scale is None:
+            self._scale = torch.full((), self._init_scale, dtype=torch.float32, device=dev)
+            self._growth_tracker = torch.full((), self._init_growth_tracker, dtype=torch.int32, device=dev)
+        elif self._scale.device != dev:
+            raise ValueError(f"FusedGradScaler: state lives on {self._scale.device}, used on {dev}")
+        return self._scale
+
+    def _native(self, dev: torch.device, step: torch.Tensor):
+        scale = self._device_scale(dev)
+        return (N.AmpState(scale.data_ptr(), self._growth_tracker.data_ptr(), step.data_ptr()),
+                N.AmpConfig(float(self._growth_factor), float(self._backoff_factor), int(self._growth_interval)))
+
+    def scale(self, outputs: torch.Tensor) -> torch.Tensor:
+        """`outputs * scale` (for `scaler.scale(loss).backward()`), without a host synchronisation."""
+        if not isinstance(outputs, torch.Tensor) or outputs.device.type != "cuda":
+            raise ValueError("FusedGradScaler.scale: a tensor on a HIP device")
+        return outputs * self._device_scale(outputs.device)
+
+    def get_scale(self) -> float:
+        """The current scale (synchronises: for logging)."""
+        return self._init_scale if self._scale is None else self._scale.item()
+
+    def get_growth_factor(self) -> float:
+        return self._growth_factor
+
+    def get_backoff_factor(self) -> float:
+        return self._backoff_factor
+
+    def get_growth_interval(self) -> int:
+        return self._growth_interval
+
+    def _get_growth_tracker(self) -> int:
+        return self._init_growth_tracker if self._growth_tracker is None else int(self._growth_tracker.item())
+
+    def state_dict(self) -> dict:
+        """torch.amp.GradScaler.state_dict()'s layout (the trainer's "scaler_state_dict", trainer.py:431-432)."""
+        return {"scale": self.get_scale(), "growth_factor": self._growth_factor, "backoff_factor": self._backoff_factor,
+                "growth_interval": self._growth_interval, "_growth_tracker": self._get_growth_tracker()}
+
+    def load_state_dict(self, state_dict: dict) -> None:
+        if len(state_dict) == 0:
+            raise RuntimeError("The source state dict is empty, possibly because it was saved from a disabled instance of GradScaler.")
+        self._init_scale = float(state_dict["scale"])
+        if self._scale is not None:
+            self._scale.fill_(state_dict["scale"])
+        self._growth_factor = float(state_dict["growth_factor"])
+        self._backoff_factor = float(state_dict["backoff_factor"])
+        self._growth_interval = int(state_dict["growth_interval"])
+        self._init_growth_tracker = int(state_dict["_growth_tracker"])
+        if self._growth_tracker is not None:
+            self._growth_tracker.fill_(state_dict["_growth_tracker"])
 
 
 class FusedAdamW(torch.optim.Optimizer):
@@ -56,6 +135,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self._ema = torch.cat([p.detach().reshape(-1) for p in ps]) if ema_decay is not None else None  # EMAModel.__init__: a clone
         self._stats = torch.zeros(3, dtype=torch.float32, device=dev)
         self._step = 0
+        self._dstep = None    # device int32 AdamW step count, from the first step with a grad_scaler on
         self._native = None   # llie_optimizer*
         self._layout = None   # (param pointers, gradient offsets) the native tables were built for
         o = 0
@@ -94,33 +174,52 @@ class FusedAdamW(torch.optim.Optimizer):
             pass
 
     # ------------------------------------------------------------------ the step
-    def _launch(self, grad_base: int, grad_scale: float) -> None:
+    def _launch(self, grad_base: int, grad_scale: float, grad_scaler: Optional[FusedGradScaler] = None) -> None:
         g = self.param_groups[0]
-        self._step += 1
+        if grad_scaler is None and self._dstep is not None:
+            raise ValueError("FusedAdamW: this optimiser has taken steps with a grad_scaler (its step count lives on the "
+                             "device); every later step needs one too")
+        if grad_scaler is not None and not isinstance(grad_scaler, FusedGradScaler):
+            raise ValueError("grad_scaler must be a FusedGradScaler")
+        if grad_scaler is None:
+            self._step += 1
         h = N.OptHyper(float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
                        float(self.max_grad_norm) if self.max_grad_norm else 0.0,
                        float(self.ema_decay) if self.ema_decay is not None else -1.0, float(grad_scale), self._step,
                        1 if self.skip_nonfinite else 0)
         with torch.cuda.device(self._dev):
-            N.check(N.lib().llie_optimizer_step(self._native, grad_base, C.byref(h), self._stats.data_ptr(),
-                                                torch.cuda.current_stream(self._dev).cuda_stream), "FusedAdamW.step")
+            stream = torch.cuda.current_stream(self._dev).cuda_stream
+            if grad_scaler is None:
+                N.check(N.lib().llie_optimizer_step(self._native, grad_base, C.byref(h), self._stats.data_ptr(), stream),
+                        "FusedAdamW.step")
+                return
+            if self._dstep is None:  # seeded from the host count (torch.full: a fill kernel, no copy, no sync)
+                self._dstep = torch.full((), self._step, dtype=torch.int32, device=self._dev)
+            state, cfg = grad_scaler._native(self._dev, self._dstep)
+            N.check(N.lib().llie_optimizer_step_amp(self._native, grad_base, C.byref(h), C.byref(state), C.byref(cfg),
+                                                    self._stats.data_ptr(), stream), "FusedAdamW.step (grad_scaler)")
 
     @torch.no_grad()
-    def step_flat(self, flat: torch.Tensor, offsets: List[int], grad_scale: float = 1.0) -> torch.Tensor:
+    def step_flat(self, flat: torch.Tensor, offsets: List[int], grad_scale: float = 1.0, *,
+                  grad_scaler: Optional[FusedGradScaler] = None) -> torch.Tensor:
         """One update from a flat fp32 gradient buffer (parameter i at `flat[offsets[i]:]`, e.g. what llie_unet_backward
-        writes).  Returns the gradient norm before clipping as a device scalar (what clip_grad_norm_ returns)."""
+        writes).  Returns the gradient norm before clipping as a device scalar (what clip_grad_norm_ returns).
+        With `grad_scaler` the gradients are the scaled ones (backward of `grad_scaler.scale(loss)`), and this one call is
+        `scaler.unscale_ -> clip_grad_norm_ -> scaler.step -> scaler.update -> EMA update`: a step with an inf / NaN gradient
+        leaves parameters, moments and the step count alone (the EMA shadows still move) and backs the scale off."""
         if flat.dtype != torch.float32 or not flat.is_contiguous() or flat.device != self._dev:
             raise ValueError("flat gradients: contiguous fp32 on the parameters' device")
         if len(offsets) != len(self._numel) or any(o < 0 or o + n > flat.numel() for o, n in zip(offsets, self._numel)):
             raise ValueError("gradient offsets do not fit the flat buffer")
         self._bind(list(offsets))
-        self._launch(flat.data_ptr(), grad_scale)
+        self._launch(flat.data_ptr(), grad_scale, grad_scaler)
         return self._stats[0]
 
     @torch.no_grad()
-    def step(self, closure=None, *, grad_scale: float = 1.0):
+    def step(self, closure=None, *, grad_scale: float = 1.0, grad_scaler: Optional[FusedGradScaler] = None):
         """`clip_grad_norm_` (if max_grad_norm) + `AdamW.step` + EMA update (if ema_decay) on the `.grad` of every parameter.
-        Every parameter must have a gradient (the engine's backward pass always writes all of them)."""
+        Every parameter must have a gradient (the engine's backward pass always writes all of them).  `grad_scaler`: as
+        step_flat's."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -139,12 +238,13 @@ class FusedAdamW(torch.optim.Optimizer):
         # offsets relative to the lowest gradient: with the engine's backward pass these are the views of one flat buffer
         # and never change; gradients from elsewhere just rebuild the tables when their relative placement moves
         self._bind([(q - base) // 4 for q in ptrs])
-        self._launch(base, grad_scale)
+        self._launch(base, grad_scale, grad_scaler)
         self._keep = grads  # alive until the next step's launch is queued behind this one
         return loss
 
     def grad_norm(self) -> torch.Tensor:
-        """Norm of the (scaled) gradients of the last step, before clipping: device scalar."""
+        """Norm of the gradients of the last step times grad_scale (unscaled by the grad_scaler's scale), before clipping:
+        device scalar."""
         return self._stats[0]
 
     def last_step_skipped(self) -> bool:
@@ -163,6 +263,8 @@ class FusedAdamW(torch.optim.Optimizer):
 
     # ------------------------------------------------------------------ checkpoint layout of torch.optim.AdamW
     def state_dict(self):
+        if self._dstep is not None:  # updates actually taken (synchronises: checkpoints only)
+            self._step = int(self._dstep.item())
         for st in self.state.values():
             st["step"] = torch.tensor(float(self._step))
         sd = super().state_dict()
@@ -185,6 +287,8 @@ class FusedAdamW(torch.optim.Optimizer):
             self.state[p] = {"step": torch.tensor(float(step)), "exp_avg": self._m[o:o + n].view_as(p), "exp_avg_sq": self._v[o:o + n].view_as(p)}
             o += n
         self._step = step
+        if self._dstep is not None:
+            self._dstep.fill_(step)
         if ema is not None and self._ema is not None:
             self._ema.copy_(ema.to(self._dev))
 
@@ -215,12 +319,19 @@ class TrainStep:
     """One optimisation step of the reference trainer (trainer.py:281-324) on the engine, without autograd:
     q-sample (low_light_diffusion.py:140-160) -> llie_unet_train_forward -> loss and d(loss)/d(eps) -> llie_unet_backward into a
     persistent flat buffer -> one all-reduce of that buffer over the ranks -> FusedAdamW.step_flat (clip, AdamW, EMA).
-    `loss_type` / `use_velocity_target` as LowLightDiffusion.compute_loss.  Returns the loss (device scalar)."""
+    `loss_type` / `use_velocity_target` as LowLightDiffusion.compute_loss.  With `grad_scaler` (a FusedGradScaler: fp16 engines
+    need one, their unscaled gradients underflow) d(loss)/d(eps) is multiplied by the device scale before the backward pass,
+    which is `scaler.scale(loss).backward()`, and the optimiser unscales, skips and updates the scale on the device.
+    Returns the loss (device scalar, unscaled)."""
 
-    def __init__(self, model, optimizer: FusedAdamW, loss_type: str = "mse", use_velocity_target: bool = False, group=None):
+    def __init__(self, model, optimizer: FusedAdamW, loss_type: str = "mse", use_velocity_target: bool = False, group=None,
+                 grad_scaler: Optional[FusedGradScaler] = None):
         if loss_type not in ("mse", "huber", "l1"):
             raise ValueError(f"Unknown loss type: {loss_type}")
+        if grad_scaler is not None and not isinstance(grad_scaler, FusedGradScaler):
+            raise ValueError("grad_scaler must be a FusedGradScaler")
         self.model, self.opt, self.loss_type, self.velocity, self.group = model, optimizer, loss_type, use_velocity_target, group
+        self.grad_scaler = grad_scaler
         self._order = _engine_order(model.unet, optimizer, "TrainStep")
         if use_velocity_target and getattr(model.scheduler.config, "prediction_type", "epsilon") != "v_prediction":
             raise ValueError("use_velocity_target needs a scheduler with prediction_type='v_prediction'")
@@ -264,13 +375,15 @@ class TrainStep:
                 a = diff.abs()
                 loss = torch.where(a < 1.0, 0.5 * diff * diff, a - 0.5).mean()
                 d_eps = diff.clamp(-1.0, 1.0) / n
+            if self.grad_scaler is not None:
+                d_eps = d_eps * self.grad_scaler._device_scale(dev)
             N.check(L.llie_unet_backward(h.h, d_eps.data_ptr(), self._flat.data_ptr(), b, self._ws.data_ptr(), nbytes, st),
                     "EfficientUNet.backward")
         scale = 1.0
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
             dist.all_reduce(self._flat, group=self.group)  # one collective over all gradients; the average rides on grad_scale
             scale = 1.0 / dist.get_world_size(self.group)
-        self.opt.step_flat(self._flat, self._offsets, grad_scale=scale)
+        self.opt.step_flat(self._flat, self._offsets, grad_scale=scale, grad_scaler=self.grad_scaler)
         return loss
 
 
@@ -282,16 +395,19 @@ class DistillStep:
       llie_unet_backward into a flat buffer -> FusedAdamW.step_flat -> llie_ema_update.
     Same numbers as `loss = distill.consistency_distillation_loss(...); loss.backward(); optimizer.step();
     distill.update_ema(ema_decay)`.  The EMA student's engine weights are reloaded at its next forward (content check on the
-    device).  Returns the loss (device scalar).  fp16 students are refused: the step has no loss scaling (the autograd path
-    with GradScaler has); fp32 and bf16 run."""
+    device).  Returns the loss (device scalar, unscaled).  fp16 students need a `grad_scaler` (FusedGradScaler: d(loss)/d(eps)
+    times the device scale, unscale / skip / scale update in the optimiser's launches) and are refused without one; update_ema
+    runs every step, skipped or not, as in the reference loop.  fp32 and bf16 run either way."""
 
-    def __init__(self, distill, optimizer: FusedAdamW, ema_decay: float = 0.95):
+    def __init__(self, distill, optimizer: FusedAdamW, ema_decay: float = 0.95, grad_scaler: Optional[FusedGradScaler] = None):
         if not (0 <= ema_decay <= 1):
             raise ValueError("ema_decay must be in [0, 1]")
-        if distill.student.compute_dtype in ("fp16", "float16", torch.float16):
+        if grad_scaler is not None and not isinstance(grad_scaler, FusedGradScaler):
+            raise ValueError("grad_scaler must be a FusedGradScaler")
+        if grad_scaler is None and distill.student.compute_dtype in ("fp16", "float16", torch.float16):
             raise ValueError("DistillStep: fp16 students need loss scaling, which this step does not do; use the autograd "
                              "path (consistency_distillation_loss + GradScaler) or bf16")
-        self.distill, self.opt, self.ema_decay = distill, optimizer, ema_decay
+        self.distill, self.opt, self.ema_decay, self.grad_scaler = distill, optimizer, ema_decay, grad_scaler
         self._order = _engine_order(distill.student.unet, optimizer, "DistillStep")
         self._flat = None
         self._ws = None
@@ -305,7 +421,7 @@ class DistillStep:
         d._check_inputs(low_light, normal_light)
         unet = d.student.unet
         dtype = resolve_compute_dtype(unet.compute_dtype)
-        if dtype == N.LLIE_F16:
+        if dtype == N.LLIE_F16 and self.grad_scaler is None:
             raise ValueError("DistillStep: fp16 students need loss scaling, which this step does not do; use the autograd "
                              "path (consistency_distillation_loss + GradScaler) or bf16")
         b, dev = low_light.shape[0], low_light.device
@@ -327,9 +443,11 @@ class DistillStep:
                     "EfficientUNet.forward (training)")
         e_ema = d.ema_student.unet.forward_split(x_next, low, t_next)
         loss, d_eps = consistency_loss(sched, x_t, x_next, e_student, e_ema, t, t_next)
+        if self.grad_scaler is not None:
+            d_eps = d_eps * self.grad_scaler._device_scale(dev)
         with torch.cuda.device(dev):
             N.check(L.llie_unet_backward(h.h, d_eps.data_ptr(), self._flat.data_ptr(), b, self._ws.data_ptr(), nbytes,
                                          torch.cuda.current_stream(dev).cuda_stream), "EfficientUNet.backward")
-        self.opt.step_flat(self._flat, self._offsets)
+        self.opt.step_flat(self._flat, self._offsets, grad_scaler=self.grad_scaler)
         d.update_ema(self.ema_decay)
         return loss

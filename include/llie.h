@@ -192,6 +192,29 @@ int llie_optimizer_create(const llie_opt_tensor* tensors /* host array */, int c
 void llie_optimizer_destroy(llie_optimizer* opt);
 int64_t llie_optimizer_numel(const llie_optimizer* opt);
 int llie_optimizer_step(llie_optimizer* opt, const float* grad_base, const llie_opt_hyper* hyper, float* stats3, llie_stream stream);
+/* llie_optimizer_step_amp: the same step with torch.amp.GradScaler around it (scaler.unscale_ -> clip_grad_norm_ ->
+ * scaler.step -> scaler.update, then the EMA update), the loss scaler's state in device memory, no host synchronisation.
+ * The gradients are the scaled ones (backward of loss * scale).  inv = (float)(1 / (double)*scale); the factor applied to
+ * every gradient is inv * grad_scale * clip coefficient, the clip coefficient coming from the norm of the unscaled gradients.
+ * found_inf = some gradient element is inf or NaN.  Then:
+ *   found_inf:  parameters and moments unchanged, *step unchanged; the EMA shadows still move (shadow = decay shadow +
+ *               (1 - decay) param: the reference trainer updates its EMA every iteration);
+ *   otherwise:  *step += 1 and the AdamW update with the bias corrections of that count (formed on the device, in double);
+ * and *scale / *growth_tracker are updated as torch's _amp_update_scale_: found_inf -> scale *= backoff_factor, tracker = 0;
+ * else tracker + 1 == growth_interval -> scale *= growth_factor if the result is finite, tracker = 0; else tracker += 1.
+ * hyper->step and hyper->skip_nonfinite are not used.  stats3 as llie_optimizer_step's: {norm of the unscaled gradients
+ * (times grad_scale), factor applied, 1 if skipped}.  Fixed-order sums: bitwise reproducible. */
+typedef struct llie_amp_state { /* device pointers */
+  float* scale;            /* torch.amp.GradScaler's _scale */
+  int32_t* growth_tracker; /* GradScaler's _growth_tracker */
+  int32_t* step;           /* the optimiser's AdamW step count: updates taken so far */
+} llie_amp_state;
+typedef struct llie_amp_config {
+  double growth_factor, backoff_factor;
+  int32_t growth_interval;
+} llie_amp_config;
+int llie_optimizer_step_amp(llie_optimizer* opt, const float* grad_base, const llie_opt_hyper* hyper, const llie_amp_state* state,
+                            const llie_amp_config* cfg, float* stats3, llie_stream stream);
 
 /* ---- Consistency distillation (LowLightLCMDistillation.consistency_distillation_loss / update_ema,
  * low_light_diffusion.py:284-408).  Tensors are device fp32 NCHW [batch, 3, S, S] (per_sample = 3*S*S elements per
