@@ -2,7 +2,7 @@
 """Headline benchmark: images/sec of the 4-step LCM `enhance` loop, variant small, 256x256, fp16,
 batch 32 per GPU (BASELINE.json configs[1]), synthetic inputs and random-init weights.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one `LowLightDiffusion.enhance(x, 4)` call on this rank's batch (4 UNet forwards + 4
 scheduler steps), inputs already resident in HBM.  For N > 1 the driver launches one process per GPU
@@ -14,6 +14,11 @@ JSON line.
 timed region -- `enhanced` (the gathered batch for N > 1), or with --train `loss` and `params` (the parameters
 after the step).  At most DUMP_BYTES in all; a larger array is replaced by a fixed, seeded sample of its
 flattened entries.  Weights, inputs and device noise are seeded, so equal arguments give equal inputs.
+
+A plain run does only what the headline figure needs: set up, warm up, time the steps, dump, print the line.
+--full adds, after the timed region and on rank 0 only, what takes runs of its own: `roofline` (per-kernel event
+passes and an HBM copy probe) and, on one GPU, `cpu_baseline` (the CPU oracle on the host's cores) with `quality`
+(PSNR / max-abs against it).  --no-roofline / --no-cpu-baseline leave either out of a --full run.
 """
 from __future__ import annotations
 
@@ -308,8 +313,11 @@ def main() -> None:
     ap.add_argument("--image_size", type=int, default=256)
     ap.add_argument("--lcm_steps", type=int, default=4)
     ap.add_argument("--dtype", default="fp16", choices=["fp32", "fp16", "bf16"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: roofline (per-kernel passes, "
+                         "HBM copy probe) and, on one GPU, the CPU-oracle baseline and quality against it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out cpu_baseline and quality")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out roofline")
     ap.add_argument("--train-autograd", dest="train_autograd", action="store_true",
                     help="with --train: loss.backward() + clip_grad_norm_ + torch.optim.AdamW + foreach EMA on the engine's autograd "
                          "node instead of TrainStep / FusedAdamW (same arithmetic)")
@@ -321,6 +329,8 @@ def main() -> None:
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_roofline = True
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))

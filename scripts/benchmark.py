@@ -63,7 +63,7 @@ def main(argv=None):
     if args.format != "pytorch":
         raise SystemExit(f"--format {args.format}: exported-model runtimes are outside this engine's scope; use --format pytorch")
     if args.device != "cuda":
-        raise SystemExit("the engine has no CPU path; use --device cuda (for a CPU number see bench.py's cpu_baseline)")
+        raise SystemExit("the engine has no CPU path; use --device cuda (for a CPU number see cpu_baseline in `bench.py --full`)")
     print("=" * 60)
     print("Low-Light Enhancement Model Benchmark")
     print("=" * 60)

@@ -7,7 +7,7 @@
   * isolated SinusoidalPosEmb / time MLP and SqueezeExcitation KATs
   * the recompute-form kernels (irbx.hip) against the unfused pair and the oracle
   * in-place weight writes that bypass version counters, copy.deepcopy, out-of-range timesteps
-  * the multi-rank bench.py path (two ranks rehearsed on the one GPU)
+  * the multi-rank bench.py path (two ranks rehearsed on the one GPU) and a plain run's headline-only line
 """
 import copy
 import importlib
@@ -493,7 +493,7 @@ def _bench(args, world):
 def test_bench_two_ranks_inference(tmp_path):
     """bench.py as the driver launches it for N > 1 (torch.distributed.run, one rank per process, barrier + max over ranks,
     async all_gather of the outputs), rehearsed with both ranks on this box's one GPU over gloo."""
-    line = _bench(["--steps", "2", "--warmup", "1", "--batch", "4", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], 2)
+    line = _bench(["--steps", "2", "--warmup", "1", "--batch", "4", "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], 2)
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 8 and line["scaling"] == "weak"
     assert line["value"] > 0 and line["steps"] == 2 and line["unit"] == "images/sec"
     assert abs(line["value"] - 8 * 2 / (line["ms_per_step"] * 2e-3)) / line["value"] < 1e-2
@@ -502,6 +502,22 @@ def test_bench_two_ranks_inference(tmp_path):
     enh = np.load(tmp_path / "enhanced.npy")
     assert enh.dtype == np.float32 and enh.shape == (8, 3, 256, 256)
     assert np.isfinite(enh).all() and np.abs(enh).max() <= 1.0 and not np.array_equal(enh[:4], enh[4:])
+
+
+def test_bench_plain_run_is_the_headline_only(tmp_path):
+    """Without --full, bench.py sets up, warms up, times, dumps and prints the headline line: no roofline passes, copy
+    probe or CPU baseline after the timed region."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["unit"] == "images/sec" and line["higher_is_better"] is True and line["dtype"] == "fp16" and line["n_gpus"] == 1
+    assert line["value"] > 0 and abs(line["value"] - 4 * 2 / (line["ms_per_step"] * 2e-3)) / line["value"] < 1e-2
+    assert not {"roofline", "cpu_baseline", "quality"} & line.keys()
+    enh = np.load(tmp_path / "enhanced.npy")
+    assert enh.dtype == np.float32 and enh.shape == (4, 3, 256, 256) and np.isfinite(enh).all()
 
 
 def test_bench_two_ranks_training():
