@@ -29,6 +29,10 @@ EXPORTS = [
     "llie_optimizer_create", "llie_optimizer_destroy", "llie_optimizer_numel", "llie_optimizer_step",
     "llie_optimizer_step_amp",
     "llie_consistency_target", "llie_consistency_loss", "llie_ema_create", "llie_ema_update", "llie_ema_destroy",
+    "llie_wgrad", "llie_wgrad_msplit", "llie_wgrad_partial_floats", "llie_dw_wgrad", "llie_dw_wgrad_strips",
+    "llie_groupnorm_backward", "llie_groupnorm_backward_scratch_floats", "llie_linattn_backward", "llie_linattn_dkv_floats",
+    "llie_upsample2x_backward", "llie_dilate2x", "llie_linear_dx", "llie_linear_dx_scratch_floats", "llie_linear_dw",
+    "llie_final_bwd_data",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 
@@ -36,6 +40,15 @@ K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 class GemmSeg(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("channels", C.c_int), ("scale", C.c_void_p), ("bias", C.c_void_p),
                 ("affine_ld", C.c_int), ("act", C.c_int)]
+
+
+class GnBackwardArgs(C.Structure):
+    """llie_gn_backward_args (include/llie.h): one GroupNorm site of the backward pass."""
+    _fields_ = [("g", C.c_void_p), ("dz", C.c_void_p), ("x0", C.c_void_p), ("x1", C.c_void_p), ("c0", C.c_int), ("c1", C.c_int),
+                ("scale", C.c_void_p), ("shift", C.c_void_p), ("act", C.c_int), ("mean", C.c_void_p), ("rstd", C.c_void_p),
+                ("gamma", C.c_void_p), ("beta", C.c_void_p), ("film", C.c_void_p), ("film_stride", C.c_int64), ("dfilm", C.c_void_p),
+                ("dfilm_stride", C.c_int64), ("dgamma", C.c_void_p), ("dbeta", C.c_void_p), ("add0", C.c_void_p), ("add1_0", C.c_void_p),
+                ("add1_1", C.c_void_p), ("dx0", C.c_void_p), ("dx1", C.c_void_p), ("batch", C.c_int), ("pixels", C.c_int)]
 
 
 class LibraryNotBuilt(RuntimeError):
@@ -179,6 +192,25 @@ def lib() -> C.CDLL:
     L.llie_unet_train_forward.argtypes = [vp, vp, vp, vp, vp, ci, vp, i64, vp]
     L.llie_unet_backward.argtypes = [vp, vp, vp, ci, vp, i64, vp]
     L.llie_module_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, i64, vp]
+    L.llie_wgrad.argtypes = [ci, vp, ci, C.POINTER(GemmSeg), ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, i64, vp, i64, i64, i64, ci, vp]
+    L.llie_wgrad_msplit.argtypes = [ci, ci, ci, ci, ci, ci, ci]
+    L.llie_wgrad_partial_floats.argtypes = [ci, ci, ci, ci]
+    L.llie_wgrad_partial_floats.restype = i64
+    L.llie_dw_wgrad.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
+    L.llie_dw_wgrad_strips.argtypes = [ci, ci]
+    L.llie_groupnorm_backward.argtypes = [ci, C.POINTER(GnBackwardArgs), vp, i64, vp]
+    L.llie_groupnorm_backward_scratch_floats.argtypes = [ci, ci, ci]
+    L.llie_groupnorm_backward_scratch_floats.restype = i64
+    L.llie_linattn_backward.argtypes = [ci, vp, vp, vp, vp, vp, i64, ci, ci, ci, vp]
+    L.llie_linattn_dkv_floats.argtypes = [ci, ci, ci]
+    L.llie_linattn_dkv_floats.restype = i64
+    L.llie_upsample2x_backward.argtypes = [ci, vp, vp, ci, ci, ci, ci, vp]
+    L.llie_dilate2x.argtypes = [ci, vp, vp, ci, ci, ci, ci, vp]
+    L.llie_linear_dx.argtypes = [ci, vp, i64, vp, vp, ci, ci, ci, vp, i64, vp]
+    L.llie_linear_dx_scratch_floats.argtypes = [ci, ci, ci]
+    L.llie_linear_dx_scratch_floats.restype = i64
+    L.llie_linear_dw.argtypes = [vp, i64, vp, vp, vp, ci, ci, ci, vp]
+    L.llie_final_bwd_data.argtypes = [ci, vp, vp, vp, ci, ci, ci, ci, ci, vp]
     L.llie_profile_report.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.llie_profile_dump.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.llie_profile_begin.argtypes = [vp, ci]

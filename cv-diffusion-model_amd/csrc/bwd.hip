@@ -298,6 +298,41 @@ hipError_t launch_gn_bwd_apply(int dtype, const GnApplyArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+hipError_t launch_gn_site_bwd(int dtype, const GnSiteArgs& a, hipStream_t s) {
+  const int C = a.c0 + a.c1, M = a.B * a.P;
+  hipError_t e = hipSuccess;
+  if (!a.slab_ready) {
+    BwdMaskArgs m{};
+    m.g = a.g; m.x0 = a.x0; m.c0 = a.c0; m.x1 = a.x1; m.c1 = a.c1;
+    m.as = a.as; m.ab = a.ab; m.act = a.act; m.dz = a.act == ACT_NONE ? nullptr : a.dz;
+    m.slab = a.slab; m.M = M; m.C = C; m.P = a.P;
+    e = launch_bwd_mask_reduce(dtype, m, s);
+  }
+  GnBwdArgs k{};
+  if (C / 32 <= kGnCoefMaxCg) {  // the coefficient kernel sums the tile partials of its group itself (no slab_reduce launch)
+    k.slab = a.slab; k.ntiles = a.ntiles;
+  } else {
+    if (e == hipSuccess) e = launch_slab_reduce(a.slab, a.S, a.B, a.ntiles, 2, 2, C, s);
+    k.S = a.S;
+  }
+  k.mean = a.mean; k.rstd = a.rstd; k.gamma = a.gamma;
+  k.film = a.film; k.film_stride = a.film_stride; k.C = C; k.groups = 32; k.P = a.P; k.B = a.B;
+  k.A = a.A; k.Bq = a.Bq; k.Cq = a.Cq; k.dG = a.dG; k.dBc = a.dBc;
+  if (e == hipSuccess) e = launch_gn_bwd_coef(k, s);
+  GnParamGradArgs q{};
+  q.dG = a.dG; q.dBc = a.dBc; q.gamma = a.gamma; q.beta = a.beta;
+  q.film = a.film; q.film_stride = a.film_stride; q.dgamma = a.dgamma; q.dbeta = a.dbeta; q.dfilm = a.dfilm; q.dfilm_stride = a.dfilm_stride;
+  q.B = a.B; q.C = C;
+  if (e == hipSuccess) e = launch_gn_param_grad(q, s);
+  GnApplyArgs p{};
+  p.dz = a.act == ACT_NONE || !a.dz ? a.g : a.dz; p.x0 = a.x0; p.c0 = a.c0; p.x1 = a.x1; p.c1 = a.c1;
+  p.A = a.A; p.Bq = a.Bq; p.Cq = a.Cq;
+  p.add0 = a.add0; p.add1_0 = a.add1_0; p.add1_1 = a.add1_1;
+  p.dx0 = a.dx0; p.dx1 = a.dx1; p.M = M; p.P = a.P;
+  if (e == hipSuccess) e = launch_gn_bwd_apply(dtype, p, s);
+  return e;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256) add_into_kernel(T* dst, const T* src, int64_t nvec) {
   constexpr int VEC = Elem<T>::VEC;
@@ -992,6 +1027,15 @@ hipError_t launch_linattn_bwd_kv(int dtype, const AttnBwdArgs& a, hipStream_t s)
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
+}
+
+hipError_t launch_linattn_bwd(int dtype, const AttnBwdArgs& a, float* tot, hipStream_t s) {
+  hipError_t e = launch_linattn_bwd_q(dtype, a, s);
+  if (e == hipSuccess) e = launch_slab_reduce(a.dkv, tot, a.B * a.heads, (a.N + 63) / 64, 1, 1, 32 * 33, s);
+  AttnBwdArgs b = a;
+  b.dkv = tot;
+  if (e == hipSuccess) e = launch_linattn_bwd_kv(dtype, b, s);
+  return e;
 }
 
 }  // namespace llie

@@ -1199,56 +1199,44 @@ struct Back {
     defer(part);
   }
 
-  // activation backward + GroupNorm backward coefficients + norm parameter gradients at one norm site.
+  // activation backward + GroupNorm backward (coefficients, norm parameter gradients, input gradient) at one norm site, on
+  // launch_gn_site_bwd.  gn_plan takes the site's scratch from the arena and releases what only the coefficient pass reads;
+  // the caller may then allocate the input gradient it writes into, and gn_bwd enqueues the whole site and releases the rest.
   //   g: gradient w.r.t. the activation output act(norm(x)) [M][C]; dz is written over g when act != none.
-  struct Coef { size_t A, Bq, Cq; };
   //   pre_slab / pre_tiles: the producer already applied the activation derivative and wrote the partial sums
-  //   (depthwise backward epilogue); then only the reduction and the coefficient kernels run here.
-  Coef gn_site(size_t g, const Tens& x0, const Tens* x1, const GnRec& rec, int act, size_t gamma, size_t beta,
-               float* dgamma, float* dbeta, const float* film, int64_t fstride, float* dfilm, int64_t dfstride,
-               size_t pre_slab = 0, int pre_tiles = 0) {
-    const int C = x0.C + (x1 ? x1->C : 0), P = x0.H * x0.W, M = B * P, nt = pre_tiles ? pre_tiles : (P + 63) / 64;
-    const size_t slab = pre_tiles ? pre_slab : alloc((size_t)B * nt * 2 * C * 4);
-    const size_t S = alloc((size_t)B * 2 * C * 4);
-    Coef k{alloc((size_t)B * C * 4), alloc((size_t)B * C * 4), alloc((size_t)B * C * 4)};
-    const size_t dG = alloc((size_t)B * C * 4), dBc = alloc((size_t)B * C * 4);
-    if (!dry) {
-      BwdMaskArgs m{};
-      m.g = p(g); m.x0 = p(x0.off); m.c0 = x0.C; m.x1 = x1 ? p(x1->off) : nullptr; m.c1 = x1 ? x1->C : 0;
-      m.as = p<float>(rec.as); m.ab = p<float>(rec.ab); m.act = act; m.dz = act == ACT_NONE ? nullptr : p(g);
-      m.slab = p<float>(slab); m.M = M; m.C = C; m.P = P;
-      if (!pre_tiles) chk(launch_bwd_mask_reduce(dt, m, s));
-      GnBwdArgs a{};
-      if (C / 32 <= 64) {  // the coefficient kernel sums the tile partials of its group itself (no slab_reduce launch)
-        a.slab = p<float>(slab); a.ntiles = nt;
-      } else {
-        chk(launch_slab_reduce(p<float>(slab), p<float>(S), B, nt, 2, 2, C, s));
-        a.S = p<float>(S);
-      }
-      a.mean = p<float>(rec.mean); a.rstd = p<float>(rec.rstd); a.gamma = wptr<float>(gamma);
-      a.film = film; a.film_stride = fstride; a.C = C; a.groups = 32; a.P = P; a.B = B;
-      a.A = p<float>(k.A); a.Bq = p<float>(k.Bq); a.Cq = p<float>(k.Cq); a.dG = p<float>(dG); a.dBc = p<float>(dBc);
-      chk(launch_gn_bwd_coef(a, s));
-      GnParamGradArgs q{};
-      q.dG = p<float>(dG); q.dBc = p<float>(dBc); q.gamma = wptr<float>(gamma); q.beta = wptr<float>(beta);
-      q.film = film; q.film_stride = fstride; q.dgamma = dgamma; q.dbeta = dbeta; q.dfilm = dfilm; q.dfilm_stride = dfstride;
-      q.B = B; q.C = C;
-      chk(launch_gn_param_grad(q, s));
-    }
-    if (!pre_tiles) ar->free(slab);
-    ar->free(S); ar->free(dG); ar->free(dBc);
+  //   (depthwise backward epilogue); then only the reduction and the coefficient kernels run before the apply.
+  struct Coef { size_t slab, S, A, Bq, Cq, dG, dBc; int nt; bool pre; };
+  Coef gn_plan(const Tens& x0, const Tens* x1, size_t pre_slab = 0, int pre_tiles = 0) {
+    const int C = x0.C + (x1 ? x1->C : 0), P = x0.H * x0.W, nt = pre_tiles ? pre_tiles : (P + 63) / 64;
+    Coef k{};
+    k.nt = nt; k.pre = pre_tiles != 0;
+    k.slab = pre_tiles ? pre_slab : alloc((size_t)B * nt * 2 * C * 4);
+    k.S = alloc((size_t)B * 2 * C * 4);
+    k.A = alloc((size_t)B * C * 4); k.Bq = alloc((size_t)B * C * 4); k.Cq = alloc((size_t)B * C * 4);
+    k.dG = alloc((size_t)B * C * 4); k.dBc = alloc((size_t)B * C * 4);
+    // released here, as the workspace plan always has: the input gradient a caller allocates before gn_bwd may land on them; it is
+    // written only by the site's last kernel, after they have been read
+    if (!pre_tiles) ar->free(k.slab);
+    ar->free(k.S); ar->free(k.dG); ar->free(k.dBc);
     return k;
   }
-  void free_coef(const Coef& k) { ar->free(k.A); ar->free(k.Bq); ar->free(k.Cq); }
-  void apply(size_t dz, const Tens& x0, const Tens* x1, const Coef& k, size_t add0, bool has_add0, size_t a10, bool has10,
-             size_t a11, bool has11, size_t dx0, size_t dx1) {
-    if (dry) return;
-    GnApplyArgs a{};
-    a.dz = p(dz); a.x0 = p(x0.off); a.c0 = x0.C; a.x1 = x1 ? p(x1->off) : nullptr; a.c1 = x1 ? x1->C : 0;
-    a.A = p<float>(k.A); a.Bq = p<float>(k.Bq); a.Cq = p<float>(k.Cq);
-    a.add0 = has_add0 ? p(add0) : nullptr; a.add1_0 = has10 ? p(a10) : nullptr; a.add1_1 = has11 ? p(a11) : nullptr;
-    a.dx0 = p(dx0); a.dx1 = x1 ? p(dx1) : nullptr; a.M = B * x0.H * x0.W; a.P = x0.H * x0.W;
-    chk(launch_gn_bwd_apply(dt, a, s));
+  void gn_bwd(const Coef& k, size_t g, const Tens& x0, const Tens* x1, const GnRec& rec, int act, size_t gamma, size_t beta,
+              float* dgamma, float* dbeta, const float* film, int64_t fstride, float* dfilm, int64_t dfstride,
+              size_t add0, bool has_add0, size_t a10, bool has10, size_t a11, bool has11, size_t dx0, size_t dx1) {
+    if (!dry) {
+      GnSiteArgs a{};
+      a.g = p(g); a.dz = act == ACT_NONE ? nullptr : p(g);
+      a.x0 = p(x0.off); a.c0 = x0.C; a.x1 = x1 ? p(x1->off) : nullptr; a.c1 = x1 ? x1->C : 0;
+      a.as = p<float>(rec.as); a.ab = p<float>(rec.ab); a.act = act; a.mean = p<float>(rec.mean); a.rstd = p<float>(rec.rstd);
+      a.gamma = wptr<float>(gamma); a.beta = wptr<float>(beta);
+      a.film = film; a.film_stride = fstride; a.dfilm = dfilm; a.dfilm_stride = dfstride; a.dgamma = dgamma; a.dbeta = dbeta;
+      a.slab = p<float>(k.slab); a.ntiles = k.nt; a.slab_ready = k.pre;
+      a.S = p<float>(k.S); a.A = p<float>(k.A); a.Bq = p<float>(k.Bq); a.Cq = p<float>(k.Cq); a.dG = p<float>(k.dG); a.dBc = p<float>(k.dBc);
+      a.add0 = has_add0 ? p(add0) : nullptr; a.add1_0 = has10 ? p(a10) : nullptr; a.add1_1 = has11 ? p(a11) : nullptr;
+      a.dx0 = p(dx0); a.dx1 = x1 ? p(dx1) : nullptr; a.B = B; a.P = x0.H * x0.W;
+      chk(launch_gn_site_bwd(dt, a, s));
+    }
+    ar->free(k.A); ar->free(k.Bq); ar->free(k.Cq);
   }
 
   // ---- InvertedResidualBlock
@@ -1320,10 +1308,10 @@ struct Back {
     // norm2 + FiLM + ReLU6
     const float* film = dry ? nullptr : p<float>(tp->film) + w.film_off;
     float* dfl = dry ? nullptr : p<float>(dfilm) + w.film_off;
-    Coef k2 = gn_site(da2, r.h1, nullptr, r.n2, ACT_RELU6, w.n2g, w.n2b, gp(pf + 2), gp(pf + 3), film, F, dfl, F, dzslab, dztiles);
+    const Coef k2 = gn_plan(r.h1, nullptr, dzslab, dztiles);
     ar->free(dzslab);
-    apply(da2, r.h1, nullptr, k2, 0, false, 0, false, 0, false, da2, 0);  // dh1, in place
-    free_coef(k2);
+    gn_bwd(k2, da2, r.h1, nullptr, r.n2, ACT_RELU6, w.n2g, w.n2b, gp(pf + 2), gp(pf + 3), film, F, dfl, F,
+           0, false, 0, false, 0, false, da2, 0);  // dh1, in place
     // expand
     const size_t da1 = alloc((size_t)M * cin * es());
     gemm(da2, hid, wptr(w.w_expand_t), da1, cin, M, P);
@@ -1337,12 +1325,12 @@ struct Back {
     }
     defer(da2);
     // norm1 + ReLU6, then the block input (residual / skip-conv gradient added, existing gradients accumulated)
-    Coef k1 = gn_site(da1, r.x0, x1, r.n1, ACT_RELU6, w.n1g, w.n1b, gp(pf + 0), gp(pf + 1), nullptr, 0, nullptr, 0);
+    const Coef k1 = gn_plan(r.x0, x1);
     bool e0 = false, e1 = false;
     const size_t g0 = grad_of(r.x0, e0);
     const size_t g1 = x1 ? grad_of(*x1, e1) : 0;
-    apply(da1, r.x0, x1, k1, w.skip ? dxs : dY, true, g0, e0, g1, e1, g0, g1);
-    free_coef(k1);
+    gn_bwd(k1, da1, r.x0, x1, r.n1, ACT_RELU6, w.n1g, w.n1b, gp(pf + 0), gp(pf + 1), nullptr, 0, nullptr, 0,
+           w.skip ? dxs : dY, true, g0, e0, g1, e1, g0, g1);
     ar->free(da1);
     if (w.skip) ar->free(dxs);
     defer(dY);
@@ -1356,10 +1344,10 @@ struct Back {
     const size_t dY = take_grad(r.y);
     const Geo g11{H, W, H, W, 1, 0, 0};
     // y = norm2(tmp) + x
-    Coef k2 = gn_site(dY, r.tmp, nullptr, r.n2, ACT_NONE, w.n2g, w.n2b, gp(pf + 4), gp(pf + 5), nullptr, 0, nullptr, 0);
+    const Coef k2 = gn_plan(r.tmp, nullptr);
     const size_t dtmp = alloc((size_t)M * C * es());
-    apply(dY, r.tmp, nullptr, k2, 0, false, 0, false, 0, false, dtmp, 0);
-    free_coef(k2);
+    gn_bwd(k2, dY, r.tmp, nullptr, r.n2, ACT_NONE, w.n2g, w.n2b, gp(pf + 4), gp(pf + 5), nullptr, 0, nullptr, 0,
+           0, false, 0, false, 0, false, dtmp, 0);
     // to_out
     const size_t dao = alloc((size_t)M * inner * es());
     gemm(dtmp, C, wptr(w.w_out_t), dao, inner, M, N);
@@ -1378,10 +1366,7 @@ struct Back {
         AttnBwdArgs a{};
         a.qkv = p(r.qkv); a.dout = p(dao); a.dqkv = p(dqkv); a.kv = p<float>(r.kv); a.nsplit = r.nsplit;
         a.dkv = p<float>(part); a.B = B; a.N = N; a.heads = w.heads;
-        chk(launch_linattn_bwd_q(dt, a, s));
-        chk(launch_slab_reduce(p<float>(part), p<float>(tot), B * w.heads, nt, 1, 1, 32 * 33, s));
-        a.dkv = p<float>(tot);
-        chk(launch_linattn_bwd_kv(dt, a, s));
+        chk(launch_linattn_bwd(dt, a, p<float>(tot), s));
       }
       ar->free(part); ar->free(tot);
     }
@@ -1396,11 +1381,11 @@ struct Back {
     }
     defer(dqkv);
     // norm (no activation) + residual
-    Coef k1 = gn_site(dxn, r.x, nullptr, r.n1, ACT_NONE, w.ng, w.nb, gp(pf + 0), gp(pf + 1), nullptr, 0, nullptr, 0);
+    const Coef k1 = gn_plan(r.x, nullptr);
     bool e0 = false;
     const size_t g0 = grad_of(r.x, e0);
-    apply(dxn, r.x, nullptr, k1, dY, true, g0, e0, 0, false, g0, 0);
-    free_coef(k1);
+    gn_bwd(k1, dxn, r.x, nullptr, r.n1, ACT_NONE, w.ng, w.nb, gp(pf + 0), gp(pf + 1), nullptr, 0, nullptr, 0,
+           dY, true, g0, e0, 0, false, g0, 0);
     ar->free(dxn);
     ar->free(dY);
     join();
@@ -1509,10 +1494,9 @@ struct Back {
       wgrad(g32, 32, &sg, 1, C0, geo, gp(pidx("final_conv.weight")), (int64_t)C0 * 9, 9, 0, 9, g.out_channels, 0);
       defer(g32);  // released at the first operator's join
     }
-    Coef kf = gn_site(da, tp->hlast, nullptr, tp->fin, ACT_SILU, c->fin_g, c->fin_b, gp(pidx("final_norm.weight")),
-                      gp(pidx("final_norm.bias")), nullptr, 0, nullptr, 0);
-    apply(da, tp->hlast, nullptr, kf, 0, false, 0, false, 0, false, da, 0);
-    free_coef(kf);
+    const Coef kf = gn_plan(tp->hlast, nullptr);
+    gn_bwd(kf, da, tp->hlast, nullptr, tp->fin, ACT_SILU, c->fin_g, c->fin_b, gp(pidx("final_norm.weight")),
+           gp(pidx("final_norm.bias")), nullptr, 0, nullptr, 0, 0, false, 0, false, 0, false, da, 0);
     gmap[tp->hlast.off] = da;
     run_ops(dfilm, F);
     // input conv
@@ -2313,6 +2297,125 @@ int llie_film(const float* silu_temb, const float* wf, const float* bf, float* f
   FilmArgs a{};
   a.silu_temb = silu_temb; a.rows = rows; a.T = T; a.wf = wf; a.bf = bf; a.film = film; a.F = F;
   return kerr("film", launch_film(a, reinterpret_cast<hipStream_t>(stream)));
+}
+
+// ---- backward kernels (training): thin wrappers over the launch API; every contract check runs here, before any HIP call
+static bool dtype_ok(int dtype) { return dtype >= 0 && dtype <= 2; }
+static int wgrad_rule(int dtype, int batch, int pixels, int N, int K, int ntap, int ragged_rule) {
+  const int M = wgrad_rows(batch, pixels);
+  return ragged_rule ? wgrad_msplit_ragged(dtype, M, N, K, ntap) : wgrad_msplit(dtype, M, N, K, ntap);
+}
+int llie_wgrad_msplit(int dtype, int batch, int pixels, int N, int K, int ntap, int ragged_rule) {
+  if (!dtype_ok(dtype) || batch <= 0 || pixels <= 0 || N <= 0 || K <= 0 || (ntap != 1 && ntap != 9)) return LLIE_ERR_ARG;
+  return wgrad_rule(dtype, batch, pixels, N, K, ntap, ragged_rule);
+}
+int64_t llie_wgrad_partial_floats(int msplit, int N, int K, int ntap) {
+  if (msplit <= 0 || N <= 0 || K <= 0 || (ntap != 1 && ntap != 9)) return LLIE_ERR_ARG;
+  return (int64_t)msplit * ntap * N * K;
+}
+int llie_wgrad(int dtype, const void* g, int N, const llie_gemm_seg* segs, int nseg, int batch, int Ho, int Wo, int Hi, int Wi, int stride,
+               int dy, int dx, int ntap, int nstore, int kstore, float* partial, int64_t partial_floats, float* out, int64_t ldn, int64_t ldk,
+               int64_t off, int msplit, llie_stream stream) {
+  if (!dtype_ok(dtype) || !g || !segs || !partial || !out || nseg < 1 || nseg > 3 || N <= 0 || N % 32 || batch <= 0 || Ho <= 0 ||
+      Wo <= 0 || Hi <= 0 || Wi <= 0 || (stride != 1 && stride != 2) || (ntap != 1 && ntap != 9) || dy < -1 || dy > 1 || dx < -1 ||
+      dx > 1 || msplit < 0 || ldn < 0 || ldk < 0 || off < 0)
+    return LLIE_ERR_ARG;
+  WgradArgs a{};
+  a.nseg = nseg;
+  for (int i = 0; i < nseg; ++i) {
+    const llie_gemm_seg& sg = segs[i];
+    if (!sg.ptr || sg.channels <= 0 || sg.channels % 32 || sg.act < ACT_NONE || sg.act > ACT_SILU || (sg.bias && !sg.scale) ||
+        (sg.scale && sg.affine_ld < sg.channels))
+      return LLIE_ERR_ARG;
+    a.seg[i] = GemmSeg{sg.ptr, sg.channels, sg.scale, sg.bias, sg.affine_ld, sg.act};
+    a.K += sg.channels;
+  }
+  // the output pixel grid must lie inside the input's (stride-s conv with pad 1 or a 1x1 tap)
+  if (nstore < 0 || nstore > N || kstore < 0 || kstore > a.K || (Ho - 1) * stride >= Hi || (Wo - 1) * stride >= Wi) return LLIE_ERR_ARG;
+  const int P = Ho * Wo, M = wgrad_rows(batch, P);
+  const int ms = msplit ? msplit : wgrad_rule(dtype, batch, P, N, a.K, ntap, P % 64 != 0);
+  if (ms > M / 64 || partial_floats < (int64_t)ms * ntap * N * a.K) return LLIE_ERR_ARG;
+  a.g = g; a.N = N; a.B = batch; a.Ho = Ho; a.Wo = Wo; a.Hi = Hi; a.Wi = Wi; a.stride = stride; a.dy = dy; a.dx = dx;
+  a.ntap = ntap; a.nstore = nstore; a.kstore = kstore; a.partial = partial; a.out = out; a.ldn = ldn; a.ldk = ldk; a.off = off; a.msplit = ms;
+  return kerr("wgrad", launch_wgrad(dtype, a, reinterpret_cast<hipStream_t>(stream)));
+}
+int llie_dw_wgrad_strips(int H, int W) { return H > 0 && W > 0 ? dw_wgrad_strips(H, W) : LLIE_ERR_ARG; }
+int llie_dw_wgrad(int dtype, const void* g, const float* gs, const float* gb, const void* h, const float* as, const float* ab, float* partial,
+                  float* out, int batch, int H, int W, int C, llie_stream stream) {
+  if (!dtype_ok(dtype) || !g || !h || !as || !ab || !partial || !out || batch <= 0 || H <= 0 || W <= 0 || C <= 0 || C % (dtype == 0 ? 32 : 64))
+    return LLIE_ERR_ARG;
+  DwWgradArgs a{};
+  a.g = g; a.gs = gs; a.gb = gb; a.h = h; a.as = as; a.ab = ab; a.partial = partial; a.out = out; a.B = batch; a.H = H; a.W = W; a.C = C;
+  return kerr("dw_wgrad", launch_dw_wgrad(dtype, a, reinterpret_cast<hipStream_t>(stream)));
+}
+int64_t llie_groupnorm_backward_scratch_floats(int batch, int C, int pixels) {
+  if (batch <= 0 || C <= 0 || pixels <= 0) return LLIE_ERR_ARG;
+  return (int64_t)batch * C * (2 * ((pixels + 63) / 64) + 7);  // slab, S, A, Bq, Cq, dG, dBc
+}
+int llie_groupnorm_backward(int dtype, const llie_gn_backward_args* a, float* scratch, int64_t scratch_floats, llie_stream stream) {
+  if (!dtype_ok(dtype) || !a || !scratch) return LLIE_ERR_ARG;
+  const int C = a->c0 + a->c1;
+  if (!a->g || !a->x0 || !a->dx0 || !a->scale || !a->shift || !a->mean || !a->rstd || !a->gamma || !a->beta || !a->dgamma || !a->dbeta ||
+      a->act < ACT_NONE || a->act > ACT_SILU || (a->act != ACT_NONE && !a->dz) || a->batch <= 0 || a->pixels <= 0 || a->c0 <= 0 ||
+      a->c0 % 32 || a->c1 < 0 || a->c1 % 32 || (a->c1 && (!a->x1 || !a->dx1)) || (!a->c1 && (a->x1 || a->dx1 || a->add1_1)) ||
+      (a->dfilm && !a->film) || (a->film && a->film_stride < 0) || (a->dfilm && a->dfilm_stride < 2 * C) ||
+      (int64_t)a->batch * a->pixels * C / (dtype == 0 ? 4 : 8) >= (1ll << 31) ||
+      scratch_floats < llie_groupnorm_backward_scratch_floats(a->batch, C, a->pixels))
+    return LLIE_ERR_ARG;
+  const int nt = (a->pixels + 63) / 64;
+  const size_t bc = (size_t)a->batch * C;
+  GnSiteArgs s{};
+  s.g = a->g; s.dz = a->act == ACT_NONE ? nullptr : a->dz; s.x0 = a->x0; s.x1 = a->x1; s.c0 = a->c0; s.c1 = a->c1;
+  s.as = a->scale; s.ab = a->shift; s.act = a->act; s.mean = a->mean; s.rstd = a->rstd; s.gamma = a->gamma; s.beta = a->beta;
+  s.film = a->film; s.film_stride = a->film_stride; s.dfilm = a->dfilm; s.dfilm_stride = a->dfilm_stride; s.dgamma = a->dgamma; s.dbeta = a->dbeta;
+  s.slab = scratch; s.ntiles = nt; s.slab_ready = 0;
+  s.S = scratch + bc * 2 * nt; s.A = s.S + 2 * bc; s.Bq = s.A + bc; s.Cq = s.Bq + bc; s.dG = s.Cq + bc; s.dBc = s.dG + bc;
+  s.add0 = a->add0; s.add1_0 = a->add1_0; s.add1_1 = a->add1_1; s.dx0 = a->dx0; s.dx1 = a->dx1; s.B = a->batch; s.P = a->pixels;
+  return kerr("groupnorm_backward", launch_gn_site_bwd(dtype, s, reinterpret_cast<hipStream_t>(stream)));
+}
+int64_t llie_linattn_dkv_floats(int batch, int N, int heads) {
+  if (batch <= 0 || N <= 0 || heads <= 0) return LLIE_ERR_ARG;
+  return (int64_t)batch * heads * ((N + 63) / 64 + 1) * 32 * 33;  // tile partials, then their sum
+}
+int llie_linattn_backward(int dtype, const void* qkv, const float* kv_scratch, const void* dout, void* dqkv, float* dkv_scratch,
+                          int64_t dkv_floats, int batch, int N, int heads, llie_stream stream) {
+  if (!dtype_ok(dtype) || !qkv || !kv_scratch || !dout || !dqkv || !dkv_scratch || batch <= 0 || N <= 0 || heads <= 0 ||
+      dkv_floats < llie_linattn_dkv_floats(batch, N, heads))
+    return LLIE_ERR_ARG;
+  AttnBwdArgs a{};
+  a.qkv = qkv; a.dout = dout; a.dqkv = dqkv; a.kv = kv_scratch; a.nsplit = linattn_nsplit(N); a.dkv = dkv_scratch;
+  a.B = batch; a.N = N; a.heads = heads;
+  float* tot = dkv_scratch + (size_t)batch * heads * ((N + 63) / 64) * 32 * 33;
+  return kerr("linattn_backward", launch_linattn_bwd(dtype, a, tot, reinterpret_cast<hipStream_t>(stream)));
+}
+int llie_upsample2x_backward(int dtype, const void* dout, void* din, int batch, int Hi, int Wi, int C, llie_stream stream) {
+  if (!dtype_ok(dtype) || !dout || !din || batch <= 0 || Hi <= 0 || Wi <= 0 || C <= 0 || C % (dtype == 0 ? 4 : 8)) return LLIE_ERR_ARG;
+  return kerr("upsample2x_backward", launch_upsample2x_bwd(dtype, dout, din, batch, Hi, Wi, C, reinterpret_cast<hipStream_t>(stream)));
+}
+int llie_dilate2x(int dtype, const void* in, void* out, int batch, int Hi, int Wi, int C, llie_stream stream) {
+  if (!dtype_ok(dtype) || !in || !out || batch <= 0 || Hi <= 0 || Wi <= 0 || C <= 0 || C % (dtype == 0 ? 4 : 8)) return LLIE_ERR_ARG;
+  return kerr("dilate2x", launch_dilate2x(dtype, in, out, batch, Hi, Wi, C, reinterpret_cast<hipStream_t>(stream)));
+}
+int64_t llie_linear_dx_scratch_floats(int batch, int R, int Kc) {
+  if (batch <= 0 || R <= 0 || Kc <= 0) return LLIE_ERR_ARG;
+  return (int64_t)linear_dx_chunks(R) * batch * Kc;
+}
+int llie_linear_dx(int wdtype, const float* dy, int64_t dy_stride, const void* w, float* dx, int batch, int R, int Kc, float* scratch,
+                   int64_t scratch_floats, llie_stream stream) {
+  if (!dtype_ok(wdtype) || !dy || !w || !dx || batch <= 0 || R <= 0 || Kc <= 0 || dy_stride < R ||
+      (scratch && scratch_floats < llie_linear_dx_scratch_floats(batch, R, Kc)))
+    return LLIE_ERR_ARG;
+  return kerr("linear_dx", launch_linear_dx(wdtype, dy, dy_stride, w, dx, batch, R, Kc, reinterpret_cast<hipStream_t>(stream), scratch));
+}
+int llie_linear_dw(const float* dy, int64_t dy_stride, const float* x, float* dw, float* db, int batch, int R, int Kc, llie_stream stream) {
+  if (!dy || !x || !dw || batch <= 0 || R <= 0 || Kc <= 0 || dy_stride < R) return LLIE_ERR_ARG;
+  return kerr("linear_dw", launch_linear_dw(dy, dy_stride, x, dw, db, batch, R, Kc, reinterpret_cast<hipStream_t>(stream)));
+}
+int llie_final_bwd_data(int dtype, const float* deps, const float* w, void* da, int batch, int H, int W, int C, int Cout, llie_stream stream) {
+  if (!dtype_ok(dtype) || !deps || !w || !da || batch <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || Cout < 1 || Cout > 4) return LLIE_ERR_ARG;
+  FinalBwdArgs a{};
+  a.deps = deps; a.w = w; a.da = da; a.B = batch; a.H = H; a.W = W; a.C = C; a.Cout = Cout;
+  return kerr("final_bwd_data", launch_final_bwd_data(dtype, a, reinterpret_cast<hipStream_t>(stream)));
 }
 
 int llie_preprocess_u8(const uint8_t* img, int batch, int H0, int W0, float* out, int S, llie_stream stream) {

@@ -402,6 +402,25 @@ struct GnApplyArgs {
   int M, P;
 };
 hipError_t launch_gn_bwd_apply(int dtype, const GnApplyArgs& a, hipStream_t s);
+// One norm site of the training backward, in the engine's order: (1) bwd_mask_reduce (skipped when the producer already wrote dz
+// and the tile partials: slab_ready), the tile partials summed inside gn_bwd_coef (C / 32 <= 64) or by slab_reduce into S,
+// (2) gn_bwd_coef, gn_param_grad, (3) gn_bwd_apply.  32 groups.  Scratch: slab [B][ntiles][2][C], S [B][2][C] (used only when
+// C / 32 > 64), A / Bq / Cq / dG / dBc [B][C].
+struct GnSiteArgs {
+  const void* g; void* dz;            // incoming gradient of act(norm(x)); dz = g * act' (may alias g; null: act none, g is dz)
+  const void* x0; const void* x1; int c0, c1;
+  const float* as; const float* ab; int act;                    // forward record: the norm's affine, the activation
+  const float* mean; const float* rstd;                         // forward record [B][32]
+  const float* gamma; const float* beta;
+  const float* film; int64_t film_stride; float* dfilm; int64_t dfilm_stride;
+  float* dgamma; float* dbeta;
+  float* slab; int ntiles; int slab_ready;
+  float* S; float* A; float* Bq; float* Cq; float* dG; float* dBc;
+  const void* add0; const void* add1_0; const void* add1_1;     // as GnApplyArgs
+  void* dx0; void* dx1;
+  int B, P;
+};
+hipError_t launch_gn_site_bwd(int dtype, const GnSiteArgs& a, hipStream_t s);
 hipError_t launch_add_into(int dtype, void* dst, const void* src, int64_t n, hipStream_t s);   // dst += src
 hipError_t launch_fill_zero(void* dst, int64_t bytes, hipStream_t s);
 hipError_t launch_zero_fill(void* dst, int64_t bytes, hipStream_t s);  // kernel, not a memset node
@@ -481,6 +500,8 @@ struct AttnBwdArgs {
 };
 hipError_t launch_linattn_bwd_q(int dtype, const AttnBwdArgs& a, hipStream_t s);
 hipError_t launch_linattn_bwd_kv(int dtype, const AttnBwdArgs& a, hipStream_t s);
+// both passes: a.dkv = the tile partials [B][heads][ceil(N/64)][32][33], reduced in tile order into tot [B][heads][32][33]
+hipError_t launch_linattn_bwd(int dtype, const AttnBwdArgs& a, float* tot, hipStream_t s);
 
 // (9) optimiser step over all parameter tensors (optim.hip): gradient norm -> clip coefficient -> AdamW (+ EMA shadow)
 constexpr int kOptChunk = 4096;  // elements per workgroup

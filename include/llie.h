@@ -333,6 +333,69 @@ int llie_se_mlp(int dtype, const float* pool_sums, int pixels, const void* w1, c
                 float* hidden_scratch, float* gate, int batch, int C, int Cs, llie_stream stream);
 int llie_film(const float* silu_temb, const float* wf, const float* bf, float* film, int rows, int T, int F, llie_stream stream);
 
+/* ---- Backward kernels of the training step (bwd.hip, wgrad.hip), one entry point each, with the conventions above: dtype 0 / 1 / 2,
+ * NHWC activations and activation gradients of the compute type, fp32 tables and parameter gradients, device pointers.  Every
+ * entry point returns LLIE_ERR_ARG for a bad argument before it makes any HIP call.
+ *
+ * llie_wgrad: weight gradient of a 1x1 conv, or of a 3x3 conv (ntap 9: all taps; ntap 1: the single tap (dy, dx) in -1..1) --
+ *   out[n*ldn + k*ldk + off (+ tap)] = sum_m g[m][n] * A'[src(m)][k] for n < nstore, k < kstore (0 = all), A' = act(A_seg * scale +
+ *   bias) rounded to the compute type (up to 3 K-segments as llie_pw_gemm; act 0 none, 1 ReLU6, 2 SiLU), m = (b, y, x) over
+ *   Ho x Wo, src(m) = input pixel (y*stride + dy, x*stride + dx) of an Hi x Wi map (zero outside).  g: [batch*Ho*Wo][N];
+ *   N and every segment's channels multiples of 32.  The pixel rows are split msplit ways (0: llie_wgrad_msplit with
+ *   ragged_rule = (Ho*Wo % 64 != 0)) into partial [msplit][ntap][N][K] fp32 (llie_wgrad_partial_floats), summed in split order.
+ * llie_wgrad_msplit: the split the engine takes for these sizes: ragged_rule 0 = the rule at image sizes that are multiples of
+ *   64, 1 = the rule of every other image size.
+ * llie_dw_wgrad: depthwise 3x3 weight gradient out[c][tap] (reference layout [C][1][3][3]) = sum over (b, y, x) of
+ *   (g*gs + gb) * relu6(h*scale + shift) at the tap's input pixel; gs / gb (or NULL) and scale / shift are [batch][C];
+ *   C a multiple of 32 (fp32) or 64 (2-byte); partial: batch * llie_dw_wgrad_strips(H, W) * 9 * C floats.
+ * llie_groupnorm_backward: one GroupNorm(32, C) site of the backward pass as the engine runs it, for
+ *   y = act((xhat * gamma + beta) * (1 + s) + f) with the forward record (scale / shift = the affine x*scale + shift of
+ *   llie_groupnorm_finalize, mean / rstd [batch][32]): dz = g * act' (stored over dz, which may alias g; act 0 none, 1 ReLU6,
+ *   2 SiLU), dgamma / dbeta [C], with FiLM rows (film[b][c] = s, film[b][C + c] = f, row stride film_stride) also dfilm
+ *   (same layout; NULL = not wanted), and dx = d/dx (+ add0, dense [M][C]) (+ add1, split like x), written to dx0 / dx1.  x0 / x1:
+ *   a virtual concat of c0 + c1 channels (c1 = 0: no x1).  scratch: llie_groupnorm_backward_scratch_floats floats.
+ * llie_linattn_backward: gradient dqkv [batch][N][3 * 32 heads] of llie_linattn w.r.t. its qkv, given d(out); kv_scratch: what
+ *   llie_linattn left there for the same qkv; dkv_scratch: llie_linattn_dkv_floats floats (the per-64-position partials
+ *   [batch][heads][ceil(N/64)][32][33], then their sum).
+ * llie_upsample2x_backward: adjoint of bilinear x2 (align_corners=False): [batch][2Hi][2Wi][C] -> [batch][Hi][Wi][C];
+ *   llie_dilate2x: out[2y][2x] = in[y][x], zero elsewhere.  C a multiple of 4 (fp32) or 8.
+ * llie_linear_dx: dx[b][k] = sum_r dy[b * dy_stride + r] * w[r][k] (w [R][Kc] of the type wdtype, dx fp32); scratch (or NULL):
+ *   llie_linear_dx_scratch_floats floats, lets a long R run in parallel chunks.  llie_linear_dw: dw[r][k] = sum_b dy[b][r] x[b][k],
+ *   db[r] = sum_b dy[b][r] (db may be NULL).
+ * llie_final_bwd_data: input gradient of the output head's 3x3 conv (pad 1): da[b][y][x][c] (NHWC, compute type) =
+ *   sum_{o,tap} deps[b][o][y - ky + 1][x - kx + 1] * w[tap][c][o], deps fp32 NCHW [batch][Cout][H][W], w fp32 [9][C][4], Cout <= 4. */
+int llie_wgrad(int dtype, const void* g, int N, const llie_gemm_seg* segs, int nseg, int batch, int Ho, int Wo, int Hi, int Wi, int stride,
+               int dy, int dx, int ntap, int nstore, int kstore, float* partial, int64_t partial_floats, float* out, int64_t ldn, int64_t ldk,
+               int64_t off, int msplit, llie_stream stream);
+int llie_wgrad_msplit(int dtype, int batch, int pixels, int N, int K, int ntap, int ragged_rule);
+int64_t llie_wgrad_partial_floats(int msplit, int N, int K, int ntap);
+int llie_dw_wgrad(int dtype, const void* g, const float* gs, const float* gb, const void* h, const float* scale, const float* shift,
+                  float* partial, float* out, int batch, int H, int W, int C, llie_stream stream);
+int llie_dw_wgrad_strips(int H, int W);
+typedef struct llie_gn_backward_args {
+  const void* g; void* dz;
+  const void* x0; const void* x1; int c0, c1;
+  const float* scale; const float* shift; int act;
+  const float* mean; const float* rstd; const float* gamma; const float* beta;
+  const float* film; int64_t film_stride; float* dfilm; int64_t dfilm_stride;
+  float* dgamma; float* dbeta;
+  const void* add0; const void* add1_0; const void* add1_1;
+  void* dx0; void* dx1;
+  int batch, pixels;
+} llie_gn_backward_args;
+int llie_groupnorm_backward(int dtype, const llie_gn_backward_args* args, float* scratch, int64_t scratch_floats, llie_stream stream);
+int64_t llie_groupnorm_backward_scratch_floats(int batch, int C, int pixels);
+int llie_linattn_backward(int dtype, const void* qkv, const float* kv_scratch, const void* dout, void* dqkv, float* dkv_scratch,
+                          int64_t dkv_floats, int batch, int N, int heads, llie_stream stream);
+int64_t llie_linattn_dkv_floats(int batch, int N, int heads);
+int llie_upsample2x_backward(int dtype, const void* dout, void* din, int batch, int Hi, int Wi, int C, llie_stream stream);
+int llie_dilate2x(int dtype, const void* in, void* out, int batch, int Hi, int Wi, int C, llie_stream stream);
+int llie_linear_dx(int wdtype, const float* dy, int64_t dy_stride, const void* w, float* dx, int batch, int R, int Kc, float* scratch,
+                   int64_t scratch_floats, llie_stream stream);
+int64_t llie_linear_dx_scratch_floats(int batch, int R, int Kc);
+int llie_linear_dw(const float* dy, int64_t dy_stride, const float* x, float* dw, float* db, int batch, int R, int Kc, llie_stream stream);
+int llie_final_bwd_data(int dtype, const float* deps, const float* w, void* da, int batch, int H, int W, int C, int Cout, llie_stream stream);
+
 /* Statistics pass of the recompute form of InvertedResidualBlock (efficient_unet.py:207-212) on its own: Gram matrix
  * G = sum_px a' a'^T and column sums m = sum_px a' of a' = clamp01(x * scale + bias) rounded to the compute type, per image
  * (gram.hip).  x0 / x1: NHWC [batch][pixels][c0 / c1] of the compute type (x1 may be NULL with c1 = 0), c0 + c1 in {32, 64, 96},

@@ -494,6 +494,81 @@ def test_groupnorm_finalize_rejects_bad_arguments_before_touching_the_device():
         assert call(**kw) < 0, kw
 
 
+def test_backward_kernel_entry_points_reject_bad_arguments_without_a_device():
+    """The per-kernel backward entry points (include/llie.h: llie_wgrad .. llie_final_bwd_data) check their whole contract on the
+    host: null pointers, bad dtypes / acts / tap counts, sizes the kernels do not take, splits beyond the rows, too-small partial /
+    scratch buffers and inconsistent concat or FiLM arguments come back as LLIE_ERR_ARG before any HIP call, so this runs without a
+    GPU; pointers are dummies that are never read."""
+    import ctypes as C
+    L = native.lib()
+    buf = (C.c_float * 64)()
+    p = C.cast(buf, C.c_void_p).value
+    E = native.ERR_ARG
+
+    def wg(dtype=2, g=p, n=64, segs=((p, 64, None, None, 0, 0),), batch=2, Ho=16, Wo=16, Hi=16, Wi=16, stride=1, dy=0, dx=0, ntap=1,
+           nstore=0, kstore=0, part=p, pf=1 << 30, out=p, ms=0):
+        arr = (native.GemmSeg * max(1, len(segs)))(*[native.GemmSeg(*s) for s in segs])
+        return L.llie_wgrad(dtype, g, n, arr, len(segs), batch, Ho, Wo, Hi, Wi, stride, dy, dx, ntap, nstore, kstore, part, pf, out,
+                            64, 1, 0, ms, None)
+    bad_wgrad = [dict(dtype=3), dict(g=None), dict(part=None), dict(out=None), dict(n=48), dict(n=0), dict(segs=()),
+                 dict(segs=((p, 64, None, None, 0, 0),) * 4), dict(segs=((None, 64, None, None, 0, 0),)),
+                 dict(segs=((p, 40, None, None, 0, 0),)), dict(segs=((p, 64, p, None, 32, 1),)),    # affine row shorter than the segment
+                 dict(segs=((p, 64, None, p, 64, 1),)),                                              # shift without scale
+                 dict(segs=((p, 64, p, p, 64, 3),)), dict(ntap=3), dict(stride=3), dict(dy=2), dict(batch=0),
+                 dict(nstore=65), dict(kstore=-1), dict(ms=9), dict(ms=-1), dict(pf=64 * 64 - 1, ms=1),
+                 dict(Ho=9, Wo=9, Hi=16, Wi=16, stride=2)]                                           # output grid leaves the input
+    for kw in bad_wgrad:
+        assert wg(**kw) == E, kw
+    assert L.llie_wgrad_msplit(2, 0, 256, 64, 64, 1, 0) == E and L.llie_wgrad_msplit(2, 1, 256, 64, 64, 3, 0) == E
+    assert L.llie_wgrad_msplit(2, 2, 256, 64, 64, 9, 0) >= 1 and L.llie_wgrad_partial_floats(3, 32, 64, 9) == 3 * 9 * 32 * 64
+    assert L.llie_wgrad_partial_floats(0, 32, 64, 1) == E
+
+    def dw(dtype=1, g=p, h=p, sc=p, sh=p, part=p, out=p, B=1, H=16, W=16, Cc=64):
+        return L.llie_dw_wgrad(dtype, g, None, None, h, sc, sh, part, out, B, H, W, Cc, None)
+    for kw in (dict(dtype=-1), dict(g=None), dict(h=None), dict(sc=None), dict(sh=None), dict(part=None), dict(out=None), dict(B=0),
+               dict(H=0), dict(W=0), dict(Cc=32), dict(dtype=0, Cc=48)):
+        assert dw(**kw) == E, kw
+    assert L.llie_dw_wgrad_strips(0, 8) == E and L.llie_dw_wgrad_strips(40, 25) == 8
+
+    def gn(dtype=2, scratch=p, nscr=1 << 30, **kw):
+        a = native.GnBackwardArgs()
+        for k, v in dict(g=p, dz=p, x0=p, c0=64, scale=p, shift=p, act=1, mean=p, rstd=p, gamma=p, beta=p, dgamma=p, dbeta=p, dx0=p,
+                         batch=2, pixels=81).items():
+            setattr(a, k, v)
+        for k, v in kw.items():
+            setattr(a, k, v)
+        return L.llie_groupnorm_backward(dtype, C.byref(a), scratch, nscr, None)
+    for kw in (dict(dtype=3), dict(scratch=None), dict(nscr=2 * 64 * 11 - 1), dict(g=None), dict(x0=None), dict(dx0=None), dict(mean=None),
+               dict(dgamma=None), dict(act=3), dict(act=2, dz=None), dict(c0=48), dict(c0=0), dict(c1=32), dict(c1=32, x1=p),
+               dict(x1=p), dict(dfilm=p, dfilm_stride=128), dict(dfilm=p, film=p, dfilm_stride=127), dict(batch=0), dict(pixels=0)):
+        assert gn(**kw) == E, kw
+    assert L.llie_groupnorm_backward(2, None, p, 1 << 30, None) == E
+    assert L.llie_groupnorm_backward_scratch_floats(2, 64, 81) == 2 * 64 * (2 * 2 + 7)
+
+    nd = L.llie_linattn_dkv_floats(2, 81, 4)
+    assert nd == 2 * 4 * 3 * 32 * 33
+    for args in ((3, p, p, p, p, p, nd, 2, 81, 4), (1, None, p, p, p, p, nd, 2, 81, 4), (1, p, None, p, p, p, nd, 2, 81, 4),
+                 (1, p, p, None, p, p, nd, 2, 81, 4), (1, p, p, p, None, p, nd, 2, 81, 4), (1, p, p, p, p, None, nd, 2, 81, 4),
+                 (1, p, p, p, p, p, nd - 1, 2, 81, 4), (1, p, p, p, p, p, nd, 2, 0, 4), (1, p, p, p, p, p, nd, 2, 81, 0)):
+        assert L.llie_linattn_backward(*args, None) == E, args
+    for f in (L.llie_upsample2x_backward, L.llie_dilate2x):
+        for args in ((3, p, p, 1, 4, 4, 32), (1, None, p, 1, 4, 4, 32), (1, p, None, 1, 4, 4, 32), (1, p, p, 0, 4, 4, 32),
+                     (1, p, p, 1, 4, 4, 12), (0, p, p, 1, 4, 4, 6), (1, p, p, 1, 0, 4, 32)):
+            assert f(*args, None) == E, (f, args)
+    ns = L.llie_linear_dx_scratch_floats(2, 1000, 64)
+    assert ns == 8 * 2 * 64 and L.llie_linear_dx_scratch_floats(2, 200, 64) == 2 * 64
+    for args in ((3, p, 1000, p, p, 2, 1000, 64, p, ns), (0, None, 1000, p, p, 2, 1000, 64, p, ns), (0, p, 999, p, p, 2, 1000, 64, p, ns),
+                 (0, p, 1000, None, p, 2, 1000, 64, p, ns), (0, p, 1000, p, None, 2, 1000, 64, p, ns), (0, p, 1000, p, p, 0, 1000, 64, p, ns),
+                 (0, p, 1000, p, p, 2, 1000, 64, p, ns - 1)):
+        assert L.llie_linear_dx(*args, None) == E, args
+    for args in ((None, 8, p, p, p, 2, 8, 4), (p, 7, p, p, p, 2, 8, 4), (p, 8, None, p, p, 2, 8, 4), (p, 8, p, None, p, 2, 8, 4),
+                 (p, 8, p, p, p, 2, 8, 0)):
+        assert L.llie_linear_dw(*args, None) == E, args
+    for args in ((3, p, p, p, 1, 8, 8, 32, 3), (1, None, p, p, 1, 8, 8, 32, 3), (1, p, None, p, 1, 8, 8, 32, 3), (1, p, p, None, 1, 8, 8, 32, 3),
+                 (1, p, p, p, 1, 8, 8, 36, 3), (1, p, p, p, 1, 8, 8, 32, 5), (1, p, p, p, 1, 8, 8, 32, 0), (1, p, p, p, 1, 0, 8, 32, 3)):
+        assert L.llie_final_bwd_data(*args, None) == E, args
+
+
 def test_optimizer_entry_points_reject_bad_arguments_without_a_device():
     """llie_optimizer_create / _step (include/llie.h): null tables, empty tensors and negative gradient offsets come back as
     LLIE_ERR_ARG before any HIP call; FusedAdamW refuses CPU parameters (no CPU fallback) and more than one parameter group."""
