@@ -56,8 +56,7 @@ __device__ __forceinline__ void dw_body_impl(const DwArgs& a, const int TYL, con
 
   const int tid = threadIdx.x, cl = tid & 7, xl = tid >> 3;
   const int tiles_x = (a.W + TX - 1) / TX;
-  // grid: x = channel chunk (fastest, so the workgroups that share a strip's DRAM pages are dispatched together when
-  // g_dw_swap is set), y = strip; or x = strip, y = chunk
+  // grid: x = strip, y = channel chunk (swap = 1, the other order, lost and is never launched)
   const int tile_id = swap ? blockIdx.y : blockIdx.x, chunk_id = swap ? blockIdx.x : blockIdx.y;
   const int tx = tile_id % tiles_x, ty = tile_id / tiles_x;
   const int x0 = tx * TX, y0 = ty * TYL;
@@ -255,28 +254,34 @@ __device__ __forceinline__ void dw_body_impl(const DwArgs& a, const int TYL, con
   }
 }
 
+// dbg (bit 0: no MACs, bit 1: no activation) and swap are the run-time flags of retired timing experiments: every launch
+// passes 0.  The fp16 forward kernels fold them away (their MACs are pinned by the v_fma_mix asm above).  The fp32 and bf16
+// forward kernels keep them as live arguments, so that their code stays the parent's, instruction for instruction: with
+// the flags folded hipcc contracts the first two products of an output row the other way round (other bits, seen in the
+// fp32 engine) and spills 16 bytes per thread inside the row loop of the bf16 kernel under its 168-VGPR cap (DESIGN.md
+// section 8, round 2 lessons).
+template <typename T> constexpr bool kDwLiveFlags = !std::is_same<T, half_t>::value;
 template <typename T, int TX, int PFV, bool S6 = false>
 __global__ void __launch_bounds__(8 * TX, (std::is_same<T, bf16_t>::value ? 3 : 1))
 dwconv3x3_kernel(const DwArgs a, const int TYL, const int dbg, const int swap) {
-  dw_body<T, TX, PFV, false, S6>(a, TYL, dbg, swap);
+  if constexpr (kDwLiveFlags<T>) dw_body<T, TX, PFV, false, S6>(a, TYL, dbg, swap);
+  else dw_body<T, TX, PFV, false, S6>(a, TYL, 0, 0);
 }
 template <typename T, int TX, int PFV, bool S6 = false>
 __global__ void __launch_bounds__(8 * TX) dwconv3x3_ragged_kernel(const DwArgs a, const int TYL, const int dbg, const int swap) {
-  dw_body_impl<T, TX, PFV, false, S6, true>(a, TYL, dbg, swap);  // partial strips at the right / bottom edge (W % 8 or H % 8 != 0)
+  // partial strips at the right / bottom edge (W % 8 or H % 8 != 0)
+  if constexpr (kDwLiveFlags<T>) dw_body_impl<T, TX, PFV, false, S6, true>(a, TYL, dbg, swap);
+  else dw_body_impl<T, TX, PFV, false, S6, true>(a, TYL, 0, 0);
 }
 template <typename T, int TX, int PFV>
-__global__ void __launch_bounds__(8 * TX) dwconv3x3_bwd_kernel(const DwArgs a, const int TYL, const int swap) {
-  dw_body<T, TX, PFV, true>(a, TYL, 0, swap);
+__global__ void __launch_bounds__(8 * TX) dwconv3x3_bwd_kernel(const DwArgs a, const int TYL) {
+  dw_body<T, TX, PFV, true>(a, TYL, 0, 0);
 }
 template <typename T, int TX, int PFV>
-__global__ void __launch_bounds__(8 * TX) dwconv3x3_bwd_ragged_kernel(const DwArgs a, const int TYL, const int swap) {
-  dw_body_impl<T, TX, PFV, true, false, true>(a, TYL, 0, swap);  // partial strips at the right / bottom edge
+__global__ void __launch_bounds__(8 * TX) dwconv3x3_bwd_ragged_kernel(const DwArgs a, const int TYL) {
+  dw_body_impl<T, TX, PFV, true, false, true>(a, TYL, 0, 0);  // partial strips at the right / bottom edge
 }
 
-static int g_dw_swap = 0;
-void dwconv_swap(int v) { g_dw_swap = v; }
-static int g_dw_dbg = 0;
-void dwconv_debug(int v) { g_dw_dbg = v; }  // bits 0-1: timing ablations
 static int dw_tx(int W) { return (W % 32 == 0) ? 32 : ((W % 16 == 0) ? 16 : (W % 8 == 0 ? 8 : (W > 16 ? 32 : 16))); }
 // Strip height: as tall as possible (fewer halo rows) while the launch still has >= 1024 workgroups to
 // fill 256 CUs; small batches get shorter strips.  `chunks` = C / channels per WG.  The pool slab does
@@ -299,7 +304,6 @@ static hipError_t launch_dw_t(const DwArgs& a, hipStream_t s) {
   const int tx = dw_tx(a.W), tyl = dw_pick_tyl(a.B, a.H, a.W, a.C / CC);
   const int tiles = ((a.W + tx - 1) / tx) * ((a.H + tyl - 1) / tyl);
   dim3 grid(tiles, a.C / CC, a.B);
-  if (g_dw_swap) grid = dim3(a.C / CC, tiles, a.B);
   static const std::string names[3] = {std::string("dwconv3x3_kernel<") + TypeName<T>::value + ", 32, 4>",
                                        std::string("dwconv3x3_kernel<") + TypeName<T>::value + ", 16, 4>",
                                        std::string("dwconv3x3_kernel<") + TypeName<T>::value + ", 8, 4>"};
@@ -307,8 +311,8 @@ static hipError_t launch_dw_t(const DwArgs& a, hipStream_t s) {
   if (ragged && a.bx) {  // backward instantiation; TX is 16 or 32 here
     if (!a.bas || !a.bab || !a.bslab || a.pool || a.s6) return hipErrorInvalidValue;
     note_kernel("dwconv3x3_bwd_ragged_kernel");
-    if (tx == 32) hipLaunchKernelGGL((dwconv3x3_bwd_ragged_kernel<T, 32, kDwPF>), grid, dim3(256), 0, s, a, tyl, g_dw_swap);
-    else hipLaunchKernelGGL((dwconv3x3_bwd_ragged_kernel<T, 16, kDwPF>), grid, dim3(128), 0, s, a, tyl, g_dw_swap);
+    if (tx == 32) hipLaunchKernelGGL((dwconv3x3_bwd_ragged_kernel<T, 32, kDwPF>), grid, dim3(256), 0, s, a, tyl);
+    else hipLaunchKernelGGL((dwconv3x3_bwd_ragged_kernel<T, 16, kDwPF>), grid, dim3(128), 0, s, a, tyl);
     return hipGetLastError();
   }
   if (ragged) {  // TX is 16 or 32 here
@@ -316,38 +320,38 @@ static hipError_t launch_dw_t(const DwArgs& a, hipStream_t s) {
     if constexpr (sizeof(T) == 2) {
       if (a.s6) {
         if (a.no_act) return hipErrorInvalidValue;
-        if (tx == 32) hipLaunchKernelGGL((dwconv3x3_ragged_kernel<T, 32, kDwPF, true>), grid, dim3(256), 0, s, a, tyl, 0, g_dw_swap);
-        else hipLaunchKernelGGL((dwconv3x3_ragged_kernel<T, 16, kDwPF, true>), grid, dim3(128), 0, s, a, tyl, 0, g_dw_swap);
+        if (tx == 32) hipLaunchKernelGGL((dwconv3x3_ragged_kernel<T, 32, kDwPF, true>), grid, dim3(256), 0, s, a, tyl, 0, 0);
+        else hipLaunchKernelGGL((dwconv3x3_ragged_kernel<T, 16, kDwPF, true>), grid, dim3(128), 0, s, a, tyl, 0, 0);
         return hipGetLastError();
       }
     } else if (a.s6) {
       return hipErrorInvalidValue;
     }
-    if (tx == 32) hipLaunchKernelGGL((dwconv3x3_ragged_kernel<T, 32, kDwPF>), grid, dim3(256), 0, s, a, tyl, 0, g_dw_swap);
-    else hipLaunchKernelGGL((dwconv3x3_ragged_kernel<T, 16, kDwPF>), grid, dim3(128), 0, s, a, tyl, 0, g_dw_swap);
+    if (tx == 32) hipLaunchKernelGGL((dwconv3x3_ragged_kernel<T, 32, kDwPF>), grid, dim3(256), 0, s, a, tyl, 0, 0);
+    else hipLaunchKernelGGL((dwconv3x3_ragged_kernel<T, 16, kDwPF>), grid, dim3(128), 0, s, a, tyl, 0, 0);
     return hipGetLastError();
   }
   if (a.bx) {  // backward instantiation
     if (!a.bas || !a.bab || !a.bslab || a.pool) return hipErrorInvalidValue;
-    if (tx == 32) hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, 32, kDwPF>), grid, dim3(256), 0, s, a, tyl, g_dw_swap);
-    else if (tx == 16) hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, 16, kDwPF>), grid, dim3(128), 0, s, a, tyl, g_dw_swap);
-    else hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, 8, kDwPF>), grid, dim3(64), 0, s, a, tyl, g_dw_swap);
+    if (tx == 32) hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, 32, kDwPF>), grid, dim3(256), 0, s, a, tyl);
+    else if (tx == 16) hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, 16, kDwPF>), grid, dim3(128), 0, s, a, tyl);
+    else hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, 8, kDwPF>), grid, dim3(64), 0, s, a, tyl);
     return hipGetLastError();
   }
   if constexpr (sizeof(T) == 2) {
     if (a.s6) {
       if (a.no_act) return hipErrorInvalidValue;
-      if (tx == 32) hipLaunchKernelGGL((dwconv3x3_kernel<T, 32, kDwPF, true>), grid, dim3(256), 0, s, a, tyl, g_dw_dbg & 3, g_dw_swap);
-      else if (tx == 16) hipLaunchKernelGGL((dwconv3x3_kernel<T, 16, kDwPF, true>), grid, dim3(128), 0, s, a, tyl, g_dw_dbg & 3, g_dw_swap);
-      else hipLaunchKernelGGL((dwconv3x3_kernel<T, 8, kDwPF, true>), grid, dim3(64), 0, s, a, tyl, g_dw_dbg & 3, g_dw_swap);
+      if (tx == 32) hipLaunchKernelGGL((dwconv3x3_kernel<T, 32, kDwPF, true>), grid, dim3(256), 0, s, a, tyl, 0, 0);
+      else if (tx == 16) hipLaunchKernelGGL((dwconv3x3_kernel<T, 16, kDwPF, true>), grid, dim3(128), 0, s, a, tyl, 0, 0);
+      else hipLaunchKernelGGL((dwconv3x3_kernel<T, 8, kDwPF, true>), grid, dim3(64), 0, s, a, tyl, 0, 0);
       return hipGetLastError();
     }
   } else if (a.s6) {
     return hipErrorInvalidValue;
   }
-  if (tx == 32) hipLaunchKernelGGL((dwconv3x3_kernel<T, 32, kDwPF>), grid, dim3(256), 0, s, a, tyl, g_dw_dbg & 3, g_dw_swap);
-  else if (tx == 16) hipLaunchKernelGGL((dwconv3x3_kernel<T, 16, kDwPF>), grid, dim3(128), 0, s, a, tyl, g_dw_dbg & 3, g_dw_swap);
-  else hipLaunchKernelGGL((dwconv3x3_kernel<T, 8, kDwPF>), grid, dim3(64), 0, s, a, tyl, g_dw_dbg & 3, g_dw_swap);
+  if (tx == 32) hipLaunchKernelGGL((dwconv3x3_kernel<T, 32, kDwPF>), grid, dim3(256), 0, s, a, tyl, 0, 0);
+  else if (tx == 16) hipLaunchKernelGGL((dwconv3x3_kernel<T, 16, kDwPF>), grid, dim3(128), 0, s, a, tyl, 0, 0);
+  else hipLaunchKernelGGL((dwconv3x3_kernel<T, 8, kDwPF>), grid, dim3(64), 0, s, a, tyl, 0, 0);
   return hipGetLastError();
 }
 

@@ -549,14 +549,11 @@ int build_module(llie_ctx* c) {
 // inference path of 2-byte engines wherever irbx_supported(); llie_tune("irbx", 0) restores the unfused pair.
 int g_use_irbx = getenv("LLIE_NO_IRBX") ? 0 : 1;
 int g_gram = 1;  // norm2 statistics of the recompute form from the Gram matrix of the block input (gram.hip); 0 = expand_stats
-int g_ztot = 1;  // SE pool as fixed-point totals + fused gate kernel (llie_tune("ztot", 0): the slab + three launches, as in training)
 // Cache policy of the big activation tensors (inference): a tensor of at least g_nt_min_mb MiB (this run's batch) is stored
 // non-temporally by its producer (common.h: st_vec_pol).  g_nt_mask picks the producers: 1 expand_dw (h2), 2 pw_expand (h1),
 // 4 dwconv3x3 (h2), 8 project / attention GEMM outputs, 16 dense 3x3 conv outputs.  Values never change, only where lines live.
 int g_nt_min_mb = 100, g_nt_mask = 1;
 int g_se_mfma = 1;  // SE MLP of the wide blocks as two MFMA launches (small.hip: se_fc1_mfma / se_fc2_mfma); 0 = the row-parallel pair
-int g_skip_small = 0;  // timing ablation only (results are garbage): bit 0 no gn_finalize launches, bit 1 no SE launches
-int g_irbx_mask = 0x7;  // debug: which input widths may take the recompute form (bit 0: 32, bit 1: 64, bit 2: 96 channels)
 // Backward pass: run the weight-gradient kernels on a side stream next to the activation-gradient chain
 // (llie_tune("bwd_async", 0) puts everything back on the caller's stream).
 int g_bwd_async = 1;
@@ -671,11 +668,6 @@ struct Run {
     a.film = film; a.film_stride = film_stride; a.eps = 1e-5f;
     a.as = p<float>(as); a.ab = p<float>(ab); a.B = B; a.post_scale = post_scale;
     if (tape && rec) { a.mean_out = p<float>(mo); a.rstd_out = p<float>(ro); }
-    if (g_skip_small & 1) return;
-    if ((g_skip_small & 4) && film && a.P <= 4096) return;          // bound on a producer-tail finalize behind pw_expand (norm2 + FiLM)
-    if ((g_skip_small & 8) && !film && !x1 && a.P <= 4096) return;  // ... behind project GEMMs / convs (norm1, single source)
-    if ((g_skip_small & 16) && !film && !x1 && a.P >= 16384) return; // the single-source norm1 finalizes of the high-resolution levels
-    if ((g_skip_small & 32) && (film || x1) && a.P >= 16384) return; // the other high-resolution ones (norm2 + FiLM behind expand_stats / pw_expand, concat inputs)
     timed(LLIE_K_OTHER, (int64_t)B * C * 8, [&] { return launch_gn_finalize(a, s); }, "gn_finalize_kernel");
   }
 
@@ -692,7 +684,7 @@ struct Run {
     gn(x0, x1, w.n1g, w.n1b, nullptr, 0, as1, ab1, &rec.n1, s6 ? 1.f / 6.f : 0.f);
     // Recompute form (2-byte T, narrow inputs): a statistics-only expand pass, then the fused expand + depthwise kernel
     // rebuilds h1 on the fly, so the 4x-expanded tensor never touches HBM (irbx.hip).
-    const bool fusedx = !tape && g_use_irbx && w.hid == w.hid_r && w.cin == w.cin_r && ((g_irbx_mask >> (w.cin / 32 - 1)) & 1) &&
+    const bool fusedx = !tape && g_use_irbx && w.hid == w.hid_r && w.cin == w.cin_r &&
                         irbx_supported(dt, w.cin, x0.C, w.hid, H, W);
     // K1: expand with norm1 + ReLU6 prologue
     Tens h1;
@@ -755,7 +747,7 @@ struct Run {
     if (gram) {
       as2 = ar->alloc((size_t)B * w.hid * 4);
       ab2 = ar->alloc((size_t)B * w.hid * 4);
-      if (!dry && !(g_skip_small & 1)) {
+      if (!dry) {
         GramFinalizeArgs fa{};
         fa.gtot = p<float>(gtot); fa.w1 = wptr(w.w_expand); fa.K = w.cin; fa.Chid = w.hid; fa.groups = gn_groups(w.hid); fa.P = P; fa.B = B;
         fa.gamma = wptr<float>(w.n2g); fa.beta = wptr<float>(w.n2b);
@@ -772,21 +764,21 @@ struct Run {
     const size_t h2 = ar->alloc((size_t)M * w.hid * es());
     // SE pool: inference adds fixed-point channel totals into the zeroed region (one gate kernel follows); training keeps
     // the slab of tile partials (the backward pass and the 3-launch SE path read it)
-    const bool ztot = !tape && g_ztot && w.hid % 128 == 0;
-    const size_t pool = ztot ? 0 : ar->alloc((size_t)B * dnt * w.hid * 4);
-    const size_t ptot = ztot ? ztake((size_t)B * w.hid * 8) : 0;
+    const bool fixtot = !tape && w.hid % 128 == 0;
+    const size_t pool = fixtot ? 0 : ar->alloc((size_t)B * dnt * w.hid * 4);
+    const size_t ptot = fixtot ? ztake((size_t)B * w.hid * 8) : 0;
     if (!dry) {
       if (fusedx) {
         xa.as2 = p<float>(as2); xa.ab2 = p<float>(ab2); xa.out = p(h2);
-        xa.pool = ztot ? nullptr : p<float>(pool);
-        xa.pool_tot = ztot ? p<unsigned long long>(ptot) : nullptr;
+        xa.pool = fixtot ? nullptr : p<float>(pool);
+        xa.pool_tot = fixtot ? p<unsigned long long>(ptot) : nullptr;
         xa.nt = w.cin <= 64 ? nt_store(1, (int64_t)M * w.hid) : 0;  // 96 -> 384: the kernel itself loses more than its consumer gains
         timed(LLIE_K_DW, (int64_t)M * (w.cin + w.hid) * (int64_t)es(), [&] { return launch_expand_dw(dt, xa, s); });
       } else {
         DwArgs d{};
         d.in = p(h1.off); d.out = p(h2); d.as = p<float>(as2); d.ab = p<float>(ab2);
-        d.w = wptr<float>(w.w_dw); d.pool = ztot ? nullptr : p<float>(pool);
-        d.pool_tot = ztot ? p<unsigned long long>(ptot) : nullptr; d.B = B; d.H = H; d.W = W; d.C = w.hid; d.s6 = s6dw ? 1 : 0;
+        d.w = wptr<float>(w.w_dw); d.pool = fixtot ? nullptr : p<float>(pool);
+        d.pool_tot = fixtot ? p<unsigned long long>(ptot) : nullptr; d.B = B; d.H = H; d.W = W; d.C = w.hid; d.s6 = s6dw ? 1 : 0;
         d.nt = nt_store(4, (int64_t)M * w.hid);
         timed(LLIE_K_DW, 2LL * M * w.hid * (int64_t)es(), [&] { return launch_dwconv3x3(dt, d, s); });
       }
@@ -797,27 +789,27 @@ struct Run {
     rel(as2); rel(ab2);
     // SE MLP
     // (wide blocks of the 2-byte inference engines: fc1's pre-activations accumulate as integers in the zero-initialised region)
-    const bool sepre_ok = ztot && dt != LLIE_F32 && g_se_mfma && w.hid >= 768 && w.hid % 256 == 0 && w.sq % 64 == 0 && w.sq <= 512;
+    const bool sepre_ok = fixtot && dt != LLIE_F32 && g_se_mfma && w.hid >= 768 && w.hid % 256 == 0 && w.sq % 64 == 0 && w.sq <= 512;
     const size_t sepre = sepre_ok ? ztake((size_t)B * w.sq * 8) : 0;
     const size_t sehid = ar->alloc((size_t)B * w.sq * 4), gate = ar->alloc((size_t)B * w.hid * 4);
     const size_t semean = ar->alloc((size_t)B * w.hid * 4);
     if (!dry) {
       SeArgs e{};
-      e.pool = ztot ? nullptr : p<float>(pool); e.ntiles = dnt; e.P = P;
+      e.pool = fixtot ? nullptr : p<float>(pool); e.ntiles = dnt; e.P = P;
       e.w1 = wptr(w.se_w1); e.b1 = wptr<float>(w.se_b1); e.w2 = wptr(w.se_w2); e.b2 = wptr<float>(w.se_b2);
       e.mean = p<float>(semean); e.hid = p<float>(sehid); e.gate = p<float>(gate); e.B = B; e.C = w.hid; e.Cs = w.sq;
-      if (ztot) e.tot = p<unsigned long long>(ptot);
+      if (fixtot) e.tot = p<unsigned long long>(ptot);
       if (sepre_ok) e.pre = p<long long>(sepre);
       if (sepre_ok && g_se_mfma && se_mlp_mfma_supported(dt, e)) {
-        if (!(g_skip_small & 2)) timed(LLIE_K_SE, (int64_t)B * w.hid * 12 + 2LL * w.hid * w.sq * (int64_t)es(), [&] { return launch_se_mlp_mfma(dt, e, s); });
-      } else if (ztot && w.hid <= 384) {
-        if (!(g_skip_small & 2)) timed(LLIE_K_SE, (int64_t)B * w.hid * 12 + 2LL * w.hid * w.sq * (int64_t)es(), [&] { return launch_se_gate(dt, e, s); });
-      } else if (!(g_skip_small & 2)) timed(LLIE_K_SE, ((int64_t)B * dnt * w.hid * 4) + 2LL * w.hid * w.sq * (int64_t)es(), [&] {
+        timed(LLIE_K_SE, (int64_t)B * w.hid * 12 + 2LL * w.hid * w.sq * (int64_t)es(), [&] { return launch_se_mlp_mfma(dt, e, s); });
+      } else if (fixtot && w.hid <= 384) {
+        timed(LLIE_K_SE, (int64_t)B * w.hid * 12 + 2LL * w.hid * w.sq * (int64_t)es(), [&] { return launch_se_gate(dt, e, s); });
+      } else timed(LLIE_K_SE, ((int64_t)B * dnt * w.hid * 4) + 2LL * w.hid * w.sq * (int64_t)es(), [&] {
         hipError_t r1 = launch_se_fc1(dt, e, s);
         return r1 != hipSuccess ? r1 : launch_se_fc2(dt, e, s);
       });
     }
-    if (!ztot) rel(pool);
+    if (!fixtot) rel(pool);
     rel(sehid); rel(semean);
     // K3: project with SE gate prologue (+ skip conv as extra K segments, or identity residual)
     Tens y = new_tens(w.cout, H, W, pw_gemm_ntiles(P), w.cout_r);
@@ -2639,37 +2631,23 @@ int llie_tune(const char* knob, int value) {
   if (!knob) return LLIE_ERR_ARG;
   ++g_tune_epoch;
   if (!strcmp(knob, "gemm_bk")) { pw_gemm_force_bk(value); return LLIE_OK; }
-  if (!strcmp(knob, "gemm_bk128")) { pw_gemm_bk128(value); return LLIE_OK; }
-  if (!strcmp(knob, "skip_small")) { g_skip_small = value; return LLIE_OK; }
   if (!strcmp(knob, "se_mfma")) { g_se_mfma = value; return LLIE_OK; }
   if (!strcmp(knob, "nt_min_mb")) { g_nt_min_mb = value; return LLIE_OK; }
   if (!strcmp(knob, "nt_mask")) { g_nt_mask = value; return LLIE_OK; }
-  if (!strcmp(knob, "ztot")) { g_ztot = value; return LLIE_OK; }
   if (!strcmp(knob, "gram")) { g_gram = value; return LLIE_OK; }
   if (!strcmp(knob, "irbx")) { g_use_irbx = value != 0; return LLIE_OK; }
-  if (!strcmp(knob, "irbx_dbuf")) { irbx_tune(value, 0); return LLIE_OK; }
-  if (!strcmp(knob, "irbx_tiles")) { irbx_tune(-1, value); return LLIE_OK; }
+  if (!strcmp(knob, "irbx_dbuf")) { irbx_tune(value); return LLIE_OK; }
   if (!strcmp(knob, "irbx_stamp")) { irbx_stamp(value); return LLIE_OK; }
-  if (!strcmp(knob, "irbx_mask")) { g_irbx_mask = value; return LLIE_OK; }
-  if (!strcmp(knob, "irbx_ablate")) { irbx_ablate(value); return LLIE_OK; }
-  if (!strcmp(knob, "irbx_dwv")) { irbx_dwv(value); return LLIE_OK; }
   if (!strcmp(knob, "irbx_grid")) { irbx_grid(0, value); return LLIE_OK; }
   if (!strcmp(knob, "irbx_grid2")) { irbx_grid(2, value); return LLIE_OK; }
   if (!strcmp(knob, "irbx_grid4")) { irbx_grid(4, value); return LLIE_OK; }
   if (!strcmp(knob, "irbx_grid6")) { irbx_grid(6, value); return LLIE_OK; }
-  if (!strcmp(knob, "irbx_var")) { irbx_var(value); return LLIE_OK; }
   if (!strcmp(knob, "conv_stamp")) { conv3x3_stamp(value); return LLIE_OK; }
   if (!strcmp(knob, "gemm_stamp")) { pw_gemm_stamp(value); return LLIE_OK; }
   if (!strcmp(knob, "pwx")) { pw_expand_enable(value); return LLIE_OK; }
-  if (!strcmp(knob, "pwx_ablate")) { pw_expand_debug(value, -1); return LLIE_OK; }
-  if (!strcmp(knob, "pwx_stamp")) { pw_expand_debug(-1, value); return LLIE_OK; }
-  if (!strcmp(knob, "pwx_nbw")) { pw_expand_debug(-1, -1, value); return LLIE_OK; }
-  if (!strcmp(knob, "gemm_ablate")) { pw_gemm_debug(value); return LLIE_OK; }
-  if (!strcmp(knob, "dw_ablate")) { dwconv_debug(value); return LLIE_OK; }
-  if (!strcmp(knob, "dw_swap")) { dwconv_swap(value); return LLIE_OK; }
+  if (!strcmp(knob, "pwx_stamp")) { pw_expand_debug(value); return LLIE_OK; }
   if (!strcmp(knob, "bwd_async")) { g_bwd_async = value; return LLIE_OK; }
   if (!strcmp(knob, "enhance_split")) { g_enhance_split = value; return LLIE_OK; }
-  if (!strcmp(knob, "wgrad_target")) { wgrad_set_target(value); return LLIE_OK; }
   return LLIE_ERR_ARG;
 }
 

@@ -175,11 +175,11 @@ __global__ void __launch_bounds__(WM* WN * 64) pw_gemm_kernel(const GemmArgs g) 
   const int wm = wave / WN, wn = wave % WN;
   const int nb = g.N / BN;
   // n fastest: neighbours share the A tile.  Workgroups are dealt round-robin to the 8 XCDs (one L2 each), so with more than
-  // one N tile the tiles of an M tile are kept on one XCD's L2 (dbg bit 4 = plain order, for A/B runs: up to 14 % faster on the 1024-pixel layers)
+  // one N tile the tiles of an M tile are kept on one XCD's L2 (up to 14 % faster than plain order on the 1024-pixel layers)
   int mt = blockIdx.x / nb, ntile = blockIdx.x % nb;
   const int tpi = RAGGED ? (g.P + BM - 1) / BM : g.P / BM;  // M tiles per image
   const int mtiles = (g.M / g.P) * tpi;
-  if (nb > 1 && mtiles % 8 == 0 && !(g.dbg & 16)) {
+  if (nb > 1 && mtiles % 8 == 0) {
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
     mt = (slot / nb) * 8 + xcd;
     ntile = slot % nb;
@@ -316,9 +316,9 @@ __global__ void __launch_bounds__(WM* WN * 64) pw_gemm_kernel(const GemmArgs g) 
   }
   prefetch(0);
   for (int c = 0; c < nchunks; ++c) {
-    if (!(g.dbg & 2) || c == 0) stage();  // dbg bit 1: timing ablation (no re-staging)
+    stage();
     wg_barrier();
-    if (c + 1 < nchunks && !(g.dbg & 1)) prefetch((c + 1) * BK);  // dbg bit 0: timing ablation (stale tiles)
+    if (c + 1 < nchunks) prefetch((c + 1) * BK);
     const int lr = lane & 31, lk = (lane >> 5) * 16;
 #pragma unroll
     for (int sub = 0; sub < BK / 32; ++sub) {
@@ -415,10 +415,10 @@ static hipError_t launch_cfg(const GemmArgs& a, hipStream_t s) {
 int pw_gemm_tile_rows(int P) { return (P % 128 == 0) ? 128 : 64; }
 int pw_gemm_ntiles(int P) { const int bm = pw_gemm_tile_rows(P); return (P + bm - 1) / bm; }  // statistics partials per image
 
-// tuning knobs for tools/gpu_tune.py (0 = automatic)
-static int g_force_bk = 0, g_bk128 = 1024;
+// knob "gemm_bk" (0 = automatic)
+static int g_force_bk = 0;
 void pw_gemm_force_bk(int bk) { g_force_bk = bk; }
-void pw_gemm_bk128(int v) { g_bk128 = v; }
+constexpr long kBk128MaxGrid = 1024;  // 128-wide K chunks for launches of up to this many workgroups
 
 template <typename T>
 static hipError_t launch_t(const GemmArgs& a, hipStream_t s) {
@@ -434,7 +434,7 @@ static hipError_t launch_t(const GemmArgs& a, hipStream_t s) {
     // small grids (about as many workgroups as the chip holds at once): a workgroup's time is chunks x memory latency, so
     // twice the chunk: -10...-16 % on the long-K project layers of the low resolutions (and at B = 1), +10 % on large grids.
     // The sequence of 32-wide k-steps per accumulator is unchanged: same bits, whatever the batch size chooses
-    if (g_bk128 && BM == 128 && BN == 128 && (long)(a.M / 128) * (a.N / 128) <= g_bk128) {
+    if (BM == 128 && BN == 128 && (long)(a.M / 128) * (a.N / 128) <= kBk128MaxGrid) {
       bool k128 = true;
       for (int i = 0; i < a.nseg; ++i) k128 = k128 && (a.seg[i].ch % 128 == 0);
       if (k128) return launch_cfg<T, 128, 128, 2, 2, 128>(a, s);
@@ -464,12 +464,7 @@ static hipError_t launch_t(const GemmArgs& a, hipStream_t s) {
   return launch_cfg<T, 64, 32, 2, 1, 32>(a, s);
 }
 
-static int g_gemm_dbg = 0;
-void pw_gemm_debug(int v) { g_gemm_dbg = v; }
-
-hipError_t launch_pw_gemm(int dtype, const GemmArgs& a0, hipStream_t s) {
-  GemmArgs a = a0;
-  a.dbg = g_gemm_dbg;
+hipError_t launch_pw_gemm(int dtype, const GemmArgs& a, hipStream_t s) {
   if (a.nostore && (!a.stats || a.res)) return hipErrorInvalidValue;
   // host-side shape contract of the kernel (checked before any launch: an out-of-contract shape
   // would index out of bounds on the device)

@@ -173,16 +173,10 @@ constexpr int kXStamps = 9;
 // 2 next tile's loads issued + halo validity, 3 tile-top barrier, 4 pool flush behind it, 5 chunk-top barrier + flush
 // (chunks after the first), 6 expand MFMAs + epilogue + ds_write, 7 barrier behind them, 8 depthwise phase incl. the h2
 // stores and the pool partial); never used in production.
-// ABL (diagnostic builds only): timing ablations -- 1 no h2 stores, 2 no pool sums, 4 h2 stores confined to L2, 8 no depthwise MFMAs,
-// 16 h2 stores as contiguous kilobytes (wrong layout, same bytes), 32 no workgroup barriers inside the tile loop (what a
-// barrier-free structure could gain at most; results wrong).
-// DWV = form of the depthwise phase: 0 = one tap per 32x32x16 MFMA (k = 16 channels of a diagonal weight matrix),
-// 1 = two taps per 16x16x32 MFMA (k = 2 taps x 16 channels): the same ds_read_b128 data operand per MFMA, half the
-// matrix-pipe time per MFMA -> 640 instead of 1 152 pipe cycles per 64-channel chunk and wave.
-// VAR (bit mask): 1 = the 64- / 96-channel variants request the next tile's x under the last chunk's depthwise phase (sX is
-// free from that chunk's expand phase on; the registers are live for one phase only), 2 = h2 leaves with non-temporal stores.
-constexpr int kXDefaultVar = 0;
-template <typename T, int KS, bool DBUF, bool STAMP = false, int ABL = 0, int DWV = 1, int VAR = kXDefaultVar>
+// The depthwise phase issues two taps per 16x16x32 MFMA (k = 2 taps x 16 channels): one ds_read_b128 data operand per MFMA,
+// 640 matrix-pipe cycles per 64-channel chunk and wave (one tap per 32x32x16 MFMA, round 2's form, took 1 152).
+// NTST = h2 leaves with non-temporal stores (IrbxArgs::nt).
+template <typename T, int KS, bool DBUF, bool STAMP = false, bool NTST = false>
 __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_kernel(const IrbxArgs a, const int tiles_per_wg, const int chunks_per_wg) {
   constexpr int K = 16 * KS;
   constexpr int XP = (K + 8) * 2;                        // sX pixel pitch in bytes (80 / 144 / 208 / 272: conflict-free ds_read_b128)
@@ -193,8 +187,6 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
   constexpr int XPT = (kXNPX + QSTEP - 1) / QSTEP;       // passes: 3 / 6 / 9
   constexpr int SH_BYTES = kXNPB * 32 * SHP;
   constexpr bool PREF = KS <= 2;        // next tile's x prefetched into registers at the top of the tile
-  constexpr bool LATE = !PREF && (VAR & 1);  // ... or under the tile's last depthwise phase
-  constexpr bool NTST = (VAR & 2) != 0;
   typedef typename Elem<T>::vec_t vec_t;
   extern __shared__ __align__(16) unsigned char smem[];
   // [sH: (DBUF ? 2 : 1) x 192 x 128 B][sX: 192 x XP][wds: 9 x Chid T][aff2: 2 x Chid fp32][aff1: 2 x K fp32][red: 2 x 4 x 64 fp32]
@@ -227,13 +219,10 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
   const int chunk1 = chunk0 + chunks_per_wg < nchunks_all ? chunk0 + chunks_per_wg : nchunks_all;
 
   // ---- per-workgroup constants: depthwise weights (packed T), affine tables of this image
-  if constexpr (DWV == 1) {  // [tap pair][channel][2]: one dword = this channel's weights of taps 2 p and 2 p + 1 (tap 9 = 0)
-    for (int i = tid; i < 10 * a.Chid; i += 256) {
-      const int t = i & 1, c = (i >> 1) % a.Chid, tap = 2 * ((i >> 1) / a.Chid) + t;
-      wds[i] = tap < 9 ? (T)(6.f * a.wd[tap * a.Chid + c]) : (T)0.f;
-    }
-  } else {
-    for (int i = tid; i < 9 * a.Chid; i += 256) wds[i] = (T)(6.f * a.wd[i]);  // the tile in LDS holds relu6(.) / 6
+  // [tap pair][channel][2]: one dword = this channel's weights of taps 2 p and 2 p + 1 (tap 9 = 0); the tile in LDS holds relu6(.) / 6
+  for (int i = tid; i < 10 * a.Chid; i += 256) {
+    const int t = i & 1, c = (i >> 1) % a.Chid, tap = 2 * ((i >> 1) / a.Chid) + t;
+    wds[i] = tap < 9 ? (T)(6.f * a.wd[tap * a.Chid + c]) : (T)0.f;
   }
   for (int i = tid; i < a.Chid; i += 256) {
     aff2[i] = a.as2[(size_t)b * a.Chid + i];                      // applied to acc' = acc / 6: scale unchanged,
@@ -246,22 +235,6 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
   // pixels 180..191 of the last MFMA block do not exist: their operand rows stay zero
   for (int i = tid; i < (kXNPB * 32 - kXNPX) * (XP / 16); i += 256)
     *reinterpret_cast<u32x4*>(sX + kXNPX * XP + i * 16) = u32x4{0u, 0u, 0u, 0u};
-
-  // depthwise phase roles: wave = (channel block chb, output rows 4 pxg .. 4 pxg + 3); lane = pixel n of a 2-row block.
-  // dmask: where this lane's weight sits in the diagonal operand -- channel n of the block is element n & 7 of k-slice
-  // (n >> 3) = 2 s + h, i.e. one 16-bit half of one dword for one (s, h) and nothing elsewhere
-  uint32_t dmask[2][4];
-#pragma unroll
-  for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-      dmask[s2][d] = ((n >> 3) == 2 * s2 + h && ((n & 7) >> 1) == d) ? ((n & 1) ? 0xFFFF0000u : 0x0000FFFFu) : 0u;
-  int dq[2], drow[2];  // halo pixel of tap (0, 0) and output row of this lane in its two blocks
-#pragma unroll
-  for (int blk = 0; blk < 2; ++blk) {
-    drow[blk] = 2 * (2 * pxg + blk) + (n >> 4);
-    dq[blk] = drow[blk] * kXH_W + (n & 15);
-  }
 
   const int ntiles_img = tiles_x * (a.H / kXT_H);
   // tiles_per_wg > 0: fixed runs; <= 0: the image's tiles split evenly over the gridDim.x workgroups (knob "irbx_grid")
@@ -306,7 +279,7 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
     }
   };
   int ty = tile_first / tiles_x, tx = tile_first % tiles_x;   // the only division: once per workgroup
-  if ((PREF || LATE) && tile_first < tile_last) load_tile(ty, tx);
+  if (PREF && tile_first < tile_last) load_tile(ty, tx);
   // weight slices (A operand) of the chunk about to run.  They are always fetched one depthwise phase ahead and BEFORE
   // that phase's stores: the wait in front of the MFMAs then leaves the (younger) stores in flight instead of draining them.
   vec_t wf[KS];
@@ -326,9 +299,6 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
       if (slot >= 0) tk[slot] += now - t_prev;
       t_prev = now;
     }
-  };
-  auto tile_barrier = [&]() {  // the barriers inside the tile loop (ABL 32 removes them: timing only)
-    if constexpr (!(ABL & 32)) wg_barrier();
   };
   stamp(-1);
   const bool has_pool = a.pool != nullptr || a.pool_tot != nullptr;
@@ -369,7 +339,7 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
     if (txn == tiles_x) { txn = 0; ++tyn; }
     // ---- activate this tile's x (norm1 + ReLU6) into sX, prefetch the next tile.  Every wave is past the last
     // MFMA phase of the previous tile here (the barrier that follows it), so sX is free.
-    if (!PREF && !LATE) load_tile(ty, tx);
+    if (!PREF) load_tile(ty, tx);
     // Every vector-memory operation so far has to be complete here anyway (raw[] below is older than all of them), but the
     // compiler's wait sits inside the predicated block below; said unconditionally, the chunk loop is entered with nothing
     // pending, and the wait for the prefetched weight slices at its head becomes vmcnt(4 + ...) -- the depthwise phase's four
@@ -395,7 +365,7 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
       }
     }
     stamp(2);
-    tile_barrier();
+    wg_barrier();
     stamp(3);
     if (!DBUF) flush_pool();
     stamp(4);
@@ -406,7 +376,7 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
     for (int chunk = chunk0; chunk < chunk1; ++chunk) {
       unsigned char* buf = sH + (DBUF ? par * SH_BYTES : 0);
       if (!DBUF && chunk > chunk0) {
-        tile_barrier();  // previous depthwise phase done with sH
+        wg_barrier();  // previous depthwise phase done with sH
         flush_pool();
         stamp(5);
       }
@@ -472,20 +442,16 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
         *reinterpret_cast<u32x4*>(buf + q * SHP + (chb * 4 + 2 * h + 1) * 16) = hi2;
       }
       stamp(6);
-      tile_barrier();
+      wg_barrier();
       if (DBUF) flush_pool();
-      if constexpr (LATE) {  // sX has been read for the last time in this tile: its next contents are requested under the depthwise phase
-        if (chunk + 1 == chunk1 && tile + 1 < tile_last) load_tile(tyn, txn);
-      }
       stamp(7);
       // ---- depthwise 3x3 on the MFMA pipe.  The VALU is what this kernel runs out of (a wave64 instruction costs a SIMD
       // 4 cycles; 72 FMAs per 16 output bytes), the matrix pipe idles.  A depthwise tap is a diagonal matrix:
-      //   out[ch][px] += sum_k diag(w_tap)[ch][k] * in[k][px + tap]      (k over the block's channels, 16 per MFMA)
-      // so a wave owns 32 channels x two 32-pixel blocks (2 output rows each) and issues 9 taps x 2 k-steps x 2 blocks
-      // = 36 MFMAs: the data operand is one ds_read_b128 per MFMA (lane = pixel, 8 channels), the weight operand this
-      // lane's weight masked into its diagonal position (4 v_and per tap and k-step).  3 % of the MACs are useful, which
-      // still equals the VALU's rate -- on a pipe that was idle, for a quarter of the VALU instructions.
-      if constexpr (DWV == 1) {
+      //   out[ch][px] += sum_k diag(w_tap)[ch][k] * in[k][px + tap]      (k over the block's channels, 16 per tap)
+      // the data operand is one ds_read_b128 per MFMA (lane = pixel, 8 channels), the weight operand this lane's weight
+      // masked into its diagonal position (4 v_and per step).  A few per cent of the MACs are useful, which still equals
+      // the VALU's rate -- on a pipe that was idle, for a quarter of the VALU instructions.
+      {
         // ---- two taps per MFMA: D[16 ch][16 px] += A[16 ch][k] B[k][16 px], k = 16 t + c (tap slot t, channel c of the
         // 16-channel tile), in this order of k: lane (li = lane & 15, g = lane >> 4) holds k-slice g = tap slot g & 1, channels 8 (g >> 1) + j.
         //   B: lane = output pixel li of one tile row; its 8 channels of the halo pixel under tap slot g & 1: ONE ds_read_b128,
@@ -535,10 +501,7 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
           for (int d = 0; d < 4; ++d) t[d] = wdup & amask[d];
           const vec_t af = reinterpret_cast<const vec_t&>(t);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            if constexpr (!(ABL & 8)) dacc[c2][r] = mfma16x16<T>(af, bf[step & 1][r], dacc[c2][r]);
-            else asm volatile("" :: "v"(bf[step & 1][r]), "v"(af));
-          }
+          for (int r = 0; r < 4; ++r) dacc[c2][r] = mfma16x16<T>(af, bf[step & 1][r], dacc[c2][r]);
         }
         // accumulators: lane (pixel li of row r, g): channels 16 c2 + 4 g + e.  v_permlane16_swap between the two tiles gives
         // every lane 8 consecutive channels of its pixel: even g: 4 g .. 4 g + 7, odd g: 16 + 4 (g - 1) .. 16 + 4 g + 3
@@ -560,13 +523,11 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
           const u32x4 v = {s0[0], s1[0], s0[1], s1[1]};
           const int orow = 4 * pxg + r;
           T* op = out + ((size_t)(y0 + orow) * a.W + x0p + li) * a.Chid + chunk * 64 + chb * 32 + choff;
-          if constexpr ((ABL & 4) != 0) op = out + ((size_t)orow * a.W + x0p + li) * a.Chid + chunk * 64 + chb * 32 + choff;
-          if constexpr (ABL & 1) asm volatile("" :: "v"(v));
-          else if constexpr (NTST) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(op));
+          if constexpr (NTST) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(op));
           else *reinterpret_cast<u32x4*>(op) = v;
         }
         // SE pool partial: channel sums over the wave's 64 pixels -- the 4 rows in registers, then the 16 pixel lanes of a row by DPP
-        if (has_pool && !(ABL & 2)) {
+        if (has_pool) {
           float v[8];
 #pragma unroll
           for (int c2 = 0; c2 < 2; ++c2)
@@ -592,130 +553,6 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
             float* rp = red + (DBUF ? par : 0) * 256 + wave * 64 + 4 * g;
             *reinterpret_cast<f32x4*>(rp) = f32x4{v[0], v[1], v[2], v[3]};
             *reinterpret_cast<f32x4*>(rp + 16) = f32x4{v[4], v[5], v[6], v[7]};
-          }
-          pend_tile = tile; pend_chunk = chunk; pend_par = DBUF ? par : 0;
-        }
-      } else
-      {
-        const T* wcol = wds + chunk * 64 + chb * 32 + n;
-        f32x16 dacc[2];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dacc[0][r] = dacc[1][r] = 0.f;
-        // The phase is LDS-latency bound unless the operand reads run well ahead of their MFMAs (two waves per SIMD hide
-        // little): all nine weights first, then the data operands of tap t + 1 are in flight while tap t multiplies.
-        uint32_t wv[9];
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) wv[tap] = *reinterpret_cast<const uint16_t*>(wcol + tap * a.Chid);
-        vec_t bf[2][4];
-        auto ld_tap = [&](int tap, vec_t (&bb)[4]) {
-          const int ky = tap / 3, kx = tap % 3;
-#pragma unroll
-          for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2)
-              bb[blk * 2 + s2] = *reinterpret_cast<const vec_t*>(buf + (dq[blk] + ky * kXH_W + kx) * SHP + (chb * 4 + 2 * s2 + h) * 16);
-        };
-        ld_tap(0, bf[0]);
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-          if (tap + 1 < 9) ld_tap(tap + 1, bf[(tap + 1) & 1]);
-          __builtin_amdgcn_sched_barrier(0);  // keep the look-ahead reads above this tap's MFMAs (the scheduler sinks them to
-                                              // their use otherwise: one or two reads in flight, the phase waits on LDS latency)
-          const uint32_t wdup = wv[tap] | (wv[tap] << 16);
-          vec_t af[2];
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2) {
-            u32x4 t;
-#pragma unroll
-            for (int d = 0; d < 4; ++d) t[d] = wdup & dmask[s2][d];
-            af[s2] = reinterpret_cast<const vec_t&>(t);
-          }
-#pragma unroll
-          for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-              const vec_t bv = bf[tap & 1][blk * 2 + s2];
-              if constexpr (!(ABL & 8)) dacc[blk] = mfma16<T>(af[s2], bv, dacc[blk]);
-              else asm volatile("" :: "v"(bv), "v"(af[s2]));
-            }
-        }
-        // accumulators: lane = pixel n of the block, 16 channels (r&3) + 8(r>>2) + 4h -> T, lane halves exchanged so that
-        // each lane owns 8 consecutive channels, two 16-byte stores per block
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk) {
-          uint32_t pk[4][2];
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            typedef T t2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-              t2 o;
-              o[0] = (T)dacc[blk][4 * g + 2 * j];
-              o[1] = (T)dacc[blk][4 * g + 2 * j + 1];
-              pk[g][j] = *reinterpret_cast<uint32_t*>(&o);
-            }
-          }
-          u32x4 lo, hi2;
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            const u32x2 r02 = __builtin_amdgcn_permlane32_swap(pk[0][j], pk[2][j], false, false);
-            const u32x2 r13 = __builtin_amdgcn_permlane32_swap(pk[1][j], pk[3][j], false, false);
-            lo[j] = r02[0]; lo[2 + j] = r02[1];
-            hi2[j] = r13[0]; hi2[2 + j] = r13[1];
-          }
-          T* op = out + ((size_t)(y0 + drow[blk]) * a.W + x0p + (n & 15)) * a.Chid + chunk * 64 + chb * 32 + 16 * h;
-          if constexpr ((ABL & 4) != 0)  // timing ablation: every tile row lands in image row 0..7 -> the stores hit in L2, no HBM writes
-            op = out + ((size_t)(drow[blk]) * a.W + x0p + (n & 15)) * a.Chid + chunk * 64 + chb * 32 + 16 * h;
-          if constexpr ((ABL & 16) != 0) {  // timing ablation (wrong layout, same bytes): both stores of a wave write one contiguous KB each
-            T* cp = out + (((((size_t)tile * nchunks_all + chunk) * 4 + wave) * 2 + blk) * 1024) + lane * 8;
-            *reinterpret_cast<u32x4*>(cp) = lo;
-            *reinterpret_cast<u32x4*>(cp + 512) = hi2;
-          } else if constexpr (!(ABL & 1)) {
-            *reinterpret_cast<u32x4*>(op) = lo;
-            *reinterpret_cast<u32x4*>(op + 8) = hi2;
-          } else {
-            asm volatile("" :: "v"(lo), "v"(hi2));
-          }
-        }
-        // SE pool partial of this (tile, chunk): the 16 channel values of a lane summed over the wave's 64 pixels -- the
-        // two blocks in registers, then a halving butterfly over the 32 pixel lanes (lane n ends up with channel slot (n>>1)&15)
-        if (has_pool && !(ABL & 2)) {
-          float v[16];
-#pragma unroll
-          for (int r = 0; r < 16; ++r) v[r] = dacc[0][r] + dacc[1][r];
-          // halving butterfly over pixel-lane bits 4 and 3 (lane-dependent choice between two registers as a bit blend with an
-          // opaque all-ones / zero mask, v_bfi_b32: written as a ternary the compiler builds a 16-way indexed select chain);
-          // bit 4 crosses the 16-lane DPP rows (ds_swizzle, the only LDS round trip), bit 3 is a row rotate by 8
-          {
-            uint32_t m = (n & 16) ? 0xFFFFFFFFu : 0u;
-            asm volatile("" : "+v"(m));
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-              const uint32_t lo = __float_as_uint(v[i]), hi = __float_as_uint(v[8 + i]);
-              const float keep = __uint_as_float((hi & m) | (lo & ~m));
-              const int send = (int)((lo & m) | (hi & ~m));
-              v[i] = keep + __int_as_float(__builtin_amdgcn_ds_swizzle(send, 0x401F));  // lane ^ 16
-            }
-            m = (n & 8) ? 0xFFFFFFFFu : 0u;
-            asm volatile("" : "+v"(m));
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              const uint32_t lo = __float_as_uint(v[i]), hi = __float_as_uint(v[4 + i]);
-              const float keep = __uint_as_float((hi & m) | (lo & ~m));
-              const int send = (int)((lo & m) | (hi & ~m));
-              v[i] = keep + __int_as_float(__builtin_amdgcn_update_dpp(0, send, 0x128, 0xF, 0xF, false));  // row_ror:8 = lane ^ 8
-            }
-          }
-          // the 4 remaining values are complete sums over the 8 lanes that share bits 4..3: quad xor 1, quad xor 2, half mirror
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            v[i] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[i]), 0xB1, 0xF, 0xF, false));   // quad_perm [1,0,3,2]
-            v[i] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[i]), 0x4E, 0xF, 0xF, false));   // quad_perm [2,3,0,1]
-            v[i] += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v[i]), 0x141, 0xF, 0xF, false));  // row_half_mirror
-          }
-          if ((n & 7) == 0) {  // r = 8 b4 + 4 b3 + {0..3} -> channel slots 8 (2 b4 + b3) + 4 h + {0..3}: 16 contiguous bytes
-            f32x4 o = {v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<f32x4*>(red + (DBUF ? par : 0) * 256 + wave * 64 + 8 * (n >> 3) + 4 * h) = o;
           }
           pend_tile = tile; pend_chunk = chunk; pend_par = DBUF ? par : 0;
         }
@@ -759,16 +596,12 @@ int irbx_stats_rows(int P) {
   return rp;
 }
 
-static int g_irbx_dbuf = 0, g_irbx_tiles = 4, g_irbx_stamp = 0, g_irbx_ablate = 0, g_irbx_dwv = 1;
+static int g_irbx_dbuf = 0, g_irbx_stamp = 0;
 static int g_irbx_grid[3] = {0, 0, 0};  // per input width (32, 64, 96 channels)
 void irbx_grid(int ks, int v) {
   for (int i = 0; i < 3; ++i)
     if (ks == 0 || ks == 2 * (i + 1)) g_irbx_grid[i] = v;
 }
-static int g_irbx_var = kXDefaultVar;
-void irbx_var(int v) { g_irbx_var = v; }
-void irbx_dwv(int v) { g_irbx_dwv = v; }
-void irbx_ablate(int v) { g_irbx_ablate = v; }
 static unsigned long long* g_irbx_dbg = nullptr;
 static size_t g_irbx_dbg_n = 0;  // entries of the last stamped launch
 void irbx_stamp(int v) { g_irbx_stamp = v; }
@@ -784,9 +617,8 @@ hipError_t irbx_stamp_fetch(double* out) {
   out[kXStamps] = (double)(g_irbx_dbg_n / kXStamps);
   return hipSuccess;
 }
-void irbx_tune(int dbuf, int tiles_per_wg) {
+void irbx_tune(int dbuf) {
   if (dbuf >= 0) g_irbx_dbuf = dbuf;
-  if (tiles_per_wg > 0) g_irbx_tiles = tiles_per_wg;
 }
 
 template <typename T, int KS, int NBW>
@@ -812,16 +644,23 @@ hipError_t launch_expand_stats(int dtype, const IrbxArgs& a, hipStream_t s) {
   return dtype == 1 ? launch_stats_t<half_t>(a, s) : launch_stats_t<bf16_t>(a, s);
 }
 
+constexpr int kXTilesPerWg = 4;  // longest run of tiles along x one workgroup takes
+
+template <typename T, int KS, bool DBUF, bool STAMP, bool NTST>
+static hipError_t launch_dw_one(const IrbxArgs& a, dim3 grid, size_t lds, int tpw, int cpw, hipStream_t s) {
+  static std::atomic<uint64_t> attr_done{0};
+  if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&expand_dw_kernel<T, KS, DBUF, STAMP, NTST>), 128 * 1024, attr_done); e != hipSuccess)
+    return e;
+  hipLaunchKernelGGL((expand_dw_kernel<T, KS, DBUF, STAMP, NTST>), grid, dim3(256), lds, s, a, tpw, cpw);
+  return hipGetLastError();
+}
 template <typename T, int KS, bool DBUF>
 static hipError_t launch_dw_cfg(const IrbxArgs& a, hipStream_t s) {
   const size_t lds = (size_t)(DBUF ? 2 : 1) * kXNPB * 32 * SHP + (size_t)kXNPB * 32 * (16 * KS + 8) * 2 + (size_t)10 * a.Chid * 2 +
                      (size_t)2 * a.Chid * 4 + (size_t)2 * 16 * KS * 4 + 2 * 256 * 4 + (KS <= 4 ? (size_t)KS * 64 * 8 : 0);
-  static std::atomic<uint64_t> attr_done{0};
-  if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&expand_dw_kernel<T, KS, DBUF>), 128 * 1024, attr_done); e != hipSuccess)
-    return e;
   const int ntiles = irbx_pool_tiles(a.H, a.W), nchunks = a.Chid / 64;
   // tiles per workgroup: a run along x (neighbouring halo columns hit L1), as long as the launch keeps >= 2048 workgroups
-  int tpw = g_irbx_tiles;
+  int tpw = kXTilesPerWg;
   while (tpw > 1 && ((a.W / kXT_W) % tpw || (long)(ntiles / tpw) * a.B < 2048)) tpw >>= 1;
   // channel chunks per workgroup: all of them (x tile loaded once) unless the launch would be too small
   int cpw = nchunks;
@@ -837,68 +676,23 @@ static hipError_t launch_dw_cfg(const IrbxArgs& a, hipStream_t s) {
     tpw = 0;
   }
   if constexpr (std::is_same<T, half_t>::value && !DBUF) {
-    if (g_irbx_stamp || a.ablate) {  // diagnostic builds: in-kernel cycle stamps and / or timing ablations (fp16 only)
+    if (g_irbx_stamp) {  // diagnostic build: in-kernel cycle stamps (fp16 only)
       IrbxArgs b = a;
-      if (g_irbx_stamp) {
-        const size_t n = (size_t)grid.x * grid.y * grid.z * 4 * kXStamps;
-        if (n > g_irbx_dbg_n || !g_irbx_dbg) {
-          if (g_irbx_dbg) (void)hipFree(g_irbx_dbg);
-          hipError_t e = hipMalloc(reinterpret_cast<void**>(&g_irbx_dbg), n * 8);
-          if (e != hipSuccess) return e;
-        }
-        g_irbx_dbg_n = n;
-        b.dbg = g_irbx_dbg;
-      }
-      auto go = [&](auto kern) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+      const size_t n = (size_t)grid.x * grid.y * grid.z * 4 * kXStamps;
+      if (n > g_irbx_dbg_n || !g_irbx_dbg) {
+        if (g_irbx_dbg) (void)hipFree(g_irbx_dbg);
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&g_irbx_dbg), n * 8);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, b, tpw, cpw);
-        return hipGetLastError();
-      };
-      if (g_irbx_stamp) {
-        switch (a.ablate) {
-          case 0: return go(&expand_dw_kernel<T, KS, DBUF, true, 0>);
-          case 1: return go(&expand_dw_kernel<T, KS, DBUF, true, 1>);
-          case 32: return go(&expand_dw_kernel<T, KS, DBUF, true, 32>);
-        }
-      } else {
-        switch (a.ablate) {
-          case 1: return go(&expand_dw_kernel<T, KS, DBUF, false, 1>);
-          case 4: return go(&expand_dw_kernel<T, KS, DBUF, false, 4>);
-          case 8: return go(&expand_dw_kernel<T, KS, DBUF, false, 8>);
-          case 32: return go(&expand_dw_kernel<T, KS, DBUF, false, 32>);
-          case 33: return go(&expand_dw_kernel<T, KS, DBUF, false, 33>);
-        }
       }
-      return hipErrorInvalidValue;
+      g_irbx_dbg_n = n;
+      b.dbg = g_irbx_dbg;
+      return launch_dw_one<T, KS, DBUF, true, false>(b, grid, lds, tpw, cpw, s);
     }
-  }
-  if (g_irbx_dwv == 0) {  // one tap per 32x32x16 MFMA (round 2's form), for A/B runs
-    static std::atomic<uint64_t> attr0{0};
-    if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&expand_dw_kernel<T, KS, DBUF, false, 0, 0>), 128 * 1024, attr0); e != hipSuccess)
-      return e;
-    hipLaunchKernelGGL((expand_dw_kernel<T, KS, DBUF, false, 0, 0>), grid, dim3(256), lds, s, a, tpw, cpw);
-    return hipGetLastError();
   }
   if constexpr (!DBUF) {
-    if (g_irbx_var != kXDefaultVar || a.nt) {  // knob "irbx_var": A/B of the variants (see VAR); IrbxArgs::nt = bit 2
-      auto go = [&](auto kern) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, tpw, cpw);
-        return hipGetLastError();
-      };
-      switch (g_irbx_var | (a.nt ? 2 : 0)) {
-        case 0: return go(&expand_dw_kernel<T, KS, DBUF, false, 0, 1, 0>);
-        case 1: return go(&expand_dw_kernel<T, KS, DBUF, false, 0, 1, 1>);
-        case 2: return go(&expand_dw_kernel<T, KS, DBUF, false, 0, 1, 2>);
-        case 3: return go(&expand_dw_kernel<T, KS, DBUF, false, 0, 1, 3>);
-      }
-      return hipErrorInvalidValue;
-    }
+    if (a.nt) return launch_dw_one<T, KS, DBUF, false, true>(a, grid, lds, tpw, cpw, s);
   }
-  hipLaunchKernelGGL((expand_dw_kernel<T, KS, DBUF>), grid, dim3(256), lds, s, a, tpw, cpw);
-  return hipGetLastError();
+  return launch_dw_one<T, KS, DBUF, false, false>(a, grid, lds, tpw, cpw, s);
 }
 template <typename T>
 static hipError_t launch_dw_t(const IrbxArgs& a, hipStream_t s) {
@@ -920,10 +714,8 @@ static hipError_t launch_dw_t(const IrbxArgs& a, hipStream_t s) {
   }
   return hipErrorInvalidValue;
 }
-hipError_t launch_expand_dw(int dtype, const IrbxArgs& a0, hipStream_t s) {
-  if (!irbx_supported(dtype, a0.c0 + a0.c1, a0.c0, a0.Chid, a0.H, a0.W) || (a0.c1 && !a0.x1) || !a0.out) return hipErrorInvalidValue;
-  IrbxArgs a = a0;
-  a.ablate = g_irbx_ablate;
+hipError_t launch_expand_dw(int dtype, const IrbxArgs& a, hipStream_t s) {
+  if (!irbx_supported(dtype, a.c0 + a.c1, a.c0, a.Chid, a.H, a.W) || (a.c1 && !a.x1) || !a.out) return hipErrorInvalidValue;
   return dtype == 1 ? launch_dw_t<half_t>(a, s) : launch_dw_t<bf16_t>(a, s);
 }
 

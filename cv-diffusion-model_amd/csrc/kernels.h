@@ -49,7 +49,6 @@ struct GemmArgs {
   int M, N, K;        // K = sum of seg ch
   int P;              // rows (pixels) per image; M = B * P
   int nostore;        // 1: compute and write only the statistics slab (out may be null)
-  int dbg;            // timing ablations (set by the launcher from pw_gemm_debug; 0 in production)
   const void* dot;    // optional [M][N] T: the slab then holds (sum out*dot, sum out) instead of (sum, sum of squares)
   int nt;             // 1: `out` is stored non-temporally (set by the engine for tensors beyond the Infinity Cache, common.h: st_vec_pol)
   unsigned long long* stamps;  // diagnostic builds only (pw_gemm_stamp)
@@ -60,8 +59,6 @@ hipError_t launch_pw_gemm(int dtype, const GemmArgs& a, hipStream_t s);
 int pw_gemm_tile_rows(int P);  // BM used for a given P
 int pw_gemm_ntiles(int P);     // stats slab tiles per image = ceil(P / BM)
 void pw_gemm_force_bk(int bk);  // tuning knob (0 = automatic)
-void pw_gemm_bk128(int max_grid);  // 128-wide K chunks for launches of up to this many workgroups (0 = never)
-void pw_gemm_debug(int v);      // timing ablations; results are wrong when non-zero
 
 // Expanding pointwise GEMM in activation-stationary form (pwx.hip; 2-byte T, every segment ACT_RELU6_S6):
 //   out[M][N] = sum_seg clamp01(A_seg * as + ab) . Wf^T,  Wf = the [N][K] weights times 6, pre-packed in MFMA fragment order
@@ -86,7 +83,7 @@ bool pw_expand_serves_k(int K);  // the kernel exists for this input width (the 
 hipError_t launch_pw_expand(int dtype, const ExpandArgs& a, hipStream_t s);
 hipError_t launch_pack_expand(int dtype, const float* src, void* dst, int N, int K, float scale, hipStream_t s);
 void pw_expand_enable(int v);  // knob "pwx" (1 = use where supported)
-void pw_expand_debug(int ablate, int stamp, int nbw = -1);  // timing studies (results wrong when 0 < ablate < 6); -1 = leave unchanged
+void pw_expand_debug(int stamp);  // knob "pwx_stamp": 1 = launch the cycle-stamped build
 hipError_t pw_expand_stamp_fetch(double* out4);
 
 // GroupNorm statistics -> per-(image, channel) affine tables.
@@ -170,25 +167,19 @@ struct IrbxArgs {
   float* stats;                                  // expand_stats output
   int B, H, W, Chid;
   unsigned long long* dbg;                       // diagnostic builds only (irbx_stamp)
-  int ablate;                                    // timing ablations (results wrong when non-zero; 0 in production)
   int nt;                                        // 1: h2 is stored non-temporally (see GemmArgs::nt)
 };
-void irbx_ablate(int v);
 void irbx_grid(int ks, int v);   // knobs "irbx_grid" (ks = 0: all), "irbx_grid2/4/6": workgroups per expand_dw launch (0 = heuristics)
-void irbx_var(int v);    // knob "irbx_var": expand_dw variant bits (irbx.hip: VAR)
-void irbx_dwv(int v);  // depthwise phase of expand_dw: 1 = two taps per 16x16x32 MFMA (default), 0 = one tap per 32x32x16 MFMA
 void irbx_stamp(int v);
 hipError_t irbx_stamp_fetch(double* out10);  // 9 slots (irbx.hip: STAMP) + the number of waves averaged
 bool irbx_supported(int dtype, int Cin, int c0, int Chid, int H, int W);
 int irbx_pool_tiles(int H, int W);
 int irbx_stats_rows(int P);
-void irbx_tune(int dbuf, int tiles_per_wg);
+void irbx_tune(int dbuf);  // knob "irbx_dbuf"
 hipError_t launch_expand_stats(int dtype, const IrbxArgs& a, hipStream_t s);
 hipError_t launch_expand_dw(int dtype, const IrbxArgs& a, hipStream_t s);
 int dwconv_ntiles(int H, int W);  // pool slab entries per image: (H/8 row segments) x (W / strip width)
 int dw_pick_tyl(int B, int H, int W, int chunks);
-void dwconv_swap(int v);   // 1: channel chunk is the fastest grid index
-void dwconv_debug(int v);  // timing ablations (bit 0: no MACs, bit 1: no activation); results are wrong when set
 
 // Squeeze-and-Excitation MLP (efficient_unet.py:96-100) in two launches.
 //   fc1: mean[b][c] = sum_tiles pool / P (own launch);  hid[b][j] = relu6(b1[j] + sum_c W1[j][c] * mean[b][c])
@@ -441,7 +432,6 @@ struct WgradArgs {
 int wgrad_msplit(int dtype, int M, int N, int K, int ntap);
 int wgrad_msplit_ragged(int dtype, int M, int N, int K, int ntap);  // image sizes off the multiples of 64
 int wgrad_rows(int B, int P);  // rows the weight-gradient GEMM walks: B * P, padded per image to 64-row chunks when P % 64 != 0
-void wgrad_set_target(int workgroups);  // tuning knob: workgroups per launch the row split aims for (default 1024)
 hipError_t launch_wgrad(int dtype, const WgradArgs& a, hipStream_t s);
 
 // (5) depthwise 3x3 weight gradient: dw[c][tap] (reference layout [C][1][3][3]) =

@@ -59,26 +59,25 @@ template <typename T> __device__ __forceinline__ f32x16 mfma_u(const u32x4& a, c
 template <typename T> constexpr uint32_t one_bits() { return std::is_same<T, half_t>::value ? 0x3C00u : 0x3F80u; }
 
 constexpr int kStagePitch = 144;  // bytes per staged 64-channel row: 128 + one 16-byte pad (conflict-free ds_read_b128)
-constexpr bool pwx_has_tile(int KS, int NBW, int ABL) { return ABL == 0 || NBW * KS * 1024 < 4 * 32 * kStagePitch; }
-constexpr int pwx_lds_bytes(int KS, int NBW, int ABL) {
-  return 2 * NBW * KS * 1024 + 2 * 4 * NBW * 64 * 4 + (pwx_has_tile(KS, NBW, ABL) ? 4 * 32 * kStagePitch : 0);
+constexpr bool pwx_has_tile(int KS, int NBW, bool REGSTORE) { return !REGSTORE || NBW * KS * 1024 < 4 * 32 * kStagePitch; }
+constexpr int pwx_lds_bytes(int KS, int NBW, bool REGSTORE) {
+  return 2 * NBW * KS * 1024 + 2 * 4 * NBW * 64 * 4 + (pwx_has_tile(KS, NBW, REGSTORE) ? 4 * 32 * kStagePitch : 0);
 }
 
 }  // namespace
 
-// KS = K / 16 MFMA steps; NBW = 32-channel blocks per LDS buffer.
-// ABL 6 = stores straight from registers (32 rows x 32 bytes per instruction; correct results).
-// Diagnostic instantiations (llie_tune "pwx_ablate" / "pwx_stamp", timing studies only): ABL 1 = every store instruction
-// writes 1 KB of contiguous memory (wrong layout, same bytes), 2 = no output stores, 3 / 4 / 5 = 64 / 128 / 256 bytes per
-// row and instruction (wrong layout); STAMP = s_memtime per wave after the A phase and at the end.  Template parameters, not run-time flags: a flag inside the MFMA loop changes the code it measures.
-template <typename T, int KS, int NBW, int ABL = 0, bool STAMP = false>
+// KS = K / 16 MFMA steps; NBW = 32-channel blocks per LDS buffer (1 everywhere, see kPwxNbw).
+// REGSTORE = output stores straight from registers (32 rows x 32 bytes per instruction) instead of through the LDS tile.
+// STAMP (llie_tune "pwx_stamp") = s_memtime per wave after the A phase and at the end.  Template parameters, not run-time
+// flags: a flag inside the MFMA loop changes the code it measures.
+template <typename T, int KS, int NBW, bool REGSTORE = false, bool STAMP = false>
 __global__ void __launch_bounds__(256, 2) pw_expand_kernel(const ExpandArgs g) {
   unsigned long long t_start = 0, t_a = 0, t_wait = 0;
   if constexpr (STAMP) t_start = __builtin_amdgcn_s_memtime();
   static_assert(sizeof(T) == 2 && KS % 4 == 0, "");
   constexpr int BUF = NBW * KS * 1024;  // bytes per weight buffer
-  constexpr bool LDSOUT = ABL == 0;  // production store path: full 128-byte lines through a wave-private LDS tile
-  constexpr bool HAS_TILE = pwx_has_tile(KS, NBW, ABL);  // wave-private [32 pixels][64 channels + pad] tiles behind the statistics
+  constexpr bool LDSOUT = !REGSTORE;  // full 128-byte lines through a wave-private LDS tile
+  constexpr bool HAS_TILE = pwx_has_tile(KS, NBW, REGSTORE);  // wave-private [32 pixels][64 channels + pad] tiles behind the statistics
   extern __shared__ __align__(16) unsigned char smem[];
   float* red = reinterpret_cast<float*>(smem + 2 * BUF);  // [2][4 waves][NBW][2][32]
   unsigned char* tbuf = smem + 2 * BUF + 2 * 4 * NBW * 64 * 4 + (threadIdx.x >> 6) * (32 * kStagePitch);
@@ -256,19 +255,8 @@ __global__ void __launch_bounds__(256, 2) pw_expand_kernel(const ExpandArgs g) {
         u32x4 v = {a[0], b[0], a[1], b[1]};  // lower lanes: channels 0-7, upper lanes: channels 8-15 of that half
         if constexpr (LDSOUT) {
           *reinterpret_cast<u32x4*>(tbuf + lr * kStagePitch + (((it * NBW + j) & 1) * 32 + lh * 8 + q * 4) * 2) = v;
-        } else if constexpr (ABL == 6) {  // straight from registers: 32 rows x 32 bytes per instruction
+        } else {  // straight from registers: 32 rows x 32 bytes per instruction
           *reinterpret_cast<u32x4*>(outp + (it * NBW + j) * 32 + q * 4) = v;
-        } else if constexpr (ABL == 1) {
-          T* lin = reinterpret_cast<T*>(g.out) + ((m0 + wave * 32) * g.N) + (size_t)(((it * NBW + j) * 2 + (q >> 2)) * 64 + lane) * 8;
-          *reinterpret_cast<u32x4*>(lin) = v;
-        } else if constexpr (ABL >= 3) {  // same footprint, PPR 16-byte pieces per row and instruction (3: 64 B, 4: 128 B, 5: 256 B)
-          constexpr int PPR = ABL == 3 ? 4 : (ABL == 4 ? 8 : 16);
-          constexpr int IPG = PPR / 2;  // instructions per group of PPR / 4 blocks
-          const int t = ((it * NBW + j) * 2 + (q >> 2));
-          const int row = (t % IPG) * (64 / PPR) + lane / PPR, col = (t / IPG) * (PPR * 8) + (lane % PPR) * 8;
-          *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(g.out) + (m0 + wave * 32 + row) * g.N + nbase + col) = v;
-        } else {
-          asm volatile("" ::"v"(v));
         }
       }
       if constexpr (LDSOUT) {
@@ -343,21 +331,9 @@ hipError_t launch_pack_expand(int dtype, const float* src, void* dst, int N, int
 static int g_use_pwx = 1;
 void pw_expand_enable(int v) { g_use_pwx = v; }
 
-// 32-channel blocks per LDS buffer for a given K (0 = K not served); g_pwx_nbw overrides where the variant exists.
-// One block per buffer everywhere: the smaller LDS footprint (three workgroups per CU up to K = 256) is worth more than
-// the saved barriers (profiles/r03/pwx_nbw.txt)
-static int g_pwx_nbw = 0;
-static int nbw_for(int K) {
-  const int f = g_pwx_nbw;
-  switch (K) {
-    case 128: return (f == 1 || f == 2 || f == 4) ? f : 1;
-    case 192: return (f == 1 || f == 2) ? f : 1;
-    case 256: return (f == 1 || f == 2) ? f : 1;
-    case 384: return 1;
-    case 512: return 1;
-  }
-  return 0;
-}
+// 32-channel blocks per LDS buffer.  One everywhere: the smaller LDS footprint (three workgroups per CU up to K = 256) is
+// worth more than the saved barriers (measured in round 3: profiles/r03)
+constexpr int kPwxNbw = 1;
 static int nsplit_for(int M, int N, int nbw) {
   // small grids: split the channels of a pixel tile over workgroups until the chip's 512 slots (2 per CU) are filled
   int ns = 1;
@@ -367,8 +343,7 @@ static int nsplit_for(int M, int N, int nbw) {
 bool pw_expand_serves_k(int K) { return K == 128 || K == 192 || K == 256 || K == 384 || K == 512; }
 bool pw_expand_supported(int dtype, const GemmSeg* seg, int nseg, int M, int N, int K, int P) {
   if (!g_use_pwx || (dtype != 1 && dtype != 2) || nseg < 1 || nseg > 3 || P % 128 || M % P) return false;
-  const int nbw = nbw_for(K);
-  if (!nbw || N % (32 * nbw) || N % 64) return false;  // pairs of 32-channel blocks leave as 128-byte lines
+  if (!pw_expand_serves_k(K) || N % (32 * kPwxNbw) || N % 64) return false;  // pairs of 32-channel blocks leave as 128-byte lines
   int k = 0;
   for (int i = 0; i < nseg; ++i) {
     if (seg[i].ch % 64 || seg[i].act != ACT_RELU6_S6 || !seg[i].as || !seg[i].ab) return false;
@@ -377,15 +352,11 @@ bool pw_expand_supported(int dtype, const GemmSeg* seg, int nseg, int M, int N, 
   return k == K;
 }
 
-static int g_pwx_ablate = 0, g_pwx_stamp = 0;
+static int g_pwx_stamp = 0;
 static unsigned long long* g_pwx_stamps = nullptr;
 static size_t g_pwx_stamp_waves = 0;
 constexpr size_t kPwxStampWaves = 1u << 18;
-void pw_expand_debug(int ablate, int stamp, int nbw) {
-  if (ablate >= 0) g_pwx_ablate = ablate;
-  if (stamp >= 0) g_pwx_stamp = stamp;
-  if (nbw >= 0) g_pwx_nbw = nbw;
-}
+void pw_expand_debug(int stamp) { g_pwx_stamp = stamp; }
 hipError_t pw_expand_stamp_fetch(double* out4) {  // mean s_memtime ticks per wave of the last stamped launch: {A phase, channel loop, of which in the vmcnt wait at the top of a buffer}, waves
   if (!g_pwx_stamps || !g_pwx_stamp_waves) return hipErrorInvalidValue;
   std::vector<unsigned long long> h(g_pwx_stamp_waves * 3);
@@ -397,15 +368,15 @@ hipError_t pw_expand_stamp_fetch(double* out4) {  // mean s_memtime ticks per wa
   return hipSuccess;
 }
 
-template <typename T, int KS, int NBW, int ABL = 0, bool STAMP = false>
+template <typename T, int KS, int NBW, bool REGSTORE = false, bool STAMP = false>
 static hipError_t launch_one(ExpandArgs a, hipStream_t s) {
-  constexpr int lds = pwx_lds_bytes(KS, NBW, ABL);
+  constexpr int lds = pwx_lds_bytes(KS, NBW, REGSTORE);
   static std::atomic<uint64_t> attr_done{0};
-  if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&pw_expand_kernel<T, KS, NBW, ABL, STAMP>), lds, attr_done); e != hipSuccess) return e;
-  hipLaunchKernelGGL((pw_expand_kernel<T, KS, NBW, ABL, STAMP>), dim3((unsigned)((a.M / 128) * a.nsplit)), dim3(256), lds, s, a);
+  if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&pw_expand_kernel<T, KS, NBW, REGSTORE, STAMP>), lds, attr_done); e != hipSuccess) return e;
+  hipLaunchKernelGGL((pw_expand_kernel<T, KS, NBW, REGSTORE, STAMP>), dim3((unsigned)((a.M / 128) * a.nsplit)), dim3(256), lds, s, a);
   return hipGetLastError();
 }
-template <typename T, int KS, int NBW>
+template <typename T, int KS, int NBW = kPwxNbw>
 static hipError_t launch_cfg(ExpandArgs a, hipStream_t s) {
   a.nsplit = nsplit_for(a.M, a.N, NBW);
   static const std::string name = std::string("pw_expand_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) + ", " + std::to_string(NBW) + ">";
@@ -417,31 +388,20 @@ static hipError_t launch_cfg(ExpandArgs a, hipStream_t s) {
       if (!g_pwx_stamps && hipMalloc(reinterpret_cast<void**>(&g_pwx_stamps), kPwxStampWaves * 24) != hipSuccess) return hipErrorOutOfMemory;
       g_pwx_stamp_waves = waves;
       a.stamps = g_pwx_stamps;
-      if (g_pwx_ablate == 1) return launch_one<T, KS, NBW, 1, true>(a, s);
-      if (g_pwx_ablate == 2) return launch_one<T, KS, NBW, 2, true>(a, s);
-      return launch_one<T, KS, NBW, 0, true>(a, s);
+      return launch_one<T, KS, NBW, false, true>(a, s);
     }
-    if (g_pwx_ablate == 1) return launch_one<T, KS, NBW, 1>(a, s);
-    if (g_pwx_ablate == 2) return launch_one<T, KS, NBW, 2>(a, s);
-    if (g_pwx_ablate == 3) return launch_one<T, KS, NBW, 3>(a, s);
-    if (g_pwx_ablate == 4) return launch_one<T, KS, NBW, 4>(a, s);
-    if (g_pwx_ablate == 5) return launch_one<T, KS, NBW, 5>(a, s);
   }
-  if (g_pwx_ablate == 6) return launch_one<T, KS, NBW, 6>(a, s);  // a correct variant: available for every shape
-  if (g_pwx_ablate == 7) return launch_one<T, KS, NBW>(a, s);
   // K = 512: the LDS tile would leave room for one workgroup per CU only (64 KB of weight buffers): registers -> HBM there
-  if constexpr (KS == 32) return launch_one<T, KS, NBW, 6>(a, s);
-  return launch_one<T, KS, NBW>(a, s);
+  return launch_one<T, KS, NBW, KS == 32>(a, s);
 }
 template <typename T>
 static hipError_t launch_t(const ExpandArgs& a, hipStream_t s) {
-  const int nbw = nbw_for(a.K);
   switch (a.K) {
-    case 128: return nbw == 4 ? launch_cfg<T, 8, 4>(a, s) : (nbw == 2 ? launch_cfg<T, 8, 2>(a, s) : launch_cfg<T, 8, 1>(a, s));
-    case 192: return nbw == 2 ? launch_cfg<T, 12, 2>(a, s) : launch_cfg<T, 12, 1>(a, s);
-    case 256: return nbw == 2 ? launch_cfg<T, 16, 2>(a, s) : launch_cfg<T, 16, 1>(a, s);
-    case 384: return launch_cfg<T, 24, 1>(a, s);
-    case 512: return launch_cfg<T, 32, 1>(a, s);
+    case 128: return launch_cfg<T, 8>(a, s);
+    case 192: return launch_cfg<T, 12>(a, s);
+    case 256: return launch_cfg<T, 16>(a, s);
+    case 384: return launch_cfg<T, 24>(a, s);
+    case 512: return launch_cfg<T, 32>(a, s);
   }
   return hipErrorInvalidValue;
 }

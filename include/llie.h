@@ -424,16 +424,14 @@ int llie_copy_probe(const void* src, void* dst, int64_t bytes, llie_stream strea
  * The ceiling the write-dominated 4x expansions (efficient_unet.py:174) are compared with. */
 int llie_rw_probe(const void* src, void* dst, int64_t units, int reads, int writes, int nontemporal, llie_stream stream);
 /* Engine knobs (process-wide; every call starts a new epoch of the hipGraph cache).  Production defaults in brackets.
- *   "enhance_split"  [2]    concurrent batch branches of the captured enhance graph (1 = one chain; env LLIE_ENHANCE_SPLIT)
- *   "irbx"           [1]    recompute form of the inverted-residual front half (0 = expand GEMM + depthwise kernel)
- *   "irbx_dbuf" [0], "irbx_tiles" [4], "irbx_mask" [7], "irbx_dwv" [1]   variants of the recompute kernels (A/B runs)
- *   "ztot"           [1]    SE pool as fixed-point totals + fused gate kernel (0 = slab + pool / fc1 / fc2 launches)
- *   "gemm_bk" [0 = auto], "gemm_bk128" [1024 = largest grid that takes 128-wide K chunks], "dw_swap" [0],
- *   "bwd_async" [1], "wgrad_target" [1024], "pwx" [1] (activation-stationary expand GEMM, pwx.hip; 0 = tile kernel),
- *   "gram" [1] (norm2 statistics of the recompute form from the Gram matrix of the block input, gram.hip; 0 = expand_stats),
- *   "pwx_nbw" [0 = per-K default] (32-channel blocks per weight buffer), "pwx_ablate" 6 / 7 (stores straight from registers / through the LDS tile)
- * Diagnostics whose results are WRONG or slow (timing studies only): "skip_small", "gemm_ablate", "dw_ablate",
- * "irbx_ablate", "gemm_stamp", "irbx_stamp", "conv_stamp", "pwx_ablate", "pwx_stamp".
+ *   "enhance_split" [2] concurrent batch branches of the captured enhance graph (1 = one chain; env LLIE_ENHANCE_SPLIT)
+ *   "irbx" [1] recompute form of the inverted-residual front half (0 = expand GEMM + depthwise kernel), "irbx_dbuf" [0] its double-buffered
+ *   32-channel variant, "irbx_grid" [0], "irbx_grid2" [0], "irbx_grid4" [0], "irbx_grid6" [0] workgroups per expand_dw launch (all / 32- / 64- /
+ *   96-channel inputs; 0 = heuristics), "gram" [1] (norm2 statistics of the recompute form from the Gram matrix of the block input, gram.hip;
+ *   0 = expand_stats), "pwx" [1] (activation-stationary expand GEMM, pwx.hip; 0 = tile kernel), "se_mfma" [1] (SE MLP of the wide blocks on the
+ *   MFMA pipe), "gemm_bk" [0] (0 = auto, 32 = 32-wide K chunks), "nt_mask" [1], "nt_min_mb" [100] (which producers store tensors of at least so
+ *   many MiB non-temporally: engine.cpp), "bwd_async" [1] (weight gradients on a side stream; 0 = single stream).
+ * Diagnostics, slow (cycle-stamped kernel builds read back by llie_debug_*_stamps), all [0]: "gemm_stamp", "pwx_stamp", "conv_stamp", "irbx_stamp".
  * Threading: the knobs are plain process-wide variables read by every forward; call llie_tune only while no other
  * thread is inside an llie_* compute call (same rule as the handle itself: SURVEY.md 8b, one stream at a time). */
 int llie_tune(const char* knob, int value);

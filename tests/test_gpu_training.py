@@ -248,6 +248,36 @@ def test_unet_backward_small64(dev, cd, max_l2, min_cos):
         m.compute_dtype = None
 
 
+def test_backward_side_stream_gives_the_single_stream_bits(dev):
+    """small@64, B=2, bf16: the gradients of one forward + backward with the weight-gradient kernels on their side stream
+    (knob "bwd_async" = 1, the default) equal, bit for bit, those of the single-stream order ("bwd_async" = 0) -- the
+    reference order of the race screen in tools/gpu_bwd_stress.py.  One pass each: a reference comparison, not a stress loop."""
+    native = importlib.import_module("cv-diffusion-model_amd._native")
+    m, sd, spec = _small(64, dev)
+    m.compute_dtype = "bf16"
+    g = torch.Generator().manual_seed(3)
+    low = (torch.rand(2, 3, 64, 64, generator=g) * 2 - 1).to(dev)
+    normal = (torch.rand(2, 3, 64, 64, generator=g) * 2 - 1).to(dev)
+    noise = torch.randn(2, 3, 64, 64, generator=g).to(dev)
+    t = torch.tensor([500, 37]).to(dev)
+    grads = {}
+    try:
+        for mode in (0, 1):
+            native.check(native.lib().llie_tune(b"bwd_async", mode))
+            m.zero_grad(set_to_none=True)
+            out = m(low, normal, timesteps=t, noise=noise)
+            torch.nn.functional.mse_loss(out["noise_pred"], out["noise"]).backward()
+            torch.cuda.synchronize()
+            grads[mode] = {k: p.grad.clone() for k, p in m.named_parameters()}
+    finally:
+        native.lib().llie_tune(b"bwd_async", 1)
+        m.compute_dtype = None
+    assert all(torch.isfinite(v).all() for v in grads[0].values())
+    assert len(grads[0]) == len(grads[1]) > 300
+    differ = [k for k in grads[0] if not torch.equal(grads[0][k], grads[1][k])]
+    assert not differ, f"{len(differ)} gradients differ between the stream orders: {differ[:8]}"
+
+
 def test_trainer_step_semantics(dev):
     """The reference trainer's step (trainer.py:281-338) on top of the engine: compute_loss -> backward ->
     clip_grad_norm_(1.0) -> AdamW -> EMA, three steps on fixed batches; the loss sequence follows the same

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Step time of the shipping path (hipGraph replay of `enhance`, small@256, 4 steps) under engine knob settings.
-usage: gpu_knobs.py [B] "knob=v,knob=v" "..."   (an empty string = defaults).  Timing ablation knobs give garbage results."""
+usage: gpu_knobs.py [B] "knob=v,knob=v" "..."   (an empty string = defaults)."""
 import importlib
 import os
 import sys
@@ -17,13 +17,12 @@ args = sys.argv[1:]
 B = int(args.pop(0)) if args and args[0].isdigit() else 32
 m = M.LowLightDiffusion(unet_variant="small", image_size=256, compute_dtype="fp16").to(dev).eval()
 low = torch.rand(B, 3, 256, 256, device=dev) * 2 - 1
-defaults = {}
+DEFAULTS = {"irbx": 1, "enhance_split": 2, "pwx": 1, "gram": 1, "se_mfma": 1, "nt_mask": 1, "nt_min_mb": 100, "bwd_async": 1}  # the others: 0
 
 
 def run(setting, steps=10):
     knobs = dict(kv.split("=") for kv in setting.split(",") if kv)
     for k, v in knobs.items():
-        defaults.setdefault(k, 0)
         N.check(L.llie_tune(k.encode(), int(v)))
     for _ in range(3):
         m.enhance(low, 4)
@@ -36,7 +35,7 @@ def run(setting, steps=10):
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / steps
     for k in knobs:
-        N.check(L.llie_tune(k.encode(), {"irbx": 1, "irbx_dbuf": 0, "irbx_mask": 7, "irbx_tiles": 4, "gemm_bk128": 1024, "enhance_split": 2, "ztot": 1, "pwx": 1, "irbx_dwv": 1, "gram": 1}.get(k, 0)))
+        N.check(L.llie_tune(k.encode(), DEFAULTS.get(k, 0)))
     return ms
 
 

@@ -14,7 +14,7 @@ M = importlib.import_module("cv-diffusion-model_amd")
 N = importlib.import_module("cv-diffusion-model_amd._native")
 L = N.lib()
 dev = torch.device("cuda:0")
-RESET = {"irbx": 1, "pwx": 1, "irbx_dwv": 1, "enhance_split": 2, "ztot": 1}
+RESET = {"irbx": 1, "pwx": 1, "enhance_split": 2}
 
 for dtype in (None, "fp16", "bf16"):
     torch.manual_seed(3)

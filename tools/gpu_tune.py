@@ -140,44 +140,20 @@ if __name__ == "__main__":
             for name, kind, P, segs, n in SHAPES + [("enc3.0 K1 128->512", "k1", 1024, [128], 512)]:
                 if kind != "k1" or sum(segs) < 128:
                     continue
-                L.llie_tune(b"pwx_ablate", 6)
-                ud = expand(Bx * P, segs, n, P, B=Bx)[0]
-                L.llie_tune(b"pwx_ablate", 0)
                 un, uo, nb, fl = expand(Bx * P, segs, n, P, B=Bx)
                 tot_n += un; tot_o += uo
-                print(f"B={Bx} {name:24s} pwx {un:7.1f} us {nb / un / 1e3:5.0f} GB/s {fl / un / 1e6:4.0f} TF (register-direct stores {ud:7.1f} us) | tile kernel {uo:7.1f} us {nb / uo / 1e3:5.0f} GB/s {fl / uo / 1e6:4.0f} TF", flush=True)
+                print(f"B={Bx} {name:24s} pwx {un:7.1f} us {nb / un / 1e3:5.0f} GB/s {fl / un / 1e6:4.0f} TF | tile kernel {uo:7.1f} us {nb / uo / 1e3:5.0f} GB/s {fl / uo / 1e6:4.0f} TF", flush=True)
         print(f"sum: pwx {tot_n / 2:.1f} us, tile kernel {tot_o / 2:.1f} us")
-    if "expand_nbw" in sys.argv[1:]:  # 32-channel blocks per weight buffer (LDS footprint vs barriers)
-        for rep in range(2):
-            for name, kind, P, segs, n in SHAPES + [("enc3.0 K1 128->512", "k1", 1024, [128], 512)]:
-                if kind != "k1" or sum(segs) not in (128, 192, 256):
-                    continue
-                row = []
-                for nbw in (1, 2, 4):
-                    if nbw == 4 and sum(segs) != 128:
-                        continue
-                    L.llie_tune(b"pwx_nbw", nbw)
-                    for abl in (0, 6):
-                        L.llie_tune(b"pwx_ablate", abl)
-                        row.append(f"nbw{nbw} {'tile' if abl == 0 else 'regs'} {expand(B * P, segs, n, P)[0]:6.1f}us")
-                L.llie_tune(b"pwx_nbw", 0); L.llie_tune(b"pwx_ablate", 0)
-                print(f"{name:22s} " + " | ".join(row), flush=True)
     if "expand_diag" in sys.argv[1:]:  # where the activation-stationary kernel spends its time (two representative shapes)
         out = (C.c_double * 4)()
         for name, P, segs, n in [("dec2.0 K1 192->768", 16384, [128, 64], 768), ("dec1.0 K1 384->1536", 4096, [256, 128], 1536)]:
-            for abl in (0, 6, 3, 4, 5, 1, 2):
-                L.llie_tune(b"pwx_ablate", abl)
-                L.llie_tune(b"pwx_stamp", 0)
-                un = min(expand(B * P, segs, n, P)[0] for _ in range(2))
-                if abl > 2:  # no stamped build of these
-                    print(f"{name:22s} ablate {abl}: {un:7.1f} us", flush=True)
-                    continue
-                L.llie_tune(b"pwx_stamp", 1)
-                us = expand(B * P, segs, n, P)[0]
-                N.check(L.llie_debug_pwx_stamps(out))
-                print(f"{name:22s} ablate {abl}: {un:7.1f} us ({us:7.1f} stamped)  per wave: A phase {out[0]:8.0f} cyc, channel loop {out[1]:8.0f} cyc "
-                      f"of which {out[2]:8.0f} in the DMA / store wait ({out[3]:.0f} waves)", flush=True)
-            L.llie_tune(b"pwx_ablate", 0)
+            L.llie_tune(b"pwx_stamp", 0)
+            un = min(expand(B * P, segs, n, P)[0] for _ in range(2))
+            L.llie_tune(b"pwx_stamp", 1)
+            us = expand(B * P, segs, n, P)[0]
+            N.check(L.llie_debug_pwx_stamps(out))
+            print(f"{name:22s} {un:7.1f} us ({us:7.1f} stamped)  per wave: A phase {out[0]:8.0f} cyc, channel loop {out[1]:8.0f} cyc "
+                  f"of which {out[2]:8.0f} in the DMA / store wait ({out[3]:.0f} waves)", flush=True)
             L.llie_tune(b"pwx_stamp", 0)
     if "gemm_stamp" in sys.argv[1:]:
         out = (C.c_double * 3)()
@@ -191,28 +167,6 @@ if __name__ == "__main__":
             print(f"{name:28s} {us0:8.1f} us ({us:8.1f} stamped)  per wave: K loop {out[0]:9.0f} cyc ({100*out[0]/max(tot,1):4.1f}%)  epilogue {out[1]:9.0f} cyc "
                   f"({100*out[1]/max(tot,1):4.1f}%)  waves {out[2]:.0f}", flush=True)
         L.llie_tune(b"gemm_stamp", 0)
-    if "bk128" in sys.argv[1:]:  # 128-wide K chunks; usage: gpu_tune.py bk128 [B]
-        i = sys.argv.index("bk128")
-        Bx = int(sys.argv[i + 1]) if len(sys.argv) > i + 1 else 32
-        for name, kind, P, segs, n in SHAPES + [("attn qkv 256->768", "k1", 1024, [256], 768), ("attn out 256->256", "k3", 1024, [256], 256), ("enc3.0 K3 512->256", "k3", 1024, [512], 256)]:
-            if n % 128 or any(c % 128 for c in segs):
-                continue
-            row = []
-            for knob in (0, 1 << 30, 0, 1 << 30):
-                L.llie_tune(b"gemm_bk128", knob)
-                us, gbs, tf = gemm(kind, Bx * P, segs, n, P, act=3 if kind == "k1" else 1, B=Bx)
-                row.append(f"bk={128 if knob else 64}: {us:6.1f}us")
-            print(f"B={Bx} grid={(Bx * P // 128) * (n // 128):6d} {name:28s} " + " | ".join(row), flush=True)
-        L.llie_tune(b"gemm_bk128", 0)
-    if "xcd" in sys.argv[1:]:  # XCD-aware tile order of the production kernel (gemm_ablate bit 4)
-        for name, kind, P, segs, n in SHAPES:
-            row = []
-            for knob in (0, 16, 0, 16):
-                L.llie_tune(b"gemm_ablate", knob)
-                us, gbs, tf = gemm(kind, B * P, segs, n, P, act=3 if kind == "k1" else 1)
-                row.append(f"xcd={knob >> 4}: {us:7.1f}us {tf:4.0f}TF {gbs:5.0f}GB/s")
-            print(f"{name:28s} " + " | ".join(row), flush=True)
-        L.llie_tune(b"gemm_ablate", 0)
     if "one" in sys.argv[1:]:  # one shape, for PMC passes: gpu_tune.py one <shape index>
         i = sys.argv.index("one")
         name, kind, P, segs, n = SHAPES[int(sys.argv[i + 1])]
@@ -221,13 +175,8 @@ if __name__ == "__main__":
     if "dw" in sys.argv[1:]:
         for rep in range(2):
             for H, Cc in [(256, 128), (256, 384), (128, 768), (64, 1536)]:
-                row = []
-                for mode in (0, 1):
-                    L.llie_tune(b"dw_swap", mode)
-                    us, gbs = dw(B, H, Cc)
-                    row.append(f"swap{mode}: {us:7.1f}us {gbs:5.0f}GB/s")
-                print(f"dw {H}x{H} C={Cc}: " + " | ".join(row), flush=True)
-        L.llie_tune(b"dw_swap", 0)
+                us, gbs = dw(B, H, Cc)
+                print(f"dw {H}x{H} C={Cc}: {us:7.1f}us {gbs:5.0f}GB/s", flush=True)
 
 
 def chain(B, Bc, P, H, cin, hid, cout, iters=5):
