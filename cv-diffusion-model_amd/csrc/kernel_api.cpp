@@ -1,0 +1,444 @@
+// Kernel-level entry points (unit tests, tuning), pre / post-processing, optimiser, EMA, distillation and the memory probes:
+// thin wrappers over the launch API of kernels.h.
+#include "engine.h"
+
+using namespace llie;
+
+int llie::kerr(const char* what, hipError_t e, int refuse_rc, const char* refuse_msg) {
+  if (e == hipSuccess) return LLIE_OK;
+  if (e == hipErrorInvalidValue && refuse_rc) {
+    if (refuse_msg) set_err("%s: %s", what, refuse_msg);
+    return refuse_rc;
+  }
+  set_err("%s: %s", what, hipGetErrorString(e));
+  return (int)e;
+}
+
+// the C ABI's K segments as the launch API's; returns their total channel count
+static int to_segs(const llie_gemm_seg* segs, int nseg, GemmSeg* out) {
+  int K = 0;
+  for (int i = 0; i < nseg; ++i) {
+    out[i] = GemmSeg{segs[i].ptr, segs[i].channels, segs[i].scale, segs[i].bias, segs[i].affine_ld, segs[i].act};
+    K += segs[i].channels;
+  }
+  return K;
+}
+
+extern "C" {
+
+int llie_gram_stats(int dtype, const void* x0, int c0, const void* x1, int c1, const float* scale, const float* bias, int batch, int pixels,
+                    float* part, float* gtot, unsigned int* tickets, llie_stream stream) {
+  GramArgs a{};
+  a.x0 = x0; a.x1 = x1; a.c0 = c0; a.c1 = c1; a.as1 = scale; a.ab1 = bias; a.part = part; a.gtot = gtot; a.tickets = tickets; a.B = batch; a.P = pixels;
+  if (!gram_supported(dtype, c0 + c1, c0, pixels)) { set_err("gram_stats: K in {32, 64, 96}, 2-byte dtype, pixels a multiple of 512"); return LLIE_ERR_SHAPE; }
+  // a refusal keeps the runtime's own text for hipErrorInvalidValue, mapped to LLIE_ERR_ARG
+  return kerr("gram_stats", launch_gram_stats(dtype, a, hs(stream)), LLIE_ERR_ARG, hipGetErrorString(hipErrorInvalidValue));
+}
+int64_t llie_gram_part_floats(int K, int pixels) { return (K == 32 || K == 64 || K == 96) && pixels > 0 && pixels % 512 == 0 ? (int64_t)gram_part_floats(K, pixels) : LLIE_ERR_ARG; }
+
+// ---- kernel-level entry points (unit tests, tuning): thin wrappers over the launch API
+int llie_pw_gemm(int dtype, const llie_gemm_seg* segs, int nseg, const void* w, const float* bias, const void* residual,
+                 void* out, float* stats, int M, int N, int P, llie_stream stream) {
+  if (!segs || nseg < 1 || nseg > 3 || !w || !out || dtype < 0 || dtype > 2) return LLIE_ERR_ARG;
+  GemmArgs g{};
+  g.nseg = nseg;
+  g.K = to_segs(segs, nseg, g.seg);
+  g.w = w; g.bias = bias; g.res = residual; g.out = out; g.stats = stats; g.M = M; g.N = N; g.P = P;
+  return kerr("pw_gemm", launch_pw_gemm(dtype, g, hs(stream)));
+}
+
+int llie_pw_expand(int dtype, const llie_gemm_seg* segs, int nseg, const float* w32, void* wpack, void* out, float* stats,
+                   int M, int N, int P, llie_stream stream) {
+  if (!segs || nseg < 1 || nseg > 3 || !wpack || !out || !stats || dtype < 1 || dtype > 2) return LLIE_ERR_ARG;
+  ExpandArgs x{};
+  x.nseg = nseg;
+  x.K = to_segs(segs, nseg, x.seg);
+  x.wf = wpack; x.out = out; x.stats = stats; x.M = M; x.N = N; x.P = P;
+  hipStream_t s = hs(stream);
+  hipError_t e = !pw_expand_supported(dtype, x.seg, nseg, M, N, x.K, P) ? hipErrorInvalidValue
+                 : (w32 ? launch_pack_expand(dtype, w32, wpack, N, x.K, 6.f, s) : hipSuccess);
+  if (e == hipSuccess) e = launch_pw_expand(dtype, x, s);
+  return kerr("pw_expand", e);
+}
+
+int llie_dwconv3x3(int dtype, const void* in, void* out, const float* scale, const float* bias, const float* w9c,
+                   float* pool, int B, int H, int W, int C, llie_stream stream) {
+  if (!in || !out || !scale || !bias || !w9c || dtype < 0 || dtype > 2) return LLIE_ERR_ARG;
+  DwArgs d{};
+  d.in = in; d.out = out; d.as = scale; d.ab = bias; d.w = w9c; d.pool = pool; d.B = B; d.H = H; d.W = W; d.C = C;
+  return kerr("dwconv3x3", launch_dwconv3x3(dtype, d, hs(stream)));
+}
+
+// ---- the remaining kernel-level entry points of SURVEY.md 8b (GroupNorm finalize, dense 3x3, linear attention, SE MLP, FiLM)
+int llie_groupnorm_finalize(const float* slab0, int ntiles0, int ch0, const float* slab1, int ntiles1, int ch1, int groups, int pixels,
+                            const float* gamma, const float* beta, const float* film, int64_t film_stride, float eps, float post_scale,
+                            int batch, float* scale_out, float* shift_out, llie_stream stream) {
+  if (!slab0 || !gamma || !beta || !scale_out || !shift_out || batch <= 0 || ch0 <= 0 || (slab1 && ch1 <= 0) || groups <= 0 || pixels <= 0 ||
+      ntiles0 <= 0 || (slab1 && ntiles1 <= 0) || (ch0 + (slab1 ? ch1 : 0)) % groups)
+    return LLIE_ERR_ARG;
+  GnFinalizeArgs a{};
+  a.src[0] = StatSrc{slab0, ntiles0, ch0};
+  if (slab1) a.src[1] = StatSrc{slab1, ntiles1, ch1};
+  a.C = ch0 + (slab1 ? ch1 : 0); a.groups = groups; a.P = pixels; a.gamma = gamma; a.beta = beta; a.film = film; a.film_stride = film_stride;
+  a.eps = eps; a.as = scale_out; a.ab = shift_out; a.B = batch; a.post_scale = post_scale;
+  return kerr("groupnorm_finalize", launch_gn_finalize(a, hs(stream)));
+}
+// GroupNorm-2 + FiLM affine of the recompute form from the Gram totals llie_gram_stats leaves (gram.hip: gram_finalize_kernel)
+int llie_gram_finalize(int dtype, const float* gram_totals, const void* w_expand, int K, int pixels, const float* gamma, const float* beta,
+                       const float* film, int64_t film_stride, float eps, float post_scale, int batch, float* scale_out, float* shift_out,
+                       llie_stream stream) {
+  if (!gram_totals || !w_expand || !gamma || !beta || !scale_out || !shift_out || batch <= 0 || pixels <= 0 || (K != 32 && K != 64 && K != 96) ||
+      (dtype != 1 && dtype != 2))
+    return LLIE_ERR_ARG;
+  GramFinalizeArgs a{};
+  a.gtot = gram_totals; a.w1 = w_expand; a.K = K; a.Chid = 4 * K; a.groups = 32; a.P = pixels; a.B = batch; a.gamma = gamma; a.beta = beta;
+  a.film = film; a.film_stride = film_stride; a.eps = eps; a.as = scale_out; a.ab = shift_out; a.post_scale = post_scale;
+  return kerr("gram_finalize", launch_gram_finalize(dtype, a, hs(stream)));
+}
+int llie_conv3x3(int dtype, int mode, const void* in, const void* w, const float* bias, void* out, float* stats, int batch, int Hi, int Wi,
+                 int Cin, int Cout, llie_stream stream) {
+  if (!in || !w || !out || dtype < 0 || dtype > 2 || (mode != 0 && mode != 1)) return LLIE_ERR_ARG;
+  Conv3Args a{};
+  a.in = in; a.w = w; a.bias = bias; a.out = out; a.stats = stats; a.B = batch; a.Hi = Hi; a.Wi = Wi; a.Cin = Cin; a.Cout = Cout; a.mode = mode;
+  return kerr("conv3x3", launch_conv3x3(dtype, a, hs(stream)));
+}
+int llie_conv3x3_tiles(int Ho, int Wo) { return conv3x3_ntiles(Ho, Wo); }
+int llie_linattn_splits(int N) { return linattn_nsplit(N); }
+int llie_linattn(int dtype, const void* qkv, float* kv_scratch, void* out, int batch, int N, int heads, llie_stream stream) {
+  if (!qkv || !kv_scratch || !out || dtype < 0 || dtype > 2 || batch <= 0 || N <= 0 || heads <= 0) return LLIE_ERR_ARG;
+  AttnArgs a{};
+  a.qkv = qkv; a.B = batch; a.N = N; a.heads = heads; a.kv = kv_scratch; a.out = out; a.nsplit = linattn_nsplit(N);
+  hipError_t e = launch_linattn_kv(dtype, a, hs(stream));
+  if (e == hipSuccess) e = launch_linattn_out(dtype, a, hs(stream));
+  return kerr("linattn", e);
+}
+int llie_se_mlp(int dtype, const float* pool_sums, int pixels, const void* w1, const float* b1, const void* w2, const float* b2, float* mean_scratch,
+                float* hidden_scratch, float* gate, int batch, int C, int Cs, llie_stream stream) {
+  if (!pool_sums || !w1 || !b1 || !w2 || !b2 || !mean_scratch || !hidden_scratch || !gate || dtype < 0 || dtype > 2 || batch <= 0 || C <= 0 || Cs <= 0)
+    return LLIE_ERR_ARG;
+  SeArgs a{};
+  a.pool = pool_sums; a.ntiles = 1; a.P = pixels; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.mean = mean_scratch; a.hid = hidden_scratch; a.gate = gate;
+  a.B = batch; a.C = C; a.Cs = Cs;
+  hipError_t e = launch_se_fc1(dtype, a, hs(stream));
+  if (e == hipSuccess) e = launch_se_fc2(dtype, a, hs(stream));
+  return kerr("se_mlp", e);
+}
+int llie_film(const float* silu_temb, const float* wf, const float* bf, float* film, int rows, int T, int F, llie_stream stream) {
+  if (!silu_temb || !wf || !bf || !film || rows <= 0 || T <= 0 || F <= 0) return LLIE_ERR_ARG;
+  FilmArgs a{};
+  a.silu_temb = silu_temb; a.rows = rows; a.T = T; a.wf = wf; a.bf = bf; a.film = film; a.F = F;
+  return kerr("film", launch_film(a, hs(stream)));
+}
+
+// ---- backward kernels (training): thin wrappers over the launch API; every contract check runs here, before any HIP call
+static bool dtype_ok(int dtype) { return dtype >= 0 && dtype <= 2; }
+static int wgrad_rule(int dtype, int batch, int pixels, int N, int K, int ntap, int ragged_rule) {
+  const int M = wgrad_rows(batch, pixels);
+  return ragged_rule ? wgrad_msplit_ragged(dtype, M, N, K, ntap) : wgrad_msplit(dtype, M, N, K, ntap);
+}
+int llie_wgrad_msplit(int dtype, int batch, int pixels, int N, int K, int ntap, int ragged_rule) {
+  if (!dtype_ok(dtype) || batch <= 0 || pixels <= 0 || N <= 0 || K <= 0 || (ntap != 1 && ntap != 9)) return LLIE_ERR_ARG;
+  return wgrad_rule(dtype, batch, pixels, N, K, ntap, ragged_rule);
+}
+int64_t llie_wgrad_partial_floats(int msplit, int N, int K, int ntap) {
+  if (msplit <= 0 || N <= 0 || K <= 0 || (ntap != 1 && ntap != 9)) return LLIE_ERR_ARG;
+  return (int64_t)msplit * ntap * N * K;
+}
+int llie_wgrad(int dtype, const void* g, int N, const llie_gemm_seg* segs, int nseg, int batch, int Ho, int Wo, int Hi, int Wi, int stride,
+               int dy, int dx, int ntap, int nstore, int kstore, float* partial, int64_t partial_floats, float* out, int64_t ldn, int64_t ldk,
+               int64_t off, int msplit, llie_stream stream) {
+  if (!dtype_ok(dtype) || !g || !segs || !partial || !out || nseg < 1 || nseg > 3 || N <= 0 || N % 32 || batch <= 0 || Ho <= 0 ||
+      Wo <= 0 || Hi <= 0 || Wi <= 0 || (stride != 1 && stride != 2) || (ntap != 1 && ntap != 9) || dy < -1 || dy > 1 || dx < -1 ||
+      dx > 1 || msplit < 0 || ldn < 0 || ldk < 0 || off < 0)
+    return LLIE_ERR_ARG;
+  WgradArgs a{};
+  a.nseg = nseg;
+  for (int i = 0; i < nseg; ++i) {
+    const llie_gemm_seg& sg = segs[i];
+    if (!sg.ptr || sg.channels <= 0 || sg.channels % 32 || sg.act < ACT_NONE || sg.act > ACT_SILU || (sg.bias && !sg.scale) ||
+        (sg.scale && sg.affine_ld < sg.channels))
+      return LLIE_ERR_ARG;
+  }
+  a.K = to_segs(segs, nseg, a.seg);
+  // the output pixel grid must lie inside the input's (stride-s conv with pad 1 or a 1x1 tap)
+  if (nstore < 0 || nstore > N || kstore < 0 || kstore > a.K || (Ho - 1) * stride >= Hi || (Wo - 1) * stride >= Wi) return LLIE_ERR_ARG;
+  const int P = Ho * Wo, M = wgrad_rows(batch, P);
+  const int ms = msplit ? msplit : wgrad_rule(dtype, batch, P, N, a.K, ntap, P % 64 != 0);
+  if (ms > M / 64 || partial_floats < (int64_t)ms * ntap * N * a.K) return LLIE_ERR_ARG;
+  a.g = g; a.N = N; a.B = batch; a.Ho = Ho; a.Wo = Wo; a.Hi = Hi; a.Wi = Wi; a.stride = stride; a.dy = dy; a.dx = dx;
+  a.ntap = ntap; a.nstore = nstore; a.kstore = kstore; a.partial = partial; a.out = out; a.ldn = ldn; a.ldk = ldk; a.off = off; a.msplit = ms;
+  return kerr("wgrad", launch_wgrad(dtype, a, hs(stream)));
+}
+int llie_dw_wgrad_strips(int H, int W) { return H > 0 && W > 0 ? dw_wgrad_strips(H, W) : LLIE_ERR_ARG; }
+int llie_dw_wgrad(int dtype, const void* g, const float* gs, const float* gb, const void* h, const float* as, const float* ab, float* partial,
+                  float* out, int batch, int H, int W, int C, llie_stream stream) {
+  if (!dtype_ok(dtype) || !g || !h || !as || !ab || !partial || !out || batch <= 0 || H <= 0 || W <= 0 || C <= 0 || C % (dtype == 0 ? 32 : 64))
+    return LLIE_ERR_ARG;
+  DwWgradArgs a{};
+  a.g = g; a.gs = gs; a.gb = gb; a.h = h; a.as = as; a.ab = ab; a.partial = partial; a.out = out; a.B = batch; a.H = H; a.W = W; a.C = C;
+  return kerr("dw_wgrad", launch_dw_wgrad(dtype, a, hs(stream)));
+}
+int64_t llie_groupnorm_backward_scratch_floats(int batch, int C, int pixels) {
+  if (batch <= 0 || C <= 0 || pixels <= 0) return LLIE_ERR_ARG;
+  return (int64_t)batch * C * (2 * ((pixels + 63) / 64) + 7);  // slab, S, A, Bq, Cq, dG, dBc
+}
+int llie_groupnorm_backward(int dtype, const llie_gn_backward_args* a, float* scratch, int64_t scratch_floats, llie_stream stream) {
+  if (!dtype_ok(dtype) || !a || !scratch) return LLIE_ERR_ARG;
+  const int C = a->c0 + a->c1;
+  if (!a->g || !a->x0 || !a->dx0 || !a->scale || !a->shift || !a->mean || !a->rstd || !a->gamma || !a->beta || !a->dgamma || !a->dbeta ||
+      a->act < ACT_NONE || a->act > ACT_SILU || (a->act != ACT_NONE && !a->dz) || a->batch <= 0 || a->pixels <= 0 || a->c0 <= 0 ||
+      a->c0 % 32 || a->c1 < 0 || a->c1 % 32 || (a->c1 && (!a->x1 || !a->dx1)) || (!a->c1 && (a->x1 || a->dx1 || a->add1_1)) ||
+      (a->dfilm && !a->film) || (a->film && a->film_stride < 0) || (a->dfilm && a->dfilm_stride < 2 * C) ||
+      (int64_t)a->batch * a->pixels * C / (dtype == 0 ? 4 : 8) >= (1ll << 31) ||
+      scratch_floats < llie_groupnorm_backward_scratch_floats(a->batch, C, a->pixels))
+    return LLIE_ERR_ARG;
+  const int nt = (a->pixels + 63) / 64;
+  const size_t bc = (size_t)a->batch * C;
+  GnSiteArgs s{};
+  s.g = a->g; s.dz = a->act == ACT_NONE ? nullptr : a->dz; s.x0 = a->x0; s.x1 = a->x1; s.c0 = a->c0; s.c1 = a->c1;
+  s.as = a->scale; s.ab = a->shift; s.act = a->act; s.mean = a->mean; s.rstd = a->rstd; s.gamma = a->gamma; s.beta = a->beta;
+  s.film = a->film; s.film_stride = a->film_stride; s.dfilm = a->dfilm; s.dfilm_stride = a->dfilm_stride; s.dgamma = a->dgamma; s.dbeta = a->dbeta;
+  s.slab = scratch; s.ntiles = nt; s.slab_ready = 0;
+  s.S = scratch + bc * 2 * nt; s.A = s.S + 2 * bc; s.Bq = s.A + bc; s.Cq = s.Bq + bc; s.dG = s.Cq + bc; s.dBc = s.dG + bc;
+  s.add0 = a->add0; s.add1_0 = a->add1_0; s.add1_1 = a->add1_1; s.dx0 = a->dx0; s.dx1 = a->dx1; s.B = a->batch; s.P = a->pixels;
+  return kerr("groupnorm_backward", launch_gn_site_bwd(dtype, s, hs(stream)));
+}
+int64_t llie_linattn_dkv_floats(int batch, int N, int heads) {
+  if (batch <= 0 || N <= 0 || heads <= 0) return LLIE_ERR_ARG;
+  return (int64_t)batch * heads * ((N + 63) / 64 + 1) * 32 * 33;  // tile partials, then their sum
+}
+int llie_linattn_backward(int dtype, const void* qkv, const float* kv_scratch, const void* dout, void* dqkv, float* dkv_scratch,
+                          int64_t dkv_floats, int batch, int N, int heads, llie_stream stream) {
+  if (!dtype_ok(dtype) || !qkv || !kv_scratch || !dout || !dqkv || !dkv_scratch || batch <= 0 || N <= 0 || heads <= 0 ||
+      dkv_floats < llie_linattn_dkv_floats(batch, N, heads))
+    return LLIE_ERR_ARG;
+  AttnBwdArgs a{};
+  a.qkv = qkv; a.dout = dout; a.dqkv = dqkv; a.kv = kv_scratch; a.nsplit = linattn_nsplit(N); a.dkv = dkv_scratch;
+  a.B = batch; a.N = N; a.heads = heads;
+  float* tot = dkv_scratch + (size_t)batch * heads * ((N + 63) / 64) * 32 * 33;
+  return kerr("linattn_backward", launch_linattn_bwd(dtype, a, tot, hs(stream)));
+}
+int llie_upsample2x_backward(int dtype, const void* dout, void* din, int batch, int Hi, int Wi, int C, llie_stream stream) {
+  if (!dtype_ok(dtype) || !dout || !din || batch <= 0 || Hi <= 0 || Wi <= 0 || C <= 0 || C % (dtype == 0 ? 4 : 8)) return LLIE_ERR_ARG;
+  return kerr("upsample2x_backward", launch_upsample2x_bwd(dtype, dout, din, batch, Hi, Wi, C, hs(stream)));
+}
+int llie_dilate2x(int dtype, const void* in, void* out, int batch, int Hi, int Wi, int C, llie_stream stream) {
+  if (!dtype_ok(dtype) || !in || !out || batch <= 0 || Hi <= 0 || Wi <= 0 || C <= 0 || C % (dtype == 0 ? 4 : 8)) return LLIE_ERR_ARG;
+  return kerr("dilate2x", launch_dilate2x(dtype, in, out, batch, Hi, Wi, C, hs(stream)));
+}
+int64_t llie_linear_dx_scratch_floats(int batch, int R, int Kc) {
+  if (batch <= 0 || R <= 0 || Kc <= 0) return LLIE_ERR_ARG;
+  return (int64_t)linear_dx_chunks(R) * batch * Kc;
+}
+int llie_linear_dx(int wdtype, const float* dy, int64_t dy_stride, const void* w, float* dx, int batch, int R, int Kc, float* scratch,
+                   int64_t scratch_floats, llie_stream stream) {
+  if (!dtype_ok(wdtype) || !dy || !w || !dx || batch <= 0 || R <= 0 || Kc <= 0 || dy_stride < R ||
+      (scratch && scratch_floats < llie_linear_dx_scratch_floats(batch, R, Kc)))
+    return LLIE_ERR_ARG;
+  return kerr("linear_dx", launch_linear_dx(wdtype, dy, dy_stride, w, dx, batch, R, Kc, hs(stream), scratch));
+}
+int llie_linear_dw(const float* dy, int64_t dy_stride, const float* x, float* dw, float* db, int batch, int R, int Kc, llie_stream stream) {
+  if (!dy || !x || !dw || batch <= 0 || R <= 0 || Kc <= 0 || dy_stride < R) return LLIE_ERR_ARG;
+  return kerr("linear_dw", launch_linear_dw(dy, dy_stride, x, dw, db, batch, R, Kc, hs(stream)));
+}
+int llie_final_bwd_data(int dtype, const float* deps, const float* w, void* da, int batch, int H, int W, int C, int Cout, llie_stream stream) {
+  if (!dtype_ok(dtype) || !deps || !w || !da || batch <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || Cout < 1 || Cout > 4) return LLIE_ERR_ARG;
+  FinalBwdArgs a{};
+  a.deps = deps; a.w = w; a.da = da; a.B = batch; a.H = H; a.W = W; a.C = C; a.Cout = Cout;
+  return kerr("final_bwd_data", launch_final_bwd_data(dtype, a, hs(stream)));
+}
+
+int llie_preprocess_u8(const uint8_t* img, int batch, int H0, int W0, float* out, int S, llie_stream stream) {
+  if (!img || !out) return LLIE_ERR_ARG;
+  return kerr("preprocess_u8", launch_preprocess_u8(img, batch, H0, W0, out, S, hs(stream)), LLIE_ERR_ARG, nullptr);
+}
+int llie_postprocess_u8(const float* x, int batch, int S, uint8_t* img, int H0, int W0, llie_stream stream) {
+  if (!img || !x) return LLIE_ERR_ARG;
+  return kerr("postprocess_u8", launch_postprocess_u8(x, batch, S, img, H0, W0, hs(stream)), LLIE_ERR_ARG, nullptr);
+}
+
+int llie_time_embed(llie_ctx* c, const int64_t* t, int rows, float* emb, float* temb, float* silu_temb, llie_stream stream) {
+  if (!c || !t || !temb || !silu_temb || rows <= 0 || c->cfg.kind != LLIE_UNET) return LLIE_ERR_ARG;
+  if (int rc = check_loaded(c)) return rc;
+  const llie_config& g = c->cfg;
+  TimeArgs ta{};
+  ta.t = t; ta.rows = rows; ta.dim = g.base_channels; ta.T = g.time_embed_dim;
+  ta.freqs = reinterpret_cast<const float*>(c->blob + c->freqs);
+  ta.w1 = reinterpret_cast<const float*>(c->blob + c->t_w1); ta.b1 = reinterpret_cast<const float*>(c->blob + c->t_b1);
+  ta.w3 = reinterpret_cast<const float*>(c->blob + c->t_w3); ta.b3 = reinterpret_cast<const float*>(c->blob + c->t_b3);
+  ta.temb = temb; ta.silu_temb = silu_temb; ta.emb_out = emb;
+  return kerr("time_embed", launch_time_embed(ta, hs(stream)), 0);
+}
+
+// ---- optimiser step (training): one object per parameter set, tables resident on the device
+struct llie_optimizer {
+  int device = 0;
+  OptTensor* tensors = nullptr;
+  OptChunk* chunks = nullptr;
+  double* partial = nullptr;
+  float* amp_coef = nullptr;  // [5]: the AMP step's stats and bias corrections, from its clip kernel to its update kernel
+  int count = 0, nchunks = 0;
+  int64_t numel = 0;
+};
+
+}  // extern "C"
+
+// what both optimiser steps take
+static OptStepArgs opt_args(const llie_optimizer* o, const float* grad_base, const llie_opt_hyper* h, float* stats3) {
+  OptStepArgs a{};
+  a.tensors = o->tensors; a.chunks = o->chunks; a.nchunks = o->nchunks;
+  a.gbase = grad_base; a.partial = o->partial; a.stats = stats3;
+  a.lr = h->lr; a.beta1 = h->beta1; a.beta2 = h->beta2; a.eps = h->eps; a.weight_decay = h->weight_decay;
+  a.max_grad_norm = h->max_grad_norm; a.ema_decay = h->ema_decay; a.grad_scale = h->grad_scale;
+  return a;
+}
+
+extern "C" {
+
+int llie_optimizer_create(const llie_opt_tensor* tensors, int count, llie_optimizer** out) {
+  if (!tensors || count <= 0 || !out) return LLIE_ERR_ARG;
+  std::vector<OptTensor> tt((size_t)count);
+  std::vector<OptChunk> cc;
+  int64_t total = 0;
+  for (int i = 0; i < count; ++i) {
+    const llie_opt_tensor& t = tensors[i];
+    if (!t.param || !t.exp_avg || !t.exp_avg_sq || t.numel <= 0 || t.grad_offset < 0 || t.numel > (int64_t)INT32_MAX) {
+      set_err("optimizer_create: tensor %d: null pointer, empty tensor or negative gradient offset", i);
+      return LLIE_ERR_ARG;
+    }
+    tt[(size_t)i] = OptTensor{t.param, t.exp_avg, t.exp_avg_sq, t.ema, (long long)t.grad_offset, (long long)t.numel};
+    for (int64_t o = 0; o < t.numel; o += kOptChunk) cc.push_back(OptChunk{i, (int)o});
+    total += t.numel;
+  }
+  if (cc.size() > (size_t)INT32_MAX) return LLIE_ERR_ARG;
+  auto* o = new llie_optimizer();
+  o->count = count;
+  o->nchunks = (int)cc.size();
+  o->numel = total;
+  hipError_t e = hipGetDevice(&o->device);
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&o->tensors), tt.size() * sizeof(OptTensor));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&o->chunks), cc.size() * sizeof(OptChunk));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&o->partial), cc.size() * sizeof(double));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&o->amp_coef), 5 * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(o->tensors, tt.data(), tt.size() * sizeof(OptTensor), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(o->chunks, cc.data(), cc.size() * sizeof(OptChunk), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    set_err("optimizer_create: %s", hipGetErrorString(e));
+    llie_optimizer_destroy(o);
+    return e == hipErrorNoDevice ? LLIE_ERR_NO_DEVICE : (int)e;
+  }
+  *out = o;
+  return LLIE_OK;
+}
+
+void llie_optimizer_destroy(llie_optimizer* o) {
+  if (!o) return;
+  if (o->tensors) (void)hipFree(o->tensors);
+  if (o->chunks) (void)hipFree(o->chunks);
+  if (o->partial) (void)hipFree(o->partial);
+  if (o->amp_coef) (void)hipFree(o->amp_coef);
+  delete o;
+}
+
+int64_t llie_optimizer_numel(const llie_optimizer* o) { return o ? o->numel : (int64_t)LLIE_ERR_ARG; }
+
+int llie_optimizer_step(llie_optimizer* o, const float* grad_base, const llie_opt_hyper* h, float* stats3, llie_stream stream) {
+  if (!o || !grad_base || !h || !stats3) return LLIE_ERR_ARG;
+  OptStepArgs a = opt_args(o, grad_base, h, stats3);
+  a.step = h->step; a.skip_nonfinite = h->skip_nonfinite;
+  return kerr("optimizer_step", launch_optimizer_step(a, hs(stream)), LLIE_ERR_ARG, "hyper-parameters outside their ranges (lr, eps, weight_decay >= 0; 0 <= beta < 1; ema_decay <= 1; step >= 1)");
+}
+
+int llie_optimizer_step_amp(llie_optimizer* o, const float* grad_base, const llie_opt_hyper* h, const llie_amp_state* state,
+                            const llie_amp_config* cfg, float* stats3, llie_stream stream) {
+  if (!o || !grad_base || !h || !state || !cfg || !stats3 || !state->scale || !state->growth_tracker || !state->step) return LLIE_ERR_ARG;
+  const OptStepArgs a = opt_args(o, grad_base, h, stats3);
+  OptAmpArgs amp{};
+  amp.scale = state->scale; amp.growth_tracker = state->growth_tracker; amp.step = state->step;
+  amp.growth_factor = cfg->growth_factor; amp.backoff_factor = cfg->backoff_factor; amp.growth_interval = cfg->growth_interval;
+  return kerr("optimizer_step_amp", launch_optimizer_step_amp(a, amp, o->amp_coef, hs(stream)), LLIE_ERR_ARG, "hyper-parameters outside their ranges (lr, eps, weight_decay >= 0; 0 <= beta < 1; ema_decay <= 1)");
+}
+
+// ---- consistency distillation
+int llie_consistency_target(const float* x_t, const float* e_teacher, const int64_t* t, const int64_t* t_next, const float* acp, int table_len,
+                            float* x_next, int batch, int64_t per, llie_stream stream) {
+  DistillArgs a{};
+  a.x_t = x_t; a.e_a = e_teacher; a.t = t; a.t_next = t_next; a.acp = acp; a.table_len = table_len; a.batch = batch; a.per = per; a.out = x_next;
+  return kerr("consistency_target", launch_consistency_target(a, hs(stream)), LLIE_ERR_ARG, "null pointer or empty shape");
+}
+
+int llie_consistency_loss(const float* x_t, const float* x_next, const float* e_student, const float* e_ema, const int64_t* t,
+                          const int64_t* t_next, const float* acp, int table_len, float* d_student, float* loss_out, int batch, int64_t per,
+                          void* scratch, int64_t scratch_bytes, llie_stream stream) {
+  if (batch <= 0 || per <= 0) return LLIE_ERR_ARG;
+  const int64_t need = distill_loss_partials((int64_t)batch * per) * (int64_t)sizeof(double);
+  if (!scratch || scratch_bytes < need) {
+    set_err("consistency_loss: scratch of %lld bytes needed, %lld given", (long long)need, (long long)scratch_bytes);
+    return LLIE_ERR_WORKSPACE;
+  }
+  DistillArgs a{};
+  a.x_t = x_t; a.x_next = x_next; a.e_a = e_student; a.e_b = e_ema; a.t = t; a.t_next = t_next; a.acp = acp; a.table_len = table_len;
+  a.batch = batch; a.per = per; a.out = d_student;
+  return kerr("consistency_loss", launch_consistency_loss(a, reinterpret_cast<double*>(scratch), loss_out, hs(stream)), LLIE_ERR_ARG, "null pointer or empty shape");
+}
+
+// the optimiser's table types: OptTensor.p = source parameter, OptTensor.ema = shadow written in place (m, v unused)
+struct llie_ema {
+  OptTensor* tensors = nullptr;
+  OptChunk* chunks = nullptr;
+  int nchunks = 0;
+};
+
+int llie_ema_create(float* const* ema, const float* const* params, const int64_t* numel, int count, llie_ema** out) {
+  if (!ema || !params || !numel || count <= 0 || !out) return LLIE_ERR_ARG;
+  std::vector<OptTensor> tt((size_t)count);
+  std::vector<OptChunk> cc;
+  for (int i = 0; i < count; ++i) {
+    if (!ema[i] || !params[i] || numel[i] <= 0 || numel[i] > (int64_t)INT32_MAX) {
+      set_err("ema_create: tensor %d: null pointer or empty tensor", i);
+      return LLIE_ERR_ARG;
+    }
+    tt[(size_t)i] = OptTensor{const_cast<float*>(params[i]), nullptr, nullptr, ema[i], 0, (long long)numel[i]};
+    for (int64_t o = 0; o < numel[i]; o += kOptChunk) cc.push_back(OptChunk{i, (int)o});
+  }
+  if (cc.size() > (size_t)INT32_MAX) return LLIE_ERR_ARG;
+  auto* o = new llie_ema();
+  o->nchunks = (int)cc.size();
+  hipError_t e = hipMalloc(reinterpret_cast<void**>(&o->tensors), tt.size() * sizeof(OptTensor));
+  if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&o->chunks), cc.size() * sizeof(OptChunk));
+  if (e == hipSuccess) e = hipMemcpy(o->tensors, tt.data(), tt.size() * sizeof(OptTensor), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(o->chunks, cc.data(), cc.size() * sizeof(OptChunk), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    set_err("ema_create: %s", hipGetErrorString(e));
+    llie_ema_destroy(o);
+    return e == hipErrorNoDevice ? LLIE_ERR_NO_DEVICE : (int)e;
+  }
+  *out = o;
+  return LLIE_OK;
+}
+
+int llie_ema_update(llie_ema* o, double decay, llie_stream stream) {
+  if (!o) return LLIE_ERR_ARG;
+  return kerr("ema_update", launch_ema_lerp(o->tensors, o->chunks, o->nchunks, decay, hs(stream)), LLIE_ERR_ARG, "decay must be in [0, 1]");
+}
+
+void llie_ema_destroy(llie_ema* o) {
+  if (!o) return;
+  if (o->tensors) (void)hipFree(o->tensors);
+  if (o->chunks) (void)hipFree(o->chunks);
+  delete o;
+}
+
+int llie_copy_probe(const void* src, void* dst, int64_t bytes, llie_stream stream) {
+  if (!src || !dst || bytes <= 0) return LLIE_ERR_ARG;
+  return kerr("copy_probe", launch_copy_probe(src, dst, bytes, hs(stream)), LLIE_ERR_ARG, nullptr);
+}
+
+int llie_rw_probe(const void* src, void* dst, int64_t units, int reads, int writes, int nontemporal, llie_stream stream) {
+  if (!src || !dst || units <= 0) return LLIE_ERR_ARG;
+  return kerr("rw_probe", launch_rw_probe(src, dst, units, reads, writes, nontemporal, hs(stream)), LLIE_ERR_ARG, nullptr);
+}
+
+int llie_dwconv3x3_tiles(int H, int W) { return dwconv_ntiles(H, W); }
+int llie_pw_gemm_tile_rows(int P) { return pw_gemm_tile_rows(P); }
+}  // extern "C"

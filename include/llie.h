@@ -430,7 +430,7 @@ int llie_rw_probe(const void* src, void* dst, int64_t units, int reads, int writ
  *   96-channel inputs; 0 = heuristics), "gram" [1] (norm2 statistics of the recompute form from the Gram matrix of the block input, gram.hip;
  *   0 = expand_stats), "pwx" [1] (activation-stationary expand GEMM, pwx.hip; 0 = tile kernel), "se_mfma" [1] (SE MLP of the wide blocks on the
  *   MFMA pipe), "gemm_bk" [0] (0 = auto, 32 = 32-wide K chunks), "nt_mask" [1], "nt_min_mb" [100] (which producers store tensors of at least so
- *   many MiB non-temporally: engine.cpp), "bwd_async" [1] (weight gradients on a side stream; 0 = single stream).
+ *   many MiB non-temporally: tune.cpp), "bwd_async" [1] (weight gradients on a side stream; 0 = single stream).
  * Diagnostics, slow (cycle-stamped kernel builds read back by llie_debug_*_stamps), all [0]: "gemm_stamp", "pwx_stamp", "conv_stamp", "irbx_stamp".
  * Threading: the knobs are plain process-wide variables read by every forward; call llie_tune only while no other
  * thread is inside an llie_* compute call (same rule as the handle itself: SURVEY.md 8b, one stream at a time). */

@@ -54,7 +54,7 @@ def make_spec(variant: str = "small", image_size: int = 256, in_channels: int = 
 
 def gn_groups(c: int) -> int:
     """min(32, C) wherever nn.GroupNorm accepts it (every constructible variant); otherwise the largest divisor of C
-    that is <= 32 (48 -> 24, 144 -> 24): the unpinned deviation shared with the engine (engine.cpp: gn_groups)."""
+    that is <= 32 (48 -> 24, 144 -> 24): the unpinned deviation shared with the engine (engine.h: gn_groups)."""
     g = min(32, c)
     while c % g:
         g -= 1
