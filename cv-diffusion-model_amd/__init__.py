@@ -20,6 +20,8 @@ from . import ops  # registers torch.ops.llie.*
 from .ops import register_model
 from .hostio import (load_checkpoint, extract_state_dict, preprocess_array, postprocess_array, resize_bilinear,
                      preprocess_device, postprocess_device)
+from .tiling import (tile_origins, gather_tiles_array, blend_tiles_array, gather_tiles_device, gather_noise_device,
+                     blend_tiles_device, enhance_tiled)
 
 __all__ = [
     "EfficientUNet", "EfficientUNetConfig", "create_efficient_unet", "InvertedResidualBlock", "LinearAttention", "SqueezeExcitation",
@@ -27,4 +29,6 @@ __all__ = [
     "LowLightDiffusionOutput", "LowLightLCMDistillation", "normalize_image", "denormalize_image", "shard_range", "enhance_sharded",
     "all_gather_batch", "all_reduce_gradients", "FusedAdamW", "FusedGradScaler", "TrainStep", "DistillStep", "register_model", "build_library", "library_path", "load_checkpoint", "extract_state_dict",
     "preprocess_array", "postprocess_array", "resize_bilinear", "preprocess_device", "postprocess_device",
+    "tile_origins", "gather_tiles_array", "blend_tiles_array", "gather_tiles_device", "gather_noise_device", "blend_tiles_device",
+    "enhance_tiled",
 ]

@@ -33,6 +33,7 @@ EXPORTS = [
     "llie_groupnorm_backward", "llie_groupnorm_backward_scratch_floats", "llie_linattn_backward", "llie_linattn_dkv_floats",
     "llie_upsample2x_backward", "llie_dilate2x", "llie_linear_dx", "llie_linear_dx_scratch_floats", "llie_linear_dw",
     "llie_final_bwd_data",
+    "llie_tile_count", "llie_tile_origins", "llie_tile_gather_u8", "llie_tile_gather_f32", "llie_tile_blend_u8",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 
@@ -148,6 +149,11 @@ def lib() -> C.CDLL:
     L.llie_flops.restype = i64
     L.llie_preprocess_u8.argtypes = [vp, ci, ci, ci, vp, ci, vp]
     L.llie_postprocess_u8.argtypes = [vp, ci, ci, vp, ci, ci, vp]
+    L.llie_tile_count.argtypes = [ci, ci, ci]
+    L.llie_tile_origins.argtypes = [ci, ci, ci, C.POINTER(ci)]
+    L.llie_tile_gather_u8.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp]
+    L.llie_tile_gather_f32.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]
+    L.llie_tile_blend_u8.argtypes = [vp, ci, ci, ci, ci, vp, vp]
     L.llie_pw_gemm.argtypes = [ci, C.POINTER(GemmSeg), ci, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     L.llie_pw_gemm_tile_rows.argtypes = [ci]
     L.llie_pw_expand.argtypes = [ci, C.POINTER(GemmSeg), ci, vp, vp, vp, vp, ci, ci, ci, vp]

@@ -257,6 +257,30 @@ int llie_postprocess_u8(const float* x, int batch, int S, uint8_t* img, int H0, 
   return kerr("postprocess_u8", launch_postprocess_u8(x, batch, S, img, H0, W0, hs(stream)), LLIE_ERR_ARG, nullptr);
 }
 
+int llie_tile_count(int L, int S, int v) {
+  if (!tile_plan_ok(L, L, S, v)) return LLIE_ERR_ARG;
+  return tile_axis_count(L, S, v);
+}
+int llie_tile_origins(int L, int S, int v, int* out) {
+  if (!out || !tile_plan_ok(L, L, S, v)) return LLIE_ERR_ARG;
+  const int n = tile_axis_count(L, S, v);
+  for (int i = 0; i < n; ++i) out[i] = tile_axis_origin(i, L, S, n);
+  return LLIE_OK;
+}
+int llie_tile_gather_u8(const uint8_t* img, int H, int W, int S, int v, int first, int count, float* tiles, llie_stream stream) {
+  if (!img || !tiles) return LLIE_ERR_ARG;
+  return kerr("tile_gather_u8", launch_tile_gather_u8(img, TilePlan{H, W, S, v, first, count}, tiles, hs(stream)), LLIE_ERR_ARG, nullptr);
+}
+int llie_tile_gather_f32(const float* canvas, int planes, int H, int W, int S, int v, int first, int count, float* out, llie_stream stream) {
+  if (!canvas || !out) return LLIE_ERR_ARG;
+  return kerr("tile_gather_f32", launch_tile_gather_f32(canvas, planes, TilePlan{H, W, S, v, first, count}, out, hs(stream)), LLIE_ERR_ARG,
+              nullptr);
+}
+int llie_tile_blend_u8(const float* tiles, int H, int W, int S, int v, uint8_t* img, llie_stream stream) {
+  if (!tiles || !img) return LLIE_ERR_ARG;
+  return kerr("tile_blend_u8", launch_tile_blend_u8(tiles, TilePlan{H, W, S, v, 0, 1}, img, hs(stream)), LLIE_ERR_ARG, nullptr);
+}
+
 int llie_time_embed(llie_ctx* c, const int64_t* t, int rows, float* emb, float* temb, float* silu_temb, llie_stream stream) {
   if (!c || !t || !temb || !silu_temb || rows <= 0 || c->cfg.kind != LLIE_UNET) return LLIE_ERR_ARG;
   if (int rc = check_loaded(c)) return rc;

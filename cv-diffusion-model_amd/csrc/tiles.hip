@@ -1,0 +1,222 @@
+// Full-resolution images through a fixed-size denoiser: the byte work either side of `enhance` when an image is cut into
+// overlapping S x S tiles (kernels.h (11) has the plan).  Bit-exact with the NumPy twins in tiling.py.
+//
+//   tile_gather_u8:   tile[t][c][y][x] = float(img[min(oy + y, H-1)][min(ox + x, W-1)][c]) / 127.5f - 1.0f
+//   tile_gather_f32:  out[k][j][c][y][x] = canvas[k][c][oy + y][ox + x]           (the noise every tile of an image shares)
+//   tile_blend_u8:    per pixel and channel, over the covering tiles in ascending tile number:
+//                       g = w[Y - oy] * w[X - ox];  num = num + val * g;  den = den + g     (separate fp32 operations)
+//                     out = (uint8) trunc(min(max((num / den + 1.0f) * 127.5f, 0), 255)),  w[k] = min(k + 1, S - k, v) / v  (1 if v == 0)
+//
+// Origins are computed in the kernels from (L, S, v): nothing is uploaded per call.  A thread owns four consecutive x, so a
+// wave moves contiguous runs: 768 bytes of pixels and 1 KB of each fp32 plane.  The fp32 rows start at arbitrary origins, so
+// their four-float accesses are only 4-byte aligned (global_load/store_dwordx4 need no more than that); the 12 pixel bytes go
+// as three dwords when their address allows it and as bytes otherwise.  The blend is a gather: no atomics, fixed order.
+#include "common.h"
+#include "kernels.h"
+
+namespace llie {
+
+constexpr int kTileThreads = 256;
+typedef f32x4 f32x4u __attribute__((aligned(4)));
+
+__device__ __forceinline__ void tile_origin_of(const TilePlan& p, int t, int ny, int nx, int& oy, int& ox) {
+  const int iy = t / nx, ix = t - iy * nx;
+  oy = tile_axis_origin(iy, p.H, p.S, ny);
+  ox = tile_axis_origin(ix, p.W, p.S, nx);
+}
+
+// 12 consecutive bytes (four RGB pixels)
+__device__ __forceinline__ void load12(const uint8_t* s, uint32_t (&b)[12]) {
+  if ((reinterpret_cast<uintptr_t>(s) & 3) == 0) {
+    const uint32_t* s4 = reinterpret_cast<const uint32_t*>(s);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const uint32_t d = s4[i];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) b[i * 4 + k] = (d >> (8 * k)) & 0xffu;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) b[i] = s[i];
+  }
+}
+__device__ __forceinline__ void store12(uint8_t* d, const uint32_t (&b)[12]) {
+  if ((reinterpret_cast<uintptr_t>(d) & 3) == 0) {
+    uint32_t* d4 = reinterpret_cast<uint32_t*>(d);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) d4[i] = b[i * 4] | (b[i * 4 + 1] << 8) | (b[i * 4 + 2] << 16) | (b[i * 4 + 3] << 24);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) d[i] = (uint8_t)b[i];
+  }
+}
+
+// grid.x = count * bpt (bpt workgroups cover the S * ceil(S/4) quads of a tile)
+__global__ void __launch_bounds__(kTileThreads) tile_gather_u8_kernel(const uint8_t* __restrict__ img, TilePlan p, int ny, int nx, int bpt,
+                                                                      float* __restrict__ tiles) {
+#pragma clang fp contract(off)
+  const int S = p.S, qpr = (S + 3) >> 2;
+  const int j = blockIdx.x / bpt;
+  const int q = (blockIdx.x - j * bpt) * kTileThreads + threadIdx.x;
+  if (q >= qpr * S) return;
+  const int y = q / qpr, x0 = (q - y * qpr) * 4;
+  int oy, ox;
+  tile_origin_of(p, p.first + j, ny, nx, oy, ox);
+  const uint8_t* src = img + (size_t)min(oy + y, p.H - 1) * p.W * 3;
+  const int X = ox + x0;
+  uint32_t b[12];
+  if (X + 3 < p.W) {
+    load12(src + (size_t)X * 3, b);
+  } else {  // the image ends inside this quad (only where it is narrower than a tile): replicate its last column
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint8_t* px = src + (size_t)min(X + k, p.W - 1) * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) b[k * 3 + c] = px[c];
+    }
+  }
+  float* dst = tiles + (((size_t)j * 3) * S + y) * S + x0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c, dst += (size_t)S * S) {
+    f32x4 u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) u[k] = (float)b[k * 3 + c] / 127.5f - 1.0f;
+    if (x0 + 3 < S) {
+      *reinterpret_cast<f32x4u*>(dst) = u;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (x0 + k < S) dst[k] = u[k];
+    }
+  }
+}
+
+// grid.x as above, grid.y = plane of the canvas (k * 3 + c)
+__global__ void __launch_bounds__(kTileThreads) tile_gather_f32_kernel(const float* __restrict__ canvas, TilePlan p, int ny, int nx, int bpt,
+                                                                       float* __restrict__ out) {
+  const int S = p.S, qpr = (S + 3) >> 2;
+  const int j = blockIdx.x / bpt;
+  const int q = (blockIdx.x - j * bpt) * kTileThreads + threadIdx.x;
+  if (q >= qpr * S) return;
+  const int y = q / qpr, x0 = (q - y * qpr) * 4;
+  int oy, ox;
+  tile_origin_of(p, p.first + j, ny, nx, oy, ox);
+  const int Hc = max(p.H, S), Wc = max(p.W, S);  // oy + S <= Hc and ox + S <= Wc by construction of the plan
+  const int plane = blockIdx.y, k = plane / 3, c = plane - k * 3;
+  const float* src = canvas + ((size_t)plane * Hc + oy + y) * Wc + ox + x0;
+  float* dst = out + ((((size_t)k * p.count + j) * 3 + c) * S + y) * S + x0;
+  if (x0 + 3 < S) {
+    *reinterpret_cast<f32x4u*>(dst) = *reinterpret_cast<const f32x4u*>(src);
+  } else {
+    for (int i = 0; x0 + i < S; ++i) dst[i] = src[i];
+  }
+}
+
+__device__ __forceinline__ float tile_window(int k, int S, int v) {
+  return v == 0 ? 1.0f : (float)min(min(k + 1, S - k), v) / (float)v;
+}
+// the tiles of one axis that cover position P: [lo, hi]
+__device__ __forceinline__ void tile_cover(int P, int L, int S, int n, int& lo, int& hi) {
+  if (n <= 1) { lo = hi = 0; return; }
+  const int D = L - S, m = n - 1;
+  hi = min(m, ((P + 1) * m - 1) / D);  // the last i with floor(i D / m) <= P
+  lo = hi;
+  while (lo > 0 && tile_axis_origin(lo - 1, L, S, n) + S > P) --lo;
+}
+
+// one thread per four consecutive output pixels of a row
+__global__ void __launch_bounds__(kTileThreads) tile_blend_u8_kernel(const float* __restrict__ tiles, TilePlan p, int ny, int nx,
+                                                                     uint8_t* __restrict__ img) {
+#pragma clang fp contract(off)
+  const int S = p.S, v = p.v, H = p.H, W = p.W;
+  const int qpr = (W + 3) >> 2;
+  const int64_t q = (int64_t)blockIdx.x * kTileThreads + threadIdx.x;
+  if (q >= (int64_t)qpr * H) return;
+  const int Y = (int)(q / qpr), X0 = (int)(q - (int64_t)Y * qpr) * 4;
+  const int Xl = min(X0 + 3, W - 1);
+  int ylo, yhi, xlo, xhi, unused;
+  tile_cover(Y, H, S, ny, ylo, yhi);
+  tile_cover(X0, W, S, nx, xlo, unused);
+  tile_cover(Xl, W, S, nx, unused, xhi);
+  float num[4][3], den[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) den[k] = num[k][0] = num[k][1] = num[k][2] = 0.0f;
+  for (int iy = ylo; iy <= yhi; ++iy) {
+    const int ty = Y - tile_axis_origin(iy, H, S, ny);
+    const float wy = tile_window(ty, S, v);
+    for (int ix = xlo; ix <= xhi; ++ix) {  // ascending tile number iy * nx + ix
+      const int tx = X0 - tile_axis_origin(ix, W, S, nx);
+      const float* src = tiles + (((size_t)(iy * nx + ix) * 3) * S + ty) * S;
+      src += tx;  // dereferenced only where 0 <= tx + k < S
+      if (tx >= 0 && tx + 3 < S && X0 + 3 < W) {
+        f32x4 val[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) val[c] = *reinterpret_cast<const f32x4u*>(src + (size_t)c * S * S);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float g = wy * tile_window(tx + k, S, v);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) num[k][c] = num[k][c] + val[c][k] * g;
+          den[k] = den[k] + g;
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (tx + k < 0 || tx + k >= S || X0 + k >= W) continue;
+          const float g = wy * tile_window(tx + k, S, v);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) num[k][c] = num[k][c] + src[(size_t)c * S * S + k] * g;
+          den[k] = den[k] + g;
+        }
+      }
+    }
+  }
+  uint32_t b[12];
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float r = num[k][c] / den[k];  // pixels past W have den == 0 and are not stored
+      b[k * 3 + c] = (uint32_t)truncf(fminf(fmaxf((r + 1.0f) * 127.5f, 0.f), 255.f));
+    }
+  uint8_t* dst = img + ((size_t)Y * W + X0) * 3;
+  if (X0 + 3 < W) {
+    store12(dst, b);
+  } else {
+    for (int i = 0; i < (W - X0) * 3; ++i) dst[i] = (uint8_t)b[i];
+  }
+}
+
+static bool chunk_ok(const TilePlan& p, int ny, int nx, int bpt) {
+  return p.first >= 0 && p.count > 0 && (long long)p.first + p.count <= (long long)ny * nx && (long long)p.count * bpt < (1ll << 31);
+}
+
+hipError_t launch_tile_gather_u8(const uint8_t* img, const TilePlan& p, float* tiles, hipStream_t s) {
+  if (!tile_plan_ok(p.H, p.W, p.S, p.v)) return hipErrorInvalidValue;
+  const int ny = tile_axis_count(p.H, p.S, p.v), nx = tile_axis_count(p.W, p.S, p.v);
+  const int bpt = (int)(((long long)((p.S + 3) / 4) * p.S + kTileThreads - 1) / kTileThreads);
+  if (!chunk_ok(p, ny, nx, bpt)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tile_gather_u8_kernel, dim3((unsigned)(p.count * bpt)), dim3(kTileThreads), 0, s, img, p, ny, nx, bpt, tiles);
+  return hipGetLastError();
+}
+
+hipError_t launch_tile_gather_f32(const float* canvas, int planes, const TilePlan& p, float* out, hipStream_t s) {
+  if (!tile_plan_ok(p.H, p.W, p.S, p.v) || planes <= 0 || planes % 3 || planes > 65535) return hipErrorInvalidValue;
+  const int ny = tile_axis_count(p.H, p.S, p.v), nx = tile_axis_count(p.W, p.S, p.v);
+  const int bpt = (int)(((long long)((p.S + 3) / 4) * p.S + kTileThreads - 1) / kTileThreads);
+  if (!chunk_ok(p, ny, nx, bpt)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tile_gather_f32_kernel, dim3((unsigned)(p.count * bpt), (unsigned)planes), dim3(kTileThreads), 0, s, canvas, p, ny, nx,
+                     bpt, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_tile_blend_u8(const float* tiles, const TilePlan& p, uint8_t* img, hipStream_t s) {
+  if (!tile_plan_ok(p.H, p.W, p.S, p.v)) return hipErrorInvalidValue;
+  const int ny = tile_axis_count(p.H, p.S, p.v), nx = tile_axis_count(p.W, p.S, p.v);
+  const long long blocks = ((long long)((p.W + 3) / 4) * p.H + kTileThreads - 1) / kTileThreads;
+  if (blocks >= (1ll << 31)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tile_blend_u8_kernel, dim3((unsigned)blocks), dim3(kTileThreads), 0, s, tiles, p, ny, nx, img);
+  return hipGetLastError();
+}
+
+}  // namespace llie

@@ -283,6 +283,31 @@ int llie_graph_cache_entries(const llie_ctx* ctx);
 int llie_preprocess_u8(const uint8_t* img, int batch, int H0, int W0, float* out, int S, llie_stream stream);
 int llie_postprocess_u8(const float* x, int batch, int S, uint8_t* img, int H0, int W0, llie_stream stream);
 
+/* Full-resolution images as overlapping S x S tiles (S = image_size), blended back on the device.
+ * The plan of one axis of length L with overlap v (0 <= 2v <= S): one tile at origin 0 when L <= S, otherwise
+ * n = ceil((L - S) / (S - v)) + 1 tiles at origins floor(i * (L - S) / (n - 1)), i = 0 .. n-1 (the first starts at 0, the last
+ * ends at L).  The tiles of an H x W image are numbered row-major, t = iy * nx + ix; `first` / `count` select the chunk
+ * [first, first + count) of them.
+ *   llie_tile_count:      n of one axis (host only, no GPU needed)
+ *   llie_tile_origins:    writes the n origins of one axis to `out` (host only, no GPU needed)
+ *   llie_tile_gather_u8:  uint8 HWC RGB [H][W][3] -> fp32 NCHW tiles [count][3][S][S],
+ *                         tile[c][y][x] = img[min(oy + y, H-1)][min(ox + x, W-1)][c] / 127.5 - 1 (llie_preprocess_u8's normalisation;
+ *                         the min replicates the edge where the image is smaller than a tile)
+ *   llie_tile_gather_f32: fp32 canvas [planes][max(H,S)][max(W,S)], planes = 3 k -> out [k][count][3][S][S],
+ *                         out[k][j][c][y][x] = canvas[3 k + c][oy + y][ox + x]: the noise of llie_enhance for a chunk of tiles, cut
+ *                         from one canvas so that overlapping tiles see the same noise where they overlap
+ *   llie_tile_blend_u8:   fp32 tiles [T][3][S][S] (all T = ny * nx tiles) -> uint8 HWC RGB [H][W][3]: per pixel the mean of the
+ *                         covering tiles weighted by w[y] * w[x], w[k] = min(k + 1, S - k, v) / v (1 when v == 0), accumulated in
+ *                         ascending tile number, then llie_postprocess_u8's (r + 1) * 127.5, clip [0,255], truncate.
+ * Bit-exact with the host implementation in tiling.py (fp32 arithmetic without fused multiply-adds, fixed order, no atomics).
+ * v < 0, 2v > S, a non-positive size, a chunk outside the plan or planes not a positive multiple of 3 return LLIE_ERR_ARG. */
+int llie_tile_count(int L, int S, int v);
+int llie_tile_origins(int L, int S, int v, int* out);
+int llie_tile_gather_u8(const uint8_t* img, int H, int W, int S, int v, int first, int count, float* tiles, llie_stream stream);
+int llie_tile_gather_f32(const float* canvas, int planes, int H, int W, int S, int v, int first, int count, float* out,
+                         llie_stream stream);
+int llie_tile_blend_u8(const float* tiles, int H, int W, int S, int v, uint8_t* img, llie_stream stream);
+
 /* ---- Kernel-level entry points (unit tests and tuning; SURVEY.md 8b "per-kernel entry points").
  * Activations are NHWC rows in the compute dtype T (llie_dtype); see DESIGN.md section 3.
  *

@@ -2,7 +2,8 @@
 """Image / folder enhancement CLI on the MI355X engine -- flag-compatible counterpart of the reference's
 scripts/inference.py (:30-62): --input --output --checkpoint --model --format --variant --image_size
 --num_steps --device.  Only --format pytorch exists here (ONNX / TFLite are the reference's mobile
-deployment targets, out of scope); extension: --dtype {fp32,fp16,bf16}.
+deployment targets, out of scope); extensions: --dtype {fp32,fp16,bf16}, --noise_seed, and --tile [--tile_overlap N]
+[--tile_batch N], which enhances the image at its own resolution as overlapping image_size tiles instead of resizing it.
 """
 import argparse
 import importlib
@@ -17,6 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 M = importlib.import_module("cv-diffusion-model_amd")
 hostio = importlib.import_module("cv-diffusion-model_amd.hostio")
+tiling = importlib.import_module("cv-diffusion-model_amd.tiling")
 
 
 def parse_args(argv=None):
@@ -34,6 +36,11 @@ def parse_args(argv=None):
     p.add_argument("--noise_seed", type=int, default=None,
                    help="(extension) draw the loop's noise on the CPU generator with this seed, in the reference's order, "
                         "instead of on the device: makes a run reproducible against the CPU reference")
+    p.add_argument("--tile", action="store_true",
+                   help="(extension) no resize: enhance the image at its own resolution as overlapping image_size tiles, blended "
+                        "on the device; --noise_seed then seeds the per-image noise canvas")
+    p.add_argument("--tile_overlap", type=int, default=None, help="overlap of neighbouring tiles in pixels (default image_size // 8)")
+    p.add_argument("--tile_batch", type=int, default=32, help="tiles per enhance call")
     return p.parse_args(argv)
 
 
@@ -47,11 +54,21 @@ def load_model(args):
     return model.to(args.device).eval()
 
 
-def process_single_image(args, model, input_path: str, output_path: str) -> float:
-    print(f"Processing: {input_path}")
-    rgb = hostio.load_image(input_path)
+def enhance_tiled_image(args, model, rgb):
+    """--tile: uint8 [H,W,3] -> uint8 [H,W,3] at the input's resolution."""
+    noise = None
+    if args.noise_seed is not None:  # the canvas every tile reads its noise from, drawn entry by entry in enhance's order
+        g = torch.Generator().manual_seed(args.noise_seed)
+        hc, wc = max(rgb.shape[0], args.image_size), max(rgb.shape[1], args.image_size)
+        noise = torch.stack([torch.randn(3, hc, wc, generator=g) for _ in range(args.num_steps)])
+    out = tiling.enhance_tiled(model, torch.from_numpy(rgb).to(args.device), args.num_steps, overlap=args.tile_overlap,
+                               tile_batch=args.tile_batch, noise=noise)
+    return out.cpu().numpy()
+
+
+def enhance_resized_image(args, model, rgb):
+    """The reference's path: squash to image_size, enhance, stretch back to the input's size."""
     original = rgb.shape[:2]
-    start = time.perf_counter()
     with torch.no_grad():
         # uint8 goes up, uint8 comes back: resize + normalise / denormalise run on the device
         # (bit-exact twins of hostio.preprocess_array / postprocess_array, i.e. inference.py:99-134)
@@ -61,7 +78,14 @@ def process_single_image(args, model, input_path: str, output_path: str) -> floa
             g = torch.Generator().manual_seed(args.noise_seed)
             noise = torch.stack([torch.randn(1, 3, args.image_size, args.image_size, generator=g) for _ in range(args.num_steps)])
         enhanced = model.enhance(x, num_inference_steps=args.num_steps, noise=noise)
-        out = hostio.postprocess_device(enhanced, original)[0].cpu().numpy()
+        return hostio.postprocess_device(enhanced, original)[0].cpu().numpy()
+
+
+def process_single_image(args, model, input_path: str, output_path: str) -> float:
+    print(f"Processing: {input_path}")
+    rgb = hostio.load_image(input_path)
+    start = time.perf_counter()
+    out = enhance_tiled_image(args, model, rgb) if args.tile else enhance_resized_image(args, model, rgb)
     elapsed = time.perf_counter() - start
     hostio.save_image(output_path, out)
     print(f"  Saved to: {output_path}")
