@@ -22,6 +22,8 @@ from .hostio import (load_checkpoint, extract_state_dict, preprocess_array, post
                      preprocess_device, postprocess_device)
 from .tiling import (tile_origins, gather_tiles_array, blend_tiles_array, gather_tiles_device, gather_noise_device,
                      blend_tiles_device, enhance_tiled)
+from .data import (DeviceFrameStore, DevicePairLoader, create_device_dataloaders, epoch_plan, augment_pairs_host, augment_synth_host,
+                   augment_pairs_device, augment_synth_device)
 
 __all__ = [
     "EfficientUNet", "EfficientUNetConfig", "create_efficient_unet", "InvertedResidualBlock", "LinearAttention", "SqueezeExcitation",
@@ -31,4 +33,6 @@ __all__ = [
     "preprocess_array", "postprocess_array", "resize_bilinear", "preprocess_device", "postprocess_device",
     "tile_origins", "gather_tiles_array", "blend_tiles_array", "gather_tiles_device", "gather_noise_device", "blend_tiles_device",
     "enhance_tiled",
+    "DeviceFrameStore", "DevicePairLoader", "create_device_dataloaders", "epoch_plan", "augment_pairs_host", "augment_synth_host",
+    "augment_pairs_device", "augment_synth_device",
 ]

@@ -34,6 +34,7 @@ EXPORTS = [
     "llie_upsample2x_backward", "llie_dilate2x", "llie_linear_dx", "llie_linear_dx_scratch_floats", "llie_linear_dw",
     "llie_final_bwd_data",
     "llie_tile_count", "llie_tile_origins", "llie_tile_gather_u8", "llie_tile_gather_f32", "llie_tile_blend_u8",
+    "llie_aug_pair_u8", "llie_aug_synth_u8",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 
@@ -154,6 +155,8 @@ def lib() -> C.CDLL:
     L.llie_tile_gather_u8.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp]
     L.llie_tile_gather_f32.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]
     L.llie_tile_blend_u8.argtypes = [vp, ci, ci, ci, ci, vp, vp]
+    L.llie_aug_pair_u8.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp]
+    L.llie_aug_synth_u8.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]
     L.llie_pw_gemm.argtypes = [ci, C.POINTER(GemmSeg), ci, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     L.llie_pw_gemm_tile_rows.argtypes = [ci]
     L.llie_pw_expand.argtypes = [ci, C.POINTER(GemmSeg), ci, vp, vp, vp, vp, ci, ci, ci, vp]

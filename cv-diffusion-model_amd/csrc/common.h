@@ -20,8 +20,35 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef f32x4 f32x4u __attribute__((aligned(4)));  // four floats at a 4-byte aligned address (global_load/store_dwordx4 need no more)
 
 constexpr int kWave = 64;
+
+// 12 consecutive bytes (four RGB pixels of a uint8 HWC image): three dwords when the address allows it, bytes otherwise
+__device__ __forceinline__ void load12(const uint8_t* s, uint32_t (&b)[12]) {
+  if ((reinterpret_cast<uintptr_t>(s) & 3) == 0) {
+    const uint32_t* s4 = reinterpret_cast<const uint32_t*>(s);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const uint32_t d = s4[i];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) b[i * 4 + k] = (d >> (8 * k)) & 0xffu;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) b[i] = s[i];
+  }
+}
+__device__ __forceinline__ void store12(uint8_t* d, const uint32_t (&b)[12]) {
+  if ((reinterpret_cast<uintptr_t>(d) & 3) == 0) {
+    uint32_t* d4 = reinterpret_cast<uint32_t*>(d);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) d4[i] = b[i * 4] | (b[i * 4 + 1] << 8) | (b[i * 4 + 2] << 16) | (b[i * 4 + 3] << 24);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) d[i] = (uint8_t)b[i];
+  }
+}
 
 // Host: raise a kernel's dynamic-LDS limit once per *device* (the attribute lives in the per-device function object, so a
 // process that drives two GPUs -- enhance_sharded, model.to("cuda:1") -- needs it set on both).  `done` is the call

@@ -281,6 +281,25 @@ int llie_tile_blend_u8(const float* tiles, int H, int W, int S, int v, uint8_t* 
   return kerr("tile_blend_u8", launch_tile_blend_u8(tiles, TilePlan{H, W, S, v, 0, 1}, img, hs(stream)), LLIE_ERR_ARG, nullptr);
 }
 
+static_assert(sizeof(llie_aug_row) == sizeof(AugRow) && sizeof(AugRow) == 48, "llie_aug_row and AugRow are one layout");
+static AugArgs aug_args(const uint8_t* pool, const int64_t* table, int N, const llie_aug_row* plan, int first, int count, int S, const float* z,
+                        float* low, float* high, uint8_t* low_u8, uint8_t* high_u8) {
+  AugArgs a{};
+  a.pool = pool; a.table = table; a.N = N; a.plan = reinterpret_cast<const AugRow*>(plan); a.first = first; a.count = count; a.S = S;
+  a.z = z; a.low = low; a.high = high; a.low_u8 = low_u8; a.high_u8 = high_u8;
+  return a;
+}
+int llie_aug_pair_u8(const uint8_t* pool, const int64_t* table, int N, const llie_aug_row* plan, int first, int count, int S,
+                     float* low, float* high, uint8_t* low_u8, uint8_t* high_u8, llie_stream stream) {
+  return kerr("aug_pair_u8", launch_aug_pair_u8(aug_args(pool, table, N, plan, first, count, S, nullptr, low, high, low_u8, high_u8), hs(stream)),
+              LLIE_ERR_ARG, nullptr);
+}
+int llie_aug_synth_u8(const uint8_t* pool, const int64_t* table, int N, const llie_aug_row* plan, int first, int count, int S,
+                      const float* z, float* low, float* high, uint8_t* low_u8, uint8_t* high_u8, llie_stream stream) {
+  return kerr("aug_synth_u8", launch_aug_synth_u8(aug_args(pool, table, N, plan, first, count, S, z, low, high, low_u8, high_u8), hs(stream)),
+              LLIE_ERR_ARG, nullptr);
+}
+
 int llie_time_embed(llie_ctx* c, const int64_t* t, int rows, float* emb, float* temb, float* silu_temb, llie_stream stream) {
   if (!c || !t || !temb || !silu_temb || rows <= 0 || c->cfg.kind != LLIE_UNET) return LLIE_ERR_ARG;
   if (int rc = check_loaded(c)) return rc;

@@ -556,4 +556,28 @@ hipError_t launch_tile_gather_f32(const float* canvas, int planes, const TilePla
 // (r + 1) * 127.5 clipped and truncated; one thread per 4 output pixels, no atomics
 hipError_t launch_tile_blend_u8(const float* tiles, const TilePlan& p, uint8_t* img, hipStream_t s);
 
+// (12) device-resident paired data loader (augment.hip).  Frame store: one uint8 pool of HWC RGB frames with packed rows, and a
+// table int64 [N][3] = (byte offset into the pool, H, W) per frame.  Epoch plan: one AugRow per sample (== llie_aug_row); a launch
+// handles rows [first, first + count) and writes sample j = row - first.
+constexpr int kAugHflip = 1, kAugVflip = 2, kAugRotate = 4;
+struct AugRow {
+  int low_frame, high_frame;  // frame indices (aug_synth_u8 reads high_frame only: the normal-light frame)
+  int y0, x0;                 // crop origin, the same in both frames
+  int flags;                  // kAugHflip | kAugVflip | kAugRotate
+  float ca, sa;               // cos and sin of the rotation angle, rounded once from float64 on the host
+  float gamma, level;         // synthetic degradation: darkening exponent, noise standard deviation
+  float scale[3];             // per-channel colour shift ((1, 1, 1) = none)
+};
+struct AugArgs {
+  const uint8_t* pool; const int64_t* table; int N;
+  const AugRow* plan; int first, count;
+  int S;                      // crop side; every frame must be at least S x S
+  const float* z;             // aug_synth_u8 only: standard-normal noise fp32 [count][S][S][3]
+  float* low; float* high;    // fp32 [count][3][S][S] in [-1, 1]
+  uint8_t* low_u8; uint8_t* high_u8;  // optional uint8 [count][S][S][3]: the bytes before normalisation
+};
+// null pointers (other than the optional two), N < 1, S < 1, first < 0 or count < 0: hipErrorInvalidValue; count == 0 launches nothing
+hipError_t launch_aug_pair_u8(const AugArgs& a, hipStream_t s);
+hipError_t launch_aug_synth_u8(const AugArgs& a, hipStream_t s);
+
 }  // namespace llie

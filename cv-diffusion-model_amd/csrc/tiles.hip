@@ -17,38 +17,11 @@
 namespace llie {
 
 constexpr int kTileThreads = 256;
-typedef f32x4 f32x4u __attribute__((aligned(4)));
 
 __device__ __forceinline__ void tile_origin_of(const TilePlan& p, int t, int ny, int nx, int& oy, int& ox) {
   const int iy = t / nx, ix = t - iy * nx;
   oy = tile_axis_origin(iy, p.H, p.S, ny);
   ox = tile_axis_origin(ix, p.W, p.S, nx);
-}
-
-// 12 consecutive bytes (four RGB pixels)
-__device__ __forceinline__ void load12(const uint8_t* s, uint32_t (&b)[12]) {
-  if ((reinterpret_cast<uintptr_t>(s) & 3) == 0) {
-    const uint32_t* s4 = reinterpret_cast<const uint32_t*>(s);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const uint32_t d = s4[i];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) b[i * 4 + k] = (d >> (8 * k)) & 0xffu;
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 12; ++i) b[i] = s[i];
-  }
-}
-__device__ __forceinline__ void store12(uint8_t* d, const uint32_t (&b)[12]) {
-  if ((reinterpret_cast<uintptr_t>(d) & 3) == 0) {
-    uint32_t* d4 = reinterpret_cast<uint32_t*>(d);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) d4[i] = b[i * 4] | (b[i * 4 + 1] << 8) | (b[i * 4 + 2] << 16) | (b[i * 4 + 3] << 24);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 12; ++i) d[i] = (uint8_t)b[i];
-  }
 }
 
 // grid.x = count * bpt (bpt workgroups cover the S * ceil(S/4) quads of a tile)

@@ -308,6 +308,38 @@ int llie_tile_gather_f32(const float* canvas, int planes, int H, int W, int S, i
                          llie_stream stream);
 int llie_tile_blend_u8(const float* tiles, int H, int W, int S, int v, uint8_t* img, llie_stream stream);
 
+/* Device-resident paired data loader (src/training/dataset.py): the training frames stay on the device as uint8 and one launch
+ * per batch crops, flips, rotates or degrades, and normalises them into the fp32 NCHW pair a training step takes.
+ *   pool:   uint8, every frame HWC RGB with packed rows;  table: int64 [N][3] = (byte offset into pool, H, W) per frame; every
+ *           frame is at least S x S
+ *   plan:   one llie_aug_row per sample of the epoch; a call handles rows [first, first + count) and writes sample row - first
+ *   low / high: fp32 [count][3][S][S] = byte / 127.5 - 1;  low_u8 / high_u8 (or NULL): uint8 [count][S][S][3], the bytes themselves
+ * With crop(yy, xx) = frame[y0 + (vflip ? S-1-yy : yy)][x0 + (hflip ? S-1-xx : xx)]:
+ *   aug_pair_u8, the same for frames low_frame and high_frame: without LLIE_AUG_ROTATE byte = crop(y, x); with it the crop is
+ *           rotated about its centre c = (S-1)/2 by the angle whose cosine and sine are (ca, sa): xs = (ca*u + sa*v) + c,
+ *           ys = (-sa*u + ca*v) + c with u = x - c, v = y - c, bilinear over the four neighbours with reflect-101 borders,
+ *           byte = clip(floor(value + 0.5), 0, 255).  |angle| <= 15 degrees.
+ *   aug_synth_u8 (SyntheticLowLightDataset._create_low_light), frame high_frame, hflip only: normal byte nb = crop(y, x);
+ *           n = clamp(powf(nb / 255, gamma) + level * z, 0, 1); n = clamp(n * scale[c], 0, 1); low byte = trunc(n * 255);
+ *           z: fp32 [count][S][S][3] standard-normal draws of the caller.
+ * fp32 arithmetic without fused multiply-adds, no atomics: aug_pair_u8 is bit-exact with augment_pairs_host in data.py,
+ * aug_synth_u8 with augment_synth_host up to the rounding of powf.  Frame indices and crop origins are clamped into the store,
+ * so a corrupt plan row gives wrong pixels and never a read outside the pool.  A NULL pointer other than the optional two,
+ * N < 1, S < 1, first < 0 or count < 0 return LLIE_ERR_ARG; count == 0 launches nothing. */
+enum { LLIE_AUG_HFLIP = 1, LLIE_AUG_VFLIP = 2, LLIE_AUG_ROTATE = 4 };
+typedef struct llie_aug_row {
+  int32_t low_frame, high_frame; /* frame indices */
+  int32_t y0, x0;                /* crop origin */
+  int32_t flags;                 /* LLIE_AUG_* */
+  float ca, sa;                  /* cos, sin of the rotation angle */
+  float gamma, level;            /* synthetic: exponent, noise standard deviation */
+  float scale[3];                /* synthetic: per-channel colour shift, (1, 1, 1) = none */
+} llie_aug_row;
+int llie_aug_pair_u8(const uint8_t* pool, const int64_t* table, int N, const llie_aug_row* plan, int first, int count, int S,
+                     float* low, float* high, uint8_t* low_u8, uint8_t* high_u8, llie_stream stream);
+int llie_aug_synth_u8(const uint8_t* pool, const int64_t* table, int N, const llie_aug_row* plan, int first, int count, int S,
+                      const float* z, float* low, float* high, uint8_t* low_u8, uint8_t* high_u8, llie_stream stream);
+
 /* ---- Kernel-level entry points (unit tests and tuning; SURVEY.md 8b "per-kernel entry points").
  * Activations are NHWC rows in the compute dtype T (llie_dtype); see DESIGN.md section 3.
  *
