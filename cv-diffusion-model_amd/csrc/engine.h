@@ -249,6 +249,7 @@ namespace llie {
 // The reasons behind each default are in tune.cpp: knob_defaults.
 struct Knobs {
   int use_irbx;       // "irbx": recompute form of the inverted-residual block (irbx.hip) wherever irbx_supported()
+  int irbx_project;   // "irbx_project": identity-residual recompute blocks without h2 (expand_pool + expand_dw_project); 0 = expand_dw + project GEMM
   int gram;           // "gram": norm2 statistics of the recompute form from the Gram matrix (gram.hip); 0 = expand_stats; 2 = at every size
   int nt_min_mb;      // "nt_min_mb": tensors of at least this many MiB are stored non-temporally by the producers in nt_mask
   int nt_mask;        // "nt_mask": 1 expand_dw, 2 pw_expand, 4 dwconv3x3, 8 project / attention GEMMs, 16 dense 3x3 convs

@@ -192,14 +192,22 @@ struct Run : Exec {
     }
     // K2: depthwise with affine + ReLU6 prologue and SE pool partials
     const int dnt = fusedx ? irbx_pool_tiles(H, W) : dwconv_ntiles(H, W);
-    const size_t h2 = ar->alloc((size_t)M * w.hid * es());
+    // Identity-residual recompute blocks go without h2 too: the SE pool totals come from a pass that only rebuilds h1
+    // (expand_pool), and once the gate is known expand_dw_project multiplies the depthwise result by Wp itself.  A rule on the
+    // layer alone -- never on the batch or the grid, which would break batch invariance.
+    const bool fusedp = fusedx && g_knobs.irbx_project && !w.skip && !x1 && w.cout == w.cout_r && w.hid % 128 == 0 &&
+                        irbx_project_supported(dt, w.cin, w.hid, w.cout, H, W);
+    const size_t h2 = fusedp ? 0 : ar->alloc((size_t)M * w.hid * es());
     // SE pool: inference adds fixed-point channel totals into the zeroed region (one gate kernel follows); training keeps
     // the slab of tile partials (the backward pass and the 3-launch SE path read it)
     const bool fixtot = !tape && w.hid % 128 == 0;
     const size_t pool = fixtot ? 0 : ar->alloc((size_t)B * dnt * w.hid * 4);
     const size_t ptot = fixtot ? ztake((size_t)B * w.hid * 8) : 0;
     if (!dry) {
-      if (fusedx) {
+      if (fusedp) {
+        xa.as2 = p<float>(as2); xa.ab2 = p<float>(ab2); xa.pool_tot = p<unsigned long long>(ptot);
+        timed(LLIE_K_DW, ((int64_t)M * w.cin + (int64_t)w.hid * w.cin) * (int64_t)es(), [&] { return launch_expand_pool(dt, xa, s); });
+      } else if (fusedx) {
         xa.as2 = p<float>(as2); xa.ab2 = p<float>(ab2); xa.out = p(h2);
         xa.pool = fixtot ? nullptr : p<float>(pool);
         xa.pool_tot = fixtot ? p<unsigned long long>(ptot) : nullptr;
@@ -214,10 +222,10 @@ struct Run : Exec {
         timed(LLIE_K_DW, 2LL * M * w.hid * (int64_t)es(), [&] { return launch_dwconv3x3(dt, d, s); });
       }
     }
-    rel(as1); rel(ab1);
+    if (!fusedp) { rel(as1); rel(ab1); }  // expand_dw_project applies both norms again
     if (!fusedx) rel(h1.off);
     if (gram) rel(gtot); else rel(h1.slab);
-    rel(as2); rel(ab2);
+    if (!fusedp) { rel(as2); rel(ab2); }
     // SE MLP
     // (wide blocks of the 2-byte inference engines: fc1's pre-activations accumulate as integers in the zero-initialised region)
     const bool sepre_ok = fixtot && dt != LLIE_F32 && g_knobs.se_mfma && w.hid >= 768 && w.hid % 256 == 0 && w.sq % 64 == 0 && w.sq <= 512;
@@ -243,8 +251,15 @@ struct Run : Exec {
     if (!fixtot) rel(pool);
     rel(sehid); rel(semean);
     // K3: project with SE gate prologue (+ skip conv as extra K segments, or identity residual)
-    Tens y = new_tens(w.cout, H, W, pw_gemm_ntiles(P), w.cout_r);
-    if (!dry) {
+    Tens y = new_tens(w.cout, H, W, fusedp ? irbx_project_tiles(H, W) : pw_gemm_ntiles(P), w.cout_r);
+    if (fusedp) {
+      if (!dry) {
+        xa.pool_tot = nullptr; xa.gate = p<float>(gate); xa.wp = wptr(w.w_proj); xa.y = p(y.off); xa.ystats = p<float>(y.slab);
+        timed(LLIE_K_DW, ((int64_t)M * (w.cin + w.cout) + (int64_t)w.hid * (w.cin + w.cout)) * (int64_t)es(),
+              [&] { return launch_expand_dw_project(dt, xa, s); });
+      }
+      rel(as1); rel(ab1); rel(as2); rel(ab2);
+    } else if (!dry) {
       GemmArgs g{};
       g.seg[0] = GemmSeg{p(h2), w.hid, p<float>(gate), nullptr, w.hid, ACT_NONE};
       g.nseg = 1;
@@ -262,7 +277,8 @@ struct Run : Exec {
       timed(LLIE_K_GEMM, ((int64_t)M * (g.K + w.cout + (w.skip ? 0 : w.cout)) + (int64_t)w.cout * g.K) * (int64_t)es(),
             [&] { return launch_pw_gemm(dt, g, s); });
     }
-    rel(h2); rel(gate);
+    if (!fusedp) rel(h2);
+    rel(gate);
     if (tape) {
       rec.w = (int)(&w - c->irbs.data());
       rec.x0 = x0; rec.cat = x1 != nullptr;

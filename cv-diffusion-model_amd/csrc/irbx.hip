@@ -63,8 +63,27 @@ __device__ __forceinline__ typename Elem<T>::vec_t activate8(typename Elem<T>::v
 //   32-channel blocks [w * NBW, (w + 1) * NBW) -- their weight slices stay in registers -- and multiplies them with all
 //   four 32-pixel blocks of the tile.  MFMA roles: A = pixels (rows), B = weights (columns): a lane holds 16 pixels of
 //   ONE channel, so the per-channel sums are plain register adds and no accumulator is ever stored.
-template <typename T, int KS, int NBW>
-__global__ void __launch_bounds__(256, 2) expand_stats_kernel(const IrbxArgs a, const int RP) {
+//
+// POOL: the same walk produces the SE pool totals of the block instead (expand_pool_kernel).  The depthwise conv is linear and
+// zero-padded, so sum_p dw(a)_c[p] = sum_tap w_c[tap] * S_tap with S_tap = the sum of a_c over the pixels the tap can reach:
+// the whole image minus one border row and / or column (plus the corner they share).  Nine sums of a = relu6(aff2(h1)) / 6
+// per channel -- everything, first / last row, first / last column, four corners -- replace h2: a is rounded to T where
+// expand_dw_kernel rounds the tile it parks in LDS, the weights are the 6 w in T it stages, so the two routes add the same numbers.
+// Two accumulator registers pack into one dword of T and one v_dot2 adds both to an fp32 sum; the column sums are v_dot2 with
+// a one-hot operand on the four registers that can hold a first / last column (W % 16 == 0: a 16-pixel group lies in one
+// image row, starts at a multiple of 16), the row sums a uniform branch that only the image's first and last row take.
+template <typename T> struct PackedOne;
+template <> struct PackedOne<half_t> { static constexpr uint32_t lo = 0x00003C00u, hi = 0x3C000000u; };
+template <> struct PackedOne<bf16_t> { static constexpr uint32_t lo = 0x00003F80u, hi = 0x3F800000u; };
+// c + a.lo * b.lo + a.hi * b.hi on packed dwords of T
+template <typename T> __device__ __forceinline__ float dot2_pk(uint32_t a, uint32_t b, float c) {
+  if constexpr (std::is_same<T, half_t>::value)
+    return __builtin_amdgcn_fdot2(*reinterpret_cast<const f16x2*>(&a), *reinterpret_cast<const f16x2*>(&b), c, false);
+  else return dot2_bf16(a, b, c);
+}
+
+template <typename T, int KS, int NBW, bool POOL>
+__device__ __forceinline__ void expand_scan(const IrbxArgs& a, const int RP) {
   constexpr int K = 16 * KS, XP = (K + 8) * 2;  // LDS pixel pitch in bytes: conflict-free ds_read_b128
   typedef typename Elem<T>::vec_t vec_t;
   __shared__ __align__(16) unsigned char sA[2][128 * XP];
@@ -89,6 +108,23 @@ __global__ void __launch_bounds__(256, 2) expand_stats_kernel(const IrbxArgs a, 
   float s1[NBW], s2[NBW];
 #pragma unroll
   for (int j = 0; j < NBW; ++j) s1[j] = s2[j] = 0.f;
+  // POOL: aff2 of this lane's channels (applied to acc = h1 / 6: shift / 6, clamp01), the border sums, and the position of the
+  // next 16-pixel group: (image row, group inside the row)
+  constexpr int NP = POOL ? NBW : 1;
+  float sc2[NP], sh2[NP], c0s[NP], cws[NP], r0s[NP], rhs[NP], kk[NP][4];
+  const int w16 = a.W / 16;
+  int grow = 0, gcol = 0;
+  if constexpr (POOL) {
+#pragma unroll
+    for (int j = 0; j < NBW; ++j) {
+      const int c = (wave * NBW + j) * 32 + n;
+      sc2[j] = a.as2[(size_t)b * a.Chid + c];
+      sh2[j] = a.ab2[(size_t)b * a.Chid + c] * kSixth;
+      c0s[j] = cws[j] = r0s[j] = rhs[j] = kk[j][0] = kk[j][1] = kk[j][2] = kk[j][3] = 0.f;
+    }
+    const int g0 = tile * (RP / 16);
+    grow = g0 / w16; gcol = g0 % w16;
+  }
 
   // cooperative load: vector v = tid + j*256 of a step -> pixel v / (2 KS), channel vector v % (2 KS)
   const int nsteps = RP / 128;
@@ -120,6 +156,18 @@ __global__ void __launch_bounds__(256, 2) expand_stats_kernel(const IrbxArgs a, 
       vec_t af[KS];
 #pragma unroll
       for (int s = 0; s < KS; ++s) af[s] = *reinterpret_cast<const vec_t*>(buf + (pb * 32 + n) * XP + (16 * s + 8 * h) * 2);
+      // POOL: the block's two 16-pixel groups (accumulator registers 0..7 and 8..15): which border classes they touch
+      uint32_t mc0[2] = {0u, 0u}, mcw[2] = {0u, 0u};  // one-hot operands: this lane's first-column / last-column pixel of the group
+      bool top[2] = {false, false}, bot[2] = {false, false};
+      if constexpr (POOL) {
+#pragma unroll
+        for (int gi = 0; gi < 2; ++gi) {
+          mc0[gi] = (gcol == 0 && h == 0) ? PackedOne<T>::lo : 0u;        // pixel offset 0 of the group: register 8 gi, lower half
+          mcw[gi] = (gcol == w16 - 1 && h == 1) ? PackedOne<T>::hi : 0u;  // pixel offset 15: register 8 gi + 7, upper half
+          top[gi] = grow == 0; bot[gi] = grow == a.H - 1;
+          if (++gcol == w16) { gcol = 0; ++grow; }
+        }
+      }
 #pragma unroll
       for (int j = 0; j < NBW; ++j) {
         f32x16 acc;
@@ -127,6 +175,33 @@ __global__ void __launch_bounds__(256, 2) expand_stats_kernel(const IrbxArgs a, 
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
         for (int s = 0; s < KS; ++s) acc = mfma16<T>(af[s], wf[j][s], acc);
+        if constexpr (POOL) {
+          constexpr uint32_t ones = PackedOne<T>::lo | PackedOne<T>::hi;
+          uint32_t pk[8];  // registers (2 i, 2 i + 1) = two neighbouring pixels
+#pragma unroll
+          for (int i = 0; i < 8; ++i) pk[i] = affine_clamp01_pack<T>(acc[2 * i], acc[2 * i + 1], sc2[j], sc2[j], sh2[j], sh2[j]);
+          float gs[2];
+#pragma unroll
+          for (int gi = 0; gi < 2; ++gi) {
+            gs[gi] = dot2_pk<T>(pk[4 * gi], ones, 0.f);
+#pragma unroll
+            for (int i = 1; i < 4; ++i) gs[gi] = dot2_pk<T>(pk[4 * gi + i], ones, gs[gi]);
+            c0s[j] = dot2_pk<T>(pk[4 * gi], mc0[gi], c0s[j]);
+            cws[j] = dot2_pk<T>(pk[4 * gi + 3], mcw[gi], cws[j]);
+            if (top[gi]) {
+              r0s[j] += gs[gi];
+              kk[j][0] = dot2_pk<T>(pk[4 * gi], mc0[gi], kk[j][0]);
+              kk[j][1] = dot2_pk<T>(pk[4 * gi + 3], mcw[gi], kk[j][1]);
+            }
+            if (bot[gi]) {
+              rhs[j] += gs[gi];
+              kk[j][2] = dot2_pk<T>(pk[4 * gi], mc0[gi], kk[j][2]);
+              kk[j][3] = dot2_pk<T>(pk[4 * gi + 3], mcw[gi], kk[j][3]);
+            }
+          }
+          s1[j] += gs[0] + gs[1];
+          continue;
+        }
         // packed fp32 (v_pk_add_f32 / v_pk_fma_f32: two values per instruction) -- this reduction, not the MFMAs, is what
         // the wave spends its issue slots on
         f32x2 t1 = {0.f, 0.f}, t2 = {0.f, 0.f};
@@ -143,6 +218,34 @@ __global__ void __launch_bounds__(256, 2) expand_stats_kernel(const IrbxArgs a, 
   }
   // lane halves hold different pixel rows of the same channel; every wave owns its channels outright
   const int ntiles = P / RP;
+  if constexpr (POOL) {
+#pragma unroll
+    for (int j = 0; j < NBW; ++j) {
+      float v[9] = {s1[j], r0s[j], rhs[j], c0s[j], cws[j], kk[j][0], kk[j][1], kk[j][2], kk[j][3]};
+#pragma unroll
+      for (int i = 0; i < 9; ++i) v[i] += __shfl_xor(v[i], 32, 64);
+      if (h == 0) {
+        const int c = (wave * NBW + j) * 32 + n;
+        float t = 0.f;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {  // tap (ky, kx) reads pixel p + (ky - 1, kx - 1): p itself must leave the far border out
+          const int ky = tap / 3, kx = tap % 3;
+          float st = v[0];
+          if (ky == 2) st -= v[1];
+          if (ky == 0) st -= v[2];
+          if (kx == 2) st -= v[3];
+          if (kx == 0) st -= v[4];
+          if (ky == 2 && kx == 2) st += v[5];
+          if (ky == 2 && kx == 0) st += v[6];
+          if (ky == 0 && kx == 2) st += v[7];
+          if (ky == 0 && kx == 0) st += v[8];
+          t = __builtin_fmaf((float)(T)(6.f * a.wd[tap * a.Chid + c]), st, t);
+        }
+        fixed_add(a.pool_tot + (size_t)b * a.Chid + c, t, kPoolFixScale);
+      }
+    }
+    return;
+  }
 #pragma unroll
   for (int j = 0; j < NBW; ++j) {
     s1[j] += __shfl_xor(s1[j], 32, 64);
@@ -153,6 +256,14 @@ __global__ void __launch_bounds__(256, 2) expand_stats_kernel(const IrbxArgs a, 
       a.stats[((size_t)(b * ntiles + tile) * 2 + 1) * a.Chid + c] = 36.f * s2[j];
     }
   }
+}
+template <typename T, int KS, int NBW>
+__global__ void __launch_bounds__(256, 2) expand_stats_kernel(const IrbxArgs a, const int RP) {
+  expand_scan<T, KS, NBW, false>(a, RP);
+}
+template <typename T, int KS, int NBW>
+__global__ void __launch_bounds__(256, 2) expand_pool_kernel(const IrbxArgs a, const int RP) {
+  expand_scan<T, KS, NBW, true>(a, RP);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -176,8 +287,16 @@ constexpr int kXStamps = 9;
 // The depthwise phase issues two taps per 16x16x32 MFMA (k = 2 taps x 16 channels): one ds_read_b128 data operand per MFMA,
 // 640 matrix-pipe cycles per 64-channel chunk and wave (one tap per 32x32x16 MFMA, round 2's form, took 1 152).
 // NTST = h2 leaves with non-temporal stores (IrbxArgs::nt).
-template <typename T, int KS, bool DBUF, bool STAMP = false, bool NTST = false>
-__global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_kernel(const IrbxArgs a, const int tiles_per_wg, const int chunks_per_wg) {
+//
+// PCO > 0 (expand_dw_project_kernel): the project GEMM of an identity-residual block as the tail, PCO = Cout = Cin.  h2 never
+// leaves the workgroup: a wave owns two output rows and ALL 64 channels of the chunk in the depthwise phase (instead of four
+// rows and 32 channels), so after the SE gate (fp32, on the accumulators) and the same permlane16 swap that used to feed the
+// h2 stores, a lane holds 8 consecutive channels of one pixel -- a B fragment of a 16x16x32 MFMA whose A fragment is 16 rows
+// of Wp.  y[32 pixels][PCO] accumulates in fp32 over the chunks (PCO / 2 registers); the tile's epilogue adds the raw x of
+// the centre pixels, rounds to T, stores y and leaves y's GroupNorm partials as the tile's slab entry.  No pool work here:
+// the gate is already known (expand_pool_kernel).
+template <typename T, int KS, bool DBUF, bool STAMP, bool NTST, int PCO>
+__device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tiles_per_wg, const int chunks_per_wg) {
   constexpr int K = 16 * KS;
   constexpr int XP = (K + 8) * 2;                        // sX pixel pitch in bytes (80 / 144 / 208 / 272: conflict-free ds_read_b128)
   // x halo tile staging: thread -> (pixel xq0, 16-byte channel vector xkv); pass j covers pixel xq0 + j * QSTEP.  The channel
@@ -203,6 +322,8 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
   constexpr bool PACC_LDS = KS <= 4;
   long long* pacc_lds = reinterpret_cast<long long*>(red + 2 * 256);
   long long pacc_reg[PACC_LDS ? 1 : KS];
+  float* gate_s = reinterpret_cast<float*>(red + 2 * 256);  // PCO: the image's SE gate [Chid] takes the pool totals' place
+  static_assert(PCO == 0 || (PACC_LDS && !DBUF && !STAMP && PCO == K), "project tail: identity blocks of the single-buffered kernel");
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = lane & 31, h = lane >> 5;
@@ -232,6 +353,8 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
     aff1[i] = a.as1[(size_t)b * K + i];      // already / 6 (GnFinalizeArgs::post_scale)
     aff1[K + i] = a.ab1[(size_t)b * K + i];
   }
+  if constexpr (PCO > 0)
+    for (int i = tid; i < a.Chid; i += 256) gate_s[i] = a.gate[(size_t)b * a.Chid + i];
   // pixels 180..191 of the last MFMA block do not exist: their operand rows stay zero
   for (int i = tid; i < (kXNPB * 32 - kXNPX) * (XP / 16); i += 256)
     *reinterpret_cast<u32x4*>(sX + kXNPX * XP + i * 16) = u32x4{0u, 0u, 0u, 0u};
@@ -301,10 +424,11 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
     }
   };
   stamp(-1);
-  const bool has_pool = a.pool != nullptr || a.pool_tot != nullptr;
+  const bool has_pool = PCO == 0 && (a.pool != nullptr || a.pool_tot != nullptr);
   int par = 0;  // sH / red buffer parity (DBUF)
   int pend_tile = -1, pend_chunk = 0, pend_par = 0;  // pool partial waiting for its cross-wave sum
-  if constexpr (PACC_LDS) {
+  if constexpr (PCO > 0) {
+  } else if constexpr (PACC_LDS) {
     if (tid < 64) {  // threads 0..63 own channel tid of every chunk (Chid / 64 = KS chunks at most); only they touch it
 #pragma unroll
       for (int q = 0; q < KS; ++q) pacc_lds[q * 64 + tid] = 0;
@@ -314,6 +438,15 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
     for (int q = 0; q < KS; ++q) pacc_reg[q] = 0;
   }
   auto flush_pool = [&]() {  // after a barrier that follows the depthwise phase which wrote red[pend_par]
+    if constexpr (PCO > 0) {
+      // y's statistics of the tile before: the four waves' (sum, sum of squares) [wave][2][PCO], added in wave order
+      if (pend_tile >= 0 && tid < 2 * PCO) {
+        const float t = (red[tid] + red[2 * PCO + tid]) + (red[4 * PCO + tid] + red[6 * PCO + tid]);
+        a.ystats[((size_t)b * ntiles_img + pend_tile) * 2 * PCO + tid] = t;
+      }
+      pend_tile = -1;
+      return;
+    }
     if (pend_tile >= 0 && tid < 64) {
       const float* r = red + pend_par * 256;  // wave (chb, pxg) = chb + 2 pxg left its 32 channel sums at [wave * 64 + channel]
       const int cbb = tid >> 5, ci = tid & 31;
@@ -370,6 +503,13 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
     if (!DBUF) flush_pool();
     stamp(4);
 
+    typedef float f32x4v __attribute__((ext_vector_type(4)));
+    constexpr int NCB = PCO > 0 ? PCO / 16 : 1;  // 16-row blocks of Wp
+    f32x4v yacc[2][NCB];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int cb = 0; cb < NCB; ++cb) yacc[r][cb] = f32x4v{0.f, 0.f, 0.f, 0.f};
     // (Unrolling this loop lets hipcc count the memory operations between a prefetch and its use -- vmcnt(5) instead of
     // vmcnt(2) for the weight slices -- but costs 11 spilled registers, and every spill reload waits vmcnt(0), i.e. for the
     // h2 stores in flight: 35.7 vs 34.7 ms per step.  The run-time loop stays.)
@@ -451,7 +591,86 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
       // the data operand is one ds_read_b128 per MFMA (lane = pixel, 8 channels), the weight operand this lane's weight
       // masked into its diagonal position (4 v_and per step).  A few per cent of the MACs are useful, which still equals
       // the VALU's rate -- on a pipe that was idle, for a quarter of the VALU instructions.
-      {
+      if constexpr (PCO > 0) {
+        // ---- the same two-tap MFMAs with the wave's share turned: rows 2 wave, 2 wave + 1 of the tile x the chunk's four
+        // 16-channel tiles (20 steps of 2 MFMAs; operand reads and LDS addressing per instruction are those of the block below)
+        const int li = lane & 15, g = lane >> 4;
+        uint32_t amask[4];
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+          amask[d] = (((li & 7) >> 1) == d && (g >> 1) == (li >> 3)) ? ((li & 1) ? 0xFFFF0000u : 0x0000FFFFu) : 0u;
+        const uint32_t* wpair = reinterpret_cast<const uint32_t*>(wds) + chunk * 64 + li;  // + (pair * Chid + 16 c)
+        const uint32_t wsel = (g & 1) ? 0x03020302u : 0x01000100u;
+        const int choff = 8 * (g >> 1) + 16 * (g & 1);  // the lane's 8 channels of a 32-channel half after the swap below
+        // Wp fragments of this chunk: rows 16 cb + li, k = the lane's 8 channels of half kb -- in flight under the depthwise steps
+        vec_t wpf[NCB][2];
+        const T* wp = reinterpret_cast<const T*>(a.wp) + (size_t)li * a.Chid + chunk * 64 + choff;
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+          for (int kb = 0; kb < 2; ++kb) wpf[cb][kb] = ld_vec<T>(wp + (size_t)cb * 16 * a.Chid + 32 * kb);
+        f32x4v dacc[4][2];
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+          for (int r = 0; r < 2; ++r) dacc[c][r] = f32x4v{0.f, 0.f, 0.f, 0.f};
+        const unsigned char* bbase = buf + ((2 * wave) * kXH_W + li) * SHP + (g >> 1) * 16;
+        const bool upper = (g & 1) != 0;
+        vec_t bf[2][2];
+        uint32_t wq[2];
+        auto ld_step = [&](int step, vec_t (&bb)[2], uint32_t& w2) {  // step = 4 * pair + c
+          const int pr = step >> 2, c = step & 3;
+          const int ta = 2 * pr, tb = 2 * pr + 1 < 9 ? 2 * pr + 1 : 8;
+          const int offa = (ta / 3) * kXH_W + ta % 3, offb = (tb / 3) * kXH_W + tb % 3;
+          const unsigned char* p0 = bbase + (upper ? offb : offa) * SHP + c * 32;
+#pragma unroll
+          for (int r = 0; r < 2; ++r) bb[r] = *reinterpret_cast<const vec_t*>(p0 + r * kXH_W * SHP);
+          w2 = wpair[pr * a.Chid + 16 * c];
+        };
+        ld_step(0, bf[0], wq[0]);
+#pragma unroll
+        for (int step = 0; step < 20; ++step) {
+          if (step + 1 < 20) ld_step(step + 1, bf[(step + 1) & 1], wq[(step + 1) & 1]);
+          __builtin_amdgcn_sched_barrier(0);  // keep the look-ahead reads above this step's MFMAs
+          const int c = step & 3;
+          const uint32_t wdup = __builtin_amdgcn_perm(wq[step & 1], wq[step & 1], wsel);
+          u32x4 t;
+#pragma unroll
+          for (int d = 0; d < 4; ++d) t[d] = wdup & amask[d];
+          const vec_t af = reinterpret_cast<const vec_t&>(t);
+#pragma unroll
+          for (int r = 0; r < 2; ++r) dacc[c][r] = mfma16x16<T>(af, bf[step & 1][r], dacc[c][r]);
+        }
+        // SE gate on the fp32 accumulators (lane: channels 16 c + 4 g + e), one rounding to T, then y += Wp . (gate * h2)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const f32x4 gt = *reinterpret_cast<const f32x4*>(gate_s + chunk * 64 + 16 * c + 4 * g);
+#pragma unroll
+          for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dacc[c][r][e] *= gt[e];
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+          for (int kb = 0; kb < 2; ++kb) {
+            uint32_t p0[2], p1[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+              typedef T t2 __attribute__((ext_vector_type(2)));
+              t2 o0, o1;
+              o0[0] = (T)dacc[2 * kb][r][2 * j]; o0[1] = (T)dacc[2 * kb][r][2 * j + 1];
+              o1[0] = (T)dacc[2 * kb + 1][r][2 * j]; o1[1] = (T)dacc[2 * kb + 1][r][2 * j + 1];
+              p0[j] = *reinterpret_cast<uint32_t*>(&o0);
+              p1[j] = *reinterpret_cast<uint32_t*>(&o1);
+            }
+            const u32x2 s0 = __builtin_amdgcn_permlane16_swap(p0[0], p1[0], false, false);
+            const u32x2 s1 = __builtin_amdgcn_permlane16_swap(p0[1], p1[1], false, false);
+            const u32x4 v = {s0[0], s1[0], s0[1], s1[1]};  // channels 32 kb + choff .. + 7 of pixel li
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) yacc[r][cb] = mfma16x16<T>(wpf[cb][kb], reinterpret_cast<const vec_t&>(v), yacc[r][cb]);
+          }
+      } else {
         // ---- two taps per MFMA: D[16 ch][16 px] += A[16 ch][k] B[k][16 px], k = 16 t + c (tap slot t, channel c of the
         // 16-channel tile), in this order of k: lane (li = lane & 15, g = lane >> 4) holds k-slice g = tap slot g & 1, channels 8 (g >> 1) + j.
         //   B: lane = output pixel li of one tile row; its 8 channels of the halo pixel under tap slot g & 1: ONE ds_read_b128,
@@ -463,7 +682,6 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
         // pixels; equal addresses broadcast): conflict-free, 4 instead of 8 LDS cycles for each of the 40 reads.)
         // A wave owns 32 channels (2 tiles) x its 4 output rows (4 pixel tiles): 8 accumulator tiles of 4 registers,
         // 5 tap pairs (the last one half empty) = 40 MFMAs of 16 cycles.
-        typedef float f32x4v __attribute__((ext_vector_type(4)));
         const int li = lane & 15, g = lane >> 4;
         uint32_t amask[4];
 #pragma unroll
@@ -560,6 +778,67 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
       if (DBUF) par ^= 1;
       stamp(8);
     }
+    if constexpr (PCO > 0) {
+      // ---- y = round(acc + x) for the wave's 2 rows x 16 pixels: lane (pixel li, g) holds rows 16 cb + 4 g + e of every block cb
+      const int li = lane & 15, g = lane >> 4;
+      const int choff = 8 * (g >> 1) + 16 * (g & 1);
+      T* yout = reinterpret_cast<T*>(a.y) + (size_t)b * P * PCO;
+      float st[2][NCB * 4];  // (sum, sum of squares) of the rounded outputs, this lane's 2 pixels
+#pragma unroll
+      for (int i = 0; i < NCB * 4; ++i) st[0][i] = st[1][i] = 0.f;
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const size_t pix = (size_t)(y0 + 2 * wave + r) * a.W + x0p + li;
+        uint32_t pk[NCB][2];
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb) {
+          typedef T t4 __attribute__((ext_vector_type(4)));
+          typedef T t2 __attribute__((ext_vector_type(2)));
+          const t4 res = *reinterpret_cast<const t4*>(x0 + pix * PCO + 16 * cb + 4 * g);  // the tile's own loads left it in L2
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            t2 o;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+              o[e] = (T)(yacc[r][cb][2 * j + e] + (float)res[2 * j + e]);
+              const float q = (float)o[e];
+              st[0][4 * cb + 2 * j + e] += q;
+              st[1][4 * cb + 2 * j + e] = __builtin_fmaf(q, q, st[1][4 * cb + 2 * j + e]);
+            }
+            pk[cb][j] = *reinterpret_cast<uint32_t*>(&o);
+          }
+        }
+#pragma unroll
+        for (int pp = 0; pp < NCB / 2; ++pp) {
+          const u32x2 s0 = __builtin_amdgcn_permlane16_swap(pk[2 * pp][0], pk[2 * pp + 1][0], false, false);
+          const u32x2 s1 = __builtin_amdgcn_permlane16_swap(pk[2 * pp][1], pk[2 * pp + 1][1], false, false);
+          *reinterpret_cast<u32x4*>(yout + pix * PCO + 32 * pp + choff) = u32x4{s0[0], s1[0], s0[1], s1[1]};
+        }
+      }
+      // sums over the 16 pixel lanes of a row by DPP (as the pool partial of the plain kernel), eight values at a time
+#pragma unroll
+      for (int w8 = 0; w8 < NCB; ++w8) {
+        float* v = &st[w8 & 1][(w8 >> 1) * 8];
+#define LLIE_DPP_STEP(ROR)                                                                                               \
+  _Pragma("unroll") for (int i = 0; i < 8; ++i)                                                                          \
+      asm volatile("v_add_f32_dpp %0, %0, %0 row_ror:" #ROR " row_mask:0xf bank_mask:0xf" : "+v"(v[i]));
+        asm volatile("s_nop 1" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
+        LLIE_DPP_STEP(8)
+        LLIE_DPP_STEP(4)
+        LLIE_DPP_STEP(2)
+        LLIE_DPP_STEP(1)
+#undef LLIE_DPP_STEP
+      }
+      if (li == 0) {  // red[wave][which][channel 16 cb + 4 g + e]
+#pragma unroll
+        for (int which = 0; which < 2; ++which)
+#pragma unroll
+          for (int cb = 0; cb < NCB; ++cb)
+            *reinterpret_cast<f32x4*>(red + (wave * 2 + which) * PCO + 16 * cb + 4 * g) =
+                f32x4{st[which][4 * cb], st[which][4 * cb + 1], st[which][4 * cb + 2], st[which][4 * cb + 3]};
+      }
+      pend_tile = tile;
+    }
     ty = tyn; tx = txn;
   }
   if constexpr (STAMP) {
@@ -568,6 +847,10 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
 #pragma unroll
       for (int i = 0; i < kXStamps; ++i) a.dbg[(wg * 4 + wave) * kXStamps + i] = tk[i];
     }
+  }
+  if constexpr (PCO > 0) {
+    wg_barrier();
+    flush_pool();
   }
   if (has_pool) {
     wg_barrier();
@@ -580,6 +863,16 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
   }
 }
 
+template <typename T, int KS, bool DBUF, bool STAMP = false, bool NTST = false>
+__global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_kernel(const IrbxArgs a, const int tiles_per_wg, const int chunks_per_wg) {
+  expand_dw_body<T, KS, DBUF, STAMP, NTST, 0>(a, tiles_per_wg, chunks_per_wg);
+}
+// two workgroups per CU: the y accumulators and the Wp fragments do not fit the 168 registers of three
+template <typename T, int KS>
+__global__ void __launch_bounds__(256, 2) expand_dw_project_kernel(const IrbxArgs a, const int tiles_per_wg) {
+  expand_dw_body<T, KS, false, false, false, 16 * KS>(a, tiles_per_wg, KS);
+}
+
 // ---------------------------------------------------------------------------------------------
 int irbx_stats_rows(int P);
 bool irbx_supported(int dtype, int Cin, int c0, int Chid, int H, int W) {
@@ -589,6 +882,11 @@ bool irbx_supported(int dtype, int Cin, int c0, int Chid, int H, int W) {
   return W % kXT_W == 0 && H % kXT_H == 0 && (H * W) % irbx_stats_rows(H * W) == 0;
 }
 int irbx_pool_tiles(int H, int W) { return (H / kXT_H) * (W / kXT_W); }
+// the project tail: identity-residual blocks of the 32- and 64-channel levels (a rule on the layer alone, never on the batch)
+bool irbx_project_supported(int dtype, int Cin, int Chid, int Cout, int H, int W) {
+  return (Cin == 32 || Cin == 64) && Cout == Cin && irbx_supported(dtype, Cin, Cin, Chid, H, W);
+}
+int irbx_project_tiles(int H, int W) { return irbx_pool_tiles(H, W); }  // slab entries of y per image: one per 8 x 16 tile
 // pixels per statistics partial: fixed per image size (never a function of the batch: bitwise batch invariance)
 int irbx_stats_rows(int P) {
   int rp = 128;  // a power of two in [128, 1024], about P / 64
@@ -642,6 +940,31 @@ hipError_t launch_expand_stats(int dtype, const IrbxArgs& a, hipStream_t s) {
   if (!irbx_supported(dtype, a.c0 + a.c1, a.c0, a.Chid, a.H, a.W) || (a.c1 && !a.x1) || !a.stats) return hipErrorInvalidValue;
   if (a.Chid != 4 * (a.c0 + a.c1)) return hipErrorInvalidValue;
   return dtype == 1 ? launch_stats_t<half_t>(a, s) : launch_stats_t<bf16_t>(a, s);
+}
+
+template <typename T, int KS, int NBW>
+static hipError_t launch_pool_cfg(const IrbxArgs& a, hipStream_t s) {
+  const int P = a.H * a.W, RP = irbx_stats_rows(P);
+  static const std::string name = std::string("expand_pool_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) + ", " +
+                                  std::to_string(NBW) + ">";
+  note_kernel(name.c_str());
+  hipLaunchKernelGGL((expand_pool_kernel<T, KS, NBW>), dim3(P / RP, 1, a.B), dim3(256), 0, s, a, RP);
+  return hipGetLastError();
+}
+template <typename T>
+static hipError_t launch_pool_t(const IrbxArgs& a, hipStream_t s) {
+  switch (a.c0 + a.c1) {
+    case 32: return launch_pool_cfg<T, 2, 1>(a, s);
+    case 64: return launch_pool_cfg<T, 4, 2>(a, s);
+    case 96: return launch_pool_cfg<T, 6, 3>(a, s);
+  }
+  return hipErrorInvalidValue;
+}
+// pool_tot += the image's SE pool totals (fixed point, kPoolFixScale); the caller zeroes it
+hipError_t launch_expand_pool(int dtype, const IrbxArgs& a, hipStream_t s) {
+  if (!irbx_supported(dtype, a.c0 + a.c1, a.c0, a.Chid, a.H, a.W) || (a.c1 && !a.x1) || !a.pool_tot || !a.as2 || !a.ab2 || !a.wd)
+    return hipErrorInvalidValue;
+  return dtype == 1 ? launch_pool_t<half_t>(a, s) : launch_pool_t<bf16_t>(a, s);
 }
 
 constexpr int kXTilesPerWg = 4;  // longest run of tiles along x one workgroup takes
@@ -713,6 +1036,31 @@ static hipError_t launch_dw_t(const IrbxArgs& a, hipStream_t s) {
     }
   }
   return hipErrorInvalidValue;
+}
+template <typename T, int KS>
+static hipError_t launch_project_cfg(const IrbxArgs& a, hipStream_t s) {
+  const size_t lds = (size_t)kXNPB * 32 * SHP + (size_t)kXNPB * 32 * (16 * KS + 8) * 2 + (size_t)10 * a.Chid * 2 + (size_t)2 * a.Chid * 4 +
+                     (size_t)2 * 16 * KS * 4 + 2 * 256 * 4 + (size_t)KS * 64 * 8;
+  const int ntiles = irbx_pool_tiles(a.H, a.W);
+  int tpw = kXTilesPerWg;  // as launch_dw_cfg; every workgroup takes all channel chunks (y accumulates over them)
+  while (tpw > 1 && ((a.W / kXT_W) % tpw || (long)(ntiles / tpw) * a.B < 2048)) tpw >>= 1;
+  static const std::string name = std::string("expand_dw_project_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) + ">";
+  note_kernel(name.c_str());
+  static std::atomic<uint64_t> attr_done{0};
+  if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&expand_dw_project_kernel<T, KS>), 128 * 1024, attr_done); e != hipSuccess) return e;
+  hipLaunchKernelGGL((expand_dw_project_kernel<T, KS>), dim3(ntiles / tpw, 1, a.B), dim3(256), lds, s, a, tpw);
+  return hipGetLastError();
+}
+template <typename T>
+static hipError_t launch_project_t(const IrbxArgs& a, hipStream_t s) {
+  return a.c0 == 32 ? launch_project_cfg<T, 2>(a, s) : launch_project_cfg<T, 4>(a, s);
+}
+// y = Wp . (gate * dw3x3(relu6(aff2(W1 . relu6(aff1(x)))))) + x with y's statistics slab [B][irbx_project_tiles][2][Cout]; Cout = Cin = c0
+hipError_t launch_expand_dw_project(int dtype, const IrbxArgs& a, hipStream_t s) {
+  if (a.c1 || a.x1 || !irbx_project_supported(dtype, a.c0, a.Chid, a.c0, a.H, a.W) || !a.gate || !a.wp || !a.y || !a.ystats || !a.as2 || !a.ab2 ||
+      !a.wd)
+    return hipErrorInvalidValue;
+  return dtype == 1 ? launch_project_t<half_t>(a, s) : launch_project_t<bf16_t>(a, s);
 }
 hipError_t launch_expand_dw(int dtype, const IrbxArgs& a, hipStream_t s) {
   if (!irbx_supported(dtype, a.c0 + a.c1, a.c0, a.Chid, a.H, a.W) || (a.c1 && !a.x1) || !a.out) return hipErrorInvalidValue;

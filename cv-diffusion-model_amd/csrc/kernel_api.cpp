@@ -482,6 +482,45 @@ int llie_rw_probe(const void* src, void* dst, int64_t units, int reads, int writ
   return kerr("rw_probe", launch_rw_probe(src, dst, units, reads, writes, nontemporal, hs(stream)), LLIE_ERR_ARG, nullptr);
 }
 
+// ---- recompute form of the inverted-residual block (irbx.hip), kernel by kernel
+static IrbxArgs irbx_args(const void* x0, int c0, const void* x1, int c1, const float* scale1, const float* shift1, const void* w_expand,
+                          const float* scale2, const float* shift2, const float* w_dw, int batch, int H, int W) {
+  IrbxArgs a{};
+  a.x0 = x0; a.c0 = c0; a.x1 = x1; a.c1 = c1; a.as1 = scale1; a.ab1 = shift1; a.w1 = w_expand; a.as2 = scale2; a.ab2 = shift2; a.wd = w_dw;
+  a.B = batch; a.H = H; a.W = W; a.Chid = 4 * (c0 + c1);
+  return a;
+}
+static const char* kIrbxShapes = "2-byte dtype, c0 + c1 in {32, 64, 96}, c0 % 16 == 0, H % 8 == 0, W % 16 == 0";
+int llie_expand_dw(int dtype, const void* x0, int c0, const void* x1, int c1, const float* scale1, const float* shift1, const void* w_expand,
+                   const float* scale2, const float* shift2, const float* w_dw, void* h2, unsigned long long* pool_totals, int batch, int H, int W,
+                   llie_stream stream) {
+  if (!x0 || !scale1 || !shift1 || !w_expand || !scale2 || !shift2 || !w_dw || !h2 || batch <= 0 || c0 <= 0 || c1 < 0 || (c1 > 0) != (x1 != nullptr))
+    return LLIE_ERR_ARG;
+  IrbxArgs a = irbx_args(x0, c0, x1, c1, scale1, shift1, w_expand, scale2, shift2, w_dw, batch, H, W);
+  a.out = h2; a.pool_tot = pool_totals;
+  return kerr("expand_dw", launch_expand_dw(dtype, a, hs(stream)), LLIE_ERR_SHAPE, kIrbxShapes);
+}
+int llie_expand_pool(int dtype, const void* x0, int c0, const void* x1, int c1, const float* scale1, const float* shift1, const void* w_expand,
+                     const float* scale2, const float* shift2, const float* w_dw, unsigned long long* pool_totals, int batch, int H, int W,
+                     llie_stream stream) {
+  if (!x0 || !scale1 || !shift1 || !w_expand || !scale2 || !shift2 || !w_dw || !pool_totals || batch <= 0 || c0 <= 0 || c1 < 0 ||
+      (c1 > 0) != (x1 != nullptr))
+    return LLIE_ERR_ARG;
+  IrbxArgs a = irbx_args(x0, c0, x1, c1, scale1, shift1, w_expand, scale2, shift2, w_dw, batch, H, W);
+  a.pool_tot = pool_totals;
+  return kerr("expand_pool", launch_expand_pool(dtype, a, hs(stream)), LLIE_ERR_SHAPE, kIrbxShapes);
+}
+int llie_expand_dw_project(int dtype, const void* x, int C, const float* scale1, const float* shift1, const void* w_expand, const float* scale2,
+                           const float* shift2, const float* w_dw, const float* gate, const void* w_project, void* y, float* stats, int batch,
+                           int H, int W, llie_stream stream) {
+  if (!x || !scale1 || !shift1 || !w_expand || !scale2 || !shift2 || !w_dw || !gate || !w_project || !y || !stats || batch <= 0 || C <= 0)
+    return LLIE_ERR_ARG;
+  IrbxArgs a = irbx_args(x, C, nullptr, 0, scale1, shift1, w_expand, scale2, shift2, w_dw, batch, H, W);
+  a.gate = gate; a.wp = w_project; a.y = y; a.ystats = stats;
+  return kerr("expand_dw_project", launch_expand_dw_project(dtype, a, hs(stream)), LLIE_ERR_SHAPE, "2-byte dtype, C in {32, 64}, H % 8 == 0, W % 16 == 0");
+}
+int llie_irbx_project_tiles(int H, int W) { return H > 0 && W > 0 && H % 8 == 0 && W % 16 == 0 ? irbx_project_tiles(H, W) : LLIE_ERR_ARG; }
+
 int llie_dwconv3x3_tiles(int H, int W) { return dwconv_ntiles(H, W); }
 int llie_pw_gemm_tile_rows(int P) { return pw_gemm_tile_rows(P); }
 }  // extern "C"

@@ -471,6 +471,30 @@ int llie_gram_finalize(int dtype, const float* gram_totals, const void* w_expand
 int llie_dwconv3x3(int dtype, const void* in, void* out, const float* scale, const float* bias, const float* w9c,
                    float* pool, int B, int H, int W, int C, llie_stream stream);
 int llie_dwconv3x3_tiles(int H, int W);
+/* The recompute form of InvertedResidualBlock (efficient_unet.py:203-236; irbx.hip), kernel by kernel.  x0 / x1: the block input,
+ * NHWC [batch][H][W][c0 / c1] of a 2-byte compute type (x1 NULL with c1 = 0), Cin = c0 + c1 in {32, 64, 96}, c0 % 16 == 0,
+ * H % 8 == 0, W % 16 == 0, Chid = 4 Cin.  scale1 / shift1 [batch][Cin]: norm1's affine DIVIDED BY 6 (a' = clamp01(x scale1 + shift1)
+ * = relu6(norm1 x) / 6, rounded to the compute type); w_expand [Chid][Cin] of the compute type; scale2 / shift2 [batch][Chid]:
+ * norm2 + FiLM, undivided: a = relu6(scale2 h1 + shift2) with h1 = 6 w_expand a'; w_dw fp32 [9][Chid] tap-major.
+ * expand_dw: h2 = depthwise3x3(a) [batch][H][W][Chid]; pool_totals (or NULL): uint64 [batch][Chid], += round(2^24 partial sums
+ *   of h2 per channel) (integer adds: independent of order); the caller zeroes it.
+ * expand_pool: the same totals without h2: the conv is linear and zero-padded, so a channel's sum of h2 follows from nine sums of a
+ *   (all pixels, first / last row, first / last column, four corners) -- one pass that only rebuilds h1.
+ * expand_dw_project (identity-residual blocks, Cout = Cin = C in {32, 64}, one input segment): y = w_project (gate * h2) + x with the
+ *   SE gate [batch][Chid] given, w_project [C][Chid] of the compute type; h2 never leaves the workgroup.  stats: fp32 slab
+ *   [batch][irbx_project_tiles(H, W)][2][C] of y's per-channel (sum, sum of squares), one entry per 8 x 16 tile.
+ * The engine takes the last two for the blocks irbx_project_supported names unless the knob "irbx_project" [1] is 0 (then
+ * expand_dw and the project GEMM, as for every other recompute block; tests and A/B measurements). */
+int llie_expand_dw(int dtype, const void* x0, int c0, const void* x1, int c1, const float* scale1, const float* shift1, const void* w_expand,
+                   const float* scale2, const float* shift2, const float* w_dw, void* h2, unsigned long long* pool_totals, int batch, int H, int W,
+                   llie_stream stream);
+int llie_expand_pool(int dtype, const void* x0, int c0, const void* x1, int c1, const float* scale1, const float* shift1, const void* w_expand,
+                     const float* scale2, const float* shift2, const float* w_dw, unsigned long long* pool_totals, int batch, int H, int W,
+                     llie_stream stream);
+int llie_expand_dw_project(int dtype, const void* x, int C, const float* scale1, const float* shift1, const void* w_expand, const float* scale2,
+                           const float* shift2, const float* w_dw, const float* gate, const void* w_project, void* y, float* stats, int batch,
+                           int H, int W, llie_stream stream);
+int llie_irbx_project_tiles(int H, int W);
 /* dst[0:bytes] = src[0:bytes] with 16-byte lane accesses: the on-box HBM copy-bandwidth probe behind bench.py's
  * `peak_measured` ("a copy-kernel bandwidth probe"; 2 x bytes move per call). */
 int llie_copy_probe(const void* src, void* dst, int64_t bytes, llie_stream stream);
