@@ -35,7 +35,7 @@ EXPORTS = [
     "llie_final_bwd_data",
     "llie_tile_count", "llie_tile_origins", "llie_tile_gather_u8", "llie_tile_gather_f32", "llie_tile_blend_u8",
     "llie_aug_pair_u8", "llie_aug_synth_u8",
-    "llie_expand_dw", "llie_expand_pool", "llie_expand_dw_project", "llie_irbx_project_tiles",
+    "llie_expand_dw", "llie_expand_pool", "llie_expand_dw_project", "llie_expand_dw_project_skip", "llie_irbx_project_tiles",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 
@@ -177,6 +177,7 @@ def lib() -> C.CDLL:
     L.llie_expand_dw.argtypes = [ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     L.llie_expand_pool.argtypes = [ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     L.llie_expand_dw_project.argtypes = [ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]
+    L.llie_expand_dw_project_skip.argtypes = [ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, ci, ci, ci, vp]
     L.llie_irbx_project_tiles.argtypes = [ci, ci]
     L.llie_tune.argtypes = [C.c_char_p, ci]
     L.llie_debug_irbx_stamps.argtypes = [C.POINTER(C.c_double)]

@@ -249,7 +249,8 @@ namespace llie {
 // The reasons behind each default are in tune.cpp: knob_defaults.
 struct Knobs {
   int use_irbx;       // "irbx": recompute form of the inverted-residual block (irbx.hip) wherever irbx_supported()
-  int irbx_project;   // "irbx_project": identity-residual recompute blocks without h2 (expand_pool + expand_dw_project); 0 = expand_dw + project GEMM
+  int irbx_project;   // "irbx_project": recompute blocks without h2 (expand_pool + expand_dw_project): 1 = every shape irbx_project_supported
+                      // names, 2 = its identity-residual shapes only, 0 = none (expand_dw + project GEMM)
   int gram;           // "gram": norm2 statistics of the recompute form from the Gram matrix (gram.hip); 0 = expand_stats; 2 = at every size
   int nt_min_mb;      // "nt_min_mb": tensors of at least this many MiB are stored non-temporally by the producers in nt_mask
   int nt_mask;        // "nt_mask": 1 expand_dw, 2 pw_expand, 4 dwconv3x3, 8 project / attention GEMMs, 16 dense 3x3 convs
@@ -259,6 +260,16 @@ struct Knobs {
   int epoch;          // llie_tune calls so far: keys the graph cache and the zero-region sizes, which bake kernel choices in
 };
 extern Knobs g_knobs;
+
+// Which form of the project tail (kernels.h: kIrbxProject*) the inference engine runs a block in, 0 = expand_dw + project GEMM (or
+// no recompute form at all).  c0 = channels of the block's first input segment (= w.cin without a virtual concat).  A rule on
+// the layer and the knobs alone -- never on the batch or the grid, which would break batch invariance; the byte model
+// (llie_path_bytes) asks the same function.
+inline int irb_project_form(int dt, const IrbW& w, int c0, int H, int W) {
+  if (!g_knobs.use_irbx || !g_knobs.irbx_project || w.hid != w.hid_r || w.cin != w.cin_r || w.cout != w.cout_r || w.hid % 128) return 0;
+  const int form = llie::irbx_project_supported(dt, w.cin, c0, w.hid, w.cout, w.skip, H, W);
+  return form == llie::kIrbxProjectSkip && g_knobs.irbx_project == 2 ? 0 : form;
+}
 
 // ---------------------------------------------------------------------------------------------
 // What the forward (forward.cpp: Run) and the backward pass (backward.cpp: Back) share: context, arena, stream, workspace.

@@ -192,11 +192,11 @@ struct Run : Exec {
     }
     // K2: depthwise with affine + ReLU6 prologue and SE pool partials
     const int dnt = fusedx ? irbx_pool_tiles(H, W) : dwconv_ntiles(H, W);
-    // Identity-residual recompute blocks go without h2 too: the SE pool totals come from a pass that only rebuilds h1
-    // (expand_pool), and once the gate is known expand_dw_project multiplies the depthwise result by Wp itself.  A rule on the
-    // layer alone -- never on the batch or the grid, which would break batch invariance.
-    const bool fusedp = fusedx && g_knobs.irbx_project && !w.skip && !x1 && w.cout == w.cout_r && w.hid % 128 == 0 &&
-                        irbx_project_supported(dt, w.cin, w.hid, w.cout, H, W);
+    // Identity-residual recompute blocks and the 96 -> 32 skip-conv block go without h2 too: the SE pool totals come from a pass
+    // that only rebuilds h1 (expand_pool), and once the gate is known expand_dw_project multiplies the depthwise result by Wp
+    // itself and adds the shortcut.  A rule on the layer alone (irb_project_form) -- never on the batch or the grid, which would
+    // break batch invariance.
+    const bool fusedp = fusedx && irb_project_form(dt, w, x0.C, H, W) != 0;
     const size_t h2 = fusedp ? 0 : ar->alloc((size_t)M * w.hid * es());
     // SE pool: inference adds fixed-point channel totals into the zeroed region (one gate kernel follows); training keeps
     // the slab of tile partials (the backward pass and the 3-launch SE path read it)
@@ -255,8 +255,9 @@ struct Run : Exec {
     if (fusedp) {
       if (!dry) {
         xa.pool_tot = nullptr; xa.gate = p<float>(gate); xa.wp = wptr(w.w_proj); xa.y = p(y.off); xa.ystats = p<float>(y.slab);
+        xa.ldp = w.hid + (w.skip ? w.cin : 0);  // project and skip share one K-concatenated matrix (model.cpp)
         timed(LLIE_K_DW, ((int64_t)M * (w.cin + w.cout) + (int64_t)w.hid * (w.cin + w.cout)) * (int64_t)es(),
-              [&] { return launch_expand_dw_project(dt, xa, s); });
+              [&] { return launch_expand_dw_project(dt, xa, w.cout, w.skip, s); });
       }
       rel(as1); rel(ab1); rel(as2); rel(ab2);
     } else if (!dry) {

@@ -295,6 +295,10 @@ constexpr int kXStamps = 9;
 // of Wp.  y[32 pixels][PCO] accumulates in fp32 over the chunks (PCO / 2 registers); the tile's epilogue adds the raw x of
 // the centre pixels, rounds to T, stores y and leaves y's GroupNorm partials as the tile's slab entry.  No pool work here:
 // the gate is already known (expand_pool_kernel).
+// PCO != K (96 -> 32): the block has a skip conv instead of the identity shortcut, and its input may be a virtual concat.  Wp is
+// then the engine's K-concatenated matrix [PCO][Chid + K] (row stride IrbxArgs::ldp), project columns first: the chunk tail reads
+// the project columns as before, and the tile's epilogue runs K / 32 more k-steps y += Wskip . x on the raw centre pixels (no norm,
+// no activation: the skip segments of pw_gemm) in place of the residual add.
 template <typename T, int KS, bool DBUF, bool STAMP, bool NTST, int PCO>
 __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tiles_per_wg, const int chunks_per_wg) {
   constexpr int K = 16 * KS;
@@ -322,8 +326,12 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
   constexpr bool PACC_LDS = KS <= 4;
   long long* pacc_lds = reinterpret_cast<long long*>(red + 2 * 256);
   long long pacc_reg[PACC_LDS ? 1 : KS];
-  float* gate_s = reinterpret_cast<float*>(red + 2 * 256);  // PCO: the image's SE gate [Chid] takes the pool totals' place
-  static_assert(PCO == 0 || (PACC_LDS && !DBUF && !STAMP && PCO == K), "project tail: identity blocks of the single-buffered kernel");
+  constexpr bool PSKIP = PCO > 0 && PCO != K;  // skip conv in place of the identity shortcut
+  // PCO: the image's SE gate [Chid] takes the pool totals' place; the skip form (no LDS pool totals at KS = 6, and 768 B left of
+  // what two workgroups per CU allow) puts it behind the 4 x 2 x PCO floats of `red` the project form needs
+  float* gate_s = reinterpret_cast<float*>(red + (PSKIP ? 8 * PCO : 2 * 256));
+  static_assert(PCO == 0 || (!DBUF && !STAMP && (PCO == K ? PACC_LDS : PCO % 32 == 0 && PCO <= 64)),
+                "project tail: single-buffered kernel; identity blocks keep the gate in the pool totals' LDS");
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = lane & 31, h = lane >> 5;
@@ -604,11 +612,11 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
         const int choff = 8 * (g >> 1) + 16 * (g & 1);  // the lane's 8 channels of a 32-channel half after the swap below
         // Wp fragments of this chunk: rows 16 cb + li, k = the lane's 8 channels of half kb -- in flight under the depthwise steps
         vec_t wpf[NCB][2];
-        const T* wp = reinterpret_cast<const T*>(a.wp) + (size_t)li * a.Chid + chunk * 64 + choff;
+        const T* wp = reinterpret_cast<const T*>(a.wp) + (size_t)li * a.ldp + chunk * 64 + choff;
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
-          for (int kb = 0; kb < 2; ++kb) wpf[cb][kb] = ld_vec<T>(wp + (size_t)cb * 16 * a.Chid + 32 * kb);
+          for (int kb = 0; kb < 2; ++kb) wpf[cb][kb] = ld_vec<T>(wp + (size_t)cb * 16 * a.ldp + 32 * kb);
         f32x4v dacc[4][2];
 #pragma unroll
         for (int c = 0; c < 4; ++c)
@@ -783,6 +791,26 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
       const int li = lane & 15, g = lane >> 4;
       const int choff = 8 * (g >> 1) + 16 * (g & 1);
       T* yout = reinterpret_cast<T*>(a.y) + (size_t)b * P * PCO;
+      if constexpr (PSKIP) {
+        // y += Wskip . x: k-step ks covers input channels 32 ks .. 32 ks + 31, lane (li, g) holds channels 32 ks + 8 g .. + 7 of
+        // row 16 cb + li of Wskip (A) and of pixel li of the row (B); a 16-byte vector never straddles the segments (c0 % 16 == 0).
+        // The tile's own loads have left x in L2.
+        const T* wsk = reinterpret_cast<const T*>(a.wp) + (size_t)li * a.ldp + a.Chid + 8 * g;
+#pragma unroll
+        for (int ks = 0; ks < K / 32; ++ks) {
+          const int ch = 32 * ks + 8 * g;
+          vec_t wsf[NCB];
+#pragma unroll
+          for (int cb = 0; cb < NCB; ++cb) wsf[cb] = ld_vec<T>(wsk + (size_t)cb * 16 * a.ldp + 32 * ks);
+#pragma unroll
+          for (int r = 0; r < 2; ++r) {
+            const size_t pix = (size_t)(y0 + 2 * wave + r) * a.W + x0p + li;
+            const vec_t xv = ch < a.c0 ? ld_vec<T>(x0 + pix * a.c0 + ch) : ld_vec<T>(x1 + pix * a.c1 + (ch - a.c0));
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) yacc[r][cb] = mfma16x16<T>(wsf[cb], xv, yacc[r][cb]);
+          }
+        }
+      }
       float st[2][NCB * 4];  // (sum, sum of squares) of the rounded outputs, this lane's 2 pixels
 #pragma unroll
       for (int i = 0; i < NCB * 4; ++i) st[0][i] = st[1][i] = 0.f;
@@ -794,13 +822,14 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
         for (int cb = 0; cb < NCB; ++cb) {
           typedef T t4 __attribute__((ext_vector_type(4)));
           typedef T t2 __attribute__((ext_vector_type(2)));
-          const t4 res = *reinterpret_cast<const t4*>(x0 + pix * PCO + 16 * cb + 4 * g);  // the tile's own loads left it in L2
+          t4 res = t4{};
+          if constexpr (!PSKIP) res = *reinterpret_cast<const t4*>(x0 + pix * PCO + 16 * cb + 4 * g);  // the tile's own loads left it in L2
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
             t2 o;
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
-              o[e] = (T)(yacc[r][cb][2 * j + e] + (float)res[2 * j + e]);
+              o[e] = PSKIP ? (T)yacc[r][cb][2 * j + e] : (T)(yacc[r][cb][2 * j + e] + (float)res[2 * j + e]);
               const float q = (float)o[e];
               st[0][4 * cb + 2 * j + e] += q;
               st[1][4 * cb + 2 * j + e] = __builtin_fmaf(q, q, st[1][4 * cb + 2 * j + e]);
@@ -868,9 +897,9 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
   expand_dw_body<T, KS, DBUF, STAMP, NTST, 0>(a, tiles_per_wg, chunks_per_wg);
 }
 // two workgroups per CU: the y accumulators and the Wp fragments do not fit the 168 registers of three
-template <typename T, int KS>
+template <typename T, int KS, int PCO>
 __global__ void __launch_bounds__(256, 2) expand_dw_project_kernel(const IrbxArgs a, const int tiles_per_wg) {
-  expand_dw_body<T, KS, false, false, false, 16 * KS>(a, tiles_per_wg, KS);
+  expand_dw_body<T, KS, false, false, false, PCO>(a, tiles_per_wg, KS);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -882,9 +911,13 @@ bool irbx_supported(int dtype, int Cin, int c0, int Chid, int H, int W) {
   return W % kXT_W == 0 && H % kXT_H == 0 && (H * W) % irbx_stats_rows(H * W) == 0;
 }
 int irbx_pool_tiles(int H, int W) { return (H / kXT_H) * (W / kXT_W); }
-// the project tail: identity-residual blocks of the 32- and 64-channel levels (a rule on the layer alone, never on the batch)
-bool irbx_project_supported(int dtype, int Cin, int Chid, int Cout, int H, int W) {
-  return (Cin == 32 || Cin == 64) && Cout == Cin && irbx_supported(dtype, Cin, Cin, Chid, H, W);
+// the project tail (a rule on the layer alone, never on the batch): kIrbxProjectIdentity for the identity-residual blocks of the
+// 32- and 64-channel levels (one input segment), kIrbxProjectSkip for the 96 -> 32 block with a skip conv (one or two segments),
+// 0 for every other block
+int irbx_project_supported(int dtype, int Cin, int c0, int Chid, int Cout, bool skip, int H, int W) {
+  if (!irbx_supported(dtype, Cin, c0, Chid, H, W)) return 0;
+  if (!skip) return (Cin == 32 || Cin == 64) && Cout == Cin && c0 == Cin ? kIrbxProjectIdentity : 0;
+  return Cin == 96 && Cout == 32 ? kIrbxProjectSkip : 0;
 }
 int irbx_project_tiles(int H, int W) { return irbx_pool_tiles(H, W); }  // slab entries of y per image: one per 8 x 16 tile
 // pixels per statistics partial: fixed per image size (never a function of the batch: bitwise batch invariance)
@@ -1037,30 +1070,39 @@ static hipError_t launch_dw_t(const IrbxArgs& a, hipStream_t s) {
   }
   return hipErrorInvalidValue;
 }
-template <typename T, int KS>
+template <typename T, int KS, int PCO>
 static hipError_t launch_project_cfg(const IrbxArgs& a, hipStream_t s) {
+  // [sH][sX][wds][aff2][aff1], then red (2 x 256 floats) + the pool totals' place (gate), or, skip form, red (8 PCO floats) + gate
   const size_t lds = (size_t)kXNPB * 32 * SHP + (size_t)kXNPB * 32 * (16 * KS + 8) * 2 + (size_t)10 * a.Chid * 2 + (size_t)2 * a.Chid * 4 +
-                     (size_t)2 * 16 * KS * 4 + 2 * 256 * 4 + (size_t)KS * 64 * 8;
+                     (size_t)2 * 16 * KS * 4 + (PCO == 16 * KS ? 2 * 256 * 4 + (size_t)KS * 64 * 8 : (size_t)8 * PCO * 4 + (size_t)a.Chid * 4);
   const int ntiles = irbx_pool_tiles(a.H, a.W);
   int tpw = kXTilesPerWg;  // as launch_dw_cfg; every workgroup takes all channel chunks (y accumulates over them)
   while (tpw > 1 && ((a.W / kXT_W) % tpw || (long)(ntiles / tpw) * a.B < 2048)) tpw >>= 1;
-  static const std::string name = std::string("expand_dw_project_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) + ">";
+  static const std::string name = std::string("expand_dw_project_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) +
+                                  (PCO == 16 * KS ? std::string() : ", " + std::to_string(PCO)) + ">";
   note_kernel(name.c_str());
   static std::atomic<uint64_t> attr_done{0};
-  if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&expand_dw_project_kernel<T, KS>), 128 * 1024, attr_done); e != hipSuccess) return e;
-  hipLaunchKernelGGL((expand_dw_project_kernel<T, KS>), dim3(ntiles / tpw, 1, a.B), dim3(256), lds, s, a, tpw);
+  if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&expand_dw_project_kernel<T, KS, PCO>), 128 * 1024, attr_done); e != hipSuccess) return e;
+  hipLaunchKernelGGL((expand_dw_project_kernel<T, KS, PCO>), dim3(ntiles / tpw, 1, a.B), dim3(256), lds, s, a, tpw);
   return hipGetLastError();
 }
 template <typename T>
-static hipError_t launch_project_t(const IrbxArgs& a, hipStream_t s) {
-  return a.c0 == 32 ? launch_project_cfg<T, 2>(a, s) : launch_project_cfg<T, 4>(a, s);
+static hipError_t launch_project_t(const IrbxArgs& a, int form, hipStream_t s) {
+  if (form == kIrbxProjectSkip) return launch_project_cfg<T, 6, 32>(a, s);
+  return a.c0 == 32 ? launch_project_cfg<T, 2, 32>(a, s) : launch_project_cfg<T, 4, 64>(a, s);
 }
-// y = Wp . (gate * dw3x3(relu6(aff2(W1 . relu6(aff1(x)))))) + x with y's statistics slab [B][irbx_project_tiles][2][Cout]; Cout = Cin = c0
-hipError_t launch_expand_dw_project(int dtype, const IrbxArgs& a, hipStream_t s) {
-  if (a.c1 || a.x1 || !irbx_project_supported(dtype, a.c0, a.Chid, a.c0, a.H, a.W) || !a.gate || !a.wp || !a.y || !a.ystats || !a.as2 || !a.ab2 ||
-      !a.wd)
+// y = Wp . (gate * dw3x3(relu6(aff2(W1 . relu6(aff1(x)))))) + shortcut with y's statistics slab [B][irbx_project_tiles][2][Cout].
+// !skip: the identity form (shortcut x, one segment, wp [cout][Chid], cout = Cin = c0; a.ldp is set here); skip: the skip form
+// (shortcut Wskip . x, wp [cout][a.ldp] = project columns, then skip columns, a.ldp >= Chid + Cin)
+hipError_t launch_expand_dw_project(int dtype, const IrbxArgs& a0, int cout, bool skip, hipStream_t s) {
+  IrbxArgs a = a0;
+  const int Cin = a.c0 + a.c1;
+  if (!skip) a.ldp = a.Chid;
+  const int form = irbx_project_supported(dtype, Cin, a.c0, a.Chid, cout, skip, a.H, a.W);
+  if (!form || (a.c1 != 0) != (a.x1 != nullptr) || a.ldp < a.Chid + (skip ? Cin : 0) || a.ldp % 8 || !a.gate || !a.wp || !a.y || !a.ystats ||
+      !a.as2 || !a.ab2 || !a.wd)
     return hipErrorInvalidValue;
-  return dtype == 1 ? launch_project_t<half_t>(a, s) : launch_project_t<bf16_t>(a, s);
+  return dtype == 1 ? launch_project_t<half_t>(a, form, s) : launch_project_t<bf16_t>(a, form, s);
 }
 hipError_t launch_expand_dw(int dtype, const IrbxArgs& a, hipStream_t s) {
   if (!irbx_supported(dtype, a.c0 + a.c1, a.c0, a.Chid, a.H, a.W) || (a.c1 && !a.x1) || !a.out) return hipErrorInvalidValue;

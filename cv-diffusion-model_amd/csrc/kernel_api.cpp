@@ -517,7 +517,19 @@ int llie_expand_dw_project(int dtype, const void* x, int C, const float* scale1,
     return LLIE_ERR_ARG;
   IrbxArgs a = irbx_args(x, C, nullptr, 0, scale1, shift1, w_expand, scale2, shift2, w_dw, batch, H, W);
   a.gate = gate; a.wp = w_project; a.y = y; a.ystats = stats;
-  return kerr("expand_dw_project", launch_expand_dw_project(dtype, a, hs(stream)), LLIE_ERR_SHAPE, "2-byte dtype, C in {32, 64}, H % 8 == 0, W % 16 == 0");
+  return kerr("expand_dw_project", launch_expand_dw_project(dtype, a, C, false, hs(stream)), LLIE_ERR_SHAPE,
+              "2-byte dtype, C in {32, 64}, H % 8 == 0, W % 16 == 0");
+}
+int llie_expand_dw_project_skip(int dtype, const void* x0, int c0, const void* x1, int c1, const float* scale1, const float* shift1,
+                                const void* w_expand, const float* scale2, const float* shift2, const float* w_dw, const float* gate,
+                                const void* w_project_skip, int ld, int cout, void* y, float* stats, int batch, int H, int W, llie_stream stream) {
+  if (!x0 || !scale1 || !shift1 || !w_expand || !scale2 || !shift2 || !w_dw || !gate || !w_project_skip || !y || !stats || batch <= 0 || c0 <= 0 ||
+      c1 < 0 || (c1 > 0) != (x1 != nullptr) || cout <= 0 || ld < 5 * (c0 + c1))
+    return LLIE_ERR_ARG;
+  IrbxArgs a = irbx_args(x0, c0, x1, c1, scale1, shift1, w_expand, scale2, shift2, w_dw, batch, H, W);
+  a.gate = gate; a.wp = w_project_skip; a.ldp = ld; a.y = y; a.ystats = stats;
+  return kerr("expand_dw_project_skip", launch_expand_dw_project(dtype, a, cout, true, hs(stream)), LLIE_ERR_SHAPE,
+              "2-byte dtype, c0 + c1 == 96, c0 % 16 == 0, cout == 32, ld % 8 == 0, H % 8 == 0, W % 16 == 0");
 }
 int llie_irbx_project_tiles(int H, int W) { return H > 0 && W > 0 && H % 8 == 0 && W % 16 == 0 ? irbx_project_tiles(H, W) : LLIE_ERR_ARG; }
 

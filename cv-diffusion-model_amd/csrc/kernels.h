@@ -156,8 +156,9 @@ hipError_t launch_gram_finalize(int dtype, const GramFinalizeArgs& a, hipStream_
 
 // Recompute form of the block's front half (irbx.hip, 2-byte T): expand_stats writes only h1's statistics slab
 // ([B][P / irbx_stats_rows(P)][2][Chid]), expand_dw produces h2 and the SE pool slab ([B][irbx_pool_tiles][Chid]).
-// Identity-residual blocks (irbx_project_supported) go without h2 as well: expand_pool adds the SE pool totals from a pass that
-// only rebuilds h1, and expand_dw_project, given the gate, multiplies the depthwise result by Wp itself and writes y.
+// The blocks irbx_project_supported names (identity-residual 32 -> 32 and 64 -> 64; 96 -> 32 with a skip conv) go without h2 as
+// well: expand_pool adds the SE pool totals from a pass that only rebuilds h1, and expand_dw_project, given the gate, multiplies
+// the depthwise result by Wp itself, adds the shortcut and writes y.
 struct IrbxArgs {
   const void* x0; const void* x1; int c0, c1;   // block input (virtual concat), Cin = c0 + c1 in {32, 64, 96, 128}
   const float* as1; const float* ab1;            // [B][Cin]   GroupNorm-1 affine DIVIDED BY 6 (post_scale): a' = clamp01(.) = relu6 / 6
@@ -170,23 +171,26 @@ struct IrbxArgs {
   int B, H, W, Chid;
   unsigned long long* dbg;                       // diagnostic builds only (irbx_stamp)
   int nt;                                        // 1: h2 is stored non-temporally (see GemmArgs::nt)
-  // expand_dw_project: SE gate [B][Chid], project weights [Cout][Chid] T, y [B][H][W][Cout] T (Cout = Cin = c0, x1 absent) and
-  // y's statistics slab [B][irbx_project_tiles][2][Cout]
+  // expand_dw_project: SE gate [B][Chid], project weights [Cout][ldp] T, y [B][H][W][Cout] T and y's statistics slab
+  // [B][irbx_project_tiles][2][Cout].  Identity form: Cout = Cin = c0, x1 absent, ldp = Chid (set by the launcher); skip form:
+  // columns [Chid, Chid + Cin) of wp are the skip conv's weights (the engine's K-concatenated matrix)
   const float* gate; const void* wp; void* y; float* ystats;
+  int ldp;
 };
 void irbx_grid(int ks, int v);   // knobs "irbx_grid" (ks = 0: all), "irbx_grid2/4/6": workgroups per expand_dw launch (0 = heuristics)
 void irbx_stamp(int v);
 hipError_t irbx_stamp_fetch(double* out10);  // 9 slots (irbx.hip: STAMP) + the number of waves averaged
 bool irbx_supported(int dtype, int Cin, int c0, int Chid, int H, int W);
 int irbx_pool_tiles(int H, int W);
-bool irbx_project_supported(int dtype, int Cin, int Chid, int Cout, int H, int W);
+constexpr int kIrbxProjectIdentity = 1, kIrbxProjectSkip = 2;  // forms of the project tail
+int irbx_project_supported(int dtype, int Cin, int c0, int Chid, int Cout, bool skip, int H, int W);  // 0 or the form
 int irbx_project_tiles(int H, int W);
 int irbx_stats_rows(int P);
 void irbx_tune(int dbuf);  // knob "irbx_dbuf"
 hipError_t launch_expand_stats(int dtype, const IrbxArgs& a, hipStream_t s);
 hipError_t launch_expand_dw(int dtype, const IrbxArgs& a, hipStream_t s);
 hipError_t launch_expand_pool(int dtype, const IrbxArgs& a, hipStream_t s);        // needs as2 / ab2 / wd; adds into pool_tot
-hipError_t launch_expand_dw_project(int dtype, const IrbxArgs& a, hipStream_t s);
+hipError_t launch_expand_dw_project(int dtype, const IrbxArgs& a, int cout, bool skip, hipStream_t s);
 int dwconv_ntiles(int H, int W);  // pool slab entries per image: (H/8 row segments) x (W / strip width)
 int dw_pick_tyl(int B, int H, int W, int chunks);
 

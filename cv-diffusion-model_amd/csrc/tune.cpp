@@ -11,8 +11,9 @@ static Knobs knob_defaults() {
   // Recompute form (irbx.hip: statistics-only expand + tile-fused expand/depthwise): default for the
   // inference path of 2-byte engines wherever irbx_supported(); llie_tune("irbx", 0) restores the unfused pair.
   k.use_irbx = getenv("LLIE_NO_IRBX") ? 0 : 1;
-  // Identity-residual recompute blocks: the SE pool from a pass that only rebuilds h1 (expand_pool), the project GEMM as
-  // expand_dw's tail (expand_dw_project) -- h2 never reaches HBM either; llie_tune("irbx_project", 0) restores expand_dw + pw_gemm.
+  // Recompute blocks irbx_project_supported names: the SE pool from a pass that only rebuilds h1 (expand_pool), the project GEMM
+  // as expand_dw's tail (expand_dw_project) -- h2 never reaches HBM either; llie_tune("irbx_project", 0) restores expand_dw +
+  // pw_gemm, 2 keeps only the identity-residual shapes (A/B of the 96 -> 32 skip-conv block alone).
   k.irbx_project = 1;
   k.gram = 1;  // norm2 statistics of the recompute form from the Gram matrix of the block input (gram.hip); 0 = expand_stats
   // Cache policy of the big activation tensors (inference): a tensor of at least nt_min_mb MiB (this run's batch) is stored
@@ -62,7 +63,7 @@ int llie_tune(const char* knob, int value) {
   if (!strcmp(knob, "nt_mask")) { g_knobs.nt_mask = value; return LLIE_OK; }
   if (!strcmp(knob, "gram")) { g_knobs.gram = value; return LLIE_OK; }
   if (!strcmp(knob, "irbx")) { g_knobs.use_irbx = value != 0; return LLIE_OK; }
-  if (!strcmp(knob, "irbx_project")) { g_knobs.irbx_project = value != 0; return LLIE_OK; }
+  if (!strcmp(knob, "irbx_project")) { g_knobs.irbx_project = value < 0 || value > 2 ? 1 : value; return LLIE_OK; }
   if (!strcmp(knob, "irbx_dbuf")) { irbx_tune(value); return LLIE_OK; }
   if (!strcmp(knob, "irbx_stamp")) { irbx_stamp(value); return LLIE_OK; }
   if (!strcmp(knob, "irbx_grid")) { irbx_grid(0, value); return LLIE_OK; }

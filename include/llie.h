@@ -483,8 +483,12 @@ int llie_dwconv3x3_tiles(int H, int W);
  * expand_dw_project (identity-residual blocks, Cout = Cin = C in {32, 64}, one input segment): y = w_project (gate * h2) + x with the
  *   SE gate [batch][Chid] given, w_project [C][Chid] of the compute type; h2 never leaves the workgroup.  stats: fp32 slab
  *   [batch][irbx_project_tiles(H, W)][2][C] of y's per-channel (sum, sum of squares), one entry per 8 x 16 tile.
- * The engine takes the last two for the blocks irbx_project_supported names unless the knob "irbx_project" [1] is 0 (then
- * expand_dw and the project GEMM, as for every other recompute block; tests and A/B measurements). */
+ * expand_dw_project_skip (the 96 -> 32 block: a skip conv for a shortcut, c0 + c1 = 96 in one or two segments, cout = 32):
+ *   y = w_project (gate * h2) + w_skip x, x the raw concatenated input; w_project_skip [cout][ld] of the compute type holds w_project
+ *   in columns [0, Chid) and w_skip in [Chid, Chid + Cin) (ld >= Chid + Cin, ld % 8 == 0).  stats as above.
+ * The engine takes expand_pool and the matching project kernel for the blocks these two cover while the knob "irbx_project" is
+ * 1 [the default]; 2 keeps only the identity-residual blocks, 0 none (then expand_dw and the project GEMM, as for every other
+ * recompute block; tests and A/B measurements). */
 int llie_expand_dw(int dtype, const void* x0, int c0, const void* x1, int c1, const float* scale1, const float* shift1, const void* w_expand,
                    const float* scale2, const float* shift2, const float* w_dw, void* h2, unsigned long long* pool_totals, int batch, int H, int W,
                    llie_stream stream);
@@ -494,6 +498,9 @@ int llie_expand_pool(int dtype, const void* x0, int c0, const void* x1, int c1, 
 int llie_expand_dw_project(int dtype, const void* x, int C, const float* scale1, const float* shift1, const void* w_expand, const float* scale2,
                            const float* shift2, const float* w_dw, const float* gate, const void* w_project, void* y, float* stats, int batch,
                            int H, int W, llie_stream stream);
+int llie_expand_dw_project_skip(int dtype, const void* x0, int c0, const void* x1, int c1, const float* scale1, const float* shift1,
+                                const void* w_expand, const float* scale2, const float* shift2, const float* w_dw, const float* gate,
+                                const void* w_project_skip, int ld, int cout, void* y, float* stats, int batch, int H, int W, llie_stream stream);
 int llie_irbx_project_tiles(int H, int W);
 /* dst[0:bytes] = src[0:bytes] with 16-byte lane accesses: the on-box HBM copy-bandwidth probe behind bench.py's
  * `peak_measured` ("a copy-kernel bandwidth probe"; 2 x bytes move per call). */

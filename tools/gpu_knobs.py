@@ -17,7 +17,7 @@ args = sys.argv[1:]
 B = int(args.pop(0)) if args and args[0].isdigit() else 32
 m = M.LowLightDiffusion(unet_variant="small", image_size=256, compute_dtype="fp16").to(dev).eval()
 low = torch.rand(B, 3, 256, 256, device=dev) * 2 - 1
-DEFAULTS = {"irbx": 1, "enhance_split": 2, "pwx": 1, "gram": 1, "se_mfma": 1, "nt_mask": 1, "nt_min_mb": 100, "bwd_async": 1}  # the others: 0
+DEFAULTS = {"irbx": 1, "irbx_project": 1, "enhance_split": 2, "pwx": 1, "gram": 1, "se_mfma": 1, "nt_mask": 1, "nt_min_mb": 100, "bwd_async": 1}  # the others: 0
 
 
 def run(setting, steps=10):
