@@ -261,14 +261,38 @@ struct Knobs {
 };
 extern Knobs g_knobs;
 
-// Which form of the project tail (kernels.h: kIrbxProject*) the inference engine runs a block in, 0 = expand_dw + project GEMM (or
-// no recompute form at all).  c0 = channels of the block's first input segment (= w.cin without a virtual concat).  A rule on
-// the layer and the knobs alone -- never on the batch or the grid, which would break batch invariance; the byte model
-// (llie_path_bytes) asks the same function.
-inline int irb_project_form(int dt, const IrbW& w, int c0, int H, int W) {
-  if (!g_knobs.use_irbx || !g_knobs.irbx_project || w.hid != w.hid_r || w.cin != w.cin_r || w.cout != w.cout_r || w.hid % 128) return 0;
-  const int form = llie::irbx_project_supported(dt, w.cin, c0, w.hid, w.cout, w.skip, H, W);
-  return form == llie::kIrbxProjectSkip && g_knobs.irbx_project == 2 ? 0 : form;
+// The launch sequence of an inverted-residual block (forward.cpp: Run::irb; the byte model, llie_path_bytes, asks too):
+//   unfused    expand GEMM, dwconv3x3, SE, project GEMM: fp32 engines, training, wide or padded blocks
+//   recompute  2-byte inference, narrow inputs: a statistics-only expand pass, then expand_dw rebuilds h1 on the fly (irbx.hip)
+//   project    identity-residual recompute blocks and the 96 -> 32 skip-conv block go without h2 too: the SE pool totals come from a
+//              pass that only rebuilds h1 (expand_pool); given the gate, expand_dw_project applies Wp itself and adds the shortcut
+enum IrbForm { kIrbUnfused, kIrbRecompute, kIrbProject };
+struct IrbPath {
+  IrbForm form;
+  // 2-byte inference engines carry norm1's ReLU6 as clamp01(z / 6): the tables come out divided by 6 and the expand GEMM (or the
+  // recompute kernels) puts the 6 back (kernels.h: ACT_RELU6_S6); the unfused depthwise treats norm2's alike (DwArgs::s6), the
+  // recompute kernels take norm2's plain tables (their accumulators are already / 6).  Training keeps the plain tables.
+  bool s6;
+  // SE pool: inference adds fixed-point channel totals into the zeroed region (one gate kernel follows); training keeps the
+  // slab of tile partials (the backward pass and the 3-launch SE path read it)
+  bool fixtot;
+  // recompute forms: norm2's statistics from the Gram matrix of the activated input (gram.hip) -- the statistics pass is then a
+  // plain read of x -- or, knob "gram" = 0, from a second run of the expand GEMM (expand_stats).  From 32 768 pixels per image
+  // on: below, the workgroup epilogue and the last-ticket sum outweigh the saved MFMAs (measured at B = 1 and B = 32; the rule
+  // must not depend on the batch, it fixes the statistics' summation order)
+  bool gram;
+};
+// c0 = channels of the block's first input segment (= w.cin without a virtual concat).  A rule on the layer, the image size, the
+// dtype and the knobs alone -- never on the batch or the grid, which would break batch invariance.
+inline IrbPath irb_path(int dt, const IrbW& w, int c0, int H, int W, bool training) {
+  IrbPath p{kIrbUnfused, !training && dt != LLIE_F32, !training && w.hid % 128 == 0, false};
+  // (!fixtot: the recompute kernels only know the fixed-point totals; every hid irbx_supported accepts is a multiple of 128)
+  if (!p.fixtot || !g_knobs.use_irbx || w.hid != w.hid_r || w.cin != w.cin_r || !irbx_supported(dt, w.cin, c0, w.hid, H, W)) return p;
+  p.gram = g_knobs.gram && (H * W >= 32768 || g_knobs.gram > 1) && gram_supported(dt, w.cin, c0, H * W);
+  const int tail = g_knobs.irbx_project && w.cout == w.cout_r ? irbx_project_supported(dt, w.cin, c0, w.hid, w.cout, w.skip, H, W) : 0;
+  // knob "irbx_project" = 2 keeps the identity-residual shapes only
+  p.form = tail && !(tail == kIrbxProjectSkip && g_knobs.irbx_project == 2) ? kIrbProject : kIrbRecompute;
+  return p;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -105,166 +105,163 @@ struct Run : Exec {
     timed(LLIE_K_OTHER, (int64_t)B * C * 8, [&] { return launch_gn_finalize(a, s); }, "gn_finalize_kernel");
   }
 
-  // InvertedResidualBlock.forward (efficient_unet.py:203-236) as 7 launches.
-  Tens irb(const IrbW& w, const Tens& x0, const Tens* x1, const float* film, int64_t film_stride) {
+  // one-segment GEMM out[M][N] = act(seg) W[N][K]^T; callers add further segments, a residual or the store policy
+  static GemmArgs gemm1(GemmSeg seg, const void* w, void* out, float* stats, int M, int N, int K, int P) {
+    GemmArgs g{};
+    g.seg[0] = seg; g.nseg = 1; g.w = w; g.out = out; g.stats = stats; g.M = M; g.N = N; g.K = K; g.P = P;
+    return g;
+  }
+  // the block's SE MLP over pool partials or totals the caller adds (small.hip)
+  SeArgs se_args(const IrbW& w, int P, size_t semean, size_t sehid, size_t gate) const {
+    SeArgs e{};
+    e.P = P; e.w1 = wptr(w.se_w1); e.b1 = wptr<float>(w.se_b1); e.w2 = wptr(w.se_w2); e.b2 = wptr<float>(w.se_b2);
+    e.mean = p<float>(semean); e.hid = p<float>(sehid); e.gate = p<float>(gate); e.B = B; e.C = w.hid; e.Cs = w.sq;
+    return e;
+  }
+
+  // What the stages of one inverted-residual block hand on (workspace offsets)
+  struct IrbTmp {
+    size_t as1 = 0, ab1 = 0, as2 = 0, ab2 = 0;  // norm1 / norm2 + FiLM tables
+    Tens h1;                                    // unfused form only
+    size_t h2 = 0, pool = 0, ptot = 0;          // depthwise output (none in the project form); SE pool: tile partials or fixed-point totals
+    int dnt = 0;                                // tiles per image of the kernel that pooled
+    size_t sehid = 0, semean = 0, gate = 0;
+    IrbxArgs xa{};                              // recompute forms: the kernels' inputs (irbx.hip); each launch adds its outputs to a copy
+  };
+
+  // K1: expand with norm1 + ReLU6 prologue; norm2 + FiLM folded into one affine; K2: depthwise with affine + ReLU6 prologue and SE pool
+  void front_unfused(const IrbPath& path, const IrbW& w, const Tens& x0, const Tens* x1, const float* film, int64_t film_stride, IrbRec& rec, IrbTmp& t) {
     const int H = x0.H, W = x0.W, P = H * W, M = B * P;
-    size_t as1, ab1;
-    IrbRec rec{};
-    snprintf(tag, sizeof tag, "irb P=%d %d->%d hid=%d", P, w.cin, w.cout, w.hid);
-    // 2-byte inference engines carry norm1's ReLU6 as clamp01(z / 6): the tables come out divided by 6 and the expand
-    // GEMM (or the recompute kernels) puts the 6 back (kernels.h: ACT_RELU6_S6).  Training keeps the plain tables.
-    const bool s6 = !tape && dt != LLIE_F32;
-    gn(x0, x1, w.n1g, w.n1b, nullptr, 0, as1, ab1, &rec.n1, s6 ? 1.f / 6.f : 0.f);
-    // Recompute form (2-byte T, narrow inputs): a statistics-only expand pass, then the fused expand + depthwise kernel
-    // rebuilds h1 on the fly, so the 4x-expanded tensor never touches HBM (irbx.hip).
-    const bool fusedx = !tape && g_knobs.use_irbx && w.hid == w.hid_r && w.cin == w.cin_r &&
-                        irbx_supported(dt, w.cin, x0.C, w.hid, H, W);
-    // K1: expand with norm1 + ReLU6 prologue
-    Tens h1;
-    h1.C = w.hid; h1.Cr = w.hid_r; h1.H = H; h1.W = W; h1.ntiles = fusedx ? P / irbx_stats_rows(P) : pw_gemm_ntiles(P); h1.valid = true;
-    h1.off = fusedx ? 0 : ar->alloc((size_t)B * P * w.hid * es());
-    // norm2's statistics of the recompute form: from the Gram matrix of the activated input (gram.hip) -- the statistics
-    // pass is then a plain read of x -- or, knob "gram" = 0, from a second run of the expand GEMM (expand_stats)
-    // (from 32 768 pixels per image on: below, the workgroup epilogue and the last-ticket sum outweigh the saved MFMAs --
-    // measured at B = 1 and B = 32; the rule must not depend on the batch, it fixes the statistics' summation order)
-    const bool gram = fusedx && g_knobs.gram && (P >= 32768 || g_knobs.gram > 1) && gram_supported(dt, w.cin, x0.C, P);
-    h1.slab = gram ? 0 : ar->alloc((size_t)B * h1.ntiles * 2 * w.hid * 4);
-    const size_t gpart = gram ? ar->alloc((size_t)B * gram_part_floats(w.cin, P) * 4) : 0;
-    const size_t gtot = gram ? ar->alloc((size_t)B * (w.cin * w.cin + w.cin) * 4) : 0;
-    const size_t gtick = gram ? ztake((size_t)B * 4) : 0;
-    IrbxArgs xa{};
-    if (fusedx && !dry) {
-      xa.x0 = p(x0.off); xa.c0 = x0.C; xa.x1 = x1 ? p(x1->off) : nullptr; xa.c1 = x1 ? x1->C : 0;
-      xa.as1 = p<float>(as1); xa.ab1 = p<float>(ab1); xa.w1 = wptr(w.w_expand); xa.wd = wptr<float>(w.w_dw);
-      xa.stats = gram ? nullptr : p<float>(h1.slab); xa.B = B; xa.H = H; xa.W = W; xa.Chid = w.hid;
-      if (gram) {
-        GramArgs ga{};
-        ga.x0 = xa.x0; ga.x1 = xa.x1; ga.c0 = xa.c0; ga.c1 = xa.c1; ga.as1 = xa.as1; ga.ab1 = xa.ab1;
-        ga.part = p<float>(gpart); ga.gtot = p<float>(gtot); ga.tickets = p<unsigned int>(gtick); ga.B = B; ga.P = P;
-        timed(LLIE_K_GEMM, (int64_t)M * w.cin * (int64_t)es(), [&] { return launch_gram_stats(dt, ga, s); });
-      } else {
-        timed(LLIE_K_GEMM, ((int64_t)M * w.cin + (int64_t)w.hid * w.cin) * (int64_t)es(), [&] { return launch_expand_stats(dt, xa, s); });
-      }
-    } else if (!dry) {
-      GemmArgs g{};
-      const int act1 = s6 ? ACT_RELU6_S6 : ACT_RELU6;
-      g.seg[0] = GemmSeg{p(x0.off), x0.C, p<float>(as1), p<float>(ab1), w.cin, act1};
-      g.nseg = 1;
-      if (x1) {
-        g.seg[1] = GemmSeg{p(x1->off), x1->C, p<float>(as1) + x0.C, p<float>(ab1) + x0.C, w.cin, act1};
-        g.nseg = 2;
-      }
-      g.w = wptr(w.w_expand); g.out = p(h1.off); g.stats = p<float>(h1.slab);
-      g.M = M; g.N = w.hid; g.K = w.cin; g.P = P;
+    Tens& h1 = t.h1;
+    h1.C = w.hid; h1.Cr = w.hid_r; h1.H = H; h1.W = W; h1.ntiles = pw_gemm_ntiles(P); h1.valid = true;
+    h1.off = ar->alloc((size_t)B * P * w.hid * es());
+    h1.slab = ar->alloc((size_t)B * h1.ntiles * 2 * w.hid * 4);
+    if (!dry) {
+      const int act1 = path.s6 ? ACT_RELU6_S6 : ACT_RELU6;
+      GemmArgs g = gemm1(GemmSeg{p(x0.off), x0.C, p<float>(t.as1), p<float>(t.ab1), w.cin, act1}, wptr(w.w_expand), p(h1.off), p<float>(h1.slab), M, w.hid, w.cin, P);
+      if (x1) g.seg[g.nseg++] = GemmSeg{p(x1->off), x1->C, p<float>(t.as1) + x0.C, p<float>(t.ab1) + x0.C, w.cin, act1};
       const int64_t kbytes = ((int64_t)M * (w.cin + w.hid) + (int64_t)w.hid * w.cin) * (int64_t)es();
-      if (s6 && w.has_wf && pw_expand_supported(dt, g.seg, g.nseg, M, w.hid, w.cin, P)) {
+      if (path.s6 && w.has_wf && pw_expand_supported(dt, g.seg, g.nseg, M, w.hid, w.cin, P)) {
         // activation-stationary form: pixels activated once and held in registers, packed weights streamed (pwx.hip)
         ExpandArgs x{};
         for (int i = 0; i < g.nseg; ++i) x.seg[i] = g.seg[i];
-        x.nseg = g.nseg; x.wf = wptr(w.w_expand_f); x.out = g.out; x.stats = g.stats;
-        x.M = M; x.N = w.hid; x.K = w.cin; x.P = P;
+        x.nseg = g.nseg; x.wf = wptr(w.w_expand_f); x.out = g.out; x.stats = g.stats; x.M = M; x.N = w.hid; x.K = w.cin; x.P = P;
         x.nt = nt_store(2, (int64_t)M * w.hid);
         timed(LLIE_K_GEMM, kbytes, [&] { return launch_pw_expand(dt, x, s); });
       } else {
-        if (s6) g.nt = nt_store(2, (int64_t)M * w.hid);
+        if (path.s6) g.nt = nt_store(2, (int64_t)M * w.hid);
         timed(LLIE_K_GEMM, kbytes, [&] { return launch_pw_gemm(dt, g, s); });
       }
     }
-    // norm2 + FiLM folded into one affine
-    size_t as2, ab2;
-    // unfused depthwise of a 2-byte inference engine: tables / 6 and clamp01 in its prologue too (DwArgs::s6); the
-    // recompute kernel takes the plain tables (it rescales the shift itself: its accumulators are already / 6)
-    const bool s6dw = s6 && !fusedx;
-    if (gram) {
-      as2 = ar->alloc((size_t)B * w.hid * 4);
-      ab2 = ar->alloc((size_t)B * w.hid * 4);
+    gn(h1, nullptr, w.n2g, w.n2b, film, film_stride, t.as2, t.ab2, &rec.n2, path.s6 ? 1.f / 6.f : 0.f);
+    t.dnt = dwconv_ntiles(H, W);
+    t.h2 = ar->alloc((size_t)M * w.hid * es());
+    t.pool = path.fixtot ? 0 : ar->alloc((size_t)B * t.dnt * w.hid * 4);
+    t.ptot = path.fixtot ? ztake((size_t)B * w.hid * 8) : 0;
+    if (!dry) {
+      DwArgs d{};
+      d.in = p(h1.off); d.out = p(t.h2); d.as = p<float>(t.as2); d.ab = p<float>(t.ab2); d.w = wptr<float>(w.w_dw);
+      if (path.fixtot) d.pool_tot = p<unsigned long long>(t.ptot); else d.pool = p<float>(t.pool);
+      d.B = B; d.H = H; d.W = W; d.C = w.hid; d.s6 = path.s6 ? 1 : 0; d.nt = nt_store(4, (int64_t)M * w.hid);
+      timed(LLIE_K_DW, 2LL * M * w.hid * (int64_t)es(), [&] { return launch_dwconv3x3(dt, d, s); });
+    }
+    rel(t.as1); rel(t.ab1); rel(h1.off); rel(h1.slab); rel(t.as2); rel(t.ab2);
+  }
+
+  IrbxArgs irbx_args(const IrbW& w, const Tens& x0, const Tens* x1, size_t as1, size_t ab1) const {
+    IrbxArgs a{};
+    a.x0 = p(x0.off); a.c0 = x0.C; a.x1 = x1 ? p(x1->off) : nullptr; a.c1 = x1 ? x1->C : 0; a.as1 = p<float>(as1); a.ab1 = p<float>(ab1);
+    a.w1 = wptr(w.w_expand); a.wd = wptr<float>(w.w_dw); a.B = B; a.H = x0.H; a.W = x0.W; a.Chid = w.hid;
+    return a;
+  }
+  // Recompute and project forms (inference, fixed-point pool totals): norm2's statistics without h1, its affine, then expand_dw
+  // (h2 and the pool totals) or, project form, expand_pool (the totals alone; the norm tables stay for expand_dw_project)
+  void front_recompute(const IrbPath& path, const IrbW& w, const Tens& x0, const Tens* x1, const float* film, int64_t film_stride, IrbTmp& t) {
+    const int H = x0.H, W = x0.W, P = H * W, M = B * P;
+    const bool pool_only = path.form == kIrbProject;
+    Tens st;  // h1 as norm2 sees it: the statistics slab of expand_stats alone
+    st.C = w.hid; st.Cr = w.hid_r; st.H = H; st.W = W; st.ntiles = P / irbx_stats_rows(P); st.valid = true;
+    st.slab = path.gram ? 0 : ar->alloc((size_t)B * st.ntiles * 2 * w.hid * 4);
+    const size_t gpart = path.gram ? ar->alloc((size_t)B * gram_part_floats(w.cin, P) * 4) : 0;
+    const size_t gtot = path.gram ? ar->alloc((size_t)B * (w.cin * w.cin + w.cin) * 4) : 0;
+    const size_t gtick = path.gram ? ztake((size_t)B * 4) : 0;
+    if (!dry) {
+      t.xa = irbx_args(w, x0, x1, t.as1, t.ab1);
+      if (path.gram) {
+        GramArgs ga{};
+        ga.x0 = t.xa.x0; ga.x1 = t.xa.x1; ga.c0 = t.xa.c0; ga.c1 = t.xa.c1; ga.as1 = t.xa.as1; ga.ab1 = t.xa.ab1;
+        ga.part = p<float>(gpart); ga.gtot = p<float>(gtot); ga.tickets = p<unsigned int>(gtick); ga.B = B; ga.P = P;
+        timed(LLIE_K_GEMM, (int64_t)M * w.cin * (int64_t)es(), [&] { return launch_gram_stats(dt, ga, s); });
+      } else {
+        IrbxArgs a = t.xa;
+        a.stats = p<float>(st.slab);
+        timed(LLIE_K_GEMM, ((int64_t)M * w.cin + (int64_t)w.hid * w.cin) * (int64_t)es(), [&] { return launch_expand_stats(dt, a, s); });
+      }
+    }
+    if (path.gram) {
+      t.as2 = ar->alloc((size_t)B * w.hid * 4); t.ab2 = ar->alloc((size_t)B * w.hid * 4);
       if (!dry) {
         GramFinalizeArgs fa{};
         fa.gtot = p<float>(gtot); fa.w1 = wptr(w.w_expand); fa.K = w.cin; fa.Chid = w.hid; fa.groups = gn_groups(w.hid); fa.P = P; fa.B = B;
-        fa.gamma = wptr<float>(w.n2g); fa.beta = wptr<float>(w.n2b);
-        fa.film = film ? film + w.film_off : nullptr; fa.film_stride = film_stride; fa.eps = 1e-5f;
-        fa.as = p<float>(as2); fa.ab = p<float>(ab2); fa.post_scale = 0.f;
+        fa.gamma = wptr<float>(w.n2g); fa.beta = wptr<float>(w.n2b); fa.film = film; fa.film_stride = film_stride; fa.eps = 1e-5f;
+        fa.as = p<float>(t.as2); fa.ab = p<float>(t.ab2); fa.post_scale = 0.f;
         timed(LLIE_K_OTHER, (int64_t)B * w.hid * 8, [&] { return launch_gram_finalize(dt, fa, s); }, "gram_finalize_kernel");
       }
       rel(gpart);
     } else {
-      gn(h1, nullptr, w.n2g, w.n2b, film ? film + w.film_off : nullptr, film_stride, as2, ab2, &rec.n2, s6dw ? 1.f / 6.f : 0.f);
+      gn(st, nullptr, w.n2g, w.n2b, film, film_stride, t.as2, t.ab2);
     }
-    // K2: depthwise with affine + ReLU6 prologue and SE pool partials
-    const int dnt = fusedx ? irbx_pool_tiles(H, W) : dwconv_ntiles(H, W);
-    // Identity-residual recompute blocks and the 96 -> 32 skip-conv block go without h2 too: the SE pool totals come from a pass
-    // that only rebuilds h1 (expand_pool), and once the gate is known expand_dw_project multiplies the depthwise result by Wp
-    // itself and adds the shortcut.  A rule on the layer alone (irb_project_form) -- never on the batch or the grid, which would
-    // break batch invariance.
-    const bool fusedp = fusedx && irb_project_form(dt, w, x0.C, H, W) != 0;
-    const size_t h2 = fusedp ? 0 : ar->alloc((size_t)M * w.hid * es());
-    // SE pool: inference adds fixed-point channel totals into the zeroed region (one gate kernel follows); training keeps
-    // the slab of tile partials (the backward pass and the 3-launch SE path read it)
-    const bool fixtot = !tape && w.hid % 128 == 0;
-    const size_t pool = fixtot ? 0 : ar->alloc((size_t)B * dnt * w.hid * 4);
-    const size_t ptot = fixtot ? ztake((size_t)B * w.hid * 8) : 0;
+    t.dnt = irbx_pool_tiles(H, W);
+    t.h2 = pool_only ? 0 : ar->alloc((size_t)M * w.hid * es());
+    t.ptot = ztake((size_t)B * w.hid * 8);
     if (!dry) {
-      if (fusedp) {
-        xa.as2 = p<float>(as2); xa.ab2 = p<float>(ab2); xa.pool_tot = p<unsigned long long>(ptot);
-        timed(LLIE_K_DW, ((int64_t)M * w.cin + (int64_t)w.hid * w.cin) * (int64_t)es(), [&] { return launch_expand_pool(dt, xa, s); });
-      } else if (fusedx) {
-        xa.as2 = p<float>(as2); xa.ab2 = p<float>(ab2); xa.out = p(h2);
-        xa.pool = fixtot ? nullptr : p<float>(pool);
-        xa.pool_tot = fixtot ? p<unsigned long long>(ptot) : nullptr;
-        xa.nt = w.cin <= 64 ? nt_store(1, (int64_t)M * w.hid) : 0;  // 96 -> 384: the kernel itself loses more than its consumer gains
-        timed(LLIE_K_DW, (int64_t)M * (w.cin + w.hid) * (int64_t)es(), [&] { return launch_expand_dw(dt, xa, s); });
+      t.xa.as2 = p<float>(t.as2); t.xa.ab2 = p<float>(t.ab2);
+      IrbxArgs a = t.xa;
+      a.pool_tot = p<unsigned long long>(t.ptot);
+      if (pool_only) {
+        timed(LLIE_K_DW, ((int64_t)M * w.cin + (int64_t)w.hid * w.cin) * (int64_t)es(), [&] { return launch_expand_pool(dt, a, s); });
       } else {
-        DwArgs d{};
-        d.in = p(h1.off); d.out = p(h2); d.as = p<float>(as2); d.ab = p<float>(ab2);
-        d.w = wptr<float>(w.w_dw); d.pool = fixtot ? nullptr : p<float>(pool);
-        d.pool_tot = fixtot ? p<unsigned long long>(ptot) : nullptr; d.B = B; d.H = H; d.W = W; d.C = w.hid; d.s6 = s6dw ? 1 : 0;
-        d.nt = nt_store(4, (int64_t)M * w.hid);
-        timed(LLIE_K_DW, 2LL * M * w.hid * (int64_t)es(), [&] { return launch_dwconv3x3(dt, d, s); });
+        a.out = p(t.h2);
+        a.nt = w.cin <= 64 ? nt_store(1, (int64_t)M * w.hid) : 0;  // 96 -> 384: the kernel itself loses more than its consumer gains
+        timed(LLIE_K_DW, (int64_t)M * (w.cin + w.hid) * (int64_t)es(), [&] { return launch_expand_dw(dt, a, s); });
       }
     }
-    if (!fusedp) { rel(as1); rel(ab1); }  // expand_dw_project applies both norms again
-    if (!fusedx) rel(h1.off);
-    if (gram) rel(gtot); else rel(h1.slab);
-    if (!fusedp) { rel(as2); rel(ab2); }
-    // SE MLP
-    // (wide blocks of the 2-byte inference engines: fc1's pre-activations accumulate as integers in the zero-initialised region)
+    if (!pool_only) { rel(t.as1); rel(t.ab1); }
+    rel(path.gram ? gtot : st.slab);
+    if (!pool_only) { rel(t.as2); rel(t.ab2); }
+  }
+
+  // SE MLP: pool partials or totals -> gate
+  // (wide blocks of the 2-byte inference engines: fc1's pre-activations accumulate as integers in the zero-initialised region)
+  void se_gate(const IrbPath& path, const IrbW& w, int P, IrbTmp& t) {
+    const bool fixtot = path.fixtot;
     const bool sepre_ok = fixtot && dt != LLIE_F32 && g_knobs.se_mfma && w.hid >= 768 && w.hid % 256 == 0 && w.sq % 64 == 0 && w.sq <= 512;
     const size_t sepre = sepre_ok ? ztake((size_t)B * w.sq * 8) : 0;
-    const size_t sehid = ar->alloc((size_t)B * w.sq * 4), gate = ar->alloc((size_t)B * w.hid * 4);
-    const size_t semean = ar->alloc((size_t)B * w.hid * 4);
+    t.sehid = ar->alloc((size_t)B * w.sq * 4); t.gate = ar->alloc((size_t)B * w.hid * 4); t.semean = ar->alloc((size_t)B * w.hid * 4);
     if (!dry) {
-      SeArgs e{};
-      e.pool = fixtot ? nullptr : p<float>(pool); e.ntiles = dnt; e.P = P;
-      e.w1 = wptr(w.se_w1); e.b1 = wptr<float>(w.se_b1); e.w2 = wptr(w.se_w2); e.b2 = wptr<float>(w.se_b2);
-      e.mean = p<float>(semean); e.hid = p<float>(sehid); e.gate = p<float>(gate); e.B = B; e.C = w.hid; e.Cs = w.sq;
-      if (fixtot) e.tot = p<unsigned long long>(ptot);
+      SeArgs e = se_args(w, P, t.semean, t.sehid, t.gate);
+      e.ntiles = t.dnt;
+      if (fixtot) e.tot = p<unsigned long long>(t.ptot); else e.pool = p<float>(t.pool);
       if (sepre_ok) e.pre = p<long long>(sepre);
-      if (sepre_ok && g_knobs.se_mfma && se_mlp_mfma_supported(dt, e)) {
+      if (sepre_ok && se_mlp_mfma_supported(dt, e)) {
         timed(LLIE_K_SE, (int64_t)B * w.hid * 12 + 2LL * w.hid * w.sq * (int64_t)es(), [&] { return launch_se_mlp_mfma(dt, e, s); });
       } else if (fixtot && w.hid <= 384) {
         timed(LLIE_K_SE, (int64_t)B * w.hid * 12 + 2LL * w.hid * w.sq * (int64_t)es(), [&] { return launch_se_gate(dt, e, s); });
-      } else timed(LLIE_K_SE, ((int64_t)B * dnt * w.hid * 4) + 2LL * w.hid * w.sq * (int64_t)es(), [&] {
+      } else timed(LLIE_K_SE, ((int64_t)B * t.dnt * w.hid * 4) + 2LL * w.hid * w.sq * (int64_t)es(), [&] {
         hipError_t r1 = launch_se_fc1(dt, e, s);
         return r1 != hipSuccess ? r1 : launch_se_fc2(dt, e, s);
       });
     }
-    if (!fixtot) rel(pool);
-    rel(sehid); rel(semean);
-    // K3: project with SE gate prologue (+ skip conv as extra K segments, or identity residual)
-    Tens y = new_tens(w.cout, H, W, fusedp ? irbx_project_tiles(H, W) : pw_gemm_ntiles(P), w.cout_r);
-    if (fusedp) {
-      if (!dry) {
-        xa.pool_tot = nullptr; xa.gate = p<float>(gate); xa.wp = wptr(w.w_proj); xa.y = p(y.off); xa.ystats = p<float>(y.slab);
-        xa.ldp = w.hid + (w.skip ? w.cin : 0);  // project and skip share one K-concatenated matrix (model.cpp)
-        timed(LLIE_K_DW, ((int64_t)M * (w.cin + w.cout) + (int64_t)w.hid * (w.cin + w.cout)) * (int64_t)es(),
-              [&] { return launch_expand_dw_project(dt, xa, w.cout, w.skip, s); });
-      }
-      rel(as1); rel(ab1); rel(as2); rel(ab2);
-    } else if (!dry) {
-      GemmArgs g{};
-      g.seg[0] = GemmSeg{p(h2), w.hid, p<float>(gate), nullptr, w.hid, ACT_NONE};
-      g.nseg = 1;
-      g.K = w.hid;
+    if (!fixtot) rel(t.pool);
+    rel(t.sehid); rel(t.semean);
+  }
+
+  // K3: project with SE gate prologue (+ skip conv as extra K segments, or identity residual)
+  Tens project_gemm(const IrbW& w, const Tens& x0, const Tens* x1, IrbTmp& t) {
+    const int P = x0.H * x0.W, M = B * P;
+    Tens y = new_tens(w.cout, x0.H, x0.W, pw_gemm_ntiles(P), w.cout_r);
+    if (!dry) {
+      GemmArgs g = gemm1(GemmSeg{p(t.h2), w.hid, p<float>(t.gate), nullptr, w.hid, ACT_NONE}, wptr(w.w_proj), p(y.off), p<float>(y.slab), M, w.cout, w.hid, P);
       if (w.skip) {
         g.seg[g.nseg++] = GemmSeg{p(x0.off), x0.C, nullptr, nullptr, 0, ACT_NONE};
         if (x1) g.seg[g.nseg++] = GemmSeg{p(x1->off), x1->C, nullptr, nullptr, 0, ACT_NONE};
@@ -272,19 +269,46 @@ struct Run : Exec {
       } else {
         g.res = p(x0.off);
       }
-      g.w = wptr(w.w_proj); g.out = p(y.off); g.stats = p<float>(y.slab);
-      g.M = M; g.N = w.cout; g.P = P;
       g.nt = nt_store(8, (int64_t)M * w.cout);
       timed(LLIE_K_GEMM, ((int64_t)M * (g.K + w.cout + (w.skip ? 0 : w.cout)) + (int64_t)w.cout * g.K) * (int64_t)es(),
             [&] { return launch_pw_gemm(dt, g, s); });
     }
-    if (!fusedp) rel(h2);
-    rel(gate);
+    rel(t.h2); rel(t.gate);
+    return y;
+  }
+  // project form: expand_dw_project rebuilds h1 and the depthwise result (both norms again), gates, projects, adds the shortcut
+  Tens project_fused(const IrbW& w, const Tens& x0, IrbTmp& t) {
+    const int H = x0.H, W = x0.W, M = B * H * W;
+    Tens y = new_tens(w.cout, H, W, irbx_project_tiles(H, W), w.cout_r);
+    if (!dry) {
+      IrbxArgs a = t.xa;
+      a.gate = p<float>(t.gate); a.wp = wptr(w.w_proj); a.y = p(y.off); a.ystats = p<float>(y.slab);
+      a.ldp = w.hid + (w.skip ? w.cin : 0);  // project and skip share one K-concatenated matrix (model.cpp)
+      timed(LLIE_K_DW, ((int64_t)M * (w.cin + w.cout) + (int64_t)w.hid * (w.cin + w.cout)) * (int64_t)es(),
+            [&] { return launch_expand_dw_project(dt, a, w.cout, w.skip, s); });
+    }
+    rel(t.as1); rel(t.ab1); rel(t.as2); rel(t.ab2); rel(t.gate);
+    return y;
+  }
+
+  // InvertedResidualBlock.forward (efficient_unet.py:203-236) in the form irb_path picks (engine.h): 7 launches unfused
+  Tens irb(const IrbW& w, const Tens& x0, const Tens* x1, const float* film, int64_t film_stride) {
+    const int P = x0.H * x0.W;
+    const IrbPath path = irb_path(dt, w, x0.C, x0.H, x0.W, tape != nullptr);
+    IrbRec rec{};
+    IrbTmp t;  // what the stages hand on
+    snprintf(tag, sizeof tag, "irb P=%d %d->%d hid=%d", P, w.cin, w.cout, w.hid);
+    gn(x0, x1, w.n1g, w.n1b, nullptr, 0, t.as1, t.ab1, &rec.n1, path.s6 ? 1.f / 6.f : 0.f);
+    const float* film2 = film ? film + w.film_off : nullptr;  // this block's rows of the FiLM projection
+    if (path.form == kIrbUnfused) front_unfused(path, w, x0, x1, film2, film_stride, rec, t);
+    else front_recompute(path, w, x0, x1, film2, film_stride, t);
+    se_gate(path, w, P, t);
+    Tens y = path.form == kIrbProject ? project_fused(w, x0, t) : project_gemm(w, x0, x1, t);
     if (tape) {
       rec.w = (int)(&w - c->irbs.data());
       rec.x0 = x0; rec.cat = x1 != nullptr;
       if (x1) rec.x1 = *x1;
-      rec.h1 = h1; rec.h2 = h2; rec.gate = gate; rec.sehid = sehid; rec.semean = semean; rec.y = y;
+      rec.h1 = t.h1; rec.h2 = t.h2; rec.gate = t.gate; rec.sehid = t.sehid; rec.semean = t.semean; rec.y = y;
       tape->ops.push_back({0, (int)tape->irbs.size()});
       tape->irbs.push_back(rec);
     }
@@ -300,10 +324,7 @@ struct Run : Exec {
     gn(x, nullptr, w.ng, w.nb, nullptr, 0, as, ab, &rec.n1);
     const size_t qkv = ar->alloc((size_t)M * 3 * w.inner * es());
     if (!dry) {
-      GemmArgs g{};
-      g.seg[0] = GemmSeg{p(x.off), x.C, p<float>(as), p<float>(ab), x.C, ACT_NONE};
-      g.nseg = 1; g.w = wptr(w.w_qkv); g.out = p(qkv);
-      g.M = M; g.N = 3 * w.inner; g.K = x.C; g.P = N;
+      const GemmArgs g = gemm1(GemmSeg{p(x.off), x.C, p<float>(as), p<float>(ab), x.C, ACT_NONE}, wptr(w.w_qkv), p(qkv), nullptr, M, 3 * w.inner, x.C, N);
       timed(LLIE_K_GEMM, ((int64_t)M * (x.C + 3 * w.inner) + 3LL * w.inner * x.C) * (int64_t)es(), [&] { return launch_pw_gemm(dt, g, s); });
     }
     rel(as); rel(ab);
@@ -319,10 +340,7 @@ struct Run : Exec {
     rel(qkv); rel(kv);
     Tens tmp = new_tens(x.C, H, W, pw_gemm_ntiles(N));
     if (!dry) {
-      GemmArgs g{};
-      g.seg[0] = GemmSeg{p(ao), w.inner, nullptr, nullptr, 0, ACT_NONE};
-      g.nseg = 1; g.w = wptr(w.w_out); g.out = p(tmp.off); g.stats = p<float>(tmp.slab);
-      g.M = M; g.N = x.C; g.K = w.inner; g.P = N;
+      const GemmArgs g = gemm1(GemmSeg{p(ao), w.inner, nullptr, nullptr, 0, ACT_NONE}, wptr(w.w_out), p(tmp.off), p<float>(tmp.slab), M, x.C, w.inner, N);
       timed(LLIE_K_GEMM, ((int64_t)M * (x.C + w.inner) + (int64_t)w.inner * x.C) * (int64_t)es(), [&] { return launch_pw_gemm(dt, g, s); });
     }
     rel(ao);
@@ -503,10 +521,8 @@ struct Run : Exec {
       const size_t semean = ar->alloc((size_t)B * C * 4), zero = ar->alloc((size_t)B * C * 4);
       out = new_tens(C, H, W, P / kAffineTileRows);
       if (!dry) {
-        SeArgs e{};
-        e.pool = p<float>(x0.slab); e.ntiles = P / 64; e.pool_stride = 2 * C; e.P = P;
-        e.w1 = wptr(w.se_w1); e.b1 = wptr<float>(w.se_b1); e.w2 = wptr(w.se_w2); e.b2 = wptr<float>(w.se_b2);
-        e.mean = p<float>(semean); e.hid = p<float>(sehid); e.gate = p<float>(gate); e.B = B; e.C = C; e.Cs = w.sq;
+        SeArgs e = se_args(w, P, semean, sehid, gate);
+        e.pool = p<float>(x0.slab); e.ntiles = P / 64; e.pool_stride = 2 * C;
         chk(launch_se_fc1(dt, e, s));
         chk(launch_se_fc2(dt, e, s));
         chk(launch_fill_zero(p(zero), (int64_t)B * C * 4, s));

@@ -903,7 +903,6 @@ __global__ void __launch_bounds__(256, 2) expand_dw_project_kernel(const IrbxArg
 }
 
 // ---------------------------------------------------------------------------------------------
-int irbx_stats_rows(int P);
 bool irbx_supported(int dtype, int Cin, int c0, int Chid, int H, int W) {
   if (dtype != 1 && dtype != 2) return false;
   if (Cin != 32 && Cin != 64 && Cin != 96) return false;  // Cin = 128: 92 KB of LDS = one workgroup per CU, not worth it
@@ -948,59 +947,58 @@ hipError_t irbx_stamp_fetch(double* out) {
   out[kXStamps] = (double)(g_irbx_dbg_n / kXStamps);
   return hipSuccess;
 }
-void irbx_tune(int dbuf) {
-  if (dbuf >= 0) g_irbx_dbuf = dbuf;
-}
+void irbx_tune(int dbuf) { if (dbuf >= 0) g_irbx_dbuf = dbuf; }
 
-template <typename T, int KS, int NBW>
-static hipError_t launch_stats_cfg(const IrbxArgs& a, hipStream_t s) {
+// expand_stats (POOL = false) and expand_pool: the same scan of x, one workgroup per irbx_stats_rows(P) pixels of an image
+template <typename T, int KS, int NBW, bool POOL>
+static hipError_t launch_scan_cfg(const IrbxArgs& a, hipStream_t s) {
   const int P = a.H * a.W, RP = irbx_stats_rows(P);
-  static const std::string name = std::string("expand_stats_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) + ", " +
-                                  std::to_string(NBW) + ">";
+  static const std::string name = std::string(POOL ? "expand_pool_kernel<" : "expand_stats_kernel<") + TypeName<T>::value + ", " +
+                                  std::to_string(KS) + ", " + std::to_string(NBW) + ">";
   note_kernel(name.c_str());
-  hipLaunchKernelGGL((expand_stats_kernel<T, KS, NBW>), dim3(P / RP, 1, a.B), dim3(256), 0, s, a, RP);
+  constexpr auto kernel = POOL ? &expand_pool_kernel<T, KS, NBW> : &expand_stats_kernel<T, KS, NBW>;
+  hipLaunchKernelGGL(kernel, dim3(P / RP, 1, a.B), dim3(256), 0, s, a, RP);
   return hipGetLastError();
 }
-template <typename T>
-static hipError_t launch_stats_t(const IrbxArgs& a, hipStream_t s) {
-  const int Cin = a.c0 + a.c1;
-  if (Cin == 32 && a.Chid == 128) return launch_stats_cfg<T, 2, 1>(a, s);
-  if (Cin == 64 && a.Chid == 256) return launch_stats_cfg<T, 4, 2>(a, s);
-  if (Cin == 96 && a.Chid == 384) return launch_stats_cfg<T, 6, 3>(a, s);
+template <typename T, bool POOL>
+static hipError_t launch_scan_t(const IrbxArgs& a, hipStream_t s) {
+  switch (a.c0 + a.c1) {  // Chid = 4 Cin: irbx_supported
+    case 32: return launch_scan_cfg<T, 2, 1, POOL>(a, s);
+    case 64: return launch_scan_cfg<T, 4, 2, POOL>(a, s);
+    case 96: return launch_scan_cfg<T, 6, 3, POOL>(a, s);
+  }
   return hipErrorInvalidValue;
 }
 hipError_t launch_expand_stats(int dtype, const IrbxArgs& a, hipStream_t s) {
   if (!irbx_supported(dtype, a.c0 + a.c1, a.c0, a.Chid, a.H, a.W) || (a.c1 && !a.x1) || !a.stats) return hipErrorInvalidValue;
-  if (a.Chid != 4 * (a.c0 + a.c1)) return hipErrorInvalidValue;
-  return dtype == 1 ? launch_stats_t<half_t>(a, s) : launch_stats_t<bf16_t>(a, s);
-}
-
-template <typename T, int KS, int NBW>
-static hipError_t launch_pool_cfg(const IrbxArgs& a, hipStream_t s) {
-  const int P = a.H * a.W, RP = irbx_stats_rows(P);
-  static const std::string name = std::string("expand_pool_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) + ", " +
-                                  std::to_string(NBW) + ">";
-  note_kernel(name.c_str());
-  hipLaunchKernelGGL((expand_pool_kernel<T, KS, NBW>), dim3(P / RP, 1, a.B), dim3(256), 0, s, a, RP);
-  return hipGetLastError();
-}
-template <typename T>
-static hipError_t launch_pool_t(const IrbxArgs& a, hipStream_t s) {
-  switch (a.c0 + a.c1) {
-    case 32: return launch_pool_cfg<T, 2, 1>(a, s);
-    case 64: return launch_pool_cfg<T, 4, 2>(a, s);
-    case 96: return launch_pool_cfg<T, 6, 3>(a, s);
-  }
-  return hipErrorInvalidValue;
+  return dtype == 1 ? launch_scan_t<half_t, false>(a, s) : launch_scan_t<bf16_t, false>(a, s);
 }
 // pool_tot += the image's SE pool totals (fixed point, kPoolFixScale); the caller zeroes it
 hipError_t launch_expand_pool(int dtype, const IrbxArgs& a, hipStream_t s) {
   if (!irbx_supported(dtype, a.c0 + a.c1, a.c0, a.Chid, a.H, a.W) || (a.c1 && !a.x1) || !a.pool_tot || !a.as2 || !a.ab2 || !a.wd)
     return hipErrorInvalidValue;
-  return dtype == 1 ? launch_pool_t<half_t>(a, s) : launch_pool_t<bf16_t>(a, s);
+  return dtype == 1 ? launch_scan_t<half_t, true>(a, s) : launch_scan_t<bf16_t, true>(a, s);
 }
 
+// Dynamic LDS of expand_dw_body, in the order of its layout comment (at `smem`): sH (twice when double-buffered), sX, the packed
+// depthwise weights, aff2, aff1, then `red` (2 x 256 floats) + the pool totals where they live in LDS (KS <= 4; the identity
+// project tail keeps the gate there) or, skip tail (PCO != 16 KS), `red` (8 PCO floats) + the gate (Chid floats)
+constexpr size_t irbx_lds_bytes(int KS, int Chid, bool dbuf, int PCO) {
+  const size_t body = (size_t)(dbuf ? 2 : 1) * kXNPB * 32 * SHP + (size_t)kXNPB * 32 * (16 * KS + 8) * 2 + (size_t)10 * Chid * 2 +
+                      (size_t)2 * Chid * 4 + (size_t)2 * 16 * KS * 4;
+  if (PCO != 0 && PCO != 16 * KS) return body + (size_t)8 * PCO * 4 + (size_t)Chid * 4;
+  return body + 2 * 256 * 4 + (KS <= 4 ? (size_t)KS * 64 * 8 : 0);
+}
+// 96 -> 32: 256 B short of what two workgroups per CU allow (profiles/r08/README.md)
+static_assert(irbx_lds_bytes(6, 384, false, 32) == 81664 && irbx_lds_bytes(6, 384, false, 32) <= 80 * 1024, "expand_dw_project<6, 32>: two workgroups per CU");
+
 constexpr int kXTilesPerWg = 4;  // longest run of tiles along x one workgroup takes
+// tiles per workgroup: a run along x (neighbouring halo columns hit L1), as long as the launch keeps >= 2048 workgroups
+static int irbx_tiles_per_wg(const IrbxArgs& a) {
+  int tpw = kXTilesPerWg;
+  while (tpw > 1 && ((a.W / kXT_W) % tpw || (long)(irbx_pool_tiles(a.H, a.W) / tpw) * a.B < 2048)) tpw >>= 1;
+  return tpw;
+}
 
 template <typename T, int KS, bool DBUF, bool STAMP, bool NTST>
 static hipError_t launch_dw_one(const IrbxArgs& a, dim3 grid, size_t lds, int tpw, int cpw, hipStream_t s) {
@@ -1012,12 +1010,9 @@ static hipError_t launch_dw_one(const IrbxArgs& a, dim3 grid, size_t lds, int tp
 }
 template <typename T, int KS, bool DBUF>
 static hipError_t launch_dw_cfg(const IrbxArgs& a, hipStream_t s) {
-  const size_t lds = (size_t)(DBUF ? 2 : 1) * kXNPB * 32 * SHP + (size_t)kXNPB * 32 * (16 * KS + 8) * 2 + (size_t)10 * a.Chid * 2 +
-                     (size_t)2 * a.Chid * 4 + (size_t)2 * 16 * KS * 4 + 2 * 256 * 4 + (KS <= 4 ? (size_t)KS * 64 * 8 : 0);
+  const size_t lds = irbx_lds_bytes(KS, a.Chid, DBUF, 0);
   const int ntiles = irbx_pool_tiles(a.H, a.W), nchunks = a.Chid / 64;
-  // tiles per workgroup: a run along x (neighbouring halo columns hit L1), as long as the launch keeps >= 2048 workgroups
-  int tpw = kXTilesPerWg;
-  while (tpw > 1 && ((a.W / kXT_W) % tpw || (long)(ntiles / tpw) * a.B < 2048)) tpw >>= 1;
+  int tpw = irbx_tiles_per_wg(a);
   // channel chunks per workgroup: all of them (x tile loaded once) unless the launch would be too small
   int cpw = nchunks;
   while (cpw > 1 && (long)(ntiles / tpw) * a.B * (nchunks / cpw) < 1024 && cpw % 2 == 0) cpw >>= 1;
@@ -1055,29 +1050,17 @@ static hipError_t launch_dw_t(const IrbxArgs& a, hipStream_t s) {
   const int Cin = a.c0 + a.c1;
   // llie_tune("irbx_dbuf", 1): double-buffered h1 tile for the 32-channel inputs (one barrier per chunk, 76 KB of LDS = two
   // workgroups per CU).  The single-buffered kernel (49 KB, three workgroups per CU) is the default: 1 % faster end to end
-  if (g_irbx_dbuf) {
-    switch (Cin) {
-      case 32: return launch_dw_cfg<T, 2, true>(a, s);
-      case 64: return launch_dw_cfg<T, 4, false>(a, s);
-      case 96: return launch_dw_cfg<T, 6, false>(a, s);
-    }
-  } else {
-    switch (Cin) {
-      case 32: return launch_dw_cfg<T, 2, false>(a, s);
-      case 64: return launch_dw_cfg<T, 4, false>(a, s);
-      case 96: return launch_dw_cfg<T, 6, false>(a, s);
-    }
+  switch (Cin) {
+    case 32: return g_irbx_dbuf ? launch_dw_cfg<T, 2, true>(a, s) : launch_dw_cfg<T, 2, false>(a, s);
+    case 64: return launch_dw_cfg<T, 4, false>(a, s);
+    case 96: return launch_dw_cfg<T, 6, false>(a, s);
   }
   return hipErrorInvalidValue;
 }
 template <typename T, int KS, int PCO>
 static hipError_t launch_project_cfg(const IrbxArgs& a, hipStream_t s) {
-  // [sH][sX][wds][aff2][aff1], then red (2 x 256 floats) + the pool totals' place (gate), or, skip form, red (8 PCO floats) + gate
-  const size_t lds = (size_t)kXNPB * 32 * SHP + (size_t)kXNPB * 32 * (16 * KS + 8) * 2 + (size_t)10 * a.Chid * 2 + (size_t)2 * a.Chid * 4 +
-                     (size_t)2 * 16 * KS * 4 + (PCO == 16 * KS ? 2 * 256 * 4 + (size_t)KS * 64 * 8 : (size_t)8 * PCO * 4 + (size_t)a.Chid * 4);
-  const int ntiles = irbx_pool_tiles(a.H, a.W);
-  int tpw = kXTilesPerWg;  // as launch_dw_cfg; every workgroup takes all channel chunks (y accumulates over them)
-  while (tpw > 1 && ((a.W / kXT_W) % tpw || (long)(ntiles / tpw) * a.B < 2048)) tpw >>= 1;
+  const size_t lds = irbx_lds_bytes(KS, a.Chid, false, PCO);
+  const int ntiles = irbx_pool_tiles(a.H, a.W), tpw = irbx_tiles_per_wg(a);  // every workgroup takes all channel chunks (y accumulates over them)
   static const std::string name = std::string("expand_dw_project_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) +
                                   (PCO == 16 * KS ? std::string() : ", " + std::to_string(PCO)) + ">";
   note_kernel(name.c_str());

@@ -572,7 +572,7 @@ int llie_params_loaded(const llie_ctx* c) {
 // engine != 0: what the engine's own kernel selection has to move -- blocks that run in the recompute form (irbx.hip)
 // read x three times and never store h1: (3Cin + 2Chid + Cout) P (SURVEY.md 8d "recompute variant").  x0c = channels of
 // the first input segment of the first block (virtual concat), 0 = none.  Blocks that also take the project form
-// (irb_project_form: h2 stays on chip) move (4Cin + Cout) P: x is read by the statistics pass, the pool pass, the main pass and
+// (irb_path: h2 stays on chip) move (4Cin + Cout) P: x is read by the statistics pass, the pool pass, the main pass and
 // the shortcut, y is written.
 static void count_blocks(const llie_ctx* c, const std::vector<Block>& bl, int64_t P, int64_t& elems, int64_t& flops, int engine = 0,
                          int x0c = 0) {
@@ -581,12 +581,10 @@ static void count_blocks(const llie_ctx* c, const std::vector<Block>& bl, int64_
     if (b.kind == 0) {
       const IrbW& w = c->irbs[b.idx];
       const int S = (int)std::lround(std::sqrt((double)P));
-      const bool fx = engine && g_knobs.use_irbx && w.hid == w.hid_r && w.cin == w.cin_r &&
-                      irbx_supported(c->dt, w.cin, (first && x0c) ? x0c : w.cin, w.hid, S, S);
-      const bool fp = fx && irb_project_form(c->dt, w, (first && x0c) ? x0c : w.cin, S, S) != 0;
+      const IrbForm form = engine ? irb_path(c->dt, w, (first && x0c) ? x0c : w.cin, S, S, false).form : kIrbUnfused;
       first = false;
-      if (fp) elems += (4LL * w.cin + w.cout) * P;
-      else if (fx) elems += (3LL * w.cin + 2LL * w.hid + w.cout) * P;
+      if (form == kIrbProject) elems += (4LL * w.cin + w.cout) * P;
+      else if (form == kIrbRecompute) elems += (3LL * w.cin + 2LL * w.hid + w.cout) * P;
       else elems += (2LL * w.cin + 4LL * w.hid + w.cout) * P;
       flops += 2LL * P * ((int64_t)w.cin * w.hid + 9LL * w.hid + (int64_t)w.hid * w.cout + (w.skip ? (int64_t)w.cin * w.cout : 0));
     } else {
