@@ -35,6 +35,7 @@ EXPORTS = [
     "llie_final_bwd_data",
     "llie_tile_count", "llie_tile_origins", "llie_tile_gather_u8", "llie_tile_gather_f32", "llie_tile_blend_u8",
     "llie_aug_pair_u8", "llie_aug_synth_u8",
+    "llie_upconv_fold_elems", "llie_upconv_fold_weights", "llie_conv3x3_upfold", "llie_conv3x3_upfold_tiles",
     "llie_expand_dw", "llie_expand_pool", "llie_expand_dw_project", "llie_expand_dw_project_skip", "llie_irbx_project_tiles",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
@@ -167,6 +168,11 @@ def lib() -> C.CDLL:
     L.llie_groupnorm_finalize.argtypes = [vp, ci, ci, vp, ci, ci, ci, ci, vp, vp, vp, i64, C.c_float, C.c_float, ci, vp, vp, vp]
     L.llie_conv3x3.argtypes = [ci, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
     L.llie_conv3x3_tiles.argtypes = [ci, ci]
+    L.llie_upconv_fold_elems.argtypes = [ci]
+    L.llie_upconv_fold_elems.restype = i64
+    L.llie_upconv_fold_weights.argtypes = [ci, vp, vp, ci, vp]
+    L.llie_conv3x3_upfold.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
+    L.llie_conv3x3_upfold_tiles.argtypes = [ci, ci]
     L.llie_linattn.argtypes = [ci, vp, vp, vp, ci, ci, ci, vp]
     L.llie_linattn_splits.argtypes = [ci]
     L.llie_se_mlp.argtypes = [ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]

@@ -849,6 +849,302 @@ static hipError_t launch_conv_t(const Conv3Args& a, hipStream_t s) {
   return launch_conv_cfg<T, MODE, 8, 32, 2, 1>(a, s);
 }
 
+// =============================================================================================
+// Up-sampling conv with the bilinear x2 folded into the weights (small.hip: upconv_fold_kernel, kernels.h: the blob's layout).
+// Output pixel (2i + a, 2j + b) is a 3x3 conv, with the weights of phase (a, b), of the LOW-resolution input replicate-padded by
+// one pixel: a stride-1 implicit GEMM with M = 8 x 16 low-resolution pixels, N = 128 (phase, cout) pairs, K = 9 taps x Cin.
+// The 10 x 18 patch of a 32-channel chunk is a plain clamped copy -- no blend, a sixteenth of the loads per output of
+// conv3x3_kernel's MODE 1.  An N tile never mixes row phases: one phase x 128 outputs, or (C64: Cout = 64) one row phase x both
+// column phases x 64 outputs, where a wave column (wn) is one column phase.  Either way a low-resolution pixel's 128 columns
+// are 256 contiguous bytes of the output.
+// The outermost ring of the output, where the conv's zero padding must win over the replicate clamp, takes correction terms as
+// extra k-steps ("taps" 9..15) into the same accumulators: three on the centre patch row for pixels of the image's first
+// (a = 0) / last (a = 1) row, three on the centre column for its first / last column, one for the corner.  A lane whose pixel
+// is not on that edge reads an all-zero patch pixel instead; workgroups that touch no edge run nine steps, and a wave skips
+// the MFMAs of 32-row blocks without such a pixel.  Skipped and zero terms add exactly 0, so every pixel sees one fixed
+// summation order: bitwise reproducible and batch invariant like the kernel above.
+// Statistics: one slab entry per (low-resolution tile, phase): entry tile * 4 + phase.
+// Workgroup order: edge workgroups run up to 16 steps per chunk where the others run 9, and a launch is only a few rounds of
+// workgroups deep, so the heaviest go first (both edges, then one edge, then none) and the light ones fill the tail.
+struct UpfoldStep { int kind, toff, sbase, cnt, k; };  // kind 0 interior tap, 1 row edge, 2 column edge, 3 corner
+template <typename T, bool C64>
+__global__ void __launch_bounds__(256) conv3x3_upfold_kernel(const Conv3Args a) {
+  constexpr int NT = 256, WN = 2, TH = 8, TW = 16, BN = 128, MI = 2, NI = 2;
+  constexpr int VEC = Elem<T>::VEC, VPR = 32 / VEC, PITCH = TilePitch<T>::value;
+  constexpr int PH = TH + 2, PW = TW + 2, ZP = PH * PW;  // patch pixel ZP is all zero
+  constexpr int B_PER = BN * VPR / NT;
+  constexpr int CP = BN + 4;
+  typedef typename Elem<T>::vec_t vec_t;
+  static_assert(VEC == 8 && B_PER * NT == BN * VPR, "2-byte types only");
+
+  extern __shared__ __align__(16) unsigned char smem[];
+  T* sP = reinterpret_cast<T*>(smem);   // [PH * PW + 1][PITCH]
+  T* sB = sP + (ZP + 1) * PITCH;        // [2][BN][PITCH]
+  float* sC = reinterpret_cast<float*>(smem);
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave / WN, wn = wave % WN;
+  const int H = a.Hi, W = a.Wi, Ho = 2 * H, Wo = 2 * W, C = a.Cin;
+  const int tiles_x = W / TW, tiles = tiles_x * (H / TH);
+  const int nb = C / BN;
+  // blockIdx = (t * B + image) * cout blocks + cout block; t enumerates (row combination r, column combination c), heaviest first.
+  // r: (row phase, tile row) -- 0 = (0, first) and 1 = (1, last) are the two that touch an image row edge; c likewise for
+  // (column phase, tile column), or (C64: both column phases in one workgroup) the tile column alone, first and last touching.
+  const int TY = H / TH, TX = tiles_x;
+  const int NR = 2 * TY, NC = C64 ? TX : 2 * TX, HC = C64 && TX == 1 ? 1 : 2, nbk = C64 ? 1 : nb;
+  int bid = blockIdx.x;
+  const int nblk = bid % nbk; bid /= nbk;
+  const int b = bid % a.B, t = bid / a.B;
+  int r, c;
+  {
+    const int n_rc = 2 * HC, n_r = 2 * (NC - HC), n_c = (NR - 2) * HC;
+    if (t < n_rc) { r = t / HC; c = t % HC; }
+    else if (t < n_rc + n_r) { r = (t - n_rc) & 1; c = HC + ((t - n_rc) >> 1); }
+    else if (t < n_rc + n_r + n_c) { r = 2 + (t - n_rc - n_r) / HC; c = (t - n_rc - n_r) % HC; }
+    else { r = 2 + (t - n_rc - n_r - n_c) / (NC - HC); c = HC + (t - n_rc - n_r - n_c) % (NC - HC); }
+  }
+  const int pa = r < 2 ? r : (r - 2 < TY - 1 ? 0 : 1);                                   // row phase
+  const int ty = r < 2 ? r * (TY - 1) : (r - 2 < TY - 1 ? r - 1 : r - 2 - (TY - 1));
+  const int pb = C64 ? 0 : (c < 2 ? c : (c - 2 < TX - 1 ? 0 : 1));                       // column phase (of column 0)
+  const int tx = C64 ? (c == 0 ? 0 : (c == 1 ? TX - 1 : c - 1)) : (c < 2 ? c * (TX - 1) : (c - 2 < TX - 1 ? c - 1 : c - 2 - (TX - 1)));
+  const int tile = ty * TX + tx;
+  const int iy0 = ty * TH, ix0 = tx * TW;
+  const int phase0 = pa * 2 + pb;   // phase a * 2 + b of column 0 (C64: columns 64.. are phase0 + 1)
+  const int n0 = nblk * BN;
+  const int pbw = C64 ? wn : pb;  // column phase of this wave
+  const int kv = (tid % VPR) * VEC;
+  const T* in = reinterpret_cast<const T*>(a.in) + (size_t)b * H * W * C;
+  const T* wbase = reinterpret_cast<const T*>(a.w);
+
+  // which edges this workgroup / this wave touches
+  const bool row_touch = pa == 0 ? iy0 == 0 : iy0 + TH == H;
+  const bool col0 = ix0 == 0, col1 = ix0 + TW == W;
+  const bool wg_col = C64 ? (col0 || col1) : ((phase0 & 1) ? col1 : col0);
+  const bool wave_col = pbw ? col1 : col0;
+  const int ie = pa ? TH - 1 : 0, je = pbw ? TW - 1 : 0;  // the edge pixels' tile coordinates
+  const int nsteps = 9 + (row_touch ? 3 : 0) + (wg_col ? 3 : 0) + (row_touch && wg_col ? 1 : 0);
+  auto decode = [&](int st) {
+    if (st < 9) return UpfoldStep{0, ((st / 3) * PW + st % 3) * PITCH, 0, 9, st};
+    st -= 9;
+    if (row_touch) {
+      if (st < 3) return UpfoldStep{1, (PW + st) * PITCH, 36, 3, st};
+      st -= 3;
+    }
+    if (st < 3) return UpfoldStep{2, (st * PW + 1) * PITCH, 48, 3, st};
+    return UpfoldStep{3, (PW + 1) * PITCH, 60, 1, 0};
+  };
+
+  f32x16 acc[MI][NI];
+#pragma unroll
+  for (int i = 0; i < MI; ++i)
+#pragma unroll
+    for (int j = 0; j < NI; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+  // GEMM row m of a tile is pixel (m / 16, (m % 16 + 14 (m / 16 & 1)) % 16): odd tile rows rotated by two pixels, which keeps the
+  // A reads conflict-free on the 18-pixel patch rows (see conv3x3_kernel, MODE 1)
+  auto tile_px = [](int m, int& py, int& px) {
+    py = m / TW;
+    px = ((m % TW) + 14 * (py & 1)) & 15;
+  };
+  const int zoff = ZP * PITCH + (lane >> 5) * 16;
+  int arow[MI], amask[MI], bmask[MI];  // amask: bit k = this lane's pixel takes part in steps of kind k; bmask: some pixel of the block does
+#pragma unroll
+  for (int i = 0; i < MI; ++i) {
+    const int blk = wm * MI + i;
+    int py, px;
+    tile_px(blk * 32 + (lane & 31), py, px);
+    arow[i] = (py * PW + px) * PITCH + (lane >> 5) * 16;
+    const bool lr = row_touch && py == ie, lc = wave_col && px == je;
+    amask[i] = 1 | (lr ? 2 : 0) | (lc ? 4 : 0) | (lr && lc ? 8 : 0);
+    const bool br = row_touch && (ie >> 1) == blk;  // a block is two tile rows; every block holds a pixel of each column
+    bmask[i] = 1 | (br ? 2 : 0) | (wave_col ? 4 : 0) | (br && wave_col ? 8 : 0);
+  }
+
+  vec_t rb[B_PER];
+  auto prefetch_w = [&](const UpfoldStep& st, int c0) {
+#pragma unroll
+    for (int i = 0; i < B_PER; ++i) {
+      const int n = (tid + i * NT) / VPR;
+      const int phase = C64 ? phase0 + (n >> 6) : phase0, co = C64 ? (n & 63) : n0 + n;
+      rb[i] = ld_vec<T>(wbase + ((size_t)(st.sbase + phase * st.cnt + st.k) * C + co) * C + c0 + kv);
+    }
+  };
+  auto stage_w = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < B_PER; ++i) st_vec<T>(sB + buf * (BN * PITCH) + ((tid + i * NT) / VPR) * PITCH + kv, rb[i]);
+  };
+
+  // the patch of one chunk: loads issued one chunk ahead, kept raw in registers during the current chunk's steps
+  constexpr int P_ITEMS = (PH * PW * VPR + NT - 1) / NT;
+  vec_t praw[P_ITEMS];
+  auto issue_patch = [&](int c0) {
+#pragma unroll
+    for (int it = 0; it < P_ITEMS; ++it) {
+      const int i = tid + it * NT;
+      if (i < PH * PW * VPR) {
+        const int pix = i / VPR;
+        const int gy = min(max(iy0 - 1 + pix / PW, 0), H - 1), gx = min(max(ix0 - 1 + pix % PW, 0), W - 1);  // replicate padding
+        praw[it] = ld_vec<T>(in + ((size_t)gy * W + gx) * C + c0 + kv);
+      }
+    }
+  };
+  auto commit_patch = [&]() {
+#pragma unroll
+    for (int it = 0; it < P_ITEMS; ++it) {
+      const int i = tid + it * NT;
+      if (i < PH * PW * VPR) st_vec<T>(sP + (i / VPR) * PITCH + kv, praw[it]);
+    }
+  };
+  if (tid < VPR) {
+    vec_t z;
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) z[e] = (T)0.f;
+    st_vec<T>(sP + ZP * PITCH + kv, z);
+  }
+
+  const int anyb = bmask[0] | bmask[1];  // bit k: this wave has MFMAs in steps of kind k
+  auto run_step = [&](int st, const UpfoldStep& cur, int c0) {
+    if ((anyb >> cur.kind) & 1) {
+      T fa[MI][16], fb[NI][16];
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        if (!((bmask[i] >> cur.kind) & 1)) continue;
+        const T* p = sP + (((amask[i] >> cur.kind) & 1) ? arow[i] + cur.toff : zoff);
+#pragma unroll
+        for (int q = 0; q < 16 / VEC; ++q) *reinterpret_cast<vec_t*>(&fa[i][q * VEC]) = *reinterpret_cast<const vec_t*>(p + q * VEC);
+      }
+#pragma unroll
+      for (int j = 0; j < NI; ++j) {
+        const T* p = sB + (st & 1) * (BN * PITCH) + ((wn * NI + j) * 32 + (lane & 31)) * PITCH + (lane >> 5) * 16;
+#pragma unroll
+        for (int q = 0; q < 16 / VEC; ++q) *reinterpret_cast<vec_t*>(&fb[j][q * VEC]) = *reinterpret_cast<const vec_t*>(p + q * VEC);
+      }
+#pragma unroll
+      for (int i = 0; i < MI; ++i) {
+        if (!((bmask[i] >> cur.kind) & 1)) continue;
+#pragma unroll
+        for (int j = 0; j < NI; ++j) Mfma<T>::chunk(fa[i], fb[j], acc[i][j]);
+      }
+    }
+    if (st + 1 < nsteps) {
+      stage_w((st + 1) & 1);  // its last readers finished before the previous barrier
+      if (st + 2 < nsteps) prefetch_w(decode(st + 2), c0);
+    }
+    wg_barrier();  // next W tile visible; everyone done with this one (and, after the last step, with the patch)
+  };
+
+  issue_patch(0);
+  for (int c0 = 0; c0 < C; c0 += 32) {
+    prefetch_w(decode(0), c0);
+    commit_patch();
+    stage_w(0);
+    prefetch_w(decode(1), c0);
+    wg_barrier();  // patch and W tile of step 0 visible
+    if (c0 + 32 < C) issue_patch(c0 + 32);
+#pragma unroll
+    for (int st = 0; st < 9; ++st) run_step(st, decode(st), c0);
+    for (int st = 9; st < nsteps; ++st) run_step(st, decode(st), c0);
+  }
+
+  // ---- epilogue: conv3x3_kernel's, with the phase in the output address and in the slab entry
+  constexpr int VR = BN / VEC, RPP = NT / VR, SROWS = 2 * 32;
+  const int cv = tid % VR, r0 = tid / VR;
+  const int ephase = C64 ? phase0 + (cv * VEC >> 6) : phase0, ech = C64 ? (cv * VEC & 63) : n0 + cv * VEC;  // of this thread's columns
+  float bias[VEC], s1[VEC], s2[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) {
+    bias[e] = a.bias ? a.bias[ech + e] : 0.f;
+    s1[e] = 0.f;
+    s2[e] = 0.f;
+  }
+  T* outp = reinterpret_cast<T*>(a.out) + (size_t)b * Ho * Wo * C;
+#pragma unroll
+  for (int pi = 0; pi < MI; ++pi) {
+    if (pi) wg_barrier();
+#pragma unroll
+    for (int j = 0; j < NI; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int row = wm * 32 + mfma_row(r, lane);
+        const int col = (wn * NI + j) * 32 + (lane & 31);
+        sC[row * CP + col] = acc[pi][j][r];
+      }
+    wg_barrier();
+    for (int srow = r0; srow < SROWS; srow += RPP) {
+      const int row = ((srow >> 5) * MI + pi) * 32 + (srow & 31);  // pixel index inside the tile
+      float v[VEC];
+      const float* pc = sC + srow * CP + cv * VEC;
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) v[e] = pc[e] + bias[e];
+      int py, px;
+      tile_px(row, py, px);
+      const int oy = 2 * (iy0 + py) + pa, ox = 2 * (ix0 + px) + (ephase & 1);
+      vec_t ov = f32_to_vec<T>(v);
+      st_vec_pol<T>(outp + ((size_t)oy * Wo + ox) * C + ech, ov, a.nt != 0);
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        const float q = (float)ov[e];
+        s1[e] += q;
+        s2[e] += q * q;
+      }
+    }
+  }
+  if (a.stats) {
+#pragma unroll
+    for (int o = VR; o < 64; o <<= 1)
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        s1[e] += __shfl_xor(s1[e], o, 64);
+        s2[e] += __shfl_xor(s2[e], o, 64);
+      }
+    float* red = sC + SROWS * CP;
+    constexpr int NW = NT / 64;
+    if (lane < VR) {
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) {
+        red[(wave * 2 + 0) * BN + cv * VEC + e] = s1[e];
+        red[(wave * 2 + 1) * BN + cv * VEC + e] = s2[e];
+      }
+    }
+    wg_barrier();
+    for (int i = tid; i < 2 * BN; i += NT) {
+      const int which = i / BN, c = i % BN;
+      float t = 0.f;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) t += red[(w * 2 + which) * BN + c];
+      const int phase = C64 ? phase0 + (c >> 6) : phase0, ch = C64 ? (c & 63) : n0 + c;
+      a.stats[((size_t)((b * tiles + tile) * 4 + phase) * 2 + which) * C + ch] = t;
+    }
+  }
+}
+
+bool conv3x3_upfold_ok(int dtype, int Hi, int Wi, int C) {
+  return (dtype == 1 || dtype == 2) && Hi > 0 && Wi > 0 && Hi % 8 == 0 && Wi % 16 == 0 && (C == 64 || (C > 0 && C % 128 == 0));
+}
+int conv3x3_upfold_ntiles(int Ho, int Wo) { return 4 * (Ho / 16) * (Wo / 32); }  // (low-resolution 8 x 16 tile, phase) pairs
+
+template <typename T, bool C64>
+static hipError_t launch_upfold_cfg(const Conv3Args& a, hipStream_t s) {
+  constexpr int PITCH = TilePitch<T>::value;
+  constexpr size_t tiles = (size_t)(10 * 18 + 1 + 2 * 128) * PITCH * sizeof(T);
+  constexpr size_t ctile = (size_t)64 * (128 + 4) * 4 + (size_t)4 * 2 * 128 * 4;
+  constexpr size_t lds = tiles > ctile ? tiles : ctile;
+  static_assert(lds <= 48 * 1024, "static LDS limit");
+  const unsigned grid = (unsigned)(a.B * (a.Hi / 8) * (a.Wi / 16) * (C64 ? 2 : 4 * (a.Cin / 128)));
+  static const std::string name = std::string("conv3x3_upfold_kernel<") + TypeName<T>::value + ", " + (C64 ? "64" : "128") + ">";
+  note_kernel(name.c_str());
+  hipLaunchKernelGGL((conv3x3_upfold_kernel<T, C64>), dim3(grid), dim3(256), lds, s, a);
+  return hipGetLastError();
+}
+// a.w = the folded blob (upconv_fold_elems(C) elements of the compute type); a.mode is ignored
+hipError_t launch_conv3x3_upfold(int dtype, const Conv3Args& a, hipStream_t s) {
+  if (a.Cin != a.Cout || a.B < 1 || !conv3x3_upfold_ok(dtype, a.Hi, a.Wi, a.Cin)) return hipErrorInvalidValue;
+  if (dtype == 1) return a.Cin == 64 ? launch_upfold_cfg<half_t, true>(a, s) : launch_upfold_cfg<half_t, false>(a, s);
+  return a.Cin == 64 ? launch_upfold_cfg<bf16_t, true>(a, s) : launch_upfold_cfg<bf16_t, false>(a, s);
+}
+
 hipError_t launch_conv3x3(int dtype, const Conv3Args& a, hipStream_t s) {
   if (a.mode < 0 || a.mode > 2) return hipErrorInvalidValue;
   switch (dtype) {

@@ -58,6 +58,9 @@ struct Param {
   bool has_f = false;
   size_t f_off = 0;
   float f_scale = 1.f;
+  // PK_CONV3 of an up-sampling conv, 2-byte engines: third copy = the 64 folded sets of conv3x3_upfold_kernel (launch_upconv_fold)
+  bool has_fold = false;
+  size_t fold_off = 0;
 };
 
 // cin / cout / hid are the PHYSICAL channel counts of the tensors (multiples of 32; hid of 64 for 2-byte types);
@@ -87,6 +90,8 @@ struct ConvW {
   size_t w, bias;
   size_t w_t;
   int i_w, i_bias;  // parameter indices, as in IrbW
+  bool has_fold = false;  // up-sampling convs of the 2-byte engines: bilinear x2 folded into per-phase weights (kernels.h)
+  size_t w_fold = 0;
 };
 struct Block {
   int kind;  // 0 irb, 1 attn
@@ -256,6 +261,7 @@ struct Knobs {
   int nt_mask;        // "nt_mask": 1 expand_dw, 2 pw_expand, 4 dwconv3x3, 8 project / attention GEMMs, 16 dense 3x3 convs
   int se_mfma;        // "se_mfma": SE MLP of the wide blocks as two MFMA launches; 0 = the row-parallel pair
   int bwd_async;      // "bwd_async": weight-gradient kernels of the backward pass on a side stream
+  int upconv_fold;    // "upconv_fold": up-sampling convs from folded weights wherever upconv_fold_supported(); 0 = blend in the kernel
   int enhance_split;  // "enhance_split": concurrent branches of the captured enhance graph (< 2: a single chain)
   int epoch;          // llie_tune calls so far: keys the graph cache and the zero-region sizes, which bake kernel choices in
 };
@@ -293,6 +299,16 @@ inline IrbPath irb_path(int dt, const IrbW& w, int c0, int H, int W, bool traini
   // knob "irbx_project" = 2 keeps the identity-residual shapes only
   p.form = tail && !(tail == kIrbxProjectSkip && g_knobs.irbx_project == 2) ? kIrbProject : kIrbRecompute;
   return p;
+}
+
+// The up-sampling conv of an inference forward (forward.cpp: Run::conv3) runs from the folded weights (conv3x3_upfold_kernel: no
+// bilinear blend in the kernel) on 2-byte engines, for maps of whole 8 x 16 low-resolution tiles, at C = 64 and C = 128: the
+// channel counts measured faster than conv3x3_kernel's mode 1 in every pair (profiles/r10; C = 256 at 32 x 32 was 5 % slower --
+// there a quarter more k-steps go to the border corrections -- and keeps the blending kernel).  So do the fp32 engine, ragged
+// maps, the training forward (it keeps the up-sampled tensor) and llie_conv3x3.  A rule on the layer, the map and the knobs
+// alone, never on the batch.
+inline bool upconv_fold_supported(int dt, int Hi, int Wi, int C) {
+  return g_knobs.upconv_fold && (C == 64 || C == 128) && conv3x3_upfold_ok(dt, Hi, Wi, C);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -366,7 +366,9 @@ struct Run : Exec {
 
   Tens conv3(const ConvW& w, const Tens& x, int mode) {
     const int Ho = mode == 0 ? x.H / 2 : x.H * 2, Wo = mode == 0 ? x.W / 2 : x.W * 2;
-    Tens y = new_tens(w.c, Ho, Wo, conv3x3_ntiles(Ho, Wo), w.c_r);
+    // up-sampling convs of an inference forward run from the folded weights wherever the rule of engine.h says so
+    const bool fold = mode == 1 && !tape && w.has_fold && upconv_fold_supported(dt, x.H, x.W, w.c);
+    Tens y = new_tens(w.c, Ho, Wo, fold ? conv3x3_upfold_ntiles(Ho, Wo) : conv3x3_ntiles(Ho, Wo), w.c_r);
     Tens u;
     snprintf(tag, sizeof tag, "conv3 mode=%d C=%d %dx%d", mode, w.c, x.H, x.W);
     if (tape && mode == 1) {
@@ -381,11 +383,13 @@ struct Run : Exec {
       a.B = B; a.Hi = in.H; a.Wi = in.W; a.Cin = w.c; a.Cout = w.c; a.mode = u.valid ? 2 : mode;
       if (u.valid) {
         chk(launch_upsample2x(dt, p(x.off), p(u.off), B, x.H, x.W, w.c, s));
-        chk(launch_conv3x3(dt, a, s));
+        timed(LLIE_K_CONV3, (2LL * B * w.c * Ho * Wo + 9LL * w.c * w.c) * (int64_t)es(), [&] { return launch_conv3x3(dt, a, s); });
       } else {
         a.nt = nt_store(16, (int64_t)B * Ho * Wo * w.c);
+        if (fold) a.w = wptr(w.w_fold);
+        // the algorithmic bytes charge the 9 C^2 source weights in either form (the folded blob is 64 C^2)
         timed(LLIE_K_CONV3, ((int64_t)B * w.c * ((int64_t)x.H * x.W + (int64_t)Ho * Wo) + 9LL * w.c * w.c) * (int64_t)es(),
-              [&] { return launch_conv3x3(dt, a, s); });
+              [&] { return fold ? launch_conv3x3_upfold(dt, a, s) : launch_conv3x3(dt, a, s); });
       }
     }
     if (tape) {

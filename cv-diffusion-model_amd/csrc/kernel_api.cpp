@@ -103,6 +103,19 @@ int llie_conv3x3(int dtype, int mode, const void* in, const void* w, const float
   return kerr("conv3x3", launch_conv3x3(dtype, a, hs(stream)));
 }
 int llie_conv3x3_tiles(int Ho, int Wo) { return conv3x3_ntiles(Ho, Wo); }
+int64_t llie_upconv_fold_elems(int C) { return C > 0 ? (int64_t)upconv_fold_elems(C) : LLIE_ERR_ARG; }
+int llie_upconv_fold_weights(int dtype, const float* w_oihw, void* folded, int C, llie_stream stream) {
+  if (!w_oihw || !folded || C < 1 || (dtype != 1 && dtype != 2)) return LLIE_ERR_ARG;
+  return kerr("upconv_fold_weights", launch_upconv_fold(dtype, w_oihw, folded, C, hs(stream)));
+}
+int llie_conv3x3_upfold(int dtype, const void* in, const void* folded, const float* bias, void* out, float* stats, int batch, int Hi, int Wi,
+                        int C, llie_stream stream) {
+  if (!in || !folded || !out || (dtype != 1 && dtype != 2)) return LLIE_ERR_ARG;
+  Conv3Args a{};
+  a.in = in; a.w = folded; a.bias = bias; a.out = out; a.stats = stats; a.B = batch; a.Hi = Hi; a.Wi = Wi; a.Cin = C; a.Cout = C; a.mode = 1;
+  return kerr("conv3x3_upfold", launch_conv3x3_upfold(dtype, a, hs(stream)));
+}
+int llie_conv3x3_upfold_tiles(int Ho, int Wo) { return conv3x3_upfold_ntiles(Ho, Wo); }
 int llie_linattn_splits(int N) { return linattn_nsplit(N); }
 int llie_linattn(int dtype, const void* qkv, float* kv_scratch, void* out, int batch, int N, int heads, llie_stream stream) {
   if (!qkv || !kv_scratch || !out || dtype < 0 || dtype > 2 || batch <= 0 || N <= 0 || heads <= 0) return LLIE_ERR_ARG;

@@ -282,6 +282,19 @@ void conv3x3_stamp(int v);
 hipError_t conv3x3_stamp_fetch(double* out8);  // 7 per-wave cycle sums (conv.hip: STAMP) + waves averaged
 hipError_t launch_conv3x3(int dtype, const Conv3Args& a, hipStream_t s);
 int conv3x3_ntiles(int Ho, int Wo);
+//   the up-sampling conv (mode 1) from folded weights: the fixed bilinear x2 lives in per-phase 3x3 weights on the low-resolution
+//   input, so the kernel blends nothing (conv.hip: conv3x3_upfold_kernel).  Cin == Cout == C; `w` = the folded blob of
+//   launch_upconv_fold: 64 sets of [Cout][Cin] T, phase p = 2 a + b for output pixels (2i + a, 2j + b):
+//     set p * 9 + r * 3 + s   interior tap (r, s) on the replicate-padded input
+//     set 36 + p * 3 + s      row-edge correction (already negated), first (a = 0) / last (a = 1) image row
+//     set 48 + p * 3 + r      column-edge correction (already negated), first (b = 0) / last (b = 1) image column
+//     set 60 + p              corner correction
+//   stats: [B][conv3x3_upfold_ntiles(Ho, Wo)][2][C]
+bool conv3x3_upfold_ok(int dtype, int Hi, int Wi, int C);  // the kernel's contract: 2-byte dtype, Hi % 8 == 0, Wi % 16 == 0, C = 64 or a multiple of 128
+hipError_t launch_conv3x3_upfold(int dtype, const Conv3Args& a, hipStream_t s);
+int conv3x3_upfold_ntiles(int Ho, int Wo);
+constexpr int kUpconvFoldSets = 64;
+inline size_t upconv_fold_elems(int C) { return (size_t)kUpconvFoldSets * C * C; }
 
 // Linear attention core (efficient_unet.py:288-302) on qkv NHWC [B][N][3*inner].
 struct AttnArgs {
@@ -315,6 +328,9 @@ hipError_t launch_cvt_rows(int dtype, const float* src, void* dst, int rows, int
                            hipStream_t s);                       // dst[r*ld + col0 + c] = T(src[r*cols + c])
 hipError_t launch_repack_conv3x3(int dtype, const float* src, void* dst, int Cout, int Cin, hipStream_t s, int Op = 0,
                                  int Ip = 0);  // OIHW -> [9][Op][Ip] (Op, Ip: padded destination dims, 0 = unpadded)
+// OIHW [C][C][3][3] fp32 -> the 64 folded sets of the up-sampling conv (layout above): fp64 arithmetic, one rounding to the compute
+// dtype (1 or 2).  `state` as in launch_load_all: with one, a no-op when the parameters did not change.
+hipError_t launch_upconv_fold(int dtype, const float* src, void* dst, int C, hipStream_t s, const unsigned long long* state = nullptr);
 hipError_t launch_repack_dw(const float* src, float* dst, int C, hipStream_t s, int Cp = 0);                 // [C][1][3][3] -> [9][Cp]
 hipError_t launch_repack_dw_flip(const float* src, float* dst, int C, hipStream_t s, int Cp = 0);            // [C][1][3][3] -> [8-tap][Cp]
 hipError_t launch_repack_init(const float* src, float* dst, int O, int I, hipStream_t s, int Op = 0);        // OIHW -> [I*9][Op]

@@ -141,7 +141,7 @@ struct Builder {
     c->attns.push_back(w);
     return (int)c->attns.size() - 1;
   }
-  ConvW add_conv3(const std::string& p, int ch_r) {
+  ConvW add_conv3(const std::string& p, int ch_r, bool up = false) {
     ConvW w{};
     const int ch = pad32(ch_r);
     if (ch != ch_r) c->padded = true;
@@ -149,7 +149,12 @@ struct Builder {
     w.w = reserve((size_t)9 * ch * ch * es());
     w.w_t = reserve((size_t)9 * ch * ch * es());
     { Param& q = add(p + ".weight", (int64_t)ch_r * ch_r * 9, PK_CONV3, w.w, &w.i_w); q.O = ch_r; q.I = ch_r; q.Op = ch; q.Ip = ch;
-      set_shape(q, {ch_r, ch_r, 3, 3}); q.has_t = true; q.t_off = w.w_t; }
+      set_shape(q, {ch_r, ch_r, 3, 3}); q.has_t = true; q.t_off = w.w_t;
+      if (up && c->dt != LLIE_F32 && ch == ch_r) {  // the folded sets of conv3x3_upfold_kernel (engine.h: upconv_fold_supported)
+        w.has_fold = true;
+        w.w_fold = reserve(upconv_fold_elems(ch) * es());
+        q.has_fold = true; q.fold_off = w.w_fold;
+      } }
     w.bias = f32(p + ".bias", ch_r, ch, &w.i_bias);
     return w;
   }
@@ -260,7 +265,7 @@ int build_unet(llie_ctx* c) {
     in_ch = out;
     if (l < 3) res *= 2;
   }
-  for (int l = 0; l < 3; ++l) c->ups.push_back(b.add_conv3("upsamplers." + std::to_string(l) + ".conv", ch[3 - l]));
+  for (int l = 0; l < 3; ++l) c->ups.push_back(b.add_conv3("upsamplers." + std::to_string(l) + ".conv", ch[3 - l], true));
   c->fin_g = b.f32("final_norm.weight", ch[0], c0p, &c->i_fin_g);
   c->fin_b = b.f32("final_norm.bias", ch[0], c0p, &c->i_fin_b);
   c->fin_w = b.reserve((size_t)9 * c0p * 4 * 4);
@@ -303,7 +308,7 @@ int build_module(llie_ctx* c) {
       break;
     }
     case LLIE_DOWN: c->downs.push_back(b.add_conv3("down", g.in_channels)); break;
-    case LLIE_UP: c->ups.push_back(b.add_conv3("conv", g.in_channels)); break;
+    case LLIE_UP: c->ups.push_back(b.add_conv3("conv", g.in_channels, true)); break;
     default: return LLIE_ERR_ARG;
   }
   b.finish_film();
@@ -478,6 +483,7 @@ int llie_load_param(llie_ctx* c, const char* key, const float* src, int64_t nume
     case PK_CONV3:
       e = launch_repack_conv3x3(c->dt, src, dst, p.O, p.I, s, p.Op, p.Ip);
       if (e == hipSuccess && p.has_t && !c->padded) e = launch_repack_conv3x3_t(c->dt, src, c->blob + p.t_off, p.O, p.I, s);
+      if (e == hipSuccess && p.has_fold) e = launch_upconv_fold(c->dt, src, c->blob + p.fold_off, p.O, s);
       break;
     case PK_DW:
       e = launch_repack_dw(src, reinterpret_cast<float*>(dst), p.O, s, p.Op);
@@ -553,6 +559,9 @@ static int load_all_impl(llie_ctx* c, const float* const* srcs, int n, llie_stre
   }
   hipError_t e = launch_params_hash(c->load_descs, n, c->hash_partial, c->hash_state, conditional ? 0 : 1, s);
   if (e == hipSuccess) e = launch_load_all(c->dt, c->load_descs, n, c->blob, s, c->hash_state);
+  // the up-sampling convs' folded sets gather nine source values per element: a launch of their own, under the same "changed" flag
+  for (int i = 0; e == hipSuccess && i < n; ++i)
+    if (c->params[i].has_fold) e = launch_upconv_fold(c->dt, srcs[i], c->blob + c->params[i].fold_off, c->params[i].O, s, c->hash_state);
   if (e != hipSuccess) { set_err("llie_load_all: %s", hipGetErrorString(e)); return (int)e; }
   for (int i = 0; i < n; ++i) c->params[i].loaded = true;
   return LLIE_OK;

@@ -926,6 +926,53 @@ hipError_t launch_repack_conv3x3(int dtype, const float* src, void* dst, int O, 
   }
   return hipGetLastError();
 }
+// Up-sampling conv, 2-byte engines: the bilinear x2 (align_corners = False) folded into per-phase 3x3 weights on the replicate-padded
+// low-resolution input (layout: kernels.h, launch_conv3x3_upfold).  Output pixel (2i + a, 2j + b) of conv3x3(up2(x), w) is
+//   sum_{r,s} Wf[a][b][r][s] xr[i + r - 1, j + s - 1],  Wf[a][b][r][s] = sum_{u,v} R[a][r][u] R[b][s][v] w[u][v]
+// with R[a][r][u] the weight of low-resolution row i + r - 1 in up-sampled row 2i + a + u - 1.  On the output's outermost ring the
+// conv's zero padding replaces kernel row ue = 0 (a = 0, i = 0) / 2 (a = 1, i = H - 1) -- for which the replicate padding has put
+// x[ie] -- and likewise column ve: the correction sets hold -sum_v R[b][s][v] w[ue][v] (row edge), -sum_u R[a][r][u] w[u][ve]
+// (column edge) and +w[ue][ve] (corner, subtracted twice by the other two).  Every coefficient is a multiple of 1/16: fp64 sums
+// are exact, and the single rounding to T goes through a float rounded to odd.
+__constant__ double kUpR[2][3][3] = {{{.75, .25, 0.}, {.25, .75, .75}, {0., 0., .25}}, {{.25, 0., 0.}, {.75, .75, .25}, {0., .25, .75}}};
+template <typename T>
+__global__ void __launch_bounds__(256) upconv_fold_kernel(const float* src, T* dst, int C, const unsigned long long* state) {
+  if (state && state[1] == 0) return;  // parameters unchanged since the last load
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, cc = (long long)C * C;
+  if (idx >= 64 * cc) return;
+  const int set = (int)(idx / cc), co = (int)(idx % cc) / C, ci = (int)(idx % cc) % C;
+  const float* w = src + ((size_t)co * C + ci) * 9;
+  const int p = set < 36 ? set / 9 : (set < 60 ? ((set - 36) % 12) / 3 : set - 60), a = p >> 1, b = p & 1;
+  const int ue = a ? 2 : 0, ve = b ? 2 : 0;
+  double v = 0.0;
+  if (set < 36) {
+    const int r = (set % 9) / 3, s = set % 3;
+    for (int u = 0; u < 3; ++u)
+      for (int x = 0; x < 3; ++x) v += kUpR[a][r][u] * kUpR[b][s][x] * (double)w[u * 3 + x];
+  } else if (set < 48) {
+    const int s = (set - 36) % 3;
+    for (int x = 0; x < 3; ++x) v -= kUpR[b][s][x] * (double)w[ue * 3 + x];
+  } else if (set < 60) {
+    const int r = (set - 48) % 3;
+    for (int u = 0; u < 3; ++u) v -= kUpR[a][r][u] * (double)w[u * 3 + ve];
+  } else {
+    v = (double)w[ue * 3 + ve];
+  }
+  float f = (float)v;
+  if ((double)f != v) {  // round to odd, so that the rounding to T below is the only one that counts
+    uint32_t bits = __float_as_uint(f);
+    if (!(bits & 1u)) bits += (((double)f < v) == !(bits >> 31)) ? 1u : 0xFFFFFFFFu;
+    f = __uint_as_float(bits);
+  }
+  dst[idx] = (T)f;
+}
+hipError_t launch_upconv_fold(int dtype, const float* src, void* dst, int C, hipStream_t s, const unsigned long long* state) {
+  if (C < 1 || (dtype != 1 && dtype != 2)) return hipErrorInvalidValue;
+  dim3 grid((unsigned)((64LL * C * C + 255) / 256));
+  if (dtype == 1) hipLaunchKernelGGL(upconv_fold_kernel<half_t>, grid, dim3(256), 0, s, src, (half_t*)dst, C, state);
+  else hipLaunchKernelGGL(upconv_fold_kernel<bf16_t>, grid, dim3(256), 0, s, src, (bf16_t*)dst, C, state);
+  return hipGetLastError();
+}
 __global__ void repack_dw_kernel(const float* src, float* dst, int C, int Cp) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= C * 9) return;

@@ -20,6 +20,9 @@ static Knobs knob_defaults() {
   // non-temporally by its producer (common.h: st_vec_pol).  nt_mask picks the producers: 1 expand_dw (h2), 2 pw_expand (h1),
   // 4 dwconv3x3 (h2), 8 project / attention GEMM outputs, 16 dense 3x3 conv outputs.  Values never change, only where lines live.
   k.nt_min_mb = 100; k.nt_mask = 1;
+  // Up-sampling convs from folded weights (conv.hip: conv3x3_upfold_kernel) wherever upconv_fold_supported();
+  // llie_tune("upconv_fold", 0) restores conv3x3_kernel's mode 1, which blends the patch itself.
+  k.upconv_fold = 1;
   k.se_mfma = 1;  // SE MLP of the wide blocks as two MFMA launches (small.hip: se_fc1_mfma / se_fc2_mfma); 0 = the row-parallel pair
   // Backward pass: run the weight-gradient kernels on a side stream next to the activation-gradient chain
   // (llie_tune("bwd_async", 0) puts everything back on the caller's stream).
@@ -61,6 +64,7 @@ int llie_tune(const char* knob, int value) {
   if (!strcmp(knob, "se_mfma")) { g_knobs.se_mfma = value; return LLIE_OK; }
   if (!strcmp(knob, "nt_min_mb")) { g_knobs.nt_min_mb = value; return LLIE_OK; }
   if (!strcmp(knob, "nt_mask")) { g_knobs.nt_mask = value; return LLIE_OK; }
+  if (!strcmp(knob, "upconv_fold")) { g_knobs.upconv_fold = value != 0; return LLIE_OK; }
   if (!strcmp(knob, "gram")) { g_knobs.gram = value; return LLIE_OK; }
   if (!strcmp(knob, "irbx")) { g_knobs.use_irbx = value != 0; return LLIE_OK; }
   if (!strcmp(knob, "irbx_project")) { g_knobs.irbx_project = value < 0 || value > 2 ? 1 : value; return LLIE_OK; }

@@ -384,6 +384,17 @@ int llie_groupnorm_finalize(const float* slab0, int ntiles0, int ch0, const floa
 int llie_conv3x3(int dtype, int mode, const void* in, const void* w, const float* bias, void* out, float* stats, int batch, int Hi, int Wi,
                  int Cin, int Cout, llie_stream stream);
 int llie_conv3x3_tiles(int Ho, int Wo);
+/* The Upsample conv (:383-384) with the bilinear x2 folded into per-phase 3x3 weights on the low-resolution input: the form the
+ * 2-byte inference engines run (knob "upconv_fold").  llie_upconv_fold_weights: fp32 OIHW [C][C][3][3] -> `folded`,
+ * llie_upconv_fold_elems(C) = 64 C^2 elements of the compute type (dtype 1 or 2; interior sets [4 phases][9 taps][C][C], then the
+ * image-border corrections: 4 x 3 row-edge, 4 x 3 column-edge, 4 corner sets), rounded once.  llie_conv3x3_upfold: the conv on
+ * such a blob; Hi % 8 == 0, Wi % 16 == 0, C = 64 or a multiple of 128; stats (or NULL)
+ * [batch][llie_conv3x3_upfold_tiles(2 Hi, 2 Wi)][2][C]. */
+int64_t llie_upconv_fold_elems(int C);
+int llie_upconv_fold_weights(int dtype, const float* w_oihw, void* folded, int C, llie_stream stream);
+int llie_conv3x3_upfold(int dtype, const void* in, const void* folded, const float* bias, void* out, float* stats, int batch, int Hi, int Wi,
+                        int C, llie_stream stream);
+int llie_conv3x3_upfold_tiles(int Ho, int Wo);
 int llie_linattn(int dtype, const void* qkv, float* kv_scratch, void* out, int batch, int N, int heads, llie_stream stream);
 int llie_linattn_splits(int N);
 int llie_se_mlp(int dtype, const float* pool_sums, int pixels, const void* w1, const float* b1, const void* w2, const float* b2, float* mean_scratch,
@@ -523,6 +534,8 @@ int llie_rw_probe(const void* src, void* dst, int64_t units, int reads, int writ
  * Threading: the knobs are plain process-wide variables read by every forward; call llie_tune only while no other
  * thread is inside an llie_* compute call (same rule as the handle itself: SURVEY.md 8b, one stream at a time). */
 int llie_tune(const char* knob, int value);
+/* One more engine knob, default 1: upconv_fold -- the up-sampling convs of 2-byte inference engines run from folded weights
+ * (llie_conv3x3_upfold above) on maps of whole 8 x 16 low-resolution tiles; 0 = the kernel that blends the patch itself, everywhere. */
 int llie_debug_irbx_stamps(double* out10); /* diagnostic builds: 9 per-wave cycle sums of expand_dw (irbx.hip: STAMP) + waves averaged */
 int llie_debug_conv_stamps(double* out8); /* diagnostic builds: 7 per-wave cycle sums of the up-sampling conv (conv.hip: STAMP) + waves averaged */
 int llie_debug_gemm_stamps(double* out3); /* diagnostic builds: see gemm.hip (STAMP) */
@@ -537,7 +550,7 @@ int llie_debug_pwx_stamps(double* out4);  /* diagnostic builds: see pwx.hip (STA
 enum llie_kernel_class {
   LLIE_K_GEMM = 1,  /* pw_gemm_kernel: 1x1 convs with fused prologue / epilogue */
   LLIE_K_DW = 2,    /* dwconv3x3_kernel */
-  LLIE_K_CONV3 = 4, /* conv3x3_kernel (down / up sampling convs) */
+  LLIE_K_CONV3 = 4, /* conv3x3_kernel, conv3x3_upfold_kernel (down / up sampling convs) */
   LLIE_K_SE = 8,    /* squeeze-excitation MLP launches */
   LLIE_K_OTHER = 16 /* everything else on the forward path (norm finalize, attention core, input / output convs, time MLPs) */
 };
