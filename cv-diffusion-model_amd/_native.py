@@ -37,6 +37,7 @@ EXPORTS = [
     "llie_aug_pair_u8", "llie_aug_synth_u8",
     "llie_upconv_fold_elems", "llie_upconv_fold_weights", "llie_conv3x3_upfold", "llie_conv3x3_upfold_tiles",
     "llie_expand_dw", "llie_expand_pool", "llie_expand_dw_project", "llie_expand_dw_project_skip", "llie_irbx_project_tiles",
+    "llie_expand_stats", "llie_irbx_stats_rows",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 
@@ -185,6 +186,8 @@ def lib() -> C.CDLL:
     L.llie_expand_dw_project.argtypes = [ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     L.llie_expand_dw_project_skip.argtypes = [ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, ci, ci, ci, vp]
     L.llie_irbx_project_tiles.argtypes = [ci, ci]
+    L.llie_expand_stats.argtypes = [ci, vp, ci, vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]
+    L.llie_irbx_stats_rows.argtypes = [ci]
     L.llie_tune.argtypes = [C.c_char_p, ci]
     L.llie_debug_irbx_stamps.argtypes = [C.POINTER(C.c_double)]
     L.llie_optimizer_create.argtypes = [C.POINTER(OptTensor), ci, C.POINTER(C.c_void_p)]

@@ -72,6 +72,7 @@ __device__ __forceinline__ typename Elem<T>::vec_t activate8(typename Elem<T>::v
 // Two accumulator registers pack into one dword of T and one v_dot2 adds both to an fp32 sum; the column sums are v_dot2 with
 // a one-hot operand on the four registers that can hold a first / last column (W % 16 == 0: a 16-pixel group lies in one
 // image row, starts at a multiple of 16), the row sums a uniform branch that only the image's first and last row take.
+constexpr int kXStamps = 9;  // cycle-stamp slots of a diagnostic build (STAMP, below)
 template <typename T> struct PackedOne;
 template <> struct PackedOne<half_t> { static constexpr uint32_t lo = 0x00003C00u, hi = 0x3C000000u; };
 template <> struct PackedOne<bf16_t> { static constexpr uint32_t lo = 0x00003F80u, hi = 0x3F800000u; };
@@ -82,7 +83,10 @@ template <typename T> __device__ __forceinline__ float dot2_pk(uint32_t a, uint3
   else return dot2_bf16(a, b, c);
 }
 
-template <typename T, int KS, int NBW, bool POOL>
+// STAMP = diagnostic build (llie_tune("irbx_stamp", 2), expand_pool in fp16): s_memtime around the phases of a step, summed per
+// wave into a.dbg ([workgroup][wave][kXStamps] cycles: 0 wait for the step's loads (vmcnt), 1 activation + ds_write + next step's
+// loads issued, 2 barrier, 3 fragment reads + MFMAs until the accumulator can be read, 4 epilogue; 5.. unused)
+template <typename T, int KS, int NBW, bool POOL, bool STAMP = false>
 __device__ __forceinline__ void expand_scan(const IrbxArgs& a, const int RP) {
   constexpr int K = 16 * KS, XP = (K + 8) * 2;  // LDS pixel pitch in bytes: conflict-free ds_read_b128
   typedef typename Elem<T>::vec_t vec_t;
@@ -141,8 +145,21 @@ __device__ __forceinline__ void expand_scan(const IrbxArgs& a, const int RP) {
   };
   load(0);
   wg_barrier();  // aff1 staged
+  unsigned long long tk[5] = {}, t_prev = 0;
+  auto stamp = [&](int slot) {
+    if constexpr (STAMP) {
+      __builtin_amdgcn_sched_barrier(0);
+      const unsigned long long now = __builtin_amdgcn_s_memtime();
+      __builtin_amdgcn_sched_barrier(0);
+      if (slot >= 0) tk[slot] += now - t_prev;
+      t_prev = now;
+    }
+  };
+  stamp(-1);
   for (int step = 0; step < nsteps; ++step) {
     unsigned char* buf = sA[step & 1];
+    if constexpr (STAMP) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stamp(0);
 #pragma unroll
     for (int j = 0; j < KS; ++j) {
       const int v = tid + j * 256;
@@ -150,7 +167,9 @@ __device__ __forceinline__ void expand_scan(const IrbxArgs& a, const int RP) {
       *reinterpret_cast<vec_t*>(buf + (v / (2 * KS)) * XP + k * 2) = activate8<T>(raw[j], &aff1[0][k], &aff1[1][k]);
     }
     if (step + 1 < nsteps) load(step + 1);
+    stamp(1);
     wg_barrier();  // tile `step` complete; the other buffer (read during step - 1) is free for step + 1
+    stamp(2);
 #pragma unroll 1
     for (int pb = 0; pb < 4; ++pb) {
       vec_t af[KS];
@@ -175,6 +194,10 @@ __device__ __forceinline__ void expand_scan(const IrbxArgs& a, const int RP) {
         for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
         for (int s = 0; s < KS; ++s) acc = mfma16<T>(af[s], wf[j][s], acc);
+        if constexpr (STAMP) {  // a read of the last accumulator register: the compiler waits for the MFMAs here
+          asm volatile("" ::"s"(__builtin_amdgcn_readfirstlane(__float_as_int(acc[15]))));
+          stamp(3);
+        }
         if constexpr (POOL) {
           constexpr uint32_t ones = PackedOne<T>::lo | PackedOne<T>::hi;
           uint32_t pk[8];  // registers (2 i, 2 i + 1) = two neighbouring pixels
@@ -200,6 +223,7 @@ __device__ __forceinline__ void expand_scan(const IrbxArgs& a, const int RP) {
             }
           }
           s1[j] += gs[0] + gs[1];
+          stamp(4);
           continue;
         }
         // packed fp32 (v_pk_add_f32 / v_pk_fma_f32: two values per instruction) -- this reduction, not the MFMAs, is what
@@ -214,6 +238,12 @@ __device__ __forceinline__ void expand_scan(const IrbxArgs& a, const int RP) {
         s1[j] += t1[0] + t1[1];
         s2[j] += t2[0] + t2[1];
       }
+    }
+  }
+  if constexpr (STAMP) {
+    if (a.dbg && lane == 0) {
+      const size_t wg = (size_t)blockIdx.z * gridDim.x + blockIdx.x;
+      for (int i = 0; i < kXStamps; ++i) a.dbg[(wg * 4 + wave) * kXStamps + i] = i < 5 ? tk[i] : 0ull;
     }
   }
   // lane halves hold different pixel rows of the same channel; every wave owns its channels outright
@@ -257,6 +287,10 @@ __device__ __forceinline__ void expand_scan(const IrbxArgs& a, const int RP) {
     }
   }
 }
+template <int KS, int NBW>
+__global__ void __launch_bounds__(256, 2) expand_pool_stamp_kernel(const IrbxArgs a, const int RP) {
+  expand_scan<half_t, KS, NBW, true, true>(a, RP);
+}
 template <typename T, int KS, int NBW>
 __global__ void __launch_bounds__(256, 2) expand_stats_kernel(const IrbxArgs a, const int RP) {
   expand_scan<T, KS, NBW, false>(a, RP);
@@ -277,7 +311,6 @@ constexpr int kXNPB = 6;
 // fixed 16-byte channel slot (the expand epilogue's ds_write_b128, the depthwise MFMAs' ds_read_b128): the 144-byte
 // pitch (36 dwords) spreads consecutive pixels over distinct bank groups for either instruction's lane grouping.
 constexpr int SHP = 144;
-constexpr int kXStamps = 9;
 
 // STAMP = diagnostic build (llie_tune("irbx_stamp", 1)): s_memtime around the phases, summed per wave into a.dbg
 // ([workgroup][wave][kXStamps] cycles: 0 wait for the prefetched / loaded x tile (vmcnt), 1 activate + ds_write of the x tile,
@@ -537,7 +570,9 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
         sc2[g] = *reinterpret_cast<const f32x4*>(aff2 + ch0 + 8 * g + 4 * h);
         sh2[g] = *reinterpret_cast<const f32x4*>(aff2 + a.Chid + ch0 + 8 * g + 4 * h);
       }
-      constexpr int NACC = KS <= 2 ? 3 : 1;  // accumulators in flight: all three pixel blocks, or one at a time (registers)
+      // accumulators in flight: all three pixel blocks, or one at a time (registers; the identity tail at 32 channels fits three
+      // workgroups per CU that way)
+      constexpr int NACC = (KS <= 2 && PCO == 0) ? 3 : 1;
       f32x16 accs[NACC];
       if constexpr (NACC == 3) {
 #pragma unroll
@@ -896,9 +931,10 @@ template <typename T, int KS, bool DBUF, bool STAMP = false, bool NTST = false>
 __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_kernel(const IrbxArgs a, const int tiles_per_wg, const int chunks_per_wg) {
   expand_dw_body<T, KS, DBUF, STAMP, NTST, 0>(a, tiles_per_wg, chunks_per_wg);
 }
-// two workgroups per CU: the y accumulators and the Wp fragments do not fit the 168 registers of three
+// two workgroups per CU at 64 and 96 channels: the y accumulators and the Wp fragments do not fit the 168 registers of three; at 32
+// they do (165, none spilled) once the expand phase keeps one accumulator at a time (NACC)
 template <typename T, int KS, int PCO>
-__global__ void __launch_bounds__(256, 2) expand_dw_project_kernel(const IrbxArgs a, const int tiles_per_wg) {
+__global__ void __launch_bounds__(256, KS == 2 ? 3 : 2) expand_dw_project_kernel(const IrbxArgs a, const int tiles_per_wg) {
   expand_dw_body<T, KS, false, false, false, PCO>(a, tiles_per_wg, KS);
 }
 
@@ -956,6 +992,21 @@ static hipError_t launch_scan_cfg(const IrbxArgs& a, hipStream_t s) {
   static const std::string name = std::string(POOL ? "expand_pool_kernel<" : "expand_stats_kernel<") + TypeName<T>::value + ", " +
                                   std::to_string(KS) + ", " + std::to_string(NBW) + ">";
   note_kernel(name.c_str());
+  if constexpr (POOL && std::is_same<T, half_t>::value) {
+    if (g_irbx_stamp == 2) {  // diagnostic build: in-kernel cycle stamps
+      IrbxArgs b = a;
+      const size_t n = (size_t)(P / RP) * a.B * 4 * kXStamps;
+      if (n > g_irbx_dbg_n || !g_irbx_dbg) {
+        if (g_irbx_dbg) (void)hipFree(g_irbx_dbg);
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&g_irbx_dbg), n * 8);
+        if (e != hipSuccess) return e;
+      }
+      g_irbx_dbg_n = n;
+      b.dbg = g_irbx_dbg;
+      hipLaunchKernelGGL((expand_pool_stamp_kernel<KS, NBW>), dim3(P / RP, 1, a.B), dim3(256), 0, s, b, RP);
+      return hipGetLastError();
+    }
+  }
   constexpr auto kernel = POOL ? &expand_pool_kernel<T, KS, NBW> : &expand_stats_kernel<T, KS, NBW>;
   hipLaunchKernelGGL(kernel, dim3(P / RP, 1, a.B), dim3(256), 0, s, a, RP);
   return hipGetLastError();
@@ -1027,7 +1078,7 @@ static hipError_t launch_dw_cfg(const IrbxArgs& a, hipStream_t s) {
     tpw = 0;
   }
   if constexpr (std::is_same<T, half_t>::value && !DBUF) {
-    if (g_irbx_stamp) {  // diagnostic build: in-kernel cycle stamps (fp16 only)
+    if (g_irbx_stamp == 1) {  // diagnostic build: in-kernel cycle stamps (fp16 only)
       IrbxArgs b = a;
       const size_t n = (size_t)grid.x * grid.y * grid.z * 4 * kXStamps;
       if (n > g_irbx_dbg_n || !g_irbx_dbg) {

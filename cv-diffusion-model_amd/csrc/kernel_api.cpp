@@ -523,6 +523,14 @@ int llie_expand_pool(int dtype, const void* x0, int c0, const void* x1, int c1, 
   a.pool_tot = pool_totals;
   return kerr("expand_pool", launch_expand_pool(dtype, a, hs(stream)), LLIE_ERR_SHAPE, kIrbxShapes);
 }
+int llie_expand_stats(int dtype, const void* x0, int c0, const void* x1, int c1, const float* scale1, const float* shift1, const void* w_expand,
+                      float* stats, int batch, int H, int W, llie_stream stream) {
+  if (!x0 || !scale1 || !shift1 || !w_expand || !stats || batch <= 0 || c0 <= 0 || c1 < 0 || (c1 > 0) != (x1 != nullptr)) return LLIE_ERR_ARG;
+  IrbxArgs a = irbx_args(x0, c0, x1, c1, scale1, shift1, w_expand, nullptr, nullptr, nullptr, batch, H, W);
+  a.stats = stats;
+  return kerr("expand_stats", launch_expand_stats(dtype, a, hs(stream)), LLIE_ERR_SHAPE, kIrbxShapes);
+}
+int llie_irbx_stats_rows(int P) { return P > 0 ? irbx_stats_rows(P) : LLIE_ERR_ARG; }
 int llie_expand_dw_project(int dtype, const void* x, int C, const float* scale1, const float* shift1, const void* w_expand, const float* scale2,
                            const float* shift2, const float* w_dw, const float* gate, const void* w_project, void* y, float* stats, int batch,
                            int H, int W, llie_stream stream) {

@@ -513,6 +513,12 @@ int llie_expand_dw_project_skip(int dtype, const void* x0, int c0, const void* x
                                 const void* w_expand, const float* scale2, const float* shift2, const float* w_dw, const float* gate,
                                 const void* w_project_skip, int ld, int cout, void* y, float* stats, int batch, int H, int W, llie_stream stream);
 int llie_irbx_project_tiles(int H, int W);
+/* expand_stats: the statistics pass of the same blocks on its own (knob "gram" = 0, and every recompute block below 32 768 pixels):
+ * stats [batch][H W / llie_irbx_stats_rows(H W)][2][Chid] fp32 = (sum, sum of squares) of h1 = w_expand relu6(norm1(x)) per channel
+ * over each run of llie_irbx_stats_rows(H W) consecutive pixels; every entry is written.  Leading arguments as expand_pool. */
+int llie_expand_stats(int dtype, const void* x0, int c0, const void* x1, int c1, const float* scale1, const float* shift1, const void* w_expand,
+                      float* stats, int batch, int H, int W, llie_stream stream);
+int llie_irbx_stats_rows(int P);
 /* dst[0:bytes] = src[0:bytes] with 16-byte lane accesses: the on-box HBM copy-bandwidth probe behind bench.py's
  * `peak_measured` ("a copy-kernel bandwidth probe"; 2 x bytes move per call). */
 int llie_copy_probe(const void* src, void* dst, int64_t bytes, llie_stream stream);
@@ -536,7 +542,7 @@ int llie_rw_probe(const void* src, void* dst, int64_t units, int reads, int writ
 int llie_tune(const char* knob, int value);
 /* One more engine knob, default 1: upconv_fold -- the up-sampling convs of 2-byte inference engines run from folded weights
  * (llie_conv3x3_upfold above) on maps of whole 8 x 16 low-resolution tiles; 0 = the kernel that blends the patch itself, everywhere. */
-int llie_debug_irbx_stamps(double* out10); /* diagnostic builds: 9 per-wave cycle sums of expand_dw (irbx.hip: STAMP) + waves averaged */
+int llie_debug_irbx_stamps(double* out10); /* diagnostic builds: 9 per-wave cycle sums of expand_dw ("irbx_stamp" = 1) or of expand_pool's LDS-tile scan ("irbx_stamp" = 2, 5 slots used) (irbx.hip: STAMP) + waves averaged */
 int llie_debug_conv_stamps(double* out8); /* diagnostic builds: 7 per-wave cycle sums of the up-sampling conv (conv.hip: STAMP) + waves averaged */
 int llie_debug_gemm_stamps(double* out3); /* diagnostic builds: see gemm.hip (STAMP) */
 int llie_debug_pwx_stamps(double* out4);  /* diagnostic builds: see pwx.hip (STAMP): {A phase, channel loop, of which waiting for the weight DMA} cycles per wave, waves */
