@@ -24,6 +24,7 @@ from .tiling import (tile_origins, gather_tiles_array, blend_tiles_array, gather
                      blend_tiles_device, enhance_tiled)
 from .data import (DeviceFrameStore, DevicePairLoader, create_device_dataloaders, epoch_plan, augment_pairs_host, augment_synth_host,
                    augment_pairs_device, augment_synth_device)
+from .metrics import ImageMetrics, image_metrics, image_metrics_host, evaluate, evaluate_full_resolution
 
 __all__ = [
     "EfficientUNet", "EfficientUNetConfig", "create_efficient_unet", "InvertedResidualBlock", "LinearAttention", "SqueezeExcitation",
@@ -35,4 +36,5 @@ __all__ = [
     "enhance_tiled",
     "DeviceFrameStore", "DevicePairLoader", "create_device_dataloaders", "epoch_plan", "augment_pairs_host", "augment_synth_host",
     "augment_pairs_device", "augment_synth_device",
+    "ImageMetrics", "image_metrics", "image_metrics_host", "evaluate", "evaluate_full_resolution",
 ]

@@ -313,6 +313,39 @@ int llie_aug_synth_u8(const uint8_t* pool, const int64_t* table, int N, const ll
               LLIE_ERR_ARG, nullptr);
 }
 
+// ---- image quality (metrics.hip): every contract check runs here, before any HIP call
+static int metrics_check(const void* a, const void* b, int batch, int H, int W, const double* out3, const void* scratch, int64_t scratch_bytes) {
+  if (!a || !b || !out3 || !scratch || batch < 1) return LLIE_ERR_ARG;
+  if (H < kMetricTaps || W < kMetricTaps) {
+    set_err("image_metrics: images of at least %d x %d, got %d x %d", kMetricTaps, kMetricTaps, H, W);
+    return LLIE_ERR_SHAPE;
+  }
+  const int64_t need = llie_image_metrics_scratch_bytes(batch, H, W);
+  if (need < 0) return LLIE_ERR_ARG;
+  if (scratch_bytes < need) {
+    set_err("image_metrics: scratch of %lld bytes needed, %lld given", (long long)need, (long long)scratch_bytes);
+    return LLIE_ERR_WORKSPACE;
+  }
+  return LLIE_OK;
+}
+int64_t llie_image_metrics_scratch_bytes(int batch, int H, int W) {
+  if (batch < 1) return LLIE_ERR_ARG;
+  if (H < kMetricTaps || W < kMetricTaps) return LLIE_ERR_SHAPE;
+  const long long tiles = image_metrics_tiles(H, W) * batch;
+  return tiles < (1ll << 31) ? (int64_t)(tiles * 2 * (long long)sizeof(double)) : (int64_t)LLIE_ERR_ARG;
+}
+int llie_image_metrics_f32(const float* a, const float* b, int batch, int H, int W, float lo, float hi, double* out3, void* scratch,
+                           int64_t scratch_bytes, llie_stream stream) {
+  if (!a || !b || !out3 || !scratch || batch < 1 || !(lo != hi) || !std::isfinite(lo) || !std::isfinite(hi)) return LLIE_ERR_ARG;
+  if (int rc = metrics_check(a, b, batch, H, W, out3, scratch, scratch_bytes)) return rc;
+  return kerr("image_metrics_f32", launch_image_metrics_f32(a, b, batch, H, W, lo, hi, out3, reinterpret_cast<double*>(scratch), hs(stream)));
+}
+int llie_image_metrics_u8(const uint8_t* a, const uint8_t* b, int batch, int H, int W, double* out3, void* scratch, int64_t scratch_bytes,
+                          llie_stream stream) {
+  if (int rc = metrics_check(a, b, batch, H, W, out3, scratch, scratch_bytes)) return rc;
+  return kerr("image_metrics_u8", launch_image_metrics_u8(a, b, batch, H, W, out3, reinterpret_cast<double*>(scratch), hs(stream)));
+}
+
 int llie_time_embed(llie_ctx* c, const int64_t* t, int rows, float* emb, float* temb, float* silu_temb, llie_stream stream) {
   if (!c || !t || !temb || !silu_temb || rows <= 0 || c->cfg.kind != LLIE_UNET) return LLIE_ERR_ARG;
   if (int rc = check_loaded(c)) return rc;

@@ -609,4 +609,23 @@ struct AugArgs {
 hipError_t launch_aug_pair_u8(const AugArgs& a, hipStream_t s);
 hipError_t launch_aug_synth_u8(const AugArgs& a, hipStream_t s);
 
+// (13) image quality (metrics.hip): per image {mse, psnr, ssim} of a against b, float64 arithmetic on x = (v - lo) / (hi - lo)
+// (bytes: x = byte / 255).  SSIM is Wang et al. 2004 on RGB: 11-tap Gaussian window (sigma 1.5, normalised) applied along rows,
+// then columns, over the (H - 10) x (W - 10) positions whose window lies inside the image; biased variances E[x^2] - mu^2;
+// ssim_map = (2 mx my + C1)(2 sxy + C2) / ((mx^2 + my^2 + C1)(sx^2 + sy^2 + C2)); ssim = mean over channels and positions;
+// mse = mean of (x - y)^2 over all 3 H W values; psnr = -10 log10(mse), +inf at mse == 0.
+// One workgroup per tile of kMetricTileH x kMetricTileW valid positions writes partial[image][tile][2] = {sum ssim_map,
+// sum (x - y)^2}; a second launch adds an image's partials in a fixed order.  No atomics: bitwise reproducible, and the same bits
+// for an image alone or in a batch.
+constexpr int kMetricTaps = 11, kMetricTileH = 16, kMetricTileW = 32;
+constexpr double kMetricC1 = 1e-4, kMetricC2 = 9e-4;  // (0.01 L)^2, (0.03 L)^2 with L = 1
+inline long long image_metrics_tiles(int H, int W) {  // per image; H, W >= kMetricTaps
+  return (long long)((H - kMetricTaps + kMetricTileH) / kMetricTileH) * ((W - kMetricTaps + kMetricTileW) / kMetricTileW);
+}
+// a / b: fp32 NCHW [batch][3][H][W] or uint8 HWC [batch][H][W][3]; out3 [batch][3] doubles; partial: image_metrics_tiles * batch * 2
+// doubles.  A null pointer, batch < 1, H or W < 11, lo == hi: hipErrorInvalidValue
+hipError_t launch_image_metrics_f32(const float* a, const float* b, int batch, int H, int W, float lo, float hi, double* out3, double* partial,
+                                    hipStream_t s);
+hipError_t launch_image_metrics_u8(const uint8_t* a, const uint8_t* b, int batch, int H, int W, double* out3, double* partial, hipStream_t s);
+
 }  // namespace llie

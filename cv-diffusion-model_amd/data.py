@@ -114,6 +114,15 @@ class DeviceFrameStore:
             if h < image_size or w < image_size:
                 raise ValueError(f"frame {name} is {h}x{w}: smaller than the {image_size}x{image_size} crop")
 
+    def frame(self, index: int) -> torch.Tensor:
+        """Frame `index` as a uint8 [H,W,3] view into the pool (no copy): low-light frames are 0 .. n-1, normal-light frames
+        n .. 2n-1 in a paired store."""
+        i = int(index)
+        if not 0 <= i < self.num_frames:
+            raise IndexError(f"frame {index} of a store of {self.num_frames} frames")
+        o, h, w = (int(v) for v in self._host_table[i])
+        return self.pool[o:o + h * w * 3].view(h, w, 3)
+
     def host_frames(self) -> List[np.ndarray]:
         """The frames as NumPy arrays, in table order (what the host twins take)."""
         pool = self.pool.cpu().numpy()

@@ -1,0 +1,286 @@
+"""Image quality against ground truth: PSNR and SSIM on the device, and `evaluate` over a paired validation set.
+
+One definition serves the NumPy twin here, the kernels (csrc/metrics.hip) and the tests.  All arithmetic is float64 on the
+mapped values: x = (v - lo) / (hi - lo) for float images in `data_range = (lo, hi)` (the model's range is (-1, 1)), x = byte / 255
+for uint8 images.
+
+  window   g[k] = exp(-(k - 5)^2 / (2 * 1.5^2)), k = 0 .. 10, normalised to sum 1; the 2-D window is g (x) g, applied along the rows,
+           then along the columns, taps in ascending order
+  ssim     Wang et al. 2004 on RGB (no luma conversion): at each of the (H - 10) x (W - 10) valid positions (those whose 11 x 11
+           window lies inside the image) and for each channel, the weighted means mx, my and the biased moments
+           sx2 = sum w x^2 - mx^2, sy2 = sum w y^2 - my^2, sxy = sum w x y - mx my;
+           map = (2 mx my + C1)(2 sxy + C2) / ((mx^2 + my^2 + C1)(sx2 + sy2 + C2)), C1 = 1e-4, C2 = 9e-4 (K1 = 0.01, K2 = 0.03, L = 1);
+           ssim = mean of the map over the 3 channels and all valid positions
+  mse      mean of (x - y)^2 over all 3 H W values, border included
+  psnr     -10 log10(mse), +inf when mse == 0
+
+`image_metrics_host` is that definition in code; `image_metrics` runs it on the device (no CPU fallback) and differs from the
+twin only in the order of its sums.  skimage's `structural_similarity` defaults differ in two ways: it uses the sample covariance
+(a factor 121 / 120 on the second moments) and, with `gaussian_weights=True`, crops a border of 5 pixels from a map computed with
+reflected edges, where this definition takes the valid positions of an unpadded filter.
+"""
+from __future__ import annotations
+
+from collections import namedtuple
+from contextlib import contextmanager
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from . import _native as N
+from .data import DeviceFrameStore, DevicePairLoader
+from .tiling import enhance_tiled
+
+WINDOW_TAPS, WINDOW_SIGMA = 11, 1.5
+C1, C2 = 1e-4, 9e-4
+TILE_H, TILE_W = 16, 32  # kMetricTileH, kMetricTileW (csrc/kernels.h): valid positions per workgroup of the device kernel
+
+ImageMetrics = namedtuple("ImageMetrics", ["mse", "psnr", "ssim"])
+
+
+def ssim_window() -> np.ndarray:
+    """float64 [11]: the normalised Gaussian taps of one axis."""
+    k = np.arange(WINDOW_TAPS, dtype=np.float64) - (WINDOW_TAPS // 2)
+    g = np.exp(-(k * k) / (2.0 * WINDOW_SIGMA * WINDOW_SIGMA))
+    return g / g.sum()
+
+
+# ------------------------------------------------------------------ the host twin (float64 NumPy)
+def _mapped_pair(a, b, data_range) -> Tuple[np.ndarray, np.ndarray]:
+    """-> x, y float64 [B,3,H,W] in [0, 1] units."""
+    a, b = np.asarray(a), np.asarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        raise ValueError(f"the two images must have one shape and dtype, got {a.dtype} {a.shape} and {b.dtype} {b.shape}")
+    if a.dtype == np.uint8:
+        if a.ndim == 3:
+            a, b = a[None], b[None]
+        if a.ndim != 4 or a.shape[3] != 3:
+            raise ValueError(f"uint8 images are HWC RGB [B,H,W,3] or [H,W,3], got {a.shape}")
+        x, y = (np.ascontiguousarray(v.transpose(0, 3, 1, 2)).astype(np.float64) / 255.0 for v in (a, b))
+    elif np.issubdtype(a.dtype, np.floating):
+        if a.ndim != 4 or a.shape[1] != 3:
+            raise ValueError(f"float images are NCHW [B,3,H,W], got {a.shape}")
+        lo, hi = (float(np.float32(v)) for v in data_range)  # as the C ABI carries them
+        if not lo != hi:
+            raise ValueError(f"data_range must span an interval, got {tuple(data_range)}")
+        x, y = ((np.ascontiguousarray(v, dtype=np.float64) - lo) / (hi - lo) for v in (a, b))
+    else:
+        raise ValueError(f"images must be float [B,3,H,W] or uint8 [B,H,W,3], got {a.dtype}")
+    if x.shape[2] < WINDOW_TAPS or x.shape[3] < WINDOW_TAPS:
+        raise ValueError(f"images must be at least {WINDOW_TAPS} x {WINDOW_TAPS} (one window), got {x.shape[2]} x {x.shape[3]}")
+    return x, y
+
+
+def _window_filter(m: np.ndarray) -> np.ndarray:
+    """[..., H, W] -> [..., H - 10, W - 10]: the window along the rows, then along the columns."""
+    g = ssim_window()
+    w = m.shape[-1] - WINDOW_TAPS + 1
+    rows = np.zeros(m.shape[:-1] + (w,), dtype=np.float64)
+    for k in range(WINDOW_TAPS):
+        rows = rows + g[k] * m[..., k:k + w]
+    h = m.shape[-2] - WINDOW_TAPS + 1
+    out = np.zeros(m.shape[:-2] + (h, w), dtype=np.float64)
+    for k in range(WINDOW_TAPS):
+        out = out + g[k] * rows[..., k:k + h, :]
+    return out
+
+
+def filtered_maps(x: np.ndarray, y: np.ndarray):
+    """The five windowed maps of the definition: E[x], E[y], E[x^2], E[y^2], E[xy] over the valid positions."""
+    return tuple(_window_filter(m) for m in (x, y, x * x, y * y, x * y))
+
+
+def image_metrics_host(a, b, data_range: Tuple[float, float] = (-1.0, 1.0)) -> ImageMetrics:
+    """The definition of the module docstring: float [B,3,H,W] in `data_range`, or uint8 [B,H,W,3] / [H,W,3] (x = byte / 255,
+    `data_range` ignored) -> float64 arrays (mse, psnr, ssim) of shape [B].  ValueError below 11 x 11."""
+    x, y = _mapped_pair(a, b, data_range)
+    mx, my, xx, yy, xy = filtered_maps(x, y)
+    sx2, sy2, sxy = xx - mx * mx, yy - my * my, xy - mx * my
+    ssim_map = ((2.0 * mx * my + C1) * (2.0 * sxy + C2)) / ((mx * mx + my * my + C1) * (sx2 + sy2 + C2))
+    d = x - y
+    mse = (d * d).mean(axis=(1, 2, 3))
+    with np.errstate(divide="ignore"):
+        psnr = -10.0 * np.log10(mse)
+    return ImageMetrics(mse, psnr, ssim_map.mean(axis=(1, 2, 3)))
+
+
+# ------------------------------------------------------------------ the device function
+def _require_hip(t, what: str) -> None:
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f"{what} runs only on a HIP device (got '{where}'); there is no CPU fallback")
+
+
+def _metrics_out3(a: torch.Tensor, b: torch.Tensor, data_range) -> torch.Tensor:
+    """float64 [B,3] = (mse, psnr, ssim) per image, on the inputs' device, no synchronisation."""
+    _require_hip(a, "image_metrics")
+    _require_hip(b, "image_metrics")
+    if a.shape != b.shape or a.dtype != b.dtype or a.device != b.device:
+        raise ValueError(f"the two images must have one shape, dtype and device, got {a.dtype} {tuple(a.shape)} on {a.device} and "
+                         f"{b.dtype} {tuple(b.shape)} on {b.device}")
+    u8 = a.dtype == torch.uint8
+    if u8:
+        if a.dim() == 3:
+            a, b = a[None], b[None]
+        if a.dim() != 4 or a.shape[3] != 3:
+            raise ValueError(f"uint8 images are HWC RGB [B,H,W,3] or [H,W,3], got {tuple(a.shape)}")
+        batch, h, w = a.shape[0], a.shape[1], a.shape[2]
+    else:
+        if a.dtype != torch.float32 or a.dim() != 4 or a.shape[1] != 3:
+            raise ValueError(f"images must be fp32 NCHW [B,3,H,W] or uint8 HWC, got {a.dtype} {tuple(a.shape)}")
+        batch, h, w = a.shape[0], a.shape[2], a.shape[3]
+    a, b = a.detach().contiguous(), b.detach().contiguous()
+    dev = a.device
+    L = N.lib()
+    nbytes = int(L.llie_image_metrics_scratch_bytes(batch, h, w))
+    if nbytes < 0:
+        N.check(nbytes, f"image_metrics: {batch} images of {h} x {w} (at least 1 image of 11 x 11)")
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(batch, 3, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        if u8:
+            rc = L.llie_image_metrics_u8(a.data_ptr(), b.data_ptr(), batch, h, w, out.data_ptr(), scratch.data_ptr(), nbytes, st)
+        else:
+            lo, hi = float(data_range[0]), float(data_range[1])
+            rc = L.llie_image_metrics_f32(a.data_ptr(), b.data_ptr(), batch, h, w, lo, hi, out.data_ptr(), scratch.data_ptr(), nbytes, st)
+    N.check(rc, "image_metrics")
+    return out
+
+
+def image_metrics(a: torch.Tensor, b: torch.Tensor, data_range: Tuple[float, float] = (-1.0, 1.0)) -> ImageMetrics:
+    """Device twin of image_metrics_host: fp32 NCHW [B,3,H,W] in `data_range`, or uint8 HWC [B,H,W,3] / [H,W,3], on a HIP device ->
+    ImageMetrics(mse, psnr, ssim), float64 device tensors [B].  Two launches on the current stream, no synchronisation; the
+    results are bitwise reproducible and do not depend on the batch an image is scored in."""
+    out = _metrics_out3(a, b, data_range)
+    return ImageMetrics(out[:, 0], out[:, 1], out[:, 2])
+
+
+# ------------------------------------------------------------------ evaluation over a validation set
+@contextmanager
+def _swapped_weights(model, weights: Optional[Sequence[torch.Tensor]]):
+    """Copies `weights` (in model.parameters() order) into the parameters for the duration of the block and restores the
+    original values afterwards, whatever happens inside (the reference's apply_shadow / restore).  The engine notices both
+    writes through its content check."""
+    if weights is None:
+        yield
+        return
+    params = list(model.parameters())
+    weights = list(weights)
+    if len(weights) != len(params):
+        raise ValueError(f"weights has {len(weights)} tensors, the model {len(params)} parameters")
+    for i, (p, w) in enumerate(zip(params, weights)):
+        if tuple(w.shape) != tuple(p.shape):
+            raise ValueError(f"weights[{i}] is {tuple(w.shape)}, the parameter {tuple(p.shape)}")
+    saved = [p.detach().clone() for p in params]
+    try:
+        with torch.no_grad():
+            for p, w in zip(params, weights):
+                p.data.copy_(w)
+        yield
+    finally:
+        with torch.no_grad():
+            for p, s in zip(params, saved):
+                p.data.copy_(s)
+
+
+def _steps_of(model, num_inference_steps: Optional[int], dev) -> Tuple[int, int]:
+    """(the argument `enhance` takes, the number of noise draws it consumes)."""
+    nsteps = model.num_inference_steps if num_inference_steps is None else int(num_inference_steps)
+    model.scheduler.set_timesteps(nsteps, device=dev)
+    return nsteps, len(model.scheduler._timestep_list)
+
+
+def _summary(names, triples: np.ndarray, loss: Optional[float]) -> Dict[str, object]:
+    mse, psnr, ssim = ([float(v) for v in triples[:, j]] for j in range(3))
+    n = len(names)
+    res: Dict[str, object] = {"n": n, "psnr": sum(psnr) / n, "ssim": sum(ssim) / n, "mse": sum(mse) / n}
+    if loss is not None:
+        res["loss"] = loss
+    res["per_image"] = {"filename": list(names), "psnr": psnr, "ssim": ssim, "mse": mse}
+    return res
+
+
+@torch.no_grad()
+def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[int] = None, seed: int = 0, loss: bool = True,
+             weights: Optional[Sequence[torch.Tensor]] = None) -> Dict[str, object]:
+    """PSNR / SSIM / MSE of `model.enhance` against the normal-light images of `loader` (normally a "val" DevicePairLoader:
+    centre crops in file order, last partial batch kept), and the validation loss of the reference's `LowLightTrainer.validate`.
+
+    Draw recipe (part of the contract; the global generator is neither read nor advanced):
+      g = torch.Generator(device=dev).manual_seed(seed); steps = the scheduler's step count for `num_inference_steps`
+      (default model.num_inference_steps); S = model.image_size; T = scheduler.config.num_train_timesteps.  Per batch of b images,
+      in loader order:
+        noise = torch.randn(steps, b, 3, S, S, generator=g, device=dev)
+        if loss:  t = torch.randint(0, T, (b,), generator=g, device=dev);  eps = torch.randn(b, 3, S, S, generator=g, device=dev)
+      `model.enhance(low_light, num_inference_steps, noise=noise)` is scored against `normal_light` by `image_metrics` in the
+      model's range (-1, 1); the batch loss is F.mse_loss(model.forward(low_light, normal_light, timesteps=t, noise=eps)
+      ["noise_pred"], eps) without gradients.
+
+    Returns {"n", "psnr", "ssim", "mse", ["loss",] "per_image": {"filename", "psnr", "ssim", "mse"}}: psnr / ssim / mse are the
+    means over images of the per-image values (float64 sums in file order), loss = sum of batch losses / len(loader).  Everything
+    stays on the device until one copy at the end.  `weights=` (e.g. FusedAdamW.ema_tensors(), in model.parameters() order) is
+    copied into the parameters for the call and the original values are restored afterwards, also when the call raises."""
+    if not isinstance(loader, DevicePairLoader):
+        raise ValueError(f"evaluate expects a DevicePairLoader, got {type(loader).__name__}")
+    dev = loader.store.device
+    if dev.type != "cuda":
+        raise RuntimeError(f"evaluate runs only on a HIP device (the frame store is on '{dev}'); there is no CPU fallback")
+    with _swapped_weights(model, weights):
+        s = int(model.image_size)
+        if loader.image_size != s:
+            raise ValueError(f"the loader crops {loader.image_size} x {loader.image_size}, the model takes {s} x {s}")
+        nsteps, steps = _steps_of(model, num_inference_steps, dev)
+        t_max = int(model.scheduler.config.num_train_timesteps)
+        g = torch.Generator(device=dev).manual_seed(int(seed))
+        names, triples, losses = [], [], []
+        for batch in loader:
+            low, normal = batch["low_light"], batch["normal_light"]
+            b = low.shape[0]
+            noise = torch.randn(steps, b, 3, s, s, generator=g, device=dev)
+            if loss:
+                t = torch.randint(0, t_max, (b,), generator=g, device=dev)
+                eps = torch.randn(b, 3, s, s, generator=g, device=dev)
+            triples.append(_metrics_out3(model.enhance(low, nsteps, noise=noise), normal, (-1.0, 1.0)))
+            if loss:
+                pred = model.forward(low, normal, timesteps=t, noise=eps)["noise_pred"]
+                losses.append(F.mse_loss(pred, eps).double().reshape(1))
+            names += list(batch["filename"])
+        if not triples:
+            raise ValueError("the loader yields no batch")
+        flat = torch.cat([torch.cat(triples).reshape(-1)] + losses).cpu().numpy()  # the one device-to-host copy
+    n = len(names)
+    total = float(sum(float(v) for v in flat[3 * n:]) / len(losses)) if loss else None
+    return _summary(names, flat[:3 * n].reshape(n, 3), total)
+
+
+@torch.no_grad()
+def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_steps: Optional[int] = None, seed: int = 0,
+                             overlap: Optional[int] = None, tile_batch: int = 32,
+                             weights: Optional[Sequence[torch.Tensor]] = None) -> Dict[str, object]:
+    """PSNR / SSIM / MSE at the images' own resolution: every low-light frame of the paired `store` (any sizes >= 11 x 11) goes
+    through `enhance_tiled` and is scored against its normal-light frame on the bytes (x = byte / 255).
+
+    Draw recipe: g = torch.Generator(device=dev).manual_seed(seed); per pair i, in file order, with (H, W) its size and S =
+    model.image_size:  canvas = torch.randn(steps, 3, max(H, S), max(W, S), generator=g, device=dev), then
+    enhance_tiled(model, store.frame(i), num_inference_steps, overlap=overlap, tile_batch=tile_batch, noise=canvas) against
+    store.frame(n + i).  Returns evaluate's dictionary without "loss"; `weights=` as there."""
+    if not isinstance(store, DeviceFrameStore) or not store.paired:
+        raise ValueError("evaluate_full_resolution expects a paired DeviceFrameStore")
+    dev = store.device
+    if dev.type != "cuda":
+        raise RuntimeError(f"evaluate_full_resolution runs only on a HIP device (the frame store is on '{dev}'); there is no CPU fallback")
+    with _swapped_weights(model, weights):
+        s = int(model.image_size)
+        nsteps, steps = _steps_of(model, num_inference_steps, dev)
+        g = torch.Generator(device=dev).manual_seed(int(seed))
+        n = len(store)
+        triples = []
+        for i, (h, w) in enumerate(store.sizes):
+            canvas = torch.randn(steps, 3, max(h, s), max(w, s), generator=g, device=dev)
+            out = enhance_tiled(model, store.frame(i), nsteps, overlap=overlap, tile_batch=tile_batch, noise=canvas)
+            triples.append(_metrics_out3(out, store.frame(n + i), None))
+        flat = torch.cat(triples).cpu().numpy()
+    return _summary(store.names, flat, None)

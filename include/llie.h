@@ -340,6 +340,27 @@ int llie_aug_pair_u8(const uint8_t* pool, const int64_t* table, int N, const lli
 int llie_aug_synth_u8(const uint8_t* pool, const int64_t* table, int N, const llie_aug_row* plan, int first, int count, int S,
                       const float* z, float* low, float* high, uint8_t* low_u8, uint8_t* high_u8, llie_stream stream);
 
+/* Image quality: per image of a against b, out3 [batch][3] doubles = {mse, psnr, ssim}.  All arithmetic is float64 on the mapped
+ * values: x = (v - lo) / (hi - lo) for fp32 NCHW [batch][3][H][W] (the model's range is lo = -1, hi = 1), x = byte / 255 for uint8
+ * HWC [batch][H][W][3].
+ *   window   g[k] = exp(-(k - 5)^2 / (2 * 1.5^2)), k = 0 .. 10, normalised to sum 1; the 2-D window is the outer product, applied
+ *            along the rows, then along the columns
+ *   ssim     (Wang et al. 2004, on RGB, no luma conversion) at each of the (H - 10) x (W - 10) positions whose 11 x 11 window lies
+ *            inside the image and for each channel: weighted means mx, my; biased variances sx2 = sum w x^2 - mx^2, sy2 likewise,
+ *            sxy = sum w x y - mx my;  map = (2 mx my + C1)(2 sxy + C2) / ((mx^2 + my^2 + C1)(sx2 + sy2 + C2)), C1 = 1e-4, C2 = 9e-4;
+ *            ssim = mean of the map over the 3 channels and all those positions
+ *   mse      mean of (x - y)^2 over all 3 H W values;  psnr = -10 log10(mse), +inf when mse == 0
+ * Tiles of 16 x 32 positions write partial sums into `scratch`; a second launch adds an image's partials in a fixed order.  No
+ * atomics: results are bitwise reproducible and an image's triple is the same bits alone or in a batch.  The host implementation
+ * in metrics.py is the definition; the two differ only in summation order.
+ * Checked before any HIP call: a NULL pointer, batch < 1, lo == hi (or not finite) return LLIE_ERR_ARG; H < 11 or W < 11
+ * LLIE_ERR_SHAPE; scratch_bytes below llie_image_metrics_scratch_bytes LLIE_ERR_WORKSPACE. */
+int64_t llie_image_metrics_scratch_bytes(int batch, int H, int W);
+int llie_image_metrics_f32(const float* a, const float* b, int batch, int H, int W, float lo, float hi, double* out3, void* scratch,
+                           int64_t scratch_bytes, llie_stream stream);
+int llie_image_metrics_u8(const uint8_t* a, const uint8_t* b, int batch, int H, int W, double* out3, void* scratch,
+                          int64_t scratch_bytes, llie_stream stream);
+
 /* ---- Kernel-level entry points (unit tests and tuning; SURVEY.md 8b "per-kernel entry points").
  * Activations are NHWC rows in the compute dtype T (llie_dtype); see DESIGN.md section 3.
  *

@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""PSNR / SSIM of a checkpoint on a paired validation folder, on the MI355X engine -- the sibling of scripts/inference.py.
+
+  python scripts/evaluate.py --data LOL/eval15 --checkpoint ckpt.pt [--full_resolution] [--per_image] [--output result.json]
+
+--data is the layout DeviceFrameStore.from_folder reads (ROOT/low and ROOT/high, or lowlight / dark and normal / bright).  By
+default every pair is centre-cropped to --image_size and goes through `evaluate` in batches of --batch_size (the result then
+also holds the validation loss); --full_resolution scores every image at its own size through `evaluate_full_resolution`
+(overlapping tiles, --tile_overlap / --tile_batch as in inference.py).  One JSON line is printed, and written to --output when
+given; the per-image lists are part of it only under --per_image.  --seed seeds every draw, so a run is reproducible.
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+import inference  # noqa: E402  (model loading is shared with the enhancement CLI)
+
+M = importlib.import_module("cv-diffusion-model_amd")
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Low-Light Enhancement Evaluation: PSNR / SSIM on a paired folder (HIP engine)")
+    p.add_argument("--data", type=str, required=True, help="paired data set root (low/ and high/ inside)")
+    p.add_argument("--checkpoint", type=str, default=None, help="PyTorch checkpoint")
+    p.add_argument("--variant", type=str, default="small")
+    p.add_argument("--image_size", type=int, default=256)
+    p.add_argument("--num_steps", type=int, default=4)
+    p.add_argument("--dtype", type=str, default="fp32", choices=["fp32", "fp16", "bf16"], help="engine precision")
+    p.add_argument("--device", type=str, default="cuda" if torch.cuda.is_available() else "cpu")
+    p.add_argument("--batch_size", type=int, default=8, help="images per enhance call (centre-crop evaluation)")
+    p.add_argument("--seed", type=int, default=0, help="seed of every noise draw")
+    p.add_argument("--full_resolution", action="store_true", help="score every image at its own size, enhanced as overlapping tiles")
+    p.add_argument("--tile_overlap", type=int, default=None, help="overlap of neighbouring tiles in pixels (default image_size // 8)")
+    p.add_argument("--tile_batch", type=int, default=32, help="tiles per enhance call")
+    p.add_argument("--per_image", action="store_true", help="keep the per-image lists in the result")
+    p.add_argument("--output", type=str, default=None, help="also write the JSON line to this file")
+    return p
+
+
+def parse_args(argv=None):
+    return build_parser().parse_args(argv)
+
+
+def main(argv=None) -> int:
+    args = parse_args(argv)
+    model = inference.load_model(argparse.Namespace(format="pytorch", **vars(args)))
+    if args.full_resolution:
+        store = M.DeviceFrameStore.from_folder(args.data, device=args.device)
+        res = M.evaluate_full_resolution(model, store, num_inference_steps=args.num_steps, seed=args.seed, overlap=args.tile_overlap,
+                                         tile_batch=args.tile_batch)
+    else:
+        store = M.DeviceFrameStore.from_folder(args.data, device=args.device, image_size=args.image_size)
+        loader = M.DevicePairLoader(store, args.batch_size, args.image_size, "val")
+        res = M.evaluate(model, loader, num_inference_steps=args.num_steps, seed=args.seed)
+    if not args.per_image:
+        del res["per_image"]
+    line = json.dumps(res)
+    print(line)
+    if args.output:
+        os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
+        with open(args.output, "w") as f:
+            f.write(line + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
