@@ -25,6 +25,8 @@ from .tiling import (tile_origins, gather_tiles_array, blend_tiles_array, gather
 from .data import (DeviceFrameStore, DevicePairLoader, create_device_dataloaders, epoch_plan, augment_pairs_host, augment_synth_host,
                    augment_pairs_device, augment_synth_device)
 from .metrics import ImageMetrics, image_metrics, image_metrics_host, evaluate, evaluate_full_resolution
+from .trainer import (TrainingConfig, LowLightTrainer, train_model, make_lr_scheduler, build_checkpoint, comparison_grid,
+                      comparison_grid_host)
 
 __all__ = [
     "EfficientUNet", "EfficientUNetConfig", "create_efficient_unet", "InvertedResidualBlock", "LinearAttention", "SqueezeExcitation",
@@ -37,4 +39,6 @@ __all__ = [
     "DeviceFrameStore", "DevicePairLoader", "create_device_dataloaders", "epoch_plan", "augment_pairs_host", "augment_synth_host",
     "augment_pairs_device", "augment_synth_device",
     "ImageMetrics", "image_metrics", "image_metrics_host", "evaluate", "evaluate_full_resolution",
+    "TrainingConfig", "LowLightTrainer", "train_model", "make_lr_scheduler", "build_checkpoint", "comparison_grid",
+    "comparison_grid_host",
 ]

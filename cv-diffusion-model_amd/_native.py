@@ -35,7 +35,7 @@ EXPORTS = [
     "llie_final_bwd_data",
     "llie_tile_count", "llie_tile_origins", "llie_tile_gather_u8", "llie_tile_gather_f32", "llie_tile_blend_u8",
     "llie_aug_pair_u8", "llie_aug_synth_u8",
-    "llie_image_metrics_scratch_bytes", "llie_image_metrics_f32", "llie_image_metrics_u8",
+    "llie_image_metrics_scratch_bytes", "llie_image_metrics_f32", "llie_image_metrics_u8", "llie_comparison_grid_u8",
     "llie_upconv_fold_elems", "llie_upconv_fold_weights", "llie_conv3x3_upfold", "llie_conv3x3_upfold_tiles",
     "llie_expand_dw", "llie_expand_pool", "llie_expand_dw_project", "llie_expand_dw_project_skip", "llie_irbx_project_tiles",
     "llie_expand_stats", "llie_irbx_stats_rows",
@@ -165,6 +165,7 @@ def lib() -> C.CDLL:
     L.llie_image_metrics_scratch_bytes.restype = i64
     L.llie_image_metrics_f32.argtypes = [vp, vp, ci, ci, ci, C.c_float, C.c_float, vp, vp, i64, vp]
     L.llie_image_metrics_u8.argtypes = [vp, vp, ci, ci, ci, vp, vp, i64, vp]
+    L.llie_comparison_grid_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
     L.llie_pw_gemm.argtypes = [ci, C.POINTER(GemmSeg), ci, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     L.llie_pw_gemm_tile_rows.argtypes = [ci]
     L.llie_pw_expand.argtypes = [ci, C.POINTER(GemmSeg), ci, vp, vp, vp, vp, ci, ci, ci, vp]

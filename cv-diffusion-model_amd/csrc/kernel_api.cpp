@@ -346,6 +346,13 @@ int llie_image_metrics_u8(const uint8_t* a, const uint8_t* b, int batch, int H, 
   return kerr("image_metrics_u8", launch_image_metrics_u8(a, b, batch, H, W, out3, reinterpret_cast<double*>(scratch), hs(stream)));
 }
 
+// ---- the trainer's sample sheet (samples.hip): arguments are checked here, before any HIP call
+int llie_comparison_grid_u8(const float* low, const float* enhanced, const float* normal, int n, int H, int W, uint8_t* grid,
+                            llie_stream stream) {
+  if (!low || !enhanced || !normal || !grid || !comparison_grid_ok(n, H, W)) return LLIE_ERR_ARG;
+  return kerr("comparison_grid_u8", launch_comparison_grid_u8(low, enhanced, normal, n, H, W, grid, hs(stream)), LLIE_ERR_ARG, nullptr);
+}
+
 int llie_time_embed(llie_ctx* c, const int64_t* t, int rows, float* emb, float* temb, float* silu_temb, llie_stream stream) {
   if (!c || !t || !temb || !silu_temb || rows <= 0 || c->cfg.kind != LLIE_UNET) return LLIE_ERR_ARG;
   if (int rc = check_loaded(c)) return rc;

@@ -628,4 +628,19 @@ hipError_t launch_image_metrics_f32(const float* a, const float* b, int batch, i
                                     hipStream_t s);
 hipError_t launch_image_metrics_u8(const uint8_t* a, const uint8_t* b, int batch, int H, int W, double* out3, double* partial, hipStream_t s);
 
+// (14) the trainer's sample sheet (samples.hip): low / enhanced / normal fp32 NCHW [n][3][H][W] in the model's range -> one uint8
+// HWC picture [3 (H+2) + 2][n (W+2) + 2][3], torchvision's make_grid(cat([low, enhanced, normal]), nrow=n) with padding 2 and pad
+// value 0, then save_image's bytes: image (row r, column k) has its top-left pixel at (r (H+2) + 2, k (W+2) + 2), every other byte
+// is 0, byte = trunc(min(max(((x + 1) / 2) * 255 + 0.5, 0), 255)) in separate fp32 operations, NaN -> 0.
+constexpr int kGridPad = 2;
+__host__ __device__ inline int comparison_grid_rows(int H) { return 3 * (H + kGridPad) + kGridPad; }
+__host__ __device__ inline int comparison_grid_cols(int n, int W) { return n * (W + kGridPad) + kGridPad; }
+inline bool comparison_grid_ok(int n, int H, int W) {  // sizes whose picture and inputs index within int / size_t arithmetic
+  if (n < 1 || H < 1 || W < 1) return false;
+  return 3ll * (H + kGridPad) + kGridPad < (1ll << 31) && (long long)n * (W + kGridPad) + kGridPad < (1ll << 31);
+}
+// a null pointer or n, H, W < 1: hipErrorInvalidValue
+hipError_t launch_comparison_grid_u8(const float* low, const float* enhanced, const float* normal, int n, int H, int W, uint8_t* grid,
+                                     hipStream_t s);
+
 }  // namespace llie

@@ -1,0 +1,476 @@
+"""The reference's training loop (src/training/trainer.py: TrainingConfig, LowLightTrainer, train_model) on the HIP engine.
+
+It joins what the package already has -- `TrainStep` (the step), `FusedAdamW` (clip, AdamW, EMA), `FusedGradScaler` (fp16 loss
+scaling), `DevicePairLoader` (data), `evaluate` (validation) and `hostio` (checkpoints, PNG files) -- with torch's own
+`CosineAnnealingLR` / `OneCycleLR`, into epochs that write the reference's checkpoints (`checkpoint_epoch_{e}.pt`,
+`best_model.pt`, `final_model.pt`, read by scripts/inference.py and scripts/evaluate.py) and its per-epoch sample sheets
+(`samples_epoch_{e}.png`).  The step itself is untouched; the one piece of device work added here is the sample sheet.
+
+The sample sheet.  `comparison_grid_host` is the definition, written from torchvision's documented algorithm (torchvision is not
+available to pin it against): `make_grid(cat([low, enhanced, normal]), nrow=n)` with the defaults padding = 2, pad_value = 0,
+followed by `save_image`'s quantisation.  For n images of H x W per row the picture is uint8 HWC [3 (H+2) + 2][n (W+2) + 2][3]; the
+image of row r (0 low-light, 1 enhanced, 2 normal-light) and column k has its top-left pixel at (r (H+2) + 2, k (W+2) + 2) and
+every other byte is 0.  A pixel is, in separate fp32 operations,
+    v = (x + 1) / 2;  q = v * 255 + 0.5;  q = min(max(q, 0), 255)  (NaN -> 0);  byte = trunc(q)
+`comparison_grid` is the same on the device (csrc/samples.hip, one launch), bit for bit, and has no CPU fallback.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from pathlib import Path
+from typing import Dict, List, Optional
+
+import numpy as np
+import torch
+from torch.optim.lr_scheduler import CosineAnnealingLR, OneCycleLR
+
+from . import _native as N
+from . import hostio
+from .data import create_device_dataloaders
+from .metrics import _require_hip, _steps_of, _swapped_weights, evaluate
+from .pipeline import LowLightDiffusion
+from .training import FusedAdamW, FusedGradScaler, TrainStep
+
+try:
+    import wandb
+    HAS_WANDB = True
+except ImportError:
+    HAS_WANDB = False
+    wandb = None
+
+GRID_PADDING = 2  # kGridPad (csrc/kernels.h): make_grid's default
+SAMPLE_STEPS = 4  # generate_samples enhances with 4 steps whatever the config says (trainer.py:380)
+
+
+@dataclass
+class TrainingConfig:
+    """The reference's TrainingConfig (trainer.py:36-83), field for field, then this build's extensions."""
+
+    # Model
+    unet_variant: str = "small"
+    image_size: int = 256
+    num_inference_steps: int = 4
+
+    # Training
+    epochs: int = 100
+    batch_size: int = 8
+    learning_rate: float = 1e-4
+    weight_decay: float = 0.01
+    gradient_clip: float = 1.0
+
+    # LR Scheduler
+    scheduler_type: str = "cosine"  # "cosine" or "onecycle"
+    warmup_epochs: int = 5
+    min_lr: float = 1e-6
+
+    # Mixed Precision: fp16 with a loss scaler, as the reference's autocast + GradScaler
+    use_amp: bool = True
+
+    # EMA
+    use_ema: bool = True
+    ema_decay: float = 0.9999
+
+    # Loss
+    loss_type: str = "mse"  # "mse", "huber", "l1"
+
+    # Logging
+    log_interval: int = 100  # batches; 0 = no progress line (and no host synchronisation inside an epoch)
+    save_interval: int = 5  # epochs
+    sample_interval: int = 1  # epochs
+    num_samples: int = 4
+
+    # Paths
+    output_dir: str = "outputs"
+    checkpoint_dir: str = "checkpoints"
+
+    # Wandb
+    use_wandb: bool = False
+    wandb_project: str = "low-light-diffusion"
+    wandb_run_name: Optional[str] = None
+
+    # Resume
+    resume_from: Optional[str] = None
+
+    # ---- extensions
+    compute_dtype: Optional[str] = None  # engine precision "fp32" | "fp16" | "bf16"; None: "fp16" with use_amp, else "fp32"
+    seed: int = 0  # seeds every draw of the trainer (steps, validation, samples)
+    use_synthetic: bool = False  # train_model: SyntheticLowLightDataset's degradation over the images in train_data_dir
+    progress: bool = True  # print the progress and epoch lines
+
+
+def resolved_compute_dtype(config: TrainingConfig) -> str:
+    """The engine precision a config asks for: `compute_dtype`, or "fp16" / "fp32" by `use_amp`."""
+    if config.compute_dtype is not None:
+        return ("fp32", "fp16", "bf16")[N.dtype_code(config.compute_dtype)]  # ValueError for anything else
+    return "fp16" if config.use_amp else "fp32"
+
+
+def make_lr_scheduler(optimizer: torch.optim.Optimizer, config: TrainingConfig, steps_per_epoch: int):
+    """The reference's schedule (trainer.py:158-175), its arithmetic kept as it is: total = steps_per_epoch * epochs, warmup =
+    steps_per_epoch * warmup_epochs; "cosine" is CosineAnnealingLR(T_max=max(1, total - warmup), eta_min=min_lr) -- the warm-up
+    only shortens the period, nothing ramps up -- and anything else OneCycleLR(max_lr=learning_rate, total_steps=total,
+    pct_start=warmup / total).  It is stepped once per batch."""
+    total_steps = steps_per_epoch * config.epochs
+    warmup_steps = steps_per_epoch * config.warmup_epochs
+    if config.scheduler_type == "cosine":
+        return CosineAnnealingLR(optimizer, T_max=max(1, total_steps - warmup_steps), eta_min=config.min_lr)
+    return OneCycleLR(optimizer, max_lr=config.learning_rate, total_steps=total_steps, pct_start=warmup_steps / total_steps)
+
+
+def train_draw_seed(seed: int, epoch: int) -> int:
+    """Seed of the device generator an epoch's (timesteps, noise) come from."""
+    return (int(seed) * 1000003 + int(epoch) * 8191 + 54321) % (2 ** 63 - 1)
+
+
+def sample_draw_seed(seed: int, epoch: int) -> int:
+    """Seed of the device generator an epoch's sample sheet draws its `enhance` noise from."""
+    return (int(seed) * 1000003 + int(epoch) * 8191 + 65432) % (2 ** 63 - 1)
+
+
+# ------------------------------------------------------------------ the sample sheet
+def _grid_inputs(low, enhanced, normal, to_array):
+    imgs = [to_array(v) for v in (low, enhanced, normal)]
+    shape = tuple(imgs[0].shape)
+    if len(shape) != 4 or shape[1] != 3 or shape[0] < 1 or shape[2] < 1 or shape[3] < 1:
+        raise ValueError(f"images are NCHW [n,3,H,W] with n, H, W >= 1, got {shape}")
+    for v in imgs[1:]:
+        if tuple(v.shape) != shape:
+            raise ValueError(f"the three image batches must have one shape, got {shape} and {tuple(v.shape)}")
+    return imgs, shape
+
+
+def comparison_grid_host(low, enhanced, normal) -> np.ndarray:
+    """The definition of the module docstring: three fp32 [n,3,H,W] batches in the model's range -> uint8 [3 (H+2) + 2,
+    n (W+2) + 2, 3]."""
+    imgs, (n, _, h, w) = _grid_inputs(low, enhanced, normal, lambda v: np.asarray(v, dtype=np.float32))
+    p = GRID_PADDING
+    grid = np.zeros((3 * (h + p) + p, n * (w + p) + p, 3), dtype=np.uint8)
+    one, two, half, top = np.float32(1.0), np.float32(2.0), np.float32(0.5), np.float32(255.0)
+    for r, x in enumerate(imgs):
+        with np.errstate(invalid="ignore", over="ignore"):
+            q = ((x + one) / two) * top + half
+            assert q.dtype == np.float32
+            q = np.where(np.isnan(q), np.float32(0.0), np.minimum(np.maximum(q, np.float32(0.0)), top))
+        byte = np.trunc(q).astype(np.uint8).transpose(0, 2, 3, 1)  # [n,H,W,3]
+        for k in range(n):
+            y0, x0 = r * (h + p) + p, k * (w + p) + p
+            grid[y0:y0 + h, x0:x0 + w] = byte[k]
+    return grid
+
+
+def comparison_grid(low: torch.Tensor, enhanced: torch.Tensor, normal: torch.Tensor) -> torch.Tensor:
+    """Device twin of comparison_grid_host: three fp32 [n,3,H,W] tensors on a HIP device -> uint8 [3 (H+2) + 2, n (W+2) + 2, 3] on
+    that device.  One launch on the current stream, no synchronisation, bit-exact with the host twin."""
+    for t in (low, enhanced, normal):
+        _require_hip(t, "comparison_grid")
+
+    def dev_array(t):
+        if t.dtype != torch.float32:
+            raise ValueError(f"images must be fp32 NCHW [n,3,H,W], got {t.dtype}")
+        return t.detach().contiguous()
+
+    (low, enhanced, normal), (n, _, h, w) = _grid_inputs(low, enhanced, normal, dev_array)
+    dev = low.device
+    if enhanced.device != dev or normal.device != dev:
+        raise ValueError("the three image batches must be on one device")
+    p = GRID_PADDING
+    grid = torch.empty(3 * (h + p) + p, n * (w + p) + p, 3, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        N.check(N.lib().llie_comparison_grid_u8(low.data_ptr(), enhanced.data_ptr(), normal.data_ptr(), n, h, w, grid.data_ptr(),
+                                                torch.cuda.current_stream(dev).cuda_stream), "comparison_grid")
+    return grid
+
+
+# ------------------------------------------------------------------ checkpoints
+CHECKPOINT_KEYS = ("epoch", "global_step", "model_state_dict", "optimizer_state_dict", "scheduler_state_dict", "best_val_loss", "config")
+
+
+def build_checkpoint(*, epoch: int, global_step: int, model: torch.nn.Module, optimizer: torch.optim.Optimizer, scheduler,
+                     best_val_loss: float, config: TrainingConfig, ema_shadow: Optional[Dict[str, torch.Tensor]] = None,
+                     scaler=None) -> dict:
+    """The reference's checkpoint dictionary (trainer.py:418-434): CHECKPOINT_KEYS, plus "ema_shadow" ({parameter name: tensor},
+    EMAModel.shadow's layout) when given and "scaler_state_dict" when there is a scaler.  "optimizer_state_dict" has
+    torch.optim.AdamW's layout: FusedAdamW's flat copy of the shadows is left out, they are stored once, by name.  Everything in
+    it loads with torch.load(weights_only=True)."""
+    opt_sd = dict(optimizer.state_dict())
+    opt_sd.pop("ema_shadow_flat", None)
+    ckpt = {
+        "epoch": int(epoch),
+        "global_step": int(global_step),
+        "model_state_dict": model.state_dict(),
+        "optimizer_state_dict": opt_sd,
+        "scheduler_state_dict": scheduler.state_dict(),
+        "best_val_loss": float(best_val_loss),
+        "config": dict(config.__dict__),
+    }
+    if ema_shadow is not None:
+        ckpt["ema_shadow"] = dict(ema_shadow)
+    if scaler is not None:
+        ckpt["scaler_state_dict"] = scaler.state_dict()
+    return ckpt
+
+
+# ------------------------------------------------------------------ the trainer
+def _loader_device(loader) -> torch.device:
+    store = getattr(loader, "store", None)
+    dev = getattr(store, "device", None)
+    if dev is None:
+        raise ValueError(f"a loader is a DevicePairLoader (create_device_dataloaders), got {type(loader).__name__}")
+    return torch.device(dev)
+
+
+class LowLightTrainer:
+    """The reference's LowLightTrainer (trainer.py:121-456) over the engine: same constructor, methods, schedule of
+    validation / checkpoints / samples and checkpoint layout.
+
+    `model` is a LowLightDiffusion on a HIP device, the loaders are DevicePairLoaders on the same device; there is no CPU
+    fallback.  The engine runs in `resolved_compute_dtype(config)`; a FusedGradScaler exists only for fp16.  Every draw comes
+    from generators seeded from (config.seed, epoch): the global generator is neither read nor advanced, and a resumed run
+    continues bit for bit."""
+
+    def __init__(self, model: LowLightDiffusion, train_loader, val_loader=None, config: Optional[TrainingConfig] = None):
+        self.config = config or TrainingConfig()
+        cfg = self.config
+        params = list(model.parameters())
+        places = [("the model", params[0].device if params else torch.device("cpu")), ("train_loader", _loader_device(train_loader))]
+        if val_loader is not None:
+            places.append(("val_loader", _loader_device(val_loader)))
+        for what, dev in places:
+            if dev.type != "cuda":
+                raise RuntimeError(f"LowLightTrainer runs only on a HIP device ({what} is on '{dev}'); there is no CPU fallback")
+        self.device = places[0][1]
+        for what, dev in places[1:]:
+            if dev != self.device:
+                raise ValueError(f"{what} is on {dev}, the model on {self.device}")
+        if len(train_loader) < 1:
+            raise ValueError("train_loader yields no batch (fewer pairs than batch_size: the last partial batch is dropped)")
+        dtype = resolved_compute_dtype(cfg)
+
+        self.model = model
+        self.model.compute_dtype = dtype
+        self.train_loader = train_loader
+        self.val_loader = val_loader
+
+        self.optimizer = FusedAdamW(model.parameters(), lr=cfg.learning_rate, weight_decay=cfg.weight_decay,
+                                    max_grad_norm=cfg.gradient_clip, ema_decay=cfg.ema_decay if cfg.use_ema else None)
+        self.scheduler = make_lr_scheduler(self.optimizer, cfg, len(train_loader))
+        self.scaler = FusedGradScaler() if dtype == "fp16" else None
+        self.step = TrainStep(model, self.optimizer, loss_type=cfg.loss_type, grad_scaler=self.scaler)
+        self._names = [name for name, _ in model.named_parameters()]
+
+        self.epoch = 0
+        self.global_step = 0
+        self.best_val_loss = float("inf")
+        self.last_validation: Optional[Dict[str, object]] = None  # evaluate()'s result of the latest validate()
+
+        self.output_dir = Path(cfg.output_dir)
+        self.checkpoint_dir = Path(cfg.checkpoint_dir)
+        self.output_dir.mkdir(parents=True, exist_ok=True)
+        self.checkpoint_dir.mkdir(parents=True, exist_ok=True)
+
+        if cfg.use_wandb:
+            if not HAS_WANDB:
+                print("Warning: wandb not installed. Logging disabled.")
+                cfg.use_wandb = False
+            else:
+                wandb.init(project=cfg.wandb_project, name=cfg.wandb_run_name, config=cfg.__dict__)
+
+        if cfg.resume_from:
+            self.load_checkpoint(cfg.resume_from)
+
+    def _say(self, *a, **kw) -> None:
+        if self.config.progress:
+            print(*a, **kw)
+
+    def _ema_weights(self) -> Optional[List[torch.Tensor]]:
+        return self.optimizer.ema_tensors() if self.config.use_ema else None
+
+    # ------------------------------------------------------------------ epochs
+    def train(self, on_epoch=None) -> List[Dict[str, object]]:
+        """The reference's loop (trainer.py:216-267): per epoch train, validate when there is a val loader, write
+        checkpoint_epoch_{e}.pt when (e + 1) % save_interval == 0, best_model.pt on a strictly lower validation loss and the
+        sample sheet when (e + 1) % sample_interval == 0; final_model.pt at the end.  Returns one dictionary per epoch run:
+        {"epoch", "train_loss", "lr", "val_loss", "psnr", "ssim"} (the last three None without a val loader)."""
+        cfg = self.config
+        self._say(f"Starting training on {self.device}")
+        self._say(f"Model parameters: {self.model.get_model_size()}")
+        history = []
+        for epoch in range(self.epoch, cfg.epochs):
+            self.epoch = epoch
+            train_loss = self.train_epoch()
+            val_loss = self.validate() if self.val_loader is not None else None
+            log = {"epoch": epoch, "train_loss": train_loss, "lr": self.optimizer.param_groups[0]["lr"], "val_loss": val_loss,
+                   "psnr": self.last_validation["psnr"] if val_loss is not None else None,
+                   "ssim": self.last_validation["ssim"] if val_loss is not None else None}
+            history.append(log)
+            if on_epoch is not None:
+                on_epoch(log)
+            line = f"Epoch {epoch}: train_loss={train_loss:.4f}"
+            if val_loss is not None:
+                line += f", val_loss={val_loss:.4f}, psnr={log['psnr']:.2f}, ssim={log['ssim']:.4f}"
+            self._say(line)
+            if cfg.use_wandb:
+                wandb.log({k: v for k, v in log.items() if v is not None})
+            if (epoch + 1) % cfg.save_interval == 0:
+                self.save_checkpoint(f"checkpoint_epoch_{epoch}.pt")
+            if val_loss is not None and val_loss < self.best_val_loss:
+                self.best_val_loss = val_loss
+                self.save_checkpoint("best_model.pt")
+            if (epoch + 1) % cfg.sample_interval == 0:
+                self.generate_samples(epoch)
+        self.save_checkpoint("final_model.pt")
+        if cfg.use_wandb:
+            wandb.finish()
+        return history
+
+    def train_epoch(self) -> float:
+        """One epoch (trainer.py:269-338) of TrainStep over the train loader.
+
+        Draw recipe (part of the contract; the global generator is neither read nor advanced):
+          train_loader.set_epoch(epoch); dev = the model's device; S = config.image_size; T = scheduler.config.num_train_timesteps;
+          g = torch.Generator(device=dev).manual_seed((seed * 1000003 + epoch * 8191 + 54321) % (2 ** 63 - 1))
+          per batch of b pairs, in loader order, the reference's order of draws (low_light_diffusion.py: timesteps, then noise):
+            t = torch.randint(0, T, (b,), generator=g, device=dev)
+            noise = torch.randn(b, 3, S, S, generator=g, device=dev)
+            loss = step(low_light, normal_light, timesteps=t, noise=noise);  lr_scheduler.step()
+        The LR schedule moves once per batch, after the step, also when a grad scaler skipped the step.  The losses go into a
+        device buffer that is copied once, after the last batch; nothing else waits for the device, except the progress line
+        (every `log_interval` batches; `log_interval = 0` or `progress = False` without wandb turns it off).  Returns the
+        Python-float sum of the fp32 batch losses in step order, divided by len(train_loader) (trainer.py:325,338)."""
+        cfg, dev, loader = self.config, self.device, self.train_loader
+        self.model.train()
+        loader.set_epoch(self.epoch)
+        s, t_max = int(cfg.image_size), int(self.model.scheduler.config.num_train_timesteps)
+        g = torch.Generator(device=dev).manual_seed(train_draw_seed(cfg.seed, self.epoch))
+        n = len(loader)
+        losses = torch.zeros(n, dtype=torch.float32, device=dev)
+        report = cfg.log_interval > 0 and (cfg.progress or cfg.use_wandb)
+        for batch_idx, batch in enumerate(loader):
+            low, normal = batch["low_light"], batch["normal_light"]
+            b = low.shape[0]
+            t = torch.randint(0, t_max, (b,), generator=g, device=dev)
+            noise = torch.randn(b, 3, s, s, generator=g, device=dev)
+            loss = self.step(low, normal, timesteps=t, noise=noise)
+            # TrainStep steps through step_flat, not optimizer.step(), which torch's scheduler watches to warn about a
+            # schedule that moves before the optimiser: the optimiser has stepped
+            self.optimizer._opt_called = True
+            self.scheduler.step()
+            losses[batch_idx].copy_(loss)
+            self.global_step += 1
+            if report and batch_idx % cfg.log_interval == 0:
+                value = loss.item()
+                self._say(f"Epoch {self.epoch} [{batch_idx + 1}/{n}] loss={value:.4f}")
+                if cfg.use_wandb:
+                    wandb.log({"train_loss_step": value, "lr": self.optimizer.param_groups[0]["lr"], "global_step": self.global_step})
+        total = 0.0
+        for v in losses.cpu().tolist():  # the one device-to-host copy
+            total += v
+        return total / n
+
+    @torch.no_grad()
+    def validate(self) -> float:
+        """`evaluate(model, val_loader, num_inference_steps=config.num_inference_steps, seed=config.seed)` on the EMA weights
+        when EMA is on: returns its "loss" (the reference's validation loss, trainer.py:340-363, with seeded draws: the same
+        weights always give the same loss) and keeps the whole result in `last_validation` (PSNR / SSIM for the epoch's log line).
+        Parameters, optimiser state and the model's train() / eval() mode are as before afterwards."""
+        if self.val_loader is None:
+            raise ValueError("validate needs a val_loader")
+        mode = self.model.training
+        try:
+            res = evaluate(self.model, self.val_loader, num_inference_steps=self.config.num_inference_steps, seed=self.config.seed,
+                           weights=self._ema_weights())
+        finally:
+            self.model.train(mode)
+        self.last_validation = res
+        return res["loss"]
+
+    @torch.no_grad()
+    def generate_samples(self, epoch: int) -> Path:
+        """The sample sheet of trainer.py:365-410: the first `num_samples` pairs of the first batch of `val_loader or
+        train_loader`, enhanced with 4 steps on the EMA weights (when EMA is on), as output_dir/samples_epoch_{epoch}.png (rows:
+        low-light, enhanced, normal-light).
+
+        Draws: g = torch.Generator(device=dev).manual_seed((seed * 1000003 + epoch * 8191 + 65432) % (2 ** 63 - 1));
+        noise = torch.randn(steps, n, 3, S, S, generator=g, device=dev) with steps the scheduler's step count for 4.
+        The loader's epoch counter, the parameters and the model's mode are as before afterwards."""
+        cfg, dev = self.config, self.device
+        loader = self.val_loader or self.train_loader
+        loader_epoch = loader.epoch
+        try:
+            batch = next(iter(loader))
+        finally:
+            loader.set_epoch(loader_epoch)  # the peek is not an epoch
+        low = batch["low_light"][:cfg.num_samples].contiguous()
+        normal = batch["normal_light"][:cfg.num_samples].contiguous()
+        mode = self.model.training
+        try:
+            with _swapped_weights(self.model, self._ema_weights()):
+                nsteps, steps = _steps_of(self.model, SAMPLE_STEPS, dev)
+                g = torch.Generator(device=dev).manual_seed(sample_draw_seed(cfg.seed, epoch))
+                noise = torch.randn(steps, low.shape[0], 3, low.shape[2], low.shape[3], generator=g, device=dev)
+                enhanced = self.model.enhance(low, nsteps, noise=noise)
+                grid = comparison_grid(low, enhanced, normal).cpu().numpy()  # the one device-to-host copy
+        finally:
+            self.model.train(mode)
+        path = self.output_dir / f"samples_epoch_{epoch}.png"
+        hostio.save_image(str(path), grid)
+        if cfg.use_wandb:
+            wandb.log({"samples": wandb.Image(str(path))})
+        return path
+
+    # ------------------------------------------------------------------ checkpoints
+    def ema_shadow(self) -> Optional[Dict[str, torch.Tensor]]:
+        """{parameter name as in model.named_parameters(): shadow weight} (copies), the reference's EMAModel.shadow; None
+        without EMA."""
+        if not self.config.use_ema:
+            return None
+        return {name: t.clone() for name, t in zip(self._names, self.optimizer.ema_tensors())}
+
+    def checkpoint(self) -> dict:
+        return build_checkpoint(epoch=self.epoch, global_step=self.global_step, model=self.model, optimizer=self.optimizer,
+                                scheduler=self.scheduler, best_val_loss=self.best_val_loss, config=self.config,
+                                ema_shadow=self.ema_shadow(), scaler=self.scaler)
+
+    def save_checkpoint(self, filename: str) -> None:
+        torch.save(self.checkpoint(), self.checkpoint_dir / filename)
+        self._say(f"Saved checkpoint: {filename}")
+
+    def load_checkpoint(self, path: str) -> None:
+        """trainer.py:437-456: continues after the saved epoch.  Read with weights_only=True (nothing from the file is
+        executed).  The EMA shadows are copied by name; a name the model does not have, or one of its names missing from the
+        file, is a ValueError."""
+        ckpt = torch.load(path, map_location=self.device, weights_only=True)
+        shadow = ckpt.get("ema_shadow") if self.config.use_ema else None
+        if shadow is not None:
+            missing = [k for k in self._names if k not in shadow]
+            unexpected = [k for k in shadow if k not in set(self._names)]
+            if missing or unexpected:
+                raise ValueError(f"ema_shadow does not fit the model: missing {missing[:5]}, unexpected {unexpected[:5]}")
+        self.epoch = ckpt["epoch"] + 1
+        self.global_step = ckpt["global_step"]
+        self.best_val_loss = ckpt["best_val_loss"]
+        self.model.load_state_dict(ckpt["model_state_dict"])
+        self.optimizer.load_state_dict(ckpt["optimizer_state_dict"])
+        self.scheduler.load_state_dict(ckpt["scheduler_state_dict"])
+        if shadow is not None:
+            with torch.no_grad():
+                for name, dst in zip(self._names, self.optimizer.ema_tensors()):
+                    dst.copy_(shadow[name])
+        if self.scaler is not None and "scaler_state_dict" in ckpt:
+            self.scaler.load_state_dict(ckpt["scaler_state_dict"])
+        self._say(f"Loaded checkpoint from epoch {self.epoch - 1}")
+
+
+def train_model(train_data_dir: str, val_data_dir: Optional[str] = None, config: Optional[TrainingConfig] = None,
+                device="cuda") -> LowLightTrainer:
+    """Training entry point (trainer.py:459-496): loaders from the folders (create_device_dataloaders), a fresh model, a trainer,
+    `train()`; returns the trainer."""
+    config = config or TrainingConfig()
+    train_loader, val_loader = create_device_dataloaders(train_root=train_data_dir, val_root=val_data_dir, batch_size=config.batch_size,
+                                                         image_size=config.image_size, use_synthetic=config.use_synthetic,
+                                                         device=device, seed=config.seed)
+    model = LowLightDiffusion(unet_variant=config.unet_variant, image_size=config.image_size,
+                              num_inference_steps=config.num_inference_steps).to(train_loader.store.device)
+    trainer = LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config)
+    trainer.train()
+    return trainer

@@ -361,6 +361,19 @@ int llie_image_metrics_f32(const float* a, const float* b, int batch, int H, int
 int llie_image_metrics_u8(const uint8_t* a, const uint8_t* b, int batch, int H, int W, double* out3, void* scratch,
                           int64_t scratch_bytes, llie_stream stream);
 
+/* The trainer's per-epoch sample sheet (LowLightTrainer.generate_samples / _save_comparison, src/training/trainer.py:365-410):
+ * torchvision's make_grid(cat([low, enhanced, normal]), nrow=n) with its defaults (padding 2, pad value 0) followed by
+ * save_image's quantisation, in one launch.
+ *   low / enhanced / normal: fp32 NCHW [n][3][H][W] in the model's range (-1, 1)
+ *   grid: uint8 HWC RGB [3 (H+2) + 2][n (W+2) + 2][3].  The image of row r (0 low, 1 enhanced, 2 normal) and column k has its
+ *         top-left pixel at (r (H+2) + 2, k (W+2) + 2); every other byte is 0.
+ *   byte: v = (x + 1.0f) / 2.0f; q = v * 255.0f + 0.5f; q = min(max(q, 0), 255) (NaN -> 0); (uint8) trunc(q)
+ * Separate fp32 operations without fused multiply-adds: bit-exact with comparison_grid_host in trainer.py, which is the definition
+ * (written from torchvision's documented algorithm; torchvision itself is not available to pin it against).
+ * Checked before any HIP call: a NULL pointer or n, H, W < 1 return LLIE_ERR_ARG. */
+int llie_comparison_grid_u8(const float* low, const float* enhanced, const float* normal, int n, int H, int W, uint8_t* grid,
+                            llie_stream stream);
+
 /* ---- Kernel-level entry points (unit tests and tuning; SURVEY.md 8b "per-kernel entry points").
  * Activations are NHWC rows in the compute dtype T (llie_dtype); see DESIGN.md section 3.
  *

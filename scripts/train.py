@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""Training on the MI355X engine -- the reference's scripts/train.py over LowLightTrainer and the device-resident loaders.
+
+  python scripts/train.py --data_dir LOL/our485 --val_dir LOL/eval15 --epochs 100 --use_ema [--use_amp | --dtype bf16]
+
+--data_dir / --val_dir are the layout DeviceFrameStore.from_folder reads (ROOT/low and ROOT/high, or lowlight / dark and
+normal / bright); a --val_dir that does not exist trains without validation, as the reference's create_dataloaders does.  With
+--use_synthetic the normal-light images lie in --data_dir itself and the low-light twin is made on the device.  --use_amp is
+the reference's fp16 with a loss scaler; --dtype pins the engine precision instead (bf16 needs no scaler).  --seed seeds every
+draw, so a run is reproducible and --resume continues it bit for bit.  Checkpoints (checkpoint_epoch_{e}.pt, best_model.pt,
+final_model.pt under --checkpoint_dir) are what scripts/inference.py and scripts/evaluate.py read; the per-epoch sample sheets go
+to --output_dir.  One JSON line per epoch is printed: epoch, train_loss, lr, val_loss, psnr, ssim.
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+M = importlib.import_module("cv-diffusion-model_amd")
+
+
+def build_parser() -> argparse.ArgumentParser:
+    p = argparse.ArgumentParser(description="Train Low-Light Enhancement Model")
+    # Data
+    p.add_argument("--data_dir", type=str, default="src/data/our485", help="Dataset directory (default: src/data/our485)")
+    p.add_argument("--val_dir", type=str, default="src/data/eval15", help="Validation directory (default: src/data/eval15)")
+    # Model
+    p.add_argument("--variant", type=str, default="small", choices=["tiny", "small", "base", "large"], help="Model variant")
+    p.add_argument("--image_size", type=int, default=256, help="Image size")
+    p.add_argument("--num_steps", type=int, default=4, help="LCM inference steps")
+    # Training
+    p.add_argument("--epochs", type=int, default=100, help="Number of epochs")
+    p.add_argument("--batch_size", type=int, default=8, help="Batch size")
+    p.add_argument("--lr", type=float, default=1e-4, help="Learning rate")
+    p.add_argument("--loss", type=str, default="mse", choices=["mse", "huber", "l1"], help="Loss function")
+    # Optimization
+    p.add_argument("--use_amp", action="store_true", help="Use mixed precision (fp16 engine with a loss scaler)")
+    p.add_argument("--use_ema", action="store_true", help="Use EMA")
+    p.add_argument("--ema_decay", type=float, default=0.9999, help="EMA decay")
+    # Logging
+    p.add_argument("--output_dir", type=str, default="outputs", help="Output directory")
+    p.add_argument("--use_wandb", action="store_true", help="Log to W&B")
+    p.add_argument("--project", type=str, default="low-light-diffusion", help="W&B project")
+    # Resume
+    p.add_argument("--resume", type=str, default=None, help="Resume from checkpoint")
+    # This engine's additions
+    p.add_argument("--dtype", type=str, default=None, choices=["fp32", "fp16", "bf16"],
+                   help="engine precision (default: fp16 with --use_amp, else fp32)")
+    p.add_argument("--seed", type=int, default=0, help="seed of the weights and of every draw")
+    p.add_argument("--use_synthetic", action="store_true", help="synthetic low-light twins of the images in --data_dir")
+    p.add_argument("--checkpoint_dir", type=str, default="checkpoints", help="Checkpoint directory")
+    p.add_argument("--save_interval", type=int, default=5, help="epochs between checkpoint_epoch_{e}.pt files")
+    p.add_argument("--sample_interval", type=int, default=1, help="epochs between sample sheets")
+    return p
+
+
+def parse_args(argv=None):
+    return build_parser().parse_args(argv)
+
+
+def config_from_args(args) -> "M.TrainingConfig":
+    return M.TrainingConfig(
+        unet_variant=args.variant, image_size=args.image_size, num_inference_steps=args.num_steps,
+        epochs=args.epochs, batch_size=args.batch_size, learning_rate=args.lr, loss_type=args.loss,
+        use_amp=args.use_amp, use_ema=args.use_ema, ema_decay=args.ema_decay,
+        save_interval=args.save_interval, sample_interval=args.sample_interval,
+        output_dir=args.output_dir, checkpoint_dir=args.checkpoint_dir,
+        use_wandb=args.use_wandb, wandb_project=args.project, resume_from=args.resume,
+        compute_dtype=args.dtype, seed=args.seed, use_synthetic=args.use_synthetic)
+
+
+def main(argv=None) -> int:
+    args = parse_args(argv)
+    config = config_from_args(args)
+    if not torch.cuda.is_available():
+        raise SystemExit("scripts/train.py trains on a HIP device; there is no CPU fallback")
+    print("=" * 60)
+    print("Low-Light Enhancement Diffusion Training")
+    print("=" * 60)
+    print(f"\nLoading data from: {args.data_dir}")
+    val_dir = args.val_dir if args.val_dir and os.path.isdir(args.val_dir) else None
+    train_loader, val_loader = M.create_device_dataloaders(train_root=args.data_dir, val_root=val_dir, batch_size=args.batch_size,
+                                                           image_size=args.image_size, use_synthetic=args.use_synthetic, seed=args.seed)
+    print(f"  Train batches: {len(train_loader)}")
+    if val_loader is not None:
+        print(f"  Val batches: {len(val_loader)}")
+
+    torch.manual_seed(args.seed)  # the initial weights
+    model = M.LowLightDiffusion(unet_variant=args.variant, image_size=args.image_size, num_inference_steps=args.num_steps)
+    model = model.to(train_loader.store.device)
+    size = model.get_model_size()
+    print(f"  Parameters: {size['num_params']:,}")
+
+    trainer = M.LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config)
+    print(f"  Engine precision: {model.compute_dtype}, loss scaler: {trainer.scaler is not None}, EMA: {config.use_ema}")
+    trainer.train(on_epoch=lambda log: print(json.dumps(log), flush=True))
+    print("\nTraining complete!")
+    print(f"Checkpoints saved to: {config.checkpoint_dir}")
+    print(f"Samples saved to: {config.output_dir}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
