@@ -39,6 +39,7 @@ EXPORTS = [
     "llie_upconv_fold_elems", "llie_upconv_fold_weights", "llie_conv3x3_upfold", "llie_conv3x3_upfold_tiles",
     "llie_expand_dw", "llie_expand_pool", "llie_expand_dw_project", "llie_expand_dw_project_skip", "llie_irbx_project_tiles",
     "llie_expand_stats", "llie_irbx_stats_rows",
+    "llie_dwconv3x3_ex", "llie_dwconv3x3_strip_rows", "llie_last_kernel",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 
@@ -187,6 +188,10 @@ def lib() -> C.CDLL:
     L.llie_gram_part_floats.restype = i64
     L.llie_dwconv3x3.argtypes = [ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
     L.llie_dwconv3x3_tiles.argtypes = [ci, ci]
+    L.llie_dwconv3x3_ex.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
+    L.llie_dwconv3x3_strip_rows.argtypes = [ci, ci, ci, ci, ci]
+    L.llie_last_kernel.argtypes = []
+    L.llie_last_kernel.restype = C.c_char_p
     L.llie_expand_dw.argtypes = [ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     L.llie_expand_pool.argtypes = [ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     L.llie_expand_dw_project.argtypes = [ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]

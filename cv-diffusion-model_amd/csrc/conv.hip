@@ -788,7 +788,9 @@ hipError_t conv3x3_stamp_fetch(double* out8) {  // mean cycles per wave of the l
 }
 
 static int conv_tw(int Wo) { return (Wo % 16 == 0) ? 16 : 8; }
-int conv3x3_ntiles(int Ho, int Wo) { return ((Ho + 7) / 8) * ((Wo + conv_tw(Wo) - 1) / conv_tw(Wo)); }
+// the tile width launch_conv_t takes: ragged maps (Ho % 8 or Wo % 8) run 8-wide tiles whatever Wo is -- a 9 x 16 map is four tiles
+static int conv_tw(int Ho, int Wo) { return (Ho % 8 || Wo % 8) ? 8 : conv_tw(Wo); }
+int conv3x3_ntiles(int Ho, int Wo) { return ((Ho + 7) / 8) * ((Wo + conv_tw(Ho, Wo) - 1) / conv_tw(Ho, Wo)); }
 
 template <typename T, int MODE, int TW, int BN, int WM, int WN, bool RAGGED = false>
 static hipError_t launch_conv_cfg(const Conv3Args& a, hipStream_t s) {

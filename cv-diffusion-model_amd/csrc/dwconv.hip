@@ -283,6 +283,9 @@ __global__ void __launch_bounds__(8 * TX) dwconv3x3_bwd_ragged_kernel(const DwAr
 }
 
 static int dw_tx(int W) { return (W % 32 == 0) ? 32 : ((W % 16 == 0) ? 16 : (W % 8 == 0 ? 8 : (W > 16 ? 32 : 16))); }
+// the strip width of a launch: the ragged kernels (H % 8 or W % 8) exist for 16 and 32 columns only, so a map with ragged rows
+// and W = 8 (mod 16) runs 16-wide strips -- grid and pool slab are counted with that width
+static int dw_tx(int H, int W) { return (H % 8 && dw_tx(W) == 8) ? 16 : dw_tx(W); }
 // Strip height: as tall as possible (fewer halo rows) while the launch still has >= 1024 workgroups to
 // fill 256 CUs; small batches get shorter strips.  `chunks` = C / channels per WG.  The pool slab does
 // not depend on the choice (8-row segments), so results are bitwise independent of the batch size.
@@ -294,14 +297,14 @@ int dw_pick_tyl(int B, int H, int W, int chunks) {
     if (H % cand[i] == 0 && (long)tiles_x * (H / cand[i]) * chunks * B >= 1024) return cand[i];
   return 8;
 }
-int dwconv_ntiles(int H, int W) { return ((H + kPoolSegRows - 1) / kPoolSegRows) * ((W + dw_tx(W) - 1) / dw_tx(W)); }
+int dwconv_ntiles(int H, int W) { return ((H + kPoolSegRows - 1) / kPoolSegRows) * ((W + dw_tx(H, W) - 1) / dw_tx(H, W)); }
 
 template <typename T>
 static hipError_t launch_dw_t(const DwArgs& a, hipStream_t s) {
   constexpr int CC = 8 * Elem<T>::VEC;
   const bool ragged = a.H % 8 || a.W % 8;  // partial strips at the right / bottom edge
   if (a.C % CC || a.H < 1 || a.W < 1) return hipErrorInvalidValue;
-  const int tx = dw_tx(a.W), tyl = dw_pick_tyl(a.B, a.H, a.W, a.C / CC);
+  const int tx = dw_tx(a.H, a.W), tyl = dw_pick_tyl(a.B, a.H, a.W, a.C / CC);
   const int tiles = ((a.W + tx - 1) / tx) * ((a.H + tyl - 1) / tyl);
   dim3 grid(tiles, a.C / CC, a.B);
   static const std::string names[3] = {std::string("dwconv3x3_kernel<") + TypeName<T>::value + ", 32, 4>",

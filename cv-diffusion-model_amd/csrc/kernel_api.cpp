@@ -40,6 +40,17 @@ int64_t llie_gram_part_floats(int K, int pixels) { return (K == 32 || K == 64 ||
 int llie_pw_gemm(int dtype, const llie_gemm_seg* segs, int nseg, const void* w, const float* bias, const void* residual,
                  void* out, float* stats, int M, int N, int P, llie_stream stream) {
   if (!segs || nseg < 1 || nseg > 3 || !w || !out || dtype < 0 || dtype > 2) return LLIE_ERR_ARG;
+  // the kernel's prologue is affine (+ ReLU6 / clamp01) and runs only where a segment has a table: an activation it does not
+  // have (SiLU), an activation or a shift without a scale table, or a table row shorter than the segment would be computed as
+  // something else without a word
+  for (int i = 0; i < nseg; ++i) {
+    const llie_gemm_seg& sg = segs[i];
+    if ((sg.act != ACT_NONE && sg.act != ACT_RELU6 && sg.act != ACT_RELU6_S6) || (!sg.scale && (sg.act != ACT_NONE || sg.bias)) ||
+        (sg.scale && sg.affine_ld < sg.channels)) {
+      set_err("pw_gemm: segment %d: act 0, 1 or 3; an activation or a shift needs a scale table; affine_ld >= channels", i);
+      return LLIE_ERR_ARG;
+    }
+  }
   GemmArgs g{};
   g.nseg = nseg;
   g.K = to_segs(segs, nseg, g.seg);
@@ -68,6 +79,24 @@ int llie_dwconv3x3(int dtype, const void* in, void* out, const float* scale, con
   d.in = in; d.out = out; d.as = scale; d.ab = bias; d.w = w9c; d.pool = pool; d.B = B; d.H = H; d.W = W; d.C = C;
   return kerr("dwconv3x3", launch_dwconv3x3(dtype, d, hs(stream)));
 }
+// the forms the engines run beyond llie_dwconv3x3: fixed-point pool totals, the clamp01 prologue with weights x 6 (s6), no activation
+int llie_dwconv3x3_ex(int dtype, const void* in, void* out, const float* scale, const float* bias, const float* w9c, float* pool,
+                      unsigned long long* pool_totals, int flags, int B, int H, int W, int C, llie_stream stream) {
+  const int s6 = flags & 1, no_act = (flags >> 1) & 1;
+  if (!in || !out || !scale || !bias || !w9c || dtype < 0 || dtype > 2 || (pool && pool_totals) || flags < 0 || flags > 3 ||
+      (s6 && (no_act || dtype == 0)) || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % (dtype == 0 ? 32 : 64))
+    return LLIE_ERR_ARG;
+  DwArgs d{};
+  d.in = in; d.out = out; d.as = scale; d.ab = bias; d.w = w9c; d.pool = pool; d.pool_tot = pool_totals; d.s6 = s6; d.no_act = no_act;
+  d.B = B; d.H = H; d.W = W; d.C = C;
+  return kerr("dwconv3x3_ex", launch_dwconv3x3(dtype, d, hs(stream)));
+}
+int llie_dwconv3x3_strip_rows(int dtype, int B, int H, int W, int C) {
+  const int cc = dtype == 0 ? 32 : 64;
+  if (dtype < 0 || dtype > 2 || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % cc) return LLIE_ERR_ARG;
+  return dw_pick_tyl(B, H, W, C / cc);
+}
+const char* llie_last_kernel(void) { return last_kernel(); }
 
 // ---- the remaining kernel-level entry points of SURVEY.md 8b (GroupNorm finalize, dense 3x3, linear attention, SE MLP, FiLM)
 int llie_groupnorm_finalize(const float* slab0, int ntiles0, int ch0, const float* slab1, int ntiles1, int ch1, int groups, int pixels,
@@ -97,7 +126,7 @@ int llie_gram_finalize(int dtype, const float* gram_totals, const void* w_expand
 }
 int llie_conv3x3(int dtype, int mode, const void* in, const void* w, const float* bias, void* out, float* stats, int batch, int Hi, int Wi,
                  int Cin, int Cout, llie_stream stream) {
-  if (!in || !w || !out || dtype < 0 || dtype > 2 || (mode != 0 && mode != 1)) return LLIE_ERR_ARG;
+  if (!in || !w || !out || dtype < 0 || dtype > 2 || mode < 0 || mode > 2) return LLIE_ERR_ARG;
   Conv3Args a{};
   a.in = in; a.w = w; a.bias = bias; a.out = out; a.stats = stats; a.B = batch; a.Hi = Hi; a.Wi = Wi; a.Cin = Cin; a.Cout = Cout; a.mode = mode;
   return kerr("conv3x3", launch_conv3x3(dtype, a, hs(stream)));

@@ -379,7 +379,10 @@ int llie_comparison_grid_u8(const float* low, const float* enhanced, const float
  *
  * llie_pw_gemm: out[M][N] = sum over K-segments act(A_seg * scale + bias) . W[N][K]^T (+bias[N]) (+residual)
  *   -- the 1x1 convolutions efficient_unet.py:174,186,199,265-267 with their fused prologue/epilogue.
- *   scale/bias of a segment are fp32 [M/P][affine_ld] tables (null = identity); act: 0 none, 1 ReLU6.
+ *   scale/bias of a segment are fp32 [M/P][affine_ld] tables (null = identity); act: 0 none, 1 ReLU6, 3 = clamp01 with tables
+ *   already divided by 6 and the accumulators times 6 (2-byte dtypes, every segment or none).  Refused with LLIE_ERR_ARG before
+ *   any HIP call: any other act (the forward GEMM has no SiLU prologue), an act or a bias table without a scale table (the
+ *   prologue runs only where there is one), affine_ld < channels.
  *   stats (optional): fp32 slab [M/P][P/tile_rows][2][N] of per-channel (sum, sum of squares).
  * llie_dwconv3x3: out = depthwise3x3(relu6(in*scale+bias)), weights fp32 [9][C] tap-major
  *   (efficient_unet.py:212-220); pool (optional): fp32 [B][tiles][C] partial sums for the SE average pool. */
@@ -404,8 +407,8 @@ int llie_pw_expand(int dtype, const llie_gemm_seg* segs, int nseg, const float* 
  *   (sum, sum of squares) slabs [batch][ntiles][2][ch] of up to two channel segments (a virtual concat) to the per-(image,
  *   channel) affine `scale`, `shift` [batch][C] that consumers apply on load; `film` (or NULL): [rows][2 C] FiLM (1 + scale, shift
  *   folded in, :215-217) with row stride film_stride (0 = one row for all images); post_scale 0 = none.
- * llie_conv3x3: Downsample (:367, mode 0: stride 2, pad 1) / Upsample (:383-384, mode 1: bilinear x2 then 3x3 pad 1) as implicit
- *   GEMM; w [9][Cout][Cin] of the compute type (tap-major), stats (or NULL) [batch][llie_conv3x3_tiles(Ho, Wo)][2][Cout].
+ * llie_conv3x3: Downsample (:367, mode 0: stride 2, pad 1) / Upsample (:383-384, mode 1: bilinear x2 then 3x3 pad 1) / the plain
+ *   stride-1 pad-1 conv (mode 2: what training runs on stored up-sampled tensors, and every input-gradient conv) as implicit GEMM; w [9][Cout][Cin] of the compute type (tap-major), stats (or NULL) [batch][llie_conv3x3_tiles(Ho, Wo)][2][Cout].
  * llie_linattn: LinearAttention core (:288-302) on qkv [batch][N][3 * 32 heads] (q | k | v, head-major channels, dim_head 32):
  *   phi = elu + 1 on q and k, kv = sum_n phi(k) v^T, out = phi(q) kv / (phi(q) . sum_n phi(k) + 1e-6) -> [batch][N][32 heads];
  *   kv_scratch: llie_linattn_splits(N) * batch * heads * 32 * 33 floats.
@@ -516,6 +519,19 @@ int llie_gram_finalize(int dtype, const float* gram_totals, const void* w_expand
 int llie_dwconv3x3(int dtype, const void* in, void* out, const float* scale, const float* bias, const float* w9c,
                    float* pool, int B, int H, int W, int C, llie_stream stream);
 int llie_dwconv3x3_tiles(int H, int W);
+/* llie_dwconv3x3_ex: llie_dwconv3x3 in every form the engines launch.  pool_totals (or NULL; exclusive with pool): uint64 [B][C],
+ *   += round(2^24 x partial sums of the stored output per channel) (integer adds; the caller sets the starting value).
+ *   flags bit 0 (s6, 2-byte dtypes): scale / bias hold norm2's affine divided by 6, the prologue is clamp01(in*scale+bias) rounded to
+ *   the compute type and the weights are taken as T(6 w) -- relu6(z) w = clamp01(z / 6) (6 w); bit 1 (no_act): the prologue is the
+ *   affine alone.  Checked before any HIP call (LLIE_ERR_ARG): NULL tensors, pool and pool_totals together, s6 with no_act or in
+ *   fp32, C not a multiple of 32 (fp32) / 64 (2-byte), sizes < 1.
+ * llie_dwconv3x3_strip_rows: the strip height (8, 16, 32 or 64 rows per workgroup) the launcher takes for these sizes.
+ * llie_last_kernel: the name the last kernel launcher called on this thread recorded (kernel and template arguments, as
+ *   llie_profile_report aggregates them); "" before the first launch.  Not every launcher records one. */
+int llie_dwconv3x3_ex(int dtype, const void* in, void* out, const float* scale, const float* bias, const float* w9c, float* pool,
+                      unsigned long long* pool_totals, int flags, int B, int H, int W, int C, llie_stream stream);
+int llie_dwconv3x3_strip_rows(int dtype, int B, int H, int W, int C);
+const char* llie_last_kernel(void);
 /* The recompute form of InvertedResidualBlock (efficient_unet.py:203-236; irbx.hip), kernel by kernel.  x0 / x1: the block input,
  * NHWC [batch][H][W][c0 / c1] of a 2-byte compute type (x1 NULL with c1 = 0), Cin = c0 + c1 in {32, 64, 96}, c0 % 16 == 0,
  * H % 8 == 0, W % 16 == 0, Chid = 4 Cin.  scale1 / shift1 [batch][Cin]: norm1's affine DIVIDED BY 6 (a' = clamp01(x scale1 + shift1)

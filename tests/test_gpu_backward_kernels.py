@@ -16,20 +16,21 @@ written window, and every call is made twice and must give the same bits.
 import ctypes
 import importlib
 import math
+import os
+import sys
 import zlib
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from kernel_refs import TDT, U, _flip_slack, _r64, _ratio, _rt, _ulp  # noqa: E402  (the comparison helpers: one copy)
+
 pytestmark = pytest.mark.gpu
 N = importlib.import_module("cv-diffusion-model_amd._native")
 
-U = 2.0 ** -24
 CANARY = 12345.5
-TDT = {0: torch.float32, 1: torch.float16, 2: torch.bfloat16}
-EPS_T = {0: 2.0 ** -23, 1: 2.0 ** -10, 2: 2.0 ** -7}  # one ulp relative to the leading power of two
-EMIN_T = {0: -126, 1: -14, 2: -126}                   # exponent of the smallest normal (fp16 subnormals keep 2^-24 steps)
 DTYPES = [0, 1, 2]
 
 
@@ -41,46 +42,6 @@ def dev():
 
 def _st():
     return torch.cuda.current_stream().cuda_stream
-
-
-def _rt(x, dtype):
-    """fp32 -> the storage type (a CPU tensor of that type)."""
-    return x.float().to(TDT[dtype])
-
-
-def _r64(x, dtype):
-    """float64 value rounded to fp32 and then to the storage type, back in float64."""
-    return x.float().to(TDT[dtype]).double()
-
-
-def _ulp(x, dtype):
-    """one ulp of the storage type at |x| (float64)."""
-    a = x.abs().clamp_min(1e-38)
-    return torch.exp2(torch.floor(torch.log2(a)).clamp_min(EMIN_T[dtype])) * EPS_T[dtype]
-
-
-def _flip_slack(v, dtype, err=None):
-    """Where round_T(v) could come out differently when the kernel's fp32 value differs from v by up to `err` (default: a few fp32
-    ulps of v): err + one ulp of T; 0 elsewhere."""
-    if dtype == 0:
-        return torch.zeros_like(v)
-    d = v.abs() * 2.0 ** -18 if err is None else err
-    lo, hi = _r64(v - d, dtype), _r64(v + d, dtype)
-    return torch.where(lo != hi, d + _ulp(v, dtype), torch.zeros_like(v))
-
-
-def _ratio(out, ref, abssum, slack=None, bar=None, what=""):
-    """worst |out - ref| / (2^-24 * abssum) after the allowed slack; asserts it is below `bar`."""
-    out = out.double()
-    assert torch.isfinite(out).all(), f"{what}: entries left unwritten (NaN) or non-finite"
-    err = (out - ref).abs()
-    if slack is not None:
-        err = (err - slack).clamp_min(0.0)
-    r = (err / (U * abssum).clamp_min(1e-300)).max().item()
-    print(f"RATIO {what} {r:.3f}")
-    if bar is not None:
-        assert r < bar, f"{what}: worst error {r:.2f} x 2^-24 of the absolute sum (bar {bar})"
-    return r
 
 
 def _act64(z, act):
