@@ -739,45 +739,6 @@ hipError_t launch_upsample2x_bwd(int dtype, const void* in, void* out, int B, in
 hipError_t launch_dilate2x(int dtype, const void* in, void* out, int B, int Hi, int Wi, int C, hipStream_t s) { LLIE_PIX3(dilate2x_kernel, (size_t)B * 4 * Hi * Wi) }
 #undef LLIE_PIX3
 
-// OIHW fp32 -> [8 - tap][I][O] T: the weights of the input-gradient convolution (taps flipped, channels transposed)
-template <typename T>
-__global__ void repack_conv3x3_t_kernel(const float* src, T* dst, int O, int I) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)O * I * 9) return;
-  const int tap = (int)(i % 9);
-  const int ci = (int)((i / 9) % I), co = (int)(i / (9 * I));
-  dst[((size_t)(8 - tap) * I + ci) * O + co] = (T)src[i];
-}
-hipError_t launch_repack_conv3x3_t(int dtype, const float* src, void* dst, int O, int I, hipStream_t s) {
-  const int64_t n = (int64_t)O * I * 9;
-  dim3 grid((unsigned)((n + 255) / 256));
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(repack_conv3x3_t_kernel<float>, grid, dim3(256), 0, s, src, (float*)dst, O, I); break;
-    case 1: hipLaunchKernelGGL(repack_conv3x3_t_kernel<half_t>, grid, dim3(256), 0, s, src, (half_t*)dst, O, I); break;
-    case 2: hipLaunchKernelGGL(repack_conv3x3_t_kernel<bf16_t>, grid, dim3(256), 0, s, src, (bf16_t*)dst, O, I); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-template <typename T>
-__global__ void cvt_rows_t_kernel(const float* src, T* dst, int rows, int cols) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)rows * cols) return;
-  const int r = (int)(i / cols), c = (int)(i % cols);
-  dst[(size_t)c * rows + r] = (T)src[i];
-}
-hipError_t launch_cvt_rows_t(int dtype, const float* src, void* dst, int rows, int cols, hipStream_t s) {
-  const int64_t n = (int64_t)rows * cols;
-  dim3 grid((unsigned)((n + 255) / 256));
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(cvt_rows_t_kernel<float>, grid, dim3(256), 0, s, src, (float*)dst, rows, cols); break;
-    case 1: hipLaunchKernelGGL(cvt_rows_t_kernel<half_t>, grid, dim3(256), 0, s, src, (half_t*)dst, rows, cols); break;
-    case 2: hipLaunchKernelGGL(cvt_rows_t_kernel<bf16_t>, grid, dim3(256), 0, s, src, (bf16_t*)dst, rows, cols); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
 // ---- output head.  Forward: eps[o][p] = bias[o] + sum_{c,tap} a[p + tap - 1][c] * W[o][c][tap], a = silu(h*as + ab).
 // data gradient: da[q][c] = sum_{o,tap} deps[o][q - (tap - 1)] * W[o][c][tap]
 template <typename T>

@@ -35,8 +35,7 @@ inline size_t elem_size(int dt) { return dt == LLIE_F32 ? 4 : 2; }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // ---------------------------------------------------------------------------------------------
-// Parameter table
-enum PKind { PK_F32, PK_MAT, PK_CONV3, PK_DW, PK_INIT, PK_FINAL };
+// Parameter table (PKind and the layouts behind it: kernels.h, LoadDesc; model.cpp: make_desc turns a Param into one)
 struct Param {
   std::string key;
   int64_t numel = 0;
@@ -54,11 +53,11 @@ struct Param {
   bool has_t = false;
   size_t t_off = 0;
   int64_t goff = 0;
-  // PK_MAT, 2-byte engines: third copy = the matrix times f_scale in MFMA fragment order (pwx.hip: launch_pack_expand)
+  // PK_MAT, 2-byte engines: third copy = the matrix times f_scale in MFMA fragment order (kernels.h: pw_expand_pack_index)
   bool has_f = false;
   size_t f_off = 0;
   float f_scale = 1.f;
-  // PK_CONV3 of an up-sampling conv, 2-byte engines: third copy = the 64 folded sets of conv3x3_upfold_kernel (launch_upconv_fold)
+  // PK_CONV3 of an up-sampling conv, 2-byte engines: third copy = the 64 folded sets of conv3x3_upfold_kernel (small.hip: launch_upconv_fold)
   bool has_fold = false;
   size_t fold_off = 0;
 };

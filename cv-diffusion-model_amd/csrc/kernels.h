@@ -323,38 +323,37 @@ hipError_t launch_nchw_to_nhwc(int dtype, const float* x, void* y, float* stats,
 hipError_t launch_nhwc_to_nchw(int dtype, const void* x, float* y, int B, int C, int P, hipStream_t s, int Cdst = 0,
                                int coff = 0);  // y is [B][Cdst][P]; the C channels land at [coff, coff+C)
 
-// Weight repack at load time (fp32 reference layout -> engine layout).
-hipError_t launch_cvt_rows(int dtype, const float* src, void* dst, int rows, int cols, int dst_ld, int dst_col0,
-                           hipStream_t s);                       // dst[r*ld + col0 + c] = T(src[r*cols + c])
-hipError_t launch_repack_conv3x3(int dtype, const float* src, void* dst, int Cout, int Cin, hipStream_t s, int Op = 0,
-                                 int Ip = 0);  // OIHW -> [9][Op][Ip] (Op, Ip: padded destination dims, 0 = unpadded)
-// OIHW [C][C][3][3] fp32 -> the 64 folded sets of the up-sampling conv (layout above): fp64 arithmetic, one rounding to the compute
-// dtype (1 or 2).  `state` as in launch_load_all: with one, a no-op when the parameters did not change.
-hipError_t launch_upconv_fold(int dtype, const float* src, void* dst, int C, hipStream_t s, const unsigned long long* state = nullptr);
-hipError_t launch_repack_dw(const float* src, float* dst, int C, hipStream_t s, int Cp = 0);                 // [C][1][3][3] -> [9][Cp]
-hipError_t launch_repack_dw_flip(const float* src, float* dst, int C, hipStream_t s, int Cp = 0);            // [C][1][3][3] -> [8-tap][Cp]
-hipError_t launch_repack_init(const float* src, float* dst, int O, int I, hipStream_t s, int Op = 0);        // OIHW -> [I*9][Op]
-hipError_t launch_repack_final(const float* src, float* dst, int O, int I, hipStream_t s, int Ip = 0);       // OIHW -> [9][Ip][4]
-hipError_t launch_repack_final_mfma(int dtype, const float* src, void* dst, int O, int I, hipStream_t s, int Ip = 0);  // OIHW -> [Ip/32][18][2][4][8] T
-hipError_t launch_repack_init_mfma(int dtype, const float* src, void* dst, int O, int I, hipStream_t s, int Op = 0);   // OIHW -> [5][2][Op][8] T
-
-// All plain / matrix / 3x3 / depthwise parameters in ONE launch (an optimiser step changes every parameter: 300+
-// small repack launches would cost more than the repack itself).  Offsets are bytes into the weight blob; -1 = none.
+// Weight repack at load time (fp32 reference layout -> engine layout).  One device function (small.hip: load_one) states every
+// layout once, driven by a LoadDesc; it runs either over a device table of descriptors, one per parameter (launch_load_all: an
+// optimiser step changes every parameter, and 300+ small repack launches would cost more than the repack itself), or over a single
+// descriptor passed by value (launch_load_one: llie_load_param).  Offsets are bytes into the weight blob; -1 = no such copy.
+//   PK_F32    fp32 copy
+//   PK_MAT    [rows][cols] -> dst[r * ld + col0 + c], T or (as_t == 0) fp32;  dst_t: transposed [cols][rows] T;
+//             dst_f: times fscale in MFMA fragment order (pw_expand_pack_index), T
+//   PK_CONV3  OIHW 3x3 -> [tap][Op][Ip] T;  dst_t: [8 - tap][Ip][Op] T, the weights of the input-gradient conv
+//   PK_DW     [C][1][3][3] -> [tap][Op] fp32;  dst_t: taps flipped, [8 - tap][Op] fp32
+//   PK_INIT   input conv OIHW -> fp32 [I * 9][Op];  dst_t: the MFMA pack [tap][Op][8] T
+//   PK_FINAL  output conv OIHW (O <= 4) -> fp32 [9][Ip][4];  dst_t: the MFMA pack [Ip / 32][18][2][4][8] T
+// Padding entries (Op / Ip beyond O / I, taps and channels the packs round up to) are never written: they keep the zeros of
+// llie_create's memset of the blob.
+enum PKind : int { PK_F32, PK_MAT, PK_CONV3, PK_DW, PK_INIT, PK_FINAL };
 struct LoadDesc {
   const float* src;
-  int kind;            // 0 fp32 copy, 1 matrix (cvt_rows [+ transposed copy]), 2 OIHW 3x3 ([tap][O][I] [+ [8-tap][I][O]]), 3 depthwise ([tap][C] + flipped),
-                       // 4 input conv (fp32 [I*9][Op] + MFMA pack at dst_t), 5 output conv (fp32 [9][Ip][4] + MFMA pack at dst_t)
-  int as_t;            // matrix: destination in the compute dtype (1) or fp32 (0)
-  int rows, cols, ld, col0, O, I, Op, Ip;  // Op / Ip: padded destination dims of the 3x3 / depthwise layouts
-  long long numel, dst, dst_t;
-  long long dst_f;     // matrix: third copy, times fscale, in MFMA fragment order (pw_expand_pack_index); -1 = none
+  PKind kind;
+  int as_t;            // PK_MAT: destination in the compute dtype (1) or fp32 (0)
+  int rows, cols, ld, col0, O, I, Op, Ip;  // Op / Ip: padded destination dims of the conv / depthwise layouts
+  long long numel, dst, dst_t, dst_f;
   float fscale;
 };
 // state (optional, device): [0] = content hash of the last load, [1] = 1 when the parameters changed (set by launch_params_hash);
 // with a state the kernel is a no-op when [1] == 0
 hipError_t launch_load_all(int dtype, const LoadDesc* descs_dev, int n, char* blob, hipStream_t s, const unsigned long long* state = nullptr);
+hipError_t launch_load_one(int dtype, const LoadDesc& d, char* blob, hipStream_t s);
 hipError_t launch_params_hash(const LoadDesc* descs_dev, int n, unsigned long long* partial, unsigned long long* state, int force,
                               hipStream_t s);
+// OIHW [C][C][3][3] fp32 -> the 64 folded sets of the up-sampling conv (layout above): fp64 arithmetic, one rounding to the compute
+// dtype (1 or 2).  `state` as in launch_load_all: with one, a no-op when the parameters did not change.
+hipError_t launch_upconv_fold(int dtype, const float* src, void* dst, int C, hipStream_t s, const unsigned long long* state = nullptr);
 
 // uint8 HWC RGB <-> normalised fp32 NCHW with bilinear resize (scripts/inference.py:99-134), bit-exact with hostio.py.
 hipError_t launch_preprocess_u8(const uint8_t* img, int B, int H0, int W0, float* out, int S, hipStream_t s);
@@ -497,8 +496,6 @@ hipError_t launch_sin_embed(const int64_t* t, const float* freqs, float* emb, in
 hipError_t launch_upsample2x(int dtype, const void* in, void* out, int B, int Hi, int Wi, int C, hipStream_t s);       // bilinear, align_corners=False
 hipError_t launch_upsample2x_bwd(int dtype, const void* dout, void* din, int B, int Hi, int Wi, int C, hipStream_t s); // adjoint
 hipError_t launch_dilate2x(int dtype, const void* in, void* out, int B, int Hi, int Wi, int C, hipStream_t s);          // out[2y][2x] = in[y][x], zeros elsewhere
-hipError_t launch_repack_conv3x3_t(int dtype, const float* src, void* dst, int Cout, int Cin, hipStream_t s);           // OIHW -> [8-tap][I][O] (input-gradient conv)
-hipError_t launch_cvt_rows_t(int dtype, const float* src, void* dst, int rows, int cols, hipStream_t s);                // dst[c][r] = T(src[r][c])
 //   output head: d(eps) fp32 NCHW [B][Cout][H][W] -> da NHWC [M][C] T (gradient of the SiLU output), and its weight gradient
 struct FinalBwdArgs {
   const float* deps; const float* w;       // w: the forward kernel's repacked fp32 weights [9][C][4]

@@ -462,6 +462,26 @@ int llie_param_info(const llie_ctx* c, int i, char* key, size_t cap, int64_t* nu
   return LLIE_OK;
 }
 
+// The one statement of what is loaded where for a parameter: the main destination, which secondary copies exist, and the padded
+// destination dims.  The refusals of the engine layouts need no check here, because no handle with such a parameter exists:
+// build_unet rejects in_channels > 8 (the input conv's MFMA pack holds 8) and out_channels > 4 (the output conv's layouts hold 4),
+// the output conv's Ip is channels[0] = pad32(.), a multiple of 32 by construction, and build_module never registers either conv;
+// the fragment-order copy (has_f) is reserved only for rows % 64 == 0 and pw_expand_serves_k(cols), all multiples of 16.
+static LoadDesc make_desc(const llie_ctx* c, const Param& p, const float* src) {
+  LoadDesc d{};
+  d.src = src; d.kind = p.kind; d.numel = p.numel; d.dst = (long long)p.off;
+  d.as_t = p.as_t ? 1 : 0; d.rows = p.rows; d.cols = p.cols; d.ld = p.ld; d.col0 = p.col0;
+  d.O = p.O; d.I = p.I; d.Op = p.Op > 0 ? p.Op : p.O; d.Ip = p.Ip > 0 ? p.Ip : p.I;
+  // the transposed copies feed the backward pass, which the padded (unpinned) variants do not have; the flipped depthwise
+  // taps are written all the same (their blob space is reserved and padded like the main copy)
+  d.dst_t = p.has_t && (!c->padded || p.kind == PK_DW) ? (long long)p.t_off : -1;
+  d.dst_f = p.has_f ? (long long)p.f_off : -1; d.fscale = p.f_scale;
+  // the 2-byte engines' input / output convs run on MFMA from a pack of their own
+  if (p.kind == PK_INIT) d.dst_t = c->dt != LLIE_F32 ? (long long)c->init_wp : -1;
+  if (p.kind == PK_FINAL) d.dst_t = c->dt != LLIE_F32 ? (long long)c->fin_wp : -1;
+  return d;
+}
+
 int llie_load_param(llie_ctx* c, const char* key, const float* src, int64_t numel, llie_stream stream) {
   if (!c || !key || !src) return LLIE_ERR_ARG;
   if (const int rc = need_device(c)) return rc;
@@ -470,36 +490,13 @@ int llie_load_param(llie_ctx* c, const char* key, const float* src, int64_t nume
   Param& p = c->params[it->second];
   if (p.numel != numel) { set_err("size mismatch for '%s': expected %lld elements, got %lld", key, (long long)p.numel, (long long)numel); return LLIE_ERR_KEY; }
   hipStream_t s = hs(stream);
-  void* dst = c->blob + p.off;
-  hipError_t e = hipSuccess;
-  switch (p.kind) {
-    case PK_F32: e = hipMemcpyAsync(dst, src, (size_t)numel * 4, hipMemcpyDeviceToDevice, s); break;
-    case PK_MAT:
-      e = launch_cvt_rows(p.as_t ? c->dt : 0, src, dst, p.rows, p.cols, p.ld, p.col0, s);
-      // transposed copies feed the backward pass, which the padded (unpinned) variants do not have
-      if (e == hipSuccess && p.has_t && !c->padded) e = launch_cvt_rows_t(c->dt, src, c->blob + p.t_off, p.rows, p.cols, s);
-      if (e == hipSuccess && p.has_f) e = launch_pack_expand(c->dt, src, c->blob + p.f_off, p.rows, p.cols, p.f_scale, s);
-      break;
-    case PK_CONV3:
-      e = launch_repack_conv3x3(c->dt, src, dst, p.O, p.I, s, p.Op, p.Ip);
-      if (e == hipSuccess && p.has_t && !c->padded) e = launch_repack_conv3x3_t(c->dt, src, c->blob + p.t_off, p.O, p.I, s);
-      if (e == hipSuccess && p.has_fold) e = launch_upconv_fold(c->dt, src, c->blob + p.fold_off, p.O, s);
-      break;
-    case PK_DW:
-      e = launch_repack_dw(src, reinterpret_cast<float*>(dst), p.O, s, p.Op);
-      if (e == hipSuccess && p.has_t) e = launch_repack_dw_flip(src, reinterpret_cast<float*>(c->blob + p.t_off), p.O, s, p.Op);
-      break;
-    case PK_INIT:
-      e = launch_repack_init(src, reinterpret_cast<float*>(dst), p.O, p.I, s, p.Op);
-      if (e == hipSuccess && c->dt != LLIE_F32) e = launch_repack_init_mfma(c->dt, src, c->blob + c->init_wp, p.O, p.I, s, p.Op);
-      break;
-    case PK_FINAL:
-      e = launch_repack_final(src, reinterpret_cast<float*>(dst), p.O, p.I, s, p.Ip);
-      if (e == hipSuccess && c->dt != LLIE_F32) e = launch_repack_final_mfma(c->dt, src, c->blob + c->fin_wp, p.O, p.I, s, p.Ip);
-      break;
-  }
+  hipError_t e = launch_load_one(c->dt, make_desc(c, p, src), c->blob, s);
+  if (e == hipSuccess && p.has_fold) e = launch_upconv_fold(c->dt, src, c->blob + p.fold_off, p.O, s);
   if (e != hipSuccess) { set_err("repack of '%s' failed: %s", key, hipGetErrorString(e)); return (int)e; }
   p.loaded = true;
+  // the blob no longer holds what the last llie_load_all wrote, whose content hash a llie_refresh_params of the same tensors
+  // would find unchanged: forget its sources, so that the next batched call rebuilds its table and loads unconditionally
+  c->load_srcs.clear();
   return LLIE_OK;
 }
 
@@ -517,24 +514,7 @@ static int load_all_impl(llie_ctx* c, const float* const* srcs, int n, llie_stre
   for (int i = 0; !rebuild && i < n; ++i) rebuild = c->load_srcs[i] != srcs[i];
   if (rebuild) {
     std::vector<LoadDesc> d;
-    for (int i = 0; i < n; ++i) {
-      const Param& p = c->params[i];
-      LoadDesc e{};
-      e.src = srcs[i]; e.numel = p.numel; e.dst = (long long)p.off; e.dst_t = p.has_t ? (long long)p.t_off : -1;
-      e.as_t = p.as_t ? 1 : 0; e.rows = p.rows; e.cols = p.cols; e.ld = p.ld; e.col0 = p.col0; e.O = p.O; e.I = p.I;
-      e.Op = p.Op > 0 ? p.Op : p.O; e.Ip = p.Ip > 0 ? p.Ip : p.I;
-      e.dst_f = p.has_f ? (long long)p.f_off : -1; e.fscale = p.f_scale;
-      if (c->padded && p.kind != PK_DW) e.dst_t = -1;  // no backward pass for the padded variants (see llie_load_param)
-      switch (p.kind) {
-        case PK_F32: e.kind = 0; break;
-        case PK_MAT: e.kind = 1; break;
-        case PK_CONV3: e.kind = 2; break;
-        case PK_DW: e.kind = 3; break;
-        case PK_INIT: e.kind = 4; e.dst_t = c->dt != LLIE_F32 ? (long long)c->init_wp : -1; break;
-        case PK_FINAL: e.kind = 5; e.dst_t = c->dt != LLIE_F32 ? (long long)c->fin_wp : -1; break;
-      }
-      d.push_back(e);
-    }
+    for (int i = 0; i < n; ++i) d.push_back(make_desc(c, c->params[i], srcs[i]));
     hipError_t e = hipSuccess;
     if (!c->load_descs) e = hipMalloc(reinterpret_cast<void**>(&c->load_descs), sizeof(LoadDesc) * c->params.size());
     if (e == hipSuccess && !c->hash_partial) e = hipMalloc(reinterpret_cast<void**>(&c->hash_partial), sizeof(unsigned long long) * 32 * c->params.size());
@@ -547,14 +527,6 @@ static int load_all_impl(llie_ctx* c, const float* const* srcs, int n, llie_stre
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { set_err("llie_load_all: %s", hipGetErrorString(e)); return (int)e; }
     c->load_srcs.assign(srcs, srcs + n);
-    // the input / output convolutions' zero padding is written by their own repack kernels, once per source set
-    for (int i = 0; i < n; ++i) {
-      const PKind k = c->params[i].kind;
-      if (k == PK_INIT || k == PK_FINAL) {
-        const int rc = llie_load_param(c, c->params[i].key.c_str(), srcs[i], c->params[i].numel, stream);
-        if (rc) return rc;
-      }
-    }
     conditional = 0;
   }
   hipError_t e = launch_params_hash(c->load_descs, n, c->hash_partial, c->hash_state, conditional ? 0 : 1, s);

@@ -886,46 +886,6 @@ hipError_t launch_nhwc_to_nchw(int dtype, const void* x, float* y, int B, int C,
 
 // =============================================================================================
 // Weight repack (load time only).
-template <typename T>
-__global__ void cvt_rows_kernel(const float* src, T* dst, int rows, int cols, int ld, int col0) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)rows * cols) return;
-  const int r = (int)(i / cols), c = (int)(i % cols);
-  dst[(size_t)r * ld + col0 + c] = (T)src[i];
-}
-hipError_t launch_cvt_rows(int dtype, const float* src, void* dst, int rows, int cols, int ld, int col0, hipStream_t s) {
-  const int64_t n = (int64_t)rows * cols;
-  dim3 grid((unsigned)((n + 255) / 256));
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(cvt_rows_kernel<float>, grid, dim3(256), 0, s, src, (float*)dst, rows, cols, ld, col0); break;
-    case 1: hipLaunchKernelGGL(cvt_rows_kernel<half_t>, grid, dim3(256), 0, s, src, (half_t*)dst, rows, cols, ld, col0); break;
-    case 2: hipLaunchKernelGGL(cvt_rows_kernel<bf16_t>, grid, dim3(256), 0, s, src, (bf16_t*)dst, rows, cols, ld, col0); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-// OIHW [O][I][3][3] -> [tap][O][I]
-template <typename T>
-__global__ void repack_conv3x3_kernel(const float* src, T* dst, int O, int I, int Op, int Ip) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)O * I * 9) return;
-  const int tap = (int)(i % 9);
-  const int ci = (int)((i / 9) % I), co = (int)(i / (9 * (int64_t)I));
-  dst[((size_t)tap * Op + co) * Ip + ci] = (T)src[i];
-}
-hipError_t launch_repack_conv3x3(int dtype, const float* src, void* dst, int O, int I, hipStream_t s, int Op, int Ip) {
-  if (Op <= 0) Op = O;
-  if (Ip <= 0) Ip = I;
-  const int64_t n = (int64_t)O * I * 9;
-  dim3 grid((unsigned)((n + 255) / 256));
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(repack_conv3x3_kernel<float>, grid, dim3(256), 0, s, src, (float*)dst, O, I, Op, Ip); break;
-    case 1: hipLaunchKernelGGL(repack_conv3x3_kernel<half_t>, grid, dim3(256), 0, s, src, (half_t*)dst, O, I, Op, Ip); break;
-    case 2: hipLaunchKernelGGL(repack_conv3x3_kernel<bf16_t>, grid, dim3(256), 0, s, src, (bf16_t*)dst, O, I, Op, Ip); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
 // Up-sampling conv, 2-byte engines: the bilinear x2 (align_corners = False) folded into per-phase 3x3 weights on the replicate-padded
 // low-resolution input (layout: kernels.h, launch_conv3x3_upfold).  Output pixel (2i + a, 2j + b) of conv3x3(up2(x), w) is
 //   sum_{r,s} Wf[a][b][r][s] xr[i + r - 1, j + s - 1],  Wf[a][b][r][s] = sum_{u,v} R[a][r][u] R[b][s][v] w[u][v]
@@ -973,29 +933,6 @@ hipError_t launch_upconv_fold(int dtype, const float* src, void* dst, int C, hip
   else hipLaunchKernelGGL(upconv_fold_kernel<bf16_t>, grid, dim3(256), 0, s, src, (bf16_t*)dst, C, state);
   return hipGetLastError();
 }
-__global__ void repack_dw_kernel(const float* src, float* dst, int C, int Cp) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= C * 9) return;
-  const int tap = i % 9, c = i / 9;
-  dst[tap * Cp + c] = src[i];
-}
-hipError_t launch_repack_dw(const float* src, float* dst, int C, hipStream_t s, int Cp) {
-  if (Cp <= 0) Cp = C;
-  hipLaunchKernelGGL(repack_dw_kernel, dim3((C * 9 + 255) / 256), dim3(256), 0, s, src, dst, C, Cp);
-  return hipGetLastError();
-}
-// taps flipped: the input-gradient of a depthwise conv is the same conv with w'[t] = w[8 - t]
-__global__ void repack_dw_flip_kernel(const float* src, float* dst, int C, int Cp) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= C * 9) return;
-  const int tap = i % 9, c = i / 9;
-  dst[(8 - tap) * Cp + c] = src[i];
-}
-hipError_t launch_repack_dw_flip(const float* src, float* dst, int C, hipStream_t s, int Cp) {
-  if (Cp <= 0) Cp = C;
-  hipLaunchKernelGGL(repack_dw_flip_kernel, dim3((C * 9 + 255) / 256), dim3(256), 0, s, src, dst, C, Cp);
-  return hipGetLastError();
-}
 
 // Content hash of every parameter (fp32 bits, position-weighted, summed mod 2^64: the order of the partial sums does
 // not matter), so that writes PyTorch's version counters cannot see (`p.data.copy_()`, the reference's EMA
@@ -1037,40 +974,41 @@ hipError_t launch_params_hash(const LoadDesc* descs_dev, int n, unsigned long lo
   return hipGetLastError();
 }
 
+// Every engine layout of a parameter (kernels.h: LoadDesc), stated once: one source element per iteration, scattered to the main
+// destination and to whichever secondary copies the descriptor names.
 template <typename T>
-__global__ void __launch_bounds__(256) load_all_kernel(const LoadDesc* descs, char* blob, const unsigned long long* state) {
-  if (state && state[1] == 0) return;  // parameters unchanged since the last load
-  const LoadDesc d = descs[blockIdx.y];
+__device__ __forceinline__ void load_one(const LoadDesc& d, char* blob) {
   const float* src = d.src;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < d.numel; i += (long long)gridDim.x * 256) {
     const float v = src[i];
-    if (d.kind == 0) {
+    if (d.kind == PK_F32) {
       reinterpret_cast<float*>(blob + d.dst)[i] = v;
-    } else if (d.kind == 1) {
+    } else if (d.kind == PK_MAT) {
       const int r = (int)(i / d.cols), c = (int)(i % d.cols);
       const size_t o = (size_t)r * d.ld + d.col0 + c;
       if (d.as_t) reinterpret_cast<T*>(blob + d.dst)[o] = (T)v;
       else reinterpret_cast<float*>(blob + d.dst)[o] = v;
       if (d.dst_t >= 0) reinterpret_cast<T*>(blob + d.dst_t)[(size_t)c * d.rows + r] = (T)v;
       if (d.dst_f >= 0) reinterpret_cast<T*>(blob + d.dst_f)[pw_expand_pack_index(r, c, d.cols)] = (T)(v * d.fscale);
-    } else if (d.kind == 2) {
+    } else if (d.kind == PK_CONV3) {
       const int tap = (int)(i % 9);
       const int ci = (int)((i / 9) % d.I), co = (int)(i / (9 * (long long)d.I));
       reinterpret_cast<T*>(blob + d.dst)[((size_t)tap * d.Op + co) * d.Ip + ci] = (T)v;
       if (d.dst_t >= 0) reinterpret_cast<T*>(blob + d.dst_t)[((size_t)(8 - tap) * d.Ip + ci) * d.Op + co] = (T)v;
-    } else if (d.kind == 3) {
+    } else if (d.kind == PK_DW) {  // flipped taps: the input-gradient of a depthwise conv is the same conv with w'[t] = w[8 - t]
       const int tap = (int)(i % 9), c = (int)(i / 9);
       reinterpret_cast<float*>(blob + d.dst)[(size_t)tap * d.Op + c] = v;
       if (d.dst_t >= 0) reinterpret_cast<float*>(blob + d.dst_t)[(size_t)(8 - tap) * d.Op + c] = v;
-    } else if (d.kind == 4) {  // init conv OIHW: fp32 [I*9][Op], and (2-byte T) the MFMA pack [tap][Op][8]; padding entries
-                               // keep the zeros the first full load wrote (launch_repack_init*)
+    } else if (d.kind == PK_INIT) {  // input conv OIHW: fp32 [I*9][Op], and (2-byte T) the MFMA pack [tap][Op][8]: tap 9, channels
+                                     // >= I and outputs >= O keep the zeros of llie_create's memset of the blob, like all padding
       const int k = (int)(i % (d.I * 9)), o = (int)(i / (d.I * 9));
       reinterpret_cast<float*>(blob + d.dst)[(size_t)k * d.Op + o] = v;
       if (d.dst_t >= 0) {
         const int tap = k % 9, ci = k / 9;
         reinterpret_cast<T*>(blob + d.dst_t)[((size_t)tap * d.Op + o) * 8 + ci] = (T)v;
       }
-    } else {  // kind 5: output conv OIHW (O <= 4): fp32 [9][Ip][4], and the MFMA pack [Ip/32][18][2][4][8]
+    } else {  // PK_FINAL: output conv OIHW (O <= 4): fp32 [9][Ip][4], and the MFMA pack
+              // dst[(((chunk*18 + ks)*2 + h)*4 + o)*8 + j] = W[o][chunk*32 + (ks&1)*16 + h*8 + j][tap = ks>>1]
       const int tap = (int)(i % 9), ci = (int)((i / 9) % d.I), o = (int)(i / (9 * (long long)d.I));
       reinterpret_cast<float*>(blob + d.dst)[((size_t)tap * d.Ip + ci) * 4 + o] = v;
       if (d.dst_t >= 0) {
@@ -1080,6 +1018,14 @@ __global__ void __launch_bounds__(256) load_all_kernel(const LoadDesc* descs, ch
     }
   }
 }
+template <typename T>
+__global__ void __launch_bounds__(256) load_all_kernel(const LoadDesc* descs, char* blob, const unsigned long long* state) {
+  if (state && state[1] == 0) return;  // parameters unchanged since the last load
+  const LoadDesc d = descs[blockIdx.y];
+  load_one<T>(d, blob);
+}
+template <typename T>
+__global__ void __launch_bounds__(256) load_one_kernel(const LoadDesc d, char* blob) { load_one<T>(d, blob); }
 hipError_t launch_load_all(int dtype, const LoadDesc* descs_dev, int n, char* blob, hipStream_t s, const unsigned long long* state) {
   dim3 grid(32, n);
   switch (dtype) {
@@ -1090,70 +1036,14 @@ hipError_t launch_load_all(int dtype, const LoadDesc* descs_dev, int n, char* bl
   }
   return hipGetLastError();
 }
-
-// init_conv OIHW [O][I][3][3] -> [I*9][O];  final_conv OIHW [O<=4][I][3][3] -> [9][I][4] zero padded
-__global__ void repack_init_kernel(const float* src, float* dst, int O, int I, int Op) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= O * I * 9) return;
-  const int k = i % (I * 9), o = i / (I * 9);
-  dst[k * Op + o] = src[i];
-}
-hipError_t launch_repack_init(const float* src, float* dst, int O, int I, hipStream_t s, int Op) {
-  if (Op <= 0) Op = O;
-  hipLaunchKernelGGL(repack_init_kernel, dim3((O * I * 9 + 255) / 256), dim3(256), 0, s, src, dst, O, I, Op);
-  return hipGetLastError();
-}
-// init_conv for the MFMA kernel: dst[((s*2+h)*O + n)*8 + ci] = W[n][ci][tap = 2s+h] (zero when tap > 8 or ci >= I)
-template <typename T>
-__global__ void repack_init_mfma_kernel(const float* src, T* dst, int O, int I, int Op) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 10 * Op * 8) return;
-  const int ci = i & 7, n = (i >> 3) % Op, tap = (i >> 3) / Op;
-  dst[i] = (tap < 9 && ci < I && n < O) ? (T)src[((size_t)n * I + ci) * 9 + tap] : (T)0.f;
-}
-hipError_t launch_repack_init_mfma(int dtype, const float* src, void* dst, int O, int I, hipStream_t s, int Op) {
-  if (I > 8) return hipErrorInvalidValue;
-  if (Op <= 0) Op = O;
-  dim3 grid((10 * Op * 8 + 255) / 256);
+hipError_t launch_load_one(int dtype, const LoadDesc& d, char* blob, hipStream_t s) {
+  dim3 grid((unsigned)((d.numel + 255) / 256));
   switch (dtype) {
-    case 1: hipLaunchKernelGGL(repack_init_mfma_kernel<half_t>, grid, dim3(256), 0, s, src, (half_t*)dst, O, I, Op); break;
-    case 2: hipLaunchKernelGGL(repack_init_mfma_kernel<bf16_t>, grid, dim3(256), 0, s, src, (bf16_t*)dst, O, I, Op); break;
+    case 0: hipLaunchKernelGGL(load_one_kernel<float>, grid, dim3(256), 0, s, d, blob); break;
+    case 1: hipLaunchKernelGGL(load_one_kernel<half_t>, grid, dim3(256), 0, s, d, blob); break;
+    case 2: hipLaunchKernelGGL(load_one_kernel<bf16_t>, grid, dim3(256), 0, s, d, blob); break;
     default: return hipErrorInvalidValue;
   }
-  return hipGetLastError();
-}
-// final_conv for the MFMA kernel: dst[(((chunk*18 + ks)*2 + h)*4 + o)*8 + j] = W[o][chunk*32 + (ks&1)*16 + h*8 + j][tap = ks>>1]
-template <typename T>
-__global__ void repack_final_mfma_kernel(const float* src, T* dst, int O, int I, int Ip) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int total = (Ip / 32) * 18 * 2 * 4 * 8;
-  if (i >= total) return;
-  const int j = i & 7, o = (i >> 3) & 3, h = (i >> 5) & 1, ks = (i >> 6) % 18, chunk = (i >> 6) / 18;
-  const int ci = chunk * 32 + (ks & 1) * 16 + h * 8 + j, tap = ks >> 1;
-  dst[i] = (o < O && ci < I) ? (T)src[((size_t)o * I + ci) * 9 + tap] : (T)0.f;
-}
-hipError_t launch_repack_final_mfma(int dtype, const float* src, void* dst, int O, int I, hipStream_t s, int Ip) {
-  if (Ip <= 0) Ip = I;
-  if (O > 4 || Ip % 32) return hipErrorInvalidValue;
-  const int total = (Ip / 32) * 18 * 2 * 4 * 8;
-  dim3 grid((total + 255) / 256);
-  switch (dtype) {
-    case 1: hipLaunchKernelGGL(repack_final_mfma_kernel<half_t>, grid, dim3(256), 0, s, src, (half_t*)dst, O, I, Ip); break;
-    case 2: hipLaunchKernelGGL(repack_final_mfma_kernel<bf16_t>, grid, dim3(256), 0, s, src, (bf16_t*)dst, O, I, Ip); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-__global__ void repack_final_kernel(const float* src, float* dst, int O, int I, int Ip) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 9 * Ip * 4) return;
-  const int o = i & 3, ci = (i >> 2) % Ip, tap = (i >> 2) / Ip;
-  dst[i] = (o < O && ci < I) ? src[((size_t)o * I + ci) * 9 + tap] : 0.f;
-}
-hipError_t launch_repack_final(const float* src, float* dst, int O, int I, hipStream_t s, int Ip) {
-  if (O > 4) return hipErrorInvalidValue;
-  if (Ip <= 0) Ip = I;
-  hipLaunchKernelGGL(repack_final_kernel, dim3((9 * Ip * 4 + 255) / 256), dim3(256), 0, s, src, dst, O, I, Ip);
   return hipGetLastError();
 }
 
