@@ -40,6 +40,8 @@ EXPORTS = [
     "llie_expand_dw", "llie_expand_pool", "llie_expand_dw_project", "llie_expand_dw_project_skip", "llie_irbx_project_tiles",
     "llie_expand_stats", "llie_irbx_stats_rows",
     "llie_dwconv3x3_ex", "llie_dwconv3x3_strip_rows", "llie_last_kernel",
+    "llie_init_conv", "llie_init_conv_tiles", "llie_init_conv_pack_bytes", "llie_final_conv", "llie_final_conv_pack_bytes",
+    "llie_se_gate", "llie_affine_add", "llie_nchw_to_nhwc", "llie_nhwc_to_nchw", "llie_pw_gemm_dot",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 
@@ -190,6 +192,18 @@ def lib() -> C.CDLL:
     L.llie_dwconv3x3_tiles.argtypes = [ci, ci]
     L.llie_dwconv3x3_ex.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
     L.llie_dwconv3x3_strip_rows.argtypes = [ci, ci, ci, ci, ci]
+    L.llie_init_conv_pack_bytes.argtypes = [ci, ci]
+    L.llie_init_conv_pack_bytes.restype = i64
+    L.llie_init_conv_tiles.argtypes = [ci, ci, ci]
+    L.llie_init_conv.argtypes = [ci, vp, ci, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, i64, vp]
+    L.llie_final_conv_pack_bytes.argtypes = [ci]
+    L.llie_final_conv_pack_bytes.restype = i64
+    L.llie_final_conv.argtypes = [ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(StepCoef), vp, vp, vp, vp, vp, i64, vp]
+    L.llie_se_gate.argtypes = [ci, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp, vp, vp]
+    L.llie_affine_add.argtypes = [ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]
+    L.llie_nchw_to_nhwc.argtypes = [ci, vp, vp, vp, ci, ci, ci, ci, ci, vp]
+    L.llie_nhwc_to_nchw.argtypes = [ci, vp, vp, ci, ci, ci, ci, ci, vp]
+    L.llie_pw_gemm_dot.argtypes = [ci, C.POINTER(GemmSeg), ci, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     L.llie_last_kernel.argtypes = []
     L.llie_last_kernel.restype = C.c_char_p
     L.llie_expand_dw.argtypes = [ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]

@@ -211,12 +211,14 @@ hipError_t launch_init_conv(int dtype, const InitConvArgs& a, hipStream_t s) {
   const bool mfma = a.wp && dtype != 0;
   dim3 grid(init_conv_ntiles(a.H, a.W, mfma), a.B);  // 256-pixel tiles: 16 x 16 (VALU kernel) or 8 x 32 (MFMA kernel)
   switch (dtype) {
-    case 0: hipLaunchKernelGGL(init_conv_kernel<float>, grid, dim3(256), 0, s, a); break;
+    case 0: note_kernel("init_conv_kernel<float>"); hipLaunchKernelGGL(init_conv_kernel<float>, grid, dim3(256), 0, s, a); break;
     case 1:
+      note_kernel(a.wp ? "init_conv_mfma_kernel<_Float16>" : "init_conv_kernel<_Float16>");
       if (a.wp) hipLaunchKernelGGL(init_conv_mfma_kernel<half_t>, grid, dim3(256), 0, s, a);
       else hipLaunchKernelGGL(init_conv_kernel<half_t>, grid, dim3(256), 0, s, a);
       break;
     case 2:
+      note_kernel(a.wp ? "init_conv_mfma_kernel<__bf16>" : "init_conv_kernel<__bf16>");
       if (a.wp) hipLaunchKernelGGL(init_conv_mfma_kernel<bf16_t>, grid, dim3(256), 0, s, a);
       else hipLaunchKernelGGL(init_conv_kernel<bf16_t>, grid, dim3(256), 0, s, a);
       break;
@@ -424,12 +426,14 @@ hipError_t launch_final_conv(int dtype, const FinalConvArgs& a, hipStream_t s) {
   if (!a.fuse_step && !a.out) return hipErrorInvalidValue;
   dim3 grid(((a.H + 15) / 16) * ((a.W + 15) / 16), a.B);
   switch (dtype) {
-    case 0: hipLaunchKernelGGL(final_conv_kernel<float>, grid, dim3(256), 0, s, a); break;
+    case 0: note_kernel("final_conv_kernel<float>"); hipLaunchKernelGGL(final_conv_kernel<float>, grid, dim3(256), 0, s, a); break;
     case 1:
+      note_kernel(a.wp ? "final_conv_mfma_kernel<_Float16, 16>" : "final_conv_kernel<_Float16>");
       if (a.wp) hipLaunchKernelGGL((final_conv_mfma_kernel<half_t, 16>), grid, dim3(256), 0, s, a);
       else hipLaunchKernelGGL(final_conv_kernel<half_t>, grid, dim3(256), 0, s, a);
       break;
     case 2:
+      note_kernel(a.wp ? "final_conv_mfma_kernel<__bf16, 16>" : "final_conv_kernel<__bf16>");
       if (a.wp) hipLaunchKernelGGL((final_conv_mfma_kernel<bf16_t, 16>), grid, dim3(256), 0, s, a);
       else hipLaunchKernelGGL(final_conv_kernel<bf16_t>, grid, dim3(256), 0, s, a);
       break;

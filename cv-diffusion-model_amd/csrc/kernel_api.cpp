@@ -4,6 +4,8 @@
 
 using namespace llie;
 
+static bool dtype_ok(int dtype) { return dtype >= 0 && dtype <= 2; }
+
 int llie::kerr(const char* what, hipError_t e, int refuse_rc, const char* refuse_msg) {
   if (e == hipSuccess) return LLIE_OK;
   if (e == hipErrorInvalidValue && refuse_rc) {
@@ -37,8 +39,9 @@ int llie_gram_stats(int dtype, const void* x0, int c0, const void* x1, int c1, c
 int64_t llie_gram_part_floats(int K, int pixels) { return (K == 32 || K == 64 || K == 96) && pixels > 0 && pixels % 512 == 0 ? (int64_t)gram_part_floats(K, pixels) : LLIE_ERR_ARG; }
 
 // ---- kernel-level entry points (unit tests, tuning): thin wrappers over the launch API
-int llie_pw_gemm(int dtype, const llie_gemm_seg* segs, int nseg, const void* w, const float* bias, const void* residual,
-                 void* out, float* stats, int M, int N, int P, llie_stream stream) {
+}  // extern "C"
+static int pw_gemm_call(const char* what, int dtype, const llie_gemm_seg* segs, int nseg, const void* w, const float* bias, const void* residual,
+                        const void* dot, void* out, float* stats, int M, int N, int P, llie_stream stream) {
   if (!segs || nseg < 1 || nseg > 3 || !w || !out || dtype < 0 || dtype > 2) return LLIE_ERR_ARG;
   // the kernel's prologue is affine (+ ReLU6 / clamp01) and runs only where a segment has a table: an activation it does not
   // have (SiLU), an activation or a shift without a scale table, or a table row shorter than the segment would be computed as
@@ -47,15 +50,26 @@ int llie_pw_gemm(int dtype, const llie_gemm_seg* segs, int nseg, const void* w, 
     const llie_gemm_seg& sg = segs[i];
     if ((sg.act != ACT_NONE && sg.act != ACT_RELU6 && sg.act != ACT_RELU6_S6) || (!sg.scale && (sg.act != ACT_NONE || sg.bias)) ||
         (sg.scale && sg.affine_ld < sg.channels)) {
-      set_err("pw_gemm: segment %d: act 0, 1 or 3; an activation or a shift needs a scale table; affine_ld >= channels", i);
+      set_err("%s: segment %d: act 0, 1 or 3; an activation or a shift needs a scale table; affine_ld >= channels", what, i);
       return LLIE_ERR_ARG;
     }
   }
   GemmArgs g{};
   g.nseg = nseg;
   g.K = to_segs(segs, nseg, g.seg);
-  g.w = w; g.bias = bias; g.res = residual; g.out = out; g.stats = stats; g.M = M; g.N = N; g.P = P;
-  return kerr("pw_gemm", launch_pw_gemm(dtype, g, hs(stream)));
+  g.w = w; g.bias = bias; g.res = residual; g.dot = dot; g.out = out; g.stats = stats; g.M = M; g.N = N; g.P = P;
+  return kerr(what, launch_pw_gemm(dtype, g, hs(stream)));
+}
+extern "C" {
+int llie_pw_gemm(int dtype, const llie_gemm_seg* segs, int nseg, const void* w, const float* bias, const void* residual,
+                 void* out, float* stats, int M, int N, int P, llie_stream stream) {
+  return pw_gemm_call("pw_gemm", dtype, segs, nseg, w, bias, residual, nullptr, out, stats, M, N, P, stream);
+}
+// the backward pass's epilogue (backward.cpp: gemm(.., with_dot)): the slab holds (sum out * dot, sum out) per tile
+int llie_pw_gemm_dot(int dtype, const llie_gemm_seg* segs, int nseg, const void* w, const float* bias, const void* dot, void* out,
+                     float* stats, int M, int N, int P, llie_stream stream) {
+  if (!dot || !stats) return LLIE_ERR_ARG;
+  return pw_gemm_call("pw_gemm_dot", dtype, segs, nseg, w, bias, nullptr, dot, out, stats, M, N, P, stream);
 }
 
 int llie_pw_expand(int dtype, const llie_gemm_seg* segs, int nseg, const float* w32, void* wpack, void* out, float* stats,
@@ -165,6 +179,113 @@ int llie_se_mlp(int dtype, const float* pool_sums, int pixels, const void* w1, c
   if (e == hipSuccess) e = launch_se_fc2(dtype, a, hs(stream));
   return kerr("se_mlp", e);
 }
+
+// ---- the network's first and last kernels, the SE gate of the inference blocks, the attention tail and the layout converters.
+// Every contract check runs here, before any HIP call.  The two convs take the reference's OIHW weights: the wrapper zero-fills the
+// caller's pack scratch and runs the engine's own repack (launch_load_one with a PK_INIT / PK_FINAL descriptor) before the launch.
+static int64_t align16(int64_t n) { return (n + 15) & ~(int64_t)15; }
+static bool conv_sizes_ok(int B, int H, int W) { return B > 0 && B <= 65535 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0; }
+int64_t llie_init_conv_pack_bytes(int Cin, int Cout) {
+  if (Cin < 1 || Cin > 8 || Cout <= 0 || Cout % 32) return LLIE_ERR_ARG;
+  return align16((int64_t)Cin * 9 * Cout * 4) + (int64_t)10 * Cout * 8 * 2;  // fp32 [Cin * 9][Cout], then the MFMA pack [10][Cout][8] T
+}
+int64_t llie_final_conv_pack_bytes(int C) {
+  if (C <= 0 || C % 32) return LLIE_ERR_ARG;
+  return (int64_t)9 * C * 4 * 4 + (int64_t)(C / 32) * 18 * 2 * 4 * 8 * 2;  // fp32 [9][C][4], then the MFMA pack [C / 32][18][2][4][8] T
+}
+int llie_init_conv_tiles(int H, int W, int mfma) { return H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0 ? init_conv_ntiles(H, W, mfma != 0) : LLIE_ERR_ARG; }
+int llie_init_conv(int dtype, const float* x0, int c0, const float* x1, int c1, const float* w_oihw, const float* bias, void* out, float* stats,
+                   int batch, int H, int W, int Cout, int use_mfma, void* pack, int64_t pack_bytes, llie_stream stream) {
+  if (!dtype_ok(dtype) || !x0 || !w_oihw || !bias || !out || !pack || ((uintptr_t)pack & 15) || c0 < 1 || c1 < 0 || c0 + c1 > 8 ||
+      (c1 > 0) != (x1 != nullptr) || !conv_sizes_ok(batch, H, W) || Cout <= 0 || Cout % 32 || use_mfma < 0 || use_mfma > 1 ||
+      (use_mfma && dtype == 0) || pack_bytes < llie_init_conv_pack_bytes(c0 + c1, Cout))
+    return LLIE_ERR_ARG;
+  const int Cin = c0 + c1;
+  const int64_t need = llie_init_conv_pack_bytes(Cin, Cout), off = align16((int64_t)Cin * 9 * Cout * 4);
+  char* blob = reinterpret_cast<char*>(pack);
+  LoadDesc d{};
+  d.src = w_oihw; d.kind = PK_INIT; d.O = Cout; d.I = Cin; d.Op = Cout; d.Ip = Cin; d.numel = (long long)Cout * Cin * 9;
+  d.dst = 0; d.dst_t = use_mfma ? off : -1; d.dst_f = -1;
+  InitConvArgs a{};
+  a.x0 = x0; a.x1 = x1; a.c0 = c0; a.c1 = c1; a.w = reinterpret_cast<const float*>(blob); a.bias = bias; a.wp = use_mfma ? blob + off : nullptr;
+  a.out = out; a.stats = stats; a.B = batch; a.H = H; a.W = W; a.Cout = Cout;
+  hipStream_t s = hs(stream);
+  hipError_t e = launch_fill_zero(blob, need, s);
+  if (e == hipSuccess) e = launch_load_one(dtype, d, blob, s);
+  if (e == hipSuccess) e = launch_init_conv(dtype, a, s);
+  return kerr("init_conv", e);
+}
+int llie_final_conv(int dtype, const void* in, const float* scale, const float* shift, const float* w_oihw, const float* bias, float* out,
+                    int batch, int H, int W, int C, int Cout, int use_mfma, const llie_step_coef* coef, const float* sample, const float* noise,
+                    float* prev, float* clamped, void* pack, int64_t pack_bytes, llie_stream stream) {
+  if (!dtype_ok(dtype) || !in || !scale || !shift || !w_oihw || !bias || !pack || ((uintptr_t)pack & 15) || !conv_sizes_ok(batch, H, W) ||
+      C <= 0 || C % 32 || Cout < 1 || Cout > 4 || use_mfma < 0 || use_mfma > 1 || (use_mfma && dtype == 0) ||
+      pack_bytes < llie_final_conv_pack_bytes(C))
+    return LLIE_ERR_ARG;
+  // the scheduler step lives in the MFMA kernel's epilogue alone; without it the noise prediction is the only output
+  if (coef ? (!use_mfma || !sample || !prev || (!coef->is_last && !noise)) : (!out || sample || noise || prev || clamped)) return LLIE_ERR_ARG;
+  const int64_t need = llie_final_conv_pack_bytes(C), off = (int64_t)9 * C * 4 * 4;
+  char* blob = reinterpret_cast<char*>(pack);
+  LoadDesc d{};
+  d.src = w_oihw; d.kind = PK_FINAL; d.O = Cout; d.I = C; d.Op = Cout; d.Ip = C; d.numel = (long long)Cout * C * 9;
+  d.dst = 0; d.dst_t = use_mfma ? off : -1; d.dst_f = -1;
+  FinalConvArgs a{};
+  a.in = in; a.as = scale; a.ab = shift; a.w = reinterpret_cast<const float*>(blob); a.bias = bias; a.wp = use_mfma ? blob + off : nullptr;
+  a.out = out; a.B = batch; a.H = H; a.W = W; a.C = C; a.Cout = Cout;
+  if (coef) {
+    a.fuse_step = 1;
+    a.coef = StepCoef{coef->sqrt_alpha_t, coef->sqrt_beta_t, coef->sqrt_alpha_prev, coef->sqrt_beta_prev, coef->is_last, coef->v_prediction,
+                      coef->clamp_x0};
+    a.sample = sample; a.noise = noise; a.prev = prev; a.clamped = clamped;
+  }
+  hipStream_t s = hs(stream);
+  hipError_t e = launch_fill_zero(blob, need, s);
+  if (e == hipSuccess) e = launch_load_one(dtype, d, blob, s);
+  if (e == hipSuccess) e = launch_final_conv(dtype, a, s);
+  return kerr("final_conv", e);
+}
+// the SE gate from the depthwise kernels' fixed-point totals, by each path Run::se_gate can take: 0 se_gate_kernel, 1 se_fc1 + se_fc2
+// reading the totals, 2 the MFMA pair (2-byte types)
+int llie_se_gate(int dtype, const unsigned long long* totals, int pixels, const void* w1, const float* b1, const void* w2, const float* b2,
+                 float* gate, int batch, int C, int Cs, int path, float* hidden_scratch, long long* pre_scratch, llie_stream stream) {
+  if (!dtype_ok(dtype) || !totals || !w1 || !b1 || !w2 || !b2 || !gate || pixels <= 0 || batch <= 0 || C <= 0 || Cs <= 0 || path < 0 || path > 2)
+    return LLIE_ERR_ARG;
+  SeArgs a{};
+  a.tot = totals; a.ntiles = 1; a.P = pixels; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.hid = hidden_scratch; a.pre = pre_scratch; a.gate = gate;
+  a.B = batch; a.C = C; a.Cs = Cs;
+  hipStream_t s = hs(stream);
+  if (path == 0) {
+    if (C % (dtype == 0 ? 64 : 128) || (int64_t)(C + Cs) * 4 > 48 * 1024) return LLIE_ERR_ARG;
+    return kerr("se_gate", launch_se_gate(dtype, a, s));
+  }
+  if (path == 1) {
+    if (!hidden_scratch || C > 4096 || Cs > 4096) return LLIE_ERR_ARG;  // four images' rows in 64 KB of LDS
+    hipError_t e = launch_se_fc1(dtype, a, s);
+    if (e == hipSuccess) e = launch_se_fc2(dtype, a, s);
+    return kerr("se_gate", e);
+  }
+  if (!pre_scratch || !se_mlp_mfma_supported(dtype, a)) return LLIE_ERR_ARG;
+  hipError_t e = launch_fill_zero(pre_scratch, (int64_t)batch * Cs * 8, s);  // the kernel's contract: zero at launch
+  if (e == hipSuccess) e = launch_se_mlp_mfma(dtype, a, s);
+  return kerr("se_gate", e);
+}
+int llie_affine_add(int dtype, const void* x, const float* scale, const float* shift, const void* res, void* y, float* stats, int M, int C, int P,
+                    llie_stream stream) {
+  if (!dtype_ok(dtype) || !x || !scale || !shift || !y || M <= 0 || P <= 0 || M % P || C <= 0 || C % 8 || C > 2048) return LLIE_ERR_ARG;
+  AffineAddArgs a{};
+  a.x = x; a.as = scale; a.ab = shift; a.res = res; a.y = y; a.stats = stats; a.M = M; a.C = C; a.P = P;
+  return kerr("affine_add", launch_affine_add(dtype, a, hs(stream)));
+}
+int llie_nchw_to_nhwc(int dtype, const float* x, void* y, float* stats, int batch, int C, int P, int Csrc, int coff, llie_stream stream) {
+  if (!dtype_ok(dtype) || !x || !y || batch <= 0 || C <= 0 || C % 32 || P <= 0 || P % 64 || coff < 0 || Csrc < coff + C || batch > 65535 || C / 32 > 65535)
+    return LLIE_ERR_ARG;
+  return kerr("nchw_to_nhwc", launch_nchw_to_nhwc(dtype, x, y, stats, batch, C, P, Csrc, coff, hs(stream)));
+}
+int llie_nhwc_to_nchw(int dtype, const void* x, float* y, int batch, int C, int P, int Cdst, int coff, llie_stream stream) {
+  if (!dtype_ok(dtype) || !x || !y || batch <= 0 || C <= 0 || C % 32 || P <= 0 || P % 64 || coff < 0 || Cdst < coff + C || batch > 65535 || C / 32 > 65535)
+    return LLIE_ERR_ARG;
+  return kerr("nhwc_to_nchw", launch_nhwc_to_nchw(dtype, x, y, batch, C, P, hs(stream), Cdst, coff));
+}
 int llie_film(const float* silu_temb, const float* wf, const float* bf, float* film, int rows, int T, int F, llie_stream stream) {
   if (!silu_temb || !wf || !bf || !film || rows <= 0 || T <= 0 || F <= 0) return LLIE_ERR_ARG;
   FilmArgs a{};
@@ -173,7 +294,6 @@ int llie_film(const float* silu_temb, const float* wf, const float* bf, float* f
 }
 
 // ---- backward kernels (training): thin wrappers over the launch API; every contract check runs here, before any HIP call
-static bool dtype_ok(int dtype) { return dtype >= 0 && dtype <= 2; }
 static int wgrad_rule(int dtype, int batch, int pixels, int N, int K, int ntap, int ragged_rule) {
   const int M = wgrad_rows(batch, pixels);
   return ragged_rule ? wgrad_msplit_ragged(dtype, M, N, K, ntap) : wgrad_msplit(dtype, M, N, K, ntap);

@@ -438,6 +438,50 @@ int llie_se_mlp(int dtype, const float* pool_sums, int pixels, const void* w1, c
                 float* hidden_scratch, float* gate, int batch, int C, int Cs, llie_stream stream);
 int llie_film(const float* silu_temb, const float* wf, const float* bf, float* film, int rows, int T, int F, llie_stream stream);
 
+/* The network's first and last kernels, the SE gate of the inference blocks, the attention tail, the layout converters and the
+ * backward pass's GEMM epilogue.  Every contract clause below is checked before any HIP call and answered with LLIE_ERR_ARG.
+ * llie_init_conv: init_conv (efficient_unet.py:420,553) on the virtual concat of two fp32 NCHW halves x0 [batch][c0][H][W] and x1
+ *   [batch][c1][H][W] (x1 NULL exactly when c1 == 0; 1 <= c0, c0 + c1 <= 8) -> out NHWC [batch][H][W][Cout] of the compute type, plus
+ *   (stats, optional) the statistics slab [batch][llie_init_conv_tiles(H, W, use_mfma)][2][Cout] of the stored values: tiles of 16 x
+ *   16 pixels, or 8 rows x 32 columns with use_mfma, row-major, pixels past the image counting for nothing.  w_oihw fp32 [Cout][c0 +
+ *   c1][3][3] and bias fp32 [Cout] as the reference holds them: the call zero-fills `pack` (llie_init_conv_pack_bytes(c0 + c1,
+ *   Cout) bytes, 16-byte aligned) and repacks into it as llie_load_param does.  use_mfma 0: the VALU kernel (any dtype; fp32 operands);
+ *   1: the MFMA kernel of the 2-byte engines (inputs and weights rounded to the compute type).  Refused: H or W not a multiple of 8,
+ *   Cout not a multiple of 32, batch > 65535, use_mfma with LLIE_F32, a pack that is short or misaligned, NULL tensors.
+ * llie_final_conv: the output head (:528-530,600-602): out fp32 NCHW [batch][Cout][H][W] = conv3x3(silu(in * scale + shift)) + bias,
+ *   zero padding after the activation; in NHWC [batch][H][W][C] of the compute type, C a multiple of 32, scale / shift fp32
+ *   [batch][C], w_oihw fp32 [Cout][C][3][3], 1 <= Cout <= 4, bias fp32 [Cout]; pack: llie_final_conv_pack_bytes(C) bytes, as above.
+ *   coef non-NULL (use_mfma only) fuses llie_lcm_step into the epilogue: sample / noise / prev / clamped fp32 [batch][Cout][H][W],
+ *   noise may be NULL when is_last, clamped and then also out may be NULL.  Without coef, out is required and the four must be NULL.
+ * llie_se_gate: gate [batch][C] = sigmoid(W2 relu6(W1 mean + b1) + b2) from the depthwise kernels' fixed-point channel totals
+ *   (int64 [batch][C], mean = total / (pixels 2^24)); w1 [Cs][C], w2 [C][Cs] of the compute type, b1 / b2 fp32.  path 0: one launch
+ *   (C a multiple of 64 in fp32, 128 otherwise; (C + Cs) * 4 <= 48 KiB); path 1: the row-parallel pair, hidden_scratch fp32
+ *   [batch][Cs] (C, Cs <= 4096); path 2: the MFMA pair (2-byte types, C a multiple of 256 and >= 512, Cs a multiple of 64 in [64,
+ *   512]), pre_scratch int64 [batch][Cs], zero-filled by the call.  The mean is never stored on these paths.
+ * llie_affine_add: y = x * scale + shift (+ res) on NHWC rows [M][C] (scale / shift fp32 [M / P][C], C a multiple of 8, <= 2048, M a
+ *   multiple of P), plus (optional) y's statistics slab [M / P][ceil(P / 64)][2][C].
+ * llie_nchw_to_nhwc: channels [coff, coff + C) of x fp32 [batch][Csrc][P] -> y [batch][P][C] of the compute type, plus (optional) its
+ *   statistics slab [batch][P / 64][2][C]; llie_nhwc_to_nchw: x [batch][P][C] -> channels [coff, coff + C) of y fp32
+ *   [batch][Cdst][P], the others untouched.  C a multiple of 32, P of 64, coff + C within Csrc / Cdst.
+ * llie_pw_gemm_dot: llie_pw_gemm without a residual, with the epilogue of the backward pass: dot [M][N] of the compute type and the
+ *   (mandatory) slab, which then holds (sum out * dot, sum out) per tile instead of (sum, sum of squares). */
+int64_t llie_init_conv_pack_bytes(int Cin, int Cout);
+int llie_init_conv_tiles(int H, int W, int mfma);
+int llie_init_conv(int dtype, const float* x0, int c0, const float* x1, int c1, const float* w_oihw, const float* bias, void* out, float* stats,
+                   int batch, int H, int W, int Cout, int use_mfma, void* pack, int64_t pack_bytes, llie_stream stream);
+int64_t llie_final_conv_pack_bytes(int C);
+int llie_final_conv(int dtype, const void* in, const float* scale, const float* shift, const float* w_oihw, const float* bias, float* out,
+                    int batch, int H, int W, int C, int Cout, int use_mfma, const llie_step_coef* coef, const float* sample, const float* noise,
+                    float* prev, float* clamped, void* pack, int64_t pack_bytes, llie_stream stream);
+int llie_se_gate(int dtype, const unsigned long long* totals, int pixels, const void* w1, const float* b1, const void* w2, const float* b2,
+                 float* gate, int batch, int C, int Cs, int path, float* hidden_scratch, long long* pre_scratch, llie_stream stream);
+int llie_affine_add(int dtype, const void* x, const float* scale, const float* shift, const void* res, void* y, float* stats, int M, int C, int P,
+                    llie_stream stream);
+int llie_nchw_to_nhwc(int dtype, const float* x, void* y, float* stats, int batch, int C, int P, int Csrc, int coff, llie_stream stream);
+int llie_nhwc_to_nchw(int dtype, const void* x, float* y, int batch, int C, int P, int Cdst, int coff, llie_stream stream);
+int llie_pw_gemm_dot(int dtype, const llie_gemm_seg* segs, int nseg, const void* w, const float* bias, const void* dot, void* out,
+                     float* stats, int M, int N, int P, llie_stream stream);
+
 /* ---- Backward kernels of the training step (bwd.hip, wgrad.hip), one entry point each, with the conventions above: dtype 0 / 1 / 2,
  * NHWC activations and activation gradients of the compute type, fp32 tables and parameter gradients, device pointers.  Every
  * entry point returns LLIE_ERR_ARG for a bad argument before it makes any HIP call.

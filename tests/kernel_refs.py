@@ -1,5 +1,6 @@
 """Plain float64 references of the kernels behind the C ABI's per-kernel entry points, and the comparison helpers of the kernel
-tests (tests/test_gpu_forward_kernels.py, tests/test_forward_refs_host.py, tests/test_gpu_backward_kernels.py).
+tests (tests/test_gpu_forward_kernels.py, tests/test_gpu_boundary_kernels.py, tests/test_forward_refs_host.py,
+tests/test_gpu_backward_kernels.py).
 
 Pure torch on CPU tensors, one function per operation.  A reference mirrors exactly the roundings its kernel does -- listed in each
 docstring, read from the kernel -- and nothing else: fp32 accumulation becomes float64.  Every reference returns
@@ -13,6 +14,8 @@ MI355X (the worst ratio over every case of the kernel and three seeds stands bes
 
 Layouts are the kernels': activations NHWC, [B][P][C] or [B][H][W][C]; tables [B][ld] fp32; dtype 0 fp32, 1 fp16, 2 bf16.
 """
+import math
+
 import torch
 
 U = 2.0 ** -24
@@ -66,6 +69,49 @@ def _ratio(out, ref, abssum, slack=None, bar=None, what=""):
 def _f32(x):
     """one fp32 rounding of a float64 value"""
     return x.float().double()
+
+
+# ------------------------------------------------------------------------------------------------ device buffers of the GPU tests
+CANARY = 12352.0  # exact in fp16 and bf16
+GUARD = 16        # canary elements on each side (keeps 16-byte alignment for every type)
+NAN = float("nan")
+
+
+class Guarded:
+    """A device buffer of `shape` between two rows of canaries, filled with `fill` (NaN: entries never written show up)."""
+
+    def __init__(self, shape, dev, dtype=torch.float32, fill=NAN):
+        n = int(math.prod(shape))
+        self.full = torch.full((n + 2 * GUARD,), CANARY, dtype=dtype, device=dev)
+        self.v = self.full[GUARD:GUARD + n].view(shape)
+        self.v.fill_(fill)
+
+    @property
+    def ptr(self):
+        return self.v.data_ptr()
+
+    def cpu(self, what=""):
+        f = self.full.cpu()
+        assert (f[:GUARD] == CANARY).all() and (f[-GUARD:] == CANARY).all(), f"{what}: wrote outside its buffer"
+        return f[GUARD:-GUARD].view(self.v.shape)
+
+
+def _bits(t):
+    return t.float().view(torch.int32) if t.dtype != torch.int64 else t
+
+
+def _same(a, b, what):
+    assert torch.equal(_bits(a), _bits(b)), f"{what}: two calls differ"
+
+
+def _slab(dev, B, nt, *inner):
+    """a [B][nt][inner] slab as the kernels index it, plus one extra guarded entry past the helper's count"""
+    return Guarded((B * nt + 1,) + inner, dev)
+
+
+def _split(s, B, nt, what):
+    assert torch.isnan(s[B * nt:]).all(), f"{what}: written past the helper's tile count"
+    return s[:B * nt].view(B, nt, *s.shape[1:])
 
 
 # ------------------------------------------------------------------------------------------------ llie_pw_gemm (gemm.hip)
@@ -231,15 +277,15 @@ def conv3x3_ref(dtype, x, w, bias, mode):
     return ref, ab, sl + _ulp(ref, dtype)
 
 
-def conv_tile_stats_ref(stored, tw):
-    """Statistics slab of a [B][Ho][Wo][Cout] output as stored: [B][ceil(Ho / 8) * ceil(Wo / tw)][2][Cout], tile = 8 rows x tw
-    columns, pixels past the image count for nothing.  -> (ref, abssum, slack)."""
+def conv_tile_stats_ref(stored, tw, th=8):
+    """Statistics slab of a [B][Ho][Wo][Cout] output as stored: [B][ceil(Ho / th) * ceil(Wo / tw)][2][Cout], tile = th rows x tw
+    columns, row-major tile index, pixels past the image count for nothing.  -> (ref, abssum, slack)."""
     q = stored.double()
     B, H, W, C = q.shape
-    ny, nx = (H + 7) // 8, (W + tw - 1) // tw
-    qp = torch.zeros(B, ny * 8, nx * tw, C, dtype=torch.float64)
+    ny, nx = (H + th - 1) // th, (W + tw - 1) // tw
+    qp = torch.zeros(B, ny * th, nx * tw, C, dtype=torch.float64)
     qp[:, :H, :W] = q
-    qp = qp.view(B, ny, 8, nx, tw, C)
+    qp = qp.view(B, ny, th, nx, tw, C)
     s1, s2, sa = qp.sum((2, 4)), (qp * qp).sum((2, 4)), qp.abs().sum((2, 4))
     ref = torch.stack([s1, s2], 3).reshape(B, ny * nx, 2, C)
     ab = torch.stack([sa, s2], 3).reshape(B, ny * nx, 2, C)
@@ -336,6 +382,154 @@ def se_mlp_ref(sums, P, w1, b1, w2, b2, mean=None, hidden=None):
     return (m, ma), (h, ha), (g, g * (1 - g) * va + g)
 
 
+# ------------------------------------------------------------------------------------------------ llie_init_conv (conv.hip)
+def oihw_taps(w):
+    """OIHW [O][I][3][3] -> tap-major [9][O][I] (tap = 3 ky + kx), float64"""
+    return w.double().permute(2, 3, 0, 1).reshape(9, w.shape[0], w.shape[1])
+
+
+def init_conv_ref(dtype, x0, x1, w, bias, mfma):
+    """llie_init_conv: out NHWC [B][H][W][Cout] = conv3x3(cat(x0, x1), w) + bias, stride 1, zero padding.  x0 / x1 fp32 NCHW (x1
+    may be None), w fp32 OIHW, bias fp32.  Roundings mirrored -- VALU kernel: none (fp32 inputs and weights, the bias is the first
+    term of the fp32 sum); MFMA kernel: inputs and weights rounded to T (exact functions of the fp32 values, so no flip slack), fp32
+    accumulation -> float64, T(acc + bias).  One ulp of T of slack for the store."""
+    x = torch.cat([x0] + ([x1] if x1 is not None else []), 1).double().permute(0, 2, 3, 1)
+    W = oihw_taps(w)
+    if mfma:
+        x, W = _r64(x, dtype), _r64(W, dtype)
+    ref, ab = conv_from_padded(pad_zero(x), W, 1)
+    ref, ab = ref + bias.double(), ab + bias.double().abs()
+    return ref, ab, _ulp(ref, dtype)
+
+
+# ------------------------------------------------------------------------------------------------ llie_final_conv (conv.hip)
+def silu_operand(dtype, x, sc, sh, rounded):
+    """The output head's activated operand [B][H][W][C]: z = fma(x, sc, sh) in fp32 (one rounding), a = z / (1 + exp(-z)).  The
+    kernels evaluate it with __expf (v_exp_f32 on z log2(e): relative error (1.5 |z| + 2) 2^-24) and an IEEE division (VALU kernel) or
+    v_rcp_f32 and a product (MFMA kernel), 2 x 2^-24 more: err = |a| (1.5 |z| + 4) 2^-24.  rounded (the MFMA kernel): a is rounded to
+    T and err enters through _flip_slack; else a stays fp32 and err is returned for the caller's absolute sum.
+    -> (a, slack or None, err)"""
+    z = _f32(x.double() * sc.double()[:, None, None, :] + sh.double()[:, None, None, :])
+    a = z * torch.sigmoid(z)
+    err = a.abs() * (1.5 * z.abs() + 4.0) * U
+    if rounded:
+        return _r64(a, dtype), _flip_slack(a, dtype, err), err
+    return a, None, err
+
+
+def final_conv_ref(dtype, x, sc, sh, w, bias, mfma):
+    """llie_final_conv without the fused step: eps fp32 NCHW [B][Cout][H][W] = conv3x3(silu(x sc + sh), w) + bias, zero padding
+    outside the image (after the activation).  x NHWC [B][H][W][C] of T, sc / sh fp32 [B][C], w fp32 OIHW (Cout <= 4), bias fp32.
+    Roundings mirrored -- VALU kernel: the operand and the weights stay fp32 (the operand's evaluation error joins the absolute sum,
+    in units of 2^-24); MFMA kernel: operand and weights rounded to T (silu_operand's flip slack), fp32 accumulation -> float64.
+    The output is fp32: one fp32 ulp of slack."""
+    a, asl, err = silu_operand(dtype, x, sc, sh, mfma)
+    W = oihw_taps(w)
+    if mfma:
+        W = _r64(W, dtype)
+    ref, ab = conv_from_padded(pad_zero(a), W, 1)
+    if mfma:
+        sl, _ = conv_from_padded(pad_zero(asl), W.abs(), 1)
+    else:
+        extra, _ = conv_from_padded(pad_zero(err / U), W.abs(), 1)
+        ab, sl = ab + extra, torch.zeros_like(ref)
+    ref, ab = ref + bias.double(), ab + bias.double().abs()
+    nchw = lambda t: t.permute(0, 3, 1, 2).contiguous()  # noqa: E731
+    return nchw(ref), nchw(ab), nchw(sl + _ulp(ref, 0))
+
+
+def lcm_step_ref(eps, eps_ab, eps_sl, sample, noise, coef):
+    """The scheduler step of final_conv_mfma_kernel's epilogue, in the kernel's operation order (separate fp32 operations, no
+    contraction): x0 = sa x - sb e (v-prediction) or (x - sb e) / sa; clamped to [-1, 1] if clamp_x0; prev = x0 if is_last else sap
+    x0 + sbp n; clamped = clip(prev, -1, 1).  eps / eps_ab / eps_sl: final_conv_ref's triple; coef = (sa, sb, sap, sbp, is_last,
+    vpred, clamp_x0) with fp32 coefficient values.  The absolute sums carry the conv's through sb (/ sa) and sap; clamping is
+    1-Lipschitz and changes neither sum nor slack.  -> {"x0" | "prev" | "clamped": (ref, abssum, slack)}"""
+    sa, sb, sap, sbp = (float(torch.tensor(c, dtype=torch.float32)) for c in coef[:4])
+    is_last, vpred, clamp_x0 = coef[4:]
+    x, e = sample.double(), eps
+    if vpred:
+        x0, ab, sl = sa * x - sb * e, (sa * x).abs() + sb * eps_ab, sb * eps_sl
+    else:
+        x0, ab, sl = (x - sb * e) / sa, (x.abs() + sb * eps_ab) / sa, sb * eps_sl / sa
+    if clamp_x0:
+        x0 = x0.clamp(-1.0, 1.0)
+    prev, pab, psl = x0, ab, sl
+    if not is_last:
+        prev, pab, psl = sap * x0 + sbp * noise.double(), sap * ab + (sbp * noise.double()).abs(), sap * sl
+    return {"x0": (x0, ab, sl + _ulp(x0, 0)), "prev": (prev, pab, psl + _ulp(prev, 0)),
+            "clamped": (prev.clamp(-1.0, 1.0), pab, psl + _ulp(prev, 0))}
+
+
+# ------------------------------------------------------------------------------------------------ llie_se_gate (small.hip)
+SE_FIX = 2.0 ** 24      # kPoolFixScale: the depthwise kernels' channel totals are fixed point, x 2^24
+SE_PRE = 2.0 ** 32      # kSePreScale: fc1 pre-activations of the MFMA pair
+
+
+def se_totals_ref(dtype, totals, P, w1, b1, w2, b2, path, hidden=None, pre=None):
+    """llie_se_gate: the SE gate from int64 fixed-point channel totals [B][C].  w1 [Cs][C], w2 [C][Cs] of T, biases fp32.
+    Paths 0 (se_gate_kernel) and 1 (se_fc1_kernel + se_fc2_kernel): mean = float(double(total) * (1.0 / (P 2^24))) exactly as the
+    kernels form it, hidden = relu6(W1 mean + b1) and the gate in fp32 with nothing rounded to T.
+    Path 2 (se_fc1_mfma_kernel + se_fc2_mfma_kernel): mean = T(float(total) * float(1.f / (float(P) 2^24))), mirrored bit for bit;
+    every 64-channel slice of K (one wave) adds its fp32 partial product, rounded to a multiple of 2^-32, into `pre`; hidden =
+    T(relu6(float(pre) 2^-32 + b1)); fc2 on the MFMA with fp32 accumulation.
+    A later stage can be fed the kernel's own `hidden` (path 1) or `pre` (path 2: int64, from which the hidden operand follows
+    exactly) so that each stage is judged alone; without them the first stage's error is carried into the gate: its absolute sum
+    joins the gate's (paths 0, 1) or widens the flip slack of the rounded hidden (path 2: 8 x 2^-24 of fc1's absolute sum -- at
+    most four accumulation roundings per slice, the int64 -> float conversion, the sum with b1 -- plus the fixed-point steps).
+    -> (mean, (stage, abs, slack), (gate, abs, slack)); stage = hidden (paths 0, 1) or pre x 2^-32 before ReLU6 and bias (path 2)."""
+    W1, W2, B1, B2 = w1.double(), w2.double(), b1.double(), b2.double()
+    if path != 2:
+        m = (totals.double() * (1.0 / (float(P) * SE_FIX))).float().double()
+        h, ha = (m @ W1.t() + B1).clamp(0.0, 6.0), m.abs() @ W1.abs().t() + B1.abs()
+        hh = h if hidden is None else hidden.double()
+        v, va = hh @ W2.t() + B2, hh.abs() @ W2.abs().t() + B2.abs()
+        if hidden is None:
+            va = va + ha @ W2.abs().t()
+        g = torch.sigmoid(v)
+        return m, (h, ha, _ulp(h, 0)), (g, g * (1 - g) * va + g, _ulp(g, 0))
+    inv = torch.tensor(1.0, dtype=torch.float32) / (torch.tensor(float(P), dtype=torch.float32) * torch.tensor(SE_FIX, dtype=torch.float32))
+    m = (totals.float() * inv).to(TDT[dtype]).double()
+    ns = m.shape[1] // 64
+    parts = torch.einsum("bsk,jsk->sbj", m.view(m.shape[0], ns, 64), W1.view(W1.shape[0], ns, 64))
+    p = (torch.round(parts * SE_PRE) / SE_PRE).sum(0)
+    pa = m.abs() @ W1.abs().t()
+    psl = torch.full_like(p, ns / SE_PRE)
+    if pre is not None:
+        hT, hsl = ((pre.double() / SE_PRE).float() + b1.float()).clamp(0.0, 6.0).to(TDT[dtype]).double(), torch.zeros_like(p)
+    else:
+        hf = (p + B1).clamp(0.0, 6.0)
+        hT, hsl = _r64(hf, dtype), _flip_slack(hf, dtype, 8.0 * U * (pa + B1.abs()) + psl)
+    v, va = hT @ W2.t() + B2, hT.abs() @ W2.abs().t() + B2.abs()
+    g = torch.sigmoid(v)
+    return m, (p, pa, psl), (g, g * (1 - g) * va + g, g * (1 - g) * (hsl @ W2.abs().t()) + _ulp(g, 0))
+
+
+# ------------------------------------------------------------------------------------------------ llie_affine_add (small.hip)
+def affine_add_ref(dtype, x, sc, sh, res=None):
+    """llie_affine_add: y[b][p][c] = fma(x, sc[b][c], sh[b][c]) in fp32 (one rounding, mirrored), + res in fp32 (-> exact), stored
+    in T.  x / res [B][P][C] of T, sc / sh fp32 [B][C].  tile_stats_ref(stored, 64) is its slab."""
+    p, q = x.double() * sc.double()[:, None, :], sh.double()[:, None, :]
+    ref, ab = _f32(p + q), p.abs() + q.abs()
+    if res is not None:
+        ref, ab = ref + res.double(), ab + res.double().abs()
+    return ref, ab, _ulp(ref, dtype)
+
+
+# ------------------------------------------------------------------------------------------------ llie_pw_gemm_dot (gemm.hip)
+def gemm_dot_stats_ref(stored, dot, rows):
+    """The slab of pw_gemm's `dot` epilogue: [B][ceil(P / rows)][2][N] = (sum stored * dot, sum stored) over each tile of `rows`
+    pixel rows, absent rows counting for nothing; stored / dot [B][P][N] of T (products rounded to fp32 once, which the bar
+    covers).  -> (ref, abssum, slack)."""
+    q, d = stored.double(), dot.double()
+    B, P, N = q.shape
+    nt = (P + rows - 1) // rows
+    pad = lambda t: torch.cat([t, torch.zeros(B, nt * rows - P, N, dtype=torch.float64)], 1).view(B, nt, rows, N)  # noqa: E731
+    qp, dp = pad(q), pad(d)
+    ref = torch.stack([(qp * dp).sum(2), qp.sum(2)], 2)
+    ab = torch.stack([(qp * dp).abs().sum(2), qp.abs().sum(2)], 2)
+    return ref, ab, _ulp(ref, 0)
+
+
 # ------------------------------------------------------------------------------------------------ bars
 # BAR x 2^-24 x abssum per entry.  "worst" = the worst ratio |out - ref| / (2^-24 abssum) measured on the MI355X over all cases of
 # the kernel in tests/test_gpu_forward_kernels.py and seeds 0, 1, 2 (LLIE_FWD_TEST_SEED), as fp32 / fp16 / bf16; the bar is about
@@ -350,3 +544,16 @@ BAR_ATTN = 20.0        # worst 2.04 / 0.00 / 0.06
 BAR_ATTN_KV = 160.0    # worst 15.83 / 10.75 / 10.31 (spans of 256 and 384 positions summed one after the other; 2.6 at N = 25)
 BAR_GN = 30.0          # worst, scale 2.16, shift 3.00 (fp32 tables only)
 BAR_SE = 20.0          # worst, mean 0.00, hidden 0.62, gate 1.96 (the same for every weight type)
+# the head, tail and boundary kernels: worst over all cases of tests/test_gpu_boundary_kernels.py and seeds 0, 1, 2, as fp32 / fp16 / bf16
+BAR_INIT = 49.0           # worst 4.81 / 0.64 / 0.67 (all VALU kernel; MFMA kernel 0.42 fp16, 0.27 bf16)
+BAR_INIT_STATS = 26.0     # worst 1.29 / 2.54 / 1.93
+BAR_FINAL = 26.0          # worst 0.75 / 2.59 / 2.15 (2-byte: the MFMA kernel, 2.59 with the fused step, 1.98 / 2.15 without; VALU kernel 0.77 / 0.82)
+BAR_STEP = 23.0           # worst, prev 2.25 / 1.52, clamped 1.61 / 1.49 (fp16 / bf16: the step exists in the MFMA kernel alone)
+BAR_SE_GATE = 17.0        # worst, path 0 gate 0.64 / 0.66 / 0.56; path 1 hidden 0.31, gate 1.36; path 2 pre 0.29, gate 1.63 / 1.32
+BAR_AFFINE = 2.0          # worst 0.00 / 0.00 / 0.00: always inside the ulp of the stored value.  Not measured but reasoned: after the
+                          # mirrored fma the kernel rounds twice more in fp32 at most (the residual add; the shift, were the fma not
+                          # contracted), each by at most 2^-24 of the absolute sum
+BAR_AFFINE_STATS = 22.0   # worst 1.73 / 2.15 / 1.17
+BAR_CONVERT_STATS = 78.0  # worst 5.76 / 7.77 / 4.78, all at P = 192: nchw_to_nhwc_kernel adds a tile's 64 pixels one after the other in one
+                          # thread, where the other producers add 16 per lane and then combine lanes and waves as a tree
+BAR_GEMM_DOT = 9.0        # worst 0.84 / 0.57 / 0.37 (the output itself, under BAR_GEMM: 4.25 / 0.15 / 0.05)

@@ -3,7 +3,8 @@
 (a) On the fp32 path (nothing rounded to a 2-byte type) each reference agrees with torch's own float64 operator.
 (b) The bars have teeth: for every kernel, subtly wrong variants of the reference -- what a kernel with a mis-indexed per-image
     table, a dropped border tap, a partial tile counted in the statistics, ... would store -- are compared with the correct
-    reference through the very function, bars and slack of tests/test_gpu_forward_kernels.py, in every dtype.  Each must fail, and
+    reference through the very function, bars and slack of tests/test_gpu_forward_kernels.py and tests/test_gpu_boundary_kernels.py,
+    in every dtype.  Each must fail, and
     the correct values rounded to the storage type must pass.  A bar that lets one of these through is too loose, whatever was
     measured on the GPU.
 """
@@ -136,6 +137,110 @@ def test_se_mlp_ref_vs_torch():
     th = F.relu6(F.linear(tm, w1.double(), b1.double()))
     tg = torch.sigmoid(F.linear(th, w2.double(), b2.double()))
     assert torch.allclose(m, tm, rtol=1e-14) and torch.allclose(h, th, rtol=1e-12, atol=1e-13) and torch.allclose(gt, tg, rtol=1e-12)
+
+
+def _init_setup(dtype, H=24, W=40, split=(3, 3), cout=64, seed=700):
+    g = _g(seed + dtype)
+    B = 2
+    x0, x1 = torch.randn(B, split[0], H, W, generator=g), torch.randn(B, split[1], H, W, generator=g)
+    w = torch.randn(cout, sum(split), 3, 3, generator=g) / math.sqrt(9 * sum(split))
+    return x0, x1, w, torch.randn(cout, generator=g) * 0.3
+
+
+def test_init_conv_ref_vs_conv2d():
+    x0, x1, w, bias = _init_setup(0, split=(1, 2))
+    ref, ab, _ = R.init_conv_ref(0, x0, x1, w, bias, False)
+    t = F.conv2d(torch.cat([x0, x1], 1).double(), w.double(), bias.double(), padding=1).permute(0, 2, 3, 1)
+    _ratio(t, ref, ab, None, 1e-3, "init_conv_ref vs conv2d")  # both float64 from the same fp32 values
+    q = ref.float().double()
+    s8, _, _ = R.conv_tile_stats_ref(ref.float(), 32, 8)  # 24 x 40: 3 x 2 tiles of 8 x 32, the second column 8 pixels wide
+    s16, _, _ = R.conv_tile_stats_ref(ref.float(), 16, 16)  # 2 x 3 tiles of 16 x 16, the second row 8 pixels high
+    assert s8.shape[1] == 6 and s16.shape[1] == 6
+    assert torch.allclose(s8[:, 3, 0], q[:, 8:16, 32:].sum((1, 2)), rtol=0, atol=1e-12)
+    assert torch.allclose(s16[:, 5, 1], (q[:, 16:, 32:] ** 2).sum((1, 2)), rtol=1e-13)
+
+
+def _final_setup(dtype, H=24, W=40, C=64, cout=3, seed=800):
+    g = _g(seed + dtype)
+    B = 2
+    x = _rt(torch.randn(B, H, W, C, generator=g) * 1.5, dtype)
+    sc, sh = torch.rand(B, C, generator=g) + 0.5, torch.randn(B, C, generator=g) * 0.7
+    w = torch.randn(cout, C, 3, 3, generator=g) / math.sqrt(9 * C)
+    return g, x, sc, sh, w, torch.randn(cout, generator=g) * 0.3
+
+
+def test_final_conv_ref_vs_silu_conv2d():
+    _, x, sc, sh, w, bias = _final_setup(0, cout=4)
+    ref, ab, _ = R.final_conv_ref(0, x, sc, sh, w, bias, False)
+    z = x.double() * sc.double()[:, None, None] + sh.double()[:, None, None]
+    t = F.conv2d(F.silu(z).permute(0, 3, 1, 2), w.double(), bias.double(), padding=1)
+    _ratio(t, ref, ab, None, 2.0, "final_conv_ref vs silu + conv2d")  # the reference rounds z to fp32 once
+
+
+@pytest.mark.parametrize("k", range(8))
+def test_lcm_step_ref_vs_written_out_scheduler(k):
+    """LCMScheduler.step written out from alpha-bar: epsilon and v-prediction, with and without the deployment loop's clamp, last step"""
+    g = _g(20 + k)
+    vpred, clamp, last = k & 1, (k >> 1) & 1, k >> 2
+    e, x, n = (torch.randn(2, 3, 8, 8, generator=g, dtype=torch.float64) for _ in range(3))
+    at, ap = 0.28125, 0.71875  # alpha-bar of t and of the previous timestep; their roots are the coefficients
+    coef = (math.sqrt(at), math.sqrt(1 - at), math.sqrt(ap), math.sqrt(1 - ap), last, vpred, clamp)
+    c32 = tuple(float(torch.tensor(c, dtype=torch.float32)) for c in coef[:4])
+    out = R.lcm_step_ref(e, e.abs(), torch.zeros_like(e), x, n, coef)
+    x0 = c32[0] * x - c32[1] * e if vpred else (x - c32[1] * e) / c32[0]
+    if clamp:
+        x0 = x0.clamp(-1, 1)
+    prev = x0 if last else c32[2] * x0 + c32[3] * n
+    assert torch.allclose(out["x0"][0], x0, rtol=1e-14, atol=1e-15) and torch.allclose(out["prev"][0], prev, rtol=1e-14, atol=1e-15)
+    assert torch.equal(out["clamped"][0], out["prev"][0].clamp(-1, 1))
+    assert (out["prev"][1] >= out["prev"][0].abs() - 1e-12).all()  # an absolute sum bounds its sum
+
+
+def _se_tot_setup(dtype, B=3, C=512, Cs=64, seed=900):
+    g = _g(seed + dtype)
+    P = 324
+    tot = torch.round(torch.randn(B, C, generator=g, dtype=torch.float64) * P * 0.5 * R.SE_FIX).to(torch.int64)
+    w1, w2 = _rt(torch.randn(Cs, C, generator=g) / math.sqrt(C), dtype), _rt(torch.randn(C, Cs, generator=g) / math.sqrt(Cs), dtype)
+    return tot, P, w1, torch.randn(Cs, generator=g) * 2.5 + 2.5, w2, torch.randn(C, generator=g) * 0.5
+
+
+def test_se_totals_ref_vs_linear_sigmoid():
+    tot, P, w1, b1, w2, b2 = _se_tot_setup(0)
+    m, (h, _, _), (gt, _, _) = R.se_totals_ref(0, tot, P, w1, b1, w2, b2, 0)
+    tm = tot.double() / (P * 2.0 ** 24)
+    th = F.relu6(F.linear(tm, w1.double(), b1.double()))
+    tg = torch.sigmoid(F.linear(th, w2.double(), b2.double()))
+    assert torch.allclose(m, tm, rtol=2.0 ** -23) and torch.allclose(h, th, atol=1e-5) and torch.allclose(gt, tg, atol=1e-5)
+    # the MFMA pair rounds mean and hidden to T: the same network within those roundings
+    tot, P, w1, b1, w2, b2 = _se_tot_setup(1)
+    m, (p, pa, psl), (gt, _, _) = R.se_totals_ref(1, tot, P, w1, b1, w2, b2, 2)
+    tm = tot.double() / (P * 2.0 ** 24)
+    assert torch.allclose(m, tm, rtol=2.0 ** -10)
+    assert ((p - F.linear(m, w1.double())).abs() <= psl).all()
+    tg = torch.sigmoid(F.linear(F.relu6(F.linear(tm, w1.double(), b1.double())), w2.double(), b2.double()))
+    assert (gt - tg).abs().max() < 2e-2
+    # the kernel's own pre (here: the reference's, as the int64 the kernel leaves) reproduces the hidden operand exactly
+    pre = torch.round(p * R.SE_PRE).to(torch.int64)
+    _, _, (g2, _, gs2) = R.se_totals_ref(1, tot, P, w1, b1, w2, b2, 2, pre=pre)
+    assert ((g2 - gt).abs() <= R.se_totals_ref(1, tot, P, w1, b1, w2, b2, 2)[2][2]).all() and (gs2 < 1e-6).all()
+
+
+def test_affine_add_dot_and_converter_refs_vs_torch():
+    g = _g(31)
+    B, P, C = 2, 100, 96
+    x, res = torch.randn(B, P, C, generator=g), torch.randn(B, P, C, generator=g)
+    sc, sh = torch.rand(B, C, generator=g) + 0.5, torch.randn(B, C, generator=g)
+    ref, ab, _ = R.affine_add_ref(0, x, sc, sh, res)
+    _ratio(x.double() * sc.double()[:, None] + sh.double()[:, None] + res.double(), ref, ab, None, 2.0, "affine_add_ref")
+    dref, _, _ = R.gemm_dot_stats_ref(x, res, 64)
+    assert dref.shape == (B, 2, 2, C)
+    assert torch.allclose(dref[:, 1, 0], torch.einsum("bpc,bpc->bc", x[:, 64:].double(), res[:, 64:].double()), rtol=1e-13, atol=1e-12)
+    assert torch.allclose(dref[:, 0, 1], x[:, :64].double().sum(1), rtol=0, atol=1e-12)
+    # the converters' values are round_T(x) under a permute; their slab is tile_stats_ref over 64 pixels
+    xn = torch.randn(B, 96, 128, generator=g)
+    y = _rt(xn[:, 32:96], 1).permute(0, 2, 1)
+    sref, _, _ = R.tile_stats_ref(y, 64)
+    assert torch.allclose(sref[:, 1, 0], xn[:, 32:96, 64:].half().double().sum(2), rtol=0, atol=1e-12)
 
 
 # ================================================================================================ (b) the bars have teeth
@@ -376,9 +481,157 @@ def test_se_mlp_bars_have_teeth(dtype):
                                               "hard sigmoid": (((h @ w2.double().t() + b2.double()) + 3) / 6).clamp(0, 1)})
 
 
+INIT_TEETH = [(0, 0), (1, 0), (1, 1), (2, 1)]
+
+
+@pytest.mark.parametrize("dtype,mfma", INIT_TEETH)
+def test_init_conv_bars_have_teeth(dtype, mfma):
+    x0, x1, w, bias = _init_setup(dtype)  # 24 x 40, 3 + 3 channels, Cout 64
+    ref, ab, sl = R.init_conv_ref(dtype, x0, x1, w, bias, mfma)
+    x = torch.cat([x0, x1], 1).double().permute(0, 2, 3, 1)
+    W = R.oihw_taps(w)
+    if mfma:
+        x, W = _r64(x, dtype), _r64(W, dtype)
+    one_tap = torch.zeros_like(W)
+    one_tap[3] = W[3]
+    th, tw = (8, 32) if mfma else (16, 16)
+    drop = ref.clone()  # a tap dropped on the last row of the edge tile (tile row 0, last tile column)
+    drop[:, th - 1, 40 - 40 % tw:] -= R.conv_from_padded(R.pad_zero(x), one_tap, 1)[0][:, th - 1, 40 - 40 % tw:]
+    w2 = w.clone()
+    w2[32:] = w[:32]
+    _teeth(dtype, ref, ab, sl, R.BAR_INIT, {
+        "the two input halves swapped": R.init_conv_ref(dtype, x1, x0, w, bias, mfma)[0],
+        "a tap dropped on the last row of an edge tile": drop,
+        "second-block weights taken from the first block": R.init_conv_ref(dtype, x0, x1, w2, bias, mfma)[0],
+        "H and W exchanged": R.init_conv_ref(dtype, x0.reshape(2, 3, 40, 24), x1.reshape(2, 3, 40, 24), w, bias, mfma)[0].reshape(ref.shape),
+    })
+    stored = _r64(ref, dtype)
+    sref, sab, ssl = R.conv_tile_stats_ref(stored, tw, th)
+    rep = F.pad(stored, (0, 0, 0, -40 % tw, 0, -24 % th), mode="replicate")
+    _teeth(dtype, sref, sab, ssl, R.BAR_INIT_STATS, {"absent pixels of a partial tile counted": R.conv_tile_stats_ref(rep, tw, th)[0],
+                                                      "tiles exchanged": sref.roll(1, 1)}, stored_in=0)
+    if mfma:  # 32 x 128: 16 tiles, written in xcd_tile_order
+        x0, x1, w, bias = _init_setup(dtype, 32, 128, cout=32)
+        sref, sab, ssl = R.conv_tile_stats_ref(_r64(R.init_conv_ref(dtype, x0, x1, w, bias, True)[0], dtype), 32, 8)
+        order = torch.tensor([(b & 7) * 2 + (b >> 3) for b in range(16)])
+        nb = sref.clone()
+        nb[:, [2, 3]] = sref[:, [3, 2]]
+        _teeth(dtype, sref, sab, ssl, R.BAR_INIT_STATS, {"slab indexed by workgroup, not by tile": sref[:, order],
+                                                          "the permuted tile's entry exchanged with its neighbour": nb}, stored_in=0)
+
+
+FINAL_TEETH = [(0, 0), (1, 0), (2, 0), (1, 1), (2, 1)]
+
+
+@pytest.mark.parametrize("dtype,mfma", FINAL_TEETH)
+def test_final_conv_bars_have_teeth(dtype, mfma):
+    _, x, sc, sh, w, bias = _final_setup(dtype)  # 24 x 40, C = 64 (two chunks), Cout = 3
+    ref, ab, sl = R.final_conv_ref(dtype, x, sc, sh, w, bias, mfma)
+    a, _, _ = R.silu_operand(dtype, x, sc, sh, mfma)
+    W = _r64(R.oihw_taps(w), dtype) if mfma else R.oihw_taps(w)
+    conv = lambda ap, ww=W: (R.conv_from_padded(ap, ww, 1)[0] + bias.double()).permute(0, 3, 1, 2)  # noqa: E731
+    rep = R.pad_zero(a)
+    rep[:, 1:-1, -1] = a[:, :, -1]
+    w_late = w.clone()
+    w_late[:, 32:] = w[:, :32]
+    w4 = torch.cat([w, w[:1].roll(1, 1)], 0)  # a non-zero fourth row, stored as a fourth plane: it lands on the next image's first
+    four = ref.clone()
+    four[1, 0] = R.final_conv_ref(dtype, x, sc, sh, w4, torch.cat([bias, bias[:1]]), mfma)[0][0, 3]
+    unr = {"operand not rounded to T": conv(R.pad_zero(R.silu_operand(dtype, x, sc, sh, False)[0]))} if mfma else {}
+    _teeth(dtype, ref, ab, sl, R.BAR_FINAL, {
+        "affine of the other image": R.final_conv_ref(dtype, x, sc.roll(1, 0), sh.roll(1, 0), w, bias, mfma)[0],
+        "replicate padding on the right edge": conv(rep),
+        "the second chunk's weights staged late (chunk 0 reused)": R.final_conv_ref(dtype, x, sc, sh, w_late, bias, mfma)[0],
+        "the padded fourth weight row non-zero and stored": four,
+        "H and W exchanged": R.final_conv_ref(dtype, x.reshape(2, 40, 24, 64), sc, sh, w, bias, mfma)[0].reshape(ref.shape),
+        "relu instead of silu": conv(R.pad_zero(F.relu(a))), **unr}, stored_in=0)
+
+
+@pytest.mark.parametrize("dtype", [1, 2])
+def test_lcm_step_bars_have_teeth(dtype):
+    g, x, sc, sh, w, bias = _final_setup(dtype)
+    e, eab, esl = R.final_conv_ref(dtype, x, sc, sh, w, bias, True)
+    sample, noise = torch.randn(e.shape, generator=g), torch.randn(e.shape, generator=g)
+    sa, sb, sap, sbp = (float(torch.tensor(c, dtype=torch.float32)) for c in (0.6, 0.8, 0.9, math.sqrt(1 - 0.81)))
+    for vpred in (0, 1):
+        base = R.lcm_step_ref(e, eab, esl, sample, noise, (sa, sb, sap, sbp, 0, vpred, 1))
+        x0_raw = R.lcm_step_ref(e, eab, esl, sample, noise, (sa, sb, sap, sbp, 0, vpred, 0))["x0"][0]
+        assert (x0_raw.abs() > 1).float().mean() > 0.1  # the clamp matters
+        _teeth(dtype, *base["prev"], R.BAR_STEP, {
+            "sa and sb exchanged": R.lcm_step_ref(e, eab, esl, sample, noise, (sb, sa, sap, sbp, 0, vpred, 1))["prev"][0],
+            "sap and sbp exchanged": R.lcm_step_ref(e, eab, esl, sample, noise, (sa, sb, sbp, sap, 0, vpred, 1))["prev"][0],
+            "clamp applied after the re-noise": (sap * x0_raw + sbp * noise.double()).clamp(-1, 1),
+            "the other prediction type": R.lcm_step_ref(e, eab, esl, sample, noise, (sa, sb, sap, sbp, 0, 1 - vpred, 1))["prev"][0],
+            "sample of the other image": R.lcm_step_ref(e, eab, esl, sample.roll(1, 0), noise, (sa, sb, sap, sbp, 0, vpred, 1))["prev"][0],
+        }, stored_in=0)
+        last = R.lcm_step_ref(e, eab, esl, sample, noise, (sa, sb, sap, sbp, 1, vpred, 0))
+        _teeth(dtype, *last["prev"], R.BAR_STEP, {"noise added when is_last": sap * last["x0"][0] + sbp * noise.double()}, stored_in=0)
+        _teeth(dtype, *last["clamped"], R.BAR_STEP, {"clamped = prev": last["prev"][0]}, stored_in=0)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_se_gate_bars_have_teeth(dtype):
+    tot, P, w1, b1, w2, b2 = _se_tot_setup(dtype)
+    W1, W2 = w1.double(), w2.double()
+    m, _, (gt, ga, gs) = R.se_totals_ref(dtype, tot, P, w1, b1, w2, b2, 0)
+    wrap = tot.clone()
+    wrap[2] = tot[0]
+    _teeth(0, gt, ga, gs, R.BAR_SE_GATE, {
+        "the mean taken over P + 1": R.se_totals_ref(dtype, tot, P + 1, w1, b1, w2, b2, 0)[2][0],
+        "hidden not clamped at 6": torch.sigmoid(F.relu(m @ W1.t() + b1.double()) @ W2.t() + b2.double()),
+        "totals read as unsigned": R.se_totals_ref(dtype, tot.abs(), P, w1, b1, w2, b2, 0)[2][0],
+        "image 2 reads image 0": R.se_totals_ref(dtype, wrap, P, w1, b1, w2, b2, 0)[2][0],
+        "the last hidden row dropped": torch.sigmoid(F.relu6(m @ W1.t() + b1.double())[:, :-1] @ W2[:, :-1].t() + b2.double())})
+    if dtype == 0:
+        return
+    m, (p, pa, psl), (gt, ga, gs) = R.se_totals_ref(dtype, tot, P, w1, b1, w2, b2, 2)
+    leak = p.clone()
+    leak[2] += 2.0 ** -6 * p[0]  # a masked row's partial product, a 64th of image 0's, added to the last live row
+    short = p - m[:, -64:] @ W1[:, -64:].t()
+    _teeth(0, p, pa, psl, R.BAR_SE_GATE, {"a masked batch row leaking into pre": leak, "the last K slice dropped": short,
+                                          "the mean taken over P + 1": R.se_totals_ref(dtype, tot, P + 1, w1, b1, w2, b2, 2)[1][0]})
+    pre = torch.round(p * R.SE_PRE).to(torch.int64)
+    _, _, (gt, ga, gs) = R.se_totals_ref(dtype, tot, P, w1, b1, w2, b2, 2, pre=pre)
+    hT = _r64((p + b1.double()).clamp_min(0.0), dtype)
+    pre_leak = torch.round(leak * R.SE_PRE).to(torch.int64)
+    _teeth(0, gt, ga, gs, R.BAR_SE_GATE, {"hidden not clamped at 6": torch.sigmoid(hT @ W2.t() + b2.double()),
+                                          "pre of a leaking row": R.se_totals_ref(dtype, tot, P, w1, b1, w2, b2, 2, pre=pre_leak)[2][0],
+                                          "hidden not rounded to T": torch.sigmoid((p + b1.double()).clamp(0, 6) @ W2.t() + b2.double())})
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_affine_add_and_dot_bars_have_teeth(dtype):
+    g = _g(1000 + dtype)
+    B, P, C = 2, 65, 96
+    x, res = _rt(torch.randn(B, P, C, generator=g) * 1.5, dtype), _rt(torch.randn(B, P, C, generator=g), dtype)
+    sc, sh = torch.rand(B, C, generator=g) + 0.5, torch.randn(B, C, generator=g) * 0.7
+    ref, ab, sl = R.affine_add_ref(dtype, x, sc, sh, res)
+    r1 = res.clone()
+    r1[1, 64] = 0
+    _teeth(dtype, ref, ab, sl, R.BAR_AFFINE, {
+        "residual of the neighbouring row": R.affine_add_ref(dtype, x, sc, sh, res.roll(1, 1))[0],
+        "affine table of the other image": R.affine_add_ref(dtype, x, sc.roll(1, 0), sh.roll(1, 0), res)[0],
+        "residual omitted on the one-row tile of the last image": R.affine_add_ref(dtype, x, sc, sh, r1)[0],
+        "shift of the neighbouring channel": R.affine_add_ref(dtype, x, sc, sh.roll(1, 1), res)[0]})
+    stored = _r64(ref, dtype)
+    sref, sab, ssl = R.tile_stats_ref(stored, 64)
+    four = sref.clone()
+    four[:, 1] *= 4  # every wave counts the tile's only row
+    _teeth(dtype, sref, sab, ssl, R.BAR_AFFINE_STATS, {"a one-row tile's statistics counted four times": four, "tiles exchanged": sref.roll(1, 1)},
+           stored_in=0)
+    _teeth(dtype, sref, sab, ssl, R.BAR_CONVERT_STATS, {"tiles exchanged": sref.roll(1, 1), "image b - 1's entry": sref.roll(1, 0)}, stored_in=0)
+    dref, dab, dsl = R.gemm_dot_stats_ref(stored, res, 64)
+    rows = dref.clone()
+    rows[:, 1] += torch.stack([stored[:, 63] * res[:, 63].double(), stored[:, 63]], 1)  # the row before the partial tile counted with it
+    _teeth(dtype, dref, dab, dsl, R.BAR_GEMM_DOT, {"slab halves exchanged": dref.flip(2), "sum of squares in the second half": sref.roll(1, 2),
+                                                    "dot of the neighbouring row": R.gemm_dot_stats_ref(stored, res.roll(1, 1), 64)[0],
+                                                    "an absent row counted": rows}, stored_in=0)
+
+
 # ================================================================================================ the ABI additions, without a device
 def test_new_entry_points_check_their_contract_before_any_hip_call():
-    """llie_dwconv3x3_ex and llie_pw_gemm's segment checks return LLIE_ERR_ARG on the host (dummy pointers, never read);
+    """llie_dwconv3x3_ex, llie_pw_gemm's segment checks and the head, tail and boundary entries (llie_init_conv, llie_final_conv,
+    llie_se_gate, llie_affine_add, the converters, llie_pw_gemm_dot) return LLIE_ERR_ARG on the host (dummy pointers, never read);
     llie_dwconv3x3_strip_rows restates nothing here: it is dw_pick_tyl; llie_last_kernel returns a C string."""
     import ctypes as C
     import importlib
@@ -407,3 +660,42 @@ def test_new_entry_points_check_their_contract_before_any_hip_call():
     assert L.llie_conv3x3_tiles(9, 16) == 4 and L.llie_conv3x3_tiles(16, 16) == 2 and L.llie_conv3x3_tiles(9, 13) == 4
     assert L.llie_dwconv3x3_tiles(13, 24) == 4 and L.llie_dwconv3x3_tiles(16, 24) == 6 and L.llie_dwconv3x3_tiles(13, 9) == 2
     assert isinstance(L.llie_last_kernel(), bytes)
+    # the head, tail and boundary entries: one out-of-contract call per clause family (tests/test_gpu_boundary_kernels.py drives them all)
+    coef = native.StepCoef(0.8, 0.6, 0.9, 0.43, 0, 0, 0)
+    nbi, nbf = int(L.llie_init_conv_pack_bytes(6, 32)), int(L.llie_final_conv_pack_bytes(64))
+    assert nbi == 6 * 9 * 32 * 4 + 10 * 32 * 8 * 2 and nbf == 9 * 64 * 4 * 4 + 2 * 18 * 2 * 4 * 8 * 2
+    assert L.llie_init_conv_pack_bytes(9, 32) == E and L.llie_init_conv_pack_bytes(6, 40) == E and L.llie_final_conv_pack_bytes(48) == E
+    assert L.llie_init_conv_tiles(24, 40, 0) == 6 and L.llie_init_conv_tiles(24, 40, 1) == 6 and L.llie_init_conv_tiles(32, 128, 1) == 16
+    assert L.llie_init_conv_tiles(20, 40, 1) == E
+
+    def init(dtype=1, c0=3, x1=p, c1=3, H=16, W=16, co=32, mfma=1, pk=p, n=nbi):
+        return L.llie_init_conv(dtype, p, c0, x1, c1, p, p, p, None, 2, H, W, co, mfma, pk, n, None)
+    for kw in (dict(x1=None), dict(c1=0), dict(c0=5, c1=4), dict(H=12), dict(W=20), dict(co=48), dict(dtype=0), dict(mfma=2), dict(n=nbi - 16),
+               dict(pk=p + 4), dict(pk=None), dict(dtype=3)):
+        assert init(**kw) == E, kw
+
+    def final(dtype=1, y=p, H=16, W=16, Cc=64, co=3, mfma=1, cf=None, sample=None, noise=None, prev=None, clamped=None, pk=p, n=nbf):
+        return L.llie_final_conv(dtype, p, p, p, p, p, y, 2, H, W, Cc, co, mfma, C.byref(cf) if cf else None, sample, noise, prev, clamped, pk, n, None)
+    for kw in (dict(Cc=48), dict(co=5), dict(co=0), dict(H=12), dict(dtype=0), dict(n=nbf - 16), dict(pk=p + 8), dict(y=None), dict(prev=p),
+               dict(cf=coef, mfma=0, sample=p, noise=p, prev=p), dict(cf=coef, sample=p, prev=p), dict(cf=coef, noise=p, prev=p),
+               dict(cf=coef, sample=p, noise=p)):
+        assert final(**kw) == E, kw
+
+    def gate(dtype=1, Cc=512, Cs=64, path=0, hid=p, pre=p, P=64):
+        return L.llie_se_gate(dtype, p, P, p, p, p, p, p, 2, Cc, Cs, path, hid, pre, None)
+    for kw in (dict(P=0), dict(path=3), dict(Cc=192), dict(dtype=0, Cc=96), dict(Cc=12288), dict(path=1, hid=None), dict(path=1, Cc=4224),
+               dict(path=2, dtype=0), dict(path=2, pre=None), dict(path=2, Cc=384), dict(path=2, Cs=96), dict(path=2, Cs=576)):
+        assert gate(**kw) == E, kw
+    for rc in (L.llie_affine_add(1, p, p, p, None, p, None, 100, 32, 64, None), L.llie_affine_add(1, p, p, p, None, p, None, 128, 12, 64, None),
+               L.llie_affine_add(1, p, p, p, None, p, None, 128, 4096, 64, None), L.llie_affine_add(1, None, p, p, None, p, None, 128, 32, 64, None),
+               L.llie_nchw_to_nhwc(1, p, p, None, 2, 48, 64, 96, 0, None), L.llie_nchw_to_nhwc(1, p, p, None, 2, 32, 100, 96, 0, None),
+               L.llie_nchw_to_nhwc(1, p, p, None, 2, 32, 64, 96, 80, None), L.llie_nchw_to_nhwc(1, p, p, None, 2, 32, 64, 96, -32, None),
+               L.llie_nhwc_to_nchw(1, p, p, 2, 48, 64, 96, 0, None), L.llie_nhwc_to_nchw(1, p, p, 2, 32, 100, 96, 0, None),
+               L.llie_nhwc_to_nchw(1, p, p, 2, 64, 64, 96, 64, None), L.llie_nhwc_to_nchw(3, p, p, 2, 32, 64, 96, 0, None)):
+        assert rc == E
+
+    def dot(seg=(p, 64, p, p, 64, 0), d=p, st=p):
+        arr = (native.GemmSeg * 1)(native.GemmSeg(*seg))
+        return L.llie_pw_gemm_dot(1, arr, 1, p, None, d, p, st, 256, 64, 128, None)
+    for kw in (dict(d=None), dict(st=None), dict(seg=(p, 64, p, p, 64, 2)), dict(seg=(p, 64, None, p, 64, 0)), dict(seg=(p, 64, p, p, 32, 1))):
+        assert dot(**kw) == E, kw

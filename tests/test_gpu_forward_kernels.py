@@ -22,17 +22,14 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kernel_refs as R  # noqa: E402
-from kernel_refs import TDT, _ratio, _rt, _ulp  # noqa: E402
+from kernel_refs import NAN, TDT, Guarded, _ratio, _rt, _same, _slab, _split, _ulp  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 N = importlib.import_module("cv-diffusion-model_amd._native")
 
 SEED0 = int(os.environ.get("LLIE_FWD_TEST_SEED", "0"))
-CANARY = 12352.0  # exact in fp16 and bf16
-GUARD = 16        # canary elements on each side (keeps 16-byte alignment for every type)
 DTYPES = [0, 1, 2]
 TNAME = {0: "float", 1: "_Float16", 2: "__bf16"}
-NAN = float("nan")
 
 
 @pytest.fixture(scope="module")
@@ -51,43 +48,6 @@ def _gen(*key):
 
 def _last():
     return N.lib().llie_last_kernel().decode()
-
-
-class Guarded:
-    """A device buffer of `shape` between two rows of canaries, filled with `fill` (NaN: entries never written show up)."""
-
-    def __init__(self, shape, dev, dtype=torch.float32, fill=NAN):
-        n = int(math.prod(shape))
-        self.full = torch.full((n + 2 * GUARD,), CANARY, dtype=dtype, device=dev)
-        self.v = self.full[GUARD:GUARD + n].view(shape)
-        self.v.fill_(fill)
-
-    @property
-    def ptr(self):
-        return self.v.data_ptr()
-
-    def cpu(self, what=""):
-        f = self.full.cpu()
-        assert (f[:GUARD] == CANARY).all() and (f[-GUARD:] == CANARY).all(), f"{what}: wrote outside its buffer"
-        return f[GUARD:-GUARD].view(self.v.shape)
-
-
-def _bits(t):
-    return t.float().view(torch.int32) if t.dtype != torch.int64 else t
-
-
-def _same(a, b, what):
-    assert torch.equal(_bits(a), _bits(b)), f"{what}: two calls differ"
-
-
-def _slab(dev, B, nt, *inner):
-    """a [B][nt][inner] slab as the kernels index it, plus one extra guarded entry past the helper's count"""
-    return Guarded((B * nt + 1,) + inner, dev)
-
-
-def _split(s, B, nt, what):
-    assert torch.isnan(s[B * nt:]).all(), f"{what}: written past the helper's tile count"
-    return s[:B * nt].view(B, nt, *s.shape[1:])
 
 
 def _ptr(t):
