@@ -69,9 +69,14 @@ __device__ __forceinline__ typename Elem<T>::vec_t activate8(typename Elem<T>::v
 // the whole image minus one border row and / or column (plus the corner they share).  Nine sums of a = relu6(aff2(h1)) / 6
 // per channel -- everything, first / last row, first / last column, four corners -- replace h2: a is rounded to T where
 // expand_dw_kernel rounds the tile it parks in LDS, the weights are the 6 w in T it stages, so the two routes add the same numbers.
-// Two accumulator registers pack into one dword of T and one v_dot2 adds both to an fp32 sum; the column sums are v_dot2 with
-// a one-hot operand on the four registers that can hold a first / last column (W % 16 == 0: a 16-pixel group lies in one
-// image row, starts at a multiple of 16), the row sums a uniform branch that only the image's first and last row take.
+// Two accumulator registers pack into one dword of T and one v_dot2 adds both to an fp32 sum.  Every 16-pixel group adds its sum
+// to the total; W % 16 == 0, so a group lies in one image row and starts at a multiple of 16, and only a group of the first / last
+// image row or the first / last group of a row can touch a border class (one in eight at W = 256, one in four at W = 128).  Those
+// groups alone enter ONE wave-uniform branch that holds all border work: the one-hot operands (this lane's first- / last-column
+// pixel), the column sums (v_dot2 against them on the two registers that can hold such a pixel), the row sums and the four
+// corners.  Whether a group is an edge group follows from blockIdx and loop counters, i.e. from scalar registers.  Written as
+// plain `if`s hipcc turned all of it into selects that every group executed (88 VALU instructions per 32 x 32 block at <2, 1>,
+// 37 with the branch); the skipped instructions only ever added exact zeros, so the totals did not change by a bit.
 constexpr int kXStamps = 9;  // cycle-stamp slots of a diagnostic build (STAMP, below)
 template <typename T> struct PackedOne;
 template <> struct PackedOne<half_t> { static constexpr uint32_t lo = 0x00003C00u, hi = 0x3C000000u; };
@@ -113,11 +118,11 @@ __device__ __forceinline__ void expand_scan(const IrbxArgs& a, const int RP) {
 #pragma unroll
   for (int j = 0; j < NBW; ++j) s1[j] = s2[j] = 0.f;
   // POOL: aff2 of this lane's channels (applied to acc = h1 / 6: shift / 6, clamp01), the border sums, and the position of the
-  // next 16-pixel group: (image row, group inside the row)
+  // next 16-pixel group: (index inside the image, index inside its row)
   constexpr int NP = POOL ? NBW : 1;
   float sc2[NP], sh2[NP], c0s[NP], cws[NP], r0s[NP], rhs[NP], kk[NP][4];
-  const int w16 = a.W / 16;
-  int grow = 0, gcol = 0;
+  const int w16 = a.W / 16, gbot = (a.H - 1) * w16;  // groups per image row; first group of the last row
+  int gidx = 0, gcol = 0;
   if constexpr (POOL) {
 #pragma unroll
     for (int j = 0; j < NBW; ++j) {
@@ -126,8 +131,8 @@ __device__ __forceinline__ void expand_scan(const IrbxArgs& a, const int RP) {
       sh2[j] = a.ab2[(size_t)b * a.Chid + c] * kSixth;
       c0s[j] = cws[j] = r0s[j] = rhs[j] = kk[j][0] = kk[j][1] = kk[j][2] = kk[j][3] = 0.f;
     }
-    const int g0 = tile * (RP / 16);
-    grow = g0 / w16; gcol = g0 % w16;
+    gidx = tile * (RP / 16);
+    gcol = gidx % w16;
   }
 
   // cooperative load: vector v = tid + j*256 of a step -> pixel v / (2 KS), channel vector v % (2 KS)
@@ -175,16 +180,19 @@ __device__ __forceinline__ void expand_scan(const IrbxArgs& a, const int RP) {
       vec_t af[KS];
 #pragma unroll
       for (int s = 0; s < KS; ++s) af[s] = *reinterpret_cast<const vec_t*>(buf + (pb * 32 + n) * XP + (16 * s + 8 * h) * 2);
-      // POOL: the block's two 16-pixel groups (accumulator registers 0..7 and 8..15): which border classes they touch
-      uint32_t mc0[2] = {0u, 0u}, mcw[2] = {0u, 0u};  // one-hot operands: this lane's first-column / last-column pixel of the group
-      bool top[2] = {false, false}, bot[2] = {false, false};
+      // POOL: the block's two 16-pixel groups (accumulator registers 0..7 and 8..15): which border classes they touch.  All of it
+      // follows from blockIdx and the loop counters, so it stays in scalar registers; nothing per lane is built out here
+      bool left[2] = {false, false}, right[2] = {false, false}, top[2] = {false, false}, bot[2] = {false, false};
+      bool edge[2] = {false, false};
       if constexpr (POOL) {
 #pragma unroll
         for (int gi = 0; gi < 2; ++gi) {
-          mc0[gi] = (gcol == 0 && h == 0) ? PackedOne<T>::lo : 0u;        // pixel offset 0 of the group: register 8 gi, lower half
-          mcw[gi] = (gcol == w16 - 1 && h == 1) ? PackedOne<T>::hi : 0u;  // pixel offset 15: register 8 gi + 7, upper half
-          top[gi] = grow == 0; bot[gi] = grow == a.H - 1;
-          if (++gcol == w16) { gcol = 0; ++grow; }
+          left[gi] = gcol == 0; right[gi] = gcol == w16 - 1;
+          top[gi] = gidx < w16; bot[gi] = gidx >= gbot;
+          edge[gi] = left[gi] || right[gi] || top[gi] || bot[gi];
+          // no row counter: `row += wrapped` compiles to a VALU select and a v_readfirstlane in the middle of the epilogue
+          ++gidx;
+          gcol = gcol + 1 == w16 ? 0 : gcol + 1;
         }
       }
 #pragma unroll
@@ -209,17 +217,26 @@ __device__ __forceinline__ void expand_scan(const IrbxArgs& a, const int RP) {
             gs[gi] = dot2_pk<T>(pk[4 * gi], ones, 0.f);
 #pragma unroll
             for (int i = 1; i < 4; ++i) gs[gi] = dot2_pk<T>(pk[4 * gi + i], ones, gs[gi]);
-            c0s[j] = dot2_pk<T>(pk[4 * gi], mc0[gi], c0s[j]);
-            cws[j] = dot2_pk<T>(pk[4 * gi + 3], mcw[gi], cws[j]);
-            if (top[gi]) {
-              r0s[j] += gs[gi];
-              kk[j][0] = dot2_pk<T>(pk[4 * gi], mc0[gi], kk[j][0]);
-              kk[j][1] = dot2_pk<T>(pk[4 * gi + 3], mcw[gi], kk[j][1]);
-            }
-            if (bot[gi]) {
-              rhs[j] += gs[gi];
-              kk[j][2] = dot2_pk<T>(pk[4 * gi], mc0[gi], kk[j][2]);
-              kk[j][3] = dot2_pk<T>(pk[4 * gi + 3], mcw[gi], kk[j][3]);
+            if (edge[gi]) {
+              // Wave-uniform, and taken by one group in eight at W = 256.  The empty asm keeps it a branch: without it hipcc
+              // if-converts these few accumulating instructions into selects that every group of every block then executes.
+              asm volatile("" ::: "memory");
+              // one-hot operands: this lane's first-column pixel of the group (offset 0: register 8 gi, lower half) and its
+              // last-column pixel (offset 15: register 8 gi + 7, upper half)
+              const uint32_t mc0 = (left[gi] && h == 0) ? PackedOne<T>::lo : 0u;
+              const uint32_t mcw = (right[gi] && h == 1) ? PackedOne<T>::hi : 0u;
+              c0s[j] = dot2_pk<T>(pk[4 * gi], mc0, c0s[j]);
+              cws[j] = dot2_pk<T>(pk[4 * gi + 3], mcw, cws[j]);
+              if (top[gi]) {
+                r0s[j] += gs[gi];
+                kk[j][0] = dot2_pk<T>(pk[4 * gi], mc0, kk[j][0]);
+                kk[j][1] = dot2_pk<T>(pk[4 * gi + 3], mcw, kk[j][1]);
+              }
+              if (bot[gi]) {
+                rhs[j] += gs[gi];
+                kk[j][2] = dot2_pk<T>(pk[4 * gi], mc0, kk[j][2]);
+                kk[j][3] = dot2_pk<T>(pk[4 * gi + 3], mcw, kk[j][3]);
+              }
             }
           }
           s1[j] += gs[0] + gs[1];
