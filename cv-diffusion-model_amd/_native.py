@@ -33,6 +33,8 @@ EXPORTS = [
     "llie_groupnorm_backward", "llie_groupnorm_backward_scratch_floats", "llie_linattn_backward", "llie_linattn_dkv_floats",
     "llie_upsample2x_backward", "llie_dilate2x", "llie_linear_dx", "llie_linear_dx_scratch_floats", "llie_linear_dw",
     "llie_final_bwd_data",
+    "llie_dwconv3x3_backward", "llie_groupnorm_backward_from_slab", "llie_bias_grad", "llie_bias_grad_floats", "llie_pack_planes",
+    "llie_add_into", "llie_sin_embed", "llie_pointwise_backward",
     "llie_tile_count", "llie_tile_origins", "llie_tile_gather_u8", "llie_tile_gather_f32", "llie_tile_blend_u8",
     "llie_aug_pair_u8", "llie_aug_synth_u8",
     "llie_image_metrics_scratch_bytes", "llie_image_metrics_f32", "llie_image_metrics_u8", "llie_comparison_grid_u8",
@@ -44,6 +46,7 @@ EXPORTS = [
     "llie_se_gate", "llie_affine_add", "llie_nchw_to_nhwc", "llie_nhwc_to_nchw", "llie_pw_gemm_dot",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
+PW_SIGMOID_BWD, PW_RELU6_BWD, PW_SILU_BWD, PW_SCALE = 0, 1, 2, 3  # llie_pointwise_kind
 
 
 class GemmSeg(C.Structure):
@@ -260,6 +263,14 @@ def lib() -> C.CDLL:
     L.llie_linear_dx_scratch_floats.restype = i64
     L.llie_linear_dw.argtypes = [vp, i64, vp, vp, vp, ci, ci, ci, vp]
     L.llie_final_bwd_data.argtypes = [ci, vp, vp, vp, ci, ci, ci, ci, ci, vp]
+    L.llie_dwconv3x3_backward.argtypes = [ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
+    L.llie_groupnorm_backward_from_slab.argtypes = [ci, C.POINTER(GnBackwardArgs), vp, ci, vp, i64, vp]
+    L.llie_bias_grad_floats.argtypes = [ci, ci, ci, C.POINTER(i64), C.POINTER(i64)]
+    L.llie_bias_grad.argtypes = [ci, vp, ci, ci, ci, ci, vp, vp, vp, vp]
+    L.llie_pack_planes.argtypes = [ci, vp, ci, vp, ci, vp, ci, ci, vp]
+    L.llie_add_into.argtypes = [ci, vp, vp, i64, vp]
+    L.llie_sin_embed.argtypes = [vp, vp, vp, ci, ci, vp]
+    L.llie_pointwise_backward.argtypes = [ci, vp, vp, vp, i64, C.c_float, vp]
     L.llie_profile_report.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.llie_profile_dump.argtypes = [vp, C.c_char_p, C.c_size_t]
     L.llie_profile_begin.argtypes = [vp, ci]

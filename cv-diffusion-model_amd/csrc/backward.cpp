@@ -96,14 +96,10 @@ struct Back : Exec {
   }
 
   // bias gradient: out[0..Cstore) = column sums of g [M][C] (P pixels per image) through the caller's scratch slab
-  // [B][nt][2][C] and S [B][C], on stream `st`
-  void bias_grad(size_t g, int M, int C, int P, int nt, size_t slab, size_t S, float* out, int Cstore, hipStream_t st) {
+  // [B][bias_grad_tiles(P)][2][C] and S [B][C], on stream `st`
+  void bias_grad(size_t g, int M, int C, int P, size_t slab, size_t S, float* out, int Cstore, hipStream_t st) {
     if (dry) return;
-    BwdMaskArgs m{};
-    m.g = p(g); m.act = ACT_NONE; m.slab = p<float>(slab); m.M = M; m.C = C; m.P = P;
-    chk(launch_bwd_mask_reduce(dt, m, st));
-    chk(launch_slab_reduce(p<float>(slab), p<float>(S), B, nt, 2, 1, C, st));
-    chk(launch_batch_sum(p<float>(S), out, B, C, Cstore, st));
+    chk(launch_bias_grad(dt, p(g), M, C, P, Cstore, p<float>(slab), p<float>(S), out, st));
   }
 
   // activation backward + GroupNorm backward (coefficients, norm parameter gradients, input gradient) at one norm site, on
@@ -304,9 +300,9 @@ struct Back : Exec {
     const int C = w.c, Ho = r.y.H, Wo = r.y.W, Mo = B * Ho * Wo;
     const size_t dY = take_grad(r.y);
     {  // bias gradient: column sums of dY
-      const int nt = (Ho * Wo + 63) / 64;
+      const int nt = bias_grad_tiles(Ho * Wo);
       const size_t slab = alloc((size_t)B * nt * 2 * C * 4), S = alloc((size_t)B * C * 4);
-      bias_grad(dY, Mo, C, Ho * Wo, nt, slab, S, gp(w.i_bias), C, s);
+      bias_grad(dY, Mo, C, Ho * Wo, slab, S, gp(w.i_bias), C, s);
       ar->free(slab); ar->free(S);
     }
     const Tens& src = r.up ? r.u : r.x;  // what the conv itself read
@@ -374,7 +370,7 @@ struct Back : Exec {
       // operand (3 real rows), silu(norm(h)) recomputed in the prologue the other; bias = plane sums of d(eps).
       // It only needs d(eps) and forward tensors: side stream, joined with the first operator.
       const size_t g32 = alloc((size_t)M * 32 * es());
-      const int nt = P / 64;
+      const int nt = bias_grad_tiles(P);
       const size_t bslab = alloc((size_t)B * nt * 2 * 32 * 4), bS = alloc((size_t)B * 32 * 4);
       if (!dry) {
         FinalBwdArgs a{};
@@ -383,7 +379,7 @@ struct Back : Exec {
         chk(launch_final_bwd_data(dt, a, s));
         fork();
         chk(launch_pack_planes(dt, deps, nullptr, g.out_channels, 0, p(g32), B, P, side()));
-        bias_grad(g32, M, 32, P, nt, bslab, bS, gp(c->i_fin_bias), g.out_channels, side());  // of the packed d(eps)
+        bias_grad(g32, M, 32, P, bslab, bS, gp(c->i_fin_bias), g.out_channels, side());  // of the packed d(eps)
       }
       defer(bslab); defer(bS);
       GemmSeg sg{p(tp->hlast.off), C0, p<float>(tp->fin.as), p<float>(tp->fin.ab), C0, ACT_SILU};
@@ -401,12 +397,12 @@ struct Back : Exec {
       // dW[co][ci][tap] on the same GEMM: g = d(h0) [M][C0], the other operand the two fp32 input planes packed to
       // [M][32] NHWC (6 real channels); bias = column sums of d(h0)
       const size_t g0 = take_grad(tp->h0);
-      const int half = g.in_channels / 2, nt = P / 64;
+      const int half = g.in_channels / 2, nt = bias_grad_tiles(P);
       const size_t x32 = alloc((size_t)M * 32 * es());
       const size_t slab = alloc((size_t)B * nt * 2 * C0 * 4), S1 = alloc((size_t)B * C0 * 4);
       if (!dry) {
         chk(launch_pack_planes(dt, tp->lat, tp->cond, half, g.in_channels - half, p(x32), B, P, s));
-        bias_grad(g0, M, C0, P, nt, slab, S1, gp(c->i_init_b), c->channels_r[0], s);
+        bias_grad(g0, M, C0, P, slab, S1, gp(c->i_init_b), c->channels_r[0], s);
       }
       GemmSeg sg{p(x32), 32, nullptr, nullptr, 0, ACT_NONE};
       const Geo geo{S, S, S, S, 1, 0, 0};

@@ -139,6 +139,16 @@ hipError_t launch_batch_sum(const float* in, float* out, int B, int64_t stride, 
   hipLaunchKernelGGL(batch_sum_kernel, dim3((C + 127) / 128), dim3(128), 0, s, in, out, B, stride, C);
   return hipGetLastError();
 }
+hipError_t launch_bias_grad(int dtype, const void* g, int M, int C, int P, int Cstore, float* slab, float* S, float* out, hipStream_t s) {
+  if (P < 1 || M < P || M % P || Cstore < 1 || Cstore > C) return hipErrorInvalidValue;
+  const int B = M / P;
+  BwdMaskArgs m{};
+  m.g = g; m.act = ACT_NONE; m.slab = slab; m.M = M; m.C = C; m.P = P;
+  hipError_t e = launch_bwd_mask_reduce(dtype, m, s);
+  if (e == hipSuccess) e = launch_slab_reduce(slab, S, B, bias_grad_tiles(P), 2, 1, C, s);
+  if (e == hipSuccess) e = launch_batch_sum(S, out, B, C, Cstore, s);
+  return e;
+}
 
 // =============================================================================================
 // (2) GroupNorm backward coefficients.  With xhat = (x-mean)*rstd, G = gamma*(1+s), z = xhat*G + Bc:

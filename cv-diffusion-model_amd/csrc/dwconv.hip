@@ -310,10 +310,15 @@ static hipError_t launch_dw_t(const DwArgs& a, hipStream_t s) {
   static const std::string names[3] = {std::string("dwconv3x3_kernel<") + TypeName<T>::value + ", 32, 4>",
                                        std::string("dwconv3x3_kernel<") + TypeName<T>::value + ", 16, 4>",
                                        std::string("dwconv3x3_kernel<") + TypeName<T>::value + ", 8, 4>"};
+  static const std::string bwd_names[5] = {std::string("dwconv3x3_bwd_kernel<") + TypeName<T>::value + ", 32, 4>",
+                                           std::string("dwconv3x3_bwd_kernel<") + TypeName<T>::value + ", 16, 4>",
+                                           std::string("dwconv3x3_bwd_kernel<") + TypeName<T>::value + ", 8, 4>",
+                                           std::string("dwconv3x3_bwd_ragged_kernel<") + TypeName<T>::value + ", 32, 4>",
+                                           std::string("dwconv3x3_bwd_ragged_kernel<") + TypeName<T>::value + ", 16, 4>"};
   note_kernel(names[tx == 32 ? 0 : (tx == 16 ? 1 : 2)].c_str());
   if (ragged && a.bx) {  // backward instantiation; TX is 16 or 32 here
     if (!a.bas || !a.bab || !a.bslab || a.pool || a.s6) return hipErrorInvalidValue;
-    note_kernel("dwconv3x3_bwd_ragged_kernel");
+    note_kernel(bwd_names[tx == 32 ? 3 : 4].c_str());
     if (tx == 32) hipLaunchKernelGGL((dwconv3x3_bwd_ragged_kernel<T, 32, kDwPF>), grid, dim3(256), 0, s, a, tyl);
     else hipLaunchKernelGGL((dwconv3x3_bwd_ragged_kernel<T, 16, kDwPF>), grid, dim3(128), 0, s, a, tyl);
     return hipGetLastError();
@@ -336,6 +341,7 @@ static hipError_t launch_dw_t(const DwArgs& a, hipStream_t s) {
   }
   if (a.bx) {  // backward instantiation
     if (!a.bas || !a.bab || !a.bslab || a.pool) return hipErrorInvalidValue;
+    note_kernel(bwd_names[tx == 32 ? 0 : (tx == 16 ? 1 : 2)].c_str());
     if (tx == 32) hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, 32, kDwPF>), grid, dim3(256), 0, s, a, tyl);
     else if (tx == 16) hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, 16, kDwPF>), grid, dim3(128), 0, s, a, tyl);
     else hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, 8, kDwPF>), grid, dim3(64), 0, s, a, tyl);

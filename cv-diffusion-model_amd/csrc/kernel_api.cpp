@@ -344,26 +344,41 @@ int64_t llie_groupnorm_backward_scratch_floats(int batch, int C, int pixels) {
   if (batch <= 0 || C <= 0 || pixels <= 0) return LLIE_ERR_ARG;
   return (int64_t)batch * C * (2 * ((pixels + 63) / 64) + 7);  // slab, S, A, Bq, Cq, dG, dBc
 }
-int llie_groupnorm_backward(int dtype, const llie_gn_backward_args* a, float* scratch, int64_t scratch_floats, llie_stream stream) {
+}  // extern "C"
+// one norm site on launch_gn_site_bwd: slab NULL = the site's own mask-and-reduce pass writes dz and the tile partials into the head
+// of `scratch`; otherwise the producer's slab of `ntiles` tiles per image is summed as it stands (slab_ready)
+static int gn_site_call(const char* what, int dtype, const llie_gn_backward_args* a, float* slab, int ntiles, float* scratch,
+                        int64_t scratch_floats, llie_stream stream) {
   if (!dtype_ok(dtype) || !a || !scratch) return LLIE_ERR_ARG;
   const int C = a->c0 + a->c1;
   if (!a->g || !a->x0 || !a->dx0 || !a->scale || !a->shift || !a->mean || !a->rstd || !a->gamma || !a->beta || !a->dgamma || !a->dbeta ||
       a->act < ACT_NONE || a->act > ACT_SILU || (a->act != ACT_NONE && !a->dz) || a->batch <= 0 || a->pixels <= 0 || a->c0 <= 0 ||
       a->c0 % 32 || a->c1 < 0 || a->c1 % 32 || (a->c1 && (!a->x1 || !a->dx1)) || (!a->c1 && (a->x1 || a->dx1 || a->add1_1)) ||
       (a->dfilm && !a->film) || (a->film && a->film_stride < 0) || (a->dfilm && a->dfilm_stride < 2 * C) ||
-      (int64_t)a->batch * a->pixels * C / (dtype == 0 ? 4 : 8) >= (1ll << 31) ||
-      scratch_floats < llie_groupnorm_backward_scratch_floats(a->batch, C, a->pixels))
+      (int64_t)a->batch * a->pixels * C / (dtype == 0 ? 4 : 8) >= (1ll << 31))
     return LLIE_ERR_ARG;
-  const int nt = (a->pixels + 63) / 64;
+  // a producer's slab: the mask is already applied, so g is dz
+  if (slab && (ntiles <= 0 || a->act == ACT_NONE || a->dz != a->g)) return LLIE_ERR_ARG;
+  const int nt = slab ? ntiles : (a->pixels + 63) / 64;
   const size_t bc = (size_t)a->batch * C;
+  if (scratch_floats < (int64_t)(bc * (slab ? 7 : 2 * (size_t)nt + 7))) return LLIE_ERR_ARG;
   GnSiteArgs s{};
   s.g = a->g; s.dz = a->act == ACT_NONE ? nullptr : a->dz; s.x0 = a->x0; s.x1 = a->x1; s.c0 = a->c0; s.c1 = a->c1;
   s.as = a->scale; s.ab = a->shift; s.act = a->act; s.mean = a->mean; s.rstd = a->rstd; s.gamma = a->gamma; s.beta = a->beta;
   s.film = a->film; s.film_stride = a->film_stride; s.dfilm = a->dfilm; s.dfilm_stride = a->dfilm_stride; s.dgamma = a->dgamma; s.dbeta = a->dbeta;
-  s.slab = scratch; s.ntiles = nt; s.slab_ready = 0;
-  s.S = scratch + bc * 2 * nt; s.A = s.S + 2 * bc; s.Bq = s.A + bc; s.Cq = s.Bq + bc; s.dG = s.Cq + bc; s.dBc = s.dG + bc;
+  s.slab = slab ? slab : scratch; s.ntiles = nt; s.slab_ready = slab ? 1 : 0;
+  s.S = slab ? scratch : scratch + bc * 2 * nt; s.A = s.S + 2 * bc; s.Bq = s.A + bc; s.Cq = s.Bq + bc; s.dG = s.Cq + bc; s.dBc = s.dG + bc;
   s.add0 = a->add0; s.add1_0 = a->add1_0; s.add1_1 = a->add1_1; s.dx0 = a->dx0; s.dx1 = a->dx1; s.B = a->batch; s.P = a->pixels;
-  return kerr("groupnorm_backward", launch_gn_site_bwd(dtype, s, hs(stream)));
+  return kerr(what, launch_gn_site_bwd(dtype, s, hs(stream)));
+}
+extern "C" {
+int llie_groupnorm_backward(int dtype, const llie_gn_backward_args* a, float* scratch, int64_t scratch_floats, llie_stream stream) {
+  return gn_site_call("groupnorm_backward", dtype, a, nullptr, 0, scratch, scratch_floats, stream);
+}
+int llie_groupnorm_backward_from_slab(int dtype, const llie_gn_backward_args* a, float* slab, int ntiles, float* scratch,
+                                      int64_t scratch_floats, llie_stream stream) {
+  if (!slab) return LLIE_ERR_ARG;
+  return gn_site_call("groupnorm_backward_from_slab", dtype, a, slab, ntiles, scratch, scratch_floats, stream);
 }
 int64_t llie_linattn_dkv_floats(int batch, int N, int heads) {
   if (batch <= 0 || N <= 0 || heads <= 0) return LLIE_ERR_ARG;
@@ -408,6 +423,50 @@ int llie_final_bwd_data(int dtype, const float* deps, const float* w, void* da, 
   FinalBwdArgs a{};
   a.deps = deps; a.w = w; a.da = da; a.B = batch; a.H = H; a.W = W; a.C = C; a.Cout = Cout;
   return kerr("final_bwd_data", launch_final_bwd_data(dtype, a, hs(stream)));
+}
+// the depthwise input gradient as Back::irb_bwd launches it: the forward kernel's body with flipped taps, the affine-only prologue,
+// the ReLU6 mask of the forward pre-activation and the norm-2 partial sums in the epilogue
+int llie_dwconv3x3_backward(int dtype, const void* g, const float* gs, const float* gb, const float* w9c_flipped, const void* bx,
+                            const float* bas, const float* bab, void* dz_out, float* slab, int B, int H, int W, int C, llie_stream stream) {
+  if (!dtype_ok(dtype) || !g || !gs || !gb || !w9c_flipped || !bx || !bas || !bab || !dz_out || !slab || B <= 0 || H <= 0 || W <= 0 ||
+      C <= 0 || C % (dtype == 0 ? 32 : 64))
+    return LLIE_ERR_ARG;
+  DwArgs d{};
+  d.in = g; d.out = dz_out; d.as = gs; d.ab = gb; d.w = w9c_flipped; d.pool = nullptr; d.B = B; d.H = H; d.W = W; d.C = C; d.no_act = 1;
+  d.bx = bx; d.bas = bas; d.bab = bab; d.bslab = slab;
+  return kerr("dwconv3x3_backward", launch_dwconv3x3(dtype, d, hs(stream)));
+}
+int llie_bias_grad_floats(int batch, int C, int pixels, int64_t* slab_floats, int64_t* s_floats) {
+  if (batch <= 0 || C <= 0 || pixels <= 0 || !slab_floats || !s_floats) return LLIE_ERR_ARG;
+  *slab_floats = (int64_t)batch * bias_grad_tiles(pixels) * 2 * C;
+  *s_floats = (int64_t)batch * C;
+  return LLIE_OK;
+}
+int llie_bias_grad(int dtype, const void* g, int M, int C, int P, int Cstore, float* slab, float* S, float* out, llie_stream stream) {
+  if (!dtype_ok(dtype) || !g || !slab || !S || !out || P <= 0 || M < P || M % P || C <= 0 || C % 32 || Cstore < 1 || Cstore > C) return LLIE_ERR_ARG;
+  return kerr("bias_grad", launch_bias_grad(dtype, g, M, C, P, Cstore, slab, S, out, hs(stream)));
+}
+int llie_pack_planes(int dtype, const float* x0, int c0, const float* x1, int c1, void* out, int batch, int pixels, llie_stream stream) {
+  if (!dtype_ok(dtype) || !x0 || !out || c0 < 1 || c1 < 0 || c0 + c1 > 8 || (c1 > 0) != (x1 != nullptr) || batch <= 0 || pixels <= 0) return LLIE_ERR_ARG;
+  return kerr("pack_planes", launch_pack_planes(dtype, x0, x1, c0, c1, out, batch, pixels, hs(stream)));
+}
+int llie_add_into(int dtype, void* dst, const void* src, int64_t n, llie_stream stream) {
+  if (!dtype_ok(dtype) || !dst || !src || n <= 0 || n % (dtype == 0 ? 4 : 8)) return LLIE_ERR_ARG;
+  return kerr("add_into", launch_add_into(dtype, dst, src, n, hs(stream)));
+}
+int llie_sin_embed(const int64_t* t, const float* freqs, float* emb, int rows, int dim, llie_stream stream) {
+  if (!t || !freqs || !emb || rows <= 0 || dim < 2 || dim % 2) return LLIE_ERR_ARG;
+  return kerr("sin_embed", launch_sin_embed(t, freqs, emb, rows, dim, hs(stream)));
+}
+int llie_pointwise_backward(int kind, const float* a, const float* b, float* out, int64_t n, float scale, llie_stream stream) {
+  if (kind < LLIE_PW_SIGMOID_BWD || kind > LLIE_PW_SCALE || !a || !out || n <= 0 || (kind != LLIE_PW_SCALE && !b)) return LLIE_ERR_ARG;
+  hipStream_t s = hs(stream);
+  switch (kind) {
+    case LLIE_PW_SIGMOID_BWD: return kerr("pointwise_backward", launch_sigmoid_bwd(a, b, out, n, s));
+    case LLIE_PW_RELU6_BWD: return kerr("pointwise_backward", launch_relu6_bwd(a, b, out, n, s));
+    case LLIE_PW_SILU_BWD: return kerr("pointwise_backward", launch_silu_bwd(a, b, out, n, s));
+  }
+  return kerr("pointwise_backward", launch_scale_rows(a, out, n, scale, s));
 }
 
 int llie_preprocess_u8(const uint8_t* img, int batch, int H0, int W0, float* out, int S, llie_stream stream) {

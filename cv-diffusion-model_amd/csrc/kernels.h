@@ -392,6 +392,10 @@ hipError_t launch_bwd_mask_reduce(int dtype, const BwdMaskArgs& a, hipStream_t s
 hipError_t launch_slab_reduce(const float* slab, float* out, int B, int ntiles, int nj, int nj_out, int C, hipStream_t s);
 // out[c] = sum_b in[b*stride + c]
 hipError_t launch_batch_sum(const float* in, float* out, int B, int64_t stride, int C, hipStream_t s);
+// bias gradient: out[0..Cstore) = column sums of g [M][C] of T (P pixels per image; C a multiple of 32, Cstore <= C) -- bwd_mask_reduce
+// without activation or x, slab_reduce of its first plane, batch_sum.  Scratch: slab [M / P][bias_grad_tiles(P)][2][C], S [M / P][C].
+inline int bias_grad_tiles(int P) { return (P + 63) / 64; }
+hipError_t launch_bias_grad(int dtype, const void* g, int M, int C, int P, int Cstore, float* slab, float* S, float* out, hipStream_t s);
 
 // (2) GroupNorm backward coefficients from the reduced sums S[b][2][C] and the forward mean / rstd:
 //   dx = dz*A + x*Bq + Cq;  dG[b][c] = sum dz*xhat,  dBc[b][c] = sum dz  (before the FiLM / batch reductions)

@@ -545,6 +545,39 @@ int64_t llie_linear_dx_scratch_floats(int batch, int R, int Kc);
 int llie_linear_dw(const float* dy, int64_t dy_stride, const float* x, float* dw, float* db, int batch, int R, int Kc, llie_stream stream);
 int llie_final_bwd_data(int dtype, const float* deps, const float* w, void* da, int batch, int H, int W, int C, int Cout, llie_stream stream);
 
+/* The parts of the training backward pass that run between those kernels, each as the engine launches it.
+ * llie_dwconv3x3_backward: input gradient of the depthwise conv of one inverted-residual block, on the forward kernel's body.  g
+ *   [B][H][W][C] (the gradient of the conv's output before the SE gate); the prologue forms dh2 = g * gs + gb (gs / gb fp32 [B][C]: the
+ *   SE gate and d(mean) / pixels) rounded to the compute type; w9c_flipped fp32 [9][C]: the forward weights with the taps in reverse
+ *   order; the epilogue multiplies by the ReLU6 derivative [0 < bx * bas + bab < 6] of the forward pre-activation (bx [B][H][W][C]: the
+ *   tensor the forward conv read, bas / bab [B][C]: its norm affine) and stores dz_out in the compute type, plus slab fp32
+ *   [B][tiles][2][C] with tiles = the forward's llie_dwconv3x3_tiles: per (8-row segment, strip) the sums of dz and of dz * bx over
+ *   the pixels inside the map.  The strip height is the forward's llie_dwconv3x3_strip_rows.  Refused: NULL tensors, sizes < 1, C not a
+ *   multiple of 32 (fp32) / 64 (2-byte).
+ * llie_groupnorm_backward_from_slab: llie_groupnorm_backward for a site whose producer (llie_dwconv3x3_backward) already applied the
+ *   activation's derivative and wrote the tile partials: slab [batch][ntiles][2][C] with tiles of any pixel count.  Needs act != 0
+ *   and args->dz == args->g (dz is read, not written); scratch: 7 * batch * C floats.
+ * llie_bias_grad: out[0 .. Cstore) = column sums of g [M][C] (compute type, P pixels per image, C a multiple of 32, Cstore <= C)
+ *   through the scratch slab and S, whose sizes in floats llie_bias_grad_floats returns.
+ * llie_pack_planes: fp32 NCHW planes x0 [batch][c0][pixels] and x1 [batch][c1][pixels] (NULL with c1 = 0; c0 + c1 <= 8) -> out
+ *   [batch * pixels][32] of the compute type, channels beyond c0 + c1 zero.  llie_add_into: dst += src over n elements of the compute
+ *   type (n a multiple of 4 in fp32, 8 otherwise), the sum formed in fp32.
+ * llie_sin_embed: emb [rows][dim] = [cos | sin] of float(t[r]) * freqs[i], freqs fp32 [dim / 2], t device int64.
+ * llie_pointwise_backward: the fp32 elementwise kernels of the SE and time MLPs' backward over n elements: out = a * b * (1 - b)
+ *   (LLIE_PW_SIGMOID_BWD: b the sigmoid's output), 0 < b < 6 ? a : 0 (LLIE_PW_RELU6_BWD: b the ReLU6's output), a * silu'(b)
+ *   (LLIE_PW_SILU_BWD: b the SiLU's input), a * scale (LLIE_PW_SCALE: b unused).  out may alias a. */
+enum llie_pointwise_kind { LLIE_PW_SIGMOID_BWD = 0, LLIE_PW_RELU6_BWD = 1, LLIE_PW_SILU_BWD = 2, LLIE_PW_SCALE = 3 };
+int llie_dwconv3x3_backward(int dtype, const void* g, const float* gs, const float* gb, const float* w9c_flipped, const void* bx,
+                            const float* bas, const float* bab, void* dz_out, float* slab, int B, int H, int W, int C, llie_stream stream);
+int llie_groupnorm_backward_from_slab(int dtype, const llie_gn_backward_args* args, float* slab, int ntiles, float* scratch,
+                                      int64_t scratch_floats, llie_stream stream);
+int llie_bias_grad_floats(int batch, int C, int pixels, int64_t* slab_floats, int64_t* s_floats);
+int llie_bias_grad(int dtype, const void* g, int M, int C, int P, int Cstore, float* slab, float* S, float* out, llie_stream stream);
+int llie_pack_planes(int dtype, const float* x0, int c0, const float* x1, int c1, void* out, int batch, int pixels, llie_stream stream);
+int llie_add_into(int dtype, void* dst, const void* src, int64_t n, llie_stream stream);
+int llie_sin_embed(const int64_t* t, const float* freqs, float* emb, int rows, int dim, llie_stream stream);
+int llie_pointwise_backward(int kind, const float* a, const float* b, float* out, int64_t n, float scale, llie_stream stream);
+
 /* Statistics pass of the recompute form of InvertedResidualBlock (efficient_unet.py:207-212) on its own: Gram matrix
  * G = sum_px a' a'^T and column sums m = sum_px a' of a' = clamp01(x * scale + bias) rounded to the compute type, per image
  * (gram.hip).  x0 / x1: NHWC [batch][pixels][c0 / c1] of the compute type (x1 may be NULL with c1 = 0), c0 + c1 in {32, 64, 96},

@@ -1,6 +1,6 @@
 """Plain float64 references of the kernels behind the C ABI's per-kernel entry points, and the comparison helpers of the kernel
 tests (tests/test_gpu_forward_kernels.py, tests/test_gpu_boundary_kernels.py, tests/test_forward_refs_host.py,
-tests/test_gpu_backward_kernels.py).
+tests/test_gpu_backward_kernels.py, tests/test_backward_refs_host.py).
 
 Pure torch on CPU tensors, one function per operation.  A reference mirrors exactly the roundings its kernel does -- listed in each
 docstring, read from the kernel -- and nothing else: fp32 accumulation becomes float64.  Every reference returns
@@ -15,6 +15,7 @@ MI355X (the worst ratio over every case of the kernel and three seeds stands bes
 Layouts are the kernels': activations NHWC, [B][P][C] or [B][H][W][C]; tables [B][ld] fp32; dtype 0 fp32, 1 fp16, 2 bf16.
 """
 import math
+import zlib
 
 import torch
 
@@ -530,6 +531,193 @@ def gemm_dot_stats_ref(stored, dot, rows):
     return ref, ab, _ulp(ref, 0)
 
 
+# ------------------------------------------------------------------------------------------------ llie_dwconv3x3_backward (dwconv.hip)
+MASK_EDGE = 2.0 ** -21  # mask_unsure: z within this much of (|bx bas| + |bab|) from 0 or 6 -- eight fp32 ulps of the larger term
+
+
+def relu6_mask_ref(bx, bas, bab):
+    """The ReLU6 derivative as dw_body_impl<BWD> forms it: z = bx * bas + bab in fp32, mask = 0 < z < 6, strict on both sides.
+    Mirrored with one rounding (a fused multiply-add); the compiler may also round the product first, which moves z by at most one
+    ulp of |bx bas| + |bab|, so an entry whose z lies within MASK_EDGE of that magnitude from 0 or 6 may take either value -- unless
+    product and sum are exact in fp32 (then every evaluation order gives the same z: an exact 0 or 6 is masked, no doubt about it).
+    -> (mask, mask_unsure), bool [B][H][W][C]"""
+    p, q = bx.double() * bas.double()[:, None, None, :], bab.double()[:, None, None, :]
+    z = _f32(p + q)
+    edge = MASK_EDGE * (p.abs() + q.abs())
+    inexact = (_f32(p) != p) | (z != p + q)
+    return (z > 0.0) & (z < 6.0), ((z.abs() <= edge) | ((z - 6.0).abs() <= edge)) & inexact
+
+
+def dwconv3x3_bwd_ref(dtype, g, gs, gb, w9c, bx, bas, bab):
+    """llie_dwconv3x3_backward: dz = round_T(depthwise3x3(round_T(g * gs + gb), w9c) * [0 < bx * bas + bab < 6]), zero padding; w9c
+    is the [9][C] table the kernel is given (the forward weights with the taps reversed).  Roundings mirrored: the operand
+    dh2 = fma(g, gs, gb) in fp32 rounded to T (dw_operand with no_act), the weights rounded to T, fp32 accumulation -> float64, the
+    mask's z (relu6_mask_ref), the store rounds to T (one ulp of slack).  An entry whose mask is unsure may be 0 or the unmasked
+    value: its slack is that value's magnitude.  Masked entries have abssum 0 and slack 0: the kernel must store an exact zero.
+    -> (ref, abssum, slack, mask_unsure)"""
+    a, s = dw_operand(dtype, g, gs, gb, no_act=True)
+    wt = dw_weights(dtype, w9c)
+    acc, ab = dw_from_padded(pad_zero(a), wt)
+    sl, _ = dw_from_padded(pad_zero(s), wt.abs())
+    mask, unsure = relu6_mask_ref(bx, bas, bab)
+    m = mask.double()
+    ref = acc * m
+    slack = torch.where(unsure, acc.abs() + sl + _ulp(acc, dtype), (sl + _ulp(ref, dtype)) * m)
+    return ref, torch.where(unsure, ab, ab * m), slack, unsure
+
+
+def strip_stats2_ref(dz_stored, bx, tx, seg_rows=8):
+    """The statistics slab of llie_dwconv3x3_backward from the dz it stored: [B][ceil(H / 8) * ceil(W / tx)][2][C], entry (segment,
+    strip) = tile index segment * tiles_x + strip, plane 0 the sum of dz and plane 1 the sum of dz * bx over the tile's 8 rows x tx
+    columns that lie in the image (fp32 adds of exact values; the products are rounded to fp32 once, which the bar covers).
+    -> (ref, abssum, slack)"""
+    q, x = dz_stored.double(), bx.double()
+    B, H, W, C = q.shape
+    ny, nx = (H + seg_rows - 1) // seg_rows, (W + tx - 1) // tx
+
+    def tiles(t):
+        tp = torch.zeros(B, ny * seg_rows, nx * tx, C, dtype=torch.float64)
+        tp[:, :H, :W] = t
+        return tp.view(B, ny, seg_rows, nx, tx, C).sum((2, 4)).reshape(B, ny * nx, C)
+    ref = torch.stack([tiles(q), tiles(q * x)], 2)
+    ab = torch.stack([tiles(q.abs()), tiles((q * x).abs())], 2)
+    return ref, ab, _ulp(ref, 0)
+
+
+# The maps of the depthwise tests, forward and backward -- (H, W, TX, ragged): TX = the strip width launch_dw_t takes; non-square maps
+# both ways round.  13 x 24: ragged rows on a width that is 8 (mod 16) -- the ragged kernel has no 8-wide form and runs 16-wide strips,
+# and llie_dwconv3x3_tiles must count those
+DW_MAPS = [(8, 24, 8, False), (16, 8, 8, False), (8, 40, 8, False), (16, 16, 16, False), (8, 48, 16, False), (16, 32, 32, False),
+           (8, 64, 32, False), (9, 13, 16, True), (13, 9, 16, True), (13, 12, 16, True), (25, 18, 32, True), (18, 25, 32, True),
+           (9, 20, 32, True), (25, 50, 32, True), (25, 32, 32, True), (9, 16, 16, True), (13, 24, 16, True)]
+# the backward test adds a last segment of four rows (H = 12) on whole 16-wide strips
+DW_BWD_MAPS = DW_MAPS + [(12, 16, 16, True)]
+DW_BWD_CASES = [(H, W, tx, rg, dtype, 2 * (32 if dtype == 0 else 64)) for H, W, tx, rg in DW_BWD_MAPS for dtype in (0, 1, 2)]
+# (H, strip height, B, dtype) at W = 8 and one channel chunk: a strip as high as the map, and two 16-row strips (the second one's slab
+# segments start at 2)
+DW_BWD_STRIPS = [(H, H, 1024, dtype) for H in (16, 32, 64) for dtype in (0, 1, 2)] + [(32, 16, 512, dtype) for dtype in (0, 1, 2)]
+
+
+def seeded(seed0, *key):
+    """the generator of one test case; seed0 = LLIE_FWD_TEST_SEED"""
+    return torch.Generator().manual_seed(zlib.crc32(repr(key).encode()) % 1000003 + 7919 * seed0)
+
+
+def dw_bwd_inputs(B, H, W, C, dtype, seed0, key):
+    """Inputs of llie_dwconv3x3_backward as Back::irb_bwd meets them: g = d(a3) and bx = h1 of T, gs = the SE gate in (0, 1), gb =
+    d(mean) / P, w = the flipped taps, bas / bab = norm2's affine.  z = bx bas + bab has mean 3 and deviation about 2.5, so that
+    roughly a tenth of the entries lies below 0, a tenth above 6, and (relu6_mask_ref) next to none within rounding of either edge;
+    channel 0 holds exact zeros and sixes.
+    -> (g, gs, gb, w, bx, bas, bab)"""
+    gn = seeded(seed0, "dw_bwd", key, dtype)
+    g = _rt(torch.randn(B, H, W, C, generator=gn), dtype)
+    gs, gb = torch.rand(B, C, generator=gn) * 0.9 + 0.05, torch.randn(B, C, generator=gn) * 0.1
+    w = torch.randn(9, C, generator=gn) / 3
+    bx = _rt(torch.randn(B, H, W, C, generator=gn) * 2, dtype)
+    bas, bab = torch.rand(B, C, generator=gn) + 0.5, torch.randn(B, C, generator=gn) * 1.5 + 3.0
+    # channel 0: z = bx exactly, with every fourth pixel exactly 6 and every fourth exactly 0 -- both edges of the strict mask
+    bas[:, 0], bab[:, 0] = 1.0, 0.0
+    d = (torch.arange(H)[:, None] + torch.arange(W)[None, :]) % 4
+    bx[:, :, :, 0] = torch.where(d == 0, 6.0, torch.where(d == 2, 0.0, bx[:, :, :, 0].float())).to(bx.dtype)
+    return g, gs, gb, w, bx, bas, bab
+
+
+def dw_bwd_case_inputs(case, seed0):
+    H, W, tx, rg, dtype, C = case
+    return dw_bwd_inputs(3, H, W, C, dtype, seed0, (H, W, C))
+
+
+def dw_bwd_strip_inputs(H, rows, dtype, seed0):
+    return dw_bwd_inputs(3, H, 8, 32 if dtype == 0 else 64, dtype, seed0, ("strip", H, rows))
+
+
+def mask_unsure_ok(unsure, tx):
+    """The condition the backward depthwise cases must meet for their mask to be decided by the reference: unsure entries are at most
+    0.1 % of the case, and in no (8-row segment, strip, channel) tile do they make up every pixel."""
+    B, H, W, C = unsure.shape
+    ny, nx = (H + 7) // 8, (W + tx - 1) // tx
+    cnt = torch.zeros(B, ny * 8, nx * tx, C)
+    cnt[:, :H, :W] = unsure.float()
+    inside = torch.zeros(1, ny * 8, nx * tx, 1)
+    inside[:, :H, :W] = 1.0
+    per_tile = cnt.view(B, ny, 8, nx, tx, C).sum((2, 4))
+    pixels = inside.view(1, ny, 8, nx, tx, 1).sum((2, 4))
+    return unsure.float().mean().item() <= 1e-3 and bool((per_tile < pixels).all())
+
+
+# ------------------------------------------------------------------------------------------------ the backward pass's glue (bwd.hip)
+def bias_grad_ref(g, Cstore):
+    """llie_bias_grad: out[c] = sum over the rows of g [M][C] (T values, fp32 adds) for c < Cstore.  -> (ref, abssum, slack)"""
+    q = g.double()[:, :Cstore]
+    ref = q.sum(0)
+    return ref, q.abs().sum(0), _ulp(ref, 0)
+
+
+def pack_planes_ref(dtype, x0, x1):
+    """llie_pack_planes: fp32 planes x0 [B][c0][P], x1 [B][c1][P] or None -> [B * P][32] of T: channel c < c0 from x0, c0 <= c < c0 + c1
+    from x1, the rest zero; each value rounded to T once (exact: the test asks for equal bits)."""
+    xs = torch.cat([x0] + ([x1] if x1 is not None else []), 1)            # [B][c0 + c1][P]
+    B, c, P = xs.shape
+    out = torch.zeros(B, P, 32)
+    out[:, :, :c] = xs.permute(0, 2, 1)
+    return _rt(out.reshape(B * P, 32), dtype)
+
+
+def add_into_ref(dtype, dst, src):
+    """llie_add_into: the fp32 sum of two T values, rounded to T once (IEEE operations: the test asks for equal bits)."""
+    return (dst.float() + src.float()).to(TDT[dtype])
+
+
+def sin_freqs(dim):
+    """SinusoidalPosEmb's frequency table as llie_create tabulates it: q = (float(-ln 1e4) * i) / half in fp32, exp in double, to fp32"""
+    half = dim // 2
+    q = (torch.tensor(-math.log(10000.0), dtype=torch.float32) * torch.arange(half, dtype=torch.float32)) / float(half)
+    return q.double().exp().float()
+
+
+def sin_embed_ref(t, freqs):
+    """sin_embed_kernel / time_embed_kernel: arg = float(t) * freqs[i], one fp32 product (mirrored); emb = [cos(arg) | sin(arg)].
+    cosf / sinf reduce an argument of up to 999 with an absolute, not a relative error, so the absolute sum of an entry is 1 (the
+    functions' amplitude).  -> (ref, abssum, slack) [rows][dim]"""
+    arg = (t.float()[:, None] * freqs.float()[None, :]).double()
+    ref = torch.cat([arg.cos(), arg.sin()], 1)
+    return ref, torch.ones_like(ref), _ulp(ref, 0)
+
+
+def _silu_err(z):
+    """evaluation error of siluf(z) = z / (1 + __expf(-z)) in units of 2^-24, as silu_operand states it: |silu(z)| (1.5 |z| + 4)"""
+    return (z * torch.sigmoid(z)).abs() * (1.5 * z.abs() + 4.0)
+
+
+def time_embed_ref(emb, w1, b1, w3, b3):
+    """time_embed_kernel after the embedding: hidden = silu(W1 emb + b1), temb = W3 hidden + b3, silu_temb = silu(temb), all fp32
+    with nothing rounded in between (-> float64).  emb: the kernel's own fp32 embedding, so that the MLP is judged alone.  The
+    hidden layer's error is carried on: |silu'| times its pre-activation's absolute sum plus the evaluation error of siluf joins
+    temb's absolute sum, and likewise for silu_temb.  -> ((temb, abssum, slack), (silu_temb, abssum, slack))"""
+    e, W1, W3 = emb.double(), w1.double(), w3.double()
+    z1, z1a = e @ W1.t() + b1.double(), e.abs() @ W1.abs().t() + b1.double().abs()
+    dsilu = lambda z: torch.sigmoid(z) * (1 + z * (1 - torch.sigmoid(z)))  # noqa: E731
+    h, ha = z1 * torch.sigmoid(z1), dsilu(z1).abs() * z1a + _silu_err(z1)
+    temb, ta = h @ W3.t() + b3.double(), (h.abs() + ha) @ W3.abs().t() + b3.double().abs()
+    st, sa = temb * torch.sigmoid(temb), dsilu(temb).abs() * ta + _silu_err(temb)
+    return (temb, ta, _ulp(temb, 0)), (st, sa, _ulp(st, 0))
+
+
+def pointwise_bwd_ref(kind, a, b, scale=0.0):
+    """llie_pointwise_backward on fp32 vectors: kind 0 a b (1 - b); 1 (0 < b < 6 ? a : 0), exact; 2 a silu'(b) with sigmoid from
+    __expf (the evaluation error grows with |b| as for siluf); 3 a * scale, one rounding, exact.  -> (ref, abssum) -- abssum None
+    where the test asks for equal bits."""
+    a64, b64 = a.double(), (b.double() if b is not None else None)
+    if kind == 0:
+        return a64 * b64 * (1 - b64), a64.abs() * b64.abs() * (1 + b64.abs())
+    if kind == 1:
+        return torch.where((b64 > 0) & (b64 < 6), a64, torch.zeros_like(a64)), None
+    if kind == 2:
+        sg = torch.sigmoid(b64)
+        return a64 * sg * (1 + b64 * (1 - sg)), a64.abs() * sg * (1 + b64.abs() * (1 - sg)) * (1.5 * b64.abs() + 4.0)
+    return _f32(a64 * float(torch.tensor(scale, dtype=torch.float32))), None
+
+
 # ------------------------------------------------------------------------------------------------ bars
 # BAR x 2^-24 x abssum per entry.  "worst" = the worst ratio |out - ref| / (2^-24 abssum) measured on the MI355X over all cases of
 # the kernel in tests/test_gpu_forward_kernels.py and seeds 0, 1, 2 (LLIE_FWD_TEST_SEED), as fp32 / fp16 / bf16; the bar is about
@@ -557,3 +745,12 @@ BAR_AFFINE_STATS = 22.0   # worst 1.73 / 2.15 / 1.17
 BAR_CONVERT_STATS = 78.0  # worst 5.76 / 7.77 / 4.78, all at P = 192: nchw_to_nhwc_kernel adds a tile's 64 pixels one after the other in one
                           # thread, where the other producers add 16 per lane and then combine lanes and waves as a tree
 BAR_GEMM_DOT = 9.0        # worst 0.84 / 0.57 / 0.37 (the output itself, under BAR_GEMM: 4.25 / 0.15 / 0.05)
+# the depthwise input gradient and the backward pass's glue: worst over all cases of the tests of tests/test_gpu_backward_kernels.py
+# named beside each and seeds 0, 1, 2, as fp32 / fp16 / bf16
+BAR_DW_BWD = 32.0         # dz, worst 3.25 / 0.24 / 0.00 (test_dwconv3x3_backward_vs_float64; strip heights 2.40 / 0.11 / 0.00; norm2 site 2.95 / - / 0.16)
+BAR_DW_BWD_STATS = 11.0   # slab, worst 1.11 / 0.80 / 0.56 (strip heights 0.85 / 0.80 / 0.62)
+BAR_BIAS_GRAD = 3.6       # worst 0.36 / 0.32 / 0.18
+BAR_PW_BWD = 6.7          # worst, sigmoid' 0.67, SiLU' 0.55 (fp32 kernels)
+BAR_TIME_EMBED = 6.8      # worst, temb 0.68, silu_temb 0.53 (fp32 kernel)
+BAR_SIN_EMBED = 2.0       # worst 0.00: always inside the ulp of the stored value.  Not measured but reasoned: the device library's cosf and
+                          # sinf are accurate to 2 ulp of a result that is at most 1, one of which is the slack, the other at most 2^-24

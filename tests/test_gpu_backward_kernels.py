@@ -12,6 +12,11 @@ measured ratio |err| / (2^-24 * abs sum) on the MI355X; the bars are about 10x t
 
 Every output is filled with NaN first (entries the kernel never writes show up), strided outputs carry canary values around the
 written window, and every call is made twice and must give the same bits.
+
+The depthwise input gradient, the norm site fed by its slab and the remaining glue of the backward pass (bias gradient, pack_planes,
+add_into, the pointwise fp32 kernels, the time embedding) follow at the end of the file; their cases, references and bars stand in
+tests/kernel_refs.py, shared with tests/test_backward_refs_host.py, and LLIE_FWD_TEST_SEED (default 0) shifts their seeds: the bars
+were measured over seeds 0, 1 and 2.
 """
 import ctypes
 import importlib
@@ -25,13 +30,16 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from kernel_refs import TDT, U, _flip_slack, _r64, _ratio, _rt, _ulp  # noqa: E402  (the comparison helpers: one copy)
+import kernel_refs as R  # noqa: E402
+from kernel_refs import NAN, TDT, U, Guarded, _flip_slack, _r64, _ratio, _rt, _same, _slab, _split, _ulp  # noqa: E402  (the comparison helpers: one copy)
 
 pytestmark = pytest.mark.gpu
 N = importlib.import_module("cv-diffusion-model_amd._native")
 
 CANARY = 12345.5
 DTYPES = [0, 1, 2]
+TNAME = {0: "float", 1: "_Float16", 2: "__bf16"}
+SEED0 = int(os.environ.get("LLIE_FWD_TEST_SEED", "0"))  # shifts the seeds of the tests whose bars stand in kernel_refs.py (measured over 0, 1, 2)
 
 
 @pytest.fixture(scope="module")
@@ -42,6 +50,10 @@ def dev():
 
 def _st():
     return torch.cuda.current_stream().cuda_stream
+
+
+def _last():
+    return N.lib().llie_last_kernel().decode()
 
 
 def _act64(z, act):
@@ -278,6 +290,64 @@ GN_CASES = [  # (name, c0, c1, P, B, act, film, add0, add1, alias)
 ]
 
 
+def _rc(t, cg):
+    return t.repeat_interleave(cg, dim=1)  # [B][32] -> [B][C]
+
+
+def _gn_record(x, gamma, beta, s, f):
+    """The forward record in fp32 (what llie_groupnorm_finalize leaves) of x [B][P][C] of T: mean / rstd per group, G = gamma (1 + s),
+    the affine scale / shift.  -> (mean_f, rstd_f, G_f, scale, shift)"""
+    B, P, C = x.shape
+    cg = C // 32
+    xg = x.double().view(B, P, 32, cg)
+    mean64 = xg.mean((1, 3))
+    var64 = xg.var((1, 3), unbiased=False)
+    mean_f, rstd_f = mean64.float(), (1.0 / torch.sqrt(var64 + 1e-5)).float()
+    G_f = (gamma[None, :].double() * (1 + s.double())).float()
+    scale = (_rc(rstd_f, cg).double() * G_f.double()).float()
+    shift = ((beta[None, :].double() - _rc(mean_f, cg).double() * _rc(rstd_f, cg).double() * gamma[None, :].double()) * (1 + s.double())
+             + f.double()).float()
+    return mean_f, rstd_f, G_f, scale, shift
+
+
+def _gn_forward64(x, gamma, beta, s, f, mean_f, rstd_f):
+    """n = (xhat gamma + beta) (1 + s) + f in float64 with autograd leaves x, gamma, beta, s, f: the record's fp32 mean / rstd values, the
+    true derivative.  -> (n [B][P][C], leaves)"""
+    B, P, C = x.shape
+    cg = C // 32
+    xv = x.double().requires_grad_(True)
+    gam, bet = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
+    sv, fv = s.double().requires_grad_(True), f.double().requires_grad_(True)
+    xg = xv.view(B, P, 32, cg)
+    m_t, r_t = xg.mean((1, 3)), 1.0 / torch.sqrt(xg.var((1, 3), unbiased=False) + 1e-5)
+    m_v = mean_f.double() + (m_t - m_t.detach())
+    r_v = rstd_f.double() + (r_t - r_t.detach())
+    xhat = ((xg - m_v[:, None, :, None]) * r_v[:, None, :, None]).view(B, P, C)
+    return (xhat * gam + bet) * (1 + sv[:, None, :]) + fv[:, None, :], [xv, gam, bet, sv, fv]
+
+
+def _gn_abs_sums(dz, x, mean_f, rstd_f, G_f, gamma, beta, s, a0=None, a1=None):
+    """Absolute sums of a norm site's outputs from the dz the later stages read, following the kernel's algebra: dG = rstd (sum dz x -
+    mean sum dz).  -> dict dgamma / dbeta [C], ds / df [B][C], dx [B][P][C]"""
+    B, P, C = x.shape
+    cg = C // 32
+    mb, rb = _rc(mean_f, cg).double(), _rc(rstd_f, cg).double()             # [B][C]
+    S1a, S2a = dz.abs().sum(1), (dz * x.double()).abs().sum(1)              # [B][C]
+    dGa = rb * (S2a + mb.abs() * S1a)
+    one_s = (1 + s.double()).abs()
+    Ga = G_f.double().abs()
+    c1a = (Ga * S1a).view(B, 32, cg).sum(-1) / (cg * P)
+    c2a = (Ga * dGa).view(B, 32, cg).sum(-1) / (cg * P)
+    dxa = (dz.abs() * (rb * Ga)[:, None, :] + (x.double().abs() + mb.abs()[:, None, :]) * (rb * rb * _rc(c2a, cg))[:, None, :]
+           + (rb * _rc(c1a, cg))[:, None, :])
+    if a0 is not None:
+        dxa = dxa + a0.double().abs()
+    if a1 is not None:
+        dxa = dxa + a1.double().abs()
+    return dict(dgamma=(one_s * dGa).sum(0), dbeta=(one_s * S1a).sum(0), ds=gamma.double().abs() * dGa + beta.double().abs() * S1a,
+                df=S1a, dx=dxa)
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("case", GN_CASES, ids=[c[0] for c in GN_CASES])
 def test_groupnorm_backward_vs_float64_autograd(dev, case, dtype):
@@ -299,16 +369,7 @@ def test_groupnorm_backward_vs_float64_autograd(dev, case, dtype):
     f = torch.randn(B, C, generator=g) * 0.3 if film else torch.zeros(B, C)
     a0 = _rt(torch.randn(B, P, C, generator=g), dtype) if add0 else None
     a1 = _rt(torch.randn(B, P, C, generator=g), dtype) if add1 else None
-    # forward record in fp32 (what llie_groupnorm_finalize leaves): mean / rstd per group, the affine scale / shift
-    xg = x.double().view(B, P, 32, cg)
-    mean64 = xg.mean((1, 3))
-    var64 = xg.var((1, 3), unbiased=False)
-    mean_f, rstd_f = mean64.float(), (1.0 / torch.sqrt(var64 + 1e-5)).float()
-    rc = lambda t: t.repeat_interleave(cg, dim=1)  # noqa: E731  [B][32] -> [B][C]
-    G_f = (gamma[None, :].double() * (1 + s.double())).float()
-    scale = (rc(rstd_f).double() * G_f.double()).float()
-    shift = ((beta[None, :].double() - rc(mean_f).double() * rc(rstd_f).double() * gamma[None, :].double()) * (1 + s.double())
-             + f.double()).float()
+    mean_f, rstd_f, G_f, scale, shift = _gn_record(x, gamma, beta, s, f)
     # dz = g * act'(z), z = fma(x, scale, shift) in fp32, stored in T
     z = (x.double() * scale.double()[:, None, :] + shift.double()[:, None, :]).float().double()
     if act == 1:
@@ -384,41 +445,20 @@ def test_groupnorm_backward_vs_float64_autograd(dev, case, dtype):
     else:
         dz = gin.double()
     # (2) the rest, float64 autograd with the kernel's dz as the cotangent; the record's fp32 mean / rstd values, the true derivative
-    xv = x.double().requires_grad_(True)
-    gam, bet = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
-    sv, fv = s.double().requires_grad_(True), f.double().requires_grad_(True)
-    xg = xv.view(B, P, 32, cg)
-    m_t, r_t = xg.mean((1, 3)), 1.0 / torch.sqrt(xg.var((1, 3), unbiased=False) + 1e-5)
-    m_v = mean_f.double() + (m_t - m_t.detach())
-    r_v = rstd_f.double() + (r_t - r_t.detach())
-    xhat = ((xg - m_v[:, None, :, None]) * r_v[:, None, :, None]).view(B, P, C)
-    n = (xhat * gam + bet) * (1 + sv[:, None, :]) + fv[:, None, :]
-    gx, ggam, gbet, gs_, gf_ = torch.autograd.grad(n, [xv, gam, bet, sv, fv], dz)
+    n, leaves = _gn_forward64(x, gamma, beta, s, f, mean_f, rstd_f)
+    gx, ggam, gbet, gs_, gf_ = torch.autograd.grad(n, leaves, dz)
     if add0:
         gx = gx + a0.double()
     if add1:
         gx = gx + a1.double()
-    # absolute sums of the kernel's terms
-    mb, rb = rc(mean_f).double(), rc(rstd_f).double()                       # [B][C]
-    S1a, S2a = dz.abs().sum(1), (dz * x.double()).abs().sum(1)              # [B][C]
-    dGa = rb * (S2a + mb.abs() * S1a)
-    one_s = (1 + s.double()).abs()
-    Ga = G_f.double().abs()
-    c1a = (Ga * S1a).view(B, 32, cg).sum(-1) / (cg * P)
-    c2a = (Ga * dGa).view(B, 32, cg).sum(-1) / (cg * P)
-    dxa = (dz.abs() * (rb * Ga)[:, None, :] + (x.double().abs() + mb.abs()[:, None, :]) * (rb * rb * rc(c2a))[:, None, :]
-           + (rb * rc(c1a))[:, None, :])
-    if add0:
-        dxa = dxa + a0.double().abs()
-    if add1:
-        dxa = dxa + a1.double().abs()
+    ab = _gn_abs_sums(dz, x, mean_f, rstd_f, G_f, gamma, beta, s, a0, a1)  # absolute sums of the kernel's terms
     tag = f"gn/{name}/dt{dtype}"
-    _ratio(res["dgamma"][:C], ggam, (one_s * dGa).sum(0), _ulp(ggam, 0), GN_BAR, tag + "/dgamma")
-    _ratio(res["dbeta"][:C], gbet, (one_s * S1a).sum(0), _ulp(gbet, 0), GN_BAR, tag + "/dbeta")
+    _ratio(res["dgamma"][:C], ggam, ab["dgamma"], _ulp(ggam, 0), GN_BAR, tag + "/dgamma")
+    _ratio(res["dbeta"][:C], gbet, ab["dbeta"], _ulp(gbet, 0), GN_BAR, tag + "/dbeta")
     if film:
-        _ratio(res["dfilm"][:, :C], gs_, gamma.double().abs() * dGa + beta.double().abs() * S1a, _ulp(gs_, 0), GN_BAR, tag + "/ds")
-        _ratio(res["dfilm"][:, C:2 * C], gf_, S1a, _ulp(gf_, 0), GN_BAR, tag + "/df")
-    _ratio(res["dx"], gx, dxa, _ulp(gx, dtype), GN_BAR, tag + "/dx")
+        _ratio(res["dfilm"][:, :C], gs_, ab["ds"], _ulp(gs_, 0), GN_BAR, tag + "/ds")
+        _ratio(res["dfilm"][:, C:2 * C], gf_, ab["df"], _ulp(gf_, 0), GN_BAR, tag + "/df")
+    _ratio(res["dx"], gx, ab["dx"], _ulp(gx, dtype), GN_BAR, tag + "/dx")
 
 
 # =============================================================================================
@@ -609,3 +649,369 @@ def test_final_bwd_data_vs_float64(dev, H, C, dtype):
         outs.append(da.cpu())
     assert torch.equal(outs[0].float().view(torch.int32), outs[1].float().view(torch.int32))
     _ratio(outs[0], ref, absr, _ulp(ref, dtype), FINAL_BAR, f"final_bwd_data/H{H}/C{C}/dt{dtype}")
+
+
+# =============================================================================================
+# llie_dwconv3x3_backward: the depthwise input gradient with its ReLU6 mask and norm-2 partial sums (dwconv.hip, BWD = true).
+# Cases, inputs, references and bars (BAR_DW_BWD, BAR_DW_BWD_STATS) stand in kernel_refs.py; tests/test_backward_refs_host.py checks
+# without a GPU that the reference is float64 autograd's, that the mask is decided for every case here, and that the bars have teeth.
+def _dwb_call(dev, dtype, dd, B, H, W, C):
+    """dd: the device tensors (g, gs, gb, flipped taps, bx, bas, bab) -> (dz, slab, tiles per image), every buffer guarded"""
+    L = N.lib()
+    out = Guarded((B, H, W, C), dev, TDT[dtype])
+    nt = int(L.llie_dwconv3x3_tiles(H, W))
+    slab = _slab(dev, B, nt, 2, C)
+    N.check(L.llie_dwconv3x3_backward(dtype, *[t.data_ptr() for t in dd], out.ptr, slab.ptr, B, H, W, C, _st()), "dwconv3x3_backward")
+    torch.cuda.synchronize()
+    return out, slab, nt
+
+
+def _dwb_check(tag, dtype, inp, o, slab, nt, tx):
+    ref, ab, sl, unsure = R.dwconv3x3_bwd_ref(dtype, *inp)
+    assert R.mask_unsure_ok(unsure, tx), f"{tag}: the reference cannot decide the mask of this case"
+    _ratio(o, ref, ab, sl, R.BAR_DW_BWD, f"dw_bwd/{tag}")
+    sref, sab, ssl = R.strip_stats2_ref(o, inp[4], tx)
+    assert sref.shape[1] == nt
+    _ratio(slab, sref, sab, ssl, R.BAR_DW_BWD_STATS, f"dw_bwd_stats/{tag}")
+
+
+@pytest.mark.parametrize("case", R.DW_BWD_CASES, ids=[f"{c[0]}x{c[1]}-dt{c[4]}-c{c[5]}" for c in R.DW_BWD_CASES])
+def test_dwconv3x3_backward_vs_float64(dev, case):
+    """llie_dwconv3x3_backward on the forward test's maps (strips 8 / 16 / 32 wide, ragged W and H, ragged H on W = 8 mod 16, non-square
+    both ways) plus a four-row last segment (12 x 16), two channel chunks, B = 3 with per-image tables, every dtype: the kernel name with
+    its template arguments; dz entry by entry (masked entries must be exact zeros); the slab [B][llie_dwconv3x3_tiles][2][C] entry by
+    entry against the sums of the stored dz and of dz * bx over each (8-row segment, strip) tile's pixels inside the map; nothing
+    written outside dz and the helper's tile count (canaries); an image alone gives the bits of its row in the batch.
+    Measured worst ratio (MI355X, seeds 0..2), dz: 3.25 fp32, 0.24 fp16, 0.00 bf16, bar BAR_DW_BWD = 32; slab: 1.11 / 0.80 / 0.56, bar
+    BAR_DW_BWD_STATS = 11."""
+    L = N.lib()
+    H, W, tx, ragged, dtype, C = case
+    B = 3
+    inp = R.dw_bwd_case_inputs(case, SEED0)
+    dd = [t.to(dev) for t in inp]
+    assert int(L.llie_dwconv3x3_strip_rows(dtype, B, H, W, C)) == 8 and int(L.llie_dwconv3x3_strip_rows(dtype, 1, H, W, C)) == 8
+    want = f"dwconv3x3_bwd_{'ragged_' if ragged else ''}kernel<{TNAME[dtype]}, {tx}, 4>"
+    tag = f"{H}x{W}x{C}/dt{dtype}"
+    runs = []
+    for _ in range(2):
+        out, slab, nt = _dwb_call(dev, dtype, dd, B, H, W, C)
+        assert _last() == want, _last()
+        runs.append((out.cpu("dw_bwd dz"), _split(slab.cpu("dw_bwd slab"), B, nt, "dw_bwd slab")))
+    _same(runs[0][0], runs[1][0], tag + " dz")
+    _same(runs[0][1], runs[1][1], tag + " slab")
+    o, s = runs[0]
+    _dwb_check(tag, dtype, inp, o, s, nt, tx)
+    one = [t if t.shape == (9, C) else t[2:3].contiguous() for t in dd]
+    out1, slab1, _ = _dwb_call(dev, dtype, one, 1, H, W, C)
+    _same(out1.cpu("dw_bwd dz")[0], o[2], tag + " image 2 alone (dz)")
+    _same(_split(slab1.cpu("dw_bwd slab"), 1, nt, "dw_bwd slab")[0], s[2], tag + " image 2 alone (slab)")
+
+
+@pytest.mark.parametrize("H,rows,B,dtype", R.DW_BWD_STRIPS, ids=[f"{h}rows{r}-dt{d}" for h, r, _, d in R.DW_BWD_STRIPS])
+def test_dwconv3x3_backward_strip_heights(dev, H, rows, B, dtype):
+    """Strips of 16, 32 and 64 rows (W = 8, one channel chunk, B = 1024 made of three distinct images, as test_dwconv3x3_strip_heights):
+    the 12-row unroll wraps (up to 66 input rows) and a strip writes slab segments 1 to 7; and a 32-row map in two 16-row strips (B =
+    512), where the second strip's segments start at 2.  llie_dwconv3x3_strip_rows must name the height; images 0..2 are checked
+    against float64 (dz and slab), every other image must equal its twin bit for bit.  Bars and measured ratios as
+    test_dwconv3x3_backward_vs_float64 (worst here: dz 2.40 / 0.11 / 0.00, slab 0.85 / 0.80 / 0.62)."""
+    L = N.lib()
+    W, C = 8, 32 if dtype == 0 else 64
+    assert int(L.llie_dwconv3x3_strip_rows(dtype, B, H, W, C)) == rows
+    inp = R.dw_bwd_strip_inputs(H, rows, dtype, SEED0)
+    idx = torch.arange(B) % 3
+    dd = [(t if t.shape == (9, C) else t[idx].contiguous()).to(dev) for t in inp]
+    runs = []
+    for _ in range(2):
+        out, slab, nt = _dwb_call(dev, dtype, dd, B, H, W, C)
+        assert _last() == f"dwconv3x3_bwd_kernel<{TNAME[dtype]}, 8, 4>", _last()
+        runs.append((out.cpu("dw_bwd dz"), _split(slab.cpu("dw_bwd slab"), B, nt, "dw_bwd slab")))
+    _same(runs[0][0], runs[1][0], "dz")
+    _same(runs[0][1], runs[1][1], "slab")
+    o, s = runs[0]
+    _same(o, o[idx], "an image and its twin (dz)")
+    _same(s, s[idx], "an image and its twin (slab)")
+    _dwb_check(f"strip{H}rows{rows}/dt{dtype}", dtype, inp, o[:3], s[:3], nt, 8)
+
+
+def test_dwconv3x3_backward_refusals(dev):
+    """NULL tensors, C off the chunk size, sizes < 1, an unknown dtype: LLIE_ERR_ARG before any HIP call; the NaN-filled dz stays NaN."""
+    L = N.lib()
+    t = torch.zeros(2 * 8 * 8 * 64, device=dev)
+    out = torch.full((2 * 8 * 8 * 64,), NAN, device=dev)
+    p = t.data_ptr()
+
+    def call(dtype=1, C=64, B=2, H=8, **kw):
+        a = dict(g=p, gs=p, gb=p, w=p, bx=p, bas=p, bab=p, dz=out.data_ptr(), slab=p)
+        a.update(kw)
+        return L.llie_dwconv3x3_backward(dtype, a["g"], a["gs"], a["gb"], a["w"], a["bx"], a["bas"], a["bab"], a["dz"], a["slab"], B, H, 8, C, _st())
+    for kw in ([dict(dtype=3), dict(C=32), dict(dtype=0, C=48), dict(B=0), dict(H=0)]
+               + [{k: None} for k in ("g", "gs", "gb", "w", "bx", "bas", "bab", "dz", "slab")]):
+        assert call(**kw) == N.ERR_ARG, kw
+    torch.cuda.synchronize()
+    assert torch.isnan(out).all(), "a refused call wrote its output"
+
+
+# =============================================================================================
+# norm2 of an inverted-residual block in training: llie_dwconv3x3_backward feeds llie_groupnorm_backward_from_slab (slab_ready = 1)
+N2_CASES = [(16, 24, 8, 128), (12, 9, 16, 128), (16, 24, 8, 2048), (12, 9, 16, 2048), (8, 8, 8, 2112)]  # (H, W, strip width, C)
+N2_PARAMS = [(c, d) for c in N2_CASES for d in (0, 2)]
+
+
+@pytest.mark.parametrize("case,dtype", N2_PARAMS, ids=[f"{c[0]}x{c[1]}x{c[3]}-dt{d}" for c, d in N2_PARAMS])
+def test_norm2_site_from_depthwise_slab(dev, case, dtype):
+    """llie_dwconv3x3_backward, then llie_groupnorm_backward_from_slab with FiLM, in place as Back::irb_bwd runs them (dh1 over dz),
+    against float64 autograd of depthwise3x3(relu6(gn_film(h1))) w.r.t. h1, gamma, beta and the FiLM rows, from the stored tensors:
+    B = 3; 16 x 24 (six tiles of 64 pixels) and the ragged 12 x 9 (tiles of 72 and 36 pixels); C = 128 (cg = 4: 64 tile lanes in
+    gn_bwd_coef_kernel), 2048 (cg = 64, the widest group it sums itself) and 2112 at 8 x 8 (slab_reduce); fp32 and bf16.  The
+    reference mirrors the kernel's mask (relu6_mask_ref) and its rounding of dz to T: autograd's dz is first checked against the
+    kernel's under BAR_DW_BWD (worst 2.95 fp32, 0.16 bf16), then replaced by it, the values every later stage reads.  Measured worst
+    ratio (MI355X, seeds 0..2) over dgamma / dbeta / ds / df / dh1: 2.04 fp32, 0.98 bf16; bar GN_BAR = 20."""
+    L = N.lib()
+    H, W, tx, C = case
+    B, P = 3, H * W
+    g = R.seeded(SEED0, "norm2", case, dtype)
+    h1 = _rt(torch.randn(B, H, W, C, generator=g) * 1.3 + 0.4, dtype)
+    gamma, beta = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.5 + 0.8
+    s, f = torch.randn(B, C, generator=g) * 0.3, torch.randn(B, C, generator=g) * 0.3
+    da3 = _rt(torch.randn(B, H, W, C, generator=g), dtype)
+    gate, dmean = torch.rand(B, C, generator=g) * 0.9 + 0.05, torch.randn(B, C, generator=g) * 0.1
+    w = torch.randn(9, C, generator=g) / 3                 # the forward taps; the kernel is given them in reverse order
+    x = h1.view(B, P, C)
+    mean_f, rstd_f, G_f, scale, shift = _gn_record(x, gamma, beta, s, f)
+    filmt = torch.full((B, 2 * C + 6), CANARY)
+    filmt[:, :C], filmt[:, C:2 * C] = s, f
+    d = lambda t: t.contiguous().to(dev)  # noqa: E731
+    dd = [d(t) for t in (da3, gate, dmean, w.flip(0), h1, scale, shift)]
+    rec = {k: d(v) for k, v in dict(mean=mean_f, rstd=rstd_f, gamma=gamma, beta=beta, film=filmt).items()}
+    nt = int(L.llie_dwconv3x3_tiles(H, W))
+    results = []
+    for _ in range(2):
+        dzg, slab, _ = _dwb_call(dev, dtype, dd, B, H, W, C)
+        dz_k = dzg.cpu("dz")
+        dgam, dbet = Guarded((C,), dev), Guarded((C,), dev)
+        dfl = torch.full((B, 2 * C + 6), CANARY, device=dev)
+        dfl[:, :2 * C] = NAN
+        scr = Guarded((7 * B * C,), dev)
+        A = N.GnBackwardArgs()
+        A.g, A.dz, A.x0, A.c0, A.c1 = dzg.ptr, dzg.ptr, dd[4].data_ptr(), C, 0
+        A.scale, A.shift, A.act = dd[5].data_ptr(), dd[6].data_ptr(), 1
+        A.mean, A.rstd, A.gamma, A.beta = (rec[k].data_ptr() for k in ("mean", "rstd", "gamma", "beta"))
+        A.film, A.film_stride, A.dfilm, A.dfilm_stride = rec["film"].data_ptr(), 2 * C + 6, dfl.data_ptr(), 2 * C + 6
+        A.dgamma, A.dbeta, A.dx0, A.batch, A.pixels = dgam.ptr, dbet.ptr, dzg.ptr, B, P
+        N.check(L.llie_groupnorm_backward_from_slab(dtype, ctypes.byref(A), slab.ptr, nt, scr.ptr, 7 * B * C, _st()), "groupnorm_backward_from_slab")
+        torch.cuda.synchronize()
+        scr.cpu("gn scratch")
+        _split(slab.cpu("dw_bwd slab"), B, nt, "dw_bwd slab")
+        results.append(dict(dz=dz_k, dx=dzg.cpu("dh1").view(B, P, C), dgamma=dgam.cpu("dgamma"), dbeta=dbet.cpu("dbeta"), dfilm=dfl.cpu()))
+    for k in results[0]:
+        _same(results[0][k], results[1][k], k)
+    res = results[0]
+    assert (res["dfilm"][:, 2 * C:] == CANARY).all()
+    # float64 autograd of the whole chain; the mask and dz as the kernel rounds them
+    wt = R.dw_weights(dtype, w)
+    cot, _ = R.dw_operand(dtype, da3, gate, dmean, no_act=True)
+    mask, unsure = R.relu6_mask_ref(h1, scale, shift)
+    assert R.mask_unsure_ok(unsure, tx)
+    n, leaves = _gn_forward64(x, gamma, beta, s, f, mean_f, rstd_f)
+    seen = {}
+
+    def swap(grad):
+        seen["dz"] = grad.detach()
+        return res["dz"].double().view(B, P, C)
+    n.register_hook(swap)
+    zc = (x.double() * scale.double()[:, None, :] + shift.double()[:, None, :]).float().double()
+    a2 = n * mask.view(B, P, C).double() + 6.0 * (zc >= 6.0).double()
+    y, _ = R.dw_from_padded(R.pad_zero(a2.view(B, H, W, C)), wt)
+    gx, ggam, gbet, gs_, gf_ = torch.autograd.grad(y, leaves, cot)
+    tag = f"norm2/{H}x{W}x{C}/dt{dtype}"
+    ref, rab, rsl, _ = R.dwconv3x3_bwd_ref(dtype, *[da3, gate, dmean, w.flip(0), h1, scale, shift])
+    sure = (~unsure).double()
+    assert ((seen["dz"].view(B, H, W, C) - ref).abs() * sure <= 1e-12 * (rab + 1e-30)).all(), "autograd's dz and dwconv3x3_bwd_ref disagree"
+    _ratio(res["dz"], ref, rab, rsl, R.BAR_DW_BWD, tag + "/dz")
+    ab = _gn_abs_sums(res["dz"].double().view(B, P, C), x, mean_f, rstd_f, G_f, gamma, beta, s)
+    _ratio(res["dgamma"], ggam, ab["dgamma"], _ulp(ggam, 0), GN_BAR, tag + "/dgamma")
+    _ratio(res["dbeta"], gbet, ab["dbeta"], _ulp(gbet, 0), GN_BAR, tag + "/dbeta")
+    _ratio(res["dfilm"][:, :C], gs_, ab["ds"], _ulp(gs_, 0), GN_BAR, tag + "/ds")
+    _ratio(res["dfilm"][:, C:2 * C], gf_, ab["df"], _ulp(gf_, 0), GN_BAR, tag + "/df")
+    _ratio(res["dx"], gx, ab["dx"], _ulp(gx, dtype), GN_BAR, tag + "/dh1")
+
+
+def test_groupnorm_backward_from_slab_refusals(dev):
+    """No activation, dz that is not g, a NULL slab, no tiles, a short scratch: LLIE_ERR_ARG before any HIP call."""
+    L = N.lib()
+    t = torch.zeros(2 * 64 * 64, device=dev)
+    p = t.data_ptr()
+
+    def call(slab=p, ntiles=1, nscr=7 * 2 * 64, **kw):
+        A = N.GnBackwardArgs()
+        for k, v in dict(g=p, dz=p, x0=p, c0=64, scale=p, shift=p, act=1, mean=p, rstd=p, gamma=p, beta=p, dgamma=p, dbeta=p, dx0=p,
+                         batch=2, pixels=64).items():
+            setattr(A, k, v)
+        for k, v in kw.items():
+            setattr(A, k, v)
+        return L.llie_groupnorm_backward_from_slab(1, ctypes.byref(A), slab, ntiles, p, nscr, _st())
+    for kw in (dict(act=0), dict(dz=p + 64), dict(slab=None), dict(ntiles=0), dict(nscr=7 * 2 * 64 - 1), dict(g=None)):
+        assert call(**kw) == N.ERR_ARG, kw
+
+
+# =============================================================================================
+# llie_bias_grad: bwd_mask_reduce without activation or x, slab_reduce of the first of its two planes, batch_sum of Cstore < C columns
+BIAS_CASES = [(3, 64, 32, 3), (3, 81, 64, 64), (2, 1296, 96, 64)]  # (B, P, C, Cstore): packed d(eps); ragged tiles; C % 64 != 0, 21 tiles
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("B,P,C,Cstore", BIAS_CASES)
+def test_bias_grad_vs_float64(dev, B, P, C, Cstore, dtype):
+    """llie_bias_grad, the chain Back::bias_grad runs for the conv biases: (M, C, P, Cstore) = (3 * 64, 32, 64, 3), the packed d(eps)
+    of the output head; (3 * 81, 64, 81, 64), a partly empty last tile; (2 * 1296, 96, 1296, 64), C not a multiple of the 64-channel
+    block and more tiles than slab_reduce's 16 groups.  Columns Cstore.. of out must stay untouched (canary), the scratch sized by
+    llie_bias_grad_floats is not overrun.  Measured worst ratio (MI355X, seeds 0..2): 0.36 fp32, 0.32 fp16, 0.18 bf16; bar
+    BAR_BIAS_GRAD = 3.6."""
+    L = N.lib()
+    g = _rt(torch.randn(B * P, C, generator=R.seeded(SEED0, "bias", B, P, C, dtype)) + 0.2, dtype)
+    gd = g.to(dev)
+    ns, nS = ctypes.c_int64(), ctypes.c_int64()
+    N.check(L.llie_bias_grad_floats(B, C, P, ctypes.byref(ns), ctypes.byref(nS)), "bias_grad_floats")
+    assert (ns.value, nS.value) == (B * ((P + 63) // 64) * 2 * C, B * C)
+    outs = []
+    for _ in range(2):
+        slab, S = Guarded((ns.value,), dev), Guarded((nS.value,), dev)
+        out = torch.full((C + 8,), CANARY, device=dev)
+        out[:Cstore] = NAN
+        N.check(L.llie_bias_grad(dtype, gd.data_ptr(), B * P, C, P, Cstore, slab.ptr, S.ptr, out.data_ptr(), _st()), "bias_grad")
+        torch.cuda.synchronize()
+        slab.cpu("bias_grad slab"), S.cpu("bias_grad S")
+        outs.append(out.cpu())
+    _same(outs[0], outs[1], "bias_grad")
+    assert (outs[0][Cstore:] == CANARY).all(), "bias_grad wrote past out[Cstore]"
+    ref, ab, sl = R.bias_grad_ref(g, Cstore)
+    _ratio(outs[0][:Cstore], ref, ab, sl, R.BAR_BIAS_GRAD, f"bias_grad/{B}x{P}x{C}/dt{dtype}")
+
+
+# =============================================================================================
+# pack_planes, add_into, the four pointwise fp32 kernels
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("c0,c1", [(3, 3), (3, 0), (4, 2)])
+def test_pack_planes_exact(dev, c0, c1, dtype):
+    """llie_pack_planes: two 3-channel halves (the input conv's operand), one (the packed d(eps)) and unequal halves (4 + 2: x1 has its
+    own plane stride), B = 3, P = 100 (the last workgroup is partial): equal bits with the rounded planes, channels c0 + c1 .. 31 zero,
+    nothing past the last row."""
+    L = N.lib()
+    B, P = 3, 100
+    g = R.seeded(SEED0, "pack", c0, c1, dtype)
+    x0 = torch.randn(B, c0, P, generator=g)
+    x1 = torch.randn(B, c1, P, generator=g) if c1 else None
+    x0d, x1d = x0.to(dev), (x1.to(dev) if c1 else None)
+    outs = []
+    for _ in range(2):
+        out = Guarded((B * P, 32), dev, TDT[dtype])
+        N.check(L.llie_pack_planes(dtype, x0d.data_ptr(), c0, x1d.data_ptr() if c1 else None, c1, out.ptr, B, P, _st()), "pack_planes")
+        torch.cuda.synchronize()
+        outs.append(out.cpu("pack_planes"))
+    _same(outs[0], outs[1], "pack_planes")
+    _same(outs[0], R.pack_planes_ref(dtype, x0, x1), "pack_planes against the rounded planes")
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_add_into_exact(dev, dtype):
+    """llie_add_into over n = 8 * 257 elements (a partial last workgroup): dst + src formed in fp32 and rounded once, equal bits."""
+    L = N.lib()
+    n = 8 * 257
+    g = R.seeded(SEED0, "add_into", dtype)
+    a, b = _rt(torch.randn(n, generator=g) * 3, dtype), _rt(torch.randn(n, generator=g), dtype)
+    bd = b.to(dev)
+    outs = []
+    for _ in range(2):
+        dst = Guarded((n,), dev, TDT[dtype])
+        dst.v.copy_(a.to(dev))
+        N.check(L.llie_add_into(dtype, dst.ptr, bd.data_ptr(), n, _st()), "add_into")
+        torch.cuda.synchronize()
+        outs.append(dst.cpu("add_into"))
+    _same(outs[0], outs[1], "add_into")
+    _same(outs[0], R.add_into_ref(dtype, a, b), "add_into against the fp32 sum")
+    assert L.llie_add_into(dtype, bd.data_ptr(), bd.data_ptr(), n + 1, _st()) == N.ERR_ARG
+
+
+@pytest.mark.parametrize("kind", [N.PW_SIGMOID_BWD, N.PW_RELU6_BWD, N.PW_SILU_BWD, N.PW_SCALE])
+def test_pointwise_backward_vs_float64(dev, kind):
+    """llie_pointwise_backward, n = 1000 (a partial last workgroup): sigmoid' from the gate; ReLU6' from the activation's output with y
+    exactly 0 and exactly 6 among the values (both masked); SiLU' with |x| up to 20; the row scale.  ReLU6' and the scale must give
+    equal bits.  Measured worst ratio (MI355X, seeds 0..2): sigmoid' 0.67, SiLU' 0.55; bar BAR_PW_BWD = 6.7."""
+    L = N.lib()
+    n = 1000
+    g = R.seeded(SEED0, "pointwise", kind)
+    a = torch.randn(n, generator=g)
+    if kind == N.PW_SIGMOID_BWD:
+        b = torch.sigmoid(torch.randn(n, generator=g) * 3)
+    elif kind == N.PW_RELU6_BWD:
+        b = (torch.randn(n, generator=g) * 3 + 3).clamp(0.0, 6.0)
+        b[:4] = torch.tensor([0.0, 6.0, 1e-30, 6.0 - 2.0 ** -21])
+        assert (b == 0).sum() > 4 and (b == 6).sum() > 4
+    elif kind == N.PW_SILU_BWD:
+        b = (torch.rand(n, generator=g) * 2 - 1) * 20
+        b[:2] = torch.tensor([-20.0, 20.0])
+    else:
+        b = None
+    scale = 1.0 / 324.0
+    ad, bd = a.to(dev), (b.to(dev) if b is not None else None)
+    outs = []
+    for _ in range(2):
+        out = Guarded((n,), dev)
+        N.check(L.llie_pointwise_backward(kind, ad.data_ptr(), bd.data_ptr() if b is not None else None, out.ptr, n, scale, _st()), "pointwise_backward")
+        torch.cuda.synchronize()
+        outs.append(out.cpu("pointwise"))
+    _same(outs[0], outs[1], "pointwise")
+    ref, ab = R.pointwise_bwd_ref(kind, a, b, scale)
+    if ab is None:
+        _same(outs[0], ref.float(), f"pointwise kind {kind}")
+    else:
+        _ratio(outs[0], ref, ab, _ulp(ref, 0), R.BAR_PW_BWD, f"pointwise/kind{kind}")
+    assert L.llie_pointwise_backward(4, ad.data_ptr(), ad.data_ptr(), ad.data_ptr(), n, 1.0, _st()) == N.ERR_ARG
+    assert L.llie_pointwise_backward(0, ad.data_ptr(), None, ad.data_ptr(), n, 1.0, _st()) == N.ERR_ARG
+
+
+# =============================================================================================
+# the sinusoidal embedding and the time MLP
+def test_sin_embed_and_time_embed_vs_float64(dev):
+    """llie_time_embed on a `small` context (base_channels 32, time_embed_dim 128) with synthetic weights, t = 0, 1, 500, 999: emb against
+    float64 cos / sin of the fp32 product float(t) * freqs[i]; temb and silu_temb against the float64 MLP of the kernel's own emb;
+    llie_sin_embed with the same frequency table gives the bits of emb.  Measured worst ratio (MI355X, seeds 0..2): emb 0.00 (inside the
+    ulp of the stored value; BAR_SIN_EMBED = 2 is reasoned, see kernel_refs.py), temb 0.68, silu_temb 0.53; bar BAR_TIME_EMBED = 6.8."""
+    L = N.lib()
+    Um = importlib.import_module("cv-diffusion-model_amd.unet")
+    h = N.Handle(Um.create_efficient_unet("small", 64)._make_cfg(0))
+    try:
+        g = R.seeded(SEED0, "time_embed")
+        names = [k for k, _ in h.params()]
+        params = [(torch.randn(shape, generator=g) / math.sqrt(max(1, shape[-1] if len(shape) > 1 else 1))) for _, shape in h.params()]
+        pd = [p.to(dev) for p in params]
+        h.load_all(pd, _st())
+        by = {k: p for k, p in zip(names, params)}
+        w1, b1, w3, b3 = (next(v for k, v in by.items() if k.endswith(sfx)) for sfx in
+                          ("time_mlp.1.weight", "time_mlp.1.bias", "time_mlp.3.weight", "time_mlp.3.bias"))
+        dim, T = w1.shape[1], w1.shape[0]
+        assert (dim, T) == (32, 128)
+        t = torch.tensor([0, 1, 500, 999], dtype=torch.int64)
+        td, rows = t.to(dev), 4
+        freqs = R.sin_freqs(dim)
+        fd = freqs.to(dev)
+        runs = []
+        for _ in range(2):
+            emb, temb, st, emb2 = (Guarded((rows, k), dev) for k in (dim, T, T, dim))
+            N.check(L.llie_time_embed(h.h, td.data_ptr(), rows, emb.ptr, temb.ptr, st.ptr, _st()), "time_embed")
+            N.check(L.llie_sin_embed(td.data_ptr(), fd.data_ptr(), emb2.ptr, rows, dim, _st()), "sin_embed")
+            torch.cuda.synchronize()
+            runs.append([b.cpu("time_embed") for b in (emb, temb, st, emb2)])
+        for a, b in zip(runs[0], runs[1]):
+            _same(a, b, "time_embed")
+        emb, temb, st, emb2 = runs[0]
+        _same(emb2, emb, "sin_embed against time_embed's emb_out")
+        ref, ab, sl = R.sin_embed_ref(t, freqs)
+        _ratio(emb, ref, ab, sl, R.BAR_SIN_EMBED, "sin_embed")
+        (tr, ta, tsl), (sr, sa, ssl) = R.time_embed_ref(emb, w1, b1, w3, b3)
+        _ratio(temb, tr, ta, tsl, R.BAR_TIME_EMBED, "time_embed/temb")
+        _ratio(st, sr, sa, ssl, R.BAR_TIME_EMBED, "time_embed/silu_temb")
+        assert L.llie_sin_embed(td.data_ptr(), fd.data_ptr(), None, rows, dim, _st()) == N.ERR_ARG
+        assert L.llie_sin_embed(td.data_ptr(), fd.data_ptr(), fd.data_ptr(), rows, 31, _st()) == N.ERR_ARG
+    finally:
+        h.close()

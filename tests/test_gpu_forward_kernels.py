@@ -217,11 +217,7 @@ def test_pw_gemm_refusals(dev):
 
 # =============================================================================================
 # llie_dwconv3x3_ex (dwconv.hip): strip widths, the ragged kernel, flags, pooling outputs, strip heights
-# (H, W, TX, ragged): TX = the strip width launch_dw_t takes; non-square maps both ways round.  13 x 24: ragged rows on a width that
-# is 8 (mod 16) -- the ragged kernel has no 8-wide form and runs 16-wide strips, and llie_dwconv3x3_tiles must count those
-DW_MAPS = [(8, 24, 8, False), (16, 8, 8, False), (8, 40, 8, False), (16, 16, 16, False), (8, 48, 16, False), (16, 32, 32, False),
-           (8, 64, 32, False), (9, 13, 16, True), (13, 9, 16, True), (13, 12, 16, True), (25, 18, 32, True), (18, 25, 32, True),
-           (9, 20, 32, True), (25, 50, 32, True), (25, 32, 32, True), (9, 16, 16, True), (13, 24, 16, True)]
+DW_MAPS = R.DW_MAPS  # (H, W, TX, ragged); the backward test runs the same maps
 DW_FLAGS = {"act": 0, "s6": 1, "noact": 2}
 
 
