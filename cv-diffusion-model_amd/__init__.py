@@ -21,7 +21,8 @@ from .ops import register_model
 from .hostio import (load_checkpoint, extract_state_dict, preprocess_array, postprocess_array, resize_bilinear,
                      preprocess_device, postprocess_device)
 from .tiling import (tile_origins, gather_tiles_array, blend_tiles_array, gather_tiles_device, gather_noise_device,
-                     blend_tiles_device, enhance_tiled)
+                     blend_tiles_device, enhance_tiled, frame_pad, frame_load_array, frame_store_array, frame_load_device,
+                     frame_store_device, enhance_frame_u8)
 from .data import (DeviceFrameStore, DevicePairLoader, create_device_dataloaders, epoch_plan, augment_pairs_host, augment_synth_host,
                    augment_pairs_device, augment_synth_device)
 from .metrics import ImageMetrics, image_metrics, image_metrics_host, evaluate, evaluate_full_resolution
@@ -35,7 +36,7 @@ __all__ = [
     "all_gather_batch", "all_reduce_gradients", "FusedAdamW", "FusedGradScaler", "TrainStep", "DistillStep", "register_model", "build_library", "library_path", "load_checkpoint", "extract_state_dict",
     "preprocess_array", "postprocess_array", "resize_bilinear", "preprocess_device", "postprocess_device",
     "tile_origins", "gather_tiles_array", "blend_tiles_array", "gather_tiles_device", "gather_noise_device", "blend_tiles_device",
-    "enhance_tiled",
+    "enhance_tiled", "frame_pad", "frame_load_array", "frame_store_array", "frame_load_device", "frame_store_device", "enhance_frame_u8",
     "DeviceFrameStore", "DevicePairLoader", "create_device_dataloaders", "epoch_plan", "augment_pairs_host", "augment_synth_host",
     "augment_pairs_device", "augment_synth_device",
     "ImageMetrics", "image_metrics", "image_metrics_host", "evaluate", "evaluate_full_resolution",

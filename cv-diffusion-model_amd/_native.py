@@ -44,6 +44,8 @@ EXPORTS = [
     "llie_dwconv3x3_ex", "llie_dwconv3x3_strip_rows", "llie_last_kernel",
     "llie_init_conv", "llie_init_conv_tiles", "llie_init_conv_pack_bytes", "llie_final_conv", "llie_final_conv_pack_bytes",
     "llie_se_gate", "llie_affine_add", "llie_nchw_to_nhwc", "llie_nhwc_to_nchw", "llie_pw_gemm_dot",
+    "llie_frame_shape_ok", "llie_frame_workspace_bytes", "llie_unet_forward_hw", "llie_enhance_hw",
+    "llie_frame_pad", "llie_frame_load_u8", "llie_frame_store_u8",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 PW_SIGMOID_BWD, PW_RELU6_BWD, PW_SILU_BWD, PW_SCALE = 0, 1, 2, 3  # llie_pointwise_kind
@@ -165,6 +167,14 @@ def lib() -> C.CDLL:
     L.llie_tile_gather_u8.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp]
     L.llie_tile_gather_f32.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]
     L.llie_tile_blend_u8.argtypes = [vp, ci, ci, ci, ci, vp, vp]
+    L.llie_frame_shape_ok.argtypes = [vp, ci, ci, ci]
+    L.llie_frame_workspace_bytes.argtypes = [vp, ci, ci, ci, ci]
+    L.llie_frame_workspace_bytes.restype = i64
+    L.llie_unet_forward_hw.argtypes = [vp, vp, vp, vp, ci, vp, ci, ci, ci, vp, i64, vp]
+    L.llie_enhance_hw.argtypes = [vp, vp, vp, vp, C.POINTER(StepCoef), ci, vp, vp, vp, ci, ci, ci, vp, i64, vp]
+    L.llie_frame_pad.argtypes = [ci]
+    L.llie_frame_load_u8.argtypes = [vp, ci, ci, vp, vp]
+    L.llie_frame_store_u8.argtypes = [vp, ci, ci, vp, vp]
     L.llie_aug_pair_u8.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp]
     L.llie_aug_synth_u8.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]
     L.llie_image_metrics_scratch_bytes.argtypes = [ci, ci, ci]
@@ -376,6 +386,16 @@ class Handle:
         n = self._L.llie_enhance_workspace_bytes(self.h, batch, max_steps)
         if n < 0:
             check(int(n), "llie_enhance_workspace_bytes")
+        return int(n)
+
+    def frame_shape_ok(self, batch: int, h: int, w: int) -> None:
+        """Raises ValueError naming the rule of llie_frame_shape_ok that (batch, h, w) breaks."""
+        check(self._L.llie_frame_shape_ok(self.h, batch, h, w), "frame shape")
+
+    def frame_workspace_bytes(self, batch: int, h: int, w: int, max_steps: int = 0) -> int:
+        n = self._L.llie_frame_workspace_bytes(self.h, batch, h, w, max_steps)
+        if n < 0:
+            check(int(n), "llie_frame_workspace_bytes")
         return int(n)
 
     def algorithmic_bytes(self, batch: int) -> int:

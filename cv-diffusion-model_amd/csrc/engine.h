@@ -225,7 +225,7 @@ struct llie_ctx {
   static constexpr size_t kMaxGraphs = 16;
   uint64_t graph_clock = 0;
   std::map<std::string, GraphEntry> graphs;
-  std::map<std::tuple<int, int64_t, int>, size_t> zneed;  // (batch, pixels, knob epoch) -> bytes of zero-initialised totals one forward takes (Run::zbegin)
+  std::map<std::tuple<int, int, int, int>, size_t> zneed;  // (batch, height, width, knob epoch) -> bytes of zero-initialised totals one forward takes (Run::zbegin)
   hipStream_t cap_stream = nullptr;  // side stream used only to record captures (the legacy null stream cannot capture)
   // backward pass: weight-gradient kernels run on this stream next to the activation-gradient chain (Back::fork/join)
   hipStream_t side_stream = nullptr;
@@ -359,7 +359,11 @@ int run_module(Exec x, Tape* tape, const float* in, const float* temb, float* y,
 // scheduler step fused into the final conv's epilogue (2-byte compute dtypes only)
 struct FusedStep { StepCoef coef; const float* noise; float* prev; float* clamped; };
 int unet_forward_impl(llie_ctx* c, const float* lat, const float* cond, const int64_t* t, int uniform_t, float* eps,
-                      const FusedStep* fs, int batch, void* ws, int64_t ws_bytes, llie_stream stream);
+                      const FusedStep* fs, int batch, int H, int W, void* ws, int64_t ws_bytes, llie_stream stream);
+// forward.cpp: the frame rule of llie_frame_shape_ok, and the workspace of `max_steps` steps of the loop at H x W without that
+// check (0: plain launches, no staging area) -- the entry points at image_size go through it unchecked, as they always did
+int frame_shape_ok(const llie_ctx* c, int batch, int H, int W);
+int64_t frame_workspace(llie_ctx* c, int batch, int H, int W, int max_steps);
 // HIP status of a kernel-level entry point -> return code and llie_last_error() text.  hipErrorInvalidValue is how a launcher
 // refuses its arguments: `refuse_rc` with "<what>: <refuse_msg>" (no text when refuse_msg is null)
 int kerr(const char* what, hipError_t e, int refuse_rc = LLIE_ERR_SHAPE, const char* refuse_msg = "shape outside the kernel contract");

@@ -23,14 +23,13 @@ int llie_add_noise(const float* x0, const float* noise, const int64_t* t, const 
 // (UNet forward, scheduler step).  `base` holds two latent ping-pong images and one eps image,
 // followed by the UNet workspace.
 // `step_batch`: images per step in the noise / inter / preds / timestep arrays (>= batch when this call handles a
-// slice of a larger batch; 0 = batch)
+// slice of a larger batch; 0 = batch).  Every image is H x W.
 static int enhance_sequence(llie_ctx* c, const float* low, const float* noise, const int64_t* t_dev,
                             const llie_step_coef* coefs, int steps, float* enhanced, float* inter, float* preds,
-                            int batch, char* base, int64_t ws_bytes, llie_stream stream, int step_batch = 0) {
-  const int S = c->cfg.image_size;
-  const int64_t n = (int64_t)batch * 3 * S * S;
+                            int batch, int H, int W, char* base, int64_t ws_bytes, llie_stream stream, int step_batch = 0) {
+  const int64_t n = (int64_t)batch * 3 * H * W;
   if (step_batch <= 0) step_batch = batch;
-  const int64_t sn = (int64_t)step_batch * 3 * S * S;  // elements between consecutive steps
+  const int64_t sn = (int64_t)step_batch * 3 * H * W;  // elements between consecutive steps
   const size_t img = align_up((size_t)n * 4, 256);
   float* lat[2] = {reinterpret_cast<float*>(base), reinterpret_cast<float*>(base + img)};
   float* eps_ws = reinterpret_cast<float*>(base + 2 * img);
@@ -49,11 +48,11 @@ static int enhance_sequence(llie_ctx* c, const float* low, const float* noise, c
                                  coefs[i].is_last, coefs[i].v_prediction, coefs[i].clamp_x0},
                         nz, prev, last ? enhanced : nullptr};
       rc = unet_forward_impl(c, cur, low, t_dev + (size_t)i * step_batch, 1, preds ? preds + (size_t)i * sn : nullptr, &fs, batch,
-                             uws, uws_bytes, stream);
+                             H, W, uws, uws_bytes, stream);
       if (rc) return rc;
     } else {
       float* eps = preds ? preds + (size_t)i * sn : eps_ws;
-      rc = llie_unet_forward(c, cur, low, t_dev + (size_t)i * step_batch, 1, eps, batch, uws, uws_bytes, stream);
+      rc = unet_forward_impl(c, cur, low, t_dev + (size_t)i * step_batch, 1, eps, nullptr, batch, H, W, uws, uws_bytes, stream);
       if (rc) return rc;
       rc = llie_lcm_step(eps, cur, nz, prev, nullptr, last ? enhanced : nullptr, n, &coefs[i], stream);
       if (rc) return rc;
@@ -63,13 +62,13 @@ static int enhance_sequence(llie_ctx* c, const float* low, const float* noise, c
   return LLIE_OK;
 }
 
-int llie_enhance(llie_ctx* c, const float* low, const float* noise, const int64_t* t_dev, const llie_step_coef* coefs,
-                 int steps, float* enhanced, float* inter, float* preds, int batch, void* ws, int64_t ws_bytes,
-                 llie_stream stream) {
+// llie_enhance (H = W = image_size) and llie_enhance_hw
+static int enhance_impl(llie_ctx* c, const float* low, const float* noise, const int64_t* t_dev, const llie_step_coef* coefs,
+                        int steps, float* enhanced, float* inter, float* preds, int batch, int H, int W, void* ws, int64_t ws_bytes,
+                        llie_stream stream) {
   if (!c || !low || !noise || !t_dev || !coefs || !enhanced || !ws || steps <= 0 || batch <= 0 || c->cfg.kind != LLIE_UNET)
     return LLIE_ERR_ARG;
-  const int S = c->cfg.image_size;
-  const int64_t n = (int64_t)batch * 3 * S * S;
+  const int64_t n = (int64_t)batch * 3 * H * W;
   const size_t img = align_up((size_t)n * 4, 256);
   if ((int64_t)(3 * img) > ws_bytes) { set_err("workspace too small"); return LLIE_ERR_WORKSPACE; }
   char* base = reinterpret_cast<char*>(ws);
@@ -86,12 +85,12 @@ int llie_enhance(llie_ctx* c, const float* low, const float* noise, const int64_
   const size_t tbytes = align_up((size_t)steps * batch * 8, 256);
   const size_t stage = (n_in + n_out) * img + tbytes;
   const int64_t seq_bytes = ws_bytes - (int64_t)stage;
-  bool use_graph = !no_graph && c->prof_mask == 0 && seq_bytes >= llie_workspace_bytes(c, batch, 0, 0);
-  if (!use_graph) return enhance_sequence(c, low, noise, t_dev, coefs, steps, enhanced, inter, preds, batch, base, ws_bytes, stream);
+  bool use_graph = !no_graph && c->prof_mask == 0 && seq_bytes >= frame_workspace(c, batch, H, W, 0);
+  if (!use_graph) return enhance_sequence(c, low, noise, t_dev, coefs, steps, enhanced, inter, preds, batch, H, W, base, ws_bytes, stream);
 
   std::string key(reinterpret_cast<const char*>(coefs), sizeof(llie_step_coef) * steps);
   char tail[128];
-  snprintf(tail, sizeof tail, "|%d|%d|%d|%d|%p|%lld|%d|%d", batch, steps, inter ? 1 : 0, preds ? 1 : 0, ws, (long long)ws_bytes,
+  snprintf(tail, sizeof tail, "|%d|%dx%d|%d|%d|%d|%p|%lld|%d|%d", batch, H, W, steps, inter ? 1 : 0, preds ? 1 : 0, ws, (long long)ws_bytes,
            g_knobs.enhance_split, g_knobs.epoch);
   key += tail;
   if (c->graphs.find(key) == c->graphs.end() && c->graphs.size() >= llie_ctx::kMaxGraphs) {  // evict the least recently used entry
@@ -107,7 +106,7 @@ int llie_enhance(llie_ctx* c, const float* low, const float* noise, const int64_
   ge.used = ++c->graph_clock;
   if (!ge.seen) {
     ge.seen = true;
-    return enhance_sequence(c, low, noise, t_dev, coefs, steps, enhanced, inter, preds, batch, base, ws_bytes, stream);
+    return enhance_sequence(c, low, noise, t_dev, coefs, steps, enhanced, inter, preds, batch, H, W, base, ws_bytes, stream);
   }
   // staging area at the tail of the workspace
   char* st = base + seq_bytes;
@@ -118,7 +117,7 @@ int llie_enhance(llie_ctx* c, const float* low, const float* noise, const int64_
   float* s_preds = preds ? reinterpret_cast<float*>(st + (n_in + 1 + (inter ? steps : 0)) * img) : nullptr;
   int64_t* s_t = reinterpret_cast<int64_t*>(st + (n_in + n_out) * img);
   // NB: staged noise / inter / preds are step-major with stride `img` >= n*4; keep them dense (img == n*4 when n*4 % 256 == 0)
-  if (img != (size_t)n * 4) return enhance_sequence(c, low, noise, t_dev, coefs, steps, enhanced, inter, preds, batch, base, ws_bytes, stream);
+  if (img != (size_t)n * 4) return enhance_sequence(c, low, noise, t_dev, coefs, steps, enhanced, inter, preds, batch, H, W, base, ws_bytes, stream);
   hipError_t e = hipMemcpyAsync(s_low, low, (size_t)n * 4, hipMemcpyDeviceToDevice, us);
   if (e == hipSuccess) e = hipMemcpyAsync(s_noise, noise, (size_t)n * 4 * steps, hipMemcpyDeviceToDevice, us);
   if (e == hipSuccess) e = hipMemcpyAsync(s_t, t_dev, (size_t)steps * batch * 8, hipMemcpyDeviceToDevice, us);
@@ -142,7 +141,7 @@ int llie_enhance(llie_ctx* c, const float* low, const float* noise, const int64_
     size_t wtot = 0;
     for (int i = 0; i < nbr; ++i) {
       hb[i] = batch / nbr + (i < batch % nbr ? 1 : 0);
-      wsz[i] = llie_workspace_bytes(c, hb[i], 0, 0);
+      wsz[i] = frame_workspace(c, hb[i], H, W, 0);
       if (wsz[i] <= 0) { nbr = 1; break; }
       woff[i] = wtot;
       wtot += align_up((size_t)wsz[i], 256);
@@ -161,10 +160,10 @@ int llie_enhance(llie_ctx* c, const float* low, const float* noise, const int64_
                               set_err("enhance split: %s", hipGetErrorString(e2)); return (int)e2; }
       size_t img0 = 0;  // first image of the branch
       for (int i = 0; i < nbr; ++i) {
-        const size_t off = img0 * 3 * S * S;
+        const size_t off = img0 * 3 * H * W;
         hipStream_t bs = i == 0 ? c->cap_stream : c->branch_stream[i];
         const int rci = enhance_sequence(c, s_low + off, s_noise + off, s_t + img0, coefs, steps, s_enh + off, s_inter ? s_inter + off : nullptr,
-                                         s_preds ? s_preds + off : nullptr, hb[i], base + woff[i], wsz[i], reinterpret_cast<llie_stream>(bs), batch);
+                                         s_preds ? s_preds + off : nullptr, hb[i], H, W, base + woff[i], wsz[i], reinterpret_cast<llie_stream>(bs), batch);
         if (rc == LLIE_OK) rc = rci;
         img0 += hb[i];
       }
@@ -174,7 +173,7 @@ int llie_enhance(llie_ctx* c, const float* low, const float* noise, const int64_
         if (e2 != hipSuccess && rc == LLIE_OK) { set_err("enhance split join: %s", hipGetErrorString(e2)); rc = (int)e2; }
       }
     } else {
-      rc = enhance_sequence(c, s_low, s_noise, s_t, coefs, steps, s_enh, s_inter, s_preds, batch, base, seq_bytes,
+      rc = enhance_sequence(c, s_low, s_noise, s_t, coefs, steps, s_enh, s_inter, s_preds, batch, H, W, base, seq_bytes,
                             reinterpret_cast<llie_stream>(c->cap_stream));
     }
     hipGraph_t g = nullptr;
@@ -191,6 +190,23 @@ int llie_enhance(llie_ctx* c, const float* low, const float* noise, const int64_
   if (e == hipSuccess && preds) e = hipMemcpyAsync(preds, s_preds, (size_t)n * 4 * steps, hipMemcpyDeviceToDevice, us);
   if (e != hipSuccess) { set_err("enhance graph launch: %s", hipGetErrorString(e)); return (int)e; }
   return LLIE_OK;
+}
+
+int llie_enhance(llie_ctx* c, const float* low, const float* noise, const int64_t* t_dev, const llie_step_coef* coefs,
+                 int steps, float* enhanced, float* inter, float* preds, int batch, void* ws, int64_t ws_bytes,
+                 llie_stream stream) {
+  if (!c) return LLIE_ERR_ARG;
+  return enhance_impl(c, low, noise, t_dev, coefs, steps, enhanced, inter, preds, batch, c->cfg.image_size, c->cfg.image_size, ws, ws_bytes,
+                      stream);
+}
+
+int llie_enhance_hw(llie_ctx* c, const float* low, const float* noise, const int64_t* t_dev, const llie_step_coef* coefs,
+                    int steps, float* enhanced, float* inter, float* preds, int batch, int height, int width, void* ws,
+                    int64_t ws_bytes, llie_stream stream) {
+  if (!c || !low || !noise || !t_dev || !coefs || !enhanced || !ws || steps <= 0 || batch <= 0 || c->cfg.kind != LLIE_UNET)
+    return LLIE_ERR_ARG;
+  const int rc = frame_shape_ok(c, batch, height, width);
+  return rc ? rc : enhance_impl(c, low, noise, t_dev, coefs, steps, enhanced, inter, preds, batch, height, width, ws, ws_bytes, stream);
 }
 
 // number of entries in the context's hipGraph cache (bounded by kMaxGraphs, least recently used evicted)

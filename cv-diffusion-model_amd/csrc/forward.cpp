@@ -11,12 +11,12 @@ struct Run : Exec {
   void rel(size_t off) { if (!tape) ar->free(off); }
   // Zero-initialised totals (inference): fixed-point accumulators that kernels add to with integer atomics (SE pool sums).
   // One block of the arena per forward, cleared by a single memset node at its start and handed out by ztake() in
-  // launch order; its size comes from a counting dry run of the same forward (cached per batch and image size).
+  // launch order; its size comes from a counting dry run of the same forward (cached per batch, height and width).
   size_t zoff = 0, zcur = 0, zcap = 0;
   bool zcount = false;
-  template <typename F> void zbegin(int64_t pixels, F&& forward_again) {
+  template <typename F> void zbegin(int H, int W, F&& forward_again) {
     if (tape || zcount) return;
-    const auto key = std::make_tuple(B, pixels, g_knobs.epoch);
+    const auto key = std::make_tuple(B, H, W, g_knobs.epoch);
     auto it = c->zneed.find(key);
     if (it == c->zneed.end()) {
       size_t zbytes = 0;
@@ -414,13 +414,14 @@ struct Run : Exec {
     return h;
   }
 
-  // EfficientUNet.forward (efficient_unet.py:532-606)
+  // EfficientUNet.forward (efficient_unet.py:532-606) on H x W maps: the network is fully convolutional, so the module tree that
+  // image_size fixed (attention placement) runs at any frame frame_shape_ok accepts; H = W = image_size is the reference's call
   // `fs` (optional): scheduler step fused into the final conv's epilogue (2-byte compute dtypes only)
-  void unet(const float* lat, const float* cond, const int64_t* t, int uniform_t, float* eps, const FusedStep* fs = nullptr) {
+  void unet(const float* lat, const float* cond, const int64_t* t, int uniform_t, float* eps, int H, int W, const FusedStep* fs = nullptr) {
     const llie_config& g = c->cfg;
-    const int S = g.image_size, T = g.time_embed_dim, F = c->film_rows;
+    const int T = g.time_embed_dim, F = c->film_rows;
     const int rows = uniform_t ? 1 : B;
-    zbegin((int64_t)S * S, [&](Run& d) { d.unet(nullptr, nullptr, nullptr, uniform_t, nullptr); });
+    zbegin(H, W, [&](Run& d) { d.unet(nullptr, nullptr, nullptr, uniform_t, nullptr, H, W); });
     const size_t temb = ar->alloc((size_t)rows * T * 4), stemb = ar->alloc((size_t)rows * T * 4);
     const size_t film = ar->alloc((size_t)rows * F * 4);
     if (!dry) {
@@ -436,16 +437,16 @@ struct Run : Exec {
     const float* filmp = p<float>(film);
     const int64_t fstride = uniform_t ? 0 : F;
 
-    Tens h = new_tens(c->channels[0], S, S, init_conv_ntiles(S, S, dt != LLIE_F32), c->channels_r[0]);
+    Tens h = new_tens(c->channels[0], H, W, init_conv_ntiles(H, W, dt != LLIE_F32), c->channels_r[0]);
     if (!dry) {
       InitConvArgs a{};
       const int half = g.in_channels / 2;
       a.x0 = lat; a.x1 = cond; a.c0 = half; a.c1 = g.in_channels - half;
       a.w = wptr<float>(c->init_w); a.bias = wptr<float>(c->init_b); a.out = p(h.off); a.stats = p<float>(h.slab);
       a.wp = dt != LLIE_F32 ? wptr(c->init_wp) : nullptr;
-      a.B = B; a.H = S; a.W = S; a.Cout = c->channels[0];
+      a.B = B; a.H = H; a.W = W; a.Cout = c->channels[0];
       snprintf(tag, sizeof tag, "init_conv");
-      timed(LLIE_K_OTHER, (int64_t)B * S * S * (g.in_channels * 4 + c->channels[0] * (int64_t)es()), [&] { return launch_init_conv(dt, a, s); }, "init_conv_kernel");
+      timed(LLIE_K_OTHER, (int64_t)B * H * W * (g.in_channels * 4 + c->channels[0] * (int64_t)es()), [&] { return launch_init_conv(dt, a, s); }, "init_conv_kernel");
     }
     if (tape) {
       tape->temb = temb; tape->stemb = stemb; tape->film = film; tape->h0 = h;
@@ -477,13 +478,13 @@ struct Run : Exec {
     if (!dry) {
       FinalConvArgs a{};
       a.in = p(h.off); a.as = p<float>(as); a.ab = p<float>(ab); a.w = wptr<float>(c->fin_w); a.bias = wptr<float>(c->fin_bias);
-      a.out = eps; a.B = B; a.H = S; a.W = S; a.C = c->channels[0]; a.Cout = g.out_channels;
+      a.out = eps; a.B = B; a.H = H; a.W = W; a.C = c->channels[0]; a.Cout = g.out_channels;
       a.wp = dt != LLIE_F32 ? wptr(c->fin_wp) : nullptr;
       if (fs) {
         a.fuse_step = 1; a.coef = fs->coef; a.sample = lat; a.noise = fs->noise; a.prev = fs->prev; a.clamped = fs->clamped;
       }
       snprintf(tag, sizeof tag, "final_conv");
-      timed(LLIE_K_OTHER, (int64_t)B * S * S * (c->channels[0] * (int64_t)es() + 3 * 4 * (fs ? 4 : 1)), [&] { return launch_final_conv(dt, a, s); }, "final_conv_kernel");
+      timed(LLIE_K_OTHER, (int64_t)B * H * W * (c->channels[0] * (int64_t)es() + 3 * 4 * (fs ? 4 : 1)), [&] { return launch_final_conv(dt, a, s); }, "final_conv_kernel");
     }
     free_tens(h);
     rel(as); rel(ab);
@@ -495,7 +496,7 @@ struct Run : Exec {
     const llie_config& g = c->cfg;
     const int P = H * W;
     const int split = (g.kind == LLIE_IRB) ? g.base_channels : 0;  // IRB: optional virtual-concat split point
-    zbegin((int64_t)P, [&](Run& d) { d.module(nullptr, nullptr, nullptr, H, W); });
+    zbegin(H, W, [&](Run& d) { d.module(nullptr, nullptr, nullptr, H, W); });
     Tens x0 = new_tens(split ? split : g.in_channels, H, W, P / 64);
     Tens x1;
     if (split) x1 = new_tens(g.in_channels - split, H, W, P / 64);
@@ -555,7 +556,7 @@ struct Run : Exec {
 int llie::run_unet(Exec x, Tape* tape, const float* lat, const float* cond, const int64_t* t, float* eps) {
   Run r{x};
   r.tape = tape;
-  r.unet(lat, cond, t, 0, eps);
+  r.unet(lat, cond, t, 0, eps, x.c->cfg.image_size, x.c->cfg.image_size);
   return r.rc();
 }
 int llie::run_module(Exec x, Tape* tape, const float* in, const float* temb, float* y, int H, int W) {
@@ -566,46 +567,91 @@ int llie::run_module(Exec x, Tape* tape, const float* in, const float* temb, flo
 }
 
 int llie::unet_forward_impl(llie_ctx* c, const float* lat, const float* cond, const int64_t* t, int uniform_t, float* eps,
-                            const FusedStep* fs, int batch, void* ws, int64_t ws_bytes, llie_stream stream) {
+                            const FusedStep* fs, int batch, int H, int W, void* ws, int64_t ws_bytes, llie_stream stream) {
   if (!c || !lat || !cond || !t || (!eps && !fs) || !ws || batch <= 0 || c->cfg.kind != LLIE_UNET) return LLIE_ERR_ARG;
   int rc = check_ready(c);
   if (rc) return rc;
-  rc = fits(Run::plan(c, batch, [&](Run& d) { d.unet(nullptr, nullptr, nullptr, uniform_t, nullptr); }), ws_bytes);
+  rc = fits(Run::plan(c, batch, [&](Run& d) { d.unet(nullptr, nullptr, nullptr, uniform_t, nullptr, H, W); }), ws_bytes);
   if (rc) return rc;
   Arena ar((size_t)ws_bytes);
   Run r{Exec::live(c, &ar, stream, ws, batch)};
-  r.unet(lat, cond, t, uniform_t, eps, fs);
+  r.unet(lat, cond, t, uniform_t, eps, H, W, fs);
   return r.rc();
+}
+
+// The widest tensor one forward stores at full resolution, in channels: what the element cap of frame_shape_ok multiplies
+static int widest_full_res_channels(const llie_ctx* c) {
+  int m = std::max(c->channels[0], c->cfg.in_channels);
+  for (const std::vector<Block>* blocks : {&c->enc[0], &c->dec[3]})
+    for (const Block& b : *blocks) {
+      if (b.kind == 0) m = std::max({m, c->irbs[b.idx].cin, c->irbs[b.idx].hid, c->irbs[b.idx].cout});
+      else m = std::max({m, c->attns[b.idx].c, 3 * c->attns[b.idx].inner});
+    }
+  return m;
+}
+
+int llie::frame_shape_ok(const llie_ctx* c, int batch, int H, int W) {
+  if (!c || c->cfg.kind != LLIE_UNET || batch <= 0) return LLIE_ERR_ARG;
+  if (H % 8 || W % 8 || H < 64 || W < 64) {
+    set_err("frame %dx%d: height and width must be multiples of 8 and at least 64", H, W);
+    return LLIE_ERR_SHAPE;
+  }
+  if (batch > 65535) {
+    set_err("batch %d: at most 65535 frames per call", batch);
+    return LLIE_ERR_SHAPE;
+  }
+  const int cw = widest_full_res_channels(c);
+  if ((long long)batch * H * W * cw > 2147483647ll) {
+    set_err("frame too large: batch %d x %dx%d x %d channels exceeds the element cap 2^31 - 1; use tiles", batch, H, W, cw);
+    return LLIE_ERR_SHAPE;
+  }
+  return LLIE_OK;
+}
+
+// one forward's plan + the latents ping-pong and eps buffers of the loop; max_steps > 0: + the staging area of its hipGraph path
+// (inputs / outputs of up to `max_steps` steps with intermediates and noise predictions)
+int64_t llie::frame_workspace(llie_ctx* c, int batch, int H, int W, int max_steps) {
+  const size_t core = Run::plan(c, batch, [&](Run& d) { d.unet(nullptr, nullptr, nullptr, 0, nullptr, H, W); });
+  const size_t img = align_up((size_t)batch * 3 * H * W * 4, 256);
+  size_t n = core + 3 * img;
+  if (max_steps > 0) n += (2 + 3 * (size_t)max_steps) * img + align_up((size_t)max_steps * batch * 8, 256);
+  return (int64_t)n;
 }
 
 extern "C" {
 
 int64_t llie_workspace_bytes(llie_ctx* c, int batch, int height, int width) {
   if (!c || batch <= 0) return LLIE_ERR_ARG;
-  if (c->cfg.kind == LLIE_UNET) {
-    const size_t core = Run::plan(c, batch, [](Run& d) { d.unet(nullptr, nullptr, nullptr, 0, nullptr); });
-    // + latents ping-pong and eps buffers for llie_enhance
-    const size_t img = align_up((size_t)batch * 3 * c->cfg.image_size * c->cfg.image_size * 4, 256);
-    return (int64_t)(core + 3 * img);
-  }
+  if (c->cfg.kind == LLIE_UNET) return frame_workspace(c, batch, c->cfg.image_size, c->cfg.image_size, 0);
   if (shape_ok(c, height, width) != LLIE_OK) return LLIE_ERR_SHAPE;
   return (int64_t)Run::plan(c, batch, [&](Run& d) { d.module(nullptr, nullptr, nullptr, height, width); });
 }
 
-// Workspace for llie_enhance with room for the hipGraph staging area (inputs/outputs of up to
-// `max_steps` steps with intermediates and noise predictions).
+// Workspace for llie_enhance with room for the hipGraph staging area
 int64_t llie_enhance_workspace_bytes(llie_ctx* c, int batch, int max_steps) {
   if (!c || batch <= 0 || max_steps <= 0 || c->cfg.kind != LLIE_UNET) return LLIE_ERR_ARG;
-  const int64_t core = llie_workspace_bytes(c, batch, 0, 0);
-  if (core < 0) return core;
-  const size_t img = align_up((size_t)batch * 3 * c->cfg.image_size * c->cfg.image_size * 4, 256);
-  return core + (int64_t)((2 + 3 * (size_t)max_steps) * img + align_up((size_t)max_steps * batch * 8, 256));
+  return frame_workspace(c, batch, c->cfg.image_size, c->cfg.image_size, max_steps);
+}
+
+int llie_frame_shape_ok(const llie_ctx* c, int batch, int height, int width) { return frame_shape_ok(c, batch, height, width); }
+
+int64_t llie_frame_workspace_bytes(llie_ctx* c, int batch, int height, int width, int max_steps) {
+  if (max_steps < 0) return LLIE_ERR_ARG;
+  const int rc = frame_shape_ok(c, batch, height, width);
+  return rc ? rc : frame_workspace(c, batch, height, width, max_steps);
 }
 
 int llie_unet_forward(llie_ctx* c, const float* lat, const float* cond, const int64_t* t, int uniform_t, float* eps,
                       int batch, void* ws, int64_t ws_bytes, llie_stream stream) {
+  if (!eps || !c) return LLIE_ERR_ARG;
+  return unet_forward_impl(c, lat, cond, t, uniform_t, eps, nullptr, batch, c->cfg.image_size, c->cfg.image_size, ws, ws_bytes, stream);
+}
+
+int llie_unet_forward_hw(llie_ctx* c, const float* lat, const float* cond, const int64_t* t, int uniform_t, float* eps,
+                         int batch, int height, int width, void* ws, int64_t ws_bytes, llie_stream stream) {
   if (!eps) return LLIE_ERR_ARG;
-  return unet_forward_impl(c, lat, cond, t, uniform_t, eps, nullptr, batch, ws, ws_bytes, stream);
+  const int rc = frame_shape_ok(c, batch, height, width);
+  return rc ? rc : unet_forward_impl(c, lat, cond, t, uniform_t, eps, nullptr, batch, height, width, ws, ws_bytes, stream);
 }
 
 int llie_module_forward(llie_ctx* c, const float* x, const float* temb, float* y, int batch, int H, int W, void* ws,

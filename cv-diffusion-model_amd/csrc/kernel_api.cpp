@@ -502,6 +502,16 @@ int llie_tile_blend_u8(const float* tiles, int H, int W, int S, int v, uint8_t* 
   return kerr("tile_blend_u8", launch_tile_blend_u8(tiles, TilePlan{H, W, S, v, 0, 1}, img, hs(stream)), LLIE_ERR_ARG, nullptr);
 }
 
+int llie_frame_pad(int L) { return L > 0 && L <= (1 << 24) ? frame_pad(L) : LLIE_ERR_ARG; }
+int llie_frame_load_u8(const uint8_t* img, int H, int W, float* out, llie_stream stream) {
+  if (!img || !out) return LLIE_ERR_ARG;
+  return kerr("frame_load_u8", launch_frame_load_u8(img, H, W, out, hs(stream)), LLIE_ERR_ARG, nullptr);
+}
+int llie_frame_store_u8(const float* x, int H, int W, uint8_t* img, llie_stream stream) {
+  if (!x || !img) return LLIE_ERR_ARG;
+  return kerr("frame_store_u8", launch_frame_store_u8(x, H, W, img, hs(stream)), LLIE_ERR_ARG, nullptr);
+}
+
 static_assert(sizeof(llie_aug_row) == sizeof(AugRow) && sizeof(AugRow) == 48, "llie_aug_row and AugRow are one layout");
 static AugArgs aug_args(const uint8_t* pool, const int64_t* table, int N, const llie_aug_row* plan, int first, int count, int S, const float* z,
                         float* low, float* high, uint8_t* low_u8, uint8_t* high_u8) {

@@ -586,6 +586,14 @@ hipError_t launch_tile_gather_f32(const float* canvas, int planes, const TilePla
 // (r + 1) * 127.5 clipped and truncated; one thread per 4 output pixels, no atomics
 hipError_t launch_tile_blend_u8(const float* tiles, const TilePlan& p, uint8_t* img, hipStream_t s);
 
+// Whole frames at their own size (tiles.hip): a side L is padded to frame_pad(L), the next multiple of 8 and at least 64 -- the
+// sizes llie_frame_shape_ok accepts -- by replicating the edge.
+inline int frame_pad(int L) { return L < 64 ? 64 : (L + 7) / 8 * 8; }
+// img u8 [H][W][3] -> out fp32 [3][Hp][Wp] = img[min(y,H-1)][min(x,W-1)] / 127.5 - 1
+hipError_t launch_frame_load_u8(const uint8_t* img, int H, int W, float* out, hipStream_t s);
+// in fp32 [3][Hp][Wp] -> img u8 [H][W][3]: the crop, then (x + 1) * 127.5 clipped and truncated
+hipError_t launch_frame_store_u8(const float* in, int H, int W, uint8_t* img, hipStream_t s);
+
 // (12) device-resident paired data loader (augment.hip).  Frame store: one uint8 pool of HWC RGB frames with packed rows, and a
 // table int64 [N][3] = (byte offset into the pool, H, W) per frame.  Epoch plan: one AugRow per sample (== llie_aug_row); a launch
 // handles rows [first, first + count) and writes sample j = row - first.

@@ -7,6 +7,11 @@
 //                       g = w[Y - oy] * w[X - ox];  num = num + val * g;  den = den + g     (separate fp32 operations)
 //                     out = (uint8) trunc(min(max((num / den + 1.0f) * 127.5f, 0), 255)),  w[k] = min(k + 1, S - k, v) / v  (1 if v == 0)
 //
+//
+// Whole frames at their own size (llie_enhance_hw), Hp / Wp = frame_pad(H) / frame_pad(W):
+//   frame_load_u8:    out[c][y][x] = float(img[min(y, H-1)][min(x, W-1)][c]) / 127.5f - 1.0f,  0 <= y < Hp, 0 <= x < Wp
+//   frame_store_u8:   img[y][x][c] = (uint8) trunc(min(max((in[c][y][x] + 1.0f) * 127.5f, 0), 255)),  0 <= y < H, 0 <= x < W
+//
 // Origins are computed in the kernels from (L, S, v): nothing is uploaded per call.  A thread owns four consecutive x, so a
 // wave moves contiguous runs: 768 bytes of pixels and 1 KB of each fp32 plane.  The fp32 rows start at arbitrary origins, so
 // their four-float accesses are only 4-byte aligned (global_load/store_dwordx4 need no more than that); the 12 pixel bytes go
@@ -160,6 +165,60 @@ __global__ void __launch_bounds__(kTileThreads) tile_blend_u8_kernel(const float
   }
 }
 
+// one thread per four consecutive x of a padded row (Wp is a multiple of 8, so every quad is whole and 16-byte aligned in its plane)
+__global__ void __launch_bounds__(kTileThreads) frame_load_u8_kernel(const uint8_t* __restrict__ img, int H, int W, int Hp, int Wp,
+                                                                     float* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int qpr = Wp >> 2;
+  const int64_t q = (int64_t)blockIdx.x * kTileThreads + threadIdx.x;
+  if (q >= (int64_t)qpr * Hp) return;
+  const int y = (int)(q / qpr), x0 = (int)(q - (int64_t)y * qpr) * 4;
+  const uint8_t* src = img + (size_t)min(y, H - 1) * W * 3;
+  uint32_t b[12];
+  if (x0 + 3 < W) {
+    load12(src + (size_t)x0 * 3, b);
+  } else {  // the frame ends inside or before this quad: replicate its last column
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint8_t* px = src + (size_t)min(x0 + k, W - 1) * 3;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) b[k * 3 + c] = px[c];
+    }
+  }
+  float* dst = out + (size_t)y * Wp + x0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c, dst += (size_t)Hp * Wp) {
+    f32x4 u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) u[k] = (float)b[k * 3 + c] / 127.5f - 1.0f;
+    *reinterpret_cast<f32x4u*>(dst) = u;
+  }
+}
+
+// one thread per four consecutive output pixels of a row; the four floats it reads lie inside the padded row (x0 + 3 < Wp)
+__global__ void __launch_bounds__(kTileThreads) frame_store_u8_kernel(const float* __restrict__ in, int H, int W, int Hp, int Wp,
+                                                                      uint8_t* __restrict__ img) {
+#pragma clang fp contract(off)
+  const int qpr = (W + 3) >> 2;
+  const int64_t q = (int64_t)blockIdx.x * kTileThreads + threadIdx.x;
+  if (q >= (int64_t)qpr * H) return;
+  const int y = (int)(q / qpr), x0 = (int)(q - (int64_t)y * qpr) * 4;
+  const float* src = in + (size_t)y * Wp + x0;
+  uint32_t b[12];
+#pragma unroll
+  for (int c = 0; c < 3; ++c, src += (size_t)Hp * Wp) {
+    const f32x4 val = *reinterpret_cast<const f32x4u*>(src);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) b[k * 3 + c] = (uint32_t)truncf(fminf(fmaxf((val[k] + 1.0f) * 127.5f, 0.f), 255.f));
+  }
+  uint8_t* dst = img + ((size_t)y * W + x0) * 3;
+  if (x0 + 3 < W) {
+    store12(dst, b);
+  } else {
+    for (int i = 0; i < (W - x0) * 3; ++i) dst[i] = (uint8_t)b[i];
+  }
+}
+
 static bool chunk_ok(const TilePlan& p, int ny, int nx, int bpt) {
   return p.first >= 0 && p.count > 0 && (long long)p.first + p.count <= (long long)ny * nx && (long long)p.count * bpt < (1ll << 31);
 }
@@ -189,6 +248,29 @@ hipError_t launch_tile_blend_u8(const float* tiles, const TilePlan& p, uint8_t* 
   const long long blocks = ((long long)((p.W + 3) / 4) * p.H + kTileThreads - 1) / kTileThreads;
   if (blocks >= (1ll << 31)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(tile_blend_u8_kernel, dim3((unsigned)blocks), dim3(kTileThreads), 0, s, tiles, p, ny, nx, img);
+  return hipGetLastError();
+}
+
+// rows x quads of 256 threads; false when the frame is empty or the grid would not fit
+static bool frame_blocks(int H, int W, long long rows, long long quads, unsigned& blocks) {
+  if (H <= 0 || W <= 0 || H > (1 << 24) || W > (1 << 24)) return false;
+  const long long n = (rows * quads + kTileThreads - 1) / kTileThreads;
+  if (n >= (1ll << 31)) return false;
+  blocks = (unsigned)n;
+  return true;
+}
+
+hipError_t launch_frame_load_u8(const uint8_t* img, int H, int W, float* out, hipStream_t s) {
+  unsigned blocks;
+  if (!frame_blocks(H, W, frame_pad(H), frame_pad(W) / 4, blocks)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(frame_load_u8_kernel, dim3(blocks), dim3(kTileThreads), 0, s, img, H, W, frame_pad(H), frame_pad(W), out);
+  return hipGetLastError();
+}
+
+hipError_t launch_frame_store_u8(const float* in, int H, int W, uint8_t* img, hipStream_t s) {
+  unsigned blocks;
+  if (!frame_blocks(H, W, H, (W + 3) / 4, blocks)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(frame_store_u8_kernel, dim3(blocks), dim3(kTileThreads), 0, s, in, H, W, frame_pad(H), frame_pad(W), img);
   return hipGetLastError();
 }
 

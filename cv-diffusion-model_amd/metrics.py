@@ -31,7 +31,7 @@ import torch.nn.functional as F
 
 from . import _native as N
 from .data import DeviceFrameStore, DevicePairLoader
-from .tiling import enhance_tiled
+from .tiling import enhance_tiled, enhance_frame_u8, frame_pad
 
 WINDOW_TAPS, WINDOW_SIGMA = 11, 1.5
 C1, C2 = 1e-4, 9e-4
@@ -259,14 +259,23 @@ def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[i
 @torch.no_grad()
 def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_steps: Optional[int] = None, seed: int = 0,
                              overlap: Optional[int] = None, tile_batch: int = 32,
-                             weights: Optional[Sequence[torch.Tensor]] = None) -> Dict[str, object]:
+                             weights: Optional[Sequence[torch.Tensor]] = None, mode: str = "tiled") -> Dict[str, object]:
     """PSNR / SSIM / MSE at the images' own resolution: every low-light frame of the paired `store` (any sizes >= 11 x 11) goes
     through `enhance_tiled` and is scored against its normal-light frame on the bytes (x = byte / 255).
 
     Draw recipe: g = torch.Generator(device=dev).manual_seed(seed); per pair i, in file order, with (H, W) its size and S =
     model.image_size:  canvas = torch.randn(steps, 3, max(H, S), max(W, S), generator=g, device=dev), then
     enhance_tiled(model, store.frame(i), num_inference_steps, overlap=overlap, tile_batch=tile_batch, noise=canvas) against
-    store.frame(n + i).  Returns evaluate's dictionary without "loss"; `weights=` as there."""
+    store.frame(n + i).  Returns evaluate's dictionary without "loss"; `weights=` as there.
+
+    mode="frame": every image goes through `enhance_frame_u8` instead (one run of the network at the image's own size; images
+    past the engine's size cap raise ValueError).  The same generator, one draw per pair in the same order, with Hp / Wp =
+    frame_pad(H / W):  canvas = torch.randn(steps, 3, Hp, Wp, generator=g, device=dev), then enhance_frame_u8(model,
+    store.frame(i), num_inference_steps, noise=canvas).  `overlap` / `tile_batch` belong to the tiles and are refused."""
+    if mode not in ("tiled", "frame"):
+        raise ValueError(f'mode must be "tiled" or "frame", got {mode!r}')
+    if mode == "frame" and (overlap is not None or tile_batch != 32):
+        raise ValueError('overlap / tile_batch belong to mode="tiled"')
     if not isinstance(store, DeviceFrameStore) or not store.paired:
         raise ValueError("evaluate_full_resolution expects a paired DeviceFrameStore")
     dev = store.device
@@ -279,8 +288,12 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
         n = len(store)
         triples = []
         for i, (h, w) in enumerate(store.sizes):
-            canvas = torch.randn(steps, 3, max(h, s), max(w, s), generator=g, device=dev)
-            out = enhance_tiled(model, store.frame(i), nsteps, overlap=overlap, tile_batch=tile_batch, noise=canvas)
+            if mode == "frame":
+                canvas = torch.randn(steps, 3, frame_pad(h), frame_pad(w), generator=g, device=dev)
+                out = enhance_frame_u8(model, store.frame(i), nsteps, noise=canvas)
+            else:
+                canvas = torch.randn(steps, 3, max(h, s), max(w, s), generator=g, device=dev)
+                out = enhance_tiled(model, store.frame(i), nsteps, overlap=overlap, tile_batch=tile_batch, noise=canvas)
             triples.append(_metrics_out3(out, store.frame(n + i), None))
         flat = torch.cat(triples).cpu().numpy()
     return _summary(store.names, flat, None)

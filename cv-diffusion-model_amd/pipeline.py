@@ -113,26 +113,62 @@ class LowLightDiffusion(nn.Module):
         device = low_light.device
         if device.type != "cuda":
             raise RuntimeError("LowLightDiffusion.enhance runs only on a HIP device; there is no CPU fallback")
-        b, s = low_light.shape[0], self.image_size
+        s = self.image_size
         if tuple(low_light.shape[1:]) != (3, s, s):
             raise ValueError(f"low_light must be [B,3,{s},{s}] (latents are allocated at image_size, "
                              f"low_light_diffusion.py:208-210); got {tuple(low_light.shape)}")
+        return self._enhance_at(low_light, None, num_inference_steps, generator, return_intermediate, noise, return_noise_pred)
+
+    @torch.no_grad()
+    def enhance_frame(self, low_light: torch.Tensor, num_inference_steps: Optional[int] = None,
+                      generator: Optional[torch.Generator] = None, return_intermediate: bool = False, *,
+                      noise: Optional[Union[torch.Tensor, Sequence[torch.Tensor]]] = None,
+                      return_noise_pred: bool = False) -> Union[torch.Tensor, LowLightDiffusionOutput]:
+        """Frame mode (extension): low_light [B,3,H,W] in [-1,1] -> enhanced [B,3,H,W], the whole LCM loop at the frame's own
+        size.  The module tree is the one `image_size` fixed (attention placement, state_dict); the network is fully
+        convolutional and its attention linear in the pixel count, so it runs at any H x W the engine's frame rule accepts
+        (llie_frame_shape_ok): H and W multiples of 8 and at least 64, B <= 65535, and B*H*W times the widest full-resolution
+        channel count at most 2^31 - 1 (about 5.59 M pixels per call for `small`).  A frame that breaks a rule raises
+        ValueError naming it; frames past the size cap go through `enhance_tiled`.
+
+        Semantics, noise order and outputs are `enhance`'s, with [steps,B,3,H,W] noise; on an S x S input the result is
+        `enhance`'s, bit for bit.  Inference only."""
+        device = low_light.device
+        if device.type != "cuda":
+            raise RuntimeError("LowLightDiffusion.enhance_frame runs only on a HIP device; there is no CPU fallback")
+        if low_light.dim() != 4 or low_light.shape[1] != 3:
+            raise ValueError(f"low_light must be [B,3,H,W]; got {tuple(low_light.shape)}")
+        return self._enhance_at(low_light, (int(low_light.shape[2]), int(low_light.shape[3])), num_inference_steps, generator,
+                                return_intermediate, noise, return_noise_pred)
+
+    def _enhance_at(self, low_light, frame, num_inference_steps, generator, return_intermediate, noise, return_noise_pred):
+        """The loop of `enhance` (frame is None: image_size, llie_enhance) and `enhance_frame` (frame = (H, W), llie_enhance_hw)."""
+        device = low_light.device
+        b = low_light.shape[0]
+        hh, ww = frame if frame is not None else (self.image_size, self.image_size)
         steps = self.num_inference_steps if num_inference_steps is None else num_inference_steps
         self.scheduler.set_timesteps(steps, device=device)
         ts = self.scheduler._timestep_list
         steps = len(ts)
+        prepared = None
+        if frame is not None:
+            try:  # the workspace query applies the frame rule: a refused frame raises before any draw or launch
+                prepared = self.unet._prepare(b, device, enhance_steps=max(steps, 8), frame=frame)
+            except ValueError as e:
+                hint = "; enhance_tiled handles images of any size" if "element cap" in str(e) else ""
+                raise ValueError(f"enhance_frame: {e}{hint}") from None
 
         if noise is None:
             # drawn straight into the [steps,B,3,S,S] buffer the engine reads (same generator streams as torch.randn)
-            noise_t = torch.empty(steps, b, 3, s, s, dtype=torch.float32, device=device)
+            noise_t = torch.empty(steps, b, 3, hh, ww, dtype=torch.float32, device=device)
             noise_t[0].normal_(generator=generator)
             for i in range(1, steps):
                 noise_t[i].normal_()
         else:
             noise_t = noise if isinstance(noise, torch.Tensor) else torch.stack([n.to(device) for n in noise])
             noise_t = noise_t.to(device=device, dtype=torch.float32)
-            if tuple(noise_t.shape) != (steps, b, 3, s, s):
-                raise ValueError(f"noise must be [{steps},{b},3,{s},{s}]")
+            if tuple(noise_t.shape) != (steps, b, 3, hh, ww):
+                raise ValueError(f"noise must be [{steps},{b},3,{hh},{ww}]")
         noise_t = noise_t.contiguous()
 
         coefs = (N.StepCoef * steps)(*[self.scheduler.step_coefficients(t) for t in ts])
@@ -143,15 +179,19 @@ class LowLightDiffusion(nn.Module):
                 self._t_cache.clear()
             t_dev = self._t_cache[tkey] = torch.tensor(ts, dtype=torch.long).repeat_interleave(b).to(device)
         low = low_light.detach().float().contiguous()
-        enhanced = torch.empty(b, 3, s, s, dtype=torch.float32, device=device)
-        inter = torch.empty(steps, b, 3, s, s, dtype=torch.float32, device=device) if return_intermediate else None
-        preds = torch.empty(steps, b, 3, s, s, dtype=torch.float32, device=device) if return_noise_pred else None
-        h, ws, nbytes = self.unet._prepare(b, device, enhance_steps=max(steps, 8))
+        enhanced = torch.empty(b, 3, hh, ww, dtype=torch.float32, device=device)
+        inter = torch.empty(steps, b, 3, hh, ww, dtype=torch.float32, device=device) if return_intermediate else None
+        preds = torch.empty(steps, b, 3, hh, ww, dtype=torch.float32, device=device) if return_noise_pred else None
+        h, ws, nbytes = prepared if prepared is not None else self.unet._prepare(b, device, enhance_steps=max(steps, 8))
+        outs = (enhanced.data_ptr(), inter.data_ptr() if inter is not None else None, preds.data_ptr() if preds is not None else None)
+        stream = torch.cuda.current_stream(device).cuda_stream
         with torch.cuda.device(device):
-            N.check(N.lib().llie_enhance(
-                h.h, low.data_ptr(), noise_t.data_ptr(), t_dev.data_ptr(), coefs, steps, enhanced.data_ptr(),
-                inter.data_ptr() if inter is not None else None, preds.data_ptr() if preds is not None else None,
-                b, ws.data_ptr(), nbytes, torch.cuda.current_stream(device).cuda_stream), "enhance")
+            if frame is None:
+                N.check(N.lib().llie_enhance(h.h, low.data_ptr(), noise_t.data_ptr(), t_dev.data_ptr(), coefs, steps, *outs,
+                                             b, ws.data_ptr(), nbytes, stream), "enhance")
+            else:
+                N.check(N.lib().llie_enhance_hw(h.h, low.data_ptr(), noise_t.data_ptr(), t_dev.data_ptr(), coefs, steps, *outs,
+                                                b, hh, ww, ws.data_ptr(), nbytes, stream), "enhance_frame")
         self.scheduler._step_index = steps
         if return_intermediate or return_noise_pred:
             out = LowLightDiffusionOutput(enhanced=enhanced,

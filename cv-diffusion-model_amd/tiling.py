@@ -12,7 +12,14 @@ One definition serves the NumPy twins here, the kernels (csrc/tiles.hip) and the
   blend    per pixel and channel over the covering tiles in ascending t: g = w[Y - oy] * w[X - ox]; num += val * g; den += g
            (separate fp32 multiply and add); out = uint8(trunc(clip((num / den + 1) * 127.5, 0, 255)))
 
-The device functions are bit-exact with the host twins.  There is no CPU fallback for `enhance_tiled`.
+Frame mode (`enhance_frame_u8`) is the other route for images under the engine's size cap: no tiles, the network runs once at
+the image's own size (`LowLightDiffusion.enhance_frame`), padded to sides the network takes:
+
+  pad      frame_pad(L) = max(64, 8 * ceil(L / 8))
+  load     out[c][y][x] = float(img[min(y, H-1)][min(x, W-1)][c]) / 127.5f - 1.0f   for y < frame_pad(H), x < frame_pad(W)
+  store    img[y][x][c] = uint8(trunc(clip((x[c][y][x] + 1) * 127.5, 0, 255)))      for y < H, x < W
+
+The device functions are bit-exact with the host twins.  There is no CPU fallback for `enhance_tiled` or `enhance_frame_u8`.
 """
 from __future__ import annotations
 
@@ -104,6 +111,29 @@ def blend_tiles_array(tiles: np.ndarray, size: Tuple[int, int], overlap: int) ->
     return np.clip((r + np.float32(1.0)) * np.float32(127.5), 0, 255).astype(np.uint8)
 
 
+def frame_pad(length: int) -> int:
+    """A side of `length` pixels as frame mode runs it: the next multiple of 8, at least 64."""
+    if length <= 0:
+        raise ValueError(f"length must be positive, got {length}")
+    return max(64, -(-int(length) // 8) * 8)
+
+
+def frame_load_array(rgb_u8: np.ndarray) -> np.ndarray:
+    """uint8 [H,W,3] -> fp32 [3,Hp,Wp] in [-1,1], Hp / Wp = frame_pad(H / W); the edge is replicated into the padding."""
+    h, w = _check_image(rgb_u8, "frame_load_array")
+    px = rgb_u8[np.minimum(np.arange(frame_pad(h)), h - 1)][:, np.minimum(np.arange(frame_pad(w)), w - 1)]
+    return np.ascontiguousarray((px.astype(np.float32) / np.float32(127.5) - np.float32(1.0)).transpose(2, 0, 1))
+
+
+def frame_store_array(x: np.ndarray, size: Tuple[int, int]) -> np.ndarray:
+    """fp32 [3,Hp,Wp] -> uint8 [H,W,3]: the crop to `size`, then the reference's truncating denormalisation."""
+    h, w = int(size[0]), int(size[1])
+    if h <= 0 or w <= 0 or x.ndim != 3 or tuple(x.shape) != (3, frame_pad(h), frame_pad(w)):
+        raise ValueError(f"a {h}x{w} image is a frame [3,{frame_pad(max(h, 1))},{frame_pad(max(w, 1))}], got {tuple(x.shape)}")
+    r = x.astype(np.float32, copy=False)[:, :h, :w].transpose(1, 2, 0)
+    return np.clip((r + np.float32(1.0)) * np.float32(127.5), 0, 255).astype(np.uint8)
+
+
 # ------------------------------------------------------------------ device wrappers
 def _require_hip(t, what: str) -> None:
     if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
@@ -176,7 +206,59 @@ def blend_tiles_device(tiles: torch.Tensor, size: Tuple[int, int], overlap: int)
     return img
 
 
+def frame_load_device(rgb_u8: torch.Tensor) -> torch.Tensor:
+    """Device twin of frame_load_array: uint8 [H,W,3] on a HIP device -> fp32 [3,Hp,Wp]."""
+    _require_hip(rgb_u8, "frame_load_device")
+    h, w = _check_image(rgb_u8, "frame_load_device")
+    img = rgb_u8.contiguous()
+    out = torch.empty(3, frame_pad(h), frame_pad(w), dtype=torch.float32, device=img.device)
+    with torch.cuda.device(img.device):
+        N.check(N.lib().llie_frame_load_u8(img.data_ptr(), h, w, out.data_ptr(), _stream(img.device)), "frame_load_u8")
+    return out
+
+
+def frame_store_device(x: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
+    """Device twin of frame_store_array: fp32 [3,Hp,Wp] on a HIP device -> uint8 [H,W,3]."""
+    _require_hip(x, "frame_store_device")
+    h, w = int(size[0]), int(size[1])
+    if h <= 0 or w <= 0 or x.dim() != 3 or tuple(x.shape) != (3, frame_pad(h), frame_pad(w)):
+        raise ValueError(f"a {h}x{w} image is a frame [3,{frame_pad(max(h, 1))},{frame_pad(max(w, 1))}], got {tuple(x.shape)}")
+    x = x.detach().float().contiguous()
+    img = torch.empty(h, w, 3, dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        N.check(N.lib().llie_frame_store_u8(x.data_ptr(), h, w, img.data_ptr(), _stream(x.device)), "frame_store_u8")
+    return img
+
+
 # ------------------------------------------------------------------ the whole path
+@torch.no_grad()
+def enhance_frame_u8(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int] = None, *,
+                     generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [H,W,3] on a HIP device -> enhanced uint8 [H,W,3] at the same resolution, by one run of the network at that size.
+
+    The image is loaded into a frame [3,Hp,Wp] (Hp / Wp = frame_pad(H / W): the next multiple of 8, at least 64) with its edge
+    replicated into the padding, goes through `model.enhance_frame` at B = 1, and is cropped and denormalised back.  Noise is
+    drawn in `enhance`'s order at the frame's size; `noise=` supplies it as a canvas [steps,3,Hp,Wp] for a reproducible run.
+
+    The replicated border is part of the frame the network sees: it takes part in the GroupNorm statistics (and in the global
+    attention), so the result inside the image depends, slightly, on how much padding its size needs; an image whose sides are
+    multiples of 8 and at least 64 has none.  Against `enhance_tiled` this gives the attention one field of view over the whole
+    image and spends no work on overlaps; images past the engine's size cap (ValueError, naming it) remain with the tiles."""
+    if not isinstance(rgb_u8, torch.Tensor):
+        raise ValueError(f"enhance_frame_u8 expects a torch.Tensor, got {type(rgb_u8).__name__}")
+    h, w = _check_image(rgb_u8, "enhance_frame_u8")
+    _require_hip(rgb_u8, "enhance_frame_u8")
+    hp, wp = frame_pad(h), frame_pad(w)
+    if noise is not None:
+        if not isinstance(noise, torch.Tensor) or noise.dim() != 4 or tuple(noise.shape[1:]) != (3, hp, wp):
+            raise ValueError(f"noise must be a canvas [steps,3,{hp},{wp}]")
+        noise = noise.to(device=rgb_u8.device, dtype=torch.float32)[:, None]
+    low = frame_load_device(rgb_u8)[None]
+    out = model.enhance_frame(low, num_inference_steps, generator=generator, noise=noise)
+    return frame_store_device(out[0], (h, w))
+
+
+
 @torch.no_grad()
 def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int] = None, *, overlap: Optional[int] = None,
                   tile_batch: int = 32, generator: Optional[torch.Generator] = None,

@@ -429,9 +429,14 @@ class EfficientUNet(_NativeModule):
         self.config = config
 
     # -- native entry points used by the pipeline ----------------------------------------------
-    def _prepare(self, batch: int, device: torch.device, enhance_steps: int = 0):
+    def _prepare(self, batch: int, device: torch.device, enhance_steps: int = 0, frame: Optional[Tuple[int, int]] = None):
+        """-> (handle, workspace, bytes).  `frame` = (H, W): the workspace of frame mode at that size (ValueError naming the rule
+        when llie_frame_shape_ok refuses it)."""
         h = self._handle(resolve_compute_dtype(self.compute_dtype))
-        nbytes = h.enhance_workspace_bytes(batch, enhance_steps) if enhance_steps else h.workspace_bytes(batch)
+        if frame is not None:
+            nbytes = h.frame_workspace_bytes(batch, frame[0], frame[1], enhance_steps)
+        else:
+            nbytes = h.enhance_workspace_bytes(batch, enhance_steps) if enhance_steps else h.workspace_bytes(batch)
         ws = self._workspace(h, nbytes, device)
         return h, ws, ws.numel()
 

@@ -135,6 +135,28 @@ int llie_unet_forward(llie_ctx* ctx, const float* latents, const float* cond, co
                       int uniform_t, float* eps_out, int batch, void* workspace, int64_t workspace_bytes,
                       llie_stream stream);
 
+/* Frame mode: the network, with the module tree its image_size fixed (attention placement, state_dict), run at a frame's own
+ * H x W.  The denoiser is fully convolutional and its attention linear in the pixel count, so nothing but these rules ties it to
+ * image_size.  Inference only.  The entry points without _hw are these at H = W = image_size.
+ *   llie_frame_shape_ok (host only, no GPU needed): LLIE_OK, or LLIE_ERR_SHAPE (llie_last_error names the rule) unless
+ *       - height and width are multiples of 8 and at least 64 (three stride-2 levels, each restored by a x2 up-sampling);
+ *       - batch <= 65535;
+ *       - batch x height x width x Cmax <= 2^31 - 1, Cmax = the widest channel count the plan stores at full resolution (the
+ *         hidden width of the widest level-0 block: 384 for `small`, so about 5.59 M pixels per call).  The kernels index
+ *         elements of a tensor with 32-bit integers; this clause is what keeps that arithmetic safe.  Larger images go through
+ *         tiles (llie_tile_*).
+ *   llie_frame_workspace_bytes: scratch of llie_unet_forward_hw / llie_enhance_hw at that shape; max_steps = 0 gives the size with
+ *       which the loop runs as plain launches, max_steps > 0 adds the staging area of the hipGraph path for up to that many
+ *       steps (llie_enhance_workspace_bytes).  A shape llie_frame_shape_ok refuses returns its code.
+ *   llie_unet_forward_hw: llie_unet_forward on fp32 NCHW [B,3,H,W] halves; eps_out [B,3,H,W].
+ * A launch rule (block form, Gram statistics, folded up-sampling conv) depends on the layer, (H, W), the dtype and the knobs,
+ * never on the batch: a frame's result is the same bits alone or in a batch. */
+int llie_frame_shape_ok(const llie_ctx* ctx, int batch, int height, int width);
+int64_t llie_frame_workspace_bytes(llie_ctx* ctx, int batch, int height, int width, int max_steps);
+int llie_unet_forward_hw(llie_ctx* ctx, const float* latents, const float* cond, const int64_t* timesteps, int uniform_t,
+                         float* eps_out, int batch, int height, int width, void* workspace, int64_t workspace_bytes,
+                         llie_stream stream);
+
 /* Single-operator forward for kinds IRB / ATTN / DOWN / UP: x fp32 NCHW [B,C,H,W] -> y fp32 NCHW.
  * `temb` (IRB only): device fp32 [B, time_embed_dim] time embedding (efficient_unet.py:203). */
 int llie_module_forward(llie_ctx* ctx, const float* x, const float* temb, float* y, int batch, int height,
@@ -272,6 +294,13 @@ int llie_enhance(llie_ctx* ctx, const float* low_light, const float* noise, cons
                  const llie_step_coef* coefs, int steps, float* enhanced, float* intermediates,
                  float* noise_preds, int batch, void* workspace, int64_t workspace_bytes, llie_stream stream);
 
+/* llie_enhance on frames of their own size: every [..,3,S,S] above is [..,3,height,width]; the workspace comes from
+ * llie_frame_workspace_bytes.  Captured graphs are keyed by the frame size as well and share the context's cache of 16.
+ * A shape llie_frame_shape_ok refuses returns LLIE_ERR_SHAPE before anything is launched. */
+int llie_enhance_hw(llie_ctx* ctx, const float* low_light, const float* noise, const int64_t* timesteps_dev,
+                    const llie_step_coef* coefs, int steps, float* enhanced, float* intermediates, float* noise_preds,
+                    int batch, int height, int width, void* workspace, int64_t workspace_bytes, llie_stream stream);
+
 int llie_graph_cache_entries(const llie_ctx* ctx);
 
 /* Byte-level I/O either side of the path (scripts/inference.py:99-134), on the device:
@@ -307,6 +336,19 @@ int llie_tile_gather_u8(const uint8_t* img, int H, int W, int S, int v, int firs
 int llie_tile_gather_f32(const float* canvas, int planes, int H, int W, int S, int v, int first, int count, float* out,
                          llie_stream stream);
 int llie_tile_blend_u8(const float* tiles, int H, int W, int S, int v, uint8_t* img, llie_stream stream);
+
+/* Byte-level I/O of frame mode: a uint8 image of any size to the padded fp32 frame llie_enhance_hw takes, and back.
+ *   llie_frame_pad:      a side L -> the next multiple of 8, at least 64 (host only)
+ *   llie_frame_load_u8:  uint8 HWC RGB [H][W][3] -> fp32 [3][Hp][Wp], Hp / Wp = llie_frame_pad(H / W),
+ *                        out[c][y][x] = img[min(y, H-1)][min(x, W-1)][c] / 127.5 - 1: the edge is replicated into the padding,
+ *                        as llie_tile_gather_u8 does
+ *   llie_frame_store_u8: fp32 [3][Hp][Wp] -> uint8 HWC RGB [H][W][3]: the crop to H x W, then llie_postprocess_u8's
+ *                        (x + 1) * 127.5, clip [0,255], truncate
+ * Bit-exact with the host implementation in tiling.py (fp32 arithmetic without fused multiply-adds, no atomics).  A NULL pointer
+ * or a non-positive size returns LLIE_ERR_ARG. */
+int llie_frame_pad(int L);
+int llie_frame_load_u8(const uint8_t* img, int H, int W, float* out, llie_stream stream);
+int llie_frame_store_u8(const float* x, int H, int W, uint8_t* img, llie_stream stream);
 
 /* Device-resident paired data loader (src/training/dataset.py): the training frames stay on the device as uint8 and one launch
  * per batch crops, flips, rotates or degrades, and normalises them into the fp32 NCHW pair a training step takes.

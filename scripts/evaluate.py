@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """PSNR / SSIM of a checkpoint on a paired validation folder, on the MI355X engine -- the sibling of scripts/inference.py.
 
-  python scripts/evaluate.py --data LOL/eval15 --checkpoint ckpt.pt [--full_resolution] [--per_image] [--output result.json]
+  python scripts/evaluate.py --data LOL/eval15 --checkpoint ckpt.pt [--full_resolution [frame]] [--per_image] [--output result.json]
 
 --data is the layout DeviceFrameStore.from_folder reads (ROOT/low and ROOT/high, or lowlight / dark and normal / bright).  By
 default every pair is centre-cropped to --image_size and goes through `evaluate` in batches of --batch_size (the result then
 also holds the validation loss); --full_resolution scores every image at its own size through `evaluate_full_resolution`
-(overlapping tiles, --tile_overlap / --tile_batch as in inference.py).  One JSON line is printed, and written to --output when
+(overlapping tiles, --tile_overlap / --tile_batch as in inference.py; `--full_resolution frame` runs the network once per image
+at the image's own size instead, frame mode, and excludes the tile flags).  One JSON line is printed, and written to --output when
 given; the per-image lists are part of it only under --per_image.  --seed seeds every draw, so a run is reproducible.
 """
 import argparse
@@ -36,7 +37,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--device", type=str, default="cuda" if torch.cuda.is_available() else "cpu")
     p.add_argument("--batch_size", type=int, default=8, help="images per enhance call (centre-crop evaluation)")
     p.add_argument("--seed", type=int, default=0, help="seed of every noise draw")
-    p.add_argument("--full_resolution", action="store_true", help="score every image at its own size, enhanced as overlapping tiles")
+    p.add_argument("--full_resolution", nargs="?", const="tiled", default=None, choices=["tiled", "frame"],
+                   help="score every image at its own size: enhanced as overlapping tiles (the default), or `frame`: by one run of "
+                        "the network at that size")
     p.add_argument("--tile_overlap", type=int, default=None, help="overlap of neighbouring tiles in pixels (default image_size // 8)")
     p.add_argument("--tile_batch", type=int, default=32, help="tiles per enhance call")
     p.add_argument("--per_image", action="store_true", help="keep the per-image lists in the result")
@@ -45,7 +48,11 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def parse_args(argv=None):
-    return build_parser().parse_args(argv)
+    p = build_parser()
+    args = p.parse_args(argv)
+    if args.full_resolution == "frame" and (args.tile_overlap is not None or args.tile_batch != 32):
+        p.error("--full_resolution frame and --tile_overlap / --tile_batch exclude each other")
+    return args
 
 
 def main(argv=None) -> int:
@@ -54,7 +61,7 @@ def main(argv=None) -> int:
     if args.full_resolution:
         store = M.DeviceFrameStore.from_folder(args.data, device=args.device)
         res = M.evaluate_full_resolution(model, store, num_inference_steps=args.num_steps, seed=args.seed, overlap=args.tile_overlap,
-                                         tile_batch=args.tile_batch)
+                                         tile_batch=args.tile_batch, mode=args.full_resolution)
     else:
         store = M.DeviceFrameStore.from_folder(args.data, device=args.device, image_size=args.image_size)
         loader = M.DevicePairLoader(store, args.batch_size, args.image_size, "val")

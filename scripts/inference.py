@@ -3,7 +3,9 @@
 scripts/inference.py (:30-62): --input --output --checkpoint --model --format --variant --image_size
 --num_steps --device.  Only --format pytorch exists here (ONNX / TFLite are the reference's mobile
 deployment targets, out of scope); extensions: --dtype {fp32,fp16,bf16}, --noise_seed, and --tile [--tile_overlap N]
-[--tile_batch N], which enhances the image at its own resolution as overlapping image_size tiles instead of resizing it.
+[--tile_batch N], which enhances the image at its own resolution as overlapping image_size tiles instead of resizing it, and
+--native, which enhances it at its own resolution by one run of the network at that size (frame mode; images under the engine's
+size cap, about 5.59 M pixels for `small`).  --native and the tile flags exclude each other.
 """
 import argparse
 import importlib
@@ -41,7 +43,13 @@ def parse_args(argv=None):
                         "on the device; --noise_seed then seeds the per-image noise canvas")
     p.add_argument("--tile_overlap", type=int, default=None, help="overlap of neighbouring tiles in pixels (default image_size // 8)")
     p.add_argument("--tile_batch", type=int, default=32, help="tiles per enhance call")
-    return p.parse_args(argv)
+    p.add_argument("--native", action="store_true",
+                   help="(extension) no resize and no tiles: one run of the network at the image's own resolution (frame mode); "
+                        "--noise_seed then seeds the noise canvas at the padded size")
+    args = p.parse_args(argv)
+    if args.native and (args.tile or args.tile_overlap is not None or args.tile_batch != 32):
+        p.error("--native and --tile / --tile_overlap / --tile_batch exclude each other")
+    return args
 
 
 def load_model(args):
@@ -66,6 +74,16 @@ def enhance_tiled_image(args, model, rgb):
     return out.cpu().numpy()
 
 
+def enhance_native_image(args, model, rgb):
+    """--native: uint8 [H,W,3] -> uint8 [H,W,3] at the input's resolution, one run of the network (frame mode)."""
+    noise = None
+    if args.noise_seed is not None:  # the canvas at the padded size, drawn entry by entry in enhance's order
+        g = torch.Generator().manual_seed(args.noise_seed)
+        hp, wp = tiling.frame_pad(rgb.shape[0]), tiling.frame_pad(rgb.shape[1])
+        noise = torch.stack([torch.randn(3, hp, wp, generator=g) for _ in range(args.num_steps)])
+    return tiling.enhance_frame_u8(model, torch.from_numpy(rgb).to(args.device), args.num_steps, noise=noise).cpu().numpy()
+
+
 def enhance_resized_image(args, model, rgb):
     """The reference's path: squash to image_size, enhance, stretch back to the input's size."""
     original = rgb.shape[:2]
@@ -85,7 +103,10 @@ def process_single_image(args, model, input_path: str, output_path: str) -> floa
     print(f"Processing: {input_path}")
     rgb = hostio.load_image(input_path)
     start = time.perf_counter()
-    out = enhance_tiled_image(args, model, rgb) if args.tile else enhance_resized_image(args, model, rgb)
+    if args.native:
+        out = enhance_native_image(args, model, rgb)
+    else:
+        out = enhance_tiled_image(args, model, rgb) if args.tile else enhance_resized_image(args, model, rgb)
     elapsed = time.perf_counter() - start
     hostio.save_image(output_path, out)
     print(f"  Saved to: {output_path}")
