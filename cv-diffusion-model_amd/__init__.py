@@ -12,7 +12,7 @@ from .unet import (EfficientUNet, EfficientUNetConfig, create_efficient_unet, In
                    LinearAttention, Downsample, Upsample, SqueezeExcitation)
 from .scheduler import LCMScheduler, LCMSchedulerOutput, LCMDenoisingLoop, get_lcm_timesteps
 from .pipeline import (LowLightDiffusion, LowLightDiffusionOutput, LowLightLCMDistillation, normalize_image,
-                       denormalize_image)
+                       denormalize_image, x0_loss, x0_loss_host)
 from .sharding import shard_range, enhance_sharded, all_gather_batch, all_reduce_gradients
 from .training import FusedAdamW, FusedGradScaler, TrainStep, DistillStep
 from .build import build_library, library_path
@@ -25,7 +25,8 @@ from .tiling import (tile_origins, gather_tiles_array, blend_tiles_array, gather
                      frame_store_device, enhance_frame_u8)
 from .data import (DeviceFrameStore, DevicePairLoader, create_device_dataloaders, epoch_plan, augment_pairs_host, augment_synth_host,
                    augment_pairs_device, augment_synth_device)
-from .metrics import ImageMetrics, image_metrics, image_metrics_host, evaluate, evaluate_full_resolution
+from .metrics import (ImageMetrics, image_metrics, image_metrics_host, evaluate, evaluate_full_resolution, ssim_loss,
+                      ssim_grad_host)
 from .trainer import (TrainingConfig, LowLightTrainer, train_model, make_lr_scheduler, build_checkpoint, comparison_grid,
                       comparison_grid_host)
 
@@ -40,6 +41,7 @@ __all__ = [
     "DeviceFrameStore", "DevicePairLoader", "create_device_dataloaders", "epoch_plan", "augment_pairs_host", "augment_synth_host",
     "augment_pairs_device", "augment_synth_device",
     "ImageMetrics", "image_metrics", "image_metrics_host", "evaluate", "evaluate_full_resolution",
+    "ssim_loss", "ssim_grad_host", "x0_loss", "x0_loss_host",
     "TrainingConfig", "LowLightTrainer", "train_model", "make_lr_scheduler", "build_checkpoint", "comparison_grid",
     "comparison_grid_host",
 ]

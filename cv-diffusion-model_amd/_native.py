@@ -46,6 +46,7 @@ EXPORTS = [
     "llie_se_gate", "llie_affine_add", "llie_nchw_to_nhwc", "llie_nhwc_to_nchw", "llie_pw_gemm_dot",
     "llie_frame_shape_ok", "llie_frame_workspace_bytes", "llie_unet_forward_hw", "llie_enhance_hw",
     "llie_frame_pad", "llie_frame_load_u8", "llie_frame_store_u8",
+    "llie_ssim_grad_scratch_bytes", "llie_ssim_grad_f32", "llie_x0_loss",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 PW_SIGMOID_BWD, PW_RELU6_BWD, PW_SILU_BWD, PW_SCALE = 0, 1, 2, 3  # llie_pointwise_kind
@@ -181,6 +182,10 @@ def lib() -> C.CDLL:
     L.llie_image_metrics_scratch_bytes.restype = i64
     L.llie_image_metrics_f32.argtypes = [vp, vp, ci, ci, ci, C.c_float, C.c_float, vp, vp, i64, vp]
     L.llie_image_metrics_u8.argtypes = [vp, vp, ci, ci, ci, vp, vp, i64, vp]
+    L.llie_ssim_grad_scratch_bytes.argtypes = [ci, ci, ci]
+    L.llie_ssim_grad_scratch_bytes.restype = i64
+    L.llie_ssim_grad_f32.argtypes = [vp, vp, ci, ci, ci, C.c_float, C.c_float, vp, vp, vp, vp, i64, vp]
+    L.llie_x0_loss.argtypes = [vp, vp, vp, vp, vp, ci, ci, C.c_float, C.c_float, vp, vp, ci, ci, ci, vp, i64, vp]
     L.llie_comparison_grid_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
     L.llie_pw_gemm.argtypes = [ci, C.POINTER(GemmSeg), ci, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     L.llie_pw_gemm_tile_rows.argtypes = [ci]

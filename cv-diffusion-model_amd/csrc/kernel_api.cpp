@@ -564,6 +564,49 @@ int llie_image_metrics_u8(const uint8_t* a, const uint8_t* b, int batch, int H, 
   return kerr("image_metrics_u8", launch_image_metrics_u8(a, b, batch, H, W, out3, reinterpret_cast<double*>(scratch), hs(stream)));
 }
 
+// ---- SSIM / L1 with a gradient (ssimloss.hip): every contract check runs here, before any HIP call
+static int ssim_grad_check(const char* what, int batch, int H, int W, const void* scratch, int64_t scratch_bytes) {
+  if (!scratch || batch < 1) return LLIE_ERR_ARG;
+  if (H < kMetricTaps || W < kMetricTaps) {
+    set_err("%s: images of at least %d x %d, got %d x %d", what, kMetricTaps, kMetricTaps, H, W);
+    return LLIE_ERR_SHAPE;
+  }
+  const int64_t need = llie_ssim_grad_scratch_bytes(batch, H, W);
+  if (need < 0) return LLIE_ERR_ARG;
+  if (scratch_bytes < need) {
+    set_err("%s: scratch of %lld bytes needed, %lld given", what, (long long)need, (long long)scratch_bytes);
+    return LLIE_ERR_WORKSPACE;
+  }
+  return LLIE_OK;
+}
+int64_t llie_ssim_grad_scratch_bytes(int batch, int H, int W) {
+  if (batch < 1) return LLIE_ERR_ARG;
+  if (H < kMetricTaps || W < kMetricTaps) return LLIE_ERR_SHAPE;
+  if (3ll * batch * ((H + kMetricTileH - 1) / kMetricTileH) * ((W + kMetricTileW - 1) / kMetricTileW) >= (1ll << 31)) return LLIE_ERR_ARG;
+  return (int64_t)ssim_grad_scratch_bytes(batch, H, W);
+}
+int llie_ssim_grad_f32(const float* a, const float* b, int batch, int H, int W, float lo, float hi, const float* upstream,
+                       float* ssim_out, float* da, void* scratch, int64_t scratch_bytes, llie_stream stream) {
+  if (!a || !b || !ssim_out || !(lo != hi) || !std::isfinite(lo) || !std::isfinite(hi)) return LLIE_ERR_ARG;
+  if (int rc = ssim_grad_check("ssim_grad_f32", batch, H, W, scratch, scratch_bytes)) return rc;
+  return kerr("ssim_grad_f32", launch_ssim_grad_f32(a, b, batch, H, W, lo, hi, upstream, ssim_out, da, scratch, hs(stream)), LLIE_ERR_ARG,
+              nullptr);
+}
+int llie_x0_loss(const float* out, const float* x_t, const float* normal, const int64_t* t, const float* alphas_cumprod, int table_n,
+                 int velocity, float lambda_s, float lambda_1, float* loss_out, float* d_out, int batch, int H, int W, void* scratch,
+                 int64_t scratch_bytes, llie_stream stream) {
+  if (!out || !x_t || !normal || !t || !alphas_cumprod || table_n < 1 || !loss_out) return LLIE_ERR_ARG;
+  if (!(lambda_s >= 0.f) || !(lambda_1 >= 0.f) || !std::isfinite(lambda_s) || !std::isfinite(lambda_1)) {
+    set_err("x0_loss: the weights must be finite and >= 0");
+    return LLIE_ERR_ARG;
+  }
+  if (int rc = ssim_grad_check("x0_loss", batch, H, W, scratch, scratch_bytes)) return rc;
+  X0LossArgs x{};
+  x.out = out; x.x_t = x_t; x.normal = normal; x.t = t; x.acp = alphas_cumprod; x.table_len = table_n; x.velocity = velocity != 0;
+  x.lambda_s = lambda_s; x.lambda_1 = lambda_1; x.loss = loss_out; x.d_out = d_out; x.batch = batch; x.H = H; x.W = W;
+  return kerr("x0_loss", launch_x0_loss(x, scratch, hs(stream)), LLIE_ERR_ARG, nullptr);
+}
+
 // ---- the trainer's sample sheet (samples.hip): arguments are checked here, before any HIP call
 int llie_comparison_grid_u8(const float* low, const float* enhanced, const float* normal, int n, int H, int W, uint8_t* grid,
                             llie_stream stream) {

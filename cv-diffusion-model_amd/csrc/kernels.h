@@ -652,4 +652,35 @@ inline bool comparison_grid_ok(int n, int H, int W) {  // sizes whose picture an
 hipError_t launch_comparison_grid_u8(const float* low, const float* enhanced, const float* normal, int n, int H, int W, uint8_t* grid,
                                      hipStream_t s);
 
+// (15) SSIM / L1 with a gradient (ssimloss.hip): definition (13)'s SSIM in fp32, differentiated with respect to the first image.
+// With the filtered maps mx, my, xx, yy, xy at a valid position and sx = xx - mx^2, sy = yy - my^2, sxy = xy - mx my,
+// A1 = 2 mx my + C1, A2 = 2 sxy + C2, B1 = mx^2 + my^2 + C1, B2 = sx + sy + C2, S = A1 A2 / (B1 B2):
+//   dmx = (2 my A2 - 2 my A1) / (B1 B2) - S (2 mx / B1 - 2 mx / B2),   dxx = -S / B2,   dxy = 2 A1 / (B1 B2)
+//   dSSIM/dx = [W^T(dmx) + 2 x W^T(dxx) + y W^T(dxy)] / (3 (H - 10) (W - 10)),   dSSIM/da = dSSIM/dx / (hi - lo)
+// W^T is the transposed window filter: a full correlation that is zero outside the valid region and returns H x W.  The second
+// moments are formed as written (xx - mx^2), not around the window mean.
+// The x0 term of a training step (out = the network output [B,3,H,W], x_t the noised input, y the normal-light image,
+// abar_b = alphas_cumprod[t_b], alpha = sqrt(abar), sigma = sqrt(1 - abar)):
+//   x^ = p_b x_t + q_b out          epsilon prediction p = 1 / alpha, q = -sigma / alpha;  v prediction p = alpha, q = -sigma;  not clamped
+//   L_x0 = (1 / B) sum_b w_b [lambda_s (1 - SSIM_b(x^, y)) + lambda_1 mean|x^_b - y_b|],   w_b = abar_b,  data range (-1, 1),
+//          the L1 mean over the 3 H W values in model units
+//   dL_x0/dout = (w_b / B) q_b [-lambda_s/2 dSSIM_b/dx + lambda_1 sign(x^ - y) / (3 H W)]
+// A sample with abar_b == 0 contributes exactly 0 to the loss and nothing to the gradient (1 / alpha is never evaluated).
+// Tiles as (13); no atomics; every sum's order depends on H and W alone.
+long long ssim_grad_scratch_bytes(int batch, int H, int W);  // -1 for batch < 1 or an image below 11 x 11
+// ssim_out [batch] fp32; da (or null: forward only) = upstream_b dSSIM_b/da, stored; upstream [batch] or null (= 1).
+// A null pointer (other than the optional two), batch < 1, H or W < 11, lo == hi: hipErrorInvalidValue
+hipError_t launch_ssim_grad_f32(const float* a, const float* b, int batch, int H, int W, float lo, float hi, const float* upstream,
+                                float* ssim_out, float* da, void* scratch, hipStream_t s);
+struct X0LossArgs {
+  const float* out; const float* x_t; const float* normal;  // fp32 NCHW [batch][3][H][W]
+  const int64_t* t; const float* acp; int table_len;        // device int64 [batch], device alphas_cumprod
+  int velocity;                                             // 0 epsilon prediction, 1 v prediction
+  float lambda_s, lambda_1;                                 // >= 0
+  float* loss;                                              // one device fp32: the term alone
+  float* d_out;                                             // accumulated into (or null: loss only)
+  int batch, H, W;
+};
+hipError_t launch_x0_loss(const X0LossArgs& a, void* scratch, hipStream_t s);
+
 }  // namespace llie

@@ -14,6 +14,15 @@ for uint8 images.
   mse      mean of (x - y)^2 over all 3 H W values, border included
   psnr     -10 log10(mse), +inf when mse == 0
 
+SSIM as a loss (`ssim_loss`, `ssim_grad_host`; csrc/ssimloss.hip): the gradient of that definition with respect to the first
+image.  With the five filtered maps mx, my, xx, yy, xy at a valid position and sx = xx - mx^2, sy = yy - my^2, sxy = xy - mx my,
+A1 = 2 mx my + C1, A2 = 2 sxy + C2, B1 = mx^2 + my^2 + C1, B2 = sx + sy + C2, S = A1 A2 / (B1 B2):
+  dmx = (2 my A2 - 2 my A1) / (B1 B2) - S (2 mx / B1 - 2 mx / B2),   dxx = -S / B2,   dxy = 2 A1 / (B1 B2)
+  d ssim / d x = [W^T(dmx) + 2 x W^T(dxx) + y W^T(dxy)] / (3 (H - 10) (W - 10)),   d ssim / d a = d ssim / d x / (hi - lo)
+W^T is the transposed window filter: a full correlation that is zero outside the valid region and returns H x W.  The twin is
+float64; the device evaluates the same formulas in fp32 (second moments as written, xx - mx^2, not around the window mean) and
+carries the sums over tiles in double.
+
 `image_metrics_host` is that definition in code; `image_metrics` runs it on the device (no CPU fallback) and differs from the
 twin only in the order of its sums.  skimage's `structural_similarity` defaults differ in two ways: it uses the sample covariance
 (a factor 121 / 120 on the second moments) and, with `gaussian_weights=True`, crops a border of 5 pixels from a map computed with
@@ -106,6 +115,68 @@ def image_metrics_host(a, b, data_range: Tuple[float, float] = (-1.0, 1.0)) -> I
     return ImageMetrics(mse, psnr, ssim_map.mean(axis=(1, 2, 3)))
 
 
+# ------------------------------------------------------------------ the gradient's host twin
+def _window_taps(dtype) -> np.ndarray:
+    return ssim_window().astype(dtype)
+
+
+def _filter_valid(m: np.ndarray) -> np.ndarray:
+    """`_window_filter` in the dtype of `m`."""
+    g = _window_taps(m.dtype)
+    w = m.shape[-1] - WINDOW_TAPS + 1
+    rows = np.zeros(m.shape[:-1] + (w,), dtype=m.dtype)
+    for k in range(WINDOW_TAPS):
+        rows = rows + g[k] * m[..., k:k + w]
+    h = m.shape[-2] - WINDOW_TAPS + 1
+    out = np.zeros(m.shape[:-2] + (h, w), dtype=m.dtype)
+    for k in range(WINDOW_TAPS):
+        out = out + g[k] * rows[..., k:k + h, :]
+    return out
+
+
+def _filter_transposed(c: np.ndarray) -> np.ndarray:
+    """[..., H - 10, W - 10] -> [..., H, W]: the transpose of `_filter_valid`, along the columns, then along the rows."""
+    g = _window_taps(c.dtype)
+    h, w = c.shape[-2], c.shape[-1]
+    cols = np.zeros(c.shape[:-2] + (h + WINDOW_TAPS - 1, w), dtype=c.dtype)
+    for k in range(WINDOW_TAPS):
+        cols[..., k:k + h, :] += g[k] * c
+    out = np.zeros(cols.shape[:-1] + (w + WINDOW_TAPS - 1,), dtype=c.dtype)
+    for k in range(WINDOW_TAPS):
+        out[..., k:k + w] += g[k] * cols
+    return out
+
+
+def ssim_grad_mapped(x: np.ndarray, y: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """The formulas of the module docstring on mapped images x, y [B,3,H,W], in their dtype (float64 for the twin; the tests
+    evaluate them in float32 to size the device's rounding) -> (ssim [B], d ssim / d x [B,3,H,W])."""
+    t = x.dtype.type
+    c1, c2 = t(C1), t(C2)
+    mx, my, xx, yy, xy = (_filter_valid(m) for m in (x, y, x * x, y * y, x * y))
+    sx, sy, sxy = xx - mx * mx, yy - my * my, xy - mx * my
+    a1, a2 = t(2) * mx * my + c1, t(2) * sxy + c2
+    b1, b2 = mx * mx + my * my + c1, sx + sy + c2
+    inv = t(1) / (b1 * b2)
+    s = a1 * a2 * inv
+    dmx = (t(2) * my * a2 - t(2) * my * a1) * inv - s * (t(2) * mx / b1 - t(2) * mx / b2)
+    dxx = -s / b2
+    dxy = t(2) * a1 * inv
+    n = t(3.0 * s.shape[-2] * s.shape[-1])
+    grad = (_filter_transposed(dmx) + t(2) * x * _filter_transposed(dxx) + y * _filter_transposed(dxy)) / n
+    return s.mean(axis=(1, 2, 3)), grad
+
+
+def ssim_grad_host(a, b, data_range: Tuple[float, float] = (-1.0, 1.0)) -> Tuple[np.ndarray, np.ndarray]:
+    """float [B,3,H,W] images in `data_range` -> float64 (ssim [B], d ssim / d a [B,3,H,W]): `image_metrics_host`'s SSIM and its
+    gradient with respect to the first image, by the formulas of the module docstring.  ValueError below 11 x 11."""
+    if np.asarray(a).dtype == np.uint8:
+        raise ValueError("ssim_grad_host takes float images [B,3,H,W]")
+    x, y = _mapped_pair(a, b, data_range)
+    lo, hi = (float(np.float32(v)) for v in data_range)
+    ssim, gx = ssim_grad_mapped(x, y)
+    return ssim, gx / (hi - lo)
+
+
 # ------------------------------------------------------------------ the device function
 def _require_hip(t, what: str) -> None:
     if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
@@ -156,6 +227,66 @@ def image_metrics(a: torch.Tensor, b: torch.Tensor, data_range: Tuple[float, flo
     results are bitwise reproducible and do not depend on the batch an image is scored in."""
     out = _metrics_out3(a, b, data_range)
     return ImageMetrics(out[:, 0], out[:, 1], out[:, 2])
+
+
+def ssim_grad(a: torch.Tensor, b: torch.Tensor, data_range: Tuple[float, float] = (-1.0, 1.0), *,
+              upstream: Optional[torch.Tensor] = None, need_grad: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """llie_ssim_grad_f32: fp32 NCHW [B,3,H,W] on a HIP device -> (ssim fp32 [B], upstream_b * d ssim_b / d a, or None with
+    `need_grad=False`).  `upstream` is a device fp32 [B] (default: ones).  No synchronisation."""
+    _require_hip(a, "ssim_loss")
+    _require_hip(b, "ssim_loss")
+    if a.shape != b.shape or a.device != b.device or a.dtype != torch.float32 or b.dtype != torch.float32 or a.dim() != 4 or a.shape[1] != 3:
+        raise ValueError(f"the two images must be fp32 NCHW [B,3,H,W] of one shape on one device, got {a.dtype} {tuple(a.shape)} and "
+                         f"{b.dtype} {tuple(b.shape)}")
+    batch, h, w = a.shape[0], a.shape[2], a.shape[3]
+    a, b = a.detach().contiguous(), b.detach().contiguous()
+    dev = a.device
+    if upstream is not None:
+        if upstream.dtype != torch.float32 or tuple(upstream.shape) != (batch,) or upstream.device != dev:
+            raise ValueError(f"upstream must be fp32 [{batch}] on {dev}")
+        upstream = upstream.detach().contiguous()
+    L = N.lib()
+    nbytes = int(L.llie_ssim_grad_scratch_bytes(batch, h, w))
+    if nbytes < 0:
+        N.check(nbytes, f"ssim_loss: {batch} images of {h} x {w} (at least 1 image of 11 x 11)")
+    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    ssim = torch.empty(batch, dtype=torch.float32, device=dev)
+    da = torch.empty_like(a) if need_grad else None
+    lo, hi = float(data_range[0]), float(data_range[1])
+    with torch.cuda.device(dev):
+        rc = L.llie_ssim_grad_f32(a.data_ptr(), b.data_ptr(), batch, h, w, lo, hi, upstream.data_ptr() if upstream is not None else None,
+                                  ssim.data_ptr(), da.data_ptr() if da is not None else None, scratch.data_ptr(), nbytes,
+                                  torch.cuda.current_stream(dev).cuda_stream)
+    N.check(rc, "ssim_loss")
+    return ssim, da
+
+
+class _SsimLossFn(torch.autograd.Function):
+    """1 - SSIM as an autograd node of the first image: forward = llie_ssim_grad_f32 (value and d ssim / d a in one pass over the
+    images), backward = -grad_output_b times the gradient it wrote."""
+
+    @staticmethod
+    def forward(ctx, a, b, lo, hi):
+        need = ctx.needs_input_grad[0]
+        ssim, da = ssim_grad(a, b, (lo, hi), need_grad=need)
+        if need:
+            ctx.save_for_backward(da)
+        return 1.0 - ssim
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        da, = ctx.saved_tensors
+        return -grad_output.reshape(-1, 1, 1, 1) * da, None, None, None
+
+
+def ssim_loss(a: torch.Tensor, b: torch.Tensor, data_range: Tuple[float, float] = (-1.0, 1.0)) -> torch.Tensor:
+    """1 - SSIM(a, b) per image: fp32 [B], for fp32 NCHW [B,3,H,W] images in `data_range` on a HIP device (no CPU fallback).
+    The SSIM is `image_metrics`' definition evaluated in fp32.  Differentiable with respect to `a` only (`b` is the reference
+    image: one that requires grad raises ValueError).  Bitwise reproducible, and an image's value and gradient do not depend on
+    the batch it is scored in."""
+    if isinstance(b, torch.Tensor) and b.requires_grad:
+        raise ValueError("ssim_loss differentiates with respect to `a` only; `b` must not require grad")
+    return _SsimLossFn.apply(a, b, float(data_range[0]), float(data_range[1]))
 
 
 # ------------------------------------------------------------------ evaluation over a validation set

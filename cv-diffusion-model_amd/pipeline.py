@@ -8,6 +8,16 @@ call it unchanged.  The whole denoising loop runs as one launch sequence in libl
 `LowLightLCMDistillation` (low_light_diffusion.py:284-408) is the teacher -> student consistency-distillation
 objective on the same engine: the denoisers run through the engine's forward / backward passes, the arithmetic
 around them and the EMA update through csrc/distill.hip.
+
+The x0 term (`x0_loss`, `x0_loss_host`; csrc/ssimloss.hip, llie_x0_loss) is an image-space addition to the training loss:
+SSIM and L1 of the clean image a training step implies against the normal-light image.  With `out` the network output
+[B,3,H,W], `x_t` the noised input, `y` the normal-light image, abar_b = alphas_cumprod[t_b], alpha = sqrt(abar), sigma = sqrt(1 - abar):
+  x^ = p_b x_t + q_b out        epsilon prediction: p = 1 / alpha, q = -sigma / alpha;  v prediction: p = alpha, q = -sigma;  not clamped
+  L_x0 = (1 / B) sum_b w_b [ssim_weight (1 - SSIM_b(x^, y)) + l1_weight mean|x^_b - y_b|],   w_b = abar_b
+  SSIM_b is metrics.py's definition with data_range (-1, 1); the L1 mean runs over the 3 H W values in model units (F.l1_loss)
+  dL_x0/dout = (w_b / B) q_b [-ssim_weight / 2 dSSIM_b/dx + l1_weight sign(x^ - y) / (3 H W)]     (dSSIM/dx: metrics.py)
+The weight w_b = abar_b keeps the gradient factor w q = -alpha sigma bounded under epsilon prediction.  A sample with abar_b == 0
+(t = 999 of the zero-SNR table, where x0 is undefined) contributes exactly 0 to the loss and nothing to the gradient.
 """
 from __future__ import annotations
 
@@ -16,6 +26,7 @@ import ctypes as C
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
+import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -79,7 +90,8 @@ class LowLightDiffusion(nn.Module):
         (llie_unet_backward): `loss.backward()` fills `.grad` of every parameter, so the reference trainer's
         step (trainer.py:269-338: AdamW, GradScaler, clip_grad_norm_, EMA) runs unchanged on top.
         With a `prediction_type="v_prediction"` scheduler the dict also holds the velocity `target`
-        (lcm_scheduler.py:282-305; the reference never wires it into `compute_loss`).
+        (lcm_scheduler.py:282-305; the reference never wires it into `compute_loss`).  A caller that forms the x0 term needs
+        the noised input too: it is `scheduler.add_noise(normal_light, noise, timesteps)` of the returned draws.
         Without `normal_light`: `enhance(low_light)`."""
         if normal_light is None:
             return self.enhance(low_light)
@@ -203,22 +215,31 @@ class LowLightDiffusion(nn.Module):
 
     # ------------------------------------------------------------------ loss (:250-277)
     def compute_loss(self, low_light: torch.Tensor, normal_light: torch.Tensor, loss_type: str = "mse", *,
-                     use_velocity_target: bool = False) -> torch.Tensor:
+                     use_velocity_target: bool = False, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0) -> torch.Tensor:
         """Regresses the denoiser output against the drawn noise, as the reference does whatever the scheduler's
         prediction type (low_light_diffusion.py:262-275).  `use_velocity_target=True` (extension, needs a
         `prediction_type="v_prediction"` scheduler) regresses against `scheduler.get_velocity` instead -- the v-pred MSE of
-        BASELINE config 5, which the reference defines (lcm_scheduler.py:282-305) but never wires into its loss."""
+        BASELINE config 5, which the reference defines (lcm_scheduler.py:282-305) but never wires into its loss.
+        `x0_ssim_weight` / `x0_l1_weight` (extension): when either is non-zero, `x0_loss` of the predicted clean image against
+        `normal_light` is added (the module docstring has the definition); with both 0 nothing changes."""
+        _check_x0_weights(x0_ssim_weight, x0_l1_weight)
         out = self.forward(low_light, normal_light)
         if use_velocity_target and "target" not in out:
             raise ValueError("use_velocity_target needs a scheduler with prediction_type='v_prediction'")
         pred, noise = out["noise_pred"], (out["target"] if use_velocity_target else out["noise"])
         if loss_type == "mse":
-            return F.mse_loss(pred, noise)
-        if loss_type == "huber":
-            return F.huber_loss(pred, noise)
-        if loss_type == "l1":
-            return F.l1_loss(pred, noise)
-        raise ValueError(f"Unknown loss type: {loss_type}")
+            loss = F.mse_loss(pred, noise)
+        elif loss_type == "huber":
+            loss = F.huber_loss(pred, noise)
+        elif loss_type == "l1":
+            loss = F.l1_loss(pred, noise)
+        else:
+            raise ValueError(f"Unknown loss type: {loss_type}")
+        if x0_ssim_weight != 0 or x0_l1_weight != 0:
+            noisy = self.scheduler.add_noise(normal_light, out["noise"], out["timesteps"])  # forward's x_t, the same bits
+            loss = loss + x0_loss(self.scheduler, pred, noisy, normal_light, out["timesteps"], velocity=use_velocity_target,
+                                  ssim_weight=x0_ssim_weight, l1_weight=x0_l1_weight)
+        return loss
 
     def get_model_size(self) -> Dict[str, float]:
         return self.unet.get_memory_footprint()
@@ -283,6 +304,119 @@ class _ConsistencyLossFn(torch.autograd.Function):
     def backward(ctx, grad_output):
         d, = ctx.saved_tensors
         return (d * grad_output,) + (None,) * 6
+
+
+# ---------------------------------------------------------------------- the x0 term (module docstring)
+def _check_x0_weights(ssim_weight: float, l1_weight: float) -> None:
+    if not (ssim_weight >= 0 and l1_weight >= 0) or ssim_weight == float("inf") or l1_weight == float("inf"):
+        raise ValueError(f"x0_ssim_weight and x0_l1_weight must be finite and >= 0, got {ssim_weight} and {l1_weight}")
+
+
+def x0_term_eval(out: np.ndarray, x_t: np.ndarray, y: np.ndarray, acp: np.ndarray, velocity: bool, ssim_weight: float,
+                 l1_weight: float) -> Tuple[float, np.ndarray]:
+    """The formulas of the module docstring in the dtype of `out` (float64 for `x0_loss_host`; the tests evaluate them in
+    float32 to size the device's rounding) -> (term, d term / d out)."""
+    from .metrics import ssim_grad_mapped
+    t = out.dtype.type
+    batch = out.shape[0]
+    grad = np.zeros_like(out)
+    term = t(0)
+    ws, w1 = t(ssim_weight), t(l1_weight)
+    for b in range(batch):
+        a = t(acp[b])
+        if a == 0:
+            continue
+        alpha, sigma = np.sqrt(a), np.sqrt(t(1) - a)
+        p, q = (alpha, -sigma) if velocity else (t(1) / alpha, -sigma / alpha)
+        xh, yb = p * x_t[b:b + 1] + q * out[b:b + 1], y[b:b + 1]
+        ssim, dx = ssim_grad_mapped((xh + t(1)) / t(2), (yb + t(1)) / t(2))
+        d = xh - yb
+        term = term + a * (ws * (t(1) - ssim[0]) + w1 * np.abs(d).mean(dtype=out.dtype))
+        grad[b] = (a / t(batch)) * q * (-ws * (dx[0] / t(2)) + w1 * (np.sign(d[0]) / t(d[0].size)))
+    return term / t(batch), grad
+
+
+def x0_loss_host(out, x_t, normal, acp_t, velocity: bool, ssim_weight: float, l1_weight: float) -> Tuple[float, np.ndarray]:
+    """The definition of the x0 term in float64 NumPy: out / x_t / normal [B,3,H,W], acp_t [B] = alphas_cumprod[t_b] ->
+    (term, d term / d out [B,3,H,W]).  A sample with acp_t == 0 contributes exactly 0 to both.  ValueError for negative weights,
+    mismatched shapes and images below 11 x 11."""
+    _check_x0_weights(ssim_weight, l1_weight)
+    out, x_t, y = (np.asarray(v, dtype=np.float64) for v in (out, x_t, normal))
+    acp = np.asarray(acp_t, dtype=np.float64).reshape(-1)
+    if out.ndim != 4 or out.shape[1] != 3 or x_t.shape != out.shape or y.shape != out.shape or acp.shape[0] != out.shape[0]:
+        raise ValueError(f"out / x_t / normal must be [B,3,H,W] and acp_t [B], got {out.shape}, {x_t.shape}, {y.shape}, {acp.shape}")
+    if out.shape[2] < 11 or out.shape[3] < 11:
+        raise ValueError(f"images must be at least 11 x 11 (one window), got {out.shape[2]} x {out.shape[3]}")
+    if ssim_weight == 0 and l1_weight == 0:
+        return 0.0, np.zeros_like(out)
+    term, grad = x0_term_eval(out, x_t, y, acp, velocity, ssim_weight, l1_weight)
+    return float(term), grad
+
+
+def x0_loss_device(scheduler: LCMScheduler, out: torch.Tensor, x_t: torch.Tensor, normal: torch.Tensor, timesteps: torch.Tensor,
+                   velocity: bool, ssim_weight: float, l1_weight: float, d_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """llie_x0_loss: the term as a 0-d fp32 device tensor; its gradient with respect to `out` is ADDED to `d_out` (fp32,
+    contiguous, shaped like `out`) when one is given.  No synchronisation, no autograd."""
+    _require_hip(out, "x0_loss")
+    _check_x0_weights(ssim_weight, l1_weight)
+    dev = out.device
+    if out.dim() != 4 or out.shape[1] != 3 or x_t.shape != out.shape or normal.shape != out.shape or tuple(timesteps.shape) != (out.shape[0],):
+        raise ValueError(f"out / x_t / normal must be [B,3,H,W] and timesteps [B], got {tuple(out.shape)}, {tuple(x_t.shape)}, "
+                         f"{tuple(normal.shape)}, {tuple(timesteps.shape)}")
+    acp = scheduler._acp_on(dev)
+    if timesteps.device.type == "cpu" and timesteps.numel() and (int(timesteps.min()) < 0 or int(timesteps.max()) >= acp.numel()):
+        # device-resident timesteps cannot be checked without a synchronisation: the kernels turn one outside the table into a NaN
+        # loss and gradient for that sample instead of indexing with it (as LCMScheduler.add_noise does)
+        raise ValueError(f"timesteps must lie in [0, {acp.numel()})")
+    out, x_t, normal = (v.detach().to(device=dev, dtype=torch.float32).contiguous() for v in (out, x_t, normal))
+    t = timesteps.to(device=dev, dtype=torch.long).contiguous()
+    if d_out is not None and (d_out.dtype != torch.float32 or not d_out.is_contiguous() or d_out.shape != out.shape or d_out.device != dev):
+        raise ValueError("d_out must be contiguous fp32, shaped like out, on its device")
+    b, h, w = out.shape[0], out.shape[2], out.shape[3]
+    L = N.lib()
+    nbytes = int(L.llie_ssim_grad_scratch_bytes(b, h, w))
+    if nbytes < 0:
+        N.check(nbytes, f"x0_loss: {b} images of {h} x {w} (at least 1 image of 11 x 11)")
+    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        N.check(L.llie_x0_loss(out.data_ptr(), x_t.data_ptr(), normal.data_ptr(), t.data_ptr(), acp.data_ptr(), acp.numel(),
+                               1 if velocity else 0, float(ssim_weight), float(l1_weight), loss.data_ptr(),
+                               d_out.data_ptr() if d_out is not None else None, b, h, w, scratch.data_ptr(), nbytes,
+                               torch.cuda.current_stream(dev).cuda_stream), "x0_loss")
+    return loss
+
+
+class _X0LossFn(torch.autograd.Function):
+    """The x0 term as an autograd node of the network output: forward = llie_x0_loss into a zeroed gradient buffer, backward =
+    that buffer times grad_output (so a GradScaler's scaled backward works)."""
+
+    @staticmethod
+    def forward(ctx, out, scheduler, x_t, normal, timesteps, velocity, ssim_weight, l1_weight):
+        d = torch.zeros(out.shape, dtype=torch.float32, device=out.device) if ctx.needs_input_grad[0] else None
+        loss = x0_loss_device(scheduler, out, x_t, normal, timesteps, velocity, ssim_weight, l1_weight, d)
+        if d is not None:
+            ctx.save_for_backward(d)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        d, = ctx.saved_tensors
+        return (d * grad_output,) + (None,) * 7
+
+
+def x0_loss(model_or_scheduler, out: torch.Tensor, x_t: torch.Tensor, normal: torch.Tensor, timesteps: torch.Tensor, *,
+            velocity: bool = False, ssim_weight: float, l1_weight: float) -> torch.Tensor:
+    """The x0 term of the module docstring as a 0-d device tensor, differentiable with respect to `out` (the network output of
+    `forward`; `x_t` is the noised input it was computed from, `scheduler.add_noise(normal, noise, timesteps)`).  `velocity=True`
+    reads `out` as a v prediction.  `model_or_scheduler` supplies the alpha-bar table (a LowLightDiffusion or its LCMScheduler).
+    HIP device only; one call of llie_x0_loss, no synchronisation."""
+    scheduler = getattr(model_or_scheduler, "scheduler", model_or_scheduler)
+    if not isinstance(scheduler, LCMScheduler):
+        raise ValueError(f"x0_loss takes a LowLightDiffusion or an LCMScheduler, got {type(model_or_scheduler).__name__}")
+    if x_t.requires_grad or normal.requires_grad:
+        raise ValueError("x0_loss differentiates with respect to `out` only; x_t and normal must not require grad")
+    return _X0LossFn.apply(out, scheduler, x_t, normal, timesteps, bool(velocity), float(ssim_weight), float(l1_weight))
 
 
 class LowLightLCMDistillation(nn.Module):

@@ -226,9 +226,15 @@ class LowLightTrainer:
     `model` is a LowLightDiffusion on a HIP device, the loaders are DevicePairLoaders on the same device; there is no CPU
     fallback.  The engine runs in `resolved_compute_dtype(config)`; a FusedGradScaler exists only for fp16.  Every draw comes
     from generators seeded from (config.seed, epoch): the global generator is neither read nor advanced, and a resumed run
-    continues bit for bit."""
+    continues bit for bit.
 
-    def __init__(self, model: LowLightDiffusion, train_loader, val_loader=None, config: Optional[TrainingConfig] = None):
+    `x0_ssim_weight` / `x0_l1_weight` (extension) go to TrainStep: the training loss gains the x0 term of pipeline.py, SSIM / L1
+    of the predicted clean image against the normal-light image.  They are constructor arguments, not TrainingConfig fields,
+    and are not written into checkpoints: a caller that resumes a run passes them again.  The validation loss stays the
+    reference's MSE."""
+
+    def __init__(self, model: LowLightDiffusion, train_loader, val_loader=None, config: Optional[TrainingConfig] = None, *,
+                 x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0):
         self.config = config or TrainingConfig()
         cfg = self.config
         params = list(model.parameters())
@@ -255,7 +261,8 @@ class LowLightTrainer:
                                     max_grad_norm=cfg.gradient_clip, ema_decay=cfg.ema_decay if cfg.use_ema else None)
         self.scheduler = make_lr_scheduler(self.optimizer, cfg, len(train_loader))
         self.scaler = FusedGradScaler() if dtype == "fp16" else None
-        self.step = TrainStep(model, self.optimizer, loss_type=cfg.loss_type, grad_scaler=self.scaler)
+        self.step = TrainStep(model, self.optimizer, loss_type=cfg.loss_type, grad_scaler=self.scaler,
+                              x0_ssim_weight=x0_ssim_weight, x0_l1_weight=x0_l1_weight)
         self._names = [name for name, _ in model.named_parameters()]
 
         self.epoch = 0
@@ -462,15 +469,16 @@ class LowLightTrainer:
 
 
 def train_model(train_data_dir: str, val_data_dir: Optional[str] = None, config: Optional[TrainingConfig] = None,
-                device="cuda") -> LowLightTrainer:
+                device="cuda", *, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0) -> LowLightTrainer:
     """Training entry point (trainer.py:459-496): loaders from the folders (create_device_dataloaders), a fresh model, a trainer,
-    `train()`; returns the trainer."""
+    `train()`; returns the trainer.  `x0_ssim_weight` / `x0_l1_weight`: as LowLightTrainer's."""
     config = config or TrainingConfig()
     train_loader, val_loader = create_device_dataloaders(train_root=train_data_dir, val_root=val_data_dir, batch_size=config.batch_size,
                                                          image_size=config.image_size, use_synthetic=config.use_synthetic,
                                                          device=device, seed=config.seed)
     model = LowLightDiffusion(unet_variant=config.unet_variant, image_size=config.image_size,
                               num_inference_steps=config.num_inference_steps).to(train_loader.store.device)
-    trainer = LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config)
+    trainer = LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config,
+                              x0_ssim_weight=x0_ssim_weight, x0_l1_weight=x0_l1_weight)
     trainer.train()
     return trainer

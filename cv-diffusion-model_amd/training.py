@@ -322,16 +322,22 @@ class TrainStep:
     `loss_type` / `use_velocity_target` as LowLightDiffusion.compute_loss.  With `grad_scaler` (a FusedGradScaler: fp16 engines
     need one, their unscaled gradients underflow) d(loss)/d(eps) is multiplied by the device scale before the backward pass,
     which is `scaler.scale(loss).backward()`, and the optimiser unscales, skips and updates the scale on the device.
+    `x0_ssim_weight` / `x0_l1_weight` (>= 0): when either is non-zero, the x0 term of pipeline.py (SSIM / L1 of the predicted
+    clean image against `normal_light`) is added to the loss, and one call of llie_x0_loss adds its gradient into d(loss)/d(eps)
+    before the grad-scaler multiplication; with both 0 the step makes no such call and is unchanged bit for bit.
     Returns the loss (device scalar, unscaled)."""
 
     def __init__(self, model, optimizer: FusedAdamW, loss_type: str = "mse", use_velocity_target: bool = False, group=None,
-                 grad_scaler: Optional[FusedGradScaler] = None):
+                 grad_scaler: Optional[FusedGradScaler] = None, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0):
+        from .pipeline import _check_x0_weights
         if loss_type not in ("mse", "huber", "l1"):
             raise ValueError(f"Unknown loss type: {loss_type}")
         if grad_scaler is not None and not isinstance(grad_scaler, FusedGradScaler):
             raise ValueError("grad_scaler must be a FusedGradScaler")
+        _check_x0_weights(x0_ssim_weight, x0_l1_weight)
         self.model, self.opt, self.loss_type, self.velocity, self.group = model, optimizer, loss_type, use_velocity_target, group
         self.grad_scaler = grad_scaler
+        self.x0_ssim_weight, self.x0_l1_weight = float(x0_ssim_weight), float(x0_l1_weight)
         self._order = _engine_order(model.unet, optimizer, "TrainStep")
         if use_velocity_target and getattr(model.scheduler.config, "prediction_type", "epsilon") != "v_prediction":
             raise ValueError("use_velocity_target needs a scheduler with prediction_type='v_prediction'")
@@ -375,6 +381,11 @@ class TrainStep:
                 a = diff.abs()
                 loss = torch.where(a < 1.0, 0.5 * diff * diff, a - 0.5).mean()
                 d_eps = diff.clamp(-1.0, 1.0) / n
+            if self.x0_ssim_weight != 0.0 or self.x0_l1_weight != 0.0:
+                from .pipeline import x0_loss_device
+                d_eps = d_eps.contiguous()
+                loss = loss + x0_loss_device(model.scheduler, eps, noisy, normal_light, t, self.velocity, self.x0_ssim_weight,
+                                             self.x0_l1_weight, d_eps)  # adds d(term)/d(eps) into d_eps
             if self.grad_scaler is not None:
                 d_eps = d_eps * self.grad_scaler._device_scale(dev)
             N.check(L.llie_unet_backward(h.h, d_eps.data_ptr(), self._flat.data_ptr(), b, self._ws.data_ptr(), nbytes, st),

@@ -403,6 +403,39 @@ int llie_image_metrics_f32(const float* a, const float* b, int batch, int H, int
 int llie_image_metrics_u8(const uint8_t* a, const uint8_t* b, int batch, int H, int W, double* out3, void* scratch,
                           int64_t scratch_bytes, llie_stream stream);
 
+/* SSIM as a training loss: the SSIM of the definition above in fp32 (sums over tiles and images in double) with its gradient
+ * with respect to the first image, and the x0 term of a training step built on it.  At a valid position, with the five filtered
+ * maps mx, my, xx, yy, xy and sx = xx - mx^2, sy = yy - my^2, sxy = xy - mx my, A1 = 2 mx my + C1, A2 = 2 sxy + C2,
+ * B1 = mx^2 + my^2 + C1, B2 = sx + sy + C2, S = A1 A2 / (B1 B2):
+ *   dmx = (2 my A2 - 2 my A1) / (B1 B2) - S (2 mx / B1 - 2 mx / B2),   dxx = -S / B2,   dxy = 2 A1 / (B1 B2)
+ *   dSSIM/dx = [W^T(dmx) + 2 x W^T(dxx) + y W^T(dxy)] / (3 (H - 10) (W - 10)),   dSSIM/da = dSSIM/dx / (hi - lo)
+ * with W^T the transposed window filter (a full correlation, zero outside the valid region, H x W).
+ *   llie_ssim_grad_f32:  a, b fp32 NCHW [batch][3][H][W] in (lo, hi) -> ssim_out [batch] fp32 and, unless da is NULL,
+ *                        da = upstream_b * dSSIM_b/da (stored); upstream is device fp32 [batch] or NULL (= 1).  ssim_out is the
+ *                        same bits with and without da.
+ *   llie_x0_loss:        out (the network output), x_t (the noised input), normal (the normal-light image) fp32 NCHW
+ *                        [batch][3][H][W]; t device int64 [batch]; alphas_cumprod device fp32 [table_n]; abar = alphas_cumprod[t_b],
+ *                        alpha = sqrt(abar), sigma = sqrt(1 - abar).  The predicted clean image is x^ = p x_t + q out, not clamped:
+ *                        p = 1 / alpha, q = -sigma / alpha (velocity == 0, epsilon prediction) or p = alpha, q = -sigma
+ *                        (velocity != 0, v prediction).  With w_b = abar_b and the data range (-1, 1):
+ *                          *loss_out = (1 / B) sum_b w_b [lambda_s (1 - SSIM_b(x^, normal)) + lambda_1 mean|x^_b - normal_b|]
+ *                          d_out    += (w_b / B) q_b [-lambda_s / 2 dSSIM_b/dx + lambda_1 sign(x^ - normal) / (3 H W)]
+ *                        (d_out may be NULL: the loss alone).  A sample with abar == 0 (the last step of a zero-SNR table)
+ *                        contributes exactly 0 to the loss and its rows of d_out are not written; 1 / alpha is not evaluated.
+ * Four (three) launches on the stream, no atomics, no host synchronisation: every gradient element has one writer and the order
+ * of every sum depends on H and W alone, so results are bitwise reproducible and an image's values are the same alone or in a
+ * batch.  The host implementations are metrics.ssim_grad_host and pipeline.x0_loss_host (float64).
+ * Checked before any HIP call: a NULL pointer (other than upstream, da, d_out), batch < 1, lo == hi or not finite, a negative or
+ * non-finite lambda, table_n < 1 return LLIE_ERR_ARG; H < 11 or W < 11 LLIE_ERR_SHAPE; scratch_bytes below
+ * llie_ssim_grad_scratch_bytes LLIE_ERR_WORKSPACE.  The timesteps live on the device and are not read by the host: one outside
+ * [0, table_n) never indexes the table and makes that sample's loss and gradient NaN, as llie_add_noise does. */
+int64_t llie_ssim_grad_scratch_bytes(int batch, int H, int W);
+int llie_ssim_grad_f32(const float* a, const float* b, int batch, int H, int W, float lo, float hi, const float* upstream,
+                       float* ssim_out, float* da, void* scratch, int64_t scratch_bytes, llie_stream stream);
+int llie_x0_loss(const float* out, const float* x_t, const float* normal, const int64_t* t, const float* alphas_cumprod, int table_n,
+                 int velocity, float lambda_s, float lambda_1, float* loss_out, float* d_out, int batch, int H, int W, void* scratch,
+                 int64_t scratch_bytes, llie_stream stream);
+
 /* The trainer's per-epoch sample sheet (LowLightTrainer.generate_samples / _save_comparison, src/training/trainer.py:365-410):
  * torchvision's make_grid(cat([low, enhanced, normal]), nrow=n) with its defaults (padding 2, pad value 0) followed by
  * save_image's quantisation, in one launch.

@@ -10,6 +10,11 @@ the reference's fp16 with a loss scaler; --dtype pins the engine precision inste
 draw, so a run is reproducible and --resume continues it bit for bit.  Checkpoints (checkpoint_epoch_{e}.pt, best_model.pt,
 final_model.pt under --checkpoint_dir) are what scripts/inference.py and scripts/evaluate.py read; the per-epoch sample sheets go
 to --output_dir.  One JSON line per epoch is printed: epoch, train_loss, lr, val_loss, psnr, ssim.
+
+  python scripts/train.py --data_dir LOL/our485 --val_dir LOL/eval15 --x0_ssim_weight 0.5 --x0_l1_weight 0.5
+
+adds the image-space term to --loss: SSIM / L1 of the clean image each step implies against the normal-light image (train_loss
+then includes it; val_loss stays the MSE).  The two weights are not stored in checkpoints: pass them again with --resume.
 """
 import argparse
 import importlib
@@ -57,6 +62,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--checkpoint_dir", type=str, default="checkpoints", help="Checkpoint directory")
     p.add_argument("--save_interval", type=int, default=5, help="epochs between checkpoint_epoch_{e}.pt files")
     p.add_argument("--sample_interval", type=int, default=1, help="epochs between sample sheets")
+    p.add_argument("--x0_ssim_weight", type=float, default=0.0,
+                   help="weight of 1 - SSIM of the predicted clean image against the normal-light image, added to --loss")
+    p.add_argument("--x0_l1_weight", type=float, default=0.0, help="weight of the L1 distance of the same two images")
     return p
 
 
@@ -73,6 +81,12 @@ def config_from_args(args) -> "M.TrainingConfig":
         output_dir=args.output_dir, checkpoint_dir=args.checkpoint_dir,
         use_wandb=args.use_wandb, wandb_project=args.project, resume_from=args.resume,
         compute_dtype=args.dtype, seed=args.seed, use_synthetic=args.use_synthetic)
+
+
+def x0_weights_from_args(args) -> dict:
+    """The keywords LowLightTrainer and train_model take beside the config (not TrainingConfig fields, not in checkpoints:
+    a run resumed with --resume passes the same two flags again)."""
+    return {"x0_ssim_weight": args.x0_ssim_weight, "x0_l1_weight": args.x0_l1_weight}
 
 
 def main(argv=None) -> int:
@@ -97,7 +111,8 @@ def main(argv=None) -> int:
     size = model.get_model_size()
     print(f"  Parameters: {size['num_params']:,}")
 
-    trainer = M.LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config)
+    trainer = M.LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config,
+                                **x0_weights_from_args(args))
     print(f"  Engine precision: {model.compute_dtype}, loss scaler: {trainer.scaler is not None}, EMA: {config.use_ema}")
     trainer.train(on_epoch=lambda log: print(json.dumps(log), flush=True))
     print("\nTraining complete!")
