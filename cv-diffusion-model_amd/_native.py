@@ -36,6 +36,7 @@ EXPORTS = [
     "llie_dwconv3x3_backward", "llie_groupnorm_backward_from_slab", "llie_bias_grad", "llie_bias_grad_floats", "llie_pack_planes",
     "llie_add_into", "llie_sin_embed", "llie_pointwise_backward",
     "llie_tile_count", "llie_tile_origins", "llie_tile_gather_u8", "llie_tile_gather_f32", "llie_tile_blend_u8",
+    "llie_tile_sync_step",
     "llie_aug_pair_u8", "llie_aug_synth_u8",
     "llie_image_metrics_scratch_bytes", "llie_image_metrics_f32", "llie_image_metrics_u8", "llie_comparison_grid_u8",
     "llie_upconv_fold_elems", "llie_upconv_fold_weights", "llie_conv3x3_upfold", "llie_conv3x3_upfold_tiles",
@@ -168,6 +169,7 @@ def lib() -> C.CDLL:
     L.llie_tile_gather_u8.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp]
     L.llie_tile_gather_f32.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]
     L.llie_tile_blend_u8.argtypes = [vp, ci, ci, ci, ci, vp, vp]
+    L.llie_tile_sync_step.argtypes = [vp, ci, ci, ci, ci, vp, vp, C.POINTER(StepCoef), vp, vp, vp]
     L.llie_frame_shape_ok.argtypes = [vp, ci, ci, ci]
     L.llie_frame_workspace_bytes.argtypes = [vp, ci, ci, ci, ci]
     L.llie_frame_workspace_bytes.restype = i64

@@ -502,6 +502,14 @@ int llie_tile_blend_u8(const float* tiles, int H, int W, int S, int v, uint8_t* 
   return kerr("tile_blend_u8", launch_tile_blend_u8(tiles, TilePlan{H, W, S, v, 0, 1}, img, hs(stream)), LLIE_ERR_ARG, nullptr);
 }
 
+int llie_tile_sync_step(const float* eps_tiles, int H, int W, int S, int v, const float* canvas_in, const float* noise,
+                        const llie_step_coef* k, float* canvas_out, uint8_t* img, llie_stream stream) {
+  if (!eps_tiles || !canvas_in || !k || !canvas_out) return LLIE_ERR_ARG;
+  const StepCoef c{k->sqrt_alpha_t, k->sqrt_beta_t, k->sqrt_alpha_prev, k->sqrt_beta_prev, k->is_last, k->v_prediction, k->clamp_x0};
+  return kerr("tile_sync_step", launch_tile_sync_step(eps_tiles, TilePlan{H, W, S, v, 0, 1}, canvas_in, noise, c, canvas_out, img, hs(stream)),
+              LLIE_ERR_ARG, nullptr);
+}
+
 int llie_frame_pad(int L) { return L > 0 && L <= (1 << 24) ? frame_pad(L) : LLIE_ERR_ARG; }
 int llie_frame_load_u8(const uint8_t* img, int H, int W, float* out, llie_stream stream) {
   if (!img || !out) return LLIE_ERR_ARG;

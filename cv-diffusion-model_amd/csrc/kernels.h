@@ -585,6 +585,12 @@ hipError_t launch_tile_gather_f32(const float* canvas, int planes, const TilePla
 // tiles fp32 [T][3][S][S] (every tile of the plan) -> img u8 [H][W][3]: feathered weighted mean in ascending tile order, then
 // (r + 1) * 127.5 clipped and truncated; one thread per 4 output pixels, no atomics
 hipError_t launch_tile_blend_u8(const float* tiles, const TilePlan& p, uint8_t* img, hipStream_t s);
+// One LCM step of the latent canvas fp32 [3][max(H,S)][max(W,S)] the tiles of an image share: eps fp32 [T][3][S][S] (every tile
+// of the plan) is fused per canvas pixel -- the one covering tile's value, or the blend's weighted mean in ascending tile order --
+// and goes through lcm_step_kernel's arithmetic with the canvas and `noise` (same shape; may be NULL when c.is_last).  canvas_out
+// may be canvas_in.  img (or NULL): u8 [H][W][3], the blend's bytes of the new canvas.  One thread per 4 canvas pixels, no atomics
+hipError_t launch_tile_sync_step(const float* eps, const TilePlan& p, const float* canvas_in, const float* noise, const StepCoef& c,
+                                 float* canvas_out, uint8_t* img, hipStream_t s);
 
 // Whole frames at their own size (tiles.hip): a side L is padded to frame_pad(L), the next multiple of 8 and at least 64 -- the
 // sizes llie_frame_shape_ok accepts -- by replicating the edge.

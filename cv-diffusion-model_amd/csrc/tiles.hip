@@ -6,6 +6,10 @@
 //   tile_blend_u8:    per pixel and channel, over the covering tiles in ascending tile number:
 //                       g = w[Y - oy] * w[X - ox];  num = num + val * g;  den = den + g     (separate fp32 operations)
 //                     out = (uint8) trunc(min(max((num / den + 1.0f) * 127.5f, 0), 255)),  w[k] = min(k + 1, S - k, v) / v  (1 if v == 0)
+//   tile_sync_step:   one LCM step of the latent canvas [3][Hc][Wc] (Hc / Wc = max(H / W, S)) every tile of an image shares: per
+//                     canvas pixel and channel, e = the eps of the one covering tile, or num / den of tile_blend_u8's sums over
+//                     eps when several cover it; then lcm_step_kernel's arithmetic (small.hip) on (e, canvas, noise), written
+//                     back to the canvas, and on request tile_blend_u8's bytes of the result for y < H, x < W
 //
 //
 // Whole frames at their own size (llie_enhance_hw), Hp / Wp = frame_pad(H) / frame_pad(W):
@@ -165,6 +169,116 @@ __global__ void __launch_bounds__(kTileThreads) tile_blend_u8_kernel(const float
   }
 }
 
+// One thread per four consecutive x of a canvas row, all three channels.  The plan of (Hc, Wc) is the plan of (H, W) and its
+// tiles cover the canvas, so every pixel has at least one tile.  A thread reads its own four canvas values of a plane before it
+// writes them and no other thread touches them: canvas_out may be canvas_in.  img (or NULL) takes the bytes of the new canvas.
+__global__ void __launch_bounds__(kTileThreads) tile_sync_step_kernel(const float* __restrict__ eps, TilePlan p, int ny, int nx,
+                                                                      const float* canvas_in, const float* __restrict__ noise, StepCoef sc,
+                                                                      float* canvas_out, uint8_t* __restrict__ img) {
+#pragma clang fp contract(off)
+  const int S = p.S, v = p.v;
+  const int Hc = max(p.H, S), Wc = max(p.W, S);
+  const int qpr = (Wc + 3) >> 2;
+  const int64_t q = (int64_t)blockIdx.x * kTileThreads + threadIdx.x;
+  if (q >= (int64_t)qpr * Hc) return;
+  const int Y = (int)(q / qpr), X0 = (int)(q - (int64_t)Y * qpr) * 4;
+  const int Xl = min(X0 + 3, Wc - 1);
+  int ylo, yhi, xlo, xhi, unused;
+  tile_cover(Y, Hc, S, ny, ylo, yhi);
+  tile_cover(X0, Wc, S, nx, xlo, unused);
+  tile_cover(Xl, Wc, S, nx, unused, xhi);
+  float num[4][3], den[4], one[4][3];  // one: the eps of the covering tile seen last, used where it is the only one
+  int cover[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    den[k] = num[k][0] = num[k][1] = num[k][2] = one[k][0] = one[k][1] = one[k][2] = 0.0f;
+    cover[k] = 0;
+  }
+  for (int iy = ylo; iy <= yhi; ++iy) {
+    const int ty = Y - tile_axis_origin(iy, Hc, S, ny);
+    const float wy = tile_window(ty, S, v);
+    for (int ix = xlo; ix <= xhi; ++ix) {  // ascending tile number iy * nx + ix
+      const int tx = X0 - tile_axis_origin(ix, Wc, S, nx);
+      const float* src = eps + (((size_t)(iy * nx + ix) * 3) * S + ty) * S;
+      src += tx;  // dereferenced only where 0 <= tx + k < S
+      if (tx >= 0 && tx + 3 < S) {  // X0 + 3 <= ox + S - 1 < Wc
+        f32x4 val[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) val[c] = *reinterpret_cast<const f32x4u*>(src + (size_t)c * S * S);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float g = wy * tile_window(tx + k, S, v);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            num[k][c] = num[k][c] + val[c][k] * g;
+            one[k][c] = val[c][k];
+          }
+          den[k] = den[k] + g;
+          ++cover[k];
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (tx + k < 0 || tx + k >= S) continue;  // tx + k < S keeps X0 + k < Wc
+          const float g = wy * tile_window(tx + k, S, v);
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const float e = src[(size_t)c * S * S + k];
+            num[k][c] = num[k][c] + e * g;
+            one[k][c] = e;
+          }
+          den[k] = den[k] + g;
+          ++cover[k];
+        }
+      }
+    }
+  }
+  const bool whole = X0 + 3 < Wc;
+  const size_t plane = (size_t)Hc * Wc, at = (size_t)Y * Wc + X0;
+  uint32_t b[12];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float* xs = canvas_in + c * plane + at;
+    const float* ns = sc.is_last ? xs : noise + c * plane + at;  // read only when this is not the last step
+    f32x4 xv = {0.f, 0.f, 0.f, 0.f}, nz = {0.f, 0.f, 0.f, 0.f}, pv;
+    if (whole) {
+      xv = *reinterpret_cast<const f32x4u*>(xs);
+      if (!sc.is_last) nz = *reinterpret_cast<const f32x4u*>(ns);
+    } else {
+      for (int k = 0; X0 + k < Wc; ++k) {
+        xv[k] = xs[k];
+        if (!sc.is_last) nz[k] = ns[k];
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {  // pixels past Wc have den == 0 and are not stored
+      const float e = cover[k] == 1 ? one[k][c] : num[k][c] / den[k];
+      float x0;
+      if (sc.vpred) x0 = sc.sa * xv[k] - sc.sb * e;
+      else x0 = (xv[k] - sc.sb * e) / sc.sa;
+      if (sc.clamp_x0) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+      float pr = x0;
+      if (!sc.is_last) pr = sc.sap * x0 + sc.sbp * nz[k];
+      pv[k] = pr;
+      b[k * 3 + c] = (uint32_t)truncf(fminf(fmaxf((pr + 1.0f) * 127.5f, 0.f), 255.f));
+    }
+    float* dst = canvas_out + c * plane + at;
+    if (whole) {
+      *reinterpret_cast<f32x4u*>(dst) = pv;
+    } else {
+      for (int k = 0; X0 + k < Wc; ++k) dst[k] = pv[k];
+    }
+  }
+  if (img && Y < p.H && X0 < p.W) {
+    uint8_t* dst = img + ((size_t)Y * p.W + X0) * 3;
+    if (X0 + 3 < p.W) {
+      store12(dst, b);
+    } else {
+      for (int i = 0; i < (p.W - X0) * 3; ++i) dst[i] = (uint8_t)b[i];
+    }
+  }
+}
+
 // one thread per four consecutive x of a padded row (Wp is a multiple of 8, so every quad is whole and 16-byte aligned in its plane)
 __global__ void __launch_bounds__(kTileThreads) frame_load_u8_kernel(const uint8_t* __restrict__ img, int H, int W, int Hp, int Wp,
                                                                      float* __restrict__ out) {
@@ -248,6 +362,19 @@ hipError_t launch_tile_blend_u8(const float* tiles, const TilePlan& p, uint8_t* 
   const long long blocks = ((long long)((p.W + 3) / 4) * p.H + kTileThreads - 1) / kTileThreads;
   if (blocks >= (1ll << 31)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(tile_blend_u8_kernel, dim3((unsigned)blocks), dim3(kTileThreads), 0, s, tiles, p, ny, nx, img);
+  return hipGetLastError();
+}
+
+hipError_t launch_tile_sync_step(const float* eps, const TilePlan& p, const float* canvas_in, const float* noise, const StepCoef& c,
+                                 float* canvas_out, uint8_t* img, hipStream_t s) {
+  if (!tile_plan_ok(p.H, p.W, p.S, p.v) || (!c.is_last && !noise)) return hipErrorInvalidValue;
+  const int Hc = p.H > p.S ? p.H : p.S, Wc = p.W > p.S ? p.W : p.S;
+  if (!tile_plan_ok(Hc, Wc, p.S, p.v)) return hipErrorInvalidValue;
+  const int ny = tile_axis_count(p.H, p.S, p.v), nx = tile_axis_count(p.W, p.S, p.v);
+  const long long blocks = ((long long)((Wc + 3) / 4) * Hc + kTileThreads - 1) / kTileThreads;
+  if (blocks >= (1ll << 31)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tile_sync_step_kernel, dim3((unsigned)blocks), dim3(kTileThreads), 0, s, eps, p, ny, nx, canvas_in, noise, c, canvas_out,
+                     img);
   return hipGetLastError();
 }
 

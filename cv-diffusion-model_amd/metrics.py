@@ -390,7 +390,8 @@ def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[i
 @torch.no_grad()
 def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_steps: Optional[int] = None, seed: int = 0,
                              overlap: Optional[int] = None, tile_batch: int = 32,
-                             weights: Optional[Sequence[torch.Tensor]] = None, mode: str = "tiled") -> Dict[str, object]:
+                             weights: Optional[Sequence[torch.Tensor]] = None, mode: str = "tiled",
+                             sync: str = "none") -> Dict[str, object]:
     """PSNR / SSIM / MSE at the images' own resolution: every low-light frame of the paired `store` (any sizes >= 11 x 11) goes
     through `enhance_tiled` and is scored against its normal-light frame on the bytes (x = byte / 255).
 
@@ -402,11 +403,15 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
     mode="frame": every image goes through `enhance_frame_u8` instead (one run of the network at the image's own size; images
     past the engine's size cap raise ValueError).  The same generator, one draw per pair in the same order, with Hp / Wp =
     frame_pad(H / W):  canvas = torch.randn(steps, 3, Hp, Wp, generator=g, device=dev), then enhance_frame_u8(model,
-    store.frame(i), num_inference_steps, noise=canvas).  `overlap` / `tile_batch` belong to the tiles and are refused."""
+    store.frame(i), num_inference_steps, noise=canvas).  `overlap` / `tile_batch` / `sync` belong to the tiles and are refused.
+
+    sync="latents" (mode="tiled") passes through to `enhance_tiled`: the tiles share one latent canvas at every step."""
     if mode not in ("tiled", "frame"):
         raise ValueError(f'mode must be "tiled" or "frame", got {mode!r}')
-    if mode == "frame" and (overlap is not None or tile_batch != 32):
-        raise ValueError('overlap / tile_batch belong to mode="tiled"')
+    if mode == "frame" and (overlap is not None or tile_batch != 32 or sync != "none"):
+        raise ValueError('overlap / tile_batch / sync belong to mode="tiled"')
+    if sync not in ("none", "latents"):
+        raise ValueError(f'sync must be "none" or "latents", got {sync!r}')
     if not isinstance(store, DeviceFrameStore) or not store.paired:
         raise ValueError("evaluate_full_resolution expects a paired DeviceFrameStore")
     dev = store.device
@@ -424,7 +429,7 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
                 out = enhance_frame_u8(model, store.frame(i), nsteps, noise=canvas)
             else:
                 canvas = torch.randn(steps, 3, max(h, s), max(w, s), generator=g, device=dev)
-                out = enhance_tiled(model, store.frame(i), nsteps, overlap=overlap, tile_batch=tile_batch, noise=canvas)
+                out = enhance_tiled(model, store.frame(i), nsteps, overlap=overlap, tile_batch=tile_batch, noise=canvas, sync=sync)
             triples.append(_metrics_out3(out, store.frame(n + i), None))
         flat = torch.cat(triples).cpu().numpy()
     return _summary(store.names, flat, None)

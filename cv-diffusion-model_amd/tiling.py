@@ -12,6 +12,27 @@ One definition serves the NumPy twins here, the kernels (csrc/tiles.hip) and the
   blend    per pixel and channel over the covering tiles in ascending t: g = w[Y - oy] * w[X - ox]; num += val * g; den += g
            (separate fp32 multiply and add); out = uint8(trunc(clip((num / den + 1) * 127.5, 0, 255)))
 
+`enhance_tiled(sync="latents")` ties the tiles together at every step instead of once at the end: one latent canvas per image,
+and the tiles' predictions are fused into it after each step (a MultiDiffusion-style loop).  With Hc = max(H,S), Wc = max(W,S)
+-- the plan of (Hc, Wc) is the plan of (H, W), and its tiles cover the canvas exactly -- and the noise canvas [steps,3,Hc,Wc]
+in `enhance`'s order (entry 0 the initial latents, entry k+1 the re-noising draw of step k):
+
+  X = canvas[0]                                     # latent canvas, fp32 [3,Hc,Wc]
+  for k, t in enumerate(timesteps):
+      lat[j] = X[:, oy_j:oy_j+S, ox_j:ox_j+S]        # every tile j
+      eps[j] = unet(lat[j], low[j], t)               # low[j] from gather, as above
+      for every canvas pixel (Y, X) and channel c:   # sync step (tile_sync_step_kernel, csrc/tiles.hip)
+          over the covering tiles in ascending j:  g = w[Y-oy]*w[X-ox];  num = num + eps*g;  den = den + g
+          e  = eps of the one tile, if exactly one tile covers the pixel;  else num / den
+          x0 = (x - sb*e) / sa  (epsilon)  |  sa*x - sb*e  (v);  clip to [-1,1] if clamp_x0;  p = x0 if is_last else sap*x0 + sbp*noise,
+               with x = X[c][Y][X], noise = canvas[k+1][c][Y][X] and the scalars of `scheduler.step_coefficients(t)`: lcm_step_kernel
+          X[c][Y][X] = p
+  out[y][x][c] = uint8(trunc(clip((X[c][y][x] + 1) * 127.5, 0, 255)))  for y < H, x < W    # after the last step
+
+Every multiply and add is a separate fp32 operation, in the order written.  A pixel under exactly one tile skips the weights and
+so goes through lcm_step_kernel's arithmetic unchanged.  Blending eps rather than x0 is the same mathematics: x0 is affine in
+eps, and all covering tiles share x at a pixel.
+
 Frame mode (`enhance_frame_u8`) is the other route for images under the engine's size cap: no tiles, the network runs once at
 the image's own size (`LowLightDiffusion.enhance_frame`), padded to sides the network takes:
 
@@ -134,6 +155,85 @@ def frame_store_array(x: np.ndarray, size: Tuple[int, int]) -> np.ndarray:
     return np.clip((r + np.float32(1.0)) * np.float32(127.5), 0, 255).astype(np.uint8)
 
 
+def _step_scalars(coef):
+    """The fp32 scalars and flags of one N.StepCoef, as the kernels get them."""
+    f = np.float32
+    return (f(coef.sqrt_alpha_t), f(coef.sqrt_beta_t), f(coef.sqrt_alpha_prev), f(coef.sqrt_beta_prev), bool(coef.is_last),
+            bool(coef.v_prediction), bool(coef.clamp_x0))
+
+
+def _check_sync_shapes(eps_shape, size, overlap: int, canvas_shape, noise_shape) -> Tuple[int, int, int]:
+    h, w = int(size[0]), int(size[1])
+    if len(eps_shape) != 4 or eps_shape[1] != 3 or eps_shape[2] != eps_shape[3]:
+        raise ValueError(f"expected eps tiles [T,3,S,S], got {tuple(eps_shape)}")
+    s = int(eps_shape[2])
+    total = _tile_total(h, w, s, overlap)
+    if eps_shape[0] != total:
+        raise ValueError(f"a {h}x{w} image has {total} tiles of side {s} at overlap {overlap}, got {eps_shape[0]}")
+    want = (3, max(h, s), max(w, s))
+    if tuple(canvas_shape) != want or (noise_shape is not None and tuple(noise_shape) != want):
+        raise ValueError(f"the latent canvas and the noise of a {h}x{w} image are [3,{want[1]},{want[2]}], got {tuple(canvas_shape)}"
+                         + ("" if noise_shape is None else f" and {tuple(noise_shape)}"))
+    return h, w, s
+
+
+def sync_step_array(eps_tiles: np.ndarray, size: Tuple[int, int], overlap: int, canvas: np.ndarray, noise: Optional[np.ndarray],
+                    coef) -> np.ndarray:
+    """One step of the shared latent canvas (module docstring): eps tiles fp32 [T,3,S,S], canvas and noise fp32 [3,Hc,Wc], `coef`
+    an N.StepCoef -> the new canvas.  `noise` may be None on the last step."""
+    h, w, s = _check_sync_shapes(eps_tiles.shape, size, overlap, canvas.shape, None if noise is None else noise.shape)
+    sa, sb, sap, sbp, last, vpred, clamp = _step_scalars(coef)
+    if not last and noise is None:
+        raise ValueError("a step that is not the last needs its noise")
+    hc, wc = canvas.shape[1:]
+    oys, oxs = tile_origins(h, s, overlap), tile_origins(w, s, overlap)
+    eps_tiles = eps_tiles.astype(np.float32, copy=False)
+    win = tile_window(s, overlap)
+    g = win[:, None] * win[None, :]
+    num, one = np.zeros((3, hc, wc), dtype=np.float32), np.zeros((3, hc, wc), dtype=np.float32)
+    den, cover = np.zeros((hc, wc), dtype=np.float32), np.zeros((hc, wc), dtype=np.int32)
+    for iy, oy in enumerate(oys):
+        for ix, ox in enumerate(oxs):  # ascending tile number
+            e = eps_tiles[iy * len(oxs) + ix]
+            num[:, oy:oy + s, ox:ox + s] = num[:, oy:oy + s, ox:ox + s] + e * g
+            den[oy:oy + s, ox:ox + s] = den[oy:oy + s, ox:ox + s] + g
+            one[:, oy:oy + s, ox:ox + s] = e
+            cover[oy:oy + s, ox:ox + s] += 1
+    e = np.where(cover == 1, one, num / den)
+    x = canvas.astype(np.float32, copy=False)
+    x0 = sa * x - sb * e if vpred else (x - sb * e) / sa
+    if clamp:
+        x0 = np.minimum(np.maximum(x0, np.float32(-1.0)), np.float32(1.0))
+    return x0 if last else sap * x0 + sbp * noise.astype(np.float32, copy=False)
+
+
+def canvas_store_array(x: np.ndarray, size: Tuple[int, int]) -> np.ndarray:
+    """fp32 canvas [3,Hc,Wc] -> uint8 [H,W,3]: the crop to `size`, then the reference's truncating denormalisation."""
+    h, w = int(size[0]), int(size[1])
+    if h <= 0 or w <= 0 or x.ndim != 3 or x.shape[0] != 3 or x.shape[1] < h or x.shape[2] < w:
+        raise ValueError(f"a {h}x{w} image needs a canvas [3,>={h},>={w}], got {tuple(x.shape)}")
+    r = x.astype(np.float32, copy=False)[:, :h, :w].transpose(1, 2, 0)
+    return np.clip((r + np.float32(1.0)) * np.float32(127.5), 0, 255).astype(np.uint8)
+
+
+def enhance_tiled_sync_array(eps_fn, rgb_u8: np.ndarray, tile: int, overlap: int, coefs, timesteps, canvas: np.ndarray):
+    """The loop of `enhance_tiled(sync="latents")` on the host, the denoiser passed in: eps_fn(lat [T,3,S,S], low [T,3,S,S], t)
+    -> fp32 [T,3,S,S].  `coefs[k]` is the N.StepCoef of `timesteps[k]`; `canvas` is the noise canvas [steps,3,Hc,Wc].
+    -> (uint8 [H,W,3], the final fp32 canvas [3,Hc,Wc] before any clamp)."""
+    h, w = _check_image(rgb_u8, "enhance_tiled_sync_array")
+    hc, wc = max(h, tile), max(w, tile)
+    if canvas.ndim != 4 or tuple(canvas.shape) != (len(timesteps), 3, hc, wc) or len(coefs) != len(timesteps):
+        raise ValueError(f"{len(timesteps)} steps of a {h}x{w} image need a canvas [{len(timesteps)},3,{hc},{wc}] and as many coefficients")
+    low = gather_tiles_array(rgb_u8, tile, overlap)
+    origins = [(oy, ox) for oy in tile_origins(h, tile, overlap) for ox in tile_origins(w, tile, overlap)]
+    x = canvas[0].astype(np.float32)
+    for k, t in enumerate(timesteps):
+        lat = np.stack([x[:, oy:oy + tile, ox:ox + tile] for oy, ox in origins])
+        eps = np.asarray(eps_fn(lat, low, int(t)), dtype=np.float32)
+        x = sync_step_array(eps, (h, w), overlap, x, None if coefs[k].is_last else canvas[k + 1], coefs[k])
+    return canvas_store_array(x, (h, w)), x
+
+
 # ------------------------------------------------------------------ device wrappers
 def _require_hip(t, what: str) -> None:
     if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
@@ -206,6 +306,30 @@ def blend_tiles_device(tiles: torch.Tensor, size: Tuple[int, int], overlap: int)
     return img
 
 
+def sync_step_device(eps_tiles: torch.Tensor, size: Tuple[int, int], overlap: int, canvas: torch.Tensor, noise: Optional[torch.Tensor],
+                     coef, *, out: Optional[torch.Tensor] = None, image: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Device twin of sync_step_array: contiguous fp32 eps tiles [T,3,S,S], canvas and noise [3,Hc,Wc] on a HIP device -> the
+    new canvas, written to `out` (a fresh tensor by default; `out=canvas` steps in place).  `image` (uint8 [H,W,3], contiguous)
+    also takes the bytes of the new canvas, which is what the last step wants."""
+    _require_hip(eps_tiles, "sync_step_device")
+    h, w, s = _check_sync_shapes(eps_tiles.shape, size, overlap, canvas.shape, None if noise is None else noise.shape)
+    out = torch.empty_like(canvas) if out is None else out
+    for name, t in (("eps_tiles", eps_tiles), ("canvas", canvas), ("noise", noise), ("out", out)):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != eps_tiles.device):
+            raise ValueError(f"{name} must be a contiguous fp32 tensor on {eps_tiles.device}")
+    if out.shape != canvas.shape:
+        raise ValueError(f"out must have the canvas's shape {tuple(canvas.shape)}, got {tuple(out.shape)}")
+    if image is not None and (image.dtype != torch.uint8 or tuple(image.shape) != (h, w, 3) or not image.is_contiguous()
+                              or image.device != eps_tiles.device):
+        raise ValueError(f"image must be a contiguous uint8 [{h},{w},3] tensor on {eps_tiles.device}")
+    dev = eps_tiles.device
+    with torch.cuda.device(dev):
+        N.check(N.lib().llie_tile_sync_step(eps_tiles.data_ptr(), h, w, s, overlap, canvas.data_ptr(),
+                                            None if noise is None else noise.data_ptr(), coef, out.data_ptr(),
+                                            None if image is None else image.data_ptr(), _stream(dev)), "tile_sync_step")
+    return out
+
+
 def frame_load_device(rgb_u8: torch.Tensor) -> torch.Tensor:
     """Device twin of frame_load_array: uint8 [H,W,3] on a HIP device -> fp32 [3,Hp,Wp]."""
     _require_hip(rgb_u8, "frame_load_device")
@@ -262,7 +386,7 @@ def enhance_frame_u8(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[
 @torch.no_grad()
 def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int] = None, *, overlap: Optional[int] = None,
                   tile_batch: int = 32, generator: Optional[torch.Generator] = None,
-                  noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  noise: Optional[torch.Tensor] = None, sync: str = "none", return_canvas: bool = False):
     """uint8 [H,W,3] on a HIP device -> enhanced uint8 [H,W,3] at the same resolution.
 
     The image is cut into S x S tiles (S = model.image_size) overlapping by `overlap` pixels (default S // 8, at most S // 2);
@@ -272,9 +396,19 @@ def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int
 
     Tiling removes the resize, not the model's field of view: each tile is denoised on its own (the global attention at the
     lowest level sees one tile), so brightness may drift between distant tiles; the shared canvas and the feathered blend keep
-    neighbours consistent inside their overlap."""
+    neighbours consistent inside their overlap.
+
+    sync="latents" couples the tiles at every step instead (the module docstring has the definition): the image keeps one latent
+    canvas, every step denoises each tile's window of it (`tile_batch` tiles per `unet.forward_split`) and one launch fuses the
+    predictions back into the canvas, so neighbours start every step from the same values where they overlap and the result is
+    single-valued before any blending of pixels.  The attention is still per tile: only overlaps couple neighbours.  The noise
+    canvas is read the same way; `return_canvas=True` returns (image, the final fp32 canvas [3,max(H,S),max(W,S)] before the clamp)."""
     if not isinstance(rgb_u8, torch.Tensor):
         raise ValueError(f"enhance_tiled expects a torch.Tensor, got {type(rgb_u8).__name__}")
+    if sync not in ("none", "latents"):
+        raise ValueError(f'sync must be "none" or "latents", got {sync!r}')
+    if return_canvas and sync != "latents":
+        raise ValueError('return_canvas needs sync="latents": the default path keeps no latent canvas')
     h, w = _check_image(rgb_u8, "enhance_tiled")
     s = int(model.image_size)
     overlap = s // 8 if overlap is None else int(overlap)
@@ -298,6 +432,9 @@ def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int
         canvas = noise.to(device=dev, dtype=torch.float32).contiguous()
     img = rgb_u8.contiguous()
     total = _tile_total(h, w, s, overlap)
+    if sync == "latents":
+        out, x = _enhance_tiled_sync(model, img, s, overlap, tile_batch, canvas, total)
+        return (out, x) if return_canvas else out
     result = torch.empty(total, 3, s, s, dtype=torch.float32, device=dev)
     for first in range(0, total, tile_batch):
         count = min(tile_batch, total - first)
@@ -305,3 +442,34 @@ def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int
         draws = gather_noise_device(canvas, (h, w), s, overlap, first, count)
         result[first:first + count].copy_(model.enhance(low, nsteps, noise=draws))
     return blend_tiles_device(result, (h, w), overlap)
+
+
+def _enhance_tiled_sync(model, img: torch.Tensor, s: int, overlap: int, tile_batch: int, canvas: torch.Tensor, total: int):
+    """The loop of enhance_tiled(sync="latents") after its checks: `canvas` is the noise canvas, the scheduler's timesteps are
+    set.  Nothing inside the loop waits for the device or copies from the host."""
+    h, w = int(img.shape[0]), int(img.shape[1])
+    dev = img.device
+    ts = model.scheduler._timestep_list
+    coefs = [model.scheduler.step_coefficients(t) for t in ts]
+    t_dev = {}  # (timestep, count) -> device int64 [count], kept on the model like enhance's
+    for t in ts:
+        for count in {min(tile_batch, total), total % tile_batch} - {0}:
+            key = ("tiles", int(t), count, dev.type, dev.index)
+            cached = model._t_cache.get(key)
+            if cached is None:
+                if len(model._t_cache) > 64:
+                    model._t_cache.clear()
+                cached = model._t_cache[key] = torch.full((count,), int(t), dtype=torch.long).to(dev)
+            t_dev[int(t), count] = cached
+    x = canvas[0].clone()  # the latent canvas; `canvas` may be the caller's
+    eps = torch.empty(total, 3, s, s, dtype=torch.float32, device=dev)
+    out = torch.empty(h, w, 3, dtype=torch.uint8, device=dev)
+    for k, t in enumerate(ts):
+        for first in range(0, total, tile_batch):
+            count = min(tile_batch, total - first)
+            low = gather_tiles_device(img, s, overlap, first, count)
+            lat = gather_noise_device(x[None], (h, w), s, overlap, first, count)[0]
+            model.unet.forward_split(lat, low, t_dev[int(t), count], uniform_t=True, out=eps[first:first + count])
+        last = bool(coefs[k].is_last)
+        sync_step_device(eps, (h, w), overlap, x, None if last else canvas[k + 1], coefs[k], out=x, image=out if last else None)
+    return out, x

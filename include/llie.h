@@ -328,14 +328,24 @@ int llie_postprocess_u8(const float* x, int batch, int S, uint8_t* img, int H0, 
  *   llie_tile_blend_u8:   fp32 tiles [T][3][S][S] (all T = ny * nx tiles) -> uint8 HWC RGB [H][W][3]: per pixel the mean of the
  *                         covering tiles weighted by w[y] * w[x], w[k] = min(k + 1, S - k, v) / v (1 when v == 0), accumulated in
  *                         ascending tile number, then llie_postprocess_u8's (r + 1) * 127.5, clip [0,255], truncate.
+ *   llie_tile_sync_step:  one LCM step of the latent canvas the tiles of an image share (tiling.enhance_tiled(sync="latents")).
+ *                         eps_tiles fp32 [T][3][S][S] holds the denoiser's output for all T tiles, each run on its window of
+ *                         canvas_in fp32 [3][max(H,S)][max(W,S)].  Per canvas pixel and channel, e = the value of the one covering
+ *                         tile, or llie_tile_blend_u8's weighted mean num / den over the covering tiles when there are several;
+ *                         then llie_lcm_step's arithmetic on (e, canvas_in, noise) with `coef`, written to canvas_out (which may be
+ *                         canvas_in).  noise has the canvas's shape and may be NULL when coef->is_last.  img (or NULL; meaningful on
+ *                         the last step): uint8 HWC RGB [H][W][3], llie_tile_blend_u8's bytes of canvas_out for y < H, x < W.
  * Bit-exact with the host implementation in tiling.py (fp32 arithmetic without fused multiply-adds, fixed order, no atomics).
- * v < 0, 2v > S, a non-positive size, a chunk outside the plan or planes not a positive multiple of 3 return LLIE_ERR_ARG. */
+ * v < 0, 2v > S, a non-positive size, a chunk outside the plan, planes not a positive multiple of 3 or a NULL noise on a step
+ * that is not the last return LLIE_ERR_ARG. */
 int llie_tile_count(int L, int S, int v);
 int llie_tile_origins(int L, int S, int v, int* out);
 int llie_tile_gather_u8(const uint8_t* img, int H, int W, int S, int v, int first, int count, float* tiles, llie_stream stream);
 int llie_tile_gather_f32(const float* canvas, int planes, int H, int W, int S, int v, int first, int count, float* out,
                          llie_stream stream);
 int llie_tile_blend_u8(const float* tiles, int H, int W, int S, int v, uint8_t* img, llie_stream stream);
+int llie_tile_sync_step(const float* eps_tiles, int H, int W, int S, int v, const float* canvas_in, const float* noise,
+                        const llie_step_coef* coef, float* canvas_out, uint8_t* img, llie_stream stream);
 
 /* Byte-level I/O of frame mode: a uint8 image of any size to the padded fp32 frame llie_enhance_hw takes, and back.
  *   llie_frame_pad:      a side L -> the next multiple of 8, at least 64 (host only)

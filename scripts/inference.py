@@ -3,7 +3,8 @@
 scripts/inference.py (:30-62): --input --output --checkpoint --model --format --variant --image_size
 --num_steps --device.  Only --format pytorch exists here (ONNX / TFLite are the reference's mobile
 deployment targets, out of scope); extensions: --dtype {fp32,fp16,bf16}, --noise_seed, and --tile [--tile_overlap N]
-[--tile_batch N], which enhances the image at its own resolution as overlapping image_size tiles instead of resizing it, and
+[--tile_batch N] [--tile_sync {none,latents}], which enhances the image at its own resolution as overlapping image_size tiles
+instead of resizing it (--tile_sync latents: the tiles share one latent canvas, fused after every step), and
 --native, which enhances it at its own resolution by one run of the network at that size (frame mode; images under the engine's
 size cap, about 5.59 M pixels for `small`).  --native and the tile flags exclude each other.
 """
@@ -43,12 +44,17 @@ def parse_args(argv=None):
                         "on the device; --noise_seed then seeds the per-image noise canvas")
     p.add_argument("--tile_overlap", type=int, default=None, help="overlap of neighbouring tiles in pixels (default image_size // 8)")
     p.add_argument("--tile_batch", type=int, default=32, help="tiles per enhance call")
+    p.add_argument("--tile_sync", type=str, default="none", choices=["none", "latents"],
+                   help="with --tile: latents = keep one latent canvas per image and fuse the tiles' predictions into it after "
+                        "every step, so neighbours agree where they overlap; none = each tile runs its own loop")
     p.add_argument("--native", action="store_true",
                    help="(extension) no resize and no tiles: one run of the network at the image's own resolution (frame mode); "
                         "--noise_seed then seeds the noise canvas at the padded size")
     args = p.parse_args(argv)
-    if args.native and (args.tile or args.tile_overlap is not None or args.tile_batch != 32):
-        p.error("--native and --tile / --tile_overlap / --tile_batch exclude each other")
+    if args.native and (args.tile or args.tile_overlap is not None or args.tile_batch != 32 or args.tile_sync != "none"):
+        p.error("--native and --tile / --tile_overlap / --tile_batch / --tile_sync exclude each other")
+    if args.tile_sync != "none" and not args.tile:
+        p.error("--tile_sync belongs to --tile")
     return args
 
 
@@ -70,7 +76,7 @@ def enhance_tiled_image(args, model, rgb):
         hc, wc = max(rgb.shape[0], args.image_size), max(rgb.shape[1], args.image_size)
         noise = torch.stack([torch.randn(3, hc, wc, generator=g) for _ in range(args.num_steps)])
     out = tiling.enhance_tiled(model, torch.from_numpy(rgb).to(args.device), args.num_steps, overlap=args.tile_overlap,
-                               tile_batch=args.tile_batch, noise=noise)
+                               tile_batch=args.tile_batch, noise=noise, sync=args.tile_sync)
     return out.cpu().numpy()
 
 
