@@ -11,6 +11,7 @@ repository root) or `importlib.import_module("cv-diffusion-model_amd")`.
 from .unet import (EfficientUNet, EfficientUNetConfig, create_efficient_unet, InvertedResidualBlock,
                    LinearAttention, Downsample, Upsample, SqueezeExcitation)
 from .scheduler import LCMScheduler, LCMSchedulerOutput, LCMDenoisingLoop, get_lcm_timesteps
+from .ddim import ddim_timesteps, ddim_step_host, ddim_enhance_host
 from .pipeline import (LowLightDiffusion, LowLightDiffusionOutput, LowLightLCMDistillation, normalize_image,
                        denormalize_image, x0_loss, x0_loss_host)
 from .sharding import shard_range, enhance_sharded, all_gather_batch, all_reduce_gradients
@@ -46,4 +47,5 @@ __all__ = [
     "ssim_loss", "ssim_grad_host", "x0_loss", "x0_loss_host",
     "TrainingConfig", "LowLightTrainer", "train_model", "make_lr_scheduler", "build_checkpoint", "comparison_grid",
     "comparison_grid_host",
+    "ddim_timesteps", "ddim_step_host", "ddim_enhance_host",
 ]

@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "libllie_hip.so")
 LLIE_F32, LLIE_F16, LLIE_BF16 = 0, 1, 2
 LLIE_UNET, LLIE_IRB, LLIE_ATTN, LLIE_DOWN, LLIE_UP, LLIE_SE = 0, 1, 2, 3, 4, 5
 ERR_ARG, ERR_SHAPE, ERR_CONFIG, ERR_KEY, ERR_NOT_LOADED, ERR_WORKSPACE, ERR_NO_DEVICE = -1, -2, -3, -4, -5, -6, -7
+SAMPLER_LCM, SAMPLER_DDIM = 0, 1  # llie_step_coef.sampler
 
 EXPORTS = [
     "llie_last_error", "llie_version", "llie_create", "llie_destroy", "llie_num_params", "llie_param_info",
@@ -103,11 +104,29 @@ class AmpConfig(C.Structure):
     _fields_ = [("growth_factor", C.c_double), ("backoff_factor", C.c_double), ("growth_interval", C.c_int32)]
 
 
-class StepCoef(C.Structure):
+class _StepCoefLayout(C.Structure):
+    """llie_step_coef (include/llie.h), member by member."""
     _fields_ = [
         ("sqrt_alpha_t", C.c_float), ("sqrt_beta_t", C.c_float), ("sqrt_alpha_prev", C.c_float),
         ("sqrt_beta_prev", C.c_float), ("is_last", C.c_int), ("v_prediction", C.c_int), ("clamp_x0", C.c_int),
+        ("sampler", C.c_int),  # 0 LCM (the default of a positional construction), 1 deterministic DDIM
     ]
+
+
+class _SevenScalars(type(C.Structure)):
+    """Metaclass of StepCoef: `StepCoef._fields_` names the seven scalars of the LCM step (see there); the layout is the base's."""
+
+    @property
+    def _fields_(cls):
+        return _StepCoefLayout._fields_[:7]
+
+
+class StepCoef(_StepCoefLayout, metaclass=_SevenScalars):
+    """llie_step_coef.  The layout is _StepCoefLayout's eight members; `sampler` trails, defaults to 0 (LCM) and is set as the
+    eighth positional argument or by keyword.  `StepCoef._fields_` keeps naming the seven scalars of the LCM step: callers
+    enumerate it to read back the fp32 values a kernel gets and unpack them as (sa, sb, sap, sbp, is_last, vpred, clamp_x0), as
+    they did before the struct grew; the sampler is read as `coef.sampler`."""
+
 
 
 DISTILL_LOSS_PER_WG = 1024  # kDistillLossPerWG (csrc/kernels.h): llie_consistency_loss needs one double per this many elements

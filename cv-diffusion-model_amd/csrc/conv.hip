@@ -285,7 +285,7 @@ __global__ void __launch_bounds__(256) final_conv_kernel(const FinalConvArgs a) 
 // Roles are swapped relative to a usual conv-GEMM: the (zero-padded) weights are the A operand
 // (rows = output channel, only rows 0..2 are non-zero) and the activated halo patch is the B operand
 // (columns = pixels), so after the K loop lane p of lane-half 0 holds the 3 outputs of ITS pixel in
-// acc[0..2]: the epilogue (bias, LCMScheduler.step lcm_scheduler.py:204-242, clamp
+// acc[0..2]: the epilogue (bias, LCMScheduler.step lcm_scheduler.py:204-242 or the DDIM step of lcm_step_kernel, clamp
 // low_light_diffusion.py:240) is per-lane and its fp32 NCHW accesses are 64-byte row segments.
 // K order per 32-channel chunk: k-step = (tap, 16-channel half); lane half h takes 8 channels.
 // Weights pre-packed as [chunk][18][2][4][8] T (output channel padded to 4).
@@ -328,7 +328,7 @@ __global__ void __launch_bounds__(256, 4) final_conv_mfma_kernel(const FinalConv
         if (o < a.Cout && y < a.H && x < a.W) {
           const size_t idx = ((size_t)b * a.Cout + o) * plane + (size_t)y * a.W + x;
           pre_x[t][o] = a.sample[idx];
-          if (!a.coef.is_last) pre_n[t][o] = a.noise[idx];
+          if (!a.coef.is_last && !a.coef.sampler) pre_n[t][o] = a.noise[idx];
         }
       }
     }
@@ -412,7 +412,11 @@ __global__ void __launch_bounds__(256, 4) final_conv_mfma_kernel(const FinalConv
         else x0v = (xv - a.coef.sb * e) / a.coef.sa;
         if (a.coef.clamp_x0) x0v = fminf(fmaxf(x0v, -1.f), 1.f);
         float pv = x0v;
-        if (!a.coef.is_last) pv = a.coef.sap * x0v + a.coef.sbp * pre_n[t][o];
+        if (!a.coef.is_last) {
+          float nz = pre_n[t][o];
+          if (a.coef.sampler) nz = a.coef.vpred ? a.coef.sa * e + a.coef.sb * xv : e;  // DDIM: the predicted noise, no draw
+          pv = a.coef.sap * x0v + a.coef.sbp * nz;
+        }
         a.prev[idx] = pv;
         if (a.clamped) a.clamped[idx] = fminf(fmaxf(pv, -1.f), 1.f);
       }
@@ -422,7 +426,8 @@ __global__ void __launch_bounds__(256, 4) final_conv_mfma_kernel(const FinalConv
 }
 hipError_t launch_final_conv(int dtype, const FinalConvArgs& a, hipStream_t s) {
   if (a.H % 8 || a.W % 8 || a.C % 32 || a.Cout > 4) return hipErrorInvalidValue;
-  if (a.fuse_step && (!a.wp || dtype == 0 || !a.sample || !a.prev || (!a.coef.is_last && !a.noise))) return hipErrorInvalidValue;
+  if (a.fuse_step && (!a.wp || dtype == 0 || !a.sample || !a.prev || (!a.coef.is_last && !a.coef.sampler && !a.noise) ||
+                      (a.coef.sampler && a.coef.clamp_x0))) return hipErrorInvalidValue;
   if (!a.fuse_step && !a.out) return hipErrorInvalidValue;
   dim3 grid(((a.H + 15) / 16) * ((a.W + 15) / 16), a.B);
   switch (dtype) {

@@ -262,9 +262,11 @@ struct Knobs {
   int bwd_async;      // "bwd_async": weight-gradient kernels of the backward pass on a side stream
   int upconv_fold;    // "upconv_fold": up-sampling convs from folded weights wherever upconv_fold_supported(); 0 = blend in the kernel
   int enhance_split;  // "enhance_split": concurrent branches of the captured enhance graph (< 2: a single chain)
+  int graph_max_steps;  // "graph_max_steps": loops of more steps than this run as plain launches, never captured
   int epoch;          // llie_tune calls so far: keys the graph cache and the zero-region sizes, which bake kernel choices in
 };
 extern Knobs g_knobs;
+constexpr int kGraphMaxSteps = 20;  // default of Knobs::graph_max_steps: capture pays at 20 steps and loses at 50
 
 // The launch sequence of an inverted-residual block (forward.cpp: Run::irb; the byte model, llie_path_bytes, asks too):
 //   unfused    expand GEMM, dwconv3x3, SE, project GEMM: fp32 engines, training, wide or padded blocks
@@ -358,6 +360,11 @@ int run_unet(Exec x, Tape* tape, const float* lat, const float* cond, const int6
 int run_module(Exec x, Tape* tape, const float* in, const float* temb, float* y, int H, int W);
 // scheduler step fused into the final conv's epilogue (2-byte compute dtypes only)
 struct FusedStep { StepCoef coef; const float* noise; float* prev; float* clamped; };
+// llie_step_coef as the kernels take it; a sampler other than 0 / 1, or DDIM together with clamp_x0, is not a step (LLIE_ERR_ARG)
+inline StepCoef step_coef(const llie_step_coef& k) {
+  return StepCoef{k.sqrt_alpha_t, k.sqrt_beta_t, k.sqrt_alpha_prev, k.sqrt_beta_prev, k.is_last, k.v_prediction, k.clamp_x0, k.sampler};
+}
+inline bool step_coef_ok(const llie_step_coef& k) { return k.sampler == 0 || (k.sampler == 1 && !k.clamp_x0); }
 int unet_forward_impl(llie_ctx* c, const float* lat, const float* cond, const int64_t* t, int uniform_t, float* eps,
                       const FusedStep* fs, int batch, int H, int W, void* ws, int64_t ws_bytes, llie_stream stream);
 // forward.cpp: the frame rule of llie_frame_shape_ok, and the workspace of `max_steps` steps of the loop at H x W without that

@@ -8,9 +8,8 @@ extern "C" {
 int llie_lcm_step(const float* mo, const float* sample, const float* noise, float* prev, float* x0, float* clamped,
                   int64_t n, const llie_step_coef* k, llie_stream stream) {
   if (!mo || !sample || !prev || !k || n <= 0) return LLIE_ERR_ARG;
-  if (!k->is_last && !noise) return LLIE_ERR_ARG;
-  StepCoef c{k->sqrt_alpha_t, k->sqrt_beta_t, k->sqrt_alpha_prev, k->sqrt_beta_prev, k->is_last, k->v_prediction, k->clamp_x0};
-  return kerr("lcm_step", launch_lcm_step(mo, sample, noise, prev, x0, clamped, n, c, hs(stream)), 0);
+  if (!step_coef_ok(*k) || (!k->is_last && !k->sampler && !noise)) return LLIE_ERR_ARG;
+  return kerr("lcm_step", launch_lcm_step(mo, sample, noise, prev, x0, clamped, n, step_coef(*k), hs(stream)), 0);
 }
 
 int llie_add_noise(const float* x0, const float* noise, const int64_t* t, const float* acp, int table_len, float* out, int batch,
@@ -40,13 +39,12 @@ static int enhance_sequence(llie_ctx* c, const float* low, const float* noise, c
   for (int i = 0; i < steps; ++i) {
     const bool last = i == steps - 1;
     float* prev = inter ? inter + (size_t)i * sn : lat[i & 1];
-    const float* nz = coefs[i].is_last ? nullptr : noise + (size_t)(i + 1) * sn;
-    if (!coefs[i].is_last && i + 1 >= steps) return LLIE_ERR_ARG;  // a non-final step needs a noise draw
+    const bool draw = !coefs[i].is_last && !coefs[i].sampler;  // a DDIM step reads no noise: `noise` ends after the initial latents
+    const float* nz = draw ? noise + (size_t)(i + 1) * sn : nullptr;
+    if (draw && i + 1 >= steps) return LLIE_ERR_ARG;  // a non-final LCM step needs a noise draw
     int rc;
     if (fuse) {
-      FusedStep fs{StepCoef{coefs[i].sqrt_alpha_t, coefs[i].sqrt_beta_t, coefs[i].sqrt_alpha_prev, coefs[i].sqrt_beta_prev,
-                                 coefs[i].is_last, coefs[i].v_prediction, coefs[i].clamp_x0},
-                        nz, prev, last ? enhanced : nullptr};
+      FusedStep fs{step_coef(coefs[i]), nz, prev, last ? enhanced : nullptr};
       rc = unet_forward_impl(c, cur, low, t_dev + (size_t)i * step_batch, 1, preds ? preds + (size_t)i * sn : nullptr, &fs, batch,
                              H, W, uws, uws_bytes, stream);
       if (rc) return rc;
@@ -68,6 +66,12 @@ static int enhance_impl(llie_ctx* c, const float* low, const float* noise, const
                         llie_stream stream) {
   if (!c || !low || !noise || !t_dev || !coefs || !enhanced || !ws || steps <= 0 || batch <= 0 || c->cfg.kind != LLIE_UNET)
     return LLIE_ERR_ARG;
+  const int ddim = coefs[0].sampler;
+  for (int i = 0; i < steps; ++i)
+    if (!step_coef_ok(coefs[i]) || coefs[i].sampler != ddim) {
+      set_err("enhance: step %d: a schedule is all LCM or all DDIM steps, and DDIM has no clamp_x0", i);
+      return LLIE_ERR_ARG;
+    }
   const int64_t n = (int64_t)batch * 3 * H * W;
   const size_t img = align_up((size_t)n * 4, 256);
   if ((int64_t)(3 * img) > ws_bytes) { set_err("workspace too small"); return LLIE_ERR_WORKSPACE; }
@@ -80,12 +84,14 @@ static int enhance_impl(llie_ctx* c, const float* low, const float* noise, const
   // async copies around the graph launch.  First use of a key runs eagerly (it also performs the
   // one-time hipFuncSetAttribute calls, which must not happen during capture).
   static const bool no_graph = getenv("LLIE_NO_GRAPH") != nullptr;
-  const size_t n_in = 1 + (size_t)steps;                       // low + noise draws
+  const size_t n_noise = ddim ? 1 : (size_t)steps;             // DDIM: the initial latents are the only draw, whatever `steps`
+  const size_t n_in = 1 + n_noise;                             // low + noise draws
   const size_t n_out = 1 + (inter ? steps : 0) + (preds ? steps : 0);
   const size_t tbytes = align_up((size_t)steps * batch * 8, 256);
   const size_t stage = (n_in + n_out) * img + tbytes;
   const int64_t seq_bytes = ws_bytes - (int64_t)stage;
-  bool use_graph = !no_graph && c->prof_mask == 0 && seq_bytes >= frame_workspace(c, batch, H, W, 0);
+  // a loop of more than graph_max_steps steps is not worth capturing (several thousand nodes: DESIGN.md 7): plain launches
+  bool use_graph = !no_graph && c->prof_mask == 0 && steps <= g_knobs.graph_max_steps && seq_bytes >= frame_workspace(c, batch, H, W, 0);
   if (!use_graph) return enhance_sequence(c, low, noise, t_dev, coefs, steps, enhanced, inter, preds, batch, H, W, base, ws_bytes, stream);
 
   std::string key(reinterpret_cast<const char*>(coefs), sizeof(llie_step_coef) * steps);
@@ -119,7 +125,7 @@ static int enhance_impl(llie_ctx* c, const float* low, const float* noise, const
   // NB: staged noise / inter / preds are step-major with stride `img` >= n*4; keep them dense (img == n*4 when n*4 % 256 == 0)
   if (img != (size_t)n * 4) return enhance_sequence(c, low, noise, t_dev, coefs, steps, enhanced, inter, preds, batch, H, W, base, ws_bytes, stream);
   hipError_t e = hipMemcpyAsync(s_low, low, (size_t)n * 4, hipMemcpyDeviceToDevice, us);
-  if (e == hipSuccess) e = hipMemcpyAsync(s_noise, noise, (size_t)n * 4 * steps, hipMemcpyDeviceToDevice, us);
+  if (e == hipSuccess) e = hipMemcpyAsync(s_noise, noise, (size_t)n * 4 * n_noise, hipMemcpyDeviceToDevice, us);
   if (e == hipSuccess) e = hipMemcpyAsync(s_t, t_dev, (size_t)steps * batch * 8, hipMemcpyDeviceToDevice, us);
   if (e != hipSuccess) { set_err("enhance staging: %s", hipGetErrorString(e)); return (int)e; }
   if (!ge.exec) {

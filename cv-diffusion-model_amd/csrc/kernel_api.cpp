@@ -223,7 +223,7 @@ int llie_final_conv(int dtype, const void* in, const float* scale, const float* 
       pack_bytes < llie_final_conv_pack_bytes(C))
     return LLIE_ERR_ARG;
   // the scheduler step lives in the MFMA kernel's epilogue alone; without it the noise prediction is the only output
-  if (coef ? (!use_mfma || !sample || !prev || (!coef->is_last && !noise)) : (!out || sample || noise || prev || clamped)) return LLIE_ERR_ARG;
+  if (coef ? (!use_mfma || !sample || !prev || !step_coef_ok(*coef) || (!coef->is_last && !coef->sampler && !noise)) : (!out || sample || noise || prev || clamped)) return LLIE_ERR_ARG;
   const int64_t need = llie_final_conv_pack_bytes(C), off = (int64_t)9 * C * 4 * 4;
   char* blob = reinterpret_cast<char*>(pack);
   LoadDesc d{};
@@ -234,8 +234,7 @@ int llie_final_conv(int dtype, const void* in, const float* scale, const float* 
   a.out = out; a.B = batch; a.H = H; a.W = W; a.C = C; a.Cout = Cout;
   if (coef) {
     a.fuse_step = 1;
-    a.coef = StepCoef{coef->sqrt_alpha_t, coef->sqrt_beta_t, coef->sqrt_alpha_prev, coef->sqrt_beta_prev, coef->is_last, coef->v_prediction,
-                      coef->clamp_x0};
+    a.coef = step_coef(*coef);
     a.sample = sample; a.noise = noise; a.prev = prev; a.clamped = clamped;
   }
   hipStream_t s = hs(stream);
@@ -504,8 +503,8 @@ int llie_tile_blend_u8(const float* tiles, int H, int W, int S, int v, uint8_t* 
 
 int llie_tile_sync_step(const float* eps_tiles, int H, int W, int S, int v, const float* canvas_in, const float* noise,
                         const llie_step_coef* k, float* canvas_out, uint8_t* img, llie_stream stream) {
-  if (!eps_tiles || !canvas_in || !k || !canvas_out) return LLIE_ERR_ARG;
-  const StepCoef c{k->sqrt_alpha_t, k->sqrt_beta_t, k->sqrt_alpha_prev, k->sqrt_beta_prev, k->is_last, k->v_prediction, k->clamp_x0};
+  if (!eps_tiles || !canvas_in || !k || !canvas_out || !step_coef_ok(*k)) return LLIE_ERR_ARG;
+  const StepCoef c = step_coef(*k);
   return kerr("tile_sync_step", launch_tile_sync_step(eps_tiles, TilePlan{H, W, S, v, 0, 1}, canvas_in, noise, c, canvas_out, img, hs(stream)),
               LLIE_ERR_ARG, nullptr);
 }

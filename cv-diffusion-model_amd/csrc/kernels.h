@@ -253,7 +253,7 @@ hipError_t launch_init_conv(int dtype, const InitConvArgs& a, hipStream_t s);
 int init_conv_ntiles(int H, int W, bool mfma);  // mfma: the 2-byte engines' kernel (8 x 32 tiles); else 16 x 16
 //   final: NHWC T -> affine + SiLU -> 3x3 conv C->Cout(3) -> fp32 NCHW; the MFMA variant (2-byte T)
 //   can apply LCMScheduler.step to its own output in the epilogue (fuse_step).
-struct StepCoef { float sa, sb, sap, sbp; int is_last; int vpred; int clamp_x0; };
+struct StepCoef { float sa, sb, sap, sbp; int is_last; int vpred; int clamp_x0; int sampler; };  // llie_step_coef; sampler 1 = DDIM
 struct FinalConvArgs {
   const void* in; const float* as; const float* ab;
   const float* w; const float* bias;             // [9][C][4] (repacked, zero padded), [Cout]

@@ -1137,6 +1137,8 @@ hipError_t launch_postprocess_u8(const float* x, int B, int S, uint8_t* img, int
 // =============================================================================================
 // LCMScheduler.step (lcm_scheduler.py:204-242), same operation order as the reference:
 //   x0 = (x - sb*eps)/sa  |  x0 = sa*x - sb*v ;  prev = last ? x0 : sap*x0 + sbp*noise
+// sampler == 1, the deterministic DDIM step (low_light_diffusion.py:365-379): the predicted noise takes the draw's place,
+//   eh = eps  |  sa*v + sb*x ;  prev = last ? x0 : sap*x0 + sbp*eh          (noise is not read)
 __global__ void lcm_step_kernel(const float* eps, const float* x, const float* noise, float* prev, float* x0o,
                                 float* clamped, int64_t n, StepCoef c) {
 #pragma clang fp contract(off)
@@ -1148,14 +1150,20 @@ __global__ void lcm_step_kernel(const float* eps, const float* x, const float* n
   else x0 = (xv - c.sb * e) / c.sa;
   if (c.clamp_x0) x0 = fminf(fmaxf(x0, -1.f), 1.f);
   float p = x0;
-  if (!c.is_last) p = c.sap * x0 + c.sbp * noise[i];
+  if (!c.is_last) {
+    float nz;
+    if (!c.sampler) nz = noise[i];
+    else if (c.vpred) nz = c.sa * e + c.sb * xv;
+    else nz = e;
+    p = c.sap * x0 + c.sbp * nz;
+  }
   prev[i] = p;
   if (x0o) x0o[i] = x0;
   if (clamped) clamped[i] = fminf(fmaxf(p, -1.f), 1.f);
 }
 hipError_t launch_lcm_step(const float* eps, const float* x, const float* noise, float* prev, float* x0,
                            float* clamped, int64_t n, StepCoef c, hipStream_t s) {
-  if (!c.is_last && !noise) return hipErrorInvalidValue;
+  if ((!c.is_last && !c.sampler && !noise) || (c.sampler && c.clamp_x0)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(lcm_step_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, eps, x, noise, prev, x0,
                      clamped, n, c);
   return hipGetLastError();

@@ -8,7 +8,7 @@
 //                     out = (uint8) trunc(min(max((num / den + 1.0f) * 127.5f, 0), 255)),  w[k] = min(k + 1, S - k, v) / v  (1 if v == 0)
 //   tile_sync_step:   one LCM step of the latent canvas [3][Hc][Wc] (Hc / Wc = max(H / W, S)) every tile of an image shares: per
 //                     canvas pixel and channel, e = the eps of the one covering tile, or num / den of tile_blend_u8's sums over
-//                     eps when several cover it; then lcm_step_kernel's arithmetic (small.hip) on (e, canvas, noise), written
+//                     eps when several cover it; then lcm_step_kernel's arithmetic (small.hip; LCM or DDIM) on (e, canvas, noise), written
 //                     back to the canvas, and on request tile_blend_u8's bytes of the result for y < H, x < W
 //
 //
@@ -239,15 +239,16 @@ __global__ void __launch_bounds__(kTileThreads) tile_sync_step_kernel(const floa
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const float* xs = canvas_in + c * plane + at;
-    const float* ns = sc.is_last ? xs : noise + c * plane + at;  // read only when this is not the last step
+    const bool draw = !sc.is_last && !sc.sampler;  // the DDIM step (sampler 1) re-noises with the predicted noise: nothing to read
+    const float* ns = draw ? noise + c * plane + at : xs;
     f32x4 xv = {0.f, 0.f, 0.f, 0.f}, nz = {0.f, 0.f, 0.f, 0.f}, pv;
     if (whole) {
       xv = *reinterpret_cast<const f32x4u*>(xs);
-      if (!sc.is_last) nz = *reinterpret_cast<const f32x4u*>(ns);
+      if (draw) nz = *reinterpret_cast<const f32x4u*>(ns);
     } else {
       for (int k = 0; X0 + k < Wc; ++k) {
         xv[k] = xs[k];
-        if (!sc.is_last) nz[k] = ns[k];
+        if (draw) nz[k] = ns[k];
       }
     }
 #pragma unroll
@@ -258,7 +259,11 @@ __global__ void __launch_bounds__(kTileThreads) tile_sync_step_kernel(const floa
       else x0 = (xv[k] - sc.sb * e) / sc.sa;
       if (sc.clamp_x0) x0 = fminf(fmaxf(x0, -1.f), 1.f);
       float pr = x0;
-      if (!sc.is_last) pr = sc.sap * x0 + sc.sbp * nz[k];
+      if (!sc.is_last) {
+        float z = nz[k];
+        if (sc.sampler) z = sc.vpred ? sc.sa * e + sc.sb * xv[k] : e;
+        pr = sc.sap * x0 + sc.sbp * z;
+      }
       pv[k] = pr;
       b[k * 3 + c] = (uint32_t)truncf(fminf(fmaxf((pr + 1.0f) * 127.5f, 0.f), 255.f));
     }
@@ -367,7 +372,7 @@ hipError_t launch_tile_blend_u8(const float* tiles, const TilePlan& p, uint8_t* 
 
 hipError_t launch_tile_sync_step(const float* eps, const TilePlan& p, const float* canvas_in, const float* noise, const StepCoef& c,
                                  float* canvas_out, uint8_t* img, hipStream_t s) {
-  if (!tile_plan_ok(p.H, p.W, p.S, p.v) || (!c.is_last && !noise)) return hipErrorInvalidValue;
+  if (!tile_plan_ok(p.H, p.W, p.S, p.v) || (!c.is_last && !c.sampler && !noise) || (c.sampler && c.clamp_x0)) return hipErrorInvalidValue;
   const int Hc = p.H > p.S ? p.H : p.S, Wc = p.W > p.S ? p.W : p.S;
   if (!tile_plan_ok(Hc, Wc, p.S, p.v)) return hipErrorInvalidValue;
   const int ny = tile_axis_count(p.H, p.S, p.v), nx = tile_axis_count(p.W, p.S, p.v);

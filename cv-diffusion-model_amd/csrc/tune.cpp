@@ -33,6 +33,9 @@ static Knobs knob_defaults() {
   // stretch each other, so per-kernel durations are only meaningful from a single chain: llie_profile_* already forces
   // the eager single chain, and LLIE_ENHANCE_SPLIT=0 (or llie_tune("enhance_split", 0)) gives rocprofv3 the same.
   k.enhance_split = getenv("LLIE_ENHANCE_SPLIT") ? atoi(getenv("LLIE_ENHANCE_SPLIT")) : 2;
+  // Loops longer than this are not captured (llie_tune("graph_max_steps", n); n <= 0 restores the default): DESIGN.md 7 has the
+  // measurement behind the number.
+  k.graph_max_steps = kGraphMaxSteps;
   // Captured graphs bake in the kernel choices of the moment: every llie_tune call starts a new epoch of the graph cache.
   k.epoch = 0;
   return k;
@@ -80,6 +83,7 @@ int llie_tune(const char* knob, int value) {
   if (!strcmp(knob, "pwx_stamp")) { pw_expand_debug(value); return LLIE_OK; }
   if (!strcmp(knob, "bwd_async")) { g_knobs.bwd_async = value; return LLIE_OK; }
   if (!strcmp(knob, "enhance_split")) { g_knobs.enhance_split = value; return LLIE_OK; }
+  if (!strcmp(knob, "graph_max_steps")) { g_knobs.graph_max_steps = value > 0 ? value : kGraphMaxSteps; return LLIE_OK; }
   return LLIE_ERR_ARG;
 }
 

@@ -40,6 +40,7 @@ import torch.nn.functional as F
 
 from . import _native as N
 from .data import DeviceFrameStore, DevicePairLoader
+from .ddim import check_sampler
 from .tiling import enhance_tiled, enhance_frame_u8, frame_pad
 
 WINDOW_TAPS, WINDOW_SIGMA = 11, 1.5
@@ -317,9 +318,12 @@ def _swapped_weights(model, weights: Optional[Sequence[torch.Tensor]]):
                 p.data.copy_(s)
 
 
-def _steps_of(model, num_inference_steps: Optional[int], dev) -> Tuple[int, int]:
-    """(the argument `enhance` takes, the number of noise draws it consumes)."""
+def _steps_of(model, num_inference_steps: Optional[int], dev, sampler: str = "lcm") -> Tuple[int, int]:
+    """(the argument `enhance` takes, the number of noise draws it consumes: one per step for the LCM loop, 1 for DDIM)."""
     nsteps = model.num_inference_steps if num_inference_steps is None else int(num_inference_steps)
+    if check_sampler(sampler) == "ddim":
+        model.ddim_schedule(nsteps)  # the schedule's ValueErrors, before anything is drawn
+        return nsteps, 1
     model.scheduler.set_timesteps(nsteps, device=dev)
     return nsteps, len(model.scheduler._timestep_list)
 
@@ -336,7 +340,7 @@ def _summary(names, triples: np.ndarray, loss: Optional[float]) -> Dict[str, obj
 
 @torch.no_grad()
 def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[int] = None, seed: int = 0, loss: bool = True,
-             weights: Optional[Sequence[torch.Tensor]] = None) -> Dict[str, object]:
+             weights: Optional[Sequence[torch.Tensor]] = None, sampler: str = "lcm") -> Dict[str, object]:
     """PSNR / SSIM / MSE of `model.enhance` against the normal-light images of `loader` (normally a "val" DevicePairLoader:
     centre crops in file order, last partial batch kept), and the validation loss of the reference's `LowLightTrainer.validate`.
 
@@ -349,11 +353,14 @@ def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[i
       `model.enhance(low_light, num_inference_steps, noise=noise)` is scored against `normal_light` by `image_metrics` in the
       model's range (-1, 1); the batch loss is F.mse_loss(model.forward(low_light, normal_light, timesteps=t, noise=eps)
       ["noise_pred"], eps) without gradients.
+      sampler="ddim" scores `model.enhance(..., sampler="ddim")`, the deterministic sampler of a many-step model, at any
+      `num_inference_steps` in 1..T: steps = 1 in the recipe above (the initial latents are the only noise), the rest is unchanged.
 
     Returns {"n", "psnr", "ssim", "mse", ["loss",] "per_image": {"filename", "psnr", "ssim", "mse"}}: psnr / ssim / mse are the
     means over images of the per-image values (float64 sums in file order), loss = sum of batch losses / len(loader).  Everything
     stays on the device until one copy at the end.  `weights=` (e.g. FusedAdamW.ema_tensors(), in model.parameters() order) is
     copied into the parameters for the call and the original values are restored afterwards, also when the call raises."""
+    check_sampler(sampler)
     if not isinstance(loader, DevicePairLoader):
         raise ValueError(f"evaluate expects a DevicePairLoader, got {type(loader).__name__}")
     dev = loader.store.device
@@ -363,7 +370,7 @@ def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[i
         s = int(model.image_size)
         if loader.image_size != s:
             raise ValueError(f"the loader crops {loader.image_size} x {loader.image_size}, the model takes {s} x {s}")
-        nsteps, steps = _steps_of(model, num_inference_steps, dev)
+        nsteps, steps = _steps_of(model, num_inference_steps, dev, sampler)
         t_max = int(model.scheduler.config.num_train_timesteps)
         g = torch.Generator(device=dev).manual_seed(int(seed))
         names, triples, losses = [], [], []
@@ -374,7 +381,7 @@ def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[i
             if loss:
                 t = torch.randint(0, t_max, (b,), generator=g, device=dev)
                 eps = torch.randn(b, 3, s, s, generator=g, device=dev)
-            triples.append(_metrics_out3(model.enhance(low, nsteps, noise=noise), normal, (-1.0, 1.0)))
+            triples.append(_metrics_out3(model.enhance(low, nsteps, noise=noise, sampler=sampler), normal, (-1.0, 1.0)))
             if loss:
                 pred = model.forward(low, normal, timesteps=t, noise=eps)["noise_pred"]
                 losses.append(F.mse_loss(pred, eps).double().reshape(1))
@@ -391,7 +398,7 @@ def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[i
 def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_steps: Optional[int] = None, seed: int = 0,
                              overlap: Optional[int] = None, tile_batch: int = 32,
                              weights: Optional[Sequence[torch.Tensor]] = None, mode: str = "tiled",
-                             sync: str = "none") -> Dict[str, object]:
+                             sync: str = "none", sampler: str = "lcm") -> Dict[str, object]:
     """PSNR / SSIM / MSE at the images' own resolution: every low-light frame of the paired `store` (any sizes >= 11 x 11) goes
     through `enhance_tiled` and is scored against its normal-light frame on the bytes (x = byte / 255).
 
@@ -405,13 +412,15 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
     frame_pad(H / W):  canvas = torch.randn(steps, 3, Hp, Wp, generator=g, device=dev), then enhance_frame_u8(model,
     store.frame(i), num_inference_steps, noise=canvas).  `overlap` / `tile_batch` / `sync` belong to the tiles and are refused.
 
-    sync="latents" (mode="tiled") passes through to `enhance_tiled`: the tiles share one latent canvas at every step."""
+    sync="latents" (mode="tiled") passes through to `enhance_tiled`: the tiles share one latent canvas at every step.
+    sampler="ddim" passes through to `enhance_tiled` / `enhance_frame_u8` in every mode; steps = 1 in the draws above."""
     if mode not in ("tiled", "frame"):
         raise ValueError(f'mode must be "tiled" or "frame", got {mode!r}')
     if mode == "frame" and (overlap is not None or tile_batch != 32 or sync != "none"):
         raise ValueError('overlap / tile_batch / sync belong to mode="tiled"')
     if sync not in ("none", "latents"):
         raise ValueError(f'sync must be "none" or "latents", got {sync!r}')
+    check_sampler(sampler)
     if not isinstance(store, DeviceFrameStore) or not store.paired:
         raise ValueError("evaluate_full_resolution expects a paired DeviceFrameStore")
     dev = store.device
@@ -419,17 +428,18 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
         raise RuntimeError(f"evaluate_full_resolution runs only on a HIP device (the frame store is on '{dev}'); there is no CPU fallback")
     with _swapped_weights(model, weights):
         s = int(model.image_size)
-        nsteps, steps = _steps_of(model, num_inference_steps, dev)
+        nsteps, steps = _steps_of(model, num_inference_steps, dev, sampler)
         g = torch.Generator(device=dev).manual_seed(int(seed))
         n = len(store)
         triples = []
         for i, (h, w) in enumerate(store.sizes):
             if mode == "frame":
                 canvas = torch.randn(steps, 3, frame_pad(h), frame_pad(w), generator=g, device=dev)
-                out = enhance_frame_u8(model, store.frame(i), nsteps, noise=canvas)
+                out = enhance_frame_u8(model, store.frame(i), nsteps, noise=canvas, sampler=sampler)
             else:
                 canvas = torch.randn(steps, 3, max(h, s), max(w, s), generator=g, device=dev)
-                out = enhance_tiled(model, store.frame(i), nsteps, overlap=overlap, tile_batch=tile_batch, noise=canvas, sync=sync)
+                out = enhance_tiled(model, store.frame(i), nsteps, overlap=overlap, tile_batch=tile_batch, noise=canvas, sync=sync,
+                                    sampler=sampler)
             triples.append(_metrics_out3(out, store.frame(n + i), None))
         flat = torch.cat(triples).cpu().numpy()
     return _summary(store.names, flat, None)

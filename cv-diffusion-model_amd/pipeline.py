@@ -32,6 +32,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _native as N
+from .ddim import check_sampler
 from .scheduler import LCMScheduler
 from .unet import EfficientUNet, create_efficient_unet
 
@@ -40,6 +41,17 @@ from .unet import EfficientUNet, create_efficient_unet
 class LowLightDiffusionOutput:
     enhanced: torch.Tensor
     intermediate: Optional[list] = None
+
+
+def supplied_noise(noise, draws: int, b: int, h: int, w: int, device, sampler: str = "lcm") -> torch.Tensor:
+    """`noise=` of `enhance` / `enhance_frame` as the fp32 [draws,b,3,h,w] tensor the engine reads: a tensor of that shape or a
+    list of `draws` tensors [b,3,h,w].  draws = the step count for the LCM loop, 1 for DDIM (the initial latents only)."""
+    noise_t = noise if isinstance(noise, torch.Tensor) else torch.stack([n.to(device) for n in noise])
+    noise_t = noise_t.to(device=device, dtype=torch.float32)
+    if tuple(noise_t.shape) != (draws, b, 3, h, w):
+        raise ValueError(f"noise must be [{draws},{b},3,{h},{w}]" + (" (DDIM draws the initial latents only)" if sampler == "ddim" else "")
+                         + f", got {list(noise_t.shape)}")
+    return noise_t
 
 
 class LowLightDiffusion(nn.Module):
@@ -114,14 +126,22 @@ class LowLightDiffusion(nn.Module):
     def enhance(self, low_light: torch.Tensor, num_inference_steps: Optional[int] = None,
                 generator: Optional[torch.Generator] = None, return_intermediate: bool = False, *,
                 noise: Optional[Union[torch.Tensor, Sequence[torch.Tensor]]] = None,
-                return_noise_pred: bool = False) -> Union[torch.Tensor, LowLightDiffusionOutput]:
+                return_noise_pred: bool = False, sampler: str = "lcm") -> Union[torch.Tensor, LowLightDiffusionOutput]:
         """low_light [B,3,S,S] in [-1,1] -> enhanced [B,3,S,S].
+
+        sampler="lcm" (the default) is the reference's loop: predict x0, re-noise with a fresh draw -- the sampler of a
+        consistency student.  sampler="ddim" (extension; ddim.py has the definition) is the deterministic DDIM loop (eta = 0)
+        of a many-step epsilon- or v-prediction model: `num_inference_steps` may be anything in 1..num_train_timesteps (the
+        grid t_i = (n-1-i) * (T // n)), the initial latents are the only draw -- `generator` seeds it, and with one the global
+        generator is not touched -- and `noise=` is [1,B,3,S,S] or a one-element list.  Any other string is a ValueError, and so
+        is DDIM with a scheduler that clamps x0 (LCMDenoisingLoop).
 
         Noise: by default drawn on the device in the reference's order -- the initial latents with
         `generator` (:208-211), then one draw per non-final step from the global generator
         (lcm_scheduler.py:237).  `noise=` (extension) supplies those draws, e.g. CPU-generated ones for
         a bit-comparable run against the CPU reference: a [steps,B,3,S,S] tensor or a list of `steps`
         tensors (entries after the first are the re-noising draws of steps 0..steps-2)."""
+        check_sampler(sampler)
         device = low_light.device
         if device.type != "cuda":
             raise RuntimeError("LowLightDiffusion.enhance runs only on a HIP device; there is no CPU fallback")
@@ -129,61 +149,80 @@ class LowLightDiffusion(nn.Module):
         if tuple(low_light.shape[1:]) != (3, s, s):
             raise ValueError(f"low_light must be [B,3,{s},{s}] (latents are allocated at image_size, "
                              f"low_light_diffusion.py:208-210); got {tuple(low_light.shape)}")
-        return self._enhance_at(low_light, None, num_inference_steps, generator, return_intermediate, noise, return_noise_pred)
+        return self._enhance_at(low_light, None, num_inference_steps, generator, return_intermediate, noise, return_noise_pred, sampler)
 
     @torch.no_grad()
     def enhance_frame(self, low_light: torch.Tensor, num_inference_steps: Optional[int] = None,
                       generator: Optional[torch.Generator] = None, return_intermediate: bool = False, *,
                       noise: Optional[Union[torch.Tensor, Sequence[torch.Tensor]]] = None,
-                      return_noise_pred: bool = False) -> Union[torch.Tensor, LowLightDiffusionOutput]:
-        """Frame mode (extension): low_light [B,3,H,W] in [-1,1] -> enhanced [B,3,H,W], the whole LCM loop at the frame's own
-        size.  The module tree is the one `image_size` fixed (attention placement, state_dict); the network is fully
-        convolutional and its attention linear in the pixel count, so it runs at any H x W the engine's frame rule accepts
-        (llie_frame_shape_ok): H and W multiples of 8 and at least 64, B <= 65535, and B*H*W times the widest full-resolution
+                      return_noise_pred: bool = False, sampler: str = "lcm") -> Union[torch.Tensor, LowLightDiffusionOutput]:
+        """Frame mode (extension): low_light [B,3,H,W] in [-1,1] -> enhanced [B,3,H,W], the whole loop (`sampler`: as in
+        `enhance`) at the frame's own size.  The module tree is the one `image_size` fixed (attention placement, state_dict); the
+        network is fully convolutional and its attention linear in the pixel count, so it runs at any H x W the engine's frame rule
+        accepts (llie_frame_shape_ok): H and W multiples of 8 and at least 64, B <= 65535, and B*H*W times the widest full-resolution
         channel count at most 2^31 - 1 (about 5.59 M pixels per call for `small`).  A frame that breaks a rule raises
         ValueError naming it; frames past the size cap go through `enhance_tiled`.
 
-        Semantics, noise order and outputs are `enhance`'s, with [steps,B,3,H,W] noise; on an S x S input the result is
-        `enhance`'s, bit for bit.  Inference only."""
+        Semantics, noise order and outputs are `enhance`'s, with [steps,B,3,H,W] noise ([1,B,3,H,W] for DDIM); on an S x S input the
+        result is `enhance`'s, bit for bit.  Inference only."""
+        check_sampler(sampler)
         device = low_light.device
         if device.type != "cuda":
             raise RuntimeError("LowLightDiffusion.enhance_frame runs only on a HIP device; there is no CPU fallback")
         if low_light.dim() != 4 or low_light.shape[1] != 3:
             raise ValueError(f"low_light must be [B,3,H,W]; got {tuple(low_light.shape)}")
         return self._enhance_at(low_light, (int(low_light.shape[2]), int(low_light.shape[3])), num_inference_steps, generator,
-                                return_intermediate, noise, return_noise_pred)
+                                return_intermediate, noise, return_noise_pred, sampler)
 
-    def _enhance_at(self, low_light, frame, num_inference_steps, generator, return_intermediate, noise, return_noise_pred):
+    def ddim_schedule(self, num_inference_steps: Optional[int] = None) -> Tuple[List[int], List[N.StepCoef]]:
+        """(timesteps, one N.StepCoef each) of the DDIM loop of `num_inference_steps` steps (default: self.num_inference_steps).
+        ValueError for a step count outside 1..num_train_timesteps, a first timestep whose alpha-bar is 0 under epsilon
+        prediction, and a scheduler without the DDIM step (LCMDenoisingLoop clamps x0, which DDIM does not define)."""
+        n = self.num_inference_steps if num_inference_steps is None else num_inference_steps
+        if not isinstance(self.scheduler, LCMScheduler):
+            raise ValueError(f'sampler="ddim" is not defined for {type(self.scheduler).__name__} (the deployment loop clamps x0); '
+                             f"use an LCMScheduler")
+        ts = self.scheduler.ddim_timesteps(n)
+        c = int(self.scheduler.config.num_train_timesteps) // len(ts)
+        return ts, [self.scheduler.ddim_step_coefficients(t, t - c) for t in ts]
+
+    def _enhance_at(self, low_light, frame, num_inference_steps, generator, return_intermediate, noise, return_noise_pred,
+                    sampler="lcm"):
         """The loop of `enhance` (frame is None: image_size, llie_enhance) and `enhance_frame` (frame = (H, W), llie_enhance_hw)."""
         device = low_light.device
         b = low_light.shape[0]
         hh, ww = frame if frame is not None else (self.image_size, self.image_size)
         steps = self.num_inference_steps if num_inference_steps is None else num_inference_steps
-        self.scheduler.set_timesteps(steps, device=device)
-        ts = self.scheduler._timestep_list
+        ddim = sampler == "ddim"
+        if ddim:
+            ts, coef_list = self.ddim_schedule(steps)
+        else:
+            self.scheduler.set_timesteps(steps, device=device)
+            ts = self.scheduler._timestep_list
         steps = len(ts)
+        draws = 1 if ddim else steps  # DDIM: the initial latents are the only noise
+        # the staging area of the engine's captured loop: LCM stages one draw per step; DDIM stages none past the first, so only
+        # the per-step outputs a caller asks for make it grow with the step count
+        stage_steps = 8 if ddim and not (return_intermediate or return_noise_pred) else max(steps, 8)
         prepared = None
         if frame is not None:
             try:  # the workspace query applies the frame rule: a refused frame raises before any draw or launch
-                prepared = self.unet._prepare(b, device, enhance_steps=max(steps, 8), frame=frame)
+                prepared = self.unet._prepare(b, device, enhance_steps=stage_steps, frame=frame)
             except ValueError as e:
                 hint = "; enhance_tiled handles images of any size" if "element cap" in str(e) else ""
                 raise ValueError(f"enhance_frame: {e}{hint}") from None
 
         if noise is None:
             # drawn straight into the [steps,B,3,S,S] buffer the engine reads (same generator streams as torch.randn)
-            noise_t = torch.empty(steps, b, 3, hh, ww, dtype=torch.float32, device=device)
+            noise_t = torch.empty(draws, b, 3, hh, ww, dtype=torch.float32, device=device)
             noise_t[0].normal_(generator=generator)
-            for i in range(1, steps):
+            for i in range(1, draws):
                 noise_t[i].normal_()
         else:
-            noise_t = noise if isinstance(noise, torch.Tensor) else torch.stack([n.to(device) for n in noise])
-            noise_t = noise_t.to(device=device, dtype=torch.float32)
-            if tuple(noise_t.shape) != (steps, b, 3, hh, ww):
-                raise ValueError(f"noise must be [{steps},{b},3,{hh},{ww}]")
+            noise_t = supplied_noise(noise, draws, b, hh, ww, device, sampler)
         noise_t = noise_t.contiguous()
 
-        coefs = (N.StepCoef * steps)(*[self.scheduler.step_coefficients(t) for t in ts])
+        coefs = (N.StepCoef * steps)(*(coef_list if ddim else [self.scheduler.step_coefficients(t) for t in ts]))
         tkey = (tuple(ts), b, device.type, device.index)
         t_dev = self._t_cache.get(tkey)  # [steps*B] device timesteps: one H2D copy per (schedule, batch), not per call
         if t_dev is None:
@@ -194,7 +233,7 @@ class LowLightDiffusion(nn.Module):
         enhanced = torch.empty(b, 3, hh, ww, dtype=torch.float32, device=device)
         inter = torch.empty(steps, b, 3, hh, ww, dtype=torch.float32, device=device) if return_intermediate else None
         preds = torch.empty(steps, b, 3, hh, ww, dtype=torch.float32, device=device) if return_noise_pred else None
-        h, ws, nbytes = prepared if prepared is not None else self.unet._prepare(b, device, enhance_steps=max(steps, 8))
+        h, ws, nbytes = prepared if prepared is not None else self.unet._prepare(b, device, enhance_steps=stage_steps)
         outs = (enhanced.data_ptr(), inter.data_ptr() if inter is not None else None, preds.data_ptr() if preds is not None else None)
         stream = torch.cuda.current_stream(device).cuda_stream
         with torch.cuda.device(device):

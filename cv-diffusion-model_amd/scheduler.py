@@ -15,12 +15,17 @@ from typing import List, Optional, Tuple, Union
 import torch
 
 from . import _native as N
+from . import ddim as D
 
 
 @dataclass
 class LCMSchedulerOutput:
     prev_sample: torch.Tensor
     pred_original_sample: Optional[torch.Tensor] = None
+
+
+def _to_numpy(v):
+    return v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v
 
 
 def _require_cuda(t: torch.Tensor, what: str) -> None:
@@ -118,6 +123,63 @@ class LCMScheduler:
             raise ValueError(f"Unknown prediction type: {ptype}")
         return N.StepCoef(float(a_t ** 0.5), float((1 - a_t) ** 0.5), float(a_p ** 0.5), float((1 - a_p) ** 0.5),
                           int(prev_t == 0), int(ptype == "v_prediction"))
+
+    # ------------------------------------------------------------------ deterministic DDIM (extension; ddim.py has the definition)
+    def _ptype(self) -> str:
+        ptype = self.config.prediction_type
+        if ptype not in ("epsilon", "v_prediction"):
+            raise ValueError(f"Unknown prediction type: {ptype}")
+        return ptype
+
+    def _check_ddim_start(self, t: int) -> None:
+        if self._ptype() == "epsilon" and float(self.alphas_cumprod[t]) == 0.0:
+            raise ValueError(f"alphas_cumprod[{t}] == 0 (zero terminal SNR): epsilon prediction defines no x0 at timestep {t}, so a "
+                             f"DDIM schedule cannot contain it; use fewer steps than num_train_timesteps, or v prediction")
+
+    def ddim_timesteps(self, n: int) -> List[int]:
+        """t_i = (n - 1 - i) c, c = num_train_timesteps // n, for 1 <= n <= num_train_timesteps; the previous timestep of t is
+        t - c and t = 0 is the final step.  ValueError when the first timestep has alpha-bar 0 under epsilon prediction (n =
+        num_train_timesteps with the zero-SNR table: timestep 999)."""
+        ts = D.ddim_timesteps(n, self.config.num_train_timesteps)
+        self._check_ddim_start(ts[0])
+        return ts
+
+    def ddim_step_coefficients(self, timestep: int, prev_timestep: int) -> N.StepCoef:
+        """Scalars of one DDIM step t -> prev_t (prev_t < 0: the final step), in the 0-d fp32 tensor arithmetic of
+        `step_coefficients`."""
+        t, prev_t = int(timestep), int(prev_timestep)
+        if not 0 <= t < int(self.alphas_cumprod.numel()) or prev_t > t:
+            raise ValueError(f"a DDIM step goes from a timestep in [0, {int(self.alphas_cumprod.numel())}) to one that is not later, "
+                             f"got {t} -> {prev_t}")
+        self._check_ddim_start(t)
+        a_t = self.alphas_cumprod[t]
+        a_p = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod  # unused on the final step
+        return N.StepCoef(float(a_t ** 0.5), float((1 - a_t) ** 0.5), float(a_p ** 0.5), float((1 - a_p) ** 0.5),
+                          int(prev_t < 0), int(self._ptype() == "v_prediction"), 0, N.SAMPLER_DDIM)
+
+    def ddim_step(self, model_output: torch.Tensor, timestep: int, prev_timestep: int, sample: torch.Tensor,
+                  return_dict: bool = True) -> Union[LCMSchedulerOutput, Tuple]:
+        """One deterministic DDIM step on the device (llie_lcm_step with a DDIM coefficient; no noise is read)."""
+        _require_cuda(sample, "LCMScheduler.ddim_step")
+        coef = self.ddim_step_coefficients(timestep, prev_timestep)
+        sample_c = sample.detach().float().contiguous()
+        mo = model_output.detach().float().contiguous()
+        if mo.shape != sample_c.shape:
+            raise ValueError(f"model_output and sample must have one shape, got {tuple(mo.shape)} and {tuple(sample_c.shape)}")
+        prev = torch.empty_like(sample_c)
+        x0 = torch.empty_like(sample_c)
+        with torch.cuda.device(sample.device):
+            N.check(N.lib().llie_lcm_step(mo.data_ptr(), sample_c.data_ptr(), None, prev.data_ptr(), x0.data_ptr(), None,
+                                          sample_c.numel(), coef, torch.cuda.current_stream(sample.device).cuda_stream),
+                    "LCMScheduler.ddim_step")
+        if return_dict:
+            return LCMSchedulerOutput(prev_sample=prev, pred_original_sample=x0)
+        return (prev, x0)
+
+    def ddim_step_host(self, model_output, timestep: int, prev_timestep: int, sample):
+        """The float64 NumPy definition of `ddim_step` on this scheduler's table (ddim.ddim_step_host) -> the next latents."""
+        return D.ddim_step_host(_to_numpy(model_output), timestep, prev_timestep, _to_numpy(sample), self.alphas_cumprod.cpu().numpy(),
+                                self._ptype() == "v_prediction")
 
     # ------------------------------------------------------------------ tensor ops on the device
     def step(self, model_output: torch.Tensor, timestep: int, sample: torch.Tensor,

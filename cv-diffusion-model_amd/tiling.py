@@ -27,6 +27,8 @@ in `enhance`'s order (entry 0 the initial latents, entry k+1 the re-noising draw
           x0 = (x - sb*e) / sa  (epsilon)  |  sa*x - sb*e  (v);  clip to [-1,1] if clamp_x0;  p = x0 if is_last else sap*x0 + sbp*noise,
                with x = X[c][Y][X], noise = canvas[k+1][c][Y][X] and the scalars of `scheduler.step_coefficients(t)`: lcm_step_kernel
           X[c][Y][X] = p
+          sampler="ddim" (coef.sampler == 1; ddim.py): no noise canvas past entry 0, and the predicted noise takes the draw's place,
+               p = x0 if is_last else sap*x0 + sbp*z,  z = e (epsilon)  |  sa*e + sb*x (v);  not defined together with clamp_x0
   out[y][x][c] = uint8(trunc(clip((X[c][y][x] + 1) * 127.5, 0, 255)))  for y < H, x < W    # after the last step
 
 Every multiply and add is a separate fp32 operation, in the order written.  A pixel under exactly one tile skips the weights and
@@ -50,6 +52,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .ddim import check_sampler
 
 
 def _check_plan(tile: int, overlap: int) -> None:
@@ -159,7 +162,7 @@ def _step_scalars(coef):
     """The fp32 scalars and flags of one N.StepCoef, as the kernels get them."""
     f = np.float32
     return (f(coef.sqrt_alpha_t), f(coef.sqrt_beta_t), f(coef.sqrt_alpha_prev), f(coef.sqrt_beta_prev), bool(coef.is_last),
-            bool(coef.v_prediction), bool(coef.clamp_x0))
+            bool(coef.v_prediction), bool(coef.clamp_x0), int(coef.sampler))
 
 
 def _check_sync_shapes(eps_shape, size, overlap: int, canvas_shape, noise_shape) -> Tuple[int, int, int]:
@@ -180,10 +183,13 @@ def _check_sync_shapes(eps_shape, size, overlap: int, canvas_shape, noise_shape)
 def sync_step_array(eps_tiles: np.ndarray, size: Tuple[int, int], overlap: int, canvas: np.ndarray, noise: Optional[np.ndarray],
                     coef) -> np.ndarray:
     """One step of the shared latent canvas (module docstring): eps tiles fp32 [T,3,S,S], canvas and noise fp32 [3,Hc,Wc], `coef`
-    an N.StepCoef -> the new canvas.  `noise` may be None on the last step."""
+    an N.StepCoef -> the new canvas.  `noise` may be None on the last step, and on every step of the DDIM sampler (coef.sampler
+    == 1), which reads none."""
     h, w, s = _check_sync_shapes(eps_tiles.shape, size, overlap, canvas.shape, None if noise is None else noise.shape)
-    sa, sb, sap, sbp, last, vpred, clamp = _step_scalars(coef)
-    if not last and noise is None:
+    sa, sb, sap, sbp, last, vpred, clamp, sampler = _step_scalars(coef)
+    if sampler not in (N.SAMPLER_LCM, N.SAMPLER_DDIM) or (sampler == N.SAMPLER_DDIM and clamp):
+        raise ValueError("coef.sampler is 0 (LCM) or 1 (DDIM), and the DDIM step is not defined together with clamp_x0")
+    if not last and not sampler and noise is None:
         raise ValueError("a step that is not the last needs its noise")
     hc, wc = canvas.shape[1:]
     oys, oxs = tile_origins(h, s, overlap), tile_origins(w, s, overlap)
@@ -204,7 +210,11 @@ def sync_step_array(eps_tiles: np.ndarray, size: Tuple[int, int], overlap: int, 
     x0 = sa * x - sb * e if vpred else (x - sb * e) / sa
     if clamp:
         x0 = np.minimum(np.maximum(x0, np.float32(-1.0)), np.float32(1.0))
-    return x0 if last else sap * x0 + sbp * noise.astype(np.float32, copy=False)
+    if last:
+        return x0
+    if sampler == N.SAMPLER_DDIM:
+        return sap * x0 + sbp * (sa * e + sb * x if vpred else e)
+    return sap * x0 + sbp * noise.astype(np.float32, copy=False)
 
 
 def canvas_store_array(x: np.ndarray, size: Tuple[int, int]) -> np.ndarray:
@@ -216,21 +226,28 @@ def canvas_store_array(x: np.ndarray, size: Tuple[int, int]) -> np.ndarray:
     return np.clip((r + np.float32(1.0)) * np.float32(127.5), 0, 255).astype(np.uint8)
 
 
-def enhance_tiled_sync_array(eps_fn, rgb_u8: np.ndarray, tile: int, overlap: int, coefs, timesteps, canvas: np.ndarray):
+def enhance_tiled_sync_array(eps_fn, rgb_u8: np.ndarray, tile: int, overlap: int, coefs, timesteps, canvas: np.ndarray, *,
+                             sampler: str = "lcm"):
     """The loop of `enhance_tiled(sync="latents")` on the host, the denoiser passed in: eps_fn(lat [T,3,S,S], low [T,3,S,S], t)
-    -> fp32 [T,3,S,S].  `coefs[k]` is the N.StepCoef of `timesteps[k]`; `canvas` is the noise canvas [steps,3,Hc,Wc].
+    -> fp32 [T,3,S,S].  `coefs[k]` is the N.StepCoef of `timesteps[k]`; `canvas` is the noise canvas [steps,3,Hc,Wc], or
+    [1,3,Hc,Wc] with sampler="ddim" (the initial latents; `coefs` are then DDIM coefficients).
     -> (uint8 [H,W,3], the final fp32 canvas [3,Hc,Wc] before any clamp)."""
     h, w = _check_image(rgb_u8, "enhance_tiled_sync_array")
     hc, wc = max(h, tile), max(w, tile)
-    if canvas.ndim != 4 or tuple(canvas.shape) != (len(timesteps), 3, hc, wc) or len(coefs) != len(timesteps):
-        raise ValueError(f"{len(timesteps)} steps of a {h}x{w} image need a canvas [{len(timesteps)},3,{hc},{wc}] and as many coefficients")
+    ddim = check_sampler(sampler) == "ddim"
+    if any(int(c.sampler) != int(ddim) for c in coefs):
+        raise ValueError(f'sampler="{sampler}" needs coefficients of that sampler on every step')
+    draws = 1 if ddim else len(timesteps)
+    if canvas.ndim != 4 or tuple(canvas.shape) != (draws, 3, hc, wc) or len(coefs) != len(timesteps):
+        raise ValueError(f"{len(timesteps)} {sampler} steps of a {h}x{w} image need a canvas [{draws},3,{hc},{wc}] and "
+                         f"{len(timesteps)} coefficients")
     low = gather_tiles_array(rgb_u8, tile, overlap)
     origins = [(oy, ox) for oy in tile_origins(h, tile, overlap) for ox in tile_origins(w, tile, overlap)]
     x = canvas[0].astype(np.float32)
     for k, t in enumerate(timesteps):
         lat = np.stack([x[:, oy:oy + tile, ox:ox + tile] for oy, ox in origins])
         eps = np.asarray(eps_fn(lat, low, int(t)), dtype=np.float32)
-        x = sync_step_array(eps, (h, w), overlap, x, None if coefs[k].is_last else canvas[k + 1], coefs[k])
+        x = sync_step_array(eps, (h, w), overlap, x, None if coefs[k].is_last or ddim else canvas[k + 1], coefs[k])
     return canvas_store_array(x, (h, w)), x
 
 
@@ -357,8 +374,10 @@ def frame_store_device(x: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
 # ------------------------------------------------------------------ the whole path
 @torch.no_grad()
 def enhance_frame_u8(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int] = None, *,
-                     generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None,
+                     sampler: str = "lcm") -> torch.Tensor:
     """uint8 [H,W,3] on a HIP device -> enhanced uint8 [H,W,3] at the same resolution, by one run of the network at that size.
+    `sampler` is `enhance`'s: with "ddim" the noise canvas is [1,3,Hp,Wp], the initial latents.
 
     The image is loaded into a frame [3,Hp,Wp] (Hp / Wp = frame_pad(H / W): the next multiple of 8, at least 64) with its edge
     replicated into the padding, goes through `model.enhance_frame` at B = 1, and is cropped and denormalised back.  Noise is
@@ -370,6 +389,7 @@ def enhance_frame_u8(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[
     image and spends no work on overlaps; images past the engine's size cap (ValueError, naming it) remain with the tiles."""
     if not isinstance(rgb_u8, torch.Tensor):
         raise ValueError(f"enhance_frame_u8 expects a torch.Tensor, got {type(rgb_u8).__name__}")
+    check_sampler(sampler)
     h, w = _check_image(rgb_u8, "enhance_frame_u8")
     _require_hip(rgb_u8, "enhance_frame_u8")
     hp, wp = frame_pad(h), frame_pad(w)
@@ -378,7 +398,7 @@ def enhance_frame_u8(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[
             raise ValueError(f"noise must be a canvas [steps,3,{hp},{wp}]")
         noise = noise.to(device=rgb_u8.device, dtype=torch.float32)[:, None]
     low = frame_load_device(rgb_u8)[None]
-    out = model.enhance_frame(low, num_inference_steps, generator=generator, noise=noise)
+    out = model.enhance_frame(low, num_inference_steps, generator=generator, noise=noise, sampler=sampler)
     return frame_store_device(out[0], (h, w))
 
 
@@ -386,7 +406,7 @@ def enhance_frame_u8(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[
 @torch.no_grad()
 def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int] = None, *, overlap: Optional[int] = None,
                   tile_batch: int = 32, generator: Optional[torch.Generator] = None,
-                  noise: Optional[torch.Tensor] = None, sync: str = "none", return_canvas: bool = False):
+                  noise: Optional[torch.Tensor] = None, sync: str = "none", return_canvas: bool = False, sampler: str = "lcm"):
     """uint8 [H,W,3] on a HIP device -> enhanced uint8 [H,W,3] at the same resolution.
 
     The image is cut into S x S tiles (S = model.image_size) overlapping by `overlap` pixels (default S // 8, at most S // 2);
@@ -402,11 +422,15 @@ def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int
     canvas, every step denoises each tile's window of it (`tile_batch` tiles per `unet.forward_split`) and one launch fuses the
     predictions back into the canvas, so neighbours start every step from the same values where they overlap and the result is
     single-valued before any blending of pixels.  The attention is still per tile: only overlaps couple neighbours.  The noise
-    canvas is read the same way; `return_canvas=True` returns (image, the final fp32 canvas [3,max(H,S),max(W,S)] before the clamp)."""
+    canvas is read the same way; `return_canvas=True` returns (image, the final fp32 canvas [3,max(H,S),max(W,S)] before the clamp).
+
+    sampler="ddim" runs the deterministic DDIM loop of `enhance` in either `sync` mode: any step count in 1..num_train_timesteps,
+    and the canvas is [1,3,max(H,S),max(W,S)] -- the initial latents, drawn with `generator`; nothing else is drawn."""
     if not isinstance(rgb_u8, torch.Tensor):
         raise ValueError(f"enhance_tiled expects a torch.Tensor, got {type(rgb_u8).__name__}")
     if sync not in ("none", "latents"):
         raise ValueError(f'sync must be "none" or "latents", got {sync!r}')
+    ddim = check_sampler(sampler) == "ddim"
     if return_canvas and sync != "latents":
         raise ValueError('return_canvas needs sync="latents": the default path keeps no latent canvas')
     h, w = _check_image(rgb_u8, "enhance_tiled")
@@ -418,8 +442,14 @@ def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int
     _require_hip(rgb_u8, "enhance_tiled")
     dev = rgb_u8.device
     nsteps = model.num_inference_steps if num_inference_steps is None else num_inference_steps
-    model.scheduler.set_timesteps(nsteps, device=dev)
-    steps = len(model.scheduler._timestep_list)
+    if ddim:
+        schedule = model.ddim_schedule(nsteps)
+        steps = 1  # entries of the noise canvas: the initial latents
+    else:
+        model.scheduler.set_timesteps(nsteps, device=dev)
+        ts = model.scheduler._timestep_list
+        schedule = (ts, [model.scheduler.step_coefficients(t) for t in ts]) if sync == "latents" else None
+        steps = len(ts)
     hc, wc = max(h, s), max(w, s)
     if noise is None:
         canvas = torch.empty(steps, 3, hc, wc, dtype=torch.float32, device=dev)
@@ -433,24 +463,23 @@ def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int
     img = rgb_u8.contiguous()
     total = _tile_total(h, w, s, overlap)
     if sync == "latents":
-        out, x = _enhance_tiled_sync(model, img, s, overlap, tile_batch, canvas, total)
+        out, x = _enhance_tiled_sync(model, img, s, overlap, tile_batch, canvas, total, schedule)
         return (out, x) if return_canvas else out
     result = torch.empty(total, 3, s, s, dtype=torch.float32, device=dev)
     for first in range(0, total, tile_batch):
         count = min(tile_batch, total - first)
         low = gather_tiles_device(img, s, overlap, first, count)
         draws = gather_noise_device(canvas, (h, w), s, overlap, first, count)
-        result[first:first + count].copy_(model.enhance(low, nsteps, noise=draws))
+        result[first:first + count].copy_(model.enhance(low, nsteps, noise=draws, sampler=sampler))
     return blend_tiles_device(result, (h, w), overlap)
 
 
-def _enhance_tiled_sync(model, img: torch.Tensor, s: int, overlap: int, tile_batch: int, canvas: torch.Tensor, total: int):
-    """The loop of enhance_tiled(sync="latents") after its checks: `canvas` is the noise canvas, the scheduler's timesteps are
-    set.  Nothing inside the loop waits for the device or copies from the host."""
+def _enhance_tiled_sync(model, img: torch.Tensor, s: int, overlap: int, tile_batch: int, canvas: torch.Tensor, total: int, schedule):
+    """The loop of enhance_tiled(sync="latents") after its checks: `canvas` is the noise canvas, `schedule` the (timesteps,
+    coefficients) of the sampler.  Nothing inside the loop waits for the device or copies from the host."""
     h, w = int(img.shape[0]), int(img.shape[1])
     dev = img.device
-    ts = model.scheduler._timestep_list
-    coefs = [model.scheduler.step_coefficients(t) for t in ts]
+    ts, coefs = schedule
     t_dev = {}  # (timestep, count) -> device int64 [count], kept on the model like enhance's
     for t in ts:
         for count in {min(tile_batch, total), total % tile_batch} - {0}:
@@ -471,5 +500,6 @@ def _enhance_tiled_sync(model, img: torch.Tensor, s: int, overlap: int, tile_bat
             lat = gather_noise_device(x[None], (h, w), s, overlap, first, count)[0]
             model.unet.forward_split(lat, low, t_dev[int(t), count], uniform_t=True, out=eps[first:first + count])
         last = bool(coefs[k].is_last)
-        sync_step_device(eps, (h, w), overlap, x, None if last else canvas[k + 1], coefs[k], out=x, image=out if last else None)
+        draw = None if last or coefs[k].sampler else canvas[k + 1]  # the DDIM step reads no noise
+        sync_step_device(eps, (h, w), overlap, x, draw, coefs[k], out=x, image=out if last else None)
     return out, x

@@ -27,6 +27,7 @@ from torch.optim.lr_scheduler import CosineAnnealingLR, OneCycleLR
 from . import _native as N
 from . import hostio
 from .data import create_device_dataloaders
+from .ddim import check_sampler
 from .metrics import _require_hip, _steps_of, _swapped_weights, evaluate
 from .pipeline import LowLightDiffusion
 from .training import FusedAdamW, FusedGradScaler, TrainStep
@@ -231,12 +232,25 @@ class LowLightTrainer:
     `x0_ssim_weight` / `x0_l1_weight` (extension) go to TrainStep: the training loss gains the x0 term of pipeline.py, SSIM / L1
     of the predicted clean image against the normal-light image.  They are constructor arguments, not TrainingConfig fields,
     and are not written into checkpoints: a caller that resumes a run passes them again.  The validation loss stays the
-    reference's MSE."""
+    reference's MSE.
+
+    `val_sampler` / `val_steps` (extension; keywords like the x0 weights, neither TrainingConfig fields nor stored in checkpoints)
+    choose how validation and the sample sheet sample: val_sampler="ddim" is the deterministic sampler a many-step (teacher)
+    model wants, where the default "lcm" shows the 4-step loop of a consistency student; `val_steps` replaces
+    config.num_inference_steps in `validate` and the 4 steps of `generate_samples` (None keeps both; with "ddim" anything in
+    1..num_train_timesteps).  A schedule the model does not have is a ValueError here, not at the first validation."""
 
     def __init__(self, model: LowLightDiffusion, train_loader, val_loader=None, config: Optional[TrainingConfig] = None, *,
-                 x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0):
+                 x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0, val_sampler: str = "lcm", val_steps: Optional[int] = None):
         self.config = config or TrainingConfig()
         cfg = self.config
+        self.val_sampler = check_sampler(val_sampler)
+        if val_steps is not None and (isinstance(val_steps, bool) or int(val_steps) != val_steps or val_steps < 1):
+            raise ValueError(f"val_steps must be a positive integer or None, got {val_steps!r}")
+        self.val_steps = None if val_steps is None else int(val_steps)
+        if self.val_sampler == "ddim":
+            for n in (self._val_steps(cfg.num_inference_steps), self._val_steps(SAMPLE_STEPS)):
+                model.ddim_schedule(n)
         params = list(model.parameters())
         places = [("the model", params[0].device if params else torch.device("cpu")), ("train_loader", _loader_device(train_loader))]
         if val_loader is not None:
@@ -374,9 +388,13 @@ class LowLightTrainer:
             total += v
         return total / n
 
+    def _val_steps(self, default: int) -> int:
+        return default if self.val_steps is None else self.val_steps
+
     @torch.no_grad()
     def validate(self) -> float:
-        """`evaluate(model, val_loader, num_inference_steps=config.num_inference_steps, seed=config.seed)` on the EMA weights
+        """`evaluate(model, val_loader, num_inference_steps=config.num_inference_steps, seed=config.seed)` (with `val_sampler` and
+        `val_steps` where the constructor got them) on the EMA weights
         when EMA is on: returns its "loss" (the reference's validation loss, trainer.py:340-363, with seeded draws: the same
         weights always give the same loss) and keeps the whole result in `last_validation` (PSNR / SSIM for the epoch's log line).
         Parameters, optimiser state and the model's train() / eval() mode are as before afterwards."""
@@ -384,8 +402,8 @@ class LowLightTrainer:
             raise ValueError("validate needs a val_loader")
         mode = self.model.training
         try:
-            res = evaluate(self.model, self.val_loader, num_inference_steps=self.config.num_inference_steps, seed=self.config.seed,
-                           weights=self._ema_weights())
+            res = evaluate(self.model, self.val_loader, num_inference_steps=self._val_steps(self.config.num_inference_steps),
+                           seed=self.config.seed, weights=self._ema_weights(), sampler=self.val_sampler)
         finally:
             self.model.train(mode)
         self.last_validation = res
@@ -398,7 +416,8 @@ class LowLightTrainer:
         low-light, enhanced, normal-light).
 
         Draws: g = torch.Generator(device=dev).manual_seed((seed * 1000003 + epoch * 8191 + 65432) % (2 ** 63 - 1));
-        noise = torch.randn(steps, n, 3, S, S, generator=g, device=dev) with steps the scheduler's step count for 4.
+        noise = torch.randn(steps, n, 3, S, S, generator=g, device=dev) with steps the scheduler's step count for 4
+        (`val_steps` replaces the 4; with val_sampler="ddim" steps = 1, the initial latents, and the loop is DDIM's).
         The loader's epoch counter, the parameters and the model's mode are as before afterwards."""
         cfg, dev = self.config, self.device
         loader = self.val_loader or self.train_loader
@@ -412,10 +431,10 @@ class LowLightTrainer:
         mode = self.model.training
         try:
             with _swapped_weights(self.model, self._ema_weights()):
-                nsteps, steps = _steps_of(self.model, SAMPLE_STEPS, dev)
+                nsteps, steps = _steps_of(self.model, self._val_steps(SAMPLE_STEPS), dev, self.val_sampler)
                 g = torch.Generator(device=dev).manual_seed(sample_draw_seed(cfg.seed, epoch))
                 noise = torch.randn(steps, low.shape[0], 3, low.shape[2], low.shape[3], generator=g, device=dev)
-                enhanced = self.model.enhance(low, nsteps, noise=noise)
+                enhanced = self.model.enhance(low, nsteps, noise=noise, sampler=self.val_sampler)
                 grid = comparison_grid(low, enhanced, normal).cpu().numpy()  # the one device-to-host copy
         finally:
             self.model.train(mode)
@@ -469,9 +488,10 @@ class LowLightTrainer:
 
 
 def train_model(train_data_dir: str, val_data_dir: Optional[str] = None, config: Optional[TrainingConfig] = None,
-                device="cuda", *, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0) -> LowLightTrainer:
+                device="cuda", *, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0, val_sampler: str = "lcm",
+                val_steps: Optional[int] = None) -> LowLightTrainer:
     """Training entry point (trainer.py:459-496): loaders from the folders (create_device_dataloaders), a fresh model, a trainer,
-    `train()`; returns the trainer.  `x0_ssim_weight` / `x0_l1_weight`: as LowLightTrainer's."""
+    `train()`; returns the trainer.  `x0_ssim_weight` / `x0_l1_weight` / `val_sampler` / `val_steps`: as LowLightTrainer's."""
     config = config or TrainingConfig()
     train_loader, val_loader = create_device_dataloaders(train_root=train_data_dir, val_root=val_data_dir, batch_size=config.batch_size,
                                                          image_size=config.image_size, use_synthetic=config.use_synthetic,
@@ -479,6 +499,6 @@ def train_model(train_data_dir: str, val_data_dir: Optional[str] = None, config:
     model = LowLightDiffusion(unet_variant=config.unet_variant, image_size=config.image_size,
                               num_inference_steps=config.num_inference_steps).to(train_loader.store.device)
     trainer = LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config,
-                              x0_ssim_weight=x0_ssim_weight, x0_l1_weight=x0_l1_weight)
+                              x0_ssim_weight=x0_ssim_weight, x0_l1_weight=x0_l1_weight, val_sampler=val_sampler, val_steps=val_steps)
     trainer.train()
     return trainer

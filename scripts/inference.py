@@ -2,7 +2,8 @@
 """Image / folder enhancement CLI on the MI355X engine -- flag-compatible counterpart of the reference's
 scripts/inference.py (:30-62): --input --output --checkpoint --model --format --variant --image_size
 --num_steps --device.  Only --format pytorch exists here (ONNX / TFLite are the reference's mobile
-deployment targets, out of scope); extensions: --dtype {fp32,fp16,bf16}, --noise_seed, and --tile [--tile_overlap N]
+deployment targets, out of scope); extensions: --dtype {fp32,fp16,bf16}, --noise_seed, --sampler {lcm,ddim} (ddim: the
+deterministic sampler of a many-step model, --num_steps anything in 1..1000), and --tile [--tile_overlap N]
 [--tile_batch N] [--tile_sync {none,latents}], which enhances the image at its own resolution as overlapping image_size tiles
 instead of resizing it (--tile_sync latents: the tiles share one latent canvas, fused after every step), and
 --native, which enhances it at its own resolution by one run of the network at that size (frame mode; images under the engine's
@@ -39,6 +40,10 @@ def parse_args(argv=None):
     p.add_argument("--noise_seed", type=int, default=None,
                    help="(extension) draw the loop's noise on the CPU generator with this seed, in the reference's order, "
                         "instead of on the device: makes a run reproducible against the CPU reference")
+    p.add_argument("--sampler", type=str, default="lcm", choices=["lcm", "ddim"],
+                   help="(extension) lcm = the consistency student's loop (re-noise after every step); ddim = the deterministic "
+                        "DDIM loop of a many-step epsilon- / v-prediction model: --num_steps may be anything in 1..1000 and "
+                        "the initial latents are the only noise")
     p.add_argument("--tile", action="store_true",
                    help="(extension) no resize: enhance the image at its own resolution as overlapping image_size tiles, blended "
                         "on the device; --noise_seed then seeds the per-image noise canvas")
@@ -68,15 +73,20 @@ def load_model(args):
     return model.to(args.device).eval()
 
 
+def noise_entries(args) -> int:
+    """Entries of the noise --noise_seed draws: one per step for the LCM loop, the initial latents alone for DDIM."""
+    return 1 if args.sampler == "ddim" else args.num_steps
+
+
 def enhance_tiled_image(args, model, rgb):
     """--tile: uint8 [H,W,3] -> uint8 [H,W,3] at the input's resolution."""
     noise = None
     if args.noise_seed is not None:  # the canvas every tile reads its noise from, drawn entry by entry in enhance's order
         g = torch.Generator().manual_seed(args.noise_seed)
         hc, wc = max(rgb.shape[0], args.image_size), max(rgb.shape[1], args.image_size)
-        noise = torch.stack([torch.randn(3, hc, wc, generator=g) for _ in range(args.num_steps)])
+        noise = torch.stack([torch.randn(3, hc, wc, generator=g) for _ in range(noise_entries(args))])
     out = tiling.enhance_tiled(model, torch.from_numpy(rgb).to(args.device), args.num_steps, overlap=args.tile_overlap,
-                               tile_batch=args.tile_batch, noise=noise, sync=args.tile_sync)
+                               tile_batch=args.tile_batch, noise=noise, sync=args.tile_sync, sampler=args.sampler)
     return out.cpu().numpy()
 
 
@@ -86,8 +96,9 @@ def enhance_native_image(args, model, rgb):
     if args.noise_seed is not None:  # the canvas at the padded size, drawn entry by entry in enhance's order
         g = torch.Generator().manual_seed(args.noise_seed)
         hp, wp = tiling.frame_pad(rgb.shape[0]), tiling.frame_pad(rgb.shape[1])
-        noise = torch.stack([torch.randn(3, hp, wp, generator=g) for _ in range(args.num_steps)])
-    return tiling.enhance_frame_u8(model, torch.from_numpy(rgb).to(args.device), args.num_steps, noise=noise).cpu().numpy()
+        noise = torch.stack([torch.randn(3, hp, wp, generator=g) for _ in range(noise_entries(args))])
+    out = tiling.enhance_frame_u8(model, torch.from_numpy(rgb).to(args.device), args.num_steps, noise=noise, sampler=args.sampler)
+    return out.cpu().numpy()
 
 
 def enhance_resized_image(args, model, rgb):
@@ -100,8 +111,8 @@ def enhance_resized_image(args, model, rgb):
         noise = None
         if args.noise_seed is not None:  # reference draw order: initial latents, then one draw per non-final step
             g = torch.Generator().manual_seed(args.noise_seed)
-            noise = torch.stack([torch.randn(1, 3, args.image_size, args.image_size, generator=g) for _ in range(args.num_steps)])
-        enhanced = model.enhance(x, num_inference_steps=args.num_steps, noise=noise)
+            noise = torch.stack([torch.randn(1, 3, args.image_size, args.image_size, generator=g) for _ in range(noise_entries(args))])
+        enhanced = model.enhance(x, num_inference_steps=args.num_steps, noise=noise, sampler=args.sampler)
         return hostio.postprocess_device(enhanced, original)[0].cpu().numpy()
 
 

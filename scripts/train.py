@@ -65,6 +65,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--x0_ssim_weight", type=float, default=0.0,
                    help="weight of 1 - SSIM of the predicted clean image against the normal-light image, added to --loss")
     p.add_argument("--x0_l1_weight", type=float, default=0.0, help="weight of the L1 distance of the same two images")
+    p.add_argument("--sampler", type=str, default="lcm", choices=["lcm", "ddim"],
+                   help="how validation and the sample sheet sample: lcm = the consistency student's loop; ddim = the deterministic "
+                        "DDIM loop a many-step (teacher) model wants, with --num_steps steps (anything in 1..1000) in both")
     return p
 
 
@@ -87,6 +90,12 @@ def x0_weights_from_args(args) -> dict:
     """The keywords LowLightTrainer and train_model take beside the config (not TrainingConfig fields, not in checkpoints:
     a run resumed with --resume passes the same two flags again)."""
     return {"x0_ssim_weight": args.x0_ssim_weight, "x0_l1_weight": args.x0_l1_weight}
+
+
+def sampler_from_args(args) -> dict:
+    """LowLightTrainer's sampling keywords (like the x0 weights: not TrainingConfig fields, not in checkpoints).  The LCM default
+    keeps the trainer's own step counts; --sampler ddim runs --num_steps DDIM steps in validation and in the sample sheet."""
+    return {"val_sampler": args.sampler, "val_steps": args.num_steps if args.sampler == "ddim" else None}
 
 
 def main(argv=None) -> int:
@@ -112,7 +121,7 @@ def main(argv=None) -> int:
     print(f"  Parameters: {size['num_params']:,}")
 
     trainer = M.LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config,
-                                **x0_weights_from_args(args))
+                                **x0_weights_from_args(args), **sampler_from_args(args))
     print(f"  Engine precision: {model.compute_dtype}, loss scaler: {trainer.scaler is not None}, EMA: {config.use_ema}")
     trainer.train(on_epoch=lambda log: print(json.dumps(log), flush=True))
     print("\nTraining complete!")
