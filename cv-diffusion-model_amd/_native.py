@@ -49,6 +49,7 @@ EXPORTS = [
     "llie_frame_shape_ok", "llie_frame_workspace_bytes", "llie_unet_forward_hw", "llie_enhance_hw",
     "llie_frame_pad", "llie_frame_load_u8", "llie_frame_store_u8",
     "llie_ssim_grad_scratch_bytes", "llie_ssim_grad_f32", "llie_x0_loss",
+    "llie_train_shape_ok", "llie_unet_train_forward_hw", "llie_aug_pair_u8_hw", "llie_aug_synth_u8_hw",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 PW_SIGMOID_BWD, PW_RELU6_BWD, PW_SILU_BWD, PW_SCALE = 0, 1, 2, 3  # llie_pointwise_kind
@@ -199,6 +200,8 @@ def lib() -> C.CDLL:
     L.llie_frame_store_u8.argtypes = [vp, ci, ci, vp, vp]
     L.llie_aug_pair_u8.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp]
     L.llie_aug_synth_u8.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+    L.llie_aug_pair_u8_hw.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp]
+    L.llie_aug_synth_u8_hw.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]
     L.llie_image_metrics_scratch_bytes.argtypes = [ci, ci, ci]
     L.llie_image_metrics_scratch_bytes.restype = i64
     L.llie_image_metrics_f32.argtypes = [vp, vp, ci, ci, ci, C.c_float, C.c_float, vp, vp, i64, vp]
@@ -278,6 +281,8 @@ def lib() -> C.CDLL:
     L.llie_train_workspace_bytes.argtypes = [vp, ci, ci, ci]
     L.llie_train_workspace_bytes.restype = i64
     L.llie_unet_train_forward.argtypes = [vp, vp, vp, vp, vp, ci, vp, i64, vp]
+    L.llie_unet_train_forward_hw.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, vp, i64, vp]
+    L.llie_train_shape_ok.argtypes = [vp, ci, ci, ci]
     L.llie_unet_backward.argtypes = [vp, vp, vp, ci, vp, i64, vp]
     L.llie_module_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, i64, vp]
     L.llie_wgrad.argtypes = [ci, vp, ci, C.POINTER(GemmSeg), ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, i64, vp, i64, i64, i64, ci, vp]
@@ -402,6 +407,21 @@ class Handle:
             check(int(n), "llie_train_workspace_bytes")
         return int(n)
 
+    def train_plan(self, batch: int, h: int, w: int) -> int:
+        """Workspace bytes of a UNet training step on [batch,3,h,w]: ValueError naming the rule for a shape llie_train_shape_ok
+        refuses; image_size itself goes unasked, as it always did."""
+        s = int(self.cfg.image_size)
+        return self.train_workspace_bytes(batch) if (h, w) == (s, s) else self.train_workspace_bytes(batch, h, w)
+
+    def unet_train_forward(self, lat: int, cond: int, t: int, eps: int, batch: int, h: int, w: int, ws: int, nbytes: int, stream: int) -> None:
+        """llie_unet_train_forward at image_size, llie_unet_train_forward_hw elsewhere (one implementation; device pointers)."""
+        s = int(self.cfg.image_size)
+        if (h, w) == (s, s):
+            rc = self._L.llie_unet_train_forward(self.h, lat, cond, t, eps, batch, ws, nbytes, stream)
+        else:
+            rc = self._L.llie_unet_train_forward_hw(self.h, lat, cond, t, eps, batch, h, w, ws, nbytes, stream)
+        check(rc, "EfficientUNet.forward (training)")
+
     def grad_numel(self) -> int:
         return int(self._L.llie_grad_numel(self.h))
 
@@ -417,6 +437,10 @@ class Handle:
     def frame_shape_ok(self, batch: int, h: int, w: int) -> None:
         """Raises ValueError naming the rule of llie_frame_shape_ok that (batch, h, w) breaks."""
         check(self._L.llie_frame_shape_ok(self.h, batch, h, w), "frame shape")
+
+    def train_shape_ok(self, batch: int, h: int, w: int) -> None:
+        """Raises ValueError naming the rule of llie_train_shape_ok that (batch, h, w) breaks."""
+        check(self._L.llie_train_shape_ok(self.h, batch, h, w), "training frame shape")
 
     def frame_workspace_bytes(self, batch: int, h: int, w: int, max_steps: int = 0) -> int:
         n = self._L.llie_frame_workspace_bytes(self.h, batch, h, w, max_steps)

@@ -80,8 +80,8 @@ struct Back : Exec {
   void wgrad(size_t g, int N, const GemmSeg* segs, int nseg, int K, Geo geo, float* out, int64_t ldn, int64_t ldk, int64_t off,
              int ntap = 1, int nstore = 0, int kstore = 0) {
     const int M = wgrad_rows(B, geo.Ho * geo.Wo);  // ragged maps: padded per image to whole 64-row chunks
-    // image sizes off the multiples of 64 split their rows freely (every level); the launch decisions at multiples of 64 stay
-    const bool off64 = c->cfg.kind == LLIE_UNET && c->cfg.image_size % 64;
+    // frames off the multiples of 64 in either axis split their rows freely (every level); the launch decisions at multiples of 64 stay
+    const bool off64 = c->cfg.kind == LLIE_UNET && (tp->H % 64 || tp->W % 64);
     const int ms = off64 ? wgrad_msplit_ragged(dt, M, N, K, ntap) : wgrad_msplit(dt, M, N, K, ntap);
     const size_t part = alloc((size_t)ms * ntap * N * K * 4);
     if (!dry) {
@@ -361,7 +361,7 @@ struct Back : Exec {
   // ---- whole UNet
   void unet(const float* deps) {
     const llie_config& g = c->cfg;
-    const int S = g.image_size, C0 = c->channels[0], P = S * S, M = B * P, T = g.time_embed_dim, F = c->film_rows;
+    const int H = tp->H, W = tp->W, C0 = c->channels[0], P = H * W, M = B * P, T = g.time_embed_dim, F = c->film_rows;
     const size_t dfilm = alloc((size_t)B * F * 4);
     // output head
     const size_t da = alloc((size_t)M * C0 * es());
@@ -375,7 +375,7 @@ struct Back : Exec {
       if (!dry) {
         FinalBwdArgs a{};
         a.deps = deps; a.w = wptr<float>(c->fin_w); a.da = p(da);
-        a.B = B; a.H = S; a.W = S; a.C = C0; a.Cout = g.out_channels;
+        a.B = B; a.H = H; a.W = W; a.C = C0; a.Cout = g.out_channels;
         chk(launch_final_bwd_data(dt, a, s));
         fork();
         chk(launch_pack_planes(dt, deps, nullptr, g.out_channels, 0, p(g32), B, P, side()));
@@ -383,7 +383,7 @@ struct Back : Exec {
       }
       defer(bslab); defer(bS);
       GemmSeg sg{p(tp->hlast.off), C0, p<float>(tp->fin.as), p<float>(tp->fin.ab), C0, ACT_SILU};
-      const Geo geo{S, S, S, S, 1, 0, 0};
+      const Geo geo{H, W, H, W, 1, 0, 0};
       wgrad(g32, 32, &sg, 1, C0, geo, gp(c->i_fin_w), (int64_t)C0 * 9, 9, 0, 9, g.out_channels, 0);
       defer(g32);  // released at the first operator's join
     }
@@ -405,7 +405,7 @@ struct Back : Exec {
         bias_grad(g0, M, C0, P, slab, S1, gp(c->i_init_b), c->channels_r[0], s);
       }
       GemmSeg sg{p(x32), 32, nullptr, nullptr, 0, ACT_NONE};
-      const Geo geo{S, S, S, S, 1, 0, 0};
+      const Geo geo{H, W, H, W, 1, 0, 0};
       fork();
       wgrad(g0, C0, &sg, 1, 32, geo, gp(c->i_init_w), (int64_t)g.in_channels * 9, 9, 0, 9, c->channels_r[0], g.in_channels);
       ar->free(slab); ar->free(S1);
@@ -474,7 +474,29 @@ static int setup_async(llie_ctx* c, Back& b) {
   return LLIE_OK;
 }
 
+// The frames a UNet handle trains at: the frame rule of the forward, tightened by what only the backward pass stores.  Every
+// gradient has the shape of its forward tensor, the zero-dilated gradient of a stride-2 conv has the shape of that conv's input and
+// the tape's up-sampled tensor at full resolution carries channels[1]; the packed [M][32] operands of the head and the input conv
+// carry 32.  The weight-gradient GEMM walks wgrad_rows(B, P) rows -- each image padded to whole 64-row chunks -- and forms
+// row * channels in 32 bits, so the cap is taken over the padded rows.  Lower levels hold a quarter of the pixels at twice the
+// channels per step down, and at least 64 pixels each (H, W >= 64), so padding at most doubles them: full resolution is the bound.
+static int train_shape_ok(const llie_ctx* c, int batch, int H, int W) {
+  if (!c || c->cfg.kind != LLIE_UNET || batch <= 0) return LLIE_ERR_ARG;
+  if (c->padded) { set_err("the unpinned variants (tiny / base, zero-padded channels) are inference-only"); return LLIE_ERR_CONFIG; }
+  const int rc = frame_shape_ok(c, batch, H, W);
+  if (rc) return rc;
+  const int cw = std::max({widest_full_res_channels(c), c->channels[1], 32});
+  const long long rows = (long long)batch * (((long long)H * W + 63) / 64 * 64);
+  if (rows * cw > 2147483647ll) {
+    set_err("training frame too large: batch %d x %dx%d (rows padded to 64 per image) x %d channels exceeds the element cap 2^31 - 1",
+            batch, H, W, cw);
+    return LLIE_ERR_SHAPE;
+  }
+  return LLIE_OK;
+}
+
 // what the training entry points check before they touch the device: loaded weights and a workspace that holds the plan
+// (a UNet handle: H = W = 0 is image_size)
 static int train_ready(llie_ctx* c, int batch, int H, int W, int64_t ws_bytes) {
   int rc = check_ready(c);
   if (rc) return rc;
@@ -502,7 +524,10 @@ int64_t llie_train_workspace_bytes(llie_ctx* c, int batch, int height, int width
   Back b{x, &tape, nullptr};
   setup_async(c, b);
   if (c->cfg.kind == LLIE_UNET) {
-    run_unet(x, &tape, nullptr, nullptr, nullptr, nullptr);
+    if ((height == 0) != (width == 0) || height < 0 || width < 0) return LLIE_ERR_ARG;
+    if (height == 0) height = width = c->cfg.image_size;  // unchecked, as the entry points at image_size always were
+    else if (const int rc = train_shape_ok(c, batch, height, width)) return rc;
+    run_unet(x, &tape, nullptr, nullptr, nullptr, nullptr, height, width);
     b.unet(nullptr);
   } else {
     if (shape_ok(c, height, width) != LLIE_OK) return LLIE_ERR_SHAPE;
@@ -513,20 +538,35 @@ int64_t llie_train_workspace_bytes(llie_ctx* c, int batch, int height, int width
   return (int64_t)ar.high;
 }
 
-int llie_unet_train_forward(llie_ctx* c, const float* lat, const float* cond, const int64_t* t, float* eps, int batch,
-                            void* ws, int64_t ws_bytes, llie_stream stream) {
+int llie_train_shape_ok(const llie_ctx* c, int batch, int height, int width) { return train_shape_ok(c, batch, height, width); }
+
+// llie_unet_train_forward (H = W = 0: image_size, unchecked as always) and llie_unet_train_forward_hw
+static int train_forward_impl(llie_ctx* c, const float* lat, const float* cond, const int64_t* t, float* eps, int batch, int H, int W,
+                              void* ws, int64_t ws_bytes, llie_stream stream) {
   if (!c || !lat || !cond || !t || !eps || !ws || batch <= 0 || c->cfg.kind != LLIE_UNET) return LLIE_ERR_ARG;
   if (c->padded) { set_err("the unpinned variants (tiny / base, zero-padded channels) are inference-only"); return LLIE_ERR_CONFIG; }
-  int rc = train_ready(c, batch, 0, 0, ws_bytes);
+  int rc = train_ready(c, batch, H, W, ws_bytes);
   if (rc) return rc;
+  if (!H) H = W = c->cfg.image_size;
   delete c->train_arena;
   c->train_arena = new Arena((size_t)ws_bytes);
   c->tape.clear();
-  rc = run_unet(Exec::live(c, c->train_arena, stream, ws, batch), &c->tape, lat, cond, t, eps);
+  rc = run_unet(Exec::live(c, c->train_arena, stream, ws, batch), &c->tape, lat, cond, t, eps, H, W);
   if (rc) return rc;
   c->tape.valid = true;
   c->tape.ws = ws;
   return LLIE_OK;
+}
+
+int llie_unet_train_forward(llie_ctx* c, const float* lat, const float* cond, const int64_t* t, float* eps, int batch,
+                            void* ws, int64_t ws_bytes, llie_stream stream) {
+  return train_forward_impl(c, lat, cond, t, eps, batch, 0, 0, ws, ws_bytes, stream);
+}
+
+int llie_unet_train_forward_hw(llie_ctx* c, const float* lat, const float* cond, const int64_t* t, float* eps, int batch,
+                               int height, int width, void* ws, int64_t ws_bytes, llie_stream stream) {
+  if (height <= 0 || width <= 0) return LLIE_ERR_ARG;
+  return train_forward_impl(c, lat, cond, t, eps, batch, height, width, ws, ws_bytes, stream);
 }
 
 int llie_unet_backward(llie_ctx* c, const float* d_eps, float* grads, int batch, void* ws, int64_t ws_bytes, llie_stream stream) {

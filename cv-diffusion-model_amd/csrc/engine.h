@@ -178,6 +178,7 @@ struct Tape {
   GnRec fin;
   const float* lat = nullptr; const float* cond = nullptr; const int64_t* t = nullptr;
   int B = 0;
+  int H = 0, W = 0;  // the frame of a UNet training forward: the backward pass takes its shape from here (0 for a single operator)
   const void* ws = nullptr;
   bool valid = false;
   void clear() { irbs.clear(); attns.clear(); convs.clear(); ops.clear(); valid = false; }
@@ -356,7 +357,7 @@ int shape_ok(const llie_ctx* c, int H, int W);  // model.cpp
 // capacity check before the first launch, so that no kernel ever sees an offset past the workspace
 int fits(size_t need, int64_t ws_bytes);  // model.cpp
 // forward.cpp: the forward pass of `x`; tape != null: training forward -- nothing is released, every operator is recorded
-int run_unet(Exec x, Tape* tape, const float* lat, const float* cond, const int64_t* t, float* eps);
+int run_unet(Exec x, Tape* tape, const float* lat, const float* cond, const int64_t* t, float* eps, int H, int W);
 int run_module(Exec x, Tape* tape, const float* in, const float* temb, float* y, int H, int W);
 // scheduler step fused into the final conv's epilogue (2-byte compute dtypes only)
 struct FusedStep { StepCoef coef; const float* noise; float* prev; float* clamped; };
@@ -370,6 +371,7 @@ int unet_forward_impl(llie_ctx* c, const float* lat, const float* cond, const in
 // forward.cpp: the frame rule of llie_frame_shape_ok, and the workspace of `max_steps` steps of the loop at H x W without that
 // check (0: plain launches, no staging area) -- the entry points at image_size go through it unchecked, as they always did
 int frame_shape_ok(const llie_ctx* c, int batch, int H, int W);
+int widest_full_res_channels(const llie_ctx* c);  // what the element cap of frame_shape_ok multiplies
 int64_t frame_workspace(llie_ctx* c, int batch, int H, int W, int max_steps);
 // HIP status of a kernel-level entry point -> return code and llie_last_error() text.  hipErrorInvalidValue is how a launcher
 // refuses its arguments: `refuse_rc` with "<what>: <refuse_msg>" (no text when refuse_msg is null)

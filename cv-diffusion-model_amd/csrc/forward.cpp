@@ -450,7 +450,7 @@ struct Run : Exec {
     }
     if (tape) {
       tape->temb = temb; tape->stemb = stemb; tape->film = film; tape->h0 = h;
-      tape->lat = lat; tape->cond = cond; tape->t = t; tape->B = B;
+      tape->lat = lat; tape->cond = cond; tape->t = t; tape->B = B; tape->H = H; tape->W = W;
     }
     Tens skips[4];
     for (int l = 0; l < 4; ++l) {
@@ -553,10 +553,10 @@ struct Run : Exec {
 
 }  // namespace
 
-int llie::run_unet(Exec x, Tape* tape, const float* lat, const float* cond, const int64_t* t, float* eps) {
+int llie::run_unet(Exec x, Tape* tape, const float* lat, const float* cond, const int64_t* t, float* eps, int H, int W) {
   Run r{x};
   r.tape = tape;
-  r.unet(lat, cond, t, 0, eps, x.c->cfg.image_size, x.c->cfg.image_size);
+  r.unet(lat, cond, t, 0, eps, H, W);
   return r.rc();
 }
 int llie::run_module(Exec x, Tape* tape, const float* in, const float* temb, float* y, int H, int W) {
@@ -580,7 +580,7 @@ int llie::unet_forward_impl(llie_ctx* c, const float* lat, const float* cond, co
 }
 
 // The widest tensor one forward stores at full resolution, in channels: what the element cap of frame_shape_ok multiplies
-static int widest_full_res_channels(const llie_ctx* c) {
+int llie::widest_full_res_channels(const llie_ctx* c) {
   int m = std::max(c->channels[0], c->cfg.in_channels);
   for (const std::vector<Block>* blocks : {&c->enc[0], &c->dec[3]})
     for (const Block& b : *blocks) {

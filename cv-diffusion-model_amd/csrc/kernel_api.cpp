@@ -520,22 +520,31 @@ int llie_frame_store_u8(const float* x, int H, int W, uint8_t* img, llie_stream 
 }
 
 static_assert(sizeof(llie_aug_row) == sizeof(AugRow) && sizeof(AugRow) == 48, "llie_aug_row and AugRow are one layout");
-static AugArgs aug_args(const uint8_t* pool, const int64_t* table, int N, const llie_aug_row* plan, int first, int count, int S, const float* z,
-                        float* low, float* high, uint8_t* low_u8, uint8_t* high_u8) {
+static AugArgs aug_args(const uint8_t* pool, const int64_t* table, int N, const llie_aug_row* plan, int first, int count, int SH, int SW,
+                        const float* z, float* low, float* high, uint8_t* low_u8, uint8_t* high_u8) {
   AugArgs a{};
-  a.pool = pool; a.table = table; a.N = N; a.plan = reinterpret_cast<const AugRow*>(plan); a.first = first; a.count = count; a.S = S;
+  a.pool = pool; a.table = table; a.N = N; a.plan = reinterpret_cast<const AugRow*>(plan); a.first = first; a.count = count;
+  a.SH = SH; a.SW = SW;
   a.z = z; a.low = low; a.high = high; a.low_u8 = low_u8; a.high_u8 = high_u8;
   return a;
 }
+int llie_aug_pair_u8_hw(const uint8_t* pool, const int64_t* table, int N, const llie_aug_row* plan, int first, int count, int SH, int SW,
+                        float* low, float* high, uint8_t* low_u8, uint8_t* high_u8, llie_stream stream) {
+  return kerr("aug_pair_u8", launch_aug_pair_u8(aug_args(pool, table, N, plan, first, count, SH, SW, nullptr, low, high, low_u8, high_u8), hs(stream)),
+              LLIE_ERR_ARG, nullptr);
+}
+int llie_aug_synth_u8_hw(const uint8_t* pool, const int64_t* table, int N, const llie_aug_row* plan, int first, int count, int SH, int SW,
+                         const float* z, float* low, float* high, uint8_t* low_u8, uint8_t* high_u8, llie_stream stream) {
+  return kerr("aug_synth_u8", launch_aug_synth_u8(aug_args(pool, table, N, plan, first, count, SH, SW, z, low, high, low_u8, high_u8), hs(stream)),
+              LLIE_ERR_ARG, nullptr);
+}
 int llie_aug_pair_u8(const uint8_t* pool, const int64_t* table, int N, const llie_aug_row* plan, int first, int count, int S,
                      float* low, float* high, uint8_t* low_u8, uint8_t* high_u8, llie_stream stream) {
-  return kerr("aug_pair_u8", launch_aug_pair_u8(aug_args(pool, table, N, plan, first, count, S, nullptr, low, high, low_u8, high_u8), hs(stream)),
-              LLIE_ERR_ARG, nullptr);
+  return llie_aug_pair_u8_hw(pool, table, N, plan, first, count, S, S, low, high, low_u8, high_u8, stream);
 }
 int llie_aug_synth_u8(const uint8_t* pool, const int64_t* table, int N, const llie_aug_row* plan, int first, int count, int S,
                       const float* z, float* low, float* high, uint8_t* low_u8, uint8_t* high_u8, llie_stream stream) {
-  return kerr("aug_synth_u8", launch_aug_synth_u8(aug_args(pool, table, N, plan, first, count, S, z, low, high, low_u8, high_u8), hs(stream)),
-              LLIE_ERR_ARG, nullptr);
+  return llie_aug_synth_u8_hw(pool, table, N, plan, first, count, S, S, z, low, high, low_u8, high_u8, stream);
 }
 
 // ---- image quality (metrics.hip): every contract check runs here, before any HIP call

@@ -615,12 +615,12 @@ struct AugRow {
 struct AugArgs {
   const uint8_t* pool; const int64_t* table; int N;
   const AugRow* plan; int first, count;
-  int S;                      // crop side; every frame must be at least S x S
-  const float* z;             // aug_synth_u8 only: standard-normal noise fp32 [count][S][S][3]
-  float* low; float* high;    // fp32 [count][3][S][S] in [-1, 1]
-  uint8_t* low_u8; uint8_t* high_u8;  // optional uint8 [count][S][S][3]: the bytes before normalisation
+  int SH, SW;                 // crop height and width; every frame must be at least SH x SW
+  const float* z;             // aug_synth_u8 only: standard-normal noise fp32 [count][SH][SW][3]
+  float* low; float* high;    // fp32 [count][3][SH][SW] in [-1, 1]
+  uint8_t* low_u8; uint8_t* high_u8;  // optional uint8 [count][SH][SW][3]: the bytes before normalisation
 };
-// null pointers (other than the optional two), N < 1, S < 1, first < 0 or count < 0: hipErrorInvalidValue; count == 0 launches nothing
+// null pointers (other than the optional two), N < 1, SH < 1, SW < 1, first < 0 or count < 0: hipErrorInvalidValue; count == 0 launches nothing
 hipError_t launch_aug_pair_u8(const AugArgs& a, hipStream_t s);
 hipError_t launch_aug_synth_u8(const AugArgs& a, hipStream_t s);
 

@@ -355,6 +355,9 @@ def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[i
       ["noise_pred"], eps) without gradients.
       sampler="ddim" scores `model.enhance(..., sampler="ddim")`, the deterministic sampler of a many-step model, at any
       `num_inference_steps` in 1..T: steps = 1 in the recipe above (the initial latents are the only noise), the rest is unchanged.
+      A rectangular loader (`crop_size` = (H, W), H != W; frame-size training) is scored through `model.enhance_frame` and the
+      loss runs at that shape: the same recipe with every [.., 3, S, S] draw [.., 3, H, W].  A square loader must crop
+      model.image_size, as before.
 
     Returns {"n", "psnr", "ssim", "mse", ["loss",] "per_image": {"filename", "psnr", "ssim", "mse"}}: psnr / ssim / mse are the
     means over images of the per-image values (float64 sums in file order), loss = sum of batch losses / len(loader).  Everything
@@ -368,8 +371,11 @@ def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[i
         raise RuntimeError(f"evaluate runs only on a HIP device (the frame store is on '{dev}'); there is no CPU fallback")
     with _swapped_weights(model, weights):
         s = int(model.image_size)
-        if loader.image_size != s:
-            raise ValueError(f"the loader crops {loader.image_size} x {loader.image_size}, the model takes {s} x {s}")
+        hh, ww = loader.crop_size
+        frame = hh != ww
+        if not frame and hh != s:
+            raise ValueError(f"the loader crops {hh} x {ww}, the model takes {s} x {s}")
+        enhance = model.enhance_frame if frame else model.enhance
         nsteps, steps = _steps_of(model, num_inference_steps, dev, sampler)
         t_max = int(model.scheduler.config.num_train_timesteps)
         g = torch.Generator(device=dev).manual_seed(int(seed))
@@ -377,13 +383,13 @@ def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[i
         for batch in loader:
             low, normal = batch["low_light"], batch["normal_light"]
             b = low.shape[0]
-            noise = torch.randn(steps, b, 3, s, s, generator=g, device=dev)
+            noise = torch.randn(steps, b, 3, hh, ww, generator=g, device=dev)
             if loss:
                 t = torch.randint(0, t_max, (b,), generator=g, device=dev)
-                eps = torch.randn(b, 3, s, s, generator=g, device=dev)
-            triples.append(_metrics_out3(model.enhance(low, nsteps, noise=noise, sampler=sampler), normal, (-1.0, 1.0)))
+                eps = torch.randn(b, 3, hh, ww, generator=g, device=dev)
+            triples.append(_metrics_out3(enhance(low, nsteps, noise=noise, sampler=sampler), normal, (-1.0, 1.0)))
             if loss:
-                pred = model.forward(low, normal, timesteps=t, noise=eps)["noise_pred"]
+                pred = model.forward(low, normal, timesteps=t, noise=eps, frame=frame)["noise_pred"]
                 losses.append(F.mse_loss(pred, eps).double().reshape(1))
             names += list(batch["filename"])
         if not triples:

@@ -96,7 +96,7 @@ class LowLightDiffusion(nn.Module):
     # ------------------------------------------------------------------ training-side forward (:115-175)
     def forward(self, low_light: torch.Tensor, normal_light: Optional[torch.Tensor] = None,
                 timesteps: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
-                return_dict: bool = True) -> Union[torch.Tensor, Dict[str, torch.Tensor]]:
+                return_dict: bool = True, *, frame: bool = False) -> Union[torch.Tensor, Dict[str, torch.Tensor]]:
         """With `normal_light`: q-sample -> denoiser, returning {noise_pred, noise, timesteps}.  When gradients
         are enabled `noise_pred` carries a grad_fn whose backward is the engine's reverse pass
         (llie_unet_backward): `loss.backward()` fills `.grad` of every parameter, so the reference trainer's
@@ -104,6 +104,8 @@ class LowLightDiffusion(nn.Module):
         With a `prediction_type="v_prediction"` scheduler the dict also holds the velocity `target`
         (lcm_scheduler.py:282-305; the reference never wires it into `compute_loss`).  A caller that forms the x0 term needs
         the noised input too: it is `scheduler.add_noise(normal_light, noise, timesteps)` of the returned draws.
+        `frame=True` (extension): the training branch runs at the batch's own H x W, any shape llie_train_shape_ok accepts
+        (EfficientUNet.forward_split); without it a shape other than image_size is a ValueError, as before.
         Without `normal_light`: `enhance(low_light)`."""
         if normal_light is None:
             return self.enhance(low_light)
@@ -113,7 +115,7 @@ class LowLightDiffusion(nn.Module):
         if noise is None:
             noise = torch.randn_like(normal_light)
         noisy = self.scheduler.add_noise(normal_light, noise, timesteps)
-        noise_pred = self.unet.forward_split(noisy, low_light, timesteps, uniform_t=False)
+        noise_pred = self.unet.forward_split(noisy, low_light, timesteps, uniform_t=False, frame=frame)
         if return_dict:
             out = {"noise_pred": noise_pred, "noise": noise, "timesteps": timesteps}
             if getattr(self.scheduler.config, "prediction_type", "epsilon") == "v_prediction":
@@ -260,9 +262,11 @@ class LowLightDiffusion(nn.Module):
         `prediction_type="v_prediction"` scheduler) regresses against `scheduler.get_velocity` instead -- the v-pred MSE of
         BASELINE config 5, which the reference defines (lcm_scheduler.py:282-305) but never wires into its loss.
         `x0_ssim_weight` / `x0_l1_weight` (extension): when either is non-zero, `x0_loss` of the predicted clean image against
-        `normal_light` is added (the module docstring has the definition); with both 0 nothing changes."""
+        `normal_light` is added (the module docstring has the definition); with both 0 nothing changes.
+        The loss and the x0 term run at the batch's own H x W: [B,3,H,W] of any shape llie_train_shape_ok accepts (frame-size
+        fine-tuning; image_size is one such shape and is what it was)."""
         _check_x0_weights(x0_ssim_weight, x0_l1_weight)
-        out = self.forward(low_light, normal_light)
+        out = self.forward(low_light, normal_light, frame=True)
         if use_velocity_target and "target" not in out:
             raise ValueError("use_velocity_target needs a scheduler with prediction_type='v_prediction'")
         pred, noise = out["noise_pred"], (out["target"] if use_velocity_target else out["noise"])
@@ -275,9 +279,10 @@ class LowLightDiffusion(nn.Module):
         else:
             raise ValueError(f"Unknown loss type: {loss_type}")
         if x0_ssim_weight != 0 or x0_l1_weight != 0:
+            # one node for the base loss and the term, formed as TrainStep forms them: the same loss and d(loss)/d(pred) bits
             noisy = self.scheduler.add_noise(normal_light, out["noise"], out["timesteps"])  # forward's x_t, the same bits
-            loss = loss + x0_loss(self.scheduler, pred, noisy, normal_light, out["timesteps"], velocity=use_velocity_target,
-                                  ssim_weight=x0_ssim_weight, l1_weight=x0_l1_weight)
+            loss = _LossWithX0Fn.apply(pred, noise, self.scheduler, noisy, normal_light, out["timesteps"], loss_type,
+                                       bool(use_velocity_target), float(x0_ssim_weight), float(x0_l1_weight))
         return loss
 
     def get_model_size(self) -> Dict[str, float]:
@@ -424,6 +429,42 @@ def x0_loss_device(scheduler: LCMScheduler, out: torch.Tensor, x_t: torch.Tensor
                                d_out.data_ptr() if d_out is not None else None, b, h, w, scratch.data_ptr(), nbytes,
                                torch.cuda.current_stream(dev).cuda_stream), "x0_loss")
     return loss
+
+
+def base_loss_and_grad(pred: torch.Tensor, target: torch.Tensor, loss_type: str) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(loss, d(loss)/d(pred)) of F.mse_loss / F.l1_loss / F.huber_loss(delta=1), written out: what TrainStep hands the backward
+    pass, and what compute_loss seeds the x0 term's gradient buffer with."""
+    diff = pred - target
+    n = diff.numel()
+    if loss_type == "mse":          # mean(d^2); d/d pred = 2 d / n
+        return (diff * diff).mean(), diff * (2.0 / n)
+    if loss_type == "l1":           # mean|d|; sign(d) / n
+        return diff.abs().mean(), torch.sign(diff) / n
+    if loss_type == "huber":        # 0.5 d^2 inside, |d| - 0.5 outside; clamp(d, -1, 1) / n
+        a = diff.abs()
+        return torch.where(a < 1.0, 0.5 * diff * diff, a - 0.5).mean(), diff.clamp(-1.0, 1.0) / n
+    raise ValueError(f"Unknown loss type: {loss_type}")
+
+
+class _LossWithX0Fn(torch.autograd.Function):
+    """compute_loss with the x0 term on, as one autograd node of the network output: the base loss's gradient is written first
+    and llie_x0_loss adds the term's into it -- TrainStep's order of operations, so the two routes give the same loss and the
+    same d(loss)/d(pred), bit for bit (two nodes summed by autograd round the term's product once more).  backward = that
+    buffer times grad_output (a GradScaler's scaled backward works)."""
+
+    @staticmethod
+    def forward(ctx, pred, target, scheduler, x_t, normal, timesteps, loss_type, velocity, ssim_weight, l1_weight):
+        out = pred.detach().float()
+        loss, d = base_loss_and_grad(out, target, loss_type)
+        d = d.contiguous()
+        loss = loss + x0_loss_device(scheduler, out, x_t, normal, timesteps, velocity, ssim_weight, l1_weight, d)
+        ctx.save_for_backward(d)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        d, = ctx.saved_tensors
+        return (d * grad_output,) + (None,) * 9
 
 
 class _X0LossFn(torch.autograd.Function):

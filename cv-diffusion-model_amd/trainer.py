@@ -18,7 +18,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 from pathlib import Path
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -238,12 +238,32 @@ class LowLightTrainer:
     choose how validation and the sample sheet sample: val_sampler="ddim" is the deterministic sampler a many-step (teacher)
     model wants, where the default "lcm" shows the 4-step loop of a consistency student; `val_steps` replaces
     config.num_inference_steps in `validate` and the 4 steps of `generate_samples` (None keeps both; with "ddim" anything in
-    1..num_train_timesteps).  A schedule the model does not have is a ValueError here, not at the first validation."""
+    1..num_train_timesteps).  A schedule the model does not have is a ValueError here, not at the first validation.
+
+    `crop_size=(H, W)` (extension; a keyword like the x0 weights, neither a TrainingConfig field nor stored in checkpoints: a caller
+    that resumes passes it again) trains at a frame's own shape instead of config.image_size x config.image_size: the loaders must
+    crop (H, W) (`DevicePairLoader(..., image_size=(H, W))`), `train_epoch` draws its noise at that shape, and `validate` /
+    `generate_samples` run `enhance_frame`.  The model keeps the module tree config.image_size fixed; (H, W) is any shape
+    llie_train_shape_ok accepts at the batch size (checked here)."""
 
     def __init__(self, model: LowLightDiffusion, train_loader, val_loader=None, config: Optional[TrainingConfig] = None, *,
-                 x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0, val_sampler: str = "lcm", val_steps: Optional[int] = None):
+                 x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0, val_sampler: str = "lcm", val_steps: Optional[int] = None,
+                 crop_size: Optional[Tuple[int, int]] = None):
         self.config = config or TrainingConfig()
         cfg = self.config
+        if crop_size is None:
+            self.crop_size = (int(cfg.image_size), int(cfg.image_size))
+        else:
+            if len(crop_size) != 2:
+                raise ValueError(f"crop_size is (H, W), got {crop_size!r}")
+            self.crop_size = (int(crop_size[0]), int(crop_size[1]))
+            if self.crop_size[0] == self.crop_size[1] and self.crop_size[0] != int(cfg.image_size):
+                raise ValueError(f"a square crop_size is config.image_size ({cfg.image_size}), got {self.crop_size[0]}: validation "
+                                 "of square crops runs `enhance`, which takes image_size only")
+            for what, loader in (("train_loader", train_loader), ("val_loader", val_loader)):
+                have = getattr(loader, "crop_size", None)
+                if loader is not None and have is not None and tuple(have) != self.crop_size:
+                    raise ValueError(f"{what} crops {have[0]} x {have[1]}, crop_size is {self.crop_size[0]} x {self.crop_size[1]}")
         self.val_sampler = check_sampler(val_sampler)
         if val_steps is not None and (isinstance(val_steps, bool) or int(val_steps) != val_steps or val_steps < 1):
             raise ValueError(f"val_steps must be a positive integer or None, got {val_steps!r}")
@@ -268,6 +288,8 @@ class LowLightTrainer:
 
         self.model = model
         self.model.compute_dtype = dtype
+        if crop_size is not None:  # ValueError naming the rule, here and not at the first step
+            model.unet._handle(N.dtype_code(dtype)).train_shape_ok(max(1, int(getattr(train_loader, "batch_size", 1))), *self.crop_size)
         self.train_loader = train_loader
         self.val_loader = val_loader
 
@@ -348,7 +370,8 @@ class LowLightTrainer:
         """One epoch (trainer.py:269-338) of TrainStep over the train loader.
 
         Draw recipe (part of the contract; the global generator is neither read nor advanced):
-          train_loader.set_epoch(epoch); dev = the model's device; S = config.image_size; T = scheduler.config.num_train_timesteps;
+          train_loader.set_epoch(epoch); dev = the model's device; S = config.image_size (with `crop_size=(H, W)` every
+          [b, 3, S, S] below is [b, 3, H, W]); T = scheduler.config.num_train_timesteps;
           g = torch.Generator(device=dev).manual_seed((seed * 1000003 + epoch * 8191 + 54321) % (2 ** 63 - 1))
           per batch of b pairs, in loader order, the reference's order of draws (low_light_diffusion.py: timesteps, then noise):
             t = torch.randint(0, T, (b,), generator=g, device=dev)
@@ -361,7 +384,7 @@ class LowLightTrainer:
         cfg, dev, loader = self.config, self.device, self.train_loader
         self.model.train()
         loader.set_epoch(self.epoch)
-        s, t_max = int(cfg.image_size), int(self.model.scheduler.config.num_train_timesteps)
+        (hh, ww), t_max = self.crop_size, int(self.model.scheduler.config.num_train_timesteps)
         g = torch.Generator(device=dev).manual_seed(train_draw_seed(cfg.seed, self.epoch))
         n = len(loader)
         losses = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -370,7 +393,7 @@ class LowLightTrainer:
             low, normal = batch["low_light"], batch["normal_light"]
             b = low.shape[0]
             t = torch.randint(0, t_max, (b,), generator=g, device=dev)
-            noise = torch.randn(b, 3, s, s, generator=g, device=dev)
+            noise = torch.randn(b, 3, hh, ww, generator=g, device=dev)
             loss = self.step(low, normal, timesteps=t, noise=noise)
             # TrainStep steps through step_flat, not optimizer.step(), which torch's scheduler watches to warn about a
             # schedule that moves before the optimiser: the optimiser has stepped
@@ -418,6 +441,7 @@ class LowLightTrainer:
         Draws: g = torch.Generator(device=dev).manual_seed((seed * 1000003 + epoch * 8191 + 65432) % (2 ** 63 - 1));
         noise = torch.randn(steps, n, 3, S, S, generator=g, device=dev) with steps the scheduler's step count for 4
         (`val_steps` replaces the 4; with val_sampler="ddim" steps = 1, the initial latents, and the loop is DDIM's).
+        With a rectangular `crop_size` the images are [n, 3, H, W] and the loop is `enhance_frame`'s.
         The loader's epoch counter, the parameters and the model's mode are as before afterwards."""
         cfg, dev = self.config, self.device
         loader = self.val_loader or self.train_loader
@@ -434,7 +458,8 @@ class LowLightTrainer:
                 nsteps, steps = _steps_of(self.model, self._val_steps(SAMPLE_STEPS), dev, self.val_sampler)
                 g = torch.Generator(device=dev).manual_seed(sample_draw_seed(cfg.seed, epoch))
                 noise = torch.randn(steps, low.shape[0], 3, low.shape[2], low.shape[3], generator=g, device=dev)
-                enhanced = self.model.enhance(low, nsteps, noise=noise, sampler=self.val_sampler)
+                enhance = self.model.enhance_frame if self.crop_size[0] != self.crop_size[1] else self.model.enhance
+                enhanced = enhance(low, nsteps, noise=noise, sampler=self.val_sampler)
                 grid = comparison_grid(low, enhanced, normal).cpu().numpy()  # the one device-to-host copy
         finally:
             self.model.train(mode)
@@ -489,16 +514,19 @@ class LowLightTrainer:
 
 def train_model(train_data_dir: str, val_data_dir: Optional[str] = None, config: Optional[TrainingConfig] = None,
                 device="cuda", *, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0, val_sampler: str = "lcm",
-                val_steps: Optional[int] = None) -> LowLightTrainer:
+                val_steps: Optional[int] = None, crop_size: Optional[Tuple[int, int]] = None) -> LowLightTrainer:
     """Training entry point (trainer.py:459-496): loaders from the folders (create_device_dataloaders), a fresh model, a trainer,
-    `train()`; returns the trainer.  `x0_ssim_weight` / `x0_l1_weight` / `val_sampler` / `val_steps`: as LowLightTrainer's."""
+    `train()`; returns the trainer.  `x0_ssim_weight` / `x0_l1_weight` / `val_sampler` / `val_steps` / `crop_size`: as
+    LowLightTrainer's (with `crop_size=(H, W)` the loaders crop H x W; the model is still built at config.image_size)."""
     config = config or TrainingConfig()
     train_loader, val_loader = create_device_dataloaders(train_root=train_data_dir, val_root=val_data_dir, batch_size=config.batch_size,
-                                                         image_size=config.image_size, use_synthetic=config.use_synthetic,
+                                                         image_size=config.image_size if crop_size is None else tuple(crop_size),
+                                                         use_synthetic=config.use_synthetic,
                                                          device=device, seed=config.seed)
     model = LowLightDiffusion(unet_variant=config.unet_variant, image_size=config.image_size,
                               num_inference_steps=config.num_inference_steps).to(train_loader.store.device)
     trainer = LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config,
-                              x0_ssim_weight=x0_ssim_weight, x0_l1_weight=x0_l1_weight, val_sampler=val_sampler, val_steps=val_steps)
+                              x0_ssim_weight=x0_ssim_weight, x0_l1_weight=x0_l1_weight, val_sampler=val_sampler, val_steps=val_steps,
+                              crop_size=crop_size)
     trainer.train()
     return trainer

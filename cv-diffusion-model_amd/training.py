@@ -302,10 +302,11 @@ def _engine_order(unet, optimizer: FusedAdamW, who: str) -> List[int]:
     return [index[id(p)] for p in have]
 
 
-def _train_buffers(step, h: N.Handle, batch: int, dev: torch.device) -> int:
-    """Grow `step._ws` (train workspace) and allocate `step._flat` (flat gradients) / `step._offsets` (the optimiser's order)
-    for handle `h`; returns the workspace bytes the engine needs."""
-    nbytes = h.train_workspace_bytes(batch)
+def _train_buffers(step, h: N.Handle, batch: int, dev: torch.device, height: int = 0, width: int = 0) -> int:
+    """Grow `step._ws` (train workspace; it never shrinks) and allocate `step._flat` (flat gradients) / `step._offsets` (the
+    optimiser's order) for handle `h`; returns the workspace bytes the engine needs at `height` x `width` (0, 0: image_size;
+    ValueError naming the rule when llie_train_shape_ok refuses the shape)."""
+    nbytes = h.train_plan(batch, height, width) if height else h.train_workspace_bytes(batch)
     if step._ws is None or step._ws.numel() < nbytes or step._ws.device != dev:
         step._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     if step._flat is None or step._flat.numel() != h.grad_numel() or step._flat.device != dev:
@@ -350,9 +351,12 @@ class TrainStep:
         from .unet import resolve_compute_dtype
         model, unet = self.model, self.model.unet
         b, dev = low_light.shape[0], low_light.device
-        s = unet.config.image_size
-        if tuple(low_light.shape[1:]) != (3, s, s) or tuple(normal_light.shape) != tuple(low_light.shape):
-            raise ValueError(f"low_light / normal_light must be [B,3,{s},{s}]")
+        if low_light.dim() != 4 or low_light.shape[1] != 3 or tuple(normal_light.shape) != tuple(low_light.shape):
+            raise ValueError("low_light / normal_light must be [B,3,H,W] of one shape")
+        hh, ww = int(low_light.shape[2]), int(low_light.shape[3])
+        h = unet._handle(resolve_compute_dtype(unet.compute_dtype))
+        # the batch's own H x W (llie_train_shape_ok); the workspace follows the shape and only grows, so a loop may alternate shapes
+        nbytes = _train_buffers(self, h, b, dev, hh, ww)
         if timesteps is None:
             timesteps = torch.randint(0, model.scheduler.config.num_train_timesteps, (b,), device=dev)
         if noise is None:
@@ -361,28 +365,14 @@ class TrainStep:
         target = model.scheduler.get_velocity(normal_light, noise, timesteps) if self.velocity else noise
         cond = low_light.detach().float().contiguous()
         t = timesteps.to(device=dev, dtype=torch.long).contiguous()
-        h = unet._handle(resolve_compute_dtype(unet.compute_dtype))
-        nbytes = _train_buffers(self, h, b, dev)
-        eps = torch.empty(b, unet.config.out_channels, s, s, dtype=torch.float32, device=dev)
+        eps = torch.empty(b, unet.config.out_channels, hh, ww, dtype=torch.float32, device=dev)
         L = N.lib()
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
-            N.check(L.llie_unet_train_forward(h.h, noisy.data_ptr(), cond.data_ptr(), t.data_ptr(), eps.data_ptr(), b,
-                                              self._ws.data_ptr(), nbytes, st), "EfficientUNet.forward (training)")
-            diff = eps - target
-            n = diff.numel()
-            if self.loss_type == "mse":          # F.mse_loss: mean(d^2); d/d eps = 2 d / n
-                loss = (diff * diff).mean()
-                d_eps = diff * (2.0 / n)
-            elif self.loss_type == "l1":         # F.l1_loss: mean|d|; sign(d) / n
-                loss = diff.abs().mean()
-                d_eps = torch.sign(diff) / n
-            else:                                # F.huber_loss(delta=1): 0.5 d^2 inside, |d| - 0.5 outside; clamp(d, -1, 1) / n
-                a = diff.abs()
-                loss = torch.where(a < 1.0, 0.5 * diff * diff, a - 0.5).mean()
-                d_eps = diff.clamp(-1.0, 1.0) / n
+            h.unet_train_forward(noisy.data_ptr(), cond.data_ptr(), t.data_ptr(), eps.data_ptr(), b, hh, ww, self._ws.data_ptr(), nbytes, st)
+            from .pipeline import base_loss_and_grad, x0_loss_device
+            loss, d_eps = base_loss_and_grad(eps, target, self.loss_type)
             if self.x0_ssim_weight != 0.0 or self.x0_l1_weight != 0.0:
-                from .pipeline import x0_loss_device
                 d_eps = d_eps.contiguous()
                 loss = loss + x0_loss_device(model.scheduler, eps, noisy, normal_light, t, self.velocity, self.x0_ssim_weight,
                                              self.x0_l1_weight, d_eps)  # adds d(term)/d(eps) into d_eps

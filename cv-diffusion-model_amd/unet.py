@@ -126,14 +126,13 @@ class _UNetFn(torch.autograd.Function):
     def forward(ctx, unet, latents, cond, t, *params):
         h = unet._handle(resolve_compute_dtype(unet.compute_dtype))
         dev = latents.device
-        b, s = latents.shape[0], unet.config.image_size
-        nbytes = h.train_workspace_bytes(b)
+        b, hh, ww = latents.shape[0], int(latents.shape[2]), int(latents.shape[3])
+        nbytes = h.train_plan(b, hh, ww)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        out = torch.empty(b, unet.config.out_channels, s, s, dtype=torch.float32, device=dev)
+        out = torch.empty(b, unet.config.out_channels, hh, ww, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            N.check(N.lib().llie_unet_train_forward(h.h, latents.data_ptr(), cond.data_ptr(), t.data_ptr(), out.data_ptr(), b,
-                                                    ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream),
-                    "EfficientUNet.forward (training)")
+            h.unet_train_forward(latents.data_ptr(), cond.data_ptr(), t.data_ptr(), out.data_ptr(), b, hh, ww, ws.data_ptr(), nbytes,
+                                 torch.cuda.current_stream(dev).cuda_stream)
         ctx.unet, ctx.h, ctx.ws, ctx.nbytes, ctx.batch = unet, h, ws, nbytes, b
         ctx.keep = (latents, cond, t)  # the backward pass reads them again (input conv, time embedding)
         return out
@@ -457,14 +456,21 @@ class EfficientUNet(_NativeModule):
         return emb, temb
 
     def forward_split(self, latents: torch.Tensor, cond: torch.Tensor, timestep: torch.Tensor,
-                      uniform_t: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      uniform_t: bool = False, out: Optional[torch.Tensor] = None, *, frame: bool = False) -> torch.Tensor:
         """forward() on the two halves of cat([latents, cond], 1) (low_light_diffusion.py:222) -- the
-        concat is never materialised."""
+        concat is never materialised.  `frame=True` (extension, keyword only, like enhance_frame beside enhance): the maps may
+        have any H x W the frame rule accepts -- llie_train_shape_ok when the call records gradients, llie_frame_shape_ok
+        otherwise (ValueError naming the rule); the module tree stays the one image_size fixed.  Without it a shape other than
+        image_size is refused, as the reference's call would fail."""
         s = self.config.image_size
         b = latents.shape[0]
-        if tuple(latents.shape[2:]) != (s, s) or tuple(cond.shape[2:]) != (s, s):
-            raise ValueError(f"this engine runs the UNet at its construction size {s}x{s} "
-                             f"(got {tuple(latents.shape[2:])}); attention placement is fixed by image_size")
+        if latents.dim() != 4 or tuple(cond.shape[2:]) != tuple(latents.shape[2:]):
+            raise ValueError(f"latents and cond must be [B,C,H,W] maps of one size (got {tuple(latents.shape)} and {tuple(cond.shape)})")
+        hh, ww = int(latents.shape[2]), int(latents.shape[3])
+        if not frame and (hh, ww) != (s, s):
+            raise ValueError(f"EfficientUNet.forward runs at its construction size {s}x{s} (got {hh}x{ww}); frame=True runs any "
+                             "frame whose height and width are multiples of 8 and at least 64 (llie_frame_shape_ok, "
+                             "llie_train_shape_ok)")
         if latents.shape[1] + cond.shape[1] != self.config.in_channels or latents.shape[1] != self.config.in_channels // 2:
             raise ValueError("channel split does not match in_channels")
         dev = latents.device
@@ -476,13 +482,17 @@ class EfficientUNet(_NativeModule):
         if self._wants_grad() and not uniform_t and out is None:
             # training: activations are kept and the result carries a grad_fn (parameter gradients only)
             return _UNetFn.apply(self, latents, cond, t, *[p for _, p in self._ordered_params()])
-        h, ws, nbytes = self._prepare(b, dev)
+        h, ws, nbytes = self._prepare(b, dev, frame=None if (hh, ww) == (s, s) else (hh, ww))
         if out is None:
-            out = torch.empty(b, self.config.out_channels, s, s, dtype=torch.float32, device=dev)
+            out = torch.empty(b, self.config.out_channels, hh, ww, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            N.check(N.lib().llie_unet_forward(h.h, latents.data_ptr(), cond.data_ptr(), t.data_ptr(), int(uniform_t),
-                                              out.data_ptr(), b, ws.data_ptr(), nbytes,
-                                              torch.cuda.current_stream(dev).cuda_stream), "EfficientUNet.forward")
+            st = torch.cuda.current_stream(dev).cuda_stream
+            if (hh, ww) == (s, s):
+                N.check(N.lib().llie_unet_forward(h.h, latents.data_ptr(), cond.data_ptr(), t.data_ptr(), int(uniform_t),
+                                                  out.data_ptr(), b, ws.data_ptr(), nbytes, st), "EfficientUNet.forward")
+            else:
+                N.check(N.lib().llie_unet_forward_hw(h.h, latents.data_ptr(), cond.data_ptr(), t.data_ptr(), int(uniform_t),
+                                                     out.data_ptr(), b, hh, ww, ws.data_ptr(), nbytes, st), "EfficientUNet.forward")
         return out
 
     def forward(self, x: torch.Tensor, timestep: torch.Tensor, return_features: bool = False) -> torch.Tensor:

@@ -176,7 +176,22 @@ int llie_module_forward(llie_ctx* ctx, const float* x, const float* temb, float*
  *   llie_unet_backward:       given d(loss)/d(eps) (fp32 NCHW) -> grads; `workspace` must be the untouched
  *                             buffer of the preceding train_forward; lat / cond / t must still be alive
  *   llie_module_backward:     single operator (IRB / ATTN / DOWN / UP handles): forward + backward in one call;
- *                             dx fp32 NCHW like x, dtemb [B][T] (IRB only) */
+ *                             dx fp32 NCHW like x, dtemb [B][T] (IRB only)
+ * Training at a frame's own H x W (UNet handles; the module tree stays the one image_size fixed, as in frame mode):
+ *   llie_train_shape_ok (host only, no GPU needed): LLIE_OK for the frames a UNet trains at.  It is llie_frame_shape_ok with the
+ *       element cap taken over what the backward pass stores: batch x ceil64(height x width) x Cmax <= 2^31 - 1, where the rows
+ *       of each image are padded to whole 64-row chunks (the weight-gradient GEMM walks them so) and Cmax also covers the
+ *       up-sampled tensor the tape keeps at full resolution and the 32-channel packed copies of the head and the input conv.
+ *       `tiny` / `base` (zero-padded channels) return LLIE_ERR_CONFIG: inference only.
+ *   llie_train_workspace_bytes: for a UNet handle the plan at (height, width); 0, 0 means image_size.  A shape
+ *       llie_train_shape_ok refuses returns its code.
+ *   llie_unet_train_forward_hw: llie_unet_train_forward on fp32 NCHW [B,3,H,W]; llie_unet_train_forward is this entry at
+ *       H = W = image_size.  The tape records (H, W): llie_unet_backward takes the shape from it (d_eps [B,3,H,W]).
+ * The weight-gradient GEMM splits its rows freely when H or W is off the multiples of 64, and by the rule of the 64-grid
+ * otherwise: a rule on the frame alone, never on the batch. */
+int llie_train_shape_ok(const llie_ctx* ctx, int batch, int height, int width);
+int llie_unet_train_forward_hw(llie_ctx* ctx, const float* latents, const float* cond, const int64_t* timesteps, float* eps,
+                               int batch, int height, int width, void* workspace, int64_t workspace_bytes, llie_stream stream);
 int64_t llie_grad_numel(const llie_ctx* ctx);
 int64_t llie_param_grad_offset(const llie_ctx* ctx, int index);
 int64_t llie_train_workspace_bytes(llie_ctx* ctx, int batch, int height, int width);
@@ -404,6 +419,15 @@ int llie_aug_pair_u8(const uint8_t* pool, const int64_t* table, int N, const lli
                      float* low, float* high, uint8_t* low_u8, uint8_t* high_u8, llie_stream stream);
 int llie_aug_synth_u8(const uint8_t* pool, const int64_t* table, int N, const llie_aug_row* plan, int first, int count, int S,
                       const float* z, float* low, float* high, uint8_t* low_u8, uint8_t* high_u8, llie_stream stream);
+/* The same two on rectangular crops of SH rows x SW columns (frame-size training); the entry points above are these at
+ * SH = SW = S, with the same bits.  low / high: fp32 [count][3][SH][SW]; the optional bytes and z: [count][SH][SW][3].
+ *   crop(yy, xx) = frame[y0 + (vflip ? SH-1-yy : yy)][x0 + (hflip ? SW-1-xx : xx)]; origins are clamped into
+ *   [0, H_frame - SH] x [0, W_frame - SW]; the rotation is about (cx, cy) = ((SW-1)/2, (SH-1)/2): u = x - cx, v = y - cy,
+ *   xs = (ca*u + sa*v) + cx, ys = (-sa*u + ca*v) + cy; reflect-101 and the clamp act per axis with that axis's length. */
+int llie_aug_pair_u8_hw(const uint8_t* pool, const int64_t* table, int N, const llie_aug_row* plan, int first, int count, int SH,
+                        int SW, float* low, float* high, uint8_t* low_u8, uint8_t* high_u8, llie_stream stream);
+int llie_aug_synth_u8_hw(const uint8_t* pool, const int64_t* table, int N, const llie_aug_row* plan, int first, int count, int SH,
+                         int SW, const float* z, float* low, float* high, uint8_t* low_u8, uint8_t* high_u8, llie_stream stream);
 
 /* Image quality: per image of a against b, out3 [batch][3] doubles = {mse, psnr, ssim}.  All arithmetic is float64 on the mapped
  * values: x = (v - lo) / (hi - lo) for fp32 NCHW [batch][3][H][W] (the model's range is lo = -1, hi = 1), x = byte / 255 for uint8

@@ -15,6 +15,12 @@ to --output_dir.  One JSON line per epoch is printed: epoch, train_loss, lr, val
 
 adds the image-space term to --loss: SSIM / L1 of the clean image each step implies against the normal-light image (train_loss
 then includes it; val_loss stays the MSE).  The two weights are not stored in checkpoints: pass them again with --resume.
+
+  python scripts/train.py --data_dir LOL/our485 --val_dir LOL/eval15 --crop_height 400 --crop_width 600
+
+trains at a frame's own shape, the one frame mode (scripts/inference.py --mode frame) runs at: crops of 400 x 600 instead of
+--image_size squares, validation and sample sheets through enhance_frame.  Both flags or neither; multiples of 8, at least 64.
+The model keeps the module tree --image_size fixed.  Like the x0 weights the shape is not stored in checkpoints.
 """
 import argparse
 import importlib
@@ -68,11 +74,17 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--sampler", type=str, default="lcm", choices=["lcm", "ddim"],
                    help="how validation and the sample sheet sample: lcm = the consistency student's loop; ddim = the deterministic "
                         "DDIM loop a many-step (teacher) model wants, with --num_steps steps (anything in 1..1000) in both")
+    p.add_argument("--crop_height", type=int, default=None, help="train at crops of this height (with --crop_width) instead of --image_size squares")
+    p.add_argument("--crop_width", type=int, default=None, help="the width that goes with --crop_height")
     return p
 
 
 def parse_args(argv=None):
-    return build_parser().parse_args(argv)
+    p = build_parser()
+    args = p.parse_args(argv)
+    if (args.crop_height is None) != (args.crop_width is None):
+        p.error("--crop_height and --crop_width go together: both or neither")
+    return args
 
 
 def config_from_args(args) -> "M.TrainingConfig":
@@ -98,6 +110,11 @@ def sampler_from_args(args) -> dict:
     return {"val_sampler": args.sampler, "val_steps": args.num_steps if args.sampler == "ddim" else None}
 
 
+def crop_size_from_args(args) -> dict:
+    """LowLightTrainer's `crop_size` keyword (not a TrainingConfig field, not in checkpoints): (H, W) with both flags, else None."""
+    return {"crop_size": None if args.crop_height is None else (args.crop_height, args.crop_width)}
+
+
 def main(argv=None) -> int:
     args = parse_args(argv)
     config = config_from_args(args)
@@ -108,8 +125,10 @@ def main(argv=None) -> int:
     print("=" * 60)
     print(f"\nLoading data from: {args.data_dir}")
     val_dir = args.val_dir if args.val_dir and os.path.isdir(args.val_dir) else None
+    crop = crop_size_from_args(args)["crop_size"]
     train_loader, val_loader = M.create_device_dataloaders(train_root=args.data_dir, val_root=val_dir, batch_size=args.batch_size,
-                                                           image_size=args.image_size, use_synthetic=args.use_synthetic, seed=args.seed)
+                                                           image_size=args.image_size if crop is None else crop,
+                                                           use_synthetic=args.use_synthetic, seed=args.seed)
     print(f"  Train batches: {len(train_loader)}")
     if val_loader is not None:
         print(f"  Val batches: {len(val_loader)}")
@@ -121,7 +140,7 @@ def main(argv=None) -> int:
     print(f"  Parameters: {size['num_params']:,}")
 
     trainer = M.LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config,
-                                **x0_weights_from_args(args), **sampler_from_args(args))
+                                **x0_weights_from_args(args), **sampler_from_args(args), crop_size=crop)
     print(f"  Engine precision: {model.compute_dtype}, loss scaler: {trainer.scaler is not None}, EMA: {config.use_ema}")
     trainer.train(on_epoch=lambda log: print(json.dumps(log), flush=True))
     print("\nTraining complete!")
