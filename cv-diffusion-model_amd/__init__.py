@@ -24,7 +24,7 @@ from .hostio import (load_checkpoint, extract_state_dict, preprocess_array, post
 from .tiling import (tile_origins, gather_tiles_array, blend_tiles_array, gather_tiles_device, gather_noise_device,
                      blend_tiles_device, enhance_tiled, frame_pad, frame_load_array, frame_store_array, frame_load_device,
                      frame_store_device, enhance_frame_u8, sync_step_array, canvas_store_array, enhance_tiled_sync_array,
-                     sync_step_device)
+                     sync_step_device, auto_tile_plan)
 from .data import (DeviceFrameStore, DevicePairLoader, create_device_dataloaders, epoch_plan, augment_pairs_host, augment_synth_host,
                    augment_pairs_device, augment_synth_device)
 from .metrics import (ImageMetrics, image_metrics, image_metrics_host, evaluate, evaluate_full_resolution, ssim_loss,
@@ -40,7 +40,7 @@ __all__ = [
     "preprocess_array", "postprocess_array", "resize_bilinear", "preprocess_device", "postprocess_device",
     "tile_origins", "gather_tiles_array", "blend_tiles_array", "gather_tiles_device", "gather_noise_device", "blend_tiles_device",
     "enhance_tiled", "frame_pad", "frame_load_array", "frame_store_array", "frame_load_device", "frame_store_device", "enhance_frame_u8",
-    "sync_step_array", "canvas_store_array", "enhance_tiled_sync_array", "sync_step_device",
+    "sync_step_array", "canvas_store_array", "enhance_tiled_sync_array", "sync_step_device", "auto_tile_plan",
     "DeviceFrameStore", "DevicePairLoader", "create_device_dataloaders", "epoch_plan", "augment_pairs_host", "augment_synth_host",
     "augment_pairs_device", "augment_synth_device",
     "ImageMetrics", "image_metrics", "image_metrics_host", "evaluate", "evaluate_full_resolution",

@@ -50,6 +50,7 @@ EXPORTS = [
     "llie_frame_pad", "llie_frame_load_u8", "llie_frame_store_u8",
     "llie_ssim_grad_scratch_bytes", "llie_ssim_grad_f32", "llie_x0_loss",
     "llie_train_shape_ok", "llie_unet_train_forward_hw", "llie_aug_pair_u8_hw", "llie_aug_synth_u8_hw",
+    "llie_tile_gather_u8_hw", "llie_tile_gather_f32_hw", "llie_tile_blend_u8_hw", "llie_tile_sync_step_hw", "llie_frame_max_pixels",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 PW_SIGMOID_BWD, PW_RELU6_BWD, PW_SILU_BWD, PW_SCALE = 0, 1, 2, 3  # llie_pointwise_kind
@@ -190,7 +191,13 @@ def lib() -> C.CDLL:
     L.llie_tile_gather_f32.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, vp, vp]
     L.llie_tile_blend_u8.argtypes = [vp, ci, ci, ci, ci, vp, vp]
     L.llie_tile_sync_step.argtypes = [vp, ci, ci, ci, ci, vp, vp, C.POINTER(StepCoef), vp, vp, vp]
+    L.llie_tile_gather_u8_hw.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]
+    L.llie_tile_gather_f32_hw.argtypes = [vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp]
+    L.llie_tile_blend_u8_hw.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp]
+    L.llie_tile_sync_step_hw.argtypes = [vp, ci, ci, ci, ci, ci, ci, vp, vp, C.POINTER(StepCoef), vp, vp, vp]
     L.llie_frame_shape_ok.argtypes = [vp, ci, ci, ci]
+    L.llie_frame_max_pixels.argtypes = [vp, ci]
+    L.llie_frame_max_pixels.restype = i64
     L.llie_frame_workspace_bytes.argtypes = [vp, ci, ci, ci, ci]
     L.llie_frame_workspace_bytes.restype = i64
     L.llie_unet_forward_hw.argtypes = [vp, vp, vp, vp, ci, vp, ci, ci, ci, vp, i64, vp]
@@ -437,6 +444,13 @@ class Handle:
     def frame_shape_ok(self, batch: int, h: int, w: int) -> None:
         """Raises ValueError naming the rule of llie_frame_shape_ok that (batch, h, w) breaks."""
         check(self._L.llie_frame_shape_ok(self.h, batch, h, w), "frame shape")
+
+    def frame_max_pixels(self, batch: int = 1) -> int:
+        """The H * W the element cap of llie_frame_shape_ok allows each frame of `batch` (host only)."""
+        n = self._L.llie_frame_max_pixels(self.h, batch)
+        if n < 0:
+            check(int(n), "llie_frame_max_pixels")
+        return int(n)
 
     def train_shape_ok(self, batch: int, h: int, w: int) -> None:
         """Raises ValueError naming the rule of llie_train_shape_ok that (batch, h, w) breaks."""

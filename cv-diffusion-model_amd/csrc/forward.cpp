@@ -635,6 +635,12 @@ int64_t llie_enhance_workspace_bytes(llie_ctx* c, int batch, int max_steps) {
 
 int llie_frame_shape_ok(const llie_ctx* c, int batch, int height, int width) { return frame_shape_ok(c, batch, height, width); }
 
+// the pixel count the element cap of frame_shape_ok leaves a frame of a batch: floor((2^31 - 1) / (batch * Cmax))
+int64_t llie_frame_max_pixels(const llie_ctx* c, int batch) {
+  if (!c || c->cfg.kind != LLIE_UNET || batch <= 0) return LLIE_ERR_ARG;
+  return 2147483647ll / ((long long)batch * widest_full_res_channels(c));
+}
+
 int64_t llie_frame_workspace_bytes(llie_ctx* c, int batch, int height, int width, int max_steps) {
   if (max_steps < 0) return LLIE_ERR_ARG;
   const int rc = frame_shape_ok(c, batch, height, width);

@@ -478,35 +478,52 @@ int llie_postprocess_u8(const float* x, int batch, int S, uint8_t* img, int H0, 
 }
 
 int llie_tile_count(int L, int S, int v) {
-  if (!tile_plan_ok(L, L, S, v)) return LLIE_ERR_ARG;
+  if (!tile_plan_ok(L, L, S, S, v, v)) return LLIE_ERR_ARG;
   return tile_axis_count(L, S, v);
 }
 int llie_tile_origins(int L, int S, int v, int* out) {
-  if (!out || !tile_plan_ok(L, L, S, v)) return LLIE_ERR_ARG;
+  if (!out || !tile_plan_ok(L, L, S, S, v, v)) return LLIE_ERR_ARG;
   const int n = tile_axis_count(L, S, v);
   for (int i = 0; i < n; ++i) out[i] = tile_axis_origin(i, L, S, n);
   return LLIE_OK;
 }
-int llie_tile_gather_u8(const uint8_t* img, int H, int W, int S, int v, int first, int count, float* tiles, llie_stream stream) {
+int llie_tile_gather_u8_hw(const uint8_t* img, int H, int W, int SH, int SW, int vy, int vx, int first, int count, float* tiles,
+                           llie_stream stream) {
   if (!img || !tiles) return LLIE_ERR_ARG;
-  return kerr("tile_gather_u8", launch_tile_gather_u8(img, TilePlan{H, W, S, v, first, count}, tiles, hs(stream)), LLIE_ERR_ARG, nullptr);
-}
-int llie_tile_gather_f32(const float* canvas, int planes, int H, int W, int S, int v, int first, int count, float* out, llie_stream stream) {
-  if (!canvas || !out) return LLIE_ERR_ARG;
-  return kerr("tile_gather_f32", launch_tile_gather_f32(canvas, planes, TilePlan{H, W, S, v, first, count}, out, hs(stream)), LLIE_ERR_ARG,
+  return kerr("tile_gather_u8", launch_tile_gather_u8(img, TilePlan{H, W, SH, SW, vy, vx, first, count}, tiles, hs(stream)), LLIE_ERR_ARG,
               nullptr);
 }
-int llie_tile_blend_u8(const float* tiles, int H, int W, int S, int v, uint8_t* img, llie_stream stream) {
-  if (!tiles || !img) return LLIE_ERR_ARG;
-  return kerr("tile_blend_u8", launch_tile_blend_u8(tiles, TilePlan{H, W, S, v, 0, 1}, img, hs(stream)), LLIE_ERR_ARG, nullptr);
+int llie_tile_gather_f32_hw(const float* canvas, int planes, int H, int W, int SH, int SW, int vy, int vx, int first, int count, float* out,
+                            llie_stream stream) {
+  if (!canvas || !out) return LLIE_ERR_ARG;
+  return kerr("tile_gather_f32", launch_tile_gather_f32(canvas, planes, TilePlan{H, W, SH, SW, vy, vx, first, count}, out, hs(stream)),
+              LLIE_ERR_ARG, nullptr);
 }
-
-int llie_tile_sync_step(const float* eps_tiles, int H, int W, int S, int v, const float* canvas_in, const float* noise,
-                        const llie_step_coef* k, float* canvas_out, uint8_t* img, llie_stream stream) {
+int llie_tile_blend_u8_hw(const float* tiles, int H, int W, int SH, int SW, int vy, int vx, uint8_t* img, llie_stream stream) {
+  if (!tiles || !img) return LLIE_ERR_ARG;
+  return kerr("tile_blend_u8", launch_tile_blend_u8(tiles, TilePlan{H, W, SH, SW, vy, vx, 0, 1}, img, hs(stream)), LLIE_ERR_ARG, nullptr);
+}
+int llie_tile_sync_step_hw(const float* eps_tiles, int H, int W, int SH, int SW, int vy, int vx, const float* canvas_in, const float* noise,
+                           const llie_step_coef* k, float* canvas_out, uint8_t* img, llie_stream stream) {
   if (!eps_tiles || !canvas_in || !k || !canvas_out || !step_coef_ok(*k)) return LLIE_ERR_ARG;
   const StepCoef c = step_coef(*k);
-  return kerr("tile_sync_step", launch_tile_sync_step(eps_tiles, TilePlan{H, W, S, v, 0, 1}, canvas_in, noise, c, canvas_out, img, hs(stream)),
+  return kerr("tile_sync_step",
+              launch_tile_sync_step(eps_tiles, TilePlan{H, W, SH, SW, vy, vx, 0, 1}, canvas_in, noise, c, canvas_out, img, hs(stream)),
               LLIE_ERR_ARG, nullptr);
+}
+// the square entries: the same launchers at SH = SW = S, vy = vx = v
+int llie_tile_gather_u8(const uint8_t* img, int H, int W, int S, int v, int first, int count, float* tiles, llie_stream stream) {
+  return llie_tile_gather_u8_hw(img, H, W, S, S, v, v, first, count, tiles, stream);
+}
+int llie_tile_gather_f32(const float* canvas, int planes, int H, int W, int S, int v, int first, int count, float* out, llie_stream stream) {
+  return llie_tile_gather_f32_hw(canvas, planes, H, W, S, S, v, v, first, count, out, stream);
+}
+int llie_tile_blend_u8(const float* tiles, int H, int W, int S, int v, uint8_t* img, llie_stream stream) {
+  return llie_tile_blend_u8_hw(tiles, H, W, S, S, v, v, img, stream);
+}
+int llie_tile_sync_step(const float* eps_tiles, int H, int W, int S, int v, const float* canvas_in, const float* noise,
+                        const llie_step_coef* k, float* canvas_out, uint8_t* img, llie_stream stream) {
+  return llie_tile_sync_step_hw(eps_tiles, H, W, S, S, v, v, canvas_in, noise, k, canvas_out, img, stream);
 }
 
 int llie_frame_pad(int L) { return L > 0 && L <= (1 << 24) ? frame_pad(L) : LLIE_ERR_ARG; }

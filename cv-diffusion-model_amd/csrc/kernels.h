@@ -567,25 +567,26 @@ hipError_t launch_consistency_loss(const DistillArgs& a, double* partial, float*
 // ema = ema * decay + (1 - decay) * p over the tables' tensors (OptTensor.p = source, OptTensor.ema = destination)
 hipError_t launch_ema_lerp(const OptTensor* tensors, const OptChunk* chunks, int nchunks, double decay, hipStream_t s);
 
-// (11) full-resolution images as overlapping S x S tiles (tiles.hip).  The plan of one axis of length L, tile side S, overlap
+// (11) full-resolution images as overlapping SH x SW tiles (tiles.hip).  The plan of one axis of length L, tile side S, overlap
 // v (0 <= 2v <= S): one tile at 0 when L <= S, else n = ceil((L - S) / (S - v)) + 1 tiles at o_i = floor(i (L - S) / (n - 1)).
 // The same two functions serve the host (llie_tile_count / llie_tile_origins) and the kernels, which compute origins themselves.
 __host__ __device__ inline int tile_axis_count(int L, int S, int v) { return L <= S ? 1 : (L - S + (S - v) - 1) / (S - v) + 1; }
 __host__ __device__ inline int tile_axis_origin(int i, int L, int S, int n) { return n <= 1 ? 0 : i * (L - S) / (n - 1); }  // n * L < 2^31 (tile_plan_ok)
-inline bool tile_plan_ok(int H, int W, int S, int v) {
-  if (H <= 0 || W <= 0 || S <= 0 || v < 0 || 2 * v > S) return false;
-  const long long ny = tile_axis_count(H, S, v), nx = tile_axis_count(W, S, v);
+inline bool tile_plan_ok(int H, int W, int SH, int SW, int vy, int vx) {
+  if (H <= 0 || W <= 0 || SH <= 0 || SW <= 0 || vy < 0 || vx < 0 || 2 * vy > SH || 2 * vx > SW) return false;
+  const long long ny = tile_axis_count(H, SH, vy), nx = tile_axis_count(W, SW, vx);
   return ny * H < (1ll << 31) && nx * W < (1ll << 31) && ny * nx < (1ll << 31);
 }
-struct TilePlan { int H, W, S, v, first, count; };  // image size, tile side, overlap, chunk [first, first + count) of the row-major tiles
-// img u8 [H][W][3] -> tiles fp32 [count][3][S][S] = img / 127.5 - 1 (edge replication where the image is smaller than a tile)
+// image size, tile sides (rows use (H, SH, vy), columns (W, SW, vx)), overlaps, chunk [first, first + count) of the row-major tiles
+struct TilePlan { int H, W, SH, SW, vy, vx, first, count; };
+// img u8 [H][W][3] -> tiles fp32 [count][3][SH][SW] = img / 127.5 - 1 (edge replication where the image is smaller than a tile)
 hipError_t launch_tile_gather_u8(const uint8_t* img, const TilePlan& p, float* tiles, hipStream_t s);
-// canvas fp32 [planes][max(H,S)][max(W,S)], planes = 3 k -> out fp32 [k][count][3][S][S]: a copy
+// canvas fp32 [planes][max(H,SH)][max(W,SW)], planes = 3 k -> out fp32 [k][count][3][SH][SW]: a copy
 hipError_t launch_tile_gather_f32(const float* canvas, int planes, const TilePlan& p, float* out, hipStream_t s);
-// tiles fp32 [T][3][S][S] (every tile of the plan) -> img u8 [H][W][3]: feathered weighted mean in ascending tile order, then
+// tiles fp32 [T][3][SH][SW] (every tile of the plan) -> img u8 [H][W][3]: feathered weighted mean in ascending tile order, then
 // (r + 1) * 127.5 clipped and truncated; one thread per 4 output pixels, no atomics
 hipError_t launch_tile_blend_u8(const float* tiles, const TilePlan& p, uint8_t* img, hipStream_t s);
-// One LCM step of the latent canvas fp32 [3][max(H,S)][max(W,S)] the tiles of an image share: eps fp32 [T][3][S][S] (every tile
+// One LCM step of the latent canvas fp32 [3][max(H,SH)][max(W,SW)] the tiles of an image share: eps fp32 [T][3][SH][SW] (every tile
 // of the plan) is fused per canvas pixel -- the one covering tile's value, or the blend's weighted mean in ascending tile order --
 // and goes through lcm_step_kernel's arithmetic with the canvas and `noise` (same shape; may be NULL when c.is_last).  canvas_out
 // may be canvas_in.  img (or NULL): u8 [H][W][3], the blend's bytes of the new canvas.  One thread per 4 canvas pixels, no atomics

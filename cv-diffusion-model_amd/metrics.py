@@ -41,7 +41,7 @@ import torch.nn.functional as F
 from . import _native as N
 from .data import DeviceFrameStore, DevicePairLoader
 from .ddim import check_sampler
-from .tiling import enhance_tiled, enhance_frame_u8, frame_pad
+from .tiling import enhance_tiled, enhance_frame_u8, frame_pad, resolve_tile_plan
 
 WINDOW_TAPS, WINDOW_SIGMA = 11, 1.5
 C1, C2 = 1e-4, 9e-4
@@ -404,7 +404,8 @@ def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[i
 def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_steps: Optional[int] = None, seed: int = 0,
                              overlap: Optional[int] = None, tile_batch: int = 32,
                              weights: Optional[Sequence[torch.Tensor]] = None, mode: str = "tiled",
-                             sync: str = "none", sampler: str = "lcm") -> Dict[str, object]:
+                             sync: str = "none", sampler: str = "lcm", tile=None,
+                             max_tile_pixels: Optional[int] = None) -> Dict[str, object]:
     """PSNR / SSIM / MSE at the images' own resolution: every low-light frame of the paired `store` (any sizes >= 11 x 11) goes
     through `enhance_tiled` and is scored against its normal-light frame on the bytes (x = byte / 255).
 
@@ -419,11 +420,13 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
     store.frame(i), num_inference_steps, noise=canvas).  `overlap` / `tile_batch` / `sync` belong to the tiles and are refused.
 
     sync="latents" (mode="tiled") passes through to `enhance_tiled`: the tiles share one latent canvas at every step.
+    tile= / max_tile_pixels= (mode="tiled") pass through as well: with tile=(TH, TW) the canvas of the recipe is
+    [steps, 3, max(H, TH), max(W, TW)], and with tile="auto" TH x TW is the tile `auto_tile_plan` gives that image.
     sampler="ddim" passes through to `enhance_tiled` / `enhance_frame_u8` in every mode; steps = 1 in the draws above."""
     if mode not in ("tiled", "frame"):
         raise ValueError(f'mode must be "tiled" or "frame", got {mode!r}')
-    if mode == "frame" and (overlap is not None or tile_batch != 32 or sync != "none"):
-        raise ValueError('overlap / tile_batch / sync belong to mode="tiled"')
+    if mode == "frame" and (overlap is not None or tile_batch != 32 or sync != "none" or tile is not None or max_tile_pixels is not None):
+        raise ValueError('overlap / tile_batch / sync / tile / max_tile_pixels belong to mode="tiled"')
     if sync not in ("none", "latents"):
         raise ValueError(f'sync must be "none" or "latents", got {sync!r}')
     check_sampler(sampler)
@@ -433,7 +436,6 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
     if dev.type != "cuda":
         raise RuntimeError(f"evaluate_full_resolution runs only on a HIP device (the frame store is on '{dev}'); there is no CPU fallback")
     with _swapped_weights(model, weights):
-        s = int(model.image_size)
         nsteps, steps = _steps_of(model, num_inference_steps, dev, sampler)
         g = torch.Generator(device=dev).manual_seed(int(seed))
         n = len(store)
@@ -443,9 +445,14 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
                 canvas = torch.randn(steps, 3, frame_pad(h), frame_pad(w), generator=g, device=dev)
                 out = enhance_frame_u8(model, store.frame(i), nsteps, noise=canvas, sampler=sampler)
             else:
-                canvas = torch.randn(steps, 3, max(h, s), max(w, s), generator=g, device=dev)
-                out = enhance_tiled(model, store.frame(i), nsteps, overlap=overlap, tile_batch=tile_batch, noise=canvas, sync=sync,
-                                    sampler=sampler)
+                sh, sw, vy, vx = resolve_tile_plan(model, (h, w), tile, overlap, max_tile_pixels)
+                canvas = torch.randn(steps, 3, max(h, sh), max(w, sw), generator=g, device=dev)
+                if tile is None:
+                    plan = {"overlap": overlap}
+                else:  # the plan is settled here, so "auto" is passed on as the tile it chose
+                    plan = {"tile": (sh, sw), "overlap": (vy, vx)}
+                out = enhance_tiled(model, store.frame(i), nsteps, tile_batch=tile_batch, noise=canvas, sync=sync, sampler=sampler,
+                                    **plan)
             triples.append(_metrics_out3(out, store.frame(n + i), None))
         flat = torch.cat(triples).cpu().numpy()
     return _summary(store.names, flat, None)

@@ -211,7 +211,7 @@ class LowLightDiffusion(nn.Module):
             try:  # the workspace query applies the frame rule: a refused frame raises before any draw or launch
                 prepared = self.unet._prepare(b, device, enhance_steps=stage_steps, frame=frame)
             except ValueError as e:
-                hint = "; enhance_tiled handles images of any size" if "element cap" in str(e) else ""
+                hint = '; enhance_tiled(tile="auto") handles images of any size' if "element cap" in str(e) else ""
                 raise ValueError(f"enhance_frame: {e}{hint}") from None
 
         if noise is None:

@@ -156,6 +156,9 @@ int llie_unet_forward(llie_ctx* ctx, const float* latents, const float* cond, co
  * A launch rule (block form, Gram statistics, folded up-sampling conv) depends on the layer, (H, W), the dtype and the knobs,
  * never on the batch: a frame's result is the same bits alone or in a batch. */
 int llie_frame_shape_ok(const llie_ctx* ctx, int batch, int height, int width);
+/* host only, no GPU needed: floor((2^31 - 1) / (batch x Cmax)), the pixel count height x width that the last clause above
+ * allows a frame of `batch` (5 592 405 for `small` at batch 1).  What a tile plan sizes its tiles by (tiling.auto_tile_plan). */
+int64_t llie_frame_max_pixels(const llie_ctx* ctx, int batch);
 int64_t llie_frame_workspace_bytes(llie_ctx* ctx, int batch, int height, int width, int max_steps);
 int llie_unet_forward_hw(llie_ctx* ctx, const float* latents, const float* cond, const int64_t* timesteps, int uniform_t,
                          float* eps_out, int batch, int height, int width, void* workspace, int64_t workspace_bytes,
@@ -374,6 +377,20 @@ int llie_tile_gather_f32(const float* canvas, int planes, int H, int W, int S, i
 int llie_tile_blend_u8(const float* tiles, int H, int W, int S, int v, uint8_t* img, llie_stream stream);
 int llie_tile_sync_step(const float* eps_tiles, int H, int W, int S, int v, const float* canvas_in, const float* noise,
                         const llie_step_coef* coef, float* canvas_out, uint8_t* img, llie_stream stream);
+
+/* The same four with rectangular tiles: rows are planned with (H, SH, vy) and columns with (W, SW, vx), each axis by the rule
+ * above with its own tile side and overlap (0 <= 2 vy <= SH, 0 <= 2 vx <= SW; llie_tile_count / llie_tile_origins per axis).
+ * Tile tensors are [T][3][SH][SW], numbered row-major; the canvas is [..][max(H,SH)][max(W,SW)]; the window is
+ * wy[y] * wx[x], wy[k] = min(k + 1, SH - k, vy) / vy (1 when vy == 0) and wx likewise.  Any positive tile sides are taken: the
+ * multiple-of-8 rule belongs to the network (llie_frame_shape_ok), not to these byte kernels.  The entries above are these at
+ * SH = SW = S, vy = vx = v, to the bit.  Same errors. */
+int llie_tile_gather_u8_hw(const uint8_t* img, int H, int W, int SH, int SW, int vy, int vx, int first, int count, float* tiles,
+                           llie_stream stream);
+int llie_tile_gather_f32_hw(const float* canvas, int planes, int H, int W, int SH, int SW, int vy, int vx, int first, int count,
+                            float* out, llie_stream stream);
+int llie_tile_blend_u8_hw(const float* tiles, int H, int W, int SH, int SW, int vy, int vx, uint8_t* img, llie_stream stream);
+int llie_tile_sync_step_hw(const float* eps_tiles, int H, int W, int SH, int SW, int vy, int vx, const float* canvas_in,
+                           const float* noise, const llie_step_coef* coef, float* canvas_out, uint8_t* img, llie_stream stream);
 
 /* Byte-level I/O of frame mode: a uint8 image of any size to the padded fp32 frame llie_enhance_hw takes, and back.
  *   llie_frame_pad:      a side L -> the next multiple of 8, at least 64 (host only)

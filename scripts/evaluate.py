@@ -6,7 +6,7 @@
 --data is the layout DeviceFrameStore.from_folder reads (ROOT/low and ROOT/high, or lowlight / dark and normal / bright).  By
 default every pair is centre-cropped to --image_size and goes through `evaluate` in batches of --batch_size (the result then
 also holds the validation loss); --full_resolution scores every image at its own size through `evaluate_full_resolution`
-(overlapping tiles, --tile_overlap / --tile_batch as in inference.py; `--full_resolution frame` runs the network once per image
+(overlapping tiles, --tile_overlap / --tile_batch / --tile_size as in inference.py; `--full_resolution frame` runs the network once per image
 at the image's own size instead, frame mode, and excludes the tile flags).  One JSON line is printed, and written to --output when
 given; the per-image lists are part of it only under --per_image.  --seed seeds every draw, so a run is reproducible.
 """
@@ -53,9 +53,21 @@ def parse_args(argv=None):
     p.add_argument("--sampler", type=str, default="lcm", choices=["lcm", "ddim"],
                    help="lcm = the consistency student's loop; ddim = the deterministic DDIM loop of a many-step model "
                         "(--num_steps anything in 1..1000)")
+    p.add_argument("--tile_size", type=str, default=None, metavar="{auto|HxW}",
+                   help="with --full_resolution [tiled]: tiles of H x W run as frames instead of image_size squares; auto = the "
+                        "fewest such tiles under the engine's size cap")
     args = p.parse_args(argv)
-    if args.full_resolution == "frame" and (args.tile_overlap is not None or args.tile_batch != 32):
-        p.error("--full_resolution frame and --tile_overlap / --tile_batch exclude each other")
+    if args.full_resolution == "frame" and (args.tile_overlap is not None or args.tile_batch != 32 or args.tile_size is not None):
+        p.error("--full_resolution frame and --tile_overlap / --tile_batch / --tile_size exclude each other")
+    if args.tile_size is not None:
+        if args.full_resolution != "tiled":
+            p.error("--tile_size belongs to --full_resolution [tiled]")
+        try:
+            args.tile_size = inference.tiling.parse_tile_size(args.tile_size)
+        except ValueError as e:
+            p.error(str(e))
+        if args.tile_size == "auto" and args.tile_overlap is not None:
+            p.error("--tile_size auto chooses the overlap; drop --tile_overlap")
     return args
 
 
@@ -65,7 +77,8 @@ def main(argv=None) -> int:
     if args.full_resolution:
         store = M.DeviceFrameStore.from_folder(args.data, device=args.device)
         res = M.evaluate_full_resolution(model, store, num_inference_steps=args.num_steps, seed=args.seed, overlap=args.tile_overlap,
-                                         tile_batch=args.tile_batch, mode=args.full_resolution, sampler=args.sampler)
+                                         tile_batch=args.tile_batch, mode=args.full_resolution, sampler=args.sampler,
+                                         tile=args.tile_size)
     else:
         store = M.DeviceFrameStore.from_folder(args.data, device=args.device, image_size=args.image_size)
         loader = M.DevicePairLoader(store, args.batch_size, args.image_size, "val")

@@ -4,8 +4,9 @@ scripts/inference.py (:30-62): --input --output --checkpoint --model --format --
 --num_steps --device.  Only --format pytorch exists here (ONNX / TFLite are the reference's mobile
 deployment targets, out of scope); extensions: --dtype {fp32,fp16,bf16}, --noise_seed, --sampler {lcm,ddim} (ddim: the
 deterministic sampler of a many-step model, --num_steps anything in 1..1000), and --tile [--tile_overlap N]
-[--tile_batch N] [--tile_sync {none,latents}], which enhances the image at its own resolution as overlapping image_size tiles
-instead of resizing it (--tile_sync latents: the tiles share one latent canvas, fused after every step), and
+[--tile_batch N] [--tile_sync {none,latents}] [--tile_size {auto|HxW}], which enhances the image at its own resolution as
+overlapping image_size tiles instead of resizing it (--tile_sync latents: the tiles share one latent canvas, fused after every
+step; --tile_size: the tiles are frames of H x W, or with auto the fewest frames the engine can run -- three for 12 MP), and
 --native, which enhances it at its own resolution by one run of the network at that size (frame mode; images under the engine's
 size cap, about 5.59 M pixels for `small`).  --native and the tile flags exclude each other.
 """
@@ -52,14 +53,28 @@ def parse_args(argv=None):
     p.add_argument("--tile_sync", type=str, default="none", choices=["none", "latents"],
                    help="with --tile: latents = keep one latent canvas per image and fuse the tiles' predictions into it after "
                         "every step, so neighbours agree where they overlap; none = each tile runs its own loop")
+    p.add_argument("--tile_size", type=str, default=None, metavar="{auto|HxW}",
+                   help="with --tile: tiles of H x W (multiples of 8, at least 64) run as frames instead of image_size squares; "
+                        "auto = the fewest such tiles under the engine's size cap, overlapping by an eighth (--tile_overlap "
+                        "is then chosen for you)")
     p.add_argument("--native", action="store_true",
                    help="(extension) no resize and no tiles: one run of the network at the image's own resolution (frame mode); "
                         "--noise_seed then seeds the noise canvas at the padded size")
     args = p.parse_args(argv)
-    if args.native and (args.tile or args.tile_overlap is not None or args.tile_batch != 32 or args.tile_sync != "none"):
-        p.error("--native and --tile / --tile_overlap / --tile_batch / --tile_sync exclude each other")
+    if args.native and (args.tile or args.tile_overlap is not None or args.tile_batch != 32 or args.tile_sync != "none"
+                        or args.tile_size is not None):
+        p.error("--native and --tile / --tile_overlap / --tile_batch / --tile_sync / --tile_size exclude each other")
     if args.tile_sync != "none" and not args.tile:
         p.error("--tile_sync belongs to --tile")
+    if args.tile_size is not None:
+        if not args.tile:
+            p.error("--tile_size belongs to --tile")
+        try:
+            args.tile_size = tiling.parse_tile_size(args.tile_size)
+        except ValueError as e:
+            p.error(str(e))
+        if args.tile_size == "auto" and args.tile_overlap is not None:
+            p.error("--tile_size auto chooses the overlap; drop --tile_overlap")
     return args
 
 
@@ -83,10 +98,12 @@ def enhance_tiled_image(args, model, rgb):
     noise = None
     if args.noise_seed is not None:  # the canvas every tile reads its noise from, drawn entry by entry in enhance's order
         g = torch.Generator().manual_seed(args.noise_seed)
-        hc, wc = max(rgb.shape[0], args.image_size), max(rgb.shape[1], args.image_size)
+        sh, sw, _, _ = tiling.resolve_tile_plan(model, rgb.shape[:2], args.tile_size, args.tile_overlap)
+        hc, wc = max(rgb.shape[0], sh), max(rgb.shape[1], sw)
         noise = torch.stack([torch.randn(3, hc, wc, generator=g) for _ in range(noise_entries(args))])
     out = tiling.enhance_tiled(model, torch.from_numpy(rgb).to(args.device), args.num_steps, overlap=args.tile_overlap,
-                               tile_batch=args.tile_batch, noise=noise, sync=args.tile_sync, sampler=args.sampler)
+                               tile_batch=args.tile_batch, noise=noise, sync=args.tile_sync, sampler=args.sampler,
+                               tile=args.tile_size)
     return out.cpu().numpy()
 
 
