@@ -334,21 +334,30 @@ constexpr int SHP = 144;
 // 2 next tile's loads issued + halo validity, 3 tile-top barrier, 4 pool flush behind it, 5 chunk-top barrier + flush
 // (chunks after the first), 6 expand MFMAs + epilogue + ds_write, 7 barrier behind them, 8 depthwise phase incl. the h2
 // stores and the pool partial); never used in production.
+// llie_tune("irbx_stamp", 3) stamps expand_dw_project (fp16) with slots of its own: 0 wait for the x tile (vmcnt), 1 activate +
+// ds_write + the next tile's and the shortcut's loads issued + halo validity, 2 tile-top barrier + flush of y's statistics + the
+// shortcut into the y accumulators, 3 chunk-top barrier (chunks after the first), 4 expand MFMAs + epilogue + ds_write, 5 barrier
+// behind them, 6 depthwise steps until the last accumulator can be read, 7 pack + swap + project MFMAs issued (they complete under
+// whatever follows), 8 the tile's epilogue: rounding, y's statistics, stores issued.
 // The depthwise phase issues two taps per 16x16x32 MFMA (k = 2 taps x 16 channels): one ds_read_b128 data operand per MFMA,
 // 640 matrix-pipe cycles per 64-channel chunk and wave (one tap per 32x32x16 MFMA, round 2's form, took 1 152).
 // NTST = h2 leaves with non-temporal stores (IrbxArgs::nt).
 //
 // PCO > 0 (expand_dw_project_kernel): the project GEMM of an identity-residual block as the tail, PCO = Cout = Cin.  h2 never
 // leaves the workgroup: a wave owns two output rows and ALL 64 channels of the chunk in the depthwise phase (instead of four
-// rows and 32 channels), so after the SE gate (fp32, on the accumulators) and the same permlane16 swap that used to feed the
-// h2 stores, a lane holds 8 consecutive channels of one pixel -- a B fragment of a 16x16x32 MFMA whose A fragment is 16 rows
-// of Wp.  y[32 pixels][PCO] accumulates in fp32 over the chunks (PCO / 2 registers); the tile's epilogue adds the raw x of
-// the centre pixels, rounds to T, stores y and leaves y's GroupNorm partials as the tile's slab entry.  No pool work here:
-// the gate is already known (expand_pool_kernel).
+// rows and 32 channels), so after the same permlane16 swap that used to feed the h2 stores a lane holds 8 consecutive channels
+// of one pixel -- a B fragment of a 16x16x32 MFMA whose A fragment is 16 rows of Wp.  No pool work here: the SE gate is already
+// known (expand_pool_kernel), a constant per (image, channel), and a workgroup serves one image, so the gate is part of the
+// depthwise weights it stages, T(6 w gate): the accumulators of the depthwise phase are gate * h2 and the chunk tail has nothing
+// to multiply (expand_pool keeps T(6 w): its totals are what the gate is computed from; and so does the 64-channel form here,
+// which keeps the gate as a table in LDS and multiplies the fp32 accumulators: GATEW below).  y[32 pixels][PCO] accumulates in fp32
+// over the chunks (PCO / 2 registers) and STARTS as the shortcut -- the raw x of the centre pixels, loaded before the tile-top
+// barrier together with the next tile's prefetch -- so the tile's epilogue only rounds to T, stores y and leaves y's GroupNorm
+// partials as the tile's slab entry.
 // PCO != K (96 -> 32): the block has a skip conv instead of the identity shortcut, and its input may be a virtual concat.  Wp is
 // then the engine's K-concatenated matrix [PCO][Chid + K] (row stride IrbxArgs::ldp), project columns first: the chunk tail reads
-// the project columns as before, and the tile's epilogue runs K / 32 more k-steps y += Wskip . x on the raw centre pixels (no norm,
-// no activation: the skip segments of pw_gemm) in place of the residual add.
+// the project columns as before, and y starts as Wskip . x on the raw centre pixels: K / 32 k-steps at the top of the tile (no
+// norm, no activation: the skip segments of pw_gemm), their operands loaded before the tile-top barrier.
 template <typename T, int KS, bool DBUF, bool STAMP, bool NTST, int PCO>
 __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tiles_per_wg, const int chunks_per_wg) {
   constexpr int K = 16 * KS;
@@ -363,6 +372,7 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
   typedef typename Elem<T>::vec_t vec_t;
   extern __shared__ __align__(16) unsigned char smem[];
   // [sH: (DBUF ? 2 : 1) x 192 x 128 B][sX: 192 x XP][wds: 9 x Chid T][aff2: 2 x Chid fp32][aff1: 2 x K fp32][red: 2 x 4 x 64 fp32]
+  // [pool totals: KS x 64 int64, KS <= 4]; PCO > 0: red is 4 x 2 x PCO fp32, followed by the gate table (Chid fp32) at KS = 4 only
   unsigned char* sH = smem;
   unsigned char* sX = smem + (DBUF ? 2 : 1) * SH_BYTES;
   T* wds = reinterpret_cast<T*>(sX + kXNPB * 32 * XP);
@@ -377,11 +387,13 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
   long long* pacc_lds = reinterpret_cast<long long*>(red + 2 * 256);
   long long pacc_reg[PACC_LDS ? 1 : KS];
   constexpr bool PSKIP = PCO > 0 && PCO != K;  // skip conv in place of the identity shortcut
-  // PCO: the image's SE gate [Chid] takes the pool totals' place; the skip form (no LDS pool totals at KS = 6, and 768 B left of
-  // what two workgroups per CU allow) puts it behind the 4 x 2 x PCO floats of `red` the project form needs
-  float* gate_s = reinterpret_cast<float*>(red + (PSKIP ? 8 * PCO : 2 * 256));
-  static_assert(PCO == 0 || (!DBUF && !STAMP && (PCO == K ? PACC_LDS : PCO % 32 == 0 && PCO <= 64)),
-                "project tail: single-buffered kernel; identity blocks keep the gate in the pool totals' LDS");
+  // PCO: no pool totals, and `red` is the four waves' (sum, sum of squares) of y, 4 x 2 x PCO floats.  The image's SE gate is
+  // part of the staged depthwise weights (GATEW) -- except at 64 channels, where that measured no faster than the gate table
+  // [Chid] in LDS behind `red`, applied to the accumulators in the chunk tail (profiles/r20/README.md), and the table stays
+  constexpr bool GATEW = PCO > 0 && KS != 4;
+  float* gate_s = red + 8 * PCO;
+  static_assert(PCO == 0 || (!DBUF && (PCO == K ? KS <= 4 : PCO % 32 == 0 && PCO <= 64)),
+                "project tail: single-buffered kernel; identity form at 32 and 64 channels, skip form to 32 or 64");
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = lane & 31, h = lane >> 5;
@@ -401,7 +413,10 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
   // [tap pair][channel][2]: one dword = this channel's weights of taps 2 p and 2 p + 1 (tap 9 = 0); the tile in LDS holds relu6(.) / 6
   for (int i = tid; i < 10 * a.Chid; i += 256) {
     const int t = i & 1, c = (i >> 1) % a.Chid, tap = 2 * ((i >> 1) / a.Chid) + t;
-    wds[i] = tap < 9 ? (T)(6.f * a.wd[tap * a.Chid + c]) : (T)0.f;
+    // GATEW: times the image's SE gate -- a constant per (image, channel) like the weight itself: the fp32 product is rounded to
+    // T once, where 6 w alone was rounded, and the chunk tail has no gate to apply
+    if constexpr (GATEW) wds[i] = tap < 9 ? (T)(6.f * a.wd[tap * a.Chid + c] * a.gate[(size_t)b * a.Chid + c]) : (T)0.f;
+    else wds[i] = tap < 9 ? (T)(6.f * a.wd[tap * a.Chid + c]) : (T)0.f;
   }
   for (int i = tid; i < a.Chid; i += 256) {
     aff2[i] = a.as2[(size_t)b * a.Chid + i];                      // applied to acc' = acc / 6: scale unchanged,
@@ -411,7 +426,7 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
     aff1[i] = a.as1[(size_t)b * K + i];      // already / 6 (GnFinalizeArgs::post_scale)
     aff1[K + i] = a.ab1[(size_t)b * K + i];
   }
-  if constexpr (PCO > 0)
+  if constexpr (PCO > 0 && !GATEW)
     for (int i = tid; i < a.Chid; i += 256) gate_s[i] = a.gate[(size_t)b * a.Chid + i];
   // pixels 180..191 of the last MFMA block do not exist: their operand rows stay zero
   for (int i = tid; i < (kXNPB * 32 - kXNPX) * (XP / 16); i += 256)
@@ -472,7 +487,7 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
   wg_barrier();  // constants staged
 
   unsigned long long tk[kXStamps] = {}, t_prev = 0;
-  auto stamp = [&](int slot) {
+  auto stamp_at = [&](int slot) {
     if constexpr (STAMP) {
       __builtin_amdgcn_sched_barrier(0);
       const unsigned long long now = __builtin_amdgcn_s_memtime();
@@ -481,7 +496,9 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
       t_prev = now;
     }
   };
-  stamp(-1);
+  auto stamp = [&](int slot) { if constexpr (PCO == 0) stamp_at(slot); };   // the slots of expand_dw
+  auto pstamp = [&](int slot) { if constexpr (PCO > 0) stamp_at(slot); };   // the slots of expand_dw_project
+  stamp_at(-1);
   const bool has_pool = PCO == 0 && (a.pool != nullptr || a.pool_tot != nullptr);
   int par = 0;  // sH / red buffer parity (DBUF)
   int pend_tile = -1, pend_chunk = 0, pend_par = 0;  // pool partial waiting for its cross-wave sum
@@ -537,12 +554,50 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
     // h2 stores stay in flight -- instead of the vmcnt(0) that the merge with this path forced.
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     stamp(0);
+    pstamp(0);
 #pragma unroll
     for (int j = 0; j < XPT; ++j) {
       if (j < XPT - 1 ? xthr : xlast)
         *reinterpret_cast<vec_t*>(sxw + j * QSTEP * XP) = activate8<T>(raw[j], aff1 + xk8, aff1 + K + xk8);
     }
     stamp(1);
+    // PCO: the shortcut's operands, for the wave's 2 rows x 16 pixels (lane = pixel li, quarter g): the raw x of the centre pixels,
+    // rows 16 cb + 4 g + e of every block cb (identity form), or the K / 32 k-steps of the skip conv -- k-step ks covers input
+    // channels 32 ks .. 32 ks + 31, lane (li, g) holds channels 32 ks + 8 g .. + 7 of row 16 cb + li of Wskip (A) and of pixel li
+    // of the row (B); a 16-byte vector never straddles the segments (c0 % 16 == 0).  The tile's own loads have left x in L2.  They
+    // go out here, ahead of the next tile's prefetch, and become the start of the y accumulators behind the tile-top barrier; the
+    // staging registers (raw) are free by now.  (vmcnt counts in order, so the wait for them could leave the prefetch in flight;
+    // hipcc's does not -- the prefetch loads are lane-predicated, it assumes none was issued and waits vmcnt(0) for the last
+    // shortcut register: profiles/r20/README.md, section 1.)
+    constexpr int NCB = PCO > 0 ? PCO / 16 : 1;  // 16-row blocks of Wp
+    constexpr int NKS = PSKIP ? K / 32 : 1;
+    typedef T t4 __attribute__((ext_vector_type(4)));
+    t4 res[2][NCB];
+    vec_t wsf[NKS][NCB], xsv[NKS][2];
+    if constexpr (PCO > 0) {
+      const int li = lane & 15, g = lane >> 4;
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const size_t pix = (size_t)(y0 + 2 * wave + r) * a.W + x0p + li;
+        if constexpr (!PSKIP) {
+#pragma unroll
+          for (int cb = 0; cb < NCB; ++cb) res[r][cb] = *reinterpret_cast<const t4*>(x0 + pix * PCO + 16 * cb + 4 * g);
+        } else {
+#pragma unroll
+          for (int ks = 0; ks < NKS; ++ks) {
+            const int ch = 32 * ks + 8 * g;
+            xsv[ks][r] = ch < a.c0 ? ld_vec<T>(x0 + pix * a.c0 + ch) : ld_vec<T>(x1 + pix * a.c1 + (ch - a.c0));
+          }
+        }
+      }
+      if constexpr (PSKIP) {
+        const T* wsk = reinterpret_cast<const T*>(a.wp) + (size_t)li * a.ldp + a.Chid + 8 * g;
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+          for (int cb = 0; cb < NCB; ++cb) wsf[ks][cb] = ld_vec<T>(wsk + (size_t)cb * 16 * a.ldp + 32 * ks);
+      }
+    }
     if (PREF && tile + 1 < tile_last) load_tile(tyn, txn);
     // validity of this lane's three halo pixels (zero padding of the depthwise input): border tiles only
     const bool border = ty == 0 || tx == 0 || ty == a.H / kXT_H - 1 || tx == tiles_x - 1;
@@ -556,18 +611,31 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
       }
     }
     stamp(2);
+    pstamp(1);
     wg_barrier();
     stamp(3);
     if (!DBUF) flush_pool();
     stamp(4);
 
     typedef float f32x4v __attribute__((ext_vector_type(4)));
-    constexpr int NCB = PCO > 0 ? PCO / 16 : 1;  // 16-row blocks of Wp
+    // y[32 pixels][PCO] of the wave starts as its shortcut: raw x (identity form), Wskip . x (skip form)
     f32x4v yacc[2][NCB];
 #pragma unroll
     for (int r = 0; r < 2; ++r)
 #pragma unroll
-      for (int cb = 0; cb < NCB; ++cb) yacc[r][cb] = f32x4v{0.f, 0.f, 0.f, 0.f};
+      for (int cb = 0; cb < NCB; ++cb) {
+        if constexpr (PCO > 0 && !PSKIP) yacc[r][cb] = f32x4v{(float)res[r][cb][0], (float)res[r][cb][1], (float)res[r][cb][2], (float)res[r][cb][3]};
+        else yacc[r][cb] = f32x4v{0.f, 0.f, 0.f, 0.f};
+      }
+    if constexpr (PSKIP) {
+#pragma unroll
+      for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+          for (int cb = 0; cb < NCB; ++cb) yacc[r][cb] = mfma16x16<T>(wsf[ks][cb], xsv[ks][r], yacc[r][cb]);
+    }
+    pstamp(2);
     // (Unrolling this loop lets hipcc count the memory operations between a prefetch and its use -- vmcnt(5) instead of
     // vmcnt(2) for the weight slices -- but costs 11 spilled registers, and every spill reload waits vmcnt(0), i.e. for the
     // h2 stores in flight: 35.7 vs 34.7 ms per step.  The run-time loop stays.)
@@ -577,6 +645,7 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
         wg_barrier();  // previous depthwise phase done with sH
         flush_pool();
         stamp(5);
+        pstamp(3);
       }
       // ---- MFMA: h1^T block (32 channels x 32 pixels) x 3 pixel blocks
       const int ch0 = chunk * 64 + chb * 32;
@@ -642,9 +711,11 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
         *reinterpret_cast<u32x4*>(buf + q * SHP + (chb * 4 + 2 * h + 1) * 16) = hi2;
       }
       stamp(6);
+      pstamp(4);
       wg_barrier();
       if (DBUF) flush_pool();
       stamp(7);
+      pstamp(5);
       // ---- depthwise 3x3 on the MFMA pipe.  The VALU is what this kernel runs out of (a wave64 instruction costs a SIMD
       // 4 cycles; 72 FMAs per 16 output bytes), the matrix pipe idles.  A depthwise tap is a diagonal matrix:
       //   out[ch][px] += sum_k diag(w_tap)[ch][k] * in[k][px + tap]      (k over the block's channels, 16 per tap)
@@ -701,14 +772,21 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
 #pragma unroll
           for (int r = 0; r < 2; ++r) dacc[c][r] = mfma16x16<T>(af, bf[step & 1][r], dacc[c][r]);
         }
-        // SE gate on the fp32 accumulators (lane: channels 16 c + 4 g + e), one rounding to T, then y += Wp . (gate * h2)
+        if constexpr (STAMP) {  // a read of the last accumulator: the compiler waits for the depthwise MFMAs here
+          asm volatile("" ::"s"(__builtin_amdgcn_readfirstlane(__float_as_int(dacc[3][1][3]))));
+          pstamp(6);
+        }
+        // GATEW: the accumulators hold gate * h2 (the gate is in the staged weights); else the SE gate on the fp32 accumulators
+        // (lane: channels 16 c + 4 g + e).  One rounding to T, then y += Wp . (gate * h2)
+        if constexpr (!GATEW) {
 #pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const f32x4 gt = *reinterpret_cast<const f32x4*>(gate_s + chunk * 64 + 16 * c + 4 * g);
+          for (int c = 0; c < 4; ++c) {
+            const f32x4 gt = *reinterpret_cast<const f32x4*>(gate_s + chunk * 64 + 16 * c + 4 * g);
 #pragma unroll
-          for (int r = 0; r < 2; ++r)
+            for (int r = 0; r < 2; ++r)
 #pragma unroll
-            for (int e = 0; e < 4; ++e) dacc[c][r][e] *= gt[e];
+              for (int e = 0; e < 4; ++e) dacc[c][r][e] *= gt[e];
+          }
         }
 #pragma unroll
         for (int r = 0; r < 2; ++r)
@@ -730,6 +808,7 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb) yacc[r][cb] = mfma16x16<T>(wpf[cb][kb], reinterpret_cast<const vec_t&>(v), yacc[r][cb]);
           }
+        pstamp(7);
       } else {
         // ---- two taps per MFMA: D[16 ch][16 px] += A[16 ch][k] B[k][16 px], k = 16 t + c (tap slot t, channel c of the
         // 16-channel tile), in this order of k: lane (li = lane & 15, g = lane >> 4) holds k-slice g = tap slot g & 1, channels 8 (g >> 1) + j.
@@ -839,30 +918,11 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
       stamp(8);
     }
     if constexpr (PCO > 0) {
-      // ---- y = round(acc + x) for the wave's 2 rows x 16 pixels: lane (pixel li, g) holds rows 16 cb + 4 g + e of every block cb
+      // ---- y = round(acc) for the wave's 2 rows x 16 pixels (the shortcut is in acc since the top of the tile): lane (pixel li, g)
+      // holds rows 16 cb + 4 g + e of every block cb
       const int li = lane & 15, g = lane >> 4;
       const int choff = 8 * (g >> 1) + 16 * (g & 1);
       T* yout = reinterpret_cast<T*>(a.y) + (size_t)b * P * PCO;
-      if constexpr (PSKIP) {
-        // y += Wskip . x: k-step ks covers input channels 32 ks .. 32 ks + 31, lane (li, g) holds channels 32 ks + 8 g .. + 7 of
-        // row 16 cb + li of Wskip (A) and of pixel li of the row (B); a 16-byte vector never straddles the segments (c0 % 16 == 0).
-        // The tile's own loads have left x in L2.
-        const T* wsk = reinterpret_cast<const T*>(a.wp) + (size_t)li * a.ldp + a.Chid + 8 * g;
-#pragma unroll
-        for (int ks = 0; ks < K / 32; ++ks) {
-          const int ch = 32 * ks + 8 * g;
-          vec_t wsf[NCB];
-#pragma unroll
-          for (int cb = 0; cb < NCB; ++cb) wsf[cb] = ld_vec<T>(wsk + (size_t)cb * 16 * a.ldp + 32 * ks);
-#pragma unroll
-          for (int r = 0; r < 2; ++r) {
-            const size_t pix = (size_t)(y0 + 2 * wave + r) * a.W + x0p + li;
-            const vec_t xv = ch < a.c0 ? ld_vec<T>(x0 + pix * a.c0 + ch) : ld_vec<T>(x1 + pix * a.c1 + (ch - a.c0));
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb) yacc[r][cb] = mfma16x16<T>(wsf[cb], xv, yacc[r][cb]);
-          }
-        }
-      }
       float st[2][NCB * 4];  // (sum, sum of squares) of the rounded outputs, this lane's 2 pixels
 #pragma unroll
       for (int i = 0; i < NCB * 4; ++i) st[0][i] = st[1][i] = 0.f;
@@ -872,16 +932,13 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
         uint32_t pk[NCB][2];
 #pragma unroll
         for (int cb = 0; cb < NCB; ++cb) {
-          typedef T t4 __attribute__((ext_vector_type(4)));
           typedef T t2 __attribute__((ext_vector_type(2)));
-          t4 res = t4{};
-          if constexpr (!PSKIP) res = *reinterpret_cast<const t4*>(x0 + pix * PCO + 16 * cb + 4 * g);  // the tile's own loads left it in L2
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
             t2 o;
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
-              o[e] = PSKIP ? (T)yacc[r][cb][2 * j + e] : (T)(yacc[r][cb][2 * j + e] + (float)res[2 * j + e]);
+              o[e] = (T)yacc[r][cb][2 * j + e];
               const float q = (float)o[e];
               st[0][4 * cb + 2 * j + e] += q;
               st[1][4 * cb + 2 * j + e] = __builtin_fmaf(q, q, st[1][4 * cb + 2 * j + e]);
@@ -896,29 +953,48 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
           *reinterpret_cast<u32x4*>(yout + pix * PCO + 32 * pp + choff) = u32x4{s0[0], s1[0], s0[1], s1[1]};
         }
       }
-      // sums over the 16 pixel lanes of a row by DPP (as the pool partial of the plain kernel), eight values at a time
+      // Sums over the 16 pixel lanes of a row, sixteen values at a time, as a transposing reduction: a step halves the values a
+      // lane carries -- the lane keeps one half and adds its partner's copy of that half, the partner keeps the other -- so the
+      // steps cost 16 + 8 adds and leave lane quad k = li >> 2 with the sums of values 4 k .. 4 k + 3 over four lanes each; two
+      // butterfly steps inside the quad (4 + 4 adds) finish them: 32 adds instead of 4 x 16.  The partner is the mirrored lane
+      // (li ^ 15, then li ^ 7), and which half a lane writes is the DPP bank mask (banks = lane quads of a row): the first add of a
+      // pair completes the half kept in place, the second builds the other half from the upper registers into the lower ones.
+      // As in the pool partial of the plain kernel the adds are single v_add_f32 with a DPP source, written out because the
+      // builtin costs three instructions each, and a register written by one statement is read by DPP four or more statements
+      // later (2 wait states needed); s_nop 1 covers the ordinary VALU writes in front.  The order is fixed: the slab stays
+      // bitwise independent of the batch and the schedule.
 #pragma unroll
-      for (int w8 = 0; w8 < NCB; ++w8) {
-        float* v = &st[w8 & 1][(w8 >> 1) * 8];
-#define LLIE_DPP_STEP(ROR)                                                                                               \
-  _Pragma("unroll") for (int i = 0; i < 8; ++i)                                                                          \
-      asm volatile("v_add_f32_dpp %0, %0, %0 row_ror:" #ROR " row_mask:0xf bank_mask:0xf" : "+v"(v[i]));
-        asm volatile("s_nop 1" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
-        LLIE_DPP_STEP(8)
-        LLIE_DPP_STEP(4)
-        LLIE_DPP_STEP(2)
-        LLIE_DPP_STEP(1)
+      for (int grp = 0; grp < NCB / 2; ++grp) {
+        float v[16];  // PCO = 32: (which, cb, e) = (j >> 3, (j >> 2) & 1, j & 3); PCO = 64: which = grp, (cb, e) = (j >> 2, j & 3)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          if constexpr (NCB == 2) v[j] = st[j >> 3][j & 7];
+          else v[j] = st[grp][j];
+        }
+        asm volatile("s_nop 1" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]),
+                                 "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]));
+#define LLIE_DPP_HALVE(N, CTRL, KEEP, TAKE)                                                                                  \
+  _Pragma("unroll") for (int i = 0; i < N; ++i)                                                                              \
+      asm volatile("v_add_f32_dpp %0, %0, %0 " CTRL " row_mask:0xf bank_mask:" KEEP : "+v"(v[i]));                           \
+  _Pragma("unroll") for (int i = 0; i < N; ++i)                                                                              \
+      asm volatile("v_add_f32_dpp %0, %1, %1 " CTRL " row_mask:0xf bank_mask:" TAKE : "+v"(v[i]) : "v"(v[i + N]));
+#define LLIE_DPP_STEP(CTRL)                                                                                                  \
+  _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                              \
+      asm volatile("v_add_f32_dpp %0, %0, %0 " CTRL " row_mask:0xf bank_mask:0xf" : "+v"(v[i]));
+        LLIE_DPP_HALVE(8, "row_mirror", "0x3", "0xc")        // lanes 0..7 keep values 0..7, lanes 8..15 take 8..15
+        LLIE_DPP_HALVE(4, "row_half_mirror", "0x5", "0xa")   // quads 0 and 2 keep values 0..3 of theirs, quads 1 and 3 take 4..7
+        LLIE_DPP_STEP("quad_perm:[2,3,0,1]")
+        LLIE_DPP_STEP("quad_perm:[1,0,3,2]")
+#undef LLIE_DPP_HALVE
 #undef LLIE_DPP_STEP
-      }
-      if (li == 0) {  // red[wave][which][channel 16 cb + 4 g + e]
-#pragma unroll
-        for (int which = 0; which < 2; ++which)
-#pragma unroll
-          for (int cb = 0; cb < NCB; ++cb)
-            *reinterpret_cast<f32x4*>(red + (wave * 2 + which) * PCO + 16 * cb + 4 * g) =
-                f32x4{st[which][4 * cb], st[which][4 * cb + 1], st[which][4 * cb + 2], st[which][4 * cb + 3]};
+        if ((li & 3) == 0) {  // red[wave][which][channel 16 cb + 4 g + e]: quad k of the row holds (which, cb) = (k >> 1, k & 1) or (grp, k)
+          const int k = li >> 2;
+          const int which = NCB == 2 ? k >> 1 : grp, cb = NCB == 2 ? k & 1 : k;
+          *reinterpret_cast<f32x4*>(red + (wave * 2 + which) * PCO + 16 * cb + 4 * g) = f32x4{v[0], v[1], v[2], v[3]};
+        }
       }
       pend_tile = tile;
+      pstamp(8);
     }
     ty = tyn; tx = txn;
   }
@@ -953,6 +1029,10 @@ __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_ker
 template <typename T, int KS, int PCO>
 __global__ void __launch_bounds__(256, KS == 2 ? 3 : 2) expand_dw_project_kernel(const IrbxArgs a, const int tiles_per_wg) {
   expand_dw_body<T, KS, false, false, false, PCO>(a, tiles_per_wg, KS);
+}
+template <int KS, int PCO>
+__global__ void __launch_bounds__(256, KS == 2 ? 3 : 2) expand_dw_project_stamp_kernel(const IrbxArgs a, const int tiles_per_wg) {
+  expand_dw_body<half_t, KS, false, true, false, PCO>(a, tiles_per_wg, KS);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1001,6 +1081,19 @@ hipError_t irbx_stamp_fetch(double* out) {
   return hipSuccess;
 }
 void irbx_tune(int dbuf) { if (dbuf >= 0) g_irbx_dbuf = dbuf; }
+// the stamp buffer of a diagnostic launch of `waves` waves
+static hipError_t irbx_dbg_buffer(size_t waves, IrbxArgs& a) {
+  const size_t n = waves * kXStamps;
+  if (n > g_irbx_dbg_n || !g_irbx_dbg) {
+    if (g_irbx_dbg) (void)hipFree(g_irbx_dbg);
+    g_irbx_dbg = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&g_irbx_dbg), n * 8);
+    if (e != hipSuccess) return e;
+  }
+  g_irbx_dbg_n = n;
+  a.dbg = g_irbx_dbg;
+  return hipSuccess;
+}
 
 // expand_stats (POOL = false) and expand_pool: the same scan of x, one workgroup per irbx_stats_rows(P) pixels of an image
 template <typename T, int KS, int NBW, bool POOL>
@@ -1012,14 +1105,7 @@ static hipError_t launch_scan_cfg(const IrbxArgs& a, hipStream_t s) {
   if constexpr (POOL && std::is_same<T, half_t>::value) {
     if (g_irbx_stamp == 2) {  // diagnostic build: in-kernel cycle stamps
       IrbxArgs b = a;
-      const size_t n = (size_t)(P / RP) * a.B * 4 * kXStamps;
-      if (n > g_irbx_dbg_n || !g_irbx_dbg) {
-        if (g_irbx_dbg) (void)hipFree(g_irbx_dbg);
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&g_irbx_dbg), n * 8);
-        if (e != hipSuccess) return e;
-      }
-      g_irbx_dbg_n = n;
-      b.dbg = g_irbx_dbg;
+      if (hipError_t e = irbx_dbg_buffer((size_t)(P / RP) * a.B * 4, b); e != hipSuccess) return e;
       hipLaunchKernelGGL((expand_pool_stamp_kernel<KS, NBW>), dim3(P / RP, 1, a.B), dim3(256), 0, s, b, RP);
       return hipGetLastError();
     }
@@ -1049,16 +1135,16 @@ hipError_t launch_expand_pool(int dtype, const IrbxArgs& a, hipStream_t s) {
 }
 
 // Dynamic LDS of expand_dw_body, in the order of its layout comment (at `smem`): sH (twice when double-buffered), sX, the packed
-// depthwise weights, aff2, aff1, then `red` (2 x 256 floats) + the pool totals where they live in LDS (KS <= 4; the identity
-// project tail keeps the gate there) or, skip tail (PCO != 16 KS), `red` (8 PCO floats) + the gate (Chid floats)
+// depthwise weights, aff2, aff1, then `red` (2 x 256 floats) + the pool totals where they live in LDS (KS <= 4) or, project tail,
+// `red` (8 PCO floats) + the gate table (Chid floats) at 64 channels only: elsewhere the gate is in the depthwise weights
 constexpr size_t irbx_lds_bytes(int KS, int Chid, bool dbuf, int PCO) {
   const size_t body = (size_t)(dbuf ? 2 : 1) * kXNPB * 32 * SHP + (size_t)kXNPB * 32 * (16 * KS + 8) * 2 + (size_t)10 * Chid * 2 +
                       (size_t)2 * Chid * 4 + (size_t)2 * 16 * KS * 4;
-  if (PCO != 0 && PCO != 16 * KS) return body + (size_t)8 * PCO * 4 + (size_t)Chid * 4;
+  if (PCO != 0) return body + (size_t)8 * PCO * 4 + (KS == 4 ? (size_t)Chid * 4 : 0);
   return body + 2 * 256 * 4 + (KS <= 4 ? (size_t)KS * 64 * 8 : 0);
 }
-// 96 -> 32: 256 B short of what two workgroups per CU allow (profiles/r08/README.md)
-static_assert(irbx_lds_bytes(6, 384, false, 32) == 81664 && irbx_lds_bytes(6, 384, false, 32) <= 80 * 1024, "expand_dw_project<6, 32>: two workgroups per CU");
+// 96 -> 32: 1 792 B short of what two workgroups per CU allow (256 B while the gate table was in LDS, profiles/r08/README.md)
+static_assert(irbx_lds_bytes(6, 384, false, 32) == 80128 && irbx_lds_bytes(6, 384, false, 32) <= 80 * 1024, "expand_dw_project<6, 32>: two workgroups per CU");
 
 constexpr int kXTilesPerWg = 4;  // longest run of tiles along x one workgroup takes
 // tiles per workgroup: a run along x (neighbouring halo columns hit L1), as long as the launch keeps >= 2048 workgroups
@@ -1097,14 +1183,7 @@ static hipError_t launch_dw_cfg(const IrbxArgs& a, hipStream_t s) {
   if constexpr (std::is_same<T, half_t>::value && !DBUF) {
     if (g_irbx_stamp == 1) {  // diagnostic build: in-kernel cycle stamps (fp16 only)
       IrbxArgs b = a;
-      const size_t n = (size_t)grid.x * grid.y * grid.z * 4 * kXStamps;
-      if (n > g_irbx_dbg_n || !g_irbx_dbg) {
-        if (g_irbx_dbg) (void)hipFree(g_irbx_dbg);
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&g_irbx_dbg), n * 8);
-        if (e != hipSuccess) return e;
-      }
-      g_irbx_dbg_n = n;
-      b.dbg = g_irbx_dbg;
+      if (hipError_t e = irbx_dbg_buffer((size_t)grid.x * grid.y * grid.z * 4, b); e != hipSuccess) return e;
       return launch_dw_one<T, KS, DBUF, true, false>(b, grid, lds, tpw, cpw, s);
     }
   }
@@ -1132,6 +1211,17 @@ static hipError_t launch_project_cfg(const IrbxArgs& a, hipStream_t s) {
   static const std::string name = std::string("expand_dw_project_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) +
                                   (PCO == 16 * KS ? std::string() : ", " + std::to_string(PCO)) + ">";
   note_kernel(name.c_str());
+  if constexpr (std::is_same<T, half_t>::value) {
+    if (g_irbx_stamp == 3) {  // diagnostic build: in-kernel cycle stamps (fp16 only)
+      IrbxArgs b = a;
+      if (hipError_t e = irbx_dbg_buffer((size_t)(ntiles / tpw) * a.B * 4, b); e != hipSuccess) return e;
+      static std::atomic<uint64_t> stamp_attr_done{0};
+      if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&expand_dw_project_stamp_kernel<KS, PCO>), 128 * 1024, stamp_attr_done); e != hipSuccess)
+        return e;
+      hipLaunchKernelGGL((expand_dw_project_stamp_kernel<KS, PCO>), dim3(ntiles / tpw, 1, a.B), dim3(256), lds, s, b, tpw);
+      return hipGetLastError();
+    }
+  }
   static std::atomic<uint64_t> attr_done{0};
   if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&expand_dw_project_kernel<T, KS, PCO>), 128 * 1024, attr_done); e != hipSuccess) return e;
   hipLaunchKernelGGL((expand_dw_project_kernel<T, KS, PCO>), dim3(ntiles / tpw, 1, a.B), dim3(256), lds, s, a, tpw);

@@ -811,7 +811,7 @@ int llie_tune(const char* knob, int value);
  * And one for the loop of llie_enhance, default 20: graph_max_steps -- loops of more steps run as plain launches and are never
  * captured (measured: replaying the graph of a 50-step loop is slower than launching it); a value <= 0 restores the
  * default.  It changes no bit. */
-int llie_debug_irbx_stamps(double* out10); /* diagnostic builds: 9 per-wave cycle sums of expand_dw ("irbx_stamp" = 1) or of expand_pool's LDS-tile scan ("irbx_stamp" = 2, 5 slots used) (irbx.hip: STAMP) + waves averaged */
+int llie_debug_irbx_stamps(double* out10); /* diagnostic builds: 9 per-wave cycle sums of expand_dw ("irbx_stamp" = 1) or of expand_pool's LDS-tile scan ("irbx_stamp" = 2, 5 slots used) or of expand_dw_project ("irbx_stamp" = 3, slots of its own) (irbx.hip: STAMP) + waves averaged */
 int llie_debug_conv_stamps(double* out8); /* diagnostic builds: 7 per-wave cycle sums of the up-sampling conv (conv.hip: STAMP) + waves averaged */
 int llie_debug_gemm_stamps(double* out3); /* diagnostic builds: see gemm.hip (STAMP) */
 int llie_debug_pwx_stamps(double* out4);  /* diagnostic builds: see pwx.hip (STAMP): {A phase, channel loop, of which waiting for the weight DMA} cycles per wave, waves */

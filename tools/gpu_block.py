@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """One InvertedResidualBlock shape in a loop (GPU box): the workload for rocprofv3 passes over a single kernel family, and
-the reader of the diagnostic in-kernel cycle stamps of expand_dw (llie_tune("irbx_stamp", 1)).
+the reader of the diagnostic in-kernel cycle stamps of expand_dw (llie_tune("irbx_stamp", 1)) and of expand_dw_project (3).
 usage: gpu_block.py [cin cout hw batch split reps irbx dbuf stamp]"""
 import ctypes as C
 import importlib
@@ -43,8 +43,12 @@ def main():
         N.check(L.llie_debug_irbx_stamps(out))
         names = ["x wait (vmcnt)", "activate + ds_write", "next-tile loads + halo flags", "tile-top barrier", "pool flush", "chunk-top barrier + flush",
                  "expand MFMAs + epilogue", "barrier behind them", "depthwise phase + stores"]
+        if stamp == 3:  # expand_dw_project (the block must be one the project form takes)
+            names = ["x wait (vmcnt)", "activate + ds_write + loads issued", "tile-top barrier + flush + shortcut", "chunk-top barrier",
+                     "expand MFMAs + epilogue", "barrier behind them", "depthwise steps", "pack + swap + project MFMAs", "tile epilogue"]
+        kernel = {1: "expand_dw", 2: "expand_pool", 3: "expand_dw_project"}.get(stamp, "?")
         tot = sum(out[:9])
-        print(f"expand_dw mean shader cycles per wave over {out[9]:.0f} waves (s_memtime): total {tot:.0f}\n  "
+        print(f"{kernel} mean shader cycles per wave over {out[9]:.0f} waves (s_memtime): total {tot:.0f}\n  "
               + "\n  ".join(f"{n:30s} {v:9.0f} ({100 * v / tot:4.1f}%)" for n, v in zip(names, out)))
 
 
