@@ -318,7 +318,9 @@ __global__ void __launch_bounds__(256, 2) expand_pool_kernel(const IrbxArgs a, c
 }
 
 // ---------------------------------------------------------------------------------------------
-// (2) fused expand + norm2 / FiLM / ReLU6 + depthwise 3x3 + SE pool partials.
+// (2) fused expand + norm2 / FiLM / ReLU6 + depthwise 3x3, as two kernels built from the same phases:
+//   expand_dw_kernel          stores h2 and leaves the SE pool partials;
+//   expand_dw_project_kernel  keeps h2 in the workgroup and runs the project GEMM (+ shortcut) as its tail.
 constexpr int kXT_H = 8, kXT_W = 16;                 // output tile
 constexpr int kXH_W = kXT_W + 2, kXH_H = kXT_H + 2;  // halo tile 10 x 18 = 180 pixels -> 6 blocks of 32
 constexpr int kXNPX = kXH_W * kXH_H;
@@ -329,87 +331,70 @@ constexpr int kXNPB = 6;
 // pitch (36 dwords) spreads consecutive pixels over distinct bank groups for either instruction's lane grouping.
 constexpr int SHP = 144;
 
-// STAMP = diagnostic build (llie_tune("irbx_stamp", 1)): s_memtime around the phases, summed per wave into a.dbg
-// ([workgroup][wave][kXStamps] cycles: 0 wait for the prefetched / loaded x tile (vmcnt), 1 activate + ds_write of the x tile,
-// 2 next tile's loads issued + halo validity, 3 tile-top barrier, 4 pool flush behind it, 5 chunk-top barrier + flush
-// (chunks after the first), 6 expand MFMAs + epilogue + ds_write, 7 barrier behind them, 8 depthwise phase incl. the h2
-// stores and the pool partial); never used in production.
-// llie_tune("irbx_stamp", 3) stamps expand_dw_project (fp16) with slots of its own: 0 wait for the x tile (vmcnt), 1 activate +
-// ds_write + the next tile's and the shortcut's loads issued + halo validity, 2 tile-top barrier + flush of y's statistics + the
-// shortcut into the y accumulators, 3 chunk-top barrier (chunks after the first), 4 expand MFMAs + epilogue + ds_write, 5 barrier
-// behind them, 6 depthwise steps until the last accumulator can be read, 7 pack + swap + project MFMAs issued (they complete under
-// whatever follows), 8 the tile's epilogue: rounding, y's statistics, stores issued.
-// The depthwise phase issues two taps per 16x16x32 MFMA (k = 2 taps x 16 channels): one ds_read_b128 data operand per MFMA,
-// 640 matrix-pipe cycles per 64-channel chunk and wave (one tap per 32x32x16 MFMA, round 2's form, took 1 152).
-// NTST = h2 leaves with non-temporal stores (IrbxArgs::nt).
-//
-// PCO > 0 (expand_dw_project_kernel): the project GEMM of an identity-residual block as the tail, PCO = Cout = Cin.  h2 never
-// leaves the workgroup: a wave owns two output rows and ALL 64 channels of the chunk in the depthwise phase (instead of four
-// rows and 32 channels), so after the same permlane16 swap that used to feed the h2 stores a lane holds 8 consecutive channels
-// of one pixel -- a B fragment of a 16x16x32 MFMA whose A fragment is 16 rows of Wp.  No pool work here: the SE gate is already
-// known (expand_pool_kernel), a constant per (image, channel), and a workgroup serves one image, so the gate is part of the
-// depthwise weights it stages, T(6 w gate): the accumulators of the depthwise phase are gate * h2 and the chunk tail has nothing
-// to multiply (expand_pool keeps T(6 w): its totals are what the gate is computed from; and so does the 64-channel form here,
-// which keeps the gate as a table in LDS and multiplies the fp32 accumulators: GATEW below).  y[32 pixels][PCO] accumulates in fp32
-// over the chunks (PCO / 2 registers) and STARTS as the shortcut -- the raw x of the centre pixels, loaded before the tile-top
-// barrier together with the next tile's prefetch -- so the tile's epilogue only rounds to T, stores y and leaves y's GroupNorm
-// partials as the tile's slab entry.
-// PCO != K (96 -> 32): the block has a skip conv instead of the identity shortcut, and its input may be a virtual concat.  Wp is
-// then the engine's K-concatenated matrix [PCO][Chid + K] (row stride IrbxArgs::ldp), project columns first: the chunk tail reads
-// the project columns as before, and y starts as Wskip . x on the raw centre pixels: K / 32 k-steps at the top of the tile (no
-// norm, no activation: the skip segments of pw_gemm), their operands loaded before the tile-top barrier.
-template <typename T, int KS, bool DBUF, bool STAMP, bool NTST, int PCO>
-__device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tiles_per_wg, const int chunks_per_wg) {
-  constexpr int K = 16 * KS;
-  constexpr int XP = (K + 8) * 2;                        // sX pixel pitch in bytes (80 / 144 / 208 / 272: conflict-free ds_read_b128)
-  // x halo tile staging: thread -> (pixel xq0, 16-byte channel vector xkv); pass j covers pixel xq0 + j * QSTEP.  The channel
-  // vector -- hence the K segment, its base pointer and the norm1 table slice -- is the same in every pass and every tile.
-  constexpr int QSTEP = 256 / (2 * KS);                  // 64 / 32 / 21 pixels per pass
-  constexpr int XTHR = QSTEP * 2 * KS;                   // threads that take part (252 of 256 at KS = 6)
-  constexpr int XPT = (kXNPX + QSTEP - 1) / QSTEP;       // passes: 3 / 6 / 9
-  constexpr int SH_BYTES = kXNPB * 32 * SHP;
-  constexpr bool PREF = KS <= 2;        // next tile's x prefetched into registers at the top of the tile
-  typedef typename Elem<T>::vec_t vec_t;
-  extern __shared__ __align__(16) unsigned char smem[];
-  // [sH: (DBUF ? 2 : 1) x 192 x 128 B][sX: 192 x XP][wds: 9 x Chid T][aff2: 2 x Chid fp32][aff1: 2 x K fp32][red: 2 x 4 x 64 fp32]
-  // [pool totals: KS x 64 int64, KS <= 4]; PCO > 0: red is 4 x 2 x PCO fp32, followed by the gate table (Chid fp32) at KS = 4 only
-  unsigned char* sH = smem;
-  unsigned char* sX = smem + (DBUF ? 2 : 1) * SH_BYTES;
-  T* wds = reinterpret_cast<T*>(sX + kXNPB * 32 * XP);
-  float* aff2 = reinterpret_cast<float*>(wds + 10 * a.Chid);
-  float* aff1 = aff2 + 2 * a.Chid;
-  float* red = aff1 + 2 * K;
-  // fixed-point pool totals of this workgroup's tiles, [chunk][channel 64]: in LDS rather than in 2 KS registers of every
-  // thread -- this kernel sits exactly at an occupancy step, and a spilled register costs more than its scratch access:
-  // every reload is a vector-memory operation whose wait (vmcnt is in order) also waits for the h2 stores in flight
-  // (KS = 6 keeps them in registers: its 79 KB of LDS are two workgroups per CU only as long as nothing is added)
-  constexpr bool PACC_LDS = KS <= 4;
-  long long* pacc_lds = reinterpret_cast<long long*>(red + 2 * 256);
-  long long pacc_reg[PACC_LDS ? 1 : KS];
-  constexpr bool PSKIP = PCO > 0 && PCO != K;  // skip conv in place of the identity shortcut
-  // PCO: no pool totals, and `red` is the four waves' (sum, sum of squares) of y, 4 x 2 x PCO floats.  The image's SE gate is
-  // part of the staged depthwise weights (GATEW) -- except at 64 channels, where that measured no faster than the gate table
-  // [Chid] in LDS behind `red`, applied to the accumulators in the chunk tail (profiles/r20/README.md), and the table stays
-  constexpr bool GATEW = PCO > 0 && KS != 4;
-  float* gate_s = red + 8 * PCO;
-  static_assert(PCO == 0 || (!DBUF && (PCO == K ? KS <= 4 : PCO % 32 == 0 && PCO <= 64)),
-                "project tail: single-buffered kernel; identity form at 32 and 64 channels, skip form to 32 or 64");
+// Dynamic LDS of both kernels, as byte offsets from its start (sH = 0), for the kernels and for the launchers:
+//   [sH: (DBUF ? 2 : 1) x 192 x 144 B][sX: 192 x XP][wds: 10 x Chid T][aff2: 2 x Chid fp32][aff1: 2 x K fp32][red][tail]
+//   expand_dw (PCO = 0):          red = 2 x 4 x 64 fp32, tail = the pool totals, KS x 64 int64, where they live in LDS (KS <= 4)
+//   expand_dw_project (PCO > 0):  red = 4 x 2 x PCO fp32, tail = the gate table (Chid fp32) at 64 channels only: elsewhere the
+//                                 gate is in the depthwise weights
+struct IrbxLds { int sX, wds, aff2, aff1, red, tail, total; };
+constexpr IrbxLds irbx_lds(int KS, int Chid, bool dbuf, int PCO) {
+  IrbxLds l{};
+  l.sX = (dbuf ? 2 : 1) * kXNPB * 32 * SHP;
+  l.wds = l.sX + kXNPB * 32 * (16 * KS + 8) * 2;
+  l.aff2 = l.wds + 10 * Chid * 2;
+  l.aff1 = l.aff2 + 2 * Chid * 4;
+  l.red = l.aff1 + 2 * 16 * KS * 4;
+  l.tail = l.red + (PCO != 0 ? 8 * PCO : 2 * 256) * 4;
+  l.total = l.tail + (PCO != 0 ? (KS == 4 ? Chid * 4 : 0) : (KS <= 4 ? KS * 64 * 8 : 0));
+  return l;
+}
+constexpr size_t irbx_lds_bytes(int KS, int Chid, bool dbuf, int PCO) { return (size_t)irbx_lds(KS, Chid, dbuf, PCO).total; }
+// 96 -> 32: 1 792 B short of what two workgroups per CU allow (256 B while the gate table was in LDS, profiles/r08/README.md)
+static_assert(irbx_lds_bytes(6, 384, false, 32) == 80128 && irbx_lds_bytes(6, 384, false, 32) <= 80 * 1024, "expand_dw_project<6, 32>: two workgroups per CU");
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int n = lane & 31, h = lane >> 5;
-  const int chb = wave & 1, pxg = wave >> 1;
-  const int b = blockIdx.z;
-  const int tiles_x = a.W / kXT_W;
-  const int P = a.H * a.W;
-  const T* x0 = reinterpret_cast<const T*>(a.x0) + (size_t)b * P * a.c0;
-  const T* x1 = a.x1 ? reinterpret_cast<const T*>(a.x1) + (size_t)b * P * a.c1 : nullptr;
-  const T* w1 = reinterpret_cast<const T*>(a.w1);
-  T* out = reinterpret_cast<T*>(a.out) + (size_t)b * P * a.Chid;
-  const int chunk0 = blockIdx.y * chunks_per_wg;
-  const int nchunks_all = a.Chid / 64;
-  const int chunk1 = chunk0 + chunks_per_wg < nchunks_all ? chunk0 + chunks_per_wg : nchunks_all;
+// a thread's places: (n, h) in the 32x32 MFMAs of the expand phase, where wave (chb, pxg) owns channel half chb of the chunk
+// and pixel blocks 3 pxg .. 3 pxg + 2; (li, g) in the 16x16 MFMAs of the depthwise phase and the project tail
+struct IrbxLane { int tid, lane, wave, n, h, chb, pxg, li, g; };
+__device__ __forceinline__ IrbxLane irbx_lane() {
+  IrbxLane t;
+  t.tid = threadIdx.x; t.lane = t.tid & 63; t.wave = t.tid >> 6;
+  t.n = t.lane & 31; t.h = t.lane >> 5;
+  t.chb = t.wave & 1; t.pxg = t.wave >> 1;
+  t.li = t.lane & 15; t.g = t.lane >> 4;
+  return t;
+}
 
-  // ---- per-workgroup constants: depthwise weights (packed T), affine tables of this image
+// STAMP = diagnostic build (llie_tune("irbx_stamp", 1) expand_dw, 3 expand_dw_project; fp16): s_memtime around the phases, summed
+// per wave into a.dbg ([workgroup][wave][kXStamps] cycles; each body lists its slots); never used in production.
+template <bool STAMP>
+struct IrbxStamps {
+  unsigned long long tk[kXStamps] = {}, t_prev = 0;
+  __device__ __forceinline__ void operator()(int slot) {
+    if constexpr (STAMP) {
+      __builtin_amdgcn_sched_barrier(0);
+      const unsigned long long now = __builtin_amdgcn_s_memtime();
+      __builtin_amdgcn_sched_barrier(0);
+      if (slot >= 0) tk[slot] += now - t_prev;
+      t_prev = now;
+    }
+  }
+  __device__ __forceinline__ void store(const IrbxArgs& a, const IrbxLane& t) {
+    if constexpr (STAMP) {
+      if (a.dbg && t.lane == 0) {
+        const size_t wg = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+#pragma unroll
+        for (int i = 0; i < kXStamps; ++i) a.dbg[(wg * 4 + t.wave) * kXStamps + i] = tk[i];
+      }
+    }
+  }
+};
+
+// ---- per-workgroup constants: depthwise weights (packed T), affine tables of this image
+// GATEW: the image's SE gate is part of the staged depthwise weights; gate_s: where it is staged as a table [Chid], or null
+template <typename T, int KS, bool GATEW>
+__device__ __forceinline__ void irbx_stage_constants(const IrbxArgs& a, const int b, const int tid, T* wds, float* aff2, float* aff1,
+                                                     float* gate_s, unsigned char* sX) {
+  constexpr int K = 16 * KS, XP = (K + 8) * 2;
   // [tap pair][channel][2]: one dword = this channel's weights of taps 2 p and 2 p + 1 (tap 9 = 0); the tile in LDS holds relu6(.) / 6
   for (int i = tid; i < 10 * a.Chid; i += 256) {
     const int t = i & 1, c = (i >> 1) % a.Chid, tap = 2 * ((i >> 1) / a.Chid) + t;
@@ -426,38 +411,68 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
     aff1[i] = a.as1[(size_t)b * K + i];      // already / 6 (GnFinalizeArgs::post_scale)
     aff1[K + i] = a.ab1[(size_t)b * K + i];
   }
-  if constexpr (PCO > 0 && !GATEW)
+  if (gate_s != nullptr)
     for (int i = tid; i < a.Chid; i += 256) gate_s[i] = a.gate[(size_t)b * a.Chid + i];
   // pixels 180..191 of the last MFMA block do not exist: their operand rows stay zero
   for (int i = tid; i < (kXNPB * 32 - kXNPX) * (XP / 16); i += 256)
     *reinterpret_cast<u32x4*>(sX + kXNPX * XP + i * 16) = u32x4{0u, 0u, 0u, 0u};
+}
 
-  const int ntiles_img = tiles_x * (a.H / kXT_H);
-  // tiles_per_wg > 0: fixed runs; <= 0: the image's tiles split evenly over the gridDim.x workgroups (knob "irbx_grid")
-  const int tile_first = tiles_per_wg > 0 ? blockIdx.x * tiles_per_wg : (int)(blockIdx.x * (unsigned)ntiles_img / gridDim.x);
-  const int tile_end = tiles_per_wg > 0 ? tile_first + tiles_per_wg : (int)((blockIdx.x + 1) * (unsigned)ntiles_img / gridDim.x);
-  const int tile_last = tile_end < ntiles_img ? tile_end : ntiles_img;
+// the workgroup's run of tiles [first, last) out of the image's `per_image`.  tiles_per_wg > 0: fixed runs; <= 0: the image's
+// tiles split evenly over the gridDim.x workgroups (knob "irbx_grid")
+struct IrbxTiles { int first, last, per_image; };
+__device__ __forceinline__ IrbxTiles irbx_tiles(const IrbxArgs& a, const int tiles_per_wg) {
+  IrbxTiles r;
+  r.per_image = (a.W / kXT_W) * (a.H / kXT_H);
+  r.first = tiles_per_wg > 0 ? blockIdx.x * tiles_per_wg : (int)(blockIdx.x * (unsigned)r.per_image / gridDim.x);
+  const int end = tiles_per_wg > 0 ? r.first + tiles_per_wg : (int)((blockIdx.x + 1) * (unsigned)r.per_image / gridDim.x);
+  r.last = end < r.per_image ? end : r.per_image;
+  return r;
+}
+// tile (ty, tx) touches the image border: its halo needs bounds checks and zero padding; interior tiles need neither
+__device__ __forceinline__ bool irbx_border(const IrbxArgs& a, int ty, int tx, int tiles_x) {
+  return ty == 0 || tx == 0 || ty == a.H / kXT_H - 1 || tx == tiles_x - 1;
+}
 
-  // x halo tile: per-thread constants of the staging -- nothing in the tile loop divides
-  const int xkv = tid % (2 * KS), xq0 = tid / (2 * KS), xk8 = xkv * 8;
-  const bool xthr = XTHR == 256 || tid < XTHR;
-  const bool xseg1 = xk8 >= a.c0;
-  const T* xb = xseg1 ? x1 + (xk8 - a.c0) : x0 + xk8;   // + pixel * xc
-  const int xc = xseg1 ? a.c1 : a.c0;
-  const bool xlast = xthr && (XPT - 1) * QSTEP + xq0 < kXNPX;   // the last pass is partial
-  int xrel[XPT];                                          // pixel offset of pass j relative to the tile's first output pixel
-#pragma unroll
-  for (int j = 0; j < XPT; ++j) {
-    const int q = xq0 + j * QSTEP;
-    xrel[j] = (q / kXH_W - 1) * a.W + (q % kXH_W - 1);
-  }
-  unsigned char* sxw = sX + xq0 * XP + xk8 * 2;
+// ---- the x halo tile: raw x of the 10 x 18 pixels in registers (`raw`), then norm1 + ReLU6 into sX as [pixel][K + 8 channels].
+// thread -> (pixel xq0, 16-byte channel vector xkv); pass j covers pixel xq0 + j * QSTEP.  The channel vector -- hence the K
+// segment, its base pointer and the norm1 table slice -- is the same in every pass and every tile.
+template <typename T, int KS>
+struct IrbxHalo {
+  static constexpr int K = 16 * KS;
+  static constexpr int XP = (K + 8) * 2;                        // sX pixel pitch in bytes (80 / 144 / 208 / 272: conflict-free ds_read_b128)
+  static constexpr int QSTEP = 256 / (2 * KS);                  // 64 / 32 / 21 pixels per pass
+  static constexpr int XTHR = QSTEP * 2 * KS;                   // threads that take part (252 of 256 at KS = 6)
+  static constexpr int XPT = (kXNPX + QSTEP - 1) / QSTEP;       // passes: 3 / 6 / 9
+  static constexpr bool PREF = KS <= 2;        // next tile's x prefetched into registers at the top of the tile
+  typedef typename Elem<T>::vec_t vec_t;
+  // per-thread constants of the staging -- nothing in the tile loop divides
+  int xq0, xk8, xc;
+  bool xthr, xlast;
+  const T* xb;       // + pixel * xc
+  int xrel[XPT];     // pixel offset of pass j relative to the tile's first output pixel
+  unsigned char* sxw;
   vec_t raw[XPT];
+
+  __device__ __forceinline__ void init(const IrbxArgs& a, const T* x0, const T* x1, unsigned char* sX, const int tid) {
+    const int xkv = tid % (2 * KS);
+    xq0 = tid / (2 * KS); xk8 = xkv * 8;
+    xthr = XTHR == 256 || tid < XTHR;
+    const bool xseg1 = xk8 >= a.c0;
+    xb = xseg1 ? x1 + (xk8 - a.c0) : x0 + xk8;
+    xc = xseg1 ? a.c1 : a.c0;
+    xlast = xthr && (XPT - 1) * QSTEP + xq0 < kXNPX;   // the last pass is partial
+#pragma unroll
+    for (int j = 0; j < XPT; ++j) {
+      const int q = xq0 + j * QSTEP;
+      xrel[j] = (q / kXH_W - 1) * a.W + (q % kXH_W - 1);
+    }
+    sxw = sX + xq0 * XP + xk8 * 2;
+  }
   // (ty, tx) = tile coordinates; interior tiles need no bounds checks
-  auto load_tile = [&](int ty, int tx) {
+  __device__ __forceinline__ void load(const IrbxArgs& a, int ty, int tx, int tiles_x) {
     const int pix0 = ty * kXT_H * a.W + tx * kXT_W;
-    const bool border = ty == 0 || tx == 0 || ty == a.H / kXT_H - 1 || tx == tiles_x - 1;
-    if (!border) {
+    if (!irbx_border(a, ty, tx, tiles_x)) {
 #pragma unroll
       for (int j = 0; j < XPT; ++j) {
         if (j < XPT - 1 ? xthr : xlast) raw[j] = ld_vec<T>(xb + (size_t)(pix0 + xrel[j]) * xc);
@@ -468,42 +483,254 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
       for (int j = 0; j < XPT; ++j) {
         const int q = xq0 + j * QSTEP;
         const int gy = ty * kXT_H - 1 + q / kXH_W, gx = tx * kXT_W - 1 + q % kXH_W;
-        // outside the image: h1 is forced to zero there (ok[] below), the value is irrelevant
+        // outside the image: h1 is forced to zero there (irbx_halo_ok), the value is irrelevant
         if ((j < XPT - 1 ? xthr : xlast) && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) raw[j] = ld_vec<T>(xb + (size_t)(pix0 + xrel[j]) * xc);
         else raw[j] = vec_t{};
       }
     }
-  };
-  int ty = tile_first / tiles_x, tx = tile_first % tiles_x;   // the only division: once per workgroup
-  if (PREF && tile_first < tile_last) load_tile(ty, tx);
-  // weight slices (A operand) of the chunk about to run.  They are always fetched one depthwise phase ahead and BEFORE
-  // that phase's stores: the wait in front of the MFMAs then leaves the (younger) stores in flight instead of draining them.
-  vec_t wf[KS];
-  auto load_wf = [&](int chunk) {
+  }
+  // a' = relu6(norm1(raw)) / 6 into sX; aff1 = the image's norm1 table [2][K]
+  __device__ __forceinline__ void activate(const float* aff1) {
 #pragma unroll
-    for (int s = 0; s < KS; ++s) wf[s] = ld_vec<T>(w1 + (size_t)(chunk * 64 + chb * 32 + n) * K + 16 * s + 8 * h);
+    for (int j = 0; j < XPT; ++j) {
+      if (j < XPT - 1 ? xthr : xlast)
+        *reinterpret_cast<vec_t*>(sxw + j * QSTEP * XP) = activate8<T>(raw[j], aff1 + xk8, aff1 + K + xk8);
+    }
+  }
+};
+// validity of this lane's three halo pixels (zero padding of the depthwise input): border tiles only
+__device__ __forceinline__ void irbx_halo_ok(const IrbxArgs& a, const IrbxLane& t, const bool border, const int y0, const int x0p, bool (&ok)[3]) {
+  ok[0] = ok[1] = ok[2] = true;
+  if (border) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int q = (t.pxg * 3 + i) * 32 + t.n;
+      const int gy = y0 - 1 + q / kXH_W, gx = x0p - 1 + q % kXH_W;
+      ok[i] = q < kXNPX && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+    }
+  }
+}
+
+// ---- the expand phase of one 64-channel chunk: h1^T block (32 channels x 32 pixels) x 3 pixel blocks per wave, from sX into the
+// h1 tile.  Weight slices (A operand) of a chunk.  They are always fetched one depthwise phase ahead and BEFORE that phase's stores: the
+// wait in front of the MFMAs then leaves the (younger) stores in flight instead of draining them.
+template <typename T, int KS>
+__device__ __forceinline__ void irbx_load_wf(typename Elem<T>::vec_t (&wf)[KS], const T* w1, const int chunk, const IrbxLane& t) {
+  constexpr int K = 16 * KS;
+#pragma unroll
+  for (int s = 0; s < KS; ++s) wf[s] = ld_vec<T>(w1 + (size_t)(chunk * 64 + t.chb * 32 + t.n) * K + 16 * s + 8 * t.h);
+}
+// epilogue of one 32-channel x 32-pixel accumulator block of the expand phase: aff2 + ReLU6, zero outside the image (the conv's
+// padding), pack, exchange lane halves so that each lane owns 8 consecutive channels, two ds_write_b128 at dst (+ 16).
+// (The MFMAs in front of it are written out in both kernel bodies: as one function with this epilogue they cost
+// expand_dw_project_kernel<T, 2, 32>, which sits at its 168 registers, two spilled registers (8 bytes of scratch).)
+template <typename T>
+__device__ __forceinline__ void irbx_expand_store(const f32x16& acc, const f32x4 (&sc2)[4], const f32x4 (&sh2)[4], const bool border, const bool ok,
+                                                  unsigned char* dst) {
+  uint32_t pk[4][2];
+#pragma unroll
+  for (int g = 0; g < 4; ++g)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      pk[g][j] = affine_clamp01_pack<T>(acc[4 * g + 2 * j], acc[4 * g + 2 * j + 1], sc2[g][2 * j], sc2[g][2 * j + 1],
+                                        sh2[g][2 * j], sh2[g][2 * j + 1]);
+  if (border) {  // tiles on the image border: zero padding of the depthwise input (uniform branch, most tiles skip it)
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) pk[g][j] = ok ? pk[g][j] : 0u;
+  }
+  u32x4 lo, hi2;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const u32x2 r02 = __builtin_amdgcn_permlane32_swap(pk[0][j], pk[2][j], false, false);
+    const u32x2 r13 = __builtin_amdgcn_permlane32_swap(pk[1][j], pk[3][j], false, false);
+    lo[j] = r02[0]; lo[2 + j] = r02[1];    // h=0: channels 0..7 of the block; h=1: channels 16..23
+    hi2[j] = r13[0]; hi2[2 + j] = r13[1];  // h=0: channels 8..15;             h=1: channels 24..31
+  }
+  *reinterpret_cast<u32x4*>(dst) = lo;
+  *reinterpret_cast<u32x4*>(dst + 16) = hi2;
+}
+
+// ---- depthwise 3x3 on the MFMA pipe.  The VALU is what these kernels run out of (a wave64 instruction costs a SIMD
+// 4 cycles; 72 FMAs per 16 output bytes), the matrix pipe idles.  A depthwise tap is a diagonal matrix:
+//   out[ch][px] += sum_k diag(w_tap)[ch][k] * in[k][px + tap]      (k over the block's channels, 16 per tap)
+// the data operand is one ds_read_b128 per MFMA (lane = pixel, 8 channels), the weight operand this lane's weight
+// masked into its diagonal position (4 v_and per step).  A few per cent of the MACs are useful, which still equals
+// the VALU's rate -- on a pipe that was idle, for a quarter of the VALU instructions.
+// Two taps per 16x16x32 MFMA: D[16 ch][16 px] += A[16 ch][k] B[k][16 px], k = 16 t + c (tap slot t, channel c of the
+// 16-channel tile), in this order of k: lane (li = lane & 15, g = lane >> 4) holds k-slice g = tap slot g & 1, channels 8 (g >> 1) + j.
+//   B: lane = output pixel li of one tile row; its 8 channels of the halo pixel under tap slot g & 1: ONE ds_read_b128,
+//      address = row base + this lane's tap offset (odd and even lane quarters read different taps)
+//   A: lane = channel li of the tile; its weight of tap slot g & 1 at element li & 7 if (g >> 1) == li >> 3, else 0
+// (k = 16 t + c in MFMA order would put the channel half in g & 1: the 16-lane groups of a ds_read_b128 -- {0-3, 12-15,
+// 20-27}, ... -- would then mix 8 pixels at channel slot s with 8 at slot s + 1 and collide two-way on the 144-byte
+// pitch.  With the tap in g & 1 a group reads 16 pixels of ONE slot, 8 of them shifted by the tap distance (1 or 16
+// pixels; equal addresses broadcast): conflict-free, 4 instead of 8 LDS cycles for each of the reads.)
+// One data operand per MFMA, 640 matrix-pipe cycles per 64-channel chunk and wave (one tap per 32x32x16 MFMA, round 2's form,
+// took 1 152).
+// A wave owns ROWS output rows (ROWS pixel tiles) x CT 16-channel tiles, ROWS x CT = 8 accumulator tiles of 4 registers:
+// 5 tap pairs (the last one half empty) x CT steps of ROWS MFMAs = 40 MFMAs of 16 cycles.  expand_dw: (4, 2), a channel half of
+// the chunk (its body holds that instance written out, see there); the project tail: (2, 4), all 64 channels.
+// The caller names its share: row group rg = rows ROWS rg .. of the tile, channel half = tiles CT half .. of the chunk; buf is the
+// h1 tile in LDS, wds the staged weight pairs.
+//   bbase = the lane's pixel li of the wave's first halo row in the h1 tile, at its 16-byte slot (g >> 1) of the first channel tile
+//   wpair = the lane's channel li of the first tile in the staged weight pairs
+// dacc[c][r]: lane (pixel li of row r, g): channels 16 c + 4 g + e.
+template <typename T, int ROWS, int CT>
+__device__ __forceinline__ void irbx_dw_two_tap(f32x4 (&dacc)[CT][ROWS], const unsigned char* buf, const int rg, const int half, const T* wds,
+                                                const int chunk, const int Chid, const IrbxLane& t) {
+  typedef typename Elem<T>::vec_t vec_t;
+  const int li = t.li, g = t.g;
+  uint32_t amask[4];
+#pragma unroll
+  for (int d = 0; d < 4; ++d)
+    amask[d] = (((li & 7) >> 1) == d && (g >> 1) == (li >> 3)) ? ((li & 1) ? 0xFFFF0000u : 0x0000FFFFu) : 0u;
+  const uint32_t* wpair = reinterpret_cast<const uint32_t*>(wds) + chunk * 64 + half * (16 * CT) + li;  // + (pair * Chid + 16 c)
+  const uint32_t wsel = (g & 1) ? 0x03020302u : 0x01000100u;  // v_perm_b32 selector: this lane quarter's tap, duplicated
+#pragma unroll
+  for (int c = 0; c < CT; ++c)
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) dacc[c][r] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const unsigned char* bbase = buf + ((ROWS * rg) * kXH_W + li) * SHP + (half * (2 * CT) + (g >> 1)) * 16;
+  const bool upper = (g & 1) != 0;
+  vec_t bf[2][ROWS];
+  uint32_t wq[2];
+  auto ld_step = [&](int step, vec_t (&bb)[ROWS], uint32_t& w2) {  // step = CT * pair + c
+    const int pr = step / CT, c = step % CT;
+    const int ta = 2 * pr, tb = 2 * pr + 1 < 9 ? 2 * pr + 1 : 8;
+    const int offa = (ta / 3) * kXH_W + ta % 3, offb = (tb / 3) * kXH_W + tb % 3;
+    const unsigned char* p0 = bbase + (upper ? offb : offa) * SHP + c * 32;
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) bb[r] = *reinterpret_cast<const vec_t*>(p0 + r * kXH_W * SHP);
+    w2 = wpair[pr * Chid + 16 * c];
   };
-  load_wf(chunk0);
+  ld_step(0, bf[0], wq[0]);
+#pragma unroll
+  for (int step = 0; step < 5 * CT; ++step) {
+    if (step + 1 < 5 * CT) ld_step(step + 1, bf[(step + 1) & 1], wq[(step + 1) & 1]);
+    __builtin_amdgcn_sched_barrier(0);  // keep the look-ahead reads above this step's MFMAs
+    const int c = step % CT;
+    const uint32_t wdup = __builtin_amdgcn_perm(wq[step & 1], wq[step & 1], wsel);
+    u32x4 m;
+#pragma unroll
+    for (int d = 0; d < 4; ++d) m[d] = wdup & amask[d];
+    const vec_t af = reinterpret_cast<const vec_t&>(m);
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) dacc[c][r] = mfma16x16<T>(af, bf[step & 1][r], dacc[c][r]);
+  }
+}
+
+// Two accumulator quads of one pixel -- lane (li, g): channels 4 g + e of 16-channel tiles c0 and c0 + 1 -- rounded to T and
+// packed (p0, p1: two dwords each), then v_permlane16_swap between the two tiles gives every lane 8 consecutive channels of its
+// pixel: even g: 4 g .. 4 g + 7, odd g: 16 + 4 (g - 1) .. 16 + 4 g + 3, i.e. channels irbx_choff(g) .. + 7 of the 32
+__device__ __forceinline__ u32x4 irbx_swap8(const uint32_t (&p0)[2], const uint32_t (&p1)[2]) {
+  const u32x2 s0 = __builtin_amdgcn_permlane16_swap(p0[0], p1[0], false, false);
+  const u32x2 s1 = __builtin_amdgcn_permlane16_swap(p0[1], p1[1], false, false);
+  return u32x4{s0[0], s1[0], s0[1], s1[1]};
+}
+template <typename T>
+__device__ __forceinline__ u32x4 irbx_pack8_swap(const f32x4& q0, const f32x4& q1) {
+  uint32_t p0[2], p1[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    typedef T t2 __attribute__((ext_vector_type(2)));
+    t2 o0, o1;
+    o0[0] = (T)q0[2 * j]; o0[1] = (T)q0[2 * j + 1];
+    o1[0] = (T)q1[2 * j]; o1[1] = (T)q1[2 * j + 1];
+    p0[j] = *reinterpret_cast<uint32_t*>(&o0);
+    p1[j] = *reinterpret_cast<uint32_t*>(&o1);
+  }
+  return irbx_swap8(p0, p1);
+}
+__device__ __forceinline__ int irbx_choff(int g) { return 8 * (g >> 1) + 16 * (g & 1); }
+
+// SE pool partial of expand_dw: channel sums over the wave's 64 pixels -- the 4 rows in registers, then the 16 pixel lanes of a row
+// by DPP -- left by lane li = 0 of every row at red4 (its channels 4 g + e of the wave's two tiles)
+__device__ __forceinline__ void irbx_pool_partial(const f32x4 (&dacc)[2][4], const int li, float* red4) {
+  float v[8];
+#pragma unroll
+  for (int c2 = 0; c2 < 2; ++c2)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[4 * c2 + e] = (dacc[c2][0][e] + dacc[c2][1][e]) + (dacc[c2][2][e] + dacc[c2][3][e]);
+  // v += rotate(v) inside each 16-lane row, as ONE v_add_f32 with a DPP source per step (through
+  // __builtin_amdgcn_update_dpp hipcc emits v_mov 0 + v_mov_dpp + add: 92 instructions for this reduction instead
+  // of 32).  The eight values are stepped together, so a register written by one statement is read again eight
+  // statements later: the VALU-write -> DPP-read hazard (2 wait states) needs no s_nop inside the strings.
+#define LLIE_DPP_STEP(ROR)                                                                                               \
+  _Pragma("unroll") for (int i = 0; i < 8; ++i)                                                                          \
+      asm volatile("v_add_f32_dpp %0, %0, %0 row_ror:" #ROR " row_mask:0xf bank_mask:0xf" : "+v"(v[i]));
+  // the sums just written by ordinary VALU adds: 2 wait states before the first DPP read.  The eight values are operands of
+  // the statement, so every add that produces them is scheduled ABOVE the nop (a bare volatile asm orders only against
+  // other side effects, and hipcc's hazard recognizer does not look inside inline asm for the DPP read).
+  asm volatile("s_nop 1" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
+  LLIE_DPP_STEP(8)
+  LLIE_DPP_STEP(4)
+  LLIE_DPP_STEP(2)
+  LLIE_DPP_STEP(1)
+#undef LLIE_DPP_STEP
+  if (li == 0) {  // channels 16 c2 + 4 g + e of the wave's block
+    float* rp = red4;
+    *reinterpret_cast<f32x4*>(rp) = f32x4{v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f32x4*>(rp + 16) = f32x4{v[4], v[5], v[6], v[7]};
+  }
+}
+
+// ---- expand_dw: h2 to HBM + SE pool partials.  DBUF: the h1 tile and `red` are double-buffered (one barrier per chunk);
+// NTST = h2 leaves with non-temporal stores (IrbxArgs::nt).
+// STAMP slots: 0 wait for the prefetched / loaded x tile (vmcnt), 1 activate + ds_write of the x tile, 2 next tile's loads issued
+// + halo validity, 3 tile-top barrier, 4 pool flush behind it, 5 chunk-top barrier + flush (chunks after the first), 6 expand
+// MFMAs + epilogue + ds_write, 7 barrier behind them, 8 depthwise phase incl. the h2 stores and the pool partial.
+template <typename T, int KS, bool DBUF, bool STAMP, bool NTST>
+__device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tiles_per_wg, const int chunks_per_wg) {
+  constexpr int SH_BYTES = kXNPB * 32 * SHP;
+  typedef typename Elem<T>::vec_t vec_t;
+  typedef IrbxHalo<T, KS> Halo;
+  extern __shared__ __align__(16) unsigned char smem[];
+  const IrbxLds lds = irbx_lds(KS, a.Chid, DBUF, 0);
+  unsigned char* sH = smem;
+  unsigned char* sX = smem + lds.sX;
+  T* wds = reinterpret_cast<T*>(smem + lds.wds);
+  float* aff2 = reinterpret_cast<float*>(smem + lds.aff2);
+  float* aff1 = reinterpret_cast<float*>(smem + lds.aff1);
+  float* red = reinterpret_cast<float*>(smem + lds.red);
+  // fixed-point pool totals of this workgroup's tiles, [chunk][channel 64]: in LDS rather than in 2 KS registers of every
+  // thread -- this kernel sits exactly at an occupancy step, and a spilled register costs more than its scratch access:
+  // every reload is a vector-memory operation whose wait (vmcnt is in order) also waits for the h2 stores in flight
+  // (KS = 6 keeps them in registers: its 79 KB of LDS are two workgroups per CU only as long as nothing is added)
+  constexpr bool PACC_LDS = KS <= 4;
+  long long* pacc_lds = reinterpret_cast<long long*>(smem + lds.tail);
+  long long pacc_reg[PACC_LDS ? 1 : KS];
+
+  const IrbxLane t = irbx_lane();
+  const int tid = t.tid, n = t.n, h = t.h, chb = t.chb, pxg = t.pxg, li = t.li, g = t.g;
+  const int b = blockIdx.z;
+  const int tiles_x = a.W / kXT_W;
+  const int P = a.H * a.W;
+  const T* x0 = reinterpret_cast<const T*>(a.x0) + (size_t)b * P * a.c0;
+  const T* x1 = a.x1 ? reinterpret_cast<const T*>(a.x1) + (size_t)b * P * a.c1 : nullptr;
+  const T* w1 = reinterpret_cast<const T*>(a.w1);
+  T* out = reinterpret_cast<T*>(a.out) + (size_t)b * P * a.Chid;
+  const int chunk0 = blockIdx.y * chunks_per_wg;
+  const int nchunks_all = a.Chid / 64;
+  const int chunk1 = chunk0 + chunks_per_wg < nchunks_all ? chunk0 + chunks_per_wg : nchunks_all;
+
+  irbx_stage_constants<T, KS, false>(a, b, tid, wds, aff2, aff1, nullptr, sX);
+  const IrbxTiles run = irbx_tiles(a, tiles_per_wg);
+  Halo halo;
+  halo.init(a, x0, x1, sX, tid);
+  int ty = run.first / tiles_x, tx = run.first % tiles_x;   // the only division: once per workgroup
+  if (Halo::PREF && run.first < run.last) halo.load(a, ty, tx, tiles_x);
+  vec_t wf[KS];
+  irbx_load_wf<T, KS>(wf, w1, chunk0, t);
   wg_barrier();  // constants staged
 
-  unsigned long long tk[kXStamps] = {}, t_prev = 0;
-  auto stamp_at = [&](int slot) {
-    if constexpr (STAMP) {
-      __builtin_amdgcn_sched_barrier(0);
-      const unsigned long long now = __builtin_amdgcn_s_memtime();
-      __builtin_amdgcn_sched_barrier(0);
-      if (slot >= 0) tk[slot] += now - t_prev;
-      t_prev = now;
-    }
-  };
-  auto stamp = [&](int slot) { if constexpr (PCO == 0) stamp_at(slot); };   // the slots of expand_dw
-  auto pstamp = [&](int slot) { if constexpr (PCO > 0) stamp_at(slot); };   // the slots of expand_dw_project
-  stamp_at(-1);
-  const bool has_pool = PCO == 0 && (a.pool != nullptr || a.pool_tot != nullptr);
+  IrbxStamps<STAMP> stamp;
+  stamp(-1);
+  const bool has_pool = a.pool != nullptr || a.pool_tot != nullptr;
   int par = 0;  // sH / red buffer parity (DBUF)
   int pend_tile = -1, pend_chunk = 0, pend_par = 0;  // pool partial waiting for its cross-wave sum
-  if constexpr (PCO > 0) {
-  } else if constexpr (PACC_LDS) {
+  if constexpr (PACC_LDS) {
     if (tid < 64) {  // threads 0..63 own channel tid of every chunk (Chid / 64 = KS chunks at most); only they touch it
 #pragma unroll
       for (int q = 0; q < KS; ++q) pacc_lds[q * 64 + tid] = 0;
@@ -513,21 +740,12 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
     for (int q = 0; q < KS; ++q) pacc_reg[q] = 0;
   }
   auto flush_pool = [&]() {  // after a barrier that follows the depthwise phase which wrote red[pend_par]
-    if constexpr (PCO > 0) {
-      // y's statistics of the tile before: the four waves' (sum, sum of squares) [wave][2][PCO], added in wave order
-      if (pend_tile >= 0 && tid < 2 * PCO) {
-        const float t = (red[tid] + red[2 * PCO + tid]) + (red[4 * PCO + tid] + red[6 * PCO + tid]);
-        a.ystats[((size_t)b * ntiles_img + pend_tile) * 2 * PCO + tid] = t;
-      }
-      pend_tile = -1;
-      return;
-    }
     if (pend_tile >= 0 && tid < 64) {
       const float* r = red + pend_par * 256;  // wave (chb, pxg) = chb + 2 pxg left its 32 channel sums at [wave * 64 + channel]
       const int cbb = tid >> 5, ci = tid & 31;
-      const float t = r[cbb * 64 + ci] + r[(cbb + 2) * 64 + ci];
+      const float s = r[cbb * 64 + ci] + r[(cbb + 2) * 64 + ci];
       if (a.pool_tot) {  // fixed-point, summed over this workgroup's tiles in registers: one global atomic per chunk at the end
-        const long long v = __float2ll_rn(t * kPoolFixScale);
+        const long long v = __float2ll_rn(s * kPoolFixScale);
         if constexpr (PACC_LDS) {
           pacc_lds[(pend_chunk - chunk0) * 64 + tid] += v;
         } else {
@@ -535,117 +753,46 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
           for (int q = 0; q < KS; ++q) pacc_reg[q] += (pend_chunk - chunk0 == q) ? v : 0ll;
         }
       } else {
-        a.pool[((size_t)b * ntiles_img + pend_tile) * a.Chid + pend_chunk * 64 + tid] = t;
+        a.pool[((size_t)b * run.per_image + pend_tile) * a.Chid + pend_chunk * 64 + tid] = s;
       }
     }
     pend_tile = -1;
   };
 
-  for (int tile = tile_first; tile < tile_last; ++tile) {
+  for (int tile = run.first; tile < run.last; ++tile) {
     const int y0 = ty * kXT_H, x0p = tx * kXT_W;
     int tyn = ty, txn = tx + 1;  // the next tile of the run
     if (txn == tiles_x) { txn = 0; ++tyn; }
     // ---- activate this tile's x (norm1 + ReLU6) into sX, prefetch the next tile.  Every wave is past the last
     // MFMA phase of the previous tile here (the barrier that follows it), so sX is free.
-    if (!PREF) load_tile(ty, tx);
+    if (!Halo::PREF) halo.load(a, ty, tx, tiles_x);
     // Every vector-memory operation so far has to be complete here anyway (raw[] below is older than all of them), but the
     // compiler's wait sits inside the predicated block below; said unconditionally, the chunk loop is entered with nothing
     // pending, and the wait for the prefetched weight slices at its head becomes vmcnt(4 + ...) -- the depthwise phase's four
     // h2 stores stay in flight -- instead of the vmcnt(0) that the merge with this path forced.
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
     stamp(0);
-    pstamp(0);
-#pragma unroll
-    for (int j = 0; j < XPT; ++j) {
-      if (j < XPT - 1 ? xthr : xlast)
-        *reinterpret_cast<vec_t*>(sxw + j * QSTEP * XP) = activate8<T>(raw[j], aff1 + xk8, aff1 + K + xk8);
-    }
+    halo.activate(aff1);
     stamp(1);
-    // PCO: the shortcut's operands, for the wave's 2 rows x 16 pixels (lane = pixel li, quarter g): the raw x of the centre pixels,
-    // rows 16 cb + 4 g + e of every block cb (identity form), or the K / 32 k-steps of the skip conv -- k-step ks covers input
-    // channels 32 ks .. 32 ks + 31, lane (li, g) holds channels 32 ks + 8 g .. + 7 of row 16 cb + li of Wskip (A) and of pixel li
-    // of the row (B); a 16-byte vector never straddles the segments (c0 % 16 == 0).  The tile's own loads have left x in L2.  They
-    // go out here, ahead of the next tile's prefetch, and become the start of the y accumulators behind the tile-top barrier; the
-    // staging registers (raw) are free by now.  (vmcnt counts in order, so the wait for them could leave the prefetch in flight;
-    // hipcc's does not -- the prefetch loads are lane-predicated, it assumes none was issued and waits vmcnt(0) for the last
-    // shortcut register: profiles/r20/README.md, section 1.)
-    constexpr int NCB = PCO > 0 ? PCO / 16 : 1;  // 16-row blocks of Wp
-    constexpr int NKS = PSKIP ? K / 32 : 1;
-    typedef T t4 __attribute__((ext_vector_type(4)));
-    t4 res[2][NCB];
-    vec_t wsf[NKS][NCB], xsv[NKS][2];
-    if constexpr (PCO > 0) {
-      const int li = lane & 15, g = lane >> 4;
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const size_t pix = (size_t)(y0 + 2 * wave + r) * a.W + x0p + li;
-        if constexpr (!PSKIP) {
-#pragma unroll
-          for (int cb = 0; cb < NCB; ++cb) res[r][cb] = *reinterpret_cast<const t4*>(x0 + pix * PCO + 16 * cb + 4 * g);
-        } else {
-#pragma unroll
-          for (int ks = 0; ks < NKS; ++ks) {
-            const int ch = 32 * ks + 8 * g;
-            xsv[ks][r] = ch < a.c0 ? ld_vec<T>(x0 + pix * a.c0 + ch) : ld_vec<T>(x1 + pix * a.c1 + (ch - a.c0));
-          }
-        }
-      }
-      if constexpr (PSKIP) {
-        const T* wsk = reinterpret_cast<const T*>(a.wp) + (size_t)li * a.ldp + a.Chid + 8 * g;
-#pragma unroll
-        for (int ks = 0; ks < NKS; ++ks)
-#pragma unroll
-          for (int cb = 0; cb < NCB; ++cb) wsf[ks][cb] = ld_vec<T>(wsk + (size_t)cb * 16 * a.ldp + 32 * ks);
-      }
-    }
-    if (PREF && tile + 1 < tile_last) load_tile(tyn, txn);
-    // validity of this lane's three halo pixels (zero padding of the depthwise input): border tiles only
-    const bool border = ty == 0 || tx == 0 || ty == a.H / kXT_H - 1 || tx == tiles_x - 1;
-    bool ok[3] = {true, true, true};
-    if (border) {
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const int q = (pxg * 3 + i) * 32 + n;
-        const int gy = y0 - 1 + q / kXH_W, gx = x0p - 1 + q % kXH_W;
-        ok[i] = q < kXNPX && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-      }
-    }
+    if (Halo::PREF && tile + 1 < run.last) halo.load(a, tyn, txn, tiles_x);
+    const bool border = irbx_border(a, ty, tx, tiles_x);
+    bool ok[3];
+    irbx_halo_ok(a, t, border, y0, x0p, ok);
     stamp(2);
-    pstamp(1);
     wg_barrier();
     stamp(3);
     if (!DBUF) flush_pool();
     stamp(4);
-
-    typedef float f32x4v __attribute__((ext_vector_type(4)));
-    // y[32 pixels][PCO] of the wave starts as its shortcut: raw x (identity form), Wskip . x (skip form)
-    f32x4v yacc[2][NCB];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int cb = 0; cb < NCB; ++cb) {
-        if constexpr (PCO > 0 && !PSKIP) yacc[r][cb] = f32x4v{(float)res[r][cb][0], (float)res[r][cb][1], (float)res[r][cb][2], (float)res[r][cb][3]};
-        else yacc[r][cb] = f32x4v{0.f, 0.f, 0.f, 0.f};
-      }
-    if constexpr (PSKIP) {
-#pragma unroll
-      for (int ks = 0; ks < NKS; ++ks)
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-          for (int cb = 0; cb < NCB; ++cb) yacc[r][cb] = mfma16x16<T>(wsf[ks][cb], xsv[ks][r], yacc[r][cb]);
-    }
-    pstamp(2);
     // (Unrolling this loop lets hipcc count the memory operations between a prefetch and its use -- vmcnt(5) instead of
     // vmcnt(2) for the weight slices -- but costs 11 spilled registers, and every spill reload waits vmcnt(0), i.e. for the
     // h2 stores in flight: 35.7 vs 34.7 ms per step.  The run-time loop stays.)
+#pragma unroll 1
     for (int chunk = chunk0; chunk < chunk1; ++chunk) {
       unsigned char* buf = sH + (DBUF ? par * SH_BYTES : 0);
       if (!DBUF && chunk > chunk0) {
         wg_barrier();  // previous depthwise phase done with sH
         flush_pool();
         stamp(5);
-        pstamp(3);
       }
       // ---- MFMA: h1^T block (32 channels x 32 pixels) x 3 pixel blocks
       const int ch0 = chunk * 64 + chb * 32;
@@ -656,9 +803,8 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
         sc2[g] = *reinterpret_cast<const f32x4*>(aff2 + ch0 + 8 * g + 4 * h);
         sh2[g] = *reinterpret_cast<const f32x4*>(aff2 + a.Chid + ch0 + 8 * g + 4 * h);
       }
-      // accumulators in flight: all three pixel blocks, or one at a time (registers; the identity tail at 32 channels fits three
-      // workgroups per CU that way)
-      constexpr int NACC = (KS <= 2 && PCO == 0) ? 3 : 1;
+      // accumulators in flight: all three pixel blocks, or one at a time (registers)
+      constexpr int NACC = KS <= 2 ? 3 : 1;
       f32x16 accs[NACC];
       if constexpr (NACC == 3) {
 #pragma unroll
@@ -668,9 +814,9 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
           for (int r = 0; r < 16; ++r) accs[i][r] = 0.f;
 #pragma unroll
           for (int s = 0; s < KS; ++s)
-            accs[i] = mfma16<T>(wf[s], *reinterpret_cast<const vec_t*>(sX + q * XP + (16 * s + 8 * h) * 2), accs[i]);
+            accs[i] = mfma16<T>(wf[s], *reinterpret_cast<const vec_t*>(sX + q * Halo::XP + (16 * s + 8 * h) * 2), accs[i]);
         }
-        load_wf(chunk + 1 < chunk1 ? chunk + 1 : chunk0);  // next chunk (or the next tile's first): see above
+        irbx_load_wf<T, KS>(wf, w1, chunk + 1 < chunk1 ? chunk + 1 : chunk0, t);  // next chunk (or the next tile's first): see irbx_load_wf
       }
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
@@ -680,335 +826,76 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
           for (int r = 0; r < 16; ++r) accs[0][r] = 0.f;
 #pragma unroll
           for (int s = 0; s < KS; ++s)
-            accs[0] = mfma16<T>(wf[s], *reinterpret_cast<const vec_t*>(sX + q * XP + (16 * s + 8 * h) * 2), accs[0]);
-          if (i == 2) load_wf(chunk + 1 < chunk1 ? chunk + 1 : chunk0);
+            accs[0] = mfma16<T>(wf[s], *reinterpret_cast<const vec_t*>(sX + q * Halo::XP + (16 * s + 8 * h) * 2), accs[0]);
+          if (i == 2) irbx_load_wf<T, KS>(wf, w1, chunk + 1 < chunk1 ? chunk + 1 : chunk0, t);
         }
         const f32x16 acc = accs[NACC == 3 ? i : 0];
-        // epilogue: aff2 + ReLU6, zero outside the image (the conv's padding), pack, exchange lane halves so
-        // that each lane owns 8 consecutive channels, two ds_write_b128
-        uint32_t pk[4][2];
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            pk[g][j] = affine_clamp01_pack<T>(acc[4 * g + 2 * j], acc[4 * g + 2 * j + 1], sc2[g][2 * j], sc2[g][2 * j + 1],
-                                              sh2[g][2 * j], sh2[g][2 * j + 1]);
-        if (border) {  // tiles on the image border: zero padding of the depthwise input (uniform branch, most tiles skip it)
-#pragma unroll
-          for (int g = 0; g < 4; ++g)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) pk[g][j] = ok[i] ? pk[g][j] : 0u;
-        }
-        u32x4 lo, hi2;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const u32x2 r02 = __builtin_amdgcn_permlane32_swap(pk[0][j], pk[2][j], false, false);
-          const u32x2 r13 = __builtin_amdgcn_permlane32_swap(pk[1][j], pk[3][j], false, false);
-          lo[j] = r02[0]; lo[2 + j] = r02[1];    // h=0: channels 0..7 of the block; h=1: channels 16..23
-          hi2[j] = r13[0]; hi2[2 + j] = r13[1];  // h=0: channels 8..15;             h=1: channels 24..31
-        }
-        *reinterpret_cast<u32x4*>(buf + q * SHP + (chb * 4 + 2 * h) * 16) = lo;
-        *reinterpret_cast<u32x4*>(buf + q * SHP + (chb * 4 + 2 * h + 1) * 16) = hi2;
+        irbx_expand_store<T>(acc, sc2, sh2, border, ok[i], buf + q * SHP + (chb * 4 + 2 * h) * 16);
       }
       stamp(6);
-      pstamp(4);
       wg_barrier();
       if (DBUF) flush_pool();
       stamp(7);
-      pstamp(5);
-      // ---- depthwise 3x3 on the MFMA pipe.  The VALU is what this kernel runs out of (a wave64 instruction costs a SIMD
-      // 4 cycles; 72 FMAs per 16 output bytes), the matrix pipe idles.  A depthwise tap is a diagonal matrix:
-      //   out[ch][px] += sum_k diag(w_tap)[ch][k] * in[k][px + tap]      (k over the block's channels, 16 per tap)
-      // the data operand is one ds_read_b128 per MFMA (lane = pixel, 8 channels), the weight operand this lane's weight
-      // masked into its diagonal position (4 v_and per step).  A few per cent of the MACs are useful, which still equals
-      // the VALU's rate -- on a pipe that was idle, for a quarter of the VALU instructions.
-      if constexpr (PCO > 0) {
-        // ---- the same two-tap MFMAs with the wave's share turned: rows 2 wave, 2 wave + 1 of the tile x the chunk's four
-        // 16-channel tiles (20 steps of 2 MFMAs; operand reads and LDS addressing per instruction are those of the block below)
-        const int li = lane & 15, g = lane >> 4;
-        uint32_t amask[4];
+      // ---- depthwise (irbx_dw_two_tap explains it): the wave's 32 channels (2 tiles) x its 4 output rows.  Written out here:
+      // irbx_dw_two_tap<T, 4, 2> is the same IR in another order, and hipcc's schedule of this kernel then takes 168 registers
+      // instead of 165 at 32 channels -- all that three workgroups per CU allow -- and 207 instead of 198 at 96.
+      uint32_t amask[4];
 #pragma unroll
-        for (int d = 0; d < 4; ++d)
-          amask[d] = (((li & 7) >> 1) == d && (g >> 1) == (li >> 3)) ? ((li & 1) ? 0xFFFF0000u : 0x0000FFFFu) : 0u;
-        const uint32_t* wpair = reinterpret_cast<const uint32_t*>(wds) + chunk * 64 + li;  // + (pair * Chid + 16 c)
-        const uint32_t wsel = (g & 1) ? 0x03020302u : 0x01000100u;
-        const int choff = 8 * (g >> 1) + 16 * (g & 1);  // the lane's 8 channels of a 32-channel half after the swap below
-        // Wp fragments of this chunk: rows 16 cb + li, k = the lane's 8 channels of half kb -- in flight under the depthwise steps
-        vec_t wpf[NCB][2];
-        const T* wp = reinterpret_cast<const T*>(a.wp) + (size_t)li * a.ldp + chunk * 64 + choff;
+      for (int d = 0; d < 4; ++d)
+        amask[d] = (((li & 7) >> 1) == d && (g >> 1) == (li >> 3)) ? ((li & 1) ? 0xFFFF0000u : 0x0000FFFFu) : 0u;
+      const uint32_t* wpair = reinterpret_cast<const uint32_t*>(wds) + chunk * 64 + chb * 32 + li;  // + (pair * Chid + 16 c2)
+      const uint32_t wsel = (g & 1) ? 0x03020302u : 0x01000100u;  // v_perm_b32 selector: this lane quarter's tap, duplicated
+      f32x4 dacc[2][4];
 #pragma unroll
-        for (int cb = 0; cb < NCB; ++cb)
+      for (int c2 = 0; c2 < 2; ++c2)
 #pragma unroll
-          for (int kb = 0; kb < 2; ++kb) wpf[cb][kb] = ld_vec<T>(wp + (size_t)cb * 16 * a.ldp + 32 * kb);
-        f32x4v dacc[4][2];
+        for (int r = 0; r < 4; ++r) dacc[c2][r] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const unsigned char* bbase = buf + ((4 * pxg) * kXH_W + li) * SHP + (chb * 4 + (g >> 1)) * 16;
+      const bool upper = (g & 1) != 0;
+      vec_t bf[2][4];
+      uint32_t wq[2];
+      auto ld_step = [&](int step, vec_t (&bb)[4], uint32_t& w2) {  // step = 2 * pair + c2
+        const int pr = step >> 1, c2 = step & 1;
+        const int ta = 2 * pr, tb = 2 * pr + 1 < 9 ? 2 * pr + 1 : 8;
+        const int offa = (ta / 3) * kXH_W + ta % 3, offb = (tb / 3) * kXH_W + tb % 3;
+        const unsigned char* p0 = bbase + (upper ? offb : offa) * SHP + c2 * 32;
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
+        for (int r = 0; r < 4; ++r) bb[r] = *reinterpret_cast<const vec_t*>(p0 + r * kXH_W * SHP);
+        w2 = wpair[pr * a.Chid + 16 * c2];
+      };
+      ld_step(0, bf[0], wq[0]);
 #pragma unroll
-          for (int r = 0; r < 2; ++r) dacc[c][r] = f32x4v{0.f, 0.f, 0.f, 0.f};
-        const unsigned char* bbase = buf + ((2 * wave) * kXH_W + li) * SHP + (g >> 1) * 16;
-        const bool upper = (g & 1) != 0;
-        vec_t bf[2][2];
-        uint32_t wq[2];
-        auto ld_step = [&](int step, vec_t (&bb)[2], uint32_t& w2) {  // step = 4 * pair + c
-          const int pr = step >> 2, c = step & 3;
-          const int ta = 2 * pr, tb = 2 * pr + 1 < 9 ? 2 * pr + 1 : 8;
-          const int offa = (ta / 3) * kXH_W + ta % 3, offb = (tb / 3) * kXH_W + tb % 3;
-          const unsigned char* p0 = bbase + (upper ? offb : offa) * SHP + c * 32;
+      for (int step = 0; step < 10; ++step) {
+        if (step + 1 < 10) ld_step(step + 1, bf[(step + 1) & 1], wq[(step + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);  // keep the look-ahead reads above this step's MFMAs
+        const int c2 = step & 1;
+        const uint32_t wdup = __builtin_amdgcn_perm(wq[step & 1], wq[step & 1], wsel);
+        u32x4 m;
 #pragma unroll
-          for (int r = 0; r < 2; ++r) bb[r] = *reinterpret_cast<const vec_t*>(p0 + r * kXH_W * SHP);
-          w2 = wpair[pr * a.Chid + 16 * c];
-        };
-        ld_step(0, bf[0], wq[0]);
+        for (int d = 0; d < 4; ++d) m[d] = wdup & amask[d];
+        const vec_t af = reinterpret_cast<const vec_t&>(m);
 #pragma unroll
-        for (int step = 0; step < 20; ++step) {
-          if (step + 1 < 20) ld_step(step + 1, bf[(step + 1) & 1], wq[(step + 1) & 1]);
-          __builtin_amdgcn_sched_barrier(0);  // keep the look-ahead reads above this step's MFMAs
-          const int c = step & 3;
-          const uint32_t wdup = __builtin_amdgcn_perm(wq[step & 1], wq[step & 1], wsel);
-          u32x4 t;
+        for (int r = 0; r < 4; ++r) dacc[c2][r] = mfma16x16<T>(af, bf[step & 1][r], dacc[c2][r]);
+      }
+      const int choff = irbx_choff(g);
 #pragma unroll
-          for (int d = 0; d < 4; ++d) t[d] = wdup & amask[d];
-          const vec_t af = reinterpret_cast<const vec_t&>(t);
-#pragma unroll
-          for (int r = 0; r < 2; ++r) dacc[c][r] = mfma16x16<T>(af, bf[step & 1][r], dacc[c][r]);
-        }
-        if constexpr (STAMP) {  // a read of the last accumulator: the compiler waits for the depthwise MFMAs here
-          asm volatile("" ::"s"(__builtin_amdgcn_readfirstlane(__float_as_int(dacc[3][1][3]))));
-          pstamp(6);
-        }
-        // GATEW: the accumulators hold gate * h2 (the gate is in the staged weights); else the SE gate on the fp32 accumulators
-        // (lane: channels 16 c + 4 g + e).  One rounding to T, then y += Wp . (gate * h2)
-        if constexpr (!GATEW) {
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            const f32x4 gt = *reinterpret_cast<const f32x4*>(gate_s + chunk * 64 + 16 * c + 4 * g);
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-#pragma unroll
-              for (int e = 0; e < 4; ++e) dacc[c][r][e] *= gt[e];
-          }
-        }
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-          for (int kb = 0; kb < 2; ++kb) {
-            uint32_t p0[2], p1[2];
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-              typedef T t2 __attribute__((ext_vector_type(2)));
-              t2 o0, o1;
-              o0[0] = (T)dacc[2 * kb][r][2 * j]; o0[1] = (T)dacc[2 * kb][r][2 * j + 1];
-              o1[0] = (T)dacc[2 * kb + 1][r][2 * j]; o1[1] = (T)dacc[2 * kb + 1][r][2 * j + 1];
-              p0[j] = *reinterpret_cast<uint32_t*>(&o0);
-              p1[j] = *reinterpret_cast<uint32_t*>(&o1);
-            }
-            const u32x2 s0 = __builtin_amdgcn_permlane16_swap(p0[0], p1[0], false, false);
-            const u32x2 s1 = __builtin_amdgcn_permlane16_swap(p0[1], p1[1], false, false);
-            const u32x4 v = {s0[0], s1[0], s0[1], s1[1]};  // channels 32 kb + choff .. + 7 of pixel li
-#pragma unroll
-            for (int cb = 0; cb < NCB; ++cb) yacc[r][cb] = mfma16x16<T>(wpf[cb][kb], reinterpret_cast<const vec_t&>(v), yacc[r][cb]);
-          }
-        pstamp(7);
-      } else {
-        // ---- two taps per MFMA: D[16 ch][16 px] += A[16 ch][k] B[k][16 px], k = 16 t + c (tap slot t, channel c of the
-        // 16-channel tile), in this order of k: lane (li = lane & 15, g = lane >> 4) holds k-slice g = tap slot g & 1, channels 8 (g >> 1) + j.
-        //   B: lane = output pixel li of one tile row; its 8 channels of the halo pixel under tap slot g & 1: ONE ds_read_b128,
-        //      address = row base + this lane's tap offset (odd and even lane quarters read different taps)
-        //   A: lane = channel li of the tile; its weight of tap slot g & 1 at element li & 7 if (g >> 1) == li >> 3, else 0
-        // (k = 16 t + c in MFMA order would put the channel half in g & 1: the 16-lane groups of a ds_read_b128 -- {0-3, 12-15,
-        // 20-27}, ... -- would then mix 8 pixels at channel slot s with 8 at slot s + 1 and collide two-way on the 144-byte
-        // pitch.  With the tap in g & 1 a group reads 16 pixels of ONE slot, 8 of them shifted by the tap distance (1 or 16
-        // pixels; equal addresses broadcast): conflict-free, 4 instead of 8 LDS cycles for each of the 40 reads.)
-        // A wave owns 32 channels (2 tiles) x its 4 output rows (4 pixel tiles): 8 accumulator tiles of 4 registers,
-        // 5 tap pairs (the last one half empty) = 40 MFMAs of 16 cycles.
-        const int li = lane & 15, g = lane >> 4;
-        uint32_t amask[4];
-#pragma unroll
-        for (int d = 0; d < 4; ++d)
-          amask[d] = (((li & 7) >> 1) == d && (g >> 1) == (li >> 3)) ? ((li & 1) ? 0xFFFF0000u : 0x0000FFFFu) : 0u;
-        const uint32_t* wpair = reinterpret_cast<const uint32_t*>(wds) + chunk * 64 + chb * 32 + li;  // + (pair * Chid + 16 c2)
-        const uint32_t wsel = (g & 1) ? 0x03020302u : 0x01000100u;  // v_perm_b32 selector: this lane quarter's tap, duplicated
-        f32x4v dacc[2][4];
-#pragma unroll
-        for (int c2 = 0; c2 < 2; ++c2)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) dacc[c2][r] = f32x4v{0.f, 0.f, 0.f, 0.f};
-        const unsigned char* bbase = buf + ((4 * pxg) * kXH_W + li) * SHP + (chb * 4 + (g >> 1)) * 16;
-        const bool upper = (g & 1) != 0;
-        vec_t bf[2][4];
-        uint32_t wq[2];
-        auto ld_step = [&](int step, vec_t (&bb)[4], uint32_t& w2) {  // step = 2 * pair + c2
-          const int pr = step >> 1, c2 = step & 1;
-          const int ta = 2 * pr, tb = 2 * pr + 1 < 9 ? 2 * pr + 1 : 8;
-          const int offa = (ta / 3) * kXH_W + ta % 3, offb = (tb / 3) * kXH_W + tb % 3;
-          const unsigned char* p0 = bbase + (upper ? offb : offa) * SHP + c2 * 32;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) bb[r] = *reinterpret_cast<const vec_t*>(p0 + r * kXH_W * SHP);
-          w2 = wpair[pr * a.Chid + 16 * c2];
-        };
-        ld_step(0, bf[0], wq[0]);
-#pragma unroll
-        for (int step = 0; step < 10; ++step) {
-          if (step + 1 < 10) ld_step(step + 1, bf[(step + 1) & 1], wq[(step + 1) & 1]);
-          __builtin_amdgcn_sched_barrier(0);  // keep the look-ahead reads above this step's MFMAs
-          const int c2 = step & 1;
-          const uint32_t wdup = __builtin_amdgcn_perm(wq[step & 1], wq[step & 1], wsel);
-          u32x4 t;
-#pragma unroll
-          for (int d = 0; d < 4; ++d) t[d] = wdup & amask[d];
-          const vec_t af = reinterpret_cast<const vec_t&>(t);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) dacc[c2][r] = mfma16x16<T>(af, bf[step & 1][r], dacc[c2][r]);
-        }
-        // accumulators: lane (pixel li of row r, g): channels 16 c2 + 4 g + e.  v_permlane16_swap between the two tiles gives
-        // every lane 8 consecutive channels of its pixel: even g: 4 g .. 4 g + 7, odd g: 16 + 4 (g - 1) .. 16 + 4 g + 3
-        const int choff = 8 * (g >> 1) + 16 * (g & 1);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          uint32_t p0[2], p1[2];
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            typedef T t2 __attribute__((ext_vector_type(2)));
-            t2 o0, o1;
-            o0[0] = (T)dacc[0][r][2 * j]; o0[1] = (T)dacc[0][r][2 * j + 1];
-            o1[0] = (T)dacc[1][r][2 * j]; o1[1] = (T)dacc[1][r][2 * j + 1];
-            p0[j] = *reinterpret_cast<uint32_t*>(&o0);
-            p1[j] = *reinterpret_cast<uint32_t*>(&o1);
-          }
-          const u32x2 s0 = __builtin_amdgcn_permlane16_swap(p0[0], p1[0], false, false);
-          const u32x2 s1 = __builtin_amdgcn_permlane16_swap(p0[1], p1[1], false, false);
-          const u32x4 v = {s0[0], s1[0], s0[1], s1[1]};
-          const int orow = 4 * pxg + r;
-          T* op = out + ((size_t)(y0 + orow) * a.W + x0p + li) * a.Chid + chunk * 64 + chb * 32 + choff;
-          if constexpr (NTST) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(op));
-          else *reinterpret_cast<u32x4*>(op) = v;
-        }
-        // SE pool partial: channel sums over the wave's 64 pixels -- the 4 rows in registers, then the 16 pixel lanes of a row by DPP
-        if (has_pool) {
-          float v[8];
-#pragma unroll
-          for (int c2 = 0; c2 < 2; ++c2)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[4 * c2 + e] = (dacc[c2][0][e] + dacc[c2][1][e]) + (dacc[c2][2][e] + dacc[c2][3][e]);
-          // v += rotate(v) inside each 16-lane row, as ONE v_add_f32 with a DPP source per step (through
-          // __builtin_amdgcn_update_dpp hipcc emits v_mov 0 + v_mov_dpp + add: 92 instructions for this reduction instead
-          // of 32).  The eight values are stepped together, so a register written by one statement is read again eight
-          // statements later: the VALU-write -> DPP-read hazard (2 wait states) needs no s_nop inside the strings.
-#define LLIE_DPP_STEP(ROR)                                                                                               \
-  _Pragma("unroll") for (int i = 0; i < 8; ++i)                                                                          \
-      asm volatile("v_add_f32_dpp %0, %0, %0 row_ror:" #ROR " row_mask:0xf bank_mask:0xf" : "+v"(v[i]));
-          // the sums just written by ordinary VALU adds: 2 wait states before the first DPP read.  The eight values are operands of
-          // the statement, so every add that produces them is scheduled ABOVE the nop (a bare volatile asm orders only against
-          // other side effects, and hipcc's hazard recognizer does not look inside inline asm for the DPP read).
-          asm volatile("s_nop 1" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
-          LLIE_DPP_STEP(8)
-          LLIE_DPP_STEP(4)
-          LLIE_DPP_STEP(2)
-          LLIE_DPP_STEP(1)
-#undef LLIE_DPP_STEP
-          if (li == 0) {  // channels 16 c2 + 4 g + e of the wave's block
-            float* rp = red + (DBUF ? par : 0) * 256 + wave * 64 + 4 * g;
-            *reinterpret_cast<f32x4*>(rp) = f32x4{v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<f32x4*>(rp + 16) = f32x4{v[4], v[5], v[6], v[7]};
-          }
-          pend_tile = tile; pend_chunk = chunk; pend_par = DBUF ? par : 0;
-        }
+      for (int r = 0; r < 4; ++r) {
+        const u32x4 v = irbx_pack8_swap<T>(dacc[0][r], dacc[1][r]);
+        const int orow = 4 * t.pxg + r;
+        T* op = out + ((size_t)(y0 + orow) * a.W + x0p + li) * a.Chid + chunk * 64 + t.chb * 32 + choff;
+        if constexpr (NTST) __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(op));
+        else *reinterpret_cast<u32x4*>(op) = v;
+      }
+      if (has_pool) {
+        irbx_pool_partial(dacc, li, red + (DBUF ? par : 0) * 256 + t.wave * 64 + 4 * g);
+        pend_tile = tile; pend_chunk = chunk; pend_par = DBUF ? par : 0;
       }
       if (DBUF) par ^= 1;
       stamp(8);
     }
-    if constexpr (PCO > 0) {
-      // ---- y = round(acc) for the wave's 2 rows x 16 pixels (the shortcut is in acc since the top of the tile): lane (pixel li, g)
-      // holds rows 16 cb + 4 g + e of every block cb
-      const int li = lane & 15, g = lane >> 4;
-      const int choff = 8 * (g >> 1) + 16 * (g & 1);
-      T* yout = reinterpret_cast<T*>(a.y) + (size_t)b * P * PCO;
-      float st[2][NCB * 4];  // (sum, sum of squares) of the rounded outputs, this lane's 2 pixels
-#pragma unroll
-      for (int i = 0; i < NCB * 4; ++i) st[0][i] = st[1][i] = 0.f;
-#pragma unroll
-      for (int r = 0; r < 2; ++r) {
-        const size_t pix = (size_t)(y0 + 2 * wave + r) * a.W + x0p + li;
-        uint32_t pk[NCB][2];
-#pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) {
-          typedef T t2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-          for (int j = 0; j < 2; ++j) {
-            t2 o;
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-              o[e] = (T)yacc[r][cb][2 * j + e];
-              const float q = (float)o[e];
-              st[0][4 * cb + 2 * j + e] += q;
-              st[1][4 * cb + 2 * j + e] = __builtin_fmaf(q, q, st[1][4 * cb + 2 * j + e]);
-            }
-            pk[cb][j] = *reinterpret_cast<uint32_t*>(&o);
-          }
-        }
-#pragma unroll
-        for (int pp = 0; pp < NCB / 2; ++pp) {
-          const u32x2 s0 = __builtin_amdgcn_permlane16_swap(pk[2 * pp][0], pk[2 * pp + 1][0], false, false);
-          const u32x2 s1 = __builtin_amdgcn_permlane16_swap(pk[2 * pp][1], pk[2 * pp + 1][1], false, false);
-          *reinterpret_cast<u32x4*>(yout + pix * PCO + 32 * pp + choff) = u32x4{s0[0], s1[0], s0[1], s1[1]};
-        }
-      }
-      // Sums over the 16 pixel lanes of a row, sixteen values at a time, as a transposing reduction: a step halves the values a
-      // lane carries -- the lane keeps one half and adds its partner's copy of that half, the partner keeps the other -- so the
-      // steps cost 16 + 8 adds and leave lane quad k = li >> 2 with the sums of values 4 k .. 4 k + 3 over four lanes each; two
-      // butterfly steps inside the quad (4 + 4 adds) finish them: 32 adds instead of 4 x 16.  The partner is the mirrored lane
-      // (li ^ 15, then li ^ 7), and which half a lane writes is the DPP bank mask (banks = lane quads of a row): the first add of a
-      // pair completes the half kept in place, the second builds the other half from the upper registers into the lower ones.
-      // As in the pool partial of the plain kernel the adds are single v_add_f32 with a DPP source, written out because the
-      // builtin costs three instructions each, and a register written by one statement is read by DPP four or more statements
-      // later (2 wait states needed); s_nop 1 covers the ordinary VALU writes in front.  The order is fixed: the slab stays
-      // bitwise independent of the batch and the schedule.
-#pragma unroll
-      for (int grp = 0; grp < NCB / 2; ++grp) {
-        float v[16];  // PCO = 32: (which, cb, e) = (j >> 3, (j >> 2) & 1, j & 3); PCO = 64: which = grp, (cb, e) = (j >> 2, j & 3)
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-          if constexpr (NCB == 2) v[j] = st[j >> 3][j & 7];
-          else v[j] = st[grp][j];
-        }
-        asm volatile("s_nop 1" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]),
-                                 "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]));
-#define LLIE_DPP_HALVE(N, CTRL, KEEP, TAKE)                                                                                  \
-  _Pragma("unroll") for (int i = 0; i < N; ++i)                                                                              \
-      asm volatile("v_add_f32_dpp %0, %0, %0 " CTRL " row_mask:0xf bank_mask:" KEEP : "+v"(v[i]));                           \
-  _Pragma("unroll") for (int i = 0; i < N; ++i)                                                                              \
-      asm volatile("v_add_f32_dpp %0, %1, %1 " CTRL " row_mask:0xf bank_mask:" TAKE : "+v"(v[i]) : "v"(v[i + N]));
-#define LLIE_DPP_STEP(CTRL)                                                                                                  \
-  _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                              \
-      asm volatile("v_add_f32_dpp %0, %0, %0 " CTRL " row_mask:0xf bank_mask:0xf" : "+v"(v[i]));
-        LLIE_DPP_HALVE(8, "row_mirror", "0x3", "0xc")        // lanes 0..7 keep values 0..7, lanes 8..15 take 8..15
-        LLIE_DPP_HALVE(4, "row_half_mirror", "0x5", "0xa")   // quads 0 and 2 keep values 0..3 of theirs, quads 1 and 3 take 4..7
-        LLIE_DPP_STEP("quad_perm:[2,3,0,1]")
-        LLIE_DPP_STEP("quad_perm:[1,0,3,2]")
-#undef LLIE_DPP_HALVE
-#undef LLIE_DPP_STEP
-        if ((li & 3) == 0) {  // red[wave][which][channel 16 cb + 4 g + e]: quad k of the row holds (which, cb) = (k >> 1, k & 1) or (grp, k)
-          const int k = li >> 2;
-          const int which = NCB == 2 ? k >> 1 : grp, cb = NCB == 2 ? k & 1 : k;
-          *reinterpret_cast<f32x4*>(red + (wave * 2 + which) * PCO + 16 * cb + 4 * g) = f32x4{v[0], v[1], v[2], v[3]};
-        }
-      }
-      pend_tile = tile;
-      pstamp(8);
-    }
     ty = tyn; tx = txn;
   }
-  if constexpr (STAMP) {
-    if (a.dbg && lane == 0) {
-      const size_t wg = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-#pragma unroll
-      for (int i = 0; i < kXStamps; ++i) a.dbg[(wg * 4 + wave) * kXStamps + i] = tk[i];
-    }
-  }
-  if constexpr (PCO > 0) {
-    wg_barrier();
-    flush_pool();
-  }
+  stamp.store(a, t);
   if (has_pool) {
     wg_barrier();
     flush_pool();
@@ -1020,19 +907,329 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
   }
 }
 
+// ---- the tile epilogue of expand_dw_project: y = round(yacc) stored, y's GroupNorm partials of the wave into red[wave][2][PCO]
+template <typename T, int PCO>
+__device__ __forceinline__ void irbx_project_store_y(const IrbxArgs& a, const IrbxLane& t, const f32x4 (&yacc)[2][PCO / 16], const int b, const int y0,
+                                                     const int x0p, float* red) {
+  constexpr int NCB = PCO / 16;
+  const int wave = t.wave, li = t.li, g = t.g;
+  const int P = a.H * a.W;
+  // ---- y = round(acc) for the wave's 2 rows x 16 pixels (the shortcut is in acc since the top of the tile): lane (pixel li, g)
+  // holds rows 16 cb + 4 g + e of every block cb
+  const int choff = irbx_choff(g);
+  T* yout = reinterpret_cast<T*>(a.y) + (size_t)b * P * PCO;
+  float st[2][NCB * 4];  // (sum, sum of squares) of the rounded outputs, this lane's 2 pixels
+#pragma unroll
+  for (int i = 0; i < NCB * 4; ++i) st[0][i] = st[1][i] = 0.f;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const size_t pix = (size_t)(y0 + 2 * wave + r) * a.W + x0p + li;
+    uint32_t pk[NCB][2];  // rounded here, not in irbx_pack8_swap: the statistics are those of the rounded values
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb) {
+      typedef T t2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        t2 o;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          o[e] = (T)yacc[r][cb][2 * j + e];
+          const float q = (float)o[e];
+          st[0][4 * cb + 2 * j + e] += q;
+          st[1][4 * cb + 2 * j + e] = __builtin_fmaf(q, q, st[1][4 * cb + 2 * j + e]);
+        }
+        pk[cb][j] = *reinterpret_cast<uint32_t*>(&o);
+      }
+    }
+#pragma unroll
+    for (int pp = 0; pp < NCB / 2; ++pp)
+      *reinterpret_cast<u32x4*>(yout + pix * PCO + 32 * pp + choff) = irbx_swap8(pk[2 * pp], pk[2 * pp + 1]);
+  }
+  // Sums over the 16 pixel lanes of a row, sixteen values at a time, as a transposing reduction: a step halves the values a
+  // lane carries -- the lane keeps one half and adds its partner's copy of that half, the partner keeps the other -- so the
+  // steps cost 16 + 8 adds and leave lane quad k = li >> 2 with the sums of values 4 k .. 4 k + 3 over four lanes each; two
+  // butterfly steps inside the quad (4 + 4 adds) finish them: 32 adds instead of 4 x 16.  The partner is the mirrored lane
+  // (li ^ 15, then li ^ 7), and which half a lane writes is the DPP bank mask (banks = lane quads of a row): the first add of a
+  // pair completes the half kept in place, the second builds the other half from the upper registers into the lower ones.
+  // As in the pool partial of expand_dw the adds are single v_add_f32 with a DPP source, written out because the
+  // builtin costs three instructions each, and a register written by one statement is read by DPP four or more statements
+  // later (2 wait states needed); s_nop 1 covers the ordinary VALU writes in front.  The order is fixed: the slab stays
+  // bitwise independent of the batch and the schedule.
+#pragma unroll
+  for (int grp = 0; grp < NCB / 2; ++grp) {
+    float v[16];  // PCO = 32: (which, cb, e) = (j >> 3, (j >> 2) & 1, j & 3); PCO = 64: which = grp, (cb, e) = (j >> 2, j & 3)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      if constexpr (NCB == 2) v[j] = st[j >> 3][j & 7];
+      else v[j] = st[grp][j];
+    }
+    asm volatile("s_nop 1" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]),
+                             "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]));
+#define LLIE_DPP_HALVE(N, CTRL, KEEP, TAKE)                                                                                  \
+  _Pragma("unroll") for (int i = 0; i < N; ++i)                                                                              \
+      asm volatile("v_add_f32_dpp %0, %0, %0 " CTRL " row_mask:0xf bank_mask:" KEEP : "+v"(v[i]));                           \
+  _Pragma("unroll") for (int i = 0; i < N; ++i)                                                                              \
+      asm volatile("v_add_f32_dpp %0, %1, %1 " CTRL " row_mask:0xf bank_mask:" TAKE : "+v"(v[i]) : "v"(v[i + N]));
+#define LLIE_DPP_STEP(CTRL)                                                                                                  \
+  _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                              \
+      asm volatile("v_add_f32_dpp %0, %0, %0 " CTRL " row_mask:0xf bank_mask:0xf" : "+v"(v[i]));
+    LLIE_DPP_HALVE(8, "row_mirror", "0x3", "0xc")        // lanes 0..7 keep values 0..7, lanes 8..15 take 8..15
+    LLIE_DPP_HALVE(4, "row_half_mirror", "0x5", "0xa")   // quads 0 and 2 keep values 0..3 of theirs, quads 1 and 3 take 4..7
+    LLIE_DPP_STEP("quad_perm:[2,3,0,1]")
+    LLIE_DPP_STEP("quad_perm:[1,0,3,2]")
+#undef LLIE_DPP_HALVE
+#undef LLIE_DPP_STEP
+    if ((li & 3) == 0) {  // red[wave][which][channel 16 cb + 4 g + e]: quad k of the row holds (which, cb) = (k >> 1, k & 1) or (grp, k)
+      const int k = li >> 2;
+      const int which = NCB == 2 ? k >> 1 : grp, cb = NCB == 2 ? k & 1 : k;
+      *reinterpret_cast<f32x4*>(red + (wave * 2 + which) * PCO + 16 * cb + 4 * g) = f32x4{v[0], v[1], v[2], v[3]};
+    }
+  }
+}
+
+// ---- expand_dw_project: the project GEMM of the block as the tail, PCO = Cout.  h2 never leaves the workgroup: a wave owns two
+// output rows and ALL 64 channels of the chunk in the depthwise phase (instead of four rows and 32 channels), so after the same
+// permlane16 swap that feeds expand_dw's h2 stores a lane holds 8 consecutive channels of one pixel -- a B fragment of a 16x16x32
+// MFMA whose A fragment is 16 rows of Wp.  No pool work here: the SE gate is already known (expand_pool_kernel), a constant per
+// (image, channel), and a workgroup serves one image, so the gate is part of the depthwise weights it stages, T(6 w gate): the
+// accumulators of the depthwise phase are gate * h2 and the chunk tail has nothing to multiply (expand_pool keeps T(6 w): its
+// totals are what the gate is computed from; and so does the 64-channel form here, which keeps the gate as a table in LDS and
+// multiplies the fp32 accumulators: GATEW below).  y[32 pixels][PCO] accumulates in fp32 over the chunks (PCO / 2 registers) and
+// STARTS as the shortcut -- the raw x of the centre pixels, loaded before the tile-top barrier together with the next tile's
+// prefetch -- so the tile's epilogue only rounds to T, stores y and leaves y's GroupNorm partials as the tile's slab entry.
+// PCO != K (96 -> 32): the block has a skip conv instead of the identity shortcut, and its input may be a virtual concat.  Wp is
+// then the engine's K-concatenated matrix [PCO][Chid + K] (row stride IrbxArgs::ldp), project columns first: the chunk tail reads
+// the project columns as before, and y starts as Wskip . x on the raw centre pixels: K / 32 k-steps at the top of the tile (no
+// norm, no activation: the skip segments of pw_gemm), their operands loaded before the tile-top barrier.
+// STAMP slots: 0 wait for the x tile (vmcnt), 1 activate + ds_write + the next tile's and the shortcut's loads issued + halo
+// validity, 2 tile-top barrier + flush of y's statistics + the shortcut into the y accumulators, 3 chunk-top barrier (chunks after
+// the first), 4 expand MFMAs + epilogue + ds_write, 5 barrier behind them, 6 depthwise steps until the last accumulator can be
+// read, 7 pack + swap + project MFMAs issued (they complete under whatever follows), 8 the tile's epilogue: rounding, y's
+// statistics, stores issued.
+template <typename T, int KS, bool STAMP, int PCO>
+__device__ __forceinline__ void expand_dw_project_body(const IrbxArgs& a, const int tiles_per_wg) {
+  constexpr int K = 16 * KS;
+  typedef typename Elem<T>::vec_t vec_t;
+  typedef IrbxHalo<T, KS> Halo;
+  constexpr bool PSKIP = PCO != K;  // skip conv in place of the identity shortcut
+  // The image's SE gate is part of the staged depthwise weights (GATEW) -- except at 64 channels, where that measured no faster
+  // than the gate table [Chid] in LDS behind `red`, applied to the accumulators in the chunk tail (profiles/r20/README.md), and
+  // the table stays
+  constexpr bool GATEW = KS != 4;
+  static_assert(PCO > 0 && (PCO == K ? KS <= 4 : PCO % 32 == 0 && PCO <= 64),
+                "project tail: single-buffered kernel; identity form at 32 and 64 channels, skip form to 32 or 64");
+  constexpr int NCB = PCO / 16;  // 16-row blocks of Wp
+  constexpr int NKS = PSKIP ? K / 32 : 1;
+  extern __shared__ __align__(16) unsigned char smem[];
+  const IrbxLds lds = irbx_lds(KS, a.Chid, false, PCO);
+  unsigned char* buf = smem;  // sH, single-buffered
+  unsigned char* sX = smem + lds.sX;
+  T* wds = reinterpret_cast<T*>(smem + lds.wds);
+  float* aff2 = reinterpret_cast<float*>(smem + lds.aff2);
+  float* aff1 = reinterpret_cast<float*>(smem + lds.aff1);
+  float* red = reinterpret_cast<float*>(smem + lds.red);  // the four waves' (sum, sum of squares) of y, 4 x 2 x PCO floats
+  float* gate_s = reinterpret_cast<float*>(smem + lds.tail);
+
+  const IrbxLane t = irbx_lane();
+  const int tid = t.tid, wave = t.wave, n = t.n, h = t.h, chb = t.chb, pxg = t.pxg, li = t.li, g = t.g;
+  const int b = blockIdx.z;
+  const int tiles_x = a.W / kXT_W;
+  const int P = a.H * a.W;
+  const T* x0 = reinterpret_cast<const T*>(a.x0) + (size_t)b * P * a.c0;
+  const T* x1 = a.x1 ? reinterpret_cast<const T*>(a.x1) + (size_t)b * P * a.c1 : nullptr;
+  const T* w1 = reinterpret_cast<const T*>(a.w1);
+  // every workgroup takes all KS = Chid / 64 channel chunks: y accumulates over them (the launch has gridDim.y = 1)
+  const int chunk0 = blockIdx.y * KS;
+  const int nchunks_all = a.Chid / 64;
+  const int chunk1 = chunk0 + KS < nchunks_all ? chunk0 + KS : nchunks_all;
+
+  irbx_stage_constants<T, KS, GATEW>(a, b, tid, wds, aff2, aff1, GATEW ? nullptr : gate_s, sX);
+  const IrbxTiles run = irbx_tiles(a, tiles_per_wg);
+  Halo halo;
+  halo.init(a, x0, x1, sX, tid);
+  int ty = run.first / tiles_x, tx = run.first % tiles_x;   // the only division: once per workgroup
+  if (Halo::PREF && run.first < run.last) halo.load(a, ty, tx, tiles_x);
+  vec_t wf[KS];
+  irbx_load_wf<T, KS>(wf, w1, chunk0, t);
+  wg_barrier();  // constants staged
+
+  IrbxStamps<STAMP> stamp;
+  stamp(-1);
+  int pend_tile = -1;  // tile whose y statistics wait in `red` for their cross-wave sum
+  auto flush_ystats = [&]() {  // after a barrier that follows the tile epilogue which wrote `red`
+    // y's statistics of the tile before: the four waves' (sum, sum of squares) [wave][2][PCO], added in wave order
+    if (pend_tile >= 0 && tid < 2 * PCO) {
+      const float s = (red[tid] + red[2 * PCO + tid]) + (red[4 * PCO + tid] + red[6 * PCO + tid]);
+      a.ystats[((size_t)b * run.per_image + pend_tile) * 2 * PCO + tid] = s;
+    }
+    pend_tile = -1;
+  };
+
+  for (int tile = run.first; tile < run.last; ++tile) {
+    const int y0 = ty * kXT_H, x0p = tx * kXT_W;
+    int tyn = ty, txn = tx + 1;  // the next tile of the run
+    if (txn == tiles_x) { txn = 0; ++tyn; }
+    // ---- activate this tile's x (norm1 + ReLU6) into sX, prefetch the next tile.  Every wave is past the last
+    // MFMA phase of the previous tile here (the barrier that follows it), so sX is free.
+    if (!Halo::PREF) halo.load(a, ty, tx, tiles_x);
+    // Every vector-memory operation so far has to be complete here anyway (raw[] below is older than all of them), but the
+    // compiler's wait sits inside the predicated block below; said unconditionally, the chunk loop is entered with nothing
+    // pending (see expand_dw_body).
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    stamp(0);
+    halo.activate(aff1);
+    // The shortcut's operands, for the wave's 2 rows x 16 pixels (lane = pixel li, quarter g): the raw x of the centre pixels,
+    // rows 16 cb + 4 g + e of every block cb (identity form), or the K / 32 k-steps of the skip conv -- k-step ks covers input
+    // channels 32 ks .. 32 ks + 31, lane (li, g) holds channels 32 ks + 8 g .. + 7 of row 16 cb + li of Wskip (A) and of pixel li
+    // of the row (B); a 16-byte vector never straddles the segments (c0 % 16 == 0).  The tile's own loads have left x in L2.  They
+    // go out here, ahead of the next tile's prefetch, and become the start of the y accumulators behind the tile-top barrier; the
+    // staging registers (raw) are free by now.  (vmcnt counts in order, so the wait for them could leave the prefetch in flight;
+    // hipcc's does not -- the prefetch loads are lane-predicated, it assumes none was issued and waits vmcnt(0) for the last
+    // shortcut register: profiles/r20/README.md, section 1.)
+    typedef T t4 __attribute__((ext_vector_type(4)));
+    t4 res[2][NCB];
+    vec_t wsf[NKS][NCB], xsv[NKS][2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const size_t pix = (size_t)(y0 + 2 * wave + r) * a.W + x0p + li;
+      if constexpr (!PSKIP) {
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb) res[r][cb] = *reinterpret_cast<const t4*>(x0 + pix * PCO + 16 * cb + 4 * g);
+      } else {
+#pragma unroll
+        for (int ks = 0; ks < NKS; ++ks) {
+          const int ch = 32 * ks + 8 * g;
+          xsv[ks][r] = ch < a.c0 ? ld_vec<T>(x0 + pix * a.c0 + ch) : ld_vec<T>(x1 + pix * a.c1 + (ch - a.c0));
+        }
+      }
+    }
+    if constexpr (PSKIP) {
+      const T* wsk = reinterpret_cast<const T*>(a.wp) + (size_t)li * a.ldp + a.Chid + 8 * g;
+#pragma unroll
+      for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb) wsf[ks][cb] = ld_vec<T>(wsk + (size_t)cb * 16 * a.ldp + 32 * ks);
+    }
+    if (Halo::PREF && tile + 1 < run.last) halo.load(a, tyn, txn, tiles_x);
+    const bool border = irbx_border(a, ty, tx, tiles_x);
+    bool ok[3];
+    irbx_halo_ok(a, t, border, y0, x0p, ok);
+    stamp(1);
+    wg_barrier();
+    flush_ystats();
+
+    // y[32 pixels][PCO] of the wave starts as its shortcut: raw x (identity form), Wskip . x (skip form)
+    f32x4 yacc[2][NCB];
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int cb = 0; cb < NCB; ++cb) {
+        if constexpr (!PSKIP) yacc[r][cb] = f32x4{(float)res[r][cb][0], (float)res[r][cb][1], (float)res[r][cb][2], (float)res[r][cb][3]};
+        else yacc[r][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    if constexpr (PSKIP) {
+#pragma unroll
+      for (int ks = 0; ks < NKS; ++ks)
+#pragma unroll
+        for (int r = 0; r < 2; ++r)
+#pragma unroll
+          for (int cb = 0; cb < NCB; ++cb) yacc[r][cb] = mfma16x16<T>(wsf[ks][cb], xsv[ks][r], yacc[r][cb]);
+    }
+    stamp(2);
+    // (A run-time loop: see expand_dw_body.  Said with a pragma: chunk1 - chunk0 <= KS is visible here, and with the depthwise
+    // steps in a function hipcc unrolls the loop fully -- 540 more instructions at KS = 2, 56 bytes of scratch.)
+#pragma unroll 1
+    for (int chunk = chunk0; chunk < chunk1; ++chunk) {
+      if (chunk > chunk0) {
+        wg_barrier();  // previous depthwise phase done with sH
+        flush_ystats();
+        stamp(3);
+      }
+      // ---- MFMA: h1^T block (32 channels x 32 pixels) x 3 pixel blocks, one accumulator at a time (registers: the identity tail
+      // at 32 channels fits three workgroups per CU that way)
+      const int ch0 = chunk * 64 + chb * 32;
+      // aff2 of this lane's 16 accumulator channels: ch0 + 8g + 4h + e
+      f32x4 sc2[4], sh2[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        sc2[g] = *reinterpret_cast<const f32x4*>(aff2 + ch0 + 8 * g + 4 * h);
+        sh2[g] = *reinterpret_cast<const f32x4*>(aff2 + a.Chid + ch0 + 8 * g + 4 * h);
+      }
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const int q = (pxg * 3 + i) * 32 + n;
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < KS; ++s)
+          acc = mfma16<T>(wf[s], *reinterpret_cast<const vec_t*>(sX + q * Halo::XP + (16 * s + 8 * h) * 2), acc);
+        if (i == 2) irbx_load_wf<T, KS>(wf, w1, chunk + 1 < chunk1 ? chunk + 1 : chunk0, t);  // next chunk (or the next tile's first)
+        irbx_expand_store<T>(acc, sc2, sh2, border, ok[i], buf + q * SHP + (chb * 4 + 2 * h) * 16);
+      }
+      stamp(4);
+      wg_barrier();
+      stamp(5);
+      // ---- depthwise with the wave's share turned: rows 2 wave, 2 wave + 1 of the tile x the chunk's four 16-channel tiles
+      const int choff = irbx_choff(g);  // the lane's 8 channels of a 32-channel half after the swap below
+      // Wp fragments of this chunk: rows 16 cb + li, k = the lane's 8 channels of half kb -- in flight under the depthwise steps
+      vec_t wpf[NCB][2];
+      const T* wp = reinterpret_cast<const T*>(a.wp) + (size_t)li * a.ldp + chunk * 64 + choff;
+#pragma unroll
+      for (int cb = 0; cb < NCB; ++cb)
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) wpf[cb][kb] = ld_vec<T>(wp + (size_t)cb * 16 * a.ldp + 32 * kb);
+      f32x4 dacc[4][2];
+      irbx_dw_two_tap<T, 2, 4>(dacc, buf, wave, 0, wds, chunk, a.Chid, t);
+      if constexpr (STAMP) {  // a read of the last accumulator: the compiler waits for the depthwise MFMAs here
+        asm volatile("" ::"s"(__builtin_amdgcn_readfirstlane(__float_as_int(dacc[3][1][3]))));
+        stamp(6);
+      }
+      // GATEW: the accumulators hold gate * h2 (the gate is in the staged weights); else the SE gate on the fp32 accumulators
+      // (lane: channels 16 c + 4 g + e).  One rounding to T, then y += Wp . (gate * h2)
+      if constexpr (!GATEW) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const f32x4 gt = *reinterpret_cast<const f32x4*>(gate_s + chunk * 64 + 16 * c + 4 * g);
+#pragma unroll
+          for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dacc[c][r][e] *= gt[e];
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int kb = 0; kb < 2; ++kb) {
+          const u32x4 v = irbx_pack8_swap<T>(dacc[2 * kb][r], dacc[2 * kb + 1][r]);  // channels 32 kb + choff .. + 7 of pixel li
+#pragma unroll
+          for (int cb = 0; cb < NCB; ++cb) yacc[r][cb] = mfma16x16<T>(wpf[cb][kb], reinterpret_cast<const vec_t&>(v), yacc[r][cb]);
+        }
+      stamp(7);
+    }
+    irbx_project_store_y<T, PCO>(a, t, yacc, b, y0, x0p, red);
+    pend_tile = tile;
+    stamp(8);
+    ty = tyn; tx = txn;
+  }
+  stamp.store(a, t);
+  wg_barrier();
+  flush_ystats();
+}
+
 template <typename T, int KS, bool DBUF, bool STAMP = false, bool NTST = false>
 __global__ void __launch_bounds__(256, (KS == 2 && !DBUF) ? 3 : 2) expand_dw_kernel(const IrbxArgs a, const int tiles_per_wg, const int chunks_per_wg) {
-  expand_dw_body<T, KS, DBUF, STAMP, NTST, 0>(a, tiles_per_wg, chunks_per_wg);
+  expand_dw_body<T, KS, DBUF, STAMP, NTST>(a, tiles_per_wg, chunks_per_wg);
 }
 // two workgroups per CU at 64 and 96 channels: the y accumulators and the Wp fragments do not fit the 168 registers of three; at 32
-// they do (165, none spilled) once the expand phase keeps one accumulator at a time (NACC)
+// they do (168, none spilled) once the expand phase keeps one accumulator at a time
 template <typename T, int KS, int PCO>
 __global__ void __launch_bounds__(256, KS == 2 ? 3 : 2) expand_dw_project_kernel(const IrbxArgs a, const int tiles_per_wg) {
-  expand_dw_body<T, KS, false, false, false, PCO>(a, tiles_per_wg, KS);
+  expand_dw_project_body<T, KS, false, PCO>(a, tiles_per_wg);
 }
 template <int KS, int PCO>
 __global__ void __launch_bounds__(256, KS == 2 ? 3 : 2) expand_dw_project_stamp_kernel(const IrbxArgs a, const int tiles_per_wg) {
-  expand_dw_body<half_t, KS, false, true, false, PCO>(a, tiles_per_wg, KS);
+  expand_dw_project_body<half_t, KS, true, PCO>(a, tiles_per_wg);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1133,18 +1330,6 @@ hipError_t launch_expand_pool(int dtype, const IrbxArgs& a, hipStream_t s) {
     return hipErrorInvalidValue;
   return dtype == 1 ? launch_scan_t<half_t, true>(a, s) : launch_scan_t<bf16_t, true>(a, s);
 }
-
-// Dynamic LDS of expand_dw_body, in the order of its layout comment (at `smem`): sH (twice when double-buffered), sX, the packed
-// depthwise weights, aff2, aff1, then `red` (2 x 256 floats) + the pool totals where they live in LDS (KS <= 4) or, project tail,
-// `red` (8 PCO floats) + the gate table (Chid floats) at 64 channels only: elsewhere the gate is in the depthwise weights
-constexpr size_t irbx_lds_bytes(int KS, int Chid, bool dbuf, int PCO) {
-  const size_t body = (size_t)(dbuf ? 2 : 1) * kXNPB * 32 * SHP + (size_t)kXNPB * 32 * (16 * KS + 8) * 2 + (size_t)10 * Chid * 2 +
-                      (size_t)2 * Chid * 4 + (size_t)2 * 16 * KS * 4;
-  if (PCO != 0) return body + (size_t)8 * PCO * 4 + (KS == 4 ? (size_t)Chid * 4 : 0);
-  return body + 2 * 256 * 4 + (KS <= 4 ? (size_t)KS * 64 * 8 : 0);
-}
-// 96 -> 32: 1 792 B short of what two workgroups per CU allow (256 B while the gate table was in LDS, profiles/r08/README.md)
-static_assert(irbx_lds_bytes(6, 384, false, 32) == 80128 && irbx_lds_bytes(6, 384, false, 32) <= 80 * 1024, "expand_dw_project<6, 32>: two workgroups per CU");
 
 constexpr int kXTilesPerWg = 4;  // longest run of tiles along x one workgroup takes
 // tiles per workgroup: a run along x (neighbouring halo columns hit L1), as long as the launch keeps >= 2048 workgroups

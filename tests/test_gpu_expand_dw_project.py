@@ -120,6 +120,55 @@ def test_expand_pool_totals_vs_float64_and_expand_dw(dev, dtype, tdt, cin, H, W,
         assert torch.equal(new[i:i + 1], run_pool(L, dtype, t, dev, split, i, i + 1)), i
 
 
+# ------------------------------------------------------------------ 1b. expand_dw's h2
+H2_BOUND = {1: 2 * 5.190203e-4, 2: 2 * 4.058995e-3}   # twice the largest error measured, per dtype (the test's docstring)
+
+
+def run_expand_dw(L, dtype, t, dev, split, totals):
+    """(h2 [B][H][W][Chid] in T, pool totals or None) from expand_dw; h2 starts as NaN"""
+    st = torch.cuda.current_stream().cuda_stream
+    B, H, W, cin = t["x"].shape
+    chid = 4 * cin
+    c0 = split if split else cin
+    x0 = t["x"][..., :c0].contiguous().to(dev)
+    x1 = t["x"][..., c0:].contiguous().to(dev) if split else None
+    d = {k: t[k].to(dev) for k in ("s1", "b1", "w1", "s2", "b2", "wd")}
+    h2 = torch.full((B, H, W, chid), float("nan"), dtype=t["x"].dtype, device=dev)
+    tot = torch.zeros(B, chid, dtype=torch.int64, device=dev) if totals else None
+    N.check(L.llie_expand_dw(dtype, x0.data_ptr(), c0, x1.data_ptr() if split else None, cin - c0, d["s1"].data_ptr(), d["b1"].data_ptr(),
+                             d["w1"].data_ptr(), d["s2"].data_ptr(), d["b2"].data_ptr(), d["wd"].data_ptr(), h2.data_ptr(),
+                             tot.data_ptr() if totals else None, B, H, W, st), "expand_dw")
+    torch.cuda.synchronize()
+    return h2.cpu(), (tot.cpu() if totals else None)
+
+
+@pytest.mark.parametrize("dtype,tdt", DTYPES)
+@pytest.mark.parametrize("cin,H,W,B,split", [(32, 8, 16, 2, 0),      # one tile
+                                             (64, 16, 32, 3, 0),     # 2 x 2 tiles, no interior tile
+                                             (32, 24, 48, 1, 0),     # one interior tile
+                                             (96, 16, 32, 2, 32)])   # two input segments
+def test_expand_dw_h2_vs_float64(dev, dtype, tdt, cin, H, W, B, split):
+    """h2 = dw3x3(relu6(norm2(W1 relu6(norm1 x)))) as expand_dw stores it, against float64 from the same T-rounded inputs and the
+    depthwise weights as staged (6 w in T), relative to max(1, |ref|max).  h2 starts as NaN so that an unwritten pixel shows, and
+    the run that also keeps the pool totals must store the same bits.
+    Measured on an MI355X with the kernel as it was before expand_dw_body was split (the split changes no bit), in the order of
+    the cases above: fp16 5.190e-4, 5.115e-4, 4.186e-4, 4.113e-4; bf16 3.337e-3, 4.059e-3, 3.253e-3, 3.064e-3 (|ref|max 11.4 to
+    17.0).  The bound is twice the largest per dtype; the factor 2 is this file's room for summation order."""
+    L = N.lib()
+    t = block_inputs(cin, H, W, B, tdt, 1000 * cin + H + W)
+    ref = front64(t, tdt, round_weights=True).permute(0, 2, 3, 1)         # [B][H][W][Chid]
+    h2, _ = run_expand_dw(L, dtype, t, dev, split, totals=False)
+    h2t, tot = run_expand_dw(L, dtype, t, dev, split, totals=True)
+    rmax = ref.abs().max().item()
+    err = (h2.double() - ref).abs().max().item() / max(1.0, rmax)
+    msg = f"max |h2 - float64| / max(1, |ref|max) = {err:.4e}, |ref|max {rmax:.3e}"
+    print(msg)
+    assert torch.isfinite(h2.float()).all()
+    assert err <= H2_BOUND[dtype], msg
+    assert torch.equal(h2, h2t)
+    assert tot.abs().sum().item() > 0
+
+
 # ------------------------------------------------------------------ 3. expand_dw_project on its own
 @pytest.mark.parametrize("dtype,tdt,tol", [(1, torch.float16, 4e-3), (2, torch.bfloat16, 3e-2)])
 @pytest.mark.parametrize("C,H,W,B", [(32, 8, 16, 2), (64, 16, 32, 3)])
