@@ -1332,11 +1332,30 @@ hipError_t launch_expand_pool(int dtype, const IrbxArgs& a, hipStream_t s) {
 }
 
 constexpr int kXTilesPerWg = 4;  // longest run of tiles along x one workgroup takes
-// tiles per workgroup: a run along x (neighbouring halo columns hit L1), as long as the launch keeps >= 2048 workgroups
-static int irbx_tiles_per_wg(const IrbxArgs& a) {
-  int tpw = kXTilesPerWg;
-  while (tpw > 1 && ((a.W / kXT_W) % tpw || (long)(irbx_pool_tiles(a.H, a.W) / tpw) * a.B < 2048)) tpw >>= 1;
-  return tpw;
+// The launch plan of expand_dw (project = false) and expand_dw_project (true) for Cin input channels (Chid = 4 Cin); both
+// launchers take it from here and llie_expand_dw_plan reports it.
+//   tpw: tiles per workgroup, a run along x (neighbouring halo columns hit L1), as long as the launch keeps >= 2048 workgroups
+//   cpw: 64-channel chunks per workgroup: all of them (x tile loaded once) unless the launch would be too small; expand_dw_project
+//        always takes all (y accumulates over them)
+//   knobs "irbx_grid", "irbx_grid2/4/6" (expand_dw only): about this many workgroups per launch, each image's tiles split evenly
+//        over its share (tpw = 0)
+IrbxPlan irbx_plan(int Cin, int B, int H, int W, bool project) {
+  const int ntiles = irbx_pool_tiles(H, W), nchunks = 4 * Cin / 64;
+  IrbxPlan p;
+  p.tpw = kXTilesPerWg;
+  while (p.tpw > 1 && ((W / kXT_W) % p.tpw || (long)(ntiles / p.tpw) * B < 2048)) p.tpw >>= 1;
+  p.cpw = nchunks;
+  if (!project)
+    while (p.cpw > 1 && (long)(ntiles / p.tpw) * B * (nchunks / p.cpw) < 1024 && p.cpw % 2 == 0) p.cpw >>= 1;
+  p.gx = ntiles / p.tpw;
+  p.gy = nchunks / p.cpw;
+  const int want = project ? 0 : g_irbx_grid[Cin / 32 - 1];
+  if (want > 0) {
+    const int gx = want / (B * p.gy);
+    p.gx = gx < 1 ? 1 : (gx > ntiles ? ntiles : gx);
+    p.tpw = 0;
+  }
+  return p;
 }
 
 template <typename T, int KS, bool DBUF, bool STAMP, bool NTST>
@@ -1350,21 +1369,12 @@ static hipError_t launch_dw_one(const IrbxArgs& a, dim3 grid, size_t lds, int tp
 template <typename T, int KS, bool DBUF>
 static hipError_t launch_dw_cfg(const IrbxArgs& a, hipStream_t s) {
   const size_t lds = irbx_lds_bytes(KS, a.Chid, DBUF, 0);
-  const int ntiles = irbx_pool_tiles(a.H, a.W), nchunks = a.Chid / 64;
-  int tpw = irbx_tiles_per_wg(a);
-  // channel chunks per workgroup: all of them (x tile loaded once) unless the launch would be too small
-  int cpw = nchunks;
-  while (cpw > 1 && (long)(ntiles / tpw) * a.B * (nchunks / cpw) < 1024 && cpw % 2 == 0) cpw >>= 1;
+  const IrbxPlan plan = irbx_plan(16 * KS, a.B, a.H, a.W, false);
+  const int tpw = plan.tpw, cpw = plan.cpw;
   static const std::string name = std::string("expand_dw_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) + ", " +
                                   (DBUF ? "1" : "0") + ">";
   note_kernel(name.c_str());
-  dim3 grid(ntiles / tpw, nchunks / cpw, a.B);
-  if (g_irbx_grid[KS / 2 - 1] > 0) {  // knobs "irbx_grid", "irbx_grid2/4/6": about this many workgroups per launch, each image's tiles split evenly over its share
-    int gx = g_irbx_grid[KS / 2 - 1] / (a.B * (nchunks / cpw));
-    gx = gx < 1 ? 1 : (gx > ntiles ? ntiles : gx);
-    grid.x = gx;
-    tpw = 0;
-  }
+  const dim3 grid(plan.gx, plan.gy, a.B);
   if constexpr (std::is_same<T, half_t>::value && !DBUF) {
     if (g_irbx_stamp == 1) {  // diagnostic build: in-kernel cycle stamps (fp16 only)
       IrbxArgs b = a;
@@ -1392,24 +1402,25 @@ static hipError_t launch_dw_t(const IrbxArgs& a, hipStream_t s) {
 template <typename T, int KS, int PCO>
 static hipError_t launch_project_cfg(const IrbxArgs& a, hipStream_t s) {
   const size_t lds = irbx_lds_bytes(KS, a.Chid, false, PCO);
-  const int ntiles = irbx_pool_tiles(a.H, a.W), tpw = irbx_tiles_per_wg(a);  // every workgroup takes all channel chunks (y accumulates over them)
+  const IrbxPlan plan = irbx_plan(16 * KS, a.B, a.H, a.W, true);
+  const int tpw = plan.tpw;
   static const std::string name = std::string("expand_dw_project_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) +
                                   (PCO == 16 * KS ? std::string() : ", " + std::to_string(PCO)) + ">";
   note_kernel(name.c_str());
   if constexpr (std::is_same<T, half_t>::value) {
     if (g_irbx_stamp == 3) {  // diagnostic build: in-kernel cycle stamps (fp16 only)
       IrbxArgs b = a;
-      if (hipError_t e = irbx_dbg_buffer((size_t)(ntiles / tpw) * a.B * 4, b); e != hipSuccess) return e;
+      if (hipError_t e = irbx_dbg_buffer((size_t)plan.gx * a.B * 4, b); e != hipSuccess) return e;
       static std::atomic<uint64_t> stamp_attr_done{0};
       if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&expand_dw_project_stamp_kernel<KS, PCO>), 128 * 1024, stamp_attr_done); e != hipSuccess)
         return e;
-      hipLaunchKernelGGL((expand_dw_project_stamp_kernel<KS, PCO>), dim3(ntiles / tpw, 1, a.B), dim3(256), lds, s, b, tpw);
+      hipLaunchKernelGGL((expand_dw_project_stamp_kernel<KS, PCO>), dim3(plan.gx, plan.gy, a.B), dim3(256), lds, s, b, tpw);
       return hipGetLastError();
     }
   }
   static std::atomic<uint64_t> attr_done{0};
   if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&expand_dw_project_kernel<T, KS, PCO>), 128 * 1024, attr_done); e != hipSuccess) return e;
-  hipLaunchKernelGGL((expand_dw_project_kernel<T, KS, PCO>), dim3(ntiles / tpw, 1, a.B), dim3(256), lds, s, a, tpw);
+  hipLaunchKernelGGL((expand_dw_project_kernel<T, KS, PCO>), dim3(plan.gx, plan.gy, a.B), dim3(256), lds, s, a, tpw);
   return hipGetLastError();
 }
 template <typename T>

@@ -886,6 +886,13 @@ int llie_expand_dw_project_skip(int dtype, const void* x0, int c0, const void* x
   return kerr("expand_dw_project_skip", launch_expand_dw_project(dtype, a, cout, true, hs(stream)), LLIE_ERR_SHAPE,
               "2-byte dtype, c0 + c1 == 96, c0 % 16 == 0, cout == 32, ld % 8 == 0, H % 8 == 0, W % 16 == 0");
 }
+int llie_expand_dw_plan(int cin, int batch, int H, int W, int project, int* plan4) {
+  if (!plan4 || cin <= 0 || batch <= 0 || H <= 0 || W <= 0 || project < 0 || project > 1) return LLIE_ERR_ARG;
+  if (!irbx_supported(1, cin, cin, 4 * cin, H, W)) return LLIE_ERR_SHAPE;
+  const IrbxPlan p = irbx_plan(cin, batch, H, W, project != 0);
+  plan4[0] = p.tpw; plan4[1] = p.cpw; plan4[2] = p.gx; plan4[3] = p.gy;
+  return LLIE_OK;
+}
 int llie_irbx_project_tiles(int H, int W) { return H > 0 && W > 0 && H % 8 == 0 && W % 16 == 0 ? irbx_project_tiles(H, W) : LLIE_ERR_ARG; }
 
 int llie_dwconv3x3_tiles(int H, int W) { return dwconv_ntiles(H, W); }

@@ -186,6 +186,10 @@ constexpr int kIrbxProjectIdentity = 1, kIrbxProjectSkip = 2;  // forms of the p
 int irbx_project_supported(int dtype, int Cin, int c0, int Chid, int Cout, bool skip, int H, int W);  // 0 or the form
 int irbx_project_tiles(int H, int W);
 int irbx_stats_rows(int P);
+// launch plan of expand_dw / expand_dw_project (irbx.hip: irbx_plan): tiles per workgroup (0 = the image's tiles split evenly over
+// grid.x workgroups, knobs "irbx_grid*"), 64-channel chunks per workgroup, grid.x, grid.y (grid.z = B).  Shapes of irbx_supported only
+struct IrbxPlan { int tpw, cpw, gx, gy; };
+IrbxPlan irbx_plan(int Cin, int B, int H, int W, bool project);
 void irbx_tune(int dbuf);  // knob "irbx_dbuf"
 hipError_t launch_expand_stats(int dtype, const IrbxArgs& a, hipStream_t s);
 hipError_t launch_expand_dw(int dtype, const IrbxArgs& a, hipStream_t s);

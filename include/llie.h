@@ -779,6 +779,14 @@ int llie_expand_dw_project_skip(int dtype, const void* x0, int c0, const void* x
                                 const void* w_expand, const float* scale2, const float* shift2, const float* w_dw, const float* gate,
                                 const void* w_project_skip, int ld, int cout, void* y, float* stats, int batch, int H, int W, llie_stream stream);
 int llie_irbx_project_tiles(int H, int W);
+/* llie_expand_dw_plan: the launch plan expand_dw (project = 0) or expand_dw_project (project = 1) takes for cin input channels at
+ *   these sizes, the "irbx_grid*" knobs included (they act on expand_dw only; the dtype and the segment split do not enter).
+ *   plan4[0] = tiles per workgroup, a run along x (4, 2 or 1: the largest that divides W / 16 and keeps 2048 workgroups; 0 = the
+ *   image's tiles split evenly over grid.x workgroups, "irbx_grid*"), plan4[1] = 64-channel chunks per workgroup (all cin / 16 of
+ *   them, halved while the launch has fewer than 1024 workgroups and the count is even; project: always all), plan4[2] = grid.x,
+ *   plan4[3] = grid.y; grid.z is the batch.  LLIE_ERR_ARG: plan4 NULL, a size < 1, project not 0 or 1; LLIE_ERR_SHAPE: outside
+ *   the shapes above (cin in {32, 64, 96}, H % 8 == 0, W % 16 == 0). */
+int llie_expand_dw_plan(int cin, int batch, int H, int W, int project, int* plan4);
 /* expand_stats: the statistics pass of the same blocks on its own (knob "gram" = 0, and every recompute block below 32 768 pixels):
  * stats [batch][H W / llie_irbx_stats_rows(H W)][2][Chid] fp32 = (sum, sum of squares) of h1 = w_expand relu6(norm1(x)) per channel
  * over each run of llie_irbx_stats_rows(H W) consecutive pixels; every entry is written.  Leading arguments as expand_pool. */

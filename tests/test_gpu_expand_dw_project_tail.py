@@ -8,6 +8,7 @@ transposing reduction of y's GroupNorm partials, through the C entry points, fp1
   * operands that make every value on the way an exact dyadic number: y equals float64 and the slab equals the sums of its tile
   * reruns bit-equal, a row of the batch equal to the image alone, nothing written outside y and the slab, nothing left unwritten
 """
+import ctypes
 import importlib
 import math
 
@@ -280,14 +281,20 @@ def test_rerun_batch_rows_and_no_stray_writes(dev, form, H, W, dtype, tdt, tol):
 @pytest.mark.parametrize("form", ["32to32", "64to64", "64+32to32"])
 def test_exact_operands_runs_of_four_tiles(dev, form, dtype, tdt):
     """A workgroup takes a run of up to four tiles along x, but only in launches that keep 2 048 workgroups: every shape above
-    runs one tile per workgroup.  The smallest launch with runs of four is B = 32 at 128 x 256; there the shortcut of a tile is
-    loaded next to the prefetch of the following one and the slab entry of a tile is flushed at the top of the next.  The exact
-    operands of test_exact_operands_y_and_slab, built and referenced on the device (float64, the depthwise conv as nine shifted
-    adds): y equals the reference, each slab entry the sums of its own tile."""
+    runs one tile per workgroup (asserted through llie_expand_dw_plan, as is that this launch has runs of four).  In a run the
+    shortcut of a tile is loaded next to the prefetch of the following one and the slab entry of a tile is flushed at the top of
+    the next.  The exact operands of test_exact_operands_y_and_slab, built and referenced on the device (float64, the depthwise
+    conv as nine shifted adds): y equals the reference, each slab entry the sums of its own tile."""
     L = N.lib()
     st = torch.cuda.current_stream().cuda_stream
     cin, cout, c0, c1 = FORMS[form]
     chid, nb, H, W = 4 * cin, 32, 128, 256
+    plan = (ctypes.c_int * 4)()
+    for (sh, sw) in SHAPES:
+        N.check(L.llie_expand_dw_plan(cin, B, sh, sw, 1, plan), "expand_dw_plan")
+        assert tuple(plan) == (1, chid // 64, (sh // 8) * (sw // 16), 1)
+    N.check(L.llie_expand_dw_plan(cin, nb, H, W, 1, plan), "expand_dw_plan")
+    assert tuple(plan) == (4, chid // 64, (H // 8) * (W // 16) // 4, 1)        # runs of four, all chunks, grid.y = 1
     g = torch.Generator(device=dev).manual_seed(cin + dtype)
 
     def ri(lo, hi, *shape):
