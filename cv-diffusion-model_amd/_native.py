@@ -42,7 +42,7 @@ EXPORTS = [
     "llie_image_metrics_scratch_bytes", "llie_image_metrics_f32", "llie_image_metrics_u8", "llie_comparison_grid_u8",
     "llie_upconv_fold_elems", "llie_upconv_fold_weights", "llie_conv3x3_upfold", "llie_conv3x3_upfold_tiles",
     "llie_expand_dw", "llie_expand_pool", "llie_expand_dw_project", "llie_expand_dw_project_skip", "llie_irbx_project_tiles",
-    "llie_expand_dw_plan",
+    "llie_expand_dw_plan", "llie_wide_project_supported", "llie_irb_forms", "llie_dwconv3x3_pool", "llie_dwconv3x3_project",
     "llie_expand_stats", "llie_irbx_stats_rows",
     "llie_dwconv3x3_ex", "llie_dwconv3x3_strip_rows", "llie_last_kernel",
     "llie_init_conv", "llie_init_conv_tiles", "llie_init_conv_pack_bytes", "llie_final_conv", "llie_final_conv_pack_bytes",
@@ -262,6 +262,10 @@ def lib() -> C.CDLL:
     L.llie_expand_dw_project_skip.argtypes = [ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, vp, vp, ci, ci, ci, vp]
     L.llie_irbx_project_tiles.argtypes = [ci, ci]
     L.llie_expand_dw_plan.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ci)]
+    L.llie_wide_project_supported.argtypes = [ci] * 9
+    L.llie_irb_forms.argtypes = [vp, ci, ci, C.POINTER(ci), ci]
+    L.llie_dwconv3x3_pool.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
+    L.llie_dwconv3x3_project.argtypes = [ci, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp, ci, ci, vp, vp, ci, ci, ci, vp]
     L.llie_expand_stats.argtypes = [ci, vp, ci, vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]
     L.llie_irbx_stats_rows.argtypes = [ci]
     L.llie_tune.argtypes = [C.c_char_p, ci]

@@ -256,6 +256,7 @@ struct Knobs {
   int use_irbx;       // "irbx": recompute form of the inverted-residual block (irbx.hip) wherever irbx_supported()
   int irbx_project;   // "irbx_project": recompute blocks without h2 (expand_pool + expand_dw_project): 1 = every shape irbx_project_supported
                       // names, 2 = its identity-residual shapes only, 0 = none (expand_dw + project GEMM)
+  int wide_project;   // "wide_project": the wide decoder blocks wide_project_supported names without h2 (dwconv3x3_pool + dwconv3x3_project)
   int gram;           // "gram": norm2 statistics of the recompute form from the Gram matrix (gram.hip); 0 = expand_stats; 2 = at every size
   int nt_min_mb;      // "nt_min_mb": tensors of at least this many MiB are stored non-temporally by the producers in nt_mask
   int nt_mask;        // "nt_mask": 1 expand_dw, 2 pw_expand, 4 dwconv3x3, 8 project / attention GEMMs, 16 dense 3x3 convs
@@ -274,7 +275,10 @@ constexpr int kGraphMaxSteps = 20;  // default of Knobs::graph_max_steps: captur
 //   recompute  2-byte inference, narrow inputs: a statistics-only expand pass, then expand_dw rebuilds h1 on the fly (irbx.hip)
 //   project    identity-residual recompute blocks and the 96 -> 32 skip-conv block go without h2 too: the SE pool totals come from a
 //              pass that only rebuilds h1 (expand_pool); given the gate, expand_dw_project applies Wp itself and adds the shortcut
-enum IrbForm { kIrbUnfused, kIrbRecompute, kIrbProject };
+//   wide       the 192 -> 64 and 384 -> 128 decoder blocks (2-byte inference): unfused up to norm2 -- h1 is stored, recomputing it is
+//              too dear -- then the SE pool totals from one read of h1 (dwconv3x3_pool) and, given the gate, depthwise + project +
+//              skip conv in one kernel (dwconv3x3_project): h2 is never allocated
+enum IrbForm { kIrbUnfused, kIrbRecompute, kIrbProject, kIrbWide };
 struct IrbPath {
   IrbForm form;
   // 2-byte inference engines carry norm1's ReLU6 as clamp01(z / 6): the tables come out divided by 6 and the expand GEMM (or the
@@ -294,6 +298,11 @@ struct IrbPath {
 // dtype and the knobs alone -- never on the batch or the grid, which would break batch invariance.
 inline IrbPath irb_path(int dt, const IrbW& w, int c0, int H, int W, bool training) {
   IrbPath p{kIrbUnfused, !training && dt != LLIE_F32, !training && w.hid % 128 == 0, false};
+  if (p.fixtot && p.s6 && g_knobs.wide_project &&
+      wide_project_supported(dt, w.cin, c0, w.hid, w.cout, w.skip, w.hid != w.hid_r || w.cin != w.cin_r || w.cout != w.cout_r, H, W)) {
+    p.form = kIrbWide;
+    return p;
+  }
   // (!fixtot: the recompute kernels only know the fixed-point totals; every hid irbx_supported accepts is a multiple of 128)
   if (!p.fixtot || !g_knobs.use_irbx || w.hid != w.hid_r || w.cin != w.cin_r || !irbx_supported(dt, w.cin, c0, w.hid, H, W)) return p;
   p.gram = g_knobs.gram && (H * W >= 32768 || g_knobs.gram > 1) && gram_supported(dt, w.cin, c0, H * W);

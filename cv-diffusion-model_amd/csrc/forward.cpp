@@ -154,6 +154,21 @@ struct Run : Exec {
       }
     }
     gn(h1, nullptr, w.n2g, w.n2b, film, film_stride, t.as2, t.ab2, &rec.n2, path.s6 ? 1.f / 6.f : 0.f);
+    if (path.form == kIrbWide) {
+      // wide form: no h2.  The pool totals from one read of h1 (nine sums); h1 and norm2's tables stay for dwconv3x3_project
+      t.dnt = irbx_project_tiles(H, W);
+      t.ptot = ztake((size_t)B * w.hid * 8);
+      if (!dry) {
+        t.xa = IrbxArgs{};
+        t.xa.h1 = p(h1.off); t.xa.as2 = p<float>(t.as2); t.xa.ab2 = p<float>(t.ab2); t.xa.wd = wptr<float>(w.w_dw);
+        t.xa.B = B; t.xa.H = H; t.xa.W = W; t.xa.Chid = w.hid;
+        IrbxArgs a = t.xa;
+        a.pool_tot = p<unsigned long long>(t.ptot);
+        timed(LLIE_K_DW, (int64_t)M * w.hid * (int64_t)es(), [&] { return launch_dwconv3x3_pool(dt, a, s); });
+      }
+      rel(t.as1); rel(t.ab1); rel(h1.slab);
+      return;
+    }
     t.dnt = dwconv_ntiles(H, W);
     t.h2 = ar->alloc((size_t)M * w.hid * es());
     t.pool = path.fixtot ? 0 : ar->alloc((size_t)B * t.dnt * w.hid * 4);
@@ -291,6 +306,22 @@ struct Run : Exec {
     return y;
   }
 
+  // wide form: dwconv3x3_project reads the stored h1 with its halo (180 pixels per 128), the raw input for the skip conv, and writes y
+  Tens project_wide(const IrbW& w, const Tens& x0, const Tens* x1, IrbTmp& t) {
+    const int H = x0.H, W = x0.W, M = B * H * W;
+    Tens y = new_tens(w.cout, H, W, irbx_project_tiles(H, W), w.cout_r);
+    if (!dry) {
+      IrbxArgs a = t.xa;
+      a.x0 = p(x0.off); a.c0 = x0.C; a.x1 = x1 ? p(x1->off) : nullptr; a.c1 = x1 ? x1->C : 0;
+      a.gate = p<float>(t.gate); a.wp = wptr(w.w_proj); a.y = p(y.off); a.ystats = p<float>(y.slab);
+      a.ldp = w.hid + w.cin;  // project and skip share one K-concatenated matrix (model.cpp)
+      timed(LLIE_K_DW, ((int64_t)M * w.hid * 45 / 32 +(int64_t)M * (w.cin + w.cout) + (int64_t)w.cout * (w.hid + w.cin)) * (int64_t)es(),
+            [&] { return launch_dwconv3x3_project(dt, a, w.cout, s); });
+    }
+    rel(t.h1.off); rel(t.as2); rel(t.ab2); rel(t.gate);
+    return y;
+  }
+
   // InvertedResidualBlock.forward (efficient_unet.py:203-236) in the form irb_path picks (engine.h): 7 launches unfused
   Tens irb(const IrbW& w, const Tens& x0, const Tens* x1, const float* film, int64_t film_stride) {
     const int P = x0.H * x0.W;
@@ -300,10 +331,10 @@ struct Run : Exec {
     snprintf(tag, sizeof tag, "irb P=%d %d->%d hid=%d", P, w.cin, w.cout, w.hid);
     gn(x0, x1, w.n1g, w.n1b, nullptr, 0, t.as1, t.ab1, &rec.n1, path.s6 ? 1.f / 6.f : 0.f);
     const float* film2 = film ? film + w.film_off : nullptr;  // this block's rows of the FiLM projection
-    if (path.form == kIrbUnfused) front_unfused(path, w, x0, x1, film2, film_stride, rec, t);
+    if (path.form == kIrbUnfused || path.form == kIrbWide) front_unfused(path, w, x0, x1, film2, film_stride, rec, t);
     else front_recompute(path, w, x0, x1, film2, film_stride, t);
     se_gate(path, w, P, t);
-    Tens y = path.form == kIrbProject ? project_fused(w, x0, t) : project_gemm(w, x0, x1, t);
+    Tens y = path.form == kIrbProject ? project_fused(w, x0, t) : path.form == kIrbWide ? project_wide(w, x0, x1, t) : project_gemm(w, x0, x1, t);
     if (tape) {
       rec.w = (int)(&w - c->irbs.data());
       rec.x0 = x0; rec.cat = x1 != nullptr;

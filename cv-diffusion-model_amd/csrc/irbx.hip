@@ -957,11 +957,14 @@ __device__ __forceinline__ void irbx_project_store_y(const IrbxArgs& a, const Ir
   // bitwise independent of the batch and the schedule.
 #pragma unroll
   for (int grp = 0; grp < NCB / 2; ++grp) {
-    float v[16];  // PCO = 32: (which, cb, e) = (j >> 3, (j >> 2) & 1, j & 3); PCO = 64: which = grp, (cb, e) = (j >> 2, j & 3)
+    // PCO = 32: (which, cb, e) = (j >> 3, (j >> 2) & 1, j & 3); PCO = 64, 128: which = grp / (NCB / 4), blocks cb = cb0 + (j >> 2), e = j & 3
+    constexpr int GPW = NCB >= 4 ? NCB / 4 : 1;  // groups per `which`
+    const int cb0 = 4 * (grp % GPW);
+    float v[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
       if constexpr (NCB == 2) v[j] = st[j >> 3][j & 7];
-      else v[j] = st[grp][j];
+      else v[j] = st[grp / GPW][4 * cb0 + j];
     }
     asm volatile("s_nop 1" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]),
                              "+v"(v[8]), "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]));
@@ -981,7 +984,7 @@ __device__ __forceinline__ void irbx_project_store_y(const IrbxArgs& a, const Ir
 #undef LLIE_DPP_STEP
     if ((li & 3) == 0) {  // red[wave][which][channel 16 cb + 4 g + e]: quad k of the row holds (which, cb) = (k >> 1, k & 1) or (grp, k)
       const int k = li >> 2;
-      const int which = NCB == 2 ? k >> 1 : grp, cb = NCB == 2 ? k & 1 : k;
+      const int which = NCB == 2 ? k >> 1 : grp / GPW, cb = NCB == 2 ? k & 1 : cb0 + k;
       *reinterpret_cast<f32x4*>(red + (wave * 2 + which) * PCO + 16 * cb + 4 * g) = f32x4{v[0], v[1], v[2], v[3]};
     }
   }
@@ -1444,6 +1447,343 @@ hipError_t launch_expand_dw_project(int dtype, const IrbxArgs& a0, int cout, boo
 hipError_t launch_expand_dw(int dtype, const IrbxArgs& a, hipStream_t s) {
   if (!irbx_supported(dtype, a.c0 + a.c1, a.c0, a.Chid, a.H, a.W) || (a.c1 && !a.x1) || !a.out) return hipErrorInvalidValue;
   return dtype == 1 ? launch_dw_t<half_t>(a, s) : launch_dw_t<bf16_t>(a, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// (3) The wide decoder blocks (192 -> 64 at hid 768, 384 -> 128 at hid 1536) without h2, from the STORED h1.  Recomputing h1 is
+// too dear there (155 GFLOP per pass), so pw_expand still writes it; what goes is the depthwise output: written once and read
+// once only because SE needs its pooled mean before the projection may start.
+//   dwconv3x3_pool_kernel     one streaming read of h1 leaves the SE pool totals: the nine-sum restatement of expand_scan<POOL>
+//                             with a = clamp01(h1 s + b) rounded to T exactly where the project kernel rounds the tile it parks
+//                             in LDS, and the weights T(6 w);
+//   dwconv3x3_project_kernel  a workgroup owns one 8 x 16 tile: per 64-channel chunk it loads the 10 x 18 halo tile of h1,
+//                             activates it into the LDS tile of the recompute kernels (that replaces their expand phase) and
+//                             runs their depthwise steps, pack-and-swap and project MFMAs; y accumulates in registers over the
+//                             chunks, starts as the skip conv of the raw input and leaves through irbx_project_store_y.
+// as2 / ab2 are norm2's tables divided by 6 (IrbxArgs::h1).
+
+// The pool pass.  grid (H / 8, Chid / 128, B): a workgroup reads 8 image rows of 128 channels; thread (cv = tid & 15, pg = tid >> 4)
+// owns 8 channels of the pixels pg, pg + 16, ... of those rows, eight loads in flight.  Sums per thread: everything, the first and
+// the last image row (a row's sum is added where the row ends: a uniform branch); the first / last column and the corners come
+// from one more load per thread (pg < 8: column 0 of row pg, else column W - 1 of row pg - 8; the lines are in L2).  The 16 pixel
+// slots are added in slot order through LDS, the nine sums combined with the weights and one fixed-point atomic per channel
+// leaves the workgroup: the float order depends on (H, W, Chid) alone, the integer adds commute.
+constexpr int kWpRows = 8;
+template <typename T>
+__global__ void __launch_bounds__(256) dwconv3x3_pool_kernel(const IrbxArgs a) {
+  typedef typename Elem<T>::vec_t vec_t;
+  __shared__ __align__(16) float red[4][16][128];  // everything, first row, last row, column pixels
+  const int tid = threadIdx.x, cv = tid & 15, pg = tid >> 4;
+  const int b = blockIdx.z, cbase = blockIdx.y * 128, y0 = blockIdx.x * kWpRows;
+  const int c8 = cbase + cv * 8;
+  const T* h1 = reinterpret_cast<const T*>(a.h1) + (size_t)b * a.H * a.W * a.Chid + c8;
+  float sc[8], sh[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    sc[e] = a.as2[(size_t)b * a.Chid + c8 + e];
+    sh[e] = a.ab2[(size_t)b * a.Chid + c8 + e];
+  }
+  auto act = [&](vec_t v, float (&f)[8]) {  // a in T, as fp32
+    const u32x4 x = reinterpret_cast<const u32x4&>(v);
+    u32x4 o;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[q] = act_clamp01_pack<T>(x[q], sc[2 * q], sc[2 * q + 1], sh[2 * q], sh[2 * q + 1]);
+    vec_to_f32<T>(reinterpret_cast<const vec_t&>(o), f);
+  };
+  float all[8], r0[8], rh[8], row[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) all[e] = r0[e] = rh[e] = row[e] = 0.f;
+  const int n = kWpRows * a.W / 16;  // a multiple of 8 (W % 16 == 0)
+  const size_t step = (size_t)16 * a.Chid;
+  const T* p = h1 + ((size_t)y0 * a.W + pg) * a.Chid;
+  int col = 0, gy = y0;
+  for (int i0 = 0; i0 < n; i0 += 8) {
+    vec_t v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) v[u] = ld_vec<T>(p + (size_t)(i0 + u) * step);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      float f[8];
+      act(v[u], f);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) row[e] += f[e];
+      col += 16;
+      if (col == a.W) {  // uniform: an image row ends
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          all[e] += row[e];
+          if (gy == 0) r0[e] += row[e];
+          if (gy == a.H - 1) rh[e] += row[e];
+          row[e] = 0.f;
+        }
+        col = 0; ++gy;
+      }
+    }
+  }
+  float cf[8];
+  act(ld_vec<T>(h1 + ((size_t)(y0 + (pg & 7)) * a.W + (pg >= 8 ? a.W - 1 : 0)) * a.Chid), cf);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    red[0][pg][cv * 8 + e] = all[e];
+    red[1][pg][cv * 8 + e] = r0[e];
+    red[2][pg][cv * 8 + e] = rh[e];
+    red[3][pg][cv * 8 + e] = cf[e];
+  }
+  wg_barrier();
+  if (tid < 128) {
+    const int c = tid;
+    float v[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // as in expand_scan: all, first / last row, first / last column, corners
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+      v[0] += red[0][s][c]; v[1] += red[1][s][c]; v[2] += red[2][s][c];
+    }
+#pragma unroll
+    for (int s = 0; s < 8; ++s) {
+      v[3] += red[3][s][c]; v[4] += red[3][8 + s][c];
+    }
+    if (y0 == 0) { v[5] = red[3][0][c]; v[6] = red[3][8][c]; }
+    if (y0 + kWpRows == a.H) { v[7] = red[3][7][c]; v[8] = red[3][15][c]; }
+    float t = 0.f;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {  // tap (ky, kx) reads pixel p + (ky - 1, kx - 1): p itself must leave the far border out
+      const int ky = tap / 3, kx = tap % 3;
+      float st = v[0];
+      if (ky == 2) st -= v[1];
+      if (ky == 0) st -= v[2];
+      if (kx == 2) st -= v[3];
+      if (kx == 0) st -= v[4];
+      if (ky == 2 && kx == 2) st += v[5];
+      if (ky == 2 && kx == 0) st += v[6];
+      if (ky == 0 && kx == 2) st += v[7];
+      if (ky == 0 && kx == 0) st += v[8];
+      t = __builtin_fmaf((float)(T)(6.f * a.wd[tap * a.Chid + cbase + c]), st, t);
+    }
+    fixed_add(a.pool_tot + (size_t)b * a.Chid + cbase + c, t, kPoolFixScale);
+  }
+}
+
+// The depthwise-project pass.  grid (tiles, 1, B), four waves.  Dynamic LDS: [sH: 192 x 144 B][wds: 10 x Chid T][wpl: PCO x 144 B]
+// [red: 4 x 2 x PCO fp32].  The SE gate is part of the staged depthwise weights, T(6 w gate), as in expand_dw_project<2, 32> and
+// <6, 32>.  The depthwise phase is the MFMA form (irbx_dw_two_tap): the project MFMAs want its accumulator layout, and the VALU
+// has the activation of the halo tile to do.  Thread (kv = tid & 7, q0 = tid >> 3) stages the 16-byte channel vector kv of the
+// halo pixels q0 + 32 j of every chunk: the six loads of a later chunk go out before this chunk's depthwise phase.
+// The chunk's project columns of Wp go through LDS too ([PCO rows][64 channels + 16 B pad], the pitch of the h1 tile): loaded once
+// per workgroup with whole 128-byte rows, read as MFMA A fragments by all four waves.  Fetched by every wave as fragments straight
+// from memory -- 16 rows x 64 bytes per load instruction -- they cost more than everything else in the chunk (profiles/r21/README.md).
+constexpr size_t wide_lds_bytes(int Chid, int PCO) { return (size_t)kXNPB * 32 * SHP + 10 * Chid * 2 + PCO * SHP + 8 * PCO * 4; }
+static_assert(2 * wide_lds_bytes(768, 64) <= 160 * 1024 && 2 * wide_lds_bytes(1536, 128) <= 160 * 1024, "two workgroups per CU");
+template <typename T, int PCO>
+__global__ void __launch_bounds__(256, 2) dwconv3x3_project_kernel(const IrbxArgs a) {
+  constexpr int NCB = PCO / 16, NPASS = kXNPB * 32 / 32;
+  // chunks the halo tile is fetched ahead: two at 64 output channels; at 128 the y accumulators and the skip conv's operands leave
+  // room for one set of staging registers only (two sets spill 80 registers)
+  constexpr int DEPTH = PCO == 64 ? 2 : 1;
+  typedef typename Elem<T>::vec_t vec_t;
+  extern __shared__ __align__(16) unsigned char smem[];
+  unsigned char* buf = smem;
+  T* wds = reinterpret_cast<T*>(smem + kXNPB * 32 * SHP);
+  unsigned char* wpl = smem + kXNPB * 32 * SHP + 10 * a.Chid * 2;
+  float* red = reinterpret_cast<float*>(wpl + PCO * SHP);
+
+  const IrbxLane t = irbx_lane();
+  const int tid = t.tid, wave = t.wave, li = t.li, g = t.g;
+  const int b = blockIdx.z;
+  const int tiles_x = a.W / kXT_W;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x % tiles_x;
+  const int y0 = ty * kXT_H, x0p = tx * kXT_W;
+  const int P = a.H * a.W, Cin = a.c0 + a.c1;
+  const T* x0 = reinterpret_cast<const T*>(a.x0) + (size_t)b * P * a.c0;
+  const T* x1 = a.x1 ? reinterpret_cast<const T*>(a.x1) + (size_t)b * P * a.c1 : nullptr;
+  const T* h1 = reinterpret_cast<const T*>(a.h1) + (size_t)b * P * a.Chid;
+  const int nchunks = a.Chid / 64;
+
+  // the thread's six halo pixels: offset inside the image's h1 (its channel vector included), and whether the pixel exists --
+  // outside the image the depthwise input is zero (the conv's padding), and pixels 180..191 of the last MFMA block do not exist
+  const int kv = tid & 7, q0 = tid >> 3;
+  // Every thread loads all six, from a pixel clamped into the image where its own does not exist: unpredicated loads are
+  // counted exactly by hipcc's vmcnt bookkeeping, so the wait for one chunk's operands leaves the younger prefetch in flight
+  // (a lane-predicated load makes it wait for everything: profiles/r20/README.md, section 1).  The tile is fetched DEPTH chunks
+  // ahead: two workgroups per CU have to keep enough bytes in flight for the memory latency (profiles/r21/README.md).
+  int hoff[NPASS];
+  bool hok[NPASS];
+#pragma unroll
+  for (int j = 0; j < NPASS; ++j) {
+    const int q = q0 + 32 * j;
+    const int gy = y0 - 1 + q / kXH_W, gx = x0p - 1 + q % kXH_W;
+    hok[j] = q < kXNPX && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+    const int cy = gy < 0 ? 0 : (gy < a.H ? gy : a.H - 1), cx = gx < 0 ? 0 : (gx < a.W ? gx : a.W - 1);
+    hoff[j] = (cy * a.W + cx) * a.Chid + kv * 8;
+  }
+  // with the tile come norm2's tables of the thread's 8 channels of that chunk: scale (2 x 4), then shift
+  vec_t raw[DEPTH][NPASS];
+  f32x4 aff[DEPTH][4];
+  const float* as2 = a.as2 + (size_t)b * a.Chid + kv * 8;
+  const float* ab2 = a.ab2 + (size_t)b * a.Chid + kv * 8;
+  auto load = [&](int chunk, vec_t (&dst)[NPASS], f32x4 (&af)[4]) {
+#pragma unroll
+    for (int j = 0; j < NPASS; ++j) dst[j] = ld_vec<T>(h1 + hoff[j] + chunk * 64);
+    af[0] = *reinterpret_cast<const f32x4*>(as2 + chunk * 64); af[1] = *reinterpret_cast<const f32x4*>(as2 + chunk * 64 + 4);
+    af[2] = *reinterpret_cast<const f32x4*>(ab2 + chunk * 64); af[3] = *reinterpret_cast<const f32x4*>(ab2 + chunk * 64 + 4);
+  };
+  // the chunk's Wp block: vector v = tid + 256 j -> row v / 8, 16-byte channel vector v % 8; one chunk ahead
+  constexpr int NWV = PCO * 8 / 256;
+  vec_t wreg[NWV];
+  auto load_wp = [&](int chunk) {
+#pragma unroll
+    for (int j = 0; j < NWV; ++j) wreg[j] = ld_vec<T>(reinterpret_cast<const T*>(a.wp) + (size_t)(q0 + 32 * j) * a.ldp + chunk * 64 + kv * 8);
+  };
+  load_wp(0);
+#pragma unroll
+  for (int d = 0; d < DEPTH; ++d) load(d, raw[d], aff[d]);
+  // The constants of irbx_stage_constants, [tap pair][channel][2] weights and the two tables.  A workgroup serves ONE tile, so
+  // their staging is not amortised over a run of tiles: a thread owns channels tid + 256 k and all its loads (nine weights, the
+  // gate, two table entries per channel) go out together -- as a loop over the 10 Chid weight slots, one dependent pair of loads
+  // per iteration, the staging alone took 30 (60) memory round trips per workgroup, most of the kernel (profiles/r21/README.md)
+  {
+    constexpr int KC = 12 * PCO / 256;  // Chid / 256: 3 or 6 channels per thread
+    float wv[KC][9], gv[KC];
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {
+      const int c = tid + 256 * k;
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) wv[k][tap] = a.wd[tap * a.Chid + c];
+      gv[k] = a.gate[(size_t)b * a.Chid + c];
+    }
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {
+      const int c = tid + 256 * k;
+#pragma unroll
+      for (int p = 0; p < 5; ++p) {
+        wds[2 * (p * a.Chid + c)] = (T)(6.f * wv[k][2 * p] * gv[k]);
+        wds[2 * (p * a.Chid + c) + 1] = p < 4 ? (T)(6.f * wv[k][2 * p + 1] * gv[k]) : (T)0.f;
+      }
+    }
+  }
+
+  // y[32 pixels][PCO] of the wave starts as Wskip . x on the raw centre pixels: Cin / 32 k-steps (expand_dw_project_body's skip
+  // form).  The x operands of six k-steps go out together (they come from HBM), the weight rows two k-steps at a time (L2)
+  f32x4 yacc[2][NCB];
+#pragma unroll
+  for (int r = 0; r < 2; ++r)
+#pragma unroll
+    for (int cb = 0; cb < NCB; ++cb) yacc[r][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  {
+    const T* wsk = reinterpret_cast<const T*>(a.wp) + (size_t)li * a.ldp + a.Chid + 8 * g;
+    const size_t pix0 = (size_t)(y0 + 2 * wave) * a.W + x0p + li;
+#pragma unroll 1
+    for (int ks0 = 0; ks0 < Cin / 32; ks0 += 6) {  // Cin / 32 is 6 or 12
+      vec_t xsv[6][2];
+#pragma unroll
+      for (int u = 0; u < 6; ++u) {
+        const int ch = 32 * (ks0 + u) + 8 * g;
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+          const size_t pix = pix0 + (size_t)r * a.W;
+          xsv[u][r] = ch < a.c0 ? ld_vec<T>(x0 + pix * a.c0 + ch) : ld_vec<T>(x1 + pix * a.c1 + (ch - a.c0));
+        }
+      }
+#pragma unroll
+      for (int u0 = 0; u0 < 6; u0 += 2) {
+        vec_t wsf[2][NCB];
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+          for (int cb = 0; cb < NCB; ++cb) wsf[u][cb] = ld_vec<T>(wsk + (size_t)cb * 16 * a.ldp + 32 * (ks0 + u0 + u));
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+          for (int r = 0; r < 2; ++r)
+#pragma unroll
+            for (int cb = 0; cb < NCB; ++cb) yacc[r][cb] = mfma16x16<T>(wsf[u][cb], xsv[u0 + u][r], yacc[r][cb]);
+      }
+    }
+  }
+
+  const int choff = irbx_choff(g);  // the lane's 8 channels of a 32-channel half after the swap below
+  // one chunk: `cur` holds its halo tile and is refilled with the tile of chunk + 2 once it has been activated into sH
+  auto chunk_step = [&](const int chunk, vec_t (&cur)[NPASS], f32x4 (&af)[4]) {
+    wg_barrier();  // weights staged (first chunk); previous depthwise phase done with sH, previous project phase with wpl
+#pragma unroll
+    for (int j = 0; j < NPASS; ++j) {  // activate8 on tables held in registers
+      const u32x4 x = reinterpret_cast<const u32x4&>(cur[j]);
+      u32x4 o;
+      o[0] = act_clamp01_pack<T>(x[0], af[0][0], af[0][1], af[2][0], af[2][1]);
+      o[1] = act_clamp01_pack<T>(x[1], af[0][2], af[0][3], af[2][2], af[2][3]);
+      o[2] = act_clamp01_pack<T>(x[2], af[1][0], af[1][1], af[3][0], af[3][1]);
+      o[3] = act_clamp01_pack<T>(x[3], af[1][2], af[1][3], af[3][2], af[3][3]);
+      *reinterpret_cast<u32x4*>(buf + (q0 + 32 * j) * SHP + kv * 16) = hok[j] ? o : u32x4{0u, 0u, 0u, 0u};
+    }
+#pragma unroll
+    for (int j = 0; j < NWV; ++j) *reinterpret_cast<vec_t*>(wpl + (q0 + 32 * j) * SHP + kv * 16) = wreg[j];
+    // the next chunk's Wp block goes out BEFORE the halo prefetch: the wait for it at the top of the next chunk (vmcnt counts in
+    // order) then leaves the younger prefetch in flight
+    load_wp(chunk + 1 < nchunks ? chunk + 1 : chunk);
+    __builtin_amdgcn_sched_barrier(0);
+    load(chunk + DEPTH < nchunks ? chunk + DEPTH : chunk, cur, af);  // (the last DEPTH refills are never used)
+    wg_barrier();
+    // depthwise: rows 2 wave, 2 wave + 1 of the tile x the chunk's four 16-channel tiles; the accumulators hold gate * h2
+    f32x4 dacc[4][2];
+    irbx_dw_two_tap<T, 2, 4>(dacc, buf, wave, 0, wds, chunk, a.Chid, t);
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+      for (int kb = 0; kb < 2; ++kb) {
+        const u32x4 v = irbx_pack8_swap<T>(dacc[2 * kb][r], dacc[2 * kb + 1][r]);  // channels 32 kb + choff .. + 7 of pixel li
+#pragma unroll
+        for (int cb = 0; cb < NCB; ++cb)  // A fragment: rows 16 cb + li of Wp, k = the lane's 8 channels of half kb
+          yacc[r][cb] = mfma16x16<T>(*reinterpret_cast<const vec_t*>(wpl + (16 * cb + li) * SHP + (32 * kb + choff) * 2),
+                                     reinterpret_cast<const vec_t&>(v), yacc[r][cb]);
+      }
+  };
+#pragma unroll 1
+  for (int chunk = 0; chunk < nchunks; chunk += DEPTH) {  // Chid / 64 is 12 or 24
+#pragma unroll
+    for (int d = 0; d < DEPTH; ++d) chunk_step(chunk + d, raw[d], aff[d]);
+  }
+  irbx_project_store_y<T, PCO>(a, t, yacc, b, y0, x0p, red);
+  wg_barrier();
+  if (tid < 2 * PCO)  // the four waves' (sum, sum of squares) [wave][2][PCO], added in wave order
+    a.ystats[((size_t)b * gridDim.x + blockIdx.x) * 2 * PCO + tid] = (red[tid] + red[2 * PCO + tid]) + (red[4 * PCO + tid] + red[6 * PCO + tid]);
+}
+
+bool wide_project_supported(int dtype, int Cin, int c0, int Chid, int Cout, bool skip, bool padded, int H, int W) {
+  if ((dtype != 1 && dtype != 2) || padded || !skip) return false;
+  if (!((Cin == 192 && Chid == 768 && Cout == 64) || (Cin == 384 && Chid == 1536 && Cout == 128))) return false;
+  if (c0 <= 0 || c0 > Cin || c0 % 16) return false;
+  if (H <= 0 || W <= 0 || (long long)H * W * Chid >= (1ll << 31)) return false;  // the project kernel's halo offsets are 32-bit
+  return H % kXT_H == 0 && W % kXT_W == 0;
+}
+// pool_tot += the image's SE pool totals (fixed point, kPoolFixScale); the caller zeroes it
+hipError_t launch_dwconv3x3_pool(int dtype, const IrbxArgs& a, hipStream_t s) {
+  if ((dtype != 1 && dtype != 2) || (a.Chid != 768 && a.Chid != 1536) || a.B <= 0 || a.H <= 0 || a.W <= 0 || a.H % kWpRows || a.W % 16 || !a.h1 ||
+      !a.pool_tot || !a.as2 || !a.ab2 || !a.wd)
+    return hipErrorInvalidValue;
+  const dim3 grid(a.H / kWpRows, a.Chid / 128, a.B);
+  static const std::string names[2] = {std::string("dwconv3x3_pool_kernel<") + TypeName<half_t>::value + ">",
+                                       std::string("dwconv3x3_pool_kernel<") + TypeName<bf16_t>::value + ">"};
+  note_kernel(names[dtype - 1].c_str());
+  if (dtype == 1) hipLaunchKernelGGL((dwconv3x3_pool_kernel<half_t>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((dwconv3x3_pool_kernel<bf16_t>), grid, dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+template <typename T, int PCO>
+static hipError_t launch_wide_project_cfg(const IrbxArgs& a, hipStream_t s) {
+  static const std::string name = std::string("dwconv3x3_project_kernel<") + TypeName<T>::value + ", " + std::to_string(PCO) + ">";
+  note_kernel(name.c_str());
+  static std::atomic<uint64_t> attr_done{0};
+  if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&dwconv3x3_project_kernel<T, PCO>), 128 * 1024, attr_done); e != hipSuccess) return e;
+  hipLaunchKernelGGL((dwconv3x3_project_kernel<T, PCO>), dim3(irbx_project_tiles(a.H, a.W), 1, a.B), dim3(256), wide_lds_bytes(a.Chid, PCO), s, a);
+  return hipGetLastError();
+}
+// y = Wp . (gate * dw3x3(clamp01(h1 as2 + ab2) x 6 w)) + Wskip . [x0 | x1] with y's statistics slab [B][irbx_project_tiles][2][cout];
+// wp [cout][a.ldp] = project columns, then skip columns (a.ldp >= Chid + Cin, a.ldp % 8 == 0)
+hipError_t launch_dwconv3x3_project(int dtype, const IrbxArgs& a, int cout, hipStream_t s) {
+  const int Cin = a.c0 + a.c1;
+  if (!wide_project_supported(dtype, Cin, a.c0, a.Chid, cout, true, false, a.H, a.W) || a.B <= 0 || (a.c1 != 0) != (a.x1 != nullptr) || !a.x0 ||
+      a.ldp < a.Chid + Cin || a.ldp % 8 || !a.h1 || !a.gate || !a.wp || !a.y || !a.ystats || !a.as2 || !a.ab2 || !a.wd)
+    return hipErrorInvalidValue;
+  if (cout == 64) return dtype == 1 ? launch_wide_project_cfg<half_t, 64>(a, s) : launch_wide_project_cfg<bf16_t, 64>(a, s);
+  return dtype == 1 ? launch_wide_project_cfg<half_t, 128>(a, s) : launch_wide_project_cfg<bf16_t, 128>(a, s);
 }
 
 }  // namespace llie

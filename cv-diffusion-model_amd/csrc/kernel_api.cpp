@@ -893,6 +893,29 @@ int llie_expand_dw_plan(int cin, int batch, int H, int W, int project, int* plan
   plan4[0] = p.tpw; plan4[1] = p.cpw; plan4[2] = p.gx; plan4[3] = p.gy;
   return LLIE_OK;
 }
+// ---- wide decoder blocks without h2, from the stored h1 (irbx.hip, section 3)
+int llie_wide_project_supported(int dtype, int cin, int c0, int chid, int cout, int skip, int padded, int H, int W) {
+  return wide_project_supported(dtype, cin, c0, chid, cout, skip != 0, padded != 0, H, W) ? 1 : 0;
+}
+static const char* kWideShapes = "2-byte dtype, skip conv, (c0 + c1, Chid, cout) in {(192, 768, 64), (384, 1536, 128)}, c0 % 16 == 0, H % 8 == 0, W % 16 == 0";
+int llie_dwconv3x3_pool(int dtype, const void* h1, const float* scale2, const float* shift2, const float* w_dw, unsigned long long* pool_totals,
+                        int batch, int H, int W, int chid, llie_stream stream) {
+  if (!h1 || !scale2 || !shift2 || !w_dw || !pool_totals || batch <= 0) return LLIE_ERR_ARG;
+  IrbxArgs a{};
+  a.h1 = h1; a.as2 = scale2; a.ab2 = shift2; a.wd = w_dw; a.pool_tot = pool_totals; a.B = batch; a.H = H; a.W = W; a.Chid = chid;
+  return kerr("dwconv3x3_pool", launch_dwconv3x3_pool(dtype, a, hs(stream)), LLIE_ERR_SHAPE, "2-byte dtype, Chid in {768, 1536}, H % 8 == 0, W % 16 == 0");
+}
+int llie_dwconv3x3_project(int dtype, const void* h1, const float* scale2, const float* shift2, const float* w_dw, const float* gate, const void* x0,
+                           int c0, const void* x1, int c1, const void* w_project_skip, int ld, int cout, void* y, float* stats, int batch, int H,
+                           int W, llie_stream stream) {
+  if (!h1 || !scale2 || !shift2 || !w_dw || !gate || !x0 || !w_project_skip || !y || !stats || batch <= 0 || c0 <= 0 || c1 < 0 ||
+      (c1 > 0) != (x1 != nullptr) || cout <= 0 || ld < 5 * (c0 + c1))
+    return LLIE_ERR_ARG;
+  IrbxArgs a{};
+  a.h1 = h1; a.as2 = scale2; a.ab2 = shift2; a.wd = w_dw; a.gate = gate; a.x0 = x0; a.c0 = c0; a.x1 = x1; a.c1 = c1; a.wp = w_project_skip;
+  a.ldp = ld; a.y = y; a.ystats = stats; a.B = batch; a.H = H; a.W = W; a.Chid = 4 * (c0 + c1);
+  return kerr("dwconv3x3_project", launch_dwconv3x3_project(dtype, a, cout, hs(stream)), LLIE_ERR_SHAPE, kWideShapes);
+}
 int llie_irbx_project_tiles(int H, int W) { return H > 0 && W > 0 && H % 8 == 0 && W % 16 == 0 ? irbx_project_tiles(H, W) : LLIE_ERR_ARG; }
 
 int llie_dwconv3x3_tiles(int H, int W) { return dwconv_ntiles(H, W); }

@@ -176,7 +176,18 @@ struct IrbxArgs {
   // columns [Chid, Chid + Cin) of wp are the skip conv's weights (the engine's K-concatenated matrix)
   const float* gate; const void* wp; void* y; float* ystats;
   int ldp;
+  // wide decoder blocks (dwconv3x3_pool / dwconv3x3_project, below): the stored h1 [B][H][W][Chid] T; as2 / ab2 are then norm2's
+  // tables DIVIDED BY 6 (the s6 form of DwArgs), since h1 is the real tensor and not an accumulator / 6
+  const void* h1;
 };
+// Wide decoder blocks without h2 (irbx.hip), from the stored h1: dwconv3x3_pool adds the SE pool totals from nine sums of
+// a = clamp01(h1 as2 + ab2) (the restatement of expand_pool), and dwconv3x3_project, given the gate, runs depthwise, gate, project
+// GEMM and skip conv per 8 x 16 tile and writes y with its statistics slab [B][irbx_project_tiles][2][Cout].  The layers of
+// wide_project_supported only: 2-byte T, unpadded, skip conv, (Cin, Chid, Cout) in {(192, 768, 64), (384, 1536, 128)},
+// c0 % 16 == 0, H % 8 == 0, W % 16 == 0.  The pool pass itself needs no more than Chid in {768, 1536} and the map rule.
+bool wide_project_supported(int dtype, int Cin, int c0, int Chid, int Cout, bool skip, bool padded, int H, int W);
+hipError_t launch_dwconv3x3_pool(int dtype, const IrbxArgs& a, hipStream_t s);     // needs h1, as2 / ab2, wd; adds into pool_tot
+hipError_t launch_dwconv3x3_project(int dtype, const IrbxArgs& a, int cout, hipStream_t s);
 void irbx_grid(int ks, int v);   // knobs "irbx_grid" (ks = 0: all), "irbx_grid2/4/6": workgroups per expand_dw launch (0 = heuristics)
 void irbx_stamp(int v);
 hipError_t irbx_stamp_fetch(double* out10);  // 9 slots (irbx.hip: STAMP) + the number of waves averaged

@@ -554,7 +554,9 @@ int llie_params_loaded(const llie_ctx* c) {
 // read x three times and never store h1: (3Cin + 2Chid + Cout) P (SURVEY.md 8d "recompute variant").  x0c = channels of
 // the first input segment of the first block (virtual concat), 0 = none.  Blocks that also take the project form
 // (irb_path: h2 stays on chip) move (4Cin + Cout) P: x is read by the statistics pass, the pool pass, the main pass and
-// the shortcut, y is written.
+// the shortcut, y is written.  The wide form (irb_path: the two decoder blocks without h2) is charged exactly as unfused, so
+// llie_path_bytes keeps its integers at every knob setting: it over-charges those two blocks by about 0.6 Chid P from now on
+// (they move 2Cin + 3.4 Chid + Cout: h1 written, read by the pool pass, read with its halo by dwconv3x3_project).
 static void count_blocks(const llie_ctx* c, const std::vector<Block>& bl, int64_t P, int64_t& elems, int64_t& flops, int engine = 0,
                          int x0c = 0) {
   bool first = true;
@@ -615,6 +617,38 @@ static int64_t model_bytes(llie_ctx* c, int batch, int engine) {
 }
 int64_t llie_algorithmic_bytes(llie_ctx* c, int batch) { return model_bytes(c, batch, 0); }
 int64_t llie_path_bytes(llie_ctx* c, int batch) { return model_bytes(c, batch, 1); }
+// The form irb_path picks for every inverted-residual block of a UNet whose full-resolution map is H x W (inference), in forward
+// order: six ints per block (cin, hid, cout, block H, block W, IrbForm).  Returns the number of blocks, or LLIE_ERR_ARG.
+int llie_irb_forms(llie_ctx* c, int H, int W, int* out6, int cap_blocks) {
+  if (!c || c->cfg.kind != LLIE_UNET || H <= 0 || W <= 0 || (cap_blocks > 0 && !out6)) return LLIE_ERR_ARG;
+  int n = 0;
+  auto walk = [&](const std::vector<Block>& bl, int h, int w, int x0c) {
+    bool first = true;
+    for (const Block& b : bl) {
+      if (b.kind != 0) { first = false; continue; }
+      const IrbW& iw = c->irbs[b.idx];
+      const IrbForm form = irb_path(c->dt, iw, (first && x0c) ? x0c : iw.cin, h, w, false).form;
+      first = false;
+      if (n < cap_blocks) {
+        int* o = out6 + 6 * n;
+        o[0] = iw.cin; o[1] = iw.hid; o[2] = iw.cout; o[3] = h; o[4] = w; o[5] = (int)form;
+      }
+      ++n;
+    }
+  };
+  const std::vector<int>& ch = c->channels;
+  int h = H, w = W;
+  for (int l = 0; l < 4; ++l) {
+    walk(c->enc[l], h, w, 0);
+    if (l < 3) { h /= 2; w /= 2; }
+  }
+  walk(c->mid, h, w, 0);
+  for (int l = 0; l < 4; ++l) {
+    if (l > 0) { h *= 2; w *= 2; }
+    walk(c->dec[l], h, w, l == 0 ? ch[3] : ch[4 - l]);
+  }
+  return n;
+}
 int64_t llie_flops(llie_ctx* c, int batch) {
   if (!c) return LLIE_ERR_ARG;
   int64_t elems, flops;

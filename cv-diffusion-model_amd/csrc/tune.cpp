@@ -15,6 +15,10 @@ static Knobs knob_defaults() {
   // as expand_dw's tail (expand_dw_project) -- h2 never reaches HBM either; llie_tune("irbx_project", 0) restores expand_dw +
   // pw_gemm, 2 keeps only the identity-residual shapes (A/B of the 96 -> 32 skip-conv block alone).
   k.irbx_project = 1;
+  // The two wide decoder blocks wide_project_supported names keep the expand GEMM and its stored h1, but go without h2: the SE
+  // pool from one read of h1 (dwconv3x3_pool), then depthwise + gate + project + skip conv in one kernel (dwconv3x3_project);
+  // llie_tune("wide_project", 0) restores dwconv3x3 + pw_gemm.
+  k.wide_project = 1;
   k.gram = 1;  // norm2 statistics of the recompute form from the Gram matrix of the block input (gram.hip); 0 = expand_stats
   // Cache policy of the big activation tensors (inference): a tensor of at least nt_min_mb MiB (this run's batch) is stored
   // non-temporally by its producer (common.h: st_vec_pol).  nt_mask picks the producers: 1 expand_dw (h2), 2 pw_expand (h1),
@@ -71,6 +75,7 @@ int llie_tune(const char* knob, int value) {
   if (!strcmp(knob, "gram")) { g_knobs.gram = value; return LLIE_OK; }
   if (!strcmp(knob, "irbx")) { g_knobs.use_irbx = value != 0; return LLIE_OK; }
   if (!strcmp(knob, "irbx_project")) { g_knobs.irbx_project = value < 0 || value > 2 ? 1 : value; return LLIE_OK; }
+  if (!strcmp(knob, "wide_project")) { g_knobs.wide_project = value != 0; return LLIE_OK; }
   if (!strcmp(knob, "irbx_dbuf")) { irbx_tune(value); return LLIE_OK; }
   if (!strcmp(knob, "irbx_stamp")) { irbx_stamp(value); return LLIE_OK; }
   if (!strcmp(knob, "irbx_grid")) { irbx_grid(0, value); return LLIE_OK; }

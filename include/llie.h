@@ -779,6 +779,30 @@ int llie_expand_dw_project_skip(int dtype, const void* x0, int c0, const void* x
                                 const void* w_expand, const float* scale2, const float* shift2, const float* w_dw, const float* gate,
                                 const void* w_project_skip, int ld, int cout, void* y, float* stats, int batch, int H, int W, llie_stream stream);
 int llie_irbx_project_tiles(int H, int W);
+/* The wide decoder blocks (192 -> 64 at Chid 768, 384 -> 128 at Chid 1536; skip conv, one or two input segments) without h2, from the
+ * STORED h1 [batch][H][W][Chid] of a 2-byte compute type.  scale2 / shift2 [batch][Chid]: norm2 + FiLM DIVIDED BY 6, as the unfused
+ * depthwise takes them in its s6 form: a = clamp01(h1 scale2 + shift2) rounded to the compute type, weights T(6 w_dw).
+ * dwconv3x3_pool: pool_totals uint64 [batch][Chid] += round(2^24 x per-channel sums of depthwise3x3(a) (6 w_dw)), from nine sums of a
+ *   (expand_pool's restatement), one streaming read of h1; the caller zeroes it.  Needs Chid in {768, 1536}, H % 8 == 0, W % 16 == 0.
+ * dwconv3x3_project: y = w_project (gate * depthwise3x3(a)) + w_skip x [batch][H][W][cout], x the raw concatenated block input
+ *   (x1 NULL with c1 = 0; Chid = 4 (c0 + c1)); w_project_skip [cout][ld] of the compute type holds w_project in columns [0, Chid) and
+ *   w_skip in [Chid, Chid + Cin) (ld % 8 == 0); stats: fp32 slab [batch][llie_irbx_project_tiles(H, W)][2][cout] of y's per-channel
+ *   (sum, sum of squares), one entry per 8 x 16 tile.  The depthwise result never leaves the workgroup.
+ * llie_wide_project_supported: 1 where the engine takes this pair (knob "wide_project" = 1 [the default]; 0 = dwconv3x3 + project
+ *   GEMM): 2-byte dtype, a skip conv, no zero-padded channels, (cin, chid, cout) one of the two triples, c0 % 16 == 0, H % 8 == 0,
+ *   W % 16 == 0; else 0.  Outside it the launchers return LLIE_ERR_SHAPE and launch nothing. */
+int llie_wide_project_supported(int dtype, int cin, int c0, int chid, int cout, int skip, int padded, int H, int W);
+/* llie_irb_forms: the launch sequence the inference engine picks for every inverted-residual block of a UNet context whose
+ *   full-resolution map is H x W, under the knobs of the moment, in forward order (encoder, middle, decoder): six ints per block --
+ *   cin, hid, cout, the block's map H and W, and the form: 0 unfused, 1 recompute (expand_dw), 2 project (expand_pool +
+ *   expand_dw_project), 3 wide (dwconv3x3_pool + dwconv3x3_project).  At most cap_blocks entries are written; returns the number
+ *   of blocks.  Needs no GPU. */
+int llie_irb_forms(llie_ctx* c, int H, int W, int* out6, int cap_blocks);
+int llie_dwconv3x3_pool(int dtype, const void* h1, const float* scale2, const float* shift2, const float* w_dw, unsigned long long* pool_totals,
+                        int batch, int H, int W, int chid, llie_stream stream);
+int llie_dwconv3x3_project(int dtype, const void* h1, const float* scale2, const float* shift2, const float* w_dw, const float* gate, const void* x0,
+                           int c0, const void* x1, int c1, const void* w_project_skip, int ld, int cout, void* y, float* stats, int batch, int H,
+                           int W, llie_stream stream);
 /* llie_expand_dw_plan: the launch plan expand_dw (project = 0) or expand_dw_project (project = 1) takes for cin input channels at
  *   these sizes, the "irbx_grid*" knobs included (they act on expand_dw only; the dtype and the segment split do not enter).
  *   plan4[0] = tiles per workgroup, a run along x (4, 2 or 1: the largest that divides W / 16 and keeps 2048 workgroups; 0 = the
@@ -818,7 +842,9 @@ int llie_tune(const char* knob, int value);
  * (llie_conv3x3_upfold above) on maps of whole 8 x 16 low-resolution tiles; 0 = the kernel that blends the patch itself, everywhere.
  * And one for the loop of llie_enhance, default 20: graph_max_steps -- loops of more steps run as plain launches and are never
  * captured (measured: replaying the graph of a 50-step loop is slower than launching it); a value <= 0 restores the
- * default.  It changes no bit. */
+ * default.  It changes no bit.
+ * And wide_project, default 1: the two wide decoder blocks of llie_wide_project_supported run without h2 (dwconv3x3_pool +
+ * dwconv3x3_project above); 0 = dwconv3x3 and the project GEMM.  Independent of "irbx_project". */
 int llie_debug_irbx_stamps(double* out10); /* diagnostic builds: 9 per-wave cycle sums of expand_dw ("irbx_stamp" = 1) or of expand_pool's LDS-tile scan ("irbx_stamp" = 2, 5 slots used) or of expand_dw_project ("irbx_stamp" = 3, slots of its own) (irbx.hip: STAMP) + waves averaged */
 int llie_debug_conv_stamps(double* out8); /* diagnostic builds: 7 per-wave cycle sums of the up-sampling conv (conv.hip: STAMP) + waves averaged */
 int llie_debug_gemm_stamps(double* out3); /* diagnostic builds: see gemm.hip (STAMP) */
