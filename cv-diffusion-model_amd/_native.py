@@ -44,6 +44,8 @@ EXPORTS = [
     "llie_expand_dw", "llie_expand_pool", "llie_expand_dw_project", "llie_expand_dw_project_skip", "llie_irbx_project_tiles",
     "llie_expand_dw_plan", "llie_wide_project_supported", "llie_irb_forms", "llie_dwconv3x3_pool", "llie_dwconv3x3_project",
     "llie_expand_stats", "llie_irbx_stats_rows",
+    "llie_wide_gram_supported", "llie_gram_wide_floats", "llie_gram_wide_part_floats", "llie_gram_wide_block", "llie_gram_wide",
+    "llie_gram_group_weights", "llie_gram_group_finalize", "llie_pw_expand_act", "llie_dwconv3x3_project_preact", "llie_irb_wide_gram",
     "llie_dwconv3x3_ex", "llie_dwconv3x3_strip_rows", "llie_last_kernel",
     "llie_init_conv", "llie_init_conv_tiles", "llie_init_conv_pack_bytes", "llie_final_conv", "llie_final_conv_pack_bytes",
     "llie_se_gate", "llie_affine_add", "llie_nchw_to_nhwc", "llie_nhwc_to_nchw", "llie_pw_gemm_dot",
@@ -268,6 +270,18 @@ def lib() -> C.CDLL:
     L.llie_dwconv3x3_project.argtypes = [ci, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp, ci, ci, vp, vp, ci, ci, ci, vp]
     L.llie_expand_stats.argtypes = [ci, vp, ci, vp, ci, vp, vp, vp, vp, ci, ci, ci, vp]
     L.llie_irbx_stats_rows.argtypes = [ci]
+    L.llie_wide_gram_supported.argtypes = [ci] * 5
+    L.llie_gram_wide_floats.argtypes = []
+    L.llie_gram_wide_floats.restype = i64
+    L.llie_gram_wide_part_floats.argtypes = [ci]
+    L.llie_gram_wide_part_floats.restype = i64
+    L.llie_gram_wide_block.argtypes = [ci, C.POINTER(ci), C.POINTER(ci)]
+    L.llie_gram_wide.argtypes = [ci, vp, ci, vp, ci, vp, vp, ci, ci, vp, vp, vp]
+    L.llie_gram_group_weights.argtypes = [ci, vp, vp, ci, ci, vp]
+    L.llie_gram_group_finalize.argtypes = [vp, vp, ci, ci, vp, vp, vp, i64, C.c_float, C.c_float, ci, vp, vp, vp]
+    L.llie_pw_expand_act.argtypes = [ci, C.POINTER(GemmSeg), ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
+    L.llie_dwconv3x3_project_preact.argtypes = [ci, vp, vp, vp, vp, ci, vp, ci, vp, ci, ci, vp, vp, ci, ci, ci, vp]
+    L.llie_irb_wide_gram.argtypes = [vp, ci, ci, C.POINTER(ci), ci]
     L.llie_tune.argtypes = [C.c_char_p, ci]
     L.llie_debug_irbx_stamps.argtypes = [C.POINTER(C.c_double)]
     L.llie_optimizer_create.argtypes = [C.POINTER(OptTensor), ci, C.POINTER(C.c_void_p)]

@@ -60,6 +60,9 @@ struct Param {
   // PK_CONV3 of an up-sampling conv, 2-byte engines: third copy = the 64 folded sets of conv3x3_upfold_kernel (small.hip: launch_upconv_fold)
   bool has_fold = false;
   size_t fold_off = 0;
+  // PK_MAT, expand weight of a block the wide Gram rule can select: fp64 M_g / u_g per GroupNorm group (kernels.h: launch_gram_group_weights)
+  bool has_mg = false;
+  size_t mg_off = 0;
 };
 
 // cin / cout / hid are the PHYSICAL channel counts of the tensors (multiples of 32; hid of 64 for 2-byte types);
@@ -74,6 +77,8 @@ struct IrbW {
   size_t w_expand_t, w_proj_t, w_dw_flip;  // training copies: [cin][hid], [hid (+cin)][cout], flipped taps
   bool has_wf = false;  // expand weights x 6 in MFMA fragment order for the activation-stationary kernel (pwx.hip)
   size_t w_expand_f = 0;
+  bool has_mg = false;  // norm2's group matrices M_g / u_g of the wide Gram form (gram.hip), fp64
+  size_t w_mg = 0;
   // index of each parameter in llie_ctx::params, recorded where the builder registers it (the backward pass writes the
   // parameter's gradient through it); i_film_*: this block's time_mlp.1; i_skip = -1 without a skip conv
   int i_n1g, i_n1b, i_n2g, i_n2b, i_expand, i_dw, i_se_w1, i_se_b1, i_se_w2, i_se_b2, i_proj, i_film_w, i_film_b, i_skip;
@@ -257,6 +262,8 @@ struct Knobs {
   int irbx_project;   // "irbx_project": recompute blocks without h2 (expand_pool + expand_dw_project): 1 = every shape irbx_project_supported
                       // names, 2 = its identity-residual shapes only, 0 = none (expand_dw + project GEMM)
   int wide_project;   // "wide_project": the wide decoder blocks wide_project_supported names without h2 (dwconv3x3_pool + dwconv3x3_project)
+  int wide_gram;      // "wide_gram" (1 = maps of at least kWideGramMinPixels pixels, 2 = every map): the 192 -> 64 wide block takes norm2's tables from the Gram of its input (gram.hip), pw_expand stores the
+                      // activated h1 and adds the SE pool totals: no pool pass (0 = dwconv3x3_pool from the stored h1)
   int gram;           // "gram": norm2 statistics of the recompute form from the Gram matrix (gram.hip); 0 = expand_stats; 2 = at every size
   int nt_min_mb;      // "nt_min_mb": tensors of at least this many MiB are stored non-temporally by the producers in nt_mask
   int nt_mask;        // "nt_mask": 1 expand_dw, 2 pw_expand, 4 dwconv3x3, 8 project / attention GEMMs, 16 dense 3x3 convs
@@ -293,14 +300,25 @@ struct IrbPath {
   // on: below, the workgroup epilogue and the last-ticket sum outweigh the saved MFMAs (measured at B = 1 and B = 32; the rule
   // must not depend on the batch, it fixes the statistics' summation order)
   bool gram;
+  // wide form, the layer gram_wide_supported names (192 -> 64 at hid 768; knob "wide_gram"): gn(norm1), the wide Gram and its group
+  // finalize give norm2's tables before the expand GEMM, pw_expand_act stores the activated h1 and adds the pool totals,
+  // dwconv3x3_project reads it pre-activated.  No statistics slab of h1, no second gn launch, no dwconv3x3_pool.  The 384 -> 128
+  // block keeps the pool pass: its Gram (78 blocks) was not built.  From kWideGramMinPixels pixels per image on (knob 2: at every
+  // size): the form trades two launches (norm2's gn, the pool pass) for three (Gram, its partial sum, the group finalize), and on a
+  // small map every launch of the block is latency; only the 128 x 128 map of a 256 x 256 frame has been measured.
+  bool wgram;
 };
+constexpr int kWideGramMinPixels = 4096;
 // c0 = channels of the block's first input segment (= w.cin without a virtual concat).  A rule on the layer, the image size, the
 // dtype and the knobs alone -- never on the batch or the grid, which would break batch invariance.
 inline IrbPath irb_path(int dt, const IrbW& w, int c0, int H, int W, bool training) {
-  IrbPath p{kIrbUnfused, !training && dt != LLIE_F32, !training && w.hid % 128 == 0, false};
+  IrbPath p{kIrbUnfused, !training && dt != LLIE_F32, !training && w.hid % 128 == 0, false, false};
   if (p.fixtot && p.s6 && g_knobs.wide_project &&
       wide_project_supported(dt, w.cin, c0, w.hid, w.cout, w.skip, w.hid != w.hid_r || w.cin != w.cin_r || w.cout != w.cout_r, H, W)) {
     p.form = kIrbWide;
+    // (the activating expand is pw_expand's: knob "pwx" on, input segments of whole 64-channel chunks)
+    p.wgram = g_knobs.wide_gram && (H * W >= kWideGramMinPixels || g_knobs.wide_gram > 1) && w.has_mg && pw_expand_enabled() && c0 % 64 == 0 &&
+              (w.cin - c0) % 64 == 0 && gram_wide_supported(dt, w.cin, c0, w.hid, H * W);
     return p;
   }
   // (!fixtot: the recompute kernels only know the fixed-point totals; every hid irbx_supported accepts is a multiple of 128)

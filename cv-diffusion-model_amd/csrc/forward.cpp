@@ -129,6 +129,48 @@ struct Run : Exec {
     IrbxArgs xa{};                              // recompute forms: the kernels' inputs (irbx.hip); each launch adds its outputs to a copy
   };
 
+  // Wide Gram form (IrbPath::wgram): norm2's tables from the Gram of the activated input, then the expand GEMM stores the activated
+  // h1 and adds the SE pool totals.  No statistics slab of h1, no second gn launch, no pool pass.
+  void front_wide_gram(const IrbW& w, const Tens& x0, const Tens* x1, const float* film, int64_t film_stride, IrbTmp& t) {
+    const int H = x0.H, W = x0.W, P = H * W, M = B * P;
+    Tens& h1 = t.h1;
+    h1.C = w.hid; h1.Cr = w.hid_r; h1.H = H; h1.W = W; h1.ntiles = 0; h1.valid = true;
+    t.as2 = ar->alloc((size_t)B * w.hid * 4); t.ab2 = ar->alloc((size_t)B * w.hid * 4);
+    const size_t gpart = ar->alloc((size_t)B * gram_wide_part_floats(P) * 4);
+    const size_t gblk = ar->alloc((size_t)B * kGramWideFloats * 4);
+    t.dnt = irbx_project_tiles(H, W);
+    t.ptot = ztake((size_t)B * w.hid * 8);
+    if (!dry) {
+      GramWideArgs ga{};
+      ga.x0 = p(x0.off); ga.c0 = x0.C; ga.x1 = x1 ? p(x1->off) : nullptr; ga.c1 = x1 ? x1->C : 0; ga.as1 = p<float>(t.as1); ga.ab1 = p<float>(t.ab1);
+      ga.part = p<float>(gpart); ga.gblk = p<float>(gblk); ga.B = B; ga.P = P;
+      timed(LLIE_K_GEMM, (int64_t)M * w.cin * (int64_t)es(), [&] { return launch_gram_wide(dt, ga, s); });
+      GramGroupFinalizeArgs fa{};
+      fa.gblk = p<float>(gblk); fa.mg = wptr<double>(w.w_mg); fa.K = w.cin; fa.Chid = w.hid; fa.groups = gn_groups(w.hid); fa.P = P; fa.B = B;
+      fa.gamma = wptr<float>(w.n2g); fa.beta = wptr<float>(w.n2b); fa.film = film; fa.film_stride = film_stride; fa.eps = 1e-5f;
+      fa.as = p<float>(t.as2); fa.ab = p<float>(t.ab2); fa.post_scale = 1.f / 6.f;
+      timed(LLIE_K_OTHER, (int64_t)B * w.hid * 8, [&] { return launch_gram_group_finalize(fa, s); }, "gram_group_finalize_kernel");
+    }
+    // the Gram's partials are gone before h1 exists: the block's high-water mark stays h1 + its input
+    rel(gpart); rel(gblk);
+    h1.off = ar->alloc((size_t)M * w.hid * es());
+    if (!dry) {
+      ExpandArgs x{};
+      x.seg[0] = GemmSeg{p(x0.off), x0.C, p<float>(t.as1), p<float>(t.ab1), w.cin, ACT_RELU6_S6};
+      x.nseg = 1;
+      if (x1) x.seg[x.nseg++] = GemmSeg{p(x1->off), x1->C, p<float>(t.as1) + x0.C, p<float>(t.ab1) + x0.C, w.cin, ACT_RELU6_S6};
+      x.wf = wptr(w.w_expand_f); x.out = p(h1.off); x.M = M; x.N = w.hid; x.K = w.cin; x.P = P; x.H = H; x.W = W;
+      x.as2 = p<float>(t.as2); x.ab2 = p<float>(t.ab2); x.wd = wptr<float>(w.w_dw); x.pool_tot = p<unsigned long long>(t.ptot);
+      x.nt = nt_store(2, (int64_t)M * w.hid);
+      const int64_t kbytes = ((int64_t)M * (w.cin + w.hid) + (int64_t)w.hid * w.cin) * (int64_t)es();
+      timed(LLIE_K_GEMM, kbytes, [&] { return launch_pw_expand_act(dt, x, s); });
+      t.xa = IrbxArgs{};
+      t.xa.h1 = p(h1.off); t.xa.h1_act = 1; t.xa.wd = wptr<float>(w.w_dw);
+      t.xa.B = B; t.xa.H = H; t.xa.W = W; t.xa.Chid = w.hid;
+    }
+    rel(t.as1); rel(t.ab1);
+  }
+
   // K1: expand with norm1 + ReLU6 prologue; norm2 + FiLM folded into one affine; K2: depthwise with affine + ReLU6 prologue and SE pool
   void front_unfused(const IrbPath& path, const IrbW& w, const Tens& x0, const Tens* x1, const float* film, int64_t film_stride, IrbRec& rec, IrbTmp& t) {
     const int H = x0.H, W = x0.W, P = H * W, M = B * P;
@@ -331,7 +373,8 @@ struct Run : Exec {
     snprintf(tag, sizeof tag, "irb P=%d %d->%d hid=%d", P, w.cin, w.cout, w.hid);
     gn(x0, x1, w.n1g, w.n1b, nullptr, 0, t.as1, t.ab1, &rec.n1, path.s6 ? 1.f / 6.f : 0.f);
     const float* film2 = film ? film + w.film_off : nullptr;  // this block's rows of the FiLM projection
-    if (path.form == kIrbUnfused || path.form == kIrbWide) front_unfused(path, w, x0, x1, film2, film_stride, rec, t);
+    if (path.form == kIrbWide && path.wgram) front_wide_gram(w, x0, x1, film2, film_stride, t);
+    else if (path.form == kIrbUnfused || path.form == kIrbWide) front_unfused(path, w, x0, x1, film2, film_stride, rec, t);
     else front_recompute(path, w, x0, x1, film2, film_stride, t);
     se_gate(path, w, P, t);
     Tens y = path.form == kIrbProject ? project_fused(w, x0, t) : path.form == kIrbWide ? project_wide(w, x0, x1, t) : project_gemm(w, x0, x1, t);

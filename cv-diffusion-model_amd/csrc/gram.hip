@@ -405,4 +405,276 @@ hipError_t launch_gram_finalize(int dtype, const GramFinalizeArgs& a, hipStream_
   return dtype == 1 ? launch_gram_finalize_t<half_t>(a, s) : launch_gram_finalize_t<bf16_t>(a, s);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The wide decoder block 192 -> 64 (hid 768): the same statistics at K = 192, so that pw_expand can store the ACTIVATED h1.
+//
+//   gram_wide_kernel           grid (P / RP, 1, B), three waves.  The 21 upper 32 x 32 blocks of G do not fit one wave's
+//                              registers, so the block pairs are split over the waves and every wave sees all pixels of the
+//                              workgroup: the 192 threads activate 32 pixels at a time into a double-buffered LDS tile (one
+//                              barrier per step).  The six 32-channel fragments form three groups of two; wave w owns group
+//                              X = w and group Y = (w + 1) % 3 and the seven blocks (x0,x0) (x0,x1) (x1,x1) (x0,y0) (x0,y1)
+//                              (x1,y0) (x1,y1): four transposed fragment reads feed seven MFMAs per 16 pixels, and m of group
+//                              X comes from the same fragments.  A wave owns its blocks outright, so the workgroup partial
+//                              leaves straight from the accumulators (gram_wide_block: block q = 7 w + t).
+//   gram_wide_reduce_kernel    grid (22, B): the image's partials added in index order -> G in block layout, then m.
+//   gram_group_finalize_kernel grid (groups, B): GroupNorm needs only the group sums, and
+//                                sum_{c in g} w_c^T G w_c = <G, M_g>,  M_g = sum_{c in g} w_c w_c^T,   sum_{c in g} w_c . m = <m, u_g>
+//                              M_g and u_g depend on the weights alone (gram_group_weights_kernel, at load time; fp64, block
+//                              layout of G with the off-diagonal blocks doubled).  K^2 fp64 MACs per (group, image) instead of
+//                              K^2 per channel.  w_c is the T(6 W) row pw_expand multiplies with, read from its packed copy: the
+//                              36 and the 6 are inside.
+//   M_g stays fp64: its entries are exact there (sums of 24 products of two T values), so the only error of the quadratic form is
+//   G's own fp32 rounding; a narrower format was not measured.
+namespace {
+template <typename T>
+__device__ __forceinline__ typename Elem<T>::vec_t gram_read_frag(const unsigned char* pa, int pitch) {
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(pa));
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(pa + 4 * pitch));
+  u32x4 w;
+  w[0] = reinterpret_cast<const uint32_t*>(&lo)[0]; w[1] = reinterpret_cast<const uint32_t*>(&lo)[1];
+  w[2] = reinterpret_cast<const uint32_t*>(&hi)[0]; w[3] = reinterpret_cast<const uint32_t*>(&hi)[1];
+  return reinterpret_cast<const typename Elem<T>::vec_t&>(w);
+}
+}  // namespace
+
+template <typename T>
+__global__ void __launch_bounds__(192, 2) gram_wide_kernel(const GramWideArgs a) {
+  constexpr int K = kGramWideK, PITCH = 448, TILE = 32 * PITCH;  // 448 % 256 == 192: the transposed reads are conflict-free (GramPitch)
+  typedef typename Elem<T>::vec_t vec_t;
+  __shared__ __align__(16) unsigned char sA[2][TILE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.z, wg = blockIdx.x, nwg = gridDim.x;
+  const T* x0 = reinterpret_cast<const T*>(a.x0) + (size_t)b * a.P * a.c0;
+  const T* x1 = a.x1 ? reinterpret_cast<const T*>(a.x1) + (size_t)b * a.P * a.c1 : nullptr;
+  // vector v = tid + 192 j of a step (j < 4) -> pixel tid / 24 + 8 j, channel vector tid % 24: a thread keeps its 8 channels, so
+  // norm1's tables stay in registers.  Activation and rounding are gram_activate8's (act_clamp01_pack on the same fp32 tables)
+  const int prow = tid / 24, k = (tid % 24) * 8;
+  const T* src = k < a.c0 ? x0 + k : x1 + (k - a.c0);
+  const int ld = k < a.c0 ? a.c0 : a.c1;
+  float sc[8], sh[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    sc[e] = a.as1[(size_t)b * K + k + e];
+    sh[e] = a.ab1[(size_t)b * K + k + e];
+  }
+  const int nsteps = a.RP / 32;
+  const size_t p_first = (size_t)wg * a.RP + prow;
+  constexpr int PF = 2;
+  u32x4 raw[PF][4];
+  auto load = [&](int step, u32x4 (&dst)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) dst[j] = *reinterpret_cast<const u32x4*>(src + (p_first + (size_t)step * 32 + 8 * j) * ld);
+  };
+#pragma unroll
+  for (int u = 0; u < PF; ++u)
+    if (u < nsteps) load(u, raw[u]);
+
+  f32x16 acc[7];
+#pragma unroll
+  for (int q = 0; q < 7; ++q)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+  float msum[2] = {0.f, 0.f};
+  uint32_t ones2;
+  {
+    typedef T t2 __attribute__((ext_vector_type(2)));
+    t2 o = {(T)1.f, (T)1.f};
+    ones2 = *reinterpret_cast<uint32_t*>(&o);
+  }
+  const int li = lane & 15, gq = lane >> 4;
+  const int tr_off = (8 * (gq >> 1) + (li >> 2)) * PITCH + (16 * (gq & 1) + 4 * (li & 3)) * 2;  // as in gram_stats_kernel
+  const int fx = 2 * wave, fy = 2 * ((wave + 1) % 3);
+  for (int step0 = 0; step0 < nsteps; step0 += PF) {
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {
+      const int step = step0 + u;
+      if (step >= nsteps) break;  // uniform
+      unsigned char* buf = sA[u & 1];  // PF is even: step & 1 == u & 1
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        u32x4 o;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[q] = act_clamp01_pack<T>(raw[u][j][q], sc[2 * q], sc[2 * q + 1], sh[2 * q], sh[2 * q + 1]);
+        *reinterpret_cast<u32x4*>(buf + (prow + 8 * j) * PITCH + k * 2) = o;
+      }
+      if (step + PF < nsteps) load(step + PF, raw[u]);
+      wg_barrier();  // tile `step` complete; the other buffer (read during step - 1) is free for step + 1
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const unsigned char* pa = buf + tr_off + ks * 16 * PITCH;
+        const vec_t ax0 = gram_read_frag<T>(pa + fx * 64, PITCH), ax1 = gram_read_frag<T>(pa + fx * 64 + 64, PITCH);
+        const vec_t ay0 = gram_read_frag<T>(pa + fy * 64, PITCH), ay1 = gram_read_frag<T>(pa + fy * 64 + 64, PITCH);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          msum[0] = gdot2<T>(reinterpret_cast<const u32x4&>(ax0)[q], ones2, msum[0]);
+          msum[1] = gdot2<T>(reinterpret_cast<const u32x4&>(ax1)[q], ones2, msum[1]);
+        }
+        acc[0] = mfma16<T>(ax0, ax0, acc[0]);
+        acc[1] = mfma16<T>(ax0, ax1, acc[1]);
+        acc[2] = mfma16<T>(ax1, ax1, acc[2]);
+        acc[3] = mfma16<T>(ax0, ay0, acc[3]);
+        acc[4] = mfma16<T>(ax0, ay1, acc[4]);
+        acc[5] = mfma16<T>(ax1, ay0, acc[5]);
+        acc[6] = mfma16<T>(ax1, ay1, acc[6]);
+      }
+    }
+  }
+  // the workgroup's partial: every block belongs to one wave; a register is 32 consecutive floats of one block row per lane half
+  float* part = a.part + ((size_t)b * nwg + wg) * kGramWideFloats;
+#pragma unroll
+  for (int q = 0; q < 7; ++q)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) part[(7 * wave + q) * 1024 + mfma_row(r, lane) * 32 + (lane & 31)] = acc[q][r];
+#pragma unroll
+  for (int f = 0; f < 2; ++f) {
+    const float t = msum[f] + __shfl_xor(msum[f], 32, 64);  // the two k-slice halves of a channel
+    if (lane < 32) part[kGramWideBlocks * 1024 + (fx + f) * 32 + lane] = t;
+  }
+}
+
+__global__ void __launch_bounds__(256) gram_wide_reduce_kernel(const GramWideArgs a, const int nwg) {
+  const int q = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+  if (q == kGramWideBlocks && tid >= kGramWideK / 4) return;
+  const float* pimg = a.part + (size_t)b * nwg * kGramWideFloats + q * 1024 + 4 * tid;
+  f32x4 s = {0.f, 0.f, 0.f, 0.f};
+  for (int w0 = 0; w0 < nwg; w0 += 16) {  // up to 16 partials in flight; the sum runs in partial order whatever the grouping
+    f32x4 v[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u)
+      if (w0 + u < nwg) v[u] = *reinterpret_cast<const f32x4*>(pimg + (size_t)(w0 + u) * kGramWideFloats);
+#pragma unroll
+    for (int u = 0; u < 16; ++u)
+      if (w0 + u < nwg) s += v[u];
+  }
+  *reinterpret_cast<f32x4*>(a.gblk + (size_t)b * kGramWideFloats + q * 1024 + 4 * tid) = s;
+}
+
+__global__ void __launch_bounds__(256) gram_group_finalize_kernel(const GramGroupFinalizeArgs a) {
+  typedef double f64x2 __attribute__((ext_vector_type(2)));
+  __shared__ double ssum[2][4];
+  const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int CG = a.Chid / a.groups, c_lo = g * CG;
+  const float* gb = a.gblk + (size_t)b * kGramWideFloats;
+  const double* mg = a.mg + (size_t)g * kGramWideFloats;
+  float p_ga = 0.f, p_be = 0.f, p_fs = 0.f, p_fh = 0.f;
+  if (tid < CG) {
+    p_ga = a.gamma[c_lo + tid];
+    p_be = a.beta[c_lo + tid];
+    if (a.film) {
+      const float* f = a.film + (size_t)b * a.film_stride;
+      p_fs = f[c_lo + tid];
+      p_fh = f[a.Chid + c_lo + tid];
+    }
+  }
+  double s2 = 0.0, s1 = 0.0;
+#pragma unroll 7
+  for (int i = 0; i < kGramWideBlocks; ++i) {  // a fixed order per thread
+    const int e = 4 * (tid + 256 * i);
+    const f32x4 gv = *reinterpret_cast<const f32x4*>(gb + e);
+    const f64x2 m0 = *reinterpret_cast<const f64x2*>(mg + e), m1 = *reinterpret_cast<const f64x2*>(mg + e + 2);
+    s2 = __builtin_fma((double)gv[0], m0[0], s2);
+    s2 = __builtin_fma((double)gv[1], m0[1], s2);
+    s2 = __builtin_fma((double)gv[2], m1[0], s2);
+    s2 = __builtin_fma((double)gv[3], m1[1], s2);
+  }
+  if (tid < kGramWideK) s1 = (double)gb[kGramWideBlocks * 1024 + tid] * mg[kGramWideBlocks * 1024 + tid];
+  const double r1 = wave_sum(s1), r2 = wave_sum(s2);
+  if (lane == 0) { ssum[0][wave] = r1; ssum[1][wave] = r2; }
+  wg_barrier();
+  const double t1 = ((ssum[0][0] + ssum[0][1]) + ssum[0][2]) + ssum[0][3];
+  const double t2 = ((ssum[1][0] + ssum[1][1]) + ssum[1][2]) + ssum[1][3];
+  // gram_finalize_kernel's tail
+  const double n = (double)CG * (double)a.P;
+  const double mean = t1 / n;
+  double var = t2 / n - mean * mean;
+  if (var < 0.0) var = 0.0;
+  const float rstd = (float)(1.0 / sqrt(var + (double)a.eps));
+  const float fmean = (float)mean;
+  if (tid < CG) {
+    const int c = c_lo + tid;
+    const float ga = p_ga * rstd;
+    float sc = ga, sh = p_be - fmean * ga;
+    if (a.film) {
+      const float fs = 1.f + p_fs, fh = p_fh;
+      sc *= fs;
+      sh = sh * fs + fh;
+    }
+    if (a.post_scale != 0.f) {
+      sc *= a.post_scale;
+      sh *= a.post_scale;
+    }
+    a.as[(size_t)b * a.Chid + c] = sc;
+    a.ab[(size_t)b * a.Chid + c] = sh;
+  }
+}
+
+// M_g and u_g from the packed expand weights pw_expand multiplies with (T(6 W) in fragment order, pw_expand_pack_index): read back
+// from the blob, not rounded a second time from the fp32 source, so the two can never disagree in a last bit.
+// grid (22, groups): block q < 21 = one 32 x 32 block of M_g, block 21 = u_g.  `state` as in launch_upconv_fold.
+template <typename T>
+__global__ void __launch_bounds__(256) gram_group_weights_kernel(const T* wf, double* mg, int Chid, int groups, const unsigned long long* state) {
+  if (state && state[1] == 0) return;  // parameters unchanged since the last load
+  constexpr int K = kGramWideK;
+  const int q = blockIdx.x, g = blockIdx.y, tid = threadIdx.x;
+  const int CG = Chid / groups;
+  auto w = [&](int c, int k) { return (double)(float)wf[pw_expand_pack_index(g * CG + c, k, K)]; };
+  double* dst = mg + (size_t)g * kGramWideFloats;
+  if (q == kGramWideBlocks) {
+    if (tid >= K) return;
+    double u = 0.0;
+    for (int c = 0; c < CG; ++c) u += w(c, tid);
+    dst[kGramWideBlocks * 1024 + tid] = u;
+    return;
+  }
+  int bi, bj;
+  gram_wide_block(q, &bi, &bj);
+  const double f = bi == bj ? 1.0 : 2.0;  // G is symmetric: an off-diagonal block stands for its mirror image too
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int e = 4 * tid + t, i = bi * 32 + (e >> 5), j = bj * 32 + (e & 31);
+    double m = 0.0;
+    for (int c = 0; c < CG; ++c) m = __builtin_fma(w(c, i), w(c, j), m);
+    dst[q * 1024 + e] = f * m;
+  }
+}
+
+int gram_wide_rows(int P) {  // pixels per workgroup: a function of P alone (it fixes the summation order)
+  int rp = 4096;
+  while (rp > 128 && (P % rp || P / rp < 16)) rp >>= 1;
+  return rp;
+}
+size_t gram_wide_part_floats(int P) { return (size_t)(P / gram_wide_rows(P)) * kGramWideFloats; }
+bool gram_wide_supported(int dtype, int K, int c0, int Chid, int P) {
+  if (dtype != 1 && dtype != 2) return false;
+  return K == kGramWideK && Chid == 4 * K && c0 > 0 && c0 <= K && c0 % 8 == 0 && P > 0 && P % 128 == 0;
+}
+hipError_t launch_gram_wide(int dtype, const GramWideArgs& a0, hipStream_t s) {
+  GramWideArgs a = a0;
+  if (!gram_wide_supported(dtype, a.c0 + a.c1, a.c0, 4 * (a.c0 + a.c1), a.P) || !a.x0 || (a.c1 != 0) != (a.x1 != nullptr) || !a.as1 || !a.ab1 || !a.part ||
+      !a.gblk || a.B <= 0)
+    return hipErrorInvalidValue;
+  a.RP = gram_wide_rows(a.P);
+  const int nwg = a.P / a.RP;
+  note_kernel("gram_wide_kernel");
+  if (dtype == 1) hipLaunchKernelGGL((gram_wide_kernel<half_t>), dim3(nwg, 1, a.B), dim3(192), 0, s, a);
+  else hipLaunchKernelGGL((gram_wide_kernel<bf16_t>), dim3(nwg, 1, a.B), dim3(192), 0, s, a);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  hipLaunchKernelGGL(gram_wide_reduce_kernel, dim3(kGramWideBlocks + 1, a.B), dim3(256), 0, s, a, nwg);
+  return hipGetLastError();
+}
+hipError_t launch_gram_group_finalize(const GramGroupFinalizeArgs& a, hipStream_t s) {
+  if (!a.gblk || !a.mg || !a.gamma || !a.beta || !a.as || !a.ab || a.groups != 32 || a.K != kGramWideK || a.Chid != 4 * a.K || a.B <= 0 || a.P <= 0)
+    return hipErrorInvalidValue;
+  note_kernel("gram_group_finalize_kernel");
+  hipLaunchKernelGGL(gram_group_finalize_kernel, dim3(a.groups, a.B), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_gram_group_weights(int dtype, const void* wpack, double* mg, int Chid, int K, hipStream_t s, const unsigned long long* state) {
+  if ((dtype != 1 && dtype != 2) || !wpack || !mg || K != kGramWideK || Chid != 4 * K) return hipErrorInvalidValue;
+  const dim3 grid(kGramWideBlocks + 1, 32);
+  if (dtype == 1) hipLaunchKernelGGL((gram_group_weights_kernel<half_t>), grid, dim3(256), 0, s, reinterpret_cast<const half_t*>(wpack), mg, Chid, 32, state);
+  else hipLaunchKernelGGL((gram_group_weights_kernel<bf16_t>), grid, dim3(256), 0, s, reinterpret_cast<const bf16_t*>(wpack), mg, Chid, 32, state);
+  return hipGetLastError();
+}
+
 }  // namespace llie

@@ -1572,7 +1572,9 @@ __global__ void __launch_bounds__(256) dwconv3x3_pool_kernel(const IrbxArgs a) {
 // from memory -- 16 rows x 64 bytes per load instruction -- they cost more than everything else in the chunk (profiles/r21/README.md).
 constexpr size_t wide_lds_bytes(int Chid, int PCO) { return (size_t)kXNPB * 32 * SHP + 10 * Chid * 2 + PCO * SHP + 8 * PCO * 4; }
 static_assert(2 * wide_lds_bytes(768, 64) <= 160 * 1024 && 2 * wide_lds_bytes(1536, 128) <= 160 * 1024, "two workgroups per CU");
-template <typename T, int PCO>
+// PREACT: a.h1 already holds a = T(clamp01(h1 as2 + ab2)) (pw_expand_act_kernel stored it): the halo tile goes to LDS as loaded
+// and norm2's tables are neither fetched nor kept in registers.
+template <typename T, int PCO, bool PREACT = false>
 __global__ void __launch_bounds__(256, 2) dwconv3x3_project_kernel(const IrbxArgs a) {
   constexpr int NCB = PCO / 16, NPASS = kXNPB * 32 / 32;
   // chunks the halo tile is fetched ahead: two at 64 output channels; at 128 the y accumulators and the skip conv's operands leave
@@ -1616,14 +1618,16 @@ __global__ void __launch_bounds__(256, 2) dwconv3x3_project_kernel(const IrbxArg
   }
   // with the tile come norm2's tables of the thread's 8 channels of that chunk: scale (2 x 4), then shift
   vec_t raw[DEPTH][NPASS];
-  f32x4 aff[DEPTH][4];
-  const float* as2 = a.as2 + (size_t)b * a.Chid + kv * 8;
-  const float* ab2 = a.ab2 + (size_t)b * a.Chid + kv * 8;
-  auto load = [&](int chunk, vec_t (&dst)[NPASS], f32x4 (&af)[4]) {
+  f32x4 aff[DEPTH][PREACT ? 1 : 4];
+  const float* as2 = PREACT ? nullptr : a.as2 + (size_t)b * a.Chid + kv * 8;
+  const float* ab2 = PREACT ? nullptr : a.ab2 + (size_t)b * a.Chid + kv * 8;
+  auto load = [&](int chunk, vec_t (&dst)[NPASS], f32x4 (&af)[PREACT ? 1 : 4]) {
 #pragma unroll
     for (int j = 0; j < NPASS; ++j) dst[j] = ld_vec<T>(h1 + hoff[j] + chunk * 64);
+    if constexpr (PREACT) return;
     af[0] = *reinterpret_cast<const f32x4*>(as2 + chunk * 64); af[1] = *reinterpret_cast<const f32x4*>(as2 + chunk * 64 + 4);
-    af[2] = *reinterpret_cast<const f32x4*>(ab2 + chunk * 64); af[3] = *reinterpret_cast<const f32x4*>(ab2 + chunk * 64 + 4);
+    af[2 % (PREACT ? 1 : 4)] = *reinterpret_cast<const f32x4*>(ab2 + chunk * 64);
+    af[3 % (PREACT ? 1 : 4)] = *reinterpret_cast<const f32x4*>(ab2 + chunk * 64 + 4);
   };
   // the chunk's Wp block: vector v = tid + 256 j -> row v / 8, 16-byte channel vector v % 8; one chunk ahead
   constexpr int NWV = PCO * 8 / 256;
@@ -1701,16 +1705,19 @@ __global__ void __launch_bounds__(256, 2) dwconv3x3_project_kernel(const IrbxArg
 
   const int choff = irbx_choff(g);  // the lane's 8 channels of a 32-channel half after the swap below
   // one chunk: `cur` holds its halo tile and is refilled with the tile of chunk + 2 once it has been activated into sH
-  auto chunk_step = [&](const int chunk, vec_t (&cur)[NPASS], f32x4 (&af)[4]) {
+  auto chunk_step = [&](const int chunk, vec_t (&cur)[NPASS], f32x4 (&af)[PREACT ? 1 : 4]) {
     wg_barrier();  // weights staged (first chunk); previous depthwise phase done with sH, previous project phase with wpl
 #pragma unroll
     for (int j = 0; j < NPASS; ++j) {  // activate8 on tables held in registers
       const u32x4 x = reinterpret_cast<const u32x4&>(cur[j]);
-      u32x4 o;
-      o[0] = act_clamp01_pack<T>(x[0], af[0][0], af[0][1], af[2][0], af[2][1]);
-      o[1] = act_clamp01_pack<T>(x[1], af[0][2], af[0][3], af[2][2], af[2][3]);
-      o[2] = act_clamp01_pack<T>(x[2], af[1][0], af[1][1], af[3][0], af[3][1]);
-      o[3] = act_clamp01_pack<T>(x[3], af[1][2], af[1][3], af[3][2], af[3][3]);
+      u32x4 o = x;
+      if constexpr (!PREACT) {
+        constexpr int A1 = PREACT ? 0 : 1, A2 = PREACT ? 0 : 2, A3 = PREACT ? 0 : 3;
+        o[0] = act_clamp01_pack<T>(x[0], af[0][0], af[0][1], af[A2][0], af[A2][1]);
+        o[1] = act_clamp01_pack<T>(x[1], af[0][2], af[0][3], af[A2][2], af[A2][3]);
+        o[2] = act_clamp01_pack<T>(x[2], af[A1][0], af[A1][1], af[A3][0], af[A3][1]);
+        o[3] = act_clamp01_pack<T>(x[3], af[A1][2], af[A1][3], af[A3][2], af[A3][3]);
+      }
       *reinterpret_cast<u32x4*>(buf + (q0 + 32 * j) * SHP + kv * 16) = hok[j] ? o : u32x4{0u, 0u, 0u, 0u};
     }
 #pragma unroll
@@ -1766,13 +1773,13 @@ hipError_t launch_dwconv3x3_pool(int dtype, const IrbxArgs& a, hipStream_t s) {
   else hipLaunchKernelGGL((dwconv3x3_pool_kernel<bf16_t>), grid, dim3(256), 0, s, a);
   return hipGetLastError();
 }
-template <typename T, int PCO>
+template <typename T, int PCO, bool PREACT = false>
 static hipError_t launch_wide_project_cfg(const IrbxArgs& a, hipStream_t s) {
-  static const std::string name = std::string("dwconv3x3_project_kernel<") + TypeName<T>::value + ", " + std::to_string(PCO) + ">";
+  static const std::string name = std::string("dwconv3x3_project_kernel<") + TypeName<T>::value + ", " + std::to_string(PCO) + (PREACT ? ", true>" : ">");
   note_kernel(name.c_str());
   static std::atomic<uint64_t> attr_done{0};
-  if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&dwconv3x3_project_kernel<T, PCO>), 128 * 1024, attr_done); e != hipSuccess) return e;
-  hipLaunchKernelGGL((dwconv3x3_project_kernel<T, PCO>), dim3(irbx_project_tiles(a.H, a.W), 1, a.B), dim3(256), wide_lds_bytes(a.Chid, PCO), s, a);
+  if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&dwconv3x3_project_kernel<T, PCO, PREACT>), 128 * 1024, attr_done); e != hipSuccess) return e;
+  hipLaunchKernelGGL((dwconv3x3_project_kernel<T, PCO, PREACT>), dim3(irbx_project_tiles(a.H, a.W), 1, a.B), dim3(256), wide_lds_bytes(a.Chid, PCO), s, a);
   return hipGetLastError();
 }
 // y = Wp . (gate * dw3x3(clamp01(h1 as2 + ab2) x 6 w)) + Wskip . [x0 | x1] with y's statistics slab [B][irbx_project_tiles][2][cout];
@@ -1780,8 +1787,12 @@ static hipError_t launch_wide_project_cfg(const IrbxArgs& a, hipStream_t s) {
 hipError_t launch_dwconv3x3_project(int dtype, const IrbxArgs& a, int cout, hipStream_t s) {
   const int Cin = a.c0 + a.c1;
   if (!wide_project_supported(dtype, Cin, a.c0, a.Chid, cout, true, false, a.H, a.W) || a.B <= 0 || (a.c1 != 0) != (a.x1 != nullptr) || !a.x0 ||
-      a.ldp < a.Chid + Cin || a.ldp % 8 || !a.h1 || !a.gate || !a.wp || !a.y || !a.ystats || !a.as2 || !a.ab2 || !a.wd)
+      a.ldp < a.Chid + Cin || a.ldp % 8 || !a.h1 || !a.gate || !a.wp || !a.y || !a.ystats || (!a.h1_act && (!a.as2 || !a.ab2)) || !a.wd)
     return hipErrorInvalidValue;
+  if (a.h1_act) {  // the activated h1 of pw_expand_act: 192 -> 64 only
+    if (cout != 64) return hipErrorInvalidValue;
+    return dtype == 1 ? launch_wide_project_cfg<half_t, 64, true>(a, s) : launch_wide_project_cfg<bf16_t, 64, true>(a, s);
+  }
   if (cout == 64) return dtype == 1 ? launch_wide_project_cfg<half_t, 64>(a, s) : launch_wide_project_cfg<bf16_t, 64>(a, s);
   return dtype == 1 ? launch_wide_project_cfg<half_t, 128>(a, s) : launch_wide_project_cfg<bf16_t, 128>(a, s);
 }

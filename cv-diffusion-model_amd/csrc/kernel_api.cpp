@@ -916,6 +916,59 @@ int llie_dwconv3x3_project(int dtype, const void* h1, const float* scale2, const
   a.ldp = ld; a.y = y; a.ystats = stats; a.B = batch; a.H = H; a.W = W; a.Chid = 4 * (c0 + c1);
   return kerr("dwconv3x3_project", launch_dwconv3x3_project(dtype, a, cout, hs(stream)), LLIE_ERR_SHAPE, kWideShapes);
 }
+// ---- the wide Gram form of the 192 -> 64 block (gram.hip, pwx.hip, irbx.hip)
+int llie_wide_gram_supported(int dtype, int cin, int c0, int chid, int pixels) { return gram_wide_supported(dtype, cin, c0, chid, pixels) ? 1 : 0; }
+int64_t llie_gram_wide_floats(void) { return kGramWideFloats; }
+int64_t llie_gram_wide_part_floats(int pixels) { return pixels > 0 && pixels % 128 == 0 ? (int64_t)gram_wide_part_floats(pixels) : LLIE_ERR_ARG; }
+int llie_gram_wide_block(int q, int* bi, int* bj) {
+  if (q < 0 || q >= kGramWideBlocks || !bi || !bj) return LLIE_ERR_ARG;
+  gram_wide_block(q, bi, bj);
+  return LLIE_OK;
+}
+int llie_gram_wide(int dtype, const void* x0, int c0, const void* x1, int c1, const float* scale, const float* bias, int batch, int pixels,
+                   float* part, float* gblk, llie_stream stream) {
+  GramWideArgs a{};
+  a.x0 = x0; a.x1 = x1; a.c0 = c0; a.c1 = c1; a.as1 = scale; a.ab1 = bias; a.part = part; a.gblk = gblk; a.B = batch; a.P = pixels;
+  if (!gram_wide_supported(dtype, c0 + c1, c0, 4 * (c0 + c1), pixels)) { set_err("gram_wide: K = 192, 2-byte dtype, pixels a multiple of 128"); return LLIE_ERR_SHAPE; }
+  return kerr("gram_wide", launch_gram_wide(dtype, a, hs(stream)), LLIE_ERR_ARG, hipGetErrorString(hipErrorInvalidValue));
+}
+int llie_gram_group_weights(int dtype, const void* wpack, double* mg, int chid, int K, llie_stream stream) {
+  if (!wpack || !mg) return LLIE_ERR_ARG;
+  return kerr("gram_group_weights", launch_gram_group_weights(dtype, wpack, mg, chid, K, hs(stream)), LLIE_ERR_SHAPE, "2-byte dtype, K = 192, Chid = 768");
+}
+int llie_gram_group_finalize(const float* gblk, const double* mg, int K, int pixels, const float* gamma, const float* beta, const float* film,
+                             int64_t film_stride, float eps, float post_scale, int batch, float* scale_out, float* shift_out, llie_stream stream) {
+  if (!gblk || !mg || !gamma || !beta || !scale_out || !shift_out || batch <= 0 || pixels <= 0 || K != kGramWideK) return LLIE_ERR_ARG;
+  GramGroupFinalizeArgs a{};
+  a.gblk = gblk; a.mg = mg; a.K = K; a.Chid = 4 * K; a.groups = 32; a.P = pixels; a.B = batch; a.gamma = gamma; a.beta = beta;
+  a.film = film; a.film_stride = film_stride; a.eps = eps; a.as = scale_out; a.ab = shift_out; a.post_scale = post_scale;
+  return kerr("gram_group_finalize", launch_gram_group_finalize(a, hs(stream)));
+}
+int llie_pw_expand_act(int dtype, const llie_gemm_seg* segs, int nseg, const float* w32, void* wpack, const float* scale2, const float* shift2,
+                       const float* w_dw, void* out, unsigned long long* pool_totals, int M, int N, int H, int W, llie_stream stream) {
+  if (!segs || nseg < 1 || nseg > 3 || !wpack || !out || !scale2 || !shift2 || !w_dw || !pool_totals || dtype < 1 || dtype > 2 || H <= 0 || W <= 0)
+    return LLIE_ERR_ARG;
+  ExpandArgs x{};
+  x.nseg = nseg;
+  x.K = to_segs(segs, nseg, x.seg);
+  x.wf = wpack; x.out = out; x.M = M; x.N = N; x.P = H * W; x.H = H; x.W = W;
+  x.as2 = scale2; x.ab2 = shift2; x.wd = w_dw; x.pool_tot = pool_totals;
+  hipStream_t s = hs(stream);
+  hipError_t e = !pw_expand_act_supported(dtype, x.seg, nseg, M, N, x.K, x.P, H, W) ? hipErrorInvalidValue
+                 : (w32 ? launch_pack_expand(dtype, w32, wpack, N, x.K, 6.f, s) : hipSuccess);
+  if (e == hipSuccess) e = launch_pw_expand_act(dtype, x, s);
+  return kerr("pw_expand_act", e);
+}
+int llie_dwconv3x3_project_preact(int dtype, const void* h1a, const float* w_dw, const float* gate, const void* x0, int c0, const void* x1, int c1,
+                                  const void* w_project_skip, int ld, int cout, void* y, float* stats, int batch, int H, int W, llie_stream stream) {
+  if (!h1a || !w_dw || !gate || !x0 || !w_project_skip || !y || !stats || batch <= 0 || c0 <= 0 || c1 < 0 || (c1 > 0) != (x1 != nullptr) || cout <= 0 ||
+      ld < 5 * (c0 + c1))
+    return LLIE_ERR_ARG;
+  IrbxArgs a{};
+  a.h1 = h1a; a.h1_act = 1; a.wd = w_dw; a.gate = gate; a.x0 = x0; a.c0 = c0; a.x1 = x1; a.c1 = c1; a.wp = w_project_skip;
+  a.ldp = ld; a.y = y; a.ystats = stats; a.B = batch; a.H = H; a.W = W; a.Chid = 4 * (c0 + c1);
+  return kerr("dwconv3x3_project_preact", launch_dwconv3x3_project(dtype, a, cout, hs(stream)), LLIE_ERR_SHAPE, kWideShapes);
+}
 int llie_irbx_project_tiles(int H, int W) { return H > 0 && W > 0 && H % 8 == 0 && W % 16 == 0 ? irbx_project_tiles(H, W) : LLIE_ERR_ARG; }
 
 int llie_dwconv3x3_tiles(int H, int W) { return dwconv_ntiles(H, W); }

@@ -73,6 +73,11 @@ struct ExpandArgs {
   int nsplit;  // set by the launcher
   int nt;      // 1: non-temporal output stores (see GemmArgs::nt)
   unsigned long long* stamps;  // diagnostic builds only (pw_expand_debug)
+  // launch_pw_expand_act: norm2's tables [B][N] DIVIDED BY 6 (DwArgs::s6), the depthwise weights [9][N] fp32, the image size
+  // (H * W == P) and the fixed-point SE pool totals [B][N] it adds to; `stats` is not used
+  const float* as2; const float* ab2; const float* wd;
+  unsigned long long* pool_tot;
+  int H, W;
 };
 __host__ __device__ inline long long pw_expand_pack_index(int n, int k, int K) {
   const int lane = (n & 31) + 32 * ((k >> 3) & 1);
@@ -81,8 +86,13 @@ __host__ __device__ inline long long pw_expand_pack_index(int n, int k, int K) {
 bool pw_expand_supported(int dtype, const GemmSeg* seg, int nseg, int M, int N, int K, int P);
 bool pw_expand_serves_k(int K);  // the kernel exists for this input width (the builder packs the fragment-ordered weight copy only then)
 hipError_t launch_pw_expand(int dtype, const ExpandArgs& a, hipStream_t s);
+// The activating form (wide block 192 -> 768 with norm2's tables from the wide Gram): stores a = T(clamp01(h1 as2 + ab2)) instead
+// of h1 and adds the SE pool totals of dwconv3x3(a, T(6 wd)) to pool_tot, as dwconv3x3_pool would from the stored h1
+bool pw_expand_act_supported(int dtype, const GemmSeg* seg, int nseg, int M, int N, int K, int P, int H, int W);
+hipError_t launch_pw_expand_act(int dtype, const ExpandArgs& a, hipStream_t s);
 hipError_t launch_pack_expand(int dtype, const float* src, void* dst, int N, int K, float scale, hipStream_t s);
 void pw_expand_enable(int v);  // knob "pwx" (1 = use where supported)
+bool pw_expand_enabled();
 void pw_expand_debug(int stamp);  // knob "pwx_stamp": 1 = launch the cycle-stamped build
 hipError_t pw_expand_stamp_fetch(double* out4);
 
@@ -154,6 +164,41 @@ bool gram_supported(int dtype, int K, int c0, int P);
 hipError_t launch_gram_stats(int dtype, const GramArgs& a, hipStream_t s);
 hipError_t launch_gram_finalize(int dtype, const GramFinalizeArgs& a, hipStream_t s);
 
+// The same statistics for the wide decoder block 192 -> 64 (hid 768), known BEFORE the expand GEMM runs, so that pw_expand can
+// store the activated h1 and add the SE pool totals itself (gram.hip).  G is kept as its 21 upper 32 x 32 blocks in the order of
+// gram_wide_block, then m: kGramWideFloats floats per image.  M_g / u_g (launch_gram_group_weights, load time) use the same layout
+// in fp64, one set per GroupNorm group, off-diagonal blocks doubled.
+constexpr int kGramWideK = 192, kGramWideBlocks = 21, kGramWideFloats = kGramWideBlocks * 1024 + kGramWideK;
+__host__ __device__ inline void gram_wide_block(int q, int* bi, int* bj) {  // block q of the layout = G[32 bi ..][32 bj ..]
+  const int w = q / 7, t = q % 7, x = 2 * w, y = 2 * ((w + 1) % 3);
+  *bi = t == 2 || t >= 5 ? x + 1 : x;
+  *bj = t == 0 ? x : (t <= 2 ? x + 1 : (t == 3 || t == 5 ? y : y + 1));
+}
+struct GramWideArgs {
+  const void* x0; const void* x1; int c0, c1;   // block input (virtual concat), c0 + c1 == 192, c0 % 8 == 0
+  const float* as1; const float* ab1;            // [B][192] GroupNorm-1 affine DIVIDED BY 6
+  float* part;                                    // [B][P / gram_wide_rows(P)][kGramWideFloats] workgroup partials
+  float* gblk;                                    // [B][kGramWideFloats]
+  int B, P, RP;                                   // RP is set by the launcher (gram_wide_rows)
+};
+struct GramGroupFinalizeArgs {
+  const float* gblk;   // as written by launch_gram_wide
+  const double* mg;    // [groups][kGramWideFloats] of the layer (launch_gram_group_weights)
+  int K, Chid, groups, P, B;
+  const float* gamma; const float* beta;   // norm2
+  const float* film; int64_t film_stride;  // null or [rows][2 Chid]
+  float eps;
+  float* as; float* ab;                    // [B][Chid]
+  float post_scale;
+};
+int gram_wide_rows(int P);
+size_t gram_wide_part_floats(int P);
+bool gram_wide_supported(int dtype, int K, int c0, int Chid, int P);
+hipError_t launch_gram_wide(int dtype, const GramWideArgs& a, hipStream_t s);  // the Gram pass and the sum of its partials
+hipError_t launch_gram_group_finalize(const GramGroupFinalizeArgs& a, hipStream_t s);
+// wpack: the layer's packed expand weights T(6 W) (launch_pack_expand / LoadDesc::dst_f), already written on this stream; `state` as in launch_load_all
+hipError_t launch_gram_group_weights(int dtype, const void* wpack, double* mg, int Chid, int K, hipStream_t s, const unsigned long long* state = nullptr);
+
 // Recompute form of the block's front half (irbx.hip, 2-byte T): expand_stats writes only h1's statistics slab
 // ([B][P / irbx_stats_rows(P)][2][Chid]), expand_dw produces h2 and the SE pool slab ([B][irbx_pool_tiles][Chid]).
 // The blocks irbx_project_supported names (identity-residual 32 -> 32 and 64 -> 64; 96 -> 32 with a skip conv) go without h2 as
@@ -179,6 +224,7 @@ struct IrbxArgs {
   // wide decoder blocks (dwconv3x3_pool / dwconv3x3_project, below): the stored h1 [B][H][W][Chid] T; as2 / ab2 are then norm2's
   // tables DIVIDED BY 6 (the s6 form of DwArgs), since h1 is the real tensor and not an accumulator / 6
   const void* h1;
+  int h1_act;  // dwconv3x3_project: 1 = h1 holds the activated values a = T(clamp01(h1 as2 + ab2)) (launch_pw_expand_act); as2 / ab2 unused
 };
 // Wide decoder blocks without h2 (irbx.hip), from the stored h1: dwconv3x3_pool adds the SE pool totals from nine sums of
 // a = clamp01(h1 as2 + ab2) (the restatement of expand_pool), and dwconv3x3_project, given the gate, runs depthwise, gate, project

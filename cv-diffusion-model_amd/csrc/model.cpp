@@ -89,6 +89,12 @@ struct Builder {
       w.w_expand_f = reserve((size_t)w.hid * w.cin * es());
       Param& q = c->params.back();
       q.has_f = true; q.f_off = w.w_expand_f; q.f_scale = 6.f;  // the 6 of ReLU6 carried as clamp01(z / 6), kernels.h
+      if (w.cin == kGramWideK && w.hid == 4 * w.cin && w.skip) {
+        // the layer irb_path's wide Gram rule can select: norm2's group matrices, rebuilt with the weight (engine.h: IrbPath::wgram)
+        w.has_mg = true;
+        w.w_mg = reserve((size_t)32 * kGramWideFloats * 8);
+        q.has_mg = true; q.mg_off = w.w_mg;
+      }
     }
     w.w_dw = reserve((size_t)9 * w.hid * 4);
     w.w_dw_flip = reserve((size_t)9 * w.hid * 4);
@@ -492,6 +498,7 @@ int llie_load_param(llie_ctx* c, const char* key, const float* src, int64_t nume
   hipStream_t s = hs(stream);
   hipError_t e = launch_load_one(c->dt, make_desc(c, p, src), c->blob, s);
   if (e == hipSuccess && p.has_fold) e = launch_upconv_fold(c->dt, src, c->blob + p.fold_off, p.O, s);
+  if (e == hipSuccess && p.has_mg) e = launch_gram_group_weights(c->dt, c->blob + p.f_off, reinterpret_cast<double*>(c->blob + p.mg_off), p.rows, p.cols, s);
   if (e != hipSuccess) { set_err("repack of '%s' failed: %s", key, hipGetErrorString(e)); return (int)e; }
   p.loaded = true;
   // the blob no longer holds what the last llie_load_all wrote, whose content hash a llie_refresh_params of the same tensors
@@ -534,6 +541,11 @@ static int load_all_impl(llie_ctx* c, const float* const* srcs, int n, llie_stre
   // the up-sampling convs' folded sets gather nine source values per element: a launch of their own, under the same "changed" flag
   for (int i = 0; e == hipSuccess && i < n; ++i)
     if (c->params[i].has_fold) e = launch_upconv_fold(c->dt, srcs[i], c->blob + c->params[i].fold_off, c->params[i].O, s, c->hash_state);
+  // and norm2's group matrices of the wide Gram form, from the packed weights the kernel above has just written: under the same flag
+  for (int i = 0; e == hipSuccess && i < n; ++i)
+    if (c->params[i].has_mg)
+      e = launch_gram_group_weights(c->dt, c->blob + c->params[i].f_off, reinterpret_cast<double*>(c->blob + c->params[i].mg_off), c->params[i].rows,
+                                    c->params[i].cols, s, c->hash_state);
   if (e != hipSuccess) { set_err("llie_load_all: %s", hipGetErrorString(e)); return (int)e; }
   for (int i = 0; i < n; ++i) c->params[i].loaded = true;
   return LLIE_OK;
@@ -633,6 +645,33 @@ int llie_irb_forms(llie_ctx* c, int H, int W, int* out6, int cap_blocks) {
         int* o = out6 + 6 * n;
         o[0] = iw.cin; o[1] = iw.hid; o[2] = iw.cout; o[3] = h; o[4] = w; o[5] = (int)form;
       }
+      ++n;
+    }
+  };
+  const std::vector<int>& ch = c->channels;
+  int h = H, w = W;
+  for (int l = 0; l < 4; ++l) {
+    walk(c->enc[l], h, w, 0);
+    if (l < 3) { h /= 2; w /= 2; }
+  }
+  walk(c->mid, h, w, 0);
+  for (int l = 0; l < 4; ++l) {
+    if (l > 0) { h *= 2; w *= 2; }
+    walk(c->dec[l], h, w, l == 0 ? ch[3] : ch[4 - l]);
+  }
+  return n;
+}
+// Which of those blocks take the wide Gram form (IrbPath::wgram), same walk and order: one int per block.  Returns the number of blocks.
+int llie_irb_wide_gram(llie_ctx* c, int H, int W, int* out1, int cap_blocks) {
+  if (!c || c->cfg.kind != LLIE_UNET || H <= 0 || W <= 0 || (cap_blocks > 0 && !out1)) return LLIE_ERR_ARG;
+  int n = 0;
+  auto walk = [&](const std::vector<Block>& bl, int h, int w, int x0c) {
+    bool first = true;
+    for (const Block& b : bl) {
+      if (b.kind != 0) { first = false; continue; }
+      const IrbW& iw = c->irbs[b.idx];
+      if (n < cap_blocks) out1[n] = irb_path(c->dt, iw, (first && x0c) ? x0c : iw.cin, h, w, false).wgram ? 1 : 0;
+      first = false;
       ++n;
     }
   };

@@ -63,6 +63,7 @@ constexpr bool pwx_has_tile(int KS, int NBW, bool REGSTORE) { return !REGSTORE |
 constexpr int pwx_lds_bytes(int KS, int NBW, bool REGSTORE) {
   return 2 * NBW * KS * 1024 + 2 * 4 * NBW * 64 * 4 + (pwx_has_tile(KS, NBW, REGSTORE) ? 4 * 32 * kStagePitch : 0);
 }
+constexpr int kPwxActMaxN = 768;  // ACT: three fp32 per output channel behind the tiles (norm2's scale and shift, the sum of the nine depthwise weights)
 
 }  // namespace
 
@@ -70,8 +71,18 @@ constexpr int pwx_lds_bytes(int KS, int NBW, bool REGSTORE) {
 // REGSTORE = output stores straight from registers (32 rows x 32 bytes per instruction) instead of through the LDS tile.
 // STAMP (llie_tune "pwx_stamp") = s_memtime per wave after the A phase and at the end.  Template parameters, not run-time
 // flags: a flag inside the MFMA loop changes the code it measures.
-template <typename T, int KS, int NBW, bool REGSTORE = false, bool STAMP = false>
-__global__ void __launch_bounds__(256, 2) pw_expand_kernel(const ExpandArgs g) {
+//
+// ACT (pw_expand_act_kernel): norm2's tables are known before the launch (gram.hip: the wide Gram), so the epilogue stores the
+// ACTIVATED h1, a = T(clamp01(acc s + b)) with one rounding, and adds the SE pool totals dwconv3x3_pool would have added from it:
+// no statistics slab.  The depthwise conv is linear and zero-padded, so the totals are nine border-aware sums of a per channel
+// (irbx.hip: expand_scan<POOL>).  This kernel adds the first of them, the sum over all pixels times the sum of the nine weights:
+// lane = channel here, so it is eight v_dot2 per block and one fixed-point add per channel and 128-pixel tile.  The other eight
+// (first / last row and column, four corners) touch 4 (H + W) pixels of the image and are taken back out by
+// pool_border_kernel from the stored tensor.  Nothing is loaded from global memory inside the channel loop: vmcnt counts in
+// order, so a load's wait would also wait for the output stores issued before it (with norm2's tables and the border weights
+// fetched per block the launch took 325 us instead of 245); the tables and the weight sums are staged in LDS before the loop.
+template <typename T, int KS, int NBW, bool REGSTORE, bool STAMP, bool ACT>
+__device__ __forceinline__ void pw_expand_body(const ExpandArgs& g) {
   unsigned long long t_start = 0, t_a = 0, t_wait = 0;
   if constexpr (STAMP) t_start = __builtin_amdgcn_s_memtime();
   static_assert(sizeof(T) == 2 && KS % 4 == 0, "");
@@ -81,6 +92,7 @@ __global__ void __launch_bounds__(256, 2) pw_expand_kernel(const ExpandArgs g) {
   extern __shared__ __align__(16) unsigned char smem[];
   float* red = reinterpret_cast<float*>(smem + 2 * BUF);  // [2][4 waves][NBW][2][32]
   unsigned char* tbuf = smem + 2 * BUF + 2 * 4 * NBW * 64 * 4 + (threadIdx.x >> 6) * (32 * kStagePitch);
+  float* swall = reinterpret_cast<float*>(smem + pwx_lds_bytes(KS, NBW, REGSTORE));  // ACT only
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int lr = lane & 31, lh = lane >> 5;
@@ -109,6 +121,16 @@ __global__ void __launch_bounds__(256, 2) pw_expand_kernel(const ExpandArgs g) {
     }
   };
   dma(0);
+  if constexpr (ACT) {  // [scale2][shift2][sum of the nine T(6 w)] of this workgroup's channels
+    for (int c = tid; c < nper; c += 256) {
+      float t = 0.f;
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) t += (float)(T)(6.f * g.wd[tap * g.N + nbase + c]);
+      swall[c] = g.as2[(size_t)img * g.N + nbase + c];
+      swall[kPwxActMaxN + c] = g.ab2[(size_t)img * g.N + nbase + c];
+      swall[2 * kPwxActMaxN + c] = t;
+    }
+  }
 
   // ---- A phase: this wave's 32 pixel rows -> activated MFMA fragments in registers --------------------------------
   u32x4 afr[KS];
@@ -179,7 +201,17 @@ __global__ void __launch_bounds__(256, 2) pw_expand_kernel(const ExpandArgs g) {
   T* outp = reinterpret_cast<T*>(g.out) + (m0 + wave * 32 + lr) * g.N + nbase + lh * 8;
   const int ntiles = tpi;
   auto flush_stats = [&](int it) {  // after a barrier: combine the four waves' partial sums of buffer `it` in wave order
-    if (tid < NBW * 64) {
+    if constexpr (ACT) {
+      // the tile's sum of the channel, times the sum of its weights, parked in the weight sum's own LDS slot (this thread alone
+      // touches it): the fixed-point adds leave together at the end.  Issued here they sat in front of every vmcnt wait of wave 0,
+      // and the other three waves waited for it at the barrier
+      if (tid < NBW * 64 && (tid & 32) == 0) {
+        const float* r = red + (size_t)(it & 1) * 4 * NBW * 64 + tid;  // [wave][lane half][channel]
+        const float t = (((r[0] + r[32]) + (r[NBW * 64] + r[NBW * 64 + 32])) + (r[2 * NBW * 64] + r[2 * NBW * 64 + 32])) + (r[3 * NBW * 64] + r[3 * NBW * 64 + 32]);
+        const int c = (it * NBW + (tid >> 6)) * 32 + (tid & 31);
+        swall[2 * kPwxActMaxN + c] *= t;
+      }
+    } else if (tid < NBW * 64) {
       const float* r = red + (size_t)(it & 1) * 4 * NBW * 64 + tid;
       const float t = ((r[0] + r[NBW * 64]) + r[2 * NBW * 64]) + r[3 * NBW * 64];
       const int j = tid >> 6, which = (tid >> 5) & 1, c = tid & 31;
@@ -201,6 +233,11 @@ __global__ void __launch_bounds__(256, 2) pw_expand_kernel(const ExpandArgs g) {
       f32x16 acc;
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+      float sc2 = 0.f, sh2 = 0.f;  // ACT: norm2's tables of the lane's channel (LDS), requested ahead of the MFMAs
+      if constexpr (ACT) {
+        sc2 = swall[(it * NBW + j) * 32 + lr];
+        sh2 = swall[kPwxActMaxN + (it * NBW + j) * 32 + lr];
+      }
       {
         // the weight fragments run PD reads ahead of their MFMAs (left alone, hipcc issues two reads, waits for both and
         // multiplies twice: at two waves per SIMD the matrix pipe then waits on LDS latency in every pair)
@@ -220,25 +257,40 @@ __global__ void __launch_bounds__(256, 2) pw_expand_kernel(const ExpandArgs g) {
       }
       // ---- epilogue of one 32 pixel x 32 channel block (lane = channel lr, registers = 16 pixels) ----
       u32x4 h0, h1;
+      if constexpr (ACT) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        h0[q] = pack2<T>(acc[2 * q], acc[2 * q + 1]);
-        h1[q] = pack2<T>(acc[8 + 2 * q], acc[8 + 2 * q + 1]);
-      }
-      float s1 = 0.f, s2 = 0.f;
+        for (int q = 0; q < 4; ++q) {
+          h0[q] = affine_clamp01_pack<T>(acc[2 * q], acc[2 * q + 1], sc2, sc2, sh2, sh2);
+          h1[q] = affine_clamp01_pack<T>(acc[8 + 2 * q], acc[8 + 2 * q + 1], sc2, sc2, sh2, sh2);
+        }
+        float gs = 0.f;  // the lane's 16 pixels of the channel, as stored
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        s1 = dot2<T>(h0[q], ones2, s1);
-        s2 = dot2<T>(h0[q], h0[q], s2);
-      }
+        for (int q = 0; q < 4; ++q) {
+          gs = dot2<T>(h0[q], ones2, gs);
+          gs = dot2<T>(h1[q], ones2, gs);
+        }
+        redw[j * 64] = gs;
+      } else {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        s1 = dot2<T>(h1[q], ones2, s1);
-        s2 = dot2<T>(h1[q], h1[q], s2);
-      }
-      {  // lanes 0-31 end up with the channel's sum, lanes 32-63 with its sum of squares (one half swap)
-        const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(s1), __float_as_uint(s2), false, false);
-        redw[j * 64] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+        for (int q = 0; q < 4; ++q) {
+          h0[q] = pack2<T>(acc[2 * q], acc[2 * q + 1]);
+          h1[q] = pack2<T>(acc[8 + 2 * q], acc[8 + 2 * q + 1]);
+        }
+        float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          s1 = dot2<T>(h0[q], ones2, s1);
+          s2 = dot2<T>(h0[q], h0[q], s2);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          s1 = dot2<T>(h1[q], ones2, s1);
+          s2 = dot2<T>(h1[q], h1[q], s2);
+        }
+        {  // lanes 0-31 end up with the channel's sum, lanes 32-63 with its sum of squares (one half swap)
+          const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(s1), __float_as_uint(s2), false, false);
+          redw[j * 64] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+        }
       }
       f32x16 d2;
 #pragma unroll
@@ -300,6 +352,10 @@ __global__ void __launch_bounds__(256, 2) pw_expand_kernel(const ExpandArgs g) {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   flush_stats(nit - 1);
+  if constexpr (ACT) {  // one fixed-point add per channel and 128-pixel tile: the float order is fixed, the integer adds commute
+    wg_barrier();
+    for (int c = tid; c < nper; c += 256) fixed_add(g.pool_tot + (size_t)img * g.N + nbase + c, swall[2 * kPwxActMaxN + c], kPoolFixScale);
+  }
   if constexpr (STAMP) {
     if (g.stamps && lane == 0) {
       const unsigned long long t_end = __builtin_amdgcn_s_memtime();
@@ -309,6 +365,14 @@ __global__ void __launch_bounds__(256, 2) pw_expand_kernel(const ExpandArgs g) {
       g.stamps[3 * wv + 2] = t_wait;
     }
   }
+}
+template <typename T, int KS, int NBW, bool REGSTORE = false, bool STAMP = false>
+__global__ void __launch_bounds__(256, 2) pw_expand_kernel(const ExpandArgs g) {
+  pw_expand_body<T, KS, NBW, REGSTORE, STAMP, false>(g);
+}
+template <typename T, int KS, int NBW>
+__global__ void __launch_bounds__(256, 2) pw_expand_act_kernel(const ExpandArgs g) {
+  pw_expand_body<T, KS, NBW, false, false, true>(g);
 }
 
 // Weight pack: fp32 [N][K] (OIHW of a 1x1 conv) -> T in MFMA B-fragment order, times `scale`:
@@ -330,6 +394,7 @@ hipError_t launch_pack_expand(int dtype, const float* src, void* dst, int N, int
 
 static int g_use_pwx = 1;
 void pw_expand_enable(int v) { g_use_pwx = v; }
+bool pw_expand_enabled() { return g_use_pwx != 0; }
 
 // 32-channel blocks per LDS buffer.  One everywhere: the smaller LDS footprint (three workgroups per CU up to K = 256) is
 // worth more than the saved barriers (measured in round 3: profiles/r03)
@@ -404,6 +469,77 @@ static hipError_t launch_t(const ExpandArgs& a, hipStream_t s) {
     case 512: return launch_cfg<T, 32>(a, s);
   }
   return hipErrorInvalidValue;
+}
+// The border part of the SE pool totals of an ACTIVATED h1 [B][H][W][N]: a tap (ky, kx) of the zero-padded depthwise conv reads pixel
+// p + (ky - 1, kx - 1), so summed over the image it misses the far border row and / or column (dwconv3x3_pool_kernel's table).
+// pw_expand_act_kernel has added (sum over all pixels) x (sum of the nine weights); this takes the border sums back out.
+// grid (4 sides, N / 64, B): side 0 / 1 = first / last row with its two corners, 2 / 3 = first / last column.  Thread (cv = tid & 7,
+// pl = tid >> 3) adds the pixels pl, pl + 32, ... of the side for 8 channels; the 32 slots are added in slot order through LDS and
+// one fixed-point add per channel leaves: the float order depends on (H, W) alone, the integer adds commute.
+template <typename T>
+__global__ void __launch_bounds__(256) pool_border_kernel(const T* h1a, const float* wd, unsigned long long* pool_tot, int H, int W, int N) {
+  __shared__ float red[32][64];
+  const int side = blockIdx.x, cbase = blockIdx.y * 64, b = blockIdx.z, tid = threadIdx.x, cv = tid & 7, pl = tid >> 3;
+  const T* img = h1a + (size_t)b * H * W * N + cbase + cv * 8;
+  const int n = side < 2 ? W : H;
+  const size_t first = side == 0 ? 0 : (side == 1 ? (size_t)(H - 1) * W : (side == 2 ? 0 : (size_t)W - 1));
+  const size_t stride = side < 2 ? 1 : (size_t)W;
+  float acc[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+  for (int i = pl; i < n; i += 32) {
+    float f[8];
+    vec_to_f32<T>(ld_vec<T>(img + (first + (size_t)i * stride) * N), f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] += f[e];
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) red[pl][cv * 8 + e] = acc[e];
+  wg_barrier();
+  if (tid >= 64) return;
+  const int c = cbase + tid;
+  float sum = 0.f;
+#pragma unroll
+  for (int p = 0; p < 32; ++p) sum += red[p][tid];
+  float w[9];
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap) w[tap] = (float)(T)(6.f * wd[tap * N + c]);
+  float t;
+  if (side < 2) {  // a row: its taps, and its two corners back in (the column sides take them out a second time)
+    const T* row = h1a + ((size_t)b * H * W + first) * N + c;
+    const float k0 = (float)row[0], k1 = (float)row[(size_t)(W - 1) * N];
+    t = side == 0 ? -sum * ((w[6] + w[7]) + w[8]) : -sum * ((w[0] + w[1]) + w[2]);
+    t = __builtin_fmaf(k0, side == 0 ? w[8] : w[2], t);
+    t = __builtin_fmaf(k1, side == 0 ? w[6] : w[0], t);
+  } else {
+    t = side == 2 ? -sum * ((w[2] + w[5]) + w[8]) : -sum * ((w[0] + w[3]) + w[6]);
+  }
+  fixed_add(pool_tot + (size_t)b * N + c, t, kPoolFixScale);
+}
+
+// The activating form: 192 -> 768 only (the block the engine's rule can select)
+bool pw_expand_act_supported(int dtype, const GemmSeg* seg, int nseg, int M, int N, int K, int P, int H, int W) {
+  return K == 192 && N == 768 && N <= kPwxActMaxN && H > 0 && W > 0 && W % 16 == 0 && H * W == P && pw_expand_supported(dtype, seg, nseg, M, N, K, P);
+}
+template <typename T>
+static hipError_t launch_act_t(ExpandArgs a, hipStream_t s) {
+  constexpr int KS = 12, NBW = kPwxNbw, lds = pwx_lds_bytes(KS, NBW, false) + 3 * kPwxActMaxN * 4;
+  static_assert(3 * lds <= 160 * 1024, "three workgroups per CU, as pw_expand_kernel<T, 12, 1>");
+  a.nsplit = nsplit_for(a.M, a.N, NBW);
+  static const std::string name = std::string("pw_expand_act_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) + ", " + std::to_string(NBW) + ">";
+  note_kernel(name.c_str());
+  static std::atomic<uint64_t> attr_done{0};
+  if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&pw_expand_act_kernel<T, KS, NBW>), lds, attr_done); e != hipSuccess) return e;
+  hipLaunchKernelGGL((pw_expand_act_kernel<T, KS, NBW>), dim3((unsigned)((a.M / 128) * a.nsplit)), dim3(256), lds, s, a);
+  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  hipLaunchKernelGGL((pool_border_kernel<T>), dim3(4, a.N / 64, a.M / a.P), dim3(256), 0, s, reinterpret_cast<const T*>(a.out), a.wd, a.pool_tot, a.H, a.W, a.N);
+  return hipGetLastError();
+}
+// out = T(clamp01((6 W a') as2 + ab2)) and pool_tot += its SE pool totals (fixed point, kPoolFixScale; the caller zeroes it)
+hipError_t launch_pw_expand_act(int dtype, const ExpandArgs& a, hipStream_t s) {
+  if (!a.wf || !a.out || !a.as2 || !a.ab2 || !a.wd || !a.pool_tot || !pw_expand_act_supported(dtype, a.seg, a.nseg, a.M, a.N, a.K, a.P, a.H, a.W))
+    return hipErrorInvalidValue;
+  return dtype == 1 ? launch_act_t<half_t>(a, s) : launch_act_t<bf16_t>(a, s);
 }
 hipError_t launch_pw_expand(int dtype, const ExpandArgs& a, hipStream_t s) {
   // host-side shape contract (an out-of-contract shape would index out of bounds on the device)

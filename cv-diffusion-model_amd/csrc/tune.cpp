@@ -19,6 +19,10 @@ static Knobs knob_defaults() {
   // pool from one read of h1 (dwconv3x3_pool), then depthwise + gate + project + skip conv in one kernel (dwconv3x3_project);
   // llie_tune("wide_project", 0) restores dwconv3x3 + pw_gemm.
   k.wide_project = 1;
+  // Of those, the 192 -> 64 block knows norm2's tables before its expand GEMM runs (the Gram of the activated input, gram.hip):
+  // pw_expand stores the activated h1 and adds the pool totals itself, the pool pass goes.  llie_tune("wide_gram", 0) restores it,
+  // 2 takes the form at every map size (1: from 4096 pixels per image).
+  k.wide_gram = 1;
   k.gram = 1;  // norm2 statistics of the recompute form from the Gram matrix of the block input (gram.hip); 0 = expand_stats
   // Cache policy of the big activation tensors (inference): a tensor of at least nt_min_mb MiB (this run's batch) is stored
   // non-temporally by its producer (common.h: st_vec_pol).  nt_mask picks the producers: 1 expand_dw (h2), 2 pw_expand (h1),
@@ -76,6 +80,7 @@ int llie_tune(const char* knob, int value) {
   if (!strcmp(knob, "irbx")) { g_knobs.use_irbx = value != 0; return LLIE_OK; }
   if (!strcmp(knob, "irbx_project")) { g_knobs.irbx_project = value < 0 || value > 2 ? 1 : value; return LLIE_OK; }
   if (!strcmp(knob, "wide_project")) { g_knobs.wide_project = value != 0; return LLIE_OK; }
+  if (!strcmp(knob, "wide_gram")) { g_knobs.wide_gram = value < 0 || value > 2 ? 1 : value; return LLIE_OK; }
   if (!strcmp(knob, "irbx_dbuf")) { irbx_tune(value); return LLIE_OK; }
   if (!strcmp(knob, "irbx_stamp")) { irbx_stamp(value); return LLIE_OK; }
   if (!strcmp(knob, "irbx_grid")) { irbx_grid(0, value); return LLIE_OK; }

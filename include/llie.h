@@ -803,6 +803,35 @@ int llie_dwconv3x3_pool(int dtype, const void* h1, const float* scale2, const fl
 int llie_dwconv3x3_project(int dtype, const void* h1, const float* scale2, const float* shift2, const float* w_dw, const float* gate, const void* x0,
                            int c0, const void* x1, int c1, const void* w_project_skip, int ld, int cout, void* y, float* stats, int batch, int H,
                            int W, llie_stream stream);
+/* The wide Gram form of the 192 -> 64 block (knob "wide_gram", default 1 = maps of at least 4096 pixels, 2 = every map; 0 = the pool pass
+ * from the stored h1, bit for bit what the engine computed before the form existed):
+ * norm2's tables are known BEFORE the expand GEMM, from the Gram matrix G = sum_px a' a'^T and m = sum_px a' of the activated input
+ * a' = clamp01(x scale1 + shift1), so the expand GEMM stores the activated h1 and adds the SE pool totals itself.
+ * llie_wide_gram_supported: 2-byte dtype, cin = 192, chid = 768, c0 % 8 == 0, pixels % 128 == 0.
+ * llie_gram_wide: gblk [batch][llie_gram_wide_floats()] fp32 = the 21 upper 32 x 32 blocks of G (block q = rows 32 bi, columns 32 bj
+ *   of llie_gram_wide_block), then m[192]; part: scratch of batch x llie_gram_wide_part_floats(pixels) floats.  Batch-invariant bits.
+ * llie_gram_group_weights: mg fp64 [32][llie_gram_wide_floats()] from the packed expand weights (wpack as llie_pw_expand fills or
+ *   takes it: the weight times 6 rounded to the compute type, what the GEMM multiplies with): per GroupNorm group M_g = sum_c w_c w_c^T
+ *   in the same block layout (off-diagonal blocks doubled) and u_g = sum_c w_c.
+ * llie_gram_group_finalize: norm2 + FiLM tables [batch][768] from <G, M_g> and <m, u_g> in fp64 (times post_scale unless 0).
+ * llie_pw_expand_act: out [M][768] = T(clamp01((w a') scale2 + shift2)), one rounding; pool_totals uint64 [batch][768] += what
+ *   llie_dwconv3x3_pool adds from such a tensor (the caller zeroes it).  w32 / wpack as llie_pw_expand; M = batch x H x W.
+ * llie_dwconv3x3_project_preact: llie_dwconv3x3_project on an h1 that already holds the activated values (cout = 64).
+ * llie_irb_wide_gram: one int per block in llie_irb_forms' order: 1 where the engine takes this form. */
+int llie_wide_gram_supported(int dtype, int cin, int c0, int chid, int pixels);
+int64_t llie_gram_wide_floats(void);
+int64_t llie_gram_wide_part_floats(int pixels);
+int llie_gram_wide_block(int q, int* bi, int* bj);
+int llie_gram_wide(int dtype, const void* x0, int c0, const void* x1, int c1, const float* scale, const float* bias, int batch, int pixels,
+                   float* part, float* gblk, llie_stream stream);
+int llie_gram_group_weights(int dtype, const void* wpack, double* mg, int chid, int K, llie_stream stream);
+int llie_gram_group_finalize(const float* gblk, const double* mg, int K, int pixels, const float* gamma, const float* beta, const float* film,
+                             int64_t film_stride, float eps, float post_scale, int batch, float* scale_out, float* shift_out, llie_stream stream);
+int llie_pw_expand_act(int dtype, const llie_gemm_seg* segs, int nseg, const float* w32, void* wpack, const float* scale2, const float* shift2,
+                       const float* w_dw, void* out, unsigned long long* pool_totals, int M, int N, int H, int W, llie_stream stream);
+int llie_dwconv3x3_project_preact(int dtype, const void* h1a, const float* w_dw, const float* gate, const void* x0, int c0, const void* x1, int c1,
+                                  const void* w_project_skip, int ld, int cout, void* y, float* stats, int batch, int H, int W, llie_stream stream);
+int llie_irb_wide_gram(llie_ctx* c, int H, int W, int* out1, int cap_blocks);
 /* llie_expand_dw_plan: the launch plan expand_dw (project = 0) or expand_dw_project (project = 1) takes for cin input channels at
  *   these sizes, the "irbx_grid*" knobs included (they act on expand_dw only; the dtype and the segment split do not enter).
  *   plan4[0] = tiles per workgroup, a run along x (4, 2 or 1: the largest that divides W / 16 and keeps 2048 workgroups; 0 = the
