@@ -54,6 +54,7 @@ EXPORTS = [
     "llie_ssim_grad_scratch_bytes", "llie_ssim_grad_f32", "llie_x0_loss",
     "llie_train_shape_ok", "llie_unet_train_forward_hw", "llie_aug_pair_u8_hw", "llie_aug_synth_u8_hw",
     "llie_tile_gather_u8_hw", "llie_tile_gather_f32_hw", "llie_tile_blend_u8_hw", "llie_tile_sync_step_hw", "llie_frame_max_pixels",
+    "llie_unet_backward_dx", "llie_init_conv_dgrad",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 PW_SIGMOID_BWD, PW_RELU6_BWD, PW_SILU_BWD, PW_SCALE = 0, 1, 2, 3  # llie_pointwise_kind
@@ -248,6 +249,7 @@ def lib() -> C.CDLL:
     L.llie_init_conv_pack_bytes.restype = i64
     L.llie_init_conv_tiles.argtypes = [ci, ci, ci]
     L.llie_init_conv.argtypes = [ci, vp, ci, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, i64, vp]
+    L.llie_init_conv_dgrad.argtypes = [ci, vp, ci, vp, vp, ci, vp, ci, ci, ci, ci, vp, i64, vp]
     L.llie_final_conv_pack_bytes.argtypes = [ci]
     L.llie_final_conv_pack_bytes.restype = i64
     L.llie_final_conv.argtypes = [ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, C.POINTER(StepCoef), vp, vp, vp, vp, vp, i64, vp]
@@ -311,6 +313,7 @@ def lib() -> C.CDLL:
     L.llie_unet_train_forward_hw.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, vp, i64, vp]
     L.llie_train_shape_ok.argtypes = [vp, ci, ci, ci]
     L.llie_unet_backward.argtypes = [vp, vp, vp, ci, vp, i64, vp]
+    L.llie_unet_backward_dx.argtypes = [vp, vp, vp, vp, vp, ci, vp, i64, vp]
     L.llie_module_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, i64, vp]
     L.llie_wgrad.argtypes = [ci, vp, ci, C.POINTER(GemmSeg), ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, i64, vp, i64, i64, i64, ci, vp]
     L.llie_wgrad_msplit.argtypes = [ci, ci, ci, ci, ci, ci, ci]

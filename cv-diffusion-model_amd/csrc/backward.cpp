@@ -358,8 +358,8 @@ struct Back : Exec {
     ar->free(scratch);
   }
 
-  // ---- whole UNet
-  void unet(const float* deps) {
+  // ---- whole UNet; dlat / dcond (optional): fp32 NCHW gradients of the two input halves, caller buffers
+  void unet(const float* deps, float* dlat = nullptr, float* dcond = nullptr) {
     const llie_config& g = c->cfg;
     const int H = tp->H, W = tp->W, C0 = c->channels[0], P = H * W, M = B * P, T = g.time_embed_dim, F = c->film_rows;
     const size_t dfilm = alloc((size_t)B * F * 4);
@@ -409,6 +409,13 @@ struct Back : Exec {
       fork();
       wgrad(g0, C0, &sg, 1, 32, geo, gp(c->i_init_w), (int64_t)g.in_channels * 9, 9, 0, 9, c->channels_r[0], g.in_channels);
       ar->free(slab); ar->free(S1);
+      // data gradient of the input conv, on the main stream beside the weight-gradient GEMM: both only read g0
+      if (!dry && (dlat || dcond)) {
+        InitDgradArgs a{};
+        a.g = p(g0); a.w = wptr<float>(c->init_w); a.dx0 = dlat; a.dx1 = dcond; a.c0 = half; a.c1 = g.in_channels - half;
+        a.B = B; a.H = H; a.W = W; a.C0 = C0;
+        chk(launch_init_conv_dgrad(dt, a, s));
+      }
       defer(x32); defer(g0);
       join();
     }
@@ -569,7 +576,8 @@ int llie_unet_train_forward_hw(llie_ctx* c, const float* lat, const float* cond,
   return train_forward_impl(c, lat, cond, t, eps, batch, height, width, ws, ws_bytes, stream);
 }
 
-int llie_unet_backward(llie_ctx* c, const float* d_eps, float* grads, int batch, void* ws, int64_t ws_bytes, llie_stream stream) {
+int llie_unet_backward_dx(llie_ctx* c, const float* d_eps, float* grads, float* d_latents, float* d_cond, int batch, void* ws,
+                          int64_t ws_bytes, llie_stream stream) {
   if (!c || !d_eps || !grads || !ws || c->cfg.kind != LLIE_UNET) return LLIE_ERR_ARG;
   if (!c->tape.valid || c->tape.ws != ws || c->tape.B != batch || !c->train_arena || (int64_t)c->train_arena->cap != ws_bytes) {
     set_err("llie_unet_backward needs the workspace of the preceding llie_unet_train_forward (same batch)");
@@ -577,8 +585,11 @@ int llie_unet_backward(llie_ctx* c, const float* d_eps, float* grads, int batch,
   }
   Back b{Exec::live(c, c->train_arena, stream, ws, batch), &c->tape, grads};
   if (const int rc = setup_async(c, b)) return rc;
-  b.unet(d_eps);
+  b.unet(d_eps, d_latents, d_cond);
   return b.rc(true);
+}
+int llie_unet_backward(llie_ctx* c, const float* d_eps, float* grads, int batch, void* ws, int64_t ws_bytes, llie_stream stream) {
+  return llie_unet_backward_dx(c, d_eps, grads, nullptr, nullptr, batch, ws, ws_bytes, stream);
 }
 
 int llie_module_backward(llie_ctx* c, const float* x, const float* temb, const float* dy, float* dx, float* dtemb, float* grads,

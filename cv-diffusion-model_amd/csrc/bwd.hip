@@ -828,6 +828,97 @@ hipError_t launch_pack_planes(int dtype, const float* x0, const float* x1, int c
   }
   return hipGetLastError();
 }
+// ---- input conv, data gradient: the transpose of init_conv_kernel (conv.hip) with the roles of patch and output exchanged.
+//   dx[b][ci][y][x] = sum_{ky,kx} sum_co g[b][y + 1 - ky][x + 1 - kx][co] * W[co][ci][ky][kx], zero outside the map
+// One thread = one pixel of a 16 x 16 tile and up to 8 input channels; the tile's 18 x 18 halo patch of g stands in LDS as fp32,
+// 32 channels of co at a time; the weights are the forward's table [ci * 9 + tap][C0], wave-uniform, so they come through the scalar
+// cache and every (ci, tap) is a dot product of two contiguous runs of 32.  The kernel is bound by VALU issue, so the products run
+// on packed FMAs: a channel has two accumulators, the even and the odd co, each one fma chain over (co block, tap, co pair), added
+// at the store.  The order depends on C0 alone; a null output's channels are neither computed nor stored, and the others do not
+// notice.
+// LDS layout: a pixel is 36 dwords (32 + one 16-byte pad) and a patch row 704 dwords (18 pixels = 648, padded to a multiple of the
+// 64 banks): the 16 pixels of a row then cover the 64 banks once per ds_read_b128, and the rows a 16-lane group mixes fall on the
+// same banks as one row would (tools/lds_bank_model.py: 4 cycles per read, the ideal; 8 with rows of 648).
+constexpr int kDgradPix = 36, kDgradRow = 704;
+template <typename T>
+__global__ void __launch_bounds__(256, 3) init_conv_dgrad_kernel(const InitDgradArgs a) {
+  constexpr int VEC = Elem<T>::VEC, NV = 32 / VEC;
+  __shared__ __attribute__((aligned(16))) float patch[18 * kDgradRow];
+  const int tid = threadIdx.x;
+  const int tiles_x = (a.W + 15) / 16;  // edge tiles may be partly empty (H, W multiples of 8)
+  const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x, b = blockIdx.y;
+  const int x0 = tx * 16, y0 = ty * 16;
+  const int lo = a.dx0 ? 0 : a.c0, n = (a.dx1 ? a.c0 + a.c1 : a.c0) - lo;  // channels [lo, lo + n) are wanted
+  const int py = tid >> 4, px = tid & 15;
+  const T* g = reinterpret_cast<const T*>(a.g) + (size_t)b * a.H * a.W * a.C0;
+  // the table is read-only for the whole launch: through the constant address space its wave-uniform loads become scalar loads
+  // (from a plain pointer hipcc issues them as vector loads of one address in all 64 lanes, which the texture path then bounds)
+  typedef const float __attribute__((address_space(4))) kfloat;
+  const kfloat* w = (const kfloat*)a.w;
+  f32x2 acc[8];  // per wanted channel: the sums over the even and over the odd co, one v_pk_fma_f32 per pair of co
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = f32x2{0.f, 0.f};
+  for (int oc0 = 0; oc0 < a.C0; oc0 += 32) {
+    if (oc0) wg_barrier();  // the previous block's reads are done
+    for (int i = tid; i < 324 * NV; i += 256) {
+      const int pix = i / NV, v = i % NV;
+      const int qy = pix / 18, qx = pix % 18;
+      const int gy = y0 + qy - 1, gx = x0 + qx - 1;
+      float f[VEC];
+#pragma unroll
+      for (int e = 0; e < VEC; ++e) f[e] = 0.f;
+      if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) ld_f32<T>(g + ((size_t)gy * a.W + gx) * a.C0 + oc0 + v * VEC, f);
+      float* d = patch + qy * kDgradRow + qx * kDgradPix + v * VEC;
+#pragma unroll
+      for (int q = 0; q < VEC; q += 4) *reinterpret_cast<f32x4*>(d + q) = f32x4{f[q], f[q + 1], f[q + 2], f[q + 3]};
+    }
+    wg_barrier();
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+      // g at (y + 1 - ky, x + 1 - kx) is patch pixel (py + 2 - ky, px + 2 - kx)
+      const float* src = patch + (py + 2 - tap / 3) * kDgradRow + (px + 2 - tap % 3) * kDgradPix;
+      f32x2 gv[16];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(src + 4 * q);
+        gv[2 * q] = f32x2{t[0], t[1]}; gv[2 * q + 1] = f32x2{t[2], t[3]};
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        if (j < n) {  // uniform
+          const kfloat* wr = w + (size_t)((lo + j) * 9 + tap) * a.C0 + oc0;
+          f32x2 s = acc[j];
+#pragma unroll
+          for (int o = 0; o < 16; ++o) s = __builtin_elementwise_fma(gv[o], f32x2{wr[2 * o], wr[2 * o + 1]}, s);
+          acc[j] = s;
+        }
+      }
+    }
+  }
+  if (y0 + py >= a.H || x0 + px >= a.W) return;
+  const size_t plane = (size_t)a.H * a.W, at = (size_t)(y0 + py) * a.W + x0 + px;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    if (j < n) {
+      const int ci = lo + j;
+      float* dst = ci < a.c0 ? a.dx0 + ((size_t)b * a.c0 + ci) * plane : a.dx1 + ((size_t)b * a.c1 + (ci - a.c0)) * plane;
+      dst[at] = acc[j][0] + acc[j][1];
+    }
+  }
+}
+hipError_t launch_init_conv_dgrad(int dtype, const InitDgradArgs& a, hipStream_t s) {
+  if (a.C0 <= 0 || a.C0 % 32 || a.c0 < 1 || a.c1 < 0 || a.c0 + a.c1 > 8 || (!a.dx0 && !a.dx1) || (a.dx1 && !a.c1) || a.B <= 0 ||
+      a.B > 65535 || a.H <= 0 || a.W <= 0)
+    return hipErrorInvalidValue;
+  dim3 grid(init_conv_ntiles(a.H, a.W, false), a.B);  // 16 x 16 tiles
+  switch (dtype) {
+    case 0: note_kernel("init_conv_dgrad_kernel<float>"); hipLaunchKernelGGL(init_conv_dgrad_kernel<float>, grid, dim3(256), 0, s, a); break;
+    case 1: note_kernel("init_conv_dgrad_kernel<_Float16>"); hipLaunchKernelGGL(init_conv_dgrad_kernel<half_t>, grid, dim3(256), 0, s, a); break;
+    case 2: note_kernel("init_conv_dgrad_kernel<__bf16>"); hipLaunchKernelGGL(init_conv_dgrad_kernel<bf16_t>, grid, dim3(256), 0, s, a); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
 // =============================================================================================
 // (8) linear attention backward (forward: efficient_unet.py:288-302).  With Q = phi(q), K = phi(k):
 //   den = Q.ks + 1e-6, out = (Q kv)/den;  dnum = dout/den, dden = -sum_e dout*out/den

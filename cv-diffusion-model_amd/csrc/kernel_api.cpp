@@ -215,6 +215,26 @@ int llie_init_conv(int dtype, const float* x0, int c0, const float* x1, int c1, 
   if (e == hipSuccess) e = launch_init_conv(dtype, a, s);
   return kerr("init_conv", e);
 }
+// the data gradient of init_conv on the forward VALU kernel's fp32 table, repacked from OIHW as above (the MFMA pack is not built)
+int llie_init_conv_dgrad(int dtype, const void* g, int Cout, const float* w_oihw, float* d_x0, int c0, float* d_x1, int c1, int batch,
+                         int H, int W, void* pack, int64_t pack_bytes, llie_stream stream) {
+  if (!dtype_ok(dtype) || !g || !w_oihw || !pack || ((uintptr_t)pack & 15) || c0 < 1 || c1 < 0 || c0 + c1 > 8 || (!d_x0 && !d_x1) ||
+      (d_x1 && c1 == 0) || !conv_sizes_ok(batch, H, W) || Cout <= 0 || Cout % 32 || pack_bytes < llie_init_conv_pack_bytes(c0 + c1, Cout))
+    return LLIE_ERR_ARG;
+  const int Cin = c0 + c1;
+  char* blob = reinterpret_cast<char*>(pack);
+  LoadDesc d{};
+  d.src = w_oihw; d.kind = PK_INIT; d.O = Cout; d.I = Cin; d.Op = Cout; d.Ip = Cin; d.numel = (long long)Cout * Cin * 9;
+  d.dst = 0; d.dst_t = -1; d.dst_f = -1;
+  InitDgradArgs a{};
+  a.g = g; a.w = reinterpret_cast<const float*>(blob); a.dx0 = d_x0; a.dx1 = d_x1; a.c0 = c0; a.c1 = c1;
+  a.B = batch; a.H = H; a.W = W; a.C0 = Cout;
+  hipStream_t s = hs(stream);
+  hipError_t e = launch_fill_zero(blob, llie_init_conv_pack_bytes(Cin, Cout), s);
+  if (e == hipSuccess) e = launch_load_one(dtype, d, blob, s);
+  if (e == hipSuccess) e = launch_init_conv_dgrad(dtype, a, s);
+  return kerr("init_conv_dgrad", e);
+}
 int llie_final_conv(int dtype, const void* in, const float* scale, const float* shift, const float* w_oihw, const float* bias, float* out,
                     int batch, int H, int W, int C, int Cout, int use_mfma, const llie_step_coef* coef, const float* sample, const float* noise,
                     float* prev, float* clamped, void* pack, int64_t pack_bytes, llie_stream stream) {

@@ -571,6 +571,15 @@ hipError_t launch_final_bwd_data(int dtype, const FinalBwdArgs& a, hipStream_t s
 //   fp32 NCHW planes ([B][c0][P] and optionally [B][c1][P]) -> NHWC T [B*P][32], zero beyond the real channels: the
 //   operand layout launch_wgrad wants (weight gradients of the output head and of the input conv)
 hipError_t launch_pack_planes(int dtype, const float* x0, const float* x1, int c0, int c1, void* out, int B, int P, hipStream_t s);
+//   input conv, data gradient: g = d(h0) NHWC [B][H][W][C0] T -> fp32 NCHW planes dx0 [B][c0][H][W] and dx1 [B][c1][H][W], the
+//   forward's two input halves; either may be null (not both; dx1 needs c1 > 0) and then costs neither stores nor arithmetic.
+//   Values are stored, one writer per element; C0 a multiple of 32, c0 + c1 <= 8, H and W multiples of 8, B <= 65535.
+struct InitDgradArgs {
+  const void* g; const float* w;  // w: the forward VALU kernel's fp32 table [(c0 + c1) * 9][C0]
+  float* dx0; float* dx1; int c0, c1;
+  int B, H, W, C0;
+};
+hipError_t launch_init_conv_dgrad(int dtype, const InitDgradArgs& a, hipStream_t s);
 
 // (8) linear attention backward.  qkv / dqkv NHWC [B][N][3*inner]; kv = forward partials [nsplit][B][heads][32][33].
 struct AttnBwdArgs {

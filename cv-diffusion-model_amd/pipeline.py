@@ -101,6 +101,9 @@ class LowLightDiffusion(nn.Module):
         are enabled `noise_pred` carries a grad_fn whose backward is the engine's reverse pass
         (llie_unet_backward): `loss.backward()` fills `.grad` of every parameter, so the reference trainer's
         step (trainer.py:269-338: AdamW, GradScaler, clip_grad_norm_, EMA) runs unchanged on top.
+        A `low_light` that requires a gradient receives one from the same backward pass
+        (llie_unet_backward_dx), so a trainable module may sit in front of the denoiser; the parameter gradients are the
+        same bits either way.
         With a `prediction_type="v_prediction"` scheduler the dict also holds the velocity `target`
         (lcm_scheduler.py:282-305; the reference never wires it into `compute_loss`).  A caller that forms the x0 term needs
         the noised input too: it is `scheduler.add_noise(normal_light, noise, timesteps)` of the returned draws.
@@ -264,7 +267,9 @@ class LowLightDiffusion(nn.Module):
         `x0_ssim_weight` / `x0_l1_weight` (extension): when either is non-zero, `x0_loss` of the predicted clean image against
         `normal_light` is added (the module docstring has the definition); with both 0 nothing changes.
         The loss and the x0 term run at the batch's own H x W: [B,3,H,W] of any shape llie_train_shape_ok accepts (frame-size
-        fine-tuning; image_size is one such shape and is what it was)."""
+        fine-tuning; image_size is one such shape and is what it was).
+        `loss.backward()` also fills the gradient of a `low_light` that requires one (forward's docstring): `compute_loss(frontend(raw),
+        normal)` trains `frontend` together with, or instead of, the denoiser."""
         _check_x0_weights(x0_ssim_weight, x0_l1_weight)
         out = self.forward(low_light, normal_light, frame=True)
         if use_velocity_target and "target" not in out:

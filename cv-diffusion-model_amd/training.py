@@ -326,10 +326,17 @@ class TrainStep:
     `x0_ssim_weight` / `x0_l1_weight` (>= 0): when either is non-zero, the x0 term of pipeline.py (SSIM / L1 of the predicted
     clean image against `normal_light`) is added to the loss, and one call of llie_x0_loss adds its gradient into d(loss)/d(eps)
     before the grad-scaler multiplication; with both 0 the step makes no such call and is unchanged bit for bit.
+    `cond_grad=True`: every call also leaves `step.cond_grad`, fp32 [B,3,H,W]: the gradient of the returned (unscaled) loss with
+    respect to `low_light`, from the same backward call (llie_unet_backward_dx), for a trainable module in front of the denoiser:
+    `low = frontend(raw); loss = step(low.detach(), normal); low.backward(step.cond_grad)`.  With a `grad_scaler` it is divided by
+    the device scale (one elementwise operation, no host read) before the optimiser updates that scale; on a step the scaler
+    skips, its values may be non-finite.  Only the condition half is exposed: with the x0 term on, x_t also enters the loss
+    directly.  It is this rank's gradient (never all-reduced).  With `cond_grad=False` the step is what it was, bit for bit.
     Returns the loss (device scalar, unscaled)."""
 
     def __init__(self, model, optimizer: FusedAdamW, loss_type: str = "mse", use_velocity_target: bool = False, group=None,
-                 grad_scaler: Optional[FusedGradScaler] = None, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0):
+                 grad_scaler: Optional[FusedGradScaler] = None, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0,
+                 cond_grad: bool = False):
         from .pipeline import _check_x0_weights
         if loss_type not in ("mse", "huber", "l1"):
             raise ValueError(f"Unknown loss type: {loss_type}")
@@ -344,6 +351,8 @@ class TrainStep:
             raise ValueError("use_velocity_target needs a scheduler with prediction_type='v_prediction'")
         self._flat = None
         self._ws = None
+        self._want_cond_grad = bool(cond_grad)
+        self.cond_grad: Optional[torch.Tensor] = None
 
     @torch.no_grad()
     def __call__(self, low_light: torch.Tensor, normal_light: torch.Tensor, timesteps: Optional[torch.Tensor] = None,
@@ -378,8 +387,15 @@ class TrainStep:
                                              self.x0_l1_weight, d_eps)  # adds d(term)/d(eps) into d_eps
             if self.grad_scaler is not None:
                 d_eps = d_eps * self.grad_scaler._device_scale(dev)
-            N.check(L.llie_unet_backward(h.h, d_eps.data_ptr(), self._flat.data_ptr(), b, self._ws.data_ptr(), nbytes, st),
-                    "EfficientUNet.backward")
+            if self._want_cond_grad:
+                dc = torch.empty_like(cond)
+                N.check(L.llie_unet_backward_dx(h.h, d_eps.data_ptr(), self._flat.data_ptr(), None, dc.data_ptr(), b, self._ws.data_ptr(),
+                                                nbytes, st), "EfficientUNet.backward")
+                # unscaled here, before step_flat below updates the device scale
+                self.cond_grad = dc / self.grad_scaler._device_scale(dev) if self.grad_scaler is not None else dc
+            else:
+                N.check(L.llie_unet_backward(h.h, d_eps.data_ptr(), self._flat.data_ptr(), b, self._ws.data_ptr(), nbytes, st),
+                        "EfficientUNet.backward")
         scale = 1.0
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
             dist.all_reduce(self._flat, group=self.group)  # one collective over all gradients; the average rides on grad_scale

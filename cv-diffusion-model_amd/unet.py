@@ -120,7 +120,8 @@ class _ModuleFn(torch.autograd.Function):
 
 class _UNetFn(torch.autograd.Function):
     """EfficientUNet.forward with autograd: the forward keeps its activations in a workspace owned by this
-    node, the backward is llie_unet_backward (parameter gradients only -- the network input is data)."""
+    node, the backward is llie_unet_backward -- or llie_unet_backward_dx when `latents` or `cond` needs a gradient: the
+    parameter gradients are the same bits either way, and only the input gradients that are needed are computed."""
 
     @staticmethod
     def forward(ctx, unet, latents, cond, t, *params):
@@ -134,7 +135,7 @@ class _UNetFn(torch.autograd.Function):
             h.unet_train_forward(latents.data_ptr(), cond.data_ptr(), t.data_ptr(), out.data_ptr(), b, hh, ww, ws.data_ptr(), nbytes,
                                  torch.cuda.current_stream(dev).cuda_stream)
         ctx.unet, ctx.h, ctx.ws, ctx.nbytes, ctx.batch = unet, h, ws, nbytes, b
-        ctx.keep = (latents, cond, t)  # the backward pass reads them again (input conv, time embedding)
+        ctx.keep = (latents.detach(), cond.detach(), t)  # the backward pass reads them again (input conv, time embedding)
         return out
 
     @staticmethod
@@ -142,11 +143,20 @@ class _UNetFn(torch.autograd.Function):
         unet, h, dev = ctx.unet, ctx.h, d_eps.device
         d_eps = d_eps.detach().float().contiguous()
         flat = torch.empty(h.grad_numel(), dtype=torch.float32, device=dev)
+        need_lat, need_cond = ctx.needs_input_grad[1:3]
+        d_lat = torch.empty_like(ctx.keep[0]) if need_lat else None
+        d_cond = torch.empty_like(ctx.keep[1]) if need_cond else None
         with torch.cuda.device(dev):
-            N.check(N.lib().llie_unet_backward(h.h, d_eps.data_ptr(), flat.data_ptr(), ctx.batch, ctx.ws.data_ptr(), ctx.nbytes,
-                                               torch.cuda.current_stream(dev).cuda_stream), "EfficientUNet.backward")
+            st = torch.cuda.current_stream(dev).cuda_stream
+            if need_lat or need_cond:
+                N.check(N.lib().llie_unet_backward_dx(h.h, d_eps.data_ptr(), flat.data_ptr(), d_lat.data_ptr() if need_lat else None,
+                                                      d_cond.data_ptr() if need_cond else None, ctx.batch, ctx.ws.data_ptr(), ctx.nbytes,
+                                                      st), "EfficientUNet.backward")
+            else:
+                N.check(N.lib().llie_unet_backward(h.h, d_eps.data_ptr(), flat.data_ptr(), ctx.batch, ctx.ws.data_ptr(), ctx.nbytes, st),
+                        "EfficientUNet.backward")
         ctx.ws = None
-        return (None, None, None, None) + _grad_views(flat, h, unet._param_list)
+        return (None, d_lat, d_cond, None) + _grad_views(flat, h, unet._param_list)
 
 
 class _NativeModule(nn.Module):
@@ -461,7 +471,11 @@ class EfficientUNet(_NativeModule):
         concat is never materialised.  `frame=True` (extension, keyword only, like enhance_frame beside enhance): the maps may
         have any H x W the frame rule accepts -- llie_train_shape_ok when the call records gradients, llie_frame_shape_ok
         otherwise (ValueError naming the rule); the module tree stays the one image_size fixed.  Without it a shape other than
-        image_size is refused, as the reference's call would fail."""
+        image_size is refused, as the reference's call would fail.
+        Gradients: with autograd on, the result carries a grad_fn when a parameter, `latents` or `cond` requires a gradient, and
+        backward() then fills the gradients of exactly those (d(latents), d(cond): llie_unet_backward_dx).  A frozen denoiser
+        (`requires_grad_(False)`) with an input that requires a gradient is such a call.  `uniform_t=True` and `out=` stay
+        gradient-free."""
         s = self.config.image_size
         b = latents.shape[0]
         if latents.dim() != 4 or tuple(cond.shape[2:]) != tuple(latents.shape[2:]):
@@ -474,14 +488,16 @@ class EfficientUNet(_NativeModule):
         if latents.shape[1] + cond.shape[1] != self.config.in_channels or latents.shape[1] != self.config.in_channels // 2:
             raise ValueError("channel split does not match in_channels")
         dev = latents.device
-        latents = latents.detach().float().contiguous()
-        cond = cond.detach().float().contiguous()
         t = timestep.to(device=dev, dtype=torch.long).contiguous()
         if t.numel() != b:
             raise ValueError("timestep must have one entry per batch row")
-        if self._wants_grad() and not uniform_t and out is None:
-            # training: activations are kept and the result carries a grad_fn (parameter gradients only)
-            return _UNetFn.apply(self, latents, cond, t, *[p for _, p in self._ordered_params()])
+        if self._wants_grad(latents, cond) and not uniform_t and out is None:
+            # training: activations are kept and the result carries a grad_fn -- to every parameter, and to `latents` / `cond`
+            # where they require a gradient (the conversions below stay on their autograd graph)
+            return _UNetFn.apply(self, latents.float().contiguous(), cond.float().contiguous(), t,
+                                 *[p for _, p in self._ordered_params()])
+        latents = latents.detach().float().contiguous()
+        cond = cond.detach().float().contiguous()
         h, ws, nbytes = self._prepare(b, dev, frame=None if (hh, ww) == (s, s) else (hh, ww))
         if out is None:
             out = torch.empty(b, self.config.out_channels, hh, ww, dtype=torch.float32, device=dev)

@@ -191,7 +191,14 @@ int llie_module_forward(llie_ctx* ctx, const float* x, const float* temb, float*
  *   llie_unet_train_forward_hw: llie_unet_train_forward on fp32 NCHW [B,3,H,W]; llie_unet_train_forward is this entry at
  *       H = W = image_size.  The tape records (H, W): llie_unet_backward takes the shape from it (d_eps [B,3,H,W]).
  * The weight-gradient GEMM splits its rows freely when H or W is off the multiples of 64, and by the rule of the 64-grid
- * otherwise: a rule on the frame alone, never on the batch. */
+ * otherwise: a rule on the frame alone, never on the batch.
+ *   llie_unet_backward_dx:    llie_unet_backward plus the gradients of the network input: d_latents fp32 NCHW [B][in_channels / 2][H][W]
+ *       and d_cond [B][in_channels - in_channels / 2][H][W] at the tape's (H, W), the two halves llie_unet_train_forward read.  Each
+ *       may be NULL and then costs nothing; with both NULL the call is llie_unet_backward, launch for launch and bit for bit
+ *       (llie_unet_backward is this call with two NULLs).  They are caller buffers: the workspace plan does not grow.  Values are
+ *       stored, not accumulated, by one kernel (the transpose of init_conv over d(h0), fp32 accumulation in a fixed order): bitwise
+ *       reproducible, the same bits with and without the backward side stream, an image's rows the same alone or in a batch, and
+ *       the parameter gradients are the bits llie_unet_backward gives.  `grads` stays required; same errors as llie_unet_backward. */
 int llie_train_shape_ok(const llie_ctx* ctx, int batch, int height, int width);
 int llie_unet_train_forward_hw(llie_ctx* ctx, const float* latents, const float* cond, const int64_t* timesteps, float* eps,
                                int batch, int height, int width, void* workspace, int64_t workspace_bytes, llie_stream stream);
@@ -202,6 +209,8 @@ int llie_unet_train_forward(llie_ctx* ctx, const float* latents, const float* co
                             int batch, void* workspace, int64_t workspace_bytes, llie_stream stream);
 int llie_unet_backward(llie_ctx* ctx, const float* d_eps, float* grads, int batch, void* workspace, int64_t workspace_bytes,
                        llie_stream stream);
+int llie_unet_backward_dx(llie_ctx* ctx, const float* d_eps, float* grads, float* d_latents, float* d_cond, int batch,
+                          void* workspace, int64_t workspace_bytes, llie_stream stream);
 int llie_module_backward(llie_ctx* ctx, const float* x, const float* temb, const float* dy, float* dx, float* dtemb,
                          float* grads, int batch, int H, int W, void* workspace, int64_t workspace_bytes, llie_stream stream);
 
@@ -587,6 +596,15 @@ int llie_film(const float* silu_temb, const float* wf, const float* bf, float* f
  *   Cout) bytes, 16-byte aligned) and repacks into it as llie_load_param does.  use_mfma 0: the VALU kernel (any dtype; fp32 operands);
  *   1: the MFMA kernel of the 2-byte engines (inputs and weights rounded to the compute type).  Refused: H or W not a multiple of 8,
  *   Cout not a multiple of 32, batch > 65535, use_mfma with LLIE_F32, a pack that is short or misaligned, NULL tensors.
+ * llie_init_conv_dgrad: the data gradient of init_conv, as llie_unet_backward_dx launches it: g NHWC [batch][H][W][Cout] of the
+ *   compute type (the gradient of init_conv's output) -> d_x0 fp32 NCHW [batch][c0][H][W] and d_x1 [batch][c1][H][W], the gradients
+ *   of llie_init_conv's two halves: d_x[ci][y][x] = sum over ky, kx, co of g[y + 1 - ky][x + 1 - kx][co] w[co][ci][ky][kx], terms
+ *   outside the map zero.  Either output may be NULL (not both; d_x1 only with c1 > 0): its channels are neither computed nor
+ *   stored.  Values are stored, not accumulated; fp32 accumulation in an order that depends on Cout alone.  w_oihw fp32 [Cout][c0 +
+ *   c1][3][3]: the call zero-fills `pack` (llie_init_conv_pack_bytes(c0 + c1, Cout) bytes, 16-byte aligned) and repacks the fp32
+ *   table of the forward's VALU kernel into it, which is what the kernel reads.  Refused: a dtype outside 0..2, NULL g / w_oihw /
+ *   pack, c0 < 1, c1 < 0, c0 + c1 > 8, H or W not a multiple of 8, batch > 65535, Cout not a positive multiple of 32, a pack that
+ *   is short or misaligned.
  * llie_final_conv: the output head (:528-530,600-602): out fp32 NCHW [batch][Cout][H][W] = conv3x3(silu(in * scale + shift)) + bias,
  *   zero padding after the activation; in NHWC [batch][H][W][C] of the compute type, C a multiple of 32, scale / shift fp32
  *   [batch][C], w_oihw fp32 [Cout][C][3][3], 1 <= Cout <= 4, bias fp32 [Cout]; pack: llie_final_conv_pack_bytes(C) bytes, as above.
@@ -608,6 +626,8 @@ int64_t llie_init_conv_pack_bytes(int Cin, int Cout);
 int llie_init_conv_tiles(int H, int W, int mfma);
 int llie_init_conv(int dtype, const float* x0, int c0, const float* x1, int c1, const float* w_oihw, const float* bias, void* out, float* stats,
                    int batch, int H, int W, int Cout, int use_mfma, void* pack, int64_t pack_bytes, llie_stream stream);
+int llie_init_conv_dgrad(int dtype, const void* g, int Cout, const float* w_oihw, float* d_x0, int c0, float* d_x1, int c1, int batch,
+                         int H, int W, void* pack, int64_t pack_bytes, llie_stream stream);
 int64_t llie_final_conv_pack_bytes(int C);
 int llie_final_conv(int dtype, const void* in, const float* scale, const float* shift, const float* w_oihw, const float* bias, float* out,
                     int batch, int H, int W, int C, int Cout, int use_mfma, const llie_step_coef* coef, const float* sample, const float* noise,
