@@ -232,6 +232,7 @@ struct llie_ctx {
   uint64_t graph_clock = 0;
   std::map<std::string, GraphEntry> graphs;
   std::map<std::tuple<int, int, int, int>, size_t> zneed;  // (batch, height, width, knob epoch) -> bytes of zero-initialised totals one forward takes (Run::zbegin)
+  std::map<std::tuple<int, int, int, int>, size_t> qplan;  // same key -> the forward's plan with per-sample timesteps, which every workspace query of a UNet handle is built on (forward.cpp: query_plan)
   hipStream_t cap_stream = nullptr;  // side stream used only to record captures (the legacy null stream cannot capture)
   // backward pass: weight-gradient kernels run on this stream next to the activation-gradient chain (Back::fork/join)
   hipStream_t side_stream = nullptr;
@@ -393,8 +394,13 @@ inline StepCoef step_coef(const llie_step_coef& k) {
   return StepCoef{k.sqrt_alpha_t, k.sqrt_beta_t, k.sqrt_alpha_prev, k.sqrt_beta_prev, k.is_last, k.v_prediction, k.clamp_x0, k.sampler};
 }
 inline bool step_coef_ok(const llie_step_coef& k) { return k.sampler == 0 || (k.sampler == 1 && !k.clamp_x0); }
+// `reserve`: bytes the caller's workspace query counts beyond the forward's plan, added to the plan in the capacity check.  The
+// loop keeps its images in front of the slice it passes and gives 0; the public forward gives loop_image_bytes, so that it refuses
+// exactly what is smaller than llie_workspace_bytes / llie_frame_workspace_bytes answered
 int unet_forward_impl(llie_ctx* c, const float* lat, const float* cond, const int64_t* t, int uniform_t, float* eps,
-                      const FusedStep* fs, int batch, int H, int W, void* ws, int64_t ws_bytes, llie_stream stream);
+                      const FusedStep* fs, int batch, int H, int W, void* ws, int64_t ws_bytes, llie_stream stream, size_t reserve = 0);
+// the latents ping-pong and eps images of the loop, which every workspace query of a UNet handle counts in front of the plan
+inline size_t loop_image_bytes(int batch, int H, int W) { return 3 * align_up((size_t)batch * 3 * H * W * 4, 256); }
 // forward.cpp: the frame rule of llie_frame_shape_ok, and the workspace of `max_steps` steps of the loop at H x W without that
 // check (0: plain launches, no staging area) -- the entry points at image_size go through it unchecked, as they always did
 int frame_shape_ok(const llie_ctx* c, int batch, int H, int W);

@@ -640,12 +640,26 @@ int llie::run_module(Exec x, Tape* tape, const float* in, const float* temb, flo
   return r.rc();
 }
 
+// The forward's plan as every workspace query of a UNet handle counts it: per-sample timesteps.  One dry run per batch, frame
+// and knob epoch (the key of llie_ctx::zneed, for the same reason: the knobs bake kernel choices into the plan)
+static size_t query_plan(llie_ctx* c, int batch, int H, int W) {
+  const auto key = std::make_tuple(batch, H, W, g_knobs.epoch);
+  auto it = c->qplan.find(key);
+  if (it == c->qplan.end())
+    it = c->qplan.emplace(key, Run::plan(c, batch, [&](Run& d) { d.unet(nullptr, nullptr, nullptr, 0, nullptr, H, W); })).first;
+  return it->second;
+}
+
 int llie::unet_forward_impl(llie_ctx* c, const float* lat, const float* cond, const int64_t* t, int uniform_t, float* eps,
-                            const FusedStep* fs, int batch, int H, int W, void* ws, int64_t ws_bytes, llie_stream stream) {
+                            const FusedStep* fs, int batch, int H, int W, void* ws, int64_t ws_bytes, llie_stream stream, size_t reserve) {
   if (!c || !lat || !cond || !t || (!eps && !fs) || !ws || batch <= 0 || c->cfg.kind != LLIE_UNET) return LLIE_ERR_ARG;
   int rc = check_ready(c);
   if (rc) return rc;
-  rc = fits(Run::plan(c, batch, [&](Run& d) { d.unet(nullptr, nullptr, nullptr, uniform_t, nullptr, H, W); }), ws_bytes);
+  // Too small is what is smaller than the queries answered, and they plan per-sample timesteps: a forward with equal timesteps
+  // (one row of time tables) would run in a few bytes less, but no query says how many, so it is held to the same figure
+  size_t need = query_plan(c, batch, H, W);
+  if (uniform_t) need = std::max(need, Run::plan(c, batch, [&](Run& d) { d.unet(nullptr, nullptr, nullptr, uniform_t, nullptr, H, W); }));
+  rc = fits(need + reserve, ws_bytes);
   if (rc) return rc;
   Arena ar((size_t)ws_bytes);
   Run r{Exec::live(c, &ar, stream, ws, batch)};
@@ -685,9 +699,9 @@ int llie::frame_shape_ok(const llie_ctx* c, int batch, int H, int W) {
 // one forward's plan + the latents ping-pong and eps buffers of the loop; max_steps > 0: + the staging area of its hipGraph path
 // (inputs / outputs of up to `max_steps` steps with intermediates and noise predictions)
 int64_t llie::frame_workspace(llie_ctx* c, int batch, int H, int W, int max_steps) {
-  const size_t core = Run::plan(c, batch, [&](Run& d) { d.unet(nullptr, nullptr, nullptr, 0, nullptr, H, W); });
+  const size_t core = query_plan(c, batch, H, W);
   const size_t img = align_up((size_t)batch * 3 * H * W * 4, 256);
-  size_t n = core + 3 * img;
+  size_t n = core + loop_image_bytes(batch, H, W);
   if (max_steps > 0) n += (2 + 3 * (size_t)max_steps) * img + align_up((size_t)max_steps * batch * 8, 256);
   return (int64_t)n;
 }
@@ -724,14 +738,16 @@ int64_t llie_frame_workspace_bytes(llie_ctx* c, int batch, int height, int width
 int llie_unet_forward(llie_ctx* c, const float* lat, const float* cond, const int64_t* t, int uniform_t, float* eps,
                       int batch, void* ws, int64_t ws_bytes, llie_stream stream) {
   if (!eps || !c) return LLIE_ERR_ARG;
-  return unet_forward_impl(c, lat, cond, t, uniform_t, eps, nullptr, batch, c->cfg.image_size, c->cfg.image_size, ws, ws_bytes, stream);
+  const int S = c->cfg.image_size;
+  return unet_forward_impl(c, lat, cond, t, uniform_t, eps, nullptr, batch, S, S, ws, ws_bytes, stream, loop_image_bytes(batch, S, S));
 }
 
 int llie_unet_forward_hw(llie_ctx* c, const float* lat, const float* cond, const int64_t* t, int uniform_t, float* eps,
                          int batch, int height, int width, void* ws, int64_t ws_bytes, llie_stream stream) {
   if (!eps) return LLIE_ERR_ARG;
   const int rc = frame_shape_ok(c, batch, height, width);
-  return rc ? rc : unet_forward_impl(c, lat, cond, t, uniform_t, eps, nullptr, batch, height, width, ws, ws_bytes, stream);
+  return rc ? rc : unet_forward_impl(c, lat, cond, t, uniform_t, eps, nullptr, batch, height, width, ws, ws_bytes, stream,
+                                     loop_image_bytes(batch, height, width));
 }
 
 int llie_module_forward(llie_ctx* c, const float* x, const float* temb, float* y, int batch, int H, int W, void* ws,

@@ -124,7 +124,9 @@ int llie_refresh_params(llie_ctx* ctx, const float* const* srcs, int n, llie_str
 int llie_params_loaded(const llie_ctx* ctx); /* 1 when every key has been loaded */
 
 /* Bytes of scratch the forward needs for a batch (UNET: spatial size = image_size; single
- * operators: H x W given). */
+ * operators: H x W given).  For a UNET handle the figure includes the three images the loop of llie_enhance keeps in front of the
+ * forward's own plan, and llie_unet_forward / llie_unet_forward_hw ask for all of it: a workspace smaller than this query (or
+ * llie_frame_workspace_bytes with max_steps = 0) answered returns LLIE_ERR_WORKSPACE before anything is launched. */
 int64_t llie_workspace_bytes(llie_ctx* ctx, int batch, int height, int width);
 /* Workspace for llie_enhance including the staging area its hipGraph path needs (inputs / outputs of
  * up to `max_steps` steps).  With only llie_workspace_bytes() the loop runs as plain launches. */
