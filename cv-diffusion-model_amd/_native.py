@@ -303,6 +303,7 @@ def lib() -> C.CDLL:
     L.llie_graph_cache_entries.restype = C.c_int
     L.llie_debug_gemm_stamps.argtypes = [C.POINTER(C.c_double)]
     L.llie_debug_conv_stamps.argtypes = [C.POINTER(C.c_double)]
+    L.llie_debug_pwx_stamps.argtypes = [C.POINTER(C.c_double)]
     L.llie_grad_numel.argtypes = [vp]
     L.llie_grad_numel.restype = i64
     L.llie_param_grad_offset.argtypes = [vp, ci]

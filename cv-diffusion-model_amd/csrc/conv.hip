@@ -781,20 +781,7 @@ __global__ void __launch_bounds__(WM* WN * 64) conv3x3_kernel(const Conv3Args a)
   }
 }
 
-static int g_conv_stamp = 0;
-static unsigned long long* g_conv_stamps = nullptr;
-static size_t g_conv_stamp_n = 0;
-void conv3x3_stamp(int v) { g_conv_stamp = v; }
-hipError_t conv3x3_stamp_fetch(double* out8) {  // mean cycles per wave of the last stamped launch (kConvStamps slots), then the wave count
-  if (!g_conv_stamps || !g_conv_stamp_n) return hipErrorInvalidValue;
-  std::vector<unsigned long long> h(g_conv_stamp_n);
-  if (hipError_t e = hipMemcpy(h.data(), g_conv_stamps, h.size() * 8, hipMemcpyDeviceToHost); e != hipSuccess) return e;
-  for (int i = 0; i < kConvStamps; ++i) out8[i] = 0.0;
-  for (size_t i = 0; i < h.size(); ++i) out8[i % kConvStamps] += (double)h[i];
-  for (int i = 0; i < kConvStamps; ++i) out8[i] /= (double)(h.size() / kConvStamps);
-  out8[kConvStamps] = (double)(h.size() / kConvStamps);
-  return hipSuccess;
-}
+StampSink g_conv_stamps{kConvStamps, 0};  // cycles per wave, the slots listed at STAMP
 
 static int conv_tw(int Wo) { return (Wo % 16 == 0) ? 16 : 8; }
 // the tile width launch_conv_t takes: ragged maps (Ho % 8 or Wo % 8) run 8-wide tiles whatever Wo is -- a 9 x 16 map is four tiles
@@ -821,17 +808,15 @@ static hipError_t launch_conv_cfg(const Conv3Args& a, hipStream_t s) {
                                   std::to_string(WN) + ">";
   note_kernel(name.c_str());
   if constexpr (MODE == 1 && TW == 16 && !RAGGED && std::is_same<T, half_t>::value) {
-    if (g_conv_stamp) {  // diagnostic build with in-kernel cycle stamps
-      const size_t n = (size_t)grid * (NT / 64) * kConvStamps;
-      if (n > g_conv_stamp_n || !g_conv_stamps) {
-        if (g_conv_stamps) (void)hipFree(g_conv_stamps);
-        if (hipError_t e = hipMalloc(reinterpret_cast<void**>(&g_conv_stamps), n * 8); e != hipSuccess) return e;
-      }
-      g_conv_stamp_n = n;
+    if (g_knobs.conv_stamp) {  // diagnostic build with in-kernel cycle stamps
       Conv3Args b = a;
-      b.stamps = g_conv_stamps;
-      if (hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_kernel<T, MODE, TW, BN, WM, WN, RAGGED, true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); e != hipSuccess) return e;
+      if (hipError_t e = g_conv_stamps.arm((size_t)grid * (NT / 64), &b.stamps); e != hipSuccess) return e;
+      static std::atomic<uint64_t> stamp_attr_done{0};
+      if (lds > 48 * 1024) {
+        if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&conv3x3_kernel<T, MODE, TW, BN, WM, WN, RAGGED, true>), (int)lds, stamp_attr_done);
+            e != hipSuccess)
+          return e;
+      }
       hipLaunchKernelGGL((conv3x3_kernel<T, MODE, TW, BN, WM, WN, RAGGED, true>), dim3(grid), dim3(NT), lds, s, b);
       return hipGetLastError();
     }

@@ -256,26 +256,7 @@ struct llie_ctx {
 namespace llie {
 
 // ---------------------------------------------------------------------------------------------
-// Tuning knobs (tune.cpp: defaults, environment variables and the llie_tune table that sets them).  Process-global.
-// The reasons behind each default are in tune.cpp: knob_defaults.
-struct Knobs {
-  int use_irbx;       // "irbx": recompute form of the inverted-residual block (irbx.hip) wherever irbx_supported()
-  int irbx_project;   // "irbx_project": recompute blocks without h2 (expand_pool + expand_dw_project): 1 = every shape irbx_project_supported
-                      // names, 2 = its identity-residual shapes only, 0 = none (expand_dw + project GEMM)
-  int wide_project;   // "wide_project": the wide decoder blocks wide_project_supported names without h2 (dwconv3x3_pool + dwconv3x3_project)
-  int wide_gram;      // "wide_gram" (1 = maps of at least kWideGramMinPixels pixels, 2 = every map): the 192 -> 64 wide block takes norm2's tables from the Gram of its input (gram.hip), pw_expand stores the
-                      // activated h1 and adds the SE pool totals: no pool pass (0 = dwconv3x3_pool from the stored h1)
-  int gram;           // "gram": norm2 statistics of the recompute form from the Gram matrix (gram.hip); 0 = expand_stats; 2 = at every size
-  int nt_min_mb;      // "nt_min_mb": tensors of at least this many MiB are stored non-temporally by the producers in nt_mask
-  int nt_mask;        // "nt_mask": 1 expand_dw, 2 pw_expand, 4 dwconv3x3, 8 project / attention GEMMs, 16 dense 3x3 convs
-  int se_mfma;        // "se_mfma": SE MLP of the wide blocks as two MFMA launches; 0 = the row-parallel pair
-  int bwd_async;      // "bwd_async": weight-gradient kernels of the backward pass on a side stream
-  int upconv_fold;    // "upconv_fold": up-sampling convs from folded weights wherever upconv_fold_supported(); 0 = blend in the kernel
-  int enhance_split;  // "enhance_split": concurrent branches of the captured enhance graph (< 2: a single chain)
-  int graph_max_steps;  // "graph_max_steps": loops of more steps than this run as plain launches, never captured
-  int epoch;          // llie_tune calls so far: keys the graph cache and the zero-region sizes, which bake kernel choices in
-};
-extern Knobs g_knobs;
+// (the tuning knobs the rules below read: kernels.h, Knobs)
 constexpr int kGraphMaxSteps = 20;  // default of Knobs::graph_max_steps: capture pays at 20 steps and loses at 50
 
 // The launch sequence of an inverted-residual block (forward.cpp: Run::irb; the byte model, llie_path_bytes, asks too):
@@ -318,7 +299,7 @@ inline IrbPath irb_path(int dt, const IrbW& w, int c0, int H, int W, bool traini
       wide_project_supported(dt, w.cin, c0, w.hid, w.cout, w.skip, w.hid != w.hid_r || w.cin != w.cin_r || w.cout != w.cout_r, H, W)) {
     p.form = kIrbWide;
     // (the activating expand is pw_expand's: knob "pwx" on, input segments of whole 64-channel chunks)
-    p.wgram = g_knobs.wide_gram && (H * W >= kWideGramMinPixels || g_knobs.wide_gram > 1) && w.has_mg && pw_expand_enabled() && c0 % 64 == 0 &&
+    p.wgram = g_knobs.wide_gram && (H * W >= kWideGramMinPixels || g_knobs.wide_gram > 1) && w.has_mg && g_knobs.pwx && c0 % 64 == 0 &&
               (w.cin - c0) % 64 == 0 && gram_wide_supported(dt, w.cin, c0, w.hid, H * W);
     return p;
   }

@@ -355,29 +355,7 @@ __global__ void __launch_bounds__(WM* WN * 64) pw_gemm_kernel(const GemmArgs g) 
   }
 }
 
-static int g_gemm_stamp = 0;
-static unsigned long long* g_gemm_stamps = nullptr;
-static size_t g_gemm_stamp_waves = 0;
-constexpr size_t kStampWaves = 1u << 20;
-void pw_gemm_stamp(int v) { g_gemm_stamp = v; }
-static hipError_t stamp_buffer(size_t waves) {
-  if (waves > kStampWaves) return hipErrorInvalidValue;
-  if (!g_gemm_stamps && hipMalloc(reinterpret_cast<void**>(&g_gemm_stamps), kStampWaves * 2 * sizeof(unsigned long long)) != hipSuccess) return hipErrorOutOfMemory;
-  g_gemm_stamp_waves = waves;
-  return hipSuccess;
-}
-hipError_t pw_gemm_stamp_fetch(double* out3) {  // mean s_memtime ticks per wave of the last stamped launch: {K loop, epilogue}, and the wave count
-  if (!g_gemm_stamps || !g_gemm_stamp_waves) return hipErrorInvalidValue;
-  std::vector<unsigned long long> h(g_gemm_stamp_waves * 2);
-  hipError_t e = hipMemcpy(h.data(), g_gemm_stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return e;
-  double a = 0, b = 0;
-  for (size_t i = 0; i < g_gemm_stamp_waves; ++i) { a += (double)h[2 * i]; b += (double)h[2 * i + 1]; }
-  out3[0] = a / (double)g_gemm_stamp_waves;
-  out3[1] = b / (double)g_gemm_stamp_waves;
-  out3[2] = (double)g_gemm_stamp_waves;
-  return hipSuccess;
-}
+StampSink g_gemm_stamps{2, 1u << 20};  // s_memtime ticks per wave: {K loop, epilogue}
 
 template <typename T, int BM, int BN, int WM, int WN, int BK, bool RAGGED = false, bool KTAIL = false>
 static hipError_t launch_cfg(const GemmArgs& a, hipStream_t s) {
@@ -394,12 +372,15 @@ static hipError_t launch_cfg(const GemmArgs& a, hipStream_t s) {
   }
   const unsigned grid = (unsigned)((a.M / a.P) * ((a.P + BM - 1) / BM) * (a.N / BN));  // == (M / BM) * (N / BN) unless RAGGED
   if constexpr (sizeof(T) == 2 && BM == 128 && !KTAIL) {
-    if (g_gemm_stamp) {
-      if (hipError_t e = stamp_buffer((size_t)grid * (NT / 64)); e != hipSuccess) return e;
+    if (g_knobs.gemm_stamp) {
       GemmArgs b = a;
-      b.stamps = g_gemm_stamps;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_gemm_kernel<T, BM, BN, WM, WN, BK, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (hipError_t e = g_gemm_stamps.arm((size_t)grid * (NT / 64), &b.stamps); e != hipSuccess) return e;
+      static std::atomic<uint64_t> stamp_attr_done{0};
+      if (lds > 48 * 1024) {
+        if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&pw_gemm_kernel<T, BM, BN, WM, WN, BK, true>), (int)lds, stamp_attr_done);
+            e != hipSuccess)
+          return e;
+      }
       hipLaunchKernelGGL((pw_gemm_kernel<T, BM, BN, WM, WN, BK, true>), dim3(grid), dim3(NT), lds, s, b);
       return hipGetLastError();
     }
@@ -415,9 +396,6 @@ static hipError_t launch_cfg(const GemmArgs& a, hipStream_t s) {
 int pw_gemm_tile_rows(int P) { return (P % 128 == 0) ? 128 : 64; }
 int pw_gemm_ntiles(int P) { const int bm = pw_gemm_tile_rows(P); return (P + bm - 1) / bm; }  // statistics partials per image
 
-// knob "gemm_bk" (0 = automatic)
-static int g_force_bk = 0;
-void pw_gemm_force_bk(int bk) { g_force_bk = bk; }
 constexpr long kBk128MaxGrid = 1024;  // 128-wide K chunks for launches of up to this many workgroups
 
 template <typename T>
@@ -429,7 +407,7 @@ static hipError_t launch_t(const GemmArgs& a, hipStream_t s) {
   // batch differ from its halves in the last bits and were removed.
   bool k64 = sizeof(T) == 2;  // BK = 64 needs every K segment to be a multiple of 64 (2-byte T only)
   for (int i = 0; i < a.nseg; ++i) k64 = k64 && (a.seg[i].ch % 64 == 0);
-  if (g_force_bk == 32) k64 = false;
+  if (g_knobs.gemm_bk == 32) k64 = false;
   if constexpr (sizeof(T) == 2) {
     // small grids (about as many workgroups as the chip holds at once): a workgroup's time is chunks x memory latency, so
     // twice the chunk: -10...-16 % on the long-K project layers of the low resolutions (and at B = 1), +10 % on large grids.
@@ -444,7 +422,7 @@ static hipError_t launch_t(const GemmArgs& a, hipStream_t s) {
     if constexpr (sizeof(T) == 2) {
       // some segment has 64 n + 32 channels (the 96 -> 32 and 32 -> 64 blocks: K = 480, 160; `base`'s 48 / 96 / 144-channel shapes):
       // 64-wide chunks with half-empty segment tails (KTAIL) instead of 32-wide ones
-      if (!k64 && g_force_bk != 32 && a.K > 64) {
+      if (!k64 && g_knobs.gemm_bk != 32 && a.K > 64) {
         if (BN == 128) return launch_cfg<T, 128, 128, 2, 2, 64, false, true>(a, s);
         if (BN == 64) return launch_cfg<T, 128, 64, 2, 2, 64, false, true>(a, s);
         return launch_cfg<T, 128, 32, 4, 1, 64, false, true>(a, s);

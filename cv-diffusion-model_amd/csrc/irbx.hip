@@ -1259,41 +1259,7 @@ int irbx_stats_rows(int P) {
   return rp;
 }
 
-static int g_irbx_dbuf = 0, g_irbx_stamp = 0;
-static int g_irbx_grid[3] = {0, 0, 0};  // per input width (32, 64, 96 channels)
-void irbx_grid(int ks, int v) {
-  for (int i = 0; i < 3; ++i)
-    if (ks == 0 || ks == 2 * (i + 1)) g_irbx_grid[i] = v;
-}
-static unsigned long long* g_irbx_dbg = nullptr;
-static size_t g_irbx_dbg_n = 0;  // entries of the last stamped launch
-void irbx_stamp(int v) { g_irbx_stamp = v; }
-// mean cycles per wave of the last stamped launch: out[0 .. kXStamps) = the slots listed at STAMP, out[kXStamps] = waves averaged
-hipError_t irbx_stamp_fetch(double* out) {
-  if (!g_irbx_dbg || !g_irbx_dbg_n) return hipErrorInvalidValue;
-  std::vector<unsigned long long> h(g_irbx_dbg_n);
-  hipError_t e = hipMemcpy(h.data(), g_irbx_dbg, g_irbx_dbg_n * 8, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return e;
-  for (int i = 0; i < kXStamps; ++i) out[i] = 0.0;
-  for (size_t i = 0; i < g_irbx_dbg_n; ++i) out[i % kXStamps] += (double)h[i];
-  for (int i = 0; i < kXStamps; ++i) out[i] /= (double)(g_irbx_dbg_n / kXStamps);
-  out[kXStamps] = (double)(g_irbx_dbg_n / kXStamps);
-  return hipSuccess;
-}
-void irbx_tune(int dbuf) { if (dbuf >= 0) g_irbx_dbuf = dbuf; }
-// the stamp buffer of a diagnostic launch of `waves` waves
-static hipError_t irbx_dbg_buffer(size_t waves, IrbxArgs& a) {
-  const size_t n = waves * kXStamps;
-  if (n > g_irbx_dbg_n || !g_irbx_dbg) {
-    if (g_irbx_dbg) (void)hipFree(g_irbx_dbg);
-    g_irbx_dbg = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&g_irbx_dbg), n * 8);
-    if (e != hipSuccess) return e;
-  }
-  g_irbx_dbg_n = n;
-  a.dbg = g_irbx_dbg;
-  return hipSuccess;
-}
+StampSink g_irbx_stamps{kXStamps, 0};  // cycles per wave, the slots listed at STAMP; shared by the three stamped kernels
 
 // expand_stats (POOL = false) and expand_pool: the same scan of x, one workgroup per irbx_stats_rows(P) pixels of an image
 template <typename T, int KS, int NBW, bool POOL>
@@ -1303,9 +1269,9 @@ static hipError_t launch_scan_cfg(const IrbxArgs& a, hipStream_t s) {
                                   std::to_string(KS) + ", " + std::to_string(NBW) + ">";
   note_kernel(name.c_str());
   if constexpr (POOL && std::is_same<T, half_t>::value) {
-    if (g_irbx_stamp == 2) {  // diagnostic build: in-kernel cycle stamps
+    if (g_knobs.irbx_stamp == 2) {  // diagnostic build: in-kernel cycle stamps
       IrbxArgs b = a;
-      if (hipError_t e = irbx_dbg_buffer((size_t)(P / RP) * a.B * 4, b); e != hipSuccess) return e;
+      if (hipError_t e = g_irbx_stamps.arm((size_t)(P / RP) * a.B * 4, &b.dbg); e != hipSuccess) return e;
       hipLaunchKernelGGL((expand_pool_stamp_kernel<KS, NBW>), dim3(P / RP, 1, a.B), dim3(256), 0, s, b, RP);
       return hipGetLastError();
     }
@@ -1352,7 +1318,7 @@ IrbxPlan irbx_plan(int Cin, int B, int H, int W, bool project) {
     while (p.cpw > 1 && (long)(ntiles / p.tpw) * B * (nchunks / p.cpw) < 1024 && p.cpw % 2 == 0) p.cpw >>= 1;
   p.gx = ntiles / p.tpw;
   p.gy = nchunks / p.cpw;
-  const int want = project ? 0 : g_irbx_grid[Cin / 32 - 1];
+  const int want = project ? 0 : g_knobs.irbx_grid[Cin / 32 - 1];
   if (want > 0) {
     const int gx = want / (B * p.gy);
     p.gx = gx < 1 ? 1 : (gx > ntiles ? ntiles : gx);
@@ -1379,9 +1345,9 @@ static hipError_t launch_dw_cfg(const IrbxArgs& a, hipStream_t s) {
   note_kernel(name.c_str());
   const dim3 grid(plan.gx, plan.gy, a.B);
   if constexpr (std::is_same<T, half_t>::value && !DBUF) {
-    if (g_irbx_stamp == 1) {  // diagnostic build: in-kernel cycle stamps (fp16 only)
+    if (g_knobs.irbx_stamp == 1) {  // diagnostic build: in-kernel cycle stamps (fp16 only)
       IrbxArgs b = a;
-      if (hipError_t e = irbx_dbg_buffer((size_t)grid.x * grid.y * grid.z * 4, b); e != hipSuccess) return e;
+      if (hipError_t e = g_irbx_stamps.arm((size_t)grid.x * grid.y * grid.z * 4, &b.dbg); e != hipSuccess) return e;
       return launch_dw_one<T, KS, DBUF, true, false>(b, grid, lds, tpw, cpw, s);
     }
   }
@@ -1396,7 +1362,7 @@ static hipError_t launch_dw_t(const IrbxArgs& a, hipStream_t s) {
   // llie_tune("irbx_dbuf", 1): double-buffered h1 tile for the 32-channel inputs (one barrier per chunk, 76 KB of LDS = two
   // workgroups per CU).  The single-buffered kernel (49 KB, three workgroups per CU) is the default: 1 % faster end to end
   switch (Cin) {
-    case 32: return g_irbx_dbuf ? launch_dw_cfg<T, 2, true>(a, s) : launch_dw_cfg<T, 2, false>(a, s);
+    case 32: return g_knobs.irbx_dbuf ? launch_dw_cfg<T, 2, true>(a, s) : launch_dw_cfg<T, 2, false>(a, s);
     case 64: return launch_dw_cfg<T, 4, false>(a, s);
     case 96: return launch_dw_cfg<T, 6, false>(a, s);
   }
@@ -1411,9 +1377,9 @@ static hipError_t launch_project_cfg(const IrbxArgs& a, hipStream_t s) {
                                   (PCO == 16 * KS ? std::string() : ", " + std::to_string(PCO)) + ">";
   note_kernel(name.c_str());
   if constexpr (std::is_same<T, half_t>::value) {
-    if (g_irbx_stamp == 3) {  // diagnostic build: in-kernel cycle stamps (fp16 only)
+    if (g_knobs.irbx_stamp == 3) {  // diagnostic build: in-kernel cycle stamps (fp16 only)
       IrbxArgs b = a;
-      if (hipError_t e = irbx_dbg_buffer((size_t)plan.gx * a.B * 4, b); e != hipSuccess) return e;
+      if (hipError_t e = g_irbx_stamps.arm((size_t)plan.gx * plan.gy * a.B * 4, &b.dbg); e != hipSuccess) return e;
       static std::atomic<uint64_t> stamp_attr_done{0};
       if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&expand_dw_project_stamp_kernel<KS, PCO>), 128 * 1024, stamp_attr_done); e != hipSuccess)
         return e;

@@ -16,6 +16,50 @@ enum Act : int { ACT_NONE = 0, ACT_RELU6 = 1, ACT_SILU = 2, ACT_RELU6_S6 = 3 };
 void note_kernel(const char* name);
 const char* last_kernel();
 
+// ---------------------------------------------------------------------------------------------
+// Tuning knobs (tune.cpp: the table of names, defaults, environment variables and value rules behind llie_tune).  Process-global;
+// the engine and the launchers read the fields directly.  The reasons behind each default are in tune.cpp, next to its row.
+struct Knobs {
+  int use_irbx;       // "irbx": recompute form of the inverted-residual block (irbx.hip) wherever irbx_supported()
+  int irbx_project;   // "irbx_project": recompute blocks without h2 (expand_pool + expand_dw_project): 1 = every shape irbx_project_supported
+                      // names, 2 = its identity-residual shapes only, 0 = none (expand_dw + project GEMM)
+  int wide_project;   // "wide_project": the wide decoder blocks wide_project_supported names without h2 (dwconv3x3_pool + dwconv3x3_project)
+  int wide_gram;      // "wide_gram" (1 = maps of at least kWideGramMinPixels pixels, 2 = every map): the 192 -> 64 wide block takes norm2's tables from the Gram of its input (gram.hip), pw_expand stores the
+                      // activated h1 and adds the SE pool totals: no pool pass (0 = dwconv3x3_pool from the stored h1)
+  int gram;           // "gram": norm2 statistics of the recompute form from the Gram matrix (gram.hip); 0 = expand_stats; 2 = at every size
+  int nt_min_mb;      // "nt_min_mb": tensors of at least this many MiB are stored non-temporally by the producers in nt_mask
+  int nt_mask;        // "nt_mask": 1 expand_dw, 2 pw_expand, 4 dwconv3x3, 8 project / attention GEMMs, 16 dense 3x3 convs
+  int se_mfma;        // "se_mfma": SE MLP of the wide blocks as two MFMA launches; 0 = the row-parallel pair
+  int bwd_async;      // "bwd_async": weight-gradient kernels of the backward pass on a side stream
+  int upconv_fold;    // "upconv_fold": up-sampling convs from folded weights wherever upconv_fold_supported(); 0 = blend in the kernel
+  int enhance_split;  // "enhance_split": concurrent branches of the captured enhance graph (< 2: a single chain)
+  int graph_max_steps;  // "graph_max_steps": loops of more steps than this run as plain launches, never captured
+  // read by the launchers
+  int pwx;            // "pwx": the activation-stationary expand GEMM (pwx.hip) where pw_expand_supported(); 0 = the tile kernel
+  int gemm_bk;        // "gemm_bk": K chunk of pw_gemm (0 = automatic, 32 = 32-wide chunks)
+  int irbx_dbuf;      // "irbx_dbuf": expand_dw's double-buffered variant for 32-channel inputs
+  int irbx_grid[3];   // "irbx_grid" (all), "irbx_grid2/4/6": workgroups per expand_dw launch, per input width 32 / 64 / 96 (0 = heuristics)
+  // 1 = launch the cycle-stamped diagnostic build of the family; "irbx_stamp": 1 expand_dw, 2 expand_pool, 3 expand_dw_project
+  int gemm_stamp, pwx_stamp, conv_stamp, irbx_stamp;
+  int epoch;          // llie_tune calls so far: keys the graph cache and the zero-region sizes, which bake kernel choices in
+};
+extern Knobs g_knobs;
+
+// Where a kernel family's cycle-stamped diagnostic builds write (host side, tune.cpp): `slots` counters per wave, wave after wave.
+// One instance per family, defined next to its launchers; llie_debug_*_stamps reads it back.
+struct StampSink {
+  int slots;
+  size_t max_waves;  // launches of more waves are refused; 0 = unbounded
+  unsigned long long* buf = nullptr;
+  size_t cap = 0, waves = 0;  // waves the buffer holds, waves of the last stamped launch
+  // the buffer a stamped launch of `waves` waves writes (grown on demand); hipErrorInvalidValue above max_waves
+  hipError_t arm(size_t launch_waves, unsigned long long** stamps);
+  // out[i] = mean over the waves of the last stamped launch of entry wave * slots + i, out[slots] = the number of waves;
+  // hipErrorInvalidValue when nothing was stamped
+  hipError_t fetch(double* out) const;
+};
+extern StampSink g_gemm_stamps, g_pwx_stamps, g_conv_stamps, g_irbx_stamps;
+
 // Per-channel statistics slab written by producers for the next GroupNorm:
 //   slab[((b * ntiles + tile) * 2 + {0: sum, 1: sum of squares}) * C + c]   (fp32)
 // `tile` enumerates the producer's row tiles inside one image.  gn_finalize reduces slabs in a fixed
@@ -51,14 +95,11 @@ struct GemmArgs {
   int nostore;        // 1: compute and write only the statistics slab (out may be null)
   const void* dot;    // optional [M][N] T: the slab then holds (sum out*dot, sum out) instead of (sum, sum of squares)
   int nt;             // 1: `out` is stored non-temporally (set by the engine for tensors beyond the Infinity Cache, common.h: st_vec_pol)
-  unsigned long long* stamps;  // diagnostic builds only (pw_gemm_stamp)
+  unsigned long long* stamps;  // diagnostic builds only (knob "gemm_stamp")
 };
-void pw_gemm_stamp(int v);
-hipError_t pw_gemm_stamp_fetch(double* out3);
 hipError_t launch_pw_gemm(int dtype, const GemmArgs& a, hipStream_t s);
 int pw_gemm_tile_rows(int P);  // BM used for a given P
 int pw_gemm_ntiles(int P);     // stats slab tiles per image = ceil(P / BM)
-void pw_gemm_force_bk(int bk);  // tuning knob (0 = automatic)
 
 // Expanding pointwise GEMM in activation-stationary form (pwx.hip; 2-byte T, every segment ACT_RELU6_S6):
 //   out[M][N] = sum_seg clamp01(A_seg * as + ab) . Wf^T,  Wf = the [N][K] weights times 6, pre-packed in MFMA fragment order
@@ -72,7 +113,7 @@ struct ExpandArgs {
   int M, N, K, P;
   int nsplit;  // set by the launcher
   int nt;      // 1: non-temporal output stores (see GemmArgs::nt)
-  unsigned long long* stamps;  // diagnostic builds only (pw_expand_debug)
+  unsigned long long* stamps;  // diagnostic builds only (knob "pwx_stamp")
   // launch_pw_expand_act: norm2's tables [B][N] DIVIDED BY 6 (DwArgs::s6), the depthwise weights [9][N] fp32, the image size
   // (H * W == P) and the fixed-point SE pool totals [B][N] it adds to; `stats` is not used
   const float* as2; const float* ab2; const float* wd;
@@ -91,10 +132,6 @@ hipError_t launch_pw_expand(int dtype, const ExpandArgs& a, hipStream_t s);
 bool pw_expand_act_supported(int dtype, const GemmSeg* seg, int nseg, int M, int N, int K, int P, int H, int W);
 hipError_t launch_pw_expand_act(int dtype, const ExpandArgs& a, hipStream_t s);
 hipError_t launch_pack_expand(int dtype, const float* src, void* dst, int N, int K, float scale, hipStream_t s);
-void pw_expand_enable(int v);  // knob "pwx" (1 = use where supported)
-bool pw_expand_enabled();
-void pw_expand_debug(int stamp);  // knob "pwx_stamp": 1 = launch the cycle-stamped build
-hipError_t pw_expand_stamp_fetch(double* out4);
 
 // GroupNorm statistics -> per-(image, channel) affine tables.
 //   mean/var over groups of cg = C/32 channels x P pixels from up to two slabs (virtual concat),
@@ -214,7 +251,7 @@ struct IrbxArgs {
   unsigned long long* pool_tot;                  // or: [B][Chid] fixed-point channel totals (see DwArgs::pool_tot)
   float* stats;                                  // expand_stats output
   int B, H, W, Chid;
-  unsigned long long* dbg;                       // diagnostic builds only (irbx_stamp)
+  unsigned long long* dbg;                       // diagnostic builds only (knob "irbx_stamp")
   int nt;                                        // 1: h2 is stored non-temporally (see GemmArgs::nt)
   // expand_dw_project: SE gate [B][Chid], project weights [Cout][ldp] T, y [B][H][W][Cout] T and y's statistics slab
   // [B][irbx_project_tiles][2][Cout].  Identity form: Cout = Cin = c0, x1 absent, ldp = Chid (set by the launcher); skip form:
@@ -234,9 +271,6 @@ struct IrbxArgs {
 bool wide_project_supported(int dtype, int Cin, int c0, int Chid, int Cout, bool skip, bool padded, int H, int W);
 hipError_t launch_dwconv3x3_pool(int dtype, const IrbxArgs& a, hipStream_t s);     // needs h1, as2 / ab2, wd; adds into pool_tot
 hipError_t launch_dwconv3x3_project(int dtype, const IrbxArgs& a, int cout, hipStream_t s);
-void irbx_grid(int ks, int v);   // knobs "irbx_grid" (ks = 0: all), "irbx_grid2/4/6": workgroups per expand_dw launch (0 = heuristics)
-void irbx_stamp(int v);
-hipError_t irbx_stamp_fetch(double* out10);  // 9 slots (irbx.hip: STAMP) + the number of waves averaged
 bool irbx_supported(int dtype, int Cin, int c0, int Chid, int H, int W);
 int irbx_pool_tiles(int H, int W);
 constexpr int kIrbxProjectIdentity = 1, kIrbxProjectSkip = 2;  // forms of the project tail
@@ -247,7 +281,6 @@ int irbx_stats_rows(int P);
 // grid.x workgroups, knobs "irbx_grid*"), 64-channel chunks per workgroup, grid.x, grid.y (grid.z = B).  Shapes of irbx_supported only
 struct IrbxPlan { int tpw, cpw, gx, gy; };
 IrbxPlan irbx_plan(int Cin, int B, int H, int W, bool project);
-void irbx_tune(int dbuf);  // knob "irbx_dbuf"
 hipError_t launch_expand_stats(int dtype, const IrbxArgs& a, hipStream_t s);
 hipError_t launch_expand_dw(int dtype, const IrbxArgs& a, hipStream_t s);
 hipError_t launch_expand_pool(int dtype, const IrbxArgs& a, hipStream_t s);        // needs as2 / ab2 / wd; adds into pool_tot
@@ -337,10 +370,8 @@ struct Conv3Args {
   int B, Hi, Wi, Cin, Cout;
   int mode;
   int nt;              // 1: non-temporal output stores (see GemmArgs::nt)
-  unsigned long long* stamps;  // diagnostic builds only (conv3x3_stamp)
+  unsigned long long* stamps;  // diagnostic builds only (knob "conv_stamp")
 };
-void conv3x3_stamp(int v);
-hipError_t conv3x3_stamp_fetch(double* out8);  // 7 per-wave cycle sums (conv.hip: STAMP) + waves averaged
 hipError_t launch_conv3x3(int dtype, const Conv3Args& a, hipStream_t s);
 int conv3x3_ntiles(int Ho, int Wo);
 //   the up-sampling conv (mode 1) from folded weights: the fixed bilinear x2 lives in per-phase 3x3 weights on the low-resolution

@@ -392,10 +392,6 @@ hipError_t launch_pack_expand(int dtype, const float* src, void* dst, int N, int
   return hipGetLastError();
 }
 
-static int g_use_pwx = 1;
-void pw_expand_enable(int v) { g_use_pwx = v; }
-bool pw_expand_enabled() { return g_use_pwx != 0; }
-
 // 32-channel blocks per LDS buffer.  One everywhere: the smaller LDS footprint (three workgroups per CU up to K = 256) is
 // worth more than the saved barriers (measured in round 3: profiles/r03)
 constexpr int kPwxNbw = 1;
@@ -407,7 +403,7 @@ static int nsplit_for(int M, int N, int nbw) {
 }
 bool pw_expand_serves_k(int K) { return K == 128 || K == 192 || K == 256 || K == 384 || K == 512; }
 bool pw_expand_supported(int dtype, const GemmSeg* seg, int nseg, int M, int N, int K, int P) {
-  if (!g_use_pwx || (dtype != 1 && dtype != 2) || nseg < 1 || nseg > 3 || P % 128 || M % P) return false;
+  if (!g_knobs.pwx || (dtype != 1 && dtype != 2) || nseg < 1 || nseg > 3 || P % 128 || M % P) return false;
   if (!pw_expand_serves_k(K) || N % (32 * kPwxNbw) || N % 64) return false;  // pairs of 32-channel blocks leave as 128-byte lines
   int k = 0;
   for (int i = 0; i < nseg; ++i) {
@@ -417,21 +413,7 @@ bool pw_expand_supported(int dtype, const GemmSeg* seg, int nseg, int M, int N, 
   return k == K;
 }
 
-static int g_pwx_stamp = 0;
-static unsigned long long* g_pwx_stamps = nullptr;
-static size_t g_pwx_stamp_waves = 0;
-constexpr size_t kPwxStampWaves = 1u << 18;
-void pw_expand_debug(int stamp) { g_pwx_stamp = stamp; }
-hipError_t pw_expand_stamp_fetch(double* out4) {  // mean s_memtime ticks per wave of the last stamped launch: {A phase, channel loop, of which in the vmcnt wait at the top of a buffer}, waves
-  if (!g_pwx_stamps || !g_pwx_stamp_waves) return hipErrorInvalidValue;
-  std::vector<unsigned long long> h(g_pwx_stamp_waves * 3);
-  if (hipError_t e = hipMemcpy(h.data(), g_pwx_stamps, h.size() * 8, hipMemcpyDeviceToHost); e != hipSuccess) return e;
-  double a = 0, b = 0, w = 0;
-  for (size_t i = 0; i < g_pwx_stamp_waves; ++i) { a += (double)h[3 * i]; b += (double)h[3 * i + 1]; w += (double)h[3 * i + 2]; }
-  out4[0] = a / (double)g_pwx_stamp_waves; out4[1] = b / (double)g_pwx_stamp_waves; out4[2] = w / (double)g_pwx_stamp_waves;
-  out4[3] = (double)g_pwx_stamp_waves;
-  return hipSuccess;
-}
+StampSink g_pwx_stamps{3, 1u << 18};  // s_memtime ticks per wave: {A phase, channel loop, of which in the vmcnt wait at the top of a buffer}
 
 template <typename T, int KS, int NBW, bool REGSTORE = false, bool STAMP = false>
 static hipError_t launch_one(ExpandArgs a, hipStream_t s) {
@@ -447,12 +429,8 @@ static hipError_t launch_cfg(ExpandArgs a, hipStream_t s) {
   static const std::string name = std::string("pw_expand_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) + ", " + std::to_string(NBW) + ">";
   note_kernel(name.c_str());
   if constexpr (std::is_same<T, half_t>::value && (KS == 12 || KS == 24)) {  // diagnostics for two representative shapes only
-    if (g_pwx_stamp) {
-      const size_t waves = (size_t)(a.M / 128) * a.nsplit * 4;
-      if (waves > kPwxStampWaves) return hipErrorInvalidValue;
-      if (!g_pwx_stamps && hipMalloc(reinterpret_cast<void**>(&g_pwx_stamps), kPwxStampWaves * 24) != hipSuccess) return hipErrorOutOfMemory;
-      g_pwx_stamp_waves = waves;
-      a.stamps = g_pwx_stamps;
+    if (g_knobs.pwx_stamp) {
+      if (hipError_t e = g_pwx_stamps.arm((size_t)(a.M / 128) * a.nsplit * 4, &a.stamps); e != hipSuccess) return e;
       return launch_one<T, KS, NBW, false, true>(a, s);
     }
   }

@@ -885,17 +885,22 @@ int llie_rw_probe(const void* src, void* dst, int64_t units, int reads, int writ
  *   0 = expand_stats), "pwx" [1] (activation-stationary expand GEMM, pwx.hip; 0 = tile kernel), "se_mfma" [1] (SE MLP of the wide blocks on the
  *   MFMA pipe), "gemm_bk" [0] (0 = auto, 32 = 32-wide K chunks), "nt_mask" [1], "nt_min_mb" [100] (which producers store tensors of at least so
  *   many MiB non-temporally: tune.cpp), "bwd_async" [1] (weight gradients on a side stream; 0 = single stream).
- * Diagnostics, slow (cycle-stamped kernel builds read back by llie_debug_*_stamps), all [0]: "gemm_stamp", "pwx_stamp", "conv_stamp", "irbx_stamp".
+ *   "irbx_project" [1] the recompute blocks expand_dw_project and expand_dw_project_skip cover run without h2 (expand_pool + the project
+ *   kernel above); 2 = the identity-residual blocks only, 0 = expand_dw and the project GEMM; any other value is taken as 1.
+ *   "wide_project" [1] the two wide decoder blocks of llie_wide_project_supported run without h2 (dwconv3x3_pool + dwconv3x3_project
+ *   above); 0 = dwconv3x3 and the project GEMM.  Independent of irbx_project.
+ *   "wide_gram" [1] the 192 -> 64 wide block takes norm2's tables from the Gram of its input (llie_gram_wide above) on maps of at least 4096
+ *   pixels, llie_pw_expand_act stores the activated h1 and adds the pool totals; 2 = on every map, 0 = the pool pass over the stored h1;
+ *   any other value is taken as 1.
+ *   "upconv_fold" [1] the up-sampling convs of 2-byte inference engines run from folded weights (llie_conv3x3_upfold above) on maps of
+ *   whole 8 x 16 low-resolution tiles; 0 = the kernel that blends the patch itself, everywhere.
+ *   "graph_max_steps" [20] loops of llie_enhance with more steps run as plain launches and are never captured (measured: replaying the
+ *   graph of a 50-step loop is slower than launching it); a value <= 0 restores the default.  It changes no bit.
+ * Diagnostics, slow (cycle-stamped kernel builds read back by llie_debug_*_stamps): "gemm_stamp" [0], "pwx_stamp" [0], "conv_stamp" [0],
+ * "irbx_stamp" [0] (1 expand_dw, 2 expand_pool, 3 expand_dw_project).
  * Threading: the knobs are plain process-wide variables read by every forward; call llie_tune only while no other
  * thread is inside an llie_* compute call (same rule as the handle itself: SURVEY.md 8b, one stream at a time). */
 int llie_tune(const char* knob, int value);
-/* One more engine knob, default 1: upconv_fold -- the up-sampling convs of 2-byte inference engines run from folded weights
- * (llie_conv3x3_upfold above) on maps of whole 8 x 16 low-resolution tiles; 0 = the kernel that blends the patch itself, everywhere.
- * And one for the loop of llie_enhance, default 20: graph_max_steps -- loops of more steps run as plain launches and are never
- * captured (measured: replaying the graph of a 50-step loop is slower than launching it); a value <= 0 restores the
- * default.  It changes no bit.
- * And wide_project, default 1: the two wide decoder blocks of llie_wide_project_supported run without h2 (dwconv3x3_pool +
- * dwconv3x3_project above); 0 = dwconv3x3 and the project GEMM.  Independent of "irbx_project". */
 int llie_debug_irbx_stamps(double* out10); /* diagnostic builds: 9 per-wave cycle sums of expand_dw ("irbx_stamp" = 1) or of expand_pool's LDS-tile scan ("irbx_stamp" = 2, 5 slots used) or of expand_dw_project ("irbx_stamp" = 3, slots of its own) (irbx.hip: STAMP) + waves averaged */
 int llie_debug_conv_stamps(double* out8); /* diagnostic builds: 7 per-wave cycle sums of the up-sampling conv (conv.hip: STAMP) + waves averaged */
 int llie_debug_gemm_stamps(double* out3); /* diagnostic builds: see gemm.hip (STAMP) */

@@ -599,16 +599,17 @@ def test_optimizer_entry_points_reject_bad_arguments_without_a_device():
 
 
 def test_llie_tune_accepts_exactly_the_documented_knobs():
-    """The knob comment of include/llie.h lists every name llie_tune takes, and nothing else: the 14 knobs that tests set (reference
+    """The knob comment of include/llie.h lists every name llie_tune takes, and nothing else: the 19 knobs that tests set (reference
     paths and invariances), the four that arm the cycle-stamped diagnostic builds, and no experiment leftovers.  Each listed name
     is accepted with its default, each removed name and a nonsense name come back as LLIE_ERR_ARG.  llie_tune only sets host
     variables, so this runs without a GPU."""
     defaults = {"pwx": 1, "gram": 1, "se_mfma": 1, "gemm_bk": 0, "irbx": 1, "irbx_dbuf": 0, "enhance_split": 2, "nt_mask": 1,
                 "nt_min_mb": 100, "irbx_grid": 0, "irbx_grid2": 0, "irbx_grid4": 0, "irbx_grid6": 0,
-                "gemm_stamp": 0, "pwx_stamp": 0, "conv_stamp": 0, "irbx_stamp": 0, "bwd_async": 1}
+                "gemm_stamp": 0, "pwx_stamp": 0, "conv_stamp": 0, "irbx_stamp": 0, "bwd_async": 1,
+                "irbx_project": 1, "wide_project": 1, "wide_gram": 1, "upconv_fold": 1, "graph_max_steps": 20}
     removed = ["skip_small", "irbx_mask", "ztot", "gemm_ablate", "gemm_bk128", "dw_ablate", "dw_swap", "irbx_ablate", "irbx_dwv",
                "irbx_var", "irbx_tiles", "pwx_ablate", "pwx_nbw", "wgrad_target"]
-    assert len(defaults) == 18 and len(removed) == 14
+    assert len(defaults) == 23 and len(removed) == 14
     header = open(os.path.join(ROOT, "include", "llie.h")).read()
     comment = re.search(r"/\* Engine knobs.*?\*/", header, re.S).group(0)
     assert set(re.findall(r'"(\w+)"', comment)) == set(defaults)
