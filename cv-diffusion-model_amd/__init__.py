@@ -15,7 +15,8 @@ from .ddim import ddim_timesteps, ddim_step_host, ddim_enhance_host
 from .pipeline import (LowLightDiffusion, LowLightDiffusionOutput, LowLightLCMDistillation, normalize_image,
                        denormalize_image, x0_loss, x0_loss_host)
 from .sharding import shard_range, enhance_sharded, all_gather_batch, all_reduce_gradients
-from .training import FusedAdamW, FusedGradScaler, TrainStep, DistillStep
+from .training import (FusedAdamW, FusedGradScaler, TrainStep, DistillStep, grad_accumulate_array,
+                       accumulation_windows)
 from .build import build_library, library_path
 from . import ops  # registers torch.ops.llie.*
 from .ops import register_model
@@ -36,7 +37,7 @@ __all__ = [
     "EfficientUNet", "EfficientUNetConfig", "create_efficient_unet", "InvertedResidualBlock", "LinearAttention", "SqueezeExcitation",
     "Downsample", "Upsample", "LCMScheduler", "LCMSchedulerOutput", "LCMDenoisingLoop", "get_lcm_timesteps", "LowLightDiffusion",
     "LowLightDiffusionOutput", "LowLightLCMDistillation", "normalize_image", "denormalize_image", "shard_range", "enhance_sharded",
-    "all_gather_batch", "all_reduce_gradients", "FusedAdamW", "FusedGradScaler", "TrainStep", "DistillStep", "register_model", "build_library", "library_path", "load_checkpoint", "extract_state_dict",
+    "all_gather_batch", "all_reduce_gradients", "FusedAdamW", "FusedGradScaler", "TrainStep", "DistillStep", "grad_accumulate_array", "accumulation_windows", "register_model", "build_library", "library_path", "load_checkpoint", "extract_state_dict",
     "preprocess_array", "postprocess_array", "resize_bilinear", "preprocess_device", "postprocess_device",
     "tile_origins", "gather_tiles_array", "blend_tiles_array", "gather_tiles_device", "gather_noise_device", "blend_tiles_device",
     "enhance_tiled", "frame_pad", "frame_load_array", "frame_store_array", "frame_load_device", "frame_store_device", "enhance_frame_u8",

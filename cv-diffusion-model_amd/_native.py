@@ -28,7 +28,7 @@ EXPORTS = [
     "llie_grad_numel", "llie_param_grad_offset", "llie_train_workspace_bytes", "llie_unet_train_forward",
     "llie_unet_backward", "llie_module_backward", "llie_load_all", "llie_profile_dump", "llie_copy_probe", "llie_rw_probe", "llie_pw_expand", "llie_gram_stats", "llie_gram_part_floats", "llie_groupnorm_finalize", "llie_conv3x3", "llie_conv3x3_tiles", "llie_linattn", "llie_linattn_splits", "llie_se_mlp", "llie_film", "llie_refresh_params", "llie_path_bytes", "llie_time_embed", "llie_debug_irbx_stamps", "llie_debug_gemm_stamps", "llie_debug_pwx_stamps", "llie_graph_cache_entries", "llie_debug_conv_stamps", "llie_gram_finalize",
     "llie_optimizer_create", "llie_optimizer_destroy", "llie_optimizer_numel", "llie_optimizer_step",
-    "llie_optimizer_step_amp",
+    "llie_optimizer_step_amp", "llie_grad_accumulate",
     "llie_consistency_target", "llie_consistency_loss", "llie_ema_create", "llie_ema_update", "llie_ema_destroy",
     "llie_wgrad", "llie_wgrad_msplit", "llie_wgrad_partial_floats", "llie_dw_wgrad", "llie_dw_wgrad_strips",
     "llie_groupnorm_backward", "llie_groupnorm_backward_scratch_floats", "llie_linattn_backward", "llie_linattn_dkv_floats",
@@ -293,6 +293,7 @@ def lib() -> C.CDLL:
     L.llie_optimizer_numel.restype = C.c_int64
     L.llie_optimizer_step.argtypes = [C.c_void_p, vp, C.POINTER(OptHyper), vp, vp]
     L.llie_optimizer_step_amp.argtypes = [C.c_void_p, vp, C.POINTER(OptHyper), C.POINTER(AmpState), C.POINTER(AmpConfig), vp, vp]
+    L.llie_grad_accumulate.argtypes = [vp, vp, i64, C.c_float, ci, vp]
     L.llie_consistency_target.argtypes = [vp, vp, vp, vp, vp, ci, vp, ci, i64, vp]
     L.llie_consistency_loss.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, ci, i64, vp, i64, vp]
     L.llie_ema_create.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), ci, C.POINTER(vp)]

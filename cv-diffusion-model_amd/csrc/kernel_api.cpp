@@ -769,6 +769,19 @@ int llie_optimizer_step_amp(llie_optimizer* o, const float* grad_base, const lli
   return kerr("optimizer_step_amp", launch_optimizer_step_amp(a, amp, o->amp_coef, hs(stream)), LLIE_ERR_ARG, "hyper-parameters outside their ranges (lr, eps, weight_decay >= 0; 0 <= beta < 1; ema_decay <= 1)");
 }
 
+int llie_grad_accumulate(float* acc, const float* grad, int64_t n, float weight, int first, llie_stream stream) {
+  if (!acc || !grad || n < 0) { set_err("grad_accumulate: null pointer or n < 0"); return LLIE_ERR_ARG; }
+  if (!std::isfinite(weight) || !(weight > 0.f)) { set_err("grad_accumulate: the weight must be finite and > 0"); return LLIE_ERR_ARG; }
+  const uintptr_t a = reinterpret_cast<uintptr_t>(acc), g = reinterpret_cast<uintptr_t>(grad);
+  if ((a | g) & 3) { set_err("grad_accumulate: pointers must be 4-byte aligned"); return LLIE_ERR_ARG; }
+  // keeps the byte count and the grid inside their types; no real buffer comes near it
+  if (n > (int64_t)1 << 40) { set_err("grad_accumulate: n above 2^40"); return LLIE_ERR_ARG; }
+  const uintptr_t bytes = (uintptr_t)n * 4;
+  if (a < g + bytes && g < a + bytes) { set_err("grad_accumulate: acc and grad overlap"); return LLIE_ERR_ARG; }
+  if (n == 0) return LLIE_OK;
+  return kerr("grad_accumulate", launch_grad_accumulate(acc, grad, (long long)n, weight, first != 0, hs(stream)), LLIE_ERR_ARG, "null pointer or n out of range");
+}
+
 // ---- consistency distillation
 int llie_consistency_target(const float* x_t, const float* e_teacher, const int64_t* t, const int64_t* t_next, const float* acp, int table_len,
                             float* x_next, int batch, int64_t per, llie_stream stream) {

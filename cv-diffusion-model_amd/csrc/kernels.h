@@ -651,6 +651,9 @@ struct OptAmpArgs {
   int growth_interval;
 };
 hipError_t launch_optimizer_step_amp(const OptStepArgs& a, const OptAmpArgs& amp, float* coef /* device [5] */, hipStream_t s);
+// gradient accumulation: acc[i] = first ? weight * grad[i] : acc[i] + weight * grad[i], i < n (two fp32 roundings, no FMA);
+// n == 0 launches nothing.  The caller has checked weight and that the ranges do not overlap.
+hipError_t launch_grad_accumulate(float* acc, const float* grad, long long n, float weight, bool first, hipStream_t s);
 
 // (10) consistency distillation (distill.hip): per-sample alpha-bar from a device table, fp32 [batch, per] tensors
 constexpr int kDistillLossPerWG = 1024;  // elements per workgroup of the loss pass (one double partial each)

@@ -301,4 +301,50 @@ hipError_t launch_optimizer_step_amp(const OptStepArgs& a, const OptAmpArgs& amp
   return hipGetLastError();
 }
 
+// Gradient accumulation over a window of micro-batches: acc = weight * g (kFirst: acc is not read, so what it held, NaNs
+// included, is gone) or acc + weight * g.  The product and the sum are two separately rounded fp32 operations (fp contraction
+// is off in the kernel: no fused multiply-add), so a NumPy twin is bit-equal; inf / NaN follow IEEE arithmetic.
+// One workgroup per run of kOptChunk elements, as the optimiser's kernels; 64-bit element index for the run's base.  A run's
+// base is a multiple of 16 KB, so the alignment of the two pointers decides the path for every run alike.
+// HBM-bound: 8 bytes per element (kFirst) or 12.  No LDS, no atomics.
+template <bool kFirst>
+__global__ void __launch_bounds__(kOptThreads) grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ grad, long long total, float w) {
+#pragma clang fp contract(off)
+  const long long base = (long long)blockIdx.x * kOptChunk;
+  const long long left = total - base;
+  const int n = left < kOptChunk ? (int)left : kOptChunk;
+  float* a = acc + base;
+  const float* g = grad + base;
+  int done = 0;
+  if (opt_aligned16(a) && opt_aligned16(g)) {
+    const int nv = n >> 2;
+    for (int i = threadIdx.x; i < nv; i += kOptThreads) {
+      const f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i);
+      f32x4 av = {0.f, 0.f, 0.f, 0.f};
+      if (!kFirst) av = reinterpret_cast<const f32x4*>(a)[i];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float prod = w * gv[k];
+        av[k] = kFirst ? prod : av[k] + prod;
+      }
+      reinterpret_cast<f32x4*>(a)[i] = av;
+    }
+    done = nv << 2;
+  }
+  for (int i = done + threadIdx.x; i < n; i += kOptThreads) {
+    const float prod = w * g[i];
+    a[i] = kFirst ? prod : a[i] + prod;
+  }
+}
+
+hipError_t launch_grad_accumulate(float* acc, const float* grad, long long n, float weight, bool first, hipStream_t s) {
+  const long long blocks = (n + kOptChunk - 1) / kOptChunk;
+  if (!acc || !grad || n < 0 || blocks > 2147483647LL) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  note_kernel(first ? "grad_accumulate_kernel<first>" : "grad_accumulate_kernel");
+  if (first) hipLaunchKernelGGL(grad_accumulate_kernel<true>, dim3((unsigned)blocks), dim3(kOptThreads), 0, s, acc, grad, n, weight);
+  else hipLaunchKernelGGL(grad_accumulate_kernel<false>, dim3((unsigned)blocks), dim3(kOptThreads), 0, s, acc, grad, n, weight);
+  return hipGetLastError();
+}
+
 }  // namespace llie

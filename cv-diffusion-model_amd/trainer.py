@@ -30,7 +30,7 @@ from .data import create_device_dataloaders
 from .ddim import check_sampler
 from .metrics import _require_hip, _steps_of, _swapped_weights, evaluate
 from .pipeline import LowLightDiffusion
-from .training import FusedAdamW, FusedGradScaler, TrainStep
+from .training import FusedAdamW, FusedGradScaler, TrainStep, accumulation_windows
 
 try:
     import wandb
@@ -244,13 +244,23 @@ class LowLightTrainer:
     that resumes passes it again) trains at a frame's own shape instead of config.image_size x config.image_size: the loaders must
     crop (H, W) (`DevicePairLoader(..., image_size=(H, W))`), `train_epoch` draws its noise at that shape, and `validate` /
     `generate_samples` run `enhance_frame`.  The model keeps the module tree config.image_size fixed; (H, W) is any shape
-    llie_train_shape_ok accepts at the batch size (checked here)."""
+    llie_train_shape_ok accepts at the batch size (checked here).
+
+    `accumulate=k` (extension; an integer >= 1, a keyword like `crop_size`: neither a TrainingConfig field nor stored in
+    checkpoints, a caller that resumes passes it again) takes one optimiser step per window of k consecutive loader batches
+    (`TrainStep.accumulate` x k, then `apply`): the effective batch is k * batch_size.  The windows of an epoch of n batches are
+    `accumulation_windows(n, k)`: the last one holds the remaining n mod k batches and is applied, nothing carries across an
+    epoch, so a checkpoint never holds an open window.  The LR schedule is built for ceil(n / k) steps per epoch and moves once
+    per `apply`; `global_step` counts optimiser steps.  k = 1 is the code path without the keyword, bit for bit."""
 
     def __init__(self, model: LowLightDiffusion, train_loader, val_loader=None, config: Optional[TrainingConfig] = None, *,
                  x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0, val_sampler: str = "lcm", val_steps: Optional[int] = None,
-                 crop_size: Optional[Tuple[int, int]] = None):
+                 crop_size: Optional[Tuple[int, int]] = None, accumulate: int = 1):
         self.config = config or TrainingConfig()
         cfg = self.config
+        if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
+            raise ValueError(f"accumulate must be an integer >= 1, got {accumulate!r}")
+        self.accumulate = accumulate
         if crop_size is None:
             self.crop_size = (int(cfg.image_size), int(cfg.image_size))
         else:
@@ -295,7 +305,7 @@ class LowLightTrainer:
 
         self.optimizer = FusedAdamW(model.parameters(), lr=cfg.learning_rate, weight_decay=cfg.weight_decay,
                                     max_grad_norm=cfg.gradient_clip, ema_decay=cfg.ema_decay if cfg.use_ema else None)
-        self.scheduler = make_lr_scheduler(self.optimizer, cfg, len(train_loader))
+        self.scheduler = make_lr_scheduler(self.optimizer, cfg, len(accumulation_windows(len(train_loader), accumulate)))
         self.scaler = FusedGradScaler() if dtype == "fp16" else None
         self.step = TrainStep(model, self.optimizer, loss_type=cfg.loss_type, grad_scaler=self.scaler,
                               x0_ssim_weight=x0_ssim_weight, x0_l1_weight=x0_l1_weight)
@@ -380,7 +390,11 @@ class LowLightTrainer:
         The LR schedule moves once per batch, after the step, also when a grad scaler skipped the step.  The losses go into a
         device buffer that is copied once, after the last batch; nothing else waits for the device, except the progress line
         (every `log_interval` batches; `log_interval = 0` or `progress = False` without wandb turns it off).  Returns the
-        Python-float sum of the fp32 batch losses in step order, divided by len(train_loader) (trainer.py:325,338)."""
+        Python-float sum of the fp32 batch losses in step order, divided by len(train_loader) (trainer.py:325,338).
+
+        With `accumulate=k` > 1 the draws are the same, per batch and in the same order; `step(...)` becomes
+        `step.accumulate(...)`, and after the last batch of each window (accumulation_windows(n, k)) come `step.apply()` and
+        `lr_scheduler.step()`.  The returned value is still the sum of the batch losses divided by n."""
         cfg, dev, loader = self.config, self.device, self.train_loader
         self.model.train()
         loader.set_epoch(self.epoch)
@@ -389,18 +403,30 @@ class LowLightTrainer:
         n = len(loader)
         losses = torch.zeros(n, dtype=torch.float32, device=dev)
         report = cfg.log_interval > 0 and (cfg.progress or cfg.use_wandb)
+        ends, done = set(), 0  # 1-based index of each window's last batch
+        for length in accumulation_windows(n, self.accumulate):
+            done += length
+            ends.add(done)
         for batch_idx, batch in enumerate(loader):
             low, normal = batch["low_light"], batch["normal_light"]
             b = low.shape[0]
             t = torch.randint(0, t_max, (b,), generator=g, device=dev)
             noise = torch.randn(b, 3, hh, ww, generator=g, device=dev)
-            loss = self.step(low, normal, timesteps=t, noise=noise)
-            # TrainStep steps through step_flat, not optimizer.step(), which torch's scheduler watches to warn about a
-            # schedule that moves before the optimiser: the optimiser has stepped
-            self.optimizer._opt_called = True
-            self.scheduler.step()
+            if self.accumulate == 1:
+                loss = self.step(low, normal, timesteps=t, noise=noise)
+                stepped = True
+            else:
+                loss = self.step.accumulate(low, normal, timesteps=t, noise=noise)
+                stepped = batch_idx + 1 in ends
+                if stepped:
+                    self.step.apply()
+            if stepped:
+                # TrainStep steps through step_flat, not optimizer.step(), which torch's scheduler watches to warn about a
+                # schedule that moves before the optimiser: the optimiser has stepped
+                self.optimizer._opt_called = True
+                self.scheduler.step()
+                self.global_step += 1
             losses[batch_idx].copy_(loss)
-            self.global_step += 1
             if report and batch_idx % cfg.log_interval == 0:
                 value = loss.item()
                 self._say(f"Epoch {self.epoch} [{batch_idx + 1}/{n}] loss={value:.4f}")
@@ -514,10 +540,11 @@ class LowLightTrainer:
 
 def train_model(train_data_dir: str, val_data_dir: Optional[str] = None, config: Optional[TrainingConfig] = None,
                 device="cuda", *, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0, val_sampler: str = "lcm",
-                val_steps: Optional[int] = None, crop_size: Optional[Tuple[int, int]] = None) -> LowLightTrainer:
+                val_steps: Optional[int] = None, crop_size: Optional[Tuple[int, int]] = None, accumulate: int = 1) -> LowLightTrainer:
     """Training entry point (trainer.py:459-496): loaders from the folders (create_device_dataloaders), a fresh model, a trainer,
     `train()`; returns the trainer.  `x0_ssim_weight` / `x0_l1_weight` / `val_sampler` / `val_steps` / `crop_size`: as
-    LowLightTrainer's (with `crop_size=(H, W)` the loaders crop H x W; the model is still built at config.image_size)."""
+    LowLightTrainer's (with `crop_size=(H, W)` the loaders crop H x W; the model is still built at config.image_size);
+    `accumulate`: LowLightTrainer's."""
     config = config or TrainingConfig()
     train_loader, val_loader = create_device_dataloaders(train_root=train_data_dir, val_root=val_data_dir, batch_size=config.batch_size,
                                                          image_size=config.image_size if crop_size is None else tuple(crop_size),
@@ -527,6 +554,6 @@ def train_model(train_data_dir: str, val_data_dir: Optional[str] = None, config:
                               num_inference_steps=config.num_inference_steps).to(train_loader.store.device)
     trainer = LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config,
                               x0_ssim_weight=x0_ssim_weight, x0_l1_weight=x0_l1_weight, val_sampler=val_sampler, val_steps=val_steps,
-                              crop_size=crop_size)
+                              crop_size=crop_size, accumulate=accumulate)
     trainer.train()
     return trainer

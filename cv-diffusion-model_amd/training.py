@@ -18,6 +18,10 @@
 `DistillStep` -- one step of consistency distillation (`LowLightLCMDistillation.consistency_distillation_loss -> backward ->
                  AdamW -> update_ema`) the same way: three denoiser passes, the distillation kernels and one flat gradient buffer.
 
+Gradient accumulation: `TrainStep` and `DistillStep` also run as windows of micro-batches -- `accumulate` per micro-batch,
+then `apply` (one optimiser step from acc = sum b_i g_i at grad_scale 1 / sum b_i) or `discard` -- see `_GradWindow`;
+`grad_accumulate_array` is the NumPy definition of the kernel behind it (llie_grad_accumulate, csrc/optim.hip).
+
 There is no CPU fallback: all three need the HIP library and parameters on a HIP device.
 """
 import ctypes as C
@@ -316,7 +320,100 @@ def _train_buffers(step, h: N.Handle, batch: int, dev: torch.device, height: int
     return nbytes
 
 
-class TrainStep:
+def grad_accumulate_array(acc, grad, weight, first):
+    """NumPy definition of llie_grad_accumulate (bit-equal to the kernel): `weight * grad` when `first`, else
+    `acc + weight * grad`, in fp32 with the product and the sum rounded separately.  With `first`, `acc` is not read.
+    Returns a new fp32 array; inf / NaN follow IEEE arithmetic."""
+    import numpy as np
+    w = np.float32(weight)
+    if not np.isfinite(w) or not w > 0:
+        raise ValueError("grad_accumulate_array: the weight must be finite and > 0")
+    g = np.asarray(grad, dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        prod = np.multiply(w, g, dtype=np.float32)
+        if first:
+            return prod
+        a = np.asarray(acc, dtype=np.float32)
+        if a.shape != g.shape:
+            raise ValueError("grad_accumulate_array: acc and grad must have one shape")
+        return np.add(a, prod, dtype=np.float32)
+
+
+def accumulation_windows(n: int, k: int) -> List[int]:
+    """Lengths of the windows that n loader batches form at `accumulate=k`: k consecutive batches each, the last one the
+    remaining n mod k when that is not 0.  They sum to n; there are ceil(n / k) of them."""
+    n, k = int(n), int(k)
+    if n < 0 or k < 1:
+        raise ValueError(f"accumulation_windows: n >= 0 and k >= 1, got n={n}, k={k}")
+    return [k] * (n // k) + ([n % k] if n % k else [])
+
+
+class _GradWindow:
+    """Gradient accumulation shared by TrainStep and DistillStep (both provide `_flat`, `_offsets`, `opt`, `grad_scaler`).
+
+    A window is a sequence of micro-batches i = 1..k of b_i images (their shapes may differ where the step allows it).
+    `accumulate` leaves g_i, the gradient of micro-batch i's own mean loss, in the flat buffer and the window keeps
+        acc = sum_i b_i * g_i          (llie_grad_accumulate: fp32, product and sum rounded separately, in micro-batch order)
+    in a second flat fp32 buffer, allocated on the first `accumulate`.  `apply` takes one optimiser step,
+        step_flat(acc, offsets, grad_scale = 1 / (world * sum_i b_i)),
+    the gradient of the mean over the window's images of each image's own mean loss (for equal shapes: the loss of the
+    concatenated batch), so nobody needs to know sum b in advance.  The window loss is formed from device scalars, without a
+    host read, as
+        num = float(b_1) * loss_1;  num = num + float(b_i) * loss_i (i = 2..k);  loss = num / float(sum b_i)      (fp32)
+    With a FusedGradScaler the scale only moves inside `apply`, so it is constant across a window; a non-finite micro-batch
+    makes `acc` non-finite, and the step is then skipped and the scale backed off exactly as for a single step.
+    `__call__` raises RuntimeError while a window is open; `apply` raises RuntimeError on an empty window; `discard` closes a
+    window without stepping."""
+
+    _acc: Optional[torch.Tensor] = None
+    _win_images = 0
+    _win_loss: Optional[torch.Tensor] = None
+
+    @property
+    def window_images(self) -> int:
+        """sum b of the open window (0: no window is open)."""
+        return self._win_images
+
+    def _no_open_window(self, who: str) -> None:
+        if self._win_images:
+            raise RuntimeError(f"{who}: a gradient-accumulation window is open ({self._win_images} images); apply() or discard() it first")
+
+    def _window_add(self, b: int, loss: torch.Tensor) -> None:
+        """acc (+)= b * flat; window loss numerator (+)= b * loss."""
+        flat = self._flat
+        first = self._win_images == 0
+        if self._acc is None or self._acc.numel() != flat.numel() or self._acc.device != flat.device:
+            if not first:
+                raise RuntimeError("the flat gradient buffer changed inside an open window")
+            self._acc = torch.empty_like(flat)
+        dev = flat.device
+        with torch.cuda.device(dev):
+            N.check(N.lib().llie_grad_accumulate(self._acc.data_ptr(), flat.data_ptr(), flat.numel(), float(b), 1 if first else 0,
+                                                 torch.cuda.current_stream(dev).cuda_stream), "accumulate")
+        term = loss * float(b)
+        self._win_loss = term if first else self._win_loss + term
+        self._win_images += b
+
+    @torch.no_grad()
+    def _window_apply(self, group=None, reduce: bool = True) -> torch.Tensor:
+        if not self._win_images:
+            raise RuntimeError("apply: no micro-batch has been accumulated")
+        world = 1
+        if reduce and dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            dist.all_reduce(self._acc, group=group)  # the window's only collective; the average rides on grad_scale
+            world = dist.get_world_size(group)
+        total = self._win_images
+        loss = self._win_loss / float(total)
+        self._win_images, self._win_loss = 0, None
+        self.opt.step_flat(self._acc, self._offsets, grad_scale=1.0 / (world * total), grad_scaler=self.grad_scaler)
+        return loss
+
+    def discard(self) -> None:
+        """Close the window without stepping (the accumulator's content is dropped: the next `accumulate` overwrites it)."""
+        self._win_images, self._win_loss = 0, None
+
+
+class TrainStep(_GradWindow):
     """One optimisation step of the reference trainer (trainer.py:281-324) on the engine, without autograd:
     q-sample (low_light_diffusion.py:140-160) -> llie_unet_train_forward -> loss and d(loss)/d(eps) -> llie_unet_backward into a
     persistent flat buffer -> one all-reduce of that buffer over the ranks -> FusedAdamW.step_flat (clip, AdamW, EMA).
@@ -332,7 +429,9 @@ class TrainStep:
     the device scale (one elementwise operation, no host read) before the optimiser updates that scale; on a step the scaler
     skips, its values may be non-finite.  Only the condition half is exposed: with the x0 term on, x_t also enters the loss
     directly.  It is this rank's gradient (never all-reduced).  With `cond_grad=False` the step is what it was, bit for bit.
-    Returns the loss (device scalar, unscaled)."""
+    Returns the loss (device scalar, unscaled).
+    Gradient accumulation: `accumulate(...)` per micro-batch, then `apply()` (or `discard()`), see _GradWindow; `__call__` is
+    one step from one batch as before and raises RuntimeError while a window is open."""
 
     def __init__(self, model, optimizer: FusedAdamW, loss_type: str = "mse", use_velocity_target: bool = False, group=None,
                  grad_scaler: Optional[FusedGradScaler] = None, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0,
@@ -357,6 +456,39 @@ class TrainStep:
     @torch.no_grad()
     def __call__(self, low_light: torch.Tensor, normal_light: torch.Tensor, timesteps: Optional[torch.Tensor] = None,
                  noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        self._no_open_window("TrainStep.__call__")
+        loss = self._micro(low_light, normal_light, timesteps, noise)
+        scale = 1.0
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
+            dist.all_reduce(self._flat, group=self.group)  # one collective over all gradients; the average rides on grad_scale
+            scale = 1.0 / dist.get_world_size(self.group)
+        self.opt.step_flat(self._flat, self._offsets, grad_scale=scale, grad_scaler=self.grad_scaler)
+        return loss
+
+    @torch.no_grad()
+    def accumulate(self, low_light: torch.Tensor, normal_light: torch.Tensor, timesteps: Optional[torch.Tensor] = None,
+                   noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One micro-batch of a window: everything `__call__` does up to and including the backward pass into the flat buffer
+        (at the batch's own H x W, which may differ from the window's other micro-batches), then `acc (+)= b * flat`
+        (llie_grad_accumulate).  Returns the micro-batch loss (device scalar, unscaled); nothing reads from the host.  A shape
+        llie_train_shape_ok refuses raises before the accumulator is touched and leaves an open window as it was."""
+        if self._want_cond_grad:
+            raise ValueError("TrainStep.accumulate: cond_grad=True is not supported in a window (the window's weight is not known "
+                             "when a micro-batch's condition gradient is produced)")
+        loss = self._micro(low_light, normal_light, timesteps, noise)
+        self._window_add(int(low_light.shape[0]), loss)
+        return loss
+
+    def apply(self) -> torch.Tensor:
+        """Close the window with one optimiser step from `acc` (see _GradWindow) and return the window loss.  With a process
+        group of more than one rank, `acc` is all-reduced first, the window's only collective, and the divisor is world * sum b:
+        every rank must have accumulated the same sum b (not checked)."""
+        return self._window_apply(self.group)
+
+    def _micro(self, low_light: torch.Tensor, normal_light: torch.Tensor, timesteps: Optional[torch.Tensor],
+               noise: Optional[torch.Tensor]) -> torch.Tensor:
+        """q-sample -> train forward -> loss and d(loss)/d(eps) (x0 term, grad-scaler multiplication) -> backward into
+        `self._flat`; returns the loss."""
         from .unet import resolve_compute_dtype
         model, unet = self.model, self.model.unet
         b, dev = low_light.shape[0], low_light.device
@@ -396,15 +528,10 @@ class TrainStep:
             else:
                 N.check(L.llie_unet_backward(h.h, d_eps.data_ptr(), self._flat.data_ptr(), b, self._ws.data_ptr(), nbytes, st),
                         "EfficientUNet.backward")
-        scale = 1.0
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
-            dist.all_reduce(self._flat, group=self.group)  # one collective over all gradients; the average rides on grad_scale
-            scale = 1.0 / dist.get_world_size(self.group)
-        self.opt.step_flat(self._flat, self._offsets, grad_scale=scale, grad_scaler=self.grad_scaler)
         return loss
 
 
-class DistillStep:
+class DistillStep(_GradWindow):
     """One optimisation step of consistency distillation (LowLightLCMDistillation, low_light_diffusion.py:325-393, then
     AdamW and update_ema) without autograd:
       draws (noise, idx) -> add_noise -> teacher forward at t -> llie_consistency_target (x_next) -> student
@@ -432,6 +559,30 @@ class DistillStep:
     @torch.no_grad()
     def __call__(self, low_light: torch.Tensor, normal_light: torch.Tensor, num_inference_steps: int = 4, *,
                  noise: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+        self._no_open_window("DistillStep.__call__")
+        loss = self._micro(low_light, normal_light, num_inference_steps, noise, idx)
+        self.opt.step_flat(self._flat, self._offsets, grad_scaler=self.grad_scaler)
+        self.distill.update_ema(self.ema_decay)
+        return loss
+
+    @torch.no_grad()
+    def accumulate(self, low_light: torch.Tensor, normal_light: torch.Tensor, num_inference_steps: int = 4, *,
+                   noise: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One micro-batch of a window (at image_size): the teacher, student and EMA-target forwards, the loss and the backward
+        pass of `__call__`, then `acc (+)= b * flat`.  Returns the micro-batch loss (device scalar)."""
+        loss = self._micro(low_light, normal_light, num_inference_steps, noise, idx)
+        self._window_add(int(low_light.shape[0]), loss)
+        return loss
+
+    def apply(self) -> torch.Tensor:
+        """Close the window: one optimiser step from `acc` (see _GradWindow), then `update_ema` once.  Returns the window loss."""
+        loss = self._window_apply(reduce=False)  # as __call__: this step has no gradient all-reduce
+        self.distill.update_ema(self.ema_decay)
+        return loss
+
+    def _micro(self, low_light: torch.Tensor, normal_light: torch.Tensor, num_inference_steps: int, noise: Optional[torch.Tensor],
+               idx: Optional[torch.Tensor]) -> torch.Tensor:
+        """The three denoiser passes, the distillation kernels and the backward pass into `self._flat`; returns the loss."""
         from .pipeline import consistency_loss, consistency_target
         from .unet import resolve_compute_dtype
         d = self.distill
@@ -465,6 +616,4 @@ class DistillStep:
         with torch.cuda.device(dev):
             N.check(L.llie_unet_backward(h.h, d_eps.data_ptr(), self._flat.data_ptr(), b, self._ws.data_ptr(), nbytes,
                                          torch.cuda.current_stream(dev).cuda_stream), "EfficientUNet.backward")
-        self.opt.step_flat(self._flat, self._offsets, grad_scaler=self.grad_scaler)
-        d.update_ema(self.ema_decay)
         return loss

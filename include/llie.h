@@ -270,6 +270,15 @@ typedef struct llie_amp_config {
 } llie_amp_config;
 int llie_optimizer_step_amp(llie_optimizer* opt, const float* grad_base, const llie_opt_hyper* hyper, const llie_amp_state* state,
                             const llie_amp_config* cfg, float* stats3, llie_stream stream);
+/* Gradient accumulation over a window of micro-batches (device fp32, e.g. the flat buffer llie_unet_backward fills):
+ * acc[i] = first ? weight * grad[i] : acc[i] + weight * grad[i], i < n.  The product and the sum are
+ * rounded separately in fp32 (no fused multiply-add), so the NumPy twin is bit-equal.  With first != 0
+ * acc is not read (stale NaNs do not survive).  n == 0: LLIE_OK, no launch.  Inf / NaN in grad propagate by ordinary
+ * arithmetic, so the loss scaler of llie_optimizer_step_amp sees a bad micro-batch at the end of the window.
+ * Checked before any HIP call (LLIE_ERR_ARG): a NULL pointer, a pointer that is not 4-byte aligned, n < 0 (or above 2^40), a
+ * weight that is not finite or is <= 0, ranges [acc, acc + n) and [grad, grad + n) that overlap.  Pointers that are both
+ * 16-byte aligned take four-float accesses with a scalar tail, others single elements; the element index is 64-bit. */
+int llie_grad_accumulate(float* acc, const float* grad, int64_t n, float weight, int first, llie_stream stream);
 
 /* ---- Consistency distillation (LowLightLCMDistillation.consistency_distillation_loss / update_ema,
  * low_light_diffusion.py:284-408).  Tensors are device fp32 NCHW [batch, 3, S, S] (per_sample = 3*S*S elements per

@@ -21,6 +21,12 @@ then includes it; val_loss stays the MSE).  The two weights are not stored in ch
 trains at a frame's own shape, the one frame mode (scripts/inference.py --mode frame) runs at: crops of 400 x 600 instead of
 --image_size squares, validation and sample sheets through enhance_frame.  Both flags or neither; multiples of 8, at least 64.
 The model keeps the module tree --image_size fixed.  Like the x0 weights the shape is not stored in checkpoints.
+
+  python scripts/train.py --data_dir LOL/our485 --crop_height 1080 --crop_width 1920 --batch_size 2 --accumulate 8
+
+takes one optimiser step per window of 8 consecutive batches (gradient accumulation): an effective batch of 16 where one call
+holds 2 frames.  The last window of an epoch holds what is left; the LR schedule moves once per window.  Not stored in
+checkpoints: pass it again with --resume.
 """
 import argparse
 import importlib
@@ -76,6 +82,8 @@ def build_parser() -> argparse.ArgumentParser:
                         "DDIM loop a many-step (teacher) model wants, with --num_steps steps (anything in 1..1000) in both")
     p.add_argument("--crop_height", type=int, default=None, help="train at crops of this height (with --crop_width) instead of --image_size squares")
     p.add_argument("--crop_width", type=int, default=None, help="the width that goes with --crop_height")
+    p.add_argument("--accumulate", type=int, default=1,
+                   help="batches per optimiser step (gradient accumulation; >= 1): the effective batch is --accumulate x --batch_size")
     return p
 
 
@@ -84,6 +92,8 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if (args.crop_height is None) != (args.crop_width is None):
         p.error("--crop_height and --crop_width go together: both or neither")
+    if args.accumulate < 1:
+        p.error("--accumulate must be >= 1")
     return args
 
 
@@ -140,7 +150,7 @@ def main(argv=None) -> int:
     print(f"  Parameters: {size['num_params']:,}")
 
     trainer = M.LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config,
-                                **x0_weights_from_args(args), **sampler_from_args(args), crop_size=crop)
+                                **x0_weights_from_args(args), **sampler_from_args(args), crop_size=crop, accumulate=args.accumulate)
     print(f"  Engine precision: {model.compute_dtype}, loss scaler: {trainer.scaler is not None}, EMA: {config.use_ema}")
     trainer.train(on_epoch=lambda log: print(json.dumps(log), flush=True))
     print("\nTraining complete!")
