@@ -6,6 +6,7 @@
 //   Downsample  (efficient_unet.py:367)  3x3 stride 2       } implicit GEMM on MFMA: M = 8 x TW output pixels,
 //   Upsample    (efficient_unet.py:383-384) bilinear x2 + 3x3 } N = Cout tile, K = 9 taps x Cin; the upsampled
 //               halo patch is interpolated on the fly into LDS, so the 4x tensor never reaches HBM.
+#include <algorithm>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -1139,6 +1140,316 @@ hipError_t launch_conv3x3_upfold(int dtype, const Conv3Args& a, hipStream_t s) {
   if (a.Cin != a.Cout || a.B < 1 || !conv3x3_upfold_ok(dtype, a.Hi, a.Wi, a.Cin)) return hipErrorInvalidValue;
   if (dtype == 1) return a.Cin == 64 ? launch_upfold_cfg<half_t, true>(a, s) : launch_upfold_cfg<half_t, false>(a, s);
   return a.Cin == 64 ? launch_upfold_cfg<bf16_t, true>(a, s) : launch_upfold_cfg<bf16_t, false>(a, s);
+}
+
+// =============================================================================================
+// Up-sampling conv from nine low-resolution tap maps.  conv3x3(up2(x)) is linear in x and up2 is fixed, so with Z_t = W_t x (nine
+// 1x1 maps of the LOW-resolution input, one per tap t = (dy, dx)) the output is bias + the sum over the taps that fall inside
+// the 2H x 2W image of up2(Z_t) at the tap's position: 9/4 C^2 multiply-adds per output pixel instead of 9 C^2.  up2 = bilinear
+// x2, align_corners=False = weights 3/4, 1/4 on the replicate-clamped low-resolution neighbours, so the conv's zero padding is a
+// dropped term, never a correction: every workgroup does the same work.
+// Work item = one image, one 8 x 16 low-resolution tile, 32 output channels.  One 8-wave workgroup per compute unit (the maps take
+// 104 KB of LDS) works through items blockIdx.x, + gridDim.x, ...; the first operand loads of the next item are issued before
+// the blend of this one, and this one's stores drain under the next one's MFMAs (6-10 us per launch against one workgroup per
+// item, profiles/r24).
+//   1. Maps: a plain GEMM, no shifted reads.  288 (tap, cout) rows of the [9][Cout][Cin] weights x the replicate-clamped 10 x 18
+//      patch (180 pixels, padded to 192 columns) over K = Cin, on the 16x16x32 MFMA with the weights as its A operand: a lane then
+//      holds four consecutive channels of one tap of one pixel.  Wave (wn, wp) = 9 row blocks x 3 pixel blocks.  Both operands of
+//      a 32-channel chunk are staged in LDS as unpadded 64-byte rows, 16-byte slot s of row r at slot s ^ 2 (r >> 3 & 1): with it
+//      every ds_read_b128 lane group of a fragment read covers 64 different banks.  Two buffers, the global loads of the next two
+//      chunks in registers under this chunk's MFMAs, one barrier per chunk.
+//   2. The maps, rounded to T, replace the operand buffers: [180 pixels][9 taps][32 channels], the eight channel quads of a
+//      (pixel, tap) rotated by pixel >> 1 so that the 16 pixels of a block's ds_write_b64 fall into 32 different banks; the pixel
+//      pitch (144 dwords) keeps the blend's reads conflict-free.
+//   3. Blend, separable: a thread owns two channels of one tile column and four tile rows.  Per patch row it forms H[dy][b], the
+//      three column taps of row tap dy blended for column phase b (7 map reads per dy), and an output pixel (2i + a, 2j + b) is
+//      the same combination of H over rows i - 1, i, i + 1.  One fixed order of fp32 operations for every pixel, border terms
+//      multiplied by an exact 0: bitwise reproducible and batch invariant like the two kernels above.
+//   4. + bias, round to T, store; GroupNorm partials from the rounded values go to slab entry 4 tile of the tile's four entries,
+//      the other three are written as zeros.
+// Item order: the channel blocks of one tile run on ONE XCD (workgroups are dealt round-robin to the eight XCDs and the item
+// stride is a multiple of 8), so a patch comes from HBM once and is re-read from that XCD's L2.  Which workgroup computes an
+// item changes no bit of it.
+template <typename T>
+__global__ void __launch_bounds__(512) conv3x3_upmaps_kernel(const Conv3Args a, const int nitems) {
+  constexpr int NT = 512, TH = 8, TW = 16, PW = TW + 2, NPIX = (TH + 2) * PW, BN = 32, NROW = 9 * BN;
+  constexpr int PROWS = 192, SROWS = PROWS + NROW;  // rows of one operand buffer: patch pixels (180, padded), then weight rows
+  constexpr int P_ITEMS = (NPIX * 4 + NT - 1) / NT, W_ITEMS = (NROW * 4 + NT - 1) / NT;
+  typedef typename Elem<T>::vec_t vec_t;
+  typedef T t2 __attribute__((ext_vector_type(2)));
+  typedef T t4 __attribute__((ext_vector_type(4)));
+  static_assert(Elem<T>::VEC == 8, "2-byte types only");
+
+  extern __shared__ __align__(16) unsigned char smem[];
+  T* sS = reinterpret_cast<T*>(smem);                                            // [2][SROWS][32]
+  T* sM = reinterpret_cast<T*>(smem);                                            // [NPIX][NROW], after the K loop
+  float* red = reinterpret_cast<float*>(smem + (size_t)NPIX * NROW * sizeof(T));  // [8 waves][2][BN]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int H = a.Hi, W = a.Wi, Ho = 2 * H, Wo = 2 * W, C = a.Cin;
+  const int tiles_x = W / TW, tiles = tiles_x * (H / TH), nb = C / BN, ntot = a.B * tiles;
+  const T* wbase = reinterpret_cast<const T*>(a.w);
+
+  struct Item { int b, tile, iy0, ix0, n0; };
+  auto decode = [&](int id) {
+    int t, nblk;
+    if (ntot & 7) {
+      t = id / nb; nblk = id % nb;
+    } else {
+      const int slot = id >> 3;
+      t = (slot / nb) * 8 + (id & 7); nblk = slot % nb;
+    }
+    Item it;
+    it.b = t / tiles; it.tile = t % tiles;
+    it.iy0 = (it.tile / tiles_x) * TH; it.ix0 = (it.tile % tiles_x) * TW; it.n0 = nblk * BN;
+    return it;
+  };
+
+  // ---- operand loads of one work item: its patch and its 288 weight rows, one 32-channel chunk at a time
+  const int ks = tid & 3, kv = ks * 8;
+  const T* in = nullptr;
+  int poff[P_ITEMS], woff[W_ITEMS];
+  float nbias[2];
+  auto setup = [&](const Item& it) {
+    in = reinterpret_cast<const T*>(a.in) + (size_t)it.b * H * W * C;
+#pragma unroll
+    for (int q = 0; q < P_ITEMS; ++q) {
+      const int pix = min((tid + q * NT) >> 2, NPIX - 1);
+      const int gy = min(max(it.iy0 - 1 + pix / PW, 0), H - 1), gx = min(max(it.ix0 - 1 + pix % PW, 0), W - 1);  // replicate padding
+      poff[q] = (gy * W + gx) * C + kv;
+    }
+#pragma unroll
+    for (int q = 0; q < W_ITEMS; ++q) {
+      const int row = min((tid + q * NT) >> 2, NROW - 1);
+      woff[q] = ((row >> 5) * C + it.n0 + (row & 31)) * C + kv;
+    }
+    nbias[0] = a.bias ? a.bias[it.n0 + 2 * (tid & 15)] : 0.f;
+    nbias[1] = a.bias ? a.bias[it.n0 + 2 * (tid & 15) + 1] : 0.f;
+  };
+  auto srow = [](int r, int s) { return r * 32 + ((s ^ (((r >> 3) & 1) << 1)) << 3); };  // element offset of slot s of row r
+  // two register sets: the loads of chunk k + 2 are issued when chunk k starts and written to LDS when chunk k + 1 ends
+  vec_t rp[2][P_ITEMS], rw[2][W_ITEMS];
+  auto issue = [&](int set, int c0) {
+#pragma unroll
+    for (int q = 0; q < P_ITEMS; ++q)
+      if (tid + q * NT < NPIX * 4) rp[set][q] = ld_vec<T>(in + poff[q] + c0);
+#pragma unroll
+    for (int q = 0; q < W_ITEMS; ++q)
+      if (tid + q * NT < NROW * 4) rw[set][q] = ld_vec<T>(wbase + woff[q] + c0);
+  };
+  auto commit = [&](int set, int buf) {
+    T* sp = sS + buf * (SROWS * 32);
+#pragma unroll
+    for (int q = 0; q < P_ITEMS; ++q)
+      if (tid + q * NT < NPIX * 4) st_vec<T>(sp + srow((tid + q * NT) >> 2, ks), rp[set][q]);
+#pragma unroll
+    for (int q = 0; q < W_ITEMS; ++q)
+      if (tid + q * NT < NROW * 4) st_vec<T>(sp + PROWS * 32 + srow((tid + q * NT) >> 2, ks), rw[set][q]);
+  };
+
+  const int wn = wave & 1, wp = wave >> 1;
+  int prd[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) prd[i] = srow(min((wp * 3 + i) * 16 + (lane & 15), NPIX - 1), lane >> 4);  // rows 180..191: a copy of 179, never kept
+  const int wrd = PROWS * 32 + srow(wn * 9 * 16 + (lane & 15), lane >> 4);  // + 16 rows per block: the slot does not change
+
+  int item = blockIdx.x;
+  Item cur = decode(item);
+  setup(cur);
+  issue(0, 0);
+  if (C > 32) issue(1, 32);
+  while (true) {
+    const float bias[2] = {nbias[0], nbias[1]};
+    // ---- 1. maps
+    f32x4acc acc[9][3];
+#pragma unroll
+    for (int jj = 0; jj < 9; ++jj)
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[jj][i][r] = 0.f;
+    commit(0, 0);  // (the previous item's maps are done with: the barrier that ends the loop body)
+    wg_barrier();
+    auto chunk = [&](int c0, int buf) {  // buf = (c0 / 32) & 1, a constant at both call sites: the register sets stay registers
+      if (c0 + 64 < C) issue(buf, c0 + 64);
+      const T* sp = sS + buf * (SROWS * 32);
+      vec_t pf[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) pf[i] = *reinterpret_cast<const vec_t*>(sp + prd[i]);
+#pragma unroll
+      for (int jj = 0; jj < 9; ++jj) {
+        const vec_t wf = *reinterpret_cast<const vec_t*>(sp + wrd + jj * (16 * 32));
+#pragma unroll
+        for (int i = 0; i < 3; ++i) acc[jj][i] = mfma16x16<T>(wf, pf[i], acc[jj][i]);
+      }
+      if (c0 + 32 < C) commit(buf ^ 1, buf ^ 1);  // its last readers finished before the previous barrier
+      wg_barrier();                               // next chunk visible; after the last chunk: everyone done with the operand buffers
+    };
+    for (int c0 = 0; c0 < C; c0 += 64) {
+      chunk(c0, 0);
+      if (c0 + 32 < C) chunk(c0 + 32, 1);
+    }
+
+    // ---- 2. maps to LDS, rounded to T
+    // (lv, tv: the lane and thread number again, opaque to the compiler -- it would otherwise compute the ~60 LDS and output
+    // addresses of steps 2 to 4 once, in front of the item loop, and keep them in registers through the K loop: 35 spilled)
+    int lv = lane, tv = tid;
+    asm volatile("" : "+v"(lv), "+v"(tv));
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int p = (wp * 3 + i) * 16 + (lv & 15);
+      if (p < NPIX) {
+#pragma unroll
+        for (int jj = 0; jj < 9; ++jj) {
+          const int n = (wn * 9 + jj) * 16 + 4 * (lv >> 4);  // rows n .. n + 3 of D: four channels of tap n >> 5
+          t4 v;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = (T)acc[jj][i][r];
+          *reinterpret_cast<t4*>(sM + p * NROW + (n >> 5) * 32 + (((((n & 31) >> 2) + (p >> 1)) & 7) << 2)) = v;
+        }
+      }
+    }
+    wg_barrier();
+
+    // the next item's first two chunks: their latency runs under this item's blend
+    const int next = item + (int)gridDim.x;
+    const bool has_next = next < nitems;
+    Item nx = cur;
+    if (has_next) {
+      nx = decode(next);
+      setup(nx);
+      issue(0, 0);
+      if (C > 32) issue(1, 32);
+    }
+
+    // ---- 3. blend + 4. epilogue
+    const int cp = tv & 15, j = (wave & 3) * 4 + ((tv >> 4) & 3), i0 = (wave >> 2) * 4;  // two channels, tile column, first tile row
+    const float kl = cur.ix0 + j == 0 ? 0.f : 1.f, kr = cur.ix0 + j == W - 1 ? 0.f : 1.f;
+    auto ldz = [&](int pix, int tap, float (&z)[2]) {
+      const t2 v = *reinterpret_cast<const t2*>(sM + pix * NROW + tap * 32 + ((((cp >> 1) + (pix >> 1)) & 7) << 2) + (cp & 1) * 2);
+      z[0] = (float)v[0];
+      z[1] = (float)v[1];
+    };
+    // H[dy][b] of patch row pr at this thread's column: up-sampled columns 2j + b + dx - 1 of map (dy, dx), summed over dx
+    auto hrow = [&](int pr, float (&h)[3][2][2]) {
+      const int pix = pr * PW + j;  // patch column j = tile column j - 1
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy) {
+        float l0[2], m0[2], l1[2], m1[2], r1[2], m2[2], r2[2];
+        ldz(pix, dy * 3, l0); ldz(pix + 1, dy * 3, m0);
+        ldz(pix, dy * 3 + 1, l1); ldz(pix + 1, dy * 3 + 1, m1); ldz(pix + 2, dy * 3 + 1, r1);
+        ldz(pix + 1, dy * 3 + 2, m2); ldz(pix + 2, dy * 3 + 2, r2);
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          h[dy][0][e] = 0.75f * ((kl * l0[e] + m1[e]) + m2[e]) + 0.25f * ((kl * m0[e] + l1[e]) + r2[e]);
+          h[dy][1][e] = 0.75f * ((kr * r2[e] + m1[e]) + m0[e]) + 0.25f * ((kr * m2[e] + r1[e]) + l0[e]);
+        }
+      }
+    };
+    float s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
+    T* outp = reinterpret_cast<T*>(a.out) + (size_t)cur.b * Ho * Wo * C + cur.n0 + 2 * cp;
+    float h[3][3][2][2];
+    hrow(i0, h[0]);
+    hrow(i0 + 1, h[1]);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      hrow(i0 + r + 2, h[(r + 2) % 3]);
+      const auto& hm = h[r % 3];
+      const auto& hc = h[(r + 1) % 3];
+      const auto& hp = h[(r + 2) % 3];
+      const int iy = cur.iy0 + i0 + r;
+      const float kt = iy == 0 ? 0.f : 1.f, kb = iy == H - 1 ? 0.f : 1.f;
+#pragma unroll
+      for (int pb = 0; pb < 2; ++pb) {
+        t2 o0, o1;
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const float v0 = 0.75f * ((kt * hm[0][pb][e] + hc[1][pb][e]) + hc[2][pb][e]) + 0.25f * ((kt * hc[0][pb][e] + hm[1][pb][e]) + hp[2][pb][e]);
+          const float v1 = 0.75f * ((kb * hp[2][pb][e] + hc[1][pb][e]) + hc[0][pb][e]) + 0.25f * ((kb * hc[2][pb][e] + hp[1][pb][e]) + hm[0][pb][e]);
+          o0[e] = (T)(v0 + bias[e]);
+          o1[e] = (T)(v1 + bias[e]);
+          const float q0 = (float)o0[e], q1 = (float)o1[e];
+          s1[e] += q0; s2[e] += q0 * q0;
+          s1[e] += q1; s2[e] += q1 * q1;
+        }
+        t2* d0 = reinterpret_cast<t2*>(outp + ((size_t)(2 * iy) * Wo + 2 * (cur.ix0 + j) + pb) * C);
+        t2* d1 = reinterpret_cast<t2*>(outp + ((size_t)(2 * iy + 1) * Wo + 2 * (cur.ix0 + j) + pb) * C);
+        if (a.nt) {
+          __builtin_nontemporal_store(o0, d0);
+          __builtin_nontemporal_store(o1, d1);
+        } else {
+          *d0 = o0;
+          *d1 = o1;
+        }
+      }
+    }
+    if (a.stats) {
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        s1[e] += __shfl_xor(s1[e], 16, 64); s1[e] += __shfl_xor(s1[e], 32, 64);
+        s2[e] += __shfl_xor(s2[e], 16, 64); s2[e] += __shfl_xor(s2[e], 32, 64);
+      }
+      if (lane < 16) {
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          red[(wave * 2 + 0) * BN + 2 * cp + e] = s1[e];
+          red[(wave * 2 + 1) * BN + 2 * cp + e] = s2[e];
+        }
+      }
+      wg_barrier();
+      if (tid < 8 * BN) {  // entry k of the tile's four, sum / sum of squares, channel
+        const int k = tid >> 6, which = (tid >> 5) & 1, c = tid & 31;
+        float tt = 0.f;
+        if (k == 0) {
+#pragma unroll
+          for (int w = 0; w < NT / 64; ++w) tt += red[(w * 2 + which) * BN + c];
+        }
+        a.stats[((size_t)((cur.b * tiles + cur.tile) * 4 + k) * 2 + which) * C + cur.n0 + c] = tt;
+      }
+    }
+    if (!has_next) break;
+    wg_barrier();  // everyone done with the maps and the statistics scratch
+    cur = nx;
+    item = next;
+  }
+}
+
+bool conv3x3_upmaps_ok(int dtype, int Hi, int Wi, int C) {
+  return (dtype == 1 || dtype == 2) && Hi > 0 && Wi > 0 && Hi % 8 == 0 && Wi % 16 == 0 && C > 0 && C % 32 == 0;
+}
+
+// compute units of the current device (one workgroup fits on each), asked once per device
+static int upmaps_cus() {
+  static std::atomic<int> cached[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  int n = cached[dev & 63].load(std::memory_order_acquire);
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+    cached[dev & 63].store(n, std::memory_order_release);
+  }
+  return n;
+}
+
+template <typename T>
+static hipError_t launch_upmaps_t(const Conv3Args& a, hipStream_t s) {
+  constexpr size_t lds = (size_t)180 * 288 * sizeof(T) + (size_t)8 * 2 * 32 * 4;  // the maps (> the operand buffers) + the statistics
+  static_assert(lds >= (size_t)2 * (192 + 288) * 32 * sizeof(T) && lds <= 160 * 1024, "LDS");
+  static std::atomic<uint64_t> attr_done{0};
+  if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&conv3x3_upmaps_kernel<T>), (int)lds, attr_done); e != hipSuccess) return e;
+  const int nitems = a.B * (a.Hi / 8) * (a.Wi / 16) * (a.Cin / 32);
+  int cus = upmaps_cus();
+  if (cus < 1) return hipErrorInvalidDevice;
+  if (cus & 7) cus = 1 << 30;  // the XCD order of the items counts on a stride that is a multiple of 8: else one item per workgroup
+  static const std::string name = std::string("conv3x3_upmaps_kernel<") + TypeName<T>::value + ">";
+  note_kernel(name.c_str());
+  hipLaunchKernelGGL((conv3x3_upmaps_kernel<T>), dim3((unsigned)std::min(nitems, cus)), dim3(512), lds, s, a, nitems);
+  return hipGetLastError();
+}
+// a.w = the plain [9][Cout][Cin] weights of launch_conv3x3; a.mode is ignored
+hipError_t launch_conv3x3_upmaps(int dtype, const Conv3Args& a, hipStream_t s) {
+  if (a.Cin != a.Cout || a.B < 1 || !conv3x3_upmaps_ok(dtype, a.Hi, a.Wi, a.Cin)) return hipErrorInvalidValue;
+  return dtype == 1 ? launch_upmaps_t<half_t>(a, s) : launch_upmaps_t<bf16_t>(a, s);
 }
 
 hipError_t launch_conv3x3(int dtype, const Conv3Args& a, hipStream_t s) {

@@ -321,6 +321,13 @@ inline IrbPath irb_path(int dt, const IrbW& w, int c0, int H, int W, bool traini
 inline bool upconv_fold_supported(int dt, int Hi, int Wi, int C) {
   return g_knobs.upconv_fold && (C == 64 || C == 128) && conv3x3_upfold_ok(dt, Hi, Wi, C);
 }
+// Asked before it: the same conv from nine low-resolution tap maps blended on chip (conv3x3_upmaps_kernel: a quarter of the
+// multiply-adds, plain weights), under the same conditions, at the channel counts where it measured faster than what it
+// replaces in every pair (profiles/r24).  C = 64 stays with the folded weights: there the blend alone costs what that kernel
+// takes in all.
+inline bool upconv_maps_supported(int dt, int Hi, int Wi, int C) {
+  return g_knobs.upconv_maps && (C == 128 || C == 256) && conv3x3_upmaps_ok(dt, Hi, Wi, C);
+}
 
 // ---------------------------------------------------------------------------------------------
 // What the forward (forward.cpp: Run) and the backward pass (backward.cpp: Back) share: context, arena, stream, workspace.

@@ -441,7 +441,9 @@ struct Run : Exec {
   Tens conv3(const ConvW& w, const Tens& x, int mode) {
     const int Ho = mode == 0 ? x.H / 2 : x.H * 2, Wo = mode == 0 ? x.W / 2 : x.W * 2;
     // up-sampling convs of an inference forward run from the folded weights wherever the rule of engine.h says so
-    const bool fold = mode == 1 && !tape && w.has_fold && upconv_fold_supported(dt, x.H, x.W, w.c);
+    // (nine tap maps first, then the folded weights)
+    const bool maps = mode == 1 && !tape && w.c == w.c_r && upconv_maps_supported(dt, x.H, x.W, w.c);
+    const bool fold = !maps && mode == 1 && !tape && w.has_fold && upconv_fold_supported(dt, x.H, x.W, w.c);
     Tens y = new_tens(w.c, Ho, Wo, fold ? conv3x3_upfold_ntiles(Ho, Wo) : conv3x3_ntiles(Ho, Wo), w.c_r);
     Tens u;
     snprintf(tag, sizeof tag, "conv3 mode=%d C=%d %dx%d", mode, w.c, x.H, x.W);
@@ -463,7 +465,7 @@ struct Run : Exec {
         if (fold) a.w = wptr(w.w_fold);
         // the algorithmic bytes charge the 9 C^2 source weights in either form (the folded blob is 64 C^2)
         timed(LLIE_K_CONV3, ((int64_t)B * w.c * ((int64_t)x.H * x.W + (int64_t)Ho * Wo) + 9LL * w.c * w.c) * (int64_t)es(),
-              [&] { return fold ? launch_conv3x3_upfold(dt, a, s) : launch_conv3x3(dt, a, s); });
+              [&] { return maps ? launch_conv3x3_upmaps(dt, a, s) : (fold ? launch_conv3x3_upfold(dt, a, s) : launch_conv3x3(dt, a, s)); });
       }
     }
     if (tape) {

@@ -159,6 +159,14 @@ int llie_conv3x3_upfold(int dtype, const void* in, const void* folded, const flo
   return kerr("conv3x3_upfold", launch_conv3x3_upfold(dtype, a, hs(stream)));
 }
 int llie_conv3x3_upfold_tiles(int Ho, int Wo) { return conv3x3_upfold_ntiles(Ho, Wo); }
+int llie_conv3x3_upmaps(int dtype, const void* in, const void* w, const float* bias, void* out, float* stats, int batch, int Hi, int Wi, int C,
+                        llie_stream stream) {
+  if (!in || !w || !out || (dtype != 1 && dtype != 2)) return LLIE_ERR_ARG;
+  Conv3Args a{};
+  a.in = in; a.w = w; a.bias = bias; a.out = out; a.stats = stats; a.B = batch; a.Hi = Hi; a.Wi = Wi; a.Cin = C; a.Cout = C; a.mode = 1;
+  return kerr("conv3x3_upmaps", launch_conv3x3_upmaps(dtype, a, hs(stream)));
+}
+int llie_conv3x3_upmaps_supported(int dtype, int Hi, int Wi, int C) { return conv3x3_upmaps_ok(dtype, Hi, Wi, C) ? 1 : 0; }
 int llie_linattn_splits(int N) { return linattn_nsplit(N); }
 int llie_linattn(int dtype, const void* qkv, float* kv_scratch, void* out, int batch, int N, int heads, llie_stream stream) {
   if (!qkv || !kv_scratch || !out || dtype < 0 || dtype > 2 || batch <= 0 || N <= 0 || heads <= 0) return LLIE_ERR_ARG;

@@ -32,6 +32,7 @@ struct Knobs {
   int se_mfma;        // "se_mfma": SE MLP of the wide blocks as two MFMA launches; 0 = the row-parallel pair
   int bwd_async;      // "bwd_async": weight-gradient kernels of the backward pass on a side stream
   int upconv_fold;    // "upconv_fold": up-sampling convs from folded weights wherever upconv_fold_supported(); 0 = blend in the kernel
+  int upconv_maps;    // "upconv_maps": up-sampling convs from nine low-resolution tap maps wherever upconv_maps_supported(); 0 = the rule of upconv_fold alone
   int enhance_split;  // "enhance_split": concurrent branches of the captured enhance graph (< 2: a single chain)
   int graph_max_steps;  // "graph_max_steps": loops of more steps than this run as plain launches, never captured
   // read by the launchers
@@ -385,6 +386,11 @@ int conv3x3_ntiles(int Ho, int Wo);
 bool conv3x3_upfold_ok(int dtype, int Hi, int Wi, int C);  // the kernel's contract: 2-byte dtype, Hi % 8 == 0, Wi % 16 == 0, C = 64 or a multiple of 128
 hipError_t launch_conv3x3_upfold(int dtype, const Conv3Args& a, hipStream_t s);
 int conv3x3_upfold_ntiles(int Ho, int Wo);
+//   the up-sampling conv (mode 1) from nine low-resolution tap maps, blended on chip (conv.hip: conv3x3_upmaps_kernel): a quarter of
+//   the multiply-adds.  Cin == Cout == C; `w` = the plain [9][C][C] T weights of launch_conv3x3 (no folded blob).
+//   stats: [B][conv3x3_ntiles(Ho, Wo)][2][C], four entries per low-resolution 8 x 16 tile: the first carries the sums, three are zero
+bool conv3x3_upmaps_ok(int dtype, int Hi, int Wi, int C);  // the kernel's contract: 2-byte dtype, Hi % 8 == 0, Wi % 16 == 0, C a multiple of 32
+hipError_t launch_conv3x3_upmaps(int dtype, const Conv3Args& a, hipStream_t s);
 constexpr int kUpconvFoldSets = 64;
 inline size_t upconv_fold_elems(int C) { return (size_t)kUpconvFoldSets * C * C; }
 

@@ -591,6 +591,16 @@ int llie_upconv_fold_weights(int dtype, const float* w_oihw, void* folded, int C
 int llie_conv3x3_upfold(int dtype, const void* in, const void* folded, const float* bias, void* out, float* stats, int batch, int Hi, int Wi,
                         int C, llie_stream stream);
 int llie_conv3x3_upfold_tiles(int Ho, int Wo);
+/* The same conv from nine low-resolution tap maps (knob "upconv_maps"): Z_t = W_t x for the nine taps, kept on chip, and the output is
+ * bias + the sum of the bilinear x2 of Z_t at tap t's position over the taps inside the image -- a quarter of the multiply-adds.  `w` =
+ * the plain [9][C][C] weights of llie_conv3x3 in the compute type (dtype 1 or 2), no folded blob; Hi % 8 == 0, Wi % 16 == 0, C a
+ * multiple of 32 (llie_conv3x3_upmaps_supported: 1 where the kernel accepts the shape); stats (or NULL)
+ * [batch][llie_conv3x3_tiles(2 Hi, 2 Wi)][2][C], every entry written.  The maps are rounded to the compute type once.
+ * llie_tune("upconv_maps", v), default 1: of the up-sampling convs that "upconv_fold" covers, 2-byte inference engines run those of 128
+ * and 256 channels this way; 0 = what "upconv_fold" alone picks, the launches and bits from before this form existed. */
+int llie_conv3x3_upmaps(int dtype, const void* in, const void* w, const float* bias, void* out, float* stats, int batch, int Hi, int Wi,
+                        int C, llie_stream stream);
+int llie_conv3x3_upmaps_supported(int dtype, int Hi, int Wi, int C);
 int llie_linattn(int dtype, const void* qkv, float* kv_scratch, void* out, int batch, int N, int heads, llie_stream stream);
 int llie_linattn_splits(int N);
 int llie_se_mlp(int dtype, const float* pool_sums, int pixels, const void* w1, const float* b1, const void* w2, const float* b2, float* mean_scratch,
@@ -924,7 +934,7 @@ int llie_debug_pwx_stamps(double* out4);  /* diagnostic builds: see pwx.hip (STA
 enum llie_kernel_class {
   LLIE_K_GEMM = 1,  /* pw_gemm_kernel: 1x1 convs with fused prologue / epilogue */
   LLIE_K_DW = 2,    /* dwconv3x3_kernel */
-  LLIE_K_CONV3 = 4, /* conv3x3_kernel, conv3x3_upfold_kernel (down / up sampling convs) */
+  LLIE_K_CONV3 = 4, /* conv3x3_kernel, conv3x3_upfold_kernel, conv3x3_upmaps_kernel (down / up sampling convs) */
   LLIE_K_SE = 8,    /* squeeze-excitation MLP launches */
   LLIE_K_OTHER = 16 /* everything else on the forward path (norm finalize, attention core, input / output convs, time MLPs) */
 };
