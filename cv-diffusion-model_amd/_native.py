@@ -41,7 +41,7 @@ EXPORTS = [
     "llie_aug_pair_u8", "llie_aug_synth_u8",
     "llie_image_metrics_scratch_bytes", "llie_image_metrics_f32", "llie_image_metrics_u8", "llie_comparison_grid_u8",
     "llie_upconv_fold_elems", "llie_upconv_fold_weights", "llie_conv3x3_upfold", "llie_conv3x3_upfold_tiles",
-    "llie_conv3x3_upmaps", "llie_conv3x3_upmaps_supported",
+    "llie_conv3x3_upmaps", "llie_conv3x3_upmaps_supported", "llie_conv3x3_upmaps_grid", "llie_conv3x3_upmaps_workgroups",
     "llie_expand_dw", "llie_expand_pool", "llie_expand_dw_project", "llie_expand_dw_project_skip", "llie_irbx_project_tiles",
     "llie_expand_dw_plan", "llie_wide_project_supported", "llie_irb_forms", "llie_dwconv3x3_pool", "llie_dwconv3x3_project",
     "llie_expand_stats", "llie_irbx_stats_rows",
@@ -239,6 +239,8 @@ def lib() -> C.CDLL:
     L.llie_conv3x3_upfold_tiles.argtypes = [ci, ci]
     L.llie_conv3x3_upmaps.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
     L.llie_conv3x3_upmaps_supported.argtypes = [ci, ci, ci, ci]
+    L.llie_conv3x3_upmaps_grid.argtypes = [ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
+    L.llie_conv3x3_upmaps_workgroups.argtypes = [ci, ci, ci, ci]
     L.llie_linattn.argtypes = [ci, vp, vp, vp, ci, ci, ci, vp]
     L.llie_linattn_splits.argtypes = [ci]
     L.llie_se_mlp.argtypes = [ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]

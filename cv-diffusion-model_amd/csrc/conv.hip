@@ -1431,25 +1431,41 @@ static int upmaps_cus() {
   return n;
 }
 
+static int upmaps_nitems(int B, int Hi, int Wi, int C) { return B * (Hi / 8) * (Wi / 16) * (C / 32); }
+// the rule: one workgroup per compute unit, or per item where there are fewer items
+static hipError_t upmaps_rule(int nitems, int* wgs) {
+  int cus = upmaps_cus();
+  if (cus < 1) return hipErrorInvalidDevice;
+  if (cus & 7) cus = 1 << 30;  // the XCD order of the items counts on a stride that is a multiple of 8: else one item per workgroup
+  *wgs = std::min(nitems, cus);
+  return hipSuccess;
+}
+int conv3x3_upmaps_workgroups(int B, int Hi, int Wi, int C, hipError_t* err) {
+  int wgs = 0;
+  *err = B < 1 || !conv3x3_upmaps_ok(1, Hi, Wi, C) ? hipErrorInvalidValue : upmaps_rule(upmaps_nitems(B, Hi, Wi, C), &wgs);
+  return wgs;
+}
+
 template <typename T>
-static hipError_t launch_upmaps_t(const Conv3Args& a, hipStream_t s) {
+static hipError_t launch_upmaps_t(const Conv3Args& a, hipStream_t s, int workgroups) {
   constexpr size_t lds = (size_t)180 * 288 * sizeof(T) + (size_t)8 * 2 * 32 * 4;  // the maps (> the operand buffers) + the statistics
   static_assert(lds >= (size_t)2 * (192 + 288) * 32 * sizeof(T) && lds <= 160 * 1024, "LDS");
   static std::atomic<uint64_t> attr_done{0};
   if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&conv3x3_upmaps_kernel<T>), (int)lds, attr_done); e != hipSuccess) return e;
-  const int nitems = a.B * (a.Hi / 8) * (a.Wi / 16) * (a.Cin / 32);
-  int cus = upmaps_cus();
-  if (cus < 1) return hipErrorInvalidDevice;
-  if (cus & 7) cus = 1 << 30;  // the XCD order of the items counts on a stride that is a multiple of 8: else one item per workgroup
+  const int nitems = upmaps_nitems(a.B, a.Hi, a.Wi, a.Cin);
+  int wgs = std::min(nitems, workgroups);
+  if (workgroups == 0)
+    if (hipError_t e = upmaps_rule(nitems, &wgs); e != hipSuccess) return e;
   static const std::string name = std::string("conv3x3_upmaps_kernel<") + TypeName<T>::value + ">";
   note_kernel(name.c_str());
-  hipLaunchKernelGGL((conv3x3_upmaps_kernel<T>), dim3((unsigned)std::min(nitems, cus)), dim3(512), lds, s, a, nitems);
+  hipLaunchKernelGGL((conv3x3_upmaps_kernel<T>), dim3((unsigned)wgs), dim3(512), lds, s, a, nitems);
   return hipGetLastError();
 }
-// a.w = the plain [9][Cout][Cin] weights of launch_conv3x3; a.mode is ignored
-hipError_t launch_conv3x3_upmaps(int dtype, const Conv3Args& a, hipStream_t s) {
-  if (a.Cin != a.Cout || a.B < 1 || !conv3x3_upmaps_ok(dtype, a.Hi, a.Wi, a.Cin)) return hipErrorInvalidValue;
-  return dtype == 1 ? launch_upmaps_t<half_t>(a, s) : launch_upmaps_t<bf16_t>(a, s);
+// a.w = the plain [9][Cout][Cin] weights of launch_conv3x3; a.mode is ignored.  workgroups 0: the rule; n >= 1: min(n, items),
+// any of which computes the same bits (the kernel's decode is a bijection on the items whatever the stride)
+hipError_t launch_conv3x3_upmaps(int dtype, const Conv3Args& a, hipStream_t s, int workgroups) {
+  if (a.Cin != a.Cout || a.B < 1 || workgroups < 0 || !conv3x3_upmaps_ok(dtype, a.Hi, a.Wi, a.Cin)) return hipErrorInvalidValue;
+  return dtype == 1 ? launch_upmaps_t<half_t>(a, s, workgroups) : launch_upmaps_t<bf16_t>(a, s, workgroups);
 }
 
 hipError_t launch_conv3x3(int dtype, const Conv3Args& a, hipStream_t s) {

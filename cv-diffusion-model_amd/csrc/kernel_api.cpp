@@ -159,12 +159,24 @@ int llie_conv3x3_upfold(int dtype, const void* in, const void* folded, const flo
   return kerr("conv3x3_upfold", launch_conv3x3_upfold(dtype, a, hs(stream)));
 }
 int llie_conv3x3_upfold_tiles(int Ho, int Wo) { return conv3x3_upfold_ntiles(Ho, Wo); }
-int llie_conv3x3_upmaps(int dtype, const void* in, const void* w, const float* bias, void* out, float* stats, int batch, int Hi, int Wi, int C,
-                        llie_stream stream) {
-  if (!in || !w || !out || (dtype != 1 && dtype != 2)) return LLIE_ERR_ARG;
+int llie_conv3x3_upmaps_grid(int dtype, const void* in, const void* w, const float* bias, void* out, float* stats, int batch, int Hi, int Wi,
+                             int C, int workgroups, llie_stream stream) {
+  if (!in || !w || !out || (dtype != 1 && dtype != 2) || workgroups < 0) return LLIE_ERR_ARG;
   Conv3Args a{};
   a.in = in; a.w = w; a.bias = bias; a.out = out; a.stats = stats; a.B = batch; a.Hi = Hi; a.Wi = Wi; a.Cin = C; a.Cout = C; a.mode = 1;
-  return kerr("conv3x3_upmaps", launch_conv3x3_upmaps(dtype, a, hs(stream)));
+  return kerr("conv3x3_upmaps", launch_conv3x3_upmaps(dtype, a, hs(stream), workgroups));
+}
+int llie_conv3x3_upmaps(int dtype, const void* in, const void* w, const float* bias, void* out, float* stats, int batch, int Hi, int Wi, int C,
+                        llie_stream stream) {
+  return llie_conv3x3_upmaps_grid(dtype, in, w, bias, out, stats, batch, Hi, Wi, C, 0, stream);
+}
+int llie_conv3x3_upmaps_workgroups(int batch, int Hi, int Wi, int C) {
+  hipError_t e = hipSuccess;
+  const int n = conv3x3_upmaps_workgroups(batch, Hi, Wi, C, &e);
+  if (e == hipSuccess) return n;
+  // a count is positive, so the runtime's own codes (> 0) come back negated; a refused shape is LLIE_ERR_ARG
+  const int rc = kerr("conv3x3_upmaps_workgroups", e, LLIE_ERR_ARG, "batch >= 1, Hi % 8 == 0, Wi % 16 == 0, C % 32 == 0");
+  return rc < 0 ? rc : -rc;
 }
 int llie_conv3x3_upmaps_supported(int dtype, int Hi, int Wi, int C) { return conv3x3_upmaps_ok(dtype, Hi, Wi, C) ? 1 : 0; }
 int llie_linattn_splits(int N) { return linattn_nsplit(N); }

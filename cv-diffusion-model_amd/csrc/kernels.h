@@ -390,7 +390,11 @@ int conv3x3_upfold_ntiles(int Ho, int Wo);
 //   the multiply-adds.  Cin == Cout == C; `w` = the plain [9][C][C] T weights of launch_conv3x3 (no folded blob).
 //   stats: [B][conv3x3_ntiles(Ho, Wo)][2][C], four entries per low-resolution 8 x 16 tile: the first carries the sums, three are zero
 bool conv3x3_upmaps_ok(int dtype, int Hi, int Wi, int C);  // the kernel's contract: 2-byte dtype, Hi % 8 == 0, Wi % 16 == 0, C a multiple of 32
-hipError_t launch_conv3x3_upmaps(int dtype, const Conv3Args& a, hipStream_t s);
+//   The grid is sized to the chip: workgroup g of n works through items g, g + n, ... (item = image, tile, 32 output channels).
+//   workgroups 0 = the rule, conv3x3_upmaps_workgroups (min(items, compute units); one per item where the compute units are no
+//   multiple of 8; *err says why it has no answer); n >= 1 = min(n, items) workgroups, the same bits on any n (what the tests use)
+hipError_t launch_conv3x3_upmaps(int dtype, const Conv3Args& a, hipStream_t s, int workgroups = 0);
+int conv3x3_upmaps_workgroups(int B, int Hi, int Wi, int C, hipError_t* err);
 constexpr int kUpconvFoldSets = 64;
 inline size_t upconv_fold_elems(int C) { return (size_t)kUpconvFoldSets * C * C; }
 

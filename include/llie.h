@@ -597,9 +597,19 @@ int llie_conv3x3_upfold_tiles(int Ho, int Wo);
  * multiple of 32 (llie_conv3x3_upmaps_supported: 1 where the kernel accepts the shape); stats (or NULL)
  * [batch][llie_conv3x3_tiles(2 Hi, 2 Wi)][2][C], every entry written.  The maps are rounded to the compute type once.
  * llie_tune("upconv_maps", v), default 1: of the up-sampling convs that "upconv_fold" covers, 2-byte inference engines run those of 128
- * and 256 channels this way; 0 = what "upconv_fold" alone picks, the launches and bits from before this form existed. */
+ * and 256 channels this way; 0 = what "upconv_fold" alone picks, the launches and bits from before this form existed.
+ * The kernel's grid is sized to the chip: a work item is (image, 8 x 16 low-resolution tile, 32 output channels), and workgroup g of n
+ * works through items g, g + n, ...  llie_conv3x3_upmaps_workgroups: the n that llie_conv3x3_upmaps launches for that shape on the
+ * current device = min(items, compute units), or one workgroup per item where the compute units are no multiple of 8; LLIE_ERR_ARG for
+ * batch < 1 or a shape no dtype is accepted at, minus the runtime's error code where no device answers (a count is positive).
+ * llie_conv3x3_upmaps_grid: the same launch on min(workgroups, items) workgroups, workgroups 0 = that rule (llie_conv3x3_upmaps is
+ * this case), negative = LLIE_ERR_ARG before any launch.  Which workgroup computes an item changes no bit of the output or the
+ * statistics, so every count gives the same result; the tests use it to walk the item loop at small shapes. */
 int llie_conv3x3_upmaps(int dtype, const void* in, const void* w, const float* bias, void* out, float* stats, int batch, int Hi, int Wi,
                         int C, llie_stream stream);
+int llie_conv3x3_upmaps_grid(int dtype, const void* in, const void* w, const float* bias, void* out, float* stats, int batch, int Hi,
+                             int Wi, int C, int workgroups, llie_stream stream);
+int llie_conv3x3_upmaps_workgroups(int batch, int Hi, int Wi, int C);
 int llie_conv3x3_upmaps_supported(int dtype, int Hi, int Wi, int C);
 int llie_linattn(int dtype, const void* qkv, float* kv_scratch, void* out, int batch, int N, int heads, llie_stream stream);
 int llie_linattn_splits(int N);
