@@ -828,7 +828,7 @@ hipError_t launch_pack_planes(int dtype, const float* x0, const float* x1, int c
   }
   return hipGetLastError();
 }
-// ---- input conv, data gradient: the transpose of init_conv_kernel (conv.hip) with the roles of patch and output exchanged.
+// ---- input conv, data gradient: the transpose of init_conv_kernel (conv_edge.hip) with the roles of patch and output exchanged.
 //   dx[b][ci][y][x] = sum_{ky,kx} sum_co g[b][y + 1 - ky][x + 1 - kx][co] * W[co][ci][ky][kx], zero outside the map
 // One thread = one pixel of a 16 x 16 tile and up to 8 input channels; the tile's 18 x 18 halo patch of g stands in LDS as fp32,
 // 32 channels of co at a time; the weights are the forward's table [ci * 9 + tap][C0], wave-uniform, so they come through the scalar

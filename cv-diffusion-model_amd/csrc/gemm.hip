@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "mfma_tile.h"
 
 namespace llie {
 
@@ -58,14 +59,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, f32x16 (&acc)[B
 #pragma unroll
   for (int pi = 0; pi < MI; ++pi) {
     if (pi) wg_barrier();  // previous pass fully read
-#pragma unroll
-    for (int j = 0; j < NI; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = wm * 32 + mfma_row(r, lane);
-        const int col = (wn * NI + j) * 32 + (lane & 31);
-        sC[row * CP + col] = acc[pi][j][r];
-      }
+    stage_acc_tile<CP>(sC, acc[pi], wm, wn, lane);
     wg_barrier();
 #pragma unroll
     for (int it = 0; it < (SROWS + RPP - 1) / RPP; ++it) {

@@ -376,7 +376,7 @@ struct Conv3Args {
 hipError_t launch_conv3x3(int dtype, const Conv3Args& a, hipStream_t s);
 int conv3x3_ntiles(int Ho, int Wo);
 //   the up-sampling conv (mode 1) from folded weights: the fixed bilinear x2 lives in per-phase 3x3 weights on the low-resolution
-//   input, so the kernel blends nothing (conv.hip: conv3x3_upfold_kernel).  Cin == Cout == C; `w` = the folded blob of
+//   input, so the kernel blends nothing (upconv.hip: conv3x3_upfold_kernel).  Cin == Cout == C; `w` = the folded blob of
 //   launch_upconv_fold: 64 sets of [Cout][Cin] T, phase p = 2 a + b for output pixels (2i + a, 2j + b):
 //     set p * 9 + r * 3 + s   interior tap (r, s) on the replicate-padded input
 //     set 36 + p * 3 + s      row-edge correction (already negated), first (a = 0) / last (a = 1) image row
@@ -386,7 +386,7 @@ int conv3x3_ntiles(int Ho, int Wo);
 bool conv3x3_upfold_ok(int dtype, int Hi, int Wi, int C);  // the kernel's contract: 2-byte dtype, Hi % 8 == 0, Wi % 16 == 0, C = 64 or a multiple of 128
 hipError_t launch_conv3x3_upfold(int dtype, const Conv3Args& a, hipStream_t s);
 int conv3x3_upfold_ntiles(int Ho, int Wo);
-//   the up-sampling conv (mode 1) from nine low-resolution tap maps, blended on chip (conv.hip: conv3x3_upmaps_kernel): a quarter of
+//   the up-sampling conv (mode 1) from nine low-resolution tap maps, blended on chip (upconv.hip: conv3x3_upmaps_kernel): a quarter of
 //   the multiply-adds.  Cin == Cout == C; `w` = the plain [9][C][C] T weights of launch_conv3x3 (no folded blob).
 //   stats: [B][conv3x3_ntiles(Ho, Wo)][2][C], four entries per low-resolution 8 x 16 tile: the first carries the sums, three are zero
 bool conv3x3_upmaps_ok(int dtype, int Hi, int Wi, int C);  // the kernel's contract: 2-byte dtype, Hi % 8 == 0, Wi % 16 == 0, C a multiple of 32

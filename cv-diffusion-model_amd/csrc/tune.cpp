@@ -37,10 +37,10 @@ static const KnobRow kKnobTable[] = {
   // 4 dwconv3x3 (h2), 8 project / attention GEMM outputs, 16 dense 3x3 conv outputs.  Values never change, only where lines live.
   {"nt_min_mb", SLOT(nt_min_mb), 1, 100, kAsGiven},
   {"nt_mask", SLOT(nt_mask), 1, 1, kAsGiven},
-  // Up-sampling convs from folded weights (conv.hip: conv3x3_upfold_kernel) wherever upconv_fold_supported();
+  // Up-sampling convs from folded weights (upconv.hip: conv3x3_upfold_kernel) wherever upconv_fold_supported();
   // llie_tune("upconv_fold", 0) restores conv3x3_kernel's mode 1, which blends the patch itself.
   {"upconv_fold", SLOT(upconv_fold), 1, 1, kOnOff},
-  // Up-sampling convs from nine low-resolution tap maps blended on chip (conv.hip: conv3x3_upmaps_kernel) wherever
+  // Up-sampling convs from nine low-resolution tap maps blended on chip (upconv.hip: conv3x3_upmaps_kernel) wherever
   // upconv_maps_supported(), which is asked first; llie_tune("upconv_maps", 0) leaves the choice to upconv_fold alone.
   {"upconv_maps", SLOT(upconv_maps), 1, 1, kOnOff},
   {"se_mfma", SLOT(se_mfma), 1, 1, kAsGiven},  // SE MLP of the wide blocks as two MFMA launches (small.hip: se_fc1_mfma / se_fc2_mfma); 0 = the row-parallel pair

@@ -383,7 +383,7 @@ def se_mlp_ref(sums, P, w1, b1, w2, b2, mean=None, hidden=None):
     return (m, ma), (h, ha), (g, g * (1 - g) * va + g)
 
 
-# ------------------------------------------------------------------------------------------------ llie_init_conv (conv.hip)
+# ------------------------------------------------------------------------------------------------ llie_init_conv (conv_edge.hip)
 def oihw_taps(w):
     """OIHW [O][I][3][3] -> tap-major [9][O][I] (tap = 3 ky + kx), float64"""
     return w.double().permute(2, 3, 0, 1).reshape(9, w.shape[0], w.shape[1])
@@ -403,7 +403,7 @@ def init_conv_ref(dtype, x0, x1, w, bias, mfma):
     return ref, ab, _ulp(ref, dtype)
 
 
-# ------------------------------------------------------------------------------------------------ llie_final_conv (conv.hip)
+# ------------------------------------------------------------------------------------------------ llie_final_conv (conv_edge.hip)
 def silu_operand(dtype, x, sc, sh, rounded):
     """The output head's activated operand [B][H][W][C]: z = fma(x, sc, sh) in fp32 (one rounding), a = z / (1 + exp(-z)).  The
     kernels evaluate it with __expf (v_exp_f32 on z log2(e): relative error (1.5 |z| + 2) 2^-24) and an IEEE division (VALU kernel) or

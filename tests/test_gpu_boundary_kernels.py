@@ -73,7 +73,7 @@ def _twice(call, names):
 
 
 # =============================================================================================
-# llie_init_conv (conv.hip): the VALU kernel on 16 x 16 tiles, the MFMA kernel on 8 x 32 tiles
+# llie_init_conv (conv_edge.hip): the VALU kernel on 16 x 16 tiles, the MFMA kernel on 8 x 32 tiles
 INIT_SPLITS = [(3, 3), (4, 4), (1, 2)]
 INIT_MAPS = {0: [(16, 16), (24, 40), (32, 48)], 1: [(8, 32), (24, 40), (16, 72), (32, 128)]}
 INIT_PARAMS = [(m, d, h, w, sp, co) for m in (0, 1) for d in (DTYPES if m == 0 else H2) for h, w in INIT_MAPS[m] for sp in INIT_SPLITS
@@ -121,7 +121,7 @@ def test_init_conv_vs_float64(dev, mfma, dtype, H, W, split, cout):
 
 
 # =============================================================================================
-# llie_final_conv (conv.hip): the VALU kernel, the MFMA kernel, and the MFMA kernel's fused scheduler step
+# llie_final_conv (conv_edge.hip): the VALU kernel, the MFMA kernel, and the MFMA kernel's fused scheduler step
 FINAL_MAPS = [(16, 16), (24, 40), (64, 64)]
 FINAL_PARAMS = [(m, d, h, w, c, co) for m in (0, 1) for d in (DTYPES if m == 0 else H2) for h, w in FINAL_MAPS for c in (32, 64, 96)
                 for co in (3, 4)]

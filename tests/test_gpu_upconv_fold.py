@@ -1,4 +1,4 @@
-"""The up-sampling conv from folded weights on the GPU (csrc/conv.hip: conv3x3_upfold_kernel; csrc/small.hip: upconv_fold_kernel;
+"""The up-sampling conv from folded weights on the GPU (csrc/upconv.hip: conv3x3_upfold_kernel; csrc/small.hip: upconv_fold_kernel;
 csrc/engine.h: upconv_fold_supported), through the C ABI and through the network.  The float64 fold and its identity are pinned in
 test_upconv_fold_host.py, whose helpers are reused here.  TH x TW = 8 x 16 is the kernel's low-resolution tile."""
 import functools

@@ -1,4 +1,4 @@
-"""The up-sampling conv from nine low-resolution tap maps on the GPU (csrc/conv.hip: conv3x3_upmaps_kernel; csrc/engine.h:
+"""The up-sampling conv from nine low-resolution tap maps on the GPU (csrc/upconv.hip: conv3x3_upmaps_kernel; csrc/engine.h:
 upconv_maps_supported), through the C ABI and through the network.  The identity and an emulation with the kernel's rounding
 points are pinned in test_upconv_maps_host.py.  TH x TW = 8 x 16 is the kernel's low-resolution tile."""
 import functools

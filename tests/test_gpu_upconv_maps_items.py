@@ -1,4 +1,4 @@
-"""The item loop of the up-sampling conv from nine tap maps (csrc/conv.hip: conv3x3_upmaps_kernel), and the rest of its contract.
+"""The item loop of the up-sampling conv from nine tap maps (csrc/upconv.hip: conv3x3_upmaps_kernel), and the rest of its contract.
 
 The kernel's grid is sized to the chip: min(items, compute units) workgroups, each working through items blockIdx.x, + gridDim.x,
 ...; one LDS region serves the operand buffers, then the maps, then the statistics scratch; the next item's first loads are issued

@@ -1,4 +1,4 @@
-"""The identity behind the folded up-sampling conv (csrc/small.hip: upconv_fold_kernel, csrc/conv.hip: conv3x3_upfold_kernel),
+"""The identity behind the folded up-sampling conv (csrc/small.hip: upconv_fold_kernel, csrc/upconv.hip: conv3x3_upfold_kernel),
 pinned in float64 without a GPU.
 
     y = conv3x3(up2(x), w, pad 1),   up2 = F.interpolate(scale_factor=2, mode="bilinear", align_corners=False)

@@ -1,4 +1,4 @@
-"""The identity behind the up-sampling conv from nine low-resolution tap maps (csrc/conv.hip: conv3x3_upmaps_kernel), pinned in
+"""The identity behind the up-sampling conv from nine low-resolution tap maps (csrc/upconv.hip: conv3x3_upmaps_kernel), pinned in
 float64 without a GPU.
 
     y = conv3x3(up2(x), w, pad 1),   up2 = F.interpolate(scale_factor=2, mode="bilinear", align_corners=False)

@@ -59,7 +59,7 @@ if __name__ == "__main__":
         XP = (16 * KS + 8) * 2
         report(f"expand_dw expand reads KS={KS}", [rd([(l & 31) * XP + 16 * (l >> 5) for l in range(64)])], 4)
     report("expand_dw h1 tile writes", [wr([(l & 31) * SHP + (chb * 4 + 2 * (l >> 5) + k) * 16 for l in range(64)]) for chb in range(2) for k in range(2)], 8)
-    # ---- conv3x3_kernel MODE 1 (conv.hip): A reads from the patch, 80-byte pixels, patch row = 18 pixels
+    # ---- conv3x3_kernel MODE 1 (conv.hip; row order: mfma_tile.h, tile_px): A reads from the patch, 80-byte pixels, patch row = 18 pixels
     for name, rot in (("conv3x3 up (TW=16) patch reads, plain rows (before)", 0), ("conv3x3 up (TW=16) patch reads, odd rows rotated (now)", 14)):
         v = []
         for tap in range(9):
