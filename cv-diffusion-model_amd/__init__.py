@@ -9,7 +9,7 @@ The directory name contains '-', so import it as `import cv_diffusion_model_amd`
 repository root) or `importlib.import_module("cv-diffusion-model_amd")`.
 """
 from .unet import (EfficientUNet, EfficientUNetConfig, create_efficient_unet, InvertedResidualBlock,
-                   LinearAttention, Downsample, Upsample, SqueezeExcitation)
+                   LinearAttention, StandardAttention, Downsample, Upsample, SqueezeExcitation)
 from .scheduler import LCMScheduler, LCMSchedulerOutput, LCMDenoisingLoop, get_lcm_timesteps
 from .ddim import ddim_timesteps, ddim_step_host, ddim_enhance_host
 from .pipeline import (LowLightDiffusion, LowLightDiffusionOutput, LowLightLCMDistillation, normalize_image,
@@ -34,7 +34,7 @@ from .trainer import (TrainingConfig, LowLightTrainer, train_model, make_lr_sche
                       comparison_grid_host)
 
 __all__ = [
-    "EfficientUNet", "EfficientUNetConfig", "create_efficient_unet", "InvertedResidualBlock", "LinearAttention", "SqueezeExcitation",
+    "EfficientUNet", "EfficientUNetConfig", "create_efficient_unet", "InvertedResidualBlock", "LinearAttention", "StandardAttention", "SqueezeExcitation",
     "Downsample", "Upsample", "LCMScheduler", "LCMSchedulerOutput", "LCMDenoisingLoop", "get_lcm_timesteps", "LowLightDiffusion",
     "LowLightDiffusionOutput", "LowLightLCMDistillation", "normalize_image", "denormalize_image", "shard_range", "enhance_sharded",
     "all_gather_batch", "all_reduce_gradients", "FusedAdamW", "FusedGradScaler", "TrainStep", "DistillStep", "grad_accumulate_array", "accumulation_windows", "register_model", "build_library", "library_path", "load_checkpoint", "extract_state_dict",

@@ -15,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libllie_hip.so")
 
 # enums of include/llie.h
 LLIE_F32, LLIE_F16, LLIE_BF16 = 0, 1, 2
-LLIE_UNET, LLIE_IRB, LLIE_ATTN, LLIE_DOWN, LLIE_UP, LLIE_SE = 0, 1, 2, 3, 4, 5
+LLIE_UNET, LLIE_IRB, LLIE_ATTN, LLIE_DOWN, LLIE_UP, LLIE_SE, LLIE_SOFTATTN = 0, 1, 2, 3, 4, 5, 6
 ERR_ARG, ERR_SHAPE, ERR_CONFIG, ERR_KEY, ERR_NOT_LOADED, ERR_WORKSPACE, ERR_NO_DEVICE = -1, -2, -3, -4, -5, -6, -7
 SAMPLER_LCM, SAMPLER_DDIM = 0, 1  # llie_step_coef.sampler
 
@@ -56,6 +56,7 @@ EXPORTS = [
     "llie_train_shape_ok", "llie_unet_train_forward_hw", "llie_aug_pair_u8_hw", "llie_aug_synth_u8_hw",
     "llie_tile_gather_u8_hw", "llie_tile_gather_f32_hw", "llie_tile_blend_u8_hw", "llie_tile_sync_step_hw", "llie_frame_max_pixels",
     "llie_unet_backward_dx", "llie_init_conv_dgrad",
+    "llie_softattn", "llie_softattn_backward", "llie_softattn_bwd_floats",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 PW_SIGMOID_BWD, PW_RELU6_BWD, PW_SILU_BWD, PW_SCALE = 0, 1, 2, 3  # llie_pointwise_kind
@@ -85,6 +86,7 @@ class Config(C.Structure):
         ("base_channels", C.c_int), ("channel_multipliers", C.c_int * 4), ("num_res_blocks", C.c_int),
         ("expansion_ratio", C.c_int), ("time_embed_dim", C.c_int), ("num_attention_heads", C.c_int),
         ("image_size", C.c_int), ("attention_resolutions", C.c_int * 2), ("allow_unpinned", C.c_int),
+        ("softmax_attention", C.c_int),  # appended: a zero-initialised struct keeps meaning LinearAttention
     ]
 
 
@@ -334,6 +336,10 @@ def lib() -> C.CDLL:
     L.llie_linattn_backward.argtypes = [ci, vp, vp, vp, vp, vp, i64, ci, ci, ci, vp]
     L.llie_linattn_dkv_floats.argtypes = [ci, ci, ci]
     L.llie_linattn_dkv_floats.restype = i64
+    L.llie_softattn.argtypes = [ci, vp, vp, vp, ci, ci, ci, vp]
+    L.llie_softattn_backward.argtypes = [ci, vp, vp, vp, vp, vp, vp, i64, ci, ci, ci, vp]
+    L.llie_softattn_bwd_floats.argtypes = [ci, ci, ci]
+    L.llie_softattn_bwd_floats.restype = i64
     L.llie_upsample2x_backward.argtypes = [ci, vp, vp, ci, ci, ci, ci, vp]
     L.llie_dilate2x.argtypes = [ci, vp, vp, ci, ci, ci, ci, vp]
     L.llie_linear_dx.argtypes = [ci, vp, i64, vp, vp, ci, ci, ci, vp, i64, vp]

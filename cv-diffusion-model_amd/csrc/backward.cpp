@@ -240,9 +240,57 @@ struct Back : Exec {
     join();
   }
 
+  // ---- StandardAttention: y = to_out(core(to_qkv(norm(x)))) + x
+  void softattn_bwd(const AttnRec& r) {
+    const AttnW& w = c->attns[r.w];
+    const int H = r.x.H, W = r.x.W, N = H * W, M = B * N, C = w.c, inner = w.inner;
+    const size_t dY = take_grad(r.y);  // fans out to to_out and, through the last gn_bwd's add0, to the residual
+    const Geo g11{H, W, H, W, 1, 0, 0};
+    // to_out
+    const size_t dao = alloc((size_t)M * inner * es());
+    gemm(dY, C, wptr(w.w_out_t), dao, inner, M, N);
+    {
+      GemmSeg sg{p(r.ao), inner, nullptr, nullptr, 0, ACT_NONE};
+      fork();
+      wgrad(dY, C, &sg, 1, inner, g11, gp(w.i_out), inner, 1, 0);
+    }
+    // attention core
+    const size_t dqkv = alloc((size_t)M * 3 * inner * es());
+    {
+      const size_t delta = alloc((size_t)B * w.heads * N * 4);
+      if (!dry) {
+        SoftAttnBwdArgs a{};
+        a.qkv = p(r.qkv); a.out = p(r.ao); a.dout = p(dao); a.lse = p<float>(r.lse); a.dqkv = p(dqkv); a.delta = p<float>(delta);
+        a.B = B; a.N = N; a.heads = w.heads;
+        chk(launch_softattn_bwd(dt, a, s));
+      }
+      ar->free(delta);
+    }
+    ar->free(dao);
+    // to_qkv
+    const size_t dxn = alloc((size_t)M * C * es());
+    gemm(dqkv, 3 * inner, wptr(w.w_qkv_t), dxn, C, M, N);
+    {
+      GemmSeg sg{p(r.x.off), C, p<float>(r.n1.as), p<float>(r.n1.ab), C, ACT_NONE};
+      fork();
+      wgrad(dqkv, 3 * inner, &sg, 1, C, g11, gp(w.i_qkv), C, 1, 0);
+    }
+    defer(dqkv);
+    // norm (no activation) + residual
+    const Coef k1 = gn_plan(r.x, nullptr);
+    bool e0 = false;
+    const size_t g0 = grad_of(r.x, e0);
+    gn_bwd(k1, dxn, r.x, nullptr, r.n1, ACT_NONE, w.ng, w.nb, gp(w.i_ng), gp(w.i_nb), nullptr, 0, nullptr, 0,
+           dY, true, g0, e0, 0, false, g0, 0);
+    ar->free(dxn);
+    defer(dY);  // to_out's weight gradient on the side stream reads it
+    join();
+  }
+
   // ---- LinearAttention
   void attn_bwd(const AttnRec& r) {
     const AttnW& w = c->attns[r.w];
+    if (w.soft) return softattn_bwd(r);
     const int H = r.x.H, W = r.x.W, N = H * W, M = B * N, C = w.c, inner = w.inner;
     const size_t dY = take_grad(r.y);
     const Geo g11{H, W, H, W, 1, 0, 0};

@@ -85,6 +85,7 @@ struct IrbW {
 };
 struct AttnW {
   int c, heads, inner;
+  bool soft;  // StandardAttention (softmax; no second norm: n2g / n2b unused, i_n2g = i_n2b = -1), else LinearAttention
   size_t ng, nb, w_qkv, w_out, n2g, n2b;
   size_t w_qkv_t, w_out_t;
   int i_ng, i_nb, i_qkv, i_out, i_n2g, i_n2b;  // parameter indices, as in IrbW
@@ -168,7 +169,8 @@ inline int pad32(int c) { return (c + 31) / 32 * 32; }
 // Training tape: what the forward pass leaves in the workspace for the backward pass (offsets).
 struct GnRec { size_t as = 0, ab = 0, mean = 0, rstd = 0; };
 struct IrbRec { int w; Tens x0, x1; bool cat; GnRec n1, n2; Tens h1; size_t h2, gate, sehid, semean; Tens y; };
-struct AttnRec { int w; Tens x; GnRec n1, n2; size_t qkv, kv, ao; int nsplit; Tens tmp, y; };
+// linear form: kv / nsplit, tmp (to_out's result before the second norm) and n2; softmax form: lse instead
+struct AttnRec { int w; Tens x; GnRec n1, n2; size_t qkv, kv, ao, lse; int nsplit; Tens tmp, y; };
 struct ConvRec { int w; bool up; Tens x, u, y; };
 struct TapeOp { int kind, idx; };  // kind: 0 irb, 1 attn, 2 conv; idx into the vectors below
 struct Tape {

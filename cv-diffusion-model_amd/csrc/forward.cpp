@@ -389,7 +389,35 @@ struct Run : Exec {
     return y;
   }
 
-  // LinearAttention.forward (efficient_unet.py:273-308)
+  // StandardAttention.forward after the qkv projection (efficient_unet.py:345-357): the fused softmax core, then to_out with the
+  // residual and the statistics slab of y in the GEMM's epilogue (the identity-residual epilogue of a block's project GEMM)
+  Tens softattn_tail(const AttnW& w, const Tens& x, size_t qkv, AttnRec& rec) {
+    const int H = x.H, W = x.W, N = H * W, M = B * N;
+    const size_t ao = ar->alloc((size_t)M * w.inner * es());
+    const size_t lse = tape ? ar->alloc((size_t)B * w.heads * N * 4) : 0;  // only the backward pass reads it
+    if (!dry) {
+      SoftAttnArgs a{};
+      a.qkv = p(qkv); a.out = p(ao); a.lse = tape ? p<float>(lse) : nullptr; a.B = B; a.N = N; a.heads = w.heads;
+      timed(LLIE_K_OTHER, (int64_t)M * 4 * w.inner * (int64_t)es(), [&] { return launch_softattn_fwd(dt, a, s); });
+    }
+    rel(qkv);
+    Tens y = new_tens(x.C, H, W, pw_gemm_ntiles(N));
+    if (!dry) {
+      GemmArgs g = gemm1(GemmSeg{p(ao), w.inner, nullptr, nullptr, 0, ACT_NONE}, wptr(w.w_out), p(y.off), p<float>(y.slab), M, x.C, w.inner, N);
+      g.res = p(x.off);
+      timed(LLIE_K_GEMM, ((int64_t)M * (2 * x.C + w.inner) + (int64_t)w.inner * x.C) * (int64_t)es(), [&] { return launch_pw_gemm(dt, g, s); });
+    }
+    rel(ao);
+    if (tape) {
+      rec.w = (int)(&w - c->attns.data());
+      rec.x = x; rec.qkv = qkv; rec.ao = ao; rec.lse = lse; rec.y = y;
+      tape->ops.push_back({1, (int)tape->attns.size()});
+      tape->attns.push_back(rec);
+    }
+    return y;
+  }
+
+  // LinearAttention.forward (efficient_unet.py:273-308); StandardAttention (:336-357) shares the norm and the qkv projection
   Tens attn(const AttnW& w, const Tens& x) {
     const int H = x.H, W = x.W, N = H * W, M = B * N;
     size_t as, ab;
@@ -402,6 +430,7 @@ struct Run : Exec {
       timed(LLIE_K_GEMM, ((int64_t)M * (x.C + 3 * w.inner) + 3LL * w.inner * x.C) * (int64_t)es(), [&] { return launch_pw_gemm(dt, g, s); });
     }
     rel(as); rel(ab);
+    if (w.soft) return softattn_tail(w, x, qkv, rec);
     const int nsplit = linattn_nsplit(N);
     const size_t kv = ar->alloc((size_t)nsplit * B * w.heads * 32 * 33 * 4);
     const size_t ao = ar->alloc((size_t)M * w.inner * es());
@@ -573,9 +602,10 @@ struct Run : Exec {
     const int P = H * W;
     const int split = (g.kind == LLIE_IRB) ? g.base_channels : 0;  // IRB: optional virtual-concat split point
     zbegin(H, W, [&](Run& d) { d.module(nullptr, nullptr, nullptr, H, W); });
-    Tens x0 = new_tens(split ? split : g.in_channels, H, W, P / 64);
+    const int xt = (P + 63) / 64;  // tiles of the conversion's statistics slab (P is a multiple of 64 for every kind but LLIE_SOFTATTN)
+    Tens x0 = new_tens(split ? split : g.in_channels, H, W, xt);
     Tens x1;
-    if (split) x1 = new_tens(g.in_channels - split, H, W, P / 64);
+    if (split) x1 = new_tens(g.in_channels - split, H, W, xt);
     if (!dry) {
       chk(launch_nchw_to_nhwc(dt, x, p(x0.off), p<float>(x0.slab), B, x0.C, P, g.in_channels, 0, s));
       if (split) chk(launch_nchw_to_nhwc(dt, x, p(x1.off), p<float>(x1.slab), B, x1.C, P, g.in_channels, split, s));
@@ -591,7 +621,7 @@ struct Run : Exec {
       out = irb(c->irbs[0], x0, split ? &x1 : nullptr, p<float>(film), F);
       rel(st); rel(film);
       if (tape) { tape->stemb = st; tape->film = film; }
-    } else if (g.kind == LLIE_ATTN) {
+    } else if (g.kind == LLIE_ATTN || g.kind == LLIE_SOFTATTN) {
       out = attn(c->attns[0], x0);
     } else if (g.kind == LLIE_SE) {
       // SqueezeExcitation.forward (efficient_unet.py:96-100): the 64-pixel (sum, sum of squares) slab of the layout

@@ -434,6 +434,25 @@ int llie_linattn_backward(int dtype, const void* qkv, const float* kv_scratch, c
   float* tot = dkv_scratch + (size_t)batch * heads * ((N + 63) / 64) * 32 * 33;
   return kerr("linattn_backward", launch_linattn_bwd(dtype, a, tot, hs(stream)));
 }
+int llie_softattn(int dtype, const void* qkv, void* out, float* lse_or_NULL, int batch, int N, int heads, llie_stream stream) {
+  if (!dtype_ok(dtype) || !qkv || !out || batch <= 0 || N <= 0 || heads <= 0) return LLIE_ERR_ARG;
+  SoftAttnArgs a{};
+  a.qkv = qkv; a.out = out; a.lse = lse_or_NULL; a.B = batch; a.N = N; a.heads = heads;
+  return kerr("softattn", launch_softattn_fwd(dtype, a, hs(stream)));
+}
+int64_t llie_softattn_bwd_floats(int batch, int N, int heads) {
+  if (batch <= 0 || N <= 0 || heads <= 0) return LLIE_ERR_ARG;
+  return (int64_t)batch * heads * N;  // delta per query
+}
+int llie_softattn_backward(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* scratch,
+                           int64_t scratch_floats, int batch, int N, int heads, llie_stream stream) {
+  if (!dtype_ok(dtype) || !qkv || !out || !dout || !lse || !dqkv || !scratch || batch <= 0 || N <= 0 || heads <= 0 ||
+      scratch_floats < llie_softattn_bwd_floats(batch, N, heads))
+    return LLIE_ERR_ARG;
+  SoftAttnBwdArgs a{};
+  a.qkv = qkv; a.out = out; a.dout = dout; a.lse = lse; a.dqkv = dqkv; a.delta = scratch; a.B = batch; a.N = N; a.heads = heads;
+  return kerr("softattn_backward", launch_softattn_bwd(dtype, a, hs(stream)));
+}
 int llie_upsample2x_backward(int dtype, const void* dout, void* din, int batch, int Hi, int Wi, int C, llie_stream stream) {
   if (!dtype_ok(dtype) || !dout || !din || batch <= 0 || Hi <= 0 || Wi <= 0 || C <= 0 || C % (dtype == 0 ? 4 : 8)) return LLIE_ERR_ARG;
   return kerr("upsample2x_backward", launch_upsample2x_bwd(dtype, dout, din, batch, Hi, Wi, C, hs(stream)));

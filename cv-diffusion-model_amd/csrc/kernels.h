@@ -410,6 +410,22 @@ int linattn_nsplit(int N);
 hipError_t launch_linattn_kv(int dtype, const AttnArgs& a, hipStream_t s);
 hipError_t launch_linattn_out(int dtype, const AttnArgs& a, hipStream_t s);
 
+// Softmax attention core (efficient_unet.py:349-353) in flash form on MFMA (softattn.hip), same qkv / out layout as AttnArgs.
+struct SoftAttnArgs {
+  const void* qkv; void* out;  // [B][N][3 * inner], [B][N][inner] T; dim_head = 32, scale = 32^-0.5
+  float* lse;                  // [B][heads][N] log-sum-exp of the scaled logits, or null (inference)
+  int B, N, heads;
+};
+hipError_t launch_softattn_fwd(int dtype, const SoftAttnArgs& a, hipStream_t s);
+// dqkv of the core given d(out): a dQ kernel per query tile (it leaves delta = rowsum(dout * out) for the second), then a
+// dK / dV kernel per key tile; P is recomputed from lse.  No atomics.
+struct SoftAttnBwdArgs {
+  const void* qkv; const void* out; const void* dout; const float* lse; void* dqkv;
+  float* delta;                // [B][heads][N] scratch
+  int B, N, heads;
+};
+hipError_t launch_softattn_bwd(int dtype, const SoftAttnBwdArgs& a, hipStream_t s);
+
 // y = x*as + ab (+ res), NHWC rows [M][C]; optional stats slab of y (tiles of 64 rows).
 struct AffineAddArgs {
   const void* x; const float* as; const float* ab; const void* res; void* y; float* stats;

@@ -136,14 +136,20 @@ struct Builder {
     }
     pending_skip.clear();
   }
-  int add_attn(const std::string& p, int ch, int heads) {
+  // soft: StandardAttention (efficient_unet.py:329-332: to_out is a bare conv, no second norm), else LinearAttention (:263-269)
+  int add_attn(const std::string& p, int ch, int heads, bool soft) {
     if (ch % 32) bad = true;
     AttnW w{};
-    w.c = ch; w.heads = heads; w.inner = heads * 32;
+    w.c = ch; w.heads = heads; w.inner = heads * 32; w.soft = soft;
     w.ng = f32(p + ".norm.weight", ch, 0, &w.i_ng); w.nb = f32(p + ".norm.bias", ch, 0, &w.i_nb);
     w.w_qkv = mat(p + ".to_qkv.weight", 3 * w.inner, ch, &w.i_qkv, &w.w_qkv_t);
-    w.w_out = mat(p + ".to_out.0.weight", ch, w.inner, &w.i_out, &w.w_out_t);
-    w.n2g = f32(p + ".to_out.1.weight", ch, 0, &w.i_n2g); w.n2b = f32(p + ".to_out.1.bias", ch, 0, &w.i_n2b);
+    w.i_n2g = w.i_n2b = -1;
+    if (soft) {
+      w.w_out = mat(p + ".to_out.weight", ch, w.inner, &w.i_out, &w.w_out_t);
+    } else {
+      w.w_out = mat(p + ".to_out.0.weight", ch, w.inner, &w.i_out, &w.w_out_t);
+      w.n2g = f32(p + ".to_out.1.weight", ch, 0, &w.i_n2g); w.n2b = f32(p + ".to_out.1.bias", ch, 0, &w.i_n2b);
+    }
     c->attns.push_back(w);
     return (int)c->attns.size() - 1;
   }
@@ -197,6 +203,8 @@ int build_unet(llie_ctx* c) {
   // GroupNorm(min(32,C), C) must be constructible for every site (efficient_unet.py:170-171,263,528) -- unless the
   // caller opted into the unpinned variants (allow_unpinned: groups = largest divisor <= 32, channels zero-padded)
   auto gn_ok = [](int x) { return x >= 32 && x % 32 == 0; };
+  if (g.softmax_attention != 0 && g.softmax_attention != 1) return LLIE_ERR_ARG;
+  const bool soft = g.softmax_attention != 0;
   if (g.allow_unpinned) {
     // what the padding scheme needs: the first segment of every virtual concat and every attention input unpadded
     for (int l = 1; l < 4; ++l)
@@ -246,7 +254,7 @@ int build_unet(llie_ctx* c) {
       c->enc[l].push_back({0, b.add_irb(p, r == 0 ? in_ch : ch[l], ch[l], T, e)});
       if (is_attn_res(res)) {
         const std::string pa = "encoder_blocks." + std::to_string(l) + "." + std::to_string(k++);
-        c->enc[l].push_back({1, b.add_attn(pa, ch[l], g.num_attention_heads)});
+        c->enc[l].push_back({1, b.add_attn(pa, ch[l], g.num_attention_heads, soft)});
       }
     }
     in_ch = ch[l];
@@ -254,7 +262,7 @@ int build_unet(llie_ctx* c) {
   }
   for (int l = 0; l < 3; ++l) c->downs.push_back(b.add_conv3("downsamplers." + std::to_string(l) + ".down", ch[l]));
   c->mid.push_back({0, b.add_irb("mid_block1", ch[3], ch[3], T, e)});
-  c->mid.push_back({1, b.add_attn("mid_attn", ch[3], g.num_attention_heads)});
+  c->mid.push_back({1, b.add_attn("mid_attn", ch[3], g.num_attention_heads, soft)});
   c->mid.push_back({0, b.add_irb("mid_block2", ch[3], ch[3], T, e)});
   c->dec.assign(4, {});
   for (int l = 0; l < 4; ++l) {
@@ -265,7 +273,7 @@ int build_unet(llie_ctx* c) {
       c->dec[l].push_back({0, b.add_irb(p, r == 0 ? in_ch + out : out, out, T, e, r == 0 ? in_ch : 0)});
       if (is_attn_res(res)) {
         const std::string pa = "decoder_blocks." + std::to_string(l) + "." + std::to_string(k++);
-        c->dec[l].push_back({1, b.add_attn(pa, out, g.num_attention_heads)});
+        c->dec[l].push_back({1, b.add_attn(pa, out, g.num_attention_heads, soft)});
       }
     }
     in_ch = out;
@@ -302,7 +310,11 @@ int build_module(llie_ctx* c) {
       break;
     case LLIE_ATTN:
       if (!gn_ok(g.in_channels)) return LLIE_ERR_CONFIG;
-      b.add_attn("", g.in_channels, g.num_attention_heads);
+      b.add_attn("", g.in_channels, g.num_attention_heads, false);
+      break;
+    case LLIE_SOFTATTN:
+      if (!gn_ok(g.in_channels) || g.num_attention_heads < 1) return LLIE_ERR_CONFIG;
+      b.add_attn("", g.in_channels, g.num_attention_heads, true);
       break;
     case LLIE_SE: {  // efficient_unet.py:85-94: squeezed = max(1, int(C * 0.25)), both 1x1 convs with bias
       if (g.in_channels % 32) return LLIE_ERR_CONFIG;
@@ -354,6 +366,11 @@ int llie::check_ready(const llie_ctx* c) {
 
 int llie::shape_ok(const llie_ctx* c, int H, int W) {
   const int k = c->cfg.kind;
+  if (k == LLIE_SOFTATTN) {  // any map of at least 64 pixels, the smallest the network itself runs its GEMMs and norms on
+    if (H >= 1 && W >= 1 && (long long)H * W >= 64 && (long long)H * W <= (1 << 24)) return LLIE_OK;
+    set_err("unsupported spatial size %dx%d", H, W);
+    return LLIE_ERR_SHAPE;
+  }
   int minside = 8;
   if (k == LLIE_DOWN) minside = 16;
   if (H % 8 || W % 8 || H < minside || W < minside || (H * W) % 64) {
@@ -390,6 +407,10 @@ const char* llie_version(void) { return "llie-hip 0.1 (gfx950)"; }
 int llie_create(const llie_config* cfg, llie_ctx** out) {
   if (!cfg || !out) return LLIE_ERR_ARG;
   if (cfg->compute_dtype < 0 || cfg->compute_dtype > 2) { set_err("bad compute_dtype"); return LLIE_ERR_ARG; }
+  if (cfg->kind == LLIE_UNET && cfg->softmax_attention && cfg->allow_unpinned) {
+    set_err("softmax_attention together with allow_unpinned (the zero-padded tiny / base variants) is not supported");
+    return LLIE_ERR_CONFIG;
+  }
   llie_ctx* c = new llie_ctx();
   c->cfg = *cfg;
   c->dt = cfg->compute_dtype;
@@ -584,6 +605,13 @@ static void count_blocks(const llie_ctx* c, const std::vector<Block>& bl, int64_
       flops += 2LL * P * ((int64_t)w.cin * w.hid + 9LL * w.hid + (int64_t)w.hid * w.cout + (w.skip ? (int64_t)w.cin * w.cout : 0));
     } else {
       const AttnW& w = c->attns[b.idx];
+      if (w.soft) {
+        // x read by the qkv GEMM and as the residual, y written; the core reads qkv and writes out, which the GEMMs wrote / read:
+        // 3C + 8 inner elements per pixel; the core's two products are 4 N^2 inner flops per image
+        elems += (3LL * w.c + 8LL * w.inner) * P;
+        flops += 2LL * P * ((int64_t)w.c * 3 * w.inner + (int64_t)w.inner * w.c) + 4LL * P * P * w.inner;
+        continue;
+      }
       elems += 6LL * w.c * P;
       flops += 2LL * P * ((int64_t)w.c * 3 * w.inner + (int64_t)w.inner * w.c + 2LL * w.inner * 32);
     }

@@ -811,7 +811,8 @@ hipError_t launch_affine_add(int dtype, const AffineAddArgs& a, hipStream_t s) {
 }
 
 // =============================================================================================
-// fp32 NCHW <-> NHWC T at the single-operator boundary.  Block = 64 pixels x 32 channels through LDS.
+// fp32 NCHW <-> NHWC T at the single-operator boundary.  Block = 64 pixels x 32 channels through LDS; pixels past P (the last
+// block of a map whose pixel count is no multiple of 64) are read as zeros, counted as zeros in the statistics and not stored.
 template <typename T>
 __global__ void __launch_bounds__(256) nchw_to_nhwc_kernel(const float* x, T* y, float* stats, int C, int P, int Csrc,
                                                            int coff) {
@@ -820,18 +821,18 @@ __global__ void __launch_bounds__(256) nchw_to_nhwc_kernel(const float* x, T* y,
   const int b = blockIdx.y, p0 = blockIdx.x * 64, c0 = blockIdx.z * 32;
   for (int i = tid; i < 32 * 64; i += 256) {
     const int c = i >> 6, p = i & 63;
-    sm[c * 65 + p] = x[((size_t)b * Csrc + coff + c0 + c) * P + p0 + p];
+    sm[c * 65 + p] = p0 + p < P ? x[((size_t)b * Csrc + coff + c0 + c) * P + p0 + p] : 0.f;
   }
   wg_barrier();
   for (int i = tid; i < 32 * 64; i += 256) {
     const int p = i >> 5, c = i & 31;
     const T v = (T)sm[c * 65 + p];
-    y[((size_t)b * P + p0 + p) * C + c0 + c] = v;
+    if (p0 + p < P) y[((size_t)b * P + p0 + p) * C + c0 + c] = v;
     sm[c * 65 + p] = (float)v;  // element owned by this thread in this phase: no race
   }
   if (stats) {
     wg_barrier();
-    const int ntiles = P / 64, tile = blockIdx.x;
+    const int ntiles = (P + 63) / 64, tile = blockIdx.x;
     if (tid < 32) {
       float s1 = 0.f, s2 = 0.f;
       for (int p = 0; p < 64; ++p) {
@@ -851,18 +852,18 @@ __global__ void __launch_bounds__(256) nhwc_to_nchw_kernel(const T* x, float* y,
   const int b = blockIdx.y, p0 = blockIdx.x * 64, c0 = blockIdx.z * 32;
   for (int i = tid; i < 32 * 64; i += 256) {
     const int p = i >> 5, c = i & 31;
-    sm[c * 65 + p] = (float)x[((size_t)b * P + p0 + p) * C + c0 + c];
+    sm[c * 65 + p] = p0 + p < P ? (float)x[((size_t)b * P + p0 + p) * C + c0 + c] : 0.f;
   }
   wg_barrier();
   for (int i = tid; i < 32 * 64; i += 256) {
     const int c = i >> 6, p = i & 63;
-    y[((size_t)b * Cdst + coff + c0 + c) * P + p0 + p] = sm[c * 65 + p];
+    if (p0 + p < P) y[((size_t)b * Cdst + coff + c0 + c) * P + p0 + p] = sm[c * 65 + p];
   }
 }
 hipError_t launch_nchw_to_nhwc(int dtype, const float* x, void* y, float* stats, int B, int C, int P, int Csrc, int coff,
                                hipStream_t s) {
-  if (P % 64 || C % 32) return hipErrorInvalidValue;
-  dim3 grid(P / 64, B, C / 32);
+  if (P < 1 || C % 32) return hipErrorInvalidValue;
+  dim3 grid((P + 63) / 64, B, C / 32);
   switch (dtype) {
     case 0: hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, grid, dim3(256), 0, s, x, (float*)y, stats, C, P, Csrc, coff); break;
     case 1: hipLaunchKernelGGL(nchw_to_nhwc_kernel<half_t>, grid, dim3(256), 0, s, x, (half_t*)y, stats, C, P, Csrc, coff); break;
@@ -873,8 +874,8 @@ hipError_t launch_nchw_to_nhwc(int dtype, const float* x, void* y, float* stats,
 }
 hipError_t launch_nhwc_to_nchw(int dtype, const void* x, float* y, int B, int C, int P, hipStream_t s, int Cdst, int coff) {
   if (Cdst <= 0) Cdst = C;
-  if (P % 64 || C % 32) return hipErrorInvalidValue;
-  dim3 grid(P / 64, B, C / 32);
+  if (P < 1 || C % 32) return hipErrorInvalidValue;
+  dim3 grid((P + 63) / 64, B, C / 32);
   switch (dtype) {
     case 0: hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, grid, dim3(256), 0, s, (const float*)x, y, C, P, Cdst, coff); break;
     case 1: hipLaunchKernelGGL(nhwc_to_nchw_kernel<half_t>, grid, dim3(256), 0, s, (const half_t*)x, y, C, P, Cdst, coff); break;

@@ -26,11 +26,34 @@ def extract_state_dict(obj) -> Dict[str, torch.Tensor]:
     raise ValueError("unrecognised checkpoint layout: expected a state_dict or a dict with 'model_state_dict'")
 
 
+def attention_kind(keys) -> str:
+    """"softmax" when the keys are a StandardAttention network's (`...to_out.weight`), "linear" for LinearAttention's
+    (`...to_out.0.weight`), "" when they hold no attention module."""
+    for k in keys:
+        if k.endswith(".to_out.weight") or k == "to_out.weight":
+            return "softmax"
+        if k.endswith(".to_out.0.weight") or k == "to_out.0.weight":
+            return "linear"
+    return ""
+
+
+def check_attention_kind(model: torch.nn.Module, state_dict) -> None:
+    """A checkpoint of the other attention kind is refused by name, with the flag that selects it (scripts: --attention), before
+    load_state_dict would list every attention key as missing or unexpected."""
+    have, want = attention_kind(state_dict.keys()), attention_kind(model.state_dict().keys())
+    if have and want and have != want:
+        raise ValueError(f"the checkpoint holds a {have}-attention network (use_linear_attention={have == 'linear'}) but the model "
+                         f"was built with {want} attention: pass --attention {have} "
+                         f"(create_efficient_unet(..., use_linear_attention={have == 'linear'}))")
+
+
 def load_checkpoint(model: torch.nn.Module, path: str, map_location="cpu") -> dict:
     """torch.load with weights_only=True (nothing from the file is executed), then load_state_dict.
     Returns the non-tensor metadata of a trainer checkpoint (epoch, global_step, ...) if present."""
     obj = torch.load(path, map_location=map_location, weights_only=True)
-    model.load_state_dict(extract_state_dict(obj))
+    sd = extract_state_dict(obj)
+    check_attention_kind(model, sd)
+    model.load_state_dict(sd)
     if isinstance(obj, dict) and "model_state_dict" in obj:
         return {k: v for k, v in obj.items() if k in ("epoch", "global_step", "best_val_loss")}
     return {}

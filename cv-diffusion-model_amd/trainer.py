@@ -526,6 +526,7 @@ class LowLightTrainer:
         self.epoch = ckpt["epoch"] + 1
         self.global_step = ckpt["global_step"]
         self.best_val_loss = ckpt["best_val_loss"]
+        hostio.check_attention_kind(self.model, ckpt["model_state_dict"])
         self.model.load_state_dict(ckpt["model_state_dict"])
         self.optimizer.load_state_dict(ckpt["optimizer_state_dict"])
         self.scheduler.load_state_dict(ckpt["scheduler_state_dict"])

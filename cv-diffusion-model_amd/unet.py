@@ -2,7 +2,7 @@
 
 Same names, constructor arguments, `state_dict` keys/shapes and error behaviour as
 `src/models/efficient_unet.py` of the reference (EfficientUNetConfig :24-57, EfficientUNet :387-628,
-create_efficient_unet :631-692, InvertedResidualBlock :134-236, LinearAttention :239-308,
+create_efficient_unet :631-692, InvertedResidualBlock :134-236, LinearAttention :239-308, StandardAttention :311-357,
 Downsample :360-372, Upsample :375-384) -- but no layer here computes anything in PyTorch: the
 modules only *hold* the parameters (so `.state_dict()`, `.parameters()`, `.to()`, EMA and optimisers
 work as usual) and `forward` hands raw device pointers to the C ABI.  There is no CPU fallback.
@@ -375,6 +375,20 @@ class LinearAttention(_NativeModule):
         return self._run_module(x, None, lambda h, w: (self.channels, h, w))
 
 
+class StandardAttention(_NativeModule):
+    """efficient_unet.py:311-357 (dim_head fixed at 32): GroupNorm, to_qkv, softmax(q k^T / sqrt(32)) v per head, to_out, residual.
+    The core is one fused kernel (csrc/softattn.hip); the N x N attention matrix is never stored."""
+
+    def __init__(self, channels: int, num_heads: int = 4, dim_head: int = 32):
+        if dim_head != 32:
+            raise NotImplementedError("dim_head is 32 everywhere in the reference network")
+        super().__init__(_module_cfg(N.LLIE_SOFTATTN, channels, channels, heads=num_heads))
+        self.channels = channels
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self._run_module(x, None, lambda h, w: (self.channels, h, w))
+
+
 class Downsample(_NativeModule):
     """efficient_unet.py:360-372 (use_conv=True branch: dense 3x3, stride 2, pad 1, bias)."""
 
@@ -419,8 +433,7 @@ class EfficientUNet(_NativeModule):
     """efficient_unet.py:387-628: same state_dict (321 keys for small@256), forward(x, timestep)."""
 
     def __init__(self, config: EfficientUNetConfig):
-        if not config.use_linear_attention or not config.use_se or not config.quantization_friendly \
-                or config.dropout != 0.0 or config.se_ratio != 0.25:
+        if not config.use_se or not config.quantization_friendly or config.dropout != 0.0 or config.se_ratio != 0.25:
             raise NotImplementedError("only the options used by the reference's variants are supported")
         if len(config.channel_multipliers) != 4 or len(config.attention_resolutions) != 2:
             raise NotImplementedError("4 resolution levels and 2 attention resolutions, like every reference variant")
@@ -434,6 +447,8 @@ class EfficientUNet(_NativeModule):
         c.image_size = config.image_size
         c.attention_resolutions[0], c.attention_resolutions[1] = config.attention_resolutions
         c.allow_unpinned = int(bool(config.allow_unpinned_groupnorm))
+        # use_linear_attention=False: every attention site is a StandardAttention (efficient_unet.py:447-455, 473-474, 509-517)
+        c.softmax_attention = int(not config.use_linear_attention)
         super().__init__(c)
         self.config = config
 

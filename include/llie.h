@@ -52,7 +52,8 @@ enum llie_kind {
   LLIE_ATTN = 2,   /* LinearAttention                    efficient_unet.py:239-308 */
   LLIE_DOWN = 3,   /* Downsample (3x3 stride-2 conv)     efficient_unet.py:360-372 */
   LLIE_UP = 4,     /* Upsample (bilinear x2 + 3x3 conv)  efficient_unet.py:375-384 */
-  LLIE_SE = 5      /* SqueezeExcitation (in_channels = C) efficient_unet.py:79-100; forward only */
+  LLIE_SE = 5,     /* SqueezeExcitation (in_channels = C) efficient_unet.py:79-100; forward only */
+  LLIE_SOFTATTN = 6 /* StandardAttention                  efficient_unet.py:311-357 */
 };
 
 /* Mirrors EfficientUNetConfig (efficient_unet.py:24-57) for LLIE_UNET; for the single-operator kinds
@@ -74,6 +75,9 @@ typedef struct llie_config {
                              fail with LLIE_ERR_CONFIG like the reference's ValueError.  1: build them with the
                              documented deviation groups = largest divisor of C that is <= 32 (no reference output
                              exists to pin this: parity-unpinned; inference only) */
+  int softmax_attention;  /* UNET: 0 = every attention site is a LinearAttention (use_linear_attention=True, the default of the
+                             reference); 1 = a StandardAttention (softmax; efficient_unet.py:311-357, keys norm / to_qkv / to_out).
+                             Together with allow_unpinned: LLIE_ERR_CONFIG */
 } llie_config;
 
 /* LCM scheduler coefficients for one step (host values; computed by the host-side scheduler from the
@@ -142,8 +146,9 @@ int llie_unet_forward(llie_ctx* ctx, const float* latents, const float* cond, co
                       llie_stream stream);
 
 /* Frame mode: the network, with the module tree its image_size fixed (attention placement, state_dict), run at a frame's own
- * H x W.  The denoiser is fully convolutional and its attention linear in the pixel count, so nothing but these rules ties it to
- * image_size.  Inference only.  The entry points without _hw are these at H = W = image_size.
+ * H x W.  The denoiser is fully convolutional and its attention takes any number of tokens (the linear form at a cost linear in the pixel
+ * count, the softmax form of softmax_attention = 1 at a quadratic one, in flash form: no N x N matrix is stored), so nothing but
+ * these rules ties it to image_size.  Inference only.  The entry points without _hw are these at H = W = image_size.
  *   llie_frame_shape_ok (host only, no GPU needed): LLIE_OK, or LLIE_ERR_SHAPE (llie_last_error names the rule) unless
  *       - height and width are multiples of 8 and at least 64 (three stride-2 levels, each restored by a x2 up-sampling);
  *       - batch <= 65535;
@@ -696,6 +701,12 @@ int llie_pw_gemm_dot(int dtype, const llie_gemm_seg* segs, int nseg, const void*
  * llie_linattn_backward: gradient dqkv [batch][N][3 * 32 heads] of llie_linattn w.r.t. its qkv, given d(out); kv_scratch: what
  *   llie_linattn left there for the same qkv; dkv_scratch: llie_linattn_dkv_floats floats (the per-64-position partials
  *   [batch][heads][ceil(N/64)][32][33], then their sum).
+ * llie_softattn: StandardAttention core (:349-353), out = softmax(q k^T / sqrt(32)) v per head, on the qkv layout of llie_linattn
+ *   ([batch][N][3 * 32 heads], q | k | v head-major) -> out [batch][N][32 heads]; fused (flash form) on MFMA, any N >= 1; lse_or_NULL:
+ *   [batch][heads][N] fp32 log-sum-exp of the scaled logits, which llie_softattn_backward needs.  Bitwise reproducible, and an
+ *   image's result does not depend on the batch it is in.
+ * llie_softattn_backward: dqkv [batch][N][3 * 32 heads] given d(out), with out and lse as llie_softattn left them; scratch:
+ *   llie_softattn_bwd_floats floats (delta = rowsum(dout * out) per query).  No atomics: bitwise reproducible, batch-invariant.
  * llie_upsample2x_backward: adjoint of bilinear x2 (align_corners=False): [batch][2Hi][2Wi][C] -> [batch][Hi][Wi][C];
  *   llie_dilate2x: out[2y][2x] = in[y][x], zero elsewhere.  C a multiple of 4 (fp32) or 8.
  * llie_linear_dx: dx[b][k] = sum_r dy[b * dy_stride + r] * w[r][k] (w [R][Kc] of the type wdtype, dx fp32); scratch (or NULL):
@@ -727,6 +738,10 @@ int64_t llie_groupnorm_backward_scratch_floats(int batch, int C, int pixels);
 int llie_linattn_backward(int dtype, const void* qkv, const float* kv_scratch, const void* dout, void* dqkv, float* dkv_scratch,
                           int64_t dkv_floats, int batch, int N, int heads, llie_stream stream);
 int64_t llie_linattn_dkv_floats(int batch, int N, int heads);
+int llie_softattn(int dtype, const void* qkv, void* out, float* lse_or_NULL, int batch, int N, int heads, llie_stream stream);
+int llie_softattn_backward(int dtype, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, float* scratch,
+                           int64_t scratch_floats, int batch, int N, int heads, llie_stream stream);
+int64_t llie_softattn_bwd_floats(int batch, int N, int heads);
 int llie_upsample2x_backward(int dtype, const void* dout, void* din, int batch, int Hi, int Wi, int C, llie_stream stream);
 int llie_dilate2x(int dtype, const void* in, void* out, int batch, int Hi, int Wi, int C, llie_stream stream);
 int llie_linear_dx(int wdtype, const float* dy, int64_t dy_stride, const void* w, float* dx, int batch, int R, int Kc, float* scratch,

@@ -56,6 +56,8 @@ def parse_args(argv=None):
     p.add_argument("--tile_size", type=str, default=None, metavar="{auto|HxW}",
                    help="with --full_resolution [tiled]: tiles of H x W run as frames instead of image_size squares; auto = the "
                         "fewest such tiles under the engine's size cap")
+    p.add_argument("--attention", type=str, default="linear", choices=["linear", "softmax"],
+                   help="attention of the network the checkpoint holds (softmax: use_linear_attention=False)")
     args = p.parse_args(argv)
     if args.full_resolution == "frame" and (args.tile_overlap is not None or args.tile_batch != 32 or args.tile_size is not None):
         p.error("--full_resolution frame and --tile_overlap / --tile_batch / --tile_size exclude each other")

@@ -35,6 +35,9 @@ def parse_args(argv=None):
     p.add_argument("--format", type=str, default="pytorch", choices=["pytorch", "onnx", "tflite"])
     p.add_argument("--variant", type=str, default="small")
     p.add_argument("--image_size", type=int, default=256)
+    p.add_argument("--attention", type=str, default="linear", choices=["linear", "softmax"],
+                   help="attention of the network the checkpoint holds: LinearAttention (default) or StandardAttention "
+                        "(use_linear_attention=False)")
     p.add_argument("--num_steps", type=int, default=4)
     p.add_argument("--device", type=str, default="cuda" if torch.cuda.is_available() else "cpu")
     p.add_argument("--dtype", type=str, default="fp32", choices=["fp32", "fp16", "bf16"], help="engine precision (extension)")
@@ -81,7 +84,10 @@ def parse_args(argv=None):
 def load_model(args):
     if args.format != "pytorch":
         raise SystemExit(f"--format {args.format}: exported-model runtimes are outside this engine's scope; use --format pytorch")
-    model = M.LowLightDiffusion(unet_variant=args.variant, image_size=args.image_size, num_inference_steps=4,
+    unet = None
+    if getattr(args, "attention", "linear") == "softmax":
+        unet = M.create_efficient_unet(args.variant, args.image_size, in_channels=6, use_linear_attention=False)
+    model = M.LowLightDiffusion(unet=unet, unet_variant=args.variant, image_size=args.image_size, num_inference_steps=4,
                                 compute_dtype=args.dtype)
     if args.checkpoint:
         hostio.load_checkpoint(model, args.checkpoint)

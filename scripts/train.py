@@ -50,6 +50,8 @@ def build_parser() -> argparse.ArgumentParser:
     # Model
     p.add_argument("--variant", type=str, default="small", choices=["tiny", "small", "base", "large"], help="Model variant")
     p.add_argument("--image_size", type=int, default=256, help="Image size")
+    p.add_argument("--attention", type=str, default="linear", choices=["linear", "softmax"],
+                   help="attention of the network: LinearAttention (default) or StandardAttention (use_linear_attention=False)")
     p.add_argument("--num_steps", type=int, default=4, help="LCM inference steps")
     # Training
     p.add_argument("--epochs", type=int, default=100, help="Number of epochs")
@@ -144,7 +146,10 @@ def main(argv=None) -> int:
         print(f"  Val batches: {len(val_loader)}")
 
     torch.manual_seed(args.seed)  # the initial weights
-    model = M.LowLightDiffusion(unet_variant=args.variant, image_size=args.image_size, num_inference_steps=args.num_steps)
+    unet = None
+    if args.attention == "softmax":
+        unet = M.create_efficient_unet(args.variant, args.image_size, in_channels=6, use_linear_attention=False)
+    model = M.LowLightDiffusion(unet=unet, unet_variant=args.variant, image_size=args.image_size, num_inference_steps=args.num_steps)
     model = model.to(train_loader.store.device)
     size = model.get_model_size()
     print(f"  Parameters: {size['num_params']:,}")
