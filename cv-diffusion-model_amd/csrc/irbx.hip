@@ -389,30 +389,94 @@ struct IrbxStamps {
   }
 };
 
-// ---- per-workgroup constants: depthwise weights (packed T), affine tables of this image
-// GATEW: the image's SE gate is part of the staged depthwise weights; gate_s: where it is staged as a table [Chid], or null
-template <typename T, int KS, bool GATEW>
+// ---- per-workgroup constants: depthwise weights (packed T), affine tables of this image, in ONE memory round trip.  A workgroup
+// with a short run of tiles (one tile at B = 16 on the 128 x 128 maps) does not amortise its prologue, and 2048 - 4096 workgroups
+// per launch repeat it: as a loop over the 10 Chid weight slots -- a division by Chid, one or two loads, a wait, one 16-bit LDS
+// write per iteration -- the staging alone was 5 / 10 / 15 dependent round trips per workgroup (profiles/r28/README.md).
+// Chid = 64 KS (irbx_supported), so every trip count is known here and a thread owns fixed channels: tid & 127 and a share of the
+// tap pairs at 128 channels (threads 0..127 pairs 0..2, threads 128..255 pairs 3..4), tid at 256, tid and tid + 256 at 384.  All
+// loads of a thread go out before the first value is used -- its weights, ONE gate per channel, its table entries -- and none
+// is predicated: a thread without a second channel, or past tap 8, loads from a clamped address and writes nothing (hipcc counts
+// unpredicated loads exactly; the callers' x halo and W1 loads, issued before these, complete under the same wait).
+// GATEW: the image's SE gate is part of the staged depthwise weights; GTAB: it is staged as a table [Chid] at gate_s
+template <typename T, int KS, bool GATEW, bool GTAB>
 __device__ __forceinline__ void irbx_stage_constants(const IrbxArgs& a, const int b, const int tid, T* wds, float* aff2, float* aff1,
                                                      float* gate_s, unsigned char* sX) {
-  constexpr int K = 16 * KS, XP = (K + 8) * 2;
+  constexpr int K = 16 * KS, XP = (K + 8) * 2, Chid = 64 * KS;
+  constexpr bool SPLIT = Chid < 256;                // two threads per channel
+  constexpr int NCH = SPLIT ? 1 : (Chid + 255) / 256;  // channels per thread
+  constexpr int NPR = SPLIT ? 3 : 5;                // tap pairs per thread
+  const int part = SPLIT ? tid >> 7 : 0;            // wave-uniform
+  const int p0 = NPR * part;
+  float wv[NCH][NPR][2], gv[NCH], s2v[NCH], b2v[NCH];
+#pragma unroll
+  for (int k = 0; k < NCH; ++k) {
+    const int c = (SPLIT ? tid & 127 : tid) + 256 * k, cl = c < Chid ? c : c - 256;
+#pragma unroll
+    for (int j = 0; j < NPR; ++j)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int tap = 2 * (p0 + j) + t;
+        if (SPLIT || tap < 9) wv[k][j][t] = a.wd[(tap < 9 ? tap : 8) * Chid + cl];
+        else wv[k][j][t] = 0.f;
+      }
+  }
+#pragma unroll
+  for (int k = 0; k < NCH; ++k) {
+    const int c = (SPLIT ? tid & 127 : tid) + 256 * k, cl = c < Chid ? c : c - 256;
+    gv[k] = (GATEW || GTAB) ? a.gate[(size_t)b * Chid + cl] : 1.f;
+    s2v[k] = a.as2[(size_t)b * Chid + cl];
+    b2v[k] = a.ab2[(size_t)b * Chid + cl];
+  }
+  // aff1 [2][K]: scale, then shift.  Every thread takes an entry (the threads past 2 K one that another thread has too) and writes
+  // it: a load that only a predicated block uses is sunk into that block by hipcc, behind the waits -- a round trip of its own
+  const int i1 = tid % (2 * K);
+  float v1 = i1 < K ? a.as1[(size_t)b * K + i1] : a.ab1[(size_t)b * K + i1 - K];
+  // Everything is in flight; every value is named here, outside any predicated block, so that hipcc neither sinks a load into the
+  // block that uses it (behind the waits of the blocks before) nor starts converting between two loads
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int k = 0; k < NCH; ++k) {
+#pragma unroll
+    for (int j = 0; j < NPR; ++j) asm volatile("" : "+v"(wv[k][j][0]), "+v"(wv[k][j][1]));
+    asm volatile("" : "+v"(gv[k]), "+v"(s2v[k]), "+v"(b2v[k]));
+  }
+  asm volatile("" : "+v"(v1));
+
   // [tap pair][channel][2]: one dword = this channel's weights of taps 2 p and 2 p + 1 (tap 9 = 0); the tile in LDS holds relu6(.) / 6
-  for (int i = tid; i < 10 * a.Chid; i += 256) {
-    const int t = i & 1, c = (i >> 1) % a.Chid, tap = 2 * ((i >> 1) / a.Chid) + t;
-    // GATEW: times the image's SE gate -- a constant per (image, channel) like the weight itself: the fp32 product is rounded to
-    // T once, where 6 w alone was rounded, and the chunk tail has no gate to apply
-    if constexpr (GATEW) wds[i] = tap < 9 ? (T)(6.f * a.wd[tap * a.Chid + c] * a.gate[(size_t)b * a.Chid + c]) : (T)0.f;
-    else wds[i] = tap < 9 ? (T)(6.f * a.wd[tap * a.Chid + c]) : (T)0.f;
+  uint32_t* wpair = reinterpret_cast<uint32_t*>(wds);
+#pragma unroll
+  for (int k = 0; k < NCH; ++k) {
+    const int c = (SPLIT ? tid & 127 : tid) + 256 * k;
+    if (k > 0 && c >= Chid) continue;  // 384 channels: threads 128..255 have no second channel
+#pragma unroll
+    for (int j = 0; j < NPR; ++j) {
+      const int p = p0 + j;
+      if (p >= 5) continue;  // (128 channels: the sixth pair of the upper threads)
+      // GATEW: times the image's SE gate -- a constant per (image, channel) like the weight itself: the fp32 product is rounded to
+      // T once, where 6 w alone was rounded, and the chunk tail has no gate to apply
+      T o[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        if constexpr (GATEW) o[t] = (T)(6.f * wv[k][j][t] * gv[k]);
+        else o[t] = (T)(6.f * wv[k][j][t]);
+        // One conversion per value, each with its multiply (in fp16 a v_fma_mixlo_f16), as when the slots were written one by
+        // one: left to itself hipcc converts the pair with one v_cvt_pk_f16_f32 behind separate multiplies, and the staged
+        // weights then differ from the one-by-one form in a few last bits per launch (profiles/r28/README.md, section 4)
+        asm volatile("" : "+v"(o[t]));
+      }
+      if (p == 4) o[1] = (T)0.f;
+      static_assert(sizeof(T) == 2, "two values per dword");
+      const uint32_t lo = *reinterpret_cast<const unsigned short*>(&o[0]), hi = *reinterpret_cast<const unsigned short*>(&o[1]);
+      wpair[p * Chid + c] = lo | (hi << 16);
+    }
+    if (!SPLIT || part == 0) {
+      aff2[c] = s2v[k];                   // applied to acc' = acc / 6: scale unchanged,
+      if constexpr (GTAB) gate_s[c] = gv[k];
+    }
+    if (!SPLIT || part == 1) aff2[Chid + c] = b2v[k] * kSixth;  // shift / 6, result clamped to [0, 1]
   }
-  for (int i = tid; i < a.Chid; i += 256) {
-    aff2[i] = a.as2[(size_t)b * a.Chid + i];                      // applied to acc' = acc / 6: scale unchanged,
-    aff2[a.Chid + i] = a.ab2[(size_t)b * a.Chid + i] * kSixth;    // shift / 6, result clamped to [0, 1]
-  }
-  for (int i = tid; i < K; i += 256) {
-    aff1[i] = a.as1[(size_t)b * K + i];      // already / 6 (GnFinalizeArgs::post_scale)
-    aff1[K + i] = a.ab1[(size_t)b * K + i];
-  }
-  if (gate_s != nullptr)
-    for (int i = tid; i < a.Chid; i += 256) gate_s[i] = a.gate[(size_t)b * a.Chid + i];
+  aff1[i1] = v1;                          // already / 6 (GnFinalizeArgs::post_scale)
   // pixels 180..191 of the last MFMA block do not exist: their operand rows stay zero
   for (int i = tid; i < (kXNPB * 32 - kXNPX) * (XP / 16); i += 256)
     *reinterpret_cast<u32x4*>(sX + kXNPX * XP + i * 16) = u32x4{0u, 0u, 0u, 0u};
@@ -444,7 +508,9 @@ struct IrbxHalo {
   static constexpr int QSTEP = 256 / (2 * KS);                  // 64 / 32 / 21 pixels per pass
   static constexpr int XTHR = QSTEP * 2 * KS;                   // threads that take part (252 of 256 at KS = 6)
   static constexpr int XPT = (kXNPX + QSTEP - 1) / QSTEP;       // passes: 3 / 6 / 9
-  static constexpr bool PREF = KS <= 2;        // next tile's x prefetched into registers at the top of the tile
+  // next tile's x prefetched into registers at the top of the tile.  32 channels only: at 64 and 96 the registers are there (233 / 243
+  // of 256, nothing spilled, still two workgroups per CU) but no launch got faster for it (profiles/r28/README.md, section 3)
+  static constexpr bool PREF = KS <= 2;
   typedef typename Elem<T>::vec_t vec_t;
   // per-thread constants of the staging -- nothing in the tile loop divides
   int xq0, xk8, xc;
@@ -488,6 +554,10 @@ struct IrbxHalo {
         else raw[j] = vec_t{};
       }
     }
+  }
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int j = 0; j < XPT; ++j) raw[j] = vec_t{};
   }
   // a' = relu6(norm1(raw)) / 6 into sX; aff1 = the image's norm1 table [2][K]
   __device__ __forceinline__ void activate(const float* aff1) {
@@ -678,7 +748,8 @@ __device__ __forceinline__ void irbx_pool_partial(const f32x4 (&dacc)[2][4], con
 
 // ---- expand_dw: h2 to HBM + SE pool partials.  DBUF: the h1 tile and `red` are double-buffered (one barrier per chunk);
 // NTST = h2 leaves with non-temporal stores (IrbxArgs::nt).
-// STAMP slots: 0 wait for the prefetched / loaded x tile (vmcnt), 1 activate + ds_write of the x tile, 2 next tile's loads issued
+// STAMP slots: 0 waiting for memory before a tile can start: prologue + x wait (the clock starts at kernel entry: entry -> "constants
+// staged" barrier, then every tile's wait for its prefetched / loaded x tile, vmcnt), 1 activate + ds_write of the x tile, 2 next tile's loads issued
 // + halo validity, 3 tile-top barrier, 4 pool flush behind it, 5 chunk-top barrier + flush (chunks after the first), 6 expand
 // MFMAs + epilogue + ds_write, 7 barrier behind them, 8 depthwise phase incl. the h2 stores and the pool partial.
 template <typename T, int KS, bool DBUF, bool STAMP, bool NTST>
@@ -715,18 +786,21 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
   const int nchunks_all = a.Chid / 64;
   const int chunk1 = chunk0 + chunks_per_wg < nchunks_all ? chunk0 + chunks_per_wg : nchunks_all;
 
-  irbx_stage_constants<T, KS, false>(a, b, tid, wds, aff2, aff1, nullptr, sX);
+  IrbxStamps<STAMP> stamp;
+  stamp(-1);  // the clock starts at kernel entry: slot 0 takes the prologue
+  // The prologue is one memory round trip: what the first tile needs goes out first -- its x halo (at every width: raw[] is live
+  // through the prologue only, where nothing else is), the expand weights of the first chunk -- then the constants, and the first
+  // wait is the one in front of the constants' LDS writes.
   const IrbxTiles run = irbx_tiles(a, tiles_per_wg);
   Halo halo;
   halo.init(a, x0, x1, sX, tid);
   int ty = run.first / tiles_x, tx = run.first % tiles_x;   // the only division: once per workgroup
-  if (Halo::PREF && run.first < run.last) halo.load(a, ty, tx, tiles_x);
+  if (run.first < run.last) halo.load(a, ty, tx, tiles_x);
   vec_t wf[KS];
   irbx_load_wf<T, KS>(wf, w1, chunk0, t);
+  irbx_stage_constants<T, KS, false, false>(a, b, tid, wds, aff2, aff1, nullptr, sX);
   wg_barrier();  // constants staged
-
-  IrbxStamps<STAMP> stamp;
-  stamp(-1);
+  stamp(0);
   const bool has_pool = a.pool != nullptr || a.pool_tot != nullptr;
   int par = 0;  // sH / red buffer parity (DBUF)
   int pend_tile = -1, pend_chunk = 0, pend_par = 0;  // pool partial waiting for its cross-wave sum
@@ -765,7 +839,6 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
     if (txn == tiles_x) { txn = 0; ++tyn; }
     // ---- activate this tile's x (norm1 + ReLU6) into sX, prefetch the next tile.  Every wave is past the last
     // MFMA phase of the previous tile here (the barrier that follows it), so sX is free.
-    if (!Halo::PREF) halo.load(a, ty, tx, tiles_x);
     // Every vector-memory operation so far has to be complete here anyway (raw[] below is older than all of them), but the
     // compiler's wait sits inside the predicated block below; said unconditionally, the chunk loop is entered with nothing
     // pending, and the wait for the prefetched weight slices at its head becomes vmcnt(4 + ...) -- the depthwise phase's four
@@ -893,6 +966,10 @@ __device__ __forceinline__ void expand_dw_body(const IrbxArgs& a, const int tile
       if (DBUF) par ^= 1;
       stamp(8);
     }
+    if constexpr (!Halo::PREF) {  // no registers to hold it under the tile: waited for at once
+      if (tile + 1 < run.last) halo.load(a, tyn, txn, tiles_x);
+      else halo.clear();  // (so that raw[] is not live around the loop)
+    }
     ty = tyn; tx = txn;
   }
   stamp.store(a, t);
@@ -1004,7 +1081,8 @@ __device__ __forceinline__ void irbx_project_store_y(const IrbxArgs& a, const Ir
 // then the engine's K-concatenated matrix [PCO][Chid + K] (row stride IrbxArgs::ldp), project columns first: the chunk tail reads
 // the project columns as before, and y starts as Wskip . x on the raw centre pixels: K / 32 k-steps at the top of the tile (no
 // norm, no activation: the skip segments of pw_gemm), their operands loaded before the tile-top barrier.
-// STAMP slots: 0 wait for the x tile (vmcnt), 1 activate + ds_write + the next tile's and the shortcut's loads issued + halo
+// STAMP slots: 0 waiting for memory before a tile can start: prologue + x wait (the clock starts at kernel entry: entry -> "constants
+// staged" barrier, then every tile's wait for its x tile, vmcnt), 1 activate + ds_write + the next tile's and the shortcut's loads issued + halo
 // validity, 2 tile-top barrier + flush of y's statistics + the shortcut into the y accumulators, 3 chunk-top barrier (chunks after
 // the first), 4 expand MFMAs + epilogue + ds_write, 5 barrier behind them, 6 depthwise steps until the last accumulator can be
 // read, 7 pack + swap + project MFMAs issued (they complete under whatever follows), 8 the tile's epilogue: rounding, y's
@@ -1046,18 +1124,19 @@ __device__ __forceinline__ void expand_dw_project_body(const IrbxArgs& a, const 
   const int nchunks_all = a.Chid / 64;
   const int chunk1 = chunk0 + KS < nchunks_all ? chunk0 + KS : nchunks_all;
 
-  irbx_stage_constants<T, KS, GATEW>(a, b, tid, wds, aff2, aff1, GATEW ? nullptr : gate_s, sX);
+  IrbxStamps<STAMP> stamp;
+  stamp(-1);  // the clock starts at kernel entry: slot 0 takes the prologue
+  // one memory round trip: the first tile's x halo, the first chunk's expand weights, the constants (see expand_dw_body)
   const IrbxTiles run = irbx_tiles(a, tiles_per_wg);
   Halo halo;
   halo.init(a, x0, x1, sX, tid);
   int ty = run.first / tiles_x, tx = run.first % tiles_x;   // the only division: once per workgroup
-  if (Halo::PREF && run.first < run.last) halo.load(a, ty, tx, tiles_x);
+  if (run.first < run.last) halo.load(a, ty, tx, tiles_x);
   vec_t wf[KS];
   irbx_load_wf<T, KS>(wf, w1, chunk0, t);
+  irbx_stage_constants<T, KS, GATEW, !GATEW>(a, b, tid, wds, aff2, aff1, gate_s, sX);
   wg_barrier();  // constants staged
-
-  IrbxStamps<STAMP> stamp;
-  stamp(-1);
+  stamp(0);
   int pend_tile = -1;  // tile whose y statistics wait in `red` for their cross-wave sum
   auto flush_ystats = [&]() {  // after a barrier that follows the tile epilogue which wrote `red`
     // y's statistics of the tile before: the four waves' (sum, sum of squares) [wave][2][PCO], added in wave order
@@ -1074,7 +1153,6 @@ __device__ __forceinline__ void expand_dw_project_body(const IrbxArgs& a, const 
     if (txn == tiles_x) { txn = 0; ++tyn; }
     // ---- activate this tile's x (norm1 + ReLU6) into sX, prefetch the next tile.  Every wave is past the last
     // MFMA phase of the previous tile here (the barrier that follows it), so sX is free.
-    if (!Halo::PREF) halo.load(a, ty, tx, tiles_x);
     // Every vector-memory operation so far has to be complete here anyway (raw[] below is older than all of them), but the
     // compiler's wait sits inside the predicated block below; said unconditionally, the chunk loop is entered with nothing
     // pending (see expand_dw_body).
@@ -1213,6 +1291,10 @@ __device__ __forceinline__ void expand_dw_project_body(const IrbxArgs& a, const 
     irbx_project_store_y<T, PCO>(a, t, yacc, b, y0, x0p, red);
     pend_tile = tile;
     stamp(8);
+    if constexpr (!Halo::PREF) {  // no registers to hold it under the tile: waited for at once
+      if (tile + 1 < run.last) halo.load(a, tyn, txn, tiles_x);
+      else halo.clear();  // (so that raw[] is not live around the loop)
+    }
     ty = tyn; tx = txn;
   }
   stamp.store(a, t);

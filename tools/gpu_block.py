@@ -41,10 +41,10 @@ def main():
     if stamp:
         out = (C.c_double * 10)()
         N.check(L.llie_debug_irbx_stamps(out))
-        names = ["x wait (vmcnt)", "activate + ds_write", "next-tile loads + halo flags", "tile-top barrier", "pool flush", "chunk-top barrier + flush",
+        names = ["prologue + x wait (memory)", "activate + ds_write", "next-tile loads + halo flags", "tile-top barrier", "pool flush", "chunk-top barrier + flush",
                  "expand MFMAs + epilogue", "barrier behind them", "depthwise phase + stores"]
         if stamp == 3:  # expand_dw_project (the block must be one the project form takes)
-            names = ["x wait (vmcnt)", "activate + ds_write + loads issued", "tile-top barrier + flush + shortcut", "chunk-top barrier",
+            names = ["prologue + x wait (memory)", "activate + ds_write + loads issued", "tile-top barrier + flush + shortcut", "chunk-top barrier",
                      "expand MFMAs + epilogue", "barrier behind them", "depthwise steps", "pack + swap + project MFMAs", "tile epilogue"]
         kernel = {1: "expand_dw", 2: "expand_pool", 3: "expand_dw_project"}.get(stamp, "?")
         tot = sum(out[:9])
