@@ -2,7 +2,6 @@
 // (wgrad.hip) and the input-gradient GEMMs / convolutions, which reuse the forward kernels with
 // transposed weights.  Activation gradients are NHWC T, reductions are tile partials combined in a
 // fixed order (bitwise reproducible, no float atomics).
-#include <string>
 
 #include "common.h"
 
@@ -83,24 +82,13 @@ __global__ void __launch_bounds__(256) bwd_mask_reduce_kernel(const BwdMaskArgs 
 }
 hipError_t launch_bwd_mask_reduce(int dtype, const BwdMaskArgs& a, hipStream_t s) {
   if (a.P < 1 || a.M % a.P || a.C % 32 || (a.x0 && a.c0 + a.c1 != a.C)) return hipErrorInvalidValue;
-  if (a.P % 64) {  // slab of ceil(P / 64) tiles per image
-    dim3 grid((a.M / a.P) * ((a.P + 63) / 64), (a.C + 63) / 64);
-    switch (dtype) {
-      case 0: hipLaunchKernelGGL((bwd_mask_reduce_kernel<float, true>), grid, dim3(256), 0, s, a); break;
-      case 1: hipLaunchKernelGGL((bwd_mask_reduce_kernel<half_t, true>), grid, dim3(256), 0, s, a); break;
-      case 2: hipLaunchKernelGGL((bwd_mask_reduce_kernel<bf16_t, true>), grid, dim3(256), 0, s, a); break;
-      default: return hipErrorInvalidValue;
-    }
+  return with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (a.P % 64)  // slab of ceil(P / 64) tiles per image
+      hipLaunchKernelGGL((bwd_mask_reduce_kernel<T, true>), dim3((a.M / a.P) * ((a.P + 63) / 64), (a.C + 63) / 64), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(bwd_mask_reduce_kernel<T>, dim3(a.M / 64, (a.C + 63) / 64), dim3(256), 0, s, a);
     return hipGetLastError();
-  }
-  dim3 grid(a.M / 64, (a.C + 63) / 64);
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(bwd_mask_reduce_kernel<float>, grid, dim3(256), 0, s, a); break;
-    case 1: hipLaunchKernelGGL(bwd_mask_reduce_kernel<half_t>, grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(bwd_mask_reduce_kernel<bf16_t>, grid, dim3(256), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  });
 }
 
 // out[b][j][c] = sum_t slab[b][t][j][c]; block = 64 channels of one (image, j): 16 tile groups x 16 float4 lanes
@@ -299,13 +287,10 @@ hipError_t launch_gn_bwd_apply(int dtype, const GnApplyArgs& a, hipStream_t s) {
   const size_t vecs = (size_t)a.M * C / (dtype == 0 ? 4 : 8);
   if (vecs >= (1ull << 31)) return hipErrorInvalidValue;
   dim3 grid((unsigned)((vecs + 255) / 256));
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(gn_bwd_apply_kernel<float>, grid, dim3(256), 0, s, a); break;
-    case 1: hipLaunchKernelGGL(gn_bwd_apply_kernel<half_t>, grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(gn_bwd_apply_kernel<bf16_t>, grid, dim3(256), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(gn_bwd_apply_kernel<decltype(t)>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_gn_site_bwd(int dtype, const GnSiteArgs& a, hipStream_t s) {
@@ -360,13 +345,11 @@ hipError_t launch_add_into(int dtype, void* dst, const void* src, int64_t n, hip
   if (n % vec) return hipErrorInvalidValue;
   const int64_t nv = n / vec;
   dim3 grid((unsigned)((nv + 255) / 256));
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(add_into_kernel<float>, grid, dim3(256), 0, s, (float*)dst, (const float*)src, nv); break;
-    case 1: hipLaunchKernelGGL(add_into_kernel<half_t>, grid, dim3(256), 0, s, (half_t*)dst, (const half_t*)src, nv); break;
-    case 2: hipLaunchKernelGGL(add_into_kernel<bf16_t>, grid, dim3(256), 0, s, (bf16_t*)dst, (const bf16_t*)src, nv); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(add_into_kernel<T>, grid, dim3(256), 0, s, (T*)dst, (const T*)src, nv);
+    return hipGetLastError();
+  });
 }
 hipError_t launch_fill_zero(void* dst, int64_t bytes, hipStream_t s) { return hipMemsetAsync(dst, 0, (size_t)bytes, s); }
 
@@ -512,24 +495,23 @@ __global__ void dw_wgrad_reduce_kernel(const float* partial, float* out, int npa
   for (int p = 0; p < nparts; ++p) s += partial[((size_t)p * 9 + t) * C + c];
   out[(size_t)c * 9 + t] = s;
 }
-template <typename T>
-static void launch_dw_wgrad_t(const DwWgradArgs& a, dim3 grid, int TX, hipStream_t s) {
-  if (a.W % 8) hipLaunchKernelGGL((dw_wgrad_kernel<T, 8, true>), grid, dim3(64), 0, s, a);
-  else if (TX == 32) hipLaunchKernelGGL((dw_wgrad_kernel<T, 32>), grid, dim3(256), 0, s, a);
-  else if (TX == 16) hipLaunchKernelGGL((dw_wgrad_kernel<T, 16>), grid, dim3(128), 0, s, a);
-  else hipLaunchKernelGGL((dw_wgrad_kernel<T, 8>), grid, dim3(64), 0, s, a);
-}
 hipError_t launch_dw_wgrad(int dtype, const DwWgradArgs& a, hipStream_t s) {
   const int CC = dtype == 0 ? 32 : 64;
   if (a.C % CC || a.W < 1 || a.H < 1) return hipErrorInvalidValue;
-  const int TX = dwg_tx(a.W);
   dim3 grid(dw_wgrad_strips(a.H, a.W), a.C / CC, a.B);
-  switch (dtype) {
-    case 0: launch_dw_wgrad_t<float>(a, grid, TX, s); break;
-    case 1: launch_dw_wgrad_t<half_t>(a, grid, TX, s); break;
-    case 2: launch_dw_wgrad_t<bf16_t>(a, grid, TX, s); break;
-    default: return hipErrorInvalidValue;
-  }
+  const hipError_t e = with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (a.W % 8) {
+      hipLaunchKernelGGL((dw_wgrad_kernel<T, 8, true>), grid, dim3(64), 0, s, a);
+      return hipSuccess;
+    }
+    return with_value<32, 16, 8>(dwg_tx(a.W), [&](auto tx) {
+      constexpr int TX = decltype(tx)::value;
+      hipLaunchKernelGGL((dw_wgrad_kernel<T, TX>), grid, dim3(8 * TX), 0, s, a);
+      return hipSuccess;
+    });
+  });
+  if (e != hipSuccess) return e;
   int nparts = a.B * (int)grid.x;
   if (nparts > kPartGroups) {
     hipLaunchKernelGGL(partial_groups_kernel, dim3((9 * a.C + 255) / 256, kPartGroups), dim3(256), 0, s, a.partial, (int64_t)9 * a.C, nparts);
@@ -574,12 +556,12 @@ hipError_t launch_linear_dx(int wdtype, const float* dy, int64_t dy_stride, cons
   const int rchunk = (R + chunks - 1) / chunks;
   float* dst = chunks > 1 ? scratch : dx;
   dim3 grid((Kc + 63) / 64, B, chunks);
-  switch (wdtype) {
-    case 0: hipLaunchKernelGGL(linear_dx_kernel<float>, grid, dim3(256), 0, s, dy, dy_stride, (const float*)W, dst, R, Kc, rchunk, B); break;
-    case 1: hipLaunchKernelGGL(linear_dx_kernel<half_t>, grid, dim3(256), 0, s, dy, dy_stride, (const half_t*)W, dst, R, Kc, rchunk, B); break;
-    case 2: hipLaunchKernelGGL(linear_dx_kernel<bf16_t>, grid, dim3(256), 0, s, dy, dy_stride, (const bf16_t*)W, dst, R, Kc, rchunk, B); break;
-    default: return hipErrorInvalidValue;
-  }
+  const hipError_t e = with_dtype(wdtype, [&](auto t) {
+    using WT = decltype(t);
+    hipLaunchKernelGGL(linear_dx_kernel<WT>, grid, dim3(256), 0, s, dy, dy_stride, (const WT*)W, dst, R, Kc, rchunk, B);
+    return hipSuccess;
+  });
+  if (e != hipSuccess) return e;
   if (chunks > 1) {
     const int64_t n = (int64_t)B * Kc;
     hipLaunchKernelGGL(linear_dx_combine_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scratch, dx, n, chunks);
@@ -624,14 +606,15 @@ __global__ void scale_rows_kernel(const float* x, float* out, int64_t n, float s
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = x[i] * sc;
 }
-#define LLIE_EW(name, kernel, ...)                                                                        \
-  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, __VA_ARGS__);             \
+// the four element-wise kernels above: one thread per element, 256 per block
+template <typename... A> static hipError_t launch_ew(void (*kernel)(A...), int64_t n, hipStream_t s, A... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, args...);
   return hipGetLastError();
-hipError_t launch_sigmoid_bwd(const float* dg, const float* g, float* out, int64_t n, hipStream_t s) { LLIE_EW(a, sigmoid_bwd_kernel, dg, g, out, n) }
-hipError_t launch_relu6_bwd(const float* dy, const float* y, float* out, int64_t n, hipStream_t s) { LLIE_EW(a, relu6_bwd_kernel, dy, y, out, n) }
-hipError_t launch_silu_bwd(const float* dy, const float* x, float* out, int64_t n, hipStream_t s) { LLIE_EW(a, silu_bwd_kernel, dy, x, out, n) }
-hipError_t launch_scale_rows(const float* x, float* out, int64_t n, float sc, hipStream_t s) { LLIE_EW(a, scale_rows_kernel, x, out, n, sc) }
-#undef LLIE_EW
+}
+hipError_t launch_sigmoid_bwd(const float* dg, const float* g, float* out, int64_t n, hipStream_t s) { return launch_ew(sigmoid_bwd_kernel, n, s, dg, g, out, n); }
+hipError_t launch_relu6_bwd(const float* dy, const float* y, float* out, int64_t n, hipStream_t s) { return launch_ew(relu6_bwd_kernel, n, s, dy, y, out, n); }
+hipError_t launch_silu_bwd(const float* dy, const float* x, float* out, int64_t n, hipStream_t s) { return launch_ew(silu_bwd_kernel, n, s, dy, x, out, n); }
+hipError_t launch_scale_rows(const float* x, float* out, int64_t n, float sc, hipStream_t s) { return launch_ew(scale_rows_kernel, n, s, x, out, n, sc); }
 
 __global__ void sin_embed_kernel(const int64_t* t, const float* freqs, float* emb, int dim) {
   const int r = blockIdx.x, half = dim / 2;
@@ -731,23 +714,26 @@ __global__ void __launch_bounds__(256) dilate2x_kernel(const T* in, T* out, int 
   if (!(uy & 1) && !(ux & 1)) v = ld_vec<T>(in + (((size_t)b * Hi + uy / 2) * Wi + ux / 2) * C + c);
   st_vec<T>(out + (((size_t)b * Ho + uy) * Wo + ux) * C + c, v);
 }
-#define LLIE_PIX3(kernel, npix)                                                                                  \
-  if (C % (dtype == 0 ? 4 : 8)) return hipErrorInvalidValue;                                                    \
-  {                                                                                                             \
-    const size_t n = (size_t)(npix) * (C / (dtype == 0 ? 4 : 8));                                                \
-    dim3 grid((unsigned)((n + 255) / 256));                                                                     \
-    switch (dtype) {                                                                                            \
-      case 0: hipLaunchKernelGGL(kernel<float>, grid, dim3(256), 0, s, (const float*)in, (float*)out, B, Hi, Wi, C); break;      \
-      case 1: hipLaunchKernelGGL(kernel<half_t>, grid, dim3(256), 0, s, (const half_t*)in, (half_t*)out, B, Hi, Wi, C); break;   \
-      case 2: hipLaunchKernelGGL(kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)out, B, Hi, Wi, C); break;   \
-      default: return hipErrorInvalidValue;                                                                     \
-    }                                                                                                           \
-  }                                                                                                             \
-  return hipGetLastError();
-hipError_t launch_upsample2x(int dtype, const void* in, void* out, int B, int Hi, int Wi, int C, hipStream_t s) { LLIE_PIX3(upsample2x_kernel, (size_t)B * 4 * Hi * Wi) }
-hipError_t launch_upsample2x_bwd(int dtype, const void* in, void* out, int B, int Hi, int Wi, int C, hipStream_t s) { LLIE_PIX3(upsample2x_bwd_kernel, (size_t)B * Hi * Wi) }
-hipError_t launch_dilate2x(int dtype, const void* in, void* out, int B, int Hi, int Wi, int C, hipStream_t s) { LLIE_PIX3(dilate2x_kernel, (size_t)B * 4 * Hi * Wi) }
-#undef LLIE_PIX3
+// one thread per 16-byte channel vector of `npix` output pixels; `kernel_of(T{})` is the instantiation for T
+template <typename F>
+static hipError_t launch_pix(int dtype, F kernel_of, size_t npix, const void* in, void* out, int B, int Hi, int Wi, int C, hipStream_t s) {
+  return with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (C % Elem<T>::VEC) return hipErrorInvalidValue;
+    const size_t n = npix * (C / Elem<T>::VEC);
+    hipLaunchKernelGGL(kernel_of(t), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const T*)in, (T*)out, B, Hi, Wi, C);
+    return hipGetLastError();
+  });
+}
+hipError_t launch_upsample2x(int dtype, const void* in, void* out, int B, int Hi, int Wi, int C, hipStream_t s) {
+  return launch_pix(dtype, [](auto t) { return upsample2x_kernel<decltype(t)>; }, (size_t)B * 4 * Hi * Wi, in, out, B, Hi, Wi, C, s);
+}
+hipError_t launch_upsample2x_bwd(int dtype, const void* in, void* out, int B, int Hi, int Wi, int C, hipStream_t s) {
+  return launch_pix(dtype, [](auto t) { return upsample2x_bwd_kernel<decltype(t)>; }, (size_t)B * Hi * Wi, in, out, B, Hi, Wi, C, s);
+}
+hipError_t launch_dilate2x(int dtype, const void* in, void* out, int B, int Hi, int Wi, int C, hipStream_t s) {
+  return launch_pix(dtype, [](auto t) { return dilate2x_kernel<decltype(t)>; }, (size_t)B * 4 * Hi * Wi, in, out, B, Hi, Wi, C, s);
+}
 
 // ---- output head.  Forward: eps[o][p] = bias[o] + sum_{c,tap} a[p + tap - 1][c] * W[o][c][tap], a = silu(h*as + ab).
 // data gradient: da[q][c] = sum_{o,tap} deps[o][q - (tap - 1)] * W[o][c][tap]
@@ -788,13 +774,10 @@ hipError_t launch_final_bwd_data(int dtype, const FinalBwdArgs& a, hipStream_t s
   if (a.C % 8) return hipErrorInvalidValue;
   const size_t n = (size_t)a.B * a.H * a.W * (a.C / (dtype == 0 ? 4 : 8));
   dim3 grid((unsigned)((n + 255) / 256));
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(final_bwd_data_kernel<float>, grid, dim3(256), 0, s, a); break;
-    case 1: hipLaunchKernelGGL(final_bwd_data_kernel<half_t>, grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(final_bwd_data_kernel<bf16_t>, grid, dim3(256), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(final_bwd_data_kernel<decltype(t)>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+  });
 }
 // The weight gradients of the output head and of the input conv run on the MFMA weight-gradient GEMM (wgrad.hip, nine
 // taps per launch) once their fp32 NCHW planes are packed into a 32-channel NHWC T tensor (channels beyond the real
@@ -820,13 +803,11 @@ __global__ void __launch_bounds__(256) pack_planes_kernel(const float* x0, const
 hipError_t launch_pack_planes(int dtype, const float* x0, const float* x1, int c0, int c1, void* out, int B, int P, hipStream_t s) {
   if (c0 + c1 > 8 || c0 < 1) return hipErrorInvalidValue;
   dim3 grid((unsigned)(((size_t)B * P + 255) / 256));
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(pack_planes_kernel<float>, grid, dim3(256), 0, s, x0, x1, c0, c1, (float*)out, B, P); break;
-    case 1: hipLaunchKernelGGL(pack_planes_kernel<half_t>, grid, dim3(256), 0, s, x0, x1, c0, c1, (half_t*)out, B, P); break;
-    case 2: hipLaunchKernelGGL(pack_planes_kernel<bf16_t>, grid, dim3(256), 0, s, x0, x1, c0, c1, (bf16_t*)out, B, P); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(pack_planes_kernel<T>, grid, dim3(256), 0, s, x0, x1, c0, c1, (T*)out, B, P);
+    return hipGetLastError();
+  });
 }
 // ---- input conv, data gradient: the transpose of init_conv_kernel (conv_edge.hip) with the roles of patch and output exchanged.
 //   dx[b][ci][y][x] = sum_{ky,kx} sum_co g[b][y + 1 - ky][x + 1 - kx][co] * W[co][ci][ky][kx], zero outside the map
@@ -911,13 +892,13 @@ hipError_t launch_init_conv_dgrad(int dtype, const InitDgradArgs& a, hipStream_t
       a.B > 65535 || a.H <= 0 || a.W <= 0)
     return hipErrorInvalidValue;
   dim3 grid(init_conv_ntiles(a.H, a.W, false), a.B);  // 16 x 16 tiles
-  switch (dtype) {
-    case 0: note_kernel("init_conv_dgrad_kernel<float>"); hipLaunchKernelGGL(init_conv_dgrad_kernel<float>, grid, dim3(256), 0, s, a); break;
-    case 1: note_kernel("init_conv_dgrad_kernel<_Float16>"); hipLaunchKernelGGL(init_conv_dgrad_kernel<half_t>, grid, dim3(256), 0, s, a); break;
-    case 2: note_kernel("init_conv_dgrad_kernel<__bf16>"); hipLaunchKernelGGL(init_conv_dgrad_kernel<bf16_t>, grid, dim3(256), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    static const char* const name = kernel_name<T>("init_conv_dgrad_kernel");
+    note_kernel(name);
+    hipLaunchKernelGGL(init_conv_dgrad_kernel<T>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+  });
 }
 // =============================================================================================
 // (8) linear attention backward (forward: efficient_unet.py:288-302).  With Q = phi(q), K = phi(k):
@@ -1050,45 +1031,23 @@ __global__ void __launch_bounds__(256) linattn_bwd_kv_kernel(const AttnBwdArgs a
 }
 hipError_t launch_linattn_bwd_q(int dtype, const AttnBwdArgs& a, hipStream_t s) {
   if (a.N < 1) return hipErrorInvalidValue;
-  if (a.N % 64) {
-    dim3 grid((a.N + 63) / 64, a.heads, a.B);
-    switch (dtype) {
-      case 0: hipLaunchKernelGGL((linattn_bwd_q_kernel<float, true>), grid, dim3(256), 0, s, a); break;
-      case 1: hipLaunchKernelGGL((linattn_bwd_q_kernel<half_t, true>), grid, dim3(256), 0, s, a); break;
-      case 2: hipLaunchKernelGGL((linattn_bwd_q_kernel<bf16_t, true>), grid, dim3(256), 0, s, a); break;
-      default: return hipErrorInvalidValue;
-    }
+  dim3 grid((a.N + 63) / 64, a.heads, a.B);
+  return with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (a.N % 64) hipLaunchKernelGGL((linattn_bwd_q_kernel<T, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(linattn_bwd_q_kernel<T>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
-  }
-  dim3 grid(a.N / 64, a.heads, a.B);
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(linattn_bwd_q_kernel<float>, grid, dim3(256), 0, s, a); break;
-    case 1: hipLaunchKernelGGL(linattn_bwd_q_kernel<half_t>, grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(linattn_bwd_q_kernel<bf16_t>, grid, dim3(256), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  });
 }
 hipError_t launch_linattn_bwd_kv(int dtype, const AttnBwdArgs& a, hipStream_t s) {
   if (a.N < 1) return hipErrorInvalidValue;
-  if (a.N % 64) {
-    dim3 grid((a.N + 63) / 64, a.heads, a.B);
-    switch (dtype) {
-      case 0: hipLaunchKernelGGL((linattn_bwd_kv_kernel<float, true>), grid, dim3(256), 0, s, a); break;
-      case 1: hipLaunchKernelGGL((linattn_bwd_kv_kernel<half_t, true>), grid, dim3(256), 0, s, a); break;
-      case 2: hipLaunchKernelGGL((linattn_bwd_kv_kernel<bf16_t, true>), grid, dim3(256), 0, s, a); break;
-      default: return hipErrorInvalidValue;
-    }
+  dim3 grid((a.N + 63) / 64, a.heads, a.B);
+  return with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (a.N % 64) hipLaunchKernelGGL((linattn_bwd_kv_kernel<T, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(linattn_bwd_kv_kernel<T>, grid, dim3(256), 0, s, a);
     return hipGetLastError();
-  }
-  dim3 grid(a.N / 64, a.heads, a.B);
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(linattn_bwd_kv_kernel<float>, grid, dim3(256), 0, s, a); break;
-    case 1: hipLaunchKernelGGL(linattn_bwd_kv_kernel<half_t>, grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(linattn_bwd_kv_kernel<bf16_t>, grid, dim3(256), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  });
 }
 
 hipError_t launch_linattn_bwd(int dtype, const AttnBwdArgs& a, float* tot, hipStream_t s) {

@@ -5,7 +5,11 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <mutex>
+#include <set>
+#include <string>
 #include <type_traits>
+#include <utility>
 
 #include "kernels.h"
 
@@ -318,5 +322,50 @@ __device__ __forceinline__ int mfma_row(int r, int lane) { return (r & 3) + 8 * 
 // LDS row pitch (in elements) for a [rows][32] T tile: 32 elements + one 16-byte pad => conflict-free
 // ds_read_b128 of 16-lane groups (80-byte rows for 2-byte T, 144-byte rows for float).
 template <typename T> struct TilePitch { static constexpr int value = 32 + Elem<T>::VEC; };
+
+// ---------------------------------------------------------------------------------------------
+// Host: how every launch_* function picks its kernel instantiation.  The callable is a generic lambda that takes the
+// choice as a value, `[&](auto t) { using T = decltype(t); ... }`; a code outside the set launches nothing and is refused.
+// Where a kernel exists for only some of the dispatched values, an `if constexpr` inside the lambda keeps the others
+// from being instantiated.
+// f(T{}) with the element type of `dtype`: 0 float, 1 half_t, 2 bf16_t
+template <typename F> hipError_t with_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case 0: return f(float{});
+    case 1: return f(half_t{});
+    case 2: return f(bf16_t{});
+  }
+  return hipErrorInvalidValue;
+}
+// the same for launchers whose kernels exist in the 2-byte types only
+template <typename F> hipError_t with_dtype2(int dtype, F&& f) {
+  switch (dtype) {
+    case 1: return f(half_t{});
+    case 2: return f(bf16_t{});
+  }
+  return hipErrorInvalidValue;
+}
+// f(std::integral_constant<int, V>{}) for the first V of the list equal to v
+template <int... Vs, typename F> hipError_t with_value(int v, F&& f) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)((v == Vs && ((e = f(std::integral_constant<int, Vs>{})), true)) || ...);
+  return e;
+}
+
+// "kernel<float, 32, 4>": an instantiation's name as rocprofv3 prints it, for note_kernel.  The pointer stays valid; a
+// call site keeps it in a function-local static, so the string is built once per instantiation of that site.
+inline std::string targ_str(bool v) { return v ? "true" : "false"; }
+inline std::string targ_str(int v) { return std::to_string(v); }
+inline const char* keep_kernel_name(const std::string& name) {
+  static std::mutex m;
+  static std::set<std::string> names;
+  std::lock_guard<std::mutex> lock(m);
+  return names.insert(name).first->c_str();
+}
+template <typename T, typename... Ints> const char* kernel_name(const char* kernel, Ints... targs) {
+  std::string n = std::string(kernel) + "<" + TypeName<T>::value;
+  ((n += ", " + targ_str(targs)), ...);
+  return keep_kernel_name(n + ">");
+}
 
 }  // namespace llie

@@ -3,7 +3,6 @@
 //   Upsample    (efficient_unet.py:383-384) bilinear x2 + 3x3 } N = Cout tile, K = 9 taps x Cin; the upsampled
 //               halo patch is interpolated on the fly into LDS, so the 4x tensor never reaches HBM.
 // (The 3 -> C0 head and C0 -> 3 tail convs: conv_edge.hip; the up-sampling convs from folded weights / tap maps: upconv.hip.)
-#include <string>
 #include <type_traits>
 
 #include "common.h"
@@ -353,10 +352,8 @@ static hipError_t launch_conv_cfg(const Conv3Args& a, hipStream_t s) {
   }
   const int Ho = MODE == 0 ? a.Hi / 2 : (MODE == 1 ? a.Hi * 2 : a.Hi), Wo = MODE == 0 ? a.Wi / 2 : (MODE == 1 ? a.Wi * 2 : a.Wi);
   const unsigned grid = (unsigned)(a.B * ((Ho + 7) / 8) * ((Wo + TW - 1) / TW) * (a.Cout / BN));
-  static const std::string name = std::string("conv3x3_kernel<") + TypeName<T>::value + ", " + std::to_string(MODE) + ", " +
-                                  std::to_string(TW) + ", " + std::to_string(BN) + ", " + std::to_string(WM) + ", " +
-                                  std::to_string(WN) + ">";
-  note_kernel(name.c_str());
+  static const char* const name = kernel_name<T>("conv3x3_kernel", MODE, TW, BN, WM, WN);
+  note_kernel(name);
   if constexpr (MODE == 1 && TW == 16 && !RAGGED && std::is_same<T, half_t>::value) {
     if (g_knobs.conv_stamp) {  // diagnostic build with in-kernel cycle stamps
       Conv3Args b = a;
@@ -379,30 +376,20 @@ template <typename T, int MODE>
 static hipError_t launch_conv_t(const Conv3Args& a, hipStream_t s) {
   const int Ho = MODE == 0 ? a.Hi / 2 : (MODE == 1 ? a.Hi * 2 : a.Hi), Wo = MODE == 0 ? a.Wi / 2 : (MODE == 1 ? a.Wi * 2 : a.Wi);
   if (Ho < 1 || Wo < 1 || a.Cin % 32 || a.Cout % 32 || (MODE == 0 && (a.Hi % 2 || a.Wi % 2))) return hipErrorInvalidValue;
-  const int BN = (a.Cout % 128 == 0) ? 128 : ((a.Cout % 64 == 0) ? 64 : 32);
-  if (Ho % 8 || Wo % 8) {  // partly empty edge tiles: maps that are not a multiple of 8 (image sizes % 64 != 0); MODE 2 = training
-    if (BN == 128) return launch_conv_cfg<T, MODE, 8, 128, 2, 2, true>(a, s);
-    if (BN == 64) return launch_conv_cfg<T, MODE, 8, 64, 2, 2, true>(a, s);
-    return launch_conv_cfg<T, MODE, 8, 32, 2, 1, true>(a, s);
-  }
-  if (conv_tw(Wo) == 16) {
-    if (BN == 128) return launch_conv_cfg<T, MODE, 16, 128, 2, 2>(a, s);
-    if (BN == 64) return launch_conv_cfg<T, MODE, 16, 64, 2, 2>(a, s);
-    return launch_conv_cfg<T, MODE, 16, 32, 4, 1>(a, s);
-  }
-  if (BN == 128) return launch_conv_cfg<T, MODE, 8, 128, 2, 2>(a, s);
-  if (BN == 64) return launch_conv_cfg<T, MODE, 8, 64, 2, 2>(a, s);
-  return launch_conv_cfg<T, MODE, 8, 32, 2, 1>(a, s);
+  // partly empty edge tiles: maps that are not a multiple of 8 (image sizes % 64 != 0); MODE 2 = training
+  const bool ragged = Ho % 8 || Wo % 8;
+  return with_value<128, 64, 32>((a.Cout % 128 == 0) ? 128 : ((a.Cout % 64 == 0) ? 64 : 32), [&](auto bn) {
+    constexpr int BN = decltype(bn)::value, WN = BN == 32 ? 1 : 2;  // 32-column tiles: one wave wide, 16-wide ones four waves tall
+    if (ragged) return launch_conv_cfg<T, MODE, 8, BN, 2, WN, true>(a, s);
+    if (conv_tw(Wo) == 16) return launch_conv_cfg<T, MODE, 16, BN, BN == 32 ? 4 : 2, WN>(a, s);
+    return launch_conv_cfg<T, MODE, 8, BN, 2, WN>(a, s);
+  });
 }
 
 hipError_t launch_conv3x3(int dtype, const Conv3Args& a, hipStream_t s) {
-  if (a.mode < 0 || a.mode > 2) return hipErrorInvalidValue;
-  switch (dtype) {
-    case 0: return a.mode == 0 ? launch_conv_t<float, 0>(a, s) : (a.mode == 1 ? launch_conv_t<float, 1>(a, s) : launch_conv_t<float, 2>(a, s));
-    case 1: return a.mode == 0 ? launch_conv_t<half_t, 0>(a, s) : (a.mode == 1 ? launch_conv_t<half_t, 1>(a, s) : launch_conv_t<half_t, 2>(a, s));
-    case 2: return a.mode == 0 ? launch_conv_t<bf16_t, 0>(a, s) : (a.mode == 1 ? launch_conv_t<bf16_t, 1>(a, s) : launch_conv_t<bf16_t, 2>(a, s));
-  }
-  return hipErrorInvalidValue;
+  return with_value<0, 1, 2>(a.mode, [&](auto mode) {
+    return with_dtype(dtype, [&](auto t) { return launch_conv_t<decltype(t), decltype(mode)::value>(a, s); });
+  });
 }
 
 }  // namespace llie

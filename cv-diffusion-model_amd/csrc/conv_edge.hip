@@ -205,21 +205,21 @@ hipError_t launch_init_conv(int dtype, const InitConvArgs& a, hipStream_t s) {
   if (a.H % 8 || a.W % 8 || a.Cout % 32 || a.c0 + a.c1 > 8) return hipErrorInvalidValue;
   const bool mfma = a.wp && dtype != 0;
   dim3 grid(init_conv_ntiles(a.H, a.W, mfma), a.B);  // 256-pixel tiles: 16 x 16 (VALU kernel) or 8 x 32 (MFMA kernel)
-  switch (dtype) {
-    case 0: note_kernel("init_conv_kernel<float>"); hipLaunchKernelGGL(init_conv_kernel<float>, grid, dim3(256), 0, s, a); break;
-    case 1:
-      note_kernel(a.wp ? "init_conv_mfma_kernel<_Float16>" : "init_conv_kernel<_Float16>");
-      if (a.wp) hipLaunchKernelGGL(init_conv_mfma_kernel<half_t>, grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL(init_conv_kernel<half_t>, grid, dim3(256), 0, s, a);
-      break;
-    case 2:
-      note_kernel(a.wp ? "init_conv_mfma_kernel<__bf16>" : "init_conv_kernel<__bf16>");
-      if (a.wp) hipLaunchKernelGGL(init_conv_mfma_kernel<bf16_t>, grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL(init_conv_kernel<bf16_t>, grid, dim3(256), 0, s, a);
-      break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if constexpr (sizeof(T) == 2) {  // the MFMA kernel exists for the 2-byte types only
+      if (a.wp) {
+        static const char* const name = kernel_name<T>("init_conv_mfma_kernel");
+        note_kernel(name);
+        hipLaunchKernelGGL(init_conv_mfma_kernel<T>, grid, dim3(256), 0, s, a);
+        return hipGetLastError();
+      }
+    }
+    static const char* const name = kernel_name<T>("init_conv_kernel");
+    note_kernel(name);
+    hipLaunchKernelGGL(init_conv_kernel<T>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+  });
 }
 
 // =============================================================================================
@@ -425,21 +425,21 @@ hipError_t launch_final_conv(int dtype, const FinalConvArgs& a, hipStream_t s) {
                       (a.coef.sampler && a.coef.clamp_x0))) return hipErrorInvalidValue;
   if (!a.fuse_step && !a.out) return hipErrorInvalidValue;
   dim3 grid(((a.H + 15) / 16) * ((a.W + 15) / 16), a.B);
-  switch (dtype) {
-    case 0: note_kernel("final_conv_kernel<float>"); hipLaunchKernelGGL(final_conv_kernel<float>, grid, dim3(256), 0, s, a); break;
-    case 1:
-      note_kernel(a.wp ? "final_conv_mfma_kernel<_Float16, 16>" : "final_conv_kernel<_Float16>");
-      if (a.wp) hipLaunchKernelGGL((final_conv_mfma_kernel<half_t, 16>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL(final_conv_kernel<half_t>, grid, dim3(256), 0, s, a);
-      break;
-    case 2:
-      note_kernel(a.wp ? "final_conv_mfma_kernel<__bf16, 16>" : "final_conv_kernel<__bf16>");
-      if (a.wp) hipLaunchKernelGGL((final_conv_mfma_kernel<bf16_t, 16>), grid, dim3(256), 0, s, a);
-      else hipLaunchKernelGGL(final_conv_kernel<bf16_t>, grid, dim3(256), 0, s, a);
-      break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    if constexpr (sizeof(T) == 2) {  // the MFMA kernel exists for the 2-byte types only
+      if (a.wp) {
+        static const char* const name = kernel_name<T>("final_conv_mfma_kernel", 16);
+        note_kernel(name);
+        hipLaunchKernelGGL((final_conv_mfma_kernel<T, 16>), grid, dim3(256), 0, s, a);
+        return hipGetLastError();
+      }
+    }
+    static const char* const name = kernel_name<T>("final_conv_kernel");
+    note_kernel(name);
+    hipLaunchKernelGGL(final_conv_kernel<T>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace llie

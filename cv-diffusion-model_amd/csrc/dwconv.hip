@@ -14,7 +14,6 @@
 //     and feeds three rolling output-row accumulators, so vertical reuse lives in registers.
 // LDS per workgroup is ~9 KB, so occupancy is set by registers, not LDS; halo re-reads are 2 rows per
 // TYL and 2 columns per TX.
-#include <string>
 #include <type_traits>
 
 #include "common.h"
@@ -307,70 +306,41 @@ static hipError_t launch_dw_t(const DwArgs& a, hipStream_t s) {
   const int tx = dw_tx(a.H, a.W), tyl = dw_pick_tyl(a.B, a.H, a.W, a.C / CC);
   const int tiles = ((a.W + tx - 1) / tx) * ((a.H + tyl - 1) / tyl);
   dim3 grid(tiles, a.C / CC, a.B);
-  static const std::string names[3] = {std::string("dwconv3x3_kernel<") + TypeName<T>::value + ", 32, 4>",
-                                       std::string("dwconv3x3_kernel<") + TypeName<T>::value + ", 16, 4>",
-                                       std::string("dwconv3x3_kernel<") + TypeName<T>::value + ", 8, 4>"};
-  static const std::string bwd_names[5] = {std::string("dwconv3x3_bwd_kernel<") + TypeName<T>::value + ", 32, 4>",
-                                           std::string("dwconv3x3_bwd_kernel<") + TypeName<T>::value + ", 16, 4>",
-                                           std::string("dwconv3x3_bwd_kernel<") + TypeName<T>::value + ", 8, 4>",
-                                           std::string("dwconv3x3_bwd_ragged_kernel<") + TypeName<T>::value + ", 32, 4>",
-                                           std::string("dwconv3x3_bwd_ragged_kernel<") + TypeName<T>::value + ", 16, 4>"};
-  note_kernel(names[tx == 32 ? 0 : (tx == 16 ? 1 : 2)].c_str());
-  if (ragged && a.bx) {  // backward instantiation; TX is 16 or 32 here
-    if (!a.bas || !a.bab || !a.bslab || a.pool || a.s6) return hipErrorInvalidValue;
-    note_kernel(bwd_names[tx == 32 ? 3 : 4].c_str());
-    if (tx == 32) hipLaunchKernelGGL((dwconv3x3_bwd_ragged_kernel<T, 32, kDwPF>), grid, dim3(256), 0, s, a, tyl);
-    else hipLaunchKernelGGL((dwconv3x3_bwd_ragged_kernel<T, 16, kDwPF>), grid, dim3(128), 0, s, a, tyl);
-    return hipGetLastError();
-  }
-  if (ragged) {  // TX is 16 or 32 here
-    note_kernel("dwconv3x3_ragged_kernel");
-    if constexpr (sizeof(T) == 2) {
-      if (a.s6) {
-        if (a.no_act) return hipErrorInvalidValue;
-        if (tx == 32) hipLaunchKernelGGL((dwconv3x3_ragged_kernel<T, 32, kDwPF, true>), grid, dim3(256), 0, s, a, tyl, 0, 0);
-        else hipLaunchKernelGGL((dwconv3x3_ragged_kernel<T, 16, kDwPF, true>), grid, dim3(128), 0, s, a, tyl, 0, 0);
-        return hipGetLastError();
+  return with_value<32, 16, 8>(tx, [&](auto txc) -> hipError_t {
+    constexpr int TX = decltype(txc)::value;
+    constexpr bool HAS_RAGGED = TX != 8;  // dw_tx(H, W) never gives a ragged map 8 columns
+    const dim3 block(8 * TX);
+    static const char* const fwd_name = kernel_name<T>("dwconv3x3_kernel", TX, kDwPF);
+    note_kernel(fwd_name);
+    if (ragged && !HAS_RAGGED) return hipErrorInvalidValue;
+    if (a.bx) {  // backward instantiation
+      if (!a.bas || !a.bab || !a.bslab || a.pool || (ragged && a.s6)) return hipErrorInvalidValue;
+      if (!ragged) {
+        static const char* const name = kernel_name<T>("dwconv3x3_bwd_kernel", TX, kDwPF);
+        note_kernel(name);
+        hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, TX, kDwPF>), grid, block, 0, s, a, tyl);
+      } else if constexpr (HAS_RAGGED) {
+        static const char* const name = kernel_name<T>("dwconv3x3_bwd_ragged_kernel", TX, kDwPF);
+        note_kernel(name);
+        hipLaunchKernelGGL((dwconv3x3_bwd_ragged_kernel<T, TX, kDwPF>), grid, block, 0, s, a, tyl);
       }
-    } else if (a.s6) {
-      return hipErrorInvalidValue;
-    }
-    if (tx == 32) hipLaunchKernelGGL((dwconv3x3_ragged_kernel<T, 32, kDwPF>), grid, dim3(256), 0, s, a, tyl, 0, 0);
-    else hipLaunchKernelGGL((dwconv3x3_ragged_kernel<T, 16, kDwPF>), grid, dim3(128), 0, s, a, tyl, 0, 0);
-    return hipGetLastError();
-  }
-  if (a.bx) {  // backward instantiation
-    if (!a.bas || !a.bab || !a.bslab || a.pool) return hipErrorInvalidValue;
-    note_kernel(bwd_names[tx == 32 ? 0 : (tx == 16 ? 1 : 2)].c_str());
-    if (tx == 32) hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, 32, kDwPF>), grid, dim3(256), 0, s, a, tyl);
-    else if (tx == 16) hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, 16, kDwPF>), grid, dim3(128), 0, s, a, tyl);
-    else hipLaunchKernelGGL((dwconv3x3_bwd_kernel<T, 8, kDwPF>), grid, dim3(64), 0, s, a, tyl);
-    return hipGetLastError();
-  }
-  if constexpr (sizeof(T) == 2) {
-    if (a.s6) {
-      if (a.no_act) return hipErrorInvalidValue;
-      if (tx == 32) hipLaunchKernelGGL((dwconv3x3_kernel<T, 32, kDwPF, true>), grid, dim3(256), 0, s, a, tyl, 0, 0);
-      else if (tx == 16) hipLaunchKernelGGL((dwconv3x3_kernel<T, 16, kDwPF, true>), grid, dim3(128), 0, s, a, tyl, 0, 0);
-      else hipLaunchKernelGGL((dwconv3x3_kernel<T, 8, kDwPF, true>), grid, dim3(64), 0, s, a, tyl, 0, 0);
       return hipGetLastError();
     }
-  } else if (a.s6) {
+    if (ragged) note_kernel("dwconv3x3_ragged_kernel");
+    auto forward = [&](auto s6c) {
+      constexpr bool S6 = decltype(s6c)::value;
+      if (!ragged) hipLaunchKernelGGL((dwconv3x3_kernel<T, TX, kDwPF, S6>), grid, block, 0, s, a, tyl, 0, 0);
+      else if constexpr (HAS_RAGGED) hipLaunchKernelGGL((dwconv3x3_ragged_kernel<T, TX, kDwPF, S6>), grid, block, 0, s, a, tyl, 0, 0);
+      return hipGetLastError();
+    };
+    if (!a.s6) return forward(std::false_type{});
+    if constexpr (sizeof(T) == 2) return a.no_act ? hipErrorInvalidValue : forward(std::true_type{});  // S6 forms: 2-byte types only
     return hipErrorInvalidValue;
-  }
-  if (tx == 32) hipLaunchKernelGGL((dwconv3x3_kernel<T, 32, kDwPF>), grid, dim3(256), 0, s, a, tyl, 0, 0);
-  else if (tx == 16) hipLaunchKernelGGL((dwconv3x3_kernel<T, 16, kDwPF>), grid, dim3(128), 0, s, a, tyl, 0, 0);
-  else hipLaunchKernelGGL((dwconv3x3_kernel<T, 8, kDwPF>), grid, dim3(64), 0, s, a, tyl, 0, 0);
-  return hipGetLastError();
+  });
 }
 
 hipError_t launch_dwconv3x3(int dtype, const DwArgs& a, hipStream_t s) {
-  switch (dtype) {
-    case 0: return launch_dw_t<float>(a, s);
-    case 1: return launch_dw_t<half_t>(a, s);
-    case 2: return launch_dw_t<bf16_t>(a, s);
-  }
-  return hipErrorInvalidValue;
+  return with_dtype(dtype, [&](auto t) { return launch_dw_t<decltype(t)>(a, s); });
 }
 
 }  // namespace llie

@@ -10,7 +10,6 @@
 //                                                    (sum, sumsq) slab for the next GroupNorm.
 // A rows are NHWC pixels (K contiguous), W is [N][K] (K contiguous): both MFMA operands read 16
 // contiguous K-elements per lane.  fp32 accumulation always; T = float uses the exact-f32 MFMA.
-#include <string>
 #include <vector>
 
 #include "common.h"
@@ -379,10 +378,8 @@ static hipError_t launch_cfg(const GemmArgs& a, hipStream_t s) {
       return hipGetLastError();
     }
   }
-  static const std::string name = std::string("pw_gemm_kernel<") + TypeName<T>::value + ", " + std::to_string(BM) + ", " +
-                                  std::to_string(BN) + ", " + std::to_string(WM) + ", " + std::to_string(WN) + ", " +
-                                  std::to_string(BK) + ">";
-  note_kernel(name.c_str());
+  static const char* const name = kernel_name<T>("pw_gemm_kernel", BM, BN, WM, WN, BK);
+  note_kernel(name);
   hipLaunchKernelGGL((pw_gemm_kernel<T, BM, BN, WM, WN, BK, false, RAGGED, KTAIL>), dim3(grid), dim3(NT), lds, s, a);
   return hipGetLastError();
 }
@@ -395,45 +392,36 @@ constexpr long kBk128MaxGrid = 1024;  // 128-wide K chunks for launches of up to
 template <typename T>
 static hipError_t launch_t(const GemmArgs& a, hipStream_t s) {
   const int BM = pw_gemm_tile_rows(a.P);
-  const int BN = (a.N % 128 == 0) ? 128 : ((a.N % 64 == 0) ? 64 : 32);
   // BN depends on N alone, never on the grid: the epilogue's statistics partials are summed per thread over rows r0 + i * (NT / (BN / VEC)),
   // so another BN is another summation order -- narrower tiles for tiny grids (measured in round 3: -1.6 % at B = 1) made a
   // batch differ from its halves in the last bits and were removed.
   bool k64 = sizeof(T) == 2;  // BK = 64 needs every K segment to be a multiple of 64 (2-byte T only)
   for (int i = 0; i < a.nseg; ++i) k64 = k64 && (a.seg[i].ch % 64 == 0);
   if (g_knobs.gemm_bk == 32) k64 = false;
-  if constexpr (sizeof(T) == 2) {
-    // small grids (about as many workgroups as the chip holds at once): a workgroup's time is chunks x memory latency, so
-    // twice the chunk: -10...-16 % on the long-K project layers of the low resolutions (and at B = 1), +10 % on large grids.
-    // The sequence of 32-wide k-steps per accumulator is unchanged: same bits, whatever the batch size chooses
-    if (BM == 128 && BN == 128 && (long)(a.M / 128) * (a.N / 128) <= kBk128MaxGrid) {
-      bool k128 = true;
-      for (int i = 0; i < a.nseg; ++i) k128 = k128 && (a.seg[i].ch % 128 == 0);
-      if (k128) return launch_cfg<T, 128, 128, 2, 2, 128>(a, s);
-    }
-  }
-  if (BM == 128) {
-    if constexpr (sizeof(T) == 2) {
-      // some segment has 64 n + 32 channels (the 96 -> 32 and 32 -> 64 blocks: K = 480, 160; `base`'s 48 / 96 / 144-channel shapes):
-      // 64-wide chunks with half-empty segment tails (KTAIL) instead of 32-wide ones
-      if (!k64 && g_knobs.gemm_bk != 32 && a.K > 64) {
-        if (BN == 128) return launch_cfg<T, 128, 128, 2, 2, 64, false, true>(a, s);
-        if (BN == 64) return launch_cfg<T, 128, 64, 2, 2, 64, false, true>(a, s);
-        return launch_cfg<T, 128, 32, 4, 1, 64, false, true>(a, s);
+  return with_value<128, 64, 32>((a.N % 128 == 0) ? 128 : ((a.N % 64 == 0) ? 64 : 32), [&](auto bn) {
+    // 32-column tiles are one wave wide (and four waves tall where they have 128 rows), all others 2 x 2 waves
+    constexpr int BN = decltype(bn)::value, WN = BN == 32 ? 1 : 2, WM128 = BN == 32 ? 4 : 2;
+    if constexpr (sizeof(T) == 2 && BN == 128) {
+      // small grids (about as many workgroups as the chip holds at once): a workgroup's time is chunks x memory latency, so
+      // twice the chunk: -10...-16 % on the long-K project layers of the low resolutions (and at B = 1), +10 % on large grids.
+      // The sequence of 32-wide k-steps per accumulator is unchanged: same bits, whatever the batch size chooses
+      if (BM == 128 && (long)(a.M / 128) * (a.N / 128) <= kBk128MaxGrid) {
+        bool k128 = true;
+        for (int i = 0; i < a.nseg; ++i) k128 = k128 && (a.seg[i].ch % 128 == 0);
+        if (k128) return launch_cfg<T, 128, 128, 2, 2, 128>(a, s);
       }
     }
-    if (BN == 128) return k64 ? launch_cfg<T, 128, 128, 2, 2, 64>(a, s) : launch_cfg<T, 128, 128, 2, 2, 32>(a, s);
-    if (BN == 64) return k64 ? launch_cfg<T, 128, 64, 2, 2, 64>(a, s) : launch_cfg<T, 128, 64, 2, 2, 32>(a, s);
-    return k64 ? launch_cfg<T, 128, 32, 4, 1, 64>(a, s) : launch_cfg<T, 128, 32, 4, 1, 32>(a, s);
-  }
-  if (a.P % 64) {  // the last 64-row tile of every image is partly empty (image sizes that are not a multiple of 64)
-    if (BN == 128) return launch_cfg<T, 64, 128, 2, 2, 32, true>(a, s);
-    if (BN == 64) return launch_cfg<T, 64, 64, 2, 2, 32, true>(a, s);
-    return launch_cfg<T, 64, 32, 2, 1, 32, true>(a, s);
-  }
-  if (BN == 128) return launch_cfg<T, 64, 128, 2, 2, 32>(a, s);
-  if (BN == 64) return launch_cfg<T, 64, 64, 2, 2, 32>(a, s);
-  return launch_cfg<T, 64, 32, 2, 1, 32>(a, s);
+    if (BM == 128) {
+      if constexpr (sizeof(T) == 2) {
+        // some segment has 64 n + 32 channels (the 96 -> 32 and 32 -> 64 blocks: K = 480, 160; `base`'s 48 / 96 / 144-channel shapes):
+        // 64-wide chunks with half-empty segment tails (KTAIL) instead of 32-wide ones
+        if (!k64 && g_knobs.gemm_bk != 32 && a.K > 64) return launch_cfg<T, 128, BN, WM128, WN, 64, false, true>(a, s);
+      }
+      return k64 ? launch_cfg<T, 128, BN, WM128, WN, 64>(a, s) : launch_cfg<T, 128, BN, WM128, WN, 32>(a, s);
+    }
+    // P % 64: the last 64-row tile of every image is partly empty (image sizes that are not a multiple of 64)
+    return a.P % 64 ? launch_cfg<T, 64, BN, 2, WN, 32, true>(a, s) : launch_cfg<T, 64, BN, 2, WN, 32>(a, s);
+  });
 }
 
 hipError_t launch_pw_gemm(int dtype, const GemmArgs& a, hipStream_t s) {
@@ -450,12 +438,7 @@ hipError_t launch_pw_gemm(int dtype, const GemmArgs& a, hipStream_t s) {
   for (int i = 0; i < a.nseg; ++i)  // the output scale of ACT_RELU6_S6 is per GEMM: all segments or none, 2-byte T only
     if ((a.seg[i].act == ACT_RELU6_S6) != (a.seg[0].act == ACT_RELU6_S6) || (a.seg[i].act == ACT_RELU6_S6 && (dtype == 0 || !a.seg[i].as)))
       return hipErrorInvalidValue;
-  switch (dtype) {
-    case 0: return launch_t<float>(a, s);
-    case 1: return launch_t<half_t>(a, s);
-    case 2: return launch_t<bf16_t>(a, s);
-  }
-  return hipErrorInvalidValue;
+  return with_dtype(dtype, [&](auto t) { return launch_t<decltype(t)>(a, s); });
 }
 
 }  // namespace llie

@@ -365,18 +365,6 @@ bool gram_supported(int dtype, int K, int c0, int P) {
   return c0 % 8 == 0 && P % 512 == 0 && P % gram_rows(K, P) == 0;
 }
 
-template <typename T>
-static hipError_t launch_gram_t(const GramArgs& a, int K, hipStream_t s) {
-  const dim3 grid(a.P / a.RP, 1, a.B);
-  switch (K) {
-    case 32: hipLaunchKernelGGL((gram_stats_kernel<T, 2>), grid, dim3(256), 0, s, a); break;
-    case 64: hipLaunchKernelGGL((gram_stats_kernel<T, 4>), grid, dim3(256), 0, s, a); break;
-    case 96: hipLaunchKernelGGL((gram_stats_kernel<T, 6>), grid, dim3(256), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
 hipError_t launch_gram_stats(int dtype, const GramArgs& a0, hipStream_t s) {
   GramArgs a = a0;
   const int K = a.c0 + a.c1;
@@ -384,25 +372,24 @@ hipError_t launch_gram_stats(int dtype, const GramArgs& a0, hipStream_t s) {
     return hipErrorInvalidValue;
   a.RP = gram_rows(K, a.P);
   note_kernel("gram_stats_kernel");
-  return dtype == 1 ? launch_gram_t<half_t>(a, K, s) : launch_gram_t<bf16_t>(a, K, s);
+  return with_dtype2(dtype, [&](auto t) {
+    return with_value<32, 64, 96>(K, [&](auto k) {
+      hipLaunchKernelGGL((gram_stats_kernel<decltype(t), decltype(k)::value / 16>), dim3(a.P / a.RP, 1, a.B), dim3(256), 0, s, a);
+      return hipGetLastError();
+    });
+  });
 }
 
-template <typename T>
-static hipError_t launch_gram_finalize_t(const GramFinalizeArgs& a, hipStream_t s) {
-  const dim3 grid(a.groups, a.B);
-  switch (a.K) {
-    case 32: hipLaunchKernelGGL((gram_finalize_kernel<T, 32>), grid, dim3(256), 0, s, a); break;
-    case 64: hipLaunchKernelGGL((gram_finalize_kernel<T, 64>), grid, dim3(256), 0, s, a); break;
-    case 96: hipLaunchKernelGGL((gram_finalize_kernel<T, 96>), grid, dim3(256), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
 hipError_t launch_gram_finalize(int dtype, const GramFinalizeArgs& a, hipStream_t s) {
   // the recompute blocks of this engine: Chid = 4 K, nn.GroupNorm(32, Chid)
   if ((dtype != 1 && dtype != 2) || !a.gtot || !a.w1 || !a.as || !a.ab || a.groups != 32 || a.Chid != 4 * a.K || a.B <= 0) return hipErrorInvalidValue;
   note_kernel("gram_finalize_kernel");
-  return dtype == 1 ? launch_gram_finalize_t<half_t>(a, s) : launch_gram_finalize_t<bf16_t>(a, s);
+  return with_dtype2(dtype, [&](auto t) {
+    return with_value<32, 64, 96>(a.K, [&](auto k) {
+      hipLaunchKernelGGL((gram_finalize_kernel<decltype(t), decltype(k)::value>), dim3(a.groups, a.B), dim3(256), 0, s, a);
+      return hipGetLastError();
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -656,9 +643,11 @@ hipError_t launch_gram_wide(int dtype, const GramWideArgs& a0, hipStream_t s) {
   a.RP = gram_wide_rows(a.P);
   const int nwg = a.P / a.RP;
   note_kernel("gram_wide_kernel");
-  if (dtype == 1) hipLaunchKernelGGL((gram_wide_kernel<half_t>), dim3(nwg, 1, a.B), dim3(192), 0, s, a);
-  else hipLaunchKernelGGL((gram_wide_kernel<bf16_t>), dim3(nwg, 1, a.B), dim3(192), 0, s, a);
-  if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+  const hipError_t e = with_dtype2(dtype, [&](auto t) {
+    hipLaunchKernelGGL((gram_wide_kernel<decltype(t)>), dim3(nwg, 1, a.B), dim3(192), 0, s, a);
+    return hipGetLastError();
+  });
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(gram_wide_reduce_kernel, dim3(kGramWideBlocks + 1, a.B), dim3(256), 0, s, a, nwg);
   return hipGetLastError();
 }
@@ -670,11 +659,13 @@ hipError_t launch_gram_group_finalize(const GramGroupFinalizeArgs& a, hipStream_
   return hipGetLastError();
 }
 hipError_t launch_gram_group_weights(int dtype, const void* wpack, double* mg, int Chid, int K, hipStream_t s, const unsigned long long* state) {
-  if ((dtype != 1 && dtype != 2) || !wpack || !mg || K != kGramWideK || Chid != 4 * K) return hipErrorInvalidValue;
+  if (!wpack || !mg || K != kGramWideK || Chid != 4 * K) return hipErrorInvalidValue;
   const dim3 grid(kGramWideBlocks + 1, 32);
-  if (dtype == 1) hipLaunchKernelGGL((gram_group_weights_kernel<half_t>), grid, dim3(256), 0, s, reinterpret_cast<const half_t*>(wpack), mg, Chid, 32, state);
-  else hipLaunchKernelGGL((gram_group_weights_kernel<bf16_t>), grid, dim3(256), 0, s, reinterpret_cast<const bf16_t*>(wpack), mg, Chid, 32, state);
-  return hipGetLastError();
+  return with_dtype2(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL((gram_group_weights_kernel<T>), grid, dim3(256), 0, s, reinterpret_cast<const T*>(wpack), mg, Chid, 32, state);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace llie

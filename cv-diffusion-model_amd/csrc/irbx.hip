@@ -19,7 +19,6 @@
 // The GroupNorm partial sums are fixed per-tile slab entries; the SE pool sums go into per-image 64-bit fixed-point
 // totals with integer atomics (integer adds commute).  No float atomics, so results stay bitwise independent of the
 // batch and of the schedule.
-#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -1347,9 +1346,8 @@ StampSink g_irbx_stamps{kXStamps, 0};  // cycles per wave, the slots listed at S
 template <typename T, int KS, int NBW, bool POOL>
 static hipError_t launch_scan_cfg(const IrbxArgs& a, hipStream_t s) {
   const int P = a.H * a.W, RP = irbx_stats_rows(P);
-  static const std::string name = std::string(POOL ? "expand_pool_kernel<" : "expand_stats_kernel<") + TypeName<T>::value + ", " +
-                                  std::to_string(KS) + ", " + std::to_string(NBW) + ">";
-  note_kernel(name.c_str());
+  static const char* const name = kernel_name<T>(POOL ? "expand_pool_kernel" : "expand_stats_kernel", KS, NBW);
+  note_kernel(name);
   if constexpr (POOL && std::is_same<T, half_t>::value) {
     if (g_knobs.irbx_stamp == 2) {  // diagnostic build: in-kernel cycle stamps
       IrbxArgs b = a;
@@ -1362,24 +1360,24 @@ static hipError_t launch_scan_cfg(const IrbxArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(kernel, dim3(P / RP, 1, a.B), dim3(256), 0, s, a, RP);
   return hipGetLastError();
 }
-template <typename T, bool POOL>
-static hipError_t launch_scan_t(const IrbxArgs& a, hipStream_t s) {
-  switch (a.c0 + a.c1) {  // Chid = 4 Cin: irbx_supported
-    case 32: return launch_scan_cfg<T, 2, 1, POOL>(a, s);
-    case 64: return launch_scan_cfg<T, 4, 2, POOL>(a, s);
-    case 96: return launch_scan_cfg<T, 6, 3, POOL>(a, s);
-  }
-  return hipErrorInvalidValue;
+template <bool POOL>
+static hipError_t launch_scan(int dtype, const IrbxArgs& a, hipStream_t s) {
+  return with_dtype2(dtype, [&](auto t) {
+    return with_value<32, 64, 96>(a.c0 + a.c1, [&](auto cin) {  // Chid = 4 Cin: irbx_supported
+      constexpr int NBW = decltype(cin)::value / 32;
+      return launch_scan_cfg<decltype(t), 2 * NBW, NBW, POOL>(a, s);
+    });
+  });
 }
 hipError_t launch_expand_stats(int dtype, const IrbxArgs& a, hipStream_t s) {
   if (!irbx_supported(dtype, a.c0 + a.c1, a.c0, a.Chid, a.H, a.W) || (a.c1 && !a.x1) || !a.stats) return hipErrorInvalidValue;
-  return dtype == 1 ? launch_scan_t<half_t, false>(a, s) : launch_scan_t<bf16_t, false>(a, s);
+  return launch_scan<false>(dtype, a, s);
 }
 // pool_tot += the image's SE pool totals (fixed point, kPoolFixScale); the caller zeroes it
 hipError_t launch_expand_pool(int dtype, const IrbxArgs& a, hipStream_t s) {
   if (!irbx_supported(dtype, a.c0 + a.c1, a.c0, a.Chid, a.H, a.W) || (a.c1 && !a.x1) || !a.pool_tot || !a.as2 || !a.ab2 || !a.wd)
     return hipErrorInvalidValue;
-  return dtype == 1 ? launch_scan_t<half_t, true>(a, s) : launch_scan_t<bf16_t, true>(a, s);
+  return launch_scan<true>(dtype, a, s);
 }
 
 constexpr int kXTilesPerWg = 4;  // longest run of tiles along x one workgroup takes
@@ -1422,9 +1420,8 @@ static hipError_t launch_dw_cfg(const IrbxArgs& a, hipStream_t s) {
   const size_t lds = irbx_lds_bytes(KS, a.Chid, DBUF, 0);
   const IrbxPlan plan = irbx_plan(16 * KS, a.B, a.H, a.W, false);
   const int tpw = plan.tpw, cpw = plan.cpw;
-  static const std::string name = std::string("expand_dw_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) + ", " +
-                                  (DBUF ? "1" : "0") + ">";
-  note_kernel(name.c_str());
+  static const char* const name = kernel_name<T>("expand_dw_kernel", KS, (int)DBUF);
+  note_kernel(name);
   const dim3 grid(plan.gx, plan.gy, a.B);
   if constexpr (std::is_same<T, half_t>::value && !DBUF) {
     if (g_knobs.irbx_stamp == 1) {  // diagnostic build: in-kernel cycle stamps (fp16 only)
@@ -1438,26 +1435,14 @@ static hipError_t launch_dw_cfg(const IrbxArgs& a, hipStream_t s) {
   }
   return launch_dw_one<T, KS, DBUF, false, false>(a, grid, lds, tpw, cpw, s);
 }
-template <typename T>
-static hipError_t launch_dw_t(const IrbxArgs& a, hipStream_t s) {
-  const int Cin = a.c0 + a.c1;
-  // llie_tune("irbx_dbuf", 1): double-buffered h1 tile for the 32-channel inputs (one barrier per chunk, 76 KB of LDS = two
-  // workgroups per CU).  The single-buffered kernel (49 KB, three workgroups per CU) is the default: 1 % faster end to end
-  switch (Cin) {
-    case 32: return g_knobs.irbx_dbuf ? launch_dw_cfg<T, 2, true>(a, s) : launch_dw_cfg<T, 2, false>(a, s);
-    case 64: return launch_dw_cfg<T, 4, false>(a, s);
-    case 96: return launch_dw_cfg<T, 6, false>(a, s);
-  }
-  return hipErrorInvalidValue;
-}
 template <typename T, int KS, int PCO>
 static hipError_t launch_project_cfg(const IrbxArgs& a, hipStream_t s) {
   const size_t lds = irbx_lds_bytes(KS, a.Chid, false, PCO);
   const IrbxPlan plan = irbx_plan(16 * KS, a.B, a.H, a.W, true);
   const int tpw = plan.tpw;
-  static const std::string name = std::string("expand_dw_project_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) +
-                                  (PCO == 16 * KS ? std::string() : ", " + std::to_string(PCO)) + ">";
-  note_kernel(name.c_str());
+  // PCO = 16 KS is the kernel's default argument, which the profiler's name leaves out
+  static const char* const name = PCO == 16 * KS ? kernel_name<T>("expand_dw_project_kernel", KS) : kernel_name<T>("expand_dw_project_kernel", KS, PCO);
+  note_kernel(name);
   if constexpr (std::is_same<T, half_t>::value) {
     if (g_knobs.irbx_stamp == 3) {  // diagnostic build: in-kernel cycle stamps (fp16 only)
       IrbxArgs b = a;
@@ -1474,11 +1459,6 @@ static hipError_t launch_project_cfg(const IrbxArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((expand_dw_project_kernel<T, KS, PCO>), dim3(plan.gx, plan.gy, a.B), dim3(256), lds, s, a, tpw);
   return hipGetLastError();
 }
-template <typename T>
-static hipError_t launch_project_t(const IrbxArgs& a, int form, hipStream_t s) {
-  if (form == kIrbxProjectSkip) return launch_project_cfg<T, 6, 32>(a, s);
-  return a.c0 == 32 ? launch_project_cfg<T, 2, 32>(a, s) : launch_project_cfg<T, 4, 64>(a, s);
-}
 // y = Wp . (gate * dw3x3(relu6(aff2(W1 . relu6(aff1(x)))))) + shortcut with y's statistics slab [B][irbx_project_tiles][2][Cout].
 // !skip: the identity form (shortcut x, one segment, wp [cout][Chid], cout = Cin = c0; a.ldp is set here); skip: the skip form
 // (shortcut Wskip . x, wp [cout][a.ldp] = project columns, then skip columns, a.ldp >= Chid + Cin)
@@ -1490,11 +1470,26 @@ hipError_t launch_expand_dw_project(int dtype, const IrbxArgs& a0, int cout, boo
   if (!form || (a.c1 != 0) != (a.x1 != nullptr) || a.ldp < a.Chid + (skip ? Cin : 0) || a.ldp % 8 || !a.gate || !a.wp || !a.y || !a.ystats ||
       !a.as2 || !a.ab2 || !a.wd)
     return hipErrorInvalidValue;
-  return dtype == 1 ? launch_project_t<half_t>(a, form, s) : launch_project_t<bf16_t>(a, form, s);
+  return with_dtype2(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (form == kIrbxProjectSkip) return launch_project_cfg<T, 6, 32>(a, s);
+    return a.c0 == 32 ? launch_project_cfg<T, 2, 32>(a, s) : launch_project_cfg<T, 4, 64>(a, s);
+  });
 }
 hipError_t launch_expand_dw(int dtype, const IrbxArgs& a, hipStream_t s) {
   if (!irbx_supported(dtype, a.c0 + a.c1, a.c0, a.Chid, a.H, a.W) || (a.c1 && !a.x1) || !a.out) return hipErrorInvalidValue;
-  return dtype == 1 ? launch_dw_t<half_t>(a, s) : launch_dw_t<bf16_t>(a, s);
+  return with_dtype2(dtype, [&](auto t) {
+    using T = decltype(t);
+    return with_value<32, 64, 96>(a.c0 + a.c1, [&](auto cin) {
+      constexpr int KS = decltype(cin)::value / 16;
+      // llie_tune("irbx_dbuf", 1): double-buffered h1 tile for the 32-channel inputs (one barrier per chunk, 76 KB of LDS = two
+      // workgroups per CU).  The single-buffered kernel (49 KB, three workgroups per CU) is the default: 1 % faster end to end
+      if constexpr (KS == 2) {
+        if (g_knobs.irbx_dbuf) return launch_dw_cfg<T, KS, true>(a, s);
+      }
+      return launch_dw_cfg<T, KS, false>(a, s);
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1814,17 +1809,18 @@ hipError_t launch_dwconv3x3_pool(int dtype, const IrbxArgs& a, hipStream_t s) {
       !a.pool_tot || !a.as2 || !a.ab2 || !a.wd)
     return hipErrorInvalidValue;
   const dim3 grid(a.H / kWpRows, a.Chid / 128, a.B);
-  static const std::string names[2] = {std::string("dwconv3x3_pool_kernel<") + TypeName<half_t>::value + ">",
-                                       std::string("dwconv3x3_pool_kernel<") + TypeName<bf16_t>::value + ">"};
-  note_kernel(names[dtype - 1].c_str());
-  if (dtype == 1) hipLaunchKernelGGL((dwconv3x3_pool_kernel<half_t>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((dwconv3x3_pool_kernel<bf16_t>), grid, dim3(256), 0, s, a);
-  return hipGetLastError();
+  return with_dtype2(dtype, [&](auto t) {
+    using T = decltype(t);
+    static const char* const name = kernel_name<T>("dwconv3x3_pool_kernel");
+    note_kernel(name);
+    hipLaunchKernelGGL((dwconv3x3_pool_kernel<T>), grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+  });
 }
 template <typename T, int PCO, bool PREACT = false>
 static hipError_t launch_wide_project_cfg(const IrbxArgs& a, hipStream_t s) {
-  static const std::string name = std::string("dwconv3x3_project_kernel<") + TypeName<T>::value + ", " + std::to_string(PCO) + (PREACT ? ", true>" : ">");
-  note_kernel(name.c_str());
+  static const char* const name = PREACT ? kernel_name<T>("dwconv3x3_project_kernel", PCO, true) : kernel_name<T>("dwconv3x3_project_kernel", PCO);
+  note_kernel(name);
   static std::atomic<uint64_t> attr_done{0};
   if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&dwconv3x3_project_kernel<T, PCO, PREACT>), 128 * 1024, attr_done); e != hipSuccess) return e;
   hipLaunchKernelGGL((dwconv3x3_project_kernel<T, PCO, PREACT>), dim3(irbx_project_tiles(a.H, a.W), 1, a.B), dim3(256), wide_lds_bytes(a.Chid, PCO), s, a);
@@ -1837,12 +1833,12 @@ hipError_t launch_dwconv3x3_project(int dtype, const IrbxArgs& a, int cout, hipS
   if (!wide_project_supported(dtype, Cin, a.c0, a.Chid, cout, true, false, a.H, a.W) || a.B <= 0 || (a.c1 != 0) != (a.x1 != nullptr) || !a.x0 ||
       a.ldp < a.Chid + Cin || a.ldp % 8 || !a.h1 || !a.gate || !a.wp || !a.y || !a.ystats || (!a.h1_act && (!a.as2 || !a.ab2)) || !a.wd)
     return hipErrorInvalidValue;
-  if (a.h1_act) {  // the activated h1 of pw_expand_act: 192 -> 64 only
-    if (cout != 64) return hipErrorInvalidValue;
-    return dtype == 1 ? launch_wide_project_cfg<half_t, 64, true>(a, s) : launch_wide_project_cfg<bf16_t, 64, true>(a, s);
-  }
-  if (cout == 64) return dtype == 1 ? launch_wide_project_cfg<half_t, 64>(a, s) : launch_wide_project_cfg<bf16_t, 64>(a, s);
-  return dtype == 1 ? launch_wide_project_cfg<half_t, 128>(a, s) : launch_wide_project_cfg<bf16_t, 128>(a, s);
+  if (a.h1_act && cout != 64) return hipErrorInvalidValue;  // the activated h1 of pw_expand_act: 192 -> 64 only
+  return with_dtype2(dtype, [&](auto t) {
+    using T = decltype(t);
+    if (a.h1_act) return launch_wide_project_cfg<T, 64, true>(a, s);
+    return cout == 64 ? launch_wide_project_cfg<T, 64>(a, s) : launch_wide_project_cfg<T, 128>(a, s);
+  });
 }
 
 }  // namespace llie

@@ -24,7 +24,6 @@
 //     profiles/r03/pwx_store_shape.txt), a steady trickle under the next block's MFMAs instead of a burst per tile.
 //
 // Statistics are fixed per-(128-pixel tile, channel) slab entries summed in a fixed order: bitwise independent of the batch.
-#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -386,10 +385,11 @@ __global__ void pack_expand_kernel(const float* __restrict__ src, T* __restrict_
 hipError_t launch_pack_expand(int dtype, const float* src, void* dst, int N, int K, float scale, hipStream_t s) {
   if (N % 32 || K % 16) return hipErrorInvalidValue;
   const dim3 grid((unsigned)(((long long)N * K + 255) / 256));
-  if (dtype == 1) hipLaunchKernelGGL(pack_expand_kernel<half_t>, grid, dim3(256), 0, s, src, reinterpret_cast<half_t*>(dst), N, K, scale);
-  else if (dtype == 2) hipLaunchKernelGGL(pack_expand_kernel<bf16_t>, grid, dim3(256), 0, s, src, reinterpret_cast<bf16_t*>(dst), N, K, scale);
-  else return hipErrorInvalidValue;
-  return hipGetLastError();
+  return with_dtype2(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(pack_expand_kernel<T>, grid, dim3(256), 0, s, src, reinterpret_cast<T*>(dst), N, K, scale);
+    return hipGetLastError();
+  });
 }
 
 // 32-channel blocks per LDS buffer.  One everywhere: the smaller LDS footprint (three workgroups per CU up to K = 256) is
@@ -426,8 +426,8 @@ static hipError_t launch_one(ExpandArgs a, hipStream_t s) {
 template <typename T, int KS, int NBW = kPwxNbw>
 static hipError_t launch_cfg(ExpandArgs a, hipStream_t s) {
   a.nsplit = nsplit_for(a.M, a.N, NBW);
-  static const std::string name = std::string("pw_expand_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) + ", " + std::to_string(NBW) + ">";
-  note_kernel(name.c_str());
+  static const char* const name = kernel_name<T>("pw_expand_kernel", KS, NBW);
+  note_kernel(name);
   if constexpr (std::is_same<T, half_t>::value && (KS == 12 || KS == 24)) {  // diagnostics for two representative shapes only
     if (g_knobs.pwx_stamp) {
       if (hipError_t e = g_pwx_stamps.arm((size_t)(a.M / 128) * a.nsplit * 4, &a.stamps); e != hipSuccess) return e;
@@ -436,17 +436,6 @@ static hipError_t launch_cfg(ExpandArgs a, hipStream_t s) {
   }
   // K = 512: the LDS tile would leave room for one workgroup per CU only (64 KB of weight buffers): registers -> HBM there
   return launch_one<T, KS, NBW, KS == 32>(a, s);
-}
-template <typename T>
-static hipError_t launch_t(const ExpandArgs& a, hipStream_t s) {
-  switch (a.K) {
-    case 128: return launch_cfg<T, 8>(a, s);
-    case 192: return launch_cfg<T, 12>(a, s);
-    case 256: return launch_cfg<T, 16>(a, s);
-    case 384: return launch_cfg<T, 24>(a, s);
-    case 512: return launch_cfg<T, 32>(a, s);
-  }
-  return hipErrorInvalidValue;
 }
 // The border part of the SE pool totals of an ACTIVATED h1 [B][H][W][N]: a tap (ky, kx) of the zero-padded depthwise conv reads pixel
 // p + (ky - 1, kx - 1), so summed over the image it misses the far border row and / or column (dwconv3x3_pool_kernel's table).
@@ -504,8 +493,8 @@ static hipError_t launch_act_t(ExpandArgs a, hipStream_t s) {
   constexpr int KS = 12, NBW = kPwxNbw, lds = pwx_lds_bytes(KS, NBW, false) + 3 * kPwxActMaxN * 4;
   static_assert(3 * lds <= 160 * 1024, "three workgroups per CU, as pw_expand_kernel<T, 12, 1>");
   a.nsplit = nsplit_for(a.M, a.N, NBW);
-  static const std::string name = std::string("pw_expand_act_kernel<") + TypeName<T>::value + ", " + std::to_string(KS) + ", " + std::to_string(NBW) + ">";
-  note_kernel(name.c_str());
+  static const char* const name = kernel_name<T>("pw_expand_act_kernel", KS, NBW);
+  note_kernel(name);
   static std::atomic<uint64_t> attr_done{0};
   if (hipError_t e = ensure_max_lds(reinterpret_cast<const void*>(&pw_expand_act_kernel<T, KS, NBW>), lds, attr_done); e != hipSuccess) return e;
   hipLaunchKernelGGL((pw_expand_act_kernel<T, KS, NBW>), dim3((unsigned)((a.M / 128) * a.nsplit)), dim3(256), lds, s, a);
@@ -517,12 +506,14 @@ static hipError_t launch_act_t(ExpandArgs a, hipStream_t s) {
 hipError_t launch_pw_expand_act(int dtype, const ExpandArgs& a, hipStream_t s) {
   if (!a.wf || !a.out || !a.as2 || !a.ab2 || !a.wd || !a.pool_tot || !pw_expand_act_supported(dtype, a.seg, a.nseg, a.M, a.N, a.K, a.P, a.H, a.W))
     return hipErrorInvalidValue;
-  return dtype == 1 ? launch_act_t<half_t>(a, s) : launch_act_t<bf16_t>(a, s);
+  return with_dtype2(dtype, [&](auto t) { return launch_act_t<decltype(t)>(a, s); });
 }
 hipError_t launch_pw_expand(int dtype, const ExpandArgs& a, hipStream_t s) {
   // host-side shape contract (an out-of-contract shape would index out of bounds on the device)
   if (!a.wf || !a.out || !a.stats || !pw_expand_supported(dtype, a.seg, a.nseg, a.M, a.N, a.K, a.P)) return hipErrorInvalidValue;
-  return dtype == 1 ? launch_t<half_t>(a, s) : launch_t<bf16_t>(a, s);
+  return with_dtype2(dtype, [&](auto t) {
+    return with_value<128, 192, 256, 384, 512>(a.K, [&](auto k) { return launch_cfg<decltype(t), decltype(k)::value / 16>(a, s); });
+  });
 }
 
 }  // namespace llie

@@ -484,14 +484,12 @@ hipError_t launch_se_mlp_mfma(int dtype, const SeArgs& a, hipStream_t s) {
   note_kernel("se_fc1_mfma_kernel+se_fc2_mfma_kernel");
   const int ksl = a.C / 256, kw = 64;  // 256 channels of K per workgroup, 64 per wave (4 k-steps)
   const dim3 g1(a.Cs / 32, ksl, (a.B + 31) / 32), g2(a.C / 32, (a.B + 31) / 32);
-  if (dtype == 1) {
-    hipLaunchKernelGGL(se_fc1_mfma_kernel<half_t>, g1, dim3(256), 0, s, a, kw);
-    hipLaunchKernelGGL(se_fc2_mfma_kernel<half_t>, g2, dim3(256), 0, s, a);
-  } else {
-    hipLaunchKernelGGL(se_fc1_mfma_kernel<bf16_t>, g1, dim3(256), 0, s, a, kw);
-    hipLaunchKernelGGL(se_fc2_mfma_kernel<bf16_t>, g2, dim3(256), 0, s, a);
-  }
-  return hipGetLastError();
+  return with_dtype2(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(se_fc1_mfma_kernel<T>, g1, dim3(256), 0, s, a, kw);
+    hipLaunchKernelGGL(se_fc2_mfma_kernel<T>, g2, dim3(256), 0, s, a);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_se_gate(int dtype, const SeArgs& a, hipStream_t s) {
@@ -503,13 +501,10 @@ hipError_t launch_se_gate(int dtype, const SeArgs& a, hipStream_t s) {
   if (G < 1) G = 1;
   while (a.C % G) --G;
   note_kernel("se_gate_kernel");
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(se_gate_kernel<float>, dim3(G, a.B), dim3(1024), lds, s, a); break;
-    case 1: hipLaunchKernelGGL(se_gate_kernel<half_t>, dim3(G, a.B), dim3(1024), lds, s, a); break;
-    case 2: hipLaunchKernelGGL(se_gate_kernel<bf16_t>, dim3(G, a.B), dim3(1024), lds, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(se_gate_kernel<decltype(t)>, dim3(G, a.B), dim3(1024), lds, s, a);
+    return hipGetLastError();
+  });
 }
 
 hipError_t launch_se_fc1(int dtype, const SeArgs& a, hipStream_t s) {
@@ -517,24 +512,18 @@ hipError_t launch_se_fc1(int dtype, const SeArgs& a, hipStream_t s) {
   if (!a.tot) hipLaunchKernelGGL(se_pool_kernel, dim3((a.C + 63) / 64, a.B), dim3(256), 0, s, a);
   dim3 grid((a.Cs + kSeRows - 1) / kSeRows, (a.B + kSeMaxB - 1) / kSeMaxB);
   const size_t lds = (size_t)kSeMaxB * a.C * 4;
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(se_fc1_kernel<float>, grid, dim3(256), lds, s, a); break;
-    case 1: hipLaunchKernelGGL(se_fc1_kernel<half_t>, grid, dim3(256), lds, s, a); break;
-    case 2: hipLaunchKernelGGL(se_fc1_kernel<bf16_t>, grid, dim3(256), lds, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(se_fc1_kernel<decltype(t)>, grid, dim3(256), lds, s, a);
+    return hipGetLastError();
+  });
 }
 hipError_t launch_se_fc2(int dtype, const SeArgs& a, hipStream_t s) {
   dim3 grid((a.C + kSeRows - 1) / kSeRows, (a.B + kSeMaxB - 1) / kSeMaxB);
   const size_t lds = (size_t)kSeMaxB * a.Cs * 4;
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(se_fc2_kernel<float>, grid, dim3(256), lds, s, a); break;
-    case 1: hipLaunchKernelGGL(se_fc2_kernel<half_t>, grid, dim3(256), lds, s, a); break;
-    case 2: hipLaunchKernelGGL(se_fc2_kernel<bf16_t>, grid, dim3(256), lds, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(se_fc2_kernel<decltype(t)>, grid, dim3(256), lds, s, a);
+    return hipGetLastError();
+  });
 }
 
 // =============================================================================================
@@ -708,23 +697,17 @@ int linattn_nsplit(int N) {
 hipError_t launch_linattn_kv(int dtype, const AttnArgs& a, hipStream_t s) {
   if (a.nsplit < 1 || a.N % a.nsplit || (a.nsplit > 1 && a.N % (64 * a.nsplit))) return hipErrorInvalidValue;
   dim3 grid(a.heads, a.B, a.nsplit);
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(linattn_kv_kernel<float>, grid, dim3(256), 0, s, a); break;
-    case 1: hipLaunchKernelGGL(linattn_kv_kernel<half_t>, grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(linattn_kv_kernel<bf16_t>, grid, dim3(256), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(linattn_kv_kernel<decltype(t)>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+  });
 }
 hipError_t launch_linattn_out(int dtype, const AttnArgs& a, hipStream_t s) {
   dim3 grid((a.N + 63) / 64, a.heads, a.B);
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(linattn_out_kernel<float>, grid, dim3(256), 0, s, a); break;
-    case 1: hipLaunchKernelGGL(linattn_out_kernel<half_t>, grid, dim3(256), 0, s, a); break;
-    case 2: hipLaunchKernelGGL(linattn_out_kernel<bf16_t>, grid, dim3(256), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(linattn_out_kernel<decltype(t)>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+  });
 }
 
 // =============================================================================================
@@ -801,13 +784,10 @@ hipError_t launch_affine_add(int dtype, const AffineAddArgs& a, hipStream_t s) {
   if (a.P < 1 || a.M % a.P || a.C % 8) return hipErrorInvalidValue;
   dim3 grid((a.M / a.P) * ((a.P + kAffineTileRows - 1) / kAffineTileRows));
   const size_t lds = (size_t)8 * a.C * 4;
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(affine_add_kernel<float>, grid, dim3(256), lds, s, a); break;
-    case 1: hipLaunchKernelGGL(affine_add_kernel<half_t>, grid, dim3(256), lds, s, a); break;
-    case 2: hipLaunchKernelGGL(affine_add_kernel<bf16_t>, grid, dim3(256), lds, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(affine_add_kernel<decltype(t)>, grid, dim3(256), lds, s, a);
+    return hipGetLastError();
+  });
 }
 
 // =============================================================================================
@@ -864,25 +844,21 @@ hipError_t launch_nchw_to_nhwc(int dtype, const float* x, void* y, float* stats,
                                hipStream_t s) {
   if (P < 1 || C % 32) return hipErrorInvalidValue;
   dim3 grid((P + 63) / 64, B, C / 32);
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, grid, dim3(256), 0, s, x, (float*)y, stats, C, P, Csrc, coff); break;
-    case 1: hipLaunchKernelGGL(nchw_to_nhwc_kernel<half_t>, grid, dim3(256), 0, s, x, (half_t*)y, stats, C, P, Csrc, coff); break;
-    case 2: hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, grid, dim3(256), 0, s, x, (bf16_t*)y, stats, C, P, Csrc, coff); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel<T>, grid, dim3(256), 0, s, x, (T*)y, stats, C, P, Csrc, coff);
+    return hipGetLastError();
+  });
 }
 hipError_t launch_nhwc_to_nchw(int dtype, const void* x, float* y, int B, int C, int P, hipStream_t s, int Cdst, int coff) {
   if (Cdst <= 0) Cdst = C;
   if (P < 1 || C % 32) return hipErrorInvalidValue;
   dim3 grid((P + 63) / 64, B, C / 32);
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, grid, dim3(256), 0, s, (const float*)x, y, C, P, Cdst, coff); break;
-    case 1: hipLaunchKernelGGL(nhwc_to_nchw_kernel<half_t>, grid, dim3(256), 0, s, (const half_t*)x, y, C, P, Cdst, coff); break;
-    case 2: hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, y, C, P, Cdst, coff); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(nhwc_to_nchw_kernel<T>, grid, dim3(256), 0, s, (const T*)x, y, C, P, Cdst, coff);
+    return hipGetLastError();
+  });
 }
 
 // =============================================================================================
@@ -928,11 +904,13 @@ __global__ void __launch_bounds__(256) upconv_fold_kernel(const float* src, T* d
   dst[idx] = (T)f;
 }
 hipError_t launch_upconv_fold(int dtype, const float* src, void* dst, int C, hipStream_t s, const unsigned long long* state) {
-  if (C < 1 || (dtype != 1 && dtype != 2)) return hipErrorInvalidValue;
+  if (C < 1) return hipErrorInvalidValue;
   dim3 grid((unsigned)((64LL * C * C + 255) / 256));
-  if (dtype == 1) hipLaunchKernelGGL(upconv_fold_kernel<half_t>, grid, dim3(256), 0, s, src, (half_t*)dst, C, state);
-  else hipLaunchKernelGGL(upconv_fold_kernel<bf16_t>, grid, dim3(256), 0, s, src, (bf16_t*)dst, C, state);
-  return hipGetLastError();
+  return with_dtype2(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipLaunchKernelGGL(upconv_fold_kernel<T>, grid, dim3(256), 0, s, src, (T*)dst, C, state);
+    return hipGetLastError();
+  });
 }
 
 // Content hash of every parameter (fp32 bits, position-weighted, summed mod 2^64: the order of the partial sums does
@@ -1029,23 +1007,17 @@ template <typename T>
 __global__ void __launch_bounds__(256) load_one_kernel(const LoadDesc d, char* blob) { load_one<T>(d, blob); }
 hipError_t launch_load_all(int dtype, const LoadDesc* descs_dev, int n, char* blob, hipStream_t s, const unsigned long long* state) {
   dim3 grid(32, n);
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(load_all_kernel<float>, grid, dim3(256), 0, s, descs_dev, blob, state); break;
-    case 1: hipLaunchKernelGGL(load_all_kernel<half_t>, grid, dim3(256), 0, s, descs_dev, blob, state); break;
-    case 2: hipLaunchKernelGGL(load_all_kernel<bf16_t>, grid, dim3(256), 0, s, descs_dev, blob, state); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(load_all_kernel<decltype(t)>, grid, dim3(256), 0, s, descs_dev, blob, state);
+    return hipGetLastError();
+  });
 }
 hipError_t launch_load_one(int dtype, const LoadDesc& d, char* blob, hipStream_t s) {
   dim3 grid((unsigned)((d.numel + 255) / 256));
-  switch (dtype) {
-    case 0: hipLaunchKernelGGL(load_one_kernel<float>, grid, dim3(256), 0, s, d, blob); break;
-    case 1: hipLaunchKernelGGL(load_one_kernel<half_t>, grid, dim3(256), 0, s, d, blob); break;
-    case 2: hipLaunchKernelGGL(load_one_kernel<bf16_t>, grid, dim3(256), 0, s, d, blob); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    hipLaunchKernelGGL(load_one_kernel<decltype(t)>, grid, dim3(256), 0, s, d, blob);
+    return hipGetLastError();
+  });
 }
 
 // =============================================================================================
@@ -1267,17 +1239,14 @@ hipError_t launch_rw_probe(const void* src, void* dst, int64_t units, int r, int
     hipLaunchKernelGGL(tiny_probe_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<unsigned*>(dst));
     return hipGetLastError();
   }
-#define LLIE_RW(RR, WW)                                                                                   \
-  if (r == RR && w == WW) {                                                                               \
-    if (nt == 1) hipLaunchKernelGGL((rw_probe_kernel<RR, WW, 1>), grid, block, 0, s, a, b, units);        \
-    else if (nt == 2) hipLaunchKernelGGL((rw_probe_kernel<RR, WW, 2>), grid, block, 0, s, a, b, units);   \
-    else if (nt == 3) hipLaunchKernelGGL((rw_probe_kernel<RR, WW, 3>), grid, block, 0, s, a, b, units);   \
-    else hipLaunchKernelGGL((rw_probe_kernel<RR, WW, 0>), grid, block, 0, s, a, b, units);                \
-    return hipGetLastError();                                                                             \
-  }
-  LLIE_RW(1, 0) LLIE_RW(0, 1) LLIE_RW(1, 1) LLIE_RW(1, 2) LLIE_RW(1, 4) LLIE_RW(2, 1) LLIE_RW(4, 1)
-#undef LLIE_RW
-  return hipErrorInvalidValue;
+  if (r < 0 || r > 4 || w < 0 || w > 4) return hipErrorInvalidValue;
+  return with_value<10, 1, 11, 12, 14, 21, 41>(10 * r + w, [&](auto rw) {  // the read : write mixes that exist, as 10 R + W
+    constexpr int R = decltype(rw)::value / 10, W = decltype(rw)::value % 10;
+    return with_value<1, 2, 3, 0>(nt >= 1 && nt <= 3 ? nt : 0, [&](auto mode) {
+      hipLaunchKernelGGL((rw_probe_kernel<R, W, decltype(mode)::value>), grid, block, 0, s, a, b, units);
+      return hipGetLastError();
+    });
+  });
 }
 
 }  // namespace llie

@@ -332,30 +332,25 @@ static bool sa_ok(int B, int N, int heads) {
 hipError_t launch_softattn_fwd(int dtype, const SoftAttnArgs& a, hipStream_t s) {
   if (!sa_ok(a.B, a.N, a.heads) || !a.qkv || !a.out) return hipErrorInvalidValue;
   const dim3 grid((a.N + kSaTile - 1) / kSaTile, a.heads, a.B);
-  switch (dtype) {
-    case 0: note_kernel("softattn_fwd_kernel<float>"); hipLaunchKernelGGL(softattn_fwd_kernel<float>, grid, dim3(256), 0, s, a); break;
-    case 1: note_kernel("softattn_fwd_kernel<_Float16>"); hipLaunchKernelGGL(softattn_fwd_kernel<half_t>, grid, dim3(256), 0, s, a); break;
-    case 2: note_kernel("softattn_fwd_kernel<__bf16>"); hipLaunchKernelGGL(softattn_fwd_kernel<bf16_t>, grid, dim3(256), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    static const char* const name = kernel_name<T>("softattn_fwd_kernel");
+    note_kernel(name);
+    hipLaunchKernelGGL(softattn_fwd_kernel<T>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+  });
 }
 hipError_t launch_softattn_bwd(int dtype, const SoftAttnBwdArgs& a, hipStream_t s) {
   if (!sa_ok(a.B, a.N, a.heads) || !a.qkv || !a.out || !a.dout || !a.lse || !a.dqkv || !a.delta) return hipErrorInvalidValue;
   const dim3 grid((a.N + kSaTile - 1) / kSaTile, a.heads, a.B);
-  switch (dtype) {
-    case 0:
-      hipLaunchKernelGGL(softattn_bwd_q_kernel<float>, grid, dim3(256), 0, s, a);
-      note_kernel("softattn_bwd_kv_kernel<float>"); hipLaunchKernelGGL(softattn_bwd_kv_kernel<float>, grid, dim3(256), 0, s, a); break;
-    case 1:
-      hipLaunchKernelGGL(softattn_bwd_q_kernel<half_t>, grid, dim3(256), 0, s, a);
-      note_kernel("softattn_bwd_kv_kernel<_Float16>"); hipLaunchKernelGGL(softattn_bwd_kv_kernel<half_t>, grid, dim3(256), 0, s, a); break;
-    case 2:
-      hipLaunchKernelGGL(softattn_bwd_q_kernel<bf16_t>, grid, dim3(256), 0, s, a);
-      note_kernel("softattn_bwd_kv_kernel<__bf16>"); hipLaunchKernelGGL(softattn_bwd_kv_kernel<bf16_t>, grid, dim3(256), 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  return with_dtype(dtype, [&](auto t) {
+    using T = decltype(t);
+    static const char* const name = kernel_name<T>("softattn_bwd_kv_kernel");
+    hipLaunchKernelGGL(softattn_bwd_q_kernel<T>, grid, dim3(256), 0, s, a);
+    note_kernel(name);
+    hipLaunchKernelGGL(softattn_bwd_kv_kernel<T>, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace llie

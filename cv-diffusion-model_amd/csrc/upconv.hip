@@ -2,7 +2,6 @@
 // from nine low-resolution tap maps blended on chip (conv3x3_upmaps_kernel).  The general kernel (conv.hip: conv3x3_kernel, MODE 1)
 // interpolates the halo patch instead and takes every shape these two refuse.
 #include <algorithm>
-#include <string>
 
 #include "common.h"
 #include "kernels.h"
@@ -282,16 +281,15 @@ static hipError_t launch_upfold_cfg(const Conv3Args& a, hipStream_t s) {
   constexpr size_t lds = tiles > ctile ? tiles : ctile;
   static_assert(lds <= 48 * 1024, "static LDS limit");
   const unsigned grid = (unsigned)(a.B * (a.Hi / 8) * (a.Wi / 16) * (C64 ? 2 : 4 * (a.Cin / 128)));
-  static const std::string name = std::string("conv3x3_upfold_kernel<") + TypeName<T>::value + ", " + (C64 ? "64" : "128") + ">";
-  note_kernel(name.c_str());
+  static const char* const name = kernel_name<T>("conv3x3_upfold_kernel", C64 ? 64 : 128);
+  note_kernel(name);
   hipLaunchKernelGGL((conv3x3_upfold_kernel<T, C64>), dim3(grid), dim3(256), lds, s, a);
   return hipGetLastError();
 }
 // a.w = the folded blob (upconv_fold_elems(C) elements of the compute type); a.mode is ignored
 hipError_t launch_conv3x3_upfold(int dtype, const Conv3Args& a, hipStream_t s) {
   if (a.Cin != a.Cout || a.B < 1 || !conv3x3_upfold_ok(dtype, a.Hi, a.Wi, a.Cin)) return hipErrorInvalidValue;
-  if (dtype == 1) return a.Cin == 64 ? launch_upfold_cfg<half_t, true>(a, s) : launch_upfold_cfg<half_t, false>(a, s);
-  return a.Cin == 64 ? launch_upfold_cfg<bf16_t, true>(a, s) : launch_upfold_cfg<bf16_t, false>(a, s);
+  return with_dtype2(dtype, [&](auto t) { return a.Cin == 64 ? launch_upfold_cfg<decltype(t), true>(a, s) : launch_upfold_cfg<decltype(t), false>(a, s); });
 }
 
 // =============================================================================================
@@ -608,8 +606,8 @@ static hipError_t launch_upmaps_t(const Conv3Args& a, hipStream_t s, int workgro
   int wgs = std::min(nitems, workgroups);
   if (workgroups == 0)
     if (hipError_t e = upmaps_rule(nitems, &wgs); e != hipSuccess) return e;
-  static const std::string name = std::string("conv3x3_upmaps_kernel<") + TypeName<T>::value + ">";
-  note_kernel(name.c_str());
+  static const char* const name = kernel_name<T>("conv3x3_upmaps_kernel");
+  note_kernel(name);
   hipLaunchKernelGGL((conv3x3_upmaps_kernel<T>), dim3((unsigned)wgs), dim3(512), lds, s, a, nitems);
   return hipGetLastError();
 }
@@ -617,7 +615,7 @@ static hipError_t launch_upmaps_t(const Conv3Args& a, hipStream_t s, int workgro
 // any of which computes the same bits (the kernel's decode is a bijection on the items whatever the stride)
 hipError_t launch_conv3x3_upmaps(int dtype, const Conv3Args& a, hipStream_t s, int workgroups) {
   if (a.Cin != a.Cout || a.B < 1 || workgroups < 0 || !conv3x3_upmaps_ok(dtype, a.Hi, a.Wi, a.Cin)) return hipErrorInvalidValue;
-  return dtype == 1 ? launch_upmaps_t<half_t>(a, s, workgroups) : launch_upmaps_t<bf16_t>(a, s, workgroups);
+  return with_dtype2(dtype, [&](auto t) { return launch_upmaps_t<decltype(t)>(a, s, workgroups); });
 }
 
 }  // namespace llie

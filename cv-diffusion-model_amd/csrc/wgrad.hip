@@ -6,7 +6,6 @@
 // ds_read_b64_tr_b16 (gfx950), so a lane gets 16 consecutive rows of its channel per 32-row MFMA chunk (the
 // forward GEMM's operand scheme with the roles of rows and channels swapped); fp32 reads columns directly.  The rows are split over blockIdx.z; the fp32 partials are summed in
 // split order by a second kernel, so the result does not depend on scheduling.
-#include <string>
 
 #include "common.h"
 
@@ -253,33 +252,18 @@ hipError_t launch_wgrad(int dtype, const WgradArgs& a, hipStream_t s) {
   const int t = wgrad_tile(dtype, a.N, a.K);
   dim3 grid((a.N + t - 1) / t, ((a.K + t - 1) / t) * a.ntap, a.msplit);
   const int rps = (M / kWgRows + a.msplit - 1) / a.msplit * kWgRows;  // == M / msplit unless ragged
-  if (ragged) {  // the splits start on padded chunk boundaries
-    switch (dtype) {
-      case 0: hipLaunchKernelGGL((wgrad_kernel<float, 1, true>), grid, dim3(256), 0, s, a, rps); break;
-      case 1:
-        if (t == 128) hipLaunchKernelGGL((wgrad_kernel<half_t, 2, true>), grid, dim3(256), 0, s, a, rps);
-        else hipLaunchKernelGGL((wgrad_kernel<half_t, 1, true>), grid, dim3(256), 0, s, a, rps);
-        break;
-      case 2:
-        if (t == 128) hipLaunchKernelGGL((wgrad_kernel<bf16_t, 2, true>), grid, dim3(256), 0, s, a, rps);
-        else hipLaunchKernelGGL((wgrad_kernel<bf16_t, 1, true>), grid, dim3(256), 0, s, a, rps);
-        break;
-      default: return hipErrorInvalidValue;
-    }
-  } else {
-    switch (dtype) {
-      case 0: hipLaunchKernelGGL((wgrad_kernel<float, 1>), grid, dim3(256), 0, s, a, rps); break;
-      case 1:
-        if (t == 128) hipLaunchKernelGGL((wgrad_kernel<half_t, 2>), grid, dim3(256), 0, s, a, rps);
-        else hipLaunchKernelGGL((wgrad_kernel<half_t, 1>), grid, dim3(256), 0, s, a, rps);
-        break;
-      case 2:
-        if (t == 128) hipLaunchKernelGGL((wgrad_kernel<bf16_t, 2>), grid, dim3(256), 0, s, a, rps);
-        else hipLaunchKernelGGL((wgrad_kernel<bf16_t, 1>), grid, dim3(256), 0, s, a, rps);
-        break;
-      default: return hipErrorInvalidValue;
-    }
-  }
+  const hipError_t e = with_dtype(dtype, [&](auto tt) {
+    using T = decltype(tt);
+    return with_value<64, 128>(t, [&](auto tile) {
+      constexpr int TM = decltype(tile)::value / 64;
+      return with_value<0, 1>(ragged, [&](auto r) {  // ragged: the splits start on padded chunk boundaries
+        if constexpr (sizeof(T) == 2 || TM == 1)     // no 128-wide fp32 tiles: wgrad_tile
+          hipLaunchKernelGGL((wgrad_kernel<T, TM, decltype(r)::value != 0>), grid, dim3(256), 0, s, a, rps);
+        return hipSuccess;
+      });
+    });
+  });
+  if (e != hipSuccess) return e;
   const int64_t n = (int64_t)a.ntap * a.N * a.K;
   int rows = a.msplit;
   // two stages only where one pass would leave the chip empty: from 32 768 outputs on (128 workgroups) every thread adds its
