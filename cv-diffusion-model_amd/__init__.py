@@ -13,7 +13,7 @@ from .unet import (EfficientUNet, EfficientUNetConfig, create_efficient_unet, In
 from .scheduler import LCMScheduler, LCMSchedulerOutput, LCMDenoisingLoop, get_lcm_timesteps
 from .ddim import ddim_timesteps, ddim_step_host, ddim_enhance_host
 from .pipeline import (LowLightDiffusion, LowLightDiffusionOutput, LowLightLCMDistillation, normalize_image,
-                       denormalize_image, x0_loss, x0_loss_host)
+                       denormalize_image, x0_loss, x0_loss_host, consistency_target_host, consistency_loss_host)
 from .sharding import shard_range, enhance_sharded, all_gather_batch, all_reduce_gradients
 from .training import (FusedAdamW, FusedGradScaler, TrainStep, DistillStep, grad_accumulate_array,
                        accumulation_windows)
@@ -31,7 +31,8 @@ from .data import (DeviceFrameStore, DevicePairLoader, create_device_dataloaders
 from .metrics import (ImageMetrics, image_metrics, image_metrics_host, evaluate, evaluate_full_resolution, ssim_loss,
                       ssim_grad_host)
 from .trainer import (TrainingConfig, LowLightTrainer, train_model, make_lr_scheduler, build_checkpoint, comparison_grid,
-                      comparison_grid_host)
+                      comparison_grid_host, distill_draw_seed)
+from .distiller import LowLightDistiller, timestep_index_range, default_skip_terminal
 
 __all__ = [
     "EfficientUNet", "EfficientUNetConfig", "create_efficient_unet", "InvertedResidualBlock", "LinearAttention", "StandardAttention", "SqueezeExcitation",
@@ -45,8 +46,8 @@ __all__ = [
     "DeviceFrameStore", "DevicePairLoader", "create_device_dataloaders", "epoch_plan", "augment_pairs_host", "augment_synth_host",
     "augment_pairs_device", "augment_synth_device",
     "ImageMetrics", "image_metrics", "image_metrics_host", "evaluate", "evaluate_full_resolution",
-    "ssim_loss", "ssim_grad_host", "x0_loss", "x0_loss_host",
+    "ssim_loss", "ssim_grad_host", "x0_loss", "x0_loss_host", "consistency_target_host", "consistency_loss_host",
     "TrainingConfig", "LowLightTrainer", "train_model", "make_lr_scheduler", "build_checkpoint", "comparison_grid",
-    "comparison_grid_host",
+    "comparison_grid_host", "distill_draw_seed", "LowLightDistiller", "timestep_index_range", "default_skip_terminal",
     "ddim_timesteps", "ddim_step_host", "ddim_enhance_host",
 ]

@@ -18,6 +18,7 @@ LLIE_F32, LLIE_F16, LLIE_BF16 = 0, 1, 2
 LLIE_UNET, LLIE_IRB, LLIE_ATTN, LLIE_DOWN, LLIE_UP, LLIE_SE, LLIE_SOFTATTN = 0, 1, 2, 3, 4, 5, 6
 ERR_ARG, ERR_SHAPE, ERR_CONFIG, ERR_KEY, ERR_NOT_LOADED, ERR_WORKSPACE, ERR_NO_DEVICE = -1, -2, -3, -4, -5, -6, -7
 SAMPLER_LCM, SAMPLER_DDIM = 0, 1  # llie_step_coef.sampler
+PRED_EPSILON, PRED_V = 0, 1  # LLIE_PRED_*: what a network output means to llie_consistency_target_ex / llie_consistency_loss_ex
 
 EXPORTS = [
     "llie_last_error", "llie_version", "llie_create", "llie_destroy", "llie_num_params", "llie_param_info",
@@ -29,7 +30,7 @@ EXPORTS = [
     "llie_unet_backward", "llie_module_backward", "llie_load_all", "llie_profile_dump", "llie_copy_probe", "llie_rw_probe", "llie_pw_expand", "llie_gram_stats", "llie_gram_part_floats", "llie_groupnorm_finalize", "llie_conv3x3", "llie_conv3x3_tiles", "llie_linattn", "llie_linattn_splits", "llie_se_mlp", "llie_film", "llie_refresh_params", "llie_path_bytes", "llie_time_embed", "llie_debug_irbx_stamps", "llie_debug_gemm_stamps", "llie_debug_pwx_stamps", "llie_graph_cache_entries", "llie_debug_conv_stamps", "llie_gram_finalize",
     "llie_optimizer_create", "llie_optimizer_destroy", "llie_optimizer_numel", "llie_optimizer_step",
     "llie_optimizer_step_amp", "llie_grad_accumulate",
-    "llie_consistency_target", "llie_consistency_loss", "llie_ema_create", "llie_ema_update", "llie_ema_destroy",
+    "llie_consistency_target", "llie_consistency_loss", "llie_consistency_target_ex", "llie_consistency_loss_ex", "llie_ema_create", "llie_ema_update", "llie_ema_destroy",
     "llie_wgrad", "llie_wgrad_msplit", "llie_wgrad_partial_floats", "llie_dw_wgrad", "llie_dw_wgrad_strips",
     "llie_groupnorm_backward", "llie_groupnorm_backward_scratch_floats", "llie_linattn_backward", "llie_linattn_dkv_floats",
     "llie_upsample2x_backward", "llie_dilate2x", "llie_linear_dx", "llie_linear_dx_scratch_floats", "llie_linear_dw",
@@ -303,6 +304,8 @@ def lib() -> C.CDLL:
     L.llie_grad_accumulate.argtypes = [vp, vp, i64, C.c_float, ci, vp]
     L.llie_consistency_target.argtypes = [vp, vp, vp, vp, vp, ci, vp, ci, i64, vp]
     L.llie_consistency_loss.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, ci, i64, vp, i64, vp]
+    L.llie_consistency_target_ex.argtypes = [vp, vp, vp, vp, vp, ci, vp, ci, i64, ci, vp]
+    L.llie_consistency_loss_ex.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, i64, ci, i64, ci, vp]
     L.llie_ema_create.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), ci, C.POINTER(vp)]
     L.llie_ema_update.argtypes = [vp, C.c_double, vp]
     L.llie_ema_destroy.argtypes = [vp]

@@ -4,6 +4,12 @@
 //   consistency_target:  x_next = sqrt(a_n) * (x_t - sqrt(1 - a_t) e_T) / sqrt(a_t) + sqrt(1 - a_n) e_T      (:365-376)
 //   consistency_loss:    s0 = (x_t - sqrt(1 - a_t) e_S) / sqrt(a_t),  g0 = (x_next - sqrt(1 - a_n) e_E) / sqrt(a_n),
 //                        loss = huber(s0, g0) (delta 1, mean), d(loss)/d(e_S) = clamp(s0 - g0, -1, 1) / n * (-sqrt(1 - a_t) / sqrt(a_t))
+// The prediction type of a network output o at (x, a), sa = sqrt(a), sb = sqrt(1 - a), is a template parameter (kPredEpsilon /
+// kPredV), so the epsilon instantiation is the code above, unchanged, and no element branches on it:
+//   epsilon:  x0 = (x - sb o) / sa     e^ = o              d x0 / d o = -sb / sa
+//   v:        x0 = sa x - sb o         e^ = sb x + sa o     d x0 / d o = -sb          (finite at a = 0: x0 = -o)
+// The target reads the teacher's output with the teacher's type; s0 and g0 read the student's and the EMA student's outputs
+// with the student's type.
 //   ema_lerp:            ema = ema * decay + (1 - decay) * p over every parameter tensor in one launch (:316-323)
 //
 // a_t / a_n are per sample: alphas_cumprod[t[b]] / alphas_cumprod[t_next[b]] read from the device table.  The reference's
@@ -23,6 +29,22 @@ __device__ __forceinline__ float distill_acp(const int64_t* t, int b, const floa
   return (tb >= 0 && tb < table_len) ? acp[tb] : __builtin_nanf("");
 }
 
+// x0 and e^ of a network output `o` of type PRED at (x, sa, sb); every product and difference is rounded as written
+template <int PRED>
+__device__ __forceinline__ float distill_x0(float x, float o, float sa, float sb) {
+#pragma clang fp contract(off)
+  if constexpr (PRED == kPredV) return sa * x - sb * o;
+  else return (x - sb * o) / sa;
+}
+
+template <int PRED>
+__device__ __forceinline__ float distill_eps(float x, float o, float sa, float sb) {
+#pragma clang fp contract(off)
+  if constexpr (PRED == kPredV) return sb * x + sa * o;
+  else return o;
+}
+
+template <int PRED>
 __global__ void __launch_bounds__(kDistillThreads) consistency_target_kernel(const float* __restrict__ x_t, const float* __restrict__ e_t,
                                                                             const int64_t* __restrict__ t, const int64_t* __restrict__ t_next,
                                                                             const float* __restrict__ acp, int table_len, int64_t per,
@@ -35,12 +57,14 @@ __global__ void __launch_bounds__(kDistillThreads) consistency_target_kernel(con
   const float sa = sqrtf(a), sb = sqrtf(1.f - a), san = sqrtf(an), sbn = sqrtf(1.f - an);
   const size_t o = (size_t)b * per + i;
   const float e = e_t[o];
-  const float x0 = (x_t[o] - sb * e) / sa;
-  x_next[o] = san * x0 + sbn * e;
+  const float x = x_t[o];
+  const float x0 = distill_x0<PRED>(x, e, sa, sb);
+  x_next[o] = san * x0 + sbn * distill_eps<PRED>(x, e, sa, sb);
 }
 
 // Each workgroup covers kDistillLossPerWG consecutive elements of the flattened [B, per] tensors (thread k: elements
 // k, k + 256, ...), so the partial count depends on n only.
+template <int PRED>
 __global__ void __launch_bounds__(kDistillThreads) consistency_loss_kernel(const float* __restrict__ x_t, const float* __restrict__ x_next,
                                                                           const float* __restrict__ e_s, const float* __restrict__ e_e,
                                                                           const int64_t* __restrict__ t, const int64_t* __restrict__ t_next,
@@ -55,8 +79,8 @@ __global__ void __launch_bounds__(kDistillThreads) consistency_loss_kernel(const
     const int b = (int)(i / per);
     const float a = distill_acp(t, b, acp, table_len), an = distill_acp(t_next, b, acp, table_len);
     const float sa = sqrtf(a), sb = sqrtf(1.f - a), san = sqrtf(an), sbn = sqrtf(1.f - an);
-    const float s0 = (x_t[i] - sb * e_s[i]) / sa;
-    const float g0 = (x_next[i] - sbn * e_e[i]) / san;
+    const float s0 = distill_x0<PRED>(x_t[i], e_s[i], sa, sb);
+    const float g0 = distill_x0<PRED>(x_next[i], e_e[i], san, sbn);
     const float x = s0 - g0;
     const float z = fabsf(x);
     const float l = z < 1.f ? 0.5f * z * z : z - 0.5f;  // F.huber_loss, delta = 1 (NaN takes the second branch and stays NaN)
@@ -64,7 +88,8 @@ __global__ void __launch_bounds__(kDistillThreads) consistency_loss_kernel(const
     // huber_loss_backward: x <= -1 -> -1, x >= 1 -> 1, else x (NaN falls through), times 1/n; then the autograd chain of s0
     const float c = x <= -1.f ? -1.f : (x >= 1.f ? 1.f : x);
     const float gs0 = inv_n * c;
-    d_es[i] = -(gs0 / sa) * sb;
+    if constexpr (PRED == kPredV) d_es[i] = -(gs0 * sb);
+    else d_es[i] = -(gs0 / sa) * sb;
   }
   __shared__ double red[kDistillThreads];
   red[threadIdx.x] = acc;
@@ -109,9 +134,11 @@ __global__ void __launch_bounds__(kDistillThreads) ema_lerp_kernel(const OptTens
 
 hipError_t launch_consistency_target(const DistillArgs& a, hipStream_t s) {
   if (!a.x_t || !a.e_a || !a.t || !a.t_next || !a.acp || !a.out || a.batch <= 0 || a.per <= 0 || a.table_len <= 0) return hipErrorInvalidValue;
+  if (a.pred != kPredEpsilon && a.pred != kPredV) return hipErrorInvalidValue;
   note_kernel("consistency_target_kernel");
   dim3 grid((unsigned)((a.per + kDistillThreads - 1) / kDistillThreads), (unsigned)a.batch);
-  hipLaunchKernelGGL(consistency_target_kernel, grid, dim3(kDistillThreads), 0, s, a.x_t, a.e_a, a.t, a.t_next, a.acp, a.table_len, a.per, a.out);
+  auto* kern = a.pred == kPredV ? consistency_target_kernel<kPredV> : consistency_target_kernel<kPredEpsilon>;
+  hipLaunchKernelGGL(kern, grid, dim3(kDistillThreads), 0, s, a.x_t, a.e_a, a.t, a.t_next, a.acp, a.table_len, a.per, a.out);
   return hipGetLastError();
 }
 
@@ -119,11 +146,13 @@ hipError_t launch_consistency_loss(const DistillArgs& a, double* partial, float*
   if (!a.x_t || !a.x_next || !a.e_a || !a.e_b || !a.t || !a.t_next || !a.acp || !a.out || !partial || !loss || a.batch <= 0 || a.per <= 0 ||
       a.table_len <= 0)
     return hipErrorInvalidValue;
+  if (a.pred != kPredEpsilon && a.pred != kPredV) return hipErrorInvalidValue;
   const int64_t n = (int64_t)a.batch * a.per;
   const int64_t nparts = distill_loss_partials(n);
   if (nparts > (int64_t)INT32_MAX) return hipErrorInvalidValue;
   note_kernel("consistency_loss_kernel");
-  hipLaunchKernelGGL(consistency_loss_kernel, dim3((unsigned)nparts), dim3(kDistillThreads), 0, s, a.x_t, a.x_next, a.e_a, a.e_b, a.t, a.t_next,
+  auto* kern = a.pred == kPredV ? consistency_loss_kernel<kPredV> : consistency_loss_kernel<kPredEpsilon>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)nparts), dim3(kDistillThreads), 0, s, a.x_t, a.x_next, a.e_a, a.e_b, a.t, a.t_next,
                      a.acp, a.table_len, a.per, n, (float)(1.0 / (double)n), a.out, partial);
   if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
   note_kernel("consistency_loss_final_kernel");

@@ -822,16 +822,25 @@ int llie_grad_accumulate(float* acc, const float* grad, int64_t n, float weight,
 }
 
 // ---- consistency distillation
-int llie_consistency_target(const float* x_t, const float* e_teacher, const int64_t* t, const int64_t* t_next, const float* acp, int table_len,
-                            float* x_next, int batch, int64_t per, llie_stream stream) {
+static int distill_pred_ok(const char* who, int pred) {
+  if (pred == LLIE_PRED_EPSILON || pred == LLIE_PRED_V) return LLIE_OK;
+  set_err("%s: prediction type %d (LLIE_PRED_EPSILON = 0 or LLIE_PRED_V = 1)", who, pred);
+  return LLIE_ERR_ARG;
+}
+
+int llie_consistency_target_ex(const float* x_t, const float* out_teacher, const int64_t* t, const int64_t* t_next, const float* acp,
+                               int table_len, float* x_next, int batch, int64_t per, int teacher_pred, llie_stream stream) {
+  if (int e = distill_pred_ok("consistency_target", teacher_pred); e != LLIE_OK) return e;
   DistillArgs a{};
-  a.x_t = x_t; a.e_a = e_teacher; a.t = t; a.t_next = t_next; a.acp = acp; a.table_len = table_len; a.batch = batch; a.per = per; a.out = x_next;
+  a.x_t = x_t; a.e_a = out_teacher; a.t = t; a.t_next = t_next; a.acp = acp; a.table_len = table_len; a.batch = batch; a.per = per; a.out = x_next;
+  a.pred = teacher_pred;
   return kerr("consistency_target", launch_consistency_target(a, hs(stream)), LLIE_ERR_ARG, "null pointer or empty shape");
 }
 
-int llie_consistency_loss(const float* x_t, const float* x_next, const float* e_student, const float* e_ema, const int64_t* t,
-                          const int64_t* t_next, const float* acp, int table_len, float* d_student, float* loss_out, int batch, int64_t per,
-                          void* scratch, int64_t scratch_bytes, llie_stream stream) {
+int llie_consistency_loss_ex(const float* x_t, const float* x_next, const float* out_student, const float* out_ema, const int64_t* t,
+                             const int64_t* t_next, const float* acp, int table_len, float* d_student, float* loss_out, void* scratch,
+                             int64_t scratch_bytes, int batch, int64_t per, int student_pred, llie_stream stream) {
+  if (int e = distill_pred_ok("consistency_loss", student_pred); e != LLIE_OK) return e;
   if (batch <= 0 || per <= 0) return LLIE_ERR_ARG;
   const int64_t need = distill_loss_partials((int64_t)batch * per) * (int64_t)sizeof(double);
   if (!scratch || scratch_bytes < need) {
@@ -839,9 +848,22 @@ int llie_consistency_loss(const float* x_t, const float* x_next, const float* e_
     return LLIE_ERR_WORKSPACE;
   }
   DistillArgs a{};
-  a.x_t = x_t; a.x_next = x_next; a.e_a = e_student; a.e_b = e_ema; a.t = t; a.t_next = t_next; a.acp = acp; a.table_len = table_len;
-  a.batch = batch; a.per = per; a.out = d_student;
+  a.x_t = x_t; a.x_next = x_next; a.e_a = out_student; a.e_b = out_ema; a.t = t; a.t_next = t_next; a.acp = acp; a.table_len = table_len;
+  a.batch = batch; a.per = per; a.out = d_student; a.pred = student_pred;
   return kerr("consistency_loss", launch_consistency_loss(a, reinterpret_cast<double*>(scratch), loss_out, hs(stream)), LLIE_ERR_ARG, "null pointer or empty shape");
+}
+
+// the epsilon-only entries: the epsilon instantiation of the same kernels
+int llie_consistency_target(const float* x_t, const float* e_teacher, const int64_t* t, const int64_t* t_next, const float* acp, int table_len,
+                            float* x_next, int batch, int64_t per, llie_stream stream) {
+  return llie_consistency_target_ex(x_t, e_teacher, t, t_next, acp, table_len, x_next, batch, per, LLIE_PRED_EPSILON, stream);
+}
+
+int llie_consistency_loss(const float* x_t, const float* x_next, const float* e_student, const float* e_ema, const int64_t* t,
+                          const int64_t* t_next, const float* acp, int table_len, float* d_student, float* loss_out, int batch, int64_t per,
+                          void* scratch, int64_t scratch_bytes, llie_stream stream) {
+  return llie_consistency_loss_ex(x_t, x_next, e_student, e_ema, t, t_next, acp, table_len, d_student, loss_out, scratch, scratch_bytes, batch, per,
+                                  LLIE_PRED_EPSILON, stream);
 }
 
 // the optimiser's table types: OptTensor.p = source parameter, OptTensor.ema = shadow written in place (m, v unused)

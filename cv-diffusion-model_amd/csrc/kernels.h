@@ -684,6 +684,7 @@ hipError_t launch_grad_accumulate(float* acc, const float* grad, long long n, fl
 // (10) consistency distillation (distill.hip): per-sample alpha-bar from a device table, fp32 [batch, per] tensors
 constexpr int kDistillLossPerWG = 1024;  // elements per workgroup of the loss pass (one double partial each)
 inline long long distill_loss_partials(long long n) { return (n + kDistillLossPerWG - 1) / kDistillLossPerWG; }
+constexpr int kPredEpsilon = 0, kPredV = 1;  // what a network output means (LLIE_PRED_EPSILON / LLIE_PRED_V)
 struct DistillArgs {
   const float* x_t; const float* x_next;     // x_next: loss only
   const float* e_a; const float* e_b;        // target: e_a = teacher eps; loss: e_a = student eps, e_b = EMA-target eps
@@ -691,6 +692,7 @@ struct DistillArgs {
   const float* acp; int table_len;           // device alphas_cumprod
   int batch; long long per;                  // elements per sample
   float* out;                                // target: x_next; loss: d(loss)/d(e_a)
+  int pred;                                  // target: the teacher's type; loss: the student's and the EMA target's
 };
 hipError_t launch_consistency_target(const DistillArgs& a, hipStream_t s);
 hipError_t launch_consistency_loss(const DistillArgs& a, double* partial, float* loss, hipStream_t s);

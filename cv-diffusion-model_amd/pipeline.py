@@ -300,28 +300,43 @@ def _require_hip(t: torch.Tensor, what: str) -> None:
         raise RuntimeError(f"{what} runs only on a HIP device (got '{t.device}'); there is no CPU fallback")
 
 
+PREDICTION_TYPES = ("epsilon", "v_prediction")
+
+
+def prediction_code(prediction_type: str, who: str = "prediction_type") -> int:
+    """"epsilon" / "v_prediction" -> N.PRED_EPSILON / N.PRED_V; ValueError for anything else."""
+    if prediction_type not in PREDICTION_TYPES:
+        raise ValueError(f"{who} must be one of {PREDICTION_TYPES}, got {prediction_type!r}")
+    return N.PRED_V if prediction_type == "v_prediction" else N.PRED_EPSILON
+
+
 def consistency_target(scheduler: LCMScheduler, x_t: torch.Tensor, e_teacher: torch.Tensor, t: torch.Tensor,
-                       t_next: torch.Tensor) -> torch.Tensor:
-    """The teacher's DDIM step t -> t_next (:365-376): x_next = sqrt(a_n) x0 + sqrt(1-a_n) e_T, x0 = (x_t - sqrt(1-a_t) e_T) / sqrt(a_t),
-    a from `scheduler`'s alpha-bar table; t / t_next device int64 [B] (llie_consistency_target)."""
+                       t_next: torch.Tensor, *, prediction_type: str = "epsilon") -> torch.Tensor:
+    """The teacher's DDIM step t -> t_next (:365-376): x_next = sqrt(a_n) x0 + sqrt(1-a_n) e^, with (x0, e^) what the teacher's
+    output means at (x_t, a_t) under `prediction_type` (epsilon: x0 = (x_t - sqrt(1-a_t) o) / sqrt(a_t), e^ = o; v_prediction:
+    x0 = sqrt(a_t) x_t - sqrt(1-a_t) o, e^ = sqrt(1-a_t) x_t + sqrt(a_t) o), a from `scheduler`'s alpha-bar table; t / t_next
+    device int64 [B] (llie_consistency_target_ex).  Any [B, ...] shape: the kernel sees B rows of numel / B elements."""
     _require_hip(x_t, "consistency_target")
+    pred = prediction_code(prediction_type)
     dev = x_t.device
     x_t, e_teacher = x_t.detach().float().contiguous(), e_teacher.detach().float().contiguous()
     acp = scheduler._acp_on(dev)
     b = x_t.shape[0]
     out = torch.empty_like(x_t)
     with torch.cuda.device(dev):
-        N.check(N.lib().llie_consistency_target(x_t.data_ptr(), e_teacher.data_ptr(), t.data_ptr(), t_next.data_ptr(), acp.data_ptr(),
-                                                acp.numel(), out.data_ptr(), b, x_t.numel() // b,
-                                                torch.cuda.current_stream(dev).cuda_stream), "consistency_target")
+        N.check(N.lib().llie_consistency_target_ex(x_t.data_ptr(), e_teacher.data_ptr(), t.data_ptr(), t_next.data_ptr(), acp.data_ptr(),
+                                                   acp.numel(), out.data_ptr(), b, x_t.numel() // b, pred,
+                                                   torch.cuda.current_stream(dev).cuda_stream), "consistency_target")
     return out
 
 
 def consistency_loss(scheduler: LCMScheduler, x_t: torch.Tensor, x_next: torch.Tensor, e_student: torch.Tensor, e_ema: torch.Tensor,
-                     t: torch.Tensor, t_next: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
-    """F.huber_loss(s0, g0) of :385-393 and its gradient with respect to the student's prediction (llie_consistency_loss):
-    -> (loss, a 0-d device tensor; d(loss)/d(e_student), shaped like it)."""
+                     t: torch.Tensor, t_next: torch.Tensor, *, prediction_type: str = "epsilon") -> Tuple[torch.Tensor, torch.Tensor]:
+    """F.huber_loss(s0, g0) of :385-393 and its gradient with respect to the student's prediction (llie_consistency_loss_ex):
+    -> (loss, a 0-d device tensor; d(loss)/d(e_student), shaped like it).  `prediction_type` is how the student's and the EMA
+    student's outputs are read (s0 = x0 of e_student at (x_t, a_t), g0 = x0 of e_ema at (x_next, a_n); consistency_target)."""
     _require_hip(x_t, "consistency_loss")
+    pred = prediction_code(prediction_type)
     dev = x_t.device
     x_t, x_next = x_t.detach().float().contiguous(), x_next.detach().float().contiguous()
     e_student, e_ema = e_student.detach().float().contiguous(), e_ema.detach().float().contiguous()
@@ -332,27 +347,76 @@ def consistency_loss(scheduler: LCMScheduler, x_t: torch.Tensor, x_next: torch.T
     nbytes = N.distill_scratch_bytes(n)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        N.check(N.lib().llie_consistency_loss(x_t.data_ptr(), x_next.data_ptr(), e_student.data_ptr(), e_ema.data_ptr(), t.data_ptr(),
-                                              t_next.data_ptr(), acp.data_ptr(), acp.numel(), d.data_ptr(), loss.data_ptr(), b, n // b,
-                                              scratch.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream),
-                "consistency_loss")
+        N.check(N.lib().llie_consistency_loss_ex(x_t.data_ptr(), x_next.data_ptr(), e_student.data_ptr(), e_ema.data_ptr(), t.data_ptr(),
+                                                 t_next.data_ptr(), acp.data_ptr(), acp.numel(), d.data_ptr(), loss.data_ptr(),
+                                                 scratch.data_ptr(), nbytes, b, n // b, pred,
+                                                 torch.cuda.current_stream(dev).cuda_stream), "consistency_loss")
     return loss, d
 
 
 class _ConsistencyLossFn(torch.autograd.Function):
-    """The Huber consistency loss as an autograd node of the student's prediction: forward = llie_consistency_loss, backward =
+    """The Huber consistency loss as an autograd node of the student's prediction: forward = llie_consistency_loss_ex, backward =
     the gradient it wrote times grad_output (so GradScaler's scaled backward works)."""
 
     @staticmethod
-    def forward(ctx, e_student, scheduler, x_t, x_next, e_ema, t, t_next):
-        loss, d = consistency_loss(scheduler, x_t, x_next, e_student, e_ema, t, t_next)
+    def forward(ctx, e_student, scheduler, x_t, x_next, e_ema, t, t_next, prediction_type="epsilon"):
+        loss, d = consistency_loss(scheduler, x_t, x_next, e_student, e_ema, t, t_next, prediction_type=prediction_type)
         ctx.save_for_backward(d)
         return loss
 
     @staticmethod
     def backward(ctx, grad_output):
         d, = ctx.saved_tensors
-        return (d * grad_output,) + (None,) * 6
+        return (d * grad_output,) + (None,) * 7
+
+
+def _distill_x0(x: np.ndarray, o: np.ndarray, a: np.ndarray, v: bool) -> np.ndarray:
+    sa, sb = np.sqrt(a), np.sqrt(1.0 - a)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        return sa * x - sb * o if v else (x - sb * o) / sa
+
+
+def _distill_host_args(arrays, acps):
+    arrays = [np.asarray(v, dtype=np.float64) for v in arrays]
+    shape = arrays[0].shape
+    if len(shape) < 2 or any(v.shape != shape for v in arrays):
+        raise ValueError(f"the tensors must share one [B, ...] shape, got {[v.shape for v in arrays]}")
+    acps = [np.asarray(a, dtype=np.float64).reshape(-1) for a in acps]
+    if any(a.shape[0] != shape[0] for a in acps):
+        raise ValueError(f"alpha-bar arrays must be [{shape[0]}], got {[a.shape for a in acps]}")
+    return arrays, [a.reshape((-1,) + (1,) * (len(shape) - 1)) for a in acps]
+
+
+def consistency_target_host(x_t, out_teacher, acp_t, acp_next, *, prediction_type: str = "epsilon") -> np.ndarray:
+    """The definition of `consistency_target` in float64 NumPy: x_t / out_teacher [B, ...], acp_t / acp_next [B] =
+    alphas_cumprod[t_b] / alphas_cumprod[t_next_b] (NaN for a timestep outside the table: that sample is NaN) -> x_next.
+    At acp_t == 0 the epsilon form divides by zero (inf / NaN, as the kernel); the v form is finite."""
+    v = prediction_code(prediction_type) == N.PRED_V
+    (x, o), (a, an) = _distill_host_args((x_t, out_teacher), (acp_t, acp_next))
+    sa, sb = np.sqrt(a), np.sqrt(1.0 - a)
+    x0 = _distill_x0(x, o, a, v)
+    eps = sb * x + sa * o if v else o
+    with np.errstate(invalid="ignore", over="ignore"):
+        return np.sqrt(an) * x0 + np.sqrt(1.0 - an) * eps
+
+
+def consistency_loss_host(x_t, x_next, out_student, out_ema, acp_t, acp_next, *, prediction_type: str = "epsilon",
+                          return_x0: bool = False):
+    """The definition of `consistency_loss` in float64 NumPy -> (loss, d loss / d out_student): s0 = x0 of out_student at
+    (x_t, acp_t), g0 = x0 of out_ema at (x_next, acp_next), both read as `prediction_type`; loss = mean huber(s0 - g0), delta 1;
+    gradient = clamp(s0 - g0, -1, 1) / n * q, q = -sqrt(1 - acp_t) / sqrt(acp_t) (epsilon) or -sqrt(1 - acp_t) (v_prediction).
+    `return_x0=True` appends (s0, g0).  inf / NaN follow IEEE arithmetic, as in the kernel."""
+    v = prediction_code(prediction_type) == N.PRED_V
+    (x, xn, os_, oe), (a, an) = _distill_host_args((x_t, x_next, out_student, out_ema), (acp_t, acp_next))
+    s0, g0 = _distill_x0(x, os_, a, v), _distill_x0(xn, oe, an, v)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        diff = s0 - g0
+        z = np.abs(diff)
+        loss = float(np.where(z < 1.0, 0.5 * z * z, z - 0.5).mean())
+        c = np.where(diff <= -1.0, -1.0, np.where(diff >= 1.0, 1.0, diff))  # NaN falls through, as huber_loss_backward
+        q = -np.sqrt(1.0 - a) if v else -np.sqrt(1.0 - a) / np.sqrt(a)
+        grad = c / diff.size * q
+    return (loss, grad, s0, g0) if return_x0 else (loss, grad)
 
 
 # ---------------------------------------------------------------------- the x0 term (module docstring)
@@ -511,10 +575,24 @@ class LowLightLCMDistillation(nn.Module):
     `copy.deepcopy(student_model)` and gets its own engine context.  `guidance_scale_range` is stored and never used, as in
     the reference.  Teacher and student may be different variants but must share `image_size`.
 
+    Prediction types (extension).  The teacher's output is read as `teacher.scheduler.config.prediction_type`, the student's and
+    the EMA student's as `student.scheduler.config.prediction_type` (`teacher_prediction` / `student_prediction`); each is
+    "epsilon" or "v_prediction", in any mix, and anything else is a ValueError at construction.  The alpha-bar table is the
+    teacher's scheduler's.  An output o at (x, a), sa = sqrt(a), sb = sqrt(1 - a), means
+        epsilon:       x0 = (x - sb o) / sa      e^ = o
+        v_prediction:  x0 = sa x - sb o          e^ = sb x + sa o
+    and x_next = sa_n x0 + sb_n e^ (teacher), s0 = x0(x_t, student, a_t), g0 = x0(x_next, EMA student, a_n), loss =
+    huber(s0, g0).  `consistency_target_host` / `consistency_loss_host` are the float64 definitions.
+
+    Shapes follow the batch: [B,3,H,W] of any shape the student's engine trains at (llie_train_shape_ok) and the teacher's and
+    the EMA student's engines run at (llie_frame_shape_ok) -- H and W multiples of 8 and at least 64; `image_size` is one such
+    shape and runs as it always did.  A refused shape is a ValueError naming the rule, raised before any draw.
+
     The timestep pair of a sample is t = idx*c + c-1, t_next = (idx+k)*c + c-1 (c = T // num_ddim_timesteps, k =
     num_ddim_timesteps // num_inference_steps, idx uniform in [0, num_ddim_timesteps - k)): t_next is the noisier one, as
-    written in the reference.  With the zero-SNR table alpha-bar[999] == 0, so idx = num_ddim_timesteps - k - 1 makes the
-    target x0 +-inf and the loss +inf while every gradient stays finite (Huber's gradient saturates) -- reproduced as is."""
+    written in the reference.  With the zero-SNR table alpha-bar[999] == 0, so idx = num_ddim_timesteps - k - 1 makes an
+    epsilon student's target x0 +-inf and the loss +inf while every gradient stays finite (Huber's gradient saturates) --
+    reproduced as is.  A v-prediction student's target is finite there (g0 = -out_ema), and so is its loss."""
 
     def __init__(self, teacher_model: LowLightDiffusion, student_model: LowLightDiffusion, num_ddim_timesteps: int = 50,
                  guidance_scale_range: Tuple[float, float] = (3.0, 15.0)):
@@ -522,6 +600,8 @@ class LowLightLCMDistillation(nn.Module):
         if teacher_model.image_size != student_model.image_size:
             raise ValueError(f"teacher and student must share image_size (got {teacher_model.image_size} and "
                              f"{student_model.image_size}): both denoise the same x_t")
+        for who, m in (("teacher", teacher_model), ("student", student_model)):
+            prediction_code(getattr(m.scheduler.config, "prediction_type", "epsilon"), f"the {who}'s scheduler.config.prediction_type")
         self.teacher = teacher_model
         self.teacher.eval()
         self.teacher.requires_grad_(False)
@@ -544,6 +624,15 @@ class LowLightLCMDistillation(nn.Module):
             self._release_ema()
         except Exception:  # noqa: BLE001
             pass
+
+    @property
+    def teacher_prediction(self) -> str:
+        return getattr(self.teacher.scheduler.config, "prediction_type", "epsilon")
+
+    @property
+    def student_prediction(self) -> str:
+        """How the student's and the EMA student's outputs are read."""
+        return getattr(self.student.scheduler.config, "prediction_type", "epsilon")
 
     # ------------------------------------------------------------------ timestep pairs (:344-355)
     def timestep_pairs(self, idx: torch.Tensor, num_inference_steps: int = 4) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -573,17 +662,30 @@ class LowLightLCMDistillation(nn.Module):
         return noise.contiguous(), idx.contiguous()
 
     def _check_inputs(self, low_light: torch.Tensor, normal_light: torch.Tensor) -> None:
+        """Device, [B,3,H,W] of one shape, and the three engines' shape rules: raises before any draw."""
+        from .unet import resolve_compute_dtype
         _require_hip(low_light, "LowLightLCMDistillation")
         _require_hip(normal_light, "LowLightLCMDistillation")
+        if low_light.dim() != 4 or low_light.shape[1] != 3 or tuple(normal_light.shape) != tuple(low_light.shape):
+            raise ValueError(f"low_light / normal_light must be [B,3,H,W] of one shape, got {tuple(low_light.shape)} and "
+                             f"{tuple(normal_light.shape)}")
+        b, hh, ww = int(low_light.shape[0]), int(low_light.shape[2]), int(low_light.shape[3])
         s = self.student.image_size
-        if tuple(low_light.shape[1:]) != (3, s, s) or tuple(normal_light.shape) != tuple(low_light.shape):
-            raise ValueError(f"low_light / normal_light must be [B,3,{s},{s}]")
+        if (hh, ww) == (s, s):  # image_size goes unasked, as it always did
+            return
+        for who, m, train in (("student", self.student, True), ("teacher", self.teacher, False), ("EMA student", self.ema_student, False)):
+            h = m.unet._handle(resolve_compute_dtype(m.unet.compute_dtype))
+            try:
+                (h.train_shape_ok if train else h.frame_shape_ok)(b, hh, ww)
+            except ValueError as e:
+                raise ValueError(f"LowLightLCMDistillation ({who}): {e}") from None
 
     # ------------------------------------------------------------------ the loss (:325-393)
     def consistency_distillation_loss(self, low_light: torch.Tensor, normal_light: torch.Tensor, num_inference_steps: int = 4, *,
                                       noise: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Huber consistency loss (0-d device tensor with a grad_fn reaching the student's parameters).  `noise` / `idx`
-        (extensions) supply the two draws, e.g. CPU-generated ones for a run comparable with the CPU reference."""
+        """Huber consistency loss (0-d device tensor with a grad_fn reaching the student's parameters) at the batch's own
+        H x W (the class docstring has the shape rule and the prediction types).  `noise` / `idx` (extensions) supply the two
+        draws, e.g. CPU-generated ones for a run comparable with the CPU reference."""
         self._check_inputs(low_light, normal_light)
         noise, idx = self._draws(normal_light, num_inference_steps, noise, idx)
         t, t_next = self.timestep_pairs(idx, num_inference_steps)
@@ -591,14 +693,14 @@ class LowLightLCMDistillation(nn.Module):
         low = low_light.detach().float().contiguous()
         x_t = sched.add_noise(normal_light, noise, t)
         with torch.no_grad():
-            e_teacher = self.teacher.unet.forward_split(x_t, low, t)
-            x_next = consistency_target(sched, x_t, e_teacher, t, t_next)
-        e_student = self.student.unet.forward_split(x_t, low, t)
+            e_teacher = self.teacher.unet.forward_split(x_t, low, t, frame=True)
+            x_next = consistency_target(sched, x_t, e_teacher, t, t_next, prediction_type=self.teacher_prediction)
+        e_student = self.student.unet.forward_split(x_t, low, t, frame=True)
         with torch.no_grad():
-            e_ema = self.ema_student.unet.forward_split(x_next, low, t_next)
+            e_ema = self.ema_student.unet.forward_split(x_next, low, t_next, frame=True)
         if torch.is_grad_enabled() and e_student.requires_grad:
-            return _ConsistencyLossFn.apply(e_student, sched, x_t, x_next, e_ema, t, t_next)
-        return consistency_loss(sched, x_t, x_next, e_student, e_ema, t, t_next)[0]
+            return _ConsistencyLossFn.apply(e_student, sched, x_t, x_next, e_ema, t, t_next, self.student_prediction)
+        return consistency_loss(sched, x_t, x_next, e_student, e_ema, t, t_next, prediction_type=self.student_prediction)[0]
 
     # ------------------------------------------------------------------ EMA (:316-323)
     def _ema_pairs(self):

@@ -123,6 +123,11 @@ def train_draw_seed(seed: int, epoch: int) -> int:
     return (int(seed) * 1000003 + int(epoch) * 8191 + 54321) % (2 ** 63 - 1)
 
 
+def distill_draw_seed(seed: int, epoch: int) -> int:
+    """Seed of the device generator an epoch's distillation draws (noise, idx) come from (LowLightDistiller.train_epoch)."""
+    return (int(seed) * 1000003 + int(epoch) * 8191 + 76543) % (2 ** 63 - 1)
+
+
 def sample_draw_seed(seed: int, epoch: int) -> int:
     """Seed of the device generator an epoch's sample sheet draws its `enhance` noise from."""
     return (int(seed) * 1000003 + int(epoch) * 8191 + 65432) % (2 ** 63 - 1)
@@ -220,7 +225,200 @@ def _loader_device(loader) -> torch.device:
     return torch.device(dev)
 
 
-class LowLightTrainer:
+class _EpochLoop:
+    """What LowLightTrainer and LowLightDistiller (distiller.py) share: the constructor's checks of `crop_size`, `accumulate` and the
+    devices, the epoch schedule of `train` (validation, checkpoints, best model, sample sheets), the batch loop of an epoch with
+    its accumulation windows and LR schedule, the sample sheet and `save_checkpoint`.  A subclass provides `optimizer`,
+    `scheduler`, `step`, `train_epoch`, `validate`, `checkpoint`, `load_checkpoint`, the network that validation and the sample
+    sheet run (`_net`, with `_net_weights` swapped in), and what an epoch logs and when it is the best one (`_epoch_log`,
+    `_set_best`)."""
+
+    _what = "training"
+    val_sampler = "lcm"
+    val_steps: Optional[int] = None
+
+    # ------------------------------------------------------------------ construction
+    def _init_shapes(self, config: Optional[TrainingConfig], train_loader, val_loader, crop_size, accumulate) -> None:
+        """`config`, `accumulate` and `crop_size` (default: config.image_size squared), checked against the loaders."""
+        self.config = config or TrainingConfig()
+        cfg = self.config
+        if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
+            raise ValueError(f"accumulate must be an integer >= 1, got {accumulate!r}")
+        self.accumulate = accumulate
+        if crop_size is None:
+            self.crop_size = (int(cfg.image_size), int(cfg.image_size))
+        else:
+            if len(crop_size) != 2:
+                raise ValueError(f"crop_size is (H, W), got {crop_size!r}")
+            self.crop_size = (int(crop_size[0]), int(crop_size[1]))
+            if self.crop_size[0] == self.crop_size[1] and self.crop_size[0] != int(cfg.image_size):
+                raise ValueError(f"a square crop_size is config.image_size ({cfg.image_size}), got {self.crop_size[0]}: validation "
+                                 "of square crops runs `enhance`, which takes image_size only")
+            for what, loader in (("train_loader", train_loader), ("val_loader", val_loader)):
+                have = getattr(loader, "crop_size", None)
+                if loader is not None and have is not None and tuple(have) != self.crop_size:
+                    raise ValueError(f"{what} crops {have[0]} x {have[1]}, crop_size is {self.crop_size[0]} x {self.crop_size[1]}")
+
+    def _init_devices(self, model: torch.nn.Module, train_loader, val_loader) -> None:
+        """`device`: the one HIP device the model and the loaders are on; a train loader that yields a batch."""
+        who = type(self).__name__
+        params = list(model.parameters())
+        places = [("the model", params[0].device if params else torch.device("cpu")), ("train_loader", _loader_device(train_loader))]
+        if val_loader is not None:
+            places.append(("val_loader", _loader_device(val_loader)))
+        for what, dev in places:
+            if dev.type != "cuda":
+                raise RuntimeError(f"{who} runs only on a HIP device ({what} is on '{dev}'); there is no CPU fallback")
+        self.device = places[0][1]
+        for what, dev in places[1:]:
+            if dev != self.device:
+                raise ValueError(f"{what} is on {dev}, the model on {self.device}")
+        if len(train_loader) < 1:
+            raise ValueError("train_loader yields no batch (fewer pairs than batch_size: the last partial batch is dropped)")
+
+    def _init_run(self) -> None:
+        """Counters, the output directories, wandb."""
+        cfg = self.config
+        self.epoch = 0
+        self.global_step = 0
+        self.last_validation: Optional[Dict[str, object]] = None  # evaluate()'s result of the latest validate()
+        self.output_dir = Path(cfg.output_dir)
+        self.checkpoint_dir = Path(cfg.checkpoint_dir)
+        self.output_dir.mkdir(parents=True, exist_ok=True)
+        self.checkpoint_dir.mkdir(parents=True, exist_ok=True)
+        if cfg.use_wandb:
+            if not HAS_WANDB:
+                print("Warning: wandb not installed. Logging disabled.")
+                cfg.use_wandb = False
+            else:
+                wandb.init(project=cfg.wandb_project, name=cfg.wandb_run_name, config=cfg.__dict__)
+
+    def _say(self, *a, **kw) -> None:
+        if self.config.progress:
+            print(*a, **kw)
+
+    # ------------------------------------------------------------------ epochs
+    def train(self, on_epoch=None) -> List[Dict[str, object]]:
+        """The reference's loop (trainer.py:216-267): per epoch train, validate when there is a val loader, write
+        checkpoint_epoch_{e}.pt when (e + 1) % save_interval == 0, best_model.pt when the epoch is the best so far (the trainer:
+        a strictly lower validation loss; the distiller: a strictly higher PSNR) and the sample sheet when
+        (e + 1) % sample_interval == 0; final_model.pt at the end.  Returns one dictionary per epoch run, the trainer's
+        {"epoch", "train_loss", "lr", "val_loss", "psnr", "ssim"} (the last three None without a val loader); the distiller's
+        has no "val_loss"."""
+        cfg = self.config
+        self._say(f"Starting {self._what} on {self.device}")
+        self._say(f"Model parameters: {self._net().get_model_size()}")
+        history = []
+        for epoch in range(self.epoch, cfg.epochs):
+            self.epoch = epoch
+            train_loss = self.train_epoch()
+            log, line, best = self._epoch_log(epoch, train_loss)
+            history.append(log)
+            if on_epoch is not None:
+                on_epoch(log)
+            self._say(line)
+            if cfg.use_wandb:
+                wandb.log({k: v for k, v in log.items() if v is not None})
+            if (epoch + 1) % cfg.save_interval == 0:
+                self.save_checkpoint(f"checkpoint_epoch_{epoch}.pt")
+            if best:
+                self._set_best(log)
+                self.save_checkpoint("best_model.pt")
+            if (epoch + 1) % cfg.sample_interval == 0:
+                self.generate_samples(epoch)
+        self.save_checkpoint("final_model.pt")
+        if cfg.use_wandb:
+            wandb.finish()
+        return history
+
+    def _run_epoch(self, micro) -> float:
+        """The batch loop of an epoch.  `micro(batch, windowed)` makes the batch's draws and runs `step(...)` (windowed False: a
+        whole optimiser step) or `step.accumulate(...)` (True), returning the batch loss; with `accumulate=k` > 1 `step.apply()`
+        follows the last batch of each window (accumulation_windows(n, k)).  The LR schedule moves once per optimiser step,
+        after it, also when a grad scaler skipped the step.  The losses go into a device buffer that is copied once, after the
+        last batch; nothing else waits for the device, except the progress line.  Returns the Python-float sum of the fp32
+        batch losses in step order, divided by the number of batches."""
+        cfg, dev, loader = self.config, self.device, self.train_loader
+        n = len(loader)
+        losses = torch.zeros(n, dtype=torch.float32, device=dev)
+        report = cfg.log_interval > 0 and (cfg.progress or cfg.use_wandb)
+        ends, done = set(), 0  # 1-based index of each window's last batch
+        for length in accumulation_windows(n, self.accumulate):
+            done += length
+            ends.add(done)
+        for batch_idx, batch in enumerate(loader):
+            if self.accumulate == 1:
+                loss = micro(batch, False)
+                stepped = True
+            else:
+                loss = micro(batch, True)
+                stepped = batch_idx + 1 in ends
+                if stepped:
+                    self.step.apply()
+            if stepped:
+                # the steps go through step_flat, not optimizer.step(), which torch's scheduler watches to warn about a
+                # schedule that moves before the optimiser: the optimiser has stepped
+                self.optimizer._opt_called = True
+                self.scheduler.step()
+                self.global_step += 1
+            losses[batch_idx].copy_(loss)
+            if report and batch_idx % cfg.log_interval == 0:
+                value = loss.item()
+                self._say(f"Epoch {self.epoch} [{batch_idx + 1}/{n}] loss={value:.4f}")
+                if cfg.use_wandb:
+                    wandb.log({"train_loss_step": value, "lr": self.optimizer.param_groups[0]["lr"], "global_step": self.global_step})
+        total = 0.0
+        for v in losses.cpu().tolist():  # the one device-to-host copy
+            total += v
+        return total / n
+
+    def _val_steps(self, default: int) -> int:
+        return default if self.val_steps is None else self.val_steps
+
+    @torch.no_grad()
+    def generate_samples(self, epoch: int) -> Path:
+        """The sample sheet of trainer.py:365-410: the first `num_samples` pairs of the first batch of `val_loader or
+        train_loader`, enhanced with 4 steps (the trainer: on the EMA weights when EMA is on; the distiller: by the EMA student),
+        as output_dir/samples_epoch_{epoch}.png (rows: low-light, enhanced, normal-light).
+
+        Draws: g = torch.Generator(device=dev).manual_seed((seed * 1000003 + epoch * 8191 + 65432) % (2 ** 63 - 1));
+        noise = torch.randn(steps, n, 3, S, S, generator=g, device=dev) with steps the scheduler's step count for 4
+        (`val_steps` replaces the 4; with val_sampler="ddim" steps = 1, the initial latents, and the loop is DDIM's).
+        With a rectangular `crop_size` the images are [n, 3, H, W] and the loop is `enhance_frame`'s.
+        The loader's epoch counter, the parameters and the network's mode are as before afterwards."""
+        cfg, dev = self.config, self.device
+        loader = self.val_loader or self.train_loader
+        loader_epoch = loader.epoch
+        try:
+            batch = next(iter(loader))
+        finally:
+            loader.set_epoch(loader_epoch)  # the peek is not an epoch
+        low = batch["low_light"][:cfg.num_samples].contiguous()
+        normal = batch["normal_light"][:cfg.num_samples].contiguous()
+        net = self._net()
+        mode = net.training
+        try:
+            with _swapped_weights(net, self._net_weights()):
+                nsteps, steps = _steps_of(net, self._val_steps(SAMPLE_STEPS), dev, self.val_sampler)
+                g = torch.Generator(device=dev).manual_seed(sample_draw_seed(cfg.seed, epoch))
+                noise = torch.randn(steps, low.shape[0], 3, low.shape[2], low.shape[3], generator=g, device=dev)
+                enhance = net.enhance_frame if self.crop_size[0] != self.crop_size[1] else net.enhance
+                enhanced = enhance(low, nsteps, noise=noise, sampler=self.val_sampler)
+                grid = comparison_grid(low, enhanced, normal).cpu().numpy()  # the one device-to-host copy
+        finally:
+            net.train(mode)
+        path = self.output_dir / f"samples_epoch_{epoch}.png"
+        hostio.save_image(str(path), grid)
+        if cfg.use_wandb:
+            wandb.log({"samples": wandb.Image(str(path))})
+        return path
+
+    def save_checkpoint(self, filename: str) -> None:
+        torch.save(self.checkpoint(), self.checkpoint_dir / filename)
+        self._say(f"Saved checkpoint: {filename}")
+
+
+class LowLightTrainer(_EpochLoop):
     """The reference's LowLightTrainer (trainer.py:121-456) over the engine: same constructor, methods, schedule of
     validation / checkpoints / samples and checkpoint layout.
 
@@ -256,24 +454,8 @@ class LowLightTrainer:
     def __init__(self, model: LowLightDiffusion, train_loader, val_loader=None, config: Optional[TrainingConfig] = None, *,
                  x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0, val_sampler: str = "lcm", val_steps: Optional[int] = None,
                  crop_size: Optional[Tuple[int, int]] = None, accumulate: int = 1):
-        self.config = config or TrainingConfig()
+        self._init_shapes(config, train_loader, val_loader, crop_size, accumulate)
         cfg = self.config
-        if isinstance(accumulate, bool) or not isinstance(accumulate, int) or accumulate < 1:
-            raise ValueError(f"accumulate must be an integer >= 1, got {accumulate!r}")
-        self.accumulate = accumulate
-        if crop_size is None:
-            self.crop_size = (int(cfg.image_size), int(cfg.image_size))
-        else:
-            if len(crop_size) != 2:
-                raise ValueError(f"crop_size is (H, W), got {crop_size!r}")
-            self.crop_size = (int(crop_size[0]), int(crop_size[1]))
-            if self.crop_size[0] == self.crop_size[1] and self.crop_size[0] != int(cfg.image_size):
-                raise ValueError(f"a square crop_size is config.image_size ({cfg.image_size}), got {self.crop_size[0]}: validation "
-                                 "of square crops runs `enhance`, which takes image_size only")
-            for what, loader in (("train_loader", train_loader), ("val_loader", val_loader)):
-                have = getattr(loader, "crop_size", None)
-                if loader is not None and have is not None and tuple(have) != self.crop_size:
-                    raise ValueError(f"{what} crops {have[0]} x {have[1]}, crop_size is {self.crop_size[0]} x {self.crop_size[1]}")
         self.val_sampler = check_sampler(val_sampler)
         if val_steps is not None and (isinstance(val_steps, bool) or int(val_steps) != val_steps or val_steps < 1):
             raise ValueError(f"val_steps must be a positive integer or None, got {val_steps!r}")
@@ -281,19 +463,7 @@ class LowLightTrainer:
         if self.val_sampler == "ddim":
             for n in (self._val_steps(cfg.num_inference_steps), self._val_steps(SAMPLE_STEPS)):
                 model.ddim_schedule(n)
-        params = list(model.parameters())
-        places = [("the model", params[0].device if params else torch.device("cpu")), ("train_loader", _loader_device(train_loader))]
-        if val_loader is not None:
-            places.append(("val_loader", _loader_device(val_loader)))
-        for what, dev in places:
-            if dev.type != "cuda":
-                raise RuntimeError(f"LowLightTrainer runs only on a HIP device ({what} is on '{dev}'); there is no CPU fallback")
-        self.device = places[0][1]
-        for what, dev in places[1:]:
-            if dev != self.device:
-                raise ValueError(f"{what} is on {dev}, the model on {self.device}")
-        if len(train_loader) < 1:
-            raise ValueError("train_loader yields no batch (fewer pairs than batch_size: the last partial batch is dropped)")
+        self._init_devices(model, train_loader, val_loader)
         dtype = resolved_compute_dtype(cfg)
 
         self.model = model
@@ -311,70 +481,36 @@ class LowLightTrainer:
                               x0_ssim_weight=x0_ssim_weight, x0_l1_weight=x0_l1_weight)
         self._names = [name for name, _ in model.named_parameters()]
 
-        self.epoch = 0
-        self.global_step = 0
         self.best_val_loss = float("inf")
-        self.last_validation: Optional[Dict[str, object]] = None  # evaluate()'s result of the latest validate()
-
-        self.output_dir = Path(cfg.output_dir)
-        self.checkpoint_dir = Path(cfg.checkpoint_dir)
-        self.output_dir.mkdir(parents=True, exist_ok=True)
-        self.checkpoint_dir.mkdir(parents=True, exist_ok=True)
-
-        if cfg.use_wandb:
-            if not HAS_WANDB:
-                print("Warning: wandb not installed. Logging disabled.")
-                cfg.use_wandb = False
-            else:
-                wandb.init(project=cfg.wandb_project, name=cfg.wandb_run_name, config=cfg.__dict__)
+        self._init_run()
 
         if cfg.resume_from:
             self.load_checkpoint(cfg.resume_from)
 
-    def _say(self, *a, **kw) -> None:
-        if self.config.progress:
-            print(*a, **kw)
-
     def _ema_weights(self) -> Optional[List[torch.Tensor]]:
         return self.optimizer.ema_tensors() if self.config.use_ema else None
 
-    # ------------------------------------------------------------------ epochs
-    def train(self, on_epoch=None) -> List[Dict[str, object]]:
-        """The reference's loop (trainer.py:216-267): per epoch train, validate when there is a val loader, write
-        checkpoint_epoch_{e}.pt when (e + 1) % save_interval == 0, best_model.pt on a strictly lower validation loss and the
-        sample sheet when (e + 1) % sample_interval == 0; final_model.pt at the end.  Returns one dictionary per epoch run:
-        {"epoch", "train_loss", "lr", "val_loss", "psnr", "ssim"} (the last three None without a val loader)."""
-        cfg = self.config
-        self._say(f"Starting training on {self.device}")
-        self._say(f"Model parameters: {self.model.get_model_size()}")
-        history = []
-        for epoch in range(self.epoch, cfg.epochs):
-            self.epoch = epoch
-            train_loss = self.train_epoch()
-            val_loss = self.validate() if self.val_loader is not None else None
-            log = {"epoch": epoch, "train_loss": train_loss, "lr": self.optimizer.param_groups[0]["lr"], "val_loss": val_loss,
-                   "psnr": self.last_validation["psnr"] if val_loss is not None else None,
-                   "ssim": self.last_validation["ssim"] if val_loss is not None else None}
-            history.append(log)
-            if on_epoch is not None:
-                on_epoch(log)
-            line = f"Epoch {epoch}: train_loss={train_loss:.4f}"
-            if val_loss is not None:
-                line += f", val_loss={val_loss:.4f}, psnr={log['psnr']:.2f}, ssim={log['ssim']:.4f}"
-            self._say(line)
-            if cfg.use_wandb:
-                wandb.log({k: v for k, v in log.items() if v is not None})
-            if (epoch + 1) % cfg.save_interval == 0:
-                self.save_checkpoint(f"checkpoint_epoch_{epoch}.pt")
-            if val_loss is not None and val_loss < self.best_val_loss:
-                self.best_val_loss = val_loss
-                self.save_checkpoint("best_model.pt")
-            if (epoch + 1) % cfg.sample_interval == 0:
-                self.generate_samples(epoch)
-        self.save_checkpoint("final_model.pt")
-        if cfg.use_wandb:
-            wandb.finish()
-        return history
+    def _net(self) -> LowLightDiffusion:
+        return self.model
+
+    def _net_weights(self) -> Optional[List[torch.Tensor]]:
+        return self._ema_weights()
+
+    # ------------------------------------------------------------------ epochs (`train`: _EpochLoop)
+    def _epoch_log(self, epoch: int, train_loss: float):
+        """Validate (when there is a val loader) -> (the epoch's log, its progress line, whether it is the best so far: a
+        strictly lower validation loss)."""
+        val_loss = self.validate() if self.val_loader is not None else None
+        log = {"epoch": epoch, "train_loss": train_loss, "lr": self.optimizer.param_groups[0]["lr"], "val_loss": val_loss,
+               "psnr": self.last_validation["psnr"] if val_loss is not None else None,
+               "ssim": self.last_validation["ssim"] if val_loss is not None else None}
+        line = f"Epoch {epoch}: train_loss={train_loss:.4f}"
+        if val_loss is not None:
+            line += f", val_loss={val_loss:.4f}, psnr={log['psnr']:.2f}, ssim={log['ssim']:.4f}"
+        return log, line, val_loss is not None and val_loss < self.best_val_loss
+
+    def _set_best(self, log: Dict[str, object]) -> None:
+        self.best_val_loss = log["val_loss"]
 
     def train_epoch(self) -> float:
         """One epoch (trainer.py:269-338) of TrainStep over the train loader.
@@ -400,45 +536,15 @@ class LowLightTrainer:
         loader.set_epoch(self.epoch)
         (hh, ww), t_max = self.crop_size, int(self.model.scheduler.config.num_train_timesteps)
         g = torch.Generator(device=dev).manual_seed(train_draw_seed(cfg.seed, self.epoch))
-        n = len(loader)
-        losses = torch.zeros(n, dtype=torch.float32, device=dev)
-        report = cfg.log_interval > 0 and (cfg.progress or cfg.use_wandb)
-        ends, done = set(), 0  # 1-based index of each window's last batch
-        for length in accumulation_windows(n, self.accumulate):
-            done += length
-            ends.add(done)
-        for batch_idx, batch in enumerate(loader):
+
+        def micro(batch, windowed: bool) -> torch.Tensor:
             low, normal = batch["low_light"], batch["normal_light"]
             b = low.shape[0]
             t = torch.randint(0, t_max, (b,), generator=g, device=dev)
             noise = torch.randn(b, 3, hh, ww, generator=g, device=dev)
-            if self.accumulate == 1:
-                loss = self.step(low, normal, timesteps=t, noise=noise)
-                stepped = True
-            else:
-                loss = self.step.accumulate(low, normal, timesteps=t, noise=noise)
-                stepped = batch_idx + 1 in ends
-                if stepped:
-                    self.step.apply()
-            if stepped:
-                # TrainStep steps through step_flat, not optimizer.step(), which torch's scheduler watches to warn about a
-                # schedule that moves before the optimiser: the optimiser has stepped
-                self.optimizer._opt_called = True
-                self.scheduler.step()
-                self.global_step += 1
-            losses[batch_idx].copy_(loss)
-            if report and batch_idx % cfg.log_interval == 0:
-                value = loss.item()
-                self._say(f"Epoch {self.epoch} [{batch_idx + 1}/{n}] loss={value:.4f}")
-                if cfg.use_wandb:
-                    wandb.log({"train_loss_step": value, "lr": self.optimizer.param_groups[0]["lr"], "global_step": self.global_step})
-        total = 0.0
-        for v in losses.cpu().tolist():  # the one device-to-host copy
-            total += v
-        return total / n
+            return (self.step.accumulate if windowed else self.step)(low, normal, timesteps=t, noise=noise)
 
-    def _val_steps(self, default: int) -> int:
-        return default if self.val_steps is None else self.val_steps
+        return self._run_epoch(micro)
 
     @torch.no_grad()
     def validate(self) -> float:
@@ -458,43 +564,6 @@ class LowLightTrainer:
         self.last_validation = res
         return res["loss"]
 
-    @torch.no_grad()
-    def generate_samples(self, epoch: int) -> Path:
-        """The sample sheet of trainer.py:365-410: the first `num_samples` pairs of the first batch of `val_loader or
-        train_loader`, enhanced with 4 steps on the EMA weights (when EMA is on), as output_dir/samples_epoch_{epoch}.png (rows:
-        low-light, enhanced, normal-light).
-
-        Draws: g = torch.Generator(device=dev).manual_seed((seed * 1000003 + epoch * 8191 + 65432) % (2 ** 63 - 1));
-        noise = torch.randn(steps, n, 3, S, S, generator=g, device=dev) with steps the scheduler's step count for 4
-        (`val_steps` replaces the 4; with val_sampler="ddim" steps = 1, the initial latents, and the loop is DDIM's).
-        With a rectangular `crop_size` the images are [n, 3, H, W] and the loop is `enhance_frame`'s.
-        The loader's epoch counter, the parameters and the model's mode are as before afterwards."""
-        cfg, dev = self.config, self.device
-        loader = self.val_loader or self.train_loader
-        loader_epoch = loader.epoch
-        try:
-            batch = next(iter(loader))
-        finally:
-            loader.set_epoch(loader_epoch)  # the peek is not an epoch
-        low = batch["low_light"][:cfg.num_samples].contiguous()
-        normal = batch["normal_light"][:cfg.num_samples].contiguous()
-        mode = self.model.training
-        try:
-            with _swapped_weights(self.model, self._ema_weights()):
-                nsteps, steps = _steps_of(self.model, self._val_steps(SAMPLE_STEPS), dev, self.val_sampler)
-                g = torch.Generator(device=dev).manual_seed(sample_draw_seed(cfg.seed, epoch))
-                noise = torch.randn(steps, low.shape[0], 3, low.shape[2], low.shape[3], generator=g, device=dev)
-                enhance = self.model.enhance_frame if self.crop_size[0] != self.crop_size[1] else self.model.enhance
-                enhanced = enhance(low, nsteps, noise=noise, sampler=self.val_sampler)
-                grid = comparison_grid(low, enhanced, normal).cpu().numpy()  # the one device-to-host copy
-        finally:
-            self.model.train(mode)
-        path = self.output_dir / f"samples_epoch_{epoch}.png"
-        hostio.save_image(str(path), grid)
-        if cfg.use_wandb:
-            wandb.log({"samples": wandb.Image(str(path))})
-        return path
-
     # ------------------------------------------------------------------ checkpoints
     def ema_shadow(self) -> Optional[Dict[str, torch.Tensor]]:
         """{parameter name as in model.named_parameters(): shadow weight} (copies), the reference's EMAModel.shadow; None
@@ -507,10 +576,6 @@ class LowLightTrainer:
         return build_checkpoint(epoch=self.epoch, global_step=self.global_step, model=self.model, optimizer=self.optimizer,
                                 scheduler=self.scheduler, best_val_loss=self.best_val_loss, config=self.config,
                                 ema_shadow=self.ema_shadow(), scaler=self.scaler)
-
-    def save_checkpoint(self, filename: str) -> None:
-        torch.save(self.checkpoint(), self.checkpoint_dir / filename)
-        self._say(f"Saved checkpoint: {filename}")
 
     def load_checkpoint(self, path: str) -> None:
         """trainer.py:437-456: continues after the saved epoch.  Read with weights_only=True (nothing from the file is

@@ -541,7 +541,9 @@ class DistillStep(_GradWindow):
     distill.update_ema(ema_decay)`.  The EMA student's engine weights are reloaded at its next forward (content check on the
     device).  Returns the loss (device scalar, unscaled).  fp16 students need a `grad_scaler` (FusedGradScaler: d(loss)/d(eps)
     times the device scale, unscale / skip / scale update in the optimiser's launches) and are refused without one; update_ema
-    runs every step, skipped or not, as in the reference loop.  fp32 and bf16 run either way."""
+    runs every step, skipped or not, as in the reference loop.  fp32 and bf16 run either way.
+    Batches are [B,3,H,W] of any shape LowLightLCMDistillation accepts (its docstring has the rule); the networks' outputs are
+    read with the distillation's `teacher_prediction` / `student_prediction`."""
 
     def __init__(self, distill, optimizer: FusedAdamW, ema_decay: float = 0.95, grad_scaler: Optional[FusedGradScaler] = None):
         if not (0 <= ema_decay <= 1):
@@ -568,8 +570,10 @@ class DistillStep(_GradWindow):
     @torch.no_grad()
     def accumulate(self, low_light: torch.Tensor, normal_light: torch.Tensor, num_inference_steps: int = 4, *,
                    noise: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """One micro-batch of a window (at image_size): the teacher, student and EMA-target forwards, the loss and the backward
-        pass of `__call__`, then `acc (+)= b * flat`.  Returns the micro-batch loss (device scalar)."""
+        """One micro-batch of a window (at the batch's own H x W, which may differ from the window's other micro-batches): the
+        teacher, student and EMA-target forwards, the loss and the backward pass of `__call__`, then `acc (+)= b * flat`.
+        Returns the micro-batch loss (device scalar).  A shape the engines refuse raises before any draw and leaves an open
+        window as it was."""
         loss = self._micro(low_light, normal_light, num_inference_steps, noise, idx)
         self._window_add(int(low_light.shape[0]), loss)
         return loss
@@ -593,24 +597,24 @@ class DistillStep(_GradWindow):
             raise ValueError("DistillStep: fp16 students need loss scaling, which this step does not do; use the autograd "
                              "path (consistency_distillation_loss + GradScaler) or bf16")
         b, dev = low_light.shape[0], low_light.device
+        hh, ww = int(low_light.shape[2]), int(low_light.shape[3])
         noise, idx = d._draws(normal_light, num_inference_steps, noise, idx)
         t, t_next = d.timestep_pairs(idx, num_inference_steps)
         sched = d.teacher.scheduler
         low = low_light.detach().float().contiguous()
         x_t = sched.add_noise(normal_light, noise, t)
-        e_teacher = d.teacher.unet.forward_split(x_t, low, t)
-        x_next = consistency_target(sched, x_t, e_teacher, t, t_next)
+        e_teacher = d.teacher.unet.forward_split(x_t, low, t, frame=True)
+        x_next = consistency_target(sched, x_t, e_teacher, t, t_next, prediction_type=d.teacher_prediction)
         h = unet._handle(dtype)
-        nbytes = _train_buffers(self, h, b, dev)
-        s = unet.config.image_size
-        e_student = torch.empty(b, unet.config.out_channels, s, s, dtype=torch.float32, device=dev)
+        # the batch's own H x W; the workspace follows the shape and only grows, so a loop or a window may alternate shapes
+        nbytes = _train_buffers(self, h, b, dev, hh, ww)
+        e_student = torch.empty(b, unet.config.out_channels, hh, ww, dtype=torch.float32, device=dev)
         L = N.lib()
         with torch.cuda.device(dev):
-            N.check(L.llie_unet_train_forward(h.h, x_t.data_ptr(), low.data_ptr(), t.data_ptr(), e_student.data_ptr(), b,
-                                              self._ws.data_ptr(), nbytes, torch.cuda.current_stream(dev).cuda_stream),
-                    "EfficientUNet.forward (training)")
-        e_ema = d.ema_student.unet.forward_split(x_next, low, t_next)
-        loss, d_eps = consistency_loss(sched, x_t, x_next, e_student, e_ema, t, t_next)
+            h.unet_train_forward(x_t.data_ptr(), low.data_ptr(), t.data_ptr(), e_student.data_ptr(), b, hh, ww, self._ws.data_ptr(), nbytes,
+                                 torch.cuda.current_stream(dev).cuda_stream)
+        e_ema = d.ema_student.unet.forward_split(x_next, low, t_next, frame=True)
+        loss, d_eps = consistency_loss(sched, x_t, x_next, e_student, e_ema, t, t_next, prediction_type=d.student_prediction)
         if self.grad_scaler is not None:
             d_eps = d_eps * self.grad_scaler._device_scale(dev)
         with torch.cuda.device(dev):

@@ -286,10 +286,11 @@ int llie_optimizer_step_amp(llie_optimizer* opt, const float* grad_base, const l
 int llie_grad_accumulate(float* acc, const float* grad, int64_t n, float weight, int first, llie_stream stream);
 
 /* ---- Consistency distillation (LowLightLCMDistillation.consistency_distillation_loss / update_ema,
- * low_light_diffusion.py:284-408).  Tensors are device fp32 NCHW [batch, 3, S, S] (per_sample = 3*S*S elements per
- * sample); `t` / `t_next` are device int64 [batch]; `alphas_cumprod` is the teacher scheduler's device fp32 table of
- * `table_len` entries.  The reference's operation order is kept (no fused multiply-adds).  A timestep outside
- * [0, table_len) is never used as an index: that sample's outputs are NaN (the call is asynchronous and cannot raise).
+ * low_light_diffusion.py:284-408).  Tensors are device fp32 [batch, per_sample] (NCHW [batch, 3, H, W]: per_sample = 3*H*W
+ * elements per sample; the kernels know nothing of H x W); `t` / `t_next` are device int64 [batch]; `alphas_cumprod` is the
+ * teacher scheduler's device fp32 table of `table_len` entries.  The reference's operation order is kept (no fused
+ * multiply-adds).  A timestep outside [0, table_len) is never used as an index: that sample's outputs are NaN (the call is
+ * asynchronous and cannot raise).
  *   llie_consistency_target:  x_next = sqrt(a_n) x0 + sqrt(1 - a_n) e_teacher,  x0 = (x_t - sqrt(1 - a_t) e_teacher) / sqrt(a_t)
  *   llie_consistency_loss:    s0 = (x_t - sqrt(1 - a_t) e_student) / sqrt(a_t),  g0 = (x_next - sqrt(1 - a_n) e_ema) / sqrt(a_n);
  *                             loss_out (device, 1 float) = F.huber_loss(s0, g0) (delta 1, mean);  d_student (like x_t) =
@@ -305,6 +306,24 @@ int llie_consistency_loss(const float* x_t, const float* x_next, const float* e_
                           const int64_t* t, const int64_t* t_next, const float* alphas_cumprod, int table_len,
                           float* d_student, float* loss_out, int batch, int64_t per_sample, void* scratch,
                           int64_t scratch_bytes, llie_stream stream);
+/* The same two with the prediction type of the networks as an argument (the two above are these at LLIE_PRED_EPSILON, bit for
+ * bit).  A network output o of type p at (x, a), sa = sqrt(a), sb = sqrt(1 - a):
+ *   LLIE_PRED_EPSILON:  x0 = (x - sb o) / sa     e^ = o              q = -sb / sa
+ *   LLIE_PRED_V:        x0 = sa x - sb o         e^ = sb x + sa o     q = -sb
+ *   llie_consistency_target_ex:  x_next = sa_n x0 + sb_n e^ of out_teacher at (x_t, a_t), read with teacher_pred
+ *   llie_consistency_loss_ex:    s0 = x0 of out_student at (x_t, a_t), g0 = x0 of out_ema at (x_next, a_n), both read with
+ *                                student_pred; loss = mean huber(s0 - g0), d_student = clamp(s0 - g0, -1, 1) / n * q(a_t).
+ * Every product and difference is rounded on its own, as written.  At a = 0 the epsilon form keeps the inf / NaN behaviour
+ * above; the v form is finite there (x0 = -o).  Any other prediction type: LLIE_ERR_ARG before any launch. */
+#define LLIE_PRED_EPSILON 0
+#define LLIE_PRED_V 1
+int llie_consistency_target_ex(const float* x_t, const float* out_teacher, const int64_t* t, const int64_t* t_next,
+                               const float* alphas_cumprod, int table_len, float* x_next, int batch, int64_t per_sample,
+                               int teacher_pred, llie_stream stream);
+int llie_consistency_loss_ex(const float* x_t, const float* x_next, const float* out_student, const float* out_ema,
+                             const int64_t* t, const int64_t* t_next, const float* alphas_cumprod, int table_len,
+                             float* d_student, float* loss_out, void* scratch, int64_t scratch_bytes, int batch,
+                             int64_t per_sample, int student_pred, llie_stream stream);
 /* EMA of a parameter set (update_ema, :316-323): ema[i] = ema[i] * decay + (1 - decay) * param[i] over `count` tensors in
  * one launch.  The table (device pointers, all fp32 and valid for the object's life) is built once by create. */
 typedef struct llie_ema llie_ema;

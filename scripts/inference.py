@@ -3,7 +3,8 @@
 scripts/inference.py (:30-62): --input --output --checkpoint --model --format --variant --image_size
 --num_steps --device.  Only --format pytorch exists here (ONNX / TFLite are the reference's mobile
 deployment targets, out of scope); extensions: --dtype {fp32,fp16,bf16}, --noise_seed, --sampler {lcm,ddim} (ddim: the
-deterministic sampler of a many-step model, --num_steps anything in 1..1000), and --tile [--tile_overlap N]
+deterministic sampler of a many-step model, --num_steps anything in 1..1000), --prediction {epsilon,v_prediction} (what the
+network's output means: a v-prediction teacher, or the v student scripts/distill.py --student_prediction v_prediction writes), and --tile [--tile_overlap N]
 [--tile_batch N] [--tile_sync {none,latents}] [--tile_size {auto|HxW}], which enhances the image at its own resolution as
 overlapping image_size tiles instead of resizing it (--tile_sync latents: the tiles share one latent canvas, fused after every
 step; --tile_size: the tiles are frames of H x W, or with auto the fewest frames the engine can run -- three for 12 MP), and
@@ -48,6 +49,9 @@ def parse_args(argv=None):
                    help="(extension) lcm = the consistency student's loop (re-noise after every step); ddim = the deterministic "
                         "DDIM loop of a many-step epsilon- / v-prediction model: --num_steps may be anything in 1..1000 and "
                         "the initial latents are the only noise")
+    p.add_argument("--prediction", type=str, default="epsilon", choices=["epsilon", "v_prediction"],
+                   help="(extension) what the checkpoint's network predicts: epsilon (the default, the reference's models) or "
+                        "v_prediction (a model trained or distilled as a v network)")
     p.add_argument("--tile", action="store_true",
                    help="(extension) no resize: enhance the image at its own resolution as overlapping image_size tiles, blended "
                         "on the device; --noise_seed then seeds the per-image noise canvas")
@@ -87,8 +91,12 @@ def load_model(args):
     unet = None
     if getattr(args, "attention", "linear") == "softmax":
         unet = M.create_efficient_unet(args.variant, args.image_size, in_channels=6, use_linear_attention=False)
-    model = M.LowLightDiffusion(unet=unet, unet_variant=args.variant, image_size=args.image_size, num_inference_steps=4,
-                                compute_dtype=args.dtype)
+    scheduler = None
+    if getattr(args, "prediction", "epsilon") != "epsilon":  # the default scheduler is the epsilon one, as before
+        scheduler = M.LCMScheduler(num_train_timesteps=1000, beta_schedule="scaled_linear", prediction_type=args.prediction,
+                                   num_inference_steps=4, rescale_betas_zero_snr=True)
+    model = M.LowLightDiffusion(unet=unet, scheduler=scheduler, unet_variant=args.variant, image_size=args.image_size,
+                                num_inference_steps=4, compute_dtype=args.dtype)
     if args.checkpoint:
         hostio.load_checkpoint(model, args.checkpoint)
     return model.to(args.device).eval()
