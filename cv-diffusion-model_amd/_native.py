@@ -58,6 +58,7 @@ EXPORTS = [
     "llie_tile_gather_u8_hw", "llie_tile_gather_f32_hw", "llie_tile_blend_u8_hw", "llie_tile_sync_step_hw", "llie_frame_max_pixels",
     "llie_unet_backward_dx", "llie_init_conv_dgrad",
     "llie_softattn", "llie_softattn_backward", "llie_softattn_bwd_floats",
+    "llie_pw_expand_nsplit", "llie_silu_rows",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 PW_SIGMOID_BWD, PW_RELU6_BWD, PW_SILU_BWD, PW_SCALE = 0, 1, 2, 3  # llie_pointwise_kind
@@ -248,6 +249,8 @@ def lib() -> C.CDLL:
     L.llie_linattn_splits.argtypes = [ci]
     L.llie_se_mlp.argtypes = [ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     L.llie_film.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp]
+    L.llie_pw_expand_nsplit.argtypes = [ci, ci]
+    L.llie_silu_rows.argtypes = [vp, vp, i64, vp]
     L.llie_gram_part_floats.restype = i64
     L.llie_dwconv3x3.argtypes = [ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]
     L.llie_dwconv3x3_tiles.argtypes = [ci, ci]

@@ -362,7 +362,7 @@ size_t gram_part_floats(int K, int P) {
 bool gram_supported(int dtype, int K, int c0, int P) {
   if (dtype != 1 && dtype != 2) return false;
   if (K != 32 && K != 64 && K != 96) return false;
-  return c0 % 8 == 0 && P % 512 == 0 && P % gram_rows(K, P) == 0;
+  return c0 > 0 && c0 <= K && c0 % 8 == 0 && P > 0 && P % 512 == 0 && P % gram_rows(K, P) == 0;
 }
 
 hipError_t launch_gram_stats(int dtype, const GramArgs& a0, hipStream_t s) {

@@ -180,6 +180,7 @@ int llie_conv3x3_upmaps_workgroups(int batch, int Hi, int Wi, int C) {
 }
 int llie_conv3x3_upmaps_supported(int dtype, int Hi, int Wi, int C) { return conv3x3_upmaps_ok(dtype, Hi, Wi, C) ? 1 : 0; }
 int llie_linattn_splits(int N) { return linattn_nsplit(N); }
+int llie_pw_expand_nsplit(int M, int N) { return M > 0 && M % 128 == 0 && N > 0 && N % 64 == 0 ? pw_expand_nsplit(M, N) : LLIE_ERR_ARG; }
 int llie_linattn(int dtype, const void* qkv, float* kv_scratch, void* out, int batch, int N, int heads, llie_stream stream) {
   if (!qkv || !kv_scratch || !out || dtype < 0 || dtype > 2 || batch <= 0 || N <= 0 || heads <= 0) return LLIE_ERR_ARG;
   AttnArgs a{};
@@ -330,6 +331,10 @@ int llie_film(const float* silu_temb, const float* wf, const float* bf, float* f
   FilmArgs a{};
   a.silu_temb = silu_temb; a.rows = rows; a.T = T; a.wf = wf; a.bf = bf; a.film = film; a.F = F;
   return kerr("film", launch_film(a, hs(stream)));
+}
+int llie_silu_rows(const float* in, float* out, int64_t n, llie_stream stream) {
+  if (!in || !out || n <= 0 || n > (int64_t)0x7fffffff * 256) return LLIE_ERR_ARG;
+  return kerr("silu_rows", launch_silu_rows(in, out, n, hs(stream)));
 }
 
 // ---- backward kernels (training): thin wrappers over the launch API; every contract check runs here, before any HIP call

@@ -126,6 +126,7 @@ __host__ __device__ inline long long pw_expand_pack_index(int n, int k, int K) {
   return ((((long long)(n >> 5) * (K >> 4) + (k >> 4)) * 64 + lane) << 3) + (k & 7);
 }
 bool pw_expand_supported(int dtype, const GemmSeg* seg, int nseg, int M, int N, int K, int P);
+int pw_expand_nsplit(int M, int N);  // the channel split launch_pw_expand takes: workgroups = M / 128 x this
 bool pw_expand_serves_k(int K);  // the kernel exists for this input width (the builder packs the fragment-ordered weight copy only then)
 hipError_t launch_pw_expand(int dtype, const ExpandArgs& a, hipStream_t s);
 // The activating form (wide block 192 -> 768 with norm2's tables from the wide Gram): stores a = T(clamp01(h1 as2 + ab2)) instead

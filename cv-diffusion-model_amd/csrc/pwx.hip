@@ -401,13 +401,14 @@ static int nsplit_for(int M, int N, int nbw) {
   while ((long)(M / 128) * ns < 512 && (N / (32 * nbw)) % (2 * ns) == 0 && N / (32 * nbw * 2 * ns) >= 2 && (N / (2 * ns)) % 64 == 0) ns *= 2;
   return ns;
 }
+int pw_expand_nsplit(int M, int N) { return nsplit_for(M, N, kPwxNbw); }
 bool pw_expand_serves_k(int K) { return K == 128 || K == 192 || K == 256 || K == 384 || K == 512; }
 bool pw_expand_supported(int dtype, const GemmSeg* seg, int nseg, int M, int N, int K, int P) {
   if (!g_knobs.pwx || (dtype != 1 && dtype != 2) || nseg < 1 || nseg > 3 || P % 128 || M % P) return false;
   if (!pw_expand_serves_k(K) || N % (32 * kPwxNbw) || N % 64) return false;  // pairs of 32-channel blocks leave as 128-byte lines
   int k = 0;
   for (int i = 0; i < nseg; ++i) {
-    if (seg[i].ch % 64 || seg[i].act != ACT_RELU6_S6 || !seg[i].as || !seg[i].ab) return false;
+    if (!seg[i].ptr || seg[i].ch <= 0 || seg[i].ch % 64 || seg[i].act != ACT_RELU6_S6 || !seg[i].as || !seg[i].ab || seg[i].aff_ld < seg[i].ch) return false;
     k += seg[i].ch;
   }
   return k == K;

@@ -640,6 +640,11 @@ int llie_linattn_splits(int N);
 int llie_se_mlp(int dtype, const float* pool_sums, int pixels, const void* w1, const float* b1, const void* w2, const float* b2, float* mean_scratch,
                 float* hidden_scratch, float* gate, int batch, int C, int Cs, llie_stream stream);
 int llie_film(const float* silu_temb, const float* wf, const float* bf, float* film, int rows, int T, int F, llie_stream stream);
+/* llie_pw_expand_nsplit: the channel split llie_pw_expand takes for M = batch x pixels rows and N output channels (its grid is M / 128 x
+ *   this many workgroups); M a multiple of 128, N of 64, else LLIE_ERR_ARG.
+ * llie_silu_rows: out[i] = silu(in[i]) on n fp32 values (the time embedding before llie_film, forward and backward). */
+int llie_pw_expand_nsplit(int M, int N);
+int llie_silu_rows(const float* in, float* out, int64_t n, llie_stream stream);
 
 /* The network's first and last kernels, the SE gate of the inference blocks, the attention tail, the layout converters and the
  * backward pass's GEMM epilogue.  Every contract clause below is checked before any HIP call and answered with LLIE_ERR_ARG.

@@ -1,6 +1,6 @@
 """Plain float64 references of the kernels behind the C ABI's per-kernel entry points, and the comparison helpers of the kernel
 tests (tests/test_gpu_forward_kernels.py, tests/test_gpu_boundary_kernels.py, tests/test_forward_refs_host.py,
-tests/test_gpu_backward_kernels.py, tests/test_backward_refs_host.py).
+tests/test_gpu_backward_kernels.py, tests/test_backward_refs_host.py, tests/test_gpu_expand_gram_kernels.py).
 
 Pure torch on CPU tensors, one function per operation.  A reference mirrors exactly the roundings its kernel does -- listed in each
 docstring, read from the kernel -- and nothing else: fp32 accumulation becomes float64.  Every reference returns
@@ -17,6 +17,7 @@ Layouts are the kernels': activations NHWC, [B][P][C] or [B][H][W][C]; tables [B
 import math
 import zlib
 
+import numpy as np
 import torch
 
 U = 2.0 ** -24
@@ -718,6 +719,213 @@ def pointwise_bwd_ref(kind, a, b, scale=0.0):
     return _f32(a64 * float(torch.tensor(scale, dtype=torch.float32))), None
 
 
+# ------------------------------------------------------------------------------------------------ llie_pw_expand (pwx.hip)
+def pw_expand_nsplit(M, N):
+    """nsplit_for (pwx.hip) with one 32-channel block per LDS buffer: the channels of a 128-pixel tile are halved over workgroups
+    while the grid has fewer than 512 of them, each part keeps at least two 32-channel blocks and stays a multiple of 64 wide."""
+    ns, nb = 1, N // 32
+    while (M // 128) * ns < 512 and nb % (2 * ns) == 0 and N // (64 * ns) >= 2 and (N // (2 * ns)) % 64 == 0:
+        ns *= 2
+    return ns
+
+
+def pw_expand_grid(M, N):
+    """-> (nsplit, tile remap on, nit): the remap of pw_expand_body runs where the 128-pixel tiles are a multiple of 8; nit = the
+    32-channel weight buffers a workgroup walks through."""
+    ns = pw_expand_nsplit(M, N)
+    return ns, (M // 128) % 8 == 0, N // ns // 32
+
+
+def pw_expand_weights(dtype, w32):
+    """pack_expand_kernel's (T)(w * 6.f), [N][K] float64.  fp16: hipcc folds the product and the conversion into one v_fma_mixlo_f16
+    (w * 6 + 0), the exact product rounded ONCE to fp16; bf16 has no such instruction: the product is rounded to fp32, then to bf16.
+    (The two differ where the fp32 product sits on an fp16 midpoint, about one weight in 10^4.)"""
+    e = w32.double() * 6.0  # exact: 24 + 3 significant bits
+    if dtype == 1:
+        return torch.from_numpy(e.numpy().astype(np.float16).astype(np.float64))  # numpy converts float64 to float16 directly
+    return _r64(_f32(e), dtype)
+
+
+def pw_expand_ref(dtype, xs, tabs, w32):
+    """llie_pw_expand: out[b][p][n] = sum_seg sum_k a'_seg[b][p][k] W6[n][k], a' = T(clamp01(x s + b)) with per-image tables
+    (gemm_operand, act 3), W6 = T(6 W) (pw_expand_weights).  xs: list of [B][P][ch] T tensors; tabs: (scale, shift) per segment, each
+    [B][ch] fp32 (already cut to the segment's channels); w32 fp32 [N][K].  Roundings mirrored: the operand, the weights; fp32
+    accumulation -> float64; the store rounds to T (one ulp of slack).  abssum and the flip slack are formed as pw_gemm_ref forms
+    them.  tile_stats_ref(stored, 128) is its statistics slab.  -> (ref, abssum, slack)"""
+    ops, sls = zip(*(gemm_operand(dtype, x, ACT_RELU6_S6, t[0], t[1]) for x, t in zip(xs, tabs)))
+    A, S, W = torch.cat(ops, -1), torch.cat(sls, -1), pw_expand_weights(dtype, w32)
+    ref, ab, sl = A @ W.t(), A.abs() @ W.abs().t(), S @ W.abs().t()
+    return ref, ab, sl + _ulp(ref, dtype)
+
+
+# ------------------------------------------------------------------------------------------------ llie_gram_stats / llie_gram_finalize (gram.hip)
+def gram_rows(P):
+    """gram_rows (gram.hip): pixels per workgroup -- 4096, halved down to 512 while P is no multiple of it or gives fewer than 16
+    workgroups.  nwg = P // gram_rows(P)."""
+    rp = 4096
+    while rp > 512 and (P % rp or P // rp < 16):
+        rp >>= 1
+    return rp
+
+
+def gram_operand(dtype, x, sc, bi):
+    """a' [B][p][K] as gram_activate8 forms it, and its rounding slack.  act_clamp01_pack: fp16 is one v_fma_mix with the clamp
+    modifier, the exact x s + b rounded ONCE to fp16; bf16 is fmaf, the clamp, then the conversion.  The reference rounds the exact
+    value to fp32 and then to T, which differs from either only where the fp32 value lies within one fp32 ulp of a rounding
+    boundary of T: that, not gemm_operand's wider margin, is the flip slack here -- over 10^4 to 10^5 pixels the wider one would
+    add up to more than the error of a kernel that never rounded a' at all (test_gram_bars_have_teeth)."""
+    z = _f32(x.double() * sc.double()[:, None, :] + bi.double()[:, None, :]).clamp(0.0, 1.0)
+    return _r64(z, dtype), _flip_slack(z, dtype, _ulp(z, 0))
+
+
+def gram_ref(dtype, x0, x1, sc, bi, chunk=8192):
+    """llie_gram_stats: G[b] = sum_px a' a'^T [K][K] and m[b] = sum_px a' [K] of a' = T(clamp01(x s + b)) over the virtual concat of x0
+    [B][P][c0] and x1 [B][P][c1] (or None); sc / bi fp32 [B][K].  Roundings mirrored: the operand (gram_operand); the products
+    of two T values are exact in fp32, fp32 accumulation -> float64.  The terms are non-negative, so the absolute sums are G and m
+    themselves.  Slack: one fp32 ulp, plus for every activation whose rounding to T may fall the other way its step times the other
+    factor (both factors on the diagonal).  Formed in chunks of pixels.  -> ((G, abssum, slack), (m, abssum, slack))"""
+    x = torch.cat([x0, x1], 2) if x1 is not None else x0
+    B, P, K = x.shape
+    G, SG = torch.zeros(B, K, K, dtype=torch.float64), torch.zeros(B, K, K, dtype=torch.float64)
+    m, sm = torch.zeros(B, K, dtype=torch.float64), torch.zeros(B, K, dtype=torch.float64)
+    for p0 in range(0, P, chunk):
+        a, s = gram_operand(dtype, x[:, p0:p0 + chunk], sc, bi)
+        G += torch.einsum("bpi,bpj->bij", a, a)
+        cross = torch.einsum("bpi,bpj->bij", s, a)
+        SG += cross + cross.transpose(1, 2) + torch.einsum("bpi,bpj->bij", s, s)
+        m += a.sum(1)
+        sm += s.sum(1)
+    return (G, G, SG + _ulp(G, 0)), (m, m, sm + _ulp(m, 0))
+
+
+def gram_finalize_ref(dtype, gtot, w, K, P, gamma, beta, film, film_stride, eps, post_scale):
+    """llie_gram_finalize: norm2 + FiLM of h1 = 6 W a' from the Gram totals.  gtot fp32 [B][K K + K] (G row-major, then m) exactly as
+    the kernel is given it; w [4 K][K] of T; 32 groups of K / 8 channels; film (or None): flat fp32, image b's row starting at b *
+    film_stride, (1 + film scale) at [c] and the FiLM shift at [4 K + c].  In float64 from those values: S1_c = 6 w_c . m, S2_c = 36
+    w_c^T G w_c, summed over the group; mean = S1 / n, var = max(S2 / n - mean^2, 0), n = (K / 8) P; rstd = 1 / sqrt(var + eps);
+    scale = gamma rstd (1 + fs) post, shift = ((beta - mean rstd gamma) (1 + fs) + fh) post (post_scale 0 = none).  The kernel forms
+    the sums and the variance in fp64 and the rest in fp32, so no rounding is mirrored.  The cancellation is treated as
+    gn_finalize_ref treats it: the absolute sums are those of the two expressions times 1 + kappa 2^-29, with kappa the absolute
+    sum of the quadratic form's terms (36 |w|^T G |w| / n, G >= 0) plus mean^2, over var + eps.
+    -> (scale, shift, abs_scale, abs_shift), [B][4 K]"""
+    eps = float(torch.tensor(eps, dtype=torch.float32))
+    g64, W = gtot.double(), w.double()
+    B, C, cg = g64.shape[0], 4 * K, K // 8
+    G, m = g64[:, :K * K].view(B, K, K), g64[:, K * K:]
+    s1 = 6.0 * torch.einsum("ck,bk->bc", W, m)
+    s2 = 36.0 * torch.einsum("ci,bij,cj->bc", W, G, W)
+    s2a = 36.0 * torch.einsum("ci,bij,cj->bc", W.abs(), G.abs(), W.abs())
+    n = float(cg * P)
+    grp = lambda t: t.view(B, 32, cg).sum(-1)  # noqa: E731
+    mean = grp(s1) / n
+    var = (grp(s2) / n - mean * mean).clamp_min(0.0)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    kappa = (grp(s2a) / n + mean * mean) / (var + eps)
+    rc = lambda t: t.repeat_interleave(cg, dim=1)  # noqa: E731
+    mean, rstd, cond = rc(mean), rc(rstd), 1.0 + rc(kappa) * 2.0 ** -29
+    g, b = gamma.double()[None, :], beta.double()[None, :]
+    sc, sh = g * rstd, b - mean * rstd * g
+    sha = b.abs() + (mean * rstd * g).abs()
+    if film is not None:
+        flat = film.double().reshape(-1)
+        f = torch.stack([flat[i * film_stride:i * film_stride + 2 * C] for i in range(B)])
+        fs, fh = 1.0 + f[:, :C], f[:, C:]
+        sc, sh, sha = sc * fs, sh * fs + fh, sha * fs.abs() + fh.abs()
+    if post_scale != 0.0:
+        ps = float(torch.tensor(post_scale, dtype=torch.float32))
+        sc, sh, sha = sc * ps, sh * ps, sha * abs(ps)
+    return sc, sh, sc.abs() * cond, sha * cond
+
+
+# ------------------------------------------------------------------------------------------------ llie_film / llie_silu_rows (small.hip)
+def film_ref(st, wf, bf):
+    """llie_film: film[r][f] = bf[f] + sum_t wf[f][t] st[r][t], all fp32 with nothing rounded in between (-> float64).  st [rows][T],
+    wf [F][T], bf [F].  -> (ref, abssum, slack)"""
+    s, W, b = st.double(), wf.double(), bf.double()
+    ref = s @ W.t() + b
+    return ref, s.abs() @ W.abs().t() + b.abs(), _ulp(ref, 0)
+
+
+def silu_ref(x):
+    """llie_silu_rows: siluf(x) = x / (1 + __expf(-x)) on fp32 values.  The absolute sum is the evaluation error silu_operand states,
+    |silu(x)| (1.5 |x| + 4), in units of 2^-24.  -> (ref, abssum, slack)"""
+    z = x.double()
+    ref = z * torch.sigmoid(z)
+    return ref, _silu_err(z), _ulp(ref, 0)
+
+
+# ------------------------------------------------------------------------------------------------ cases of tests/test_gpu_expand_gram_kernels.py
+# llie_pw_expand: (segments, N, P, B, affine_ld - K, (nsplit, tile remap, nit)): the grid values are what launch_cfg takes for the full
+# batch (pw_expand_grid re-derives them in tests/test_forward_refs_host.py; the GPU test asserts nsplit through llie_pw_expand_nsplit)
+PWX_CASES = [
+    ([128], 64, 128, 3, 0, (1, False, 2)),             # nsplit 1, the smallest N
+    ([128], 576, 128, 3, 0, (1, False, 18)),           # nsplit 1, an 18-buffer channel loop
+    ([64, 64], 512, 256, 3, 24, (8, False, 2)),        # two segments, affine_ld = K + 24
+    ([192], 128, 128, 8, 0, (2, True, 2)),             # nsplit 2, tile remap (8 tiles), NCH = 3: the prefetch does not rotate
+    ([64, 64, 64], 768, 384, 1, 24, (4, False, 6)),    # three segments (koff2), affine_ld = K + 24
+    ([128, 64], 1152, 1024, 1, 0, (2, True, 18)),      # the bench's nsplit = 2 with a long loop, remap
+    ([256], 1024, 128, 5, 0, (16, False, 2)),          # NCH = 4: the 3-deep prefetch rotates once
+    ([128, 64, 64], 1024, 256, 4, 0, (16, True, 2)),   # ... over three segments
+    ([384], 1536, 128, 3, 0, (8, False, 6)),           # NCH = 6
+    ([256, 64, 64], 1536, 1024, 1, 0, (8, True, 6)),   # NCH = 6 over three segments
+    ([512], 2048, 128, 2, 0, (32, False, 2)),          # K = 512: stores straight from registers, NCH = 8
+    ([384, 64, 64], 2048, 256, 4, 0, (32, True, 2)),   # ... over three segments
+    ([512], 1088, 128, 2, 0, (1, False, 34)),          # K = 512 with a 34-buffer loop, nsplit 1
+]
+# llie_gram_stats: (c0, c1, P, B, nwg)
+GRAM_CASES = [(32, 0, 512, 3, 1), (64, 32, 1536, 2, 3), (32, 32, 4096, 2, 8), (96, 0, 8704, 2, 17), (32, 0, 17408, 1, 17),
+              (64, 0, 16384, 2, 16), (64, 32, 65536, 1, 16)]
+
+
+def pwx_inputs(gen, dtype, segs, n, P, B, ld_extra=0):
+    """The input family of test_gpu_round3._expand_case: x ~ 1.5 N(0, 1) rounded to T, w ~ N(0, 1 / K), norm1's tables as gn_finalize
+    emits them for act 3 (scale / 6 in [1/12, 1/4], shift / 6 ~ N(0.4, 0.5) / 6).  The tables are one [B][K + ld_extra] pair that every
+    segment reads at its own channel offset.  -> (xs [B][P][ch], w32 [n][K], sc, bi)"""
+    K = sum(segs)
+    xs = [_rt(torch.randn(B, P, c, generator=gen) * 1.5, dtype) for c in segs]
+    w32 = torch.randn(n, K, generator=gen) / math.sqrt(K)
+    sc = (torch.rand(B, K + ld_extra, generator=gen) + 0.5) / 6
+    bi = (torch.randn(B, K + ld_extra, generator=gen) * 0.5 + 0.4) / 6
+    return xs, w32, sc, bi
+
+
+def seg_tables(segs, sc, bi):
+    """the per-segment cuts of one table pair: [(scale [B][ch], shift [B][ch])]"""
+    offs = [sum(segs[:i]) for i in range(len(segs))]
+    return [(sc[:, o:o + c], bi[:, o:o + c]) for o, c in zip(offs, segs)]
+
+
+def gram_inputs(gen, dtype, c0, c1, P, B, family):
+    """family "gauss": the inputs of pwx_inputs; "ones": tables that make every activation of the first input exactly 1 (scale 0, shift
+    1) and every other exactly 0, so that G and m are exact integers (P or 0).  -> (x0, x1 or None, sc, bi)"""
+    K = c0 + c1
+    x0 = _rt(torch.randn(B, P, c0, generator=gen) * 1.5, dtype)
+    x1 = _rt(torch.randn(B, P, c1, generator=gen) * 1.5, dtype) if c1 else None
+    sc = (torch.rand(B, K, generator=gen) + 0.5) / 6
+    bi = (torch.randn(B, K, generator=gen) * 0.5 + 0.4) / 6
+    if family == "ones":
+        sc, bi = torch.zeros(B, K), torch.zeros(B, K)
+        bi[:, :c0] = 1.0
+    return x0, x1, sc, bi
+
+
+def gram_fin_inputs(gen, dtype, K, P, B, hard):
+    """The two families of test_gpu_round4._gram_case: plain, and "hard" -- nearly constant activations near the clamp's upper end with
+    expand rows of (almost) zero sum, where the variance is a small difference of large terms.  The totals are formed in float64 from
+    the T activations and handed over in fp32, as llie_gram_stats leaves them.  -> (gtot fp32 [B][K K + K], w [4 K][K] of T, a)"""
+    if hard:
+        a = (0.9 + 0.02 * torch.randn(B, P, K, generator=gen)).clamp(0, 1)
+        w = torch.randn(4 * K, K, generator=gen) / math.sqrt(K)
+        w = w - w.mean(1, keepdim=True) * 0.98
+    else:
+        a = torch.rand(B, P, K, generator=gen).clamp(0, 1) * (torch.rand(B, 1, K, generator=gen) + 0.2)
+        w = torch.randn(4 * K, K, generator=gen) / math.sqrt(K)
+    a, w = _rt(a, dtype), _rt(w, dtype)
+    ad = a.double()
+    gtot = torch.cat([torch.einsum("bpi,bpj->bij", ad, ad).reshape(B, K * K), ad.sum(1)], 1).float()
+    return gtot, w, a
+
+
 # ------------------------------------------------------------------------------------------------ bars
 # BAR x 2^-24 x abssum per entry.  "worst" = the worst ratio |out - ref| / (2^-24 abssum) measured on the MI355X over all cases of
 # the kernel in tests/test_gpu_forward_kernels.py and seeds 0, 1, 2 (LLIE_FWD_TEST_SEED), as fp32 / fp16 / bf16; the bar is about
@@ -754,3 +962,11 @@ BAR_PW_BWD = 6.7          # worst, sigmoid' 0.67, SiLU' 0.55 (fp32 kernels)
 BAR_TIME_EMBED = 6.8      # worst, temb 0.68, silu_temb 0.53 (fp32 kernel)
 BAR_SIN_EMBED = 2.0       # worst 0.00: always inside the ulp of the stored value.  Not measured but reasoned: the device library's cosf and
                           # sinf are accurate to 2 ulp of a result that is at most 1, one of which is the slack, the other at most 2^-24
+# the expand GEMM, the Gram statistics, their finalize and FiLM: worst over all cases of tests/test_gpu_expand_gram_kernels.py, as fp16 /
+# bf16 (there is no fp32 form), each the worst of seeds 0, 1, 2 (per seed in profiles/r31/README.md); the bar is ten times the worst
+BAR_PWX = 4.3             # worst 0.42 / 0.27 (seeds 0, 1, 2: fp16 0.35, 0.42, 0.40; bf16 0.27, 0.13, 0.18)
+BAR_PWX_STATS = 17.0      # worst 1.69 / 1.54 (fp16 1.56, 1.42, 1.69; bf16 1.51, 1.54, 1.23)
+BAR_GRAM = 30.0           # G, worst 2.39 / 2.94 (fp16 2.21, 2.39, 2.22; bf16 2.88, 2.82, 2.94)
+BAR_GRAM_M = 20.0         # m, worst 1.78 / 1.93 (fp16 1.78, 1.50, 1.40; bf16 1.78, 1.62, 1.93)
+BAR_GRAM_FIN = 20.0       # worst, scale 2.00 / 1.96, shift 1.91 / 1.84 (the weights' type; the tables are fp32)
+BAR_FILM = 9.0            # worst, film 0.86 (seeds: 0.83, 0.86, 0.75), silu_rows 0.53 (fp32 kernels)

@@ -24,7 +24,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 MODULES = ["forward_kernels", "backward_kernels", "boundary_kernels", "softattn_kernels", "expand_dw_paths", "irbx_prologue", "input_grad_kernel",
            "upconv_fold", "upconv_maps", "upconv_maps_items", "expand_dw_project", "expand_dw_project_skip", "expand_dw_project_tail", "expand_scan",
-           "expand_pool_border", "wide_project", "wide_gram", "weight_loading", "stamps", "irb_paths", "round2", "round3", "round4"]
+           "expand_pool_border", "wide_project", "wide_gram", "weight_loading", "stamps", "irb_paths", "round2", "round3", "round4",
+           "expand_gram_kernels"]
 
 
 class Recorder:
