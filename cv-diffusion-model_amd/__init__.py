@@ -12,6 +12,9 @@ from .unet import (EfficientUNet, EfficientUNetConfig, create_efficient_unet, In
                    LinearAttention, StandardAttention, Downsample, Upsample, SqueezeExcitation)
 from .scheduler import LCMScheduler, LCMSchedulerOutput, LCMDenoisingLoop, get_lcm_timesteps
 from .ddim import ddim_timesteps, ddim_step_host, ddim_enhance_host
+from .guidance import (guide_array, cond_dropout_array, guidance_pair_array, scheduler_step_array, guided_enhance_host,
+                       check_guidance_scale, check_cond_dropout, check_guidance_range, guide_device, guidance_pair_device,
+                       cond_dropout_device)
 from .pipeline import (LowLightDiffusion, LowLightDiffusionOutput, LowLightLCMDistillation, normalize_image,
                        denormalize_image, x0_loss, x0_loss_host, consistency_target_host, consistency_loss_host)
 from .sharding import shard_range, enhance_sharded, all_gather_batch, all_reduce_gradients
@@ -50,4 +53,6 @@ __all__ = [
     "TrainingConfig", "LowLightTrainer", "train_model", "make_lr_scheduler", "build_checkpoint", "comparison_grid",
     "comparison_grid_host", "distill_draw_seed", "LowLightDistiller", "timestep_index_range", "default_skip_terminal",
     "ddim_timesteps", "ddim_step_host", "ddim_enhance_host",
+    "guide_array", "cond_dropout_array", "guidance_pair_array", "scheduler_step_array", "guided_enhance_host",
+    "check_guidance_scale", "check_cond_dropout", "check_guidance_range", "guide_device", "guidance_pair_device", "cond_dropout_device",
 ]

@@ -59,6 +59,7 @@ EXPORTS = [
     "llie_unet_backward_dx", "llie_init_conv_dgrad",
     "llie_softattn", "llie_softattn_backward", "llie_softattn_bwd_floats",
     "llie_pw_expand_nsplit", "llie_silu_rows",
+    "llie_guide", "llie_guidance_pair", "llie_cond_dropout",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 PW_SIGMOID_BWD, PW_RELU6_BWD, PW_SILU_BWD, PW_SCALE = 0, 1, 2, 3  # llie_pointwise_kind
@@ -309,6 +310,9 @@ def lib() -> C.CDLL:
     L.llie_consistency_loss.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, ci, i64, vp, i64, vp]
     L.llie_consistency_target_ex.argtypes = [vp, vp, vp, vp, vp, ci, vp, ci, i64, ci, vp]
     L.llie_consistency_loss_ex.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, i64, ci, i64, ci, vp]
+    L.llie_guide.argtypes = [vp, vp, vp, C.c_float, vp, ci, i64, vp]
+    L.llie_guidance_pair.argtypes = [vp, vp, vp, vp, ci, i64, vp]
+    L.llie_cond_dropout.argtypes = [vp, vp, C.c_float, vp, ci, i64, vp]
     L.llie_ema_create.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), ci, C.POINTER(vp)]
     L.llie_ema_update.argtypes = [vp, C.c_double, vp]
     L.llie_ema_destroy.argtypes = [vp]

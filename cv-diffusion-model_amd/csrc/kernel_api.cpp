@@ -871,6 +871,24 @@ int llie_consistency_loss(const float* x_t, const float* x_next, const float* e_
                                   LLIE_PRED_EPSILON, stream);
 }
 
+// ---- classifier-free guidance
+int llie_guide(const float* out_cond, const float* out_uncond, const float* w_rows, float w, float* out, int batch, int64_t per_sample,
+               llie_stream stream) {
+  return kerr("guide", launch_guide(out_cond, out_uncond, w_rows, w, out, batch, per_sample, hs(stream)), LLIE_ERR_ARG,
+              "null or unaligned pointer, empty shape, or a non-finite guidance scale");
+}
+
+int llie_guidance_pair(const float* latents, const float* cond, float* latents2, float* cond2, int batch, int64_t per_sample,
+                       llie_stream stream) {
+  return kerr("guidance_pair", launch_guidance_pair(latents, cond, latents2, cond2, batch, per_sample, hs(stream)), LLIE_ERR_ARG,
+              "null or unaligned pointer, or empty shape");
+}
+
+int llie_cond_dropout(const float* in, const float* u, float p, float* out, int batch, int64_t per_sample, llie_stream stream) {
+  return kerr("cond_dropout", launch_cond_dropout(in, u, p, out, batch, per_sample, hs(stream)), LLIE_ERR_ARG,
+              "null or unaligned pointer, empty shape, or p outside [0, 1]");
+}
+
 // the optimiser's table types: OptTensor.p = source parameter, OptTensor.ema = shadow written in place (m, v unused)
 struct llie_ema {
   OptTensor* tensors = nullptr;

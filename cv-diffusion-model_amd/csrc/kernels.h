@@ -700,6 +700,13 @@ hipError_t launch_consistency_loss(const DistillArgs& a, double* partial, float*
 // ema = ema * decay + (1 - decay) * p over the tables' tensors (OptTensor.p = source, OptTensor.ema = destination)
 hipError_t launch_ema_lerp(const OptTensor* tensors, const OptChunk* chunks, int nchunks, double decay, hipStream_t s);
 
+// (10b) classifier-free guidance (guidance.hip): fp32 [batch, per] tensors; hipErrorInvalidValue before any launch for a null or
+// unaligned pointer, an empty shape, a non-finite w (when w_rows is null) or a p outside [0, 1]
+hipError_t launch_guide(const float* out_cond, const float* out_uncond, const float* w_rows, float w, float* out, int batch, int64_t per,
+                        hipStream_t s);
+hipError_t launch_guidance_pair(const float* latents, const float* cond, float* latents2, float* cond2, int batch, int64_t per, hipStream_t s);
+hipError_t launch_cond_dropout(const float* in, const float* u, float p, float* out, int batch, int64_t per, hipStream_t s);
+
 // (11) full-resolution images as overlapping SH x SW tiles (tiles.hip).  The plan of one axis of length L, tile side S, overlap
 // v (0 <= 2v <= S): one tile at 0 when L <= S, else n = ceil((L - S) / (S - v)) + 1 tiles at o_i = floor(i (L - S) / (n - 1)).
 // The same two functions serve the host (llie_tile_count / llie_tile_origins) and the kernels, which compute origins themselves.

@@ -14,6 +14,7 @@ import torch
 
 from . import _native as N
 from . import hostio
+from .guidance import check_guidance_range, check_guidance_scale, guided_keyword
 from .metrics import evaluate
 from .pipeline import LowLightDiffusion, LowLightLCMDistillation
 from .trainer import TrainingConfig, _EpochLoop, distill_draw_seed, make_lr_scheduler, resolved_compute_dtype
@@ -69,7 +70,9 @@ class LowLightDistiller(_EpochLoop):
       per batch of b pairs, in loader order, the reference's order of draws (low_light_diffusion.py:337-349: noise, then idx):
         noise = torch.randn(b, 3, H, W, generator=g, device=dev)
         idx = torch.randint(0, hi, (b,), generator=g, device=dev)
-        loss = step(low_light, normal_light, num_inference_steps, noise=noise, idx=idx);  lr_scheduler.step()
+        u = torch.rand(b, generator=g, device=dev);  w = u * (w_hi - w_lo) + w_lo      only with distill.guidance: (w_lo, w_hi) =
+                                                                                      distill.guidance_scale_range; two fp32 operations
+        loss = step(low_light, normal_light, num_inference_steps, noise=noise, idx=idx[, w=w]);  lr_scheduler.step()
     With `accumulate=k` > 1 the draws are the same and `step(...)` becomes `step.accumulate(...)`, with `step.apply()` and
     `lr_scheduler.step()` after each window's last batch, as in the trainer.
 
@@ -84,7 +87,7 @@ class LowLightDistiller(_EpochLoop):
 
     def __init__(self, distill: LowLightLCMDistillation, train_loader, val_loader=None, config: Optional[TrainingConfig] = None, *,
                  num_inference_steps: Optional[int] = None, ema_decay: float = 0.95, skip_terminal: Optional[bool] = None,
-                 crop_size: Optional[Tuple[int, int]] = None, accumulate: int = 1):
+                 crop_size: Optional[Tuple[int, int]] = None, accumulate: int = 1, val_guidance_scale: Optional[float] = None):
         if not isinstance(distill, LowLightLCMDistillation):
             raise ValueError(f"distill is a LowLightLCMDistillation, got {type(distill).__name__}")
         self._init_shapes(config, train_loader, val_loader, crop_size, accumulate)
@@ -96,6 +99,7 @@ class LowLightDistiller(_EpochLoop):
         if not (0 <= ema_decay <= 1):
             raise ValueError(f"ema_decay must be in [0, 1], got {ema_decay!r}")
         self.ema_decay = float(ema_decay)
+        self.val_guidance_scale = check_guidance_scale(val_guidance_scale)
         if skip_terminal is not None and not isinstance(skip_terminal, bool):
             raise ValueError(f"skip_terminal is True, False or None, got {skip_terminal!r}")
         self.skip_terminal = default_skip_terminal(distill.student_prediction) if skip_terminal is None else skip_terminal
@@ -168,7 +172,11 @@ class LowLightDistiller(_EpochLoop):
             b = low.shape[0]
             noise = torch.randn(b, 3, hh, ww, generator=g, device=dev)
             idx = torch.randint(0, hi, (b,), generator=g, device=dev)
-            return (self.step.accumulate if windowed else self.step)(low, normal, steps, noise=noise, idx=idx)
+            guided = {}
+            if self.distill.guidance:
+                w_lo, w_hi = check_guidance_range(self.distill.guidance_scale_range)
+                guided["w"] = torch.rand(b, generator=g, device=dev).mul_(w_hi - w_lo).add_(w_lo)
+            return (self.step.accumulate if windowed else self.step)(low, normal, steps, noise=noise, idx=idx, **guided)
 
         return self._run_epoch(micro)
 
@@ -176,13 +184,16 @@ class LowLightDistiller(_EpochLoop):
     def validate(self) -> float:
         """`evaluate(distill.ema_student, val_loader, num_inference_steps=num_inference_steps, seed=config.seed, loss=False)`
         (through `enhance_frame` for a rectangular loader): returns the mean PSNR and keeps the whole result in
-        `last_validation`.  Parameters and the networks' train() / eval() modes are as before afterwards."""
+        `last_validation`; `val_guidance_scale` (the constructor's; normally None: a guided-distilled student needs no second
+        forward) is passed on as `guidance_scale=`, here and in the sample sheet.  Parameters and the networks' train() / eval()
+        modes are as before afterwards."""
         if self.val_loader is None:
             raise ValueError("validate needs a val_loader")
         net = self._net()
         mode = net.training
         try:
-            res = evaluate(net, self.val_loader, num_inference_steps=self.num_inference_steps, seed=self.config.seed, loss=False)
+            res = evaluate(net, self.val_loader, num_inference_steps=self.num_inference_steps, seed=self.config.seed, loss=False,
+                           **guided_keyword(self.val_guidance_scale))
         finally:
             net.train(mode)
         self.last_validation = res

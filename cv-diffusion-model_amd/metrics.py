@@ -41,6 +41,7 @@ import torch.nn.functional as F
 from . import _native as N
 from .data import DeviceFrameStore, DevicePairLoader
 from .ddim import check_sampler
+from .guidance import guided_keyword as _guided_kw
 from .tiling import enhance_tiled, enhance_frame_u8, frame_pad, resolve_tile_plan
 
 WINDOW_TAPS, WINDOW_SIGMA = 11, 1.5
@@ -340,7 +341,8 @@ def _summary(names, triples: np.ndarray, loss: Optional[float]) -> Dict[str, obj
 
 @torch.no_grad()
 def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[int] = None, seed: int = 0, loss: bool = True,
-             weights: Optional[Sequence[torch.Tensor]] = None, sampler: str = "lcm") -> Dict[str, object]:
+             weights: Optional[Sequence[torch.Tensor]] = None, sampler: str = "lcm",
+             guidance_scale: Optional[float] = None) -> Dict[str, object]:
     """PSNR / SSIM / MSE of `model.enhance` against the normal-light images of `loader` (normally a "val" DevicePairLoader:
     centre crops in file order, last partial batch kept), and the validation loss of the reference's `LowLightTrainer.validate`.
 
@@ -358,12 +360,15 @@ def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[i
       A rectangular loader (`crop_size` = (H, W), H != W; frame-size training) is scored through `model.enhance_frame` and the
       loss runs at that shape: the same recipe with every [.., 3, S, S] draw [.., 3, H, W].  A square loader must crop
       model.image_size, as before.
+      guidance_scale=w scores `model.enhance(..., guidance_scale=w)` (classifier-free guidance; None: off); the draws and the
+      loss are unchanged.
 
     Returns {"n", "psnr", "ssim", "mse", ["loss",] "per_image": {"filename", "psnr", "ssim", "mse"}}: psnr / ssim / mse are the
     means over images of the per-image values (float64 sums in file order), loss = sum of batch losses / len(loader).  Everything
     stays on the device until one copy at the end.  `weights=` (e.g. FusedAdamW.ema_tensors(), in model.parameters() order) is
     copied into the parameters for the call and the original values are restored afterwards, also when the call raises."""
     check_sampler(sampler)
+    guided = _guided_kw(guidance_scale)
     if not isinstance(loader, DevicePairLoader):
         raise ValueError(f"evaluate expects a DevicePairLoader, got {type(loader).__name__}")
     dev = loader.store.device
@@ -387,7 +392,7 @@ def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[i
             if loss:
                 t = torch.randint(0, t_max, (b,), generator=g, device=dev)
                 eps = torch.randn(b, 3, hh, ww, generator=g, device=dev)
-            triples.append(_metrics_out3(enhance(low, nsteps, noise=noise, sampler=sampler), normal, (-1.0, 1.0)))
+            triples.append(_metrics_out3(enhance(low, nsteps, noise=noise, sampler=sampler, **guided), normal, (-1.0, 1.0)))
             if loss:
                 pred = model.forward(low, normal, timesteps=t, noise=eps, frame=frame)["noise_pred"]
                 losses.append(F.mse_loss(pred, eps).double().reshape(1))
@@ -405,7 +410,7 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
                              overlap: Optional[int] = None, tile_batch: int = 32,
                              weights: Optional[Sequence[torch.Tensor]] = None, mode: str = "tiled",
                              sync: str = "none", sampler: str = "lcm", tile=None,
-                             max_tile_pixels: Optional[int] = None) -> Dict[str, object]:
+                             max_tile_pixels: Optional[int] = None, guidance_scale: Optional[float] = None) -> Dict[str, object]:
     """PSNR / SSIM / MSE at the images' own resolution: every low-light frame of the paired `store` (any sizes >= 11 x 11) goes
     through `enhance_tiled` and is scored against its normal-light frame on the bytes (x = byte / 255).
 
@@ -422,7 +427,8 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
     sync="latents" (mode="tiled") passes through to `enhance_tiled`: the tiles share one latent canvas at every step.
     tile= / max_tile_pixels= (mode="tiled") pass through as well: with tile=(TH, TW) the canvas of the recipe is
     [steps, 3, max(H, TH), max(W, TW)], and with tile="auto" TH x TW is the tile `auto_tile_plan` gives that image.
-    sampler="ddim" passes through to `enhance_tiled` / `enhance_frame_u8` in every mode; steps = 1 in the draws above."""
+    sampler="ddim" passes through to `enhance_tiled` / `enhance_frame_u8` in every mode; steps = 1 in the draws above.
+    guidance_scale= passes through the same way (refused by `enhance_tiled` with sync="latents")."""
     if mode not in ("tiled", "frame"):
         raise ValueError(f'mode must be "tiled" or "frame", got {mode!r}')
     if mode == "frame" and (overlap is not None or tile_batch != 32 or sync != "none" or tile is not None or max_tile_pixels is not None):
@@ -430,6 +436,7 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
     if sync not in ("none", "latents"):
         raise ValueError(f'sync must be "none" or "latents", got {sync!r}')
     check_sampler(sampler)
+    guided = _guided_kw(guidance_scale)
     if not isinstance(store, DeviceFrameStore) or not store.paired:
         raise ValueError("evaluate_full_resolution expects a paired DeviceFrameStore")
     dev = store.device
@@ -443,7 +450,7 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
         for i, (h, w) in enumerate(store.sizes):
             if mode == "frame":
                 canvas = torch.randn(steps, 3, frame_pad(h), frame_pad(w), generator=g, device=dev)
-                out = enhance_frame_u8(model, store.frame(i), nsteps, noise=canvas, sampler=sampler)
+                out = enhance_frame_u8(model, store.frame(i), nsteps, noise=canvas, sampler=sampler, **guided)
             else:
                 sh, sw, vy, vx = resolve_tile_plan(model, (h, w), tile, overlap, max_tile_pixels)
                 canvas = torch.randn(steps, 3, max(h, sh), max(w, sw), generator=g, device=dev)
@@ -452,7 +459,7 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
                 else:  # the plan is settled here, so "auto" is passed on as the tile it chose
                     plan = {"tile": (sh, sw), "overlap": (vy, vx)}
                 out = enhance_tiled(model, store.frame(i), nsteps, tile_batch=tile_batch, noise=canvas, sync=sync, sampler=sampler,
-                                    **plan)
+                                    **plan, **guided)
             triples.append(_metrics_out3(out, store.frame(n + i), None))
         flat = torch.cat(triples).cpu().numpy()
     return _summary(store.names, flat, None)

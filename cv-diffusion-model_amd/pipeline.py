@@ -33,6 +33,7 @@ import torch.nn.functional as F
 
 from . import _native as N
 from .ddim import check_sampler
+from . import guidance as G
 from .scheduler import LCMScheduler
 from .unet import EfficientUNet, create_efficient_unet
 
@@ -96,7 +97,8 @@ class LowLightDiffusion(nn.Module):
     # ------------------------------------------------------------------ training-side forward (:115-175)
     def forward(self, low_light: torch.Tensor, normal_light: Optional[torch.Tensor] = None,
                 timesteps: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
-                return_dict: bool = True, *, frame: bool = False) -> Union[torch.Tensor, Dict[str, torch.Tensor]]:
+                return_dict: bool = True, *, frame: bool = False, cond_dropout: float = 0.0,
+                cond_u: Optional[torch.Tensor] = None) -> Union[torch.Tensor, Dict[str, torch.Tensor]]:
         """With `normal_light`: q-sample -> denoiser, returning {noise_pred, noise, timesteps}.  When gradients
         are enabled `noise_pred` carries a grad_fn whose backward is the engine's reverse pass
         (llie_unet_backward): `loss.backward()` fills `.grad` of every parameter, so the reference trainer's
@@ -109,7 +111,13 @@ class LowLightDiffusion(nn.Module):
         the noised input too: it is `scheduler.add_noise(normal_light, noise, timesteps)` of the returned draws.
         `frame=True` (extension): the training branch runs at the batch's own H x W, any shape llie_train_shape_ok accepts
         (EfficientUNet.forward_split); without it a shape other than image_size is a ValueError, as before.
+        `cond_dropout=p` (extension; classifier-free guidance training, guidance.py): with p > 0 row b of `low_light` is replaced
+        by the null condition (all zeros) where u[b] < p, by llie_cond_dropout, before the denoiser; u is `cond_u` (fp32 [B]) or
+        `torch.rand(B, device=device)` drawn from the global device generator after the timestep and noise draws.  The
+        gradient of `low_light` is masked by the same kernel: dropped rows are exactly 0.  With p == 0 no draw is made and the
+        call is what it was.
         Without `normal_light`: `enhance(low_light)`."""
+        p_drop = G.check_cond_dropout(cond_dropout)
         if normal_light is None:
             return self.enhance(low_light)
         batch, device = low_light.shape[0], low_light.device
@@ -117,6 +125,9 @@ class LowLightDiffusion(nn.Module):
             timesteps = torch.randint(0, self.scheduler.config.num_train_timesteps, (batch,), device=device)
         if noise is None:
             noise = torch.randn_like(normal_light)
+        if p_drop > 0:
+            _require_hip(low_light, "LowLightDiffusion.forward")
+            low_light = _CondDropoutFn.apply(low_light, cond_uniforms(cond_u, batch, device), p_drop)
         noisy = self.scheduler.add_noise(normal_light, noise, timesteps)
         noise_pred = self.unet.forward_split(noisy, low_light, timesteps, uniform_t=False, frame=frame)
         if return_dict:
@@ -131,7 +142,8 @@ class LowLightDiffusion(nn.Module):
     def enhance(self, low_light: torch.Tensor, num_inference_steps: Optional[int] = None,
                 generator: Optional[torch.Generator] = None, return_intermediate: bool = False, *,
                 noise: Optional[Union[torch.Tensor, Sequence[torch.Tensor]]] = None,
-                return_noise_pred: bool = False, sampler: str = "lcm") -> Union[torch.Tensor, LowLightDiffusionOutput]:
+                return_noise_pred: bool = False, sampler: str = "lcm", guidance_scale: Optional[float] = None,
+                _passes: Optional[int] = None) -> Union[torch.Tensor, LowLightDiffusionOutput]:
         """low_light [B,3,S,S] in [-1,1] -> enhanced [B,3,S,S].
 
         sampler="lcm" (the default) is the reference's loop: predict x0, re-noise with a fresh draw -- the sampler of a
@@ -145,8 +157,20 @@ class LowLightDiffusion(nn.Module):
         `generator` (:208-211), then one draw per non-final step from the global generator
         (lcm_scheduler.py:237).  `noise=` (extension) supplies those draws, e.g. CPU-generated ones for
         a bit-comparable run against the CPU reference: a [steps,B,3,S,S] tensor or a list of `steps`
-        tensors (entries after the first are the re-noising draws of steps 0..steps-2)."""
+        tensors (entries after the first are the re-noising draws of steps 0..steps-2).
+
+        Classifier-free guidance (extension; guidance.py has the definitions): `guidance_scale=w`, any finite number other than
+        1.0, replaces the network output of every step by o_u + w (o_c - o_u), o_c the output on `low_light` and o_u the one on
+        the null condition (the all-zero image) -- for a model trained with `cond_dropout`.  None and 1.0 run the path above
+        unchanged: the captured loop, the same bits, no second forward.  The guided loop is driven from the host: per step
+        llie_guidance_pair, one denoiser pass over 2B rows (rows b and b + B are the two outputs of image b), llie_guide, the
+        scheduler's step kernel with the step's coefficients, and the final clamp; nothing in it allocates, waits for the device
+        or copies from the host.  Where the engine refuses 2B rows (llie_frame_shape_ok, workspace) the two outputs come from two
+        B-row passes instead, with the same bits (every kernel is bitwise batch-invariant).  Draws, `noise=` shapes,
+        `generator`, `return_intermediate` and `sampler` are those of the unguided call; `return_noise_pred` returns the guided
+        output of each step.  A non-finite scale is a ValueError."""
         check_sampler(sampler)
+        G.check_guidance_scale(guidance_scale)
         device = low_light.device
         if device.type != "cuda":
             raise RuntimeError("LowLightDiffusion.enhance runs only on a HIP device; there is no CPU fallback")
@@ -154,13 +178,15 @@ class LowLightDiffusion(nn.Module):
         if tuple(low_light.shape[1:]) != (3, s, s):
             raise ValueError(f"low_light must be [B,3,{s},{s}] (latents are allocated at image_size, "
                              f"low_light_diffusion.py:208-210); got {tuple(low_light.shape)}")
-        return self._enhance_at(low_light, None, num_inference_steps, generator, return_intermediate, noise, return_noise_pred, sampler)
+        return self._enhance_at(low_light, None, num_inference_steps, generator, return_intermediate, noise, return_noise_pred, sampler,
+                                guidance_scale, _passes)
 
     @torch.no_grad()
     def enhance_frame(self, low_light: torch.Tensor, num_inference_steps: Optional[int] = None,
                       generator: Optional[torch.Generator] = None, return_intermediate: bool = False, *,
                       noise: Optional[Union[torch.Tensor, Sequence[torch.Tensor]]] = None,
-                      return_noise_pred: bool = False, sampler: str = "lcm") -> Union[torch.Tensor, LowLightDiffusionOutput]:
+                      return_noise_pred: bool = False, sampler: str = "lcm", guidance_scale: Optional[float] = None,
+                      _passes: Optional[int] = None) -> Union[torch.Tensor, LowLightDiffusionOutput]:
         """Frame mode (extension): low_light [B,3,H,W] in [-1,1] -> enhanced [B,3,H,W], the whole loop (`sampler`: as in
         `enhance`) at the frame's own size.  The module tree is the one `image_size` fixed (attention placement, state_dict); the
         network is fully convolutional and its attention linear in the pixel count, so it runs at any H x W the engine's frame rule
@@ -169,15 +195,17 @@ class LowLightDiffusion(nn.Module):
         ValueError naming it; frames past the size cap go through `enhance_tiled`.
 
         Semantics, noise order and outputs are `enhance`'s, with [steps,B,3,H,W] noise ([1,B,3,H,W] for DDIM); on an S x S input the
-        result is `enhance`'s, bit for bit.  Inference only."""
+        result is `enhance`'s, bit for bit.  `guidance_scale`: as in `enhance`; a frame whose 2B rows break the frame rule runs the
+        two-pass form.  Inference only."""
         check_sampler(sampler)
+        G.check_guidance_scale(guidance_scale)
         device = low_light.device
         if device.type != "cuda":
             raise RuntimeError("LowLightDiffusion.enhance_frame runs only on a HIP device; there is no CPU fallback")
         if low_light.dim() != 4 or low_light.shape[1] != 3:
             raise ValueError(f"low_light must be [B,3,H,W]; got {tuple(low_light.shape)}")
         return self._enhance_at(low_light, (int(low_light.shape[2]), int(low_light.shape[3])), num_inference_steps, generator,
-                                return_intermediate, noise, return_noise_pred, sampler)
+                                return_intermediate, noise, return_noise_pred, sampler, guidance_scale, _passes)
 
     def ddim_schedule(self, num_inference_steps: Optional[int] = None) -> Tuple[List[int], List[N.StepCoef]]:
         """(timesteps, one N.StepCoef each) of the DDIM loop of `num_inference_steps` steps (default: self.num_inference_steps).
@@ -192,8 +220,12 @@ class LowLightDiffusion(nn.Module):
         return ts, [self.scheduler.ddim_step_coefficients(t, t - c) for t in ts]
 
     def _enhance_at(self, low_light, frame, num_inference_steps, generator, return_intermediate, noise, return_noise_pred,
-                    sampler="lcm"):
-        """The loop of `enhance` (frame is None: image_size, llie_enhance) and `enhance_frame` (frame = (H, W), llie_enhance_hw)."""
+                    sampler="lcm", guidance_scale=None, passes=None):
+        """The loop of `enhance` (frame is None: image_size, llie_enhance) and `enhance_frame` (frame = (H, W), llie_enhance_hw);
+        with a `guidance_scale` other than None / 1.0, the host-driven guided loop (`_guided_loop`) after the same setup."""
+        guided = G.guidance_is_on(guidance_scale)
+        if passes not in (None, 1, 2):
+            raise ValueError(f"_passes must be None, 1 or 2, got {passes!r}")
         device = low_light.device
         b = low_light.shape[0]
         hh, ww = frame if frame is not None else (self.image_size, self.image_size)
@@ -210,7 +242,9 @@ class LowLightDiffusion(nn.Module):
         # the per-step outputs a caller asks for make it grow with the step count
         stage_steps = 8 if ddim and not (return_intermediate or return_noise_pred) else max(steps, 8)
         prepared = None
-        if frame is not None:
+        if guided:
+            passes = self._guided_plan(b, device, frame, passes)  # a refused frame raises here, before any draw or launch
+        elif frame is not None:
             try:  # the workspace query applies the frame rule: a refused frame raises before any draw or launch
                 prepared = self.unet._prepare(b, device, enhance_steps=stage_steps, frame=frame)
             except ValueError as e:
@@ -238,6 +272,9 @@ class LowLightDiffusion(nn.Module):
         enhanced = torch.empty(b, 3, hh, ww, dtype=torch.float32, device=device)
         inter = torch.empty(steps, b, 3, hh, ww, dtype=torch.float32, device=device) if return_intermediate else None
         preds = torch.empty(steps, b, 3, hh, ww, dtype=torch.float32, device=device) if return_noise_pred else None
+        if guided:
+            self._guided_loop(low, noise_t, ts, coefs, float(guidance_scale), passes, frame is not None, enhanced, inter, preds)
+            return self._enhance_result(enhanced, inter, preds, steps, return_intermediate or return_noise_pred)
         h, ws, nbytes = prepared if prepared is not None else self.unet._prepare(b, device, enhance_steps=stage_steps)
         outs = (enhanced.data_ptr(), inter.data_ptr() if inter is not None else None, preds.data_ptr() if preds is not None else None)
         stream = torch.cuda.current_stream(device).cuda_stream
@@ -248,8 +285,11 @@ class LowLightDiffusion(nn.Module):
             else:
                 N.check(N.lib().llie_enhance_hw(h.h, low.data_ptr(), noise_t.data_ptr(), t_dev.data_ptr(), coefs, steps, *outs,
                                                 b, hh, ww, ws.data_ptr(), nbytes, stream), "enhance_frame")
+        return self._enhance_result(enhanced, inter, preds, steps, return_intermediate or return_noise_pred)
+
+    def _enhance_result(self, enhanced, inter, preds, steps, as_output):
         self.scheduler._step_index = steps
-        if return_intermediate or return_noise_pred:
+        if as_output:
             out = LowLightDiffusionOutput(enhanced=enhanced,
                                           intermediate=[inter[i] for i in range(steps)] if inter is not None else None)
             if preds is not None:
@@ -257,9 +297,76 @@ class LowLightDiffusion(nn.Module):
             return out
         return enhanced
 
+    def _guided_plan(self, b: int, device, frame, passes: Optional[int]) -> int:
+        """The form of the guided loop: 1 (one 2B-row pass per step, the default) or 2 (two B-row passes), after the engine's
+        shape and workspace queries.  B rows refused: ValueError naming the rule, as the unguided call raises.  2B rows refused
+        (the frame rule or the workspace query): the two-pass form, unless `passes` forces one pass -- then that refusal."""
+        from .unet import resolve_compute_dtype
+        h = self.unet._handle(resolve_compute_dtype(self.unet.compute_dtype))
+        try:
+            h.workspace_bytes(b) if frame is None else h.frame_workspace_bytes(b, frame[0], frame[1])
+        except ValueError as e:
+            hint = '; enhance_tiled(tile="auto") handles images of any size' if "element cap" in str(e) else ""
+            raise ValueError(f"enhance_frame: {e}{hint}" if frame is not None else str(e)) from None
+        if passes == 2:
+            return 2
+        try:
+            self.unet._prepare(2 * b, device, frame=frame)
+        except (ValueError, torch.cuda.OutOfMemoryError):
+            if passes == 1:
+                raise
+            return 2
+        return 1
+
+    def _guided_loop(self, low, noise_t, ts, coefs, w: float, passes: int, frames: bool, enhanced, inter, preds) -> None:
+        """The guided loop after `_enhance_at`'s setup (the docstring of `enhance` has the steps).  Buffers are allocated before
+        the loop; inside it there are only launches on the current stream."""
+        device = low.device
+        b = low.shape[0]
+        rows = 2 * b if passes == 1 else b
+        t_dev = []
+        for t in ts:  # device timesteps, kept on the model like the tiles path's
+            key = ("guided", int(t), rows, device.type, device.index)
+            cached = self._t_cache.get(key)
+            if cached is None:
+                if len(self._t_cache) > 64:
+                    self._t_cache.clear()
+                cached = self._t_cache[key] = torch.full((rows,), int(t), dtype=torch.long).to(device)
+            t_dev.append(cached)
+        out2 = torch.empty((2 * b,) + tuple(low.shape[1:]), dtype=torch.float32, device=device)  # rows b: o_c, rows b + B: o_u
+        o_c, o_u = out2[:b], out2[b:]
+        if passes == 1:
+            lat2, cond2 = torch.empty_like(out2), torch.empty_like(out2)
+        else:
+            null = torch.zeros_like(low)
+        guided = None if preds is not None else torch.empty_like(low)
+        lat = None if inter is not None else (torch.empty_like(low), torch.empty_like(low))
+        x = noise_t[0]
+        n = low.numel()
+        steps = len(ts)
+        L = N.lib()
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream(device).cuda_stream
+            for i in range(steps):
+                if passes == 1:
+                    G.guidance_pair_device(x, low, lat2, cond2)
+                    self.unet.forward_split(lat2, cond2, t_dev[i], uniform_t=True, out=out2, frame=frames)
+                else:
+                    self.unet.forward_split(x, low, t_dev[i], uniform_t=True, out=o_c, frame=frames)
+                    self.unet.forward_split(x, null, t_dev[i], uniform_t=True, out=o_u, frame=frames)
+                o = preds[i] if preds is not None else guided
+                N.check(L.llie_guide(o_c.data_ptr(), o_u.data_ptr(), None, w, o.data_ptr(), b, n // b, stream), "enhance (guided)")
+                last = i == steps - 1
+                prev = inter[i] if inter is not None else lat[i & 1]
+                draw = not coefs[i].is_last and not coefs[i].sampler  # a DDIM step reads no noise
+                N.check(L.llie_lcm_step(o.data_ptr(), x.data_ptr(), noise_t[i + 1].data_ptr() if draw else None, prev.data_ptr(), None,
+                                        enhanced.data_ptr() if last else None, n, coefs[i], stream), "enhance (guided)")
+                x = prev
+
     # ------------------------------------------------------------------ loss (:250-277)
     def compute_loss(self, low_light: torch.Tensor, normal_light: torch.Tensor, loss_type: str = "mse", *,
-                     use_velocity_target: bool = False, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0) -> torch.Tensor:
+                     use_velocity_target: bool = False, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0,
+                     cond_dropout: float = 0.0) -> torch.Tensor:
         """Regresses the denoiser output against the drawn noise, as the reference does whatever the scheduler's
         prediction type (low_light_diffusion.py:262-275).  `use_velocity_target=True` (extension, needs a
         `prediction_type="v_prediction"` scheduler) regresses against `scheduler.get_velocity` instead -- the v-pred MSE of
@@ -269,9 +376,11 @@ class LowLightDiffusion(nn.Module):
         The loss and the x0 term run at the batch's own H x W: [B,3,H,W] of any shape llie_train_shape_ok accepts (frame-size
         fine-tuning; image_size is one such shape and is what it was).
         `loss.backward()` also fills the gradient of a `low_light` that requires one (forward's docstring): `compute_loss(frontend(raw),
-        normal)` trains `frontend` together with, or instead of, the denoiser."""
+        normal)` trains `frontend` together with, or instead of, the denoiser.
+        `cond_dropout=p`: `forward`'s condition dropout (one more draw, `torch.rand(B)`, after the timestep and noise draws, only
+        when p > 0) -- what TrainStep(cond_dropout=p) does without autograd."""
         _check_x0_weights(x0_ssim_weight, x0_l1_weight)
-        out = self.forward(low_light, normal_light, frame=True)
+        out = self.forward(low_light, normal_light, frame=True, **({"cond_dropout": cond_dropout} if cond_dropout != 0 else {}))
         if use_velocity_target and "target" not in out:
             raise ValueError("use_velocity_target needs a scheduler with prediction_type='v_prediction'")
         pred, noise = out["noise_pred"], (out["target"] if use_velocity_target else out["noise"])
@@ -292,6 +401,34 @@ class LowLightDiffusion(nn.Module):
 
     def get_model_size(self) -> Dict[str, float]:
         return self.unet.get_memory_footprint()
+
+
+# ---------------------------------------------------------------------- condition dropout (guidance.py)
+def cond_uniforms(cond_u: Optional[torch.Tensor], batch: int, device) -> torch.Tensor:
+    """The uniforms of a condition-dropout call as contiguous fp32 [B] on `device`: `cond_u` when supplied (ValueError for another
+    shape), else `torch.rand(B, device=device)` from the global device generator."""
+    if cond_u is None:
+        return torch.rand(batch, device=device)
+    u = torch.as_tensor(cond_u)
+    if tuple(u.shape) != (batch,):
+        raise ValueError(f"cond_u must be [{batch}], got {list(u.shape)}")
+    return u.to(device=device, dtype=torch.float32).contiguous()
+
+
+class _CondDropoutFn(torch.autograd.Function):
+    """llie_cond_dropout as an autograd node of the condition: forward selects the null condition for rows with u < p, backward
+    runs the same select on the gradient, so dropped rows receive exactly 0."""
+
+    @staticmethod
+    def forward(ctx, cond, u, p):
+        ctx.save_for_backward(u)
+        ctx.p = p
+        return G.cond_dropout_device(cond.detach().float().contiguous(), u, p)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        u, = ctx.saved_tensors
+        return G.cond_dropout_device(grad_output.detach().float().contiguous(), u, ctx.p), None, None
 
 
 # ---------------------------------------------------------------------- consistency distillation (:284-408)
@@ -572,8 +709,18 @@ class LowLightLCMDistillation(nn.Module):
     """Consistency distillation teacher -> student (low_light_diffusion.py:284-408).  Constructor, attributes (`teacher`,
     `student`, `ema_student`, `num_ddim_timesteps`, `guidance_scale_range`) and the `state_dict` keys (`teacher.unet.*`,
     `student.unet.*`, `ema_student.unet.*`) are the reference's.  The teacher is put in eval mode and frozen; `ema_student` is
-    `copy.deepcopy(student_model)` and gets its own engine context.  `guidance_scale_range` is stored and never used, as in
-    the reference.  Teacher and student may be different variants but must share `image_size`.
+    `copy.deepcopy(student_model)` and gets its own engine context.  `guidance_scale_range` is stored and, as in the reference,
+    unused unless `guidance=True`.  Teacher and student may be different variants but must share `image_size`.
+
+    Guided distillation (extension, `guidance=True`, keyword only; guidance.py has the definitions).  Each sample gets a scale
+    w_b = lo + (hi - lo) u_b, (lo, hi) = `guidance_scale_range` (finite, lo <= hi, else ValueError), u = torch.rand(B, device=dev)
+    drawn third, after `noise` and `idx` (the product and the sum are two fp32 operations); `w=` of the loss and of DistillStep
+    supplies the scales instead.  The teacher's output becomes llie_guide(teacher(x_t, low), teacher(x_t, null), w) -- both from
+    one 2B-row pass (llie_guidance_pair), or from two B-row passes where the teacher's engine refuses 2B rows, with the same bits
+    -- and enters the unchanged `consistency_target`.  The student and the EMA student see `low`, as always, and are not told
+    w: the reference network has no such input, and `state_dict` parity wins.  With lo < hi the student therefore learns the
+    mixture over the range; a degenerate range (w, w) -- the scale the student is meant to reproduce -- is the normal use.  With
+    `guidance=False` nothing is drawn or launched that was not before: the same bits, the same generator state.
 
     Prediction types (extension).  The teacher's output is read as `teacher.scheduler.config.prediction_type`, the student's and
     the EMA student's as `student.scheduler.config.prediction_type` (`teacher_prediction` / `student_prediction`); each is
@@ -595,8 +742,12 @@ class LowLightLCMDistillation(nn.Module):
     reproduced as is.  A v-prediction student's target is finite there (g0 = -out_ema), and so is its loss."""
 
     def __init__(self, teacher_model: LowLightDiffusion, student_model: LowLightDiffusion, num_ddim_timesteps: int = 50,
-                 guidance_scale_range: Tuple[float, float] = (3.0, 15.0)):
+                 guidance_scale_range: Tuple[float, float] = (3.0, 15.0), *, guidance: bool = False):
         super().__init__()
+        if not isinstance(guidance, bool):
+            raise ValueError(f"guidance must be True or False, got {guidance!r}")
+        if guidance:
+            G.check_guidance_range(guidance_scale_range)
         if teacher_model.image_size != student_model.image_size:
             raise ValueError(f"teacher and student must share image_size (got {teacher_model.image_size} and "
                              f"{student_model.image_size}): both denoise the same x_t")
@@ -608,6 +759,7 @@ class LowLightLCMDistillation(nn.Module):
         self.student = student_model
         self.num_ddim_timesteps = num_ddim_timesteps
         self.guidance_scale_range = guidance_scale_range
+        self.guidance = guidance
         self.ema_student = copy.deepcopy(student_model)  # own parameters, own engine context (built lazily)
         self.ema_student.eval()
         self.ema_student.requires_grad_(False)
@@ -661,6 +813,42 @@ class LowLightLCMDistillation(nn.Module):
             raise ValueError(f"noise must be shaped like normal_light and idx must be [{b}]")
         return noise.contiguous(), idx.contiguous()
 
+    def _draw_w(self, b: int, dev, w) -> Optional[torch.Tensor]:
+        """The per-sample guidance scales, fp32 [B] on `dev`: None with guidance off (a supplied `w` is then a ValueError);
+        the supplied `w`; else lo + (hi - lo) u with u = torch.rand(B, device=dev), the third draw."""
+        if not self.guidance:
+            if w is not None:
+                raise ValueError("w= needs LowLightLCMDistillation(guidance=True)")
+            return None
+        if w is not None:
+            w = torch.as_tensor(w)
+            if tuple(w.shape) != (b,):
+                raise ValueError(f"w must be [{b}], got {list(w.shape)}")
+            return w.to(device=dev, dtype=torch.float32).contiguous()
+        lo, hi = G.check_guidance_range(self.guidance_scale_range)
+        return torch.rand(b, device=dev).mul_(hi - lo).add_(lo)
+
+    def teacher_output(self, x_t: torch.Tensor, low: torch.Tensor, t: torch.Tensor, w: Optional[torch.Tensor] = None, *,
+                       _passes: Optional[int] = None) -> torch.Tensor:
+        """The teacher's output at (x_t, t), without gradients: its forward on `low` when `w` is None; else the guided output
+        llie_guide(teacher(x_t, low), teacher(x_t, null), w), `w` device fp32 [B] -- one 2B-row pass, or two B-row passes where
+        the teacher's engine refuses 2B rows (`_passes` forces either form; the bits are the same)."""
+        with torch.no_grad():
+            if w is None:
+                return self.teacher.unet.forward_split(x_t, low, t, frame=True)
+            b = x_t.shape[0]
+            hh, ww = int(x_t.shape[2]), int(x_t.shape[3])
+            s = self.teacher.image_size
+            x_t, low = x_t.detach().float().contiguous(), low.detach().float().contiguous()
+            if self.teacher._guided_plan(b, x_t.device, None if (hh, ww) == (s, s) else (hh, ww), _passes) == 1:
+                lat2, cond2 = G.guidance_pair_device(x_t, low)
+                out2 = self.teacher.unet.forward_split(lat2, cond2, torch.cat([t, t]), frame=True)
+                o_c, o_u = out2[:b], out2[b:]
+            else:
+                o_c = self.teacher.unet.forward_split(x_t, low, t, frame=True)
+                o_u = self.teacher.unet.forward_split(x_t, torch.zeros_like(low), t, frame=True)
+            return G.guide_device(o_c, o_u, w, out=o_c)
+
     def _check_inputs(self, low_light: torch.Tensor, normal_light: torch.Tensor) -> None:
         """Device, [B,3,H,W] of one shape, and the three engines' shape rules: raises before any draw."""
         from .unet import resolve_compute_dtype
@@ -682,18 +870,21 @@ class LowLightLCMDistillation(nn.Module):
 
     # ------------------------------------------------------------------ the loss (:325-393)
     def consistency_distillation_loss(self, low_light: torch.Tensor, normal_light: torch.Tensor, num_inference_steps: int = 4, *,
-                                      noise: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+                                      noise: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None,
+                                      w: Optional[torch.Tensor] = None, _teacher_passes: Optional[int] = None) -> torch.Tensor:
         """Huber consistency loss (0-d device tensor with a grad_fn reaching the student's parameters) at the batch's own
         H x W (the class docstring has the shape rule and the prediction types).  `noise` / `idx` (extensions) supply the two
-        draws, e.g. CPU-generated ones for a run comparable with the CPU reference."""
+        draws, e.g. CPU-generated ones for a run comparable with the CPU reference.  `w` (fp32 [B], `guidance=True` only)
+        supplies the per-sample guidance scales, the third draw (the class docstring has the guided teacher)."""
         self._check_inputs(low_light, normal_light)
         noise, idx = self._draws(normal_light, num_inference_steps, noise, idx)
+        w = self._draw_w(int(low_light.shape[0]), low_light.device, w)
         t, t_next = self.timestep_pairs(idx, num_inference_steps)
         sched = self.teacher.scheduler
         low = low_light.detach().float().contiguous()
         x_t = sched.add_noise(normal_light, noise, t)
         with torch.no_grad():
-            e_teacher = self.teacher.unet.forward_split(x_t, low, t, frame=True)
+            e_teacher = self.teacher_output(x_t, low, t, w, _passes=_teacher_passes)
             x_next = consistency_target(sched, x_t, e_teacher, t, t_next, prediction_type=self.teacher_prediction)
         e_student = self.student.unet.forward_split(x_t, low, t, frame=True)
         with torch.no_grad():

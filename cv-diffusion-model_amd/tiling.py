@@ -63,6 +63,7 @@ import torch
 
 from . import _native as N
 from .ddim import check_sampler
+from .guidance import guidance_is_on, guided_keyword as _guided_kw
 
 
 def _check_plan(tile: int, overlap: int) -> None:
@@ -432,9 +433,10 @@ def frame_store_device(x: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
 @torch.no_grad()
 def enhance_frame_u8(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int] = None, *,
                      generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None,
-                     sampler: str = "lcm") -> torch.Tensor:
+                     sampler: str = "lcm", guidance_scale: Optional[float] = None) -> torch.Tensor:
     """uint8 [H,W,3] on a HIP device -> enhanced uint8 [H,W,3] at the same resolution, by one run of the network at that size.
-    `sampler` is `enhance`'s: with "ddim" the noise canvas is [1,3,Hp,Wp], the initial latents.
+    `sampler` is `enhance`'s: with "ddim" the noise canvas is [1,3,Hp,Wp], the initial latents.  `guidance_scale` is `enhance`'s
+    too (classifier-free guidance; None: off).
 
     The image is loaded into a frame [3,Hp,Wp] (Hp / Wp = frame_pad(H / W): the next multiple of 8, at least 64) with its edge
     replicated into the padding, goes through `model.enhance_frame` at B = 1, and is cropped and denormalised back.  Noise is
@@ -448,6 +450,7 @@ def enhance_frame_u8(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[
     if not isinstance(rgb_u8, torch.Tensor):
         raise ValueError(f"enhance_frame_u8 expects a torch.Tensor, got {type(rgb_u8).__name__}")
     check_sampler(sampler)
+    guided = _guided_kw(guidance_scale)
     h, w = _check_image(rgb_u8, "enhance_frame_u8")
     _require_hip(rgb_u8, "enhance_frame_u8")
     hp, wp = frame_pad(h), frame_pad(w)
@@ -456,8 +459,9 @@ def enhance_frame_u8(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[
             raise ValueError(f"noise must be a canvas [steps,3,{hp},{wp}]")
         noise = noise.to(device=rgb_u8.device, dtype=torch.float32)[:, None]
     low = frame_load_device(rgb_u8)[None]
-    out = model.enhance_frame(low, num_inference_steps, generator=generator, noise=noise, sampler=sampler)
+    out = model.enhance_frame(low, num_inference_steps, generator=generator, noise=noise, sampler=sampler, **guided)
     return frame_store_device(out[0], (h, w))
+
 
 
 
@@ -517,7 +521,7 @@ def resolve_tile_plan(model, size: Tuple[int, int], tile=None, overlap=None, max
 def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int] = None, *, overlap=None,
                   tile_batch: int = 32, generator: Optional[torch.Generator] = None,
                   noise: Optional[torch.Tensor] = None, sync: str = "none", return_canvas: bool = False, sampler: str = "lcm",
-                  tile=None, max_tile_pixels: Optional[int] = None):
+                  tile=None, max_tile_pixels: Optional[int] = None, guidance_scale: Optional[float] = None):
     """uint8 [H,W,3] on a HIP device -> enhanced uint8 [H,W,3] at the same resolution.
 
     The image is cut into S x S tiles (S = model.image_size) overlapping by `overlap` pixels (default S // 8, at most S // 2);
@@ -546,12 +550,19 @@ def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int
     batch of such frames the engine takes in one call; the result does not depend on it.  tile=(S, S) is tile=None, to the byte.
     tile="auto" plans the fewest tiles the engine can run (`auto_tile_plan` with the budget llie_frame_max_pixels, lowered to
     `max_tile_pixels` when that is given -- a bound on memory); it chooses the overlap, so `overlap=` with it is a ValueError.  An
-    image under the cap becomes one tile: `enhance_frame_u8`'s result."""
+    image under the cap becomes one tile: `enhance_frame_u8`'s result.
+
+    guidance_scale=w (classifier-free guidance, `enhance`'s keyword) passes through to every tile's `enhance` / `enhance_frame`
+    call with sync="none"; with sync="latents" a scale other than None / 1.0 is a ValueError (the shared-canvas loop has no
+    guided form)."""
     if not isinstance(rgb_u8, torch.Tensor):
         raise ValueError(f"enhance_tiled expects a torch.Tensor, got {type(rgb_u8).__name__}")
     if sync not in ("none", "latents"):
         raise ValueError(f'sync must be "none" or "latents", got {sync!r}')
     ddim = check_sampler(sampler) == "ddim"
+    guided = _guided_kw(guidance_scale)
+    if sync == "latents" and guidance_is_on(guidance_scale):
+        raise ValueError('enhance_tiled(sync="latents", guidance_scale=...) is not provided: guidance runs with sync="none" only')
     if return_canvas and sync != "latents":
         raise ValueError('return_canvas needs sync="latents": the default path keeps no latent canvas')
     h, w = _check_image(rgb_u8, "enhance_tiled")
@@ -600,7 +611,7 @@ def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int
         count = min(tile_batch, total - first)
         low = gather_tiles_device(img, *plan, first, count)
         draws = gather_noise_device(canvas, (h, w), *plan, first, count)
-        result[first:first + count].copy_(run(low, nsteps, noise=draws, sampler=sampler))
+        result[first:first + count].copy_(run(low, nsteps, noise=draws, sampler=sampler, **guided))
     return blend_tiles_device(result, (h, w), plan[1])
 
 

@@ -28,6 +28,7 @@ from . import _native as N
 from . import hostio
 from .data import create_device_dataloaders
 from .ddim import check_sampler
+from .guidance import check_cond_dropout, check_guidance_scale, guided_keyword
 from .metrics import _require_hip, _steps_of, _swapped_weights, evaluate
 from .pipeline import LowLightDiffusion
 from .training import FusedAdamW, FusedGradScaler, TrainStep, accumulation_windows
@@ -236,6 +237,7 @@ class _EpochLoop:
     _what = "training"
     val_sampler = "lcm"
     val_steps: Optional[int] = None
+    val_guidance_scale: Optional[float] = None
 
     # ------------------------------------------------------------------ construction
     def _init_shapes(self, config: Optional[TrainingConfig], train_loader, val_loader, crop_size, accumulate) -> None:
@@ -384,7 +386,8 @@ class _EpochLoop:
         Draws: g = torch.Generator(device=dev).manual_seed((seed * 1000003 + epoch * 8191 + 65432) % (2 ** 63 - 1));
         noise = torch.randn(steps, n, 3, S, S, generator=g, device=dev) with steps the scheduler's step count for 4
         (`val_steps` replaces the 4; with val_sampler="ddim" steps = 1, the initial latents, and the loop is DDIM's).
-        With a rectangular `crop_size` the images are [n, 3, H, W] and the loop is `enhance_frame`'s.
+        With a rectangular `crop_size` the images are [n, 3, H, W] and the loop is `enhance_frame`'s.  `val_guidance_scale`
+        is passed on as `guidance_scale=` (classifier-free guidance); the draws do not depend on it.
         The loader's epoch counter, the parameters and the network's mode are as before afterwards."""
         cfg, dev = self.config, self.device
         loader = self.val_loader or self.train_loader
@@ -403,7 +406,7 @@ class _EpochLoop:
                 g = torch.Generator(device=dev).manual_seed(sample_draw_seed(cfg.seed, epoch))
                 noise = torch.randn(steps, low.shape[0], 3, low.shape[2], low.shape[3], generator=g, device=dev)
                 enhance = net.enhance_frame if self.crop_size[0] != self.crop_size[1] else net.enhance
-                enhanced = enhance(low, nsteps, noise=noise, sampler=self.val_sampler)
+                enhanced = enhance(low, nsteps, noise=noise, sampler=self.val_sampler, **guided_keyword(self.val_guidance_scale))
                 grid = comparison_grid(low, enhanced, normal).cpu().numpy()  # the one device-to-host copy
         finally:
             net.train(mode)
@@ -438,6 +441,12 @@ class LowLightTrainer(_EpochLoop):
     config.num_inference_steps in `validate` and the 4 steps of `generate_samples` (None keeps both; with "ddim" anything in
     1..num_train_timesteps).  A schedule the model does not have is a ValueError here, not at the first validation.
 
+    Classifier-free guidance (extension; guidance.py; keywords like the x0 weights, neither TrainingConfig fields nor stored in
+    checkpoints).  `cond_dropout=p` in [0, 1] goes to TrainStep: with p > 0 each sample's condition is replaced by the null
+    condition with probability p, and `train_epoch`'s draw recipe gains a third draw per batch (its docstring).
+    `val_guidance_scale=w` makes `validate` and `generate_samples` sample with `guidance_scale=w` (None: unguided; the
+    validation loss is not affected).
+
     `crop_size=(H, W)` (extension; a keyword like the x0 weights, neither a TrainingConfig field nor stored in checkpoints: a caller
     that resumes passes it again) trains at a frame's own shape instead of config.image_size x config.image_size: the loaders must
     crop (H, W) (`DevicePairLoader(..., image_size=(H, W))`), `train_epoch` draws its noise at that shape, and `validate` /
@@ -453,9 +462,12 @@ class LowLightTrainer(_EpochLoop):
 
     def __init__(self, model: LowLightDiffusion, train_loader, val_loader=None, config: Optional[TrainingConfig] = None, *,
                  x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0, val_sampler: str = "lcm", val_steps: Optional[int] = None,
-                 crop_size: Optional[Tuple[int, int]] = None, accumulate: int = 1):
+                 crop_size: Optional[Tuple[int, int]] = None, accumulate: int = 1, cond_dropout: float = 0.0,
+                 val_guidance_scale: Optional[float] = None):
         self._init_shapes(config, train_loader, val_loader, crop_size, accumulate)
         cfg = self.config
+        self.cond_dropout = check_cond_dropout(cond_dropout)
+        self.val_guidance_scale = check_guidance_scale(val_guidance_scale)
         self.val_sampler = check_sampler(val_sampler)
         if val_steps is not None and (isinstance(val_steps, bool) or int(val_steps) != val_steps or val_steps < 1):
             raise ValueError(f"val_steps must be a positive integer or None, got {val_steps!r}")
@@ -478,7 +490,7 @@ class LowLightTrainer(_EpochLoop):
         self.scheduler = make_lr_scheduler(self.optimizer, cfg, len(accumulation_windows(len(train_loader), accumulate)))
         self.scaler = FusedGradScaler() if dtype == "fp16" else None
         self.step = TrainStep(model, self.optimizer, loss_type=cfg.loss_type, grad_scaler=self.scaler,
-                              x0_ssim_weight=x0_ssim_weight, x0_l1_weight=x0_l1_weight)
+                              x0_ssim_weight=x0_ssim_weight, x0_l1_weight=x0_l1_weight, cond_dropout=self.cond_dropout)
         self._names = [name for name, _ in model.named_parameters()]
 
         self.best_val_loss = float("inf")
@@ -522,7 +534,8 @@ class LowLightTrainer(_EpochLoop):
           per batch of b pairs, in loader order, the reference's order of draws (low_light_diffusion.py: timesteps, then noise):
             t = torch.randint(0, T, (b,), generator=g, device=dev)
             noise = torch.randn(b, 3, S, S, generator=g, device=dev)
-            loss = step(low_light, normal_light, timesteps=t, noise=noise);  lr_scheduler.step()
+            u = torch.rand(b, generator=g, device=dev)                  only with cond_dropout = P > 0
+            loss = step(low_light, normal_light, timesteps=t, noise=noise[, cond_u=u]);  lr_scheduler.step()
         The LR schedule moves once per batch, after the step, also when a grad scaler skipped the step.  The losses go into a
         device buffer that is copied once, after the last batch; nothing else waits for the device, except the progress line
         (every `log_interval` batches; `log_interval = 0` or `progress = False` without wandb turns it off).  Returns the
@@ -542,7 +555,8 @@ class LowLightTrainer(_EpochLoop):
             b = low.shape[0]
             t = torch.randint(0, t_max, (b,), generator=g, device=dev)
             noise = torch.randn(b, 3, hh, ww, generator=g, device=dev)
-            return (self.step.accumulate if windowed else self.step)(low, normal, timesteps=t, noise=noise)
+            drop = {"cond_u": torch.rand(b, generator=g, device=dev)} if self.cond_dropout > 0 else {}
+            return (self.step.accumulate if windowed else self.step)(low, normal, timesteps=t, noise=noise, **drop)
 
         return self._run_epoch(micro)
 
@@ -558,7 +572,8 @@ class LowLightTrainer(_EpochLoop):
         mode = self.model.training
         try:
             res = evaluate(self.model, self.val_loader, num_inference_steps=self._val_steps(self.config.num_inference_steps),
-                           seed=self.config.seed, weights=self._ema_weights(), sampler=self.val_sampler)
+                           seed=self.config.seed, weights=self._ema_weights(), sampler=self.val_sampler,
+                           **guided_keyword(self.val_guidance_scale))
         finally:
             self.model.train(mode)
         self.last_validation = res
@@ -606,11 +621,12 @@ class LowLightTrainer(_EpochLoop):
 
 def train_model(train_data_dir: str, val_data_dir: Optional[str] = None, config: Optional[TrainingConfig] = None,
                 device="cuda", *, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0, val_sampler: str = "lcm",
-                val_steps: Optional[int] = None, crop_size: Optional[Tuple[int, int]] = None, accumulate: int = 1) -> LowLightTrainer:
+                val_steps: Optional[int] = None, crop_size: Optional[Tuple[int, int]] = None, accumulate: int = 1,
+                cond_dropout: float = 0.0, val_guidance_scale: Optional[float] = None) -> LowLightTrainer:
     """Training entry point (trainer.py:459-496): loaders from the folders (create_device_dataloaders), a fresh model, a trainer,
     `train()`; returns the trainer.  `x0_ssim_weight` / `x0_l1_weight` / `val_sampler` / `val_steps` / `crop_size`: as
     LowLightTrainer's (with `crop_size=(H, W)` the loaders crop H x W; the model is still built at config.image_size);
-    `accumulate`: LowLightTrainer's."""
+    `accumulate` / `cond_dropout` / `val_guidance_scale`: LowLightTrainer's."""
     config = config or TrainingConfig()
     train_loader, val_loader = create_device_dataloaders(train_root=train_data_dir, val_root=val_data_dir, batch_size=config.batch_size,
                                                          image_size=config.image_size if crop_size is None else tuple(crop_size),
@@ -620,6 +636,7 @@ def train_model(train_data_dir: str, val_data_dir: Optional[str] = None, config:
                               num_inference_steps=config.num_inference_steps).to(train_loader.store.device)
     trainer = LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config,
                               x0_ssim_weight=x0_ssim_weight, x0_l1_weight=x0_l1_weight, val_sampler=val_sampler, val_steps=val_steps,
-                              crop_size=crop_size, accumulate=accumulate)
+                              crop_size=crop_size, accumulate=accumulate, cond_dropout=cond_dropout,
+                              val_guidance_scale=val_guidance_scale)
     trainer.train()
     return trainer

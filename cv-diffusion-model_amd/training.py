@@ -431,11 +431,17 @@ class TrainStep(_GradWindow):
     directly.  It is this rank's gradient (never all-reduced).  With `cond_grad=False` the step is what it was, bit for bit.
     Returns the loss (device scalar, unscaled).
     Gradient accumulation: `accumulate(...)` per micro-batch, then `apply()` (or `discard()`), see _GradWindow; `__call__` is
-    one step from one batch as before and raises RuntimeError while a window is open."""
+    one step from one batch as before and raises RuntimeError while a window is open.
+    `cond_dropout=p` in [0, 1] (classifier-free guidance training; guidance.py has the definitions): with p > 0, row b of the
+    condition is replaced by the null condition (all zeros) where u[b] < p -- llie_cond_dropout into a persistent buffer of the
+    step, before the train forward.  u is `cond_u` (fp32 [B], supplied like `timesteps=` and `noise=`) or `torch.rand(b,
+    device=dev)` from the global device generator, drawn after the timestep and noise draws.  `step.cond_grad` goes through the
+    same kernel: dropped rows are exactly 0.  With p == 0 no draw is made and the step is what it was, bit for bit."""
 
     def __init__(self, model, optimizer: FusedAdamW, loss_type: str = "mse", use_velocity_target: bool = False, group=None,
                  grad_scaler: Optional[FusedGradScaler] = None, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0,
-                 cond_grad: bool = False):
+                 cond_grad: bool = False, cond_dropout: float = 0.0):
+        from .guidance import check_cond_dropout
         from .pipeline import _check_x0_weights
         if loss_type not in ("mse", "huber", "l1"):
             raise ValueError(f"Unknown loss type: {loss_type}")
@@ -452,12 +458,14 @@ class TrainStep(_GradWindow):
         self._ws = None
         self._want_cond_grad = bool(cond_grad)
         self.cond_grad: Optional[torch.Tensor] = None
+        self.cond_dropout = check_cond_dropout(cond_dropout)
+        self._cond = None  # the dropped-out condition (persistent; follows the batch's shape)
 
     @torch.no_grad()
     def __call__(self, low_light: torch.Tensor, normal_light: torch.Tensor, timesteps: Optional[torch.Tensor] = None,
-                 noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 noise: Optional[torch.Tensor] = None, cond_u: Optional[torch.Tensor] = None) -> torch.Tensor:
         self._no_open_window("TrainStep.__call__")
-        loss = self._micro(low_light, normal_light, timesteps, noise)
+        loss = self._micro(low_light, normal_light, timesteps, noise, cond_u)
         scale = 1.0
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(self.group) > 1:
             dist.all_reduce(self._flat, group=self.group)  # one collective over all gradients; the average rides on grad_scale
@@ -467,7 +475,7 @@ class TrainStep(_GradWindow):
 
     @torch.no_grad()
     def accumulate(self, low_light: torch.Tensor, normal_light: torch.Tensor, timesteps: Optional[torch.Tensor] = None,
-                   noise: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   noise: Optional[torch.Tensor] = None, cond_u: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One micro-batch of a window: everything `__call__` does up to and including the backward pass into the flat buffer
         (at the batch's own H x W, which may differ from the window's other micro-batches), then `acc (+)= b * flat`
         (llie_grad_accumulate).  Returns the micro-batch loss (device scalar, unscaled); nothing reads from the host.  A shape
@@ -475,7 +483,7 @@ class TrainStep(_GradWindow):
         if self._want_cond_grad:
             raise ValueError("TrainStep.accumulate: cond_grad=True is not supported in a window (the window's weight is not known "
                              "when a micro-batch's condition gradient is produced)")
-        loss = self._micro(low_light, normal_light, timesteps, noise)
+        loss = self._micro(low_light, normal_light, timesteps, noise, cond_u)
         self._window_add(int(low_light.shape[0]), loss)
         return loss
 
@@ -486,9 +494,9 @@ class TrainStep(_GradWindow):
         return self._window_apply(self.group)
 
     def _micro(self, low_light: torch.Tensor, normal_light: torch.Tensor, timesteps: Optional[torch.Tensor],
-               noise: Optional[torch.Tensor]) -> torch.Tensor:
-        """q-sample -> train forward -> loss and d(loss)/d(eps) (x0 term, grad-scaler multiplication) -> backward into
-        `self._flat`; returns the loss."""
+               noise: Optional[torch.Tensor], cond_u: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """q-sample -> (condition dropout) -> train forward -> loss and d(loss)/d(eps) (x0 term, grad-scaler multiplication) ->
+        backward into `self._flat`; returns the loss."""
         from .unet import resolve_compute_dtype
         model, unet = self.model, self.model.unet
         b, dev = low_light.shape[0], low_light.device
@@ -505,6 +513,14 @@ class TrainStep(_GradWindow):
         noisy = model.scheduler.add_noise(normal_light, noise, timesteps).float().contiguous()
         target = model.scheduler.get_velocity(normal_light, noise, timesteps) if self.velocity else noise
         cond = low_light.detach().float().contiguous()
+        u = None
+        if self.cond_dropout > 0:  # the third draw, after timesteps and noise; none at p == 0
+            from .guidance import cond_dropout_device
+            from .pipeline import cond_uniforms
+            u = cond_uniforms(cond_u, b, dev)
+            if self._cond is None or self._cond.shape != cond.shape or self._cond.device != dev:
+                self._cond = torch.empty_like(cond)
+            cond = cond_dropout_device(cond, u, self.cond_dropout, out=self._cond)
         t = timesteps.to(device=dev, dtype=torch.long).contiguous()
         eps = torch.empty(b, unet.config.out_channels, hh, ww, dtype=torch.float32, device=dev)
         L = N.lib()
@@ -525,6 +541,8 @@ class TrainStep(_GradWindow):
                                                 nbytes, st), "EfficientUNet.backward")
                 # unscaled here, before step_flat below updates the device scale
                 self.cond_grad = dc / self.grad_scaler._device_scale(dev) if self.grad_scaler is not None else dc
+                if u is not None:  # the gradient of the null condition's rows does not reach low_light: exactly 0
+                    cond_dropout_device(self.cond_grad, u, self.cond_dropout, out=self.cond_grad)
             else:
                 N.check(L.llie_unet_backward(h.h, d_eps.data_ptr(), self._flat.data_ptr(), b, self._ws.data_ptr(), nbytes, st),
                         "EfficientUNet.backward")
@@ -543,7 +561,9 @@ class DistillStep(_GradWindow):
     times the device scale, unscale / skip / scale update in the optimiser's launches) and are refused without one; update_ema
     runs every step, skipped or not, as in the reference loop.  fp32 and bf16 run either way.
     Batches are [B,3,H,W] of any shape LowLightLCMDistillation accepts (its docstring has the rule); the networks' outputs are
-    read with the distillation's `teacher_prediction` / `student_prediction`."""
+    read with the distillation's `teacher_prediction` / `student_prediction`.
+    With `LowLightLCMDistillation(guidance=True)` the teacher's output is the guided one (its docstring): the per-sample scales
+    are the third draw, after `noise` and `idx`, or `w=` (fp32 [B]) of `__call__` / `accumulate`."""
 
     def __init__(self, distill, optimizer: FusedAdamW, ema_decay: float = 0.95, grad_scaler: Optional[FusedGradScaler] = None):
         if not (0 <= ema_decay <= 1):
@@ -560,21 +580,23 @@ class DistillStep(_GradWindow):
 
     @torch.no_grad()
     def __call__(self, low_light: torch.Tensor, normal_light: torch.Tensor, num_inference_steps: int = 4, *,
-                 noise: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 noise: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None,
+                 w: Optional[torch.Tensor] = None) -> torch.Tensor:
         self._no_open_window("DistillStep.__call__")
-        loss = self._micro(low_light, normal_light, num_inference_steps, noise, idx)
+        loss = self._micro(low_light, normal_light, num_inference_steps, noise, idx, w)
         self.opt.step_flat(self._flat, self._offsets, grad_scaler=self.grad_scaler)
         self.distill.update_ema(self.ema_decay)
         return loss
 
     @torch.no_grad()
     def accumulate(self, low_light: torch.Tensor, normal_light: torch.Tensor, num_inference_steps: int = 4, *,
-                   noise: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   noise: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None,
+                   w: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One micro-batch of a window (at the batch's own H x W, which may differ from the window's other micro-batches): the
         teacher, student and EMA-target forwards, the loss and the backward pass of `__call__`, then `acc (+)= b * flat`.
         Returns the micro-batch loss (device scalar).  A shape the engines refuse raises before any draw and leaves an open
         window as it was."""
-        loss = self._micro(low_light, normal_light, num_inference_steps, noise, idx)
+        loss = self._micro(low_light, normal_light, num_inference_steps, noise, idx, w)
         self._window_add(int(low_light.shape[0]), loss)
         return loss
 
@@ -585,7 +607,7 @@ class DistillStep(_GradWindow):
         return loss
 
     def _micro(self, low_light: torch.Tensor, normal_light: torch.Tensor, num_inference_steps: int, noise: Optional[torch.Tensor],
-               idx: Optional[torch.Tensor]) -> torch.Tensor:
+               idx: Optional[torch.Tensor], w: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The three denoiser passes, the distillation kernels and the backward pass into `self._flat`; returns the loss."""
         from .pipeline import consistency_loss, consistency_target
         from .unet import resolve_compute_dtype
@@ -599,11 +621,12 @@ class DistillStep(_GradWindow):
         b, dev = low_light.shape[0], low_light.device
         hh, ww = int(low_light.shape[2]), int(low_light.shape[3])
         noise, idx = d._draws(normal_light, num_inference_steps, noise, idx)
+        w = d._draw_w(b, dev, w)  # None unless the distillation was built with guidance=True: then the third draw
         t, t_next = d.timestep_pairs(idx, num_inference_steps)
         sched = d.teacher.scheduler
         low = low_light.detach().float().contiguous()
         x_t = sched.add_noise(normal_light, noise, t)
-        e_teacher = d.teacher.unet.forward_split(x_t, low, t, frame=True)
+        e_teacher = d.teacher_output(x_t, low, t, w)
         x_next = consistency_target(sched, x_t, e_teacher, t, t_next, prediction_type=d.teacher_prediction)
         h = unet._handle(dtype)
         # the batch's own H x W; the workspace follows the shape and only grows, so a loop or a window may alternate shapes

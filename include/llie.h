@@ -324,6 +324,28 @@ int llie_consistency_loss_ex(const float* x_t, const float* x_next, const float*
                              const int64_t* t, const int64_t* t_next, const float* alphas_cumprod, int table_len,
                              float* d_student, float* loss_out, void* scratch, int64_t scratch_bytes, int batch,
                              int64_t per_sample, int student_pred, llie_stream stream);
+/* Classifier-free guidance (csrc/guidance.hip), elementwise on device fp32 [batch, per_sample] tensors (the kernels know nothing
+ * of H x W).  The null condition is the all-zero image in the model's range (positive-zero bits): a constant, not a parameter.
+ *   llie_guide:          out = out_uncond + w (out_cond - out_uncond) for a network output of either prediction type; the
+ *                        difference, the product and the sum are each rounded on their own (no fused multiply-add).  w is
+ *                        w_rows[b] (device fp32 [batch]) when `w_rows` is non-NULL, the host scalar `w` otherwise.  `out` may alias
+ *                        `out_cond` (or `out_uncond`).
+ *   llie_guidance_pair:  latents2 [2 batch] = the latents twice; cond2 [2 batch] = `cond` followed by `batch` null rows: in one
+ *                        launch, the input of one 2 batch-row denoiser pass whose rows b and b + batch are the conditional and
+ *                        the unconditional output of sample b.  The outputs must not overlap the inputs.
+ *   llie_cond_dropout:   out[b] = u[b] < p ? null row : in[b] (strictly; `u` device fp32 [batch], uniform in [0, 1); the
+ *                        comparison is made in fp32).  A select, not a multiply: inf / NaN of a dropped row give 0.  `out` may
+ *                        alias `in`.  The same call masks a gradient: dropped rows of d(cond) are zero.
+ * 16-byte accesses where the pointers and per_sample allow (all pointers 16-byte aligned and per_sample % 4 == 0, or one row),
+ * scalar ones for the tail and otherwise; the bits do not depend on it.  LLIE_ERR_ARG before any launch for a null pointer (`w_rows`
+ * excepted), a pointer that is not 4-byte aligned, batch <= 0, per_sample <= 0, a non-finite `w` (when it is used) or `p`, and a
+ * `p` outside [0, 1]. */
+int llie_guide(const float* out_cond, const float* out_uncond, const float* w_rows, float w, float* out, int batch,
+               int64_t per_sample, llie_stream stream);
+int llie_guidance_pair(const float* latents, const float* cond, float* latents2, float* cond2, int batch, int64_t per_sample,
+                       llie_stream stream);
+int llie_cond_dropout(const float* in, const float* u, float p, float* out, int batch, int64_t per_sample, llie_stream stream);
+
 /* EMA of a parameter set (update_ema, :316-323): ema[i] = ema[i] * decay + (1 - decay) * param[i] over `count` tensors in
  * one launch.  The table (device pointers, all fp32 and valid for the object's life) is built once by create. */
 typedef struct llie_ema llie_ema;

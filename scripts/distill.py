@@ -11,7 +11,8 @@ student's, --teacher_prediction / --student_prediction what each network's outpu
 trained with TrainStep(use_velocity_target=True) is v_prediction).  --init_student starts the student (and the EMA target) from
 a checkpoint, usually the teacher's own when the variants agree; without it the student starts from --seed's random weights.
 --num_ddim_timesteps is the teacher's DDIM grid (50), --num_steps the step count distilled for, --target_ema_decay the decay of
-the EMA target network (0.95).  --crop_height / --crop_width distil at a frame's own shape; --accumulate as in train.py.
+the EMA target network (0.95).  --guidance_scale_range LO HI distils the classifier-free-guided teacher (a teacher trained
+with train.py --cond_dropout): each sample's scale is uniform in [LO, HI], and LO = HI is the normal use.  --crop_height / --crop_width distil at a frame's own shape; --accumulate as in train.py.
 
 Checkpoints have the trainer's names (checkpoint_epoch_{e}.pt, best_model.pt by validation PSNR, final_model.pt); their
 "model_state_dict" is the EMA student, so
@@ -21,6 +22,7 @@ Checkpoints have the trainer's names (checkpoint_epoch_{e}.pt, best_model.pt by 
 runs the student as it is.  One JSON line per epoch is printed: epoch, train_loss, lr, psnr, ssim.
 """
 import argparse
+import math
 import importlib
 import json
 import os
@@ -82,6 +84,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--crop_width", type=int, default=None, help="the width that goes with --crop_height")
     p.add_argument("--accumulate", type=int, default=1,
                    help="batches per optimiser step (gradient accumulation; >= 1): the effective batch is --accumulate x --batch_size")
+    p.add_argument("--guidance_scale_range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="distil the classifier-free-guided teacher: each sample's teacher output is o_u + w (o_c - o_u) with w "
+                        "uniform in [LO, HI] (LO = HI, one scale, is the normal use); the student then needs no second forward. "
+                        "Default: off")
     return p
 
 
@@ -94,6 +100,11 @@ def parse_args(argv=None):
         p.error("--accumulate must be >= 1")
     if not 0.0 <= args.target_ema_decay <= 1.0:
         p.error("--target_ema_decay must be in [0, 1]")
+    if args.guidance_scale_range is not None:
+        lo, hi = args.guidance_scale_range
+        if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+            p.error("--guidance_scale_range LO HI: finite, LO <= HI")
+        args.guidance_scale_range = (lo, hi)
     if args.teacher_variant is None:
         args.teacher_variant = args.variant
     if args.teacher_attention is None:
@@ -116,6 +127,12 @@ def distiller_keywords(args) -> dict:
     """LowLightDistiller's keywords beside the config."""
     return {"num_inference_steps": args.num_steps, "ema_decay": args.target_ema_decay,
             "crop_size": None if args.crop_height is None else (args.crop_height, args.crop_width), "accumulate": args.accumulate}
+
+
+def guidance_keywords(args) -> dict:
+    """LowLightLCMDistillation's guidance keywords: nothing without --guidance_scale_range (the range stays stored and unused)."""
+    r = getattr(args, "guidance_scale_range", None)
+    return {} if r is None else {"guidance_scale_range": tuple(r), "guidance": True}
 
 
 def build_network(variant: str, attention: str, prediction: str, image_size: int, num_steps: int) -> "M.LowLightDiffusion":
@@ -151,7 +168,8 @@ def main(argv=None) -> int:
     student = build_network(args.variant, args.attention, args.student_prediction, args.image_size, args.num_steps)
     if args.init_student:
         hostio.load_checkpoint(student, args.init_student)
-    distill = M.LowLightLCMDistillation(teacher, student, num_ddim_timesteps=args.num_ddim_timesteps).to(train_loader.store.device)
+    distill = M.LowLightLCMDistillation(teacher, student, num_ddim_timesteps=args.num_ddim_timesteps,
+                                        **guidance_keywords(args)).to(train_loader.store.device)
     print(f"  Teacher: {args.teacher_variant} ({args.teacher_prediction}), student: {args.variant} ({args.student_prediction}), "
           f"{student.get_model_size()['num_params']:,} parameters")
 

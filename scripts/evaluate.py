@@ -11,6 +11,7 @@ at the image's own size instead, frame mode, and excludes the tile flags).  One 
 given; the per-image lists are part of it only under --per_image.  --seed seeds every draw, so a run is reproducible.
 """
 import argparse
+import math
 import importlib
 import json
 import os
@@ -58,7 +59,11 @@ def parse_args(argv=None):
                         "fewest such tiles under the engine's size cap")
     p.add_argument("--attention", type=str, default="linear", choices=["linear", "softmax"],
                    help="attention of the network the checkpoint holds (softmax: use_linear_attention=False)")
+    p.add_argument("--guidance_scale", type=float, default=None, help="classifier-free guidance scale w: every step uses o_u + w (o_c - o_u), o_u the output on the "
+                        "all-zero condition (a second forward per step; for a model trained with --cond_dropout).  Default: off")
     args = p.parse_args(argv)
+    if args.guidance_scale is not None and not math.isfinite(args.guidance_scale):
+        p.error("--guidance_scale must be finite")
     if args.full_resolution == "frame" and (args.tile_overlap is not None or args.tile_batch != 32 or args.tile_size is not None):
         p.error("--full_resolution frame and --tile_overlap / --tile_batch / --tile_size exclude each other")
     if args.tile_size is not None:
@@ -80,11 +85,11 @@ def main(argv=None) -> int:
         store = M.DeviceFrameStore.from_folder(args.data, device=args.device)
         res = M.evaluate_full_resolution(model, store, num_inference_steps=args.num_steps, seed=args.seed, overlap=args.tile_overlap,
                                          tile_batch=args.tile_batch, mode=args.full_resolution, sampler=args.sampler,
-                                         tile=args.tile_size)
+                                         tile=args.tile_size, **inference.guided(args))
     else:
         store = M.DeviceFrameStore.from_folder(args.data, device=args.device, image_size=args.image_size)
         loader = M.DevicePairLoader(store, args.batch_size, args.image_size, "val")
-        res = M.evaluate(model, loader, num_inference_steps=args.num_steps, seed=args.seed, sampler=args.sampler)
+        res = M.evaluate(model, loader, num_inference_steps=args.num_steps, seed=args.seed, sampler=args.sampler, **inference.guided(args))
     if not args.per_image:
         del res["per_image"]
     line = json.dumps(res)

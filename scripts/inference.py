@@ -12,6 +12,7 @@ step; --tile_size: the tiles are frames of H x W, or with auto the fewest frames
 size cap, about 5.59 M pixels for `small`).  --native and the tile flags exclude each other.
 """
 import argparse
+import math
 import importlib
 import os
 import sys
@@ -67,7 +68,14 @@ def parse_args(argv=None):
     p.add_argument("--native", action="store_true",
                    help="(extension) no resize and no tiles: one run of the network at the image's own resolution (frame mode); "
                         "--noise_seed then seeds the noise canvas at the padded size")
+    p.add_argument("--guidance_scale", type=float, default=None,
+                   help="(extension) classifier-free guidance scale w: every step uses o_u + w (o_c - o_u), o_u the output on the "
+                        "all-zero condition (a second forward per step; for a model trained with --cond_dropout).  Default: off")
     args = p.parse_args(argv)
+    if args.guidance_scale is not None and not math.isfinite(args.guidance_scale):
+        p.error("--guidance_scale must be finite")
+    if args.guidance_scale not in (None, 1.0) and args.tile_sync == "latents":
+        p.error("--guidance_scale and --tile_sync latents exclude each other")
     if args.native and (args.tile or args.tile_overlap is not None or args.tile_batch != 32 or args.tile_sync != "none"
                         or args.tile_size is not None):
         p.error("--native and --tile / --tile_overlap / --tile_batch / --tile_sync / --tile_size exclude each other")
@@ -102,6 +110,12 @@ def load_model(args):
     return model.to(args.device).eval()
 
 
+def guided(args) -> dict:
+    """--guidance_scale as the `guidance_scale=` keyword of the enhance calls (nothing without the flag)."""
+    w = getattr(args, "guidance_scale", None)
+    return {} if w is None else {"guidance_scale": w}
+
+
 def noise_entries(args) -> int:
     """Entries of the noise --noise_seed draws: one per step for the LCM loop, the initial latents alone for DDIM."""
     return 1 if args.sampler == "ddim" else args.num_steps
@@ -117,7 +131,7 @@ def enhance_tiled_image(args, model, rgb):
         noise = torch.stack([torch.randn(3, hc, wc, generator=g) for _ in range(noise_entries(args))])
     out = tiling.enhance_tiled(model, torch.from_numpy(rgb).to(args.device), args.num_steps, overlap=args.tile_overlap,
                                tile_batch=args.tile_batch, noise=noise, sync=args.tile_sync, sampler=args.sampler,
-                               tile=args.tile_size)
+                               tile=args.tile_size, **guided(args))
     return out.cpu().numpy()
 
 
@@ -128,7 +142,7 @@ def enhance_native_image(args, model, rgb):
         g = torch.Generator().manual_seed(args.noise_seed)
         hp, wp = tiling.frame_pad(rgb.shape[0]), tiling.frame_pad(rgb.shape[1])
         noise = torch.stack([torch.randn(3, hp, wp, generator=g) for _ in range(noise_entries(args))])
-    out = tiling.enhance_frame_u8(model, torch.from_numpy(rgb).to(args.device), args.num_steps, noise=noise, sampler=args.sampler)
+    out = tiling.enhance_frame_u8(model, torch.from_numpy(rgb).to(args.device), args.num_steps, noise=noise, sampler=args.sampler, **guided(args))
     return out.cpu().numpy()
 
 
@@ -143,7 +157,7 @@ def enhance_resized_image(args, model, rgb):
         if args.noise_seed is not None:  # reference draw order: initial latents, then one draw per non-final step
             g = torch.Generator().manual_seed(args.noise_seed)
             noise = torch.stack([torch.randn(1, 3, args.image_size, args.image_size, generator=g) for _ in range(noise_entries(args))])
-        enhanced = model.enhance(x, num_inference_steps=args.num_steps, noise=noise, sampler=args.sampler)
+        enhanced = model.enhance(x, num_inference_steps=args.num_steps, noise=noise, sampler=args.sampler, **guided(args))
         return hostio.postprocess_device(enhanced, original)[0].cpu().numpy()
 
 

@@ -29,6 +29,7 @@ holds 2 frames.  The last window of an epoch holds what is left; the LR schedule
 checkpoints: pass it again with --resume.
 """
 import argparse
+import math
 import importlib
 import json
 import os
@@ -86,6 +87,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--crop_width", type=int, default=None, help="the width that goes with --crop_height")
     p.add_argument("--accumulate", type=int, default=1,
                    help="batches per optimiser step (gradient accumulation; >= 1): the effective batch is --accumulate x --batch_size")
+    p.add_argument("--cond_dropout", type=float, default=0.0,
+                   help="classifier-free guidance training: probability in [0, 1] of replacing a sample's low-light condition by the "
+                        "all-zero image (0 = off)")
+    p.add_argument("--guidance_scale", type=float, default=None,
+                   help="guidance scale w of validation and of the sample sheet: o_u + w (o_c - o_u) at every step (default: off)")
     return p
 
 
@@ -96,6 +102,10 @@ def parse_args(argv=None):
         p.error("--crop_height and --crop_width go together: both or neither")
     if args.accumulate < 1:
         p.error("--accumulate must be >= 1")
+    if not 0.0 <= args.cond_dropout <= 1.0:
+        p.error("--cond_dropout must be in [0, 1]")
+    if args.guidance_scale is not None and not math.isfinite(args.guidance_scale):
+        p.error("--guidance_scale must be finite")
     return args
 
 
@@ -120,6 +130,12 @@ def sampler_from_args(args) -> dict:
     """LowLightTrainer's sampling keywords (like the x0 weights: not TrainingConfig fields, not in checkpoints).  The LCM default
     keeps the trainer's own step counts; --sampler ddim runs --num_steps DDIM steps in validation and in the sample sheet."""
     return {"val_sampler": args.sampler, "val_steps": args.num_steps if args.sampler == "ddim" else None}
+
+
+def guidance_from_args(args) -> dict:
+    """LowLightTrainer's classifier-free guidance keywords (not TrainingConfig fields, not in checkpoints): --cond_dropout trains
+    with the condition dropped, --guidance_scale samples validation and the sample sheet with guidance."""
+    return {"cond_dropout": args.cond_dropout, "val_guidance_scale": args.guidance_scale}
 
 
 def crop_size_from_args(args) -> dict:
@@ -155,7 +171,8 @@ def main(argv=None) -> int:
     print(f"  Parameters: {size['num_params']:,}")
 
     trainer = M.LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config,
-                                **x0_weights_from_args(args), **sampler_from_args(args), crop_size=crop, accumulate=args.accumulate)
+                                **x0_weights_from_args(args), **sampler_from_args(args), crop_size=crop, accumulate=args.accumulate,
+                                **guidance_from_args(args))
     print(f"  Engine precision: {model.compute_dtype}, loss scaler: {trainer.scaler is not None}, EMA: {config.use_ema}")
     trainer.train(on_epoch=lambda log: print(json.dumps(log), flush=True))
     print("\nTraining complete!")
