@@ -12,6 +12,7 @@ from .unet import (EfficientUNet, EfficientUNetConfig, create_efficient_unet, In
                    LinearAttention, StandardAttention, Downsample, Upsample, SqueezeExcitation)
 from .scheduler import LCMScheduler, LCMSchedulerOutput, LCMDenoisingLoop, get_lcm_timesteps
 from .ddim import ddim_timesteps, ddim_step_host, ddim_enhance_host
+from .dpm import dpm_timesteps, dpm_max_steps, dpm_step_coefficients, dpm_step_host, dpm_step_f32, dpm_enhance_host
 from .guidance import (guide_array, cond_dropout_array, guidance_pair_array, scheduler_step_array, guided_enhance_host,
                        check_guidance_scale, check_cond_dropout, check_guidance_range, guide_device, guidance_pair_device,
                        cond_dropout_device)
@@ -53,6 +54,7 @@ __all__ = [
     "TrainingConfig", "LowLightTrainer", "train_model", "make_lr_scheduler", "build_checkpoint", "comparison_grid",
     "comparison_grid_host", "distill_draw_seed", "LowLightDistiller", "timestep_index_range", "default_skip_terminal",
     "ddim_timesteps", "ddim_step_host", "ddim_enhance_host",
+    "dpm_timesteps", "dpm_max_steps", "dpm_step_coefficients", "dpm_step_host", "dpm_step_f32", "dpm_enhance_host",
     "guide_array", "cond_dropout_array", "guidance_pair_array", "scheduler_step_array", "guided_enhance_host",
     "check_guidance_scale", "check_cond_dropout", "check_guidance_range", "guide_device", "guidance_pair_device", "cond_dropout_device",
 ]

@@ -60,6 +60,7 @@ EXPORTS = [
     "llie_softattn", "llie_softattn_backward", "llie_softattn_bwd_floats",
     "llie_pw_expand_nsplit", "llie_silu_rows",
     "llie_guide", "llie_guidance_pair", "llie_cond_dropout",
+    "llie_dpm_step", "llie_enhance_dpm", "llie_enhance_dpm_hw",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 PW_SIGMOID_BWD, PW_RELU6_BWD, PW_SILU_BWD, PW_SCALE = 0, 1, 2, 3  # llie_pointwise_kind
@@ -140,6 +141,13 @@ class StepCoef(_StepCoefLayout, metaclass=_SevenScalars):
     they did before the struct grew; the sampler is read as `coef.sampler`."""
 
 
+class DpmCoef(C.Structure):
+    """llie_dpm_coef (include/llie.h): one step of DPM-Solver++ 2M.  The float members round a Python float (float64) once to fp32."""
+    _fields_ = [
+        ("sqrt_alpha_t", C.c_float), ("sqrt_beta_t", C.c_float), ("k_x", C.c_float), ("k_0", C.c_float), ("k_1", C.c_float),
+        ("v_prediction", C.c_int), ("order", C.c_int), ("is_last", C.c_int),
+    ]
+
 
 DISTILL_LOSS_PER_WG = 1024  # kDistillLossPerWG (csrc/kernels.h): llie_consistency_loss needs one double per this many elements
 
@@ -212,6 +220,9 @@ def lib() -> C.CDLL:
     L.llie_frame_workspace_bytes.restype = i64
     L.llie_unet_forward_hw.argtypes = [vp, vp, vp, vp, ci, vp, ci, ci, ci, vp, i64, vp]
     L.llie_enhance_hw.argtypes = [vp, vp, vp, vp, C.POINTER(StepCoef), ci, vp, vp, vp, ci, ci, ci, vp, i64, vp]
+    L.llie_dpm_step.argtypes = [vp, vp, vp, vp, vp, i64, C.POINTER(DpmCoef), vp]
+    L.llie_enhance_dpm.argtypes = [vp, vp, vp, vp, C.POINTER(DpmCoef), ci, vp, vp, vp, ci, vp, i64, vp]
+    L.llie_enhance_dpm_hw.argtypes = [vp, vp, vp, vp, C.POINTER(DpmCoef), ci, vp, vp, vp, ci, ci, ci, vp, i64, vp]
     L.llie_frame_pad.argtypes = [ci]
     L.llie_frame_load_u8.argtypes = [vp, ci, ci, vp, vp]
     L.llie_frame_store_u8.argtypes = [vp, ci, ci, vp, vp]

@@ -384,6 +384,10 @@ inline StepCoef step_coef(const llie_step_coef& k) {
   return StepCoef{k.sqrt_alpha_t, k.sqrt_beta_t, k.sqrt_alpha_prev, k.sqrt_beta_prev, k.is_last, k.v_prediction, k.clamp_x0, k.sampler};
 }
 inline bool step_coef_ok(const llie_step_coef& k) { return k.sampler == 0 || (k.sampler == 1 && !k.clamp_x0); }
+// llie_dpm_coef as solver.hip takes it (dpm_coef_ok: an order other than 1 / 2 or a non-finite scalar is not a step)
+inline DpmCoef dpm_coef(const llie_dpm_coef& k) {
+  return DpmCoef{k.sqrt_alpha_t, k.sqrt_beta_t, k.k_x, k.k_0, k.k_1, k.v_prediction, k.order, k.is_last};
+}
 // `reserve`: bytes the caller's workspace query counts beyond the forward's plan, added to the plan in the capacity check.  The
 // loop keeps its images in front of the slice it passes and gives 0; the public forward gives loop_image_bytes, so that it refuses
 // exactly what is smaller than llie_workspace_bytes / llie_frame_workspace_bytes answered

@@ -707,6 +707,15 @@ hipError_t launch_guide(const float* out_cond, const float* out_uncond, const fl
 hipError_t launch_guidance_pair(const float* latents, const float* cond, float* latents2, float* cond2, int batch, int64_t per, hipStream_t s);
 hipError_t launch_cond_dropout(const float* in, const float* u, float p, float* out, int batch, int64_t per, hipStream_t s);
 
+// (10c) the DPM-Solver++ 2M step (solver.hip): fp32 [n] tensors.  llie_dpm_coef as the kernel takes it.
+struct DpmCoef { float sa, sb, kx, k0, k1; int vpred, order, is_last; };
+bool dpm_coef_ok(const DpmCoef& c);  // order 1 or 2, every scalar finite
+// prev may alias x; hist (the previous step's x0, read when order == 2, then overwritten with this step's) may be null only when
+// order == 1 && is_last; clamped may be null.  hipErrorInvalidValue before any launch for a null or unaligned pointer, n <= 0 or a
+// coefficient dpm_coef_ok refuses
+hipError_t launch_dpm_step(const float* out, const float* x, float* hist, float* prev, float* clamped, int64_t n, const DpmCoef& c,
+                           hipStream_t s);
+
 // (11) full-resolution images as overlapping SH x SW tiles (tiles.hip).  The plan of one axis of length L, tile side S, overlap
 // v (0 <= 2v <= S): one tile at 0 when L <= S, else n = ceil((L - S) / (S - v)) + 1 tiles at o_i = floor(i (L - S) / (n - 1)).
 // The same two functions serve the host (llie_tile_count / llie_tile_origins) and the kernels, which compute origins themselves.

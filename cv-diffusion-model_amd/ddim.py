@@ -23,12 +23,12 @@ from typing import Callable, Dict, List, Optional
 
 import numpy as np
 
-SAMPLERS = ("lcm", "ddim")
+SAMPLERS = ("lcm", "ddim", "dpmpp_2m")  # "dpmpp_2m": the second-order sampler of dpm.py
 
 
 def check_sampler(sampler: str) -> str:
     if sampler not in SAMPLERS:
-        raise ValueError(f'sampler must be "lcm" or "ddim", got {sampler!r}')
+        raise ValueError(f'sampler must be "lcm", "ddim" or "dpmpp_2m", got {sampler!r}')
     return sampler
 
 

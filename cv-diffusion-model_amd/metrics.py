@@ -320,10 +320,11 @@ def _swapped_weights(model, weights: Optional[Sequence[torch.Tensor]]):
 
 
 def _steps_of(model, num_inference_steps: Optional[int], dev, sampler: str = "lcm") -> Tuple[int, int]:
-    """(the argument `enhance` takes, the number of noise draws it consumes: one per step for the LCM loop, 1 for DDIM)."""
+    """(the argument `enhance` takes, the number of noise draws it consumes: one per step for the LCM loop, 1 for DDIM and
+    DPM-Solver++)."""
     nsteps = model.num_inference_steps if num_inference_steps is None else int(num_inference_steps)
-    if check_sampler(sampler) == "ddim":
-        model.ddim_schedule(nsteps)  # the schedule's ValueErrors, before anything is drawn
+    if check_sampler(sampler) != "lcm":
+        (model.ddim_schedule if sampler == "ddim" else model.dpm_schedule)(nsteps)  # the schedule's ValueErrors, before anything is drawn
         return nsteps, 1
     model.scheduler.set_timesteps(nsteps, device=dev)
     return nsteps, len(model.scheduler._timestep_list)
@@ -357,6 +358,8 @@ def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[i
       ["noise_pred"], eps) without gradients.
       sampler="ddim" scores `model.enhance(..., sampler="ddim")`, the deterministic sampler of a many-step model, at any
       `num_inference_steps` in 1..T: steps = 1 in the recipe above (the initial latents are the only noise), the rest is unchanged.
+      sampler="dpmpp_2m" scores the second-order sampler of such a model (dpm.py) the same way, also with steps = 1, at any step
+      count `model.dpm_schedule` accepts.
       A rectangular loader (`crop_size` = (H, W), H != W; frame-size training) is scored through `model.enhance_frame` and the
       loss runs at that shape: the same recipe with every [.., 3, S, S] draw [.., 3, H, W].  A square loader must crop
       model.image_size, as before.
@@ -428,6 +431,7 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
     tile= / max_tile_pixels= (mode="tiled") pass through as well: with tile=(TH, TW) the canvas of the recipe is
     [steps, 3, max(H, TH), max(W, TW)], and with tile="auto" TH x TW is the tile `auto_tile_plan` gives that image.
     sampler="ddim" passes through to `enhance_tiled` / `enhance_frame_u8` in every mode; steps = 1 in the draws above.
+    sampler="dpmpp_2m" does the same, except that `enhance_tiled` refuses it with sync="latents".
     guidance_scale= passes through the same way (refused by `enhance_tiled` with sync="latents")."""
     if mode not in ("tiled", "frame"):
         raise ValueError(f'mode must be "tiled" or "frame", got {mode!r}')
@@ -436,6 +440,8 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
     if sync not in ("none", "latents"):
         raise ValueError(f'sync must be "none" or "latents", got {sync!r}')
     check_sampler(sampler)
+    if sync == "latents" and sampler == "dpmpp_2m":
+        raise ValueError('evaluate_full_resolution(sync="latents", sampler="dpmpp_2m") is not provided: enhance_tiled refuses the pair')
     guided = _guided_kw(guidance_scale)
     if not isinstance(store, DeviceFrameStore) or not store.paired:
         raise ValueError("evaluate_full_resolution expects a paired DeviceFrameStore")

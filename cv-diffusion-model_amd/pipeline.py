@@ -33,6 +33,7 @@ import torch.nn.functional as F
 
 from . import _native as N
 from .ddim import check_sampler
+from . import dpm as DPM
 from . import guidance as G
 from .scheduler import LCMScheduler
 from .unet import EfficientUNet, create_efficient_unet
@@ -46,11 +47,13 @@ class LowLightDiffusionOutput:
 
 def supplied_noise(noise, draws: int, b: int, h: int, w: int, device, sampler: str = "lcm") -> torch.Tensor:
     """`noise=` of `enhance` / `enhance_frame` as the fp32 [draws,b,3,h,w] tensor the engine reads: a tensor of that shape or a
-    list of `draws` tensors [b,3,h,w].  draws = the step count for the LCM loop, 1 for DDIM (the initial latents only)."""
+    list of `draws` tensors [b,3,h,w].  draws = the step count for the LCM loop, 1 for DDIM and DPM-Solver++ (the initial latents
+    only)."""
     noise_t = noise if isinstance(noise, torch.Tensor) else torch.stack([n.to(device) for n in noise])
     noise_t = noise_t.to(device=device, dtype=torch.float32)
     if tuple(noise_t.shape) != (draws, b, 3, h, w):
-        raise ValueError(f"noise must be [{draws},{b},3,{h},{w}]" + (" (DDIM draws the initial latents only)" if sampler == "ddim" else "")
+        raise ValueError(f"noise must be [{draws},{b},3,{h},{w}]" + (" (DDIM draws the initial latents only)" if sampler == "ddim" else
+                                                             " (DPM-Solver++ draws the initial latents only)" if sampler == "dpmpp_2m" else "")
                          + f", got {list(noise_t.shape)}")
     return noise_t
 
@@ -151,7 +154,11 @@ class LowLightDiffusion(nn.Module):
         of a many-step epsilon- or v-prediction model: `num_inference_steps` may be anything in 1..num_train_timesteps (the
         grid t_i = (n-1-i) * (T // n)), the initial latents are the only draw -- `generator` seeds it, and with one the global
         generator is not touched -- and `noise=` is [1,B,3,S,S] or a one-element list.  Any other string is a ValueError, and so
-        is DDIM with a scheduler that clamps x0 (LCMDenoisingLoop).
+        is DDIM with a scheduler that clamps x0 (LCMDenoisingLoop).  sampler="dpmpp_2m" (extension; dpm.py has the definition) is
+        DPM-Solver++ 2M for the same models: a second-order multistep solver on a grid uniform in log-SNR, with the same number of
+        network calls per step count, the same first timestep, the same single draw and the same `noise=` shape as DDIM.  The
+        table's spacing in log-SNR bounds its step count (32 for the default table; `dpm_schedule` raises ValueError past it,
+        naming the limit).  Its step is one more elementwise launch per step in every compute dtype (llie_dpm_step).
 
         Noise: by default drawn on the device in the reference's order -- the initial latents with
         `generator` (:208-211), then one draw per non-final step from the global generator
@@ -164,8 +171,8 @@ class LowLightDiffusion(nn.Module):
         the null condition (the all-zero image) -- for a model trained with `cond_dropout`.  None and 1.0 run the path above
         unchanged: the captured loop, the same bits, no second forward.  The guided loop is driven from the host: per step
         llie_guidance_pair, one denoiser pass over 2B rows (rows b and b + B are the two outputs of image b), llie_guide, the
-        scheduler's step kernel with the step's coefficients, and the final clamp; nothing in it allocates, waits for the device
-        or copies from the host.  Where the engine refuses 2B rows (llie_frame_shape_ok, workspace) the two outputs come from two
+        scheduler's step kernel with the step's coefficients (llie_dpm_step and one history tensor for "dpmpp_2m"), and the final
+        clamp; nothing in it allocates, waits for the device or copies from the host.  Where the engine refuses 2B rows (llie_frame_shape_ok, workspace) the two outputs come from two
         B-row passes instead, with the same bits (every kernel is bitwise batch-invariant).  Draws, `noise=` shapes,
         `generator`, `return_intermediate` and `sampler` are those of the unguided call; `return_noise_pred` returns the guided
         output of each step.  A non-finite scale is a ValueError."""
@@ -219,6 +226,20 @@ class LowLightDiffusion(nn.Module):
         c = int(self.scheduler.config.num_train_timesteps) // len(ts)
         return ts, [self.scheduler.ddim_step_coefficients(t, t - c) for t in ts]
 
+    def dpm_schedule(self, num_inference_steps: Optional[int] = None) -> Tuple[List[int], List[N.DpmCoef]]:
+        """(timesteps, one N.DpmCoef each) of the DPM-Solver++ 2M loop of `num_inference_steps` steps (default:
+        self.num_inference_steps): dpm.dpm_timesteps / dpm.dpm_step_coefficients on the scheduler's table, each float64 scalar
+        rounded once to fp32.  ValueError for a step count the grid refuses (not an integer, < 1, more than the table's spacing in
+        log-SNR allows, a first timestep whose alpha-bar is 0) and a scheduler that clamps x0 (LCMDenoisingLoop), as `ddim_schedule`."""
+        n = self.num_inference_steps if num_inference_steps is None else num_inference_steps
+        if not isinstance(self.scheduler, LCMScheduler):
+            raise ValueError(f'sampler="dpmpp_2m" is not defined for {type(self.scheduler).__name__} (the deployment loop clamps x0); '
+                             f"use an LCMScheduler")
+        acp = self.scheduler.alphas_cumprod.detach().cpu().numpy()
+        ts = DPM.dpm_timesteps(n, acp)
+        recs = DPM.dpm_step_coefficients(ts, acp, self.scheduler._ptype() == "v_prediction")
+        return ts, [N.DpmCoef(r.sqrt_alpha_t, r.sqrt_beta_t, r.k_x, r.k_0, r.k_1, r.v_prediction, r.order, r.is_last) for r in recs]
+
     def _enhance_at(self, low_light, frame, num_inference_steps, generator, return_intermediate, noise, return_noise_pred,
                     sampler="lcm", guidance_scale=None, passes=None):
         """The loop of `enhance` (frame is None: image_size, llie_enhance) and `enhance_frame` (frame = (H, W), llie_enhance_hw);
@@ -230,15 +251,18 @@ class LowLightDiffusion(nn.Module):
         b = low_light.shape[0]
         hh, ww = frame if frame is not None else (self.image_size, self.image_size)
         steps = self.num_inference_steps if num_inference_steps is None else num_inference_steps
-        ddim = sampler == "ddim"
-        if ddim:
+        dpm = sampler == "dpmpp_2m"
+        ddim = sampler == "ddim" or dpm  # one draw, no staged noise past it: what the two many-step samplers share
+        if dpm:
+            ts, coef_list = self.dpm_schedule(steps)
+        elif ddim:
             ts, coef_list = self.ddim_schedule(steps)
         else:
             self.scheduler.set_timesteps(steps, device=device)
             ts = self.scheduler._timestep_list
         steps = len(ts)
-        draws = 1 if ddim else steps  # DDIM: the initial latents are the only noise
-        # the staging area of the engine's captured loop: LCM stages one draw per step; DDIM stages none past the first, so only
+        draws = 1 if ddim else steps  # DDIM, DPM-Solver++: the initial latents are the only noise
+        # the staging area of the engine's captured loop: LCM stages one draw per step; the others stage none past the first, so only
         # the per-step outputs a caller asks for make it grow with the step count
         stage_steps = 8 if ddim and not (return_intermediate or return_noise_pred) else max(steps, 8)
         prepared = None
@@ -261,7 +285,8 @@ class LowLightDiffusion(nn.Module):
             noise_t = supplied_noise(noise, draws, b, hh, ww, device, sampler)
         noise_t = noise_t.contiguous()
 
-        coefs = (N.StepCoef * steps)(*(coef_list if ddim else [self.scheduler.step_coefficients(t) for t in ts]))
+        coefs = (N.DpmCoef * steps)(*coef_list) if dpm else \
+            (N.StepCoef * steps)(*(coef_list if ddim else [self.scheduler.step_coefficients(t) for t in ts]))
         tkey = (tuple(ts), b, device.type, device.index)
         t_dev = self._t_cache.get(tkey)  # [steps*B] device timesteps: one H2D copy per (schedule, batch), not per call
         if t_dev is None:
@@ -279,7 +304,13 @@ class LowLightDiffusion(nn.Module):
         outs = (enhanced.data_ptr(), inter.data_ptr() if inter is not None else None, preds.data_ptr() if preds is not None else None)
         stream = torch.cuda.current_stream(device).cuda_stream
         with torch.cuda.device(device):
-            if frame is None:
+            if dpm and frame is None:
+                N.check(N.lib().llie_enhance_dpm(h.h, low.data_ptr(), noise_t.data_ptr(), t_dev.data_ptr(), coefs, steps, *outs,
+                                                 b, ws.data_ptr(), nbytes, stream), "enhance")
+            elif dpm:
+                N.check(N.lib().llie_enhance_dpm_hw(h.h, low.data_ptr(), noise_t.data_ptr(), t_dev.data_ptr(), coefs, steps, *outs,
+                                                    b, hh, ww, ws.data_ptr(), nbytes, stream), "enhance_frame")
+            elif frame is None:
                 N.check(N.lib().llie_enhance(h.h, low.data_ptr(), noise_t.data_ptr(), t_dev.data_ptr(), coefs, steps, *outs,
                                              b, ws.data_ptr(), nbytes, stream), "enhance")
             else:
@@ -341,6 +372,8 @@ class LowLightDiffusion(nn.Module):
             null = torch.zeros_like(low)
         guided = None if preds is not None else torch.empty_like(low)
         lat = None if inter is not None else (torch.empty_like(low), torch.empty_like(low))
+        dpm = isinstance(coefs[0], N.DpmCoef)
+        hist = torch.empty_like(low) if dpm else None  # DPM-Solver++: the previous step's x0
         x = noise_t[0]
         n = low.numel()
         steps = len(ts)
@@ -358,6 +391,11 @@ class LowLightDiffusion(nn.Module):
                 N.check(L.llie_guide(o_c.data_ptr(), o_u.data_ptr(), None, w, o.data_ptr(), b, n // b, stream), "enhance (guided)")
                 last = i == steps - 1
                 prev = inter[i] if inter is not None else lat[i & 1]
+                if dpm:
+                    N.check(L.llie_dpm_step(o.data_ptr(), x.data_ptr(), hist.data_ptr(), prev.data_ptr(), enhanced.data_ptr() if last else None,
+                                            n, coefs[i], stream), "enhance (guided)")
+                    x = prev
+                    continue
                 draw = not coefs[i].is_last and not coefs[i].sampler  # a DDIM step reads no noise
                 N.check(L.llie_lcm_step(o.data_ptr(), x.data_ptr(), noise_t[i + 1].data_ptr() if draw else None, prev.data_ptr(), None,
                                         enhanced.data_ptr() if last else None, n, coefs[i], stream), "enhance (guided)")

@@ -296,6 +296,8 @@ def enhance_tiled_sync_array(eps_fn, rgb_u8: np.ndarray, tile, overlap, coefs, t
     sh, sw, vy, vx = _plan(tile, overlap)
     hc, wc = max(h, sh), max(w, sw)
     ddim = check_sampler(sampler) == "ddim"
+    if sampler == "dpmpp_2m":
+        raise ValueError('the shared-canvas loop is defined for sampler="lcm" and "ddim": its step keeps no history of x0 for "dpmpp_2m"')
     if any(int(c.sampler) != int(ddim) for c in coefs):
         raise ValueError(f'sampler="{sampler}" needs coefficients of that sampler on every step')
     draws = 1 if ddim else len(timesteps)
@@ -435,7 +437,7 @@ def enhance_frame_u8(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[
                      generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None,
                      sampler: str = "lcm", guidance_scale: Optional[float] = None) -> torch.Tensor:
     """uint8 [H,W,3] on a HIP device -> enhanced uint8 [H,W,3] at the same resolution, by one run of the network at that size.
-    `sampler` is `enhance`'s: with "ddim" the noise canvas is [1,3,Hp,Wp], the initial latents.  `guidance_scale` is `enhance`'s
+    `sampler` is `enhance`'s: with "ddim" and "dpmpp_2m" the noise canvas is [1,3,Hp,Wp], the initial latents.  `guidance_scale` is `enhance`'s
     too (classifier-free guidance; None: off).
 
     The image is loaded into a frame [3,Hp,Wp] (Hp / Wp = frame_pad(H / W): the next multiple of 8, at least 64) with its edge
@@ -541,6 +543,8 @@ def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int
 
     sampler="ddim" runs the deterministic DDIM loop of `enhance` in either `sync` mode: any step count in 1..num_train_timesteps,
     and the canvas is [1,3,max(H,S),max(W,S)] -- the initial latents, drawn with `generator`; nothing else is drawn.
+    sampler="dpmpp_2m" (DPM-Solver++ 2M, dpm.py) takes the same canvas and runs with sync="none" only: every tile's `enhance` /
+    `enhance_frame` call keeps its own history; with sync="latents" it is a ValueError (the shared-canvas step keeps none).
 
     tile=(TH, TW) makes the tiles frames of that size instead of S x S squares: any frame the engine accepts (sides multiples of
     8 and at least 64, under the element cap; ValueError naming the rule otherwise, before anything is drawn or launched).  The
@@ -560,7 +564,11 @@ def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int
     if sync not in ("none", "latents"):
         raise ValueError(f'sync must be "none" or "latents", got {sync!r}')
     ddim = check_sampler(sampler) == "ddim"
+    dpm = sampler == "dpmpp_2m"
     guided = _guided_kw(guidance_scale)
+    if sync == "latents" and dpm:
+        raise ValueError('enhance_tiled(sync="latents", sampler="dpmpp_2m") is not provided: the shared-canvas step keeps no history of '
+                         'x0; use sync="none", or sampler="ddim"')
     if sync == "latents" and guidance_is_on(guidance_scale):
         raise ValueError('enhance_tiled(sync="latents", guidance_scale=...) is not provided: guidance runs with sync="none" only')
     if return_canvas and sync != "latents":
@@ -585,6 +593,9 @@ def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int
     if ddim:
         schedule = model.ddim_schedule(nsteps)
         steps = 1  # entries of the noise canvas: the initial latents
+    elif dpm:
+        model.dpm_schedule(nsteps)  # the schedule's ValueErrors, before anything is drawn; each tile's call builds its own
+        schedule, steps = None, 1
     else:
         model.scheduler.set_timesteps(nsteps, device=dev)
         ts = model.scheduler._timestep_list

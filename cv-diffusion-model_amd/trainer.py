@@ -385,7 +385,8 @@ class _EpochLoop:
 
         Draws: g = torch.Generator(device=dev).manual_seed((seed * 1000003 + epoch * 8191 + 65432) % (2 ** 63 - 1));
         noise = torch.randn(steps, n, 3, S, S, generator=g, device=dev) with steps the scheduler's step count for 4
-        (`val_steps` replaces the 4; with val_sampler="ddim" steps = 1, the initial latents, and the loop is DDIM's).
+        (`val_steps` replaces the 4; with val_sampler="ddim" or "dpmpp_2m" steps = 1, the initial latents, and the loop is that
+        sampler's).
         With a rectangular `crop_size` the images are [n, 3, H, W] and the loop is `enhance_frame`'s.  `val_guidance_scale`
         is passed on as `guidance_scale=` (classifier-free guidance); the draws do not depend on it.
         The loader's epoch counter, the parameters and the network's mode are as before afterwards."""
@@ -439,7 +440,8 @@ class LowLightTrainer(_EpochLoop):
     choose how validation and the sample sheet sample: val_sampler="ddim" is the deterministic sampler a many-step (teacher)
     model wants, where the default "lcm" shows the 4-step loop of a consistency student; `val_steps` replaces
     config.num_inference_steps in `validate` and the 4 steps of `generate_samples` (None keeps both; with "ddim" anything in
-    1..num_train_timesteps).  A schedule the model does not have is a ValueError here, not at the first validation.
+    1..num_train_timesteps; val_sampler="dpmpp_2m" is the second-order sampler of dpm.py for the same models, at any step count
+    `model.dpm_schedule` accepts).  A schedule the model does not have is a ValueError here, not at the first validation.
 
     Classifier-free guidance (extension; guidance.py; keywords like the x0 weights, neither TrainingConfig fields nor stored in
     checkpoints).  `cond_dropout=p` in [0, 1] goes to TrainStep: with p > 0 each sample's condition is replaced by the null
@@ -472,9 +474,9 @@ class LowLightTrainer(_EpochLoop):
         if val_steps is not None and (isinstance(val_steps, bool) or int(val_steps) != val_steps or val_steps < 1):
             raise ValueError(f"val_steps must be a positive integer or None, got {val_steps!r}")
         self.val_steps = None if val_steps is None else int(val_steps)
-        if self.val_sampler == "ddim":
+        if self.val_sampler != "lcm":
             for n in (self._val_steps(cfg.num_inference_steps), self._val_steps(SAMPLE_STEPS)):
-                model.ddim_schedule(n)
+                (model.ddim_schedule if self.val_sampler == "ddim" else model.dpm_schedule)(n)
         self._init_devices(model, train_loader, val_loader)
         dtype = resolved_compute_dtype(cfg)
 

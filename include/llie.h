@@ -96,6 +96,20 @@ typedef struct llie_step_coef {
                                             is read.  Not defined together with clamp_x0 (LLIE_ERR_ARG) */
 } llie_step_coef;
 
+/* Coefficients of one step of the DPM-Solver++ 2M sampler (data-prediction form; llie_dpm_step below has the arithmetic).  Host
+ * values: computed in float64 from the alpha-bar table and rounded once to fp32.  With alpha = sqrt(abar), sigma = sqrt(1 - abar),
+ * lambda = log(alpha / sigma), t the step's timestep, p the next one, h = lambda_p - lambda_t and r = h_previous / h:
+ *   k_x = sigma_p / sigma_t
+ *   order 1 (the first step):  k_0 = -alpha_p expm1(-h),                     k_1 = 0
+ *   order 2:                   k_0 = -alpha_p expm1(-h) (1 + 1 / (2 r)),     k_1 = alpha_p expm1(-h) / (2 r) */
+typedef struct llie_dpm_coef {
+  float sqrt_alpha_t, sqrt_beta_t;   /* x0 from the network output, as in llie_step_coef */
+  float k_x, k_0, k_1;               /* ignored when is_last */
+  int   v_prediction;                /* 0 epsilon, 1 v_prediction */
+  int   order;                       /* 1: the history is not read.  2: it holds the previous step's x0.  Anything else: LLIE_ERR_ARG */
+  int   is_last;                     /* the step at t = 0: prev = x0 */
+} llie_dpm_coef;
+
 const char* llie_last_error(void);
 const char* llie_version(void);
 
@@ -365,6 +379,20 @@ void llie_ema_destroy(llie_ema* ema);
 int llie_lcm_step(const float* model_output, const float* sample, const float* noise, float* prev_out,
                   float* x0_out, float* clamped_out, int64_t n, const llie_step_coef* coef, llie_stream stream);
 
+/* One step of DPM-Solver++ 2M (csrc/solver.hip), the second-order multistep sampler of a many-step model, elementwise on fp32 [n]:
+ *   x0   = (sample - sqrt_beta_t*model_output)/sqrt_alpha_t  (epsilon)  |  sqrt_alpha_t*sample - sqrt_beta_t*model_output  (v)
+ *   a = k_x*sample;  b = k_0*x0;  s = a + b;        order 2 only:  d = k_1*hist;  s = s + d
+ *   prev = is_last ? x0 : s;      hist = x0, written after hist was read;      clamped = prev.clamp(-1, 1)
+ * Every multiply and add is a separate fp32 operation, in the order written.  `hist` carries the x0 of one step to the next: an
+ * order-1 step only writes it, an order-2 step reads the previous x0 and replaces it.  A thread owns one element (or four), reads
+ * it from every input, then writes it: `prev_out` may alias `sample`, and `hist` is updated in place; `hist` must not overlap
+ * any other tensor.  `hist` may be NULL only when order == 1 && is_last; `clamped_out` is optional.  16-byte accesses where every
+ * pointer is 16-byte aligned, scalar ones for the tail and otherwise; the bits do not depend on it.  No noise is read.
+ * LLIE_ERR_ARG before any launch for a null pointer (the optional ones excepted), a pointer that is not 4-byte aligned, n <= 0, an
+ * order other than 1 or 2, and a non-finite coefficient. */
+int llie_dpm_step(const float* model_output, const float* sample, float* hist, float* prev_out, float* clamped_out, int64_t n,
+                  const llie_dpm_coef* coef, llie_stream stream);
+
 /* LCMScheduler.add_noise / get_velocity (lcm_scheduler.py:255-305): per-sample timesteps (device
  * int64[B]) index a device fp32 alpha-bar table [num_train_timesteps]; tensors fp32 [B, per_sample]. */
 int llie_add_noise(const float* x0, const float* noise, const int64_t* timesteps, const float* alphas_cumprod,
@@ -396,6 +424,21 @@ int llie_enhance(llie_ctx* ctx, const float* low_light, const float* noise, cons
 int llie_enhance_hw(llie_ctx* ctx, const float* low_light, const float* noise, const int64_t* timesteps_dev,
                     const llie_step_coef* coefs, int steps, float* enhanced, float* intermediates, float* noise_preds,
                     int batch, int height, int width, void* workspace, int64_t workspace_bytes, llie_stream stream);
+
+/* The same loop with the DPM-Solver++ 2M sampler: `coefs` host array [steps] of llie_dpm_coef, the first of order 1.  `noise` is
+ * [1,B,3,S,S], the initial latents; nothing else is drawn.  Per step: the denoiser, then llie_dpm_step as a plain elementwise launch
+ * in every compute dtype (the output head's fused step epilogue is LCM's and DDIM's only).  Outputs, workspace sizes, staging, graph
+ * capture (keyed by the coefficient bytes), the branch split, LLIE_NO_GRAPH and the graph_max_steps rule are llie_enhance's; as
+ * with DDIM, a workspace sized for 8 LCM steps holds a loop of any length without intermediates / noise_preds.  The loop needs no
+ * image beyond the three every workspace query counts: without `intermediates` the latents are updated in place in one and the
+ * history lives in the other; with `intermediates` the history takes one of the two.  LLIE_ERR_ARG for a coefficient
+ * llie_dpm_step refuses and for a first step of order 2.  llie_enhance_dpm_hw: frames of their own size, as llie_enhance_hw. */
+int llie_enhance_dpm(llie_ctx* ctx, const float* low_light, const float* noise, const int64_t* timesteps_dev,
+                     const llie_dpm_coef* coefs, int steps, float* enhanced, float* intermediates, float* noise_preds, int batch,
+                     void* workspace, int64_t workspace_bytes, llie_stream stream);
+int llie_enhance_dpm_hw(llie_ctx* ctx, const float* low_light, const float* noise, const int64_t* timesteps_dev,
+                        const llie_dpm_coef* coefs, int steps, float* enhanced, float* intermediates, float* noise_preds,
+                        int batch, int height, int width, void* workspace, int64_t workspace_bytes, llie_stream stream);
 
 int llie_graph_cache_entries(const llie_ctx* ctx);
 

@@ -51,9 +51,10 @@ def build_parser() -> argparse.ArgumentParser:
 def parse_args(argv=None):
     p = build_parser()
     # tests/test_metrics_host.py pins build_parser()'s flags as an exact set, so the sampler flag joins the parser here
-    p.add_argument("--sampler", type=str, default="lcm", choices=["lcm", "ddim"],
+    p.add_argument("--sampler", type=str, default="lcm", choices=["lcm", "ddim", "dpmpp_2m"],
                    help="lcm = the consistency student's loop; ddim = the deterministic DDIM loop of a many-step model "
-                        "(--num_steps anything in 1..1000)")
+                        "(--num_steps anything in 1..1000); dpmpp_2m = DPM-Solver++ 2M for the same models (second order, at "
+                        "most 32 steps with the default table)")
     p.add_argument("--tile_size", type=str, default=None, metavar="{auto|HxW}",
                    help="with --full_resolution [tiled]: tiles of H x W run as frames instead of image_size squares; auto = the "
                         "fewest such tiles under the engine's size cap")

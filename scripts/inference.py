@@ -2,8 +2,9 @@
 """Image / folder enhancement CLI on the MI355X engine -- flag-compatible counterpart of the reference's
 scripts/inference.py (:30-62): --input --output --checkpoint --model --format --variant --image_size
 --num_steps --device.  Only --format pytorch exists here (ONNX / TFLite are the reference's mobile
-deployment targets, out of scope); extensions: --dtype {fp32,fp16,bf16}, --noise_seed, --sampler {lcm,ddim} (ddim: the
-deterministic sampler of a many-step model, --num_steps anything in 1..1000), --prediction {epsilon,v_prediction} (what the
+deployment targets, out of scope); extensions: --dtype {fp32,fp16,bf16}, --noise_seed, --sampler {lcm,ddim,dpmpp_2m} (ddim: the
+deterministic sampler of a many-step model, --num_steps anything in 1..1000; dpmpp_2m: the second-order sampler of such a model,
+up to 32 steps with the default table), --prediction {epsilon,v_prediction} (what the
 network's output means: a v-prediction teacher, or the v student scripts/distill.py --student_prediction v_prediction writes), and --tile [--tile_overlap N]
 [--tile_batch N] [--tile_sync {none,latents}] [--tile_size {auto|HxW}], which enhances the image at its own resolution as
 overlapping image_size tiles instead of resizing it (--tile_sync latents: the tiles share one latent canvas, fused after every
@@ -46,10 +47,11 @@ def parse_args(argv=None):
     p.add_argument("--noise_seed", type=int, default=None,
                    help="(extension) draw the loop's noise on the CPU generator with this seed, in the reference's order, "
                         "instead of on the device: makes a run reproducible against the CPU reference")
-    p.add_argument("--sampler", type=str, default="lcm", choices=["lcm", "ddim"],
+    p.add_argument("--sampler", type=str, default="lcm", choices=["lcm", "ddim", "dpmpp_2m"],
                    help="(extension) lcm = the consistency student's loop (re-noise after every step); ddim = the deterministic "
                         "DDIM loop of a many-step epsilon- / v-prediction model: --num_steps may be anything in 1..1000 and "
-                        "the initial latents are the only noise")
+                        "the initial latents are the only noise; dpmpp_2m = DPM-Solver++ 2M for the same models: second order, "
+                        "a grid uniform in log-SNR, at most 32 steps with the default table, not with --tile_sync latents")
     p.add_argument("--prediction", type=str, default="epsilon", choices=["epsilon", "v_prediction"],
                    help="(extension) what the checkpoint's network predicts: epsilon (the default, the reference's models) or "
                         "v_prediction (a model trained or distilled as a v network)")
@@ -76,6 +78,8 @@ def parse_args(argv=None):
         p.error("--guidance_scale must be finite")
     if args.guidance_scale not in (None, 1.0) and args.tile_sync == "latents":
         p.error("--guidance_scale and --tile_sync latents exclude each other")
+    if args.sampler == "dpmpp_2m" and args.tile_sync == "latents":
+        p.error("--sampler dpmpp_2m and --tile_sync latents exclude each other")
     if args.native and (args.tile or args.tile_overlap is not None or args.tile_batch != 32 or args.tile_sync != "none"
                         or args.tile_size is not None):
         p.error("--native and --tile / --tile_overlap / --tile_batch / --tile_sync / --tile_size exclude each other")
@@ -117,8 +121,9 @@ def guided(args) -> dict:
 
 
 def noise_entries(args) -> int:
-    """Entries of the noise --noise_seed draws: one per step for the LCM loop, the initial latents alone for DDIM."""
-    return 1 if args.sampler == "ddim" else args.num_steps
+    """Entries of the noise --noise_seed draws: one per step for the LCM loop, the initial latents alone for DDIM and
+    DPM-Solver++."""
+    return args.num_steps if args.sampler == "lcm" else 1
 
 
 def enhance_tiled_image(args, model, rgb):

@@ -80,9 +80,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--x0_ssim_weight", type=float, default=0.0,
                    help="weight of 1 - SSIM of the predicted clean image against the normal-light image, added to --loss")
     p.add_argument("--x0_l1_weight", type=float, default=0.0, help="weight of the L1 distance of the same two images")
-    p.add_argument("--sampler", type=str, default="lcm", choices=["lcm", "ddim"],
+    p.add_argument("--sampler", type=str, default="lcm", choices=["lcm", "ddim", "dpmpp_2m"],
                    help="how validation and the sample sheet sample: lcm = the consistency student's loop; ddim = the deterministic "
-                        "DDIM loop a many-step (teacher) model wants, with --num_steps steps (anything in 1..1000) in both")
+                        "DDIM loop a many-step (teacher) model wants, with --num_steps steps (anything in 1..1000) in both; "
+                        "dpmpp_2m = DPM-Solver++ 2M for the same models, with --num_steps steps (at most 32 with the default table)")
     p.add_argument("--crop_height", type=int, default=None, help="train at crops of this height (with --crop_width) instead of --image_size squares")
     p.add_argument("--crop_width", type=int, default=None, help="the width that goes with --crop_height")
     p.add_argument("--accumulate", type=int, default=1,
@@ -128,8 +129,9 @@ def x0_weights_from_args(args) -> dict:
 
 def sampler_from_args(args) -> dict:
     """LowLightTrainer's sampling keywords (like the x0 weights: not TrainingConfig fields, not in checkpoints).  The LCM default
-    keeps the trainer's own step counts; --sampler ddim runs --num_steps DDIM steps in validation and in the sample sheet."""
-    return {"val_sampler": args.sampler, "val_steps": args.num_steps if args.sampler == "ddim" else None}
+    keeps the trainer's own step counts; --sampler ddim / dpmpp_2m runs --num_steps steps of that sampler in validation and in the sample
+    sheet."""
+    return {"val_sampler": args.sampler, "val_steps": args.num_steps if args.sampler != "lcm" else None}
 
 
 def guidance_from_args(args) -> dict:
