@@ -135,7 +135,8 @@ def test_unet_backward_ragged_half_engines(dev, cd, size, scale):
     element, below fp16's smallest normal (6.1e-5), and the gradients that sum it over every pixel (biases, norm affines)
     lose their low bits in subnormals -- on or off the 64 grid: unscaled, 1 / 15 / 219 of the tensors fall below 0.98 at
     128 / 224 / 256 (profiles/r05).  The unscaled fp16 check of test_unet_backward_small64 runs at 64, where the same
-    derivative is 16x larger."""
+    derivative is 16x larger.
+    The rounding-level check of the half engines' backward, ragged maps included: tests/test_gpu_backward_decisive_net.py."""
     m, sd, spec = _model("small", size, dev, cd)
     low, normal, noise, t = _inputs(size, 2, seed=7 * size)
     _, _, gref = _ref_unet_grads(sd, spec, low, normal, t, noise)

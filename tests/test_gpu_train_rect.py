@@ -217,7 +217,8 @@ def test_unet_backward_rect_vs_autograd(dev, variant, hh, ww, batch):
 def test_unet_backward_rect_half_engines(dev, cd, hh, ww, scale):
     """bf16 / fp16 engines: every parameter gradient at cosine >= 0.98 against CPU autograd.  fp16 runs under a static loss scale
     of 1024, as a grad scaler would supply (test_unet_backward_ragged_half_engines has the reasoning): at B = 2 and 7488 or 8192
-    pixels d(loss)/d(eps) is ~4e-5 per element unscaled, below fp16's smallest normal."""
+    pixels d(loss)/d(eps) is ~4e-5 per element unscaled, below fp16's smallest normal.
+    The rounding-level check of the half engines' backward, H != W included: tests/test_gpu_backward_decisive_net.py."""
     (low, normal, noise, t), _, _, gref = _reference("small", hh, ww, 2, two_byte=True)
     m = _model("small", dev, cd)
     _engine_step(m, low, normal, noise, t, dev, scale=float(scale))

@@ -209,7 +209,8 @@ def test_unet_backward_small64(dev, cd, max_l2, min_cos):
 
     fp32 engine: measured relative L2 <= 1.9e-3, cosine >= 0.999998, median max-error 8e-5 of the tensor's
     largest entry; the handful of tensors near 1e-3..1e-2 sit behind 8x8 maps where single ReLU6 mask flips
-    (z within rounding of 0 or 6) move whole gradient entries.  bf16 / fp16 engines: cosine >= 0.99 measured."""
+    (z within rounding of 0 or 6) move whole gradient entries.  bf16 / fp16 engines: cosine >= 0.99 measured.
+    The rounding-level check of the same pass, with masks that cannot flip: tests/test_gpu_backward_decisive_net.py."""
     m, sd, spec = _small(64, dev)
     m.compute_dtype = cd
     try:
