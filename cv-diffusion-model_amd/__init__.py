@@ -16,6 +16,7 @@ from .dpm import dpm_timesteps, dpm_max_steps, dpm_step_coefficients, dpm_step_h
 from .guidance import (guide_array, cond_dropout_array, guidance_pair_array, scheduler_step_array, guided_enhance_host,
                        check_guidance_scale, check_cond_dropout, check_guidance_range, guide_device, guidance_pair_device,
                        cond_dropout_device)
+from .snrloss import (check_snr_gamma, snr_weight_array, snr_loss_host, snr_loss_f32, snr_loss_device, snr_loss_chunk)
 from .pipeline import (LowLightDiffusion, LowLightDiffusionOutput, LowLightLCMDistillation, normalize_image,
                        denormalize_image, x0_loss, x0_loss_host, consistency_target_host, consistency_loss_host)
 from .sharding import shard_range, enhance_sharded, all_gather_batch, all_reduce_gradients
@@ -57,4 +58,5 @@ __all__ = [
     "dpm_timesteps", "dpm_max_steps", "dpm_step_coefficients", "dpm_step_host", "dpm_step_f32", "dpm_enhance_host",
     "guide_array", "cond_dropout_array", "guidance_pair_array", "scheduler_step_array", "guided_enhance_host",
     "check_guidance_scale", "check_cond_dropout", "check_guidance_range", "guide_device", "guidance_pair_device", "cond_dropout_device",
+    "check_snr_gamma", "snr_weight_array", "snr_loss_host", "snr_loss_f32", "snr_loss_device", "snr_loss_chunk",
 ]

@@ -19,6 +19,7 @@ LLIE_UNET, LLIE_IRB, LLIE_ATTN, LLIE_DOWN, LLIE_UP, LLIE_SE, LLIE_SOFTATTN = 0, 
 ERR_ARG, ERR_SHAPE, ERR_CONFIG, ERR_KEY, ERR_NOT_LOADED, ERR_WORKSPACE, ERR_NO_DEVICE = -1, -2, -3, -4, -5, -6, -7
 SAMPLER_LCM, SAMPLER_DDIM = 0, 1  # llie_step_coef.sampler
 PRED_EPSILON, PRED_V = 0, 1  # LLIE_PRED_*: what a network output means to llie_consistency_target_ex / llie_consistency_loss_ex
+LOSS_MSE, LOSS_L1, LOSS_HUBER = 0, 1, 2  # LLIE_LOSS_*: loss_type of llie_snr_loss
 
 EXPORTS = [
     "llie_last_error", "llie_version", "llie_create", "llie_destroy", "llie_num_params", "llie_param_info",
@@ -61,6 +62,7 @@ EXPORTS = [
     "llie_pw_expand_nsplit", "llie_silu_rows",
     "llie_guide", "llie_guidance_pair", "llie_cond_dropout",
     "llie_dpm_step", "llie_enhance_dpm", "llie_enhance_dpm_hw",
+    "llie_snr_loss_chunk", "llie_snr_loss_scratch_bytes", "llie_snr_loss",
 ]
 K_GEMM, K_DW, K_CONV3, K_SE, K_OTHER = 1, 2, 4, 8, 16
 PW_SIGMOID_BWD, PW_RELU6_BWD, PW_SILU_BWD, PW_SCALE = 0, 1, 2, 3  # llie_pointwise_kind
@@ -238,6 +240,11 @@ def lib() -> C.CDLL:
     L.llie_ssim_grad_scratch_bytes.restype = i64
     L.llie_ssim_grad_f32.argtypes = [vp, vp, ci, ci, ci, C.c_float, C.c_float, vp, vp, vp, vp, i64, vp]
     L.llie_x0_loss.argtypes = [vp, vp, vp, vp, vp, ci, ci, C.c_float, C.c_float, vp, vp, ci, ci, ci, vp, i64, vp]
+    L.llie_snr_loss_chunk.argtypes = []
+    L.llie_snr_loss_chunk.restype = i64
+    L.llie_snr_loss_scratch_bytes.argtypes = [ci, i64]
+    L.llie_snr_loss_scratch_bytes.restype = i64
+    L.llie_snr_loss.argtypes = [vp, vp, vp, vp, ci, ci, ci, C.c_float, vp, vp, vp, vp, ci, i64, vp, i64, vp]
     L.llie_comparison_grid_u8.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
     L.llie_pw_gemm.argtypes = [ci, C.POINTER(GemmSeg), ci, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     L.llie_pw_gemm_tile_rows.argtypes = [ci]

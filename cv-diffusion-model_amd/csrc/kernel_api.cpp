@@ -704,6 +704,48 @@ int llie_x0_loss(const float* out, const float* x_t, const float* normal, const 
   return kerr("x0_loss", launch_x0_loss(x, scratch, hs(stream)), LLIE_ERR_ARG, nullptr);
 }
 
+// ---- the noise-space loss with a Min-SNR-gamma weight (snrloss.hip): every contract check runs here, before any HIP call
+static_assert(LLIE_LOSS_MSE == kLossMse && LLIE_LOSS_L1 == kLossL1 && LLIE_LOSS_HUBER == kLossHuber, "LLIE_LOSS_* are the kernels' codes");
+int64_t llie_snr_loss_chunk(void) { return kSnrChunk; }
+int64_t llie_snr_loss_scratch_bytes(int batch, int64_t per_sample) {
+  const long long n = snr_loss_scratch_bytes(batch, per_sample);
+  return n < 0 ? (int64_t)LLIE_ERR_ARG : (int64_t)n;
+}
+int llie_snr_loss(const float* pred, const float* target, const int64_t* t, const float* alphas_cumprod, int table_n, int loss_type,
+                  int velocity, float gamma, float* loss_out, float* sample_loss, float* weight, float* d_pred, int batch,
+                  int64_t per_sample, void* scratch, int64_t scratch_bytes, llie_stream stream) {
+  if (!pred || !target || !t || !alphas_cumprod || !loss_out || !scratch || batch < 1 || per_sample < 1 || table_n < 1) return LLIE_ERR_ARG;
+  for (const void* p : {(const void*)pred, (const void*)target, (const void*)alphas_cumprod, (const void*)loss_out, (const void*)sample_loss,
+                        (const void*)weight, (const void*)d_pred})
+    if (reinterpret_cast<uintptr_t>(p) & 3) {
+      set_err("snr_loss: fp32 pointers must be 4-byte aligned");
+      return LLIE_ERR_ARG;
+    }
+  if ((reinterpret_cast<uintptr_t>(t) | reinterpret_cast<uintptr_t>(scratch)) & 7) {
+    set_err("snr_loss: t and scratch must be 8-byte aligned");
+    return LLIE_ERR_ARG;
+  }
+  if (loss_type != LLIE_LOSS_MSE && loss_type != LLIE_LOSS_L1 && loss_type != LLIE_LOSS_HUBER) {
+    set_err("snr_loss: unknown loss_type %d", loss_type);
+    return LLIE_ERR_ARG;
+  }
+  if (!std::isfinite(gamma) || !(gamma > 0.f)) {
+    set_err("snr_loss: snr_gamma must be finite and > 0");
+    return LLIE_ERR_ARG;
+  }
+  const int64_t need = llie_snr_loss_scratch_bytes(batch, per_sample);
+  if (need < 0) return LLIE_ERR_ARG;
+  if (scratch_bytes < need) {
+    set_err("snr_loss: scratch of %lld bytes needed, %lld given", (long long)need, (long long)scratch_bytes);
+    return LLIE_ERR_WORKSPACE;
+  }
+  SnrLossArgs x{};
+  x.pred = pred; x.target = target; x.t = t; x.acp = alphas_cumprod; x.table_len = table_n; x.loss_type = loss_type;
+  x.velocity = velocity != 0; x.gamma = gamma; x.loss = loss_out; x.sample_loss = sample_loss; x.weight = weight; x.d_pred = d_pred;
+  x.batch = batch; x.per = per_sample;
+  return kerr("snr_loss", launch_snr_loss(x, scratch, hs(stream)), LLIE_ERR_ARG, nullptr);
+}
+
 // ---- the trainer's sample sheet (samples.hip): arguments are checked here, before any HIP call
 int llie_comparison_grid_u8(const float* low, const float* enhanced, const float* normal, int n, int H, int W, uint8_t* grid,
                             llie_stream stream) {

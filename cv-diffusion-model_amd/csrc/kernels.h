@@ -839,4 +839,32 @@ struct X0LossArgs {
 };
 hipError_t launch_x0_loss(const X0LossArgs& a, void* scratch, hipStream_t s);
 
+// (16) the noise-space loss with a Min-SNR-gamma weight (snrloss.hip).  pred / target fp32 [B][n], d = pred - target:
+//   l(d), l'(d):  mse d^2, 2 d;   l1 |d|, sign(d) (0 at 0);   huber (delta 1) 0.5 d^2 where |d| < 1 else |d| - 0.5, clamp(d, -1, 1)
+//   abar = acp[t_b];  w_b = (abar == 0 ? 1 : min(1, (gamma (1 - abar)) / abar))  (epsilon)  or  min(abar, gamma (1 - abar))  (v)
+//   m_b = (1 / n) sum_i l(d_bi)  (unweighted);   loss = (1 / B) sum_b w_b m_b;   d_pred[b][i] = l'(d_bi) c_b,
+//   c_b = (w_b / (float)B) / (float)n -- fp32, one rounding per operation, no fused multiply-add.
+// A timestep outside [0, table_len) never indexes the table: w_b, the sample's gradient rows and the loss are NaN.
+// A sample is kSnrChunk-element chunks, one workgroup each; no atomics; the order of every sum depends on n (m_b) or B (loss) alone.
+constexpr int kLossMse = 0, kLossL1 = 1, kLossHuber = 2;  // LLIE_LOSS_*
+constexpr int64_t kSnrChunk = 4096;
+inline int64_t snr_loss_chunks(int64_t per) { return per < 1 ? 0 : (per + kSnrChunk - 1) / kSnrChunk; }
+// B doubles (the means) + B * chunks floats (the per-workgroup partials); -1 for batch < 1, per < 1 or more than 2^31 - 1 workgroups
+inline long long snr_loss_scratch_bytes(int batch, int64_t per) {
+  const int64_t chunks = snr_loss_chunks(per);
+  if (batch < 1 || chunks < 1 || (int64_t)batch * chunks > (int64_t)INT32_MAX) return -1;
+  return (long long)batch * 8 + (long long)batch * chunks * 4;
+}
+struct SnrLossArgs {
+  const float* pred; const float* target;             // fp32 [batch][per]
+  const int64_t* t; const float* acp; int table_len;  // device int64 [batch], device alphas_cumprod
+  int loss_type, velocity; float gamma;               // kLoss*; 0 epsilon prediction, 1 v prediction; finite, > 0
+  float* loss;                                        // one device fp32
+  float* sample_loss; float* weight;                  // [batch] each, or null
+  float* d_pred;                                      // stored (or null: the loss alone, the same bits)
+  int batch; int64_t per;
+};
+// A null required pointer, batch or per < 1, table_len < 1, an unknown loss_type, gamma not finite or <= 0: hipErrorInvalidValue
+hipError_t launch_snr_loss(const SnrLossArgs& a, void* scratch, hipStream_t s);
+
 }  // namespace llie

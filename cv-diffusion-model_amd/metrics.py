@@ -365,6 +365,8 @@ def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[i
       model.image_size, as before.
       guidance_scale=w scores `model.enhance(..., guidance_scale=w)` (classifier-free guidance; None: off); the draws and the
       loss are unchanged.
+      The loss is always this flat, unweighted MSE: a trainer's `snr_gamma` (Min-SNR-gamma weighting, snrloss.py) does not reach
+      it, so runs with and without that flag stay comparable.
 
     Returns {"n", "psnr", "ssim", "mse", ["loss",] "per_image": {"filename", "psnr", "ssim", "mse"}}: psnr / ssim / mse are the
     means over images of the per-image values (float64 sums in file order), loss = sum of batch losses / len(loader).  Everything

@@ -36,6 +36,7 @@ from .ddim import check_sampler
 from . import dpm as DPM
 from . import guidance as G
 from .scheduler import LCMScheduler
+from .snrloss import check_snr_gamma
 from .unet import EfficientUNet, create_efficient_unet
 
 
@@ -404,7 +405,7 @@ class LowLightDiffusion(nn.Module):
     # ------------------------------------------------------------------ loss (:250-277)
     def compute_loss(self, low_light: torch.Tensor, normal_light: torch.Tensor, loss_type: str = "mse", *,
                      use_velocity_target: bool = False, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0,
-                     cond_dropout: float = 0.0) -> torch.Tensor:
+                     cond_dropout: float = 0.0, snr_gamma: Optional[float] = None) -> torch.Tensor:
         """Regresses the denoiser output against the drawn noise, as the reference does whatever the scheduler's
         prediction type (low_light_diffusion.py:262-275).  `use_velocity_target=True` (extension, needs a
         `prediction_type="v_prediction"` scheduler) regresses against `scheduler.get_velocity` instead -- the v-pred MSE of
@@ -416,12 +417,24 @@ class LowLightDiffusion(nn.Module):
         `loss.backward()` also fills the gradient of a `low_light` that requires one (forward's docstring): `compute_loss(frontend(raw),
         normal)` trains `frontend` together with, or instead of, the denoiser.
         `cond_dropout=p`: `forward`'s condition dropout (one more draw, `torch.rand(B)`, after the timestep and noise draws, only
-        when p > 0) -- what TrainStep(cond_dropout=p) does without autograd."""
+        when p > 0) -- what TrainStep(cond_dropout=p) does without autograd.
+        `snr_gamma=g` (extension; finite, > 0; None = off): Min-SNR-gamma weighting of the noise-space loss (snrloss.py has the
+        definition): the loss becomes (1 / B) sum_b w_b m_b with w_b from `use_velocity_target`, computed with its gradient by
+        one call of llie_snr_loss inside one autograd node, the x0 term (not multiplied by w) added into the same gradient
+        buffer -- the loss and d(loss)/d(pred) bits of TrainStep(snr_gamma=g).  With None nothing changes."""
         _check_x0_weights(x0_ssim_weight, x0_l1_weight)
+        snr_gamma = check_snr_gamma(snr_gamma)
+        if loss_type not in ("mse", "huber", "l1") and snr_gamma is not None:
+            raise ValueError(f"Unknown loss type: {loss_type}")
         out = self.forward(low_light, normal_light, frame=True, **({"cond_dropout": cond_dropout} if cond_dropout != 0 else {}))
         if use_velocity_target and "target" not in out:
             raise ValueError("use_velocity_target needs a scheduler with prediction_type='v_prediction'")
         pred, noise = out["noise_pred"], (out["target"] if use_velocity_target else out["noise"])
+        if snr_gamma is not None:
+            x0_on = x0_ssim_weight != 0 or x0_l1_weight != 0
+            noisy = self.scheduler.add_noise(normal_light, out["noise"], out["timesteps"]) if x0_on else None  # forward's x_t
+            return _SnrLossFn.apply(pred, noise, self.scheduler, noisy, normal_light, out["timesteps"], loss_type,
+                                    bool(use_velocity_target), snr_gamma, float(x0_ssim_weight), float(x0_l1_weight))
         if loss_type == "mse":
             loss = F.mse_loss(pred, noise)
         elif loss_type == "huber":
@@ -709,6 +722,30 @@ class _LossWithX0Fn(torch.autograd.Function):
     def backward(ctx, grad_output):
         d, = ctx.saved_tensors
         return (d * grad_output,) + (None,) * 9
+
+
+class _SnrLossFn(torch.autograd.Function):
+    """compute_loss with `snr_gamma` set, as one autograd node of the network output: llie_snr_loss stores the weighted loss's
+    gradient into a buffer, then (x0 term on) llie_x0_loss adds the term's into it -- TrainStep's order of operations, so the
+    two routes share the loss and d(loss)/d(pred) bits.  backward = that buffer times grad_output."""
+
+    @staticmethod
+    def forward(ctx, pred, target, scheduler, x_t, normal, timesteps, loss_type, velocity, gamma, ssim_weight, l1_weight):
+        from .snrloss import snr_loss_device
+        out = pred.detach().float().contiguous()
+        d = torch.empty_like(out)
+        loss, _, _ = snr_loss_device(scheduler, out, target, timesteps, loss_type, velocity, gamma, d)
+        if ssim_weight != 0 or l1_weight != 0:
+            loss = loss + x0_loss_device(scheduler, out, x_t, normal, timesteps, velocity, ssim_weight, l1_weight, d)
+        else:
+            loss = loss.clone()  # a view of the kernel's output block otherwise
+        ctx.save_for_backward(d)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        d, = ctx.saved_tensors
+        return (d * grad_output,) + (None,) * 10
 
 
 class _X0LossFn(torch.autograd.Function):

@@ -29,6 +29,7 @@ from . import hostio
 from .data import create_device_dataloaders
 from .ddim import check_sampler
 from .guidance import check_cond_dropout, check_guidance_scale, guided_keyword
+from .snrloss import check_snr_gamma
 from .metrics import _require_hip, _steps_of, _swapped_weights, evaluate
 from .pipeline import LowLightDiffusion
 from .training import FusedAdamW, FusedGradScaler, TrainStep, accumulation_windows
@@ -436,6 +437,11 @@ class LowLightTrainer(_EpochLoop):
     and are not written into checkpoints: a caller that resumes a run passes them again.  The validation loss stays the
     reference's MSE.
 
+    `snr_gamma=g` (extension; finite, > 0, None = off; a keyword like the x0 weights: neither a TrainingConfig field nor stored in
+    checkpoints, a caller that resumes a run passes it again) goes to TrainStep: Min-SNR-gamma weighting of the training loss
+    (snrloss.py).  The validation loss in `validate` / `evaluate` stays unweighted, so that runs with and without the flag stay
+    comparable.
+
     `val_sampler` / `val_steps` (extension; keywords like the x0 weights, neither TrainingConfig fields nor stored in checkpoints)
     choose how validation and the sample sheet sample: val_sampler="ddim" is the deterministic sampler a many-step (teacher)
     model wants, where the default "lcm" shows the 4-step loop of a consistency student; `val_steps` replaces
@@ -465,7 +471,8 @@ class LowLightTrainer(_EpochLoop):
     def __init__(self, model: LowLightDiffusion, train_loader, val_loader=None, config: Optional[TrainingConfig] = None, *,
                  x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0, val_sampler: str = "lcm", val_steps: Optional[int] = None,
                  crop_size: Optional[Tuple[int, int]] = None, accumulate: int = 1, cond_dropout: float = 0.0,
-                 val_guidance_scale: Optional[float] = None):
+                 val_guidance_scale: Optional[float] = None, snr_gamma: Optional[float] = None):
+        self.snr_gamma = check_snr_gamma(snr_gamma)
         self._init_shapes(config, train_loader, val_loader, crop_size, accumulate)
         cfg = self.config
         self.cond_dropout = check_cond_dropout(cond_dropout)
@@ -492,7 +499,8 @@ class LowLightTrainer(_EpochLoop):
         self.scheduler = make_lr_scheduler(self.optimizer, cfg, len(accumulation_windows(len(train_loader), accumulate)))
         self.scaler = FusedGradScaler() if dtype == "fp16" else None
         self.step = TrainStep(model, self.optimizer, loss_type=cfg.loss_type, grad_scaler=self.scaler,
-                              x0_ssim_weight=x0_ssim_weight, x0_l1_weight=x0_l1_weight, cond_dropout=self.cond_dropout)
+                              x0_ssim_weight=x0_ssim_weight, x0_l1_weight=x0_l1_weight, cond_dropout=self.cond_dropout,
+                              **({} if self.snr_gamma is None else {"snr_gamma": self.snr_gamma}))
         self._names = [name for name, _ in model.named_parameters()]
 
         self.best_val_loss = float("inf")
@@ -624,11 +632,12 @@ class LowLightTrainer(_EpochLoop):
 def train_model(train_data_dir: str, val_data_dir: Optional[str] = None, config: Optional[TrainingConfig] = None,
                 device="cuda", *, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0, val_sampler: str = "lcm",
                 val_steps: Optional[int] = None, crop_size: Optional[Tuple[int, int]] = None, accumulate: int = 1,
-                cond_dropout: float = 0.0, val_guidance_scale: Optional[float] = None) -> LowLightTrainer:
+                cond_dropout: float = 0.0, val_guidance_scale: Optional[float] = None,
+                snr_gamma: Optional[float] = None) -> LowLightTrainer:
     """Training entry point (trainer.py:459-496): loaders from the folders (create_device_dataloaders), a fresh model, a trainer,
     `train()`; returns the trainer.  `x0_ssim_weight` / `x0_l1_weight` / `val_sampler` / `val_steps` / `crop_size`: as
     LowLightTrainer's (with `crop_size=(H, W)` the loaders crop H x W; the model is still built at config.image_size);
-    `accumulate` / `cond_dropout` / `val_guidance_scale`: LowLightTrainer's."""
+    `accumulate` / `cond_dropout` / `val_guidance_scale` / `snr_gamma`: LowLightTrainer's."""
     config = config or TrainingConfig()
     train_loader, val_loader = create_device_dataloaders(train_root=train_data_dir, val_root=val_data_dir, batch_size=config.batch_size,
                                                          image_size=config.image_size if crop_size is None else tuple(crop_size),
@@ -639,6 +648,6 @@ def train_model(train_data_dir: str, val_data_dir: Optional[str] = None, config:
     trainer = LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config,
                               x0_ssim_weight=x0_ssim_weight, x0_l1_weight=x0_l1_weight, val_sampler=val_sampler, val_steps=val_steps,
                               crop_size=crop_size, accumulate=accumulate, cond_dropout=cond_dropout,
-                              val_guidance_scale=val_guidance_scale)
+                              val_guidance_scale=val_guidance_scale, snr_gamma=snr_gamma)
     trainer.train()
     return trainer

@@ -436,18 +436,27 @@ class TrainStep(_GradWindow):
     condition is replaced by the null condition (all zeros) where u[b] < p -- llie_cond_dropout into a persistent buffer of the
     step, before the train forward.  u is `cond_u` (fp32 [B], supplied like `timesteps=` and `noise=`) or `torch.rand(b,
     device=dev)` from the global device generator, drawn after the timestep and noise draws.  `step.cond_grad` goes through the
-    same kernel: dropped rows are exactly 0.  With p == 0 no draw is made and the step is what it was, bit for bit."""
+    same kernel: dropped rows are exactly 0.  With p == 0 no draw is made and the step is what it was, bit for bit.
+    `snr_gamma=g` (finite, > 0; None = off): Min-SNR-gamma weighting of the noise-space loss (snrloss.py has the definition).
+    One call of llie_snr_loss replaces the torch arithmetic between the forward and the backward pass: it returns
+    (1 / B) sum_b w_b m_b, with w_b from `use_velocity_target`, and stores d(loss)/d(eps) into a buffer of the step; the x0 term
+    then adds into that buffer exactly as without the flag (its own abar weight unchanged, not multiplied by w), and the
+    grad-scaler multiplication, `cond_grad`, `cond_dropout` and `accumulate` / `apply` follow unchanged.  After each call
+    `step.sample_loss` (the unweighted per-sample means m_b) and `step.snr_weight` (w_b), fp32 [B] on the device, hold the last
+    micro-batch's values; nothing reads them on the host.  With None the step is what it was, bit for bit."""
 
     def __init__(self, model, optimizer: FusedAdamW, loss_type: str = "mse", use_velocity_target: bool = False, group=None,
                  grad_scaler: Optional[FusedGradScaler] = None, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0,
-                 cond_grad: bool = False, cond_dropout: float = 0.0):
+                 cond_grad: bool = False, cond_dropout: float = 0.0, snr_gamma: Optional[float] = None):
         from .guidance import check_cond_dropout
+        from .snrloss import check_snr_gamma
         from .pipeline import _check_x0_weights
         if loss_type not in ("mse", "huber", "l1"):
             raise ValueError(f"Unknown loss type: {loss_type}")
         if grad_scaler is not None and not isinstance(grad_scaler, FusedGradScaler):
             raise ValueError("grad_scaler must be a FusedGradScaler")
         _check_x0_weights(x0_ssim_weight, x0_l1_weight)
+        self.snr_gamma = check_snr_gamma(snr_gamma)
         self.model, self.opt, self.loss_type, self.velocity, self.group = model, optimizer, loss_type, use_velocity_target, group
         self.grad_scaler = grad_scaler
         self.x0_ssim_weight, self.x0_l1_weight = float(x0_ssim_weight), float(x0_l1_weight)
@@ -460,6 +469,9 @@ class TrainStep(_GradWindow):
         self.cond_grad: Optional[torch.Tensor] = None
         self.cond_dropout = check_cond_dropout(cond_dropout)
         self._cond = None  # the dropped-out condition (persistent; follows the batch's shape)
+        self._d_eps = None  # d(loss)/d(eps) of the weighted loss (persistent; follows the batch's shape)
+        self.sample_loss: Optional[torch.Tensor] = None
+        self.snr_weight: Optional[torch.Tensor] = None
 
     @torch.no_grad()
     def __call__(self, low_light: torch.Tensor, normal_light: torch.Tensor, timesteps: Optional[torch.Tensor] = None,
@@ -528,7 +540,15 @@ class TrainStep(_GradWindow):
             st = torch.cuda.current_stream(dev).cuda_stream
             h.unet_train_forward(noisy.data_ptr(), cond.data_ptr(), t.data_ptr(), eps.data_ptr(), b, hh, ww, self._ws.data_ptr(), nbytes, st)
             from .pipeline import base_loss_and_grad, x0_loss_device
-            loss, d_eps = base_loss_and_grad(eps, target, self.loss_type)
+            if self.snr_gamma is None:
+                loss, d_eps = base_loss_and_grad(eps, target, self.loss_type)
+            else:
+                from .snrloss import snr_loss_device
+                if self._d_eps is None or self._d_eps.shape != eps.shape or self._d_eps.device != dev:
+                    self._d_eps = torch.empty_like(eps)
+                d_eps = self._d_eps
+                loss, self.sample_loss, self.snr_weight = snr_loss_device(model.scheduler, eps, target, t, self.loss_type, self.velocity,
+                                                                          self.snr_gamma, d_eps)
             if self.x0_ssim_weight != 0.0 or self.x0_l1_weight != 0.0:
                 d_eps = d_eps.contiguous()
                 loss = loss + x0_loss_device(model.scheduler, eps, noisy, normal_light, t, self.velocity, self.x0_ssim_weight,

@@ -609,6 +609,45 @@ int llie_x0_loss(const float* out, const float* x_t, const float* normal, const 
                  int velocity, float lambda_s, float lambda_1, float* loss_out, float* d_out, int batch, int H, int W, void* scratch,
                  int64_t scratch_bytes, llie_stream stream);
 
+/* The noise-space training loss with a per-sample Min-SNR-gamma weight (Hang et al., ICCV 2023; `gamma` is the snr_gamma of
+ * TrainStep, compute_loss and scripts/train.py), its per-sample values and d(loss)/d(pred) in one read of pred and target and
+ * one write of the gradient (csrc/snrloss.hip).
+ *   pred, target     fp32 [batch][per_sample], any per_sample >= 1 (the network's is 3 H W);  d = pred - target
+ *   t                device int64 [batch];  alphas_cumprod device fp32 [table_n];  abar = alphas_cumprod[t_b]
+ *   loss_type        LLIE_LOSS_MSE    l(d) = d^2                                          l'(d) = 2 d
+ *                    LLIE_LOSS_L1     l(d) = |d|                                          l'(d) = sign(d), sign(0) = 0 as torch.sign
+ *                    LLIE_LOSS_HUBER  l(d) = 0.5 d^2 where |d| < 1, else |d| - 0.5        l'(d) = clamp(d, -1, 1)      (delta = 1)
+ *   velocity == 0    w_b = 1 if abar == 0, otherwise min(1, (gamma (1 - abar)) / abar): min(SNR, gamma) / SNR with
+ *                    SNR = abar / (1 - abar), whose limit is 1 on the zero-SNR step
+ *   velocity != 0    w_b = min(abar, gamma (1 - abar)): min(SNR, gamma) / (SNR + 1) without a division, exactly 0 at abar == 0
+ *   sample_loss[b]   m_b = (1 / n) sum_i l(d_bi), n = per_sample: unweighted, so it can be logged per timestep (optional)
+ *   weight[b]        w_b (optional)
+ *   *loss_out        (1 / B) sum_b w_b m_b; with every w_b = 1 this is F.mse_loss / F.l1_loss / F.huber_loss
+ *   d_pred[b][i]     l'(d_bi) c_b, c_b = (w_b / (float)B) / (float)n; stored, not accumulated; must not overlap pred or target
+ *                    (optional: without it the call returns the loss alone, the same bits)
+ * The weight, c_b, d and l'(d) c_b are each separate fp32 operations in the order written, no fused multiply-add, so the host fp32
+ * twin (snrloss.snr_loss_f32) gives the bits of `weight` and `d_pred`; every n the engines accept converts to float exactly (the
+ * cap 3 * 5 592 405 = 2^24 - 1).  snrloss.snr_loss_host is the definition in float64.
+ * Two launches on the stream, no atomics, no host synchronisation.  Pass 1: one workgroup per (sample, chunk of
+ * llie_snr_loss_chunk() elements) leaves one fp32 partial in `scratch`; 16-byte accesses where pred, target, d_pred and every row
+ * start are 16-byte aligned, scalar ones otherwise and for the tail, with the same bits either way.  Pass 2: one workgroup adds a
+ * sample's partials in ascending chunk order, then the samples in ascending order, in double.  The order of every sum depends on
+ * per_sample alone (m_b) or on batch alone (the total): m_b is the same bits for a sample alone or in a batch, and from run to run;
+ * every gradient element has one writer.
+ * A t_b outside [0, table_n) never indexes the table: that sample's weight, its rows of d_pred and *loss_out are NaN (its
+ * sample_loss stays what it is), the convention of llie_add_noise and llie_x0_loss.
+ * Checked before any HIP call: a NULL pred, target, t, alphas_cumprod, loss_out or scratch, an fp32 pointer that is not 4-byte
+ * aligned (t, scratch: 8-byte), batch < 1, per_sample < 1, table_n < 1, an unknown loss_type, a gamma that is not finite or <= 0,
+ * more than 2^31 - 1 workgroups return LLIE_ERR_ARG; scratch_bytes below llie_snr_loss_scratch_bytes LLIE_ERR_WORKSPACE. */
+#define LLIE_LOSS_MSE 0
+#define LLIE_LOSS_L1 1
+#define LLIE_LOSS_HUBER 2
+int64_t llie_snr_loss_chunk(void);
+int64_t llie_snr_loss_scratch_bytes(int batch, int64_t per_sample);
+int llie_snr_loss(const float* pred, const float* target, const int64_t* t, const float* alphas_cumprod, int table_n,
+                  int loss_type, int velocity, float gamma, float* loss_out, float* sample_loss, float* weight,
+                  float* d_pred, int batch, int64_t per_sample, void* scratch, int64_t scratch_bytes, llie_stream stream);
+
 /* The trainer's per-epoch sample sheet (LowLightTrainer.generate_samples / _save_comparison, src/training/trainer.py:365-410):
  * torchvision's make_grid(cat([low, enhanced, normal]), nrow=n) with its defaults (padding 2, pad value 0) followed by
  * save_image's quantisation, in one launch.

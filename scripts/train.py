@@ -93,6 +93,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "all-zero image (0 = off)")
     p.add_argument("--guidance_scale", type=float, default=None,
                    help="guidance scale w of validation and of the sample sheet: o_u + w (o_c - o_u) at every step (default: off)")
+    p.add_argument("--snr_gamma", type=float, default=None,
+                   help="Min-SNR-gamma weighting of the training loss: each sample's --loss is weighted by min(SNR, gamma) / SNR "
+                        "at its timestep (finite, > 0; 5 is the usual choice; default: off, every timestep counts the same)")
     return p
 
 
@@ -107,6 +110,8 @@ def parse_args(argv=None):
         p.error("--cond_dropout must be in [0, 1]")
     if args.guidance_scale is not None and not math.isfinite(args.guidance_scale):
         p.error("--guidance_scale must be finite")
+    if args.snr_gamma is not None and not (math.isfinite(args.snr_gamma) and args.snr_gamma > 0):
+        p.error("--snr_gamma must be finite and > 0")
     return args
 
 
@@ -138,6 +143,12 @@ def guidance_from_args(args) -> dict:
     """LowLightTrainer's classifier-free guidance keywords (not TrainingConfig fields, not in checkpoints): --cond_dropout trains
     with the condition dropped, --guidance_scale samples validation and the sample sheet with guidance."""
     return {"cond_dropout": args.cond_dropout, "val_guidance_scale": args.guidance_scale}
+
+
+def snr_from_args(args) -> dict:
+    """LowLightTrainer's `snr_gamma` keyword (like the x0 weights: not a TrainingConfig field, not in checkpoints; a run resumed
+    with --resume passes the flag again): None without --snr_gamma."""
+    return {"snr_gamma": args.snr_gamma}
 
 
 def crop_size_from_args(args) -> dict:
@@ -174,7 +185,7 @@ def main(argv=None) -> int:
 
     trainer = M.LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config,
                                 **x0_weights_from_args(args), **sampler_from_args(args), crop_size=crop, accumulate=args.accumulate,
-                                **guidance_from_args(args))
+                                **guidance_from_args(args), **snr_from_args(args))
     print(f"  Engine precision: {model.compute_dtype}, loss scaler: {trainer.scaler is not None}, EMA: {config.use_ema}")
     trainer.train(on_epoch=lambda log: print(json.dumps(log), flush=True))
     print("\nTraining complete!")
