@@ -15,7 +15,8 @@ from .ddim import ddim_timesteps, ddim_step_host, ddim_enhance_host
 from .dpm import dpm_timesteps, dpm_max_steps, dpm_step_coefficients, dpm_step_host, dpm_step_f32, dpm_enhance_host
 from .guidance import (guide_array, cond_dropout_array, guidance_pair_array, scheduler_step_array, guided_enhance_host,
                        check_guidance_scale, check_cond_dropout, check_guidance_range, guide_device, guidance_pair_device,
-                       cond_dropout_device)
+                       cond_dropout_device, check_guidance_rescale, guided_keyword, guide_rescale_host, guide_rescale_array,
+                       guide_rescale_device)
 from .snrloss import (check_snr_gamma, snr_weight_array, snr_loss_host, snr_loss_f32, snr_loss_device, snr_loss_chunk)
 from .pipeline import (LowLightDiffusion, LowLightDiffusionOutput, LowLightLCMDistillation, normalize_image,
                        denormalize_image, x0_loss, x0_loss_host, consistency_target_host, consistency_loss_host)
@@ -58,5 +59,6 @@ __all__ = [
     "dpm_timesteps", "dpm_max_steps", "dpm_step_coefficients", "dpm_step_host", "dpm_step_f32", "dpm_enhance_host",
     "guide_array", "cond_dropout_array", "guidance_pair_array", "scheduler_step_array", "guided_enhance_host",
     "check_guidance_scale", "check_cond_dropout", "check_guidance_range", "guide_device", "guidance_pair_device", "cond_dropout_device",
+    "check_guidance_rescale", "guided_keyword", "guide_rescale_host", "guide_rescale_array", "guide_rescale_device",
     "check_snr_gamma", "snr_weight_array", "snr_loss_host", "snr_loss_f32", "snr_loss_device", "snr_loss_chunk",
 ]

@@ -61,6 +61,7 @@ EXPORTS = [
     "llie_softattn", "llie_softattn_backward", "llie_softattn_bwd_floats",
     "llie_pw_expand_nsplit", "llie_silu_rows",
     "llie_guide", "llie_guidance_pair", "llie_cond_dropout",
+    "llie_guide_rescale_chunk", "llie_guide_rescale_scratch_bytes", "llie_guide_rescale",
     "llie_dpm_step", "llie_enhance_dpm", "llie_enhance_dpm_hw",
     "llie_snr_loss_chunk", "llie_snr_loss_scratch_bytes", "llie_snr_loss",
 ]
@@ -330,6 +331,11 @@ def lib() -> C.CDLL:
     L.llie_consistency_loss_ex.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, i64, ci, i64, ci, vp]
     L.llie_guide.argtypes = [vp, vp, vp, C.c_float, vp, ci, i64, vp]
     L.llie_guidance_pair.argtypes = [vp, vp, vp, vp, ci, i64, vp]
+    L.llie_guide_rescale_chunk.argtypes = []
+    L.llie_guide_rescale_chunk.restype = i64
+    L.llie_guide_rescale_scratch_bytes.argtypes = [ci, i64]
+    L.llie_guide_rescale_scratch_bytes.restype = i64
+    L.llie_guide_rescale.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp, vp, vp, i64, ci, i64, vp]
     L.llie_cond_dropout.argtypes = [vp, vp, C.c_float, vp, ci, i64, vp]
     L.llie_ema_create.argtypes = [C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), ci, C.POINTER(vp)]
     L.llie_ema_update.argtypes = [vp, C.c_double, vp]

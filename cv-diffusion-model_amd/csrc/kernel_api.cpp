@@ -920,6 +920,48 @@ int llie_guide(const float* out_cond, const float* out_uncond, const float* w_ro
               "null or unaligned pointer, empty shape, or a non-finite guidance scale");
 }
 
+// guidance rescale: every contract check runs here, before any HIP call
+int64_t llie_guide_rescale_chunk(void) { return kGuideRescaleChunk; }
+int64_t llie_guide_rescale_scratch_bytes(int batch, int64_t per_sample) {
+  const long long n = guide_rescale_scratch_bytes(batch, per_sample);
+  return n < 0 ? (int64_t)LLIE_ERR_ARG : (int64_t)n;
+}
+int llie_guide_rescale(const float* out_cond, const float* out_uncond, const float* w_rows, float w, float phi, float* out, float* factor,
+                       void* scratch, int64_t scratch_bytes, int batch, int64_t per_sample, llie_stream stream) {
+  if (!out_cond || !out_uncond || !out || !scratch || batch < 1 || per_sample < 1) {
+    set_err("guide_rescale: null pointer or empty shape");
+    return LLIE_ERR_ARG;
+  }
+  for (const void* p : {(const void*)out_cond, (const void*)out_uncond, (const void*)w_rows, (const void*)out, (const void*)factor})
+    if (reinterpret_cast<uintptr_t>(p) & 3) {
+      set_err("guide_rescale: fp32 pointers must be 4-byte aligned");
+      return LLIE_ERR_ARG;
+    }
+  if (reinterpret_cast<uintptr_t>(scratch) & 7) {
+    set_err("guide_rescale: scratch must be 8-byte aligned");
+    return LLIE_ERR_ARG;
+  }
+  if (!w_rows && !std::isfinite(w)) {
+    set_err("guide_rescale: the guidance scale must be finite");
+    return LLIE_ERR_ARG;
+  }
+  if (!std::isfinite(phi) || phi < 0.f || phi > 1.f) {
+    set_err("guide_rescale: phi must be in [0, 1]");
+    return LLIE_ERR_ARG;
+  }
+  const int64_t need = llie_guide_rescale_scratch_bytes(batch, per_sample);
+  if (need < 0) {
+    set_err("guide_rescale: more than 2^31 - 1 workgroups");
+    return LLIE_ERR_ARG;
+  }
+  if (scratch_bytes < need) {
+    set_err("guide_rescale: scratch of %lld bytes needed, %lld given", (long long)need, (long long)scratch_bytes);
+    return LLIE_ERR_WORKSPACE;
+  }
+  return kerr("guide_rescale", launch_guide_rescale(out_cond, out_uncond, w_rows, w, phi, out, factor, scratch, batch, per_sample, hs(stream)),
+              LLIE_ERR_ARG, nullptr);
+}
+
 int llie_guidance_pair(const float* latents, const float* cond, float* latents2, float* cond2, int batch, int64_t per_sample,
                        llie_stream stream) {
   return kerr("guidance_pair", launch_guidance_pair(latents, cond, latents2, cond2, batch, per_sample, hs(stream)), LLIE_ERR_ARG,

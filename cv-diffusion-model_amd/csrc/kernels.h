@@ -706,6 +706,26 @@ hipError_t launch_guide(const float* out_cond, const float* out_uncond, const fl
                         hipStream_t s);
 hipError_t launch_guidance_pair(const float* latents, const float* cond, float* latents2, float* cond2, int batch, int64_t per, hipStream_t s);
 hipError_t launch_cond_dropout(const float* in, const float* u, float p, float* out, int batch, int64_t per, hipStream_t s);
+// Guidance rescale (Lin et al. 2024, section 3.4): the guided output of a row scaled towards the standard deviation of its
+// conditional output.  For row b, n = per, g = o_u + w (o_c - o_u) as launch_guide rounds it:
+//   S1c = sum o_c, S2c = sum o_c^2, S1g = sum g, S2g = sum g^2 in double (each value widened first, every square exact)
+//   var_c = max(S2c - S1c^2 / n, 0), var_g likewise;  r32 = (float)sqrt(var_c / var_g), 1 where var_g is not > 0 or r32 not finite
+//   f_b = fl(fl(phi r32) + fl(1 - phi));  out = fl(f_b g);  factor[b] = f_b (optional)
+// A row is kGuideRescaleChunk-element chunks, one workgroup each; no atomics; the order of every sum depends on n alone.
+// phi == 0 launches guide_kernel alone (factor = 1): launch_guide's bits.
+constexpr int64_t kGuideRescaleChunk = 4096;
+inline int64_t guide_rescale_chunks(int64_t per) { return per < 1 ? 0 : (per + kGuideRescaleChunk - 1) / kGuideRescaleChunk; }
+// batch * 4 * chunks doubles (the per-workgroup partials) + batch floats (the factors), rounded up to 8 bytes; -1 for batch < 1,
+// per < 1 or more than 2^31 - 1 workgroups in a launch
+inline long long guide_rescale_scratch_bytes(int batch, int64_t per) {
+  const int64_t chunks = guide_rescale_chunks(per);
+  if (batch < 1 || chunks < 1 || (int64_t)batch * chunks > (int64_t)INT32_MAX || (per + 255) / 256 > (int64_t)INT32_MAX) return -1;
+  return (long long)batch * chunks * 32 + (((long long)batch * 4 + 7) & ~7LL);
+}
+// as launch_guide, and hipErrorInvalidValue for a null or not 8-byte aligned scratch, a misaligned factor, a phi that is not finite
+// or outside [0, 1], and a shape guide_rescale_scratch_bytes refuses
+hipError_t launch_guide_rescale(const float* out_cond, const float* out_uncond, const float* w_rows, float w, float phi, float* out,
+                                float* factor, void* scratch, int batch, int64_t per, hipStream_t s);
 
 // (10c) the DPM-Solver++ 2M step (solver.hip): fp32 [n] tensors.  llie_dpm_coef as the kernel takes it.
 struct DpmCoef { float sa, sb, kx, k0, k1; int vpred, order, is_last; };

@@ -14,8 +14,12 @@ distil the guided teacher into a student that needs one forward -- and they shar
                      [0, 1], compared in fp32.  A select, not a multiply: an inf or NaN in a dropped row gives 0.  p = 0 drops
                      nothing, p = 1 everything.
 
-The device runs the same fp32 operations (llie_guide, llie_guidance_pair, llie_cond_dropout), so these functions give its bits;
-its tests compare against them.  Nothing here needs a GPU or the engine's library.
+  guidance rescale   (Lin et al. 2024, section 3.4) the guided output of row b times f_b = phi r_b + (1 - phi), r_b the ratio of the
+                     standard deviations of o_c[b] and o[b] over the whole row, from float64 moments: `guide_rescale_host` is the
+                     definition, `guide_rescale_array` the fp32 twin.  phi = 0 is the guided output, phi = 1 matches the deviations.
+
+The device runs the same fp32 operations (llie_guide, llie_guidance_pair, llie_cond_dropout, llie_guide_rescale given its factor),
+so these functions give its bits; its tests compare against them.  Nothing here needs a GPU or the engine's library.
 """
 from __future__ import annotations
 
@@ -44,11 +48,26 @@ def guidance_is_on(guidance_scale) -> bool:
     return w is not None and w != 1.0
 
 
-def guided_keyword(guidance_scale) -> dict:
-    """`guidance_scale=` as the keyword a pass-through hands on to `enhance` / `enhance_frame`: nothing when it is None, so the
-    unguided call is the call it always was.  ValueError for a scale that is not finite."""
+def check_guidance_rescale(guidance_rescale) -> float:
+    """`guidance_rescale=` (phi) of the sampling and distillation entries: None (off) or a number in [0, 1] -> its float, None
+    meaning 0.0.  ValueError otherwise (bool and NaN included)."""
+    if guidance_rescale is None:
+        return 0.0
+    if isinstance(guidance_rescale, bool) or not isinstance(guidance_rescale, (int, float, np.integer, np.floating)) \
+            or not 0.0 <= float(guidance_rescale) <= 1.0:
+        raise ValueError(f"guidance_rescale must be None or a number in [0, 1], got {guidance_rescale!r}")
+    return float(guidance_rescale)
+
+
+def guided_keyword(guidance_scale, guidance_rescale=None) -> dict:
+    """`guidance_scale=` (and `guidance_rescale=`) as the keywords a pass-through hands on to `enhance` / `enhance_frame`: nothing
+    for a None, so the unguided call is the call it always was.  ValueError for a scale that is not finite or a rescale outside
+    [0, 1]."""
     w = check_guidance_scale(guidance_scale)
-    return {} if w is None else {"guidance_scale": w}
+    kw = {} if w is None else {"guidance_scale": w}
+    if guidance_rescale is not None:
+        kw["guidance_rescale"] = check_guidance_rescale(guidance_rescale)
+    return kw
 
 
 def check_cond_dropout(p) -> float:
@@ -95,6 +114,55 @@ def guide_array(out_cond, out_uncond, w) -> np.ndarray:
         d = (c - u).astype(np.float32)
         p = (wv * d).astype(np.float32)
         return (u + p).astype(np.float32)
+
+
+def _rescale_ratio(c: np.ndarray, g: np.ndarray) -> np.ndarray:
+    """r_b = sqrt(var_c / var_g) of fp32 rows in float64, from the moments S1 = sum x, S2 = sum x^2 of the widened values:
+    var = max(S2 - S1^2 / n, 0), a NaN counting as 0.  1.0 where var_g is not > 0 or the fp32 rounding of r_b is not finite."""
+    b = c.shape[0]
+    c64, g64 = c.reshape(b, -1).astype(np.float64), g.reshape(b, -1).astype(np.float64)
+    n = np.float64(c64.shape[1])
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        dc = (c64 * c64).sum(axis=1) - c64.sum(axis=1) ** 2 / n
+        dg = (g64 * g64).sum(axis=1) - g64.sum(axis=1) ** 2 / n
+        var_c, var_g = np.where(dc > 0, dc, 0.0), np.where(dg > 0, dg, 0.0)
+        r = np.sqrt(var_c / np.where(var_g > 0, var_g, 1.0))
+        ok = (var_g > 0) & np.isfinite(r.astype(np.float32))
+    return np.where(ok, r, 1.0)
+
+
+def guide_rescale_host(out_cond, out_uncond, w, phi) -> Tuple[np.ndarray, np.ndarray]:
+    """Guidance rescale (Lin et al. 2024, section 3.4), the definition: (out, factor) in float64 for fp32 rows out_cond /
+    out_uncond [B, ...].  g = `guide_array` (its three fp32 roundings), widened; over each whole row, in float64,
+    r_b = sqrt(var_c / var_g) from the moments (`_rescale_ratio`: 1 for a constant row and for one element); phi is taken as its
+    fp32 value; factor_b = phi r_b + (1 - phi); out = factor_b g.  phi = 1 gives row b the standard deviation of out_cond[b],
+    phi = 0 returns g.  The usual formulation (the std over dims 1.., g std_c / std_g, then the phi-blend) agrees to 1e-10."""
+    p = np.float64(np.float32(check_guidance_rescale(phi)))
+    c = _rows(out_cond, "out_cond")
+    g = guide_array(c, out_uncond, w)
+    factor = p * _rescale_ratio(c, g) + (1.0 - p)
+    return factor.reshape((-1,) + (1,) * (g.ndim - 1)) * g.astype(np.float64), factor
+
+
+def guide_rescale_array(out_cond, out_uncond, w, phi, factor=None) -> np.ndarray:
+    """The fp32 twin of llie_guide_rescale: out = fl(f_b g), g = `guide_array`.  With the device's `factor` [B] supplied these are
+    the kernel's output bits; without it f_b = fl(fl(phi r32) + fl(1 - phi)), r32 the ratio of `guide_rescale_host` rounded once to
+    fp32 -- within rounding of the device's, whose sums run in another order."""
+    f = np.float32
+    p = f(check_guidance_rescale(phi))
+    c = _rows(out_cond, "out_cond")
+    g = guide_array(c, out_uncond, w)
+    if factor is None:
+        r32 = _rescale_ratio(c, g).astype(f)
+        fb = ((p * r32).astype(f) + f(f(1) - p)).astype(f) if p != 0 else np.ones(c.shape[0], dtype=f)
+    else:
+        fb = np.asarray(factor, dtype=f)
+        if fb.shape != (c.shape[0],):
+            raise ValueError(f"factor must be [{c.shape[0]}], got {fb.shape}")
+    if p == 0 and factor is None:
+        return g
+    with np.errstate(invalid="ignore", over="ignore"):
+        return (fb.reshape((-1,) + (1,) * (g.ndim - 1)) * g).astype(f)
 
 
 def cond_dropout_array(cond, u, p) -> np.ndarray:
@@ -159,15 +227,17 @@ def scheduler_step_array(model_output, sample, noise, coef) -> np.ndarray:
         return ((sap * x0).astype(f) + (sbp * nz).astype(f)).astype(f)
 
 
-def guided_enhance_host(unet_fn: Callable, low, noise, timesteps: Sequence[int], coefs: Sequence, w) -> Dict[str, object]:
+def guided_enhance_host(unet_fn: Callable, low, noise, timesteps: Sequence[int], coefs: Sequence, w, rescale=None) -> Dict[str, object]:
     """The guided loop of `enhance(..., guidance_scale=w)` on the host, the denoiser passed in, written like
     `ddim.ddim_enhance_host`: unet_fn(latents fp32 [B,3,H,W], cond fp32 [B,3,H,W], t) -> the network output [B,3,H,W].
     `low` [B,3,H,W]; `noise` [draws,B,3,H,W] in `enhance`'s order (the initial latents, then one draw per non-final LCM step; DDIM
     reads only the first); `timesteps` and `coefs` (one `N.StepCoef` each) are the schedule.  Per step: the conditional output on
     `low`, the unconditional one on the null condition, `guide_array`, `scheduler_step_array` -- all fp32, the device's operations.
     `w` None runs the unguided loop (one call per step, no combination); any finite `w`, 1.0 included, runs the guided one.
+    `rescale` (phi; None or 0: off, the loop above) replaces `guide_array` by `guide_rescale_array` in the guided loop.
     -> {"enhanced" (clamped), "intermediate" (latents after each step), "noise_pred" (the guided output of each step), "timesteps"}."""
     wv = check_guidance_scale(w)
+    phi = check_guidance_rescale(rescale)
     low = np.ascontiguousarray(np.asarray(low, dtype=np.float32))
     noise = np.asarray(noise, dtype=np.float32)
     ts = [int(t) for t in timesteps]
@@ -180,7 +250,9 @@ def guided_enhance_host(unet_fn: Callable, low, noise, timesteps: Sequence[int],
     inter, preds = [], []
     for i, (t, coef) in enumerate(zip(ts, coefs)):
         out = np.asarray(unet_fn(x, low, t), dtype=np.float32)
-        if wv is not None:
+        if wv is not None and phi > 0:
+            out = guide_rescale_array(out, np.asarray(unet_fn(x, null, t), dtype=np.float32), wv, phi)
+        elif wv is not None:
             out = guide_array(out, np.asarray(unet_fn(x, null, t), dtype=np.float32), wv)
         draw = None
         if not _coef_fields(coef)[4] and not _coef_fields(coef)[7]:
@@ -230,6 +302,58 @@ def guide_device(out_cond, out_uncond, w, out=None):
     with torch.cuda.device(dev):
         N.check(N.lib().llie_guide(out_cond.data_ptr(), out_uncond.data_ptr(), w_rows, ws, out.data_ptr(), b, per,
                                    torch.cuda.current_stream(dev).cuda_stream), "guide")
+    return out
+
+
+_rescale_scratch: Dict[tuple, object] = {}  # (device type, index) -> the scratch tensor of guide_rescale_device, grown on demand
+
+
+def guide_rescale_scratch(batch: int, per_sample: int, device):
+    """A uint8 device tensor of llie_guide_rescale_scratch_bytes(batch, per_sample) bytes or more, kept and reused per device
+    (launches on one stream use it in turn).  ValueError for a shape the kernel refuses."""
+    import torch
+    from . import _native as N
+    need = int(N.lib().llie_guide_rescale_scratch_bytes(int(batch), int(per_sample)))
+    if need < 0:
+        raise ValueError(f"guide_rescale: batch {batch} x per_sample {per_sample} is outside the kernel's contract")
+    key = (device.type, device.index)
+    buf = _rescale_scratch.get(key)
+    if buf is None or buf.numel() < need:
+        buf = _rescale_scratch[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    return buf
+
+
+def guide_rescale_device(out_cond, out_uncond, w, phi, out=None, factor=None):
+    """llie_guide_rescale on contiguous fp32 device tensors [B, ...] of one shape: `w` as in `guide_device`, `phi` in [0, 1];
+    `out` (default: a new tensor) may be `out_cond` or `out_uncond`; `factor` (optional) a contiguous fp32 [B] device tensor that
+    receives f_b.  The scratch tensor is the module's, reused from call to call.  At most three launches, no synchronisation."""
+    import torch
+    from . import _native as N
+    pv = check_guidance_rescale(phi)
+    b, per, dev = _device_rows((out_cond, out_uncond), "guide_rescale")
+    if out_uncond.shape != out_cond.shape:
+        raise ValueError(f"out_cond and out_uncond must have one shape, got {tuple(out_cond.shape)} and {tuple(out_uncond.shape)}")
+    if out is None:
+        out = torch.empty_like(out_cond)
+    elif out.shape != out_cond.shape or _device_rows((out,), "guide_rescale")[2] != dev:
+        raise ValueError("guide_rescale: out must be shaped like out_cond, on its device")
+    if factor is not None and (factor.dtype != torch.float32 or tuple(factor.shape) != (b,) or factor.device != dev
+                               or not factor.is_contiguous()):
+        raise ValueError(f"factor must be a contiguous fp32 [{b}] tensor on the outputs' device")
+    if isinstance(w, torch.Tensor):
+        if w.dtype != torch.float32 or tuple(w.shape) != (b,) or w.device != dev or not w.is_contiguous():
+            raise ValueError(f"a per-row w must be a contiguous fp32 [{b}] tensor on the outputs' device")
+        w_rows, ws = w.data_ptr(), 0.0
+    else:
+        ws = check_guidance_scale(w)
+        if ws is None:
+            raise ValueError("guide_rescale: w must be a finite number or a device tensor")
+        w_rows = None
+    scratch = guide_rescale_scratch(b, per, dev)
+    with torch.cuda.device(dev):
+        N.check(N.lib().llie_guide_rescale(out_cond.data_ptr(), out_uncond.data_ptr(), w_rows, ws, pv, out.data_ptr(),
+                                           factor.data_ptr() if factor is not None else None, scratch.data_ptr(), scratch.numel(), b, per,
+                                           torch.cuda.current_stream(dev).cuda_stream), "guide_rescale")
     return out
 
 

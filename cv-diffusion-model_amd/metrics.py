@@ -343,7 +343,7 @@ def _summary(names, triples: np.ndarray, loss: Optional[float]) -> Dict[str, obj
 @torch.no_grad()
 def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[int] = None, seed: int = 0, loss: bool = True,
              weights: Optional[Sequence[torch.Tensor]] = None, sampler: str = "lcm",
-             guidance_scale: Optional[float] = None) -> Dict[str, object]:
+             guidance_scale: Optional[float] = None, guidance_rescale: Optional[float] = None) -> Dict[str, object]:
     """PSNR / SSIM / MSE of `model.enhance` against the normal-light images of `loader` (normally a "val" DevicePairLoader:
     centre crops in file order, last partial batch kept), and the validation loss of the reference's `LowLightTrainer.validate`.
 
@@ -363,8 +363,8 @@ def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[i
       A rectangular loader (`crop_size` = (H, W), H != W; frame-size training) is scored through `model.enhance_frame` and the
       loss runs at that shape: the same recipe with every [.., 3, S, S] draw [.., 3, H, W].  A square loader must crop
       model.image_size, as before.
-      guidance_scale=w scores `model.enhance(..., guidance_scale=w)` (classifier-free guidance; None: off); the draws and the
-      loss are unchanged.
+      guidance_scale=w scores `model.enhance(..., guidance_scale=w)` (classifier-free guidance; None: off) and
+      guidance_rescale=phi adds `guidance_rescale=phi` to that call; the draws and the loss are unchanged.
       The loss is always this flat, unweighted MSE: a trainer's `snr_gamma` (Min-SNR-gamma weighting, snrloss.py) does not reach
       it, so runs with and without that flag stay comparable.
 
@@ -373,7 +373,7 @@ def evaluate(model, loader: DevicePairLoader, *, num_inference_steps: Optional[i
     stays on the device until one copy at the end.  `weights=` (e.g. FusedAdamW.ema_tensors(), in model.parameters() order) is
     copied into the parameters for the call and the original values are restored afterwards, also when the call raises."""
     check_sampler(sampler)
-    guided = _guided_kw(guidance_scale)
+    guided = _guided_kw(guidance_scale, guidance_rescale)
     if not isinstance(loader, DevicePairLoader):
         raise ValueError(f"evaluate expects a DevicePairLoader, got {type(loader).__name__}")
     dev = loader.store.device
@@ -415,7 +415,8 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
                              overlap: Optional[int] = None, tile_batch: int = 32,
                              weights: Optional[Sequence[torch.Tensor]] = None, mode: str = "tiled",
                              sync: str = "none", sampler: str = "lcm", tile=None,
-                             max_tile_pixels: Optional[int] = None, guidance_scale: Optional[float] = None) -> Dict[str, object]:
+                             max_tile_pixels: Optional[int] = None, guidance_scale: Optional[float] = None,
+                             guidance_rescale: Optional[float] = None) -> Dict[str, object]:
     """PSNR / SSIM / MSE at the images' own resolution: every low-light frame of the paired `store` (any sizes >= 11 x 11) goes
     through `enhance_tiled` and is scored against its normal-light frame on the bytes (x = byte / 255).
 
@@ -434,7 +435,8 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
     [steps, 3, max(H, TH), max(W, TW)], and with tile="auto" TH x TW is the tile `auto_tile_plan` gives that image.
     sampler="ddim" passes through to `enhance_tiled` / `enhance_frame_u8` in every mode; steps = 1 in the draws above.
     sampler="dpmpp_2m" does the same, except that `enhance_tiled` refuses it with sync="latents".
-    guidance_scale= passes through the same way (refused by `enhance_tiled` with sync="latents")."""
+    guidance_scale= passes through the same way (refused by `enhance_tiled` with sync="latents"), and guidance_rescale= with it
+    (with tiles the rescale's statistic is per tile: `enhance_tiled`)."""
     if mode not in ("tiled", "frame"):
         raise ValueError(f'mode must be "tiled" or "frame", got {mode!r}')
     if mode == "frame" and (overlap is not None or tile_batch != 32 or sync != "none" or tile is not None or max_tile_pixels is not None):
@@ -444,7 +446,7 @@ def evaluate_full_resolution(model, store: DeviceFrameStore, *, num_inference_st
     check_sampler(sampler)
     if sync == "latents" and sampler == "dpmpp_2m":
         raise ValueError('evaluate_full_resolution(sync="latents", sampler="dpmpp_2m") is not provided: enhance_tiled refuses the pair')
-    guided = _guided_kw(guidance_scale)
+    guided = _guided_kw(guidance_scale, guidance_rescale)
     if not isinstance(store, DeviceFrameStore) or not store.paired:
         raise ValueError("evaluate_full_resolution expects a paired DeviceFrameStore")
     dev = store.device

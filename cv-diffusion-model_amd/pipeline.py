@@ -147,6 +147,7 @@ class LowLightDiffusion(nn.Module):
                 generator: Optional[torch.Generator] = None, return_intermediate: bool = False, *,
                 noise: Optional[Union[torch.Tensor, Sequence[torch.Tensor]]] = None,
                 return_noise_pred: bool = False, sampler: str = "lcm", guidance_scale: Optional[float] = None,
+                guidance_rescale: Optional[float] = None,
                 _passes: Optional[int] = None) -> Union[torch.Tensor, LowLightDiffusionOutput]:
         """low_light [B,3,S,S] in [-1,1] -> enhanced [B,3,S,S].
 
@@ -176,9 +177,18 @@ class LowLightDiffusion(nn.Module):
         clamp; nothing in it allocates, waits for the device or copies from the host.  Where the engine refuses 2B rows (llie_frame_shape_ok, workspace) the two outputs come from two
         B-row passes instead, with the same bits (every kernel is bitwise batch-invariant).  Draws, `noise=` shapes,
         `generator`, `return_intermediate` and `sampler` are those of the unguided call; `return_noise_pred` returns the guided
-        output of each step.  A non-finite scale is a ValueError."""
+        output of each step.  A non-finite scale is a ValueError.
+
+        `guidance_rescale=phi` (extension; Lin et al. 2024, section 3.4; `guidance.guide_rescale_host` has the definition): guidance
+        at a useful scale inflates the standard deviation of the guided output, which the zero-terminal-SNR table hands to x0 as
+        over-exposure.  With phi in (0, 1] the guided output of each image and step is scaled by phi std(o_c) / std(o) + (1 - phi),
+        the standard deviations taken over the image's whole C H W: llie_guide_rescale (moments, factor, apply) takes llie_guide's
+        place in the loop, two more launches per step; `return_noise_pred` returns the rescaled output.  0.7 is the paper's value;
+        None and 0.0 are the guided loop above, bit for bit.  With guidance off the rescale is the identity by definition (o = o_c),
+        so the unguided path runs unchanged; a phi outside [0, 1] is a ValueError either way."""
         check_sampler(sampler)
         G.check_guidance_scale(guidance_scale)
+        G.check_guidance_rescale(guidance_rescale)
         device = low_light.device
         if device.type != "cuda":
             raise RuntimeError("LowLightDiffusion.enhance runs only on a HIP device; there is no CPU fallback")
@@ -187,13 +197,14 @@ class LowLightDiffusion(nn.Module):
             raise ValueError(f"low_light must be [B,3,{s},{s}] (latents are allocated at image_size, "
                              f"low_light_diffusion.py:208-210); got {tuple(low_light.shape)}")
         return self._enhance_at(low_light, None, num_inference_steps, generator, return_intermediate, noise, return_noise_pred, sampler,
-                                guidance_scale, _passes)
+                                guidance_scale, _passes, guidance_rescale)
 
     @torch.no_grad()
     def enhance_frame(self, low_light: torch.Tensor, num_inference_steps: Optional[int] = None,
                       generator: Optional[torch.Generator] = None, return_intermediate: bool = False, *,
                       noise: Optional[Union[torch.Tensor, Sequence[torch.Tensor]]] = None,
                       return_noise_pred: bool = False, sampler: str = "lcm", guidance_scale: Optional[float] = None,
+                      guidance_rescale: Optional[float] = None,
                       _passes: Optional[int] = None) -> Union[torch.Tensor, LowLightDiffusionOutput]:
         """Frame mode (extension): low_light [B,3,H,W] in [-1,1] -> enhanced [B,3,H,W], the whole loop (`sampler`: as in
         `enhance`) at the frame's own size.  The module tree is the one `image_size` fixed (attention placement, state_dict); the
@@ -203,17 +214,18 @@ class LowLightDiffusion(nn.Module):
         ValueError naming it; frames past the size cap go through `enhance_tiled`.
 
         Semantics, noise order and outputs are `enhance`'s, with [steps,B,3,H,W] noise ([1,B,3,H,W] for DDIM); on an S x S input the
-        result is `enhance`'s, bit for bit.  `guidance_scale`: as in `enhance`; a frame whose 2B rows break the frame rule runs the
-        two-pass form.  Inference only."""
+        result is `enhance`'s, bit for bit.  `guidance_scale` and `guidance_rescale`: as in `enhance` (the rescale's statistic is
+        over the whole frame); a frame whose 2B rows break the frame rule runs the two-pass form.  Inference only."""
         check_sampler(sampler)
         G.check_guidance_scale(guidance_scale)
+        G.check_guidance_rescale(guidance_rescale)
         device = low_light.device
         if device.type != "cuda":
             raise RuntimeError("LowLightDiffusion.enhance_frame runs only on a HIP device; there is no CPU fallback")
         if low_light.dim() != 4 or low_light.shape[1] != 3:
             raise ValueError(f"low_light must be [B,3,H,W]; got {tuple(low_light.shape)}")
         return self._enhance_at(low_light, (int(low_light.shape[2]), int(low_light.shape[3])), num_inference_steps, generator,
-                                return_intermediate, noise, return_noise_pred, sampler, guidance_scale, _passes)
+                                return_intermediate, noise, return_noise_pred, sampler, guidance_scale, _passes, guidance_rescale)
 
     def ddim_schedule(self, num_inference_steps: Optional[int] = None) -> Tuple[List[int], List[N.StepCoef]]:
         """(timesteps, one N.StepCoef each) of the DDIM loop of `num_inference_steps` steps (default: self.num_inference_steps).
@@ -242,10 +254,11 @@ class LowLightDiffusion(nn.Module):
         return ts, [N.DpmCoef(r.sqrt_alpha_t, r.sqrt_beta_t, r.k_x, r.k_0, r.k_1, r.v_prediction, r.order, r.is_last) for r in recs]
 
     def _enhance_at(self, low_light, frame, num_inference_steps, generator, return_intermediate, noise, return_noise_pred,
-                    sampler="lcm", guidance_scale=None, passes=None):
+                    sampler="lcm", guidance_scale=None, passes=None, guidance_rescale=None):
         """The loop of `enhance` (frame is None: image_size, llie_enhance) and `enhance_frame` (frame = (H, W), llie_enhance_hw);
         with a `guidance_scale` other than None / 1.0, the host-driven guided loop (`_guided_loop`) after the same setup."""
         guided = G.guidance_is_on(guidance_scale)
+        phi = G.check_guidance_rescale(guidance_rescale)
         if passes not in (None, 1, 2):
             raise ValueError(f"_passes must be None, 1 or 2, got {passes!r}")
         device = low_light.device
@@ -299,7 +312,7 @@ class LowLightDiffusion(nn.Module):
         inter = torch.empty(steps, b, 3, hh, ww, dtype=torch.float32, device=device) if return_intermediate else None
         preds = torch.empty(steps, b, 3, hh, ww, dtype=torch.float32, device=device) if return_noise_pred else None
         if guided:
-            self._guided_loop(low, noise_t, ts, coefs, float(guidance_scale), passes, frame is not None, enhanced, inter, preds)
+            self._guided_loop(low, noise_t, ts, coefs, float(guidance_scale), passes, frame is not None, enhanced, inter, preds, phi)
             return self._enhance_result(enhanced, inter, preds, steps, return_intermediate or return_noise_pred)
         h, ws, nbytes = prepared if prepared is not None else self.unet._prepare(b, device, enhance_steps=stage_steps)
         outs = (enhanced.data_ptr(), inter.data_ptr() if inter is not None else None, preds.data_ptr() if preds is not None else None)
@@ -350,9 +363,9 @@ class LowLightDiffusion(nn.Module):
             return 2
         return 1
 
-    def _guided_loop(self, low, noise_t, ts, coefs, w: float, passes: int, frames: bool, enhanced, inter, preds) -> None:
+    def _guided_loop(self, low, noise_t, ts, coefs, w: float, passes: int, frames: bool, enhanced, inter, preds, phi: float = 0.0) -> None:
         """The guided loop after `_enhance_at`'s setup (the docstring of `enhance` has the steps).  Buffers are allocated before
-        the loop; inside it there are only launches on the current stream."""
+        the loop; inside it there are only launches on the current stream.  `phi` > 0: llie_guide_rescale in llie_guide's place."""
         device = low.device
         b = low.shape[0]
         rows = 2 * b if passes == 1 else b
@@ -377,6 +390,9 @@ class LowLightDiffusion(nn.Module):
         hist = torch.empty_like(low) if dpm else None  # DPM-Solver++: the previous step's x0
         x = noise_t[0]
         n = low.numel()
+        if phi > 0:
+            scratch = G.guide_rescale_scratch(b, n // b, device)
+            factor = torch.empty(b, dtype=torch.float32, device=device)
         steps = len(ts)
         L = N.lib()
         with torch.cuda.device(device):
@@ -389,7 +405,11 @@ class LowLightDiffusion(nn.Module):
                     self.unet.forward_split(x, low, t_dev[i], uniform_t=True, out=o_c, frame=frames)
                     self.unet.forward_split(x, null, t_dev[i], uniform_t=True, out=o_u, frame=frames)
                 o = preds[i] if preds is not None else guided
-                N.check(L.llie_guide(o_c.data_ptr(), o_u.data_ptr(), None, w, o.data_ptr(), b, n // b, stream), "enhance (guided)")
+                if phi > 0:
+                    N.check(L.llie_guide_rescale(o_c.data_ptr(), o_u.data_ptr(), None, w, phi, o.data_ptr(), factor.data_ptr(),
+                                                 scratch.data_ptr(), scratch.numel(), b, n // b, stream), "enhance (guided)")
+                else:
+                    N.check(L.llie_guide(o_c.data_ptr(), o_u.data_ptr(), None, w, o.data_ptr(), b, n // b, stream), "enhance (guided)")
                 last = i == steps - 1
                 prev = inter[i] if inter is not None else lat[i & 1]
                 if dpm:
@@ -796,6 +816,10 @@ class LowLightLCMDistillation(nn.Module):
     w: the reference network has no such input, and `state_dict` parity wins.  With lo < hi the student therefore learns the
     mixture over the range; a degenerate range (w, w) -- the scale the student is meant to reproduce -- is the normal use.  With
     `guidance=False` nothing is drawn or launched that was not before: the same bits, the same generator state.
+    `guidance_rescale=phi` (keyword only, `guidance=True` only: a non-zero value without it is a ValueError) distils the teacher
+    with guidance rescale, as `enhance(guidance_rescale=phi)` samples it: llie_guide_rescale with the per-row scales takes
+    llie_guide's place, so a student distilled at (w, w) does not inherit the over-exposure of a large w.  0.0 (the default)
+    launches nothing that was not launched before.
 
     Prediction types (extension).  The teacher's output is read as `teacher.scheduler.config.prediction_type`, the student's and
     the EMA student's as `student.scheduler.config.prediction_type` (`teacher_prediction` / `student_prediction`); each is
@@ -817,12 +841,16 @@ class LowLightLCMDistillation(nn.Module):
     reproduced as is.  A v-prediction student's target is finite there (g0 = -out_ema), and so is its loss."""
 
     def __init__(self, teacher_model: LowLightDiffusion, student_model: LowLightDiffusion, num_ddim_timesteps: int = 50,
-                 guidance_scale_range: Tuple[float, float] = (3.0, 15.0), *, guidance: bool = False):
+                 guidance_scale_range: Tuple[float, float] = (3.0, 15.0), *, guidance: bool = False,
+                 guidance_rescale: float = 0.0):
         super().__init__()
         if not isinstance(guidance, bool):
             raise ValueError(f"guidance must be True or False, got {guidance!r}")
         if guidance:
             G.check_guidance_range(guidance_scale_range)
+            guidance_rescale = G.check_guidance_rescale(guidance_rescale)
+        elif guidance_rescale is not None and (isinstance(guidance_rescale, bool) or guidance_rescale != 0):
+            raise ValueError(f"guidance_rescale={guidance_rescale!r} needs LowLightLCMDistillation(guidance=True)")
         if teacher_model.image_size != student_model.image_size:
             raise ValueError(f"teacher and student must share image_size (got {teacher_model.image_size} and "
                              f"{student_model.image_size}): both denoise the same x_t")
@@ -835,6 +863,7 @@ class LowLightLCMDistillation(nn.Module):
         self.num_ddim_timesteps = num_ddim_timesteps
         self.guidance_scale_range = guidance_scale_range
         self.guidance = guidance
+        self.guidance_rescale = guidance_rescale if guidance else 0.0
         self.ema_student = copy.deepcopy(student_model)  # own parameters, own engine context (built lazily)
         self.ema_student.eval()
         self.ema_student.requires_grad_(False)
@@ -907,7 +936,8 @@ class LowLightLCMDistillation(nn.Module):
                        _passes: Optional[int] = None) -> torch.Tensor:
         """The teacher's output at (x_t, t), without gradients: its forward on `low` when `w` is None; else the guided output
         llie_guide(teacher(x_t, low), teacher(x_t, null), w), `w` device fp32 [B] -- one 2B-row pass, or two B-row passes where
-        the teacher's engine refuses 2B rows (`_passes` forces either form; the bits are the same)."""
+        the teacher's engine refuses 2B rows (`_passes` forces either form; the bits are the same).  With `guidance_rescale` > 0
+        llie_guide_rescale takes llie_guide's place."""
         with torch.no_grad():
             if w is None:
                 return self.teacher.unet.forward_split(x_t, low, t, frame=True)
@@ -922,6 +952,9 @@ class LowLightLCMDistillation(nn.Module):
             else:
                 o_c = self.teacher.unet.forward_split(x_t, low, t, frame=True)
                 o_u = self.teacher.unet.forward_split(x_t, torch.zeros_like(low), t, frame=True)
+            phi = getattr(self, "guidance_rescale", 0.0)
+            if phi > 0:
+                return G.guide_rescale_device(o_c, o_u, w, phi, out=o_c)
             return G.guide_device(o_c, o_u, w, out=o_c)
 
     def _check_inputs(self, low_light: torch.Tensor, normal_light: torch.Tensor) -> None:

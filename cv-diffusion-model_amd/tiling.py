@@ -435,10 +435,11 @@ def frame_store_device(x: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
 @torch.no_grad()
 def enhance_frame_u8(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int] = None, *,
                      generator: Optional[torch.Generator] = None, noise: Optional[torch.Tensor] = None,
-                     sampler: str = "lcm", guidance_scale: Optional[float] = None) -> torch.Tensor:
+                     sampler: str = "lcm", guidance_scale: Optional[float] = None,
+                     guidance_rescale: Optional[float] = None) -> torch.Tensor:
     """uint8 [H,W,3] on a HIP device -> enhanced uint8 [H,W,3] at the same resolution, by one run of the network at that size.
     `sampler` is `enhance`'s: with "ddim" and "dpmpp_2m" the noise canvas is [1,3,Hp,Wp], the initial latents.  `guidance_scale` is `enhance`'s
-    too (classifier-free guidance; None: off).
+    too (classifier-free guidance; None: off), and so is `guidance_rescale` (its statistic is taken over the padded frame).
 
     The image is loaded into a frame [3,Hp,Wp] (Hp / Wp = frame_pad(H / W): the next multiple of 8, at least 64) with its edge
     replicated into the padding, goes through `model.enhance_frame` at B = 1, and is cropped and denormalised back.  Noise is
@@ -452,7 +453,7 @@ def enhance_frame_u8(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[
     if not isinstance(rgb_u8, torch.Tensor):
         raise ValueError(f"enhance_frame_u8 expects a torch.Tensor, got {type(rgb_u8).__name__}")
     check_sampler(sampler)
-    guided = _guided_kw(guidance_scale)
+    guided = _guided_kw(guidance_scale, guidance_rescale)
     h, w = _check_image(rgb_u8, "enhance_frame_u8")
     _require_hip(rgb_u8, "enhance_frame_u8")
     hp, wp = frame_pad(h), frame_pad(w)
@@ -523,7 +524,8 @@ def resolve_tile_plan(model, size: Tuple[int, int], tile=None, overlap=None, max
 def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int] = None, *, overlap=None,
                   tile_batch: int = 32, generator: Optional[torch.Generator] = None,
                   noise: Optional[torch.Tensor] = None, sync: str = "none", return_canvas: bool = False, sampler: str = "lcm",
-                  tile=None, max_tile_pixels: Optional[int] = None, guidance_scale: Optional[float] = None):
+                  tile=None, max_tile_pixels: Optional[int] = None, guidance_scale: Optional[float] = None,
+                  guidance_rescale: Optional[float] = None):
     """uint8 [H,W,3] on a HIP device -> enhanced uint8 [H,W,3] at the same resolution.
 
     The image is cut into S x S tiles (S = model.image_size) overlapping by `overlap` pixels (default S // 8, at most S // 2);
@@ -558,14 +560,17 @@ def enhance_tiled(model, rgb_u8: torch.Tensor, num_inference_steps: Optional[int
 
     guidance_scale=w (classifier-free guidance, `enhance`'s keyword) passes through to every tile's `enhance` / `enhance_frame`
     call with sync="none"; with sync="latents" a scale other than None / 1.0 is a ValueError (the shared-canvas loop has no
-    guided form)."""
+    guided form).  `guidance_rescale=phi` passes through with it.  The rescale's standard deviations are those of one network
+    call, so with tiles they are taken per tile, not over the image: two tiles of one image may be scaled by different factors
+    (the blend over the overlaps hides the seam, as it does for the tiles' separate GroupNorm statistics); an image that fits one
+    frame has one statistic."""
     if not isinstance(rgb_u8, torch.Tensor):
         raise ValueError(f"enhance_tiled expects a torch.Tensor, got {type(rgb_u8).__name__}")
     if sync not in ("none", "latents"):
         raise ValueError(f'sync must be "none" or "latents", got {sync!r}')
     ddim = check_sampler(sampler) == "ddim"
     dpm = sampler == "dpmpp_2m"
-    guided = _guided_kw(guidance_scale)
+    guided = _guided_kw(guidance_scale, guidance_rescale)
     if sync == "latents" and dpm:
         raise ValueError('enhance_tiled(sync="latents", sampler="dpmpp_2m") is not provided: the shared-canvas step keeps no history of '
                          'x0; use sync="none", or sampler="ddim"')

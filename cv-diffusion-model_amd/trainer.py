@@ -28,7 +28,7 @@ from . import _native as N
 from . import hostio
 from .data import create_device_dataloaders
 from .ddim import check_sampler
-from .guidance import check_cond_dropout, check_guidance_scale, guided_keyword
+from .guidance import check_cond_dropout, check_guidance_rescale, check_guidance_scale, guided_keyword
 from .snrloss import check_snr_gamma
 from .metrics import _require_hip, _steps_of, _swapped_weights, evaluate
 from .pipeline import LowLightDiffusion
@@ -239,6 +239,7 @@ class _EpochLoop:
     val_sampler = "lcm"
     val_steps: Optional[int] = None
     val_guidance_scale: Optional[float] = None
+    val_guidance_rescale: Optional[float] = None
 
     # ------------------------------------------------------------------ construction
     def _init_shapes(self, config: Optional[TrainingConfig], train_loader, val_loader, crop_size, accumulate) -> None:
@@ -389,7 +390,8 @@ class _EpochLoop:
         (`val_steps` replaces the 4; with val_sampler="ddim" or "dpmpp_2m" steps = 1, the initial latents, and the loop is that
         sampler's).
         With a rectangular `crop_size` the images are [n, 3, H, W] and the loop is `enhance_frame`'s.  `val_guidance_scale`
-        is passed on as `guidance_scale=` (classifier-free guidance); the draws do not depend on it.
+        is passed on as `guidance_scale=` (classifier-free guidance) and `val_guidance_rescale` as `guidance_rescale=`; the draws
+        do not depend on them.
         The loader's epoch counter, the parameters and the network's mode are as before afterwards."""
         cfg, dev = self.config, self.device
         loader = self.val_loader or self.train_loader
@@ -408,7 +410,8 @@ class _EpochLoop:
                 g = torch.Generator(device=dev).manual_seed(sample_draw_seed(cfg.seed, epoch))
                 noise = torch.randn(steps, low.shape[0], 3, low.shape[2], low.shape[3], generator=g, device=dev)
                 enhance = net.enhance_frame if self.crop_size[0] != self.crop_size[1] else net.enhance
-                enhanced = enhance(low, nsteps, noise=noise, sampler=self.val_sampler, **guided_keyword(self.val_guidance_scale))
+                enhanced = enhance(low, nsteps, noise=noise, sampler=self.val_sampler,
+                                   **guided_keyword(self.val_guidance_scale, self.val_guidance_rescale))
                 grid = comparison_grid(low, enhanced, normal).cpu().numpy()  # the one device-to-host copy
         finally:
             net.train(mode)
@@ -453,7 +456,8 @@ class LowLightTrainer(_EpochLoop):
     checkpoints).  `cond_dropout=p` in [0, 1] goes to TrainStep: with p > 0 each sample's condition is replaced by the null
     condition with probability p, and `train_epoch`'s draw recipe gains a third draw per batch (its docstring).
     `val_guidance_scale=w` makes `validate` and `generate_samples` sample with `guidance_scale=w` (None: unguided; the
-    validation loss is not affected).
+    validation loss is not affected); `val_guidance_rescale=phi` in [0, 1] adds `guidance_rescale=phi` to those calls (None:
+    nothing is handed on).
 
     `crop_size=(H, W)` (extension; a keyword like the x0 weights, neither a TrainingConfig field nor stored in checkpoints: a caller
     that resumes passes it again) trains at a frame's own shape instead of config.image_size x config.image_size: the loaders must
@@ -471,12 +475,14 @@ class LowLightTrainer(_EpochLoop):
     def __init__(self, model: LowLightDiffusion, train_loader, val_loader=None, config: Optional[TrainingConfig] = None, *,
                  x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0, val_sampler: str = "lcm", val_steps: Optional[int] = None,
                  crop_size: Optional[Tuple[int, int]] = None, accumulate: int = 1, cond_dropout: float = 0.0,
-                 val_guidance_scale: Optional[float] = None, snr_gamma: Optional[float] = None):
+                 val_guidance_scale: Optional[float] = None, snr_gamma: Optional[float] = None,
+                 val_guidance_rescale: Optional[float] = None):
         self.snr_gamma = check_snr_gamma(snr_gamma)
         self._init_shapes(config, train_loader, val_loader, crop_size, accumulate)
         cfg = self.config
         self.cond_dropout = check_cond_dropout(cond_dropout)
         self.val_guidance_scale = check_guidance_scale(val_guidance_scale)
+        self.val_guidance_rescale = None if val_guidance_rescale is None else check_guidance_rescale(val_guidance_rescale)
         self.val_sampler = check_sampler(val_sampler)
         if val_steps is not None and (isinstance(val_steps, bool) or int(val_steps) != val_steps or val_steps < 1):
             raise ValueError(f"val_steps must be a positive integer or None, got {val_steps!r}")
@@ -583,7 +589,7 @@ class LowLightTrainer(_EpochLoop):
         try:
             res = evaluate(self.model, self.val_loader, num_inference_steps=self._val_steps(self.config.num_inference_steps),
                            seed=self.config.seed, weights=self._ema_weights(), sampler=self.val_sampler,
-                           **guided_keyword(self.val_guidance_scale))
+                           **guided_keyword(self.val_guidance_scale, self.val_guidance_rescale))
         finally:
             self.model.train(mode)
         self.last_validation = res
@@ -633,11 +639,11 @@ def train_model(train_data_dir: str, val_data_dir: Optional[str] = None, config:
                 device="cuda", *, x0_ssim_weight: float = 0.0, x0_l1_weight: float = 0.0, val_sampler: str = "lcm",
                 val_steps: Optional[int] = None, crop_size: Optional[Tuple[int, int]] = None, accumulate: int = 1,
                 cond_dropout: float = 0.0, val_guidance_scale: Optional[float] = None,
-                snr_gamma: Optional[float] = None) -> LowLightTrainer:
+                snr_gamma: Optional[float] = None, val_guidance_rescale: Optional[float] = None) -> LowLightTrainer:
     """Training entry point (trainer.py:459-496): loaders from the folders (create_device_dataloaders), a fresh model, a trainer,
     `train()`; returns the trainer.  `x0_ssim_weight` / `x0_l1_weight` / `val_sampler` / `val_steps` / `crop_size`: as
     LowLightTrainer's (with `crop_size=(H, W)` the loaders crop H x W; the model is still built at config.image_size);
-    `accumulate` / `cond_dropout` / `val_guidance_scale` / `snr_gamma`: LowLightTrainer's."""
+    `accumulate` / `cond_dropout` / `val_guidance_scale` / `val_guidance_rescale` / `snr_gamma`: LowLightTrainer's."""
     config = config or TrainingConfig()
     train_loader, val_loader = create_device_dataloaders(train_root=train_data_dir, val_root=val_data_dir, batch_size=config.batch_size,
                                                          image_size=config.image_size if crop_size is None else tuple(crop_size),
@@ -648,6 +654,6 @@ def train_model(train_data_dir: str, val_data_dir: Optional[str] = None, config:
     trainer = LowLightTrainer(model=model, train_loader=train_loader, val_loader=val_loader, config=config,
                               x0_ssim_weight=x0_ssim_weight, x0_l1_weight=x0_l1_weight, val_sampler=val_sampler, val_steps=val_steps,
                               crop_size=crop_size, accumulate=accumulate, cond_dropout=cond_dropout,
-                              val_guidance_scale=val_guidance_scale, snr_gamma=snr_gamma)
+                              val_guidance_scale=val_guidance_scale, snr_gamma=snr_gamma, val_guidance_rescale=val_guidance_rescale)
     trainer.train()
     return trainer

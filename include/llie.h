@@ -353,7 +353,33 @@ int llie_consistency_loss_ex(const float* x_t, const float* x_next, const float*
  * 16-byte accesses where the pointers and per_sample allow (all pointers 16-byte aligned and per_sample % 4 == 0, or one row),
  * scalar ones for the tail and otherwise; the bits do not depend on it.  LLIE_ERR_ARG before any launch for a null pointer (`w_rows`
  * excepted), a pointer that is not 4-byte aligned, batch <= 0, per_sample <= 0, a non-finite `w` (when it is used) or `p`, and a
- * `p` outside [0, 1]. */
+ * `p` outside [0, 1].
+ *
+ * Guidance rescale (Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed", section 3.4): guidance at a useful
+ * scale inflates the standard deviation of the guided output, which a zero-terminal-SNR table hands straight to x0;
+ * llie_guide_rescale scales the guided output of each row back towards the standard deviation of its conditional output.  For row b
+ * of [batch, n] tensors, n = per_sample (the whole C H W of an image), phi an fp32 value in [0, 1]:
+ *   g     = out_uncond + w (out_cond - out_uncond), llie_guide's three separately rounded fp32 operations (w: as in llie_guide)
+ *   S1c = sum out_cond, S2c = sum out_cond^2, S1g = sum g, S2g = sum g^2 over the row in double, each fp32 value widened first
+ *   var_c = max(S2c - S1c^2 / n, 0), var_g likewise (the ratio is the same for the biased and the unbiased estimator)
+ *   r32   = (float)sqrt(var_c / var_g) (double, rounded once); 1 where var_g is not > 0 or r32 is not finite: a constant row and
+ *           n = 1 are not rescaled and never give an inf
+ *   f_b   = fl(fl(phi r32) + fl(1 - phi)), three fp32 operations, no fused multiply-add;   out = fl(f_b g);   factor[b] = f_b
+ * phi = 1 matches the standard deviations fully; phi = 0 is llie_guide: guide_kernel alone is launched, factor = 1, the same bits.
+ * Otherwise three launches, no atomics, no host synchronisation, no allocation: the moments (one workgroup per row and chunk of
+ * llie_guide_rescale_chunk() elements leaves four double partials in `scratch`), the factor (one workgroup per row adds them in
+ * ascending chunk order) and the apply pass (llie_guide's items, one more rounding).  The partition of a row depends on per_sample
+ * alone, so a row's factor and output are the same bits alone or in a batch, from run to run, and whichever accesses carried them.
+ * `out` may alias `out_cond` or `out_uncond`; `factor` (device fp32 [batch]) may be NULL; `scratch` holds at least
+ * llie_guide_rescale_scratch_bytes(batch, per_sample) bytes (negative: the shape is refused) and is 8-byte aligned.  guidance.py has
+ * the float64 definition (guide_rescale_host) and the fp32 twin (guide_rescale_array).
+ * LLIE_ERR_ARG before any HIP call for a null pointer (`w_rows` and `factor` excepted), a pointer that is not 4-byte aligned
+ * (`scratch`: 8-byte), batch < 1, per_sample < 1, a non-finite `w` when it is used, a `phi` that is not finite or outside [0, 1] and
+ * more than 2^31 - 1 workgroups; LLIE_ERR_WORKSPACE for scratch_bytes below llie_guide_rescale_scratch_bytes. */
+int64_t llie_guide_rescale_chunk(void);
+int64_t llie_guide_rescale_scratch_bytes(int batch, int64_t per_sample);
+int llie_guide_rescale(const float* out_cond, const float* out_uncond, const float* w_rows, float w, float phi, float* out,
+                       float* factor, void* scratch, int64_t scratch_bytes, int batch, int64_t per_sample, llie_stream stream);
 int llie_guide(const float* out_cond, const float* out_uncond, const float* w_rows, float w, float* out, int batch,
                int64_t per_sample, llie_stream stream);
 int llie_guidance_pair(const float* latents, const float* cond, float* latents2, float* cond2, int batch, int64_t per_sample,

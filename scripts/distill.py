@@ -12,7 +12,8 @@ trained with TrainStep(use_velocity_target=True) is v_prediction).  --init_stude
 a checkpoint, usually the teacher's own when the variants agree; without it the student starts from --seed's random weights.
 --num_ddim_timesteps is the teacher's DDIM grid (50), --num_steps the step count distilled for, --target_ema_decay the decay of
 the EMA target network (0.95).  --guidance_scale_range LO HI distils the classifier-free-guided teacher (a teacher trained
-with train.py --cond_dropout): each sample's scale is uniform in [LO, HI], and LO = HI is the normal use.  --crop_height / --crop_width distil at a frame's own shape; --accumulate as in train.py.
+with train.py --cond_dropout): each sample's scale is uniform in [LO, HI], and LO = HI is the normal use; --guidance_rescale PHI adds guidance rescale to that
+teacher (0.7 is the usual value).  --crop_height / --crop_width distil at a frame's own shape; --accumulate as in train.py.
 
 Checkpoints have the trainer's names (checkpoint_epoch_{e}.pt, best_model.pt by validation PSNR, final_model.pt); their
 "model_state_dict" is the EMA student, so
@@ -88,6 +89,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="distil the classifier-free-guided teacher: each sample's teacher output is o_u + w (o_c - o_u) with w "
                         "uniform in [LO, HI] (LO = HI, one scale, is the normal use); the student then needs no second forward. "
                         "Default: off")
+    p.add_argument("--guidance_rescale", type=float, default=None,
+                   help="with --guidance_scale_range: distil the teacher with guidance rescale phi in [0, 1] (Lin et al. 2024): its "
+                        "guided output is scaled by phi std(o_c) / std(o) + (1 - phi) per sample, so the student does not inherit the "
+                        "over-exposure of a large w (0.7 is the paper's value).  Default: off")
     return p
 
 
@@ -105,6 +110,11 @@ def parse_args(argv=None):
         if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
             p.error("--guidance_scale_range LO HI: finite, LO <= HI")
         args.guidance_scale_range = (lo, hi)
+    if args.guidance_rescale is not None:
+        if not 0.0 <= args.guidance_rescale <= 1.0:
+            p.error("--guidance_rescale must be in [0, 1]")
+        if args.guidance_scale_range is None and args.guidance_rescale != 0:
+            p.error("--guidance_rescale needs --guidance_scale_range")
     if args.teacher_variant is None:
         args.teacher_variant = args.variant
     if args.teacher_attention is None:
@@ -131,8 +141,13 @@ def distiller_keywords(args) -> dict:
 
 def guidance_keywords(args) -> dict:
     """LowLightLCMDistillation's guidance keywords: nothing without --guidance_scale_range (the range stays stored and unused)."""
-    r = getattr(args, "guidance_scale_range", None)
-    return {} if r is None else {"guidance_scale_range": tuple(r), "guidance": True}
+    r, phi = getattr(args, "guidance_scale_range", None), getattr(args, "guidance_rescale", None)
+    if r is None:
+        return {}
+    kw = {"guidance_scale_range": tuple(r), "guidance": True}
+    if phi is not None:
+        kw["guidance_rescale"] = phi
+    return kw
 
 
 def build_network(variant: str, attention: str, prediction: str, image_size: int, num_steps: int) -> "M.LowLightDiffusion":

@@ -62,9 +62,15 @@ def parse_args(argv=None):
                    help="attention of the network the checkpoint holds (softmax: use_linear_attention=False)")
     p.add_argument("--guidance_scale", type=float, default=None, help="classifier-free guidance scale w: every step uses o_u + w (o_c - o_u), o_u the output on the "
                         "all-zero condition (a second forward per step; for a model trained with --cond_dropout).  Default: off")
+    p.add_argument("--guidance_rescale", type=float, default=None,
+                   help="guidance rescale phi in [0, 1] (Lin et al. 2024): with --guidance_scale, the guided output of each "
+                        "image and step is scaled by phi std(o_c) / std(o) + (1 - phi), which removes the over-exposure of a large w "
+                        "(0.7 is the paper's value).  Default: off")
     args = p.parse_args(argv)
     if args.guidance_scale is not None and not math.isfinite(args.guidance_scale):
         p.error("--guidance_scale must be finite")
+    if args.guidance_rescale is not None and not 0.0 <= args.guidance_rescale <= 1.0:
+        p.error("--guidance_rescale must be in [0, 1]")
     if args.full_resolution == "frame" and (args.tile_overlap is not None or args.tile_batch != 32 or args.tile_size is not None):
         p.error("--full_resolution frame and --tile_overlap / --tile_batch / --tile_size exclude each other")
     if args.tile_size is not None:

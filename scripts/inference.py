@@ -73,9 +73,15 @@ def parse_args(argv=None):
     p.add_argument("--guidance_scale", type=float, default=None,
                    help="(extension) classifier-free guidance scale w: every step uses o_u + w (o_c - o_u), o_u the output on the "
                         "all-zero condition (a second forward per step; for a model trained with --cond_dropout).  Default: off")
+    p.add_argument("--guidance_rescale", type=float, default=None,
+                   help="(extension) guidance rescale phi in [0, 1] (Lin et al. 2024): with --guidance_scale, the guided output of each "
+                        "image and step is scaled by phi std(o_c) / std(o) + (1 - phi), which removes the over-exposure of a large w "
+                        "(0.7 is the paper's value).  Default: off")
     args = p.parse_args(argv)
     if args.guidance_scale is not None and not math.isfinite(args.guidance_scale):
         p.error("--guidance_scale must be finite")
+    if args.guidance_rescale is not None and not 0.0 <= args.guidance_rescale <= 1.0:
+        p.error("--guidance_rescale must be in [0, 1]")
     if args.guidance_scale not in (None, 1.0) and args.tile_sync == "latents":
         p.error("--guidance_scale and --tile_sync latents exclude each other")
     if args.sampler == "dpmpp_2m" and args.tile_sync == "latents":
@@ -115,9 +121,13 @@ def load_model(args):
 
 
 def guided(args) -> dict:
-    """--guidance_scale as the `guidance_scale=` keyword of the enhance calls (nothing without the flag)."""
-    w = getattr(args, "guidance_scale", None)
-    return {} if w is None else {"guidance_scale": w}
+    """--guidance_scale and --guidance_rescale as the `guidance_scale=` / `guidance_rescale=` keywords of the enhance calls
+    (nothing without the flags)."""
+    w, phi = getattr(args, "guidance_scale", None), getattr(args, "guidance_rescale", None)
+    kw = {} if w is None else {"guidance_scale": w}
+    if phi is not None:
+        kw["guidance_rescale"] = phi
+    return kw
 
 
 def noise_entries(args) -> int:

@@ -93,6 +93,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "all-zero image (0 = off)")
     p.add_argument("--guidance_scale", type=float, default=None,
                    help="guidance scale w of validation and of the sample sheet: o_u + w (o_c - o_u) at every step (default: off)")
+    p.add_argument("--guidance_rescale", type=float, default=None,
+                   help="guidance rescale phi in [0, 1] of validation and of the sample sheet (with --guidance_scale): the guided output "
+                        "is scaled by phi std(o_c) / std(o) + (1 - phi) per image and step (default: off)")
     p.add_argument("--snr_gamma", type=float, default=None,
                    help="Min-SNR-gamma weighting of the training loss: each sample's --loss is weighted by min(SNR, gamma) / SNR "
                         "at its timestep (finite, > 0; 5 is the usual choice; default: off, every timestep counts the same)")
@@ -110,6 +113,8 @@ def parse_args(argv=None):
         p.error("--cond_dropout must be in [0, 1]")
     if args.guidance_scale is not None and not math.isfinite(args.guidance_scale):
         p.error("--guidance_scale must be finite")
+    if args.guidance_rescale is not None and not 0.0 <= args.guidance_rescale <= 1.0:
+        p.error("--guidance_rescale must be in [0, 1]")
     if args.snr_gamma is not None and not (math.isfinite(args.snr_gamma) and args.snr_gamma > 0):
         p.error("--snr_gamma must be finite and > 0")
     return args
@@ -141,8 +146,12 @@ def sampler_from_args(args) -> dict:
 
 def guidance_from_args(args) -> dict:
     """LowLightTrainer's classifier-free guidance keywords (not TrainingConfig fields, not in checkpoints): --cond_dropout trains
-    with the condition dropped, --guidance_scale samples validation and the sample sheet with guidance."""
-    return {"cond_dropout": args.cond_dropout, "val_guidance_scale": args.guidance_scale}
+    with the condition dropped, --guidance_scale samples validation and the sample sheet with guidance, --guidance_rescale adds
+    the rescale to them (nothing without the flag)."""
+    kw = {"cond_dropout": args.cond_dropout, "val_guidance_scale": args.guidance_scale}
+    if getattr(args, "guidance_rescale", None) is not None:
+        kw["val_guidance_rescale"] = args.guidance_rescale
+    return kw
 
 
 def snr_from_args(args) -> dict:
